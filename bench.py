@@ -21,7 +21,9 @@ the sample axis is sharded (N/G per GPU, "strong" scaling: total work fixed) and
 516-float rank records (online-softmax partial + position sums) crosses xGMI per step (RCCL all-gather; COVO_EXCHANGE=peer:
 direct peer writes, csrc/exchange.hip).
 
-Rank 0 prints ONE JSON line with `roofline` (the fused rollout kernel in the variant the timed step runs -- it also
+A plain run sets up (recording pass), warms up, times the K steps, writes the last timed step's outputs under
+`--dump-outputs DIR` and prints the headline line (`value`, `ms_per_step`, ...).  Everything else below is measured only with
+`--full`: rank 0's line then also holds `roofline` (the fused rollout kernel in the variant the timed step runs -- it also
 leaves the softmax records --, HBM bound, 516 B/sample algorithmic, mean launch duration measured live with events on
 the launch stream; `traffic` / `counters` from the committed PMC passes of this command, dropped when the kernel
 sources changed since), `roofline_gemm` (the noise GEMM against the fp32 MFMA peak: as a launch of its own, and what it adds to the
@@ -47,6 +49,23 @@ MFMA_F32_PEAK_TFLOPS = 157.3   # MI355X_MICROARCH.md: dense fp32 matrix peak (v_
 ROLLOUT_BYTES_PER_SAMPLE = 516  # 32 x 16 B action read + 4 B cost write
 GEMM_FLOP_PER_SAMPLE_DENSE = 2 * 128 * 128  # dense-equivalent 2 n^2
 GEMM_FLOP_PER_SAMPLE_ISSUED = 20480         # lower-triangular k-skip in 32-wide groups: (1 + 2 + 3 + 4)/16 of the dense MFMAs
+DUMP_LIMIT_BYTES = 64 << 20                 # --dump-outputs: all files together
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: the arrays the last timed step handed its caller, one DIR/<name>.npy each, float64 where the output is
+    float64 and float32 otherwise.  An array above its share of DUMP_LIMIT_BYTES is cut to a fixed sample (seed 0) of its
+    flattened elements, so two runs with the same arguments write the same elements."""
+    import torch
+    os.makedirs(dirname, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, t in arrays.items():
+        a = t.detach().cpu().numpy() if torch.is_tensor(t) else np.asarray(t)
+        a = a.astype(np.float64 if a.dtype == np.float64 else np.float32)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def record_episode(env, controller, params, T, with_counts):
@@ -112,7 +131,7 @@ def cpu_baseline(states, params, N, H, lam, budget_s=15.0):
     OpenMP over samples).  epsilon is drawn once outside the loop (the reference's threefry draw is not ported)."""
     from oracle import c_oracle as CO
     from oracle import ref_np as R
-    cores = os.cpu_count() or 1
+    cores = int(os.environ.get("OMP_NUM_THREADS") or os.cpu_count() or 1)  # a thread count the caller set is kept
     os.environ["OMP_NUM_THREADS"] = str(cores)
     ns = states[40]
     so = R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
@@ -138,7 +157,7 @@ def cpu_baseline(states, params, N, H, lam, budget_s=15.0):
     return {"value": n_done / el, "unit": "control-steps/s", "cores": cores, "kind": "port",
             "sample": f"{n_done} full-size covo-online control steps (N={N}, H={H}) of the C oracle port: fp64 hyper-dual "
                       f"Hessian ({1e3 * t_h / n_done:.1f} ms/step) + fp64 LAPACK eigh/cholesky + fp32 noise GEMM, rollout and "
-                      f"softmax update, OpenMP on all host cores; {el:.1f} s of CPU work"}
+                      f"softmax update, OpenMP on {cores} host threads; {el:.1f} s of CPU work"}
 
 
 def sigma_chain_counts(core):
@@ -313,7 +332,7 @@ def bench_envs(args, world, rank, device, backend):
     t0 = time.perf_counter()
     for _ in range(args.steps):
         keys[:, 1] += 1
-        b(None, keys)
+        u = b(None, keys)
     barrier()
     elapsed = time.perf_counter() - t0
     if world > 1:
@@ -321,6 +340,26 @@ def bench_envs(args, world, rank, device, backend):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(b.a_mean).all(), "non-finite a_mean after the timed region"
+    out = {
+        "metric": "mpc_control_steps_per_sec", "value": world * E * args.steps / elapsed,
+        "unit": "control-steps/s (env instances x steps)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"covo-online `tracking` with domain randomisation, {world * E} env instances x N={N} H={H} "
+                               f"lam={args.lam} sigma=0.5: {E} instances per GPU in one batched graph (covo_mpc_step_batched), "
+                               f"env-sharded over {world} rank(s), no collective (BASELINE.json configs[4]; teacher-forced noisy "
+                               "states after a 20-step closed-loop warm-up)",
+                   "controller": "covo-online", "envs_total": world * E, "envs_per_gpu": E, "N_per_env": N, "H": H},
+    }
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"u": u, "a_mean": b.a_mean, "a_cov": b.a_cov})
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(out))
+        b.core.close()
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # launch groups of the step (graph replays of 10 copies each, GPU time per copy)
     phases = {}
     try:
@@ -359,18 +398,7 @@ def bench_envs(args, world, rank, device, backend):
     if rank == 0:
         alg_bytes = E * N * ROLLOUT_BYTES_PER_SAMPLE
         ro_us = phases.get("rollout_us")
-        out = {
-            "metric": "mpc_control_steps_per_sec", "value": world * E * args.steps / elapsed,
-            "unit": "control-steps/s (env instances x steps)", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"covo-online `tracking` with domain randomisation, {world * E} env instances x N={N} H={H} "
-                                   f"lam={args.lam} sigma=0.5: {E} instances per GPU in one batched graph (covo_mpc_step_batched), "
-                                   f"env-sharded over {world} rank(s), no collective (BASELINE.json configs[4]; teacher-forced noisy "
-                                   "states after a 20-step closed-loop warm-up)",
-                       "controller": "covo-online", "envs_total": world * E, "envs_per_gpu": E, "N_per_env": N, "H": H},
-            "phases_us_per_batched_step": phases,
-        }
+        out["phases_us_per_batched_step"] = phases
         traffic = traffic_src = None
         try:  # the committed counter passes of THIS command (scripts/profile_bench.sh), dropped when the kernel sources changed
             with open(os.path.join(ROOT, "profiles", "r06_bench_envs_pmc_summary.json")) as f:
@@ -437,6 +465,23 @@ def rendezvous_only(args, world, rank):
         dist.destroy_process_group()
 
 
+def headline(args, world, elapsed, H, n_states, idx_timed, n_local, exchange_name):
+    """--config samples: the fields of the result line every run prints; --full adds its measurements to them."""
+    return {
+        "metric": "mpc_control_steps_per_sec", "value": args.steps / elapsed, "unit": "control-steps/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
+        "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "config": {"workload": f"{args.controller} {args.task} N={args.N} H={H} lam={args.lam} sigma=0.5 "
+                               f"(teacher-forced on the recorded inputs -- noisy state, a_mean, key -- of this controller's own "
+                               f"{n_states}-step closed-loop episode, timed steps spread evenly over the episode; samples sharded "
+                               f"{world}x{n_local}, one exchange of the 516-float rank records per step: {exchange_name})",
+                   "controller": args.controller, "task": args.task, "N_global": args.N, "N_local": n_local, "H": H,
+                   "timed_episode_steps": idx_timed if len(idx_timed) <= 64 else f"{len(idx_timed)} indices, stride "
+                                                                                f"{n_states / len(idx_timed):.2f}",
+                   "pos_stats_info": bool(args.info)},
+    }
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -451,6 +496,12 @@ def main():
     ap.add_argument("--lam", type=float, default=0.01)
     ap.add_argument("--info", action="store_true", help="also compute pos_mean/pos_std (covo.py:281); XLA drops "
                     "them as dead code in the reference's eval loop (quadrotor.py:523-538)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything beside the headline: roofline and GEMM figures, Sigma chain "
+                         "counts, closed loop, the pos_info leg, the rollout sweep, the CPU baseline (the --no-* switches below "
+                         "drop single parts of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned as DIR/<name>.npy (float32 / float64, 64 MB at most)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-closed-loop", action="store_true", help="skip the closed-loop episodes (profiler counter passes)")
     ap.add_argument("--no-info-leg", action="store_true", help="skip the second timed loop with pos_mean/pos_std on")
@@ -511,7 +562,7 @@ def main():
     n_states = params.max_steps_in_episode
     online = args.controller == "covo-online"
     # ---- untimed recording pass: the controller's OWN closed-loop episode (every rank runs the same replicated env)
-    rec = record_episode(env, controller, params, n_states, with_counts=online)
+    rec = record_episode(env, controller, params, n_states, with_counts=online and args.full)
     host_states, s_reset = rec["states"], rec["s_reset"]
     cp = rec["cp_reset"]  # offline: the Sigma table of this episode's reset state
     packed_d = torch.from_numpy(rec["packed"]).to(device)
@@ -528,13 +579,12 @@ def main():
     def step(i, cp_prev):
         """One teacher-forced controller __call__ on the recorded inputs of closed-loop step i: noisy state, a_mean, key.
         (Everything else of control_params is what the previous call returned: covo-online's a_cov is an output only, covo-offline's
-        table is per episode, MPPI's a_cov -- gamma_sigma = 0: H identical blocks, invariant under the shift -- equals the recorded.)"""
-        u, cp_out, _ = controller(None, None, params, rec["keys"][i], cp_prev.replace(a_mean=a_mean_rows[i]),
-                                  {"noisy_state": dstates[i]})
-        return cp_out
+        table is per episode, MPPI's a_cov -- gamma_sigma = 0: H identical blocks, invariant under the shift -- equals the recorded.)
+        -> (u, control_params, info) as the controller returns them."""
+        return controller(None, None, params, rec["keys"][i], cp_prev.replace(a_mean=a_mean_rows[i]), {"noisy_state": dstates[i]})
 
     for i in idx_warm:
-        cp = step(i, cp)
+        cp = step(i, cp)[1]
     torch.cuda.synchronize()
 
     if world > 1:
@@ -542,7 +592,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in idx_timed:
-        cp = step(i, cp)
+        u, cp, info = step(i, cp)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -552,6 +602,17 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     assert torch.isfinite(cp.a_mean).all(), "non-finite a_mean after the timed region"
+    if args.dump_outputs and rank == 0:  # right here: the returned tensors alias the controller's buffers, which --full reuses
+        outs = {"u": u, "a_mean": cp.a_mean, "a_cov": cp.a_cov}
+        outs.update({k: v for k, v in info.items() if torch.is_tensor(v)})
+        dump_outputs(args.dump_outputs, outs)
+    n_local, exchange_name = core.n_local, core.exchange
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, world, elapsed, H, n_states, idx_timed, n_local, exchange_name)))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     kstate = dstates[idx_timed[len(idx_timed) // 2]]  # the state the stand-alone kernel timings below run on
 
     # The rollout kernel of the timed steps runs inside the fused step and cannot be bracketed individually from the host.
@@ -589,7 +650,7 @@ def main():
             # in an episode's last ~30 steps (time + k >= 300 freezes the rewards, quadrotor.py:483) the samples' costs nearly
             # coincide, every sample carries weight and the epilogue walks whole waves: 16.5 us there against 11.6 elsewhere
             probe_idx = [idx_timed[(2 * q + 1) * len(idx_timed) // 6] for q in range(3)] if len(idx_timed) >= 3 else [idx_timed[0]]
-            cp = step(probe_idx[1], cp)
+            cp = step(probe_idx[1], cp)[1]
             # every figure is a DIFFERENCE of two graph-replay times; for covo-online both carry the ~135 us Sigma chain, so 1 % of
             # clock wander between the two replays would move the 10 us rollout by 1.4 us (r03: the driver's 20-step command read
             # frac 0.34 ... 0.43 run to run).  The selections are therefore replayed interleaved, four times each, and the
@@ -638,7 +699,7 @@ def main():
                 in_step_by_index = {str(probe_idx[1]): in_step_us}
                 for q in (0, 2):
                     if q < len(probe_idx):
-                        cp = step(probe_idx[q], cp)
+                        cp = step(probe_idx[q], cp)[1]
                         in_step_by_index[str(probe_idx[q])] = rollout_in_step()
                 in_step_us = float(np.mean(list(in_step_by_index.values())))  # the judged figure: the mean over the three indices
             if not (gemm_in_step_us and gemm_in_step_us > 0):
@@ -655,7 +716,7 @@ def main():
         try:
             cnt = []
             for i in idx_timed[:100]:
-                cp = step(i, cp)
+                cp = step(i, cp)[1]
                 cnt.append(sigma_chain_counts(core))
             chain_counts = {"mean_squarings": float(np.mean([c[0] for c in cnt])),
                             "mean_newton_schulz_iterations": float(np.mean([c[1] for c in cnt])), "steps": len(cnt),
@@ -677,7 +738,6 @@ def main():
         except Exception as e:  # noqa: BLE001
             split = {"error": str(e)}
 
-    n_local, exchange_name = core.n_local, core.exchange
     closed = closed_loop(env, controller, params, n_states, rec) if (world == 1 and rank == 0 and not args.no_closed_loop) else None
 
     # ---- the same steps with covo.py:281's pos_mean / pos_std (a22) computed: a second controller, same inputs, same keys,
@@ -737,19 +797,7 @@ def main():
         achieved = alg_bytes / (launch_us * 1e-6) / 1e9
         pmc, pmc_src = pmc_counters(args, n_local)
         kin = (pmc or {}).get("kernels", {})
-        value = args.steps / elapsed
-        out = {
-            "metric": "mpc_control_steps_per_sec", "value": value, "unit": "control-steps/s",
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * elapsed / args.steps,
-            "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"workload": f"{args.controller} {args.task} N={args.N} H={H} lam={args.lam} sigma=0.5 "
-                                   f"(teacher-forced on the recorded inputs -- noisy state, a_mean, key -- of this controller's own "
-                                   f"{n_states}-step closed-loop episode, timed steps spread evenly over the episode; samples sharded "
-                                   f"{world}x{n_local}, one exchange of the 516-float rank records per step: {exchange_name})",
-                       "controller": args.controller, "task": args.task, "N_global": args.N, "N_local": n_local, "H": H,
-                       "timed_episode_steps": idx_timed if len(idx_timed) <= 64 else f"{len(idx_timed)} indices, stride "
-                                                                                    f"{n_states / len(idx_timed):.2f}",
-                       "pos_stats_info": bool(args.info)},
+        out = {**headline(args, world, elapsed, H, n_states, idx_timed, n_local, exchange_name),
             "roofline": {"bound": "hbm", "kernel": kernel_name,
                          "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": achieved / HBM_PEAK_GBS,
                          "traffic": (pmc or {}).get("traffic_bytes_per_launch"), "counters_source": pmc_src,

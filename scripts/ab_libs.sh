@@ -3,7 +3,7 @@
 # (lib = path of a libcovo_hip*.so, e.g. one built from another commit with `make VARIANT=old`).  Prints value and us per step.
 ARGS="$1"; A="$2"; B="$3"; N="${4:-3}"
 for i in $(seq "$N"); do for L in "$A" "$B"; do
-    COVO_HIP_LIB="$L" python bench.py $ARGS 2>/dev/null | tail -1 | L="$L" python -c "
+    COVO_HIP_LIB="$L" python bench.py --full $ARGS 2>/dev/null | tail -1 | L="$L" python -c "
 import json, os, sys
 d = json.loads(sys.stdin.read())
 cl = (d.get('closed_loop') or {}).get('device_env')

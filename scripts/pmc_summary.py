@@ -180,7 +180,7 @@ if "rollout_in_step" in per_kernel and "traffic_bytes_per_launch" in per_kernel[
     out["kernel"] = "rollout_pipe3_kernel<..., REC = true> (the in-step variant)"
 out["note"] = ("N_local=65536; traffic = 2 x FETCH_SIZE (gfx950 16-B/lane correction) + WRITE_SIZE, fabric counters include "
                "Infinity-Cache hits; SQ *_CYCLES / WAIT_* / ACTIVE_INST_* are quad-cycles summed over all waves")
-out["command"] = ("rocprofv3 --pmc <one counter set per pass> -- python3 bench.py --steps 30 --warmup 5 --no-cpu-baseline "
+out["command"] = ("rocprofv3 --pmc <one counter set per pass> -- python3 bench.py --full --steps 30 --warmup 5 --no-cpu-baseline "
                   "--no-closed-loop --no-info-leg   (scripts/profile_bench.sh)")
 json.dump(out, open(os.path.join(root, "profiles", f"{RND}_bench_pmc_summary.json"), "w"), indent=1)
 print(json.dumps({k: v.get("derived") for k, v in per_kernel.items()}, indent=1))

@@ -67,7 +67,7 @@ for tag in ("square_tail", "iter_tail", "T_quad", "YZ_quad"):
     if e.get("SQ_BUSY_CU_CYCLES") and e.get("SQ_VALU_MFMA_BUSY_CYCLES") is not None:
         d["mfma_busy_share_of_simd_busy"] = (e["SQ_VALU_MFMA_BUSY_CYCLES"] / 1024) / (e["SQ_BUSY_CU_CYCLES"] * 4 / 1024)
     e["derived"] = d
-out["command"] = ("rocprofv3 --pmc <one counter set per pass> -- python3 bench.py --config envs --steps 30 --warmup 5 --no-closed-loop "
+out["command"] = ("rocprofv3 --pmc <one counter set per pass> -- python3 bench.py --full --config envs --steps 30 --warmup 5 --no-closed-loop "
                   "(scripts/profile_bench.sh)")
 json.dump(out, open(os.path.join(root, "profiles", f"{RND}_bench_envs_pmc_summary.json"), "w"), indent=1)
 print(json.dumps({"traffic_bytes_per_launch": out.get("traffic_bytes_per_launch"),

@@ -8,7 +8,7 @@ sq, it, defl = int(sys.argv[1]), int(sys.argv[2]), int(sys.argv[3])
 # (per-handle switches since round 6: every handle bench.py creates takes these defaults from the environment, csrc/step.hip)
 os.environ["COVO_NS_TAIL"] = f"{sq},{it}"
 os.environ["COVO_NS_DEFLATE"] = str(defl)
-sys.argv = ["bench.py", "--no-cpu-baseline", "--no-info-leg"] + sys.argv[4:]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--no-info-leg"] + sys.argv[4:]
 import bench
 buf = io.StringIO()
 with contextlib.redirect_stdout(buf):
