@@ -505,23 +505,6 @@ int covo_sigma(covo_handle_t h, const double *R, int32_t batch, float sample_sig
 
 // ---- per-HANDLE experiment switches (CovoOpts, covo_common.hpp); every setter bumps the handle's epoch: its captured step graphs
 // hold the old launch set / kernel arguments and are re-captured at the next step
-int covo_debug_set_ns_tail(covo_handle_t h, int n_squarings, int n_iters)
-{
-    REQUIRE(h, "covo_debug_set_ns_tail: null handle");
-    if (n_squarings > 64 || n_iters > 64 || (n_squarings < 0) != (n_iters < 0)) {
-        covo_set_error("covo_debug_set_ns_tail: (%d, %d) out of range", n_squarings, n_iters);
-        return COVO_E_BADARG;
-    }
-    if (n_squarings < 0) {  // back to the defaults, defined in ONE place (sigma_ns.hip)
-        sigma_ns_tail_defaults(h->opt);
-    } else {
-        h->opt.ns_tail_squarings = h->opt.ns_tail_squarings_batched = n_squarings;  // batch 1 and batched launches alike
-        h->opt.ns_tail_iters = h->opt.ns_tail_iters_batched = n_iters;
-    }
-    ++h->opt.epoch;
-    return 0;
-}
-
 int covo_debug_set_stream_gemm(covo_handle_t h, int on)
 {
     REQUIRE(h, "covo_debug_set_stream_gemm: null handle");
@@ -542,14 +525,6 @@ int covo_debug_set_fold_begin(covo_handle_t h, int on)
 {
     REQUIRE(h, "covo_debug_set_fold_begin: null handle");
     h->opt.fold_begin = on ? 1 : 0;
-    ++h->opt.epoch;
-    return 0;
-}
-
-int covo_debug_set_ns_ritz_inside(covo_handle_t h, int on)
-{
-    REQUIRE(h, "covo_debug_set_ns_ritz_inside: null handle");
-    h->opt.ns_ritz_inside = (on == 2) ? 2 : (on ? 1 : 0);  // (2: timing reference, the last iterate only)
     ++h->opt.epoch;
     return 0;
 }

@@ -12,17 +12,15 @@ enum { ST_POS = 0, ST_VEL = 3, ST_QUAT = 6, ST_OMEGA = 10, ST_FDIST = 13, ST_POS
 
 // Experiment switches of ONE handle (round 6: rounds 1-5 kept them in process-global variables that flipped every handle of the
 // process and were not thread-safe).  covo_create fills them from the environment (covo_default_opts: COVO_STREAM_GEMM,
-// COVO_FUSE_SMALL, COVO_FOLD_BEGIN, COVO_NS_DEFLATE, COVO_NS_RITZ_INSIDE, read once per handle); covo_debug_set_*(handle, ...) change
+// COVO_FUSE_SMALL, COVO_FOLD_BEGIN, COVO_NS_DEFLATE, COVO_NS_MERGED, read once per handle); covo_debug_set_*(handle, ...) change
 // them for that handle only and bump `epoch`, which makes the handle re-capture its step graphs (they bake the launch set in).
 struct CovoOpts {
     int stream_gemm;   // covo-online's noise GEMM streamed inside the Sigma chain's finalize launch (sigma_ns.hip: ns_finalize_stream_kernel)
     int fuse_small;    // the fused small step (step_small.hip) is taken where eligible
     int fold_begin;    // eager covo-online steps: the begin work rides in the Hessian's first launch
-    int ns_tail_iters, ns_tail_squarings, ns_tail_iters_batched, ns_tail_squarings_batched;  // phases folded into the persistent launches
     int ns_deflate;      // the Newton-Schulz iteration deflates the bottom eigenpair
     int ns_force_agent;  // take the agent-scope coherence fallback although the placement check passed
     int ns_merged;       // one matrix: squaring chain + evaluations + Newton-Schulz iterations as ONE launch (ns_chain_kernel)
-    int ns_ritz_inside;  // 1: the Rayleigh-Ritz evaluations ride in the squaring launch; 0: one scan launch; 2: the last iterate only
     int epoch;
 };
 CovoOpts covo_default_opts();  // step.hip
@@ -83,11 +81,13 @@ __device__ __forceinline__ T *rebase_global(T *kernarg_base, T *loaded)
     return (T *)((const char *)kernarg_base + off);
 }
 
-// debug/profiling switches (covo_debug_set): which launches of the Hessian (bit k = kernel k of hessian_adj.hip) and how
-// many stages of the Sigma pipeline (1 prep+squarings, 2 +Ritz, 3 +Newton-Schulz, 4 +finalize) are enqueued.
-// Defaults enqueue everything; only covo_debug_time_step changes them, and restores them.
-extern int g_dbg_hess_mask, g_dbg_sigma_stages;
-void sigma_ns_tail_defaults(CovoOpts &o);  // sigma_ns.hip: the four tail lengths at their defaults (defined in ONE place)
+// Which launches a step enqueues: all of them, except in the graphs covo_debug_time_step / covo_debug_time_batched capture of a part
+// of a step.  step: enqueue_step's launch groups (1 begin, 2 Hessian, 4 Sigma, 8 noise GEMM, 16 rollout, 32 softmax update); hess:
+// bit k = kernel k of hessian_adj.hip; sigma_stages: how far the Sigma chain goes (1 squarings, 2 + the Ritz scan, 3 + Newton-Schulz,
+// 4 + finalize: launch_sigma_ns).
+struct DebugMasks {
+    int step = 63, hess = 15, sigma_stages = 4;
+};
 
 #define COVO_CHECK_HIP(expr)                                                         \
     do {                                                                             \
@@ -226,7 +226,8 @@ int launch_hessian(const float *state, const float *pos_traj, const float *vel_t
                    const float *f_tab = nullptr,         // [batch][H][4] per-step disturbance table (disturb.hip), device
                    const void *models_dev = nullptr,     // dm::Model[batch] next to consts_dev (drag / mixed with per-instance parameters)
                    int *status_dev = nullptr,            // the handle's sticky status word: COVO_DEVSTAT_ADJOINT on a costate time-out
-                   const HessBegin *begin = nullptr);    // batch 1: KB also does the step's begin work (a_mean = where the shifted mean goes)
+                   const HessBegin *begin = nullptr,     // batch 1: KB also does the step's begin work (a_mean = where the shifted mean goes)
+                   const DebugMasks &dbg = DebugMasks());
 // true: launch_hessian leaves R's Sigma-chain statistics when asked to (the adjoint kernels do, for every disturbance model;
 // launch_hessian_pairs does not)
 inline bool hessian_leaves_stats(const covo_env_params &p)
@@ -268,7 +269,7 @@ struct StreamGemmArgs {
 int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sample_sigma, float *Sigma, float *L, void *workspace,
                     hipStream_t s, const EpsGenArgs *gen = nullptr, int *status = nullptr, bool persistent_ok = true,
                     CovDeferred *cov = nullptr, bool r_has_stats = false, const StreamGemmArgs *stream = nullptr,
-                    bool *streamed = nullptr);
+                    bool *streamed = nullptr, const DebugMasks &dbg = DebugMasks());
 struct SymStatsOut;  // sym_stats.hpp
 SymStatsOut sigma_ns_stats_out(void *workspace, int batch = 1);
 void step_state_destroy(covo_ctx *h);

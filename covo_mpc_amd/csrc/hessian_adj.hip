@@ -99,7 +99,7 @@ size_t hessian_workspace_bytes(int batch) { return (size_t)batch * WS_COUNT_MAX 
 int launch_hessian(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
                    const float *a_mean, int batch, double *R, void *workspace, hipStream_t s, const void *consts_dev,
                    size_t traj_stride, const SymStatsOut *stats, const float *f_tab, const void *models_dev, int *status_dev,
-                   const HessBegin *begin)
+                   const HessBegin *begin, const DebugMasks &dbg)
 {
     const bool fs = p.disturb_kind == COVO_DISTURB_DRAG || p.disturb_kind == COVO_DISTURB_MIXED;
     if (fs && (consts_dev != nullptr) != (models_dev != nullptr)) {
@@ -132,7 +132,7 @@ int launch_hessian(const float *state, const float *pos_traj, const float *vel_t
     std::memset(&A.blk, 0, sizeof(A.blk));
     A.derive_keys = 0;
     A.shared_noise_scale = 0.0f;
-    if (begin != nullptr && batch == 1 && (g_dbg_hess_mask & 1)) {
+    if (begin != nullptr && batch == 1 && (dbg.hess & 1)) {
         A.a_mean_raw = begin->a_mean_raw;
         A.dyn_out = begin->dyn_out;
         A.seq = begin->seq;
@@ -160,13 +160,13 @@ int launch_hessian(const float *state, const float *pos_traj, const float *vel_t
     // one instance keeps them in one launch (the hyper-dual workgroups start under the chains: 27.9 -> 25.7 us in round 3)
     const bool split_hd = batch >= 8;
 #define ADJ_LAUNCH(NS, JAC)                                                                                                      \
-    do {                                                                                                                          \
-        if (g_dbg_hess_mask & 1) hipLaunchKernelGGL(JAC, dim3(NS::HH, batch), dim3(64), 0, s, A);                                 \
-        if ((g_dbg_hess_mask & 2) && split_hd) {                                                                                  \
-            hipLaunchKernelGGL(NS::adj_chain_kernel, dim3(9, batch), dim3(256), 0, s, A);                                         \
-            hipLaunchKernelGGL(NS::adj_hd_kernel, dim3(NS::HH, batch), dim3(256), 0, s, A);                                       \
-        } else if (g_dbg_hess_mask & 2) hipLaunchKernelGGL(NS::adj_chain_kernel, dim3(9 + NS::HH, batch), dim3(256), 0, s, A);    \
-        if (g_dbg_hess_mask & 8) hipLaunchKernelGGL(NS::adj_gemm_kernel, dim3(36, batch), dim3(512), 0, s, A);                    \
+    do {                                                                                                                         \
+        if (dbg.hess & 1) hipLaunchKernelGGL(JAC, dim3(NS::HH, batch), dim3(64), 0, s, A);                                       \
+        if ((dbg.hess & 2) && split_hd) {                                                                                        \
+            hipLaunchKernelGGL(NS::adj_chain_kernel, dim3(9, batch), dim3(256), 0, s, A);                                        \
+            hipLaunchKernelGGL(NS::adj_hd_kernel, dim3(NS::HH, batch), dim3(256), 0, s, A);                                      \
+        } else if (dbg.hess & 2) hipLaunchKernelGGL(NS::adj_chain_kernel, dim3(9 + NS::HH, batch), dim3(256), 0, s, A);          \
+        if (dbg.hess & 8) hipLaunchKernelGGL(NS::adj_gemm_kernel, dim3(36, batch), dim3(512), 0, s, A);                          \
     } while (0)
     if (fs) ADJ_LAUNCH(adj16, adj16::adj_jac_kernel<true>);
     else if (A.f_tab != nullptr) ADJ_LAUNCH(adj13, adj13::adj_jac_kernel<true>);

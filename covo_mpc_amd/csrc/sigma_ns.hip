@@ -62,18 +62,6 @@
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
-// -DNS_STAMPS: workgroup 0 of the iteration tail records wall_clock64() (10 ns) at the seams of every phase (scripts/ns_tail_cost.py)
-#ifdef NS_STAMPS
-__shared__ long long g_stamp[192];
-__shared__ int g_nstamp;
-#define NS_STAMP()                                                                    \
-    do {                                                                              \
-        if (threadIdx.x == 0 && g_nstamp < 192) g_stamp[g_nstamp++] = wall_clock64(); \
-    } while (0)
-#else
-#define NS_STAMP() do { } while (0)
-#endif
-
 // -DNS_EVAL_STAMPS: wall_clock64() (10 ns ticks) of the squaring launch's seams into SC_STAMPS + 96 ..: [0] chain workgroup 0 enters,
 // [1] leaves; per k = 2 .. 16 at [2 + 3 (k - 2)]: X_k seen complete, evaluated, decided; [70 ..]: the seams inside the evaluation of X_8 (scripts/ritz_timeline.py)
 #ifdef NS_EVAL_STAMPS
@@ -133,7 +121,7 @@ enum { SC_SHIFT = 0, SC_LMIN, SC_DELTA, SC_SCALE, SC_SUMLOGB, SC_ZBUF, SC_ITERS,
        SC_FPART = SC_RPART + 128 * 8,              // per-tile sums of squares (36)
        SC_U = SC_FPART + 64,                       // the bottom Ritz vector u (128)
        SC_FLAGS = SC_U + 128,                      // barrier flag words of the two persistent launches: 2 x 64 unsigned (ns_flag_barrier)
-       SC_STAMPS = SC_FLAGS + 64,                  // -DNS_STAMPS: 192 time stamps of the iteration tail's workgroup 0
+       SC_STAMPS = SC_FLAGS + 64,                  // 192 time stamps of -DNS_EVAL_STAMPS / -DNS_STREAM_STAMPS builds
        SC_COUNT = SC_STAMPS + 192 };
 constexpr double NS_DEFL_SAFETY = 0.7;   // the NS table assumes 1e-2 + 0.7 x (gap bound): the bound's linearisation is good to ~3 %
 constexpr double NS_DEFL_MIN_GAP = 2e-2; // below this the interval shrinks by < 3x: not worth a rank-1 correction
@@ -429,19 +417,19 @@ __global__ __launch_bounds__(256) void ns_square_kernel(const double *__restrict
 // goes stationary (k = 8.6 against 11.1; |lambda error| <= 5e-14 at that k).  So the chain's lambda_min is DEFINED as
 //     the Ritz value of X_kwin,  kwin = the first k in [2, 16] whose pair passes (ritz_eval: pass), else the filter's last iterate,
 // a pure function of A: every path evaluates the same X_k with the same code (ritz_eval) and takes the same kwin (ritz_decide) --
-//   * one matrix, persistent launch: evaluating workgroups ride in the squaring launch (ns_square_tail_pair_kernel<true>), read X_k
-//     the moment its barrier has passed, and stop the chain; the chain meanwhile runs ahead (every X_k keeps a buffer of its own),
-//     so an evaluation costs the chain nothing and the separate Ritz launch is gone;
-//   * batches / shared-device handles / the debug splits: the squarings run to their own stop as before and ONE launch evaluates
-//     every k of every matrix (ns_ritz_scan_kernel).
+//   * persistent launches (one matrix and batches): evaluating workgroups ride in the squaring launch (ns_square_evaluator), read X_k
+//     the moment its barrier has passed, and stop the chain; the chain meanwhile runs ahead, so an evaluation costs the chain nothing
+//     and the separate Ritz launch is gone;
+//   * shared-device handles (every phase its own launch): the squarings run to their own stop and ONE launch evaluates every k of
+//     every matrix (ns_ritz_scan_kernel).
 constexpr double RITZ_PASS_E = 0.05;  // e_k = (1 - |X_k|_F^2) / 2 below this: the gap bound's linearisation holds (ritz_eval)
 constexpr int RITZ_K0 = 2;                          // first evaluated iterate (the stationarity test needs two norms: the filter never stops before X_2)
 constexpr int RITZ_NK = NS_SQUARINGS - RITZ_K0 + 1;  // evaluations per matrix: X_2 .. X_16
 struct XBufs {  // X_1 -> xq (it outlives the filter: iteration 1 of the Newton-Schulz part rebuilds A^2 from it, NsFirst); X_2 -> x1, and then
     double *x0, *x1, *hist, *xq;  // X_3 .. X_16 -> the history;  hist == nullptr: no history, odd k -> x0, even k -> x1 (the launch with the
     size_t M;                     // evaluations inside: they take what they need of X_k before the chain comes round to its buffer
-                                  // again -- ns_square_evaluator).  x0, x1 are T and T^T of the iterations later.
-                                  // M: doubles between the buffers of consecutive k (batch x 128 x 128)
+                                  // again -- ns_square_evaluator).  The history's first two matrices are T and T^T of the iterations
+                                  // (launch_sigma_ns).  M: doubles between the buffers of consecutive k (batch x 128 x 128)
 };
 __host__ __device__ __forceinline__ double *ns_xk(const XBufs xb, int k)
 {
@@ -937,8 +925,9 @@ __device__ __forceinline__ bool ritz_decide(RitzLds &L, double u, double *s, int
         }
         const int d = (prev == 2) ? 2 : ((L.o_pass || final) ? 1 : 0);  // 2: decided before; 1: this one is taken; 0: not taken
         L.decide = d;
-        // the flags first (nothing in this launch reads the results themselves; the launches that do come after its end): the
-        // chain stops (it may be two squarings further by now), the evaluation of X_(k+1) has its answer
+        // the flags first: the chain stops (it may be two squarings further by now), the evaluation of X_(k+1) has its answer.
+        // The results follow (ritz_publish); what reads them inside this launch -- the Newton-Schulz side of the merged launch --
+        // waits for SC_READY, which is raised behind them
         if (d == 1) gst<COH_AGENT>(s + SC_SQ_DONE, 1.0);
         gst<COH_AGENT>(s + SC_VERD + k - RITZ_K0, d == 0 ? 1.0 : 2.0);
     }
@@ -948,11 +937,11 @@ __device__ __forceinline__ bool ritz_decide(RitzLds &L, double u, double *s, int
     return d != 0;
 }
 
-// every k of every matrix in ONE launch (the paths whose squarings are launches of their own / run batched): workgroup
+// every k of every matrix in ONE launch (the phased plan: the squarings are launches of their own): workgroup
 // (k - RITZ_K0) + RITZ_NK * b -- X_(k-1)'s workgroup has the id before it, so the verdict it waits for is always being worked on
 // (dispatch is in id order; the wait is bounded anyway)
 __global__ __launch_bounds__(256) void ns_ritz_scan_kernel(const double *__restrict__ Aall, const XBufs xb, double *__restrict__ scall,
-                                                           const int deflate, const int final_only)
+                                                           const int deflate)
 {
     __shared__ RitzLds L;
     const int b = blockIdx.x / RITZ_NK, k = RITZ_K0 + (int)(blockIdx.x % RITZ_NK), tid = threadIdx.x;
@@ -960,10 +949,6 @@ __global__ __launch_bounds__(256) void ns_ritz_scan_kernel(const double *__restr
     const int k_final = (int)s[SC_SQ];  // (a launch boundary ago)
     if (k > k_final) return;
     const bool final = k == k_final;
-    if (final_only) {  // timing reference (COVO_NS_RITZ_INSIDE=2): rounds 1-4's rule -- the filter's last iterate, nothing else
-        if (tid == 0 && k == k_final - 1) gst<COH_AGENT>(s + SC_VERD + k - RITZ_K0, 1.0);
-        if (!final) return;
-    }
     // a cheap "not taken": the bounded part of the spectrum is still there, or the norm is not yet in the range in which an
     // evaluation can pass (ritz_eval: o_pass) -- an iterate that cannot pass and is not the last
     const double e_k = 0.5 * (1.0 - slot_sum(s + SC_SQN + k * 64, NS_TILES, tid & 63));
@@ -1345,7 +1330,6 @@ __device__ __forceinline__ int ns_flag_barrier(unsigned *flags, unsigned phase, 
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this thread's stores have been acknowledged (by the L2 / by memory)
     __syncthreads();
-    NS_STAMP();  // stores acknowledged
     if (threadIdx.x < 64) {
         const int lane = threadIdx.x;
         const unsigned word = (xcc << 24) | ((stop_v != 0.0) ? NS_FLAG_STOP : 0u) | phase;
@@ -1372,7 +1356,6 @@ __device__ __forceinline__ int ns_flag_barrier(unsigned *flags, unsigned phase, 
         if (lane == 0) res = good ? ((one_xcd ? 2 : 1) | (stopped ? 4 : 0)) : 0;
     }
     __syncthreads();
-    NS_STAMP();  // barrier passed
     return res;
 }
 
@@ -1381,7 +1364,7 @@ __device__ __forceinline__ int ns_flag_barrier(unsigned *flags, unsigned phase, 
 // matrix runs its WHOLE tail at its own pace next to the others (4 per XCD at 32 matrices) instead of paying, launch by launch,
 // for the slowest matrix of the batch; when the grid exceeds what is resident, workgroups are dispatched in id order, so the
 // matrices ahead of a partially resident one are complete or running and always finish: no deadlock.
-__device__ __forceinline__ bool ns_tail_block(int nw, int batch, int &b, int &w, unsigned xcd0 = 0u)
+__device__ __forceinline__ bool ns_persist_block(int nw, int batch, int &b, int &w, unsigned xcd0 = 0u)
 {
     // xcd0 (batch 1 only): the workgroups that stay are the linear ids = xcd0 (mod 8) -- the Newton-Schulz workgroups of the merged
     // launch sit on XCD 1, its squaring chain on XCD 0
@@ -1390,7 +1373,7 @@ __device__ __forceinline__ bool ns_tail_block(int nw, int batch, int &b, int &w,
     w = (int)(slot % (unsigned)nw);
     return b < batch;
 }
-static inline dim3 ns_tail_grid(int nw, int batch) { return dim3(8 * nw * ((batch + 7) / 8)); }
+static inline dim3 ns_persist_grid(int nw, int batch) { return dim3(8 * nw * ((batch + 7) / 8)); }
 
 struct NsBufs {
     double *Y[2], *Yt[2], *Z[2], *Zt[2], *T, *Tt;
@@ -1439,9 +1422,9 @@ __device__ __forceinline__ void pair_mma_reduce(const PairOps &o, double (*redp)
 // (it runs the pair's code with tile 0 -- an upper tile -- left out).  0.77 MB of operands per squaring instead of 1.15, 20
 // workgroups at the barrier instead of 36.  Per tile the arithmetic of ns_square_body.
 constexpr int NS_SQ_PAIR_WG = 20;
-// EVAL (evaluations ride in the launch): SC_SQ_DONE is raised from OUTSIDE the chain, at any time -- the chain's workgroups do
-// not look at it themselves (they would disagree within a phase); workgroup 0 passes it on through the barrier (ns_flag_barrier)
-template <bool FIRST, int COH, bool EVAL = false>
+// The evaluations ride in the launch: SC_SQ_DONE is raised from OUTSIDE the chain, at any time -- the chain's workgroups do not look
+// at it themselves (they would disagree within a phase); workgroup 0 passes it on through the barrier (ns_flag_barrier)
+template <bool FIRST, int COH>
 __device__ __forceinline__ bool ns_square_pair_body(const double *X, double *O, double *s, int step, int w,
                                                     double (*redp)[4][4][64], double (*partp)[4])
 {
@@ -1469,11 +1452,9 @@ __device__ __forceinline__ bool ns_square_pair_body(const double *X, double *O, 
         }
     }
     if (!FIRST) {
-        const double done = gld<COH>(s + SC_SQ_DONE);
         const double p1 = (lane < NS_TILES) ? gld<COH>(s + SC_SQN + step * 64 + lane) : 0.0;
         const double p0 = (lane < NS_TILES && step >= 2) ? gld<COH>(s + SC_SQN + (step - 1) * 64 + lane) : 0.0;
         t_in = gld<COH>(s + SC_SQN + step * 64 + 63);
-        if (!EVAL && done != 0.0) return false;
         nrm = wr::wave64_allsum(p1);
         if (step >= 2 && t_in > NS_SQ_TGUARD) {
             const double prev = wr::wave64_allsum(p0);
@@ -1514,29 +1495,26 @@ __device__ __forceinline__ bool ns_square_pair_body(const double *X, double *O, 
 constexpr int NS_SQ_EVAL_WG = 8;        // evaluating workgroups of the one-matrix launch: an evaluation takes three squarings
 constexpr int NS_SQ_EVAL_WG_BATCH = 3;  // ... per matrix of a batched launch (its squarings take twice as long; LEAN evaluations)
 template <int COH, int NEVAL>
-__device__ __forceinline__ void ns_square_tail_pair_rest(const XBufs xb, double *scall, int step_first, int step_last, int w,
-                                                         unsigned xcc, double (*redp)[4][4][64], double (*partp)[4])
+__device__ __forceinline__ void ns_square_tail_pair_rest(const XBufs xb, double *scall, int w, unsigned xcc, double (*redp)[4][4][64],
+                                                         double (*partp)[4])
 {
-    constexpr bool EVAL = NEVAL > 0;
     constexpr int NW = NS_SQ_PAIR_WG + NEVAL;
     unsigned *flags = reinterpret_cast<unsigned *>(scall + SC_FLAGS);
     unsigned phase = 1;
-    for (int step = step_first + 1; step <= step_last; ++step) {  // squaring `step` reads X_step, writes X_(step + 1)
-        if (!ns_square_pair_body<false, COH, EVAL>(ns_xk(xb, step), ns_xk(xb, step + 1), scall, step, w, redp, partp)) return;
-        // (with evaluations riding along the last iterate, too, is announced by a barrier: the flag words are what they poll)
-        if (EVAL || step < step_last) {
-            // (the squaring after this barrier, number `phase`, writes X_(phase + 1) over X_(phase - 1): X_(phase - 1)'s evaluation must
-            // have its columns and X_phase's evaluation the diagonal -- workgroup 0 holds the barrier for them)
-            ++phase;
-            const bool gd = EVAL && w == 0;
-            const int r = ns_flag_barrier<COH>(flags, phase, w, NW, xcc, scall + SC_BARFAIL, gd ? scall + SC_SQ_DONE : nullptr,
-                                               (gd && phase >= 2 && phase <= NS_SQUARINGS) ? scall + SC_HAVE_DIAG + phase - RITZ_K0 : nullptr,
-                                               (gd && phase >= 3 && phase <= NS_SQUARINGS + 1) ? scall + SC_HAVE_COLS + phase - 1 - RITZ_K0 : nullptr);
-            if (r == 0 || (r & 4)) return;
-        }
-        if (EVAL && w == 0) EV_STAMP(scall, 48 + step + 1);  // X_(step + 1) complete
+    for (int step = 1; step < NS_SQUARINGS; ++step) {  // squaring `step` reads X_step, writes X_(step + 1)
+        if (!ns_square_pair_body<false, COH>(ns_xk(xb, step), ns_xk(xb, step + 1), scall, step, w, redp, partp)) return;
+        // (the last iterate, too, is announced by a barrier: the flag words are what the evaluations poll)
+        // (the squaring after this barrier, number `phase`, writes X_(phase + 1) over X_(phase - 1): X_(phase - 1)'s evaluation must
+        // have its columns and X_phase's evaluation the diagonal -- workgroup 0 holds the barrier for them)
+        ++phase;
+        const bool gd = w == 0;
+        const int r = ns_flag_barrier<COH>(flags, phase, w, NW, xcc, scall + SC_BARFAIL, gd ? scall + SC_SQ_DONE : nullptr,
+                                           (gd && phase >= 2 && phase <= NS_SQUARINGS) ? scall + SC_HAVE_DIAG + phase - RITZ_K0 : nullptr,
+                                           (gd && phase >= 3 && phase <= NS_SQUARINGS + 1) ? scall + SC_HAVE_COLS + phase - 1 - RITZ_K0 : nullptr);
+        if (r == 0 || (r & 4)) return;
+        if (w == 0) EV_STAMP(scall, 48 + step + 1);  // X_(step + 1) complete
     }
-    if (EVAL && w == 0 && threadIdx.x == 0) gst<COH_AGENT>(scall + SC_SQ_FINAL, (double)(step_last + 1));  // the cap: X_16 is the last
+    if (w == 0 && threadIdx.x == 0) gst<COH_AGENT>(scall + SC_SQ_FINAL, (double)NS_SQUARINGS);  // the cap: X_16 is the last
 }
 // ---- an evaluating workgroup of the one-matrix squaring launch (e = 0 .. NS_SQ_EVAL_WG - 1): X_k for k = RITZ_K0 + e, + NS_SQ_EVAL_WG, ...
 // Polls the chain's barrier flag words (X_k is complete once all of them have reached k): picks its columns on X_(k-1) while X_k is
@@ -1639,13 +1617,18 @@ __device__ __forceinline__ void ns_square_evaluator(const double *__restrict__ A
         if (decided) return;
     }
 }
-// NEVAL: evaluating workgroups per matrix (0: none -- the evaluations are a launch of their own, ns_ritz_scan_kernel)
+// Every squaring but the first runs behind a barrier of this launch, the Rayleigh-Ritz evaluations ride along (NEVAL evaluating
+// workgroups per matrix).  Which phases to fold into the persistent launches was measured in rounds 2-5: a live folded squaring is
+// 0.85 us cheaper than its launch, a live iteration 0.7 us (one XCD, plain stores, flag words; covo_sigma 167.5 us with nothing
+// folded, 151.7 with both tails).  bench / closed-loop steps/s by (folded squarings, folded iterations): one matrix (9, 6) 5 236 /
+// 4 644, (12, 8) 5 280 / 4 738, (15, 8) 5 364-5 384 / 4 811-4 829, (15, 11) 5 370-5 375 / 4 813-4 815 -> every squaring and every
+// iteration but the first (NS_SQUARINGS - 1, NS_ITERS - 1).  Batched: NS_BATCH_TAIL_ITERS.
 // DYN (the merged launch): the reduction buffer and the evaluations' RitzLds live in the launch's dynamic LDS (`dyn`) -- the merged
 // kernel's static LDS + the 129 KiB its log-det workgroup needs must stay under 160 KiB
 constexpr size_t NS_SQ_DYN_DOUBLES = 2 * 4 * 4 * 64 + 8 + (sizeof(RitzLds) + 7) / 8;
 template <int NEVAL, bool LEAN, bool DYN = false>
-__device__ __forceinline__ void ns_square_tail_pair_impl(const double *A, const XBufs xb_all, double *scall, int step_first, int step_last,
-                                                         int batch, int force_agent, int deflate, double *dyn = nullptr)
+__device__ __forceinline__ void ns_square_tail_pair_impl(const double *A, const XBufs xb_all, double *scall, int batch, int force_agent,
+                                                         int deflate, double *dyn = nullptr)
 {
     double (*redp)[4][4][64];
     double (*partp)[4];
@@ -1658,16 +1641,14 @@ __device__ __forceinline__ void ns_square_tail_pair_impl(const double *A, const 
         redp = redp_s;
         partp = partp_s;
     }
-    constexpr bool EVAL = NEVAL > 0;
     constexpr int NW = NS_SQ_PAIR_WG + NEVAL;
     int b, w;
-    if (!ns_tail_block(NW, batch, b, w)) return;
-    // (EVAL: two buffers -- ns_square_evaluator)
-    const XBufs xb{xb_all.x0 + (size_t)b * SN * SN, xb_all.x1 + (size_t)b * SN * SN,
-                   EVAL ? nullptr : xb_all.hist + (size_t)b * SN * SN, xb_all.xq + (size_t)b * SN * SN, xb_all.M};
+    if (!ns_persist_block(NW, batch, b, w)) return;
+    // (two buffers and no history -- ns_square_evaluator)
+    const XBufs xb{xb_all.x0 + (size_t)b * SN * SN, xb_all.x1 + (size_t)b * SN * SN, nullptr, xb_all.xq + (size_t)b * SN * SN, xb_all.M};
     scall += (size_t)b * SC_COUNT;
     const unsigned xcc = ns_xcc_id();
-    if (EVAL && w >= NS_SQ_PAIR_WG) {
+    if (w >= NS_SQ_PAIR_WG) {
         if constexpr (DYN) {
             RitzLds &L = *reinterpret_cast<RitzLds *>(dyn + 2 * 4 * 4 * 64 + 8);
             ns_square_evaluator<NEVAL, LEAN>(A + (size_t)b * SN * SN, xb, scall, w - NS_SQ_PAIR_WG, xcc, deflate, L);
@@ -1677,31 +1658,27 @@ __device__ __forceinline__ void ns_square_tail_pair_impl(const double *A, const 
         }
         return;
     }
-    if (EVAL && w == 0) EV_STAMP(scall, 0);
-    if (step_first == 0) {
-        (void)ns_square_pair_body<true, COH_AGENT>(A + (size_t)b * SN * SN, ns_xk(xb, 1), scall, 0, w, redp, partp);
-    } else if (!ns_square_pair_body<false, COH_AGENT>(ns_xk(xb, step_first), ns_xk(xb, step_first + 1), scall, step_first, w, redp, partp))
-        return;
-    if (step_first == step_last) return;
+    if (w == 0) EV_STAMP(scall, 0);
+    (void)ns_square_pair_body<true, COH_AGENT>(A + (size_t)b * SN * SN, ns_xk(xb, 1), scall, 0, w, redp, partp);
     int r = ns_flag_barrier<COH_AGENT>(reinterpret_cast<unsigned *>(scall + SC_FLAGS), 1u, w, NW, xcc, scall + SC_BARFAIL);
     if (r == 2 && force_agent) r = 1;
     if (w == 0 && threadIdx.x == 0) scall[SC_PROF + 5] = (double)r;  // diagnostics: which mode the squaring launch ran in
-    if (r == 2) ns_square_tail_pair_rest<COH_XCD, NEVAL>(xb, scall, step_first, step_last, w, xcc, redp, partp);
-    else if (r == 1) ns_square_tail_pair_rest<COH_AGENT, NEVAL>(xb, scall, step_first, step_last, w, xcc, redp, partp);
-    if (EVAL && w == 0) EV_STAMP(scall, 1);
+    if (r == 2) ns_square_tail_pair_rest<COH_XCD, NEVAL>(xb, scall, w, xcc, redp, partp);
+    else if (r == 1) ns_square_tail_pair_rest<COH_AGENT, NEVAL>(xb, scall, w, xcc, redp, partp);
+    if (w == 0) EV_STAMP(scall, 1);
 }
 template <int NEVAL>
-__global__ __launch_bounds__(256) void ns_square_tail_pair_kernel(const double *A, const XBufs xb_all, double *scall, int step_first,
-                                                                  int step_last, int batch, int force_agent, int deflate)
+__global__ __launch_bounds__(256) void ns_square_tail_pair_kernel(const double *A, const XBufs xb_all, double *scall, int batch,
+                                                                  int force_agent, int deflate)
 {
-    ns_square_tail_pair_impl<NEVAL, false>(A, xb_all, scall, step_first, step_last, batch, force_agent, deflate);
+    ns_square_tail_pair_impl<NEVAL, false>(A, xb_all, scall, batch, force_agent, deflate);
 }
 // batched, evaluations inside: four matrices per XCD = 92 workgroups on its 32 CUs -- three per CU, i.e. three waves per SIMD
 // (<= 168 VGPRs: the LEAN evaluation keeps A in memory)
-__global__ __launch_bounds__(256, 3) void ns_square_tail_pair_lean_kernel(const double *A, const XBufs xb_all, double *scall, int step_first,
-                                                                          int step_last, int batch, int force_agent, int deflate)
+__global__ __launch_bounds__(256, 3) void ns_square_tail_pair_lean_kernel(const double *A, const XBufs xb_all, double *scall, int batch,
+                                                                          int force_agent, int deflate)
 {
-    ns_square_tail_pair_impl<NS_SQ_EVAL_WG_BATCH, true>(A, xb_all, scall, step_first, step_last, batch, force_agent, deflate);
+    ns_square_tail_pair_impl<NS_SQ_EVAL_WG_BATCH, true>(A, xb_all, scall, batch, force_agent, deflate);
 }
 
 constexpr int NS_PAIR_WG = 32;
@@ -1715,10 +1692,8 @@ __device__ __forceinline__ bool ns_T_pair_body(const double *Y, const double *Zt
     pair_load<COH>(ops, Zt, Y, p, tj, lane, wv, LoadPlain{});  // (Z^T)^T . Y = Z.Y
     const double a = gld<COH>(s + SC_COEF + 2 * iter), bq = gld<COH>(s + SC_COEF + 2 * iter + 1);
     if (ns_converged<COH>(s, iter, lane, w == 0 && tid == 0)) return false;
-    NS_STAMP();  // operands + slots have arrived
     double pv[2];
     pair_mma_reduce(ops, redp, wv, lane, pv);
-    NS_STAMP();  // products reduced
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
         const int ti = 2 * p + h;
@@ -1734,9 +1709,9 @@ __device__ __forceinline__ bool ns_T_pair_body(const double *Y, const double *Zt
 }
 // Part 2 on 2 x 2 tile BLOCKS (round 5): workgroups 0..15 form the blocks of Y' = Y.T, 16..31 those of Z' = T.Z -- one product of four
 // tiles per workgroup instead of two products of two tiles one after the other.  What this phase waits for is the XCD's ONE L2
-// (16 channels x 64 B/clk): pairs pull 4 MB of operands through it (~2 us: the stamps of -DNS_STAMPS show the second product's
+// (16 channels x 64 B/clk): pairs pull 4 MB of operands through it (~2 us: round 5's phase stamps showed the second product's
 // operands arriving 2.0 us after the first's), blocks 2 MB; the MFMA count per wave is the same (32).  Per tile the arithmetic of
-// ns_YZ_body (quad_mma_reduce), as in the batched launches.  redq: 4 x 4 x 4 x 64 doubles of LDS.  Measured (-DNS_STAMPS, one matrix): the
+// ns_YZ_body (quad_mma_reduce), as in the batched launches.  redq: 4 x 4 x 4 x 64 doubles of LDS.  Measured (phase stamps, one matrix): the
 // phase 3.9 us against 4.2 (operands 1.4 us against 1.2 + the second product's 1.2 under its own product; product 1.3 against 2.0;
 // four tiles' stores 0.8 against 0.5); same box, whole step 173.3 against 175.2 us.  (Round 4 had tried all 48 operand loads of the
 // two pair products in flight together: no difference -- the bytes, not the second latency.)
@@ -1755,10 +1730,8 @@ __device__ __forceinline__ bool ns_YZ_quad_body(const double *Yt, const double *
         gst<COH>(s + SC_ZBUF, (double)zbuf_out);
         gst<COH>(s + SC_ITERS, (double)(iter + 1));
     }
-    NS_STAMP();  // operands + slots have arrived
     double v[4];
     quad_mma_reduce(ops, redq, wv, lane, v);
-    NS_STAMP();  // products reduced
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int ti = 2 * mi + (t >> 1), tj = 2 * mj + (t & 1);
@@ -1768,9 +1741,10 @@ __device__ __forceinline__ bool ns_YZ_quad_body(const double *Yt, const double *
     return true;
 }
 template <int COH>
-__device__ __forceinline__ void ns_iter_tail_pair_rest(const NsBufs &B, size_t off, double *scall, int iter_first, int iter_last, int w,
-                                                       unsigned xcc, double (*redp)[4][4][64], double (*partp)[4], bool t_first)
+__device__ __forceinline__ void ns_iter_tail_pair_rest(const NsBufs &B, size_t off, double *scall, int iter_first, int w, unsigned xcc,
+                                                       double (*redp)[4][4][64], double (*partp)[4], bool t_first)
 {
+    constexpr int iter_last = NS_ITERS - 1;
     // t_first: part 1 of iteration iter_first is still to do (the launch began by writing Y1, Z1 out); else the launch's first phase was it
     unsigned *flags = reinterpret_cast<unsigned *>(scall + SC_FLAGS) + 64;
     unsigned phase = 1;
@@ -1790,11 +1764,17 @@ __device__ __forceinline__ void ns_iter_tail_pair_rest(const NsBufs &B, size_t o
 }
 template <int NWAVES>
 __device__ void ns_logdetB_workgroup(const double *__restrict__ A, double *__restrict__ s, double *__restrict__ sm, double *__restrict__ red);
-// with_table (one matrix, every iteration folded: iter_first = 1): the coefficient table of the iterations to come -- a serial
-// recurrence, ~1.5 us on one lane -- is the work of one of the workgroups the launch would send away anyway (linear id 1: another
-// XCD, so it publishes coherently and raises SC_BAR); iteration 1 itself does not need it (NsFirst carries its coefficients)
-// early_logdet (one matrix): linear id 2 factors B = A + delta I for its log det (ns_logdetB_workgroup; the launch then carries
-// 129 KiB of dynamic LDS: one workgroup per CU, which is how the XCD's 32 CUs host the 32 workgroups of the iterations anyway)
+// Batched launches fold only their last NS_BATCH_TAIL_ITERS iterations: early on every matrix is live, and four matrices' workgroups
+// on an XCD's 32 CUs keep its ONE L2 busy 65-80 % of the launch (profiles/r04_sigma_batch_l2_counters.log) where a launch spreads
+// each phase over the chip.  bench.py --config envs, bench / closed-loop control-steps/s by folded iterations (every squaring
+// folded): 3 81 815 / 75 187; 4 82 553 / 75 641; 5 82 865 / 74 674; 6 82 978 / 74 796; 8 81 889 / 74 194; 11 80 713 / 73 431.
+constexpr int NS_BATCH_TAIL_ITERS = 4;
+// EARLY_LOGDET (one matrix, every iteration folded: iterations 1 .. NS_ITERS - 1):
+//  * the coefficient table of the iterations to come -- a serial recurrence, ~1.5 us on one lane -- is the work of one of the
+//    workgroups the launch would send away anyway (linear id 1: another XCD, so it publishes coherently and raises SC_BAR);
+//    iteration 1 itself does not need it (NsFirst carries its coefficients);
+//  * linear id 2 factors B = A + delta I for its log det (ns_logdetB_workgroup; the launch then carries 129 KiB of dynamic LDS: one
+//    workgroup per CU, which is how the XCD's 32 CUs host the 32 workgroups of the iterations anyway).
 // (a template argument: the factorisation's registers -- 184 against 122 -- must not cost the batched launches their third wave per SIMD)
 // MERGED launch (round 6, one matrix): the squaring chain with its evaluations (XCD 0) and the Newton-Schulz workgroups (XCD 1; log det
 // on XCD 2, the coefficient table on XCD 3) are ONE launch -- ns_chain_kernel below.  The Newton-Schulz side is resident, placed and
@@ -1822,9 +1802,10 @@ __device__ __forceinline__ bool ns_wait_result(double *s)
     return ready_ok != 0;
 }
 template <bool EARLY_LOGDET>
-__device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const NsBufs B, double *scall, int iter_first, int iter_last,
-                                                       int batch, int force_agent, int with_table, int merged, double *ld_sm)
+__device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const NsBufs B, double *scall, int batch, int force_agent, int merged,
+                                                       double *ld_sm)
 {
+    constexpr int iter_first = EARLY_LOGDET ? 1 : NS_ITERS - NS_BATCH_TAIL_ITERS;
     // dynamic LDS: the factorisation's matrix (129 KiB, EARLY_LOGDET) / the iterations' reduction buffer (32 KiB: four tiles x four
     // K-quarters, ns_YZ_quad_body; the pairs of part 1 use half of it) -- static and dynamic together must stay under 160 KiB
     double (*redp)[4][4][64] = reinterpret_cast<double (*)[4][4][64]>(ld_sm);
@@ -1834,7 +1815,7 @@ __device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const Ns
         ns_logdetB_workgroup<4>(A, scall, ld_sm, &partp[0][0]);
         return;
     }
-    if (with_table && blockIdx.x == (merged ? 3u : 1u)) {  // (merged: XCD 1 hosts the iterations)
+    if (EARLY_LOGDET && blockIdx.x == (merged ? 3u : 1u)) {  // (merged: XCD 1 hosts the iterations)
         if (merged && !ns_wait_result(scall)) return;
         if (threadIdx.x == 0) {
             ns_coef_table<COH_AGENT>(scall);
@@ -1844,19 +1825,14 @@ __device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const Ns
         return;
     }
     int b, w;
-    if (!ns_tail_block(NS_PAIR_WG, batch, b, w, merged ? 1u : 0u)) return;
+    if (!ns_persist_block(NS_PAIR_WG, batch, b, w, merged ? 1u : 0u)) return;
     const size_t off = (size_t)b * SN * SN;
     scall += (size_t)b * SC_COUNT;
     const unsigned xcc = ns_xcc_id();
-    const bool odd = (iter_first & 1) != 0;
+    constexpr bool odd = (iter_first & 1) != 0;
     if (merged && !ns_wait_result(scall)) return;
-#ifdef NS_STAMPS
-    if (threadIdx.x == 0) g_nstamp = 0;
-    __syncthreads();
-    NS_STAMP();
-#endif
     // the launch's first phase (agent-scope stores: the placement check comes with the barrier behind it)
-    if (with_table) {
+    if (EARLY_LOGDET) {
         // every iteration folded: Y1 and Z1 written out once (element-wise: NsFirst, no product), so that iteration 1's two phases
         // load plain tiles like every other iteration's.  (The batched and the launch-per-phase paths form the same values on load
         // instead -- for them a phase more is a launch more; here forming them on load cost 3.3 us over the phase it saved.)
@@ -1881,7 +1857,7 @@ __device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const Ns
     int r = ns_flag_barrier<COH_AGENT>(reinterpret_cast<unsigned *>(scall + SC_FLAGS) + 64, 1u, w, NS_PAIR_WG, xcc, scall + SC_BARFAIL);
     if (r == 2 && force_agent) r = 1;
     if (w == 0 && threadIdx.x == 0) scall[SC_PROF + 6] = (double)r;
-    if (with_table) {
+    if (EARLY_LOGDET) {
         // the coefficient table must be there before part 1 of iteration 2 reads it (it normally is: ~2 us against this launch's ~4)
         __shared__ int tab_ok;
         if (threadIdx.x == 0) {
@@ -1900,19 +1876,14 @@ __device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const Ns
         __syncthreads();
         if (!tab_ok) return;
     }
-    if (r == 2) ns_iter_tail_pair_rest<COH_XCD>(B, off, scall, iter_first, iter_last, w, xcc, redp, partp, with_table != 0);
-    else if (r == 1) ns_iter_tail_pair_rest<COH_AGENT>(B, off, scall, iter_first, iter_last, w, xcc, redp, partp, with_table != 0);
-#ifdef NS_STAMPS
-    if (b == 0 && w == 0 && threadIdx.x == 0)
-        for (int i = 0; i < 192; ++i) scall[SC_STAMPS + i] = (i < g_nstamp) ? (double)(g_stamp[i] - g_stamp[0]) : -1.0;
-#endif
+    if (r == 2) ns_iter_tail_pair_rest<COH_XCD>(B, off, scall, iter_first, w, xcc, redp, partp, EARLY_LOGDET);
+    else if (r == 1) ns_iter_tail_pair_rest<COH_AGENT>(B, off, scall, iter_first, w, xcc, redp, partp, EARLY_LOGDET);
 }
 template <bool EARLY_LOGDET>
-__global__ __launch_bounds__(256) void ns_iter_tail_pair_kernel(const double *A, const NsBufs B, double *scall, int iter_first, int iter_last,
-                                                                int batch, int force_agent, int with_table)
+__global__ __launch_bounds__(256) void ns_iter_tail_pair_kernel(const double *A, const NsBufs B, double *scall, int batch, int force_agent)
 {
     extern __shared__ __attribute__((aligned(16))) double ld_sm[];
-    ns_iter_tail_pair_impl<EARLY_LOGDET>(A, B, scall, iter_first, iter_last, batch, force_agent, with_table, 0, ld_sm);
+    ns_iter_tail_pair_impl<EARLY_LOGDET>(A, B, scall, batch, force_agent, 0, ld_sm);
 }
 // one matrix, every squaring and every iteration folded: linear ids = 0 (mod 8) are the squaring launch's workgroups (chain +
 // evaluations), = 1 (mod 8) the iterations', 2 the log-det workgroup, 3 the coefficient table -- 8 x 32 ids, 129 KiB of dynamic LDS
@@ -1925,10 +1896,10 @@ __global__ __launch_bounds__(256) void ns_chain_kernel(const double *A, const XB
     static_assert(NS_SQ_DYN_DOUBLES * sizeof(double) <= (size_t)SN * (SN + 1) * sizeof(double), "the squaring side's LDS fits the launch's");
     static_assert(NS_SQ_PAIR_WG + NEVAL <= NS_PAIR_WG, "grid = 8 x NS_PAIR_WG covers the squaring side");
     if ((blockIdx.x & 7u) == 0u) {
-        ns_square_tail_pair_impl<NEVAL, false, true>(A, xb_all, scall, 0, NS_SQUARINGS - 1, 1, force_agent, deflate, ld_sm);
+        ns_square_tail_pair_impl<NEVAL, false, true>(A, xb_all, scall, 1, force_agent, deflate, ld_sm);
         return;
     }
-    ns_iter_tail_pair_impl<true>(A, B, scall, 1, NS_ITERS - 1, 1, force_agent, 1, 1, ld_sm);
+    ns_iter_tail_pair_impl<true>(A, B, scall, 1, force_agent, 1, ld_sm);
 }
 
 // ---- log det B on its own (round 5).  Sigma = c B^(-1/2) needs log c = 2 log(sigma) + log det B / (2 n) (covo.py:124-128).  Rounds
@@ -2479,37 +2450,6 @@ __global__ __launch_bounds__(512) void ns_finalize_stream_kernel(const double *_
         __hip_atomic_fetch_or(status, COVO_DEVSTAT_GRID_BARRIER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
 
-// how many of the chain's last squarings / Newton-Schulz iterations run inside the persistent launches; covo_debug_set_ns_tail.
-// Rounds 2-3 (persistent launches spread over the XCDs, every access sc1, one counter): a folded phase cost nothing once the
-// chain had converged (a separate launch: 1.6 us) but, while live, +0.4 us per squaring / +1.4 us per iteration over its
-// separate launch(es), so only the often-idle phases were folded (squarings 7.., iterations 6..).
-// Round 4 (one XCD, plain stores, flag words; see ns_flag_barrier): a live folded squaring is 0.85 us CHEAPER than its launch, a
-// live iteration 0.7 us (scripts/ns_tail_cost.py on a 14-squaring / 9-iteration matrix: covo_sigma 167.5 us with nothing folded,
-// 156.5 squarings folded, 161.8 iterations folded, 151.7 both), so batch 1 folds everything but the first squaring and
-// iteration 0.  Same box, scripts/tail_bench.py, bench / closed loop steps/s: rounds 2-3 code (9, 6) 5 277-5 305 / 4 685-4 692;
-// round 4 code (9, 6) 5 236 / 4 644, (12, 8) 5 280 / 4 738, (15, 8) 5 364-5 384 / 4 811-4 829, (15, 11) 5 370-5 375 / 4 813-4 815.
-// Where the rest of a phase goes (workgroup 0's seams, -DNS_STAMPS): part 1 of an iteration = 1.08 us until the operands are in
-// (each CU of the one XCD pulls 64 KB through its 64 B/clk port), 0.40 MFMA + reduce, 0.64 until the stores are acknowledged,
-// 0.64 flag -> poll; part 2 = 1.36 / 0.84 (2 048 fp64-MFMA cycles per SIMD: a quarter of the phase is now the ONE XCD's matrix
-// throughput) / 0.6 / 1.3-1.7 (the other workgroup of the CU finishes its MFMAs later).
-// Batched (the env-batched step, covo-offline's table): all squarings are folded -- every matrix runs them at its own pace, 4
-// matrices per XCD at 32 -- but only the last 4 iterations: early on every matrix is live, and four matrices' workgroups on an XCD's
-// 32 CUs keep its ONE L2 busy 65-80 % of the launch (profiles/r04_sigma_batch_l2_counters.log) where a launch spreads each phase
-// over the chip.  bench.py --config envs, control-steps/s / Sigma us per batched step, one tile per workgroup (64 per matrix):
-// (0, 0) 71 186 / 288; (15, 0) 73 395 / 274; (15, 3) 74 851 / 266; (15, 5) 75 943 / 255; (15, 7) 73 142 / 274; (15, 11) 72 163 / 282.
-// With the 2 x 2 blocks of the batched launches and the pairs of the persistent one (32 workgroups per matrix), bench / closed
-// loop: (15, 3) 81 815 / 75 187; (15, 4) 82 553 / 75 641; (15, 5) 82 865 / 74 674; (15, 6) 82 978 / 74 796; (15, 8) 81 889 / 74 194;
-// (15, 11) 80 713 / 73 431 -> the last 4.  The squaring launch on pairs too (20 workgroups per matrix instead of 36, a third fewer
-// operand bytes): one matrix 5 464-5 470 / 4 874-4 886 against 5 428-5 457 / 4 844-4 854, batched 83 663 / 76 231 against 82 535 / 75 461.
-// THE defaults of the four tail lengths (also what covo_debug_set_ns_tail(handle, -1, -1) restores); the other switches of a
-// handle (deflation, forced agent-scope coherence, where the Ritz evaluations run): CovoOpts, covo_default_opts (step.hip)
-void sigma_ns_tail_defaults(CovoOpts &o)
-{
-    o.ns_tail_iters = NS_ITERS - 1;
-    o.ns_tail_squarings = o.ns_tail_squarings_batched = NS_SQUARINGS - 1;
-    o.ns_tail_iters_batched = 4;
-}
-
 SymStatsOut sigma_ns_stats_out(void *workspace, int batch)
 {
     double *ws = reinterpret_cast<double *>(workspace);
@@ -2525,21 +2465,31 @@ SymStatsOut sigma_ns_stats_out(void *workspace, int batch)
 }
 // 11 matrices, the slots, then the filter's history X_3 .. X_16 and X_1 (XBufs)
 size_t sigma_ns_workspace_bytes(int batch) { return (size_t)batch * ((11 + NS_SQUARINGS - 1) * SN * SN + SC_COUNT) * sizeof(double); }
-// (opt.ns_ritz_inside == 0 -- COVO_NS_RITZ_INSIDE=0 / covo_debug_set_ns_ritz_inside(h, 0): the one-matrix chain, too, evaluates after
-// its squarings: ns_ritz_scan_kernel)
 
+// The chain runs one of four fixed launch plans ([prep]: ns_prep_kernel, unless the Hessian has left A's statistics: r_has_stats):
+//   MERGED     one matrix, persistent, r_has_stats, opt.ns_merged:  ns_chain_kernel -> finalize
+//   TWO_LAUNCH one matrix, persistent, otherwise:  [prep] -> squarings with the evaluations inside -> iterations 1 .. 11 with the
+//              coefficient table and log det B -> finalize
+//   BATCHED    batch > 1, persistent:  [prep] -> squarings with the evaluations inside -> iteration 1 (element-wise) -> 7 x (T, Y'Z')
+//              -> the last NS_BATCH_TAIL_ITERS iterations -> finalize (with log det B)
+//   PHASED     COVO_FLAG_SHARED_DEVICE (no persistent launch):  [prep] -> 16 squarings -> the Ritz scan -> iteration 1 -> 11 x (T, Y'Z')
+//              -> finalize (with log det B)
+// sigma_stages (covo_debug_time_step) cuts each plan short: 1 the squarings, 2 + the scan launch, 3 + the Newton-Schulz iterations,
+// 4 + finalize; below 3 one matrix takes the two-launch plan.
 int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sample_sigma, float *Sigma, float *L, void *workspace,
                     hipStream_t s, const EpsGenArgs *gen, int *status, bool persistent_ok, CovDeferred *cov, bool r_has_stats,
-                    const StreamGemmArgs *stream, bool *streamed)
+                    const StreamGemmArgs *stream, bool *streamed, const DebugMasks &dbg)
 {
+    const int sigma_stages = dbg.sigma_stages;
     if (streamed != nullptr) *streamed = false;
     double *ws = reinterpret_cast<double *>(workspace);
     const size_t M = (size_t)batch * SN * SN;
-    double *A = ws, *X0 = ws + M, *X1 = ws + 2 * M;
+    double *A = ws;
     double *Y[2] = {ws + 3 * M, ws + 4 * M}, *Yt[2] = {ws + 5 * M, ws + 6 * M};
     double *Z[2] = {ws + 7 * M, ws + 8 * M}, *Zt[2] = {ws + 9 * M, ws + 10 * M};
-    double *T = X0, *Tt = X1;  // the squaring buffers are free once lambda_min is known
     double *sc = ws + 11 * M;
+    double *hist0 = sc + (size_t)batch * SC_COUNT;
+    const XBufs xb{ws + M, ws + 2 * M, hist0, hist0 + (size_t)(NS_SQUARINGS - 2) * M, M};
     const size_t lds = (size_t)SN * (SN + 1) * sizeof(double);
     static unsigned long long attr_devices = 0;  // (per device: covo_first_on_device)
     if (covo_first_on_device(attr_devices)) {
@@ -2554,96 +2504,76 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
     }
     if (r_has_stats) A = const_cast<double *>(R);  // exactly symmetric, statistics already in sc (KD): no prep launch
     else hipLaunchKernelGGL(ns_prep_kernel, ns_grid(NS_TILES, batch), dim3(256), 0, s, R, A, sc, batch);
-    double *hist0 = sc + (size_t)batch * SC_COUNT;
-    const XBufs xb{X0, X1, hist0, hist0 + (size_t)(NS_SQUARINGS - 2) * M, M};
-    const bool fold_first = persistent_ok && (batch == 1 ? opt.ns_tail_squarings : opt.ns_tail_squarings_batched) >= NS_SQUARINGS - 1;
-    if (!fold_first) hipLaunchKernelGGL(ns_square_kernel<true>, ns_grid(NS_TILES, batch), dim3(256), 0, s, A, ns_xk(xb, 1), sc, 0, batch);
-    // the remaining squarings / iterations run inside persistent launches (20 / 32 workgroups per matrix, one XCD per matrix)
-    int sq_tail = persistent_ok ? (batch == 1 ? opt.ns_tail_squarings : opt.ns_tail_squarings_batched) : 0;
-    if (sq_tail > NS_SQUARINGS - 1) sq_tail = NS_SQUARINGS - 1;
-    const int sq_sep = NS_SQUARINGS - sq_tail;
-    for (int i = 1; i < sq_sep; ++i)
-        hipLaunchKernelGGL(ns_square_kernel<false>, ns_grid(NS_TILES, batch), dim3(256), 0, s, ns_xk(xb, i), ns_xk(xb, i + 1), sc, i, batch);
-    // every squaring folded: the Rayleigh-Ritz evaluations ride in the squaring launch and stop it (ns_square_evaluator)
-    const bool eval_inside = fold_first && opt.ns_ritz_inside == 1;
-    // round 6: one matrix with both persistent launches whole -> ONE launch (ns_chain_kernel): the iterations' workgroups wait inside
-    // for the chain's result.  r_has_stats: SC_READY and the barrier flag words were cleared a launch ahead (KD).
-    const bool merged = opt.ns_merged && batch == 1 && persistent_ok && eval_inside && r_has_stats && sq_tail >= NS_SQUARINGS - 1 &&
-                        opt.ns_tail_iters >= NS_ITERS - 1 && g_dbg_sigma_stages >= 3;
-    if (merged) {
-        NsBufs B;
-        for (int k = 0; k < 2; ++k) {
-            B.Y[k] = Y[k];
-            B.Yt[k] = Yt[k];
-            B.Z[k] = Z[k];
-            B.Zt[k] = Zt[k];
-        }
-        B.T = T;
-        B.Tt = Tt;
-        B.A = A;
-        B.X1 = ns_xk(xb, 1);
-        hipLaunchKernelGGL((ns_chain_kernel<NS_SQ_EVAL_WG>), ns_tail_grid(NS_PAIR_WG, 1), dim3(256), lds, s, A, xb, B, sc, opt.ns_force_agent,
+    // T, T^T of the iterations: the first two matrices of the filter's history -- a squaring launch with the evaluations inside keeps
+    // no history, and the phased plan's scan launch has finished with it -- so no squaring writes them while an iteration runs
+    NsBufs B;
+    for (int k = 0; k < 2; ++k) {
+        B.Y[k] = Y[k];
+        B.Yt[k] = Yt[k];
+        B.Z[k] = Z[k];
+        B.Zt[k] = Zt[k];
+    }
+    B.T = hist0;
+    B.Tt = hist0 + M;
+    B.A = A;
+    B.X1 = ns_xk(xb, 1);
+    enum { MERGED, TWO_LAUNCH, BATCHED, PHASED } plan;
+    if (!persistent_ok) plan = PHASED;
+    else if (batch > 1) plan = BATCHED;
+    else if (opt.ns_merged && r_has_stats && sigma_stages >= 3) plan = MERGED;  // (SC_READY and the flag words cleared by KD)
+    else plan = TWO_LAUNCH;
+    switch (plan) {
+    case MERGED:
+        hipLaunchKernelGGL((ns_chain_kernel<NS_SQ_EVAL_WG>), ns_persist_grid(NS_PAIR_WG, 1), dim3(256), lds, s, A, xb, B, sc, opt.ns_force_agent,
                            opt.ns_deflate);
-    } else
-    if (sq_tail > 0) {
-        if (eval_inside && batch == 1)
-            hipLaunchKernelGGL((ns_square_tail_pair_kernel<NS_SQ_EVAL_WG>), ns_tail_grid(NS_SQ_PAIR_WG + NS_SQ_EVAL_WG, batch), dim3(256), 0,
-                               s, A, xb, sc, 0, NS_SQUARINGS - 1, batch, opt.ns_force_agent, opt.ns_deflate);
-        else if (eval_inside)
-            hipLaunchKernelGGL(ns_square_tail_pair_lean_kernel, ns_tail_grid(NS_SQ_PAIR_WG + NS_SQ_EVAL_WG_BATCH, batch),
-                               dim3(256), 0, s, A, xb, sc, 0, NS_SQUARINGS - 1, batch, opt.ns_force_agent, opt.ns_deflate);
-        else
-            hipLaunchKernelGGL((ns_square_tail_pair_kernel<0>), ns_tail_grid(NS_SQ_PAIR_WG, batch), dim3(256), 0, s, A, xb, sc,
-                               fold_first ? 0 : sq_sep, NS_SQUARINGS - 1, batch, opt.ns_force_agent, opt.ns_deflate);
-    }
-    if (g_dbg_sigma_stages < 2) return 0;
-    if (!eval_inside && !merged) hipLaunchKernelGGL(ns_ritz_scan_kernel, dim3(batch * RITZ_NK), dim3(256), 0, s, A, xb, sc, opt.ns_deflate, opt.ns_ritz_inside == 2 ? 1 : 0);
-    if (g_dbg_sigma_stages < 3) return 0;
-    // Iteration 0 is no product (NsFirst): Y1 and Z1 are written out element-wise from A and X_1 -- by the first phase of the persistent
-    // launch when one matrix folds every iteration into it, else by a launch of their own (which also makes the coefficient table).
-    const double *Xq = ns_xk(xb, 1);  // X_1
-    const bool fold_all = batch == 1 && persistent_ok && opt.ns_tail_iters >= NS_ITERS - 1;
-    if (!fold_all && !merged) hipLaunchKernelGGL(ns_first_elem_kernel, ns_grid(65, batch), dim3(256), 0, s, A, Xq, Y[1], Yt[1], Z[1], Zt[1], sc, 1, batch);
-    bool early_logdet = false;
-    int n_tail = persistent_ok ? (batch == 1 ? opt.ns_tail_iters : opt.ns_tail_iters_batched) : 0;
-    if (n_tail > NS_ITERS - 1) n_tail = NS_ITERS - 1;
-    const int n_sep = NS_ITERS - n_tail;
-    for (int i = 1; i < n_sep; ++i) {
-        const int in = i & 1, out = in ^ 1;
-        if (batch > 1) {  // 2 x 2 tile blocks per workgroup: same tiles, same bits, half the operand traffic
-            hipLaunchKernelGGL(ns_T_quad_kernel, ns_grid(16, batch), dim3(256), 0, s, Y[in], Zt[in], T, Tt, sc, i, batch);
-            hipLaunchKernelGGL(ns_YZ_quad_kernel, ns_grid(32, batch), dim3(256), 0, s, Yt[in], Z[in], T, Tt, Y[out], Yt[out], Z[out],
+        break;
+    case TWO_LAUNCH:
+        hipLaunchKernelGGL((ns_square_tail_pair_kernel<NS_SQ_EVAL_WG>), ns_persist_grid(NS_SQ_PAIR_WG + NS_SQ_EVAL_WG, 1), dim3(256), 0, s, A,
+                           xb, sc, 1, opt.ns_force_agent, opt.ns_deflate);
+        if (sigma_stages < 3) return 0;
+        hipLaunchKernelGGL(ns_iter_tail_pair_kernel<true>, ns_persist_grid(NS_PAIR_WG, 1), dim3(256), lds, s, A, B, sc, 1, opt.ns_force_agent);
+        break;
+    case BATCHED:
+        hipLaunchKernelGGL(ns_square_tail_pair_lean_kernel, ns_persist_grid(NS_SQ_PAIR_WG + NS_SQ_EVAL_WG_BATCH, batch), dim3(256), 0, s, A,
+                           xb, sc, batch, opt.ns_force_agent, opt.ns_deflate);
+        if (sigma_stages < 3) return 0;
+        hipLaunchKernelGGL(ns_first_elem_kernel, ns_grid(65, batch), dim3(256), 0, s, A, B.X1, Y[1], Yt[1], Z[1], Zt[1], sc, 1, batch);
+        for (int i = 1; i < NS_ITERS - NS_BATCH_TAIL_ITERS; ++i) {  // 2 x 2 tile blocks per workgroup: same tiles, same bits
+            const int in = i & 1, out = in ^ 1;
+            hipLaunchKernelGGL(ns_T_quad_kernel, ns_grid(16, batch), dim3(256), 0, s, Y[in], Zt[in], B.T, B.Tt, sc, i, batch);
+            hipLaunchKernelGGL(ns_YZ_quad_kernel, ns_grid(32, batch), dim3(256), 0, s, Yt[in], Z[in], B.T, B.Tt, Y[out], Yt[out], Z[out],
                                Zt[out], sc, i, out, batch);
-            continue;
         }
-        hipLaunchKernelGGL(ns_T_kernel, ns_grid(64, batch), dim3(256), 0, s, Y[in], Zt[in], T, Tt, sc, i, batch);
-        hipLaunchKernelGGL(ns_YZ_kernel, ns_grid(128, batch), dim3(256), 0, s, Yt[in], Z[in], T, Tt, Y[out], Yt[out], Z[out],
-                           Zt[out], sc, i, out, batch);
-    }
-    if (n_tail > 0) {
-        NsBufs B;
-        for (int k = 0; k < 2; ++k) {
-            B.Y[k] = Y[k];
-            B.Yt[k] = Yt[k];
-            B.Z[k] = Z[k];
-            B.Zt[k] = Zt[k];
+        hipLaunchKernelGGL(ns_iter_tail_pair_kernel<false>, ns_persist_grid(NS_PAIR_WG, batch), dim3(256), 4 * 4 * 4 * 64 * sizeof(double), s, A,
+                           B, sc, batch, opt.ns_force_agent);
+        break;
+    case PHASED:
+        hipLaunchKernelGGL(ns_square_kernel<true>, ns_grid(NS_TILES, batch), dim3(256), 0, s, A, ns_xk(xb, 1), sc, 0, batch);
+        for (int i = 1; i < NS_SQUARINGS; ++i)
+            hipLaunchKernelGGL(ns_square_kernel<false>, ns_grid(NS_TILES, batch), dim3(256), 0, s, ns_xk(xb, i), ns_xk(xb, i + 1), sc, i, batch);
+        if (sigma_stages < 2) return 0;
+        hipLaunchKernelGGL(ns_ritz_scan_kernel, dim3(batch * RITZ_NK), dim3(256), 0, s, A, xb, sc, opt.ns_deflate);
+        if (sigma_stages < 3) return 0;
+        hipLaunchKernelGGL(ns_first_elem_kernel, ns_grid(65, batch), dim3(256), 0, s, A, B.X1, Y[1], Yt[1], Z[1], Zt[1], sc, 1, batch);
+        for (int i = 1; i < NS_ITERS; ++i) {
+            const int in = i & 1, out = in ^ 1;
+            if (batch > 1) {  // 2 x 2 tile blocks per workgroup: same tiles, same bits, half the operand traffic
+                hipLaunchKernelGGL(ns_T_quad_kernel, ns_grid(16, batch), dim3(256), 0, s, Y[in], Zt[in], B.T, B.Tt, sc, i, batch);
+                hipLaunchKernelGGL(ns_YZ_quad_kernel, ns_grid(32, batch), dim3(256), 0, s, Yt[in], Z[in], B.T, B.Tt, Y[out], Yt[out], Z[out],
+                                   Zt[out], sc, i, out, batch);
+            } else {
+                hipLaunchKernelGGL(ns_T_kernel, ns_grid(64, batch), dim3(256), 0, s, Y[in], Zt[in], B.T, B.Tt, sc, i, batch);
+                hipLaunchKernelGGL(ns_YZ_kernel, ns_grid(128, batch), dim3(256), 0, s, Yt[in], Z[in], B.T, B.Tt, Y[out], Yt[out], Z[out],
+                                   Zt[out], sc, i, out, batch);
+            }
         }
-        B.T = T;
-        B.Tt = Tt;
-        B.A = A;
-        B.X1 = Xq;
-        // one matrix: log det B rides in this launch (ns_logdetB_workgroup), ~50 us before the finalize launch wants it
-        early_logdet = batch == 1;
-        if (merged) {
-        } else if (early_logdet)
-            hipLaunchKernelGGL(ns_iter_tail_pair_kernel<true>, ns_tail_grid(NS_PAIR_WG, batch), dim3(256), lds, s, A, B, sc,
-                               fold_all ? 1 : n_sep, NS_ITERS - 1, batch, opt.ns_force_agent, fold_all ? 1 : 0);
-        else
-            hipLaunchKernelGGL(ns_iter_tail_pair_kernel<false>, ns_tail_grid(NS_PAIR_WG, batch), dim3(256), 4 * 4 * 4 * 64 * sizeof(double), s, A, B, sc,
-                               n_sep, NS_ITERS - 1, batch, opt.ns_force_agent, 0);
+        break;
     }
-    if (g_dbg_sigma_stages < 4) return 0;
-    if (stream != nullptr && early_logdet && batch == 1) {
+    if (sigma_stages < 4) return 0;
+    // one matrix on the persistent plans: log det B rides in the Newton-Schulz launch (ns_logdetB_workgroup), ~50 us before the
+    // finalize launch wants it
+    const bool early_logdet = plan == MERGED || plan == TWO_LAUNCH;
+    if (stream != nullptr && early_logdet) {
         // the noise GEMM rides in the finalize launch (ns_finalize_stream_kernel): one workgroup factors, the others multiply
         // workers b = 1 .. W take the tiles [8 b, 8 b + 8); the tiles [0, 8) are hosted one per worker (ns_finalize_stream_kernel)
         const int ntiles = (stream->N + 31) / 32;

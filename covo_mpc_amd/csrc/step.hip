@@ -7,7 +7,6 @@
 // The second call with the same buffers captures the sequence into a hipGraph, later calls replay it.
 // Quantities that change every step (Philox key, MPPI's shared disturbance draw) live in a 32-byte
 // device block refreshed by one async copy before each replay, so the captured kernel arguments stay valid.
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -77,7 +76,7 @@ struct StepState {
 constexpr int DYN_BYTES = 48;
 // up to this many samples per GPU the step's epsilon is drawn by passenger workgroups of the Sigma chain's last launch
 // (~6 us of work per 65 536 samples inside a ~30 us single-workgroup kernel); beyond, the GEMM draws it itself
-constexpr int EPS_AHEAD_MAX_N = 262144;
+constexpr int EPS_TILED_MAX_N = 262144;
 
 static int step_state_init(covo_ctx *h)
 {
@@ -96,7 +95,7 @@ static int step_state_init(covo_ctx *h)
     COVO_CHECK_HIP(hipMemset(st->ticket, 0, sizeof(unsigned)));
     COVO_CHECK_HIP(hipMalloc(&st->sync, 16 * sizeof(unsigned)));
     COVO_CHECK_HIP(hipMemset(st->sync, 0, 16 * sizeof(unsigned)));
-    if (h->cfg.n_local <= EPS_AHEAD_MAX_N)
+    if (h->cfg.n_local <= EPS_TILED_MAX_N)
         COVO_CHECK_HIP(hipMalloc(&st->eps_tiled, (size_t)((h->cfg.n_local + 31) / 32) * 16 * 64 * sizeof(float4)));
     h->step = st;
     return 0;
@@ -126,21 +125,14 @@ void step_state_destroy(covo_ctx *h)
     h->step = nullptr;
 }
 
-int g_dbg_hess_mask = 15, g_dbg_sigma_stages = 4;
-static const int g_dbg_eps_ahead = [] {  // COVO_EPS_AHEAD=0: the GEMM draws epsilon itself (A/B measurements)
-    const char *v = std::getenv("COVO_EPS_AHEAD");
-    return v ? std::atoi(v) : 1;
-}();
 // The experiment switches a new handle starts with (CovoOpts, covo_common.hpp), from the environment:
 //   COVO_FUSE_SMALL=0     covo-offline and MPPI steps of <= 256 sample groups run their staged launches (begin | noise | rollout +
 //                         records | merge) instead of the one fused launch of step_small.hip
 //   COVO_STREAM_GEMM=0    covo-online's noise GEMM as a launch of its own behind the Sigma chain's finalize launch (rounds 1-4)
 //                         instead of streamed under the factorisation inside it (sigma_ns.hip: ns_finalize_stream_kernel)
 //   COVO_FOLD_BEGIN=0     eager covo-online steps keep the begin launch (default: its work rides in the Hessian's first launch)
-//   COVO_NS_TAIL=sq,it    phases folded into the Sigma chain's persistent launches, as covo_debug_set_ns_tail
 //   COVO_NS_MERGED=0      the Sigma chain's two persistent launches (squarings | iterations) as two launches (rounds 4-5) instead of one
-//   COVO_NS_DEFLATE=0     the undeflated Newton-Schulz iteration;  COVO_NS_RITZ_INSIDE=0 / 2: the Ritz evaluations as one scan
-//                         launch after the squarings / the filter's last iterate only (rounds 1-4's rule, timing reference)
+//   COVO_NS_DEFLATE=0     the undeflated Newton-Schulz iteration
 // covo_debug_set_*(handle, ...) change them per handle afterwards (A/B measurements, parity tests).
 CovoOpts covo_default_opts()
 {
@@ -152,31 +144,22 @@ CovoOpts covo_default_opts()
     o.fuse_small = env_int("COVO_FUSE_SMALL", 1);
     o.stream_gemm = env_int("COVO_STREAM_GEMM", 1);
     o.fold_begin = env_int("COVO_FOLD_BEGIN", 1);
-    sigma_ns_tail_defaults(o);
-    if (const char *v = std::getenv("COVO_NS_TAIL")) {  // "squarings,iterations" as covo_debug_set_ns_tail (scripts/tail_bench.py)
-        int sq = -1, it = -1;
-        if (std::sscanf(v, "%d,%d", &sq, &it) == 2 && sq >= 0 && it >= 0 && sq <= 64 && it <= 64) {
-            o.ns_tail_squarings = o.ns_tail_squarings_batched = sq;
-            o.ns_tail_iters = o.ns_tail_iters_batched = it;
-        }
-    }
     o.ns_deflate = env_int("COVO_NS_DEFLATE", 1) ? 1 : 0;
     o.ns_force_agent = 0;
     o.ns_merged = env_int("COVO_NS_MERGED", 1) ? 1 : 0;
-    const int ri = env_int("COVO_NS_RITZ_INSIDE", 1);
-    o.ns_ritz_inside = ri == 2 ? 2 : (ri ? 1 : 0);
     o.epoch = 0;
     return o;
 }
-static int g_dbg_step_mask = 63;  // (1: unused, the begin launch is not part of the graph) 2 Hessian, 4 Sigma, 8 noise GEMM, 16 rollout, 32 softmax update
 
 // the launch sequence of one step (everything reads per-step scalars from st->dyn)
 // begin != null (eager covo-online steps): no begin launch ran -- the Hessian's first launch does its work (HessBegin) and every
-// launch reads the caller's state where it lies (state_direct) instead of the fixed-address copy
+// launch reads the caller's state where it lies (state_direct) instead of the fixed-address copy.  dbg.step bit 1 is unused here (the
+// begin launch is not part of the graph).
 static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, const covo_step_args &a, hipStream_t s,
+                        const DebugMasks &dbg = DebugMasks(),
                         const HessBegin *begin = nullptr, const float *state_direct = nullptr)
 {
-    const int M = g_dbg_step_mask;
+    const int M = dbg.step;
     const int N = a.n_samples;
     const float *fdev = reinterpret_cast<const float *>(st->dyn + 2);
     float *am_shift = a.a_mean_shift ? a.a_mean_shift : st->a_mean_shift;
@@ -193,14 +176,14 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
                                                    a.mode == COVO_MODE_COVO_ONLINE ? st->f_tab_hess : nullptr, s))) return rc;
     if (a.mode == COVO_MODE_COVO_ONLINE) {
         // the Hessian's last launch leaves the Sigma chain's input statistics in the chain's workspace: no prep launch
-        const bool stats = (M & 2) && (M & 4) && (g_dbg_hess_mask & 15) == 15 && hessian_leaves_stats(p);
+        const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15 && hessian_leaves_stats(p);
         const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma);
         if ((M & 2) && (rc = launch_hessian(state, a.pos_traj, a.vel_traj, a.T, p, am_shift, 1, st->R, h->ws_hess, s, nullptr, 0,
-                                            stats ? &so : nullptr, tables ? st->f_tab_hess : nullptr, nullptr, h->status_dev, begin)))
+                                            stats ? &so : nullptr, tables ? st->f_tab_hess : nullptr, nullptr, h->status_dev, begin, dbg)))
             return rc;  // :134-185
         float *Sig = a.a_cov ? a.a_cov : st->Sigma;
         // epsilon needs only the act key: it is drawn under the chain's single-workgroup finalize launch, the GEMM loads it
-        const bool ahead = st->eps_tiled != nullptr && (M & 4) && g_dbg_sigma_stages >= 4 && g_dbg_eps_ahead;
+        const bool ahead = st->eps_tiled != nullptr && (M & 4) && dbg.sigma_stages >= 4;
         EpsGenArgs gen;
         gen.eps_tiled = ahead ? st->eps_tiled : nullptr;
         gen.dyn = st->dyn;
@@ -212,7 +195,7 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
         // a_cov is written by the GEMM's first workgroups, not by the chain's one-workgroup finalize launch (CovDeferred)
         CovDeferred cov;
         std::memset(&cov, 0, sizeof(cov));
-        const bool defer = (M & 8) && g_dbg_sigma_stages >= 4;
+        const bool defer = (M & 8) && dbg.sigma_stages >= 4;
         // the GEMM streamed under the factorisation, inside the chain's last launch (one matrix, persistent launches allowed)
         StreamGemmArgs sg;
         sg.mu = am_shift;
@@ -224,11 +207,11 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
         sg.sync = st->sync;
         sg.a_cov_out = Sig;
         sg.nanp = covo_propagate_nan(h) ? 1 : 0;
-        const bool want_stream = h->opt.stream_gemm && (M & 4) && (M & 8) && g_dbg_sigma_stages >= 4;
+        const bool want_stream = h->opt.stream_gemm && (M & 4) && (M & 8) && dbg.sigma_stages >= 4;
         bool streamed = false;
         if ((M & 4) && (rc = launch_sigma_ns(h->opt, st->R, 1, a.sample_sigma, Sig, st->L, h->ws_sigma, s, &gen, h->status_dev,
                                              (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0, defer ? &cov : nullptr, stats,
-                                             want_stream ? &sg : nullptr, &streamed))) return rc;
+                                             want_stream ? &sg : nullptr, &streamed, dbg))) return rc;
         if (streamed) {
         } else if (ahead) {
             if ((M & 8) && (rc = launch_noise_gemm(st->L, am_shift, reinterpret_cast<const float *>(st->eps_tiled), 0, 0,
@@ -311,7 +294,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     }
     // eager covo-online steps (no per-step force tables, whose launch precedes the Hessian and reads the scalars): the begin work
     // rides in the Hessian's first launch -- one launch boundary less (COVO_FOLD_BEGIN=0 keeps the begin launch)
-    if (h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 && g_dbg_hess_mask == 15 &&
+    if (h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
         !(params->disturb_kind >= COVO_DISTURB_PERIODIC && params->disturb_kind <= COVO_DISTURB_MIXED)) {
         HessBegin hb;
         hb.a_mean_raw = args->a_mean_in ? args->a_mean_in : args->a_mean;
@@ -321,7 +304,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
         hb.derive_keys = args->derive_keys;
         hb.shared_noise_scale = shared_noise_scale;
         st->have_key = false;
-        return enqueue_step(h, st, *params, *args, s, &hb, args->state);
+        return enqueue_step(h, st, *params, *args, s, DebugMasks(), &hb, args->state);
     }
     hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, s,
                        args->a_mean_in ? args->a_mean_in : args->a_mean,
@@ -403,9 +386,10 @@ int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const 
                            blk, args->mode == COVO_MODE_MPPI ? args->a_cov : (float *)nullptr, st->Ls, st->sync);
         COVO_CHECK_HIP(hipStreamSynchronize(run));
     }
-    g_dbg_step_mask = step_mask;
-    g_dbg_hess_mask = hess_mask;
-    g_dbg_sigma_stages = sigma_stages;
+    DebugMasks dbg;
+    dbg.step = step_mask;
+    dbg.hess = hess_mask;
+    dbg.sigma_stages = sigma_stages;
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     int rc = 0;
@@ -414,13 +398,10 @@ int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const 
         for (int r = 0; r < reps && !rc; ++r) {
             if (args->mode == COVO_MODE_COVO_ONLINE && h->opt.stream_gemm && (step_mask & 12) == 12)
                 hipLaunchKernelGGL(stream_seq_bump_kernel, dim3(1), dim3(1), 0, cs, st->sync);
-            rc = enqueue_step(h, st, *params, *args, cs);
+            rc = enqueue_step(h, st, *params, *args, cs, dbg);
         }
         e = hipStreamEndCapture(cs, &g);
     }
-    g_dbg_step_mask = 63;
-    g_dbg_hess_mask = 15;
-    g_dbg_sigma_stages = 4;
     if (rc) return rc;
     COVO_CHECK_HIP(e);
     COVO_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
@@ -596,26 +577,26 @@ void batch_state_destroy(covo_ctx *h)
 // chain of the two halves of the instances on two forked branches, every phase its own launch: 72 700 control-steps/s against
 // 71 200 unforked with the same launches and 76 300 with the persistent tails -- which must not run side by side: two persistent
 // launches can starve each other of workgroup slots, the barriers then time out.)
-static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, hipStream_t s)
+static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, hipStream_t s, const DebugMasks &dbg = DebugMasks())
 {
     const int E = a.n_envs, N = a.n_samples;
-    const int M = g_dbg_step_mask;  // 63 outside covo_debug_time_batched (which replays selected launch groups)
+    const int M = dbg.step;  // 63 outside covo_debug_time_batched (which replays selected launch groups)
     int rc;
     if (M & 1) hipLaunchKernelGGL(batch_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, b->a_mean_shift, b->dyn);
     // covo.py:231: CoVO's sampling rollouts run step_env(deterministic=True); get_hessian likewise (covo.py:152)
     if ((M & 1) && b->tables && (rc = launch_disturb_tables_batched(b->models, a.states, b->dyn, E, 1, b->tab_rollout, b->tab_hess, s)))
         return rc;
     // as in the single step: the Hessian's last launch leaves every instance's Sigma-chain input statistics, no prep launch
-    const bool stats = (M & 2) && (M & 4) && (g_dbg_hess_mask & 15) == 15 && hessian_leaves_stats(b->params[0]);
+    const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15 && hessian_leaves_stats(b->params[0]);
     const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma, E);
     if ((M & 2) && (rc = launch_hessian(a.states, a.pos_traj, a.vel_traj, a.T, b->params[0], b->a_mean_shift, E, b->R, h->ws_hess, s,
                                         b->consts, (size_t)a.T * 3, stats ? &so : nullptr, b->tables ? b->tab_hess : nullptr, b->models,
-                                        h->status_dev)))
+                                        h->status_dev, nullptr, dbg)))
         return rc;
     float *Sig = a.a_cov ? a.a_cov : b->Sigma;
     // epsilon needs only the act keys: every instance's is drawn under the chain's finalize launch (32 of 256 CUs factor), the GEMM
     // loads it -- the in-kernel Philox costs the batched GEMM ~9 us, its matrix pipe hides no vector work
-    const bool ahead = b->eps_tiled != nullptr && (M & 4) && (M & 8) && g_dbg_sigma_stages >= 4 && g_dbg_eps_ahead;
+    const bool ahead = b->eps_tiled != nullptr && (M & 4) && (M & 8) && dbg.sigma_stages >= 4;
     EpsGenArgs gen;
     gen.eps_tiled = ahead ? b->eps_tiled : nullptr;
     gen.dyn = b->dyn;
@@ -625,7 +606,7 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     gen.dyn_stride = 12;
     gen.eps_stride = (size_t)((N + 31) / 32) * 16 * 64;
     if ((M & 4) && (rc = launch_sigma_ns(h->opt, b->R, E, a.sample_sigma, Sig, b->L, h->ws_sigma, s, &gen, h->status_dev,
-                                         (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0, nullptr, stats))) return rc;
+                                         (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0, nullptr, stats, nullptr, nullptr, dbg))) return rc;
     if (ahead) {
         if ((rc = launch_noise_gemm(b->L, b->a_mean_shift, reinterpret_cast<const float *>(b->eps_tiled), 0, 0, 0, N, a.a, s, nullptr,
                                     nullptr, 0, E, true, nullptr, covo_propagate_nan(h))))
@@ -654,16 +635,16 @@ int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us
     }
     hipStream_t cs = h->side_stream;
     COVO_CHECK_HIP(hipStreamSynchronize(run));
-    g_dbg_step_mask = step_mask;
+    DebugMasks dbg;
+    dbg.step = step_mask;
     hipGraph_t g = nullptr;
     hipGraphExec_t ge = nullptr;
     int rc = 0;
     hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
     if (e == hipSuccess) {
-        for (int r = 0; r < reps && !rc; ++r) rc = batch_enqueue(h, b, b->key, cs);
+        for (int r = 0; r < reps && !rc; ++r) rc = batch_enqueue(h, b, b->key, cs, dbg);
         e = hipStreamEndCapture(cs, &g);
     }
-    g_dbg_step_mask = 63;
     if (rc) return rc;
     COVO_CHECK_HIP(e);
     COVO_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));

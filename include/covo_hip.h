@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define COVO_ABI_VERSION 7
+#define COVO_ABI_VERSION 8
 
 #define COVO_H 32            /* horizon (compile-time in the fused kernels)          */
 #define COVO_DU 4            /* action dim, quadjax/envs/quadrotor.py:198            */
@@ -376,7 +376,7 @@ int covo_sigma_jacobi(covo_handle_t h, const double *R, int32_t batch, float sam
                       float *L_out, void *stream);
 
 /* ---- Experiment switches of ONE handle (round 6; rounds 1-5 kept them process-global).  A new handle takes its defaults from the
- * environment (COVO_FUSE_SMALL, COVO_STREAM_GEMM, COVO_FOLD_BEGIN, COVO_NS_DEFLATE, COVO_NS_RITZ_INSIDE; csrc/step.hip:
+ * environment (COVO_FUSE_SMALL, COVO_STREAM_GEMM, COVO_FOLD_BEGIN, COVO_NS_DEFLATE, COVO_NS_MERGED; csrc/step.hip:
  * covo_default_opts); the setters below change them for THAT handle only and make it re-capture its step graphs at the next step.
  * They exist for A/B measurements and the parity tests: every pair of settings gives the same bits unless stated otherwise.
  * A handle is single-threaded (as every entry point that takes one). */
@@ -400,11 +400,6 @@ int covo_debug_set_fold_begin(covo_handle_t h, int on);
  * scale, the iterate the result was taken from, iteration counts, barrier status ... --, then the filter's iterate buffers) to
  * `out` (device or pinned host). */
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);
-/* How many of the eigh-free Sigma chain's last Chebyshev squarings / Newton-Schulz iterations run inside the two persistent
- * launches (phases separated by barriers inside the launch) instead of as one / two launches each.  Defaults: one matrix (15, 11)
- * = all but the first of each; batched launches (15, 4).  The call sets both; (64, 64) = all but the first of each, (0, 0) = every
- * phase its own launch, (-1, -1) = back to the defaults.  The result does not depend on it bit for bit. */
-int covo_debug_set_ns_tail(covo_handle_t h, int n_squarings, int n_iters);
 /* 0 switches the deflation of the bottom eigenpair in the eigh-free Sigma chain off (sigma_ns.hip: the Newton-Schulz iteration then
  * runs on B itself, ~2 iterations more); default on.  Results agree to fp64 rounding either way (not bit for bit: another
  * iteration sequence). */
@@ -418,11 +413,6 @@ int covo_debug_set_ns_merged(covo_handle_t h, int on);
  * access stays an agent-scope atomic, COH_AGENT) -- the fallback of the placement check, which no MI355X box takes by itself; 0
  * (default): as detected.  Same Sigma and L bit for bit. */
 int covo_debug_set_ns_coherence(covo_handle_t h, int force_agent);
-/* 0 makes the one-matrix Sigma chain evaluate its Rayleigh-Ritz pairs AFTER the squaring launch (ns_ritz_scan_kernel, what batches
- * and shared-device handles do) instead of inside it; default 1.  Same Sigma and L bit for bit: lambda_min is a function of the
- * matrix alone (sigma_ns.hip: ritz_decide).  2: a timing reference only -- rounds 1-4's rule (the Ritz step reads the filter's last
- * iterate and nothing else; Sigma then differs in the last bits). */
-int covo_debug_set_ns_ritz_inside(covo_handle_t h, int on);
 int covo_debug_hess_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */

@@ -671,12 +671,12 @@ def core_scalars(core, batch, count=24):
     return out.cpu().numpy()
 
 
-def test_sigma_tail_launch_is_bit_identical():
-    """The Sigma chain's squarings and Newton-Schulz iterations run inside two persistent launches whose phases are
-    separated by barriers inside the launch (sigma_ns.hip: ns_square_tail_pair_kernel, ns_iter_tail_pair_kernel; all workgroups of a matrix
-    on one XCD, sc1 loads, plain stores once the placement is verified).  Every phase its own launch, only some of them folded,
-    or all of them (the default for one matrix) must give the same Sigma and L bit for bit -- for one matrix and for a batch
-    (every matrix of a batched launch runs its tail at its own pace; 11 matrices: XCDs with one and with two of them)."""
+def test_sigma_persistent_plans_equal_phased_plan():
+    """The Sigma chain's squarings and Newton-Schulz iterations run inside persistent launches whose phases are separated by
+    barriers inside the launch (sigma_ns.hip: ns_square_tail_pair_kernel, ns_iter_tail_pair_kernel; all workgroups of a matrix on one
+    XCD, sc1 loads, plain stores once the placement is verified).  The phased plan -- every phase its own launch, what a
+    COVO_FLAG_SHARED_DEVICE handle runs -- must give the same Sigma and L bit for bit, for one matrix and for a batch (every matrix
+    of a batched launch runs its tail at its own pace; 11 matrices: XCDs with one and with two of them)."""
     from covo_mpc_amd import _lib
     lib = _lib.load_library()
     rng = np.random.default_rng(5)
@@ -687,13 +687,13 @@ def test_sigma_tail_launch_is_bit_identical():
     w = np.concatenate([np.abs(rng.standard_normal(20)) * 50, rng.standard_normal(108) * 0.05]); mats.append((Q * w) @ Q.T)
     w = np.concatenate([[-2.0, -1.1, -0.7], np.geomspace(0.01, 900.0, n - 3)]); mats.append((Q * w) @ Q.T)  # closed-loop-like
     core = SamplingCore(256, 32, 0.01, 1.0, device=DEV)
+    phased = SamplingCore(256, 32, 0.01, 1.0, device=DEV, shared_device=True)
     try:
         for Rm in mats:
             R_d = torch.from_numpy(np.ascontiguousarray(Rm)).to(DEV)
             outs = []
-            for tail in ((0, 0), (0, 2), (6, 3), (64, 64), (-1, -1)):
-                _lib.check(lib.covo_debug_set_ns_tail(core.h, *tail))
-                Sig, L = core.sigma(R_d[None], 0.5)
+            for c in (phased, core):
+                Sig, L = c.sigma(R_d[None], 0.5)
                 outs.append((Sig.clone(), L.clone()))
             assert torch.isfinite(outs[0][0]).all()
             for Sig, L in outs[1:]:
@@ -702,9 +702,8 @@ def test_sigma_tail_launch_is_bit_identical():
         batch = [mats[i % 3] * (1.0 + 0.25 * (i // 3)) + 0.1 * (i // 3) * np.eye(n) for i in range(11)]
         R_b = torch.from_numpy(np.ascontiguousarray(np.stack(batch))).to(DEV)
         outs = []
-        for tail in ((0, 0), (64, 0), (0, 64), (64, 64), (-1, -1)):
-            _lib.check(lib.covo_debug_set_ns_tail(core.h, *tail))
-            Sig, L = core.sigma(R_b, 0.5, batch=11)
+        for c in (phased, core):
+            Sig, L = c.sigma(R_b, 0.5, batch=11)
             outs.append((Sig.clone(), L.clone()))
         assert torch.isfinite(outs[0][0]).all()
         for Sig, L in outs[1:]:
@@ -725,7 +724,6 @@ def test_sigma_tail_launch_is_bit_identical():
         assert torch.equal(Sig_a, outs[0][0]) and torch.equal(L_a, outs[0][1])
     finally:
         _lib.check(lib.covo_debug_set_ns_coherence(core.h, 0))
-        _lib.check(lib.covo_debug_set_ns_tail(core.h, -1, -1))
 
 
 def test_batched_step_single_instance_and_errors():
@@ -1046,11 +1044,11 @@ def _sigma_chain_iters(core):
     return int(o[7]), int(o[6]), bool(o[29] != 0.0)  # SC_KWIN, SC_ITERS, SC_GAM
 
 
-def test_sigma_early_ritz_inside_equals_scan_equals_batch():
+def test_sigma_early_ritz_equals_scan_equals_batch():
     """lambda_min is the Ritz value of X_kwin, kwin = the first filter iterate whose bottom Ritz pair passes its own residual
     test (sigma_ns.hip: ritz_eval / ritz_decide) -- a function of the matrix alone.  The evaluations riding inside the
-    squaring launch (one matrix), the scan launch after the squarings (covo_debug_set_ns_ritz_inside(handle, 0)) and the batched chain
-    give the same Sigma and L bit for bit; on real Hessians kwin comes well before the filter's own stop."""
+    squaring launch (one matrix), the scan launch after squarings that run to their own stop (a shared-device handle: the phased
+    plan) and the batched chain give the same Sigma and L bit for bit; on real Hessians kwin comes well before the filter's own stop."""
     g = np.load(os.path.join(HERE, "golden", "hessians_r03.npz"))
     mats = [m for k in g.files for m in g[k]]
     n_real = len(mats)
@@ -1064,25 +1062,22 @@ def test_sigma_early_ritz_inside_equals_scan_equals_batch():
     mats.append(np.load(os.path.join(HERE, "golden", "sigma_nullblock_small_lmin.npy")))
     mats.append(np.eye(128))
     core = SamplingCore(256, 32, 0.01, 1.0, device=DEV)
+    scan = SamplingCore(256, 32, 0.01, 1.0, device=DEV, shared_device=True)
     out = torch.zeros(32, dtype=torch.float64, device=DEV)
     res, kwin, ksq = {}, [], []
-    try:
-        for inside in (1, 0):
-            _lib.check(core.lib.covo_debug_set_ns_ritz_inside(core.h, inside))
-            for i, Rm in enumerate(mats):
-                Sigma, L = core.sigma(torch.from_numpy(Rm[None].copy()).to(DEV), 0.5)
-                res[inside, i] = (Sigma[0].cpu().numpy(), L[0].cpu().numpy())
-                _lib.check(core.lib.covo_debug_sigma_workspace(core.h, _lib.ptr(out), 11 * 128 * 128, 32, core.stream()))
-                o = out.cpu().numpy()
-                assert o[26] == 0.0, (inside, i)  # SC_BARFAIL
-                if inside == 0:  # the scan path runs the filter to its own stop: SC_KWIN against SC_SQ
-                    kwin.append(int(o[7]))
-                    ksq.append(int(o[8]))
-                    assert 2 <= o[7] <= o[8] <= 16, (i, o[7], o[8])
-                ref = R.optimize_sigma(Rm, 0.5, 32, 4)
-                assert np.linalg.norm(res[inside, i][0] - ref) / np.linalg.norm(ref) < 1e-6, (inside, i)
-    finally:
-        _lib.check(core.lib.covo_debug_set_ns_ritz_inside(core.h, 1))
+    for inside, c in ((1, core), (0, scan)):
+        for i, Rm in enumerate(mats):
+            Sigma, L = c.sigma(torch.from_numpy(Rm[None].copy()).to(DEV), 0.5)
+            res[inside, i] = (Sigma[0].cpu().numpy(), L[0].cpu().numpy())
+            _lib.check(c.lib.covo_debug_sigma_workspace(c.h, _lib.ptr(out), 11 * 128 * 128, 32, c.stream()))
+            o = out.cpu().numpy()
+            assert o[26] == 0.0, (inside, i)  # SC_BARFAIL
+            if inside == 0:  # the scan path runs the filter to its own stop: SC_KWIN against SC_SQ
+                kwin.append(int(o[7]))
+                ksq.append(int(o[8]))
+                assert 2 <= o[7] <= o[8] <= 16, (i, o[7], o[8])
+            ref = R.optimize_sigma(Rm, 0.5, 32, 4)
+            assert np.linalg.norm(res[inside, i][0] - ref) / np.linalg.norm(ref) < 1e-6, (inside, i)
     for i in range(len(mats)):
         assert np.array_equal(res[1, i][0], res[0, i][0]) and np.array_equal(res[1, i][1], res[0, i][1]), i
     kwin, ksq = np.array(kwin), np.array(ksq)
