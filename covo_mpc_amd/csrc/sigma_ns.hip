@@ -162,44 +162,60 @@ __device__ __forceinline__ void gst(double *p, double v)
     else *p = v;
 }
 
-struct TileOps {
-    double a[8], b[8];
+// MI x MJ tiles of C = At^T . B per workgroup: block (bi, bj) is the left tiles MI bi .. MI bi + MI - 1 by the right tiles
+// MJ bj .. MJ bj + MJ - 1, and TileBlock holds this wave's K-quarter of their operands (a block shares its operands: MI + MJ tile
+// columns read for MI x MJ tiles).  Every tile is computed as one tile alone would be -- 8 MFMAs over [32 q, 32 q + 32) on an
+// accumulator of its own, the four partial tiles summed (0 + 1) + (2 + 3) -- so every tiling of a phase gives the same bits.
+template <int MI, int MJ>
+struct TileBlock {
+    double a[MI][8], b[MJ][8];
 };
-// issue the 16 operand loads of this wave's K-quarter (callers issue them BEFORE looking at any flag: every
-// launch of the chain then pays one memory latency, not one per dependent scalar)
-template <int COH = COH_NONE, class F>
-__device__ __forceinline__ void tile_load(TileOps &o, const double *A, const double *B, int ti, int tj, int lane, int kq, F f)
+// issue the operand loads of this wave's K-quarter (callers issue them BEFORE looking at any flag: every launch of the chain then
+// pays one memory latency, not one per dependent scalar).  Left and right tiles alternate: the launched 2 x 2 Y'Z' keeps 5 waves per SIMD.
+template <int COH, int MI, int MJ, class F>
+__device__ __forceinline__ void block_load(TileBlock<MI, MJ> &o, const double *At, const double *B, int bi, int bj, int lane, int kq, F f)
 {
     const int lo = lane & 15, hi = lane >> 4;
 #pragma unroll
     for (int kk = 0; kk < 8; ++kk) {
         const int k = 32 * kq + 4 * kk + hi;
-        o.a[kk] = f(gld<COH>(A + (size_t)k * SN + 16 * ti + lo), k, 16 * ti + lo);
-        o.b[kk] = f(gld<COH>(B + (size_t)k * SN + 16 * tj + lo), k, 16 * tj + lo);
+#pragma unroll
+        for (int h = 0; h < (MI > MJ ? MI : MJ); ++h) {
+            if (h < MI) o.a[h][kk] = f(gld<COH>(At + (size_t)k * SN + 16 * MI * bi + 16 * h + lo), k, 16 * MI * bi + 16 * h + lo);
+            if (h < MJ) o.b[h][kk] = f(gld<COH>(B + (size_t)k * SN + 16 * MJ * bj + 16 * h + lo), k, 16 * MJ * bj + 16 * h + lo);
+        }
     }
 }
-__device__ __forceinline__ f64x4 tile_mma(const TileOps &o)
-{
-    f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[kk], o.b[kk], acc, 0, 0, 0);
-    return acc;
-}
-// sums the four K-quarters; wave wv returns the tile element (row, col) = ((lane>>4) + 4 wv, lane&15) it will store
-__device__ __forceinline__ double tile_reduce(const f64x4 &acc, double (*red)[4][64], int wv, int lane)
+// tile t = MJ ia + ib of the block: this wave's element (row (lane >> 4) + 4 wv, col lane & 15) of it in v[t], summed over the four
+// K-quarters through red[t][wv][r][lane] (skip0: tile 0 is not wanted, v[0] is then meaningless)
+template <int MI, int MJ>
+__device__ __forceinline__ void block_mma_reduce(const TileBlock<MI, MJ> &o, double (*red)[4][4][64], int wv, int lane, double (&v)[MI * MJ],
+                                                 bool skip0 = false)
 {
 #pragma unroll
-    for (int r = 0; r < 4; ++r) red[wv][r][lane] = acc[r];
+    for (int t = 0; t < MI * MJ; ++t) {
+        if (t == 0 && skip0) continue;  // (uniform)
+        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[t / MJ][kk], o.b[t % MJ][kk], acc, 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) red[t][wv][r][lane] = acc[r];
+    }
     __syncthreads();
-    return (red[0][wv][lane] + red[1][wv][lane]) + (red[2][wv][lane] + red[3][wv][lane]);
+#pragma unroll
+    for (int t = 0; t < MI * MJ; ++t) v[t] = (red[t][0][wv][lane] + red[t][1][wv][lane]) + (red[t][2][wv][lane] + red[t][3][wv][lane]);
 }
-// workgroup sum (256 threads) of one double per lane, fixed order; valid in every thread
-__device__ __forceinline__ double wg_sum4(double v, double *part, int wv, int lane)
+// the per-tile slot epilogue (|X|_F^2 into SC_SQN, |Z Y - I|_F^2 into SC_ERR): every wave sums its lanes' share x of tile t ...
+__device__ __forceinline__ void tile_part(double (*part)[4], int t, int wv, int lane, double x)
 {
-    v = wr::wave64_allsum(v);
-    if (lane == 0) part[wv] = v;
-    __syncthreads();
-    return (part[0] + part[1]) + (part[2] + part[3]);
+    const double ws = wr::wave64_allsum(x);
+    if (lane == 0) part[t][wv] = ws;
+}
+// ... and, behind a barrier, one thread per tile stores the tile's sum (0 + 1) + (2 + 3) into its slot
+template <int COH>
+__device__ __forceinline__ void tile_slot(double *slot, const double (*part)[4], int t)
+{
+    gst<COH>(slot, (part[t][0] + part[t][1]) + (part[t][2] + part[t][3]));
 }
 // sum of n <= 64 slots, fixed order; valid in every lane
 __device__ __forceinline__ double slot_sum(const double *__restrict__ p, int n, int lane)
@@ -224,6 +240,13 @@ __device__ __forceinline__ bool ns_block(int batch, int &b, int &w)
     return b < batch;
 }
 static inline dim3 ns_grid(int tiles, int batch) { return dim3(tiles, batch == 1 ? 1 : (batch + 7) / 8 * 8); }
+// A launched phase of a batch (gridDim.y > 1) reads its "done" flag BEFORE its operands: most matrices are done long before the slowest,
+// and a finished one must not pull its operands through the L2s again (round 4).  Elsewhere the operand loads go first: one round trip.
+template <int COH>
+__device__ __forceinline__ bool ns_batch_done(const double *s, int flag)
+{
+    return COH == COH_NONE && gridDim.y > 1 && s[flag] != 0.0;
+}
 
 // The squaring stage (a filter iteration: self-correcting) works on exactly symmetric matrices: only tiles
 // with ti >= tj are computed and every value is stored together with its mirror image (36 tiles).
@@ -337,31 +360,53 @@ __device__ __forceinline__ void ns_square_first_stats(double *s, int w, int tid,
     }
 }
 
-// ---- one doubling of the Chebyshev degree: Xout = Xin^2 / |Xin|_F^2 - I / t_out, t_out = 2 t_in^2 |Xin|_F^2 (36 lower
-// tiles); |Xout|_F^2 partials go to slot row step+1, t_out to slot 63 of that row.
-// FIRST: Xin is A and the operand is Y0 = alpha I - beta A (see the header), t_in = 1.
-// Returns false when the filter is found stationary (nothing was written).  Workgroup w of matrix b.
-template <bool FIRST, int COH>
-__device__ __forceinline__ bool ns_square_body(const double *Xin, double *Xout, double *scall, int step, int b, int w,
-                                               double (*red)[4][64], double *part)
+// ---- one doubling of the Chebyshev degree: Xout = Xin^2 / |Xin|_F^2 - I / t_out, t_out = 2 t_in^2 |Xin|_F^2; |Xout|_F^2 partials go to
+// slot row step+1, t_out to slot 63 of that row.  FIRST: Xin is A and the operand is Y0 = alpha I - beta A (see the header), t_in = 1.
+// MI = 2 (round 4): the lower triangle's 36 tiles as 20 workgroups -- for m = 0..3 the pairs {(2m, tj), (2m + 1, tj)}, tj = 0..2m,
+// which share their right operand X(:, tj), and the diagonal tile (2m + 1, 2m + 1) alone (it runs the pair's code with tile 0 -- an
+// upper tile -- left out).  0.77 MB of operands per squaring instead of 1.15, 20 workgroups at a barrier instead of 36.
+// MI = 1: one tile per workgroup, 36 workgroups -- the launched squarings of ONE matrix, which are latency: pairs cost them ~8 us per
+// chain.  Returns false when the filter is found stationary or stopped (nothing was written).  X, O, s: this matrix's.
+constexpr int NS_SQ_PAIR_WG = 20;
+// Inside the persistent launches the evaluations ride along: SC_SQ_DONE is raised from OUTSIDE the chain, at any time -- the chain's
+// workgroups do not look at it themselves (they would disagree within a phase); workgroup 0 passes it on through the barrier
+// (ns_flag_barrier).  Only launched squarings (COH_NONE) read it.
+template <bool FIRST, int COH, int MI = 2>
+__device__ __forceinline__ bool ns_square_pair_body(const double *X, double *O, double *s, int step, int w,
+                                                    double (*redp)[4][4][64], double (*partp)[4])
 {
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const double *X = Xin + (size_t)b * SN * SN;
-    double *O = Xout + (size_t)b * SN * SN;
-    double *s = scall + (size_t)b * SC_COUNT;
     double nrm, t_in = 1.0, alpha = 0.0, beta = 0.0;
-    if (FIRST) ns_square_first_stats<COH>(s, w, tid, lane, wv, &red[0][0][0], alpha, beta, nrm);
-    int ti, tj;
-    tri_tile(w, ti, tj);
-    // batched launches (gridDim.y > 1: the env-batched step, covo-offline's table): every squaring the cap allows is launched for
-    // every matrix, and most matrices are done long before the slowest -- a finished one must not pull its 32 KB of operands
-    // through the L2s again (round 4: the flag first there; batch 1 keeps the operand loads ahead of the flag, one round trip)
-    if (!FIRST && !COH && gridDim.y > 1 && s[SC_SQ_DONE] != 0.0) return false;
-    TileOps ops;
-    if (FIRST) tile_load<COH>(ops, X, X, ti, tj, lane, wv, LoadAffine{alpha, beta});
-    else tile_load<COH>(ops, X, X, ti, tj, lane, wv, LoadPlain{});
+    // the tiles (MI m + h, tj), h < MI.  MI = 2: w -> (m, local), group m holds 2m + 2 workgroups (offsets 0, 2, 6, 12)
+    int m, tj;
+    bool single = false;
+    if (MI == 2) {
+        m = (w >= 12) ? 3 : (w >= 6) ? 2 : (w >= 2) ? 1 : 0;
+        const int local = w - m * (m + 1);
+        single = local == 2 * m + 1;
+        tj = single ? 2 * m + 1 : local;
+    } else {
+        tri_tile(w, m, tj);
+    }
+    if (!FIRST && ns_batch_done<COH>(s, SC_SQ_DONE)) return false;
+    TileBlock<MI, 1> ops;
+    // (the operands of A are asked for BEFORE the statistics that make Y0 = alpha I - beta A out of them: the chain's first round
+    // trip -- A comes from memory, the Hessian's launches wrote it from other XCDs -- runs under the statistics' two barriers)
+    block_load<COH>(ops, X, X, m, tj, lane, wv, LoadPlain{});
+    if (FIRST) {
+        ns_square_first_stats<COH>(s, w, tid, lane, wv, &redp[0][0][0][0], alpha, beta, nrm);
+        const LoadAffine f{alpha, beta};
+        const int lo = lane & 15, hi = lane >> 4;
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            const int k = 32 * wv + 4 * kk + hi;
+#pragma unroll
+            for (int h = 0; h < MI; ++h) ops.a[h][kk] = f(ops.a[h][kk], k, 16 * MI * m + 16 * h + lo);
+            ops.b[0][kk] = f(ops.b[0][kk], k, 16 * tj + lo);
+        }
+    }
     if (!FIRST) {
-        const double done = gld<COH>(s + SC_SQ_DONE);
+        const double done = (COH == COH_NONE) ? gld<COH>(s + SC_SQ_DONE) : 0.0;
         const double p1 = (lane < NS_TILES) ? gld<COH>(s + SC_SQN + step * 64 + lane) : 0.0;
         const double p0 = (lane < NS_TILES && step >= 2) ? gld<COH>(s + SC_SQN + (step - 1) * 64 + lane) : 0.0;
         t_in = gld<COH>(s + SC_SQN + step * 64 + 63);
@@ -386,24 +431,36 @@ __device__ __forceinline__ bool ns_square_body(const double *Xin, double *Xout, 
         gst<COH>(s + SC_SQ, (double)(step + 1));
         gst<COH>(s + SC_SQN + (step + 1) * 64 + 63, t_out);
     }
-    const f64x4 acc = tile_mma(ops);
-    const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-    const double v = tile_reduce(acc, red, wv, lane) * (1.0 / nrm) - ((row == col) ? inv_t : 0.0);
-    store_sym<COH>(O, row, col, v);
-    const double tot = wg_sum4((row > col) ? 2.0 * v * v : ((row == col) ? v * v : 0.0), part, wv, lane);
-    if (tid == 0) gst<COH>(s + SC_SQN + (step + 1) * 64 + w, tot);
+    double pv[MI];
+    block_mma_reduce(ops, redp, wv, lane, pv, single);
+#pragma unroll
+    for (int h = 0; h < MI; ++h) {
+        if (h == 0 && single) continue;  // (uniform)
+        const int ti = MI * m + h;
+        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
+        const double v = pv[h] * (1.0 / nrm) - ((row == col) ? inv_t : 0.0);
+        store_sym<COH>(O, row, col, v);
+        tile_part(partp, h, wv, lane, (row > col) ? 2.0 * v * v : ((row == col) ? v * v : 0.0));
+    }
+    __syncthreads();
+    if (tid < MI && !(tid == 0 && single)) {
+        const int ti = MI * m + tid;
+        tile_slot<COH>(s + SC_SQN + (step + 1) * 64 + ti * (ti + 1) / 2 + tj, partp, tid);
+    }
     return true;
 }
 
-template <bool FIRST>
+// the shared-device plan's squarings, one launch each: grid (NS_SQ_PAIR_WG or NS_TILES workgroups, batch)
+template <bool FIRST, int MI>
 __global__ __launch_bounds__(256) void ns_square_kernel(const double *__restrict__ Xin, double *__restrict__ Xout,
                                                         double *__restrict__ scall, int step, int batch)
 {
-    __shared__ double red[4][4][64];
-    __shared__ double part[4];
+    __shared__ double redp[MI][4][4][64];
+    __shared__ double partp[MI][4];
     int b, w;
     if (!ns_block(batch, b, w)) return;
-    (void)ns_square_body<FIRST, COH_NONE>(Xin, Xout, scall, step, b, w, red, part);
+    const size_t off = (size_t)b * SN * SN;
+    (void)ns_square_pair_body<FIRST, COH_NONE, MI>(Xin + off, Xout + off, scall + (size_t)b * SC_COUNT, step, w, redp, partp);
 }
 
 // ---- Rayleigh-Ritz on the RITZ largest-diagonal columns of X_k, the filter after k squarings: lambda_min(A), delta; then the
@@ -1055,82 +1112,6 @@ __device__ __forceinline__ bool ns_converged(double *s, int iter, int lane, bool
     return false;
 }
 
-// ---- Newton-Schulz step k >= 1, part 1:  T = a_k I + b_k Z.Y  (64 tiles; T and T^T are stored).
-// Returns false when the iteration has converged (nothing was written).  Workgroup w of matrix b.
-template <int COH>
-__device__ __forceinline__ bool ns_T_body(const double *Yall, const double *Ztall, double *Tall, double *Ttall, double *scall,
-                                          int iter, int b, int w, double (*red)[4][64], double *part)
-{
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double *s = scall + (size_t)b * SC_COUNT;
-    const size_t off = (size_t)b * SN * SN;
-    const int ti = w >> 3, tj = w & 7;
-    if (!COH && gridDim.y > 1 && s[SC_NS_DONE] != 0.0) return false;  // batched: the flag before the operands (see ns_square_body)
-    TileOps ops;
-    tile_load<COH>(ops, Ztall + off, Yall + off, ti, tj, lane, wv, LoadPlain{});  // (Z^T)^T . Y = Z.Y
-    const double a = s[SC_COEF + 2 * iter], bq = s[SC_COEF + 2 * iter + 1];  // (the table: ns_first_elem_kernel's extra workgroup)
-    if (ns_converged<COH>(s, iter, lane, w == 0 && tid == 0)) return false;  // Y, Z are final
-    const f64x4 acc = tile_mma(ops);
-    const double p = tile_reduce(acc, red, wv, lane);
-    const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-    store_both<COH>(Tall + off, Ttall + off, row, col, fma(bq, p, (row == col) ? a : 0.0));
-    const double d = p - ((row == col) ? 1.0 : 0.0);
-    const double tot = wg_sum4(d * d, part, wv, lane);
-    if (tid == 0) gst<COH>(s + SC_ERR + iter * 64 + w, tot);  // |Z Y - I|_F^2 partial
-    return true;
-}
-
-// ---- part 2:  Y' = Y.T (tiles 0..63),  Z' = T.Z (tiles 64..127); each with its transpose.  Workgroup wx in 0..127.
-template <int COH>
-__device__ __forceinline__ bool ns_YZ_body(const double *Ytall, const double *Zall, const double *Tall, const double *Ttall,
-                                           double *Yout, double *Ytout, double *Zout, double *Ztout, double *scall, int iter,
-                                           int zbuf_out, int b, int wx, double (*red)[4][64])
-{
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double *s = scall + (size_t)b * SC_COUNT;
-    const bool isZ = wx >= 64;
-    const int w = wx & 63;
-    const size_t off = (size_t)b * SN * SN;
-    const int ti = w >> 3, tj = w & 7;
-    // Y' = Y.T : left factor Y -> pass Y^T;   Z' = T.Z : left factor T -> pass T^T
-    if (!COH && gridDim.y > 1 && s[SC_NS_DONE] != 0.0) return false;  // batched: the flag before the operands (see ns_square_body)
-    TileOps ops;
-    tile_load<COH>(ops, (isZ ? Ttall : Ytall) + off, (isZ ? Zall : Tall) + off, ti, tj, lane, wv, LoadPlain{});
-    if (ns_converged<COH>(s, iter, lane, false)) return false;  // part 1 of this iteration raised the flag
-    if (wx == 0 && tid == 0) {
-        gst<COH>(s + SC_ZBUF, (double)zbuf_out);  // which Z buffer holds the newest iterate
-        gst<COH>(s + SC_ITERS, (double)(iter + 1));
-    }
-    const f64x4 acc = tile_mma(ops);
-    const double v = tile_reduce(acc, red, wv, lane);
-    const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-    store_both<COH>((isZ ? Zout : Yout) + off, (isZ ? Ztout : Ytout) + off, row, col, v);
-    return true;
-}
-
-__global__ __launch_bounds__(256) void ns_T_kernel(const double *__restrict__ Yall, const double *__restrict__ Ztall,
-                                                   double *__restrict__ Tall, double *__restrict__ Ttall,
-                                                   double *__restrict__ scall, int iter, int batch)
-{
-    __shared__ double red[4][4][64];
-    __shared__ double part[4];
-    int b, w;
-    if (!ns_block(batch, b, w)) return;
-    (void)ns_T_body<COH_NONE>(Yall, Ztall, Tall, Ttall, scall, iter, b, w, red, part);
-}
-
-__global__ __launch_bounds__(256) void ns_YZ_kernel(const double *__restrict__ Ytall, const double *__restrict__ Zall,
-                                                    const double *__restrict__ Tall, const double *__restrict__ Ttall,
-                                                    double *__restrict__ Yout, double *__restrict__ Ytout,
-                                                    double *__restrict__ Zout, double *__restrict__ Ztout,
-                                                    double *__restrict__ scall, int iter, int zbuf_out, int batch)
-{
-    __shared__ double red[4][4][64];
-    int b, w;
-    if (!ns_block(batch, b, w)) return;
-    (void)ns_YZ_body<COH_NONE>(Ytall, Zall, Tall, Ttall, Yout, Ytout, Zout, Ztout, scall, iter, zbuf_out, b, w, red);
-}
-
 // ---- "iteration 0" of the launch-per-phase and the batched paths: Y1, Z1 (and their transposes) written out element-wise (NsFirst:
 // no product) -- grid (64 tiles + one workgroup for the coefficient table, batch); the one-matrix persistent launch does the same as
 // its first phase.  Same functors, same bits.
@@ -1160,115 +1141,105 @@ __global__ __launch_bounds__(256) void ns_first_elem_kernel(const double *__rest
     store_both(Zout + off, Ztout + off, row, col, LoadZ1{f}(av, row, col));
 }
 
-// ---- batched launches of the Newton-Schulz phases: one workgroup = a 2 x 2 block of 16 x 16 tiles (round 4).  With one tile per
-// workgroup a batched phase moves 32 KB of operands per tile through the CU's L1 port (Y.T and T.Z at 32 matrices: 4 096
-// workgroups, 134 MB = as many port cycles as the fp64 MFMAs take) -- a 2 x 2 block shares its operands (64 KB for four tiles) and
-// needs a quarter of the workgroups.  EVERY tile is computed exactly as the one-tile bodies compute it -- wave q takes the
-// K-quarter [32 q, 32 q + 32), 8 MFMAs on an accumulator of its own, the four partial tiles summed (0 + 1) + (2 + 3), the
-// per-tile slots filled by the same reductions -- so a matrix of a batch still equals the same matrix alone bit for bit.
-struct QuadOps {
-    double a[2][8], b[2][8];
-};
-template <int COH = COH_NONE, class F>
-__device__ __forceinline__ void quad_load(QuadOps &o, const double *A, const double *B, int mi, int mj, int lane, int kq, F f)
+// ---- Newton-Schulz step k >= 1, part 1:  T = a_k I + b_k Z.Y  (T and T^T are stored), workgroup w forming an MI x MJ block of tiles
+// (launched: as part 2).  Returns false when the iteration has converged (nothing was written).  Y, Zt, T, Tt, s: this matrix's.
+// Persistent launches: 2 x 1 (round 4), the two tiles share their right operand: 48 KB instead of 64 per two tiles, and what a phase of
+// the confined launch waits for is ONE L2 (profiles/r04_sigma_batch_l2_counters.log: 2 MB of operands for part 1, 4 MB for part 2,
+// against 16 channels x 64 B/clk) -- the MFMA time does not move, and the barrier has half the workgroups.
+template <int COH, int MI, int MJ>
+__device__ __forceinline__ bool ns_T_block_body(const double *Y, const double *Zt, double *T, double *Tt, double *s, int iter, int w,
+                                                double (*red)[4][4][64], double (*part)[4])
 {
-    const int lo = lane & 15, hi = lane >> 4;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    constexpr int NJ = 8 / MJ;  // blocks per row of tiles
+    const int bi = w / NJ, bj = w % NJ;
+    if (ns_batch_done<COH>(s, SC_NS_DONE)) return false;
+    TileBlock<MI, MJ> ops;
+    block_load<COH>(ops, Zt, Y, bi, bj, lane, wv, LoadPlain{});  // (Z^T)^T . Y = Z.Y
+    // (the table: ns_first_elem_kernel's extra workgroup, or a workgroup of the one-matrix persistent launch)
+    const double a = gld<COH>(s + SC_COEF + 2 * iter), bq = gld<COH>(s + SC_COEF + 2 * iter + 1);
+    if (ns_converged<COH>(s, iter, lane, w == 0 && tid == 0)) return false;  // Y, Z are final
+    double v[MI * MJ];
+    block_mma_reduce(ops, red, wv, lane, v);
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-        const int k = 32 * kq + 4 * kk + hi;
-#pragma unroll
-        for (int h = 0; h < 2; ++h) {
-            o.a[h][kk] = f(gld<COH>(A + (size_t)k * SN + 32 * mi + 16 * h + lo), k, 32 * mi + 16 * h + lo);
-            o.b[h][kk] = f(gld<COH>(B + (size_t)k * SN + 32 * mj + 16 * h + lo), k, 32 * mj + 16 * h + lo);
-        }
+    for (int t = 0; t < MI * MJ; ++t) {
+        const int ti = MI * bi + t / MJ, tj = MJ * bj + t % MJ;
+        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
+        store_both<COH>(T, Tt, row, col, fma(bq, v[t], (row == col) ? a : 0.0));
+        const double d = v[t] - ((row == col) ? 1.0 : 0.0);
+        tile_part(part, t, wv, lane, d * d);
     }
-}
-// the four tiles (ia, ib): this wave's element (row (lane >> 4) + 4 wv, col lane & 15) of each, v[2 ia + ib]
-__device__ __forceinline__ void quad_mma_reduce(const QuadOps &o, double (*redq)[4][4][64], int wv, int lane, double v[4])
-{
-#pragma unroll
-    for (int ia = 0; ia < 2; ++ia)
-#pragma unroll
-        for (int ib = 0; ib < 2; ++ib) {
-            f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-            for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[ia][kk], o.b[ib][kk], acc, 0, 0, 0);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) redq[2 * ia + ib][wv][r][lane] = acc[r];
-        }
     __syncthreads();
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-        v[t] = (redq[t][0][wv][lane] + redq[t][1][wv][lane]) + (redq[t][2][wv][lane] + redq[t][3][wv][lane]);
+    if (tid < MI * MJ) tile_slot<COH>(s + SC_ERR + iter * 64 + (MI * bi + tid / MJ) * 8 + MJ * bj + tid % MJ, part, tid);  // |Z Y - I|_F^2
+    return true;
 }
 
-// part 1 (ns_T_body): grid (16 blocks, batch)
+// ---- part 2:  Y' = Y.T (the first NB = 64 / (MI MJ) workgroups),  Z' = T.Z (the next NB), each with its transpose, workgroup w forming
+// an MI x MJ block of tiles: 2 x 2 in the persistent launches and in batches, single tiles in the launches of one matrix.
+//  * launched, batched (round 4): one tile per workgroup moves 32 KB of operands per tile through the CU's L1 port (134 MB at 32
+//    matrices, as many port cycles as the fp64 MFMAs take); a 2 x 2 block shares its operands.  The launches of ONE matrix are latency:
+//    four tiles per workgroup cost its chain ~27 us.
+//  * persistent (round 5): one product of four tiles instead of two pair products one after the other.  The phase waits for the XCD's
+//    ONE L2: pairs pull 4 MB of operands through it, blocks 2 MB; the MFMA count per wave is the same.  Phase stamps, one matrix: 3.9
+//    us against 4.2; whole step 173.3 against 175.2 us.  (All 48 operand loads of two pair products in flight together: no difference.)
+// Returns false when the iteration has converged (nothing was written).  red: MI MJ x 4 x 4 x 64 doubles of LDS.
+template <int COH, int MI, int MJ>
+__device__ __forceinline__ bool ns_YZ_block_body(const double *Yt, const double *Z, const double *T, const double *Tt, double *Yo, double *Yto,
+                                                 double *Zo, double *Zto, double *s, int iter, int zbuf_out, int w,
+                                                 double (*red)[4][4][64])
+{
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    constexpr int NB = 64 / (MI * MJ), NJ = 8 / MJ;  // blocks per product, per row of tiles
+    const bool isZ = w >= NB;
+    const int q = w & (NB - 1), bi = q / NJ, bj = q % NJ;
+    if (ns_batch_done<COH>(s, SC_NS_DONE)) return false;
+    TileBlock<MI, MJ> ops;
+    // Y' = Y.T : left factor Y -> pass Y^T;   Z' = T.Z : left factor T -> pass T^T
+    block_load<COH>(ops, isZ ? Tt : Yt, isZ ? Z : T, bi, bj, lane, wv, LoadPlain{});
+    if (ns_converged<COH>(s, iter, lane, false)) return false;  // part 1 of this iteration raised the flag
+    if (w == 0 && tid == 0) {
+        gst<COH>(s + SC_ZBUF, (double)zbuf_out);  // which Z buffer holds the newest iterate
+        gst<COH>(s + SC_ITERS, (double)(iter + 1));
+    }
+    double v[MI * MJ];
+    block_mma_reduce(ops, red, wv, lane, v);
+#pragma unroll
+    for (int t = 0; t < MI * MJ; ++t) {
+        const int ti = MI * bi + t / MJ, tj = MJ * bj + t % MJ;
+        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
+        store_both<COH>(isZ ? Zo : Yo, isZ ? Zto : Yto, row, col, v[t]);
+    }
+    return true;
+}
+
+// the launched iterations (the batched and the shared-device plans) on MI x MJ blocks: part 1 on grid (64 / (MI MJ) blocks, batch),
+// part 2 on grid (128 / (MI MJ) blocks, batch)
+template <int MI, int MJ>
 __global__ __launch_bounds__(256) void ns_T_quad_kernel(const double *__restrict__ Yall, const double *__restrict__ Ztall,
                                                         double *__restrict__ Tall, double *__restrict__ Ttall,
                                                         double *__restrict__ scall, int iter, int batch)
 {
-    __shared__ double redq[4][4][4][64];
-    __shared__ double partq[4][4];
+    __shared__ double red[MI * MJ][4][4][64];
+    __shared__ double part[MI * MJ][4];
     int b, w;
     if (!ns_block(batch, b, w)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double *s = scall + (size_t)b * SC_COUNT;
     const size_t off = (size_t)b * SN * SN;
-    const int mi = w >> 2, mj = w & 3;
-    if (s[SC_NS_DONE] != 0.0) return;  // the flag before the operands (see ns_square_body)
-    QuadOps ops;
-    quad_load(ops, Ztall + off, Yall + off, mi, mj, lane, wv, LoadPlain{});  // (Z^T)^T . Y = Z.Y
-    const double a = s[SC_COEF + 2 * iter], bq = s[SC_COEF + 2 * iter + 1];
-    if (ns_converged<COH_NONE>(s, iter, lane, w == 0 && tid == 0)) return;
-    double p[4];
-    quad_mma_reduce(ops, redq, wv, lane, p);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int ti = 2 * mi + (t >> 1), tj = 2 * mj + (t & 1);
-        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-        store_both(Tall + off, Ttall + off, row, col, fma(bq, p[t], (row == col) ? a : 0.0));
-        const double d = p[t] - ((row == col) ? 1.0 : 0.0);
-        const double ws = wr::wave64_allsum(d * d);
-        if (lane == 0) partq[t][wv] = ws;
-    }
-    __syncthreads();
-    if (tid < 4) {
-        const int ti = 2 * mi + (tid >> 1), tj = 2 * mj + (tid & 1);
-        s[SC_ERR + iter * 64 + ti * 8 + tj] = (partq[tid][0] + partq[tid][1]) + (partq[tid][2] + partq[tid][3]);
-    }
+    (void)ns_T_block_body<COH_NONE, MI, MJ>(Yall + off, Ztall + off, Tall + off, Ttall + off, scall + (size_t)b * SC_COUNT, iter, w, red,
+                                            part);
 }
-
-// part 2 (ns_YZ_body): grid (32 blocks, batch): blocks 0..15 of Y' = Y.T, 16..31 of Z' = T.Z
+template <int MI, int MJ>
 __global__ __launch_bounds__(256) void ns_YZ_quad_kernel(const double *__restrict__ Ytall, const double *__restrict__ Zall,
                                                          const double *__restrict__ Tall, const double *__restrict__ Ttall,
                                                          double *__restrict__ Yout, double *__restrict__ Ytout,
                                                          double *__restrict__ Zout, double *__restrict__ Ztout,
                                                          double *__restrict__ scall, int iter, int zbuf_out, int batch)
 {
-    __shared__ double redq[4][4][4][64];
-    int b, wx;
-    if (!ns_block(batch, b, wx)) return;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double *s = scall + (size_t)b * SC_COUNT;
-    const bool isZ = wx >= 16;
-    const int w = wx & 15, mi = w >> 2, mj = w & 3;
+    __shared__ double red[MI * MJ][4][4][64];
+    int b, w;
+    if (!ns_block(batch, b, w)) return;
     const size_t off = (size_t)b * SN * SN;
-    if (s[SC_NS_DONE] != 0.0) return;
-    QuadOps ops;
-    quad_load(ops, (isZ ? Ttall : Ytall) + off, (isZ ? Zall : Tall) + off, mi, mj, lane, wv, LoadPlain{});
-    if (ns_converged<COH_NONE>(s, iter, lane, false)) return;  // part 1 of this iteration raised the flag
-    if (wx == 0 && tid == 0) {
-        s[SC_ZBUF] = (double)zbuf_out;
-        s[SC_ITERS] = (double)(iter + 1);
-    }
-    double v[4];
-    quad_mma_reduce(ops, redq, wv, lane, v);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int ti = 2 * mi + (t >> 1), tj = 2 * mj + (t & 1);
-        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-        store_both((isZ ? Zout : Yout) + off, (isZ ? Ztout : Ytout) + off, row, col, v[t]);
-    }
+    (void)ns_YZ_block_body<COH_NONE, MI, MJ>(Ytall + off, Zall + off, Tall + off, Ttall + off, Yout + off, Ytout + off, Zout + off,
+                                             Ztout + off, scall + (size_t)b * SC_COUNT, iter, zbuf_out, w, red);
 }
 
 // ---- the chain's dependent phases inside ONE persistent launch (batch 1 only: the launch's workgroups must be
@@ -1380,118 +1351,6 @@ struct NsBufs {
     const double *A, *X1;  // iteration 1 forms its operands from the chain's input and the filter's first iterate (NsFirst)
 };
 
-// ---- the iteration tail on PAIRS of tiles (round 4): workgroup w of 32 forms the tiles (2 p, tj) and (2 p + 1, tj), p = w >> 3,
-// tj = w & 7, of T, then of Y' and of Z'.  The two tiles share their right operand: 48 KB instead of 64 per two tiles, and what a
-// phase of the confined launch waits for is ONE L2 (profiles/r04_sigma_batch_l2_counters.log: 2 MB of operands for part 1, 4 MB
-// for part 2, against 16 channels x 64 B/clk) -- the MFMA time does not move (32 workgroups x one wave per SIMD x 16 / 32 MFMAs =
-// 64 x two waves x 8 / 16), and the barrier has half the workgroups.  Per tile the arithmetic of ns_T_body / ns_YZ_body.
-struct PairOps {
-    double a[2][8], b[8];
-};
-template <int COH, class F>
-__device__ __forceinline__ void pair_load(PairOps &o, const double *A, const double *B, int p, int tj, int lane, int kq, F f)
-{
-    const int lo = lane & 15, hi = lane >> 4;
-#pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-        const int k = 32 * kq + 4 * kk + hi;
-        o.a[0][kk] = f(gld<COH>(A + (size_t)k * SN + 32 * p + lo), k, 32 * p + lo);
-        o.a[1][kk] = f(gld<COH>(A + (size_t)k * SN + 32 * p + 16 + lo), k, 32 * p + 16 + lo);
-        o.b[kk] = f(gld<COH>(B + (size_t)k * SN + 16 * tj + lo), k, 16 * tj + lo);
-    }
-}
-// (skip0: tile 0 of the pair is not wanted; v[0] is then meaningless)
-__device__ __forceinline__ void pair_mma_reduce(const PairOps &o, double (*redp)[4][4][64], int wv, int lane, double v[2],
-                                                bool skip0 = false)
-{
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (h == 0 && skip0) continue;  // (uniform)
-        f64x4 acc = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[h][kk], o.b[kk], acc, 0, 0, 0);
-#pragma unroll
-        for (int r = 0; r < 4; ++r) redp[h][wv][r][lane] = acc[r];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int h = 0; h < 2; ++h) v[h] = (redp[h][0][wv][lane] + redp[h][1][wv][lane]) + (redp[h][2][wv][lane] + redp[h][3][wv][lane]);
-}
-// ---- the squaring launch on pairs (round 4): the lower triangle's 36 tiles as 20 workgroups -- for m = 0..3 the pairs
-// {(2m, tj), (2m + 1, tj)}, tj = 0..2m, which share their right operand X(:, tj), and the diagonal tile (2m + 1, 2m + 1) alone
-// (it runs the pair's code with tile 0 -- an upper tile -- left out).  0.77 MB of operands per squaring instead of 1.15, 20
-// workgroups at the barrier instead of 36.  Per tile the arithmetic of ns_square_body.
-constexpr int NS_SQ_PAIR_WG = 20;
-// The evaluations ride in the launch: SC_SQ_DONE is raised from OUTSIDE the chain, at any time -- the chain's workgroups do not look
-// at it themselves (they would disagree within a phase); workgroup 0 passes it on through the barrier (ns_flag_barrier)
-template <bool FIRST, int COH>
-__device__ __forceinline__ bool ns_square_pair_body(const double *X, double *O, double *s, int step, int w,
-                                                    double (*redp)[4][4][64], double (*partp)[4])
-{
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    double nrm, t_in = 1.0, alpha = 0.0, beta = 0.0;
-    // w -> (m, local): group m holds 2m + 2 workgroups (offsets 0, 2, 6, 12)
-    const int m = (w >= 12) ? 3 : (w >= 6) ? 2 : (w >= 2) ? 1 : 0;
-    const int local = w - m * (m + 1);
-    const bool single = local == 2 * m + 1;
-    const int tj = single ? 2 * m + 1 : local;
-    PairOps ops;
-    // (the operands of A are asked for BEFORE the statistics that make Y0 = alpha I - beta A out of them: the chain's first round
-    // trip -- A comes from memory, the Hessian's launches wrote it from other XCDs -- runs under the statistics' two barriers)
-    pair_load<COH>(ops, X, X, m, tj, lane, wv, LoadPlain{});
-    if (FIRST) {
-        ns_square_first_stats<COH>(s, w, tid, lane, wv, &redp[0][0][0][0], alpha, beta, nrm);
-        const LoadAffine f{alpha, beta};
-        const int lo = lane & 15, hi = lane >> 4;
-#pragma unroll
-        for (int kk = 0; kk < 8; ++kk) {
-            const int k = 32 * wv + 4 * kk + hi;
-            ops.a[0][kk] = f(ops.a[0][kk], k, 32 * m + lo);
-            ops.a[1][kk] = f(ops.a[1][kk], k, 32 * m + 16 + lo);
-            ops.b[kk] = f(ops.b[kk], k, 16 * tj + lo);
-        }
-    }
-    if (!FIRST) {
-        const double p1 = (lane < NS_TILES) ? gld<COH>(s + SC_SQN + step * 64 + lane) : 0.0;
-        const double p0 = (lane < NS_TILES && step >= 2) ? gld<COH>(s + SC_SQN + (step - 1) * 64 + lane) : 0.0;
-        t_in = gld<COH>(s + SC_SQN + step * 64 + 63);
-        nrm = wr::wave64_allsum(p1);
-        if (step >= 2 && t_in > NS_SQ_TGUARD) {
-            const double prev = wr::wave64_allsum(p0);
-            if (fabs(nrm - prev) <= NS_SQ_TOL * nrm) {
-                if (w == 0 && tid == 0) {
-                    gst<COH>(s + SC_SQ_FINAL, (double)step);  // X_step is the filter's last iterate
-                    gst<COH>(s + SC_SQ_DONE, 1.0);
-                }
-                return false;
-            }
-        }
-    }
-    const double t_out = 2.0 * t_in * t_in * nrm;  // overflows to +inf once the filter has separated: 1 / t_out = 0
-    const double inv_t = 1.0 / t_out;
-    if (w == 0 && tid == 0) {
-        gst<COH>(s + SC_SQ, (double)(step + 1));
-        gst<COH>(s + SC_SQN + (step + 1) * 64 + 63, t_out);
-    }
-    double pv[2];
-    pair_mma_reduce(ops, redp, wv, lane, pv, single);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        if (h == 0 && single) continue;  // (uniform)
-        const int ti = 2 * m + h;
-        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-        const double v = pv[h] * (1.0 / nrm) - ((row == col) ? inv_t : 0.0);
-        store_sym<COH>(O, row, col, v);
-        const double ws = wr::wave64_allsum((row > col) ? 2.0 * v * v : ((row == col) ? v * v : 0.0));
-        if (lane == 0) partp[h][wv] = ws;
-    }
-    __syncthreads();
-    if (tid < 2 && !(tid == 0 && single)) {
-        const int ti = 2 * m + tid;
-        gst<COH>(s + SC_SQN + (step + 1) * 64 + ti * (ti + 1) / 2 + tj, (partp[tid][0] + partp[tid][1]) + (partp[tid][2] + partp[tid][3]));
-    }
-    return true;
-}
 constexpr int NS_SQ_EVAL_WG = 8;        // evaluating workgroups of the one-matrix launch: an evaluation takes three squarings
 constexpr int NS_SQ_EVAL_WG_BATCH = 3;  // ... per matrix of a batched launch (its squarings take twice as long; LEAN evaluations)
 template <int COH, int NEVAL>
@@ -1681,65 +1540,7 @@ __global__ __launch_bounds__(256, 3) void ns_square_tail_pair_lean_kernel(const 
     ns_square_tail_pair_impl<NS_SQ_EVAL_WG_BATCH, true>(A, xb_all, scall, batch, force_agent, deflate);
 }
 
-constexpr int NS_PAIR_WG = 32;
-template <int COH>
-__device__ __forceinline__ bool ns_T_pair_body(const double *Y, const double *Zt, double *T, double *Tt, double *s, int iter, int w,
-                                               double (*redp)[4][4][64], double (*partp)[4])
-{
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int p = w >> 3, tj = w & 7;
-    PairOps ops;
-    pair_load<COH>(ops, Zt, Y, p, tj, lane, wv, LoadPlain{});  // (Z^T)^T . Y = Z.Y
-    const double a = gld<COH>(s + SC_COEF + 2 * iter), bq = gld<COH>(s + SC_COEF + 2 * iter + 1);
-    if (ns_converged<COH>(s, iter, lane, w == 0 && tid == 0)) return false;
-    double pv[2];
-    pair_mma_reduce(ops, redp, wv, lane, pv);
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int ti = 2 * p + h;
-        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-        store_both<COH>(T, Tt, row, col, fma(bq, pv[h], (row == col) ? a : 0.0));
-        const double d = pv[h] - ((row == col) ? 1.0 : 0.0);
-        const double ws = wr::wave64_allsum(d * d);
-        if (lane == 0) partp[h][wv] = ws;
-    }
-    __syncthreads();
-    if (tid < 2) gst<COH>(s + SC_ERR + iter * 64 + (2 * p + tid) * 8 + tj, (partp[tid][0] + partp[tid][1]) + (partp[tid][2] + partp[tid][3]));
-    return true;
-}
-// Part 2 on 2 x 2 tile BLOCKS (round 5): workgroups 0..15 form the blocks of Y' = Y.T, 16..31 those of Z' = T.Z -- one product of four
-// tiles per workgroup instead of two products of two tiles one after the other.  What this phase waits for is the XCD's ONE L2
-// (16 channels x 64 B/clk): pairs pull 4 MB of operands through it (~2 us: round 5's phase stamps showed the second product's
-// operands arriving 2.0 us after the first's), blocks 2 MB; the MFMA count per wave is the same (32).  Per tile the arithmetic of
-// ns_YZ_body (quad_mma_reduce), as in the batched launches.  redq: 4 x 4 x 4 x 64 doubles of LDS.  Measured (phase stamps, one matrix): the
-// phase 3.9 us against 4.2 (operands 1.4 us against 1.2 + the second product's 1.2 under its own product; product 1.3 against 2.0;
-// four tiles' stores 0.8 against 0.5); same box, whole step 173.3 against 175.2 us.  (Round 4 had tried all 48 operand loads of the
-// two pair products in flight together: no difference -- the bytes, not the second latency.)
-template <int COH>
-__device__ __forceinline__ bool ns_YZ_quad_body(const double *Yt, const double *Z, const double *T, const double *Tt, double *Yo, double *Yto,
-                                                double *Zo, double *Zto, double *s, int iter, int zbuf_out, int w,
-                                                double (*redq)[4][4][64])
-{
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const bool isZ = w >= 16;
-    const int q = w & 15, mi = q >> 2, mj = q & 3;
-    QuadOps ops;
-    quad_load<COH>(ops, isZ ? Tt : Yt, isZ ? Z : T, mi, mj, lane, wv, LoadPlain{});
-    if (ns_converged<COH>(s, iter, lane, false)) return false;
-    if (w == 0 && tid == 0) {
-        gst<COH>(s + SC_ZBUF, (double)zbuf_out);
-        gst<COH>(s + SC_ITERS, (double)(iter + 1));
-    }
-    double v[4];
-    quad_mma_reduce(ops, redq, wv, lane, v);
-#pragma unroll
-    for (int t = 0; t < 4; ++t) {
-        const int ti = 2 * mi + (t >> 1), tj = 2 * mj + (t & 1);
-        const int row = 16 * ti + (lane >> 4) + 4 * wv, col = 16 * tj + (lane & 15);
-        store_both<COH>(isZ ? Zo : Yo, isZ ? Zto : Yto, row, col, v[t]);
-    }
-    return true;
-}
+constexpr int NS_PAIR_WG = 32;  // workgroups of the persistent iterations: part 1 on 2 x 1 pairs, part 2 on 2 x 2 blocks
 template <int COH>
 __device__ __forceinline__ void ns_iter_tail_pair_rest(const NsBufs &B, size_t off, double *scall, int iter_first, int w, unsigned xcc,
                                                        double (*redp)[4][4][64], double (*partp)[4], bool t_first)
@@ -1755,10 +1556,10 @@ __device__ __forceinline__ void ns_iter_tail_pair_rest(const NsBufs &B, size_t o
         double *Yo = (odd ? B.Y[0] : B.Y[1]) + off, *Yto = (odd ? B.Yt[0] : B.Yt[1]) + off;
         double *Zo = (odd ? B.Z[0] : B.Z[1]) + off, *Zto = (odd ? B.Zt[0] : B.Zt[1]) + off;
         if (iter > iter_first || t_first) {
-            if (!ns_T_pair_body<COH>(Yi, Zti, B.T + off, B.Tt + off, scall, iter, w, redp, partp)) return;
+            if (!ns_T_block_body<COH, 2, 1>(Yi, Zti, B.T + off, B.Tt + off, scall, iter, w, redp, partp)) return;
             if (!ns_flag_barrier<COH>(flags, ++phase, w, NS_PAIR_WG, xcc, scall + SC_BARFAIL)) return;
         }
-        (void)ns_YZ_quad_body<COH>(Yti, Zi, B.T + off, B.Tt + off, Yo, Yto, Zo, Zto, scall, iter, odd ? 0 : 1, w, redp);
+        (void)ns_YZ_block_body<COH, 2, 2>(Yti, Zi, B.T + off, B.Tt + off, Yo, Yto, Zo, Zto, scall, iter, odd ? 0 : 1, w, redp);
         if (iter < iter_last && !ns_flag_barrier<COH>(flags, ++phase, w, NS_PAIR_WG, xcc, scall + SC_BARFAIL)) return;
     }
 }
@@ -1807,7 +1608,7 @@ __device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const Ns
 {
     constexpr int iter_first = EARLY_LOGDET ? 1 : NS_ITERS - NS_BATCH_TAIL_ITERS;
     // dynamic LDS: the factorisation's matrix (129 KiB, EARLY_LOGDET) / the iterations' reduction buffer (32 KiB: four tiles x four
-    // K-quarters, ns_YZ_quad_body; the pairs of part 1 use half of it) -- static and dynamic together must stay under 160 KiB
+    // K-quarters, ns_YZ_block_body; the pairs of part 1 use half of it) -- static and dynamic together must stay under 160 KiB
     double (*redp)[4][4][64] = reinterpret_cast<double (*)[4][4][64]>(ld_sm);
     __shared__ double partp[2][4];
     if (EARLY_LOGDET && blockIdx.x == 2) {  // (another of the linear ids the launch sends away: XCD 2)
@@ -1851,7 +1652,7 @@ __device__ __forceinline__ void ns_iter_tail_pair_impl(const double *A, const Ns
             store_both<COH_AGENT>(B.Y[1] + off, B.Yt[1] + off, row, col, fy(av, row, col));
             store_both<COH_AGENT>(B.Z[1] + off, B.Zt[1] + off, row, col, fz(av, row, col));
         }
-    } else if (!ns_T_pair_body<COH_AGENT>((odd ? B.Y[1] : B.Y[0]) + off, (odd ? B.Zt[1] : B.Zt[0]) + off, B.T + off, B.Tt + off, scall,
+    } else if (!ns_T_block_body<COH_AGENT, 2, 1>((odd ? B.Y[1] : B.Y[0]) + off, (odd ? B.Zt[1] : B.Zt[0]) + off, B.T + off, B.Tt + off, scall,
                                           iter_first, w, redp, partp))
         return;
     int r = ns_flag_barrier<COH_AGENT>(reinterpret_cast<unsigned *>(scall + SC_FLAGS) + 64, 1u, w, NS_PAIR_WG, xcc, scall + SC_BARFAIL);
@@ -2466,6 +2267,21 @@ SymStatsOut sigma_ns_stats_out(void *workspace, int batch)
 // 11 matrices, the slots, then the filter's history X_3 .. X_16 and X_1 (XBufs)
 size_t sigma_ns_workspace_bytes(int batch) { return (size_t)batch * ((11 + NS_SQUARINGS - 1) * SN * SN + SC_COUNT) * sizeof(double); }
 
+// Y1, Z1 written out element-wise (ns_first_elem_kernel, which also leaves the coefficient table), then the launches (T, Y'Z') of
+// iterations 1 .. i_end - 1 on MI x MJ tile blocks
+template <int MI, int MJ>
+static void ns_launch_iters(hipStream_t s, const NsBufs &B, double *sc, int i_end, int batch)
+{
+    hipLaunchKernelGGL(ns_first_elem_kernel, ns_grid(65, batch), dim3(256), 0, s, B.A, B.X1, B.Y[1], B.Yt[1], B.Z[1], B.Zt[1], sc, 1, batch);
+    for (int i = 1; i < i_end; ++i) {
+        const int in = i & 1, out = in ^ 1;
+        hipLaunchKernelGGL((ns_T_quad_kernel<MI, MJ>), ns_grid(64 / (MI * MJ), batch), dim3(256), 0, s, B.Y[in], B.Zt[in], B.T, B.Tt, sc, i,
+                           batch);
+        hipLaunchKernelGGL((ns_YZ_quad_kernel<MI, MJ>), ns_grid(128 / (MI * MJ), batch), dim3(256), 0, s, B.Yt[in], B.Z[in], B.T, B.Tt,
+                           B.Y[out], B.Yt[out], B.Z[out], B.Zt[out], sc, i, out, batch);
+    }
+}
+
 // The chain runs one of four fixed launch plans ([prep]: ns_prep_kernel, unless the Hessian has left A's statistics: r_has_stats):
 //   MERGED     one matrix, persistent, r_has_stats, opt.ns_merged:  ns_chain_kernel -> finalize
 //   TWO_LAUNCH one matrix, persistent, otherwise:  [prep] -> squarings with the evaluations inside -> iterations 1 .. 11 with the
@@ -2537,36 +2353,27 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
         hipLaunchKernelGGL(ns_square_tail_pair_lean_kernel, ns_persist_grid(NS_SQ_PAIR_WG + NS_SQ_EVAL_WG_BATCH, batch), dim3(256), 0, s, A,
                            xb, sc, batch, opt.ns_force_agent, opt.ns_deflate);
         if (sigma_stages < 3) return 0;
-        hipLaunchKernelGGL(ns_first_elem_kernel, ns_grid(65, batch), dim3(256), 0, s, A, B.X1, Y[1], Yt[1], Z[1], Zt[1], sc, 1, batch);
-        for (int i = 1; i < NS_ITERS - NS_BATCH_TAIL_ITERS; ++i) {  // 2 x 2 tile blocks per workgroup: same tiles, same bits
-            const int in = i & 1, out = in ^ 1;
-            hipLaunchKernelGGL(ns_T_quad_kernel, ns_grid(16, batch), dim3(256), 0, s, Y[in], Zt[in], B.T, B.Tt, sc, i, batch);
-            hipLaunchKernelGGL(ns_YZ_quad_kernel, ns_grid(32, batch), dim3(256), 0, s, Yt[in], Z[in], B.T, B.Tt, Y[out], Yt[out], Z[out],
-                               Zt[out], sc, i, out, batch);
-        }
+        ns_launch_iters<2, 2>(s, B, sc, NS_ITERS - NS_BATCH_TAIL_ITERS, batch);
         hipLaunchKernelGGL(ns_iter_tail_pair_kernel<false>, ns_persist_grid(NS_PAIR_WG, batch), dim3(256), 4 * 4 * 4 * 64 * sizeof(double), s, A,
                            B, sc, batch, opt.ns_force_agent);
         break;
     case PHASED:
-        hipLaunchKernelGGL(ns_square_kernel<true>, ns_grid(NS_TILES, batch), dim3(256), 0, s, A, ns_xk(xb, 1), sc, 0, batch);
-        for (int i = 1; i < NS_SQUARINGS; ++i)
-            hipLaunchKernelGGL(ns_square_kernel<false>, ns_grid(NS_TILES, batch), dim3(256), 0, s, ns_xk(xb, i), ns_xk(xb, i + 1), sc, i, batch);
+        // one matrix on single tiles, batches on pairs / 2 x 2 blocks (the launches of one matrix are latency; same tiles, same bits)
+        if (batch == 1) {
+            hipLaunchKernelGGL((ns_square_kernel<true, 1>), ns_grid(NS_TILES, 1), dim3(256), 0, s, A, ns_xk(xb, 1), sc, 0, 1);
+            for (int i = 1; i < NS_SQUARINGS; ++i)
+                hipLaunchKernelGGL((ns_square_kernel<false, 1>), ns_grid(NS_TILES, 1), dim3(256), 0, s, ns_xk(xb, i), ns_xk(xb, i + 1), sc, i, 1);
+        } else {
+            hipLaunchKernelGGL((ns_square_kernel<true, 2>), ns_grid(NS_SQ_PAIR_WG, batch), dim3(256), 0, s, A, ns_xk(xb, 1), sc, 0, batch);
+            for (int i = 1; i < NS_SQUARINGS; ++i)
+                hipLaunchKernelGGL((ns_square_kernel<false, 2>), ns_grid(NS_SQ_PAIR_WG, batch), dim3(256), 0, s, ns_xk(xb, i), ns_xk(xb, i + 1),
+                                   sc, i, batch);
+        }
         if (sigma_stages < 2) return 0;
         hipLaunchKernelGGL(ns_ritz_scan_kernel, dim3(batch * RITZ_NK), dim3(256), 0, s, A, xb, sc, opt.ns_deflate);
         if (sigma_stages < 3) return 0;
-        hipLaunchKernelGGL(ns_first_elem_kernel, ns_grid(65, batch), dim3(256), 0, s, A, B.X1, Y[1], Yt[1], Z[1], Zt[1], sc, 1, batch);
-        for (int i = 1; i < NS_ITERS; ++i) {
-            const int in = i & 1, out = in ^ 1;
-            if (batch > 1) {  // 2 x 2 tile blocks per workgroup: same tiles, same bits, half the operand traffic
-                hipLaunchKernelGGL(ns_T_quad_kernel, ns_grid(16, batch), dim3(256), 0, s, Y[in], Zt[in], B.T, B.Tt, sc, i, batch);
-                hipLaunchKernelGGL(ns_YZ_quad_kernel, ns_grid(32, batch), dim3(256), 0, s, Yt[in], Z[in], B.T, B.Tt, Y[out], Yt[out], Z[out],
-                                   Zt[out], sc, i, out, batch);
-            } else {
-                hipLaunchKernelGGL(ns_T_kernel, ns_grid(64, batch), dim3(256), 0, s, Y[in], Zt[in], B.T, B.Tt, sc, i, batch);
-                hipLaunchKernelGGL(ns_YZ_kernel, ns_grid(128, batch), dim3(256), 0, s, Yt[in], Z[in], B.T, B.Tt, Y[out], Yt[out], Z[out],
-                                   Zt[out], sc, i, out, batch);
-            }
-        }
+        if (batch == 1) ns_launch_iters<1, 1>(s, B, sc, NS_ITERS, batch);
+        else ns_launch_iters<2, 2>(s, B, sc, NS_ITERS, batch);
         break;
     }
     if (sigma_stages < 4) return 0;
