@@ -22,7 +22,7 @@ COVO_RANK_RECORD_FLOATS = COVO_PARTIAL_FLOATS + 2 * COVO_POS_STATS_DOUBLES  # 51
 COVO_COV_FLOATS = COVO_H * 10
 COVO_RANK_RECORD_COV_FLOATS = COVO_PARTIAL_FLOATS + COVO_COV_FLOATS + 2 * COVO_POS_STATS_DOUBLES  # 836: with MPPI's second moments
 COVO_EXCHANGE_HANDLE_BYTES = 128
-ABI_VERSION = 8
+ABI_VERSION = 9
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -67,6 +67,12 @@ class BatchArgsC(C.Structure):
     _fields_ = [("n_envs", C.c_int32), ("n_samples", C.c_int32), ("T", C.c_int32), ("pad_", C.c_int32),
                 ("states", _P), ("pos_traj", _P), ("vel_traj", _P), ("a_mean", _P), ("a_cov", _P), ("a", _P), ("cost", _P),
                 ("groupmin", _P), ("gamma_mean", C.c_float), ("sample_sigma", C.c_float)]
+
+
+class BatchModeArgsC(C.Structure):
+    """struct covo_batch_mode_args (include/covo_hip.h): the batched step with a mode, for the *_mode entry points."""
+    _fields_ = [("base", BatchArgsC), ("mode", C.c_int32), ("n_table", C.c_int32), ("L_table", _P),
+                ("L_table_stride", C.c_int64), ("gamma_sigma", C.c_float), ("pad_", C.c_int32)]
 
 
 REWARD_KINDS = {"penyaw": 0, "realworld": 1}                 # COVO_REWARD_*
@@ -135,6 +141,9 @@ _SIGS = {
                                         C.POINTER(C.c_uint32), C.c_int32, C.c_float, _P, C.c_int32, C.c_int32, _P]),
     "covo_run_episode_batched": (C.c_int, [_P, C.POINTER(BatchArgsC), C.POINTER(EnvParamsC), _P, _P, C.c_int32, C.c_float, _P,
                                            C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, _P]),
+    "covo_mpc_step_batched_mode": (C.c_int, [_P, C.POINTER(BatchModeArgsC), C.POINTER(EnvParamsC), C.POINTER(C.c_uint32), _P]),
+    "covo_run_episode_batched_mode": (C.c_int, [_P, C.POINTER(BatchModeArgsC), C.POINTER(EnvParamsC), _P, _P, C.c_int32, C.c_float,
+                                                _P, C.c_int32, C.c_int32, C.POINTER(C.c_uint32), C.c_int32, _P]),
     "covo_debug_set_ns_deflate": (C.c_int, [_P, C.c_int]),             # per-handle experiment switches (covo_hip.h)
     "covo_debug_set_fuse_small": (C.c_int, [_P, C.c_int]),
     "covo_debug_set_fold_begin": (C.c_int, [_P, C.c_int]),

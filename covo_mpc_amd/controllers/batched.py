@@ -1,11 +1,13 @@
-"""CoVO-online for E independent env instances in one call (BASELINE.json configs[4]).
+"""The sampling controllers for E independent env instances in one call (BASELINE.json configs[4]).
 
 The reference runs its `--mode render` / eval loop on one env instance and reaches many instances through
 `jax.vmap` of the whole controller (quadjax/envs/quadrotor.py:497-538 is written per instance and vmap-clean).
-Here that is `covo_mpc_step_batched` (include/covo_hip.h, csrc/step.hip): one hipGraph holding ONE batched
-Hessian + Sigma launch set for all instances and the per-instance sampling path.  Every instance has its own
-state, reference trajectory, (domain-randomised) parameters, mean and key; instance e's result is bit-identical
-to `CoVOController.__call__` on that instance alone (tests/test_gpu_parity.py::test_batched_step_equals_replicas).
+Here that is `covo_mpc_step_batched` / `covo_mpc_step_batched_mode` (include/covo_hip.h, csrc/step.hip):
+  covo-online   one hipGraph holding ONE batched Hessian + Sigma launch set for all instances and the per-instance sampling path;
+  covo-offline, MPPI   the key upload plus ONE fused launch for all instances (csrc/step_small.hip, instance = grid dimension).
+Every instance has its own state, reference trajectory, (domain-randomised) parameters, mean, key (and, per mode, Sigma table or
+block covariances); instance e's result is bit-identical to the single controller's `__call__` on that instance alone
+(tests/test_gpu_parity.py::test_batched_step_equals_replicas, tests/test_gpu_batched_modes.py).
 Instances never exchange data ("replicas only"): to use G GPUs give each rank E/G instances.
 """
 from __future__ import annotations
@@ -21,8 +23,18 @@ from ._core import SamplingCore
 
 
 class BatchedCoVOController:
+    """CoVO-MPC for E instances.  mode="online" (default): Sigma from every instance's own Hessian at every step;
+    mode="offline": Sigma looked up in a per-instance table built by `reset` (covo.py:44-112, per instance)."""
+    MODE = None  # subclasses with a fixed mode (BatchedMPPIController)
+
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
-                 sample_sigma: float = 0.5, a_mean_init=None, device=None):
+                 sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online"):
+        if self.MODE is not None:
+            self.mode = self.MODE
+        elif mode in ("online", "offline"):
+            self.mode = _lib.MODE_COVO_ONLINE if mode == "online" else _lib.MODE_COVO_OFFLINE
+        else:
+            raise NotImplementedError(mode)  # covo.py:113-114
         if not 0 < n_envs <= _lib.COVO_MAX_ENVS:
             raise ValueError(f"n_envs={n_envs} outside (0, {_lib.COVO_MAX_ENVS}]")
         self.env, self.E, self.N, self.H = env, int(n_envs), int(N), int(H)
@@ -39,7 +51,10 @@ class BatchedCoVOController:
         self.a_mean = torch.zeros((E, COVO_NA), **f32)
         if a_mean_init is not None:
             self.a_mean.copy_(torch.as_tensor(a_mean_init, **f32).reshape(1, COVO_NA).expand(E, COVO_NA))
-        self.a_cov = torch.zeros((E, COVO_NA, COVO_NA), **f32)
+        # online: the Sigma every instance sampled from (out); MPPI: the H 4x4 blocks (in/out, shifted in place each step)
+        self.a_cov = torch.zeros((E, COVO_H, 4, 4) if self.mode == _lib.MODE_MPPI else (E, COVO_NA, COVO_NA), **f32)
+        self.a_cov_offline = self.a_chol_offline = None  # offline: [E][T][128][128] tables, built by reset()
+        self.gamma_sigma = 0.0
         self._a = torch.empty((E, COVO_H, n, 4), **f32)
         self._cost = torch.empty((E, n), **f32)
         self._groupmin = torch.empty((E, (n + 63) // 64), **f32)
@@ -60,21 +75,71 @@ class BatchedCoVOController:
         self._traj = (pos, vel, T)
         from .base import env_model_params_c
         self._params = (_lib.EnvParamsC * self.E)(*[env_model_params_c(self.env, p) for p in env_params])
-        a = _lib.BatchArgsC()
+        self._args = self._make_args(self._states, pos, vel, T)
+        self._states_buf = self._states
+        self._episode = None
+
+    def _make_args(self, states, pos, vel, T):
+        """struct covo_batch_mode_args over the controller's buffers; its `base` is the covo_batch_args of the covo-online entries."""
+        m = _lib.BatchModeArgsC()
+        a = m.base
         a.n_envs, a.n_samples, a.T = self.E, self.N, T
-        a.states, a.pos_traj, a.vel_traj = self._states.data_ptr(), pos.data_ptr(), vel.data_ptr()
+        a.states, a.pos_traj, a.vel_traj = states.data_ptr(), pos.data_ptr(), vel.data_ptr()
         a.a_mean, a.a_cov = self.a_mean.data_ptr(), self.a_cov.data_ptr()
         a.a, a.cost, a.groupmin = self._a.data_ptr(), self._cost.data_ptr(), self._groupmin.data_ptr()
         a.gamma_mean, a.sample_sigma = self.gamma_mean, self.sample_sigma
-        self._args = a
-        self._states_buf = self._states
-        self._episode = None
+        m.mode, m.gamma_sigma = self.mode, self.gamma_sigma
+        self._fill_table(m)
+        return m
+
+    def _fill_table(self, m):
+        if self.mode == _lib.MODE_COVO_OFFLINE and self.a_chol_offline is not None:
+            L = self.a_chol_offline
+            m.L_table, m.n_table, m.L_table_stride = L.data_ptr(), int(L.shape[1]), int(L.shape[1]) * COVO_NA * COVO_NA
+
+    def reset(self, env_states, env_params, keys):
+        """covo-offline: instance e's Sigma table and its Cholesky factors from instance e's own start state, parameters and key,
+        through CoVOController.reset_a_cov_offline (covo.py:58-104; once per episode, a host loop over the instances).
+        -> (a_cov_offline, a_chol_offline) [E, T, 128, 128].  The other modes have nothing to build."""
+        if self.mode != _lib.MODE_COVO_OFFLINE:
+            return None
+        from .covo import CoVOController, CoVOParams
+        torch = self.core.torch
+        cp = CoVOParams(gamma_mean=self.gamma_mean, gamma_sigma=0.0, discount=self.core.discount, sample_sigma=self.sample_sigma,
+                        a_mean=None, a_cov=None, a_cov_offline=None)
+        if getattr(self, "_builder", None) is None:
+            self._builder = CoVOController(self.env, cp, self.N, self.H, self.core.lam, "offline", device=self.core.device,
+                                           compute_info=False)
+        Sig, L = [], []
+        for st, p, k in zip(env_states, env_params, keys):
+            out = self._builder.reset_a_cov_offline(st, p, cp, k)
+            Sig.append(out.a_cov_offline.clone())
+            L.append(out.a_chol_offline.clone())
+        if len(Sig) != self.E:
+            raise ValueError(f"{len(Sig)} instances given, controller has {self.E}")
+        return self.set_tables(torch.stack(Sig), torch.stack(L))
+
+    def set_tables(self, a_cov_offline, a_chol_offline):
+        """covo-offline: take ready-made per-instance tables [E, T, 128, 128] (Sigma and its lower Cholesky factors)."""
+        if self.mode != _lib.MODE_COVO_OFFLINE:
+            raise ValueError("only the covo-offline controller has Sigma tables")
+        if tuple(a_chol_offline.shape[:1] + a_chol_offline.shape[2:]) != (self.E, COVO_NA, COVO_NA):
+            raise ValueError(f"a_chol_offline {tuple(a_chol_offline.shape)} is not [{self.E}, T, {COVO_NA}, {COVO_NA}]")
+        self.a_cov_offline, self.a_chol_offline = a_cov_offline.contiguous(), a_chol_offline.contiguous()
+        if self._args is not None:
+            self._fill_table(self._args)
+        return self.a_cov_offline, self.a_chol_offline
+
+    def _check_ready(self):
+        if self._args is None:
+            raise RuntimeError("call set_instances(env_states, env_params) first")
+        if self.mode == _lib.MODE_COVO_OFFLINE and self.a_chol_offline is None:
+            raise RuntimeError("covo-offline: call controller.reset(...) first (a_cov_offline table missing)")
 
     def __call__(self, noisy_states, rng_acts):
         """One control step of every instance.  noisy_states: E env states (or a float32 [E, 32] device tensor of
         packed states); rng_acts: uint32 [E, 2] raw controller keys.  -> first actions [E, 4] (view of a_mean)."""
-        if self._args is None:
-            raise RuntimeError("call set_instances(env_states, env_params) first")
+        self._check_ready()
         torch = self.core.torch
         buf = self._states_buf  # the tensor args.states points at: the controller's own, or a bound episode's noisy states
         if noisy_states is None or noisy_states is buf:
@@ -85,9 +150,14 @@ class BatchedCoVOController:
             packed = [as_device_state(s, self.core.device).packed for s in noisy_states]
             torch.stack(packed, out=buf)
         keys = np.ascontiguousarray(np.asarray(rng_acts, dtype=np.uint32).reshape(self.E, 2))
-        check(self.core.lib.covo_mpc_step_batched(self.core.h, C.byref(self._args), self._params,
-                                                  keys.ctypes.data_as(C.POINTER(C.c_uint32)), self.core.stream()),
-              "covo_mpc_step_batched")
+        if self.mode == _lib.MODE_COVO_ONLINE:
+            check(self.core.lib.covo_mpc_step_batched(self.core.h, C.byref(self._args.base), self._params,
+                                                      keys.ctypes.data_as(C.POINTER(C.c_uint32)), self.core.stream()),
+                  "covo_mpc_step_batched")
+        else:
+            check(self.core.lib.covo_mpc_step_batched_mode(self.core.h, C.byref(self._args), self._params,
+                                                           keys.ctypes.data_as(C.POINTER(C.c_uint32)), self.core.stream()),
+                  "covo_mpc_step_batched_mode")
         return self.a_mean.view(self.E, COVO_H, 4)[:, 0]
 
     def time_phases(self, step_mask: int, reps: int = 10) -> float:
@@ -106,13 +176,7 @@ class BatchedCoVOController:
             raise ValueError(f"episode has {episode.E} instances, controller {self.E}")
         self._traj = (episode.pos_traj, episode.vel_traj, episode.T)
         self._params = episode.params_c
-        a = _lib.BatchArgsC()
-        a.n_envs, a.n_samples, a.T = self.E, self.N, episode.T
-        a.states, a.pos_traj, a.vel_traj = episode.noisy.data_ptr(), episode.pos_traj.data_ptr(), episode.vel_traj.data_ptr()
-        a.a_mean, a.a_cov = self.a_mean.data_ptr(), self.a_cov.data_ptr()
-        a.a, a.cost, a.groupmin = self._a.data_ptr(), self._cost.data_ptr(), self._groupmin.data_ptr()
-        a.gamma_mean, a.sample_sigma = self.gamma_mean, self.sample_sigma
-        self._args = a
+        self._args = self._make_args(episode.noisy, episode.pos_traj, episode.vel_traj, episode.T)
         self._states_buf = episode.noisy
         self._episode = episode
 
@@ -122,12 +186,34 @@ class BatchedCoVOController:
         [E, 2] -> the chains' keys after the segment.  Asynchronous; episode.read_log() synchronises."""
         if getattr(self, "_episode", None) is not episode:
             self.bind_episode(episode)
+        self._check_ready()
         env = self.env
         keys = np.ascontiguousarray(np.asarray(rngs, dtype=np.uint32).reshape(self.E, 2)).copy()
-        check(self.core.lib.covo_run_episode_batched(
-            self.core.h, C.byref(self._args), self._params, _lib.ptr(episode.true), _lib.ptr(episode.acc_traj),
+        online = self.mode == _lib.MODE_COVO_ONLINE
+        fn = self.core.lib.covo_run_episode_batched if online else self.core.lib.covo_run_episode_batched_mode
+        check(fn(
+            self.core.h, C.byref(self._args.base) if online else C.byref(self._args), self._params, _lib.ptr(episode.true), _lib.ptr(episode.acc_traj),
             1 if env.generate_noisy_state else 0, float(env.default_params.obs_noise_scale), _lib.ptr(episode.log),
             int(episode.log.shape[1]), int(episode.n_steps), keys.ctypes.data_as(C.POINTER(C.c_uint32)), int(n_steps),
-            self.core.stream()), "covo_run_episode_batched")
+            self.core.stream()), "covo_run_episode_batched" if online else "covo_run_episode_batched_mode")
         episode.n_steps += int(n_steps)
         return keys
+
+
+class BatchedMPPIController(BatchedCoVOController):
+    """MPPI (mppi.py:11-134) for E instances: the same methods as BatchedCoVOController; `a_cov` [E, H, 4, 4] starts as
+    diag(sigmas**2) tiled over the horizon (quadrotor.py:705-720, as controllers/mppi.py for one instance) and is shifted in
+    place by every step (mppi.py:43-49).  sigmas: one standard deviation for all four action components, or four of them."""
+    MODE = _lib.MODE_MPPI
+
+    def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
+                 gamma_sigma: float = 0.0, a_mean_init=None, device=None):
+        if float(gamma_sigma) != 0.0:
+            raise NotImplementedError(f"gamma_sigma={gamma_sigma}: MPPI's covariance adaptation (mppi.py:119-125) is not batched; "
+                                      "the batched fused launch needs gamma_sigma == 0 (the reference's default)")
+        sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
+        super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
+                         a_mean_init=a_mean_init, device=device)
+        torch = self.core.torch
+        blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
+        self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

@@ -68,6 +68,9 @@ __global__ void raise_status_kernel(int *status, int bits)
 }
 
 int covo_debug_batched_hessians_impl(covo_ctx *h, double *out, int64_t offset_doubles, int64_t count, hipStream_t s);  // step.hip
+int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
+                                 hipStream_t s);  // step.hip
+const char *batch_small_refusal(const covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, int *which);  // step.hip
 
 extern "C" {
 
@@ -694,22 +697,65 @@ int covo_env_step_batched(covo_handle_t h, int32_t n_envs, float *states, float 
                                    noisy_on, obs_noise_scale, log, log_stride, log_index, (hipStream_t)stream);
 }
 
-int covo_run_episode_batched(covo_handle_t h, const covo_batch_args *args, const covo_env_params *params, float *states_true,
-                             const float *acc_traj, int32_t noisy_on, float obs_noise_scale, float *log, int32_t log_stride,
-                             int32_t log_index, uint32_t *rngs, int32_t n_steps, void *stream)
+// every argument check of a batched step in `mode` (covo_mpc_step_batched / _mode, covo_run_episode_batched / _mode): nothing
+// is launched before all of them have passed.  *norm: the argument block with its padding zeroed (it is a cache key)
+static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *m, const covo_env_params *params,
+                            const char *what, covo_batch_mode_args *norm)
 {
-    REQUIRE(h, "covo_run_episode_batched: null handle");
-    CHECK_DEVICE(h, "covo_run_episode_batched");
-    REQUIRE(args && params && states_true && acc_traj && rngs && n_steps > 0, "covo_run_episode_batched: bad argument");
+    REQUIRE(args->n_envs > 0 && args->n_envs <= COVO_MAX_ENVS, "%s: n_envs=%d outside (0, %d]", what, args->n_envs, COVO_MAX_ENVS);
+    REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "%s: n_samples=%d outside (0, %d]", what, args->n_samples,
+            h->cfg.n_local);
+    const int mode = m ? m->mode : COVO_MODE_COVO_ONLINE;
+    REQUIRE(mode == COVO_MODE_MPPI || mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_COVO_OFFLINE, "%s: mode=%d is not a COVO_MODE_*",
+            what, mode);
+    REQUIRE(args->states && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost &&
+                (args->groupmin || mode != COVO_MODE_COVO_ONLINE) && args->T > 0,
+            "%s: null buffer", what);
+    for (int e = 0; e < args->n_envs; ++e) {
+        CHECK_MODEL(&params[e], what);
+        REQUIRE(params[e].reward_kind == params[0].reward_kind && params[e].rollover_terminate == params[0].rollover_terminate &&
+                    params[e].disturb_kind == params[0].disturb_kind,
+                "%s: all instances must share reward_kind, rollover_terminate and disturb_kind (one kernel "
+                "variant per launch); disturb_params / period / scale may differ", what);
+    }
+    if (mode == COVO_MODE_COVO_ONLINE) return 0;
+    REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
+    REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),
+            "%s: covo-offline needs L_table (the per-instance Sigma factor table is missing: n_table=%d)", what, m->n_table);
+    std::memset(norm, 0, sizeof(*norm));
+    norm->base.n_envs = args->n_envs; norm->base.n_samples = args->n_samples; norm->base.T = args->T;
+    norm->base.states = args->states; norm->base.pos_traj = args->pos_traj; norm->base.vel_traj = args->vel_traj;
+    norm->base.a_mean = args->a_mean; norm->base.a_cov = args->a_cov; norm->base.a = args->a; norm->base.cost = args->cost;
+    norm->base.groupmin = args->groupmin; norm->base.gamma_mean = args->gamma_mean; norm->base.sample_sigma = args->sample_sigma;
+    norm->mode = mode;
+    norm->gamma_sigma = m->gamma_sigma;
+    if (mode == COVO_MODE_COVO_OFFLINE) {
+        norm->n_table = m->n_table;
+        norm->L_table = m->L_table;
+        norm->L_table_stride = m->L_table_stride;
+    }
+    int which = 0;
+    const char *why = batch_small_refusal(h, norm, params, &which);
+    REQUIRE(why == nullptr, "%s: instance %d cannot take the batched fused launch: %s (there is no staged batched fallback)", what,
+            which, why);
+    return 0;
+}
+
+static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, const covo_batch_mode_args *m, const covo_env_params *params,
+                               float *states_true, const float *acc_traj, int32_t noisy_on, float obs_noise_scale, float *log,
+                               int32_t log_stride, int32_t log_index, uint32_t *rngs, int32_t n_steps, void *stream, const char *what)
+{
+    REQUIRE(h, "%s: null handle", what);
+    CHECK_DEVICE(h, what);
+    REQUIRE(args && params && states_true && acc_traj && rngs && n_steps > 0, "%s: bad argument", what);
     const int E = args->n_envs;
-    REQUIRE(E > 0 && E <= COVO_MAX_ENVS, "covo_run_episode_batched: n_envs=%d outside (0, %d]", E, COVO_MAX_ENVS);
-    REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "covo_run_episode_batched: n_samples=%d outside (0, %d]",
-            args->n_samples, h->cfg.n_local);
-    REQUIRE(args->states && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin && args->T > 0,
-            "covo_run_episode_batched: bad step arguments");
+    covo_batch_mode_args norm;
+    int rc = check_batch_step(h, args, m, params, what, &norm);
+    if (rc) return rc;
+    const bool online = !m || m->mode == COVO_MODE_COVO_ONLINE;
     REQUIRE(log == nullptr || (log_index >= 0 && log_index + n_steps <= log_stride),
-            "covo_run_episode_batched: log rows [%d, %d) outside [0, %d)", log_index, log_index + n_steps, log_stride);
-    int rc = check_batch_models(params, E, "covo_run_episode_batched");
+            "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
+    rc = check_batch_models(params, E, what);
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
@@ -725,7 +771,8 @@ int covo_run_episode_batched(covo_handle_t h, const covo_batch_args *args, const
             host_philox_split(key, 2u, &step_keys[2 * e]);
             host_philox_split(nrng, 0u, &next[2 * e]);
         }
-        if ((rc = covo_step_batched_impl(h, args, params, act_keys, s))) return rc;
+        if ((rc = online ? covo_step_batched_impl(h, args, params, act_keys, s) : covo_step_batched_small_impl(h, &norm, params, act_keys, s)))
+            return rc;
         if ((rc = launch_env_step_batched(states_true, const_cast<float *>(args->states), args->pos_traj, args->vel_traj, acc_traj,
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
                                           log_stride, log_index + t, s)))
@@ -733,6 +780,22 @@ int covo_run_episode_batched(covo_handle_t h, const covo_batch_args *args, const
         std::memcpy(rngs, next, (size_t)2 * E * sizeof(uint32_t));
     }
     return 0;
+}
+
+int covo_run_episode_batched(covo_handle_t h, const covo_batch_args *args, const covo_env_params *params, float *states_true,
+                             const float *acc_traj, int32_t noisy_on, float obs_noise_scale, float *log, int32_t log_stride,
+                             int32_t log_index, uint32_t *rngs, int32_t n_steps, void *stream)
+{
+    return run_episode_batched(h, args, nullptr, params, states_true, acc_traj, noisy_on, obs_noise_scale, log, log_stride, log_index,
+                               rngs, n_steps, stream, "covo_run_episode_batched");
+}
+
+int covo_run_episode_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params, float *states_true,
+                                  const float *acc_traj, int32_t noisy_on, float obs_noise_scale, float *log, int32_t log_stride,
+                                  int32_t log_index, uint32_t *rngs, int32_t n_steps, void *stream)
+{
+    return run_episode_batched(h, args ? &args->base : nullptr, args, params, states_true, acc_traj, noisy_on, obs_noise_scale, log,
+                               log_stride, log_index, rngs, n_steps, stream, "covo_run_episode_batched_mode");
 }
 
 int covo_debug_time_batched(covo_handle_t h, int32_t step_mask, int32_t reps, float *us_out, void *stream)
@@ -748,21 +811,22 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     REQUIRE(h, "covo_mpc_step_batched: null handle");
     CHECK_DEVICE(h, "covo_mpc_step_batched");
     REQUIRE(args && params && keys, "covo_mpc_step_batched: null argument");
-    REQUIRE(args->n_envs > 0 && args->n_envs <= COVO_MAX_ENVS, "covo_mpc_step_batched: n_envs=%d outside (0, %d]", args->n_envs,
-            COVO_MAX_ENVS);
-    REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "covo_mpc_step_batched: n_samples=%d outside (0, %d]",
-            args->n_samples, h->cfg.n_local);
-    REQUIRE(args->states && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin &&
-                args->T > 0,
-            "covo_mpc_step_batched: null buffer");
-    for (int e = 0; e < args->n_envs; ++e) {
-        CHECK_MODEL(&params[e], "covo_mpc_step_batched");
-        REQUIRE(params[e].reward_kind == params[0].reward_kind && params[e].rollover_terminate == params[0].rollover_terminate &&
-                    params[e].disturb_kind == params[0].disturb_kind,
-                "covo_mpc_step_batched: all instances must share reward_kind, rollover_terminate and disturb_kind (one kernel "
-                "variant per launch); disturb_params / period / scale may differ");
-    }
+    int rc = check_batch_step(h, args, nullptr, params, "covo_mpc_step_batched", nullptr);
+    if (rc) return rc;
     return covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream);
+}
+
+int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params, const uint32_t *keys,
+                               void *stream)
+{
+    REQUIRE(h, "covo_mpc_step_batched_mode: null handle");
+    CHECK_DEVICE(h, "covo_mpc_step_batched_mode");
+    REQUIRE(args && params && keys, "covo_mpc_step_batched_mode: null argument");
+    covo_batch_mode_args norm;
+    int rc = check_batch_step(h, &args->base, args, params, "covo_mpc_step_batched_mode", &norm);
+    if (rc) return rc;
+    if (args->mode == COVO_MODE_COVO_ONLINE) return covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream);
+    return covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
 }
 
 int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, int32_t step_mask,

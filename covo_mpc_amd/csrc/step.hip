@@ -461,7 +461,45 @@ __global__ void batch_begin_kernel(const float *__restrict__ a_mean, float *__re
     }
 }
 
+// the env-batched MPPI / covo-offline step (covo_mpc_step_batched_mode): ONE fused launch for all instances (step_small.hip,
+// grid = groups x instances) behind the key upload; scratch and graph cache of its own, next to the covo-online batch's
+struct BatchSmall {
+    int n_envs = 0, groups = 0;
+    uint32_t *dyn = nullptr;     // [E][12]: the instances' raw rng_act of the current step (batch_set_dyn_kernel)
+    void *args = nullptr;        // SmallStepArgs[E]
+    unsigned *tickets = nullptr; // [E] arrival counters; each wraps to 0 with its instance's last workgroup (atomicInc)
+    float *records = nullptr;    // [E][groups][COVO_PARTIAL_FLOATS]
+    std::vector<char> args_host;
+    std::vector<covo_env_params> params;
+    covo_batch_mode_args key;
+    hipStream_t stream = nullptr;
+    bool have_key = false, have_graph = false;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+};
+
+static void batch_small_drop_graph(BatchSmall *m)
+{
+    if (m->have_graph) {
+        (void)hipGraphExecDestroy(m->exec);
+        (void)hipGraphDestroy(m->graph);
+        m->have_graph = false;
+    }
+}
+static void batch_small_free(BatchSmall *m)
+{
+    batch_small_drop_graph(m);
+    (void)hipFree(m->dyn);
+    (void)hipFree(m->args);
+    (void)hipFree(m->tickets);
+    (void)hipFree(m->records);
+    m->dyn = nullptr; m->args = nullptr; m->tickets = nullptr; m->records = nullptr;
+    m->n_envs = m->groups = 0;
+    m->have_key = false;
+}
+
 struct BatchState {
+    BatchSmall small;
     int n_envs = 0;
     uint32_t *dyn = nullptr;        // [E][12]
     float *a_mean_shift = nullptr;  // [E][128]
@@ -528,6 +566,10 @@ void step_graphs_drop(covo_ctx *h)
         b->have_graph = false;
     }
     if (b) b->have_key = false;
+    if (b) {
+        batch_small_drop_graph(&b->small);
+        b->small.have_key = false;
+    }
 }
 
 // the device array of per-instance env constants for covo_env_step_batched, rebuilt only when the parameters change
@@ -563,6 +605,7 @@ void batch_state_destroy(covo_ctx *h)
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     if (!b) return;
     batch_state_free(b);
+    batch_small_free(&b->small);
     (void)hipFree(b->eps_tiled);
     (void)hipFree(b->env_inst);  // (not in batch_state_free: the batched step re-allocates its scratch when the instance count
                                  // changes, possibly between batch_env_inst and the env step launch that reads this array)
@@ -788,6 +831,126 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         return 0;
     }
     return batch_enqueue(h, b, *args, s);
+}
+
+// MPPI / covo-offline for E instances: key upload + ONE fused launch (no begin launch: every workgroup shifts its instance's mean
+// and derives its instance's keys itself, as an eager single step does).  The second identical call captures the fused launch
+// into a graph; the key upload stays eager in front of it (its kernel arguments ARE the keys).  The caller (capi.hip) has
+// checked eligibility: nothing here is refused after a launch.
+static covo_step_args batch_small_instance(const covo_batch_mode_args &m, int e)
+{
+    const covo_batch_args &a = m.base;
+    const int N = a.n_samples;
+    covo_step_args sa;
+    std::memset(&sa, 0, sizeof(sa));
+    sa.mode = m.mode;
+    sa.n_samples = N;
+    sa.T = a.T;
+    sa.n_table = m.n_table;
+    sa.state = a.states + (size_t)e * COVO_STATE_FLOATS;
+    sa.pos_traj = a.pos_traj + (size_t)e * a.T * 3;
+    sa.vel_traj = a.vel_traj + (size_t)e * a.T * 3;
+    sa.a_mean = a.a_mean + (size_t)e * COVO_NA;
+    sa.a_cov = (m.mode == COVO_MODE_MPPI) ? a.a_cov + (size_t)e * COVO_H * 16 : nullptr;
+    sa.L_table = (m.mode == COVO_MODE_COVO_OFFLINE) ? m.L_table + (size_t)e * m.L_table_stride : nullptr;
+    sa.a = a.a + (size_t)e * COVO_H * N * 4;
+    sa.cost = a.cost + (size_t)e * N;
+    sa.gamma_mean = a.gamma_mean;
+    sa.sample_sigma = a.sample_sigma;
+    sa.derive_keys = 1;
+    sa.rollout_deterministic = (m.mode == COVO_MODE_MPPI) ? 0 : 1;  // covo.py:231 / mppi.py:74
+    sa.gamma_sigma = m.gamma_sigma;
+    return sa;
+}
+
+// null: every instance of the batch can take the fused launch; else why not (instance index in *which)
+const char *batch_small_refusal(const covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, int *which)
+{
+    for (int e = 0; e < m->base.n_envs; ++e) {
+        const covo_step_args sa = batch_small_instance(*m, e);
+        const char *why = step_small_refusal(h, params[e], sa);
+        if (why) {
+            *which = e;
+            return why;
+        }
+    }
+    return nullptr;
+}
+
+int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
+                                 hipStream_t s)
+{
+    const int E = m->base.n_envs, N = m->base.n_samples, ng = (N + COVO_WAVE - 1) / COVO_WAVE;
+    if (h->dbg_epoch != h->opt.epoch) {  // as in covo_step_impl
+        step_graphs_drop(h);
+        h->dbg_epoch = h->opt.epoch;
+    }
+    BatchState *b = reinterpret_cast<BatchState *>(h->batch);
+    if (!b) {
+        b = new BatchState();
+        h->batch = b;
+    }
+    BatchSmall *q = &b->small;
+    const bool same = q->have_key && q->n_envs == E && std::memcmp(&q->key, m, sizeof(*m)) == 0 && q->stream == s &&
+                      std::memcmp(q->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
+    if (!same) {
+        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old argument blocks are done
+        batch_small_drop_graph(q);
+        if (q->n_envs != E || q->groups != ng) {
+            batch_small_free(q);
+            COVO_CHECK_HIP(hipMalloc(&q->dyn, (size_t)E * 12 * sizeof(uint32_t)));
+            COVO_CHECK_HIP(hipMalloc(&q->args, step_small_args_bytes(E)));
+            COVO_CHECK_HIP(hipMalloc(&q->tickets, (size_t)E * sizeof(unsigned)));
+            COVO_CHECK_HIP(hipMalloc(&q->records, (size_t)E * ng * COVO_PARTIAL_FLOATS * sizeof(float)));
+            q->n_envs = E;
+            q->groups = ng;
+        }
+        COVO_CHECK_HIP(hipMemset(q->tickets, 0, (size_t)E * sizeof(unsigned)));
+        q->params.assign(params, params + E);
+        q->args_host.assign(step_small_args_bytes(E), 0);
+        for (int e = 0; e < E; ++e) {
+            const covo_step_args sa = batch_small_instance(*m, e);
+            // the one shared gaussian vector of MPPI's sampling rollouts (free.py:66-70), per instance; off for CoVO (deterministic)
+            const float scale = (params[e].disturb_kind == COVO_DISTURB_GAUSSIAN && !sa.rollout_deterministic) ? params[e].dyn_noise_scale : 0.0f;
+            step_small_fill_args(h, q->args_host.data(), e, params[e], sa, q->dyn + 12 * e, scale, q->tickets + e,
+                                 q->records + (size_t)e * ng * COVO_PARTIAL_FLOATS);
+        }
+        COVO_CHECK_HIP(hipMemcpy(q->args, q->args_host.data(), q->args_host.size(), hipMemcpyHostToDevice));
+        std::memset(&q->key, 0, sizeof(q->key));
+        q->key = *m;
+        q->stream = s;
+        q->have_key = true;
+    }
+    BatchDyn blk;
+    std::memset(&blk, 0, sizeof(blk));
+    for (int e = 0; e < E; ++e) {
+        blk.w[e][0] = keys[2 * e];
+        blk.w[e][1] = keys[2 * e + 1];
+    }
+    hipLaunchKernelGGL(batch_set_dyn_kernel, dim3(1), dim3(256), 0, s, q->dyn, blk, E);
+    const bool mppi = m->mode == COVO_MODE_MPPI;
+    if (q->have_graph) {
+        COVO_CHECK_HIP(hipGraphLaunch(q->exec, s));
+        return 0;
+    }
+    if (same && (h->cfg.flags & COVO_FLAG_NO_GRAPH) == 0) {  // second identical call: capture
+        hipStream_t cs = h->side_stream;
+        COVO_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+        const int rc = launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, cs);
+        hipGraph_t g = nullptr;
+        const hipError_t e = hipStreamEndCapture(cs, &g);
+        if (rc) return rc;
+        if (e != hipSuccess) {
+            covo_set_error("covo_mpc_step_batched_mode: stream capture failed: %s", hipGetErrorString(e));
+            return (int)e;
+        }
+        COVO_CHECK_HIP(hipGraphInstantiate(&q->exec, g, nullptr, nullptr, 0));
+        q->graph = g;
+        q->have_graph = true;
+        COVO_CHECK_HIP(hipGraphLaunch(q->exec, s));
+        return 0;
+    }
+    return launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, s);
 }
 
 // test hook: the Hessians of the LAST batched step (E x 128 x 128 doubles), device -> host

@@ -49,9 +49,34 @@ constexpr size_t SS_LDS_GEMM = sizeof(SmallLds) + (size_t)COVO_NA * NG_LDA * siz
 constexpr size_t SS_LDS_MPPI = sizeof(SmallLds) + sizeof(MergeLds);
 static_assert(sizeof(MergeLds) <= (size_t)COVO_NA * NG_LDA * sizeof(float), "merge scratch must fit the factor image");
 
-template <bool MPPI, bool DISC1, bool ROLL>
-__global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArgs P)
+// BATCHED (the env-batched step, covo_mpc_step_batched_mode): grid = (groups per instance, instances).  Workgroup row y does for
+// instance y what the single launch does for its one instance; instance y's argument block -- own state, trajectories, model
+// constants, mean, covariances or factor table, work buffers, records, ticket -- is batch[y] in device memory (wave-uniform scalar
+// loads), P_ is instance 0's block as a kernel argument and only anchors the pointers' address space (rebase_global).  Every
+// quantity that counts workgroups (record index, ticket wrap, the merge's record count, the group mapping) is blockIdx.x /
+// gridDim.x, i.e. per instance: instance y's step is bit-identical to the single launch on it.  The per-step keys come from
+// device memory: dyn_mem = that instance's RAW rng_act (batch_set_dyn_kernel), derived per workgroup like an eager single step.
+template <bool MPPI, bool DISC1, bool ROLL, bool BATCHED = false>
+__global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArgs P_, const SmallStepArgs *__restrict__ batch)
 {
+    SmallStepArgs Pb;
+    if (BATCHED) {
+        Pb = batch[blockIdx.y];
+        Pb.R.state = rebase_global(P_.R.state, Pb.R.state);
+        Pb.R.pos_traj = rebase_global(P_.R.pos_traj, Pb.R.pos_traj);
+        Pb.R.vel_traj = rebase_global(P_.R.vel_traj, Pb.R.vel_traj);
+        Pb.R.a = rebase_global(P_.R.a, Pb.R.a);
+        Pb.R.cost = rebase_global(P_.R.cost, Pb.R.cost);
+        Pb.R.records = rebase_global(P_.R.records, Pb.R.records);
+        Pb.R.merge_ticket = rebase_global(P_.R.merge_ticket, Pb.R.merge_ticket);
+        Pb.R.merge_out = rebase_global(P_.R.merge_out, Pb.R.merge_out);
+        Pb.a_mean_in = rebase_global(P_.a_mean_in, Pb.a_mean_in);
+        Pb.L_table = rebase_global(P_.L_table, Pb.L_table);
+        Pb.mppi_cov = rebase_global(P_.mppi_cov, Pb.mppi_cov);
+        Pb.dyn_mem = rebase_global(P_.dyn_mem, Pb.dyn_mem);
+        Pb.a_mean_shift_out = nullptr;  // (the merge blends with the shifted mean in LDS; nobody else reads it)
+    }
+    const SmallStepArgs &P = BATCHED ? Pb : P_;
     extern __shared__ __attribute__((aligned(16))) unsigned char ss_raw[];
     SmallLds &S = *reinterpret_cast<SmallLds *>(ss_raw);
     float *Ls = reinterpret_cast<float *>(ss_raw + sizeof(SmallLds));       // [128][NG_LDA] (covo-offline)
@@ -64,7 +89,7 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
     // ---- phase 0
     const float *__restrict__ a_mean = P.a_mean_in;
     if (tid < COVO_NA) {
-        if (P.dyn_mem != nullptr) {  // (a captured graph: the begin launch has shifted the mean of THIS replay; a_mean_in is not baked in)
+        if (!BATCHED && P.dyn_mem != nullptr) {  // (a captured graph: the begin launch has shifted the mean of THIS replay; a_mean_in is not baked in)
             S.mus[tid] = P.a_mean_shift_out[tid];
         } else {
             const float v = (tid < COVO_NA - COVO_DU) ? a_mean[tid + COVO_DU] : a_mean[tid];  // covo.py:201-203
@@ -72,7 +97,14 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
             if (blockIdx.x == 0 && P.a_mean_shift_out != nullptr) P.a_mean_shift_out[tid] = v;
         }
     } else if (tid < COVO_NA + 4) {
-        if (P.dyn_mem != nullptr) {  // a captured graph: the begin launch has left the step's scalars in device memory
+        if (BATCHED) {  // no begin launch: the instance's raw rng_act lies in device memory, every workgroup derives from it
+            DynBlock kb;
+#pragma unroll
+            for (int i = 0; i < 12; ++i) kb.w[i] = 0u;
+            kb.w[0] = P.dyn_mem[0];
+            kb.w[1] = P.dyn_mem[1];
+            step_begin_derive(tid - COVO_NA, kb, 1, P.shared_noise_scale, S.dyn);
+        } else if (P.dyn_mem != nullptr) {  // a captured graph: the begin launch has left the step's scalars in device memory
             const int q = tid - COVO_NA;
             if (q == 0) { S.dyn[0] = P.dyn_mem[0]; S.dyn[1] = P.dyn_mem[1]; }
             else S.dyn[1 + q] = P.dyn_mem[1 + q];
@@ -224,27 +256,36 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
     }
 }
 
-bool step_small_eligible(const covo_ctx *h, const covo_env_params &p, const covo_step_args &a)
+// why the step (args, params) cannot run as the one fused launch, in words a caller can act on; null: it can
+const char *step_small_refusal(const covo_ctx *h, const covo_env_params &p, const covo_step_args &a)
 {
-    if (a.mode != COVO_MODE_COVO_OFFLINE && a.mode != COVO_MODE_MPPI) return false;
-    if (a.mode == COVO_MODE_MPPI && a.gamma_sigma != 0.0f) return false;      // second moments: reduce.hip's own stage 1
-    if (a.pos_stats != nullptr) return false;                                  // covo.py:281's statistics: the STATS rollout
-    if (p.reward_kind != COVO_REWARD_PENYAW) return false;
-    if (p.disturb_kind != COVO_DISTURB_NONE && p.disturb_kind != COVO_DISTURB_GAUSSIAN) return false;  // per-step tables
+    if (a.mode != COVO_MODE_COVO_OFFLINE && a.mode != COVO_MODE_MPPI) return "the mode is neither MPPI nor covo-offline";
+    if (a.mode == COVO_MODE_MPPI && a.gamma_sigma != 0.0f)                     // second moments: reduce.hip's own stage 1
+        return "gamma_sigma != 0 (MPPI's covariance adaptation)";
+    if (a.pos_stats != nullptr) return "position statistics are requested";    // covo.py:281's statistics: the STATS rollout
+    if (p.reward_kind != COVO_REWARD_PENYAW) return "reward_kind is not COVO_REWARD_PENYAW (the realworld reward)";
+    if (p.disturb_kind != COVO_DISTURB_NONE && p.disturb_kind != COVO_DISTURB_GAUSSIAN)  // per-step tables
+        return "disturb_kind needs per-step tables (only COVO_DISTURB_NONE and COVO_DISTURB_GAUSSIAN)";
     const int ng = (a.n_samples + COVO_WAVE - 1) / COVO_WAVE;
-    return ng >= 1 && ng <= h->max_red_blocks && ng <= 256;
+    if (ng < 1 || ng > h->max_red_blocks || ng > 256) return "n_samples is outside [1, 16384] (at most 256 groups of 64 samples)";
+    return nullptr;
 }
 
-int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state, float *a_mean_shift,
-                      const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s)
+bool step_small_eligible(const covo_ctx *h, const covo_env_params &p, const covo_step_args &a)
 {
-    SmallStepArgs P;
+    return step_small_refusal(h, p, a) == nullptr;
+}
+
+static void fill_small_args(SmallStepArgs &P, covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state,
+                            float *a_mean_shift, const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale,
+                            unsigned *ticket, float *records)
+{
     std::memset(&P, 0, sizeof(P));
     const int N = a.n_samples;
     fill_rollout_args(P.R, state, a.pos_traj, a.vel_traj, a.T, p, nullptr, a.a, N, h->cfg.discount, a.cost, nullptr, nullptr, nullptr,
                       nullptr, a.mode == COVO_MODE_MPPI ? 4 : 0);
     P.R.clip = 0;  // the stripes come straight from this launch's own clipped draw
-    P.R.records = h->ws_partials;
+    P.R.records = records;
     P.R.inv_lam = 1.0f / h->cfg.lam;
     P.R.merge_ticket = ticket;
     P.R.merge_final = a.partial_out == nullptr;
@@ -261,17 +302,30 @@ int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_arg
     P.derive_keys = a.derive_keys;
     P.shared_noise_scale = shared_noise_scale;
     P.nanp = covo_propagate_nan(h) ? 1 : 0;
-    const int ng = (N + COVO_WAVE - 1) / COVO_WAVE;
+}
+
+// the dynamic LDS above 64 KB is a per-device opt-in of every instantiation
+static int small_attrs_once()
+{
     static unsigned long long attr_devices = 0;  // (per device: covo_first_on_device)
     if (covo_first_on_device(attr_devices)) {
-#define SS_ATTR(MPPI, D, R) COVO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(step_small_kernel<MPPI, D, R>), \
-                                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MPPI ? SS_LDS_MPPI : SS_LDS_GEMM)))
+#define SS_ATTR1(MPPI, D, R, B) COVO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(step_small_kernel<MPPI, D, R, B>), \
+                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MPPI ? SS_LDS_MPPI : SS_LDS_GEMM)))
+#define SS_ATTR(MPPI, D, R) SS_ATTR1(MPPI, D, R, false); SS_ATTR1(MPPI, D, R, true)
         SS_ATTR(false, false, false); SS_ATTR(false, false, true); SS_ATTR(false, true, false); SS_ATTR(false, true, true);
         SS_ATTR(true, false, false); SS_ATTR(true, false, true); SS_ATTR(true, true, false); SS_ATTR(true, true, true);
 #undef SS_ATTR
+#undef SS_ATTR1
     }
-    const bool mppi = a.mode == COVO_MODE_MPPI, disc1 = h->cfg.discount == 1.0f, roll = P.R.rollover != 0;
-#define SS_GO(MPPI, D, R) hipLaunchKernelGGL((step_small_kernel<MPPI, D, R>), dim3(ng), dim3(SS_BLOCK), MPPI ? SS_LDS_MPPI : SS_LDS_GEMM, s, P)
+    return 0;
+}
+
+template <bool BATCHED>
+static int small_go(const SmallStepArgs &P, const SmallStepArgs *batch, int nb, bool mppi, bool disc1, hipStream_t s)
+{
+    const int ng = (P.R.N + COVO_WAVE - 1) / COVO_WAVE;
+    const bool roll = P.R.rollover != 0;
+#define SS_GO(MPPI, D, R) hipLaunchKernelGGL((step_small_kernel<MPPI, D, R, BATCHED>), dim3(ng, nb), dim3(SS_BLOCK), MPPI ? SS_LDS_MPPI : SS_LDS_GEMM, s, P, batch)
     if (mppi) {
         if (disc1) { if (roll) SS_GO(true, true, true); else SS_GO(true, true, false); }
         else       { if (roll) SS_GO(true, false, true); else SS_GO(true, false, false); }
@@ -282,4 +336,34 @@ int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_arg
 #undef SS_GO
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state, float *a_mean_shift,
+                      const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s)
+{
+    SmallStepArgs P;
+    fill_small_args(P, h, p, a, state, a_mean_shift, blk, dyn_mem, shared_noise_scale, ticket, h->ws_partials);
+    int rc = small_attrs_once();
+    if (rc) return rc;
+    return small_go<false>(P, nullptr, 1, a.mode == COVO_MODE_MPPI, h->cfg.discount == 1.0f, s);
+}
+
+// ---- the env-batched form: one argument block per instance in device memory (step.hip keeps the host and device arrays)
+size_t step_small_args_bytes(int n) { return (size_t)n * sizeof(SmallStepArgs); }
+
+void step_small_fill_args(covo_ctx *h, void *out, int index, const covo_env_params &p, const covo_step_args &a, const uint32_t *raw_key_mem,
+                          float shared_noise_scale, unsigned *ticket, float *records)
+{
+    fill_small_args(reinterpret_cast<SmallStepArgs *>(out)[index], h, p, a, a.state, nullptr, nullptr, raw_key_mem, shared_noise_scale,
+                    ticket, records);
+}
+
+// all instances alike in mode, sample count, reward, rollover flag and disturbance kind (the caller has checked): instance 0 picks
+// the variant
+int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s)
+{
+    int rc = small_attrs_once();
+    if (rc) return rc;
+    return small_go<true>(*reinterpret_cast<const SmallStepArgs *>(args_host), reinterpret_cast<const SmallStepArgs *>(args_dev), n, mppi,
+                          h->cfg.discount == 1.0f, s);
 }

@@ -25,3 +25,13 @@ bool step_small_eligible(const covo_ctx *h, const covo_env_params &p, const covo
 // state: the noisy state this launch reads (args.state, or the graph's fixed-address copy); blk / dyn_mem: exactly one non-null
 int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state, float *a_mean_shift,
                       const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s);
+// why not, in words a caller can act on (null: eligible)
+const char *step_small_refusal(const covo_ctx *h, const covo_env_params &p, const covo_step_args &a);
+// The env-batched form (grid = groups per instance x instances): instance `index`'s argument block, described like a single step
+// by (p, a) with a.state / a.a_mean / a.a_cov / a.L_table / a.a / a.cost its own buffers, into the host array `out`;
+// raw_key_mem: DEVICE uint32[2], that instance's raw rng_act of the current step; ticket / records: its own arrival counter and
+// [groups][COVO_PARTIAL_FLOATS] records.  The device copy of the array is the launch's `args_dev`.
+size_t step_small_args_bytes(int n);
+void step_small_fill_args(covo_ctx *h, void *out, int index, const covo_env_params &p, const covo_step_args &a, const uint32_t *raw_key_mem,
+                          float shared_noise_scale, unsigned *ticket, float *records);
+int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s);

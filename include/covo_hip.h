@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define COVO_ABI_VERSION 8
+#define COVO_ABI_VERSION 9
 
 #define COVO_H 32            /* horizon (compile-time in the fused kernels)          */
 #define COVO_DU 4            /* action dim, quadjax/envs/quadrotor.py:198            */
@@ -507,6 +507,41 @@ typedef struct covo_batch_args {
 int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const covo_env_params *params,
                           const uint32_t *keys, void *stream);
 
+/* The env-batched step with a MODE: MPPI and covo-offline for n_envs independent instances next to covo-online, so that the three
+ * controllers can be compared on the same instances (mppi.py:43-125, covo.py:201-278 per instance).
+ * ABI choice: NEW entry points with an argument struct of their own.  covo_batch_args is unchanged, and a zeroed `pad_` in it
+ * keeps meaning covo-online through covo_mpc_step_batched / covo_run_episode_batched (COVO_MODE_MPPI is 0: `pad_` could not
+ * have become the mode).  Here `mode` is explicit:
+ *   COVO_MODE_COVO_ONLINE   exactly covo_mpc_step_batched(h, &args->base, ...): the other fields are ignored.
+ *   COVO_MODE_MPPI          base.a_cov = float[n_envs][H][4][4], in/out, shifted in place every step (mppi.py:43-49); the rollouts
+ *                           are non-deterministic (mppi.py:74): under COVO_DISTURB_GAUSSIAN every instance draws its one shared
+ *                           vector from its own key.  gamma_sigma must be 0.
+ *   COVO_MODE_COVO_OFFLINE  L_table = instance e's float[n_table][128][128] lower factors at L_table + e * L_table_stride
+ *                           (stride in floats; 0: all instances share one table), row clamp(state[e].time) per step (covo.py:107);
+ *                           deterministic rollouts (covo.py:231).  base.a_cov is not touched.
+ * MPPI and covo-offline run as ONE fused launch for all instances (csrc/step_small.hip with the instance as a grid dimension)
+ * behind the key upload -- two launches per batched step, the fused one replayed from a hipGraph; instance e's new mean, action
+ * buffer, costs (and MPPI's covariances) are bit-identical to covo_mpc_step on instance e alone.  base.groupmin is not used by
+ * them (may be NULL).  There is no staged fallback: what the fused launch does not take is refused before anything is launched,
+ * with a message that names the condition -- for every instance: reward_kind = COVO_REWARD_PENYAW, disturb_kind NONE or GAUSSIAN,
+ * gamma_sigma == 0, n_samples <= 16 384 (256 groups of 64); all instances share reward_kind, rollover_terminate and disturb_kind.
+ * covo_debug_time_batched is refused after a step in these two modes (it replays covo-online's launch groups only; time the
+ * fused launch with events around covo_mpc_step_batched_mode).
+ * covo_run_episode_batched_mode = covo_run_episode_batched with the batched step in the chosen mode (same key threading, same
+ * env step: it needs only a_mean[e][0..3]). */
+typedef struct covo_batch_mode_args {
+    covo_batch_args base;
+    int32_t mode;            /* COVO_MODE_* */
+    int32_t n_table;         /* offline: rows of every instance's L_table */
+    const float *L_table;    /* offline: see above */
+    int64_t L_table_stride;  /* offline: floats between consecutive instances' tables; 0 = one shared table */
+    float gamma_sigma;       /* MPPI: must be 0 (the covariance adaptation is not batched) */
+    int32_t pad_;
+} covo_batch_mode_args;
+
+int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params,
+                               const uint32_t *keys, void *stream);
+
 /* Lower Cholesky factors of `batch` symmetric PD n x n fp32 matrices (n <= 128), the
  * factorisation inside jax.random.multivariate_normal (covo.py:216, mppi.py:59). */
 int covo_cholesky(covo_handle_t h, const float *A, int32_t n, int32_t batch, float *L_out, void *stream);
@@ -573,6 +608,11 @@ int covo_run_episode_batched(covo_handle_t h, const covo_batch_args *args, const
                              float obs_noise_scale, float *log /* [n_envs][log_stride][4], nullable */, int32_t log_stride,
                              int32_t log_index, uint32_t *rngs /* host [n_envs][2], in/out */, int32_t n_steps, void *stream);
 
+int covo_run_episode_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params /* [n_envs] */,
+                                  float *states_true /* [n_envs][32] */, const float *acc_traj /* [n_envs][T][3] */, int32_t noisy_on,
+                                  float obs_noise_scale, float *log /* [n_envs][log_stride][4], nullable */, int32_t log_stride,
+                                  int32_t log_index, uint32_t *rngs /* host [n_envs][2], in/out */, int32_t n_steps, void *stream);
+
 /* Profiling aid: `reps` copies of the selected launches of one control step, captured into one hipGraph and
  * replayed; *us_out = GPU microseconds per copy.  step_mask bits: 1 shift_mean, 2 Hessian, 4 Sigma, 8 noise GEMM,
  * 16 rollout, 32 softmax update; hess_mask bits: the four kernels of the adjoint Hessian; sigma_stages 1..4:
@@ -585,7 +625,8 @@ int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const c
                          int32_t hess_mask, int32_t sigma_stages, int32_t reps, float *us_out, void *stream);
 
 /* The same for the LAST covo_mpc_step_batched call of the handle (all instances; the begin launch, bit 1, re-splits the keys and
- * is normally left out). */
+ * is normally left out).  covo-online only: refused when no covo-online batched step has run (covo_mpc_step_batched_mode's MPPI /
+ * covo-offline steps are one launch with nothing to select). */
 int covo_debug_time_batched(covo_handle_t h, int32_t step_mask, int32_t reps, float *us_out, void *stream);
 
 /* Test hook: a one-thread kernel on `stream` ORs `bits` into the handle's status word the way a failing kernel would

@@ -1,0 +1,314 @@
+"""GPU tests (-m gpu) of the env-batched MPPI and covo-offline steps (covo_mpc_step_batched_mode, csrc/step_small.hip with the
+instance as a grid dimension; controllers/batched.py: BatchedMPPIController, BatchedCoVOController(mode="offline")):
+  * instance e of a batched step == the single controller on instance e alone, bit for bit (same device functions, one ticket
+    and one record set per instance);
+  * against oracle/ directly: per-sample costs (C fp64 rollout with the instance's own parameters, 1e-5) and the new mean
+    (ref_np.softmax_update, 1e-4 unless the two best costs are closer than 1e-3 * lam / 0.01) -- the bars of
+    tests/test_gpu_parity.py::_oracle_check_of_a_fused_step, including its cap of max(2, N // 4096) samples per call that may
+    use the widened bar (1.5 x what the fp32 C oracle loses against the fp64 one on the same samples);
+  * whole episodes (control step + env step on the device) against per-instance episodes;
+  * refusals: argument checks that return before any launch.
+"""
+import types
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+if not torch.cuda.is_available():
+    pytest.skip("needs the MI355X", allow_module_level=True)
+
+from covo_mpc_amd import _lib  # noqa: E402
+from covo_mpc_amd import random as cr  # noqa: E402
+from oracle import c_oracle as CO  # noqa: E402
+from oracle import ref_np as R  # noqa: E402
+
+DEV = "cuda:0"
+ST_TIME = 25  # packed state: the step counter's int32 bits (include/covo_hip.h)
+
+
+def rel_err(x, ref):
+    return np.abs(x - ref) / np.maximum(np.abs(ref), 1.0)
+
+
+def _env(rollover=False, disturb="gaussian", **kw):
+    import covo_mpc_amd as cm
+    return cm.envs.Quad3D(task="tracking", obs_type="quad_params", enable_randomizer=True, disturb_type=disturb,
+                          disable_rollover_terminate=not rollover, generate_noisy_state=True, device=DEV, **kw)
+
+
+def _oracle_params(params):
+    return R.Params(m=float(params.m), action_scale=float(params.action_scale), alpha_bodyrate=float(params.alpha_bodyrate),
+                    disturb_params=tuple(float(x) for x in params.disturb_params)).fp32()
+
+
+def _oracle_state(ns):
+    return R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
+                   vel_tar=ns.vel_tar, acc_tar=ns.acc_tar, time=ns.time, pos_traj=ns.pos_traj, vel_traj=ns.vel_traj,
+                   acc_traj=ns.acc_traj).astype(np.float64)
+
+
+def _instances(env, name, N, lam, E, seed=0, warm=True):
+    """E domain-randomised instances, each with its own trajectory (reset key), a state a few steps into the episode (reached
+    with its own random actions), its own key chain and its own single-instance controller."""
+    import covo_mpc_amd as cm
+    inst = []
+    for e in range(E):
+        params = env.sample_params(cr.PRNGKey(seed + 100 + e))
+        c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam}", device=DEV, compute_info=False)
+        obs, info, state = env.reset(cr.PRNGKey(seed + 200 + e), params)
+        rng = np.random.default_rng(seed + 1000 + e)
+        for k in range((2 + e % 4) if warm else 0):
+            u = (0.3 * rng.standard_normal(4)).clip(-1, 1).astype(np.float32)
+            obs, state, _, _, info = env.step(cr.PRNGKey(seed + 5000 + 10 * e + k), state, u, params)
+        inst.append(dict(params=params, c=c, cp=c.init_control_params, obs=obs, info=info, state=state,
+                         key=cr.PRNGKey(seed + 300 + e), reset_key=cr.PRNGKey(seed + 400 + e)))
+    return inst
+
+
+_TABLES = {}
+
+
+def _offline_tables(env, inst, tag):
+    """Every instance's Sigma table from a single CoVOController.reset on it (cached: the same instances come back in every case)."""
+    out = []
+    for e, i in enumerate(inst):
+        k = (tag, e)
+        if k not in _TABLES:
+            cp = i["c"].reset(i["state"], i["params"], i["c"].init_control_params, i["reset_key"])
+            _TABLES[k] = (cp.a_cov_offline, cp.a_chol_offline)
+        out.append(_TABLES[k])
+        i["cp"] = i["cp"].replace(a_cov_offline=out[-1][0], a_chol_offline=out[-1][1])
+    return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
+
+
+def _batched(env, name, inst, N, lam):
+    import covo_mpc_amd as cm
+    E, cp0 = len(inst), inst[0]["cp"]
+    if name == "mppi":
+        b = cm.controllers.BatchedMPPIController(env, E, N, 32, float(lam), sigmas=cp0.sample_sigma, discount=cp0.discount,
+                                                 gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=DEV)
+        assert torch.equal(b.a_cov[0], cp0.a_cov)  # quadrotor.py:705-720: diag(sigma^2) tiled over H, as the single factory's
+    else:
+        b = cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
+                                                 sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, mode="offline")
+    return b
+
+
+CASES = [("mppi", 1024, "0.01", False), ("mppi", 100, "5.0", True), ("covo-offline", 4096, "0.01", False),
+         ("covo-offline", 40, "0.01", True)]
+
+
+@pytest.mark.parametrize("name,N,lam,rollover", CASES)
+@pytest.mark.parametrize("E", [1, 5, 32])
+@pytest.mark.parametrize("graph", ["graph", "eager"])
+def test_batched_mode_step_equals_replicas(name, N, lam, rollover, E, graph, monkeypatch):
+    """3 consecutive batched steps (eager first call, capture, replay -- or three eager calls) on E domain-randomised instances,
+    each with its own mid-episode state, trajectory and key, under the GAUSSIAN disturbance (MPPI: every instance draws its own
+    shared vector from its own key), with and without rollover termination: a_mean, the action buffer, the costs and MPPI's
+    a_cov of instance e are torch.equal to those of a single-instance controller stepped on instance e alone."""
+    monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
+    env = _env(rollover=rollover)
+    inst = _instances(env, name, N, lam, E)
+    b = _batched(env, name, inst, N, lam)
+    b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
+    if name == "covo-offline":
+        with pytest.raises(RuntimeError, match="call controller.reset"):
+            b([i["info"]["noisy_state"] for i in inst], np.zeros((E, 2), dtype=np.uint32))
+        b.set_tables(*_offline_tables(env, inst, (N, rollover)))
+    assert b.core.uses_graph == (graph == "graph")
+    for step in range(3):
+        k_acts = []
+        for i in inst:
+            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
+            k_acts.append(np.asarray(k_act))
+        u_b = b([i["info"]["noisy_state"] for i in inst], np.stack(k_acts)).clone()
+        for e, i in enumerate(inst):
+            u, i["cp"], _ = i["c"](i["obs"], i["state"], i["params"], k_acts[e], i["cp"], i["info"])
+            where = (name, N, E, graph, step, e)
+            assert torch.equal(b.a_mean[e].view(32, 4), i["cp"].a_mean), where
+            assert torch.equal(b._a[e], i["c"].core.a), where
+            assert torch.equal(b._cost[e], i["c"].core.cost), where
+            assert torch.equal(u_b[e], u), where
+            if name == "mppi":
+                assert torch.equal(b.a_cov[e], i["cp"].a_cov), where
+            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u.cpu().numpy(), i["params"])
+    assert b.core.device_status() == 0 and torch.isfinite(b.a_mean).all()
+    if E > 1:
+        assert (b.a_mean[0] - b.a_mean[1]).abs().max() > 1e-4  # different plants, different plans
+
+
+def _oracle_check_instance(name, env, params, ns, a_mean_before, k_act, a_dev_t, cost_dev_t, a_mean_new_t, lam, rollover=False):
+    """The checks and bars of tests/test_gpu_parity.py::_oracle_check_of_a_fused_step for one instance of a batch, with the
+    instance's own parameters.  -> how many samples used the widened bar (at most max(2, N // 4096) may)."""
+    N = a_dev_t.shape[1]
+    so, po = _oracle_state(ns), _oracle_params(params)
+    am = R.shift_mean(np.asarray(a_mean_before, dtype=np.float64).reshape(32, 4))
+    fs = np.zeros(3)
+    if name == "mppi":  # mppi.py:69,74: one shared non-deterministic draw for every sample and step
+        _, step_key = cr.split(cr.split(k_act)[0])
+        fs = np.asarray(env.rollout_disturbance(step_key, params, deterministic=False), dtype=np.float64)
+    a_dev = a_dev_t.permute(1, 0, 2).contiguous().cpu().numpy().astype(np.float64)
+    cost_dev = cost_dev_t.cpu().numpy()
+    cost_ref = CO.rollout(so, po, a_dev, 1.0, fs, dtype=np.float64, rollover=rollover)
+    rel = rel_err(cost_dev, cost_ref)
+    bar, used = 1e-5, 0
+    if rel.max() >= bar:
+        c32 = CO.rollout(so.astype(np.float32), po, a_dev.astype(np.float32), 1.0, fs.astype(np.float32), dtype=np.float32,
+                         rollover=rollover)
+        bar = max(bar, 1.5 * rel_err(c32, cost_ref).max())
+        used = int((rel >= 1e-5).sum())
+        print(f"  {name} N={N}: {used} samples beyond 1e-5 (max {rel.max():.3e}; fp32 oracle vs fp64 {rel_err(c32, cost_ref).max():.3e})")
+        assert used <= max(2, N // 4096), (name, N, used)
+    assert rel.max() < bar, (name, N, rel.max(), bar)
+    a_ref, _ = R.softmax_update(cost_ref, a_dev, float(lam), 1.0, am)
+    gap = np.diff(np.sort(cost_ref)[:2])[0]
+    err = np.abs(a_mean_new_t.cpu().numpy().reshape(32, 4) - a_ref).max()
+    print(f"  {name} N={N}: max rel cost err {rel.max():.3e}, mean err {err:.3e}, top-2 gap {gap:.3e}")
+    assert err < 1e-4 or gap < 1e-3 * float(lam) / 0.01, (name, N, err, gap)
+    return used
+
+
+@pytest.mark.parametrize("name,N", [("mppi", 1024), ("covo-offline", 4096)])
+def test_batched_mode_step_against_the_oracle(name, N):
+    """One batch of 6 instances per mode against oracle/ directly (not only against the sibling path): every instance's costs
+    against the C fp64 rollout with that instance's parameters, state and -- MPPI -- shared disturbance draw, and its new mean
+    against ref_np.softmax_update of the oracle's costs.  covo-offline builds its tables through the batched controller's own
+    reset()."""
+    lam, E = "0.01", 6
+    env = _env()
+    inst = _instances(env, name, N, lam, E, seed=7)
+    b = _batched(env, name, inst, N, lam)
+    b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
+    if name == "covo-offline":
+        b.reset([i["state"] for i in inst], [i["params"] for i in inst], [i["reset_key"] for i in inst])
+    total = 0
+    for step in range(2):
+        k_acts = []
+        for i in inst:
+            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
+            k_acts.append(np.asarray(k_act))
+        am_before = b.a_mean.cpu().numpy().copy()
+        noisy = [i["info"]["noisy_state"] for i in inst]
+        u_b = b(noisy, np.stack(k_acts)).clone()
+        torch.cuda.synchronize()
+        for e, i in enumerate(inst):
+            total += _oracle_check_instance(name, env, i["params"], noisy[e], am_before[e], k_acts[e], b._a[e], b._cost[e],
+                                            b.a_mean[e], lam)
+            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u_b[e].cpu().numpy(), i["params"])
+    print(f"{name}: {total} samples in all used the widened bar")
+
+
+@pytest.mark.parametrize("name,N", [("mppi", 1024), ("covo-offline", 2048)])
+def test_run_episode_batched_mode_equals_per_instance_episodes(name, N):
+    """covo_run_episode_batched_mode, 40 steps on 8 instances in two segments, against 8 per-instance episodes of the single
+    controller with the same keys: logs, means, final states, key chains (and MPPI's covariances) bit-identical.  Instance 3 starts
+    at step 285 of its episode: it terminates and auto-resets inside the segment.  covo-offline: the batched reset()'s tables
+    equal those of 8 single CoVOController.reset calls."""
+    import covo_mpc_amd as cm
+    E, n, lam = 8, 40, "0.01"
+    env = _env()
+    inst = _instances(env, name, N, lam, E, seed=50, warm=False)
+    params = [i["params"] for i in inst]
+    b = _batched(env, name, inst, N, lam)
+    reset_keys = [cr.PRNGKey(150 + e) for e in range(E)]
+    ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
+    late = torch.tensor([285], dtype=torch.int32, device=DEV).view(torch.float32)
+    ep.true[3, ST_TIME:ST_TIME + 1] = late
+    ep.noisy[3, ST_TIME:ST_TIME + 1] = late
+    table_keys = [cr.PRNGKey(250 + e) for e in range(E)]
+    if name == "covo-offline":
+        with pytest.raises(RuntimeError, match="call controller.reset"):
+            b.run_episode(ep, np.zeros((E, 2), dtype=np.uint32), 1)
+        b.reset(ep.states0, params, table_keys)
+    rngs0 = np.stack([np.asarray(cr.PRNGKey(160 + e)) for e in range(E)])
+    rngs = b.run_episode(ep, rngs0, n // 2)
+    rngs = b.run_episode(ep, rngs, n - n // 2)
+    log = ep.read_log()
+    assert log.shape == (E, n, 4)
+    assert log[3, :, 3].sum() >= 1 and log[0, :, 3].sum() == 0  # instance 3 finished its episode inside the segment
+    for e, i in enumerate(inst):
+        c = i["c"]
+        c.alias_outputs = True
+        se = cm.envs.DeviceEpisode(env, reset_keys[e], params[e], (c.core.lib, c.core.h), DEV)
+        if e == 3:
+            se.true[ST_TIME:ST_TIME + 1] = late
+            se.noisy[ST_TIME:ST_TIME + 1] = late
+        cp = c.reset(se.state0, params[e], c.init_control_params, table_keys[e])
+        if name == "covo-offline":
+            assert torch.equal(cp.a_cov_offline, b.a_cov_offline[e]) and torch.equal(cp.a_chol_offline, b.a_chol_offline[e]), e
+        cp, rng = c.run_episode(se, params[e], cp, rngs0[e], n)
+        assert np.array_equal(se.read_log(), log[e]), e
+        assert torch.equal(cp.a_mean.reshape(-1), b.a_mean[e]) and torch.equal(se.true, ep.true[e]), e
+        if name == "mppi":
+            assert torch.equal(cp.a_cov, b.a_cov[e]), e
+        assert np.array_equal(np.asarray(rng, dtype=np.uint32), rngs[e]), e
+
+
+def test_batched_mode_refusals_name_the_condition_and_leave_the_handle_usable():
+    """What the batched fused launch does not take is refused by argument checks, before any launch, with a message that names the
+    condition; the handle works afterwards."""
+    import covo_mpc_amd as cm
+    from covo_mpc_amd.dynamics import utils
+    N, lam, E = 256, "0.01", 2
+
+    def build(env, name="mppi", n=N, **kw):
+        inst = _instances(env, name, n, lam, E, warm=False)
+        cp0 = inst[0]["cp"]
+        if name == "mppi":
+            b = cm.controllers.BatchedMPPIController(env, E, n, 32, 0.01, sigmas=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, **kw)
+        else:
+            b = cm.controllers.BatchedCoVOController(env, E, n, 32, 0.01, a_mean_init=cp0.a_mean, device=DEV, mode="offline")
+        b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
+        return b, inst
+
+    keys = np.arange(2 * E, dtype=np.uint32).reshape(E, 2) + 1
+    # gamma_sigma != 0: the constructor, and the C boundary for a caller that sets the field itself
+    with pytest.raises(NotImplementedError, match="gamma_sigma"):
+        cm.controllers.BatchedMPPIController(_env(), E, N, 32, 0.01, gamma_sigma=0.2, device=DEV)
+    b, inst = build(_env())
+    noisy = [i["info"]["noisy_state"] for i in inst]
+    b._args.gamma_sigma = 0.2
+    with pytest.raises(_lib.CovoError, match="gamma_sigma != 0"):
+        b(noisy, keys)
+    b._args.gamma_sigma = 0.0
+    # more instances than COVO_MAX_ENVS
+    with pytest.raises(ValueError, match="n_envs"):
+        cm.controllers.BatchedMPPIController(_env(), _lib.COVO_MAX_ENVS + 1, N, 32, 0.01, device=DEV)
+    b._args.base.n_envs = _lib.COVO_MAX_ENVS + 1
+    with pytest.raises(_lib.CovoError, match="n_envs=65"):
+        b(noisy, keys)
+    b._args.base.n_envs = E
+    # ... and the handle still works: the refused calls launched nothing and left nothing behind
+    u = b(noisy, keys).clone()
+    assert torch.isfinite(u).all() and b.core.device_status() == 0
+    # the realworld reward
+    env_r = _env()
+    env_r.reward_fn = utils.tracking_realworld_reward_fn
+    br, inst_r = build(env_r)
+    with pytest.raises(_lib.CovoError, match="realworld reward"):
+        br([i["info"]["noisy_state"] for i in inst_r], keys)
+    # a disturbance model with per-step tables
+    bp, inst_p = build(_env(disturb="periodic"))
+    with pytest.raises(_lib.CovoError, match="per-step tables"):
+        bp([i["info"]["noisy_state"] for i in inst_p], keys)
+    # N > 16 384
+    bn, inst_n = build(_env(), n=16384 + 64)
+    with pytest.raises(_lib.CovoError, match="16384"):
+        bn([i["info"]["noisy_state"] for i in inst_n], keys)
+    # covo-offline without a table: the controller, and the C boundary
+    bo, inst_o = build(_env(), name="covo-offline")
+    with pytest.raises(RuntimeError, match="a_cov_offline table missing"):
+        bo([i["info"]["noisy_state"] for i in inst_o], keys)
+    bo.a_chol_offline = torch.zeros(1, device=DEV)  # (past the controller's own check; the argument block still has no table)
+    with pytest.raises(_lib.CovoError, match="table is missing"):
+        bo([i["info"]["noisy_state"] for i in inst_o], keys)
+    # covo_debug_time_batched replays covo-online's launch groups only
+    with pytest.raises(_lib.CovoError, match="covo_mpc_step_batched first"):
+        b.time_phases(16)
+    for c in (b, br, bp, bn, bo):
+        assert c.core.device_status() == 0
+    u2 = b(noisy, keys)
+    assert torch.isfinite(u2).all()
