@@ -22,7 +22,9 @@ COVO_RANK_RECORD_FLOATS = COVO_PARTIAL_FLOATS + 2 * COVO_POS_STATS_DOUBLES  # 51
 COVO_COV_FLOATS = COVO_H * 10
 COVO_RANK_RECORD_COV_FLOATS = COVO_PARTIAL_FLOATS + COVO_COV_FLOATS + 2 * COVO_POS_STATS_DOUBLES  # 836: with MPPI's second moments
 COVO_EXCHANGE_HANDLE_BYTES = 128
-ABI_VERSION = 9
+ABI_VERSION = 10
+COVO_DIAG_FLOATS = 8  # per-step sampling diagnostics of one instance (covo_set_step_diag)
+DIAG_FIELDS = ("ess", "cost_min", "cost_weighted", "cost_mean", "weight_sum", "n_samples")
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -150,6 +152,8 @@ _SIGS = {
     "covo_debug_set_stream_gemm": (C.c_int, [_P, C.c_int]),
     "covo_debug_set_ns_coherence": (C.c_int, [_P, C.c_int]),
     "covo_debug_set_ns_merged": (C.c_int, [_P, C.c_int]),
+    "covo_set_step_diag": (C.c_int, [_P, _P, C.c_int32]),             # per-step sampling diagnostics (covo_hip.h)
+    "covo_set_episode_diag_log": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),

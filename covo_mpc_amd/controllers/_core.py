@@ -52,7 +52,7 @@ def exchange_records(record, gathered_flat, process_group=None):
 class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
-                 cov_records: bool = False, propagate_nan=None):
+                 cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1):
         import torch
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
@@ -138,6 +138,17 @@ class SamplingCore:
         self.stats = self.record[n_part:].view(torch.float64)  # this shard's sums (528- / 1 808-byte offset: 8-aligned)
         self.gathered = torch.zeros((self.world * self.rec_floats,), **f32) if self.world > 1 else None
         self.stats_total = torch.zeros((COVO_POS_STATS_DOUBLES,), dtype=torch.float64, device=self.device) if self.world > 1 else self.stats
+        # compute_diag: every step also leaves its sampling diagnostics {ess, cost_min, cost_weighted, cost_mean, weight_sum,
+        # n_samples, 0, 0} in self.diag (row e = instance e of a batched step) -- formed by the update's own launches
+        # (covo_set_step_diag); off by default, and off changes nothing
+        self.compute_diag = bool(compute_diag)
+        self.diag = None
+        if self.compute_diag:
+            if self.world > 1:
+                raise NotImplementedError("compute_diag on sample-sharded ranks: the rank records carry no diagnostic sums "
+                                          "(covo_set_step_diag refuses sample-sharded steps)")
+            self.diag = torch.zeros((int(diag_rows), _lib.COVO_DIAG_FLOATS), **f32)
+            check(self.lib.covo_set_step_diag(self.h, ptr(self.diag), int(diag_rows)), "covo_set_step_diag")
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -271,6 +282,26 @@ class SamplingCore:
                                             ptr(self.stats_total) if self.compute_info else None, self.stream()),
               "covo_merge_ranks_cov")
         return out_mean, out_cov
+
+    def diag_info(self) -> dict:
+        """{"ess", "cost_min", "cost_weighted", "cost_mean"} of the last step as 0-d views of self.diag (no sync, no copy); {} when
+        the core was built without compute_diag."""
+        if self.diag is None:
+            return {}
+        return {name: self.diag[0, i] for i, name in enumerate(_lib.DIAG_FIELDS[:4])}
+
+    def require_fused_for_diag(self):
+        if self.compute_diag:
+            raise NotImplementedError("compute_diag is formed by the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') does not produce it")
+
+    def attach_diag_log(self, episode, rows_left: int):
+        """Bind `episode`'s diagnostic log (allocated on first use) for the segment that starts at episode.n_steps."""
+        if not self.compute_diag:
+            return
+        if getattr(episode, "diag_log", None) is None:
+            episode.alloc_diag_log()
+        check(self.lib.covo_set_episode_diag_log(self.h, ptr(episode.diag_log_view()), int(rows_left)), "covo_set_episode_diag_log")
 
     def device_status(self, clear: bool = False) -> int:
         """Sticky COVO_DEVSTAT_* bits raised by kernels of earlier calls (0 = fine); no synchronisation."""
@@ -482,6 +513,8 @@ class SamplingCore:
         args, am, _, cov_out = self._prepare_step(mode, episode.noisy_state, a_mean, derive_keys=True, carry_only=True, **kw)
         key = (C.c_uint32 * 2)(int(rng[0]), int(rng[1]))
         env = episode.env
+        # compute_diag: step k of the segment also writes row n_steps + k of the episode's [T + 1, 8] diagnostic log
+        self.attach_diag_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # the env step's auto-reset (base.py:22-40) is a property of the EPISODE, the model constants come from the controller
         params_c = type(params_c).from_buffer_copy(params_c)
         for f in ("reset_traj", "reset_dt", "reset_disturb_scale"):

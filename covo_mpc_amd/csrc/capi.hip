@@ -94,6 +94,8 @@ int covo_create(const covo_config *cfg, covo_handle_t *out)
     const int nb = (cfg->n_local + 255) / 256, ng = (cfg->n_local + 63) / 64;
     COVO_CHECK_HIP(hipMalloc(&h->ws_partials, (size_t)h->max_red_blocks * COVO_PARTIAL_FLOATS * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->ws_partials_cov, softmax_cov_workspace_floats(h->max_red_blocks) * sizeof(float)));
+    COVO_CHECK_HIP(hipMalloc(&h->ws_diag_rec, (size_t)h->max_red_blocks * 4 * sizeof(float)));
+    COVO_CHECK_HIP(hipMalloc(&h->diag_scratch, (size_t)COVO_MAX_ENVS * COVO_DIAG_FLOATS * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->ws_blockmin, (size_t)ng * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->ws_stats, (size_t)(nb > 256 ? nb : 256) * COVO_H * 6 * sizeof(double)));  // one row per rollout workgroup
     h->ws_sigma_bytes = sigma_ns_workspace_bytes(1);
@@ -127,6 +129,8 @@ int covo_destroy(covo_handle_t h)
     } while (0)
     DESTROY(hipFree(h->ws_partials));
     DESTROY(hipFree(h->ws_partials_cov));
+    DESTROY(hipFree(h->ws_diag_rec));
+    DESTROY(hipFree(h->diag_scratch));
     DESTROY(hipFree(h->ws_blockmin));
     DESTROY(hipFree(h->ws_stats));
     DESTROY(hipFree(h->ws_sigma));
@@ -556,6 +560,41 @@ int covo_debug_set_ns_coherence(covo_handle_t h, int force_agent)
     return 0;
 }
 
+// ---- per-step sampling diagnostics.  The captured step graphs bake in where the steps write: a change of that target bumps the
+// epoch like a debug switch (attaching the episode log next to a step buffer changes no launch of a step: its rows are copied by
+// an eager launch of the episode drivers)
+int covo_set_step_diag(covo_handle_t h, float *diag, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_diag: null handle");
+    REQUIRE(diag == nullptr || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_diag: n_inst=%d outside (0, %d]", n_inst,
+            COVO_MAX_ENVS);
+    const float *before = covo_diag_target(h);
+    h->diag_out = diag;
+    h->diag_n = diag ? n_inst : 0;
+    if (covo_diag_target(h) != before) ++h->opt.epoch;
+    return 0;
+}
+
+int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_diag_log: null handle");
+    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_diag_log: stride=%d", stride);
+    const float *before = covo_diag_target(h);
+    h->diag_log = log;
+    h->diag_log_stride = log ? stride : 0;
+    if (covo_diag_target(h) != before) ++h->opt.epoch;
+    return 0;
+}
+
+// a step for n_inst instances with diagnostics attached: the buffer has a row for each
+#define CHECK_DIAG(h, n_inst, what)                                                                                       \
+    REQUIRE(covo_diag_target(h) == nullptr || (n_inst) <= covo_diag_capacity(h),                                          \
+            "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, (int)(n_inst), covo_diag_capacity(h))
+#define REFUSE_SHARDED_DIAG(h, args, what)                                                                                \
+    REQUIRE((args)->partial_out == nullptr || covo_diag_target(h) == nullptr,                                             \
+            "%s: sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log) are not available for sample-sharded "   \
+            "steps (partial_out != NULL): the rank records carry no diagnostic sums; detach the buffer", what)
+
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)
 {
     REQUIRE(h && out, "covo_debug_sigma_workspace: bad argument");
@@ -624,6 +663,9 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin &&
                 args->T > 0 && args->mode >= 0 && args->mode <= 2,
             "covo_run_episode: bad step arguments");
+    REFUSE_SHARDED_DIAG(h, args, "covo_run_episode");
+    REQUIRE(h->diag_log == nullptr || n_steps <= h->diag_log_stride, "covo_run_episode: %d steps, the diagnostic log "
+            "(covo_set_episode_diag_log) has %d rows", n_steps, h->diag_log_stride);
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -652,6 +694,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
                     return rc;
             }
         }
+        if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, 1, h->diag_log_stride, t, s))) return rc;
         rc = launch_env_step(state_true, const_cast<float *>(args->state), args->pos_traj, args->vel_traj, acc_traj, args->T,
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
@@ -757,6 +800,10 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
     rc = check_batch_models(params, E, what);
     if (rc) return rc;
+    CHECK_DIAG(h, E, what);
+    REQUIRE(h->diag_log == nullptr || (log_index >= 0 && log_index + n_steps <= h->diag_log_stride),
+            "%s: diagnostic log rows [%d, %d) outside [0, %d) (covo_set_episode_diag_log)", what, log_index, log_index + n_steps,
+            h->diag_log_stride);
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -772,6 +819,8 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             host_philox_split(nrng, 0u, &next[2 * e]);
         }
         if ((rc = online ? covo_step_batched_impl(h, args, params, act_keys, s) : covo_step_batched_small_impl(h, &norm, params, act_keys, s)))
+            return rc;
+        if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, E, h->diag_log_stride, log_index + t, s)))
             return rc;
         if ((rc = launch_env_step_batched(states_true, const_cast<float *>(args->states), args->pos_traj, args->vel_traj, acc_traj,
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
@@ -813,6 +862,7 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     REQUIRE(args && params && keys, "covo_mpc_step_batched: null argument");
     int rc = check_batch_step(h, args, nullptr, params, "covo_mpc_step_batched", nullptr);
     if (rc) return rc;
+    CHECK_DIAG(h, args->n_envs, "covo_mpc_step_batched");
     return covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream);
 }
 
@@ -825,6 +875,7 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     covo_batch_mode_args norm;
     int rc = check_batch_step(h, &args->base, args, params, "covo_mpc_step_batched_mode", &norm);
     if (rc) return rc;
+    CHECK_DIAG(h, args->base.n_envs, "covo_mpc_step_batched_mode");
     if (args->mode == COVO_MODE_COVO_ONLINE) return covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream);
     return covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
 }
@@ -886,6 +937,7 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
             "covo_mpc_step: gamma_sigma != 0 is MPPI's covariance adaptation (mppi.py:119-125)");
     REQUIRE(!needs_table(params) || args->derive_keys == 1, "covo_mpc_step: disturb_kind=%d needs derive_keys = 1 (the per-step "
             "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
+    REFUSE_SHARDED_DIAG(h, args, "covo_mpc_step");
     return covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);
 }
 

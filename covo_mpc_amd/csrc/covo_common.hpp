@@ -47,7 +47,17 @@ struct covo_ctx {
     int *status_dev;          // its device address
     void *exchange;           // Exchange (exchange.hip): peer-write exchange of the rank records, or null
     int dbg_epoch;            // opt.epoch when this handle's step graphs were captured (a debug setter since then: re-capture)
+    // per-step sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log); all null / 0: off
+    float *diag_out;          // caller's [diag_n][COVO_DIAG_FLOATS]: instance e's row of every step
+    int diag_n;
+    float *diag_log;          // caller's [n_inst][diag_log_stride][COVO_DIAG_FLOATS]: the episode drivers copy each step's rows there
+    int diag_log_stride;
+    float *diag_scratch;      // [COVO_MAX_ENVS][COVO_DIAG_FLOATS]: where the steps write when only the log is attached
+    float *ws_diag_rec;       // [max_blocks][4] stage-1 diagnostic records next to ws_partials (softmax_merge.hpp)
 };
+// where the steps of this handle write their diagnostics (null: off) and for how many instances
+static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->diag_log ? h->diag_scratch : nullptr); }
+static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->diag_log ? COVO_MAX_ENVS : 0); }
 
 void covo_set_error(const char *fmt, ...);
 
@@ -163,7 +173,8 @@ int launch_rollout(const float *state, const float *pos_traj, const float *vel_t
                    float *records = nullptr, float lam = 0.0f,   // records: one online-softmax record per workgroup (rollout.hip)
                    const float *f_tab = nullptr,                 // [H][4] per-step disturbance table (disturb.hip), device
                    int xcd_groups = 0,    // 64-sample groups per workgroup of the kernel that wrote `a` (0: the noise GEMM's for this N)
-                   bool propagate_nan = false);  // the re-clip of untrusted stripes keeps a NaN (COVO_FLAG_PROPAGATE_NAN)
+                   bool propagate_nan = false,  // the re-clip of untrusted stripes keeps a NaN (COVO_FLAG_PROPAGATE_NAN)
+                   float *diag_rec = nullptr);  // with records: one diagnostic record per workgroup next to them (softmax_merge.hpp)
 int launch_disturb_table(const covo_env_params &p, const float *state, int batch, const uint32_t *keys_dev, uint32_t key0,
                          uint32_t key1, int key_mode, int deterministic, float *out, hipStream_t s);
 int launch_disturb_tables_step(const covo_env_params &p, const float *state, const uint32_t *dyn, int rollout_deterministic,
@@ -179,15 +190,17 @@ size_t rollout_args_bytes(int n);
 void rollout_fill_args(void *out, int index, const float *state, const float *pos_traj, const float *vel_traj, int T,
                        const covo_env_params &p, const float *a, int N, float discount, float *cost, float *groupmin,
                        const float *f_shared_dev, float *records = nullptr, float lam = 0.0f, bool trust_clipped = true,
-                       const float *f_tab = nullptr);
+                       const float *f_tab = nullptr, float *diag_rec = nullptr);
 int launch_rollout_batched(const void *args_host, const void *args_dev, int nbatch, hipStream_t s);
 // a_mean_out != null: finish on this GPU (normalise + blend); else write the merged record to partial_out
 int launch_softmax_reduce(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
                           float *partial_out, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                          hipStream_t s, float *partials_ws = nullptr, int batch = 1);  // batch > 1: dense per-instance slices, own partials_ws
+                          hipStream_t s, float *partials_ws = nullptr, int batch = 1,  // batch > 1: dense per-instance slices, own partials_ws
+                          float *diag_rec = nullptr, float *diag_out = nullptr);  // diag_out: [batch][COVO_DIAG_FLOATS] (with a_mean_out), diag_rec: scratch [batch][blocks][4]
 // a_mean_out == null: the merged record goes to partial_out (sample-sharded step); batch > 1: dense per-instance slices
 int launch_merge(const float *partials, int G, float lam, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                 hipStream_t s, float *partial_out = nullptr, int batch = 1, int stride = COVO_PARTIAL_FLOATS);
+                 hipStream_t s, float *partial_out = nullptr, int batch = 1, int stride = COVO_PARTIAL_FLOATS,
+                 const float *diag_rec = nullptr, float *diag_out = nullptr, int n_samples = 0);  // diag_out: [batch][COVO_DIAG_FLOATS] from [batch][G][4]
 // exchange.hip: the rank records of a sample-sharded step and their peer-write exchange
 int launch_rank_stats_sum(const float *records, int G, double *out, hipStream_t s, bool cov = false);
 int exchange_create(covo_ctx *h, int world, int rank, void *handle_out);
@@ -201,7 +214,7 @@ int exchange_records(covo_ctx *h, const float *record, float *gathered_dst, cons
 size_t softmax_cov_workspace_floats(int max_blocks);
 int launch_softmax_update_cov(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
                               const float *a_mean_old, float gamma_mean, const float *a_cov_old, float gamma_sigma,
-                              float *a_mean_out, float *a_cov_out, hipStream_t s);
+                              float *a_mean_out, float *a_cov_out, hipStream_t s, float *diag_out = nullptr);
 int launch_softmax_reduce_cov(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
                               const float *a_mean_old, float *record_out, hipStream_t s);
 int launch_merge_cov(const float *records, int G, int stride, float lam, const float *a_mean_old, float gamma_mean,
@@ -288,6 +301,8 @@ int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, 
                             const uint32_t *step_keys, int noisy_on, float obs_noise_scale, float *log, int log_stride,
                             int log_index, hipStream_t s);
 int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_t s, const void **inst_dev);  // step.hip
+// the episode drivers: row e of the step's diagnostics -> row `index` of instance e's diagnostic log
+int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s);
 int launch_env_step(float *state, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,
                     const covo_env_params &p, const float *action, const uint32_t *step_key, int noisy_on,
                     float obs_noise_scale, float *log, int log_index, hipStream_t s);

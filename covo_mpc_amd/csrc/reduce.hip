@@ -38,12 +38,13 @@ __global__ __launch_bounds__(256) void groupmin_kernel(const float *__restrict__
 // rec[COVO_PARTIAL_FLOATS + 10 t + j] = sum_n w_n d_i d_j for the 10 pairs i <= j of step t (cov_pair below).
 constexpr int RD_COV_FLOATS = COVO_H * 10;                                   // 320
 constexpr int RD_COV_RECORD_FLOATS = COVO_PARTIAL_FLOATS + RD_COV_FLOATS;    // 452
-template <bool COV>
-__global__ __launch_bounds__(RD_BLOCK) void softmax_partial_kernel(const float *__restrict__ cost,
-                                                                   const float4 *__restrict__ a, int N,
-                                                                   const float *__restrict__ blockmin, int nbm,
-                                                                   float inv_lam, float *__restrict__ partials,
-                                                                   const float4 *__restrict__ mu)
+// DIAG (covo_set_step_diag): the workgroup also leaves its diagnostic record {sum w^2, sum w (c - m), sum (c - m), samples}
+// (softmax_merge.hpp: MergeDiag; m is the global minimum here) in dpart[workgroup].
+template <bool COV, bool DIAG>
+__device__ __forceinline__ void softmax_partial_body(const float *__restrict__ cost, const float4 *__restrict__ a, int N,
+                                                     const float *__restrict__ blockmin, int nbm, float inv_lam,
+                                                     float *__restrict__ partials, const float4 *__restrict__ mu,
+                                                     float *__restrict__ dpart)
 {
     constexpr int REC = COV ? RD_COV_RECORD_FLOATS : COVO_PARTIAL_FLOATS;
     __shared__ float red[RD_WAVES];
@@ -57,6 +58,7 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_kernel(const float *
         a += y * ((size_t)COVO_H * N);
         blockmin += y * nbm;
         partials += y * gridDim.x * REC;
+        if (DIAG) dpart += y * gridDim.x * MG_DIAG_REC;
     }
 
     // ---- exact global minimum of cost from the per-block minima
@@ -73,6 +75,11 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_kernel(const float *
 #pragma unroll
     for (int i = 0; i < 4; ++i) acc[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     float s_lane = 0.0f;
+    float d_lane[DIAG ? MG_DIAG_REC : 1];
+    if (DIAG) {
+#pragma unroll
+        for (int j = 0; j < MG_DIAG_REC; ++j) d_lane[j] = 0.0f;
+    }
     float acc2[COV ? 4 : 1][10];  // COV: pairs (0,0) (0,1) (0,2) (0,3) (1,1) (1,2) (1,3) (2,2) (2,3) (3,3) of steps 8 tb + tq
     float4 mu4[COV ? 4 : 1];
     if (COV) {
@@ -89,6 +96,13 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_kernel(const float *
         const float c = (n < N) ? cost[n] : __builtin_inff();
         const float w = expf((m - c) * inv_lam);  // covo.py:266
         s_lane += w;
+        if (DIAG && n < N) {  // every product rounded on its own: no contraction into the sums
+            const float dc = c - m;
+            d_lane[0] += __fmul_rn(w, w);
+            d_lane[1] += __fmul_rn(w, dc);
+            d_lane[2] += dc;
+            d_lane[3] += 1.0f;
+        }
         const unsigned long long live = __ballot(w > 0.0f);
         if (live == 0ull) continue;
 #pragma unroll
@@ -159,8 +173,38 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_kernel(const float *
         rec[0] = m;
         rec[1] = (ss[0] + ss[1]) + (ss[2] + ss[3]);
     }
+    if constexpr (DIAG) {
+        __shared__ float sd[RD_WAVES][MG_DIAG_REC];
+#pragma unroll
+        for (int j = 0; j < MG_DIAG_REC; ++j) {
+            const float d = wave_sum(d_lane[j]);
+            if (lane == 0) sd[wave][j] = d;
+        }
+        __syncthreads();
+        if (tid < MG_DIAG_REC)  // the waves' sums in ascending order
+            dpart[(size_t)blockIdx.x * MG_DIAG_REC + tid] = ((sd[0][tid] + sd[1][tid]) + sd[2][tid]) + sd[3][tid];
+    }
 }
 
+
+template <bool COV>
+__global__ __launch_bounds__(RD_BLOCK) void softmax_partial_kernel(const float *__restrict__ cost,
+                                                                   const float4 *__restrict__ a, int N,
+                                                                   const float *__restrict__ blockmin, int nbm,
+                                                                   float inv_lam, float *__restrict__ partials,
+                                                                   const float4 *__restrict__ mu)
+{
+    softmax_partial_body<COV, false>(cost, a, N, blockmin, nbm, inv_lam, partials, mu, nullptr);
+}
+template <bool COV>
+__global__ __launch_bounds__(RD_BLOCK) void softmax_partial_diag_kernel(const float *__restrict__ cost,
+                                                                        const float4 *__restrict__ a, int N,
+                                                                        const float *__restrict__ blockmin, int nbm,
+                                                                        float inv_lam, float *__restrict__ partials,
+                                                                        const float4 *__restrict__ mu, float *__restrict__ dpart)
+{
+    softmax_partial_body<COV, true>(cost, a, N, blockmin, nbm, inv_lam, partials, mu, dpart);
+}
 
 // index of the pair (i, j), i <= j, in a record's 10 second moments per step
 __device__ __forceinline__ int cov_pair(int i, int j)
@@ -305,6 +349,45 @@ __global__ __launch_bounds__(MG_THREADS) void merge_kernel(const float *__restri
     merge_body<MG_THREADS, FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds);
 }
 
+// the same, and the diagnostic records dpart [instances][G][MG_DIAG_REC] merged into row x of diag_out [instances][COVO_DIAG_FLOATS]
+template <bool FINAL>
+__global__ __launch_bounds__(MG_THREADS) void merge_diag_kernel(const float *__restrict__ partials, int G, float inv_lam,
+                                                                const float *__restrict__ a_mean_old, float gamma_mean,
+                                                                float *__restrict__ out, int stride, const float *__restrict__ dpart,
+                                                                float *__restrict__ diag_out, float n_samples)
+{
+    __shared__ MergeLds lds;
+    __shared__ float dred[3][MG_VWAVES];
+    const size_t x = blockIdx.x;
+    partials += x * G * stride;
+    if (FINAL) a_mean_old += x * COVO_NA;
+    out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
+    MergeDiag D;
+    D.rec = dpart + x * G * MG_DIAG_REC;
+    D.out = diag_out + x * COVO_DIAG_FLOATS;
+    D.n = n_samples;
+    D.red = dred;
+    merge_body<MG_THREADS, FINAL, false, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds, D);
+}
+
+// the episode drivers (capi.hip): the step's diagnostics [n_inst][COVO_DIAG_FLOATS] -> row `index` of every instance's log
+__global__ void diag_log_rows_kernel(const float *__restrict__ diag, float *__restrict__ log, int n_inst, int stride, int index)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_inst * COVO_DIAG_FLOATS) {
+        const int e = i / COVO_DIAG_FLOATS, j = i % COVO_DIAG_FLOATS;
+        log[((size_t)e * stride + index) * COVO_DIAG_FLOATS + j] = diag[i];
+    }
+}
+
+int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s)
+{
+    const int n = n_inst * COVO_DIAG_FLOATS;
+    hipLaunchKernelGGL(diag_log_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, diag, log, n_inst, stride, index);
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
 __global__ void shift_mean_kernel(const float *__restrict__ in, float *__restrict__ out)
 {
     const int i = threadIdx.x;  // 128 threads; covo.py:201-203
@@ -313,7 +396,7 @@ __global__ void shift_mean_kernel(const float *__restrict__ in, float *__restric
 
 int launch_softmax_reduce(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
                           float *partial_out, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                          hipStream_t s, float *partials_ws, int batch)
+                          hipStream_t s, float *partials_ws, int batch, float *diag_rec, float *diag_out)
 {
     const float inv_lam = 1.0f / h->cfg.lam;
     if (partials_ws == nullptr) partials_ws = h->ws_partials;
@@ -325,6 +408,15 @@ int launch_softmax_reduce(covo_ctx *h, const float *cost, const float *a, int N,
     const int ngroups = (N + 63) / 64;
     int grid = (ngroups + RD_WAVES - 1) / RD_WAVES;
     if (grid > h->max_red_blocks) grid = h->max_red_blocks;
+    if (diag_out != nullptr && a_mean_out != nullptr) {  // the same two launches in their diagnostic variants
+        hipLaunchKernelGGL(softmax_partial_diag_kernel<false>, dim3(grid, batch), dim3(RD_BLOCK), 0, s, cost,
+                           reinterpret_cast<const float4 *>(a), N, blockmin, n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr,
+                           diag_rec);
+        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(batch), dim3(MG_THREADS), 0, s, partials_ws, grid, inv_lam, a_mean_old,
+                           gamma_mean, a_mean_out, COVO_PARTIAL_FLOATS, (const float *)diag_rec, diag_out, (float)N);
+        COVO_CHECK_HIP(hipGetLastError());
+        return 0;
+    }
     hipLaunchKernelGGL(softmax_partial_kernel<false>, dim3(grid, batch), dim3(RD_BLOCK), 0, s, cost,
                        reinterpret_cast<const float4 *>(a), N, blockmin, n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr);
     if (a_mean_out != nullptr)
@@ -341,9 +433,10 @@ int launch_softmax_reduce(covo_ctx *h, const float *cost, const float *a, int N,
 size_t softmax_cov_workspace_floats(int max_blocks) { return (size_t)max_blocks * RD_COV_RECORD_FLOATS; }
 int launch_softmax_update_cov(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
                               const float *a_mean_old, float gamma_mean, const float *a_cov_old, float gamma_sigma,
-                              float *a_mean_out, float *a_cov_out, hipStream_t s)
+                              float *a_mean_out, float *a_cov_out, hipStream_t s, float *diag_out)
 {
     const float inv_lam = 1.0f / h->cfg.lam;
+    const bool diag = diag_out != nullptr && a_cov_out != nullptr;
     if (blockmin == nullptr) {
         n_blockmin = (N + 63) / 64;
         hipLaunchKernelGGL(groupmin_kernel, dim3((N + 255) / 256), dim3(256), 0, s, cost, N, h->ws_blockmin);
@@ -352,8 +445,19 @@ int launch_softmax_update_cov(covo_ctx *h, const float *cost, const float *a, in
     const int ngroups = (N + 63) / 64;
     int grid = (ngroups + RD_WAVES - 1) / RD_WAVES;
     if (grid > h->max_red_blocks) grid = h->max_red_blocks;
-    hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, cost, reinterpret_cast<const float4 *>(a), N,
-                       blockmin, n_blockmin, inv_lam, h->ws_partials_cov, reinterpret_cast<const float4 *>(a_mean_old));
+    if (diag)
+        hipLaunchKernelGGL(softmax_partial_diag_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, cost,
+                           reinterpret_cast<const float4 *>(a), N, blockmin, n_blockmin, inv_lam, h->ws_partials_cov,
+                           reinterpret_cast<const float4 *>(a_mean_old), h->ws_diag_rec);
+    else
+        hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, cost, reinterpret_cast<const float4 *>(a), N,
+                           blockmin, n_blockmin, inv_lam, h->ws_partials_cov, reinterpret_cast<const float4 *>(a_mean_old));
+    // the covariance merge below has its own body: the diagnostics come from one more merge launch over the same headers {m_g, s_g}
+    // (its merged record goes to the idle ws_partials), off the path of a step without diagnostics
+    if (diag)
+        hipLaunchKernelGGL(merge_diag_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam,
+                           (const float *)nullptr, 1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, diag_out,
+                           (float)N);
     if (a_cov_out != nullptr)
         hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam, a_mean_old,
                            gamma_mean, a_cov_old, gamma_sigma, a_mean_out, a_cov_out, RD_COV_RECORD_FLOATS);
@@ -384,10 +488,13 @@ int launch_merge_cov(const float *records, int G, int stride, float lam, const f
 }
 
 int launch_merge(const float *partials, int G, float lam, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                 hipStream_t s, float *partial_out, int batch, int stride)
+                 hipStream_t s, float *partial_out, int batch, int stride, const float *diag_rec, float *diag_out, int n_samples)
 {
     if (G > MG_MAXG) { covo_set_error("covo_merge: G=%d > %d", G, MG_MAXG); return COVO_E_BADARG; }
-    if (a_mean_out != nullptr)
+    if (a_mean_out != nullptr && diag_out != nullptr)
+        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(batch), dim3(MG_THREADS), 0, s, partials, G, 1.0f / lam, a_mean_old, gamma_mean,
+                           a_mean_out, stride, diag_rec, diag_out, (float)n_samples);
+    else if (a_mean_out != nullptr)
         hipLaunchKernelGGL(merge_kernel<true>, dim3(batch), dim3(MG_THREADS), 0, s, partials, G, 1.0f / lam, a_mean_old, gamma_mean,
                            a_mean_out, stride);
     else

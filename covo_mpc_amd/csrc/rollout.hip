@@ -76,6 +76,8 @@ void fill_rollout_args(RolloutArgs &A, const float *state, const float *pos_traj
     A.merge_mean_old = nullptr;
     A.merge_gamma = 1.0f;
     A.merge_final = 0;
+    A.diag_rec = nullptr;
+    A.diag_out = nullptr;
     A.clip = 1;
     A.rollover = p.rollover_terminate != 0;
     A.reward = p.reward_kind;
@@ -121,7 +123,7 @@ static int dispatch_rollout(const RolloutArgs &A, const RolloutArgs *batch, int 
 int launch_rollout(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
                    const float *f_shared, const float *a, int N, float discount, bool trust_clipped, float *cost,
                    float *groupmin, double *pos_stats, double *stats_ws, hipStream_t s, const float *f_shared_dev,
-                   float *records, float lam, const float *f_tab, int xcd_groups, bool propagate_nan)
+                   float *records, float lam, const float *f_tab, int xcd_groups, bool propagate_nan, float *diag_rec)
 {
     RolloutArgs A;
     fill_rollout_args(A, state, pos_traj, vel_traj, T, p, f_shared, a, N, discount, cost, groupmin, stats_ws, f_shared_dev, f_tab,
@@ -137,6 +139,7 @@ int launch_rollout(const float *state, const float *pos_traj, const float *vel_t
     A.clip = trust_clipped ? 0 : (propagate_nan ? 2 : 1);
     A.records = records;
     A.inv_lam = records ? 1.0f / lam : 0.0f;
+    A.diag_rec = records ? diag_rec : nullptr;
     return dispatch_rollout<false>(A, nullptr, 0, pos_stats, s);
 }
 
@@ -154,7 +157,7 @@ size_t rollout_args_bytes(int n) { return (size_t)n * sizeof(RolloutArgs); }
 
 void rollout_fill_args(void *out, int index, const float *state, const float *pos_traj, const float *vel_traj, int T,
                        const covo_env_params &p, const float *a, int N, float discount, float *cost, float *groupmin,
-                       const float *f_shared_dev, float *records, float lam, bool trust_clipped, const float *f_tab)
+                       const float *f_shared_dev, float *records, float lam, bool trust_clipped, const float *f_tab, float *diag_rec)
 {
     RolloutArgs &A = reinterpret_cast<RolloutArgs *>(out)[index];
     // f_tab: this instance's rows of the step's disturbance tables (periodic / sin / drag / mixed; all instances share the kind)
@@ -162,6 +165,7 @@ void rollout_fill_args(void *out, int index, const float *state, const float *po
     A.clip = trust_clipped ? 0 : 1;
     A.records = records;
     A.inv_lam = records ? 1.0f / lam : 0.0f;
+    A.diag_rec = records ? diag_rec : nullptr;
 }
 
 // every instance must share instance 0's N, discount, clip, rollover, reward and disturbance kind (checked by the caller)

@@ -38,6 +38,9 @@ struct RolloutArgs {
     const float *merge_mean_old;
     float merge_gamma;
     int merge_final;
+    // the per-step sampling diagnostics (covo_set_step_diag; null: off -- only the DIAG kernel variants read these)
+    float *diag_rec;  // [workgroups][MG_DIAG_REC] stage-1 diagnostic records, next to `records`
+    float *diag_out;  // the fused small step: where the last workgroup's merge writes the COVO_DIAG_FLOATS of this instance
 };
 
 // rollout.hip: the argument block of one rollout over N samples (the producer of the stripes is the noise GEMM unless
@@ -83,10 +86,14 @@ __device__ __forceinline__ float lane_bcast(float v, int lane)  // v_readlane_b3
 // A_LDS (the fused small step): the workgroup's ONE 64-sample group has its stripes in LDS (a_lds [H][64] float4; lane l owns
 // sample l); coh (wave-uniform): the record is read by another workgroup of the SAME launch (the last arriver merges): agent-scope
 // relaxed atomic stores (write-through, coherent across the XCDs' L2s), as the Sigma chain's persistent launches publish their tiles.
-template <int NWAVES, int NW, bool A_LDS = false>
+// DIAG: the carrier waves also reduce w^2, w (c - m) and (c - m) over their valid lanes; the workgroup adds its NW waves' sums in
+// ascending order (s_d: LDS [NW][MG_DIAG_REC]) and stores them as its diagnostic record, A.diag_rec[wg], with the record's own
+// store discipline (softmax_merge.hpp: MergeDiag).
+template <int NWAVES, int NW, bool A_LDS = false, bool DIAG = false>
 __device__ __forceinline__ void rollout_record(const RolloutArgs &A, float cost, bool valid, int n, int wave, bool carrier, int lane,
                                                int wg, float *s_m, float *s_s, float (*s_v)[COVO_NA],
-                                               const float4 *__restrict__ a_lds = nullptr, const bool coh = false)
+                                               const float4 *__restrict__ a_lds = nullptr, const bool coh = false,
+                                               float (*s_d)[MG_DIAG_REC] = nullptr)
 {
     // (round 4: the waves that carry no cost -- two of three per SIMD in the pipelined kernel -- only take part in the two
     // barriers and the final stores; they used to run the whole epilogue on zero weights next to the one wave that matters)
@@ -101,6 +108,17 @@ __device__ __forceinline__ void rollout_record(const RolloutArgs &A, float cost,
     if (carrier) {
     const float w = valid ? expf((m - cost) * A.inv_lam) : 0.0f;
     const float sw = wave_sum(w);
+    if (DIAG) {
+        const float dc = valid ? cost - m : 0.0f;
+        const float s2 = wave_sum(w * w), swc = wave_sum(w * dc), sc = wave_sum(dc);
+        const float cnt = (float)__popcll(__ballot(valid));
+        if (lane == 0) {
+            s_d[wave][0] = s2;
+            s_d[wave][1] = swc;
+            s_d[wave][2] = sc;
+            s_d[wave][3] = cnt;
+        }
+    }
     unsigned long long live = __ballot(w > 0.0f);
     const int t = lane & 31, half = lane >> 5;  // lane -> action stripe t; the two half-waves take alternate live samples
     float4 acc = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
@@ -166,6 +184,15 @@ __device__ __forceinline__ void rollout_record(const RolloutArgs &A, float cost,
             rec[1] = ss;
         }
     }
+    if (DIAG && tid >= COVO_WAVE && tid < COVO_WAVE + MG_DIAG_REC) {  // (wave 1: thread 0 has the record's header to store)
+        const int j = tid - COVO_WAVE;
+        float d = s_d[0][j];
+#pragma unroll
+        for (int i = 1; i < NW; ++i) d += s_d[i][j];
+        float *drec = A.diag_rec + (size_t)wg * MG_DIAG_REC;
+        if (coh) __hip_atomic_store(drec + j, d, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        else drec[j] = d;
+    }
 }
 
 // (step_small.hip only since round 6; the same inside the product rollout launch measured slower at every size and was removed:
@@ -182,6 +209,25 @@ __device__ __forceinline__ void rollout_merge_last(const RolloutArgs &A, MergeLd
     if (!last_flag) return;
     if (A.merge_final) merge_body<THREADS, true, true>(A.records, (int)gridDim.x, A.inv_lam, A.merge_mean_old, A.merge_gamma, A.merge_out, COVO_PARTIAL_FLOATS, M);
     else merge_body<THREADS, false, true>(A.records, (int)gridDim.x, A.inv_lam, nullptr, 1.0f, A.merge_out, COVO_PARTIAL_FLOATS, M);
+}
+
+// the same with the diagnostic records merged too (always the final update: a sample-sharded step with diagnostics is refused);
+// red: LDS [3][MG_VWAVES] that nothing else uses during the merge
+template <int THREADS>
+__device__ __forceinline__ void rollout_merge_last_diag(const RolloutArgs &A, MergeLds &M, int &last_flag, float (*red)[MG_VWAVES])
+{
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    __syncthreads();
+    if (threadIdx.x == 0) last_flag = (atomicInc(A.merge_ticket, gridDim.x - 1) == gridDim.x - 1) ? 1 : 0;
+    __syncthreads();
+    if (!last_flag) return;
+    MergeDiag D;
+    D.rec = A.diag_rec;
+    D.out = A.diag_out;
+    D.n = (float)A.N;
+    D.red = red;
+    merge_body<THREADS, true, true, true>(A.records, (int)gridDim.x, A.inv_lam, A.merge_mean_old, A.merge_gamma, A.merge_out,
+                                          COVO_PARTIAL_FLOATS, M, D);
 }
 
 #ifdef ROLLOUT_LAB_BASELINE  // the one-lane-per-sample kernel of round 1: only scripts/probe/rollout_lab.hip still compiles it

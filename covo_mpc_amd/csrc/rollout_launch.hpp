@@ -11,26 +11,28 @@ static inline int pipe_groups(int N, int nbatch)
     return ng > 256 ? 2 : 1;
 }
 
-template <bool DISC1, bool ROLL, bool BATCHED, bool STATS, bool REC, int REWARD, int FDIST>
+template <bool DISC1, bool ROLL, bool BATCHED, bool STATS, bool REC, int REWARD, int FDIST, bool DIAG = false>
 static void launch_pipe3_groups(const RolloutArgs &A, const RolloutArgs *batch, int nb, int groups, hipStream_t s)
 {
     const int ng = (A.N + COVO_WAVE - 1) / COVO_WAVE;
     const dim3 grid((ng + groups - 1) / groups, nb);
     if (groups == 4)
-        hipLaunchKernelGGL((rollout_pipe3_kernel<DISC1, ROLL, 2, 4, BATCHED, -1, 3, STATS, REC, REWARD, FDIST>), grid, dim3(3 * 4 * COVO_WAVE), 0, s, A, batch);
+        hipLaunchKernelGGL((rollout_pipe3_kernel<DISC1, ROLL, 2, 4, BATCHED, -1, 3, STATS, REC, REWARD, FDIST, DIAG>), grid, dim3(3 * 4 * COVO_WAVE), 0, s, A, batch);
     else if (groups == 2)
-        hipLaunchKernelGGL((rollout_pipe3_kernel<DISC1, ROLL, 2, 2, BATCHED, -1, 3, STATS, REC, REWARD, FDIST>), grid, dim3(3 * 2 * COVO_WAVE), 0, s, A, batch);
+        hipLaunchKernelGGL((rollout_pipe3_kernel<DISC1, ROLL, 2, 2, BATCHED, -1, 3, STATS, REC, REWARD, FDIST, DIAG>), grid, dim3(3 * 2 * COVO_WAVE), 0, s, A, batch);
     else
-        hipLaunchKernelGGL((rollout_pipe3_kernel<DISC1, ROLL, 2, 1, BATCHED, -1, 3, STATS, REC, REWARD, FDIST>), grid, dim3(3 * COVO_WAVE), 0, s, A, batch);
+        hipLaunchKernelGGL((rollout_pipe3_kernel<DISC1, ROLL, 2, 1, BATCHED, -1, 3, STATS, REC, REWARD, FDIST, DIAG>), grid, dim3(3 * COVO_WAVE), 0, s, A, batch);
 }
 
 // the run-time switches of one (DISC1, BATCHED, REWARD, FDIST) family: rollover termination, position statistics (never
-// batched), softmax records (A.records, all instances of a batch alike)
+// batched), softmax records (A.records, all instances of a batch alike), the diagnostic records next to them (A.diag_rec)
 template <bool DISC1, bool BATCHED, int REWARD, int FDIST>
 static void launch_pipe3_family(const RolloutArgs &A, const RolloutArgs *batch, int nb, int groups, bool stats, hipStream_t s)
 {
     const bool rec = A.records != nullptr;
-#define RP3_GO(ROLL, STATS, REC) launch_pipe3_groups<DISC1, ROLL, BATCHED, STATS, REC, REWARD, FDIST>(A, batch, nb, groups, s)
+    const bool diag = rec && A.diag_rec != nullptr;
+#define RP3_GO1(ROLL, STATS, REC, DIAG) launch_pipe3_groups<DISC1, ROLL, BATCHED, STATS, REC, REWARD, FDIST, DIAG>(A, batch, nb, groups, s)
+#define RP3_GO(ROLL, STATS, REC) do { if (REC && diag) RP3_GO1(ROLL, STATS, REC, REC); else RP3_GO1(ROLL, STATS, REC, false); } while (0)
     if constexpr (!BATCHED) {
         if (stats) {
             if (A.rollover) { if (rec) RP3_GO(true, true, true); else RP3_GO(true, true, false); }
@@ -41,6 +43,7 @@ static void launch_pipe3_family(const RolloutArgs &A, const RolloutArgs *batch, 
     if (A.rollover) { if (rec) RP3_GO(true, false, true); else RP3_GO(true, false, false); }
     else            { if (rec) RP3_GO(false, false, true); else RP3_GO(false, false, false); }
 #undef RP3_GO
+#undef RP3_GO1
 }
 
 // the non-default reward / disturbance variants (rollout_var_r0.hip: REWARD 0 with FDIST 1, 2; rollout_var_r1.hip: REWARD 1);

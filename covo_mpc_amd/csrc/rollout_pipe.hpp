@@ -426,7 +426,7 @@ __device__ __forceinline__ void rp3_idle_barriers()
 }
 
 template <bool DISC1, bool ROLL, int CH, int GROUPS, bool BATCHED = false, int ONLY = -1, int ONLY_WAVES = 3, bool STATS = false,
-          bool REC = false, int REWARD = 0, int FDIST = 0>
+          bool REC = false, int REWARD = 0, int FDIST = 0, bool DIAG = false>
 __global__ __launch_bounds__((ONLY >= 0 ? ONLY_WAVES : 3 * GROUPS) * COVO_WAVE) void rollout_pipe3_kernel(
     const RolloutArgs A_, const RolloutArgs *__restrict__ batch)
 {
@@ -446,6 +446,7 @@ __global__ __launch_bounds__((ONLY >= 0 ? ONLY_WAVES : 3 * GROUPS) * COVO_WAVE) 
         Ab.f_shared_dev = rebase_global(A_.f_shared_dev, Ab.f_shared_dev);
         Ab.f_tab = rebase_global(A_.f_tab, Ab.f_tab);
         Ab.records = rebase_global(A_.records, Ab.records);
+        if (DIAG) Ab.diag_rec = rebase_global(A_.diag_rec, Ab.diag_rec);
     }
     const RolloutArgs &A = BATCHED ? Ab : A_;
     __shared__ Rp3Lds<CH> lds_all[ONLY >= 0 ? ONLY_WAVES : GROUPS];
@@ -470,8 +471,14 @@ __global__ __launch_bounds__((ONLY >= 0 ? ONLY_WAVES : 3 * GROUPS) * COVO_WAVE) 
     if (ONLY == -1 && REC) {  // every wave of the workgroup (the A and T waves carry no cost)
         __shared__ float rec_m[GROUPS], rec_s[GROUPS];
         __shared__ __attribute__((aligned(16))) float rec_v[GROUPS][COVO_NA];
-        rollout_record<3 * GROUPS, GROUPS>(A, cost, valid && role == 2, n, role == 2 ? gsub : 0, role == 2, lane, blockIdx.x, rec_m,
-                                           rec_s, rec_v);
+        if constexpr (DIAG) {  // (A.diag_rec != null: the step's sampling diagnostics are on)
+            __shared__ float rec_d[GROUPS][MG_DIAG_REC];
+            rollout_record<3 * GROUPS, GROUPS, false, true>(A, cost, valid && role == 2, n, role == 2 ? gsub : 0, role == 2, lane,
+                                                            blockIdx.x, rec_m, rec_s, rec_v, nullptr, false, rec_d);
+        } else {
+            rollout_record<3 * GROUPS, GROUPS>(A, cost, valid && role == 2, n, role == 2 ? gsub : 0, role == 2, lane, blockIdx.x, rec_m,
+                                               rec_s, rec_v);
+        }
     }
     if (STATS) {
         // this workgroup's {sum (p - p0), sum (p - p0)^2} per step and axis, in fp64, with each T wave's shift put back:

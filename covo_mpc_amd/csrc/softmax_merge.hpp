@@ -26,6 +26,19 @@ struct MergeLds {
     float sv[MG_SLICES][COVO_NA];
 };
 
+// DIAG (the per-step sampling diagnostics, covo_set_step_diag): next to its record every stage-1 workgroup leaves a diagnostic
+// record {sum w^2, sum w (c - m_g), sum (c - m_g), valid samples} over its samples (w = exp(-(c - m_g)/lam), m_g the record's own
+// minimum: the cost sums are formed relative to a minimum, at lam = 0.01 the differences that matter are 1e-2 on costs of order
+// 1-100).  The merge rescales them like s -- sum w^2 = sum_g s2_g scale_g^2, the two cost sums shifted by m_g - m -- over the same
+// virtual lanes in the same order, and writes the COVO_DIAG_FLOATS of include/covo_hip.h.
+constexpr int MG_DIAG_REC = 4;  // floats per stage-1 diagnostic record
+struct MergeDiag {
+    const float *rec = nullptr;  // [G][MG_DIAG_REC]
+    float *out = nullptr;        // [COVO_DIAG_FLOATS]
+    float n = 0.0f;              // the step's sample count
+    float (*red)[MG_VWAVES] = nullptr;  // LDS [3][MG_VWAVES]: the virtual waves' sums
+};
+
 template <bool COH>
 __device__ __forceinline__ float mg_load(const float *p)
 {
@@ -36,9 +49,10 @@ __device__ __forceinline__ float mg_load(const float *p)
 // FINAL: out[128] = gamma * v / s + (1 - gamma) * a_mean_old (covo.py:270-275); else out[130] = the merged record {m, s, v}.
 // stride: floats between consecutive records.  Every thread of the workgroup calls it (it contains barriers); THREADS is a
 // multiple of 64.  G <= MG_MAXG.
-template <int THREADS, bool FINAL, bool COH>
+template <int THREADS, bool FINAL, bool COH, bool DIAG = false>
 __device__ __forceinline__ void merge_body(const float *__restrict__ partials, int G, float inv_lam, const float *__restrict__ a_mean_old,
-                                           float gamma_mean, float *__restrict__ out, int stride, MergeLds &L)
+                                           float gamma_mean, float *__restrict__ out, int stride, MergeLds &L,
+                                           const MergeDiag &D = MergeDiag())
 {
 #pragma clang fp contract(off)  // every fused multiply-add below is written out: the same bits in every translation unit
     static_assert(THREADS % 64 == 0 && THREADS <= MG_THREADS, "merge_body: THREADS");
@@ -59,6 +73,7 @@ __device__ __forceinline__ void merge_body(const float *__restrict__ partials, i
     }
     // phase 1: m = min_g m_g (exact in any order); a virtual thread's header {m_g, s_g} stays in registers for phase 2
     float my_m[ROUNDS], my_s[ROUNDS];
+    float my_d[DIAG ? ROUNDS : 1][MG_DIAG_REC];
     float m = __builtin_inff();
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {
@@ -67,6 +82,10 @@ __device__ __forceinline__ void merge_body(const float *__restrict__ partials, i
         my_m[r] = mine ? mg_load<COH>(partials + (size_t)g * stride) : __builtin_inff();
         my_s[r] = mine ? mg_load<COH>(partials + (size_t)g * stride + 1) : 0.0f;
         m = fminf(m, my_m[r]);
+        if (DIAG) {
+#pragma unroll
+            for (int j = 0; j < MG_DIAG_REC; ++j) my_d[r][j] = mine ? mg_load<COH>(D.rec + (size_t)g * MG_DIAG_REC + j) : 0.0f;
+        }
     }
     m = wave_min(m);
     if (lane == 0) L.redm[wave] = m;
@@ -80,20 +99,53 @@ __device__ __forceinline__ void merge_body(const float *__restrict__ partials, i
     for (int r = 0; r < ROUNDS; ++r) {
         const int g = tid + r * THREADS;  // THREADS % 64 == 0: a wave holds one whole virtual wave, lane = g & 63
         if (g - lane < MG_THREADS) {      // (wave-uniform)
-            float sg = 0.0f;
+            float sg = 0.0f, d2 = 0.0f, dw = 0.0f, dc = 0.0f;
             if (g < G) {
                 const float sc = (my_s[r] > 0.0f) ? expf((m - my_m[r]) * inv_lam) : 0.0f;  // empty shard -> 0
                 L.scale[g] = sc;
                 sg = my_s[r] * sc;
+                if (DIAG && my_d[r][3] > 0.0f) {  // (a record without samples has m_g = inf)
+                    const float dm = my_m[r] - m;  // >= 0: c - m = (c - m_g) + dm
+                    d2 = my_d[r][0] * (sc * sc);
+                    dw = (my_d[r][1] + my_s[r] * dm) * sc;
+                    dc = my_d[r][2] + my_d[r][3] * dm;
+                }
             }
             sg = wave_sum(sg);
             if (lane == 0) L.reds[g >> 6] = sg;
+            if (DIAG) {
+                d2 = wave_sum(d2);
+                dw = wave_sum(dw);
+                dc = wave_sum(dc);
+                if (lane == 0) {
+                    D.red[0][g >> 6] = d2;
+                    D.red[1][g >> 6] = dw;
+                    D.red[2][g >> 6] = dc;
+                }
+            }
         }
     }
     __syncthreads();
     float s = 0.0f;
 #pragma unroll
     for (int i = 0; i < MG_VWAVES; ++i) s += L.reds[i];
+    if (DIAG && tid == 0) {  // the virtual waves' sums in ascending order, like s
+        float s2 = 0.0f, sw = 0.0f, sc = 0.0f;
+#pragma unroll
+        for (int i = 0; i < MG_VWAVES; ++i) {
+            s2 += D.red[0][i];
+            sw += D.red[1][i];
+            sc += D.red[2][i];
+        }
+        D.out[0] = (s * s) / s2;  // ess
+        D.out[1] = m;             // cost_min
+        D.out[2] = m + sw / s;    // cost_weighted
+        D.out[3] = m + sc / D.n;  // cost_mean
+        D.out[4] = s;             // weight_sum
+        D.out[5] = D.n;           // n_samples
+        D.out[6] = 0.0f;
+        D.out[7] = 0.0f;
+    }
     // phase 3: v[col] = sum_g v_g[col] scale_g per slice (ascending g within a slice)
 #pragma unroll
     for (int r = 0; r < ROUNDS; ++r) {

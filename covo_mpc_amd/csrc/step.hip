@@ -236,26 +236,30 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     // MPPI's covariance adaptation needs second moments the in-rollout records do not carry: its own stage 1 (reduce.hip)
     const bool cov_adapt = a.mode == COVO_MODE_MPPI && a.gamma_sigma != 0.0f;
     const bool records = G <= h->max_red_blocks && !cov_adapt;
+    // the step's sampling diagnostics (covo_set_step_diag): the diagnostic variants of the same launches; a sharded step has none
+    float *dg = a.partial_out == nullptr ? covo_diag_target(h) : nullptr;
     if ((M & 16) && (rc = launch_rollout(state, a.pos_traj, a.vel_traj, a.T, p, nullptr, a.a, N, h->cfg.discount, clipped, a.cost,
                                          records ? nullptr : a.groupmin, a.pos_stats, h->ws_stats, s, fdev,
                                          records ? h->ws_partials : nullptr, h->cfg.lam, tables ? st->f_tab_rollout : nullptr,
-                                         a.mode == COVO_MODE_MPPI ? 4 : 0, false)))  // MPPI's block-diagonal kernel: 256 samples per workgroup
+                                         a.mode == COVO_MODE_MPPI ? 4 : 0, false,  // MPPI's block-diagonal kernel: 256 samples per workgroup
+                                         (records && dg) ? h->ws_diag_rec : nullptr)))
         return rc;
     if (!(M & 32)) return 0;
     if (cov_adapt && a.partial_out != nullptr)  // a sample-sharded rank: its record with the second moments (836-float kind)
         return launch_softmax_reduce_cov(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, am_shift, a.partial_out, s);
     if (cov_adapt)  // mppi.py:109-125: new mean, then a_cov (already shifted by the begin launch) adapted in place
         return launch_softmax_update_cov(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, am_shift, a.gamma_mean, a.a_cov, a.gamma_sigma,
-                                         a.a_mean, a.a_cov, s);
+                                         a.a_mean, a.a_cov, s, dg);
     if (records) {
         if (a.partial_out != nullptr) return launch_merge(h->ws_partials, G, h->cfg.lam, nullptr, 1.0f, nullptr, s, a.partial_out);
-        return launch_merge(h->ws_partials, G, h->cfg.lam, am_shift, a.gamma_mean, a.a_mean, s);
+        return launch_merge(h->ws_partials, G, h->cfg.lam, am_shift, a.gamma_mean, a.a_mean, s, nullptr, 1, COVO_PARTIAL_FLOATS,
+                            h->ws_diag_rec, dg, N);
     }
     // weights + update: finish locally, or leave this shard's record for the all-gather (covo.py:266-275)
     if (a.partial_out != nullptr)
         return launch_softmax_reduce(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, a.partial_out, nullptr, 1.0f, nullptr, s);
     return launch_softmax_reduce(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, nullptr, am_shift, a.gamma_mean,
-                                 a.a_mean, s);
+                                 a.a_mean, s, nullptr, 1, h->ws_diag_rec, dg);
 }
 
 int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
@@ -469,6 +473,7 @@ struct BatchSmall {
     void *args = nullptr;        // SmallStepArgs[E]
     unsigned *tickets = nullptr; // [E] arrival counters; each wraps to 0 with its instance's last workgroup (atomicInc)
     float *records = nullptr;    // [E][groups][COVO_PARTIAL_FLOATS]
+    float *diag_rec = nullptr;   // [E][groups][4] the diagnostic records next to them (covo_set_step_diag)
     std::vector<char> args_host;
     std::vector<covo_env_params> params;
     covo_batch_mode_args key;
@@ -493,7 +498,8 @@ static void batch_small_free(BatchSmall *m)
     (void)hipFree(m->args);
     (void)hipFree(m->tickets);
     (void)hipFree(m->records);
-    m->dyn = nullptr; m->args = nullptr; m->tickets = nullptr; m->records = nullptr;
+    (void)hipFree(m->diag_rec);
+    m->dyn = nullptr; m->args = nullptr; m->tickets = nullptr; m->records = nullptr; m->diag_rec = nullptr;
     m->n_envs = m->groups = 0;
     m->have_key = false;
 }
@@ -508,6 +514,7 @@ struct BatchState {
     void *consts = nullptr;         // qm::Consts<double>[E]   (Hessian)
     void *ro_args = nullptr;        // RolloutArgs[E]          (rollout)
     float *partials = nullptr;      // [E][max_red_blocks][COVO_PARTIAL_FLOATS]: the instances' softmax stage-1 records
+    float *diag_rec = nullptr;      // [E][max_red_blocks][4]: their diagnostic records (covo_set_step_diag)
     void *models = nullptr;         // dm::Model[E]            (disturbance tables, drag / mixed Hessian)
     float *tab_rollout = nullptr, *tab_hess = nullptr;  // [E][H][4] the step's disturbance tables (periodic / sin / drag / mixed)
     bool tables = false;            // the instances' disturbance model needs them
@@ -540,12 +547,13 @@ static void batch_state_free(BatchState *b)
     (void)hipFree(b->consts);
     (void)hipFree(b->ro_args);
     (void)hipFree(b->partials);
+    (void)hipFree(b->diag_rec);
     (void)hipFree(b->models);
     (void)hipFree(b->tab_rollout);
     (void)hipFree(b->tab_hess);
     b->models = nullptr; b->tab_rollout = b->tab_hess = nullptr;
     b->dyn = nullptr; b->a_mean_shift = nullptr; b->R = nullptr; b->Sigma = b->L = nullptr; b->consts = nullptr;
-    b->ro_args = nullptr; b->partials = nullptr;
+    b->ro_args = nullptr; b->partials = nullptr; b->diag_rec = nullptr;
 }
 // The captured graphs (fused step, env-batched step) hold the addresses of h->ws_sigma / h->ws_hess in their kernel nodes:
 // whoever re-allocates a workspace (a larger batch through covo_sigma / covo_hessian / covo_mpc_step_batched) calls this
@@ -660,10 +668,12 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     if ((M & 16) && (rc = launch_rollout_batched(b->ro_args_host.data(), b->ro_args, E, s))) return rc;
     if (!(M & 32)) return 0;
     const int G = rollout_workgroups(N, false, E);
+    float *dg = covo_diag_target(h);  // row e of the caller's diagnostic buffer is instance e's
     if (G <= h->max_red_blocks)  // the rollout's workgroups have left the records (rollout_record): instance e's are [e][G]
-        return launch_merge(b->partials, G, h->cfg.lam, b->a_mean_shift, a.gamma_mean, a.a_mean, s, nullptr, E);
+        return launch_merge(b->partials, G, h->cfg.lam, b->a_mean_shift, a.gamma_mean, a.a_mean, s, nullptr, E, COVO_PARTIAL_FLOATS,
+                            b->diag_rec, dg, N);
     return launch_softmax_reduce(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, nullptr, b->a_mean_shift, a.gamma_mean, a.a_mean, s,
-                                 b->partials, E);
+                                 b->partials, E, b->diag_rec, dg);
 }
 
 // profiling aid (bench.py --config envs): `reps` copies of the selected launch groups of the LAST covo_mpc_step_batched call in
@@ -747,6 +757,7 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
             COVO_CHECK_HIP(hipMalloc(&b->consts, hessian_consts_bytes(E)));
             COVO_CHECK_HIP(hipMalloc(&b->ro_args, rollout_args_bytes(E)));
             COVO_CHECK_HIP(hipMalloc(&b->partials, (size_t)E * h->max_red_blocks * COVO_PARTIAL_FLOATS * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&b->diag_rec, (size_t)E * h->max_red_blocks * 4 * sizeof(float)));
             COVO_CHECK_HIP(hipMalloc(&b->models, disturb_models_bytes(E)));
             COVO_CHECK_HIP(hipMalloc(&b->tab_rollout, (size_t)E * COVO_H * 4 * sizeof(float)));
             COVO_CHECK_HIP(hipMalloc(&b->tab_hess, (size_t)E * COVO_H * 4 * sizeof(float)));
@@ -770,7 +781,8 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
                               params[e], args->a + (size_t)e * COVO_H * N * 4, N, h->cfg.discount, args->cost + (size_t)e * N,
                               brec ? nullptr : args->groupmin + (size_t)e * ng, reinterpret_cast<const float *>(b->dyn + 12 * e + 2),
                               brec ? b->partials + (size_t)e * bG * COVO_PARTIAL_FLOATS : nullptr, h->cfg.lam, true,
-                              b->tables ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr);
+                              b->tables ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr,
+                              (brec && covo_diag_target(h)) ? b->diag_rec + (size_t)e * bG * 4 : nullptr);
         COVO_CHECK_HIP(hipMemcpy(b->ro_args, b->ro_args_host.data(), b->ro_args_host.size(), hipMemcpyHostToDevice));
         {
             const size_t need_e = (size_t)E * ((N + 31) / 32) * 16 * 64;
@@ -902,18 +914,21 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
             COVO_CHECK_HIP(hipMalloc(&q->args, step_small_args_bytes(E)));
             COVO_CHECK_HIP(hipMalloc(&q->tickets, (size_t)E * sizeof(unsigned)));
             COVO_CHECK_HIP(hipMalloc(&q->records, (size_t)E * ng * COVO_PARTIAL_FLOATS * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&q->diag_rec, (size_t)E * ng * 4 * sizeof(float)));
             q->n_envs = E;
             q->groups = ng;
         }
         COVO_CHECK_HIP(hipMemset(q->tickets, 0, (size_t)E * sizeof(unsigned)));
         q->params.assign(params, params + E);
         q->args_host.assign(step_small_args_bytes(E), 0);
+        float *dg = covo_diag_target(h);
         for (int e = 0; e < E; ++e) {
             const covo_step_args sa = batch_small_instance(*m, e);
             // the one shared gaussian vector of MPPI's sampling rollouts (free.py:66-70), per instance; off for CoVO (deterministic)
             const float scale = (params[e].disturb_kind == COVO_DISTURB_GAUSSIAN && !sa.rollout_deterministic) ? params[e].dyn_noise_scale : 0.0f;
             step_small_fill_args(h, q->args_host.data(), e, params[e], sa, q->dyn + 12 * e, scale, q->tickets + e,
-                                 q->records + (size_t)e * ng * COVO_PARTIAL_FLOATS);
+                                 q->records + (size_t)e * ng * COVO_PARTIAL_FLOATS, q->diag_rec + (size_t)e * ng * 4,
+                                 dg ? dg + (size_t)e * COVO_DIAG_FLOATS : nullptr);
         }
         COVO_CHECK_HIP(hipMemcpy(q->args, q->args_host.data(), q->args_host.size(), hipMemcpyHostToDevice));
         std::memset(&q->key, 0, sizeof(q->key));

@@ -56,7 +56,9 @@ static_assert(sizeof(MergeLds) <= (size_t)COVO_NA * NG_LDA * sizeof(float), "mer
 // quantity that counts workgroups (record index, ticket wrap, the merge's record count, the group mapping) is blockIdx.x /
 // gridDim.x, i.e. per instance: instance y's step is bit-identical to the single launch on it.  The per-step keys come from
 // device memory: dyn_mem = that instance's RAW rng_act (batch_set_dyn_kernel), derived per workgroup like an eager single step.
-template <bool MPPI, bool DISC1, bool ROLL, bool BATCHED = false>
+// DIAG (covo_set_step_diag): the record stage also leaves the group's diagnostic record, the last workgroup's merge also writes the
+// instance's COVO_DIAG_FLOATS (row y of the caller's buffer); their LDS scratch is the rollout's rings, idle after phase 2.
+template <bool MPPI, bool DISC1, bool ROLL, bool BATCHED = false, bool DIAG = false>
 __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArgs P_, const SmallStepArgs *__restrict__ batch)
 {
     SmallStepArgs Pb;
@@ -70,6 +72,10 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
         Pb.R.records = rebase_global(P_.R.records, Pb.R.records);
         Pb.R.merge_ticket = rebase_global(P_.R.merge_ticket, Pb.R.merge_ticket);
         Pb.R.merge_out = rebase_global(P_.R.merge_out, Pb.R.merge_out);
+        if (DIAG) {
+            Pb.R.diag_rec = rebase_global(P_.R.diag_rec, Pb.R.diag_rec);
+            Pb.R.diag_out = rebase_global(P_.R.diag_out, Pb.R.diag_out);
+        }
         Pb.a_mean_in = rebase_global(P_.a_mean_in, Pb.a_mean_in);
         Pb.L_table = rebase_global(P_.L_table, Pb.L_table);
         Pb.mppi_cov = rebase_global(P_.mppi_cov, Pb.mppi_cov);
@@ -234,11 +240,19 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
 
     // ---- phase 3: this group's record, then the last workgroup's merge (covo.py:266-278)
     const bool carrier = wave == 2;
-    rollout_record<SS_BLOCK / COVO_WAVE, 1, true>(A, cost, valid && carrier, n, 0, carrier, lane, blockIdx.x, S.rec_m, S.rec_s,
-                                                  S.rec_v, &S.a[0][0], true);
+    static_assert(sizeof(Rp3Lds<SS_CH>) >= (3 * MG_VWAVES + MG_DIAG_REC) * sizeof(float), "diagnostic scratch must fit the rings");
+    float(*diag_red)[MG_VWAVES] = reinterpret_cast<float(*)[MG_VWAVES]>(&S.rings);
+    float(*diag_wave)[MG_DIAG_REC] = reinterpret_cast<float(*)[MG_DIAG_REC]>(reinterpret_cast<float *>(&S.rings) + 3 * MG_VWAVES);
+    if (DIAG)
+        rollout_record<SS_BLOCK / COVO_WAVE, 1, true, true>(A, cost, valid && carrier, n, 0, carrier, lane, blockIdx.x, S.rec_m, S.rec_s,
+                                                            S.rec_v, &S.a[0][0], true, diag_wave);
+    else
+        rollout_record<SS_BLOCK / COVO_WAVE, 1, true>(A, cost, valid && carrier, n, 0, carrier, lane, blockIdx.x, S.rec_m, S.rec_s,
+                                                      S.rec_v, &S.a[0][0], true);
     // the write-through stores of the record are acknowledged before the ticket; the last workgroup merges (softmax_merge.hpp)
     A.merge_mean_old = S.mus;
-    rollout_merge_last<SS_BLOCK>(A, M, S.last);
+    if (DIAG) rollout_merge_last_diag<SS_BLOCK>(A, M, S.last, diag_red);
+    else rollout_merge_last<SS_BLOCK>(A, M, S.last);
     if (!S.last) return;
     if (MPPI) {  // the in-place shift of a_cov (mppi.py:43-49): every workgroup took its factors from the old blocks long ago
         float blk[16];
@@ -278,7 +292,7 @@ bool step_small_eligible(const covo_ctx *h, const covo_env_params &p, const covo
 
 static void fill_small_args(SmallStepArgs &P, covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state,
                             float *a_mean_shift, const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale,
-                            unsigned *ticket, float *records)
+                            unsigned *ticket, float *records, float *diag_rec, float *diag_out)
 {
     std::memset(&P, 0, sizeof(P));
     const int N = a.n_samples;
@@ -291,6 +305,8 @@ static void fill_small_args(SmallStepArgs &P, covo_ctx *h, const covo_env_params
     P.R.merge_final = a.partial_out == nullptr;
     P.R.merge_out = a.partial_out ? a.partial_out : a.a_mean;
     P.R.merge_gamma = a.gamma_mean;
+    P.R.diag_rec = diag_out ? diag_rec : nullptr;
+    P.R.diag_out = diag_out;
     P.a_mean_in = a.a_mean_in ? a.a_mean_in : a.a_mean;
     P.a_mean_shift_out = a_mean_shift;
     P.L_table = a.L_table;
@@ -309,13 +325,15 @@ static int small_attrs_once()
 {
     static unsigned long long attr_devices = 0;  // (per device: covo_first_on_device)
     if (covo_first_on_device(attr_devices)) {
-#define SS_ATTR1(MPPI, D, R, B) COVO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(step_small_kernel<MPPI, D, R, B>), \
-                                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MPPI ? SS_LDS_MPPI : SS_LDS_GEMM)))
+#define SS_ATTR2(MPPI, D, R, B, G) COVO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(step_small_kernel<MPPI, D, R, B, G>), \
+                                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)(MPPI ? SS_LDS_MPPI : SS_LDS_GEMM)))
+#define SS_ATTR1(MPPI, D, R, B) SS_ATTR2(MPPI, D, R, B, false); SS_ATTR2(MPPI, D, R, B, true)
 #define SS_ATTR(MPPI, D, R) SS_ATTR1(MPPI, D, R, false); SS_ATTR1(MPPI, D, R, true)
         SS_ATTR(false, false, false); SS_ATTR(false, false, true); SS_ATTR(false, true, false); SS_ATTR(false, true, true);
         SS_ATTR(true, false, false); SS_ATTR(true, false, true); SS_ATTR(true, true, false); SS_ATTR(true, true, true);
 #undef SS_ATTR
 #undef SS_ATTR1
+#undef SS_ATTR2
     }
     return 0;
 }
@@ -325,7 +343,9 @@ static int small_go(const SmallStepArgs &P, const SmallStepArgs *batch, int nb, 
 {
     const int ng = (P.R.N + COVO_WAVE - 1) / COVO_WAVE;
     const bool roll = P.R.rollover != 0;
-#define SS_GO(MPPI, D, R) hipLaunchKernelGGL((step_small_kernel<MPPI, D, R, BATCHED>), dim3(ng, nb), dim3(SS_BLOCK), MPPI ? SS_LDS_MPPI : SS_LDS_GEMM, s, P, batch)
+    const bool diag = P.R.diag_out != nullptr;  // (all instances of a batch alike)
+#define SS_GO1(MPPI, D, R, G) hipLaunchKernelGGL((step_small_kernel<MPPI, D, R, BATCHED, G>), dim3(ng, nb), dim3(SS_BLOCK), MPPI ? SS_LDS_MPPI : SS_LDS_GEMM, s, P, batch)
+#define SS_GO(MPPI, D, R) do { if (diag) SS_GO1(MPPI, D, R, true); else SS_GO1(MPPI, D, R, false); } while (0)
     if (mppi) {
         if (disc1) { if (roll) SS_GO(true, true, true); else SS_GO(true, true, false); }
         else       { if (roll) SS_GO(true, false, true); else SS_GO(true, false, false); }
@@ -334,6 +354,7 @@ static int small_go(const SmallStepArgs &P, const SmallStepArgs *batch, int nb, 
         else       { if (roll) SS_GO(false, false, true); else SS_GO(false, false, false); }
     }
 #undef SS_GO
+#undef SS_GO1
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -342,7 +363,8 @@ int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_arg
                       const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s)
 {
     SmallStepArgs P;
-    fill_small_args(P, h, p, a, state, a_mean_shift, blk, dyn_mem, shared_noise_scale, ticket, h->ws_partials);
+    fill_small_args(P, h, p, a, state, a_mean_shift, blk, dyn_mem, shared_noise_scale, ticket, h->ws_partials, h->ws_diag_rec,
+                    a.partial_out == nullptr ? covo_diag_target(h) : nullptr);
     int rc = small_attrs_once();
     if (rc) return rc;
     return small_go<false>(P, nullptr, 1, a.mode == COVO_MODE_MPPI, h->cfg.discount == 1.0f, s);
@@ -352,10 +374,10 @@ int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_arg
 size_t step_small_args_bytes(int n) { return (size_t)n * sizeof(SmallStepArgs); }
 
 void step_small_fill_args(covo_ctx *h, void *out, int index, const covo_env_params &p, const covo_step_args &a, const uint32_t *raw_key_mem,
-                          float shared_noise_scale, unsigned *ticket, float *records)
+                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec, float *diag_out)
 {
     fill_small_args(reinterpret_cast<SmallStepArgs *>(out)[index], h, p, a, a.state, nullptr, nullptr, raw_key_mem, shared_noise_scale,
-                    ticket, records);
+                    ticket, records, diag_rec, diag_out);
 }
 
 // all instances alike in mode, sample count, reward, rollover flag and disturbance kind (the caller has checked): instance 0 picks

@@ -30,8 +30,10 @@ const char *step_small_refusal(const covo_ctx *h, const covo_env_params &p, cons
 // The env-batched form (grid = groups per instance x instances): instance `index`'s argument block, described like a single step
 // by (p, a) with a.state / a.a_mean / a.a_cov / a.L_table / a.a / a.cost its own buffers, into the host array `out`;
 // raw_key_mem: DEVICE uint32[2], that instance's raw rng_act of the current step; ticket / records: its own arrival counter and
-// [groups][COVO_PARTIAL_FLOATS] records.  The device copy of the array is the launch's `args_dev`.
+// [groups][COVO_PARTIAL_FLOATS] records; diag_rec / diag_out: its [groups][MG_DIAG_REC] diagnostic records and its row of the
+// caller's diagnostic buffer (diag_out null: diagnostics off).  The device copy of the array is the launch's `args_dev`.
 size_t step_small_args_bytes(int n);
 void step_small_fill_args(covo_ctx *h, void *out, int index, const covo_env_params &p, const covo_step_args &a, const uint32_t *raw_key_mem,
-                          float shared_noise_scale, unsigned *ticket, float *records);
+                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec = nullptr,
+                          float *diag_out = nullptr);
 int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s);

@@ -287,6 +287,23 @@ class DeviceEpisode:
         # incl. the env's reward, disturbance model and reset generator (env_step.hip runs all of them)
         self.params_c = env_model_params_c(env, params, auto_reset=auto_reset)
         self.n_steps = 0
+        self.diag_log = None  # [T + 1, 8], allocated when a controller with compute_diag runs the episode
+
+    def alloc_diag_log(self):
+        import torch
+        self.diag_log = torch.zeros((int(self.log.shape[0]), self._lib.COVO_DIAG_FLOATS), dtype=torch.float32, device=self.device)
+
+    def diag_log_view(self):
+        """the rows of the diagnostic log the next segment writes (covo_run_episode counts its rows from 0)"""
+        return self.diag_log[self.n_steps:]
+
+    def read_diag(self):
+        """-> float32[n_steps, 8]: the sampling diagnostics (include/covo_hip.h: covo_set_step_diag) of the steps run_episode has
+        enqueued under a controller with compute_diag; synchronises and checks the device status like read_log."""
+        if self.diag_log is None:
+            raise RuntimeError("no diagnostic log: run_episode under a controller built with compute_diag=True")
+        self.read_log()
+        return self.diag_log[:self.n_steps].cpu().numpy()
 
     @property
     def noisy_state(self) -> DeviceState:
@@ -366,6 +383,22 @@ class BatchedDeviceEpisode:
         self.log = torch.zeros((self.E, self.params[0].max_steps_in_episode + 1, 4), dtype=torch.float32, device=device)
         self.params_c = (_lib.EnvParamsC * self.E)(*[env_model_params_c(env, p, auto_reset=auto_reset) for p in self.params])
         self.n_steps = 0
+        self.diag_log = None  # [E, T + 1, 8], allocated when a controller with compute_diag runs the episode
+
+    def alloc_diag_log(self):
+        import torch
+        self.diag_log = torch.zeros((self.E, int(self.log.shape[1]), self._lib.COVO_DIAG_FLOATS), dtype=torch.float32, device=self.device)
+
+    def diag_log_view(self):
+        return self.diag_log  # (the batched drivers take the first row of a segment as log_index)
+
+    def read_diag(self):
+        """-> float32 [E, n_steps, 8]: every instance's sampling diagnostics of the enqueued steps (controller built with
+        compute_diag); synchronises and checks the device status like read_log."""
+        if self.diag_log is None:
+            raise RuntimeError("no diagnostic log: run_episode under a controller built with compute_diag=True")
+        self.read_log()
+        return self.diag_log[:, :self.n_steps].cpu().numpy()
 
     def step(self, step_keys, a_mean, stream=None):
         """step_keys: uint32 [E, 2] (the key Quad3D.step receives, per instance); a_mean: float32 [E, 128] device tensor whose first
@@ -393,7 +426,7 @@ class BatchedDeviceEpisode:
 
 
 def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H32_lam0.01", n_steps=None, seed: int = 1, device=None,
-                     verbose: bool = True):
+                     verbose: bool = True, diag: bool = False):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]."""
@@ -405,7 +438,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     c0, cp0 = get_controller(env, "covo-online", controller_params, device=device, compute_info=False)
     cp0 = c0.init_control_params
     b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                          sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device)
+                                          sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device,
+                                          compute_diag=diag)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
@@ -417,6 +451,11 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
         print(f"{n_envs} instances x {T} steps in {el:.2f}s = {n_envs * T / el:.0f} env-steps/s; "
               f"err_pos mean over instances: {log[:, :, 1].mean():.3f} (min {log[:, :, 1].mean(axis=1).min():.3f}, "
               f"max {log[:, :, 1].mean(axis=1).max():.3f})")
+        if diag:  # ess > 0.9 N: the costs do not discriminate -- the controller is blind (state outside the box, episode tail)
+            ess = ep.read_diag()[:, :, 0]
+            blind = (ess > 0.9 * N).sum(axis=1)
+            print("ESS median per instance: " + " ".join(f"{v:.0f}" for v in np.median(ess, axis=1)) +
+                  f"; steps with ess > 0.9 N per instance: {' '.join(str(int(v)) for v in blind)} (of {T})")
     return log[:, :, 1].mean(axis=1)
 
 
@@ -514,7 +553,7 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 
 
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
-                   compute_info=True):
+                   compute_info=True, compute_diag=False):
     """quadrotor.py:670-752."""
     import torch
 
@@ -542,7 +581,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         control_params = controllers.MPPIParams(gamma_mean=1.0, gamma_sigma=0.0, discount=1.0, sample_sigma=sigma,
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
-                                          process_group=process_group, compute_info=compute_info), control_params
+                                          process_group=process_group, compute_info=compute_info,
+                                          compute_diag=compute_diag), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -554,7 +594,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
             a_cov_offline=torch.zeros((H, env.action_dim, env.action_dim), dtype=torch.float32, device=device))
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group,
-                                          compute_info=compute_info), control_params
+                                          compute_info=compute_info, compute_diag=compute_diag), control_params
     raise NotImplementedError(controller_name)
 
 

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define COVO_ABI_VERSION 9
+#define COVO_ABI_VERSION 10
 
 #define COVO_H 32            /* horizon (compile-time in the fused kernels)          */
 #define COVO_DU 4            /* action dim, quadjax/envs/quadrotor.py:198            */
@@ -49,6 +49,7 @@ extern "C" {
 #define COVO_STATE_FLOATS 32
 #define COVO_PARTIAL_FLOATS 132
 #define COVO_POS_STATS_DOUBLES (COVO_H * 6) /* per step: sum(pos-c)[3], sum((pos-c)^2)[3] */
+#define COVO_DIAG_FLOATS 8   /* per-step sampling diagnostics of one instance (covo_set_step_diag)                       */
 
 #define COVO_FLAG_ACTIONS_CLIPPED 1 /* covo_config.flags: every `a` handed to covo_rollout_cost is already
                                        clipped to [-1,1] (true for covo_noise_* outputs): skip step_env's re-clip */
@@ -414,6 +415,30 @@ int covo_debug_set_ns_merged(covo_handle_t h, int on);
  * (default): as detected.  Same Sigma and L bit for bit. */
 int covo_debug_set_ns_coherence(covo_handle_t h, int force_agent);
 int covo_debug_hess_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);
+
+/* Per-step sampling diagnostics (ABI 10; off by default, and off changes nothing a caller can observe).  With a buffer attached,
+ * every control step of this handle -- covo_mpc_step (all modes, staged and fused, eager and graph), covo_mpc_step_batched,
+ * covo_mpc_step_batched_mode and the steps of the three episode drivers -- also writes COVO_DIAG_FLOATS floats per instance, over
+ * the step's N samples with costs c_n as the rollout wrote them, m = min c_n, w_n = exp(-(c_n - m) / lambda):
+ *   [0] ess            (sum w)^2 / sum w^2      (1: the update follows one sample; N: the costs do not discriminate)
+ *   [1] cost_min       m
+ *   [2] cost_weighted  sum w c / sum w
+ *   [3] cost_mean      sum c / N
+ *   [4] weight_sum     sum w
+ *   [5] n_samples      N as a float
+ *   [6], [7]           reserved, written as 0
+ * The sums are formed by the launches that form the update itself (stage-1 records and their merge), in a fixed order; every
+ * other output of the step is bit-identical to the same call without diagnostics.
+ * covo_set_step_diag: diag = DEVICE float[n_inst][COVO_DIAG_FLOATS], row e = instance e of a batched step (a single step writes
+ *   row 0); NULL = off.  A batched step with more instances than n_inst is refused.
+ * covo_set_episode_diag_log: log = DEVICE float[n_inst][stride][COVO_DIAG_FLOATS]; step k of an episode driver's segment writes
+ *   instance e's row to log[e][log_index + k] (covo_run_episode: log_index = 0, one instance) from the device, between that
+ *   control step and its env step; NULL = off.  A segment that would leave the log is refused.
+ * A change of where the steps write (attach, detach, another buffer) makes the handle re-capture its step graphs at the next
+ * call, like a covo_debug_set_* switch.  Out of scope: a sample-sharded step (partial_out != NULL) with diagnostics attached is
+ * refused -- the rank records carry no diagnostic sums. */
+int covo_set_step_diag(covo_handle_t h, float *diag, int32_t n_inst);
+int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

@@ -27,6 +27,7 @@ ap.add_argument("--steps", type=int, default=200, help="steps per timed window")
 ap.add_argument("--rounds", type=int, default=5)
 ap.add_argument("--no-loop", action="store_true", help="skip the per-instance baseline")
 ap.add_argument("--episode-steps", type=int, default=300)
+ap.add_argument("--diag", action="store_true", help="the batched controllers also form the per-step sampling diagnostics (compute_diag)")
 args = ap.parse_args()
 
 import torch  # noqa: E402
@@ -46,7 +47,7 @@ cp0 = c0.init_control_params
 
 
 def make_batched():
-    kw = dict(discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=DEV)
+    kw = dict(discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=DEV, compute_diag=args.diag)
     if args.mode == "mppi":
         return cm.controllers.BatchedMPPIController(env, E, N, 32, float(lam), sigmas=cp0.sample_sigma, **kw)
     return cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), sample_sigma=cp0.sample_sigma,
