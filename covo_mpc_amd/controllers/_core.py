@@ -52,7 +52,8 @@ def exchange_records(record, gathered_flat, process_group=None):
 class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
-                 cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1):
+                 cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
+                 compute_plan: bool = False):
         import torch
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
@@ -149,6 +150,17 @@ class SamplingCore:
                                           "(covo_set_step_diag refuses sample-sharded steps)")
             self.diag = torch.zeros((int(diag_rows), _lib.COVO_DIAG_FLOATS), **f32)
             check(self.lib.covo_set_step_diag(self.h, ptr(self.diag), int(diag_rows)), "covo_set_step_diag")
+        # compute_plan: every step also leaves its plan -- the rollout of the new mean itself with the step's own inputs, {cost_plan,
+        # 0, 0, 0, pos_plan[H][3]} -- in self.plan (row e = instance e of a batched step), by one extra launch behind the step
+        # (covo_set_step_plan, csrc/plan_trace.hip); off by default, and off changes nothing
+        self.compute_plan = bool(compute_plan)
+        self.plan = None
+        if self.compute_plan:
+            if self.world > 1:
+                raise NotImplementedError("compute_plan on sample-sharded ranks: a rank holds only its shard's record until the "
+                                          "exchange (covo_set_step_plan refuses sample-sharded steps)")
+            self.plan = torch.zeros((int(diag_rows), _lib.COVO_PLAN_FLOATS), **f32)
+            check(self.lib.covo_set_step_plan(self.h, ptr(self.plan), int(diag_rows)), "covo_set_step_plan")
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -290,7 +302,25 @@ class SamplingCore:
             return {}
         return {name: self.diag[0, i] for i, name in enumerate(_lib.DIAG_FIELDS[:4])}
 
+    def plan_info(self) -> dict:
+        """{"pos_plan" [H, 3], "cost_plan" 0-d} of the last step as views of self.plan (no sync, no copy); {} when the core was built
+        without compute_plan."""
+        if self.plan is None:
+            return {}
+        return {"pos_plan": self.plan[0, 4:].view(COVO_H, 3), "cost_plan": self.plan[0, 0]}
+
+    def attach_trace(self, episode, rows_left: int):
+        """Bind `episode`'s trace (allocated on first use) for the segment that starts at episode.n_steps."""
+        if not self.compute_plan:
+            return
+        if getattr(episode, "trace", None) is None:
+            episode.alloc_trace()
+        check(self.lib.covo_set_episode_trace(self.h, ptr(episode.trace_view()), int(rows_left)), "covo_set_episode_trace")
+
     def require_fused_for_diag(self):
+        if self.compute_plan:
+            raise NotImplementedError("compute_plan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') does not produce it")
         if self.compute_diag:
             raise NotImplementedError("compute_diag is formed by the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")
@@ -515,6 +545,8 @@ class SamplingCore:
         env = episode.env
         # compute_diag: step k of the segment also writes row n_steps + k of the episode's [T + 1, 8] diagnostic log
         self.attach_diag_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
+        # compute_plan: and row n_steps + k of its [T + 1, 168] trace (true state, noisy state, u, plan)
+        self.attach_trace(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # the env step's auto-reset (base.py:22-40) is a property of the EPISODE, the model constants come from the controller
         params_c = type(params_c).from_buffer_copy(params_c)
         for f in ("reset_traj", "reset_dt", "reset_disturb_scale"):

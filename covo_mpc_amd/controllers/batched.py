@@ -28,7 +28,8 @@ class BatchedCoVOController:
     MODE = None  # subclasses with a fixed mode (BatchedMPPIController)
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
-                 sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False):
+                 sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
+                 compute_plan: bool = False):
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -46,8 +47,10 @@ class BatchedCoVOController:
         # 150-270 us of host time per call)
         # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
-                                 compute_diag=compute_diag, diag_rows=int(n_envs))
+                                 compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan)
         self.diag = self.core.diag
+        # compute_plan: after a call, self.plan [E, 100] holds every instance's plan of that step {cost_plan, 0, 0, 0, pos_plan[H][3]}
+        self.plan = self.core.plan
         torch = self.core.torch
         f32 = dict(dtype=torch.float32, device=self.core.device)
         E, n = self.E, self.N
@@ -193,6 +196,7 @@ class BatchedCoVOController:
         env = self.env
         keys = np.ascontiguousarray(np.asarray(rngs, dtype=np.uint32).reshape(self.E, 2)).copy()
         self.core.attach_diag_log(episode, int(episode.log.shape[1]))  # compute_diag: rows n_steps .. of the [E, T + 1, 8] log
+        self.core.attach_trace(episode, int(episode.log.shape[1]))  # compute_plan: rows n_steps .. of the [E, T + 1, 168] trace
         online = self.mode == _lib.MODE_COVO_ONLINE
         fn = self.core.lib.covo_run_episode_batched if online else self.core.lib.covo_run_episode_batched_mode
         check(fn(
@@ -211,13 +215,13 @@ class BatchedMPPIController(BatchedCoVOController):
     MODE = _lib.MODE_MPPI
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
-                 gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False):
+                 gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False):
         if float(gamma_sigma) != 0.0:
             raise NotImplementedError(f"gamma_sigma={gamma_sigma}: MPPI's covariance adaptation (mppi.py:119-125) is not batched; "
                                       "the batched fused launch needs gamma_sigma == 0 (the reference's default)")
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
-                         a_mean_init=a_mean_init, device=device, compute_diag=compute_diag)
+                         a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

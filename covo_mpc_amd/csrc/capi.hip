@@ -117,6 +117,7 @@ int covo_destroy(covo_handle_t h)
     if (!h) return COVO_E_NOHANDLE;
     step_state_destroy(h);
     batch_state_destroy(h);
+    plan_state_destroy(h);
     exchange_destroy(h);
     int rc = 0;
 #define DESTROY(expr)                                                                                   \
@@ -595,6 +596,36 @@ int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride)
             "%s: sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log) are not available for sample-sharded "   \
             "steps (partial_out != NULL): the rank records carry no diagnostic sums; detach the buffer", what)
 
+// ---- the flight recorder (plan_trace.hip).  Its launch is eager and follows the step: attaching or detaching a buffer changes no
+// captured step graph
+int covo_set_step_plan(covo_handle_t h, float *plan, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_plan: null handle");
+    REQUIRE(plan == nullptr || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_plan: n_inst=%d outside (0, %d]", n_inst,
+            COVO_MAX_ENVS);
+    h->plan_out = plan;
+    h->plan_n = plan ? n_inst : 0;
+    return 0;
+}
+
+int covo_set_episode_trace(covo_handle_t h, float *trace, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_trace: null handle");
+    REQUIRE(trace == nullptr || stride > 0, "covo_set_episode_trace: stride=%d", stride);
+    h->trace = trace;
+    h->trace_stride = trace ? stride : 0;
+    return 0;
+}
+
+// a step for n_inst instances with a plan buffer attached: the buffer has a row for each
+#define CHECK_PLAN(h, n_inst, what)                                                                                       \
+    REQUIRE((h)->plan_out == nullptr || (n_inst) <= (h)->plan_n,                                                          \
+            "%s: %d instances, the plan buffer (covo_set_step_plan) has %d rows", what, (int)(n_inst), (h)->plan_n)
+#define REFUSE_SHARDED_PLAN(h, args, what)                                                                                \
+    REQUIRE((args)->partial_out == nullptr || !covo_plan_on(h),                                                           \
+            "%s: the plan / episode trace (covo_set_step_plan / covo_set_episode_trace) is not available for sample-sharded "   \
+            "steps (partial_out != NULL): a rank holds only its shard's record until the exchange; detach the buffer", what)
+
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)
 {
     REQUIRE(h && out, "covo_debug_sigma_workspace: bad argument");
@@ -666,6 +697,9 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     REFUSE_SHARDED_DIAG(h, args, "covo_run_episode");
     REQUIRE(h->diag_log == nullptr || n_steps <= h->diag_log_stride, "covo_run_episode: %d steps, the diagnostic log "
             "(covo_set_episode_diag_log) has %d rows", n_steps, h->diag_log_stride);
+    REFUSE_SHARDED_PLAN(h, args, "covo_run_episode");
+    REQUIRE(h->trace == nullptr || n_steps <= h->trace_stride, "covo_run_episode: %d steps, the episode trace "
+            "(covo_set_episode_trace) has %d rows", n_steps, h->trace_stride);
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -695,6 +729,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
             }
         }
         if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, 1, h->diag_log_stride, t, s))) return rc;
+        if ((rc = covo_plan_after_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, t, s))) return rc;
         rc = launch_env_step(state_true, const_cast<float *>(args->state), args->pos_traj, args->vel_traj, acc_traj, args->T,
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
@@ -804,6 +839,10 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     REQUIRE(h->diag_log == nullptr || (log_index >= 0 && log_index + n_steps <= h->diag_log_stride),
             "%s: diagnostic log rows [%d, %d) outside [0, %d) (covo_set_episode_diag_log)", what, log_index, log_index + n_steps,
             h->diag_log_stride);
+    CHECK_PLAN(h, E, what);
+    REQUIRE(h->trace == nullptr || (log_index >= 0 && log_index + n_steps <= h->trace_stride),
+            "%s: episode trace rows [%d, %d) outside [0, %d) (covo_set_episode_trace)", what, log_index, log_index + n_steps,
+            h->trace_stride);
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -821,6 +860,8 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
         if ((rc = online ? covo_step_batched_impl(h, args, params, act_keys, s) : covo_step_batched_small_impl(h, &norm, params, act_keys, s)))
             return rc;
         if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, E, h->diag_log_stride, log_index + t, s)))
+            return rc;
+        if ((rc = covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : norm.mode, params, states_true, log_index + t, s)))
             return rc;
         if ((rc = launch_env_step_batched(states_true, const_cast<float *>(args->states), args->pos_traj, args->vel_traj, acc_traj,
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
@@ -863,7 +904,9 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     int rc = check_batch_step(h, args, nullptr, params, "covo_mpc_step_batched", nullptr);
     if (rc) return rc;
     CHECK_DIAG(h, args->n_envs, "covo_mpc_step_batched");
-    return covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream);
+    CHECK_PLAN(h, args->n_envs, "covo_mpc_step_batched");
+    if ((rc = covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream))) return rc;
+    return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, (hipStream_t)stream);
 }
 
 int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params, const uint32_t *keys,
@@ -876,8 +919,11 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     int rc = check_batch_step(h, &args->base, args, params, "covo_mpc_step_batched_mode", &norm);
     if (rc) return rc;
     CHECK_DIAG(h, args->base.n_envs, "covo_mpc_step_batched_mode");
-    if (args->mode == COVO_MODE_COVO_ONLINE) return covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream);
-    return covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
+    CHECK_PLAN(h, args->base.n_envs, "covo_mpc_step_batched_mode");
+    rc = args->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream)
+                                             : covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
+    if (rc) return rc;
+    return covo_plan_after_batched(h, &args->base, args->mode, params, nullptr, -1, (hipStream_t)stream);
 }
 
 int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, int32_t step_mask,
@@ -938,7 +984,10 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
     REQUIRE(!needs_table(params) || args->derive_keys == 1, "covo_mpc_step: disturb_kind=%d needs derive_keys = 1 (the per-step "
             "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
     REFUSE_SHARDED_DIAG(h, args, "covo_mpc_step");
-    return covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);
+    REFUSE_SHARDED_PLAN(h, args, "covo_mpc_step");
+    const int rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);
+    if (rc) return rc;
+    return covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream);
 }
 
 int covo_cholesky(covo_handle_t h, const float *A, int32_t n, int32_t batch, float *L_out, void *stream)

@@ -54,7 +54,14 @@ struct covo_ctx {
     int diag_log_stride;
     float *diag_scratch;      // [COVO_MAX_ENVS][COVO_DIAG_FLOATS]: where the steps write when only the log is attached
     float *ws_diag_rec;       // [max_blocks][4] stage-1 diagnostic records next to ws_partials (softmax_merge.hpp)
+    // the flight recorder (covo_set_step_plan / covo_set_episode_trace; plan_trace.hip); all null / 0: off
+    float *plan_out;          // caller's [plan_n][COVO_PLAN_FLOATS]: instance e's plan row of every step
+    int plan_n;
+    float *trace;             // caller's [n_inst][trace_stride][COVO_TRACE_FLOATS]: the episode drivers' steps write their rows there
+    int trace_stride;
+    void *plan;               // PlanState (plan_trace.hip): the device copy of a batched step's argument blocks
 };
+static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->trace != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->diag_log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->diag_log ? COVO_MAX_ENVS : 0); }
@@ -303,6 +310,30 @@ int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, 
 int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_t s, const void **inst_dev);  // step.hip
 // the episode drivers: row e of the step's diagnostics -> row `index` of instance e's diagnostic log
 int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s);
+// plan_trace.hip: what the recorder needs to know about ONE instance of the step that has just been enqueued -- the inputs its
+// sample rollouts had.  key_mem (batched steps): the instance's raw rng_act in device memory; else key / f_shared as covo_mpc_step got them
+struct PlanInstDesc {
+    const float *state;       // the noisy state the step planned from [32]
+    const float *pos_traj, *vel_traj;
+    int T;
+    const covo_env_params *params;
+    const float *a_mean;      // [128] the mean the step leaves
+    const float *f_tab;       // the step's per-step disturbance table [H][4] (periodic / sin / drag / mixed), else null
+    const uint32_t *key_mem;
+    uint32_t key[2];
+    float f_shared[3];
+    int derive_keys;
+    float shared_noise_scale;
+};
+int launch_plan_trace(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, const float *states_true, int trace_index,
+                      hipStream_t s);
+void plan_state_destroy(covo_ctx *h);
+// step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
+// states_true + trace_index >= 0: an episode driver's step, which also writes its trace row
+int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
+                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s);
+int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
+                            const float *states_true, int trace_index, hipStream_t s);
 int launch_env_step(float *state, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,
                     const covo_env_params &p, const float *action, const uint32_t *step_key, int noisy_on,
                     float obs_noise_scale, float *log, int log_index, hipStream_t s);

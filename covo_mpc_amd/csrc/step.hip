@@ -360,6 +360,33 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     return enqueue_step(h, st, *params, *args, s);
 }
 
+// ---- the flight recorder behind a step (plan_trace.hip): one eager launch that rolls the new mean out with the inputs the step's
+// sample rollouts had.  The shared vector is re-derived from the raw key by the launch itself (every step path forms it from the
+// same device function); the per-step tables are the ones the step has just built in its own scratch.
+int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
+                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s)
+{
+    if (!covo_plan_on(h)) return 0;
+    StepState *st = reinterpret_cast<StepState *>(h->step);
+    PlanInstDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.state = args->state;
+    d.pos_traj = args->pos_traj;
+    d.vel_traj = args->vel_traj;
+    d.T = args->T;
+    d.params = params;
+    d.a_mean = args->a_mean;
+    const bool tables = params->disturb_kind >= COVO_DISTURB_PERIODIC && params->disturb_kind <= COVO_DISTURB_MIXED;
+    d.f_tab = (tables && st) ? st->f_tab_rollout : nullptr;
+    d.key[0] = key0;
+    d.key[1] = key1;
+    for (int i = 0; i < 3; ++i) d.f_shared[i] = f_shared ? f_shared[i] : 0.0f;
+    d.derive_keys = args->derive_keys;
+    d.shared_noise_scale =
+        (params->disturb_kind == COVO_DISTURB_GAUSSIAN && !args->rollout_deterministic) ? params->dyn_noise_scale : 0.0f;
+    return launch_plan_trace(h, &d, 1, false, state_true, trace_index, s);
+}
+
 
 // ---- profiling aid: `reps` copies of the selected part of one step captured into ONE graph and replayed; returns
 // the average time per copy (GPU time between two events around the replay).  Inside a graph the launches cost
@@ -966,6 +993,32 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
         return 0;
     }
     return launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, s);
+}
+
+// mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run) or MPPI / COVO_OFFLINE (covo_step_batched_small_impl)
+int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
+                            const float *states_true, int trace_index, hipStream_t s)
+{
+    if (!covo_plan_on(h)) return 0;
+    BatchState *b = reinterpret_cast<BatchState *>(h->batch);
+    const int E = args->n_envs;
+    const bool online = mode == COVO_MODE_COVO_ONLINE;
+    PlanInstDesc d[COVO_MAX_ENVS];
+    std::memset(d, 0, sizeof(d));
+    for (int e = 0; e < E; ++e) {
+        d[e].state = args->states + (size_t)e * COVO_STATE_FLOATS;
+        d[e].pos_traj = args->pos_traj + (size_t)e * args->T * 3;
+        d[e].vel_traj = args->vel_traj + (size_t)e * args->T * 3;
+        d[e].T = args->T;
+        d[e].params = &params[e];
+        d[e].a_mean = args->a_mean + (size_t)e * COVO_NA;
+        d[e].f_tab = (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
+        // the instance's raw rng_act: covo-online's begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone
+        d[e].key_mem = online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e;
+        d[e].derive_keys = 1;
+        d[e].shared_noise_scale = (mode == COVO_MODE_MPPI && params[e].disturb_kind == COVO_DISTURB_GAUSSIAN) ? params[e].dyn_noise_scale : 0.0f;
+    }
+    return launch_plan_trace(h, d, E, true, states_true, trace_index, s);
 }
 
 // test hook: the Hessians of the LAST batched step (E x 128 x 128 doubles), device -> host

@@ -258,6 +258,22 @@ class Quad3D(BaseEnvironment):
         return done
 
 
+
+def split_trace_rows(rows: np.ndarray) -> dict:
+    """Trace rows [.., n, 168] (include/covo_hip.h: covo_set_episode_trace) -> {state [.., n, 32], noisy [.., n, 32], u [.., n, 4],
+    cost_plan [.., n], pos_plan [.., n, H, 3]} as numpy views."""
+    H = (rows.shape[-1] - 72) // 3
+    return {"state": rows[..., 0:32], "noisy": rows[..., 32:64], "u": rows[..., 64:68], "cost_plan": rows[..., 68],
+            "pos_plan": rows[..., 72:].reshape(rows.shape[:-1] + (H, 3))}
+
+
+def unpack_state_row(row: np.ndarray) -> dict:
+    """One packed state float32[32] (include/covo_hip.h "Data layouts") -> the EnvState3D fields it carries."""
+    return {"pos": row[0:3].copy(), "vel": row[3:6].copy(), "quat": row[6:10].copy(), "omega": row[10:13].copy(),
+            "f_disturb": row[13:16].copy(), "pos_tar": row[16:19].copy(), "vel_tar": row[19:22].copy(),
+            "acc_tar": row[22:25].copy(), "time": int(np.ascontiguousarray(row[25:26]).view(np.int32)[0])}
+
+
 class DeviceEpisode:
     """One episode whose env state lives on the device: the true state, its noisy copy (what the
     controller plans from), the reference trajectory and the per-step log {reward, err_pos, err_vel, done}.
@@ -288,10 +304,29 @@ class DeviceEpisode:
         self.params_c = env_model_params_c(env, params, auto_reset=auto_reset)
         self.n_steps = 0
         self.diag_log = None  # [T + 1, 8], allocated when a controller with compute_diag runs the episode
+        self.trace = None     # [T + 1, 168], allocated when a controller with compute_plan runs the episode
 
     def alloc_diag_log(self):
         import torch
         self.diag_log = torch.zeros((int(self.log.shape[0]), self._lib.COVO_DIAG_FLOATS), dtype=torch.float32, device=self.device)
+
+    def alloc_trace(self):
+        import torch
+        self.trace = torch.zeros((int(self.log.shape[0]), self._lib.COVO_TRACE_FLOATS), dtype=torch.float32, device=self.device)
+
+    def trace_view(self):
+        """the rows of the trace the next segment writes (covo_run_episode counts its rows from 0)"""
+        return self.trace[self.n_steps:]
+
+    def read_trace(self):
+        """-> {state [n, 32], noisy [n, 32], u [n, 4], cost_plan [n], pos_plan [n, H, 3]} (numpy): per enqueued step the true and
+        the noisy state ENTERING its env step, the action it received and the controller's plan (include/covo_hip.h:
+        covo_set_episode_trace), under a controller built with compute_plan; synchronises and checks the device status like
+        read_log."""
+        if self.trace is None:
+            raise RuntimeError("no trace: run_episode under a controller built with compute_plan=True")
+        self.read_log()
+        return split_trace_rows(self.trace[:self.n_steps].cpu().numpy())
 
     def diag_log_view(self):
         """the rows of the diagnostic log the next segment writes (covo_run_episode counts its rows from 0)"""
@@ -384,6 +419,22 @@ class BatchedDeviceEpisode:
         self.params_c = (_lib.EnvParamsC * self.E)(*[env_model_params_c(env, p, auto_reset=auto_reset) for p in self.params])
         self.n_steps = 0
         self.diag_log = None  # [E, T + 1, 8], allocated when a controller with compute_diag runs the episode
+        self.trace = None     # [E, T + 1, 168], allocated when a controller with compute_plan runs the episode
+
+    def alloc_trace(self):
+        import torch
+        self.trace = torch.zeros((self.E, int(self.log.shape[1]), self._lib.COVO_TRACE_FLOATS), dtype=torch.float32, device=self.device)
+
+    def trace_view(self):
+        return self.trace  # (the batched drivers take the first row of a segment as log_index)
+
+    def read_trace(self):
+        """-> {state [E, n, 32], noisy [E, n, 32], u [E, n, 4], cost_plan [E, n], pos_plan [E, n, H, 3]} (numpy) of the enqueued
+        steps (controller built with compute_plan); synchronises and checks the device status like read_log."""
+        if self.trace is None:
+            raise RuntimeError("no trace: run_episode under a controller built with compute_plan=True")
+        self.read_log()
+        return split_trace_rows(self.trace[:, :self.n_steps].cpu().numpy())
 
     def alloc_diag_log(self):
         import torch
@@ -426,10 +477,11 @@ class BatchedDeviceEpisode:
 
 
 def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H32_lam0.01", n_steps=None, seed: int = 1, device=None,
-                     verbose: bool = True, diag: bool = False):
+                     verbose: bool = True, diag: bool = False, trace: bool = False):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
-    covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]."""
+    covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]; with trace=True
+    -> (that, ep.read_trace()): every instance's states, actions and plans of the episode."""
     from .. import controllers
     rng = crandom.PRNGKey(seed)
     ks = crandom.split(rng, 3 * n_envs + 1)
@@ -439,7 +491,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     cp0 = c0.init_control_params
     b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                           sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device,
-                                          compute_diag=diag)
+                                          compute_diag=diag, compute_plan=trace)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
@@ -456,6 +508,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
             blind = (ess > 0.9 * N).sum(axis=1)
             print("ESS median per instance: " + " ".join(f"{v:.0f}" for v in np.median(ess, axis=1)) +
                   f"; steps with ess > 0.9 N per instance: {' '.join(str(int(v)) for v in blind)} (of {T})")
+    if trace:
+        return log[:, :, 1].mean(axis=1), ep.read_trace()
     return log[:, :, 1].mean(axis=1)
 
 
@@ -553,7 +607,7 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 
 
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
-                   compute_info=True, compute_diag=False):
+                   compute_info=True, compute_diag=False, compute_plan=False):
     """quadrotor.py:670-752."""
     import torch
 
@@ -582,7 +636,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info,
-                                          compute_diag=compute_diag), control_params
+                                          compute_diag=compute_diag, compute_plan=compute_plan), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -594,8 +648,84 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
             a_cov_offline=torch.zeros((H, env.action_dim, env.action_dim), dtype=torch.float32, device=device))
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group,
-                                          compute_info=compute_info, compute_diag=compute_diag), control_params
+                                          compute_info=compute_info, compute_diag=compute_diag,
+                                          compute_plan=compute_plan), control_params
     raise NotImplementedError(controller_name)
+
+
+def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename="", save=True, host_env=False):
+    """quadrotor.py:594-667 without the plots: ONE closed-loop run from PRNGKey(1) -- the params, reset and control keys split off
+    in that order (:599-611) -- whose STATE SEQUENCE is returned and, with `save`, pickled to results/state_seq_<filename>.pkl
+    (relative to the working directory): a list with one dict per step, the env state ENTERING that step (:616), up to and
+    including the step whose `done` fires (`repeat_times` of them).  The dicts are keyed by EnvState3D's field names (s.__dict__,
+    :656; the device handle `traj_dev` left out) plus `reward`, and -- under a controller built with compute_plan -- `u`,
+    `pos_plan` [H, 3] and `cost_plan`: the action the step applied and the controller's own plan (include/covo_hip.h).  No plotting
+    (utils.plot_states, :661, stays out of scope).
+    Host path (controllers without a `core` or without compute_plan, host_env=True, repeat_times > 1): the Python loop with the
+    reference's per-step keys (rng, rng_act, rng_step = split(rng, 3), :617); on `done` the parameters are re-sampled and the
+    controller reset as :633-640.
+    Device path (sampling controllers built with compute_plan, repeat_times == 1): ONE run_episode segment of
+    max_steps_in_episode + 1 steps with the trace attached, one sync, rows cut at the first `done` of the env log; the states are
+    unpacked from the trace rows (the fields the device state carries: pos, vel, quat, omega, f_disturb, pos_tar, vel_tar, acc_tar,
+    time), the trajectories come from the episode's reset state.  DEVIATION: the episode drivers thread the per-step keys as
+    eval_env's run_one_step does (split(rng, 4), then one more split; quadrotor.py:520-538), not as :617 -- another realisation of
+    the same noise; the Philox stream is build-defined anyway (random.py)."""
+    rng = crandom.PRNGKey(1)
+    rng, rng_params = crandom.split(rng)
+    env_params = env.sample_params(rng_params)
+    rng, rng_reset = crandom.split(rng)
+    core = getattr(controller, "core", None)
+    device_path = (not host_env and repeat_times == 1 and core is not None and getattr(core, "compute_plan", False)
+                   and hasattr(controller, "run_episode") and core.world == 1)
+    t0 = time_module.time()
+    seq = []
+    if device_path:
+        ep = DeviceEpisode(env, rng_reset, env_params, (core.lib, core.h), core.device)
+        rng, rng_control = crandom.split(rng)
+        control_params = controller.reset(ep.state0, env_params, controller.init_control_params, rng_control)
+        controller.run_episode(ep, env_params, control_params, rng, env_params.max_steps_in_episode + 1)
+        tr = ep.read_trace()
+        log = ep.read_log()
+        dones = np.nonzero(log[:, 3] > 0.5)[0]
+        n = int(dones[0]) + 1 if len(dones) else int(log.shape[0])
+        s0 = ep.state0
+        for k in range(n):
+            d = unpack_state_row(tr["state"][k])
+            d.update(pos_traj=s0.pos_traj, vel_traj=s0.vel_traj, acc_traj=s0.acc_traj, reward=float(log[k, 0]),
+                     u=tr["u"][k].copy(), pos_plan=tr["pos_plan"][k].copy(), cost_plan=float(tr["cost_plan"][k]))
+            seq.append(d)
+    else:
+        obs, info, env_state = env.reset(rng_reset, env_params)
+        rng, rng_control = crandom.split(rng)
+        control_params = controller.reset(env_state, env_params, controller.init_control_params, rng_control)
+        n_dones = 0
+        to_np = lambda v: v.detach().cpu().numpy() if hasattr(v, "detach") else v
+        while n_dones < repeat_times:
+            d = {k: v for k, v in env_state.__dict__.items() if k != "traj_dev"}
+            rng, rng_act, rng_step = crandom.split(rng, 3)
+            action, control_params, control_info = controller(obs, env_state, env_params, rng_act, control_params, info)
+            action = to_np(action)
+            next_obs, next_env_state, reward, done, info = env.step(rng_step, env_state, action, env_params)
+            d["reward"] = reward
+            if isinstance(control_info, dict) and "pos_plan" in control_info:
+                d.update(u=np.array(action, copy=True), pos_plan=to_np(control_info["pos_plan"]).copy(),
+                         cost_plan=float(to_np(control_info["cost_plan"])))
+            seq.append(d)
+            if done:
+                rng, rng_params = crandom.split(rng)
+                env_params = env.sample_params(rng_params)
+                rng, rng_control = crandom.split(rng)
+                control_params = controller.reset(env_state, env_params, control_params, rng_control)
+                n_dones += 1
+            obs, env_state = next_obs, next_env_state
+    print(f"env running time: {time_module.time()-t0:.2f}s")
+    if save:
+        os.makedirs("results", exist_ok=True)
+        path = os.path.join("results", f"state_seq_{filename}.pkl")
+        with open(path, "wb") as f:
+            pickle.dump(seq, f)
+        print("[DEBUG] state sequence saved to ", path)
+    return seq
 
 
 @pydataclass
@@ -615,14 +745,19 @@ class Args:
 
 
 def main(args: Args):
-    """quadrotor.py:769-803 (eval mode; `render` needs matplotlib/meshcat post-processing, out of scope)."""
+    """quadrotor.py:769-803: `eval`, and `render` as the state sequence without its plots (render_env)."""
     env = Quad3D(task=args.task, obs_type=args.obs_type, lower_controller=args.lower_controller,
                  enable_randomizer=not args.noDR, disturb_type=args.disturb_type, disable_rollover_terminate=True,
                  generate_noisy_state=True, device="cuda")
     print("starting test...")
     # eval never reads the controller's info dict: quadjax's jitted run_one_step drops pos_mean / pos_std as dead code
     # (quadrotor.py:523-538), here the per-step position statistics are simply not requested
-    controller, control_params = get_controller(env, args.controller, args.controller_params, compute_info=args.mode != "eval")
+    render = args.mode == "render"
+    controller, control_params = get_controller(env, args.controller, args.controller_params, compute_info=args.mode != "eval",
+                                                compute_plan=render)
+    if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
+        return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
+                          host_env=args.host_env)
     if args.mode == "eval":
         if not args.host_env and hasattr(controller, "core"):
             # same protocol, env step on the device, whole episodes enqueued by one C call (eval_env_device)

@@ -439,6 +439,36 @@ int covo_debug_hess_workspace(covo_handle_t h, double *out, int64_t offset_doubl
  * refused -- the rank records carry no diagnostic sums. */
 int covo_set_step_diag(covo_handle_t h, float *diag, int32_t n_inst);
 int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride);
+
+/* The flight recorder: the plan of a control step and the trace of an episode (additive to ABI 10: COVO_HAS_PLAN_TRACE; off by
+ * default, and off changes nothing a caller can observe).
+ * The PLAN of a step, for one instance: a_plan = clip(a_new, -1, 1), a_new the mean the step leaves in a_mean (covo.py:275,
+ * mppi.py:116; before the next step's shift), rolled out from the state the step planned from with exactly the inputs the step's
+ * sample rollouts had -- covo_env_params, trajectory window, discount and the same disturbance (NONE / GAUSSIAN: the step's one
+ * shared vector, 0 under deterministic = 1; PERIODIC / SIN / DRAG / MIXED: the step's per-step table):
+ *   plan row  float[COVO_PLAN_FLOATS] = {cost_plan, 0, 0, 0, pos_plan[COVO_H][3]}: cost_plan is what covo_rollout_cost gives that
+ *             one action sequence (done-freeze and discount included; formed by the rollout kernel's own stage functions, bit for
+ *             bit), pos_plan[k] the position AFTER rollout step k (covo.py:234-237's poses; they keep integrating after done).
+ *   trace row float[COVO_TRACE_FLOATS] = [0..31] true state, [32..63] noisy state, [64..67] u = a_new[0][0..3], [68..167] the
+ *             step's plan row -- both states as they are between the control step and its env step, i.e. the PRE-step state of
+ *             the env step that follows (state layout above; word 25 is the int32 time).
+ * One extra eager launch per step for all instances (csrc/plan_trace.hip), behind the step; no captured step graph changes.
+ * covo_set_step_plan: plan = DEVICE float[n_inst][COVO_PLAN_FLOATS]; every control step of the handle -- covo_mpc_step (all
+ *   modes, staged and fused, eager and graph), covo_mpc_step_batched, covo_mpc_step_batched_mode and the steps of the three episode
+ *   drivers -- also writes row e for instance e (a single step: row 0); NULL = off.  A batched step with more instances than
+ *   n_inst is refused.
+ * covo_set_episode_trace: trace = DEVICE float[n_inst][stride][COVO_TRACE_FLOATS]; step k of an episode driver's segment writes
+ *   instance e's row to trace[e][log_index + k] (covo_run_episode: log_index = 0, one instance); NULL = off.  A segment that would
+ *   leave the trace is refused.
+ * Every other output of a step (u, a_mean, a_cov, costs, diagnostics, the env log, the key chain) is bit-identical with either
+ * attached or not.  Out of scope: a sample-sharded step (partial_out != NULL) with either attached is refused -- a rank holds only
+ * its shard's record until the exchange. */
+#define COVO_HAS_PLAN_TRACE 1
+#define COVO_PLAN_FLOATS  100   /* {cost_plan, 0, 0, 0, pos_plan[COVO_H][3]} */
+#define COVO_TRACE_FLOATS 168   /* [0..31] true state  [32..63] noisy state  [64..67] u
+                                   [68..167] the step's plan row (COVO_PLAN_FLOATS) */
+int covo_set_step_plan(covo_handle_t h, float *plan, int32_t n_inst);       /* DEVICE float[n_inst][COVO_PLAN_FLOATS];  NULL = off */
+int covo_set_episode_trace(covo_handle_t h, float *trace, int32_t stride);  /* DEVICE float[n_inst][stride][COVO_TRACE_FLOATS]; NULL = off */
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);
