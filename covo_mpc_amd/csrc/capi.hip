@@ -49,13 +49,12 @@ static int check_model(const covo_env_params *p, const char *what)
         covo_set_error("%s: disturb_kind=%d (COVO_DISTURB_*)", what, p->disturb_kind);
         return COVO_E_BADARG;
     }
-    if (p->disturb_kind >= COVO_DISTURB_PERIODIC && p->disturb_period <= 0) {
+    if (covo_needs_tables(*p) && p->disturb_period <= 0) {
         covo_set_error("%s: disturb_period=%d", what, p->disturb_period);
         return COVO_E_BADARG;
     }
     return 0;
 }
-static bool needs_table(const covo_env_params *p) { return p->disturb_kind >= COVO_DISTURB_PERIODIC && p->disturb_kind <= COVO_DISTURB_MIXED; }
 #define CHECK_MODEL(p, what)               \
     do {                                   \
         const int rc_ = check_model(p, what); \
@@ -66,11 +65,6 @@ __global__ void raise_status_kernel(int *status, int bits)
 {
     __hip_atomic_fetch_or(status, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
-
-int covo_debug_batched_hessians_impl(covo_ctx *h, double *out, int64_t offset_doubles, int64_t count, hipStream_t s);  // step.hip
-int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
-                                 hipStream_t s);  // step.hip
-const char *batch_small_refusal(const covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, int *which);  // step.hip
 
 extern "C" {
 
@@ -225,7 +219,7 @@ int covo_rollout_cost(covo_handle_t h, const float *state, const float *pos_traj
     REQUIRE(state && pos_traj && vel_traj && params && a && cost_out && T > 0, "covo_rollout_cost: bad argument");
     REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_rollout_cost: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
     CHECK_MODEL(params, "covo_rollout_cost");
-    REQUIRE(!needs_table(params) || f_disturb_steps, "covo_rollout_cost: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
+    REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_rollout_cost: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
             params->disturb_kind);
     return launch_rollout(state, pos_traj, vel_traj, T, *params, f_disturb_shared, a, N, h->cfg.discount,
                           (h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) != 0, cost_out, groupmin, pos_stats, h->ws_stats,
@@ -276,7 +270,7 @@ int covo_debug_time_rollout(covo_handle_t h, const float *state, const float *po
     REQUIRE(state && pos_traj && vel_traj && params && a && cost_out && us_out && T > 0 && reps > 0, "covo_debug_time_rollout: bad argument");
     REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_debug_time_rollout: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
     CHECK_MODEL(params, "covo_debug_time_rollout");
-    REQUIRE(!needs_table(params) || f_disturb_steps, "covo_debug_time_rollout: disturb_kind=%d needs f_disturb_steps", params->disturb_kind);
+    REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_debug_time_rollout: disturb_kind=%d needs f_disturb_steps", params->disturb_kind);
     hipStream_t s = (hipStream_t)stream;
     const bool clipped = (h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) != 0;
     // with_records: the variant the fused step runs (every workgroup also leaves its online-softmax record), when the launch
@@ -465,18 +459,10 @@ int covo_hessian(covo_handle_t h, const float *state, const float *pos_traj, con
     CHECK_DEVICE(h, "covo_hessian");
     REQUIRE(state && pos_traj && vel_traj && params && a_mean && R_out && T > 0 && batch > 0, "covo_hessian: bad argument");
     CHECK_MODEL(params, "covo_hessian");
-    REQUIRE(!needs_table(params) || f_disturb_steps, "covo_hessian: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
+    REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_hessian: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
             params->disturb_kind);
-    const size_t need = hessian_workspace_bytes(batch);
-    if (need > h->ws_hess_bytes) {  // only for batch sizes not seen before (never inside the steady-state step)
-        COVO_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-        step_graphs_drop(h);  // captured step graphs hold the old address
-        (void)hipFree(h->ws_hess);
-        h->ws_hess = nullptr;
-        h->ws_hess_bytes = 0;
-        COVO_CHECK_HIP(hipMalloc(&h->ws_hess, need));
-        h->ws_hess_bytes = need;
-    }
+    const int rc = covo_grow_workspace(h, &h->ws_hess, &h->ws_hess_bytes, hessian_workspace_bytes(batch), (hipStream_t)stream);
+    if (rc) return rc;
     return launch_hessian(state, pos_traj, vel_traj, T, *params, a_mean, batch, R_out, h->ws_hess, (hipStream_t)stream, nullptr, 0,
                           nullptr, f_disturb_steps, nullptr, h->status_dev);
 }
@@ -497,16 +483,8 @@ int covo_sigma(covo_handle_t h, const double *R, int32_t batch, float sample_sig
     REQUIRE(h, "covo_sigma: null handle");
     CHECK_DEVICE(h, "covo_sigma");
     REQUIRE(R && L_out && batch > 0 && sample_sigma > 0.0f, "covo_sigma: bad argument");
-    const size_t need = sigma_ns_workspace_bytes(batch);
-    if (need > h->ws_sigma_bytes) {  // only for batch sizes not seen before (never inside the steady-state step)
-        COVO_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
-        step_graphs_drop(h);  // captured step graphs hold the old address
-        (void)hipFree(h->ws_sigma);
-        h->ws_sigma = nullptr;
-        h->ws_sigma_bytes = 0;
-        COVO_CHECK_HIP(hipMalloc(&h->ws_sigma, need));
-        h->ws_sigma_bytes = need;
-    }
+    const int rc = covo_grow_workspace(h, &h->ws_sigma, &h->ws_sigma_bytes, sigma_ns_workspace_bytes(batch), (hipStream_t)stream);
+    if (rc) return rc;
     return launch_sigma_ns(h->opt, R, batch, sample_sigma, Sigma_out, L_out, h->ws_sigma, (hipStream_t)stream, nullptr, h->status_dev,
                            (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0);
 }
@@ -981,7 +959,7 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
     CHECK_MODEL(params, "covo_mpc_step");
     REQUIRE(args->gamma_sigma == 0.0f || args->mode == COVO_MODE_MPPI,
             "covo_mpc_step: gamma_sigma != 0 is MPPI's covariance adaptation (mppi.py:119-125)");
-    REQUIRE(!needs_table(params) || args->derive_keys == 1, "covo_mpc_step: disturb_kind=%d needs derive_keys = 1 (the per-step "
+    REQUIRE(!covo_needs_tables(*params) || args->derive_keys == 1, "covo_mpc_step: disturb_kind=%d needs derive_keys = 1 (the per-step "
             "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
     REFUSE_SHARDED_DIAG(h, args, "covo_mpc_step");
     REFUSE_SHARDED_PLAN(h, args, "covo_mpc_step");

@@ -66,6 +66,18 @@ static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullp
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->diag_log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->diag_log ? COVO_MAX_ENVS : 0); }
 
+// periodic / sin / drag / mixed (free.py:10-58): the disturbance model needs per-step force tables (disturb.hip)
+static inline bool covo_needs_tables(const covo_env_params &p)
+{
+    return p.disturb_kind >= COVO_DISTURB_PERIODIC && p.disturb_kind <= COVO_DISTURB_MIXED;
+}
+// scale of the one shared gaussian vector of the sampling rollouts (free.py:66-70 from the shared step key): off under
+// step_env(deterministic=True) (quadrotor.py:234-235)
+static inline float covo_shared_noise_scale(const covo_env_params &p, bool rollout_deterministic)
+{
+    return (p.disturb_kind == COVO_DISTURB_GAUSSIAN && !rollout_deterministic) ? p.dyn_noise_scale : 0.0f;
+}
+
 void covo_set_error(const char *fmt, ...);
 
 // hipFuncSetAttribute is per DEVICE: a one-time opt-in (dynamic LDS above 64 KB) guarded by a process-wide `static bool` was set on
@@ -293,11 +305,19 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
 struct SymStatsOut;  // sym_stats.hpp
 SymStatsOut sigma_ns_stats_out(void *workspace, int batch = 1);
 void step_state_destroy(covo_ctx *h);
-void step_graphs_drop(covo_ctx *h);  // before re-allocating h->ws_sigma / h->ws_hess: captured graphs hold their addresses
+void step_graphs_drop(covo_ctx *h);  // every captured step graph of the handle goes; the next step runs eagerly, the one after captures
+// h->ws_sigma / h->ws_hess (ws, bytes) to at least `need` bytes: only for batch sizes not seen before, never inside the steady-state
+// step.  The captured step graphs hold the old address in their kernel nodes: they are dropped before it is freed.
+int covo_grow_workspace(covo_ctx *h, void **ws, size_t *bytes, size_t need, hipStream_t s);
 void batch_state_destroy(covo_ctx *h);
 int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us_out, hipStream_t run);
+int covo_debug_batched_hessians_impl(covo_ctx *h, double *out, int64_t offset_doubles, int64_t count, hipStream_t s);
 int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
                            hipStream_t s);
+int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
+                                 hipStream_t s);
+// null: every instance of the batch can take the fused launch; else why not (instance index in *which)
+const char *batch_small_refusal(const covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, int *which);
 int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                    const float *f_shared, hipStream_t s);
 int launch_cholesky(const float *A, int n, int batch, float *L, hipStream_t s);

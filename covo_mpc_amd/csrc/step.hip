@@ -49,6 +49,69 @@ __global__ void step_begin_kernel(const float *__restrict__ a_mean, float *__res
 // carry the previous copy's sequence number (its workers would not wait for anything): one bump per copy
 __global__ void stream_seq_bump_kernel(unsigned *seq) { seq[0] = seq[0] + 1u; }
 
+// ---- the capture-once / replay cache every step path embeds (StepState, BatchState, BatchSmall).  The owner compares and records
+// its key itself (the three keys differ) and tells graph_cache_run whether it is unchanged:
+//   unchanged, graph present                    hipGraphLaunch on the caller's stream, nothing else
+//   unchanged, no graph, COVO_FLAG_NO_GRAPH clear   capture the step on h->side_stream, instantiate, launch on the caller's stream
+//   otherwise                                   a changed key drops the graph before anything is enqueued; eager on the caller's stream
+// so the first call with new buffers runs eagerly (all one-time attribute calls / allocations happen there), the second captures,
+// later ones replay.
+struct GraphCache {
+    bool have_key, have_graph;
+    hipGraph_t graph;
+    hipGraphExec_t exec;
+    void drop()
+    {
+        if (!have_graph) return;
+        (void)hipGraphExecDestroy(exec);
+        (void)hipGraphDestroy(graph);
+        have_graph = false;
+    }
+    void forget()  // the next call runs eagerly, the one after captures again
+    {
+        drop();
+        have_key = false;
+    }
+};
+
+// enqueue(stream) enqueues the step.  Capture is on the library's own stream (the caller's may be the legacy default stream, which
+// cannot capture); nothing executes during capture, the graph is then launched on the caller's stream.  A failed capture leaves
+// the cache without a graph.
+template <class Enqueue>
+static int graph_cache_run(covo_ctx *h, GraphCache &c, hipStream_t s, bool same, const char *name, Enqueue enqueue)
+{
+    if (!same) c.drop();
+    if (c.have_graph) {
+        COVO_CHECK_HIP(hipGraphLaunch(c.exec, s));
+        return 0;
+    }
+    if (!same || (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0) return enqueue(s);
+    hipStream_t cs = h->side_stream;
+    COVO_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
+    const int rc = enqueue(cs);
+    hipGraph_t g = nullptr;
+    hipError_t e = hipStreamEndCapture(cs, &g);
+    if (rc == 0 && e != hipSuccess) covo_set_error("%s: stream capture failed: %s", name, hipGetErrorString(e));
+    if (rc == 0 && e == hipSuccess && (e = hipGraphInstantiate(&c.exec, g, nullptr, nullptr, 0)) != hipSuccess)
+        covo_set_error("%s: hipGraphInstantiate failed: %s", name, hipGetErrorString(e));
+    if (rc != 0 || e != hipSuccess) {
+        if (g) (void)hipGraphDestroy(g);
+        return rc ? rc : (int)e;
+    }
+    c.graph = g;
+    c.have_graph = true;
+    COVO_CHECK_HIP(hipGraphLaunch(c.exec, s));
+    return 0;
+}
+
+// hipFree + null for every pointer given
+template <class... T>
+static void free_and_null(T *&...p)
+{
+    ((void)hipFree(p), ...);
+    ((p = nullptr), ...);
+}
+
 struct StepKey {
     covo_step_args args;
     covo_env_params params;
@@ -67,11 +130,8 @@ struct StepState {
     float *f_tab_rollout, *f_tab_hess;  // [H][4] per-step disturbance tables of the sampling rollouts / the Hessian (disturb.hip)
     unsigned *ticket;     // arrival counter of the fused small step (step_small.hip); 0 between launches
     unsigned *sync;       // [16] the streamed finalize launch's sequence number and panel flags (StreamGemmArgs::sync)
-    // graph cache
-    bool have_key, have_graph;
-    StepKey key;
-    hipGraph_t graph;
-    hipGraphExec_t exec;
+    GraphCache cache;
+    StepKey key;  // normalised arguments + parameters + stream; recorded by eager calls only
 };
 constexpr int DYN_BYTES = 48;
 // up to this many samples per GPU the step's epsilon is drawn by passenger workgroups of the Sigma chain's last launch
@@ -105,22 +165,9 @@ void step_state_destroy(covo_ctx *h)
 {
     StepState *st = reinterpret_cast<StepState *>(h->step);
     if (!st) return;
-    if (st->have_graph) {
-        (void)hipGraphExecDestroy(st->exec);
-        (void)hipGraphDestroy(st->graph);
-    }
-    (void)hipFree(st->dyn);
-    (void)hipFree(st->state_buf);
-    (void)hipFree(st->a_mean_shift);
-    (void)hipFree(st->R);
-    (void)hipFree(st->Sigma);
-    (void)hipFree(st->L);
-    (void)hipFree(st->Ls);
-    (void)hipFree(st->eps_tiled);
-    (void)hipFree(st->f_tab_rollout);
-    (void)hipFree(st->f_tab_hess);
-    (void)hipFree(st->ticket);
-    (void)hipFree(st->sync);
+    st->cache.drop();
+    free_and_null(st->dyn, st->state_buf, st->a_mean_shift, st->R, st->Sigma, st->L, st->Ls, st->eps_tiled, st->f_tab_rollout,
+                  st->f_tab_hess, st->ticket, st->sync);
     delete st;
     h->step = nullptr;
 }
@@ -171,7 +218,7 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
         return launch_step_small(h, p, a, state, am_shift, nullptr, st->dyn, 0.0f, st->ticket, s);
     // periodic / sin / drag / mixed (free.py:10-58): the wave-uniform part of every rollout step's force, for the sampling
     // rollouts (shared step key) and for the Hessian's deterministic rollout (per-step keys), resolved once per control step
-    const bool tables = p.disturb_kind >= COVO_DISTURB_PERIODIC && p.disturb_kind <= COVO_DISTURB_MIXED;
+    const bool tables = covo_needs_tables(p);
     if (tables && (rc = launch_disturb_tables_step(p, state, st->dyn, a.rollout_deterministic, st->f_tab_rollout,
                                                    a.mode == COVO_MODE_COVO_ONLINE ? st->f_tab_hess : nullptr, s))) return rc;
     if (a.mode == COVO_MODE_COVO_ONLINE) {
@@ -262,6 +309,14 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
                                  a.a_mean, s, nullptr, 1, h->ws_diag_rec, dg);
 }
 
+// a debug setter since the last step changed what a captured graph baked in (launch set, deflation switch, diagnostics target)
+static void step_sync_epoch(covo_ctx *h)
+{
+    if (h->dbg_epoch == h->opt.epoch) return;
+    step_graphs_drop(h);
+    h->dbg_epoch = h->opt.epoch;
+}
+
 int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                    const float *f_shared, hipStream_t s)
 {
@@ -269,10 +324,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
         int rc = step_state_init(h);
         if (rc) return rc;
     }
-    if (h->dbg_epoch != h->opt.epoch) {  // a debug setter changed what a captured graph baked in (launch set, deflation switch)
-        step_graphs_drop(h);
-        h->dbg_epoch = h->opt.epoch;
-    }
+    step_sync_epoch(h);
     StepState *st = reinterpret_cast<StepState *>(h->step);
     // per-step scalars: kernel arguments of the begin launch
     DynBlock blk;
@@ -284,22 +336,19 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
         std::memcpy(&blk.w[2 + i], &f, 4);
     }
     std::memcpy(&blk.w[8], &args->state, sizeof(const float *));
-    // the one shared gaussian vector of the sampling rollouts (free.py:66-70 from the shared step key): off under
-    // step_env(deterministic=True) (quadrotor.py:234-235)
-    const float shared_noise_scale =
-        (params->disturb_kind == COVO_DISTURB_GAUSSIAN && !args->rollout_deterministic) ? params->dyn_noise_scale : 0.0f;
+    const float shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
     // control_params.a_mean of this call: the handle's own buffer (a carried mean) or the caller's input (args->a_mean_in)
     const bool small = h->opt.fuse_small && step_small_eligible(h, *params, *args);
     if (small && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0) {
         // an eager handle: the WHOLE step is one launch, the begin launch's work included (per workgroup, step_small.hip)
-        st->have_key = false;  // (st->dyn / st->state_buf are not refreshed: a later graph capture starts from an eager call)
+        st->cache.have_key = false;  // (st->dyn / st->state_buf are not refreshed: a later graph capture starts from an eager call)
         return launch_step_small(h, *params, *args, args->state, args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift, &blk,
                                  nullptr, shared_noise_scale, st->ticket, s);
     }
     // eager covo-online steps (no per-step force tables, whose launch precedes the Hessian and reads the scalars): the begin work
     // rides in the Hessian's first launch -- one launch boundary less (COVO_FOLD_BEGIN=0 keeps the begin launch)
     if (h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
-        !(params->disturb_kind >= COVO_DISTURB_PERIODIC && params->disturb_kind <= COVO_DISTURB_MIXED)) {
+        !covo_needs_tables(*params)) {
         HessBegin hb;
         hb.a_mean_raw = args->a_mean_in ? args->a_mean_in : args->a_mean;
         hb.dyn_out = st->dyn;
@@ -307,7 +356,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
         hb.blk = &blk;
         hb.derive_keys = args->derive_keys;
         hb.shared_noise_scale = shared_noise_scale;
-        st->have_key = false;
+        st->cache.have_key = false;
         return enqueue_step(h, st, *params, *args, s, DebugMasks(), &hb, args->state);
     }
     hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, s,
@@ -324,40 +373,13 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     k.params.reset_traj = 0;  // the env step's auto-reset switches: no launch of the control step reads them
     k.params.reset_dt = k.params.reset_disturb_scale = 0.0;
     k.stream = s;
-    const bool same = st->have_key && std::memcmp(&k, &st->key, sizeof(k)) == 0;
-    if (same && st->have_graph) {
-        COVO_CHECK_HIP(hipGraphLaunch(st->exec, s));
-        return 0;
+    const bool same = st->cache.have_key && std::memcmp(&k, &st->key, sizeof(k)) == 0;
+    if (!same) {
+        st->key = k;
+        st->cache.have_key = true;
     }
-    if (same && !st->have_graph && (h->cfg.flags & COVO_FLAG_NO_GRAPH) == 0) {
-        // second call with identical buffers: capture (all one-time attribute calls / allocations happened in
-        // the eager first call)
-        // capture on the library's own stream (the caller's may be the legacy default stream, which cannot
-        // capture); nothing executes during capture, the graph is then launched on the caller's stream
-        hipStream_t cs = h->side_stream;
-        COVO_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        const int rc = enqueue_step(h, st, *params, *args, cs);
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(cs, &g);
-        if (rc) return rc;
-        if (e != hipSuccess) {
-            covo_set_error("covo_mpc_step: stream capture failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        COVO_CHECK_HIP(hipGraphInstantiate(&st->exec, g, nullptr, nullptr, 0));
-        st->graph = g;
-        st->have_graph = true;
-        COVO_CHECK_HIP(hipGraphLaunch(st->exec, s));
-        return 0;
-    }
-    if (!same && st->have_graph) {  // buffers changed: drop the stale graph
-        (void)hipGraphExecDestroy(st->exec);
-        (void)hipGraphDestroy(st->graph);
-        st->have_graph = false;
-    }
-    st->key = k;
-    st->have_key = true;
-    return enqueue_step(h, st, *params, *args, s);
+    return graph_cache_run(h, st->cache, s, same, "covo_mpc_step",
+                           [&](hipStream_t on) { return enqueue_step(h, st, *params, *args, on); });
 }
 
 // ---- the flight recorder behind a step (plan_trace.hip): one eager launch that rolls the new mean out with the inputs the step's
@@ -376,22 +398,60 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
     d.T = args->T;
     d.params = params;
     d.a_mean = args->a_mean;
-    const bool tables = params->disturb_kind >= COVO_DISTURB_PERIODIC && params->disturb_kind <= COVO_DISTURB_MIXED;
-    d.f_tab = (tables && st) ? st->f_tab_rollout : nullptr;
+    d.f_tab = (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr;
     d.key[0] = key0;
     d.key[1] = key1;
     for (int i = 0; i < 3; ++i) d.f_shared[i] = f_shared ? f_shared[i] : 0.0f;
     d.derive_keys = args->derive_keys;
-    d.shared_noise_scale =
-        (params->disturb_kind == COVO_DISTURB_GAUSSIAN && !args->rollout_deterministic) ? params->dyn_noise_scale : 0.0f;
+    d.shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
     return launch_plan_trace(h, &d, 1, false, state_true, trace_index, s);
 }
 
 
-// ---- profiling aid: `reps` copies of the selected part of one step captured into ONE graph and replayed; returns
-// the average time per copy (GPU time between two events around the replay).  Inside a graph the launches cost
-// what they cost in the product (no host launch overhead, no profiler inflation).  step_mask: enqueue_step's
-// phases; hess_mask / sigma_stages: see covo_common.hpp.  The step must have been called once before (scratch).
+// ---- profiling aids: `reps` copies of the selected part of one step captured into ONE graph and replayed; the average time per
+// copy (GPU time between two events around the replay, the best of the last three of four replays).  Inside a graph the launches
+// cost what they cost in the product (no host launch overhead, no profiler inflation).  enqueue_copy(stream) enqueues one copy.
+template <class Enqueue>
+static int time_graph_replays(covo_ctx *h, hipStream_t run, int reps, float *us_out, Enqueue enqueue_copy)
+{
+    hipStream_t cs = h->side_stream;
+    hipGraph_t g = nullptr;
+    hipGraphExec_t ge = nullptr;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    auto timed = [&]() -> int {
+        int rc = 0;
+        hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+        if (e == hipSuccess) {
+            for (int r = 0; r < reps && !rc; ++r) rc = enqueue_copy(cs);
+            e = hipStreamEndCapture(cs, &g);
+        }
+        if (rc) return rc;
+        COVO_CHECK_HIP(e);
+        COVO_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
+        COVO_CHECK_HIP(hipEventCreate(&e0));
+        COVO_CHECK_HIP(hipEventCreate(&e1));
+        float best = 1e30f;
+        for (int it = 0; it < 4; ++it) {
+            COVO_CHECK_HIP(hipEventRecord(e0, run));
+            COVO_CHECK_HIP(hipGraphLaunch(ge, run));
+            COVO_CHECK_HIP(hipEventRecord(e1, run));
+            COVO_CHECK_HIP(hipStreamSynchronize(run));
+            float ms = 0.f;
+            COVO_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
+            if (it > 0 && ms < best) best = ms;
+        }
+        *us_out = best * 1e3f / (float)reps;
+        return 0;
+    };
+    const int rc = timed();
+    if (e0) (void)hipEventDestroy(e0);
+    if (e1) (void)hipEventDestroy(e1);
+    if (ge) (void)hipGraphExecDestroy(ge);
+    if (g) (void)hipGraphDestroy(g);
+    return rc;
+}
+
+// step_mask: enqueue_step's phases; hess_mask / sigma_stages: see covo_common.hpp.  The step must have been called once before (scratch).
 int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, int step_mask,
                               int hess_mask, int sigma_stages, int reps, float *us_out, hipStream_t run)
 {
@@ -400,9 +460,7 @@ int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const 
         if (rc) return rc;
     }
     StepState *st = reinterpret_cast<StepState *>(h->step);
-    hipStream_t cs = h->side_stream;
-    const bool folded_online = h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE &&
-                               !(params->disturb_kind >= COVO_DISTURB_PERIODIC && params->disturb_kind <= COVO_DISTURB_MIXED);
+    const bool folded_online = h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && !covo_needs_tables(*params);
     if (((h->opt.fuse_small && step_small_eligible(h, *params, *args)) || folded_online) && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
         args->state != nullptr) {
         // the last step ran without a begin launch (the one-launch small step; covo-online with the begin work folded into the
@@ -421,40 +479,11 @@ int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const 
     dbg.step = step_mask;
     dbg.hess = hess_mask;
     dbg.sigma_stages = sigma_stages;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    int rc = 0;
-    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-        for (int r = 0; r < reps && !rc; ++r) {
-            if (args->mode == COVO_MODE_COVO_ONLINE && h->opt.stream_gemm && (step_mask & 12) == 12)
-                hipLaunchKernelGGL(stream_seq_bump_kernel, dim3(1), dim3(1), 0, cs, st->sync);
-            rc = enqueue_step(h, st, *params, *args, cs, dbg);
-        }
-        e = hipStreamEndCapture(cs, &g);
-    }
-    if (rc) return rc;
-    COVO_CHECK_HIP(e);
-    COVO_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    hipEvent_t e0, e1;
-    COVO_CHECK_HIP(hipEventCreate(&e0));
-    COVO_CHECK_HIP(hipEventCreate(&e1));
-    float best = 1e30f;
-    for (int it = 0; it < 4; ++it) {
-        COVO_CHECK_HIP(hipEventRecord(e0, run));
-        COVO_CHECK_HIP(hipGraphLaunch(ge, run));
-        COVO_CHECK_HIP(hipEventRecord(e1, run));
-        COVO_CHECK_HIP(hipStreamSynchronize(run));
-        float ms = 0.f;
-        COVO_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        if (it > 0 && ms < best) best = ms;
-    }
-    *us_out = best * 1e3f / (float)reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipGraphExecDestroy(ge);
-    (void)hipGraphDestroy(g);
-    return 0;
+    return time_graph_replays(h, run, reps, us_out, [&](hipStream_t cs) {
+        if (args->mode == COVO_MODE_COVO_ONLINE && h->opt.stream_gemm && (step_mask & 12) == 12)
+            hipLaunchKernelGGL(stream_seq_bump_kernel, dim3(1), dim3(1), 0, cs, st->sync);
+        return enqueue_step(h, st, *params, *args, cs, dbg);
+    });
 }
 
 
@@ -471,6 +500,17 @@ __global__ void batch_set_dyn_kernel(uint32_t *__restrict__ dyn, const BatchDyn 
 {
     const int i = threadIdx.x;
     if (i < 4 * n) dyn[12 * (i >> 2) + (i & 3)] = b.w[i >> 2][i & 3];
+}
+// the eager launch in front of every batched step (its kernel arguments ARE the keys): instance e's raw rng_act to dyn[12 e + 0..1]
+static void batch_upload_keys(uint32_t *dyn, const uint32_t *keys, int E, hipStream_t s)
+{
+    BatchDyn blk;
+    std::memset(&blk, 0, sizeof(blk));
+    for (int e = 0; e < E; ++e) {
+        blk.w[e][0] = keys[2 * e];
+        blk.w[e][1] = keys[2 * e + 1];
+    }
+    hipLaunchKernelGGL(batch_set_dyn_kernel, dim3(1), dim3(256), 0, s, dyn, blk, E);
 }
 // per instance: shift the mean (covo.py:201-203); act_key = split(rng_act)[1] (covo.py:212); f_shared = 0 (deterministic)
 __global__ void batch_begin_kernel(const float *__restrict__ a_mean, float *__restrict__ a_mean_shift, uint32_t *__restrict__ dyn)
@@ -503,32 +543,16 @@ struct BatchSmall {
     float *diag_rec = nullptr;   // [E][groups][4] the diagnostic records next to them (covo_set_step_diag)
     std::vector<char> args_host;
     std::vector<covo_env_params> params;
-    covo_batch_mode_args key;
+    covo_batch_mode_args key;  // with `stream` and `params`: what the cached argument blocks and graph were built for
     hipStream_t stream = nullptr;
-    bool have_key = false, have_graph = false;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    GraphCache cache{};
 };
 
-static void batch_small_drop_graph(BatchSmall *m)
-{
-    if (m->have_graph) {
-        (void)hipGraphExecDestroy(m->exec);
-        (void)hipGraphDestroy(m->graph);
-        m->have_graph = false;
-    }
-}
 static void batch_small_free(BatchSmall *m)
 {
-    batch_small_drop_graph(m);
-    (void)hipFree(m->dyn);
-    (void)hipFree(m->args);
-    (void)hipFree(m->tickets);
-    (void)hipFree(m->records);
-    (void)hipFree(m->diag_rec);
-    m->dyn = nullptr; m->args = nullptr; m->tickets = nullptr; m->records = nullptr; m->diag_rec = nullptr;
+    m->cache.forget();
+    free_and_null(m->dyn, m->args, m->tickets, m->records, m->diag_rec);
     m->n_envs = m->groups = 0;
-    m->have_key = false;
 }
 
 struct BatchState {
@@ -550,78 +574,80 @@ struct BatchState {
     std::vector<covo_env_params> env_inst_params;
     std::vector<char> ro_args_host;
     std::vector<covo_env_params> params;
-    covo_batch_args key;
+    covo_batch_args key;  // with `stream` and `params`: what the cached scratch and graph were built for
     hipStream_t stream = nullptr;
-    bool have_key = false, have_graph = false;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    GraphCache cache{};
     float4 *eps_tiled = nullptr;  // [E][ceil(N/32)][16][64]: the step's epsilon of every instance, drawn under the Sigma chain's
     size_t eps_cap = 0;           // finalize launch (eps_tiles.hpp), as in the single step
 };
 
+// (not env_inst and eps_tiled: the batched step re-allocates its scratch when the instance count changes, possibly between
+// batch_env_inst and the env step launch that reads env_inst; eps_tiled only ever grows)
 static void batch_state_free(BatchState *b)
 {
-    if (b->have_graph) {
-        (void)hipGraphExecDestroy(b->exec);
-        (void)hipGraphDestroy(b->graph);
-        b->have_graph = false;
-    }
-    (void)hipFree(b->dyn);
-    (void)hipFree(b->a_mean_shift);
-    (void)hipFree(b->R);
-    (void)hipFree(b->Sigma);
-    (void)hipFree(b->L);
-    (void)hipFree(b->consts);
-    (void)hipFree(b->ro_args);
-    (void)hipFree(b->partials);
-    (void)hipFree(b->diag_rec);
-    (void)hipFree(b->models);
-    (void)hipFree(b->tab_rollout);
-    (void)hipFree(b->tab_hess);
-    b->models = nullptr; b->tab_rollout = b->tab_hess = nullptr;
-    b->dyn = nullptr; b->a_mean_shift = nullptr; b->R = nullptr; b->Sigma = b->L = nullptr; b->consts = nullptr;
-    b->ro_args = nullptr; b->partials = nullptr; b->diag_rec = nullptr;
+    b->cache.drop();
+    free_and_null(b->dyn, b->a_mean_shift, b->R, b->Sigma, b->L, b->consts, b->ro_args, b->partials, b->diag_rec, b->models,
+                  b->tab_rollout, b->tab_hess);
 }
-// The captured graphs (fused step, env-batched step) hold the addresses of h->ws_sigma / h->ws_hess in their kernel nodes:
-// whoever re-allocates a workspace (a larger batch through covo_sigma / covo_hessian / covo_mpc_step_batched) calls this
-// first, so that a later covo_mpc_step re-captures instead of replaying launches that point into freed memory.
+// The captured graphs (fused step, env-batched steps) hold the addresses of h->ws_sigma / h->ws_hess in their kernel nodes and bake
+// the handle's launch set in: whoever re-allocates a workspace (covo_grow_workspace) or meets a moved debug epoch calls this
+// first, so that a later step re-captures instead of replaying launches that point into freed memory.
 void step_graphs_drop(covo_ctx *h)
 {
     StepState *st = reinterpret_cast<StepState *>(h->step);
-    if (st && st->have_graph) {
-        (void)hipGraphExecDestroy(st->exec);
-        (void)hipGraphDestroy(st->graph);
-        st->have_graph = false;
-    }
-    if (st) st->have_key = false;  // the next call runs eagerly, the one after captures again
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (b && b->have_graph) {
-        (void)hipGraphExecDestroy(b->exec);
-        (void)hipGraphDestroy(b->graph);
-        b->have_graph = false;
-    }
-    if (b) b->have_key = false;
-    if (b) {
-        batch_small_drop_graph(&b->small);
-        b->small.have_key = false;
-    }
+    if (st) st->cache.forget();
+    if (b) b->cache.forget();
+    if (b) b->small.cache.forget();
+}
+
+int covo_grow_workspace(covo_ctx *h, void **ws, size_t *bytes, size_t need, hipStream_t s)
+{
+    if (need <= *bytes) return 0;
+    COVO_CHECK_HIP(hipStreamSynchronize(s));
+    step_graphs_drop(h);
+    free_and_null(*ws);
+    *bytes = 0;
+    COVO_CHECK_HIP(hipMalloc(ws, need));
+    *bytes = need;
+    return 0;
+}
+
+static BatchState *batch_state(covo_ctx *h)
+{
+    if (!h->batch) h->batch = new BatchState();
+    return reinterpret_cast<BatchState *>(h->batch);
+}
+
+// instance e of a batched step's argument block
+struct BatchInst {
+    const float *state, *pos_traj, *vel_traj;
+    float *a_mean, *a, *cost, *groupmin;
+};
+static BatchInst batch_inst(const covo_batch_args &a, int e)
+{
+    const int N = a.n_samples;
+    BatchInst i;
+    i.state = a.states + (size_t)e * COVO_STATE_FLOATS;
+    i.pos_traj = a.pos_traj + (size_t)e * a.T * 3;
+    i.vel_traj = a.vel_traj + (size_t)e * a.T * 3;
+    i.a_mean = a.a_mean + (size_t)e * COVO_NA;
+    i.a = a.a + (size_t)e * COVO_H * N * 4;
+    i.cost = a.cost + (size_t)e * N;
+    i.groupmin = a.groupmin ? a.groupmin + (size_t)e * ((N + 63) / 64) : nullptr;
+    return i;
 }
 
 // the device array of per-instance env constants for covo_env_step_batched, rebuilt only when the parameters change
 int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_t s, const void **inst_dev)
 {
-    BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (!b) {
-        b = new BatchState();
-        h->batch = b;
-    }
+    BatchState *b = batch_state(h);
     const bool same = b->env_inst != nullptr && b->env_inst_n == E && (int)b->env_inst_params.size() == E &&
                       std::memcmp(b->env_inst_params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
     if (!same) {
         COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old array are done
         if (b->env_inst_n != E) {
-            (void)hipFree(b->env_inst);
-            b->env_inst = nullptr;
+            free_and_null(b->env_inst);
             b->env_inst_n = 0;
             COVO_CHECK_HIP(hipMalloc(&b->env_inst, env_step_inst_bytes(E)));
             b->env_inst_n = E;
@@ -641,9 +667,7 @@ void batch_state_destroy(covo_ctx *h)
     if (!b) return;
     batch_state_free(b);
     batch_small_free(&b->small);
-    (void)hipFree(b->eps_tiled);
-    (void)hipFree(b->env_inst);  // (not in batch_state_free: the batched step re-allocates its scratch when the instance count
-                                 // changes, possibly between batch_env_inst and the env step launch that reads this array)
+    free_and_null(b->eps_tiled, b->env_inst);
     delete b;
     h->batch = nullptr;
 }
@@ -709,72 +733,30 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
 int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us_out, hipStream_t run)
 {
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (!b || !b->have_key) {
+    if (!b || !b->cache.have_key) {
         covo_set_error("covo_debug_time_batched: call covo_mpc_step_batched first");
         return COVO_E_BADARG;
     }
-    hipStream_t cs = h->side_stream;
     COVO_CHECK_HIP(hipStreamSynchronize(run));
     DebugMasks dbg;
     dbg.step = step_mask;
-    hipGraph_t g = nullptr;
-    hipGraphExec_t ge = nullptr;
-    int rc = 0;
-    hipError_t e = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-    if (e == hipSuccess) {
-        for (int r = 0; r < reps && !rc; ++r) rc = batch_enqueue(h, b, b->key, cs, dbg);
-        e = hipStreamEndCapture(cs, &g);
-    }
-    if (rc) return rc;
-    COVO_CHECK_HIP(e);
-    COVO_CHECK_HIP(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
-    hipEvent_t e0, e1;
-    COVO_CHECK_HIP(hipEventCreate(&e0));
-    COVO_CHECK_HIP(hipEventCreate(&e1));
-    float best = 1e30f;
-    for (int it = 0; it < 4; ++it) {
-        COVO_CHECK_HIP(hipEventRecord(e0, run));
-        COVO_CHECK_HIP(hipGraphLaunch(ge, run));
-        COVO_CHECK_HIP(hipEventRecord(e1, run));
-        COVO_CHECK_HIP(hipStreamSynchronize(run));
-        float ms = 0.f;
-        COVO_CHECK_HIP(hipEventElapsedTime(&ms, e0, e1));
-        if (it > 0 && ms < best) best = ms;
-    }
-    *us_out = best * 1e3f / (float)reps;
-    (void)hipEventDestroy(e0);
-    (void)hipEventDestroy(e1);
-    (void)hipGraphExecDestroy(ge);
-    (void)hipGraphDestroy(g);
-    return 0;
+    return time_graph_replays(h, run, reps, us_out, [&](hipStream_t cs) { return batch_enqueue(h, b, b->key, cs, dbg); });
 }
 
 int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
                            hipStream_t s)
 {
     const int E = args->n_envs;
-    if (h->dbg_epoch != h->opt.epoch) {  // as in covo_step_impl
-        step_graphs_drop(h);
-        h->dbg_epoch = h->opt.epoch;
-    }
-    BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (!b) {
-        b = new BatchState();
-        h->batch = b;
-    }
-    bool same = b->have_key && b->n_envs == E && std::memcmp(&b->key, args, sizeof(*args)) == 0 && b->stream == s &&
-                std::memcmp(b->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
+    step_sync_epoch(h);
+    BatchState *b = batch_state(h);
+    const bool same = b->cache.have_key && b->n_envs == E && std::memcmp(&b->key, args, sizeof(*args)) == 0 && b->stream == s &&
+                      std::memcmp(b->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
     if (!same) {
         // new buffers / parameters / instance count: (re)allocate scratch and drop the stale graph (outside the steady state)
         COVO_CHECK_HIP(hipStreamSynchronize(s));
-        if (b->have_graph) {
-            (void)hipGraphExecDestroy(b->exec);
-            (void)hipGraphDestroy(b->graph);
-            b->have_graph = false;
-        }
+        b->cache.drop();
         if (b->n_envs != E) {
             batch_state_free(b);
-            b->have_graph = false;
             const size_t M = (size_t)COVO_NA * COVO_NA;
             COVO_CHECK_HIP(hipMalloc(&b->dyn, (size_t)E * 12 * sizeof(uint32_t)));
             COVO_CHECK_HIP(hipMalloc(&b->a_mean_shift, (size_t)E * COVO_NA * sizeof(float)));
@@ -797,79 +779,39 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         tmp.assign(disturb_models_bytes(E), 0);
         disturb_fill_models(params, E, tmp.data());
         COVO_CHECK_HIP(hipMemcpy(b->models, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-        b->tables = params[0].disturb_kind >= COVO_DISTURB_PERIODIC && params[0].disturb_kind <= COVO_DISTURB_MIXED;
+        b->tables = covo_needs_tables(params[0]);
         b->ro_args_host.assign(rollout_args_bytes(E), 0);
-        const int N = args->n_samples, ng = (N + 63) / 64;
+        const int N = args->n_samples;
         const int bG = rollout_workgroups(N, false, E);
         const bool brec = bG <= h->max_red_blocks;
-        for (int e = 0; e < E; ++e)
-            rollout_fill_args(b->ro_args_host.data(), e, args->states + (size_t)e * COVO_STATE_FLOATS,
-                              args->pos_traj + (size_t)e * args->T * 3, args->vel_traj + (size_t)e * args->T * 3, args->T,
-                              params[e], args->a + (size_t)e * COVO_H * N * 4, N, h->cfg.discount, args->cost + (size_t)e * N,
-                              brec ? nullptr : args->groupmin + (size_t)e * ng, reinterpret_cast<const float *>(b->dyn + 12 * e + 2),
+        for (int e = 0; e < E; ++e) {
+            const BatchInst i = batch_inst(*args, e);
+            rollout_fill_args(b->ro_args_host.data(), e, i.state, i.pos_traj, i.vel_traj, args->T, params[e], i.a, N, h->cfg.discount,
+                              i.cost, brec ? nullptr : i.groupmin, reinterpret_cast<const float *>(b->dyn + 12 * e + 2),
                               brec ? b->partials + (size_t)e * bG * COVO_PARTIAL_FLOATS : nullptr, h->cfg.lam, true,
                               b->tables ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr,
                               (brec && covo_diag_target(h)) ? b->diag_rec + (size_t)e * bG * 4 : nullptr);
+        }
         COVO_CHECK_HIP(hipMemcpy(b->ro_args, b->ro_args_host.data(), b->ro_args_host.size(), hipMemcpyHostToDevice));
         {
             const size_t need_e = (size_t)E * ((N + 31) / 32) * 16 * 64;
             if (need_e > b->eps_cap) {
-                (void)hipFree(b->eps_tiled);
-                b->eps_tiled = nullptr;
+                free_and_null(b->eps_tiled);
                 b->eps_cap = 0;
                 COVO_CHECK_HIP(hipMalloc(&b->eps_tiled, need_e * sizeof(float4)));
                 b->eps_cap = need_e;
             }
         }
-        const size_t need_s = sigma_ns_workspace_bytes(E), need_h = hessian_workspace_bytes(E);
-        if (need_s > h->ws_sigma_bytes || need_h > h->ws_hess_bytes) step_graphs_drop(h);  // captured launches point into them
-        if (need_s > h->ws_sigma_bytes) {
-            (void)hipFree(h->ws_sigma);
-            h->ws_sigma = nullptr;
-            h->ws_sigma_bytes = 0;
-            COVO_CHECK_HIP(hipMalloc(&h->ws_sigma, need_s));
-            h->ws_sigma_bytes = need_s;
-        }
-        if (need_h > h->ws_hess_bytes) {
-            (void)hipFree(h->ws_hess);
-            h->ws_hess = nullptr;
-            h->ws_hess_bytes = 0;
-            COVO_CHECK_HIP(hipMalloc(&h->ws_hess, need_h));
-            h->ws_hess_bytes = need_h;
-        }
+        int rc;  // (a grown workspace forgets every graph and key of the handle: this block records the key after it)
+        if ((rc = covo_grow_workspace(h, &h->ws_sigma, &h->ws_sigma_bytes, sigma_ns_workspace_bytes(E), s))) return rc;
+        if ((rc = covo_grow_workspace(h, &h->ws_hess, &h->ws_hess_bytes, hessian_workspace_bytes(E), s))) return rc;
         b->key = *args;
         b->stream = s;
-        b->have_key = true;
+        b->cache.have_key = true;
     }
-    BatchDyn blk;
-    std::memset(&blk, 0, sizeof(blk));
-    for (int e = 0; e < E; ++e) {
-        blk.w[e][0] = keys[2 * e];
-        blk.w[e][1] = keys[2 * e + 1];
-    }
-    hipLaunchKernelGGL(batch_set_dyn_kernel, dim3(1), dim3(256), 0, s, b->dyn, blk, E);
-    if (b->have_graph) {
-        COVO_CHECK_HIP(hipGraphLaunch(b->exec, s));
-        return 0;
-    }
-    if (same && (h->cfg.flags & COVO_FLAG_NO_GRAPH) == 0) {  // second identical call: capture
-        hipStream_t cs = h->side_stream;
-        COVO_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        const int rc = batch_enqueue(h, b, *args, cs);
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(cs, &g);
-        if (rc) return rc;
-        if (e != hipSuccess) {
-            covo_set_error("covo_mpc_step_batched: stream capture failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        COVO_CHECK_HIP(hipGraphInstantiate(&b->exec, g, nullptr, nullptr, 0));
-        b->graph = g;
-        b->have_graph = true;
-        COVO_CHECK_HIP(hipGraphLaunch(b->exec, s));
-        return 0;
-    }
-    return batch_enqueue(h, b, *args, s);
+    batch_upload_keys(b->dyn, keys, E, s);
+    return graph_cache_run(h, b->cache, s, same, "covo_mpc_step_batched",
+                           [&](hipStream_t on) { return batch_enqueue(h, b, *args, on); });
 }
 
 // MPPI / covo-offline for E instances: key upload + ONE fused launch (no begin launch: every workgroup shifts its instance's mean
@@ -879,21 +821,21 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
 static covo_step_args batch_small_instance(const covo_batch_mode_args &m, int e)
 {
     const covo_batch_args &a = m.base;
-    const int N = a.n_samples;
+    const BatchInst i = batch_inst(a, e);
     covo_step_args sa;
     std::memset(&sa, 0, sizeof(sa));
     sa.mode = m.mode;
-    sa.n_samples = N;
+    sa.n_samples = a.n_samples;
     sa.T = a.T;
     sa.n_table = m.n_table;
-    sa.state = a.states + (size_t)e * COVO_STATE_FLOATS;
-    sa.pos_traj = a.pos_traj + (size_t)e * a.T * 3;
-    sa.vel_traj = a.vel_traj + (size_t)e * a.T * 3;
-    sa.a_mean = a.a_mean + (size_t)e * COVO_NA;
+    sa.state = i.state;
+    sa.pos_traj = i.pos_traj;
+    sa.vel_traj = i.vel_traj;
+    sa.a_mean = i.a_mean;
     sa.a_cov = (m.mode == COVO_MODE_MPPI) ? a.a_cov + (size_t)e * COVO_H * 16 : nullptr;
     sa.L_table = (m.mode == COVO_MODE_COVO_OFFLINE) ? m.L_table + (size_t)e * m.L_table_stride : nullptr;
-    sa.a = a.a + (size_t)e * COVO_H * N * 4;
-    sa.cost = a.cost + (size_t)e * N;
+    sa.a = i.a;
+    sa.cost = i.cost;
     sa.gamma_mean = a.gamma_mean;
     sa.sample_sigma = a.sample_sigma;
     sa.derive_keys = 1;
@@ -902,7 +844,6 @@ static covo_step_args batch_small_instance(const covo_batch_mode_args &m, int e)
     return sa;
 }
 
-// null: every instance of the batch can take the fused launch; else why not (instance index in *which)
 const char *batch_small_refusal(const covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, int *which)
 {
     for (int e = 0; e < m->base.n_envs; ++e) {
@@ -920,21 +861,13 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
                                  hipStream_t s)
 {
     const int E = m->base.n_envs, N = m->base.n_samples, ng = (N + COVO_WAVE - 1) / COVO_WAVE;
-    if (h->dbg_epoch != h->opt.epoch) {  // as in covo_step_impl
-        step_graphs_drop(h);
-        h->dbg_epoch = h->opt.epoch;
-    }
-    BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (!b) {
-        b = new BatchState();
-        h->batch = b;
-    }
-    BatchSmall *q = &b->small;
-    const bool same = q->have_key && q->n_envs == E && std::memcmp(&q->key, m, sizeof(*m)) == 0 && q->stream == s &&
+    step_sync_epoch(h);
+    BatchSmall *q = &batch_state(h)->small;
+    const bool same = q->cache.have_key && q->n_envs == E && std::memcmp(&q->key, m, sizeof(*m)) == 0 && q->stream == s &&
                       std::memcmp(q->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
     if (!same) {
         COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old argument blocks are done
-        batch_small_drop_graph(q);
+        q->cache.drop();
         if (q->n_envs != E || q->groups != ng) {
             batch_small_free(q);
             COVO_CHECK_HIP(hipMalloc(&q->dyn, (size_t)E * 12 * sizeof(uint32_t)));
@@ -951,9 +884,9 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
         float *dg = covo_diag_target(h);
         for (int e = 0; e < E; ++e) {
             const covo_step_args sa = batch_small_instance(*m, e);
-            // the one shared gaussian vector of MPPI's sampling rollouts (free.py:66-70), per instance; off for CoVO (deterministic)
-            const float scale = (params[e].disturb_kind == COVO_DISTURB_GAUSSIAN && !sa.rollout_deterministic) ? params[e].dyn_noise_scale : 0.0f;
-            step_small_fill_args(h, q->args_host.data(), e, params[e], sa, q->dyn + 12 * e, scale, q->tickets + e,
+            // (the shared gaussian vector of MPPI's sampling rollouts, per instance; off for CoVO: deterministic)
+            step_small_fill_args(h, q->args_host.data(), e, params[e], sa, q->dyn + 12 * e,
+                                 covo_shared_noise_scale(params[e], sa.rollout_deterministic), q->tickets + e,
                                  q->records + (size_t)e * ng * COVO_PARTIAL_FLOATS, q->diag_rec + (size_t)e * ng * 4,
                                  dg ? dg + (size_t)e * COVO_DIAG_FLOATS : nullptr);
         }
@@ -961,38 +894,13 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
         std::memset(&q->key, 0, sizeof(q->key));
         q->key = *m;
         q->stream = s;
-        q->have_key = true;
+        q->cache.have_key = true;
     }
-    BatchDyn blk;
-    std::memset(&blk, 0, sizeof(blk));
-    for (int e = 0; e < E; ++e) {
-        blk.w[e][0] = keys[2 * e];
-        blk.w[e][1] = keys[2 * e + 1];
-    }
-    hipLaunchKernelGGL(batch_set_dyn_kernel, dim3(1), dim3(256), 0, s, q->dyn, blk, E);
+    batch_upload_keys(q->dyn, keys, E, s);
     const bool mppi = m->mode == COVO_MODE_MPPI;
-    if (q->have_graph) {
-        COVO_CHECK_HIP(hipGraphLaunch(q->exec, s));
-        return 0;
-    }
-    if (same && (h->cfg.flags & COVO_FLAG_NO_GRAPH) == 0) {  // second identical call: capture
-        hipStream_t cs = h->side_stream;
-        COVO_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-        const int rc = launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, cs);
-        hipGraph_t g = nullptr;
-        const hipError_t e = hipStreamEndCapture(cs, &g);
-        if (rc) return rc;
-        if (e != hipSuccess) {
-            covo_set_error("covo_mpc_step_batched_mode: stream capture failed: %s", hipGetErrorString(e));
-            return (int)e;
-        }
-        COVO_CHECK_HIP(hipGraphInstantiate(&q->exec, g, nullptr, nullptr, 0));
-        q->graph = g;
-        q->have_graph = true;
-        COVO_CHECK_HIP(hipGraphLaunch(q->exec, s));
-        return 0;
-    }
-    return launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, s);
+    return graph_cache_run(h, q->cache, s, same, "covo_mpc_step_batched_mode", [&](hipStream_t on) {
+        return launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, on);
+    });
 }
 
 // mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run) or MPPI / COVO_OFFLINE (covo_step_batched_small_impl)
@@ -1006,17 +914,18 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
     PlanInstDesc d[COVO_MAX_ENVS];
     std::memset(d, 0, sizeof(d));
     for (int e = 0; e < E; ++e) {
-        d[e].state = args->states + (size_t)e * COVO_STATE_FLOATS;
-        d[e].pos_traj = args->pos_traj + (size_t)e * args->T * 3;
-        d[e].vel_traj = args->vel_traj + (size_t)e * args->T * 3;
+        const BatchInst i = batch_inst(*args, e);
+        d[e].state = i.state;
+        d[e].pos_traj = i.pos_traj;
+        d[e].vel_traj = i.vel_traj;
         d[e].T = args->T;
         d[e].params = &params[e];
-        d[e].a_mean = args->a_mean + (size_t)e * COVO_NA;
+        d[e].a_mean = i.a_mean;
         d[e].f_tab = (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
         // the instance's raw rng_act: covo-online's begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone
         d[e].key_mem = online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e;
         d[e].derive_keys = 1;
-        d[e].shared_noise_scale = (mode == COVO_MODE_MPPI && params[e].disturb_kind == COVO_DISTURB_GAUSSIAN) ? params[e].dyn_noise_scale : 0.0f;
+        d[e].shared_noise_scale = covo_shared_noise_scale(params[e], mode != COVO_MODE_MPPI);  // (CoVO's rollouts are deterministic)
     }
     return launch_plan_trace(h, d, E, true, states_true, trace_index, s);
 }

@@ -140,6 +140,64 @@ def test_batched_mode_step_equals_replicas(name, N, lam, rollover, E, graph, mon
         assert (b.a_mean[0] - b.a_mean[1]).abs().max() > 1e-4  # different plants, different plans
 
 
+@pytest.mark.parametrize("name", ["covo-online", "mppi"])
+def test_batched_graph_caches_are_dropped_by_growth_new_buffers_and_debug_setters(name, monkeypatch):
+    """The env-batched twin of tests/test_gpu_parity.py::test_workspace_growth_drops_the_captured_step_graph, for both batched graph
+    caches (covo-online: covo_mpc_step_batched; MPPI: the fused launch of covo_mpc_step_batched_mode).  A graph-replaying handle and
+    a COVO_FLAG_NO_GRAPH handle step the same 3 instances side by side for 8 steps; a_mean and a_cov are torch.equal after every
+    step.  The graph handle captures at step 1 and then meets, each time two steps later (eager call, re-capture), every event that
+    must invalidate its caches:
+      after step 1: covo_sigma and covo_hessian on a larger batch (both workspaces the captured launches point into are re-allocated);
+      after step 3: a new a_mean buffer (the argument block, which is the cache key, changes);
+      after step 5: a covo_debug_set_* switch flipped and restored (the handle's epoch moves on)."""
+    import covo_mpc_amd as cm
+    N, lam, E, B = 1024, "0.01", 3, 5
+    env = _env()
+    inst = _instances(env, name, N, lam, E)
+    cp0 = inst[0]["cp"]
+
+    def build():
+        if name == "mppi":
+            return _batched(env, name, inst, N, lam)
+        return cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
+                                                    sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV)
+    monkeypatch.setenv("COVO_GRAPH", "1")
+    bg = build()
+    monkeypatch.delenv("COVO_GRAPH")
+    monkeypatch.setenv("COVO_NO_GRAPH", "1")
+    be = build()
+    assert bg.core.uses_graph and not be.core.uses_graph
+    for b in (bg, be):
+        b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
+    rng = np.random.default_rng(1)
+    for step in range(8):
+        k_acts = []
+        for i in inst:
+            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
+            k_acts.append(np.asarray(k_act))
+        noisy = [i["info"]["noisy_state"] for i in inst]
+        bg(noisy, np.stack(k_acts))
+        u = be(noisy, np.stack(k_acts)).clone()
+        assert torch.equal(bg.a_mean, be.a_mean) and torch.equal(bg.a_cov, be.a_cov), (name, step)
+        if step == 1:
+            A = rng.normal(size=(B, 128, 128))
+            S, L = bg.core.sigma(torch.from_numpy(0.05 * (A + np.transpose(A, (0, 2, 1)))).to(DEV), 0.5, batch=B)
+            assert torch.isfinite(S).all()
+            ds = noisy[0].to_device(DEV)
+            Hs = bg.core.hessian(ds.packed.repeat(B), ds, bg._params[0], bg.a_mean[0].repeat(B), batch=B)
+            assert torch.isfinite(Hs).all()
+        if step == 3:
+            bg.a_mean = bg.a_mean.clone()  # (in/out: a stale graph would go on updating the old buffer)
+            bg._args = bg._make_args(bg._states_buf, *bg._traj)
+        if step == 5:  # (1 is the default of a handle created without COVO_NS_MERGED in the environment)
+            _lib.check(bg.core.lib.covo_debug_set_ns_merged(bg.core.h, 0), "ns_merged")
+            _lib.check(bg.core.lib.covo_debug_set_ns_merged(bg.core.h, 1), "ns_merged")
+        for e, i in enumerate(inst):
+            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u[e].cpu().numpy(), i["params"])
+    assert bg.core.device_status() == 0 and be.core.device_status() == 0 and torch.isfinite(bg.a_mean).all()
+    assert (bg.a_mean[0] - bg.a_mean[1]).abs().max() > 1e-4  # different plants, different plans
+
+
 def _oracle_check_instance(name, env, params, ns, a_mean_before, k_act, a_dev_t, cost_dev_t, a_mean_new_t, lam, rollover=False):
     """The checks and bars of tests/test_gpu_parity.py::_oracle_check_of_a_fused_step for one instance of a batch, with the
     instance's own parameters.  -> how many samples used the widened bar (at most max(2, N // 4096) may)."""
