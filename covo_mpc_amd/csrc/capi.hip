@@ -173,14 +173,27 @@ int covo_randn_jax(covo_handle_t h, uint32_t key0, uint32_t key1, int64_t n_tota
     return launch_randn_jax(key0, key1, n_total, sample_offset, n_samples, mppi, eps_out, (hipStream_t)stream);
 }
 
+// what the four stand-alone noise entry points share: a_out = clip(mu + L eps); the caller adds eps, or the key of the in-kernel draw
+static NoiseDesc noise_desc(const covo_ctx *h, const float *L, const float *mu, int N, float *a_out)
+{
+    NoiseDesc d;
+    d.L = L;
+    d.mu = mu;
+    d.N = N;
+    d.a = a_out;
+    d.propagate_nan = covo_propagate_nan(h);
+    return d;
+}
+
 int covo_noise_gemm(covo_handle_t h, const float *L, const float *mu, const float *eps, int32_t N, float *a_out,
                     void *stream)
 {
     REQUIRE(h, "covo_noise_gemm: null handle");
     CHECK_DEVICE(h, "covo_noise_gemm");
     REQUIRE(L && mu && eps && a_out && N > 0, "covo_noise_gemm: bad argument");
-    return launch_noise_gemm(L, mu, eps, 0u, 0u, 0, N, a_out, (hipStream_t)stream, nullptr, nullptr, 0, 1, false, nullptr,
-                             covo_propagate_nan(h));
+    NoiseDesc d = noise_desc(h, L, mu, N, a_out);
+    d.eps = eps;
+    return launch_noise_gemm(d, (hipStream_t)stream);
 }
 
 int covo_noise_gemm_philox(covo_handle_t h, const float *L, const float *mu, uint32_t key0, uint32_t key1,
@@ -189,8 +202,11 @@ int covo_noise_gemm_philox(covo_handle_t h, const float *L, const float *mu, uin
     REQUIRE(h, "covo_noise_gemm_philox: null handle");
     CHECK_DEVICE(h, "covo_noise_gemm_philox");
     REQUIRE(L && mu && a_out && N > 0, "covo_noise_gemm_philox: bad argument");
-    return launch_noise_gemm(L, mu, nullptr, key0, key1, sample_offset, N, a_out, (hipStream_t)stream, nullptr, nullptr, 0, 1, false,
-                             nullptr, covo_propagate_nan(h));
+    NoiseDesc d = noise_desc(h, L, mu, N, a_out);
+    d.key[0] = key0;
+    d.key[1] = key1;
+    d.sample_offset = sample_offset;
+    return launch_noise_gemm(d, (hipStream_t)stream);
 }
 
 int covo_noise_blockdiag(covo_handle_t h, const float *Ls, const float *mu, const float *eps, int32_t N, float *a_out,
@@ -198,7 +214,9 @@ int covo_noise_blockdiag(covo_handle_t h, const float *Ls, const float *mu, cons
 {
     REQUIRE(h, "covo_noise_blockdiag: null handle");
     REQUIRE(Ls && mu && eps && a_out && N > 0, "covo_noise_blockdiag: bad argument");
-    return launch_noise_blockdiag(Ls, mu, eps, 0u, 0u, 0, N, a_out, (hipStream_t)stream, nullptr, covo_propagate_nan(h));
+    NoiseDesc d = noise_desc(h, Ls, mu, N, a_out);
+    d.eps = eps;
+    return launch_noise_blockdiag(d, (hipStream_t)stream);
 }
 
 int covo_noise_blockdiag_philox(covo_handle_t h, const float *Ls, const float *mu, uint32_t key0, uint32_t key1,
@@ -206,8 +224,11 @@ int covo_noise_blockdiag_philox(covo_handle_t h, const float *Ls, const float *m
 {
     REQUIRE(h, "covo_noise_blockdiag_philox: null handle");
     REQUIRE(Ls && mu && a_out && N > 0, "covo_noise_blockdiag_philox: bad argument");
-    return launch_noise_blockdiag(Ls, mu, nullptr, key0, key1, sample_offset, N, a_out, (hipStream_t)stream, nullptr,
-                                  covo_propagate_nan(h));
+    NoiseDesc d = noise_desc(h, Ls, mu, N, a_out);
+    d.key[0] = key0;
+    d.key[1] = key1;
+    d.sample_offset = sample_offset;
+    return launch_noise_blockdiag(d, (hipStream_t)stream);
 }
 
 int covo_rollout_cost(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
@@ -221,9 +242,24 @@ int covo_rollout_cost(covo_handle_t h, const float *state, const float *pos_traj
     CHECK_MODEL(params, "covo_rollout_cost");
     REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_rollout_cost: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
             params->disturb_kind);
-    return launch_rollout(state, pos_traj, vel_traj, T, *params, f_disturb_shared, a, N, h->cfg.discount,
-                          (h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) != 0, cost_out, groupmin, pos_stats, h->ws_stats,
-                          (hipStream_t)stream, nullptr, nullptr, 0.0f, f_disturb_steps, 0, covo_propagate_nan(h));
+    RolloutDesc d;
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.f_shared = f_disturb_shared;
+    d.f_tab = f_disturb_steps;
+    d.a = a;
+    d.N = N;
+    d.discount = h->cfg.discount;
+    d.cost = cost_out;
+    d.groupmin = groupmin;
+    d.pos_stats = pos_stats;
+    d.stats_ws = h->ws_stats;
+    if ((h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) != 0) d.clip = ROLLOUT_CLIP_TRUSTED;
+    else d.clip = covo_propagate_nan(h) ? ROLLOUT_CLIP_REAPPLY_NAN : ROLLOUT_CLIP_REAPPLY;
+    return launch_rollout(d, (hipStream_t)stream);
 }
 
 int covo_disturb_table(covo_handle_t h, const covo_env_params *params, const float *state, int32_t batch,
@@ -280,11 +316,24 @@ int covo_debug_time_rollout(covo_handle_t h, const float *state, const float *po
     hipError_t err = hipEventCreate(&e0);
     if (err == hipSuccess) err = hipEventCreate(&e1);
     int rc = 0;
-    auto launch = [&]() {
-        return launch_rollout(state, pos_traj, vel_traj, T, *params, f_disturb_shared, a, N, h->cfg.discount, clipped, cost_out,
-                              rec ? nullptr : groupmin, nullptr, h->ws_stats, s, nullptr, rec ? h->ws_partials : nullptr, h->cfg.lam,
-                              f_disturb_steps);
-    };
+    RolloutDesc d;
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.f_shared = f_disturb_shared;
+    d.f_tab = f_disturb_steps;
+    d.a = a;
+    d.N = N;
+    d.discount = h->cfg.discount;
+    d.cost = cost_out;
+    d.groupmin = rec ? nullptr : groupmin;
+    d.stats_ws = h->ws_stats;
+    d.records = rec ? h->ws_partials : nullptr;
+    d.lam = h->cfg.lam;
+    d.clip = clipped ? ROLLOUT_CLIP_TRUSTED : ROLLOUT_CLIP_REAPPLY;
+    auto launch = [&]() { return launch_rollout(d, s); };
     for (int i = 0; i < 3 && !rc && err == hipSuccess; ++i) rc = launch();
     constexpr int BATCHES = 3;
     float best = 1e30f, sum = 0.0f;
@@ -310,6 +359,31 @@ int covo_debug_time_rollout(covo_handle_t h, const float *state, const float *po
     return 0;
 }
 
+// the input half of the four stand-alone softmax updates below; the merges of rank records: G records, `stride` floats apart,
+// blended into the new mean
+static UpdateDesc update_from_costs(const float *cost, const float *a, int N, const float *groupmin)
+{
+    UpdateDesc d;
+    d.cost = cost;
+    d.a = a;
+    d.N = N;
+    d.blockmin = groupmin;
+    d.n_blockmin = (N + 63) / 64;
+    return d;
+}
+static UpdateDesc update_from_records(const float *records, int G, int stride, const float *a_mean_old, float gamma_mean,
+                                      float *a_mean_out)
+{
+    UpdateDesc d;
+    d.partials = records;
+    d.G = G;
+    d.stride = stride;
+    d.a_mean_old = a_mean_old;
+    d.gamma_mean = gamma_mean;
+    d.a_mean_out = a_mean_out;
+    return d;
+}
+
 int covo_softmax_reduce(covo_handle_t h, const float *cost, const float *a, int32_t N, const float *groupmin,
                         float *partial_out, void *stream)
 {
@@ -317,8 +391,9 @@ int covo_softmax_reduce(covo_handle_t h, const float *cost, const float *a, int3
     CHECK_DEVICE(h, "covo_softmax_reduce");
     REQUIRE(cost && a && partial_out, "covo_softmax_reduce: bad argument");
     REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_softmax_reduce: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
-    return launch_softmax_reduce(h, cost, a, N, groupmin, (N + 63) / 64, partial_out, nullptr, 1.0f, nullptr,
-                                 (hipStream_t)stream);
+    UpdateDesc d = update_from_costs(cost, a, N, groupmin);
+    d.partial_out = partial_out;
+    return launch_softmax_reduce(h, d, (hipStream_t)stream);
 }
 
 int covo_softmax_update(covo_handle_t h, const float *cost, const float *a, int32_t N, const float *groupmin,
@@ -328,8 +403,11 @@ int covo_softmax_update(covo_handle_t h, const float *cost, const float *a, int3
     CHECK_DEVICE(h, "covo_softmax_update");
     REQUIRE(cost && a && a_mean_old && a_mean_out, "covo_softmax_update: bad argument");
     REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_softmax_update: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
-    return launch_softmax_reduce(h, cost, a, N, groupmin, (N + 63) / 64, nullptr, a_mean_old, gamma_mean, a_mean_out,
-                                 (hipStream_t)stream);
+    UpdateDesc d = update_from_costs(cost, a, N, groupmin);
+    d.a_mean_old = a_mean_old;
+    d.gamma_mean = gamma_mean;
+    d.a_mean_out = a_mean_out;
+    return launch_softmax_reduce(h, d, (hipStream_t)stream);
 }
 
 int covo_softmax_update_cov(covo_handle_t h, const float *cost, const float *a, int32_t N, const float *groupmin,
@@ -340,8 +418,14 @@ int covo_softmax_update_cov(covo_handle_t h, const float *cost, const float *a, 
     CHECK_DEVICE(h, "covo_softmax_update_cov");
     REQUIRE(cost && a && a_mean_old && a_cov_old && a_mean_out && a_cov_out, "covo_softmax_update_cov: bad argument");
     REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_softmax_update_cov: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
-    return launch_softmax_update_cov(h, cost, a, N, groupmin, (N + 63) / 64, a_mean_old, gamma_mean, a_cov_old, gamma_sigma,
-                                     a_mean_out, a_cov_out, (hipStream_t)stream);
+    UpdateDesc d = update_from_costs(cost, a, N, groupmin);
+    d.a_mean_old = a_mean_old;
+    d.gamma_mean = gamma_mean;
+    d.a_mean_out = a_mean_out;
+    d.a_cov_old = a_cov_old;
+    d.gamma_sigma = gamma_sigma;
+    d.a_cov_out = a_cov_out;
+    return launch_softmax_update_cov(h, d, (hipStream_t)stream);
 }
 
 int covo_softmax_reduce_cov(covo_handle_t h, const float *cost, const float *a, int32_t N, const float *groupmin,
@@ -351,7 +435,10 @@ int covo_softmax_reduce_cov(covo_handle_t h, const float *cost, const float *a, 
     CHECK_DEVICE(h, "covo_softmax_reduce_cov");
     REQUIRE(cost && a && a_mean_old && record_out, "covo_softmax_reduce_cov: bad argument");
     REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_softmax_reduce_cov: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
-    return launch_softmax_reduce_cov(h, cost, a, N, groupmin, (N + 63) / 64, a_mean_old, record_out, (hipStream_t)stream);
+    UpdateDesc d = update_from_costs(cost, a, N, groupmin);
+    d.a_mean_old = a_mean_old;
+    d.partial_out = record_out;
+    return launch_softmax_update_cov(h, d, (hipStream_t)stream);
 }
 
 int covo_merge_ranks_cov(covo_handle_t h, const float *records, int32_t G, const float *a_mean_old, float gamma_mean,
@@ -361,10 +448,13 @@ int covo_merge_ranks_cov(covo_handle_t h, const float *records, int32_t G, const
     REQUIRE(h, "covo_merge_ranks_cov: null handle");
     CHECK_DEVICE(h, "covo_merge_ranks_cov");
     REQUIRE(records && a_mean_old && a_cov_old && a_mean_out && a_cov_out && G > 0, "covo_merge_ranks_cov: bad argument");
-    int rc = launch_merge_cov(records, G, COVO_RANK_RECORD_COV_FLOATS, h->cfg.lam, a_mean_old, gamma_mean, a_cov_old, gamma_sigma,
-                              a_mean_out, a_cov_out, (hipStream_t)stream);
+    UpdateDesc d = update_from_records(records, G, COVO_RANK_RECORD_COV_FLOATS, a_mean_old, gamma_mean, a_mean_out);
+    d.a_cov_old = a_cov_old;
+    d.gamma_sigma = gamma_sigma;
+    d.a_cov_out = a_cov_out;
+    int rc = launch_merge_cov(d, h->cfg.lam, (hipStream_t)stream);
     if (rc) return rc;
-    if (pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, pos_stats_out, (hipStream_t)stream, true);
+    if (pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, COVO_RANK_RECORD_COV_FLOATS, pos_stats_out, (hipStream_t)stream);
     return rc;
 }
 
@@ -374,7 +464,8 @@ int covo_merge(covo_handle_t h, const float *partials, int32_t G, const float *a
     REQUIRE(h, "covo_merge: null handle");
     CHECK_DEVICE(h, "covo_merge");
     REQUIRE(partials && a_mean_old && a_mean_out && G > 0, "covo_merge: bad argument");
-    return launch_merge(partials, G, h->cfg.lam, a_mean_old, gamma_mean, a_mean_out, (hipStream_t)stream);
+    return launch_merge(update_from_records(partials, G, COVO_PARTIAL_FLOATS, a_mean_old, gamma_mean, a_mean_out), h->cfg.lam,
+                        (hipStream_t)stream);
 }
 
 int covo_merge_ranks(covo_handle_t h, const float *records, int32_t G, const float *a_mean_old, float gamma_mean,
@@ -383,10 +474,10 @@ int covo_merge_ranks(covo_handle_t h, const float *records, int32_t G, const flo
     REQUIRE(h, "covo_merge_ranks: null handle");
     CHECK_DEVICE(h, "covo_merge_ranks");
     REQUIRE(records && a_mean_old && a_mean_out && G > 0, "covo_merge_ranks: bad argument");
-    int rc = launch_merge(records, G, h->cfg.lam, a_mean_old, gamma_mean, a_mean_out, (hipStream_t)stream, nullptr, 1,
-                          COVO_RANK_RECORD_FLOATS);
+    int rc = launch_merge(update_from_records(records, G, COVO_RANK_RECORD_FLOATS, a_mean_old, gamma_mean, a_mean_out), h->cfg.lam,
+                          (hipStream_t)stream);
     if (rc) return rc;
-    if (pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, pos_stats_out, (hipStream_t)stream);
+    if (pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, COVO_RANK_RECORD_FLOATS, pos_stats_out, (hipStream_t)stream);
     return rc;
 }
 
@@ -398,10 +489,10 @@ int covo_merge_ranks_wide(covo_handle_t h, const float *records, int32_t G, int3
     REQUIRE(records && a_mean_old && a_mean_out && G > 0, "covo_merge_ranks_wide: bad argument");
     REQUIRE(record_floats == COVO_RANK_RECORD_FLOATS || record_floats == COVO_RANK_RECORD_COV_FLOATS,
             "covo_merge_ranks_wide: record_floats=%d is neither COVO_RANK_RECORD_FLOATS nor COVO_RANK_RECORD_COV_FLOATS", record_floats);
-    int rc = launch_merge(records, G, h->cfg.lam, a_mean_old, gamma_mean, a_mean_out, (hipStream_t)stream, nullptr, 1, record_floats);
+    int rc = launch_merge(update_from_records(records, G, record_floats, a_mean_old, gamma_mean, a_mean_out), h->cfg.lam,
+                          (hipStream_t)stream);
     if (rc) return rc;
-    if (pos_stats_out != nullptr)
-        rc = launch_rank_stats_sum(records, G, pos_stats_out, (hipStream_t)stream, record_floats == COVO_RANK_RECORD_COV_FLOATS);
+    if (pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, record_floats, pos_stats_out, (hipStream_t)stream);
     return rc;
 }
 
@@ -463,8 +554,18 @@ int covo_hessian(covo_handle_t h, const float *state, const float *pos_traj, con
             params->disturb_kind);
     const int rc = covo_grow_workspace(h, &h->ws_hess, &h->ws_hess_bytes, hessian_workspace_bytes(batch), (hipStream_t)stream);
     if (rc) return rc;
-    return launch_hessian(state, pos_traj, vel_traj, T, *params, a_mean, batch, R_out, h->ws_hess, (hipStream_t)stream, nullptr, 0,
-                          nullptr, f_disturb_steps, nullptr, h->status_dev);
+    HessianDesc d;
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a_mean = a_mean;
+    d.f_tab = f_disturb_steps;
+    d.batch = batch;
+    d.R = R_out;
+    d.status_dev = h->status_dev;
+    return launch_hessian(d, h->ws_hess, (hipStream_t)stream, DebugMasks());
 }
 
 int covo_hessian_pairs(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
@@ -474,7 +575,17 @@ int covo_hessian_pairs(covo_handle_t h, const float *state, const float *pos_tra
     REQUIRE(h, "covo_hessian_pairs: null handle");
     REQUIRE(state && pos_traj && vel_traj && params && a_mean && R_out && T > 0 && batch > 0, "covo_hessian_pairs: bad argument");
     CHECK_MODEL(params, "covo_hessian_pairs");
-    return launch_hessian_pairs(state, pos_traj, vel_traj, T, *params, a_mean, batch, R_out, (hipStream_t)stream, f_disturb_steps);
+    HessianDesc d;
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a_mean = a_mean;
+    d.f_tab = f_disturb_steps;
+    d.batch = batch;
+    d.R = R_out;
+    return launch_hessian_pairs(d, (hipStream_t)stream);
 }
 
 int covo_sigma(covo_handle_t h, const double *R, int32_t batch, float sample_sigma, float *Sigma_out, float *L_out,
@@ -485,8 +596,15 @@ int covo_sigma(covo_handle_t h, const double *R, int32_t batch, float sample_sig
     REQUIRE(R && L_out && batch > 0 && sample_sigma > 0.0f, "covo_sigma: bad argument");
     const int rc = covo_grow_workspace(h, &h->ws_sigma, &h->ws_sigma_bytes, sigma_ns_workspace_bytes(batch), (hipStream_t)stream);
     if (rc) return rc;
-    return launch_sigma_ns(h->opt, R, batch, sample_sigma, Sigma_out, L_out, h->ws_sigma, (hipStream_t)stream, nullptr, h->status_dev,
-                           (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0);
+    SigmaNsDesc d;
+    d.R = R;
+    d.batch = batch;
+    d.sample_sigma = sample_sigma;
+    d.Sigma = Sigma_out;
+    d.L = L_out;
+    d.status = h->status_dev;
+    d.persistent_ok = (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0;
+    return launch_sigma_ns(h->opt, d, h->ws_sigma, (hipStream_t)stream, DebugMasks());
 }
 
 // ---- per-HANDLE experiment switches (CovoOpts, covo_common.hpp); every setter bumps the handle's epoch: its captured step graphs
@@ -696,13 +814,17 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
                 // mppi.py:119-125 on sharded ranks: the record also carries the 320 second moments (COVO_RANK_RECORD_COV_FLOATS);
                 // a_cov was shifted in place by the begin launch and is adapted in place, identically on every rank
                 if ((rc = exchange_records(h, args->partial_out, nullptr, &gathered, s, COVO_RANK_RECORD_COV_FLOATS))) return rc;
-                if ((rc = launch_merge_cov(gathered, exchange_world(h), COVO_RANK_RECORD_COV_FLOATS, h->cfg.lam, args->a_mean_shift,
-                                           args->gamma_mean, args->a_cov, args->gamma_sigma, args->a_mean, args->a_cov, s)))
-                    return rc;
+                UpdateDesc d = update_from_records(gathered, exchange_world(h), COVO_RANK_RECORD_COV_FLOATS, args->a_mean_shift,
+                                                   args->gamma_mean, args->a_mean);
+                d.a_cov_old = args->a_cov;
+                d.gamma_sigma = args->gamma_sigma;
+                d.a_cov_out = args->a_cov;
+                if ((rc = launch_merge_cov(d, h->cfg.lam, s))) return rc;
             } else {
                 if ((rc = exchange_records(h, args->partial_out, nullptr, &gathered, s))) return rc;
-                if ((rc = launch_merge(gathered, exchange_world(h), h->cfg.lam, args->a_mean_shift, args->gamma_mean, args->a_mean, s,
-                                       nullptr, 1, COVO_RANK_RECORD_FLOATS)))
+                if ((rc = launch_merge(update_from_records(gathered, exchange_world(h), COVO_RANK_RECORD_FLOATS, args->a_mean_shift,
+                                                           args->gamma_mean, args->a_mean),
+                                       h->cfg.lam, s)))
                     return rc;
             }
         }

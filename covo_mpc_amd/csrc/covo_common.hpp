@@ -162,10 +162,9 @@ __device__ __forceinline__ float wave_sum(float v)
 // launch entry points implemented in the .hip files (host functions)
 int launch_randn(uint32_t k0, uint32_t k1, int64_t off, int n_samples, int n_cols, float *out, hipStream_t s);
 int launch_randn_jax(uint32_t k0, uint32_t k1, int64_t n_total, int64_t off, int n_samples, int mppi, float *out, hipStream_t s);
-// eps == null: epsilon is drawn in-kernel from (k0, k1, sample_offset + n) (rng_device.hpp)
-// cov != null (fused covo-online step): a_cov = cz sym(Z) is NOT written by the chain's finalize launch -- one workgroup that
-// everything after it waits for -- but by the first workgroups of the noise GEMM that follows (same expression, same bits);
-// launch_sigma_ns fills *cov with where Z, its transpose and the scalars live.
+// Host-side launch descriptors: one per kernel family, filled field by field; every field has a default and a null /
+// zero field means "off".  Kernel-argument structs (RolloutArgs, AdjArgs, ...) are built from them inside the launch functions.
+//
 // threads per workgroup the noise GEMM launches with for (N, batch) (noise_gemm.hip: 512 once a launch fills the chip, else 256);
 // the rollout's XCD-affine sample mapping follows it (rollout.hip: xcd_remap = 64-sample groups per GEMM workgroup)
 int noise_gemm_block_threads(int N, int batch);
@@ -177,23 +176,60 @@ struct CovDeferred {
     const double *zcoef, *u;     // deflated chain (sigma_ns.hip): Z = Z~ + zcoef u u^T (*zcoef == 0: off)
     float *out;                  // a_cov [128][128]; null: nothing deferred
 };
-int launch_noise_gemm(const float *L, const float *mu, const float *eps, uint32_t k0, uint32_t k1, int64_t sample_offset,
-                      int N, float *a, hipStream_t s, const uint32_t *dyn = nullptr, const float *state_for_time = nullptr,
-                      int n_table = 0, int batch = 1,  // batch > 1 (in-kernel Philox only): dense per-instance L, mu, dyn, a
-                      bool eps_tiled = false, const CovDeferred *cov = nullptr,        // eps is the tile-ordered image of eps_tiles.hpp
-                      bool propagate_nan = false);                                     // COVO_FLAG_PROPAGATE_NAN: jnp.clip's NaN semantics
-int launch_noise_blockdiag(const float *Ls, const float *mu, const float *eps, uint32_t k0, uint32_t k1,
-                           int64_t sample_offset, int N, float *a, hipStream_t s, const uint32_t *dyn = nullptr,
-                           bool propagate_nan = false);
+// a = clip(mu + L eps): launch_noise_gemm (dense L [128][128]) and launch_noise_blockdiag (MPPI's Ls [H][4][4]; it has no
+// eps_tiled / state_for_time / batch / cov)
+struct NoiseDesc {
+    const float *L = nullptr;
+    const float *mu = nullptr;
+    const float *eps = nullptr;        // [N][128] epsilon; null: drawn in-kernel from (key, sample_offset + n) (rng_device.hpp)
+    bool eps_tiled = false;            // eps is the tile-ordered image of eps_tiles.hpp
+    uint32_t key[2] = {0u, 0u};        // the in-kernel draw's key ...
+    const uint32_t *dyn = nullptr;     // ... or, non-null, where {key0, key1} lie in device memory
+    int64_t sample_offset = 0;         // global id of local sample 0 (in-kernel draw)
+    int N = 0;
+    float *a = nullptr;                // [H][N][4] action stripes
+    const float *state_for_time = nullptr;  // non-null: L is a table [n_table][128][128], row state.time is used (covo-offline)
+    int n_table = 0;
+    int batch = 1;                     // batch > 1 (in-kernel Philox or tiled eps only): dense per-instance L, mu, dyn, a
+    // cov != null (fused covo-online step): a_cov = cz sym(Z) is NOT written by the chain's finalize launch -- one workgroup that
+    // everything after it waits for -- but by the first workgroups of the noise GEMM that follows (same expression, same bits);
+    // launch_sigma_ns fills *cov with where Z, its transpose and the scalars live.
+    const CovDeferred *cov = nullptr;
+    bool propagate_nan = false;        // COVO_FLAG_PROPAGATE_NAN: jnp.clip's NaN semantics
+};
+int launch_noise_gemm(const NoiseDesc &d, hipStream_t s);
+int launch_noise_blockdiag(const NoiseDesc &d, hipStream_t s);
 static inline bool covo_propagate_nan(const covo_ctx *h) { return (h->cfg.flags & COVO_FLAG_PROPAGATE_NAN) != 0; }
-int launch_rollout(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
-                   const float *f_shared, const float *a, int N, float discount, bool trust_clipped, float *cost,
-                   float *groupmin, double *pos_stats, double *stats_ws, hipStream_t s, const float *f_shared_dev = nullptr,
-                   float *records = nullptr, float lam = 0.0f,   // records: one online-softmax record per workgroup (rollout.hip)
-                   const float *f_tab = nullptr,                 // [H][4] per-step disturbance table (disturb.hip), device
-                   int xcd_groups = 0,    // 64-sample groups per workgroup of the kernel that wrote `a` (0: the noise GEMM's for this N)
-                   bool propagate_nan = false,  // the re-clip of untrusted stripes keeps a NaN (COVO_FLAG_PROPAGATE_NAN)
-                   float *diag_rec = nullptr);  // with records: one diagnostic record per workgroup next to them (softmax_merge.hpp)
+// how the rollout treats the action stripes it reads (RolloutArgs::clip)
+enum RolloutClip {
+    ROLLOUT_CLIP_TRUSTED = 0,  // the producer guarantees clipped stripes
+    ROLLOUT_CLIP_REAPPLY = 1,  // re-apply step_env's clip (quadrotor.py:223,258)
+    ROLLOUT_CLIP_REAPPLY_NAN = 2,  // the same, and the re-clip keeps a NaN (COVO_FLAG_PROPAGATE_NAN)
+};
+// one rollout over N samples: launch_rollout, rollout_fill_args (instance `index` of an env-batched launch) and
+// fill_rollout_args (rollout_common.hpp: the RolloutArgs block itself; step_small.hip, plan_trace.hip)
+struct RolloutDesc {
+    const float *state = nullptr;
+    const float *pos_traj = nullptr, *vel_traj = nullptr;
+    int T = 0;
+    const covo_env_params *params = nullptr;
+    const float *f_shared = nullptr;      // host {fx, fy, fz}: the one shared disturbance vector of steps >= 1 (null: zero)
+    const float *f_shared_dev = nullptr;  // the same in device memory (graph replays), overrides f_shared
+    const float *f_tab = nullptr;         // [H][4] per-step disturbance table (disturb.hip), device
+    const float *a = nullptr;             // [H][N][4] action stripes
+    int N = 0;
+    float discount = 1.0f;
+    float *cost = nullptr;                // [N]
+    float *groupmin = nullptr;            // [ceil(N/64)] per-wave cost minima
+    double *pos_stats = nullptr;          // [H*6] position statistics (launch_rollout only), with their scratch ...
+    double *stats_ws = nullptr;           // ... [workgroups][H*6]
+    float *records = nullptr;             // one online-softmax record per workgroup (rollout.hip), at temperature ...
+    float lam = 0.0f;
+    float *diag_rec = nullptr;            // with records: one diagnostic record per workgroup next to them (softmax_merge.hpp)
+    int xcd_groups = 0;  // 64-sample groups per workgroup of the kernel that wrote `a` (0: the noise GEMM's for this N)
+    RolloutClip clip = ROLLOUT_CLIP_REAPPLY;
+};
+int launch_rollout(const RolloutDesc &d, hipStream_t s);
 int launch_disturb_table(const covo_env_params &p, const float *state, int batch, const uint32_t *keys_dev, uint32_t key0,
                          uint32_t key1, int key_mode, int deterministic, float *out, hipStream_t s);
 int launch_disturb_tables_step(const covo_env_params &p, const float *state, const uint32_t *dyn, int rollout_deterministic,
@@ -206,22 +242,41 @@ int launch_disturb_tables_batched(const void *models_dev, const float *states, c
                                   int rollout_deterministic, float *tab_rollout, float *tab_hess, hipStream_t s);
 int rollout_workgroups(int N, bool stats, int nbatch = 1);
 size_t rollout_args_bytes(int n);
-void rollout_fill_args(void *out, int index, const float *state, const float *pos_traj, const float *vel_traj, int T,
-                       const covo_env_params &p, const float *a, int N, float discount, float *cost, float *groupmin,
-                       const float *f_shared_dev, float *records = nullptr, float lam = 0.0f, bool trust_clipped = true,
-                       const float *f_tab = nullptr, float *diag_rec = nullptr);
+void rollout_fill_args(void *out, int index, const RolloutDesc &d);  // (no position statistics: pos_stats is not read)
 int launch_rollout_batched(const void *args_host, const void *args_dev, int nbatch, hipStream_t s);
-// a_mean_out != null: finish on this GPU (normalise + blend); else write the merged record to partial_out
-int launch_softmax_reduce(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
-                          float *partial_out, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                          hipStream_t s, float *partials_ws = nullptr, int batch = 1,  // batch > 1: dense per-instance slices, own partials_ws
-                          float *diag_rec = nullptr, float *diag_out = nullptr);  // diag_out: [batch][COVO_DIAG_FLOATS] (with a_mean_out), diag_rec: scratch [batch][blocks][4]
-// a_mean_out == null: the merged record goes to partial_out (sample-sharded step); batch > 1: dense per-instance slices
-int launch_merge(const float *partials, int G, float lam, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                 hipStream_t s, float *partial_out = nullptr, int batch = 1, int stride = COVO_PARTIAL_FLOATS,
-                 const float *diag_rec = nullptr, float *diag_out = nullptr, int n_samples = 0);  // diag_out: [batch][COVO_DIAG_FLOATS] from [batch][G][4]
+// The softmax update (covo.py:266-275; reduce.hip).  Stage 1 + merge from the costs: launch_softmax_reduce, and with MPPI's
+// covariance adaptation (mppi.py:109-125) launch_softmax_update_cov; the merge alone from records: launch_merge, launch_merge_cov.
+struct UpdateDesc {
+    // input, from the costs ...
+    const float *cost = nullptr;      // [batch][N]
+    const float *a = nullptr;         // [batch][H][N][4]
+    int N = 0;                        // samples (launch_merge: only the diagnostics' normalisation reads it)
+    const float *blockmin = nullptr;  // [n_blockmin] per-wave cost minima; null: formed first (h->ws_blockmin)
+    int n_blockmin = 0;
+    float *partials_ws = nullptr;     // stage-1 records [batch][blocks][COVO_PARTIAL_FLOATS]; null: h->ws_partials
+    // ... or from G records per instance, `stride` floats apart (launch_merge / launch_merge_cov)
+    const float *partials = nullptr;
+    int G = 0;
+    int stride = COVO_PARTIAL_FLOATS;
+    // the blend: a_mean_out != null finishes on this GPU (normalise + blend with a_mean_old)
+    const float *a_mean_old = nullptr;  // (the covariance kinds centre their second moments on it in every case)
+    float gamma_mean = 1.0f;
+    float *a_mean_out = nullptr;
+    // a_mean_out (a_cov_out for the covariance kinds) == null: a sample-sharded rank, the merged record goes here
+    float *partial_out = nullptr;
+    // MPPI's covariance adaptation
+    const float *a_cov_old = nullptr;
+    float gamma_sigma = 0.0f;
+    float *a_cov_out = nullptr;
+    int batch = 1;                    // batch > 1: dense per-instance slices, own partials_ws
+    // the sampling diagnostics, with a final update only
+    float *diag_rec = nullptr;        // stage-1 diagnostic records [batch][blocks or G][4] (scratch of launch_softmax_reduce, input of launch_merge)
+    float *diag_out = nullptr;        // [batch][COVO_DIAG_FLOATS]
+};
+int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
+int launch_merge(const UpdateDesc &d, float lam, hipStream_t s);
 // exchange.hip: the rank records of a sample-sharded step and their peer-write exchange
-int launch_rank_stats_sum(const float *records, int G, double *out, hipStream_t s, bool cov = false);
+int launch_rank_stats_sum(const float *records, int G, int record_floats, double *out, hipStream_t s);  // COVO_RANK_RECORD_[COV_]FLOATS
 int exchange_create(covo_ctx *h, int world, int rank, void *handle_out);
 int exchange_connect(covo_ctx *h, const void *handles);
 int exchange_set_timeout(covo_ctx *h, double seconds);
@@ -231,13 +286,10 @@ int exchange_world(const covo_ctx *h);
 int exchange_records(covo_ctx *h, const float *record, float *gathered_dst, const float **gathered_out, hipStream_t s,
                      int nfloats = COVO_RANK_RECORD_FLOATS);
 size_t softmax_cov_workspace_floats(int max_blocks);
-int launch_softmax_update_cov(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
-                              const float *a_mean_old, float gamma_mean, const float *a_cov_old, float gamma_sigma,
-                              float *a_mean_out, float *a_cov_out, hipStream_t s, float *diag_out = nullptr);
-int launch_softmax_reduce_cov(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
-                              const float *a_mean_old, float *record_out, hipStream_t s);
-int launch_merge_cov(const float *records, int G, int stride, float lam, const float *a_mean_old, float gamma_mean,
-                     const float *a_cov_old, float gamma_sigma, float *a_mean_out, float *a_cov_out, hipStream_t s);
+// a_cov_out == null: this rank's record {m, s, v[128], pad[2], S2[320]} (unnormalised) goes to partial_out -- the first
+// COVO_PARTIAL_FLOATS + 320 floats of a COVO_RANK_RECORD_COV_FLOATS rank record
+int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
+int launch_merge_cov(const UpdateDesc &d, float lam, hipStream_t s);
 int launch_shift_mean(const float *in, float *out, hipStream_t s);
 size_t hessian_workspace_bytes(int batch);
 struct SymStatsOut;  // sym_stats.hpp
@@ -251,41 +303,33 @@ struct HessBegin {
     int derive_keys;
     float shared_noise_scale;
 };
-int launch_hessian(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
-                   const float *a_mean, int batch, double *R, void *workspace, hipStream_t s, const void *consts_dev = nullptr,
-                   size_t traj_stride = 0,
-                   const SymStatsOut *stats = nullptr,   // KD also leaves the Sigma chain's input statistics (sym_stats.hpp)
-                   const float *f_tab = nullptr,         // [batch][H][4] per-step disturbance table (disturb.hip), device
-                   const void *models_dev = nullptr,     // dm::Model[batch] next to consts_dev (drag / mixed with per-instance parameters)
-                   int *status_dev = nullptr,            // the handle's sticky status word: COVO_DEVSTAT_ADJOINT on a costate time-out
-                   const HessBegin *begin = nullptr,     // batch 1: KB also does the step's begin work (a_mean = where the shifted mean goes)
-                   const DebugMasks &dbg = DebugMasks());
-// true: launch_hessian leaves R's Sigma-chain statistics when asked to (the adjoint kernels do, for every disturbance model;
-// launch_hessian_pairs does not)
-inline bool hessian_leaves_stats(const covo_env_params &p)
-{
-    (void)p;
-    return true;
-}
+// the Hessian of the cost in the mean: launch_hessian (second-order adjoint, hessian_adj.hip) and launch_hessian_pairs (hessian.hip;
+// it reads neither stats, status_dev nor begin)
+struct HessianDesc {
+    const float *state = nullptr;   // [batch][32]
+    const float *pos_traj = nullptr, *vel_traj = nullptr;
+    int T = 0;
+    const covo_env_params *params = nullptr;  // instance 0's (all instances share reward and disturbance kind)
+    const float *a_mean = nullptr;  // [batch][128]
+    int batch = 1;
+    double *R = nullptr;            // [batch][128][128]
+    const void *consts_dev = nullptr;   // qm::Consts<double>[batch]: per-instance constants (hessian_fill_consts), with ...
+    size_t traj_stride = 0;             // ... per-instance trajectories, this many floats apart
+    const SymStatsOut *stats = nullptr;  // KD also leaves the Sigma chain's input statistics (sym_stats.hpp)
+    const float *f_tab = nullptr;        // [batch][H][4] per-step disturbance table (disturb.hip), device
+    const void *models_dev = nullptr;    // dm::Model[batch] next to consts_dev (drag / mixed with per-instance parameters)
+    int *status_dev = nullptr;           // the handle's sticky status word: COVO_DEVSTAT_ADJOINT on a costate time-out
+    const HessBegin *begin = nullptr;    // batch 1: KB also does the step's begin work (a_mean = where the shifted mean goes)
+};
+int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const DebugMasks &dbg);
 size_t hessian_consts_bytes(int n);
 void hessian_fill_consts(const covo_env_params *params, int n, void *out);
 // the per-pair hyper-dual rollout version (hessian.hip): slower, independent derivation, kept as a cross-check
-int launch_hessian_pairs(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
-                         const float *a_mean, int batch, double *R, hipStream_t s, const float *f_tab = nullptr,
-                         const void *consts_dev = nullptr, size_t traj_stride = 0, const void *models_dev = nullptr);
+int launch_hessian_pairs(const HessianDesc &d, hipStream_t s);
 int launch_sigma(const double *R, int batch, float sample_sigma, float *Sigma, float *L, unsigned long long *prof,
                  hipStream_t s);
 size_t sigma_ns_workspace_bytes(int batch);
 struct EpsGenArgs;  // eps_tiles.hpp
-// gen != null (fused step): the finalize launch also draws the step's epsilon in tile order (eps_tiles.hpp)
-// status: the handle's sticky status word (a timed-out grid barrier raises COVO_DEVSTAT_GRID_BARRIER there, next to the NaN
-// outputs); persistent_ok = false (COVO_FLAG_SHARED_DEVICE): every phase its own launch
-// r_has_stats (fused steps): R is exactly symmetric and its statistics (sym_stats.hpp) are already in the workspace -- left
-// there by the Hessian's last launch through sigma_ns_stats_out -- so the chain starts without its prep launch
-// stream != null (fused covo-online step, one matrix, persistent launches allowed): the noise GEMM of the step is carried out INSIDE
-// the finalize launch, streamed under the factorisation (sigma_ns.hip: ns_finalize_stream_kernel); *streamed says whether it was
-// (else the caller launches the GEMM).  gen / cov / Sigma / L are then unused: a_cov goes to stream->a_cov_out, the factor to
-// stream->L_stream.
 struct StreamGemmArgs {
     const float *mu;        // the shifted mean [128]
     const uint32_t *dyn;    // {key0, key1}: the step's sampling key in device memory
@@ -298,11 +342,29 @@ struct StreamGemmArgs {
     float *a_cov_out;       // nullable: a_cov [128][128]
     int nanp;               // COVO_FLAG_PROPAGATE_NAN
 };
-int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sample_sigma, float *Sigma, float *L, void *workspace,
-                    hipStream_t s, const EpsGenArgs *gen = nullptr, int *status = nullptr, bool persistent_ok = true,
-                    CovDeferred *cov = nullptr, bool r_has_stats = false, const StreamGemmArgs *stream = nullptr,
-                    bool *streamed = nullptr, const DebugMasks &dbg = DebugMasks());
-struct SymStatsOut;  // sym_stats.hpp
+// Sigma = optimize_sigma(R) and its Cholesky factor without an eigendecomposition (sigma_ns.hip)
+struct SigmaNsDesc {
+    const double *R = nullptr;   // [batch][128][128]
+    int batch = 1;
+    float sample_sigma = 0.0f;
+    float *Sigma = nullptr;      // [batch][128][128] a_cov, nullable
+    float *L = nullptr;          // [batch][128][128] chol(Sigma)
+    const EpsGenArgs *gen = nullptr;  // fused step: the finalize launch also draws the step's epsilon in tile order (eps_tiles.hpp)
+    int *status = nullptr;       // the handle's sticky status word (a timed-out grid barrier raises COVO_DEVSTAT_GRID_BARRIER there,
+                                 // next to the NaN outputs)
+    bool persistent_ok = true;   // false (COVO_FLAG_SHARED_DEVICE): every phase its own launch
+    CovDeferred *cov = nullptr;  // out: a_cov is left to the consumer of L (NoiseDesc::cov)
+    // fused steps: R is exactly symmetric and its statistics (sym_stats.hpp) are already in the workspace -- left there by the
+    // Hessian's last launch through sigma_ns_stats_out -- so the chain starts without its prep launch
+    bool r_has_stats = false;
+    // fused covo-online step, one matrix, persistent launches allowed: the noise GEMM of the step is carried out INSIDE the finalize
+    // launch, streamed under the factorisation (sigma_ns.hip: ns_finalize_stream_kernel); *streamed (out) says whether it was (else
+    // the caller launches the GEMM).  gen / cov / Sigma / L are then unused: a_cov goes to stream->a_cov_out, the factor to
+    // stream->L_stream.
+    const StreamGemmArgs *stream = nullptr;
+    bool *streamed = nullptr;
+};
+int launch_sigma_ns(const CovoOpts &opt, const SigmaNsDesc &d, void *workspace, hipStream_t s, const DebugMasks &dbg);
 SymStatsOut sigma_ns_stats_out(void *workspace, int batch = 1);
 void step_state_destroy(covo_ctx *h);
 void step_graphs_drop(covo_ctx *h);  // every captured step graph of the handle goes; the next step runs eagerly, the one after captures

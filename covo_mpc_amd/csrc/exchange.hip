@@ -123,10 +123,10 @@ __global__ __launch_bounds__(256) void rank_stats_sum_kernel(const float *__rest
     out[i] = acc;
 }
 
-int launch_rank_stats_sum(const float *records, int G, double *out, hipStream_t s, bool cov)
+int launch_rank_stats_sum(const float *records, int G, int record_floats, double *out, hipStream_t s)
 {
-    hipLaunchKernelGGL(rank_stats_sum_kernel, dim3(1), dim3(256), 0, s, records, G, out,
-                       cov ? COVO_RANK_RECORD_COV_FLOATS : COVO_RANK_RECORD_FLOATS,
+    const bool cov = record_floats == COVO_RANK_RECORD_COV_FLOATS;
+    hipLaunchKernelGGL(rank_stats_sum_kernel, dim3(1), dim3(256), 0, s, records, G, out, record_floats,
                        cov ? COVO_PARTIAL_FLOATS + COVO_COV_FLOATS : COVO_PARTIAL_FLOATS);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;

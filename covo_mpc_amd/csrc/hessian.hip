@@ -168,33 +168,32 @@ __global__ __launch_bounds__(64) void hessian_kernel(const HessArgs A)
     }
 }
 
-int launch_hessian_pairs(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
-                   const float *a_mean, int batch, double *R, hipStream_t s, const float *f_tab, const void *consts_dev,
-                   size_t traj_stride, const void *models_dev)
+int launch_hessian_pairs(const HessianDesc &d, hipStream_t s)
 {
+    const covo_env_params &p = *d.params;
     const bool needs_tab = p.disturb_kind >= COVO_DISTURB_PERIODIC && p.disturb_kind <= COVO_DISTURB_MIXED;
-    if (needs_tab && f_tab == nullptr) {
+    if (needs_tab && d.f_tab == nullptr) {
         covo_set_error("hessian_pairs: disturb_kind=%d needs the per-step disturbance table (covo_disturb_table)", p.disturb_kind);
         return COVO_E_BADARG;
     }
     HessArgs A;
-    A.state = state;
-    A.pos_traj = pos_traj;
-    A.vel_traj = vel_traj;
-    A.a_mean = a_mean;
-    A.R = R;
-    A.T = T;
+    A.state = d.state;
+    A.pos_traj = d.pos_traj;
+    A.vel_traj = d.vel_traj;
+    A.a_mean = d.a_mean;
+    A.R = d.R;
+    A.T = d.T;
     A.c = make_consts<double>(p);
     const dm::Model m = dm::make_model(p);
-    A.f_tab = needs_tab ? reinterpret_cast<const float4 *>(f_tab) : nullptr;
+    A.f_tab = needs_tab ? reinterpret_cast<const float4 *>(d.f_tab) : nullptr;
     A.reward = p.reward_kind;
     A.drag_k = hs_drag_k(m);
     for (int i = 0; i < 3; ++i) A.drag_off[i] = 0.5 * (double)m.dp[i];
-    A.cs = reinterpret_cast<const qm::Consts<double> *>(consts_dev);
-    A.traj_stride = traj_stride;
-    A.models = reinterpret_cast<const dm::Model *>(models_dev);
-    COVO_CHECK_HIP(hipMemsetAsync(R, 0, (size_t)batch * COVO_NA * COVO_NA * sizeof(double), s));
-    hipLaunchKernelGGL(hessian_kernel, dim3(hs_total_waves(), batch), dim3(64), 0, s, A);
+    A.cs = reinterpret_cast<const qm::Consts<double> *>(d.consts_dev);
+    A.traj_stride = d.traj_stride;
+    A.models = reinterpret_cast<const dm::Model *>(d.models_dev);
+    COVO_CHECK_HIP(hipMemsetAsync(d.R, 0, (size_t)d.batch * COVO_NA * COVO_NA * sizeof(double), s));
+    hipLaunchKernelGGL(hessian_kernel, dim3(hs_total_waves(), d.batch), dim3(64), 0, s, A);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -96,11 +96,13 @@ namespace adj16 {
 constexpr size_t WS_COUNT_MAX = adj16::WS_COUNT > adj13::WS_COUNT ? adj16::WS_COUNT : adj13::WS_COUNT;
 size_t hessian_workspace_bytes(int batch) { return (size_t)batch * WS_COUNT_MAX * sizeof(double); }
 
-int launch_hessian(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
-                   const float *a_mean, int batch, double *R, void *workspace, hipStream_t s, const void *consts_dev,
-                   size_t traj_stride, const SymStatsOut *stats, const float *f_tab, const void *models_dev, int *status_dev,
-                   const HessBegin *begin, const DebugMasks &dbg)
+int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const DebugMasks &dbg)
 {
+    const covo_env_params &p = *d.params;
+    const float *f_tab = d.f_tab;
+    const void *consts_dev = d.consts_dev, *models_dev = d.models_dev;
+    const HessBegin *begin = d.begin;
+    const int batch = d.batch;
     const bool fs = p.disturb_kind == COVO_DISTURB_DRAG || p.disturb_kind == COVO_DISTURB_MIXED;
     if (fs && (consts_dev != nullptr) != (models_dev != nullptr)) {
         covo_set_error("hessian: drag / mixed disturbance with per-instance constants needs the per-instance models too");
@@ -121,11 +123,11 @@ int launch_hessian(const float *state, const float *pos_traj, const float *vel_t
     for (int i = 0; i < 3; ++i) A.drag_off[i] = 0.5 * (double)m.dp[i];
     A.models = reinterpret_cast<const dm::Model *>(models_dev);
     A.reward = p.reward_kind;
-    A.status = status_dev;
-    A.state = state;
-    A.pos_traj = pos_traj;
-    A.vel_traj = vel_traj;
-    A.a_mean = a_mean;
+    A.status = d.status_dev;
+    A.state = d.state;
+    A.pos_traj = d.pos_traj;
+    A.vel_traj = d.vel_traj;
+    A.a_mean = d.a_mean;
     A.a_mean_raw = nullptr;
     A.dyn_out = nullptr;
     A.seq = nullptr;
@@ -142,19 +144,19 @@ int launch_hessian(const float *state, const float *pos_traj, const float *vel_t
     }
     static const int scan_prefix = [] { const char *v = std::getenv("COVO_HESS_SCAN"); return v ? std::atoi(v) : 1; }();
     A.scan_prefix = scan_prefix;
-    A.R = R;
+    A.R = d.R;
     A.ws = reinterpret_cast<double *>(workspace);
-    A.T = T;
+    A.T = d.T;
     A.c = make_consts<double>(p);
     A.cs = reinterpret_cast<const qm::Consts<double> *>(consts_dev);
-    A.traj_stride = traj_stride;
+    A.traj_stride = d.traj_stride;
     A.stats.rpart = nullptr;
     A.stats.fpart = nullptr;
     A.stats.diag = nullptr;
     A.stats.stride = 0;
     A.stats.flags = nullptr;
     A.stats.ready = nullptr;
-    if (stats != nullptr) A.stats = *stats;
+    if (d.stats != nullptr) A.stats = *d.stats;
     // launch shapes: KB 32 waves; KC 9 chains + KM's 32 hyper-dual workgroups (which also contract with the costate); KD 36 tiles
     // batched: chains and hyper-dual workgroups as two launches (hessian_adj_body.hpp: adj_hd_kernel) -- 66.5 -> 62.5 us at 32 instances;
     // one instance keeps them in one launch (the hyper-dual workgroups start under the chains: 27.9 -> 25.7 us in round 3)

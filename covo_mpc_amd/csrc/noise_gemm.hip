@@ -327,15 +327,15 @@ int noise_gemm_groups_per_workgroup(int N, int batch)
     return noise_gemm_split(N, batch) ? 1 : noise_gemm_block_threads(N, batch) / 128;
 }
 
-int launch_noise_gemm(const float *L, const float *mu, const float *eps, uint32_t k0, uint32_t k1, int64_t sample_offset,
-                      int N, float *a, hipStream_t s, const uint32_t *dyn, const float *state_for_time, int n_table, int batch,
-                      bool eps_tiled, const CovDeferred *cov, bool propagate_nan)
+int launch_noise_gemm(const NoiseDesc &d, hipStream_t s)
 {
     CovDeferred cv;
     std::memset(&cv, 0, sizeof(cv));
-    if (cov != nullptr) cv = *cov;
+    if (d.cov != nullptr) cv = *d.cov;
+    const float *L = d.L, *mu = d.mu, *eps = d.eps, *state_for_time = d.state_for_time;
+    const int N = d.N, batch = d.batch, n_table = d.n_table;
     const int ntiles = (N + 31) / 32;
-    const int nanp = propagate_nan ? 1 : 0;
+    const int nanp = d.propagate_nan ? 1 : 0;
     const int block = noise_gemm_block_threads(N, batch);
     const bool split = noise_gemm_split(N, batch);
     const int waves_per_block = block / 64;
@@ -354,17 +354,17 @@ int launch_noise_gemm(const float *L, const float *mu, const float *eps, uint32_
     }
 #define NG_GO(...)                                                                                                             \
     do {                                                                                                                         \
-        if (eps != nullptr && eps_tiled)                                                                                         \
+        if (eps != nullptr && d.eps_tiled)                                                                                         \
             hipLaunchKernelGGL((noise_gemm_kernel<false, true, __VA_ARGS__>), dim3(grid, batch), dim3(block), lds, s, L, mu, eps, 0u, 0u, (int64_t)0, \
-                               N, ntiles, reinterpret_cast<float4 *>(a), (const uint32_t *)nullptr, state_for_time, n_table, cv, nanp); \
+                               N, ntiles, reinterpret_cast<float4 *>(d.a), (const uint32_t *)nullptr, state_for_time, n_table, cv, nanp); \
         else if (eps != nullptr)                                                                                                 \
             hipLaunchKernelGGL((noise_gemm_kernel<false, false, __VA_ARGS__>), dim3(grid), dim3(block), lds, s, L, mu, eps, 0u, 0u,          \
-                               (int64_t)0, N, ntiles, reinterpret_cast<float4 *>(a), (const uint32_t *)nullptr, state_for_time,  \
+                               (int64_t)0, N, ntiles, reinterpret_cast<float4 *>(d.a), (const uint32_t *)nullptr, state_for_time, \
                                n_table, cv, nanp);                                                                               \
         else                                                                                                                     \
             hipLaunchKernelGGL((noise_gemm_kernel<true, false, __VA_ARGS__>), dim3(grid, batch), dim3(block), lds, s, L, mu,                 \
-                               (const float *)nullptr, k0, k1, sample_offset, N, ntiles, reinterpret_cast<float4 *>(a), dyn,     \
-                               state_for_time, n_table, cv, nanp);                                                               \
+                               (const float *)nullptr, d.key[0], d.key[1], d.sample_offset, N, ntiles,                        \
+                               reinterpret_cast<float4 *>(d.a), d.dyn, state_for_time, n_table, cv, nanp);                       \
     } while (0)
     if (block == 512) NG_GO(512);
     else if (split) NG_GO(256, true);
@@ -374,19 +374,20 @@ int launch_noise_gemm(const float *L, const float *mu, const float *eps, uint32_
     return 0;
 }
 
-int launch_noise_blockdiag(const float *Ls, const float *mu, const float *eps, uint32_t k0, uint32_t k1,
-                           int64_t sample_offset, int N, float *a, hipStream_t s, const uint32_t *dyn, bool propagate_nan)
+int launch_noise_blockdiag(const NoiseDesc &d, hipStream_t s)
 {
-    const int nanp = propagate_nan ? 1 : 0;
+    const int N = d.N;
+    const int nanp = d.propagate_nan ? 1 : 0;
     const size_t total = (size_t)N * COVO_H;
     const int grid = (int)((total + 255) / 256);
-    if (eps != nullptr)
-        hipLaunchKernelGGL(noise_blockdiag_kernel<false>, dim3(grid), dim3(256), 0, s, Ls, mu,
-                           reinterpret_cast<const float4 *>(eps), 0u, 0u, (int64_t)0, N, reinterpret_cast<float4 *>(a),
+    if (d.eps != nullptr)
+        hipLaunchKernelGGL(noise_blockdiag_kernel<false>, dim3(grid), dim3(256), 0, s, d.L, d.mu,
+                           reinterpret_cast<const float4 *>(d.eps), 0u, 0u, (int64_t)0, N, reinterpret_cast<float4 *>(d.a),
                            (const uint32_t *)nullptr, nanp);
     else
-        hipLaunchKernelGGL(noise_blockdiag_kernel<true>, dim3((N + 255) / 256, COVO_H), dim3(256), 0, s, Ls, mu,
-                           (const float4 *)nullptr, k0, k1, sample_offset, N, reinterpret_cast<float4 *>(a), dyn, nanp);
+        hipLaunchKernelGGL(noise_blockdiag_kernel<true>, dim3((N + 255) / 256, COVO_H), dim3(256), 0, s, d.L, d.mu,
+                           (const float4 *)nullptr, d.key[0], d.key[1], d.sample_offset, N, reinterpret_cast<float4 *>(d.a), d.dyn,
+                           nanp);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -161,9 +161,18 @@ void plan_state_destroy(covo_ctx *h)
 static void fill_plan_args(PlanArgs &P, covo_ctx *h, const PlanInstDesc &d, int e, const float *states_true)
 {
     std::memset(&P, 0, sizeof(P));
-    fill_rollout_args(P.R, d.state, d.pos_traj, d.vel_traj, d.T, *d.params, nullptr, nullptr, 1, h->cfg.discount, nullptr, nullptr,
-                      nullptr, nullptr, d.f_tab, 1);  // (the kernel sets A.cost)
-    P.R.clip = 0;  // the image is clipped in phase 0
+    RolloutDesc ro;  // one sample; the kernel sets A.cost and leaves no records
+    ro.state = d.state;
+    ro.pos_traj = d.pos_traj;
+    ro.vel_traj = d.vel_traj;
+    ro.T = d.T;
+    ro.params = d.params;
+    ro.f_tab = d.f_tab;
+    ro.N = 1;
+    ro.discount = h->cfg.discount;
+    ro.xcd_groups = 1;
+    ro.clip = ROLLOUT_CLIP_TRUSTED;  // the image is clipped in phase 0
+    fill_rollout_args(P.R, ro, 1);
     P.R.xcd_remap = 0;
     P.a_mean = d.a_mean;
     P.key_mem = d.key_mem;

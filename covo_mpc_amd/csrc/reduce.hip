@@ -394,112 +394,102 @@ __global__ void shift_mean_kernel(const float *__restrict__ in, float *__restric
     out[i] = (i < COVO_NA - COVO_DU) ? in[i + COVO_DU] : in[i];
 }
 
-int launch_softmax_reduce(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
-                          float *partial_out, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                          hipStream_t s, float *partials_ws, int batch, float *diag_rec, float *diag_out)
+// stage 1's launch shape and cost minima, shared by the two entry points below: d's own minima, or formed over the costs first
+struct Stage1 {
+    const float *blockmin;
+    int n_blockmin, grid;
+};
+static Stage1 update_stage1(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
+{
+    Stage1 st{d.blockmin, d.n_blockmin, ((d.N + 63) / 64 + RD_WAVES - 1) / RD_WAVES};
+    if (st.blockmin == nullptr) {
+        st.n_blockmin = (d.N + 63) / 64;
+        hipLaunchKernelGGL(groupmin_kernel, dim3((d.N + 255) / 256), dim3(256), 0, s, d.cost, d.N, h->ws_blockmin);
+        st.blockmin = h->ws_blockmin;
+    }
+    if (st.grid > h->max_red_blocks) st.grid = h->max_red_blocks;
+    return st;
+}
+
+int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
 {
     const float inv_lam = 1.0f / h->cfg.lam;
-    if (partials_ws == nullptr) partials_ws = h->ws_partials;
-    if (blockmin == nullptr) {
-        n_blockmin = (N + 63) / 64;
-        hipLaunchKernelGGL(groupmin_kernel, dim3((N + 255) / 256), dim3(256), 0, s, cost, N, h->ws_blockmin);
-        blockmin = h->ws_blockmin;
-    }
-    const int ngroups = (N + 63) / 64;
-    int grid = (ngroups + RD_WAVES - 1) / RD_WAVES;
-    if (grid > h->max_red_blocks) grid = h->max_red_blocks;
-    if (diag_out != nullptr && a_mean_out != nullptr) {  // the same two launches in their diagnostic variants
-        hipLaunchKernelGGL(softmax_partial_diag_kernel<false>, dim3(grid, batch), dim3(RD_BLOCK), 0, s, cost,
-                           reinterpret_cast<const float4 *>(a), N, blockmin, n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr,
-                           diag_rec);
-        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(batch), dim3(MG_THREADS), 0, s, partials_ws, grid, inv_lam, a_mean_old,
-                           gamma_mean, a_mean_out, COVO_PARTIAL_FLOATS, (const float *)diag_rec, diag_out, (float)N);
+    float *partials_ws = d.partials_ws ? d.partials_ws : h->ws_partials;
+    const Stage1 st = update_stage1(h, d, s);
+    const float4 *a4 = reinterpret_cast<const float4 *>(d.a);
+    if (d.diag_out != nullptr && d.a_mean_out != nullptr) {  // the same two launches in their diagnostic variants
+        hipLaunchKernelGGL(softmax_partial_diag_kernel<false>, dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
+                           st.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr, d.diag_rec);
+        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam, d.a_mean_old,
+                           d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, (const float *)d.diag_rec, d.diag_out, (float)d.N);
         COVO_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    hipLaunchKernelGGL(softmax_partial_kernel<false>, dim3(grid, batch), dim3(RD_BLOCK), 0, s, cost,
-                       reinterpret_cast<const float4 *>(a), N, blockmin, n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr);
-    if (a_mean_out != nullptr)
-        hipLaunchKernelGGL(merge_kernel<true>, dim3(batch), dim3(MG_THREADS), 0, s, partials_ws, grid, inv_lam, a_mean_old,
-                           gamma_mean, a_mean_out, COVO_PARTIAL_FLOATS);
+    hipLaunchKernelGGL(softmax_partial_kernel<false>, dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
+                       st.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr);
+    if (d.a_mean_out != nullptr)
+        hipLaunchKernelGGL(merge_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam, d.a_mean_old,
+                           d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS);
     else
-        hipLaunchKernelGGL(merge_kernel<false>, dim3(batch), dim3(MG_THREADS), 0, s, partials_ws, grid, inv_lam,
-                           (const float *)nullptr, 1.0f, partial_out, COVO_PARTIAL_FLOATS);
+        hipLaunchKernelGGL(merge_kernel<false>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam,
+                           (const float *)nullptr, 1.0f, d.partial_out, COVO_PARTIAL_FLOATS);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
 // MPPI's update with covariance adaptation (mppi.py:109-125): stage 1 with second moments, then merge_cov_kernel; single shard
+// (one instance, the handle's own ws_partials_cov / ws_diag_rec: d.batch, d.partials_ws and d.diag_rec are not read)
 size_t softmax_cov_workspace_floats(int max_blocks) { return (size_t)max_blocks * RD_COV_RECORD_FLOATS; }
-int launch_softmax_update_cov(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
-                              const float *a_mean_old, float gamma_mean, const float *a_cov_old, float gamma_sigma,
-                              float *a_mean_out, float *a_cov_out, hipStream_t s, float *diag_out)
+int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
 {
     const float inv_lam = 1.0f / h->cfg.lam;
-    const bool diag = diag_out != nullptr && a_cov_out != nullptr;
-    if (blockmin == nullptr) {
-        n_blockmin = (N + 63) / 64;
-        hipLaunchKernelGGL(groupmin_kernel, dim3((N + 255) / 256), dim3(256), 0, s, cost, N, h->ws_blockmin);
-        blockmin = h->ws_blockmin;
-    }
-    const int ngroups = (N + 63) / 64;
-    int grid = (ngroups + RD_WAVES - 1) / RD_WAVES;
-    if (grid > h->max_red_blocks) grid = h->max_red_blocks;
+    const bool diag = d.diag_out != nullptr && d.a_cov_out != nullptr;
+    const Stage1 st = update_stage1(h, d, s);
+    const float4 *a4 = reinterpret_cast<const float4 *>(d.a), *mean4 = reinterpret_cast<const float4 *>(d.a_mean_old);
     if (diag)
-        hipLaunchKernelGGL(softmax_partial_diag_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, cost,
-                           reinterpret_cast<const float4 *>(a), N, blockmin, n_blockmin, inv_lam, h->ws_partials_cov,
-                           reinterpret_cast<const float4 *>(a_mean_old), h->ws_diag_rec);
+        hipLaunchKernelGGL(softmax_partial_diag_kernel<true>, dim3(st.grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
+                           st.n_blockmin, inv_lam, h->ws_partials_cov, mean4, h->ws_diag_rec);
     else
-        hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, cost, reinterpret_cast<const float4 *>(a), N,
-                           blockmin, n_blockmin, inv_lam, h->ws_partials_cov, reinterpret_cast<const float4 *>(a_mean_old));
+        hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(st.grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
+                           st.n_blockmin, inv_lam, h->ws_partials_cov, mean4);
     // the covariance merge below has its own body: the diagnostics come from one more merge launch over the same headers {m_g, s_g}
     // (its merged record goes to the idle ws_partials), off the path of a step without diagnostics
     if (diag)
-        hipLaunchKernelGGL(merge_diag_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam,
-                           (const float *)nullptr, 1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, diag_out,
-                           (float)N);
-    if (a_cov_out != nullptr)
-        hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam, a_mean_old,
-                           gamma_mean, a_cov_old, gamma_sigma, a_mean_out, a_cov_out, RD_COV_RECORD_FLOATS);
-    else  // a sample-sharded rank: a_mean_out = this rank's record {m, s, v, pad, S2} (launch_softmax_reduce_cov)
-        hipLaunchKernelGGL(merge_cov_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam, a_mean_old,
-                           1.0f, (const float *)nullptr, 0.0f, a_mean_out, (float *)nullptr, RD_COV_RECORD_FLOATS);
+        hipLaunchKernelGGL(merge_diag_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam,
+                           (const float *)nullptr, 1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, d.diag_out,
+                           (float)d.N);
+    if (d.a_cov_out != nullptr)
+        hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam, d.a_mean_old,
+                           d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS);
+    else  // a sample-sharded rank: its record {m, s, v, pad, S2}, unnormalised and unblended
+        hipLaunchKernelGGL(merge_cov_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam, d.a_mean_old,
+                           1.0f, (const float *)nullptr, 0.0f, d.partial_out, (float *)nullptr, RD_COV_RECORD_FLOATS);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
-}
-
-// stage 1 with second moments + local merge -> this rank's record {m, s, v[128], pad[2], S2[320]} (unnormalised): the first
-// COVO_PARTIAL_FLOATS + 320 floats of a COVO_RANK_RECORD_COV_FLOATS rank record
-int launch_softmax_reduce_cov(covo_ctx *h, const float *cost, const float *a, int N, const float *blockmin, int n_blockmin,
-                              const float *a_mean_old, float *record_out, hipStream_t s)
-{
-    return launch_softmax_update_cov(h, cost, a, N, blockmin, n_blockmin, a_mean_old, 1.0f, nullptr, 0.0f, record_out, nullptr, s);
 }
 
 // the G all-gathered rank records (stride floats apart) -> new mean and adapted covariances, identically on every rank
-int launch_merge_cov(const float *records, int G, int stride, float lam, const float *a_mean_old, float gamma_mean,
-                     const float *a_cov_old, float gamma_sigma, float *a_mean_out, float *a_cov_out, hipStream_t s)
+int launch_merge_cov(const UpdateDesc &d, float lam, hipStream_t s)
 {
-    if (G > MG_MAXG) { covo_set_error("covo_merge_ranks_cov: G=%d > %d", G, MG_MAXG); return COVO_E_BADARG; }
-    hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, records, G, 1.0f / lam, a_mean_old, gamma_mean,
-                       a_cov_old, gamma_sigma, a_mean_out, a_cov_out, stride);
+    if (d.G > MG_MAXG) { covo_set_error("covo_merge_ranks_cov: G=%d > %d", d.G, MG_MAXG); return COVO_E_BADARG; }
+    hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam, d.a_mean_old, d.gamma_mean,
+                       d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, d.stride);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }
 
-int launch_merge(const float *partials, int G, float lam, const float *a_mean_old, float gamma_mean, float *a_mean_out,
-                 hipStream_t s, float *partial_out, int batch, int stride, const float *diag_rec, float *diag_out, int n_samples)
+int launch_merge(const UpdateDesc &d, float lam, hipStream_t s)
 {
-    if (G > MG_MAXG) { covo_set_error("covo_merge: G=%d > %d", G, MG_MAXG); return COVO_E_BADARG; }
-    if (a_mean_out != nullptr && diag_out != nullptr)
-        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(batch), dim3(MG_THREADS), 0, s, partials, G, 1.0f / lam, a_mean_old, gamma_mean,
-                           a_mean_out, stride, diag_rec, diag_out, (float)n_samples);
-    else if (a_mean_out != nullptr)
-        hipLaunchKernelGGL(merge_kernel<true>, dim3(batch), dim3(MG_THREADS), 0, s, partials, G, 1.0f / lam, a_mean_old, gamma_mean,
-                           a_mean_out, stride);
+    if (d.G > MG_MAXG) { covo_set_error("covo_merge: G=%d > %d", d.G, MG_MAXG); return COVO_E_BADARG; }
+    if (d.a_mean_out != nullptr && d.diag_out != nullptr)
+        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam, d.a_mean_old,
+                           d.gamma_mean, d.a_mean_out, d.stride, (const float *)d.diag_rec, d.diag_out, (float)d.N);
+    else if (d.a_mean_out != nullptr)
+        hipLaunchKernelGGL(merge_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam, d.a_mean_old,
+                           d.gamma_mean, d.a_mean_out, d.stride);
     else
-        hipLaunchKernelGGL(merge_kernel<false>, dim3(batch), dim3(MG_THREADS), 0, s, partials, G, 1.0f / lam,
-                           (const float *)nullptr, 1.0f, partial_out, stride);
+        hipLaunchKernelGGL(merge_kernel<false>, dim3(d.batch), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam,
+                           (const float *)nullptr, 1.0f, d.partial_out, d.stride);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -46,39 +46,38 @@ static void launch_rollout_pf(const RolloutArgs &A, const RolloutArgs *batch, in
 }
 #endif
 
-void fill_rollout_args(RolloutArgs &A, const float *state, const float *pos_traj, const float *vel_traj, int T,
-                       const covo_env_params &p, const float *f_shared, const float *a, int N, float discount,
-                       float *cost, float *groupmin, double *stats_ws, const float *f_shared_dev, const float *f_tab,
-                       int xcd_groups, int nbatch)
+void fill_rollout_args(RolloutArgs &A, const RolloutDesc &d, int nbatch)
 {
-    if (xcd_groups <= 0) xcd_groups = noise_gemm_groups_per_workgroup(N, nbatch);  // the producer is the noise GEMM unless told otherwise
-    A.state = state;
-    A.pos_traj = pos_traj;
-    A.vel_traj = vel_traj;
-    A.a = reinterpret_cast<const float4 *>(a);
-    A.cost = cost;
-    A.groupmin = groupmin;
-    A.stats_ws = stats_ws;
+    const covo_env_params &p = *d.params;
+    const int N = d.N;
+    const int xcd_groups = d.xcd_groups > 0 ? d.xcd_groups : noise_gemm_groups_per_workgroup(N, nbatch);  // the producer is the noise GEMM unless told otherwise
+    A.state = d.state;
+    A.pos_traj = d.pos_traj;
+    A.vel_traj = d.vel_traj;
+    A.a = reinterpret_cast<const float4 *>(d.a);
+    A.cost = d.cost;
+    A.groupmin = d.groupmin;
+    A.stats_ws = d.stats_ws;
     A.N = N;
-    A.T = T;
+    A.T = d.T;
     A.max_steps = p.max_steps_in_episode;
-    A.discount = discount;
-    for (int i = 0; i < 3; ++i) A.f_shared[i] = f_shared ? f_shared[i] : 0.0f;
-    A.f_shared_dev = f_shared_dev;
+    A.discount = d.discount;
+    for (int i = 0; i < 3; ++i) A.f_shared[i] = d.f_shared ? d.f_shared[i] : 0.0f;
+    A.f_shared_dev = d.f_shared_dev;
     // the producers run one 32-sample tile per wave up to N = 65 536: workgroup g of the noise GEMM (noise_gemm_block_threads / 128
     // groups of 64 samples; MPPI's block-diagonal kernel: 256 samples = 4 groups per workgroup row) sits on XCD g % 8, and the
     // rollout's workgroups take the groups their own XCD's L2 has just been written with (a mismatch costs MPPI's rollout 11 us)
     A.xcd_remap = (N % 2048 == 0 && N / 128 <= 512) ? xcd_groups : 0;
-    A.records = nullptr;
-    A.inv_lam = 0.0f;
+    A.records = d.records;
+    A.inv_lam = d.records ? 1.0f / d.lam : 0.0f;
     A.merge_ticket = nullptr;  // (step_small.hip sets these for its own launch)
     A.merge_out = nullptr;
     A.merge_mean_old = nullptr;
     A.merge_gamma = 1.0f;
     A.merge_final = 0;
-    A.diag_rec = nullptr;
+    A.diag_rec = d.records ? d.diag_rec : nullptr;
     A.diag_out = nullptr;
-    A.clip = 1;
+    A.clip = d.clip;
     A.rollover = p.rollover_terminate != 0;
     A.reward = p.reward_kind;
     // which disturbance variant (rollout_pipe.hpp): none / gaussian -> one shared vector; periodic / sin -> the per-step
@@ -86,7 +85,7 @@ void fill_rollout_args(RolloutArgs &A, const float *state, const float *pos_traj
     const dm::Model m = dm::make_model(p);
     A.fdist = (m.kind == COVO_DISTURB_PERIODIC || m.kind == COVO_DISTURB_SIN) ? 1
               : (m.kind == COVO_DISTURB_DRAG || m.kind == COVO_DISTURB_MIXED) ? 2 : 0;
-    A.f_tab = reinterpret_cast<const float4 *>(f_tab);
+    A.f_tab = reinterpret_cast<const float4 *>(d.f_tab);
     A.drag_k = dm::drag_coeff(m);
     for (int i = 0; i < 3; ++i) A.drag_off[i] = 0.5f * m.dp[i];
     A.c = make_consts<float>(p);
@@ -120,15 +119,12 @@ static int dispatch_rollout(const RolloutArgs &A, const RolloutArgs *batch, int 
     return 0;
 }
 
-int launch_rollout(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params &p,
-                   const float *f_shared, const float *a, int N, float discount, bool trust_clipped, float *cost,
-                   float *groupmin, double *pos_stats, double *stats_ws, hipStream_t s, const float *f_shared_dev,
-                   float *records, float lam, const float *f_tab, int xcd_groups, bool propagate_nan, float *diag_rec)
+int launch_rollout(const RolloutDesc &d, hipStream_t s)
 {
+    const covo_env_params &p = *d.params;
     RolloutArgs A;
-    fill_rollout_args(A, state, pos_traj, vel_traj, T, p, f_shared, a, N, discount, cost, groupmin, stats_ws, f_shared_dev, f_tab,
-                      xcd_groups);
-    if (A.fdist != 0 && f_tab == nullptr) {
+    fill_rollout_args(A, d, 1);
+    if (A.fdist != 0 && d.f_tab == nullptr) {
         covo_set_error("rollout: disturb_kind=%d needs the per-step disturbance table (covo_disturb_table)", p.disturb_kind);
         return COVO_E_BADARG;
     }
@@ -136,11 +132,7 @@ int launch_rollout(const float *state, const float *pos_traj, const float *vel_t
         covo_set_error("rollout: reward_kind=%d", p.reward_kind);
         return COVO_E_BADARG;
     }
-    A.clip = trust_clipped ? 0 : (propagate_nan ? 2 : 1);
-    A.records = records;
-    A.inv_lam = records ? 1.0f / lam : 0.0f;
-    A.diag_rec = records ? diag_rec : nullptr;
-    return dispatch_rollout<false>(A, nullptr, 0, pos_stats, s);
+    return dispatch_rollout<false>(A, nullptr, 0, d.pos_stats, s);
 }
 
 // workgroups (= softmax records, rollout_record) a rollout over N samples (x nbatch instances) is launched with, per
@@ -155,17 +147,11 @@ int rollout_workgroups(int N, bool stats, int nbatch)
 // ---- env-batched rollout: one launch, workgroup row y = instance y (step.hip: covo_mpc_step_batched)
 size_t rollout_args_bytes(int n) { return (size_t)n * sizeof(RolloutArgs); }
 
-void rollout_fill_args(void *out, int index, const float *state, const float *pos_traj, const float *vel_traj, int T,
-                       const covo_env_params &p, const float *a, int N, float discount, float *cost, float *groupmin,
-                       const float *f_shared_dev, float *records, float lam, bool trust_clipped, const float *f_tab, float *diag_rec)
+// d.f_tab: this instance's rows of the step's disturbance tables (periodic / sin / drag / mixed; all instances share the kind).
+// The XCD-affine mapping is chosen as for a launch of two instances, whatever their count (speed only, never correctness)
+void rollout_fill_args(void *out, int index, const RolloutDesc &d)
 {
-    RolloutArgs &A = reinterpret_cast<RolloutArgs *>(out)[index];
-    // f_tab: this instance's rows of the step's disturbance tables (periodic / sin / drag / mixed; all instances share the kind)
-    fill_rollout_args(A, state, pos_traj, vel_traj, T, p, nullptr, a, N, discount, cost, groupmin, nullptr, f_shared_dev, f_tab, 0, 2);
-    A.clip = trust_clipped ? 0 : 1;
-    A.records = records;
-    A.inv_lam = records ? 1.0f / lam : 0.0f;
-    A.diag_rec = records ? diag_rec : nullptr;
+    fill_rollout_args(reinterpret_cast<RolloutArgs *>(out)[index], d, 2);
 }
 
 // every instance must share instance 0's N, discount, clip, rollover, reward and disturbance kind (checked by the caller)

@@ -43,13 +43,11 @@ struct RolloutArgs {
     float *diag_out;  // the fused small step: where the last workgroup's merge writes the COVO_DIAG_FLOATS of this instance
 };
 
-// rollout.hip: the argument block of one rollout over N samples (the producer of the stripes is the noise GEMM unless
-// xcd_groups says otherwise); records / clip are set by the caller
-void fill_rollout_args(RolloutArgs &A, const float *state, const float *pos_traj, const float *vel_traj, int T,
-                       const covo_env_params &p, const float *f_shared, const float *a, int N, float discount, float *cost,
-                       float *groupmin, double *stats_ws, const float *f_shared_dev, const float *f_tab, int xcd_groups = 0,
-                       int nbatch = 1);
+static_assert(sizeof(RolloutArgs) == 256, "RolloutArgs is a kernel argument and the element of the batched launches' device arrays");
 
+// rollout.hip: the argument block of one rollout over N samples, instance of a launch of nbatch (the producer of the stripes is
+// the noise GEMM unless d.xcd_groups says otherwise); the merge_* fields and diag_out are left off (step_small.hip sets them)
+void fill_rollout_args(RolloutArgs &A, const RolloutDesc &d, int nbatch);
 
 // scripts/probe/rollout_probe.hip compiles this file with ROLLOUT_PROBE: every workgroup leaves {XCC, HW_ID, start, end}
 // (s_memrealtime, 100 MHz) -- where the dispatcher put it and when it ran.  Compiled out of the library.

@@ -2292,12 +2292,16 @@ static void ns_launch_iters(hipStream_t s, const NsBufs &B, double *sc, int i_en
 //              -> finalize (with log det B)
 // sigma_stages (covo_debug_time_step) cuts each plan short: 1 the squarings, 2 + the scan launch, 3 + the Newton-Schulz iterations,
 // 4 + finalize; below 3 one matrix takes the two-launch plan.
-int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sample_sigma, float *Sigma, float *L, void *workspace,
-                    hipStream_t s, const EpsGenArgs *gen, int *status, bool persistent_ok, CovDeferred *cov, bool r_has_stats,
-                    const StreamGemmArgs *stream, bool *streamed, const DebugMasks &dbg)
+int launch_sigma_ns(const CovoOpts &opt, const SigmaNsDesc &d, void *workspace, hipStream_t s, const DebugMasks &dbg)
 {
+    const double *R = d.R;
+    const int batch = d.batch;
+    const float sample_sigma = d.sample_sigma;
+    float *Sigma = d.Sigma;  // (null below once a_cov is left to the consumer of L)
+    CovDeferred *cov = d.cov;
+    const StreamGemmArgs *stream = d.stream;
     const int sigma_stages = dbg.sigma_stages;
-    if (streamed != nullptr) *streamed = false;
+    if (d.streamed != nullptr) *d.streamed = false;
     double *ws = reinterpret_cast<double *>(workspace);
     const size_t M = (size_t)batch * SN * SN;
     double *A = ws;
@@ -2318,7 +2322,7 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
         COVO_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(ns_finalize_stream_kernel),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     }
-    if (r_has_stats) A = const_cast<double *>(R);  // exactly symmetric, statistics already in sc (KD): no prep launch
+    if (d.r_has_stats) A = const_cast<double *>(R);  // exactly symmetric, statistics already in sc (KD): no prep launch
     else hipLaunchKernelGGL(ns_prep_kernel, ns_grid(NS_TILES, batch), dim3(256), 0, s, R, A, sc, batch);
     // T, T^T of the iterations: the first two matrices of the filter's history -- a squaring launch with the evaluations inside keeps
     // no history, and the phased plan's scan launch has finished with it -- so no squaring writes them while an iteration runs
@@ -2334,9 +2338,9 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
     B.A = A;
     B.X1 = ns_xk(xb, 1);
     enum { MERGED, TWO_LAUNCH, BATCHED, PHASED } plan;
-    if (!persistent_ok) plan = PHASED;
+    if (!d.persistent_ok) plan = PHASED;
     else if (batch > 1) plan = BATCHED;
-    else if (opt.ns_merged && r_has_stats && sigma_stages >= 3) plan = MERGED;  // (SC_READY and the flag words cleared by KD)
+    else if (opt.ns_merged && d.r_has_stats && sigma_stages >= 3) plan = MERGED;  // (SC_READY and the flag words cleared by KD)
     else plan = TWO_LAUNCH;
     switch (plan) {
     case MERGED:
@@ -2387,9 +2391,9 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
         const int workers = (ntiles - 8 + 7) / 8;
         if (ntiles >= 72 && workers <= 255) {
             hipLaunchKernelGGL(ns_finalize_stream_kernel, dim3(1 + workers), dim3(512), lds, s, Z[0], Z[1], Zt[0], Zt[1], sc, sample_sigma,
-                               *stream, status);
+                               *stream, d.status);
             COVO_CHECK_HIP(hipGetLastError());
-            if (streamed != nullptr) *streamed = true;
+            if (d.streamed != nullptr) *d.streamed = true;
             return 0;
         }
     }
@@ -2402,8 +2406,8 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
     g.dyn_stride = 0;
     g.eps_stride = 0;
     int passengers = 0;
-    if (gen != nullptr && gen->eps_tiled != nullptr) {
-        g = *gen;
+    if (d.gen != nullptr && d.gen->eps_tiled != nullptr) {
+        g = *d.gen;
         const long long ntiles = (long long)((g.N + 31) / 32) * g.n_inst;
         passengers = (int)((ntiles + 7) / 8);  // 8 waves per workgroup, one tile per wave ...
         const int nfac = early_logdet ? batch : 2 * batch;  // factoring workgroups (Z, and B where its log det is not there yet)
@@ -2426,7 +2430,7 @@ int launch_sigma_ns(const CovoOpts &opt, const double *R, int batch, float sampl
         }
     }
     hipLaunchKernelGGL(ns_finalize_kernel, dim3((early_logdet ? batch : 2 * batch) + passengers), dim3(512), lds, s, Z[0], Z[1], Zt[0],
-                       Zt[1], sc, sample_sigma, Sigma, L, batch, g, status, A, early_logdet ? 0 : 1);
+                       Zt[1], sc, sample_sigma, Sigma, d.L, batch, g, d.status, A, early_logdet ? 0 : 1);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

@@ -221,13 +221,31 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     const bool tables = covo_needs_tables(p);
     if (tables && (rc = launch_disturb_tables_step(p, state, st->dyn, a.rollout_deterministic, st->f_tab_rollout,
                                                    a.mode == COVO_MODE_COVO_ONLINE ? st->f_tab_hess : nullptr, s))) return rc;
+    // a = clip(am_shift + L eps): what the three modes' noise launches share (epsilon drawn in-kernel from the step's key in st->dyn)
+    NoiseDesc nd;
+    nd.mu = am_shift;
+    nd.dyn = st->dyn;
+    nd.sample_offset = a.sample_offset;
+    nd.N = N;
+    nd.a = a.a;
+    nd.propagate_nan = covo_propagate_nan(h);
     if (a.mode == COVO_MODE_COVO_ONLINE) {
         // the Hessian's last launch leaves the Sigma chain's input statistics in the chain's workspace: no prep launch
-        const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15 && hessian_leaves_stats(p);
+        const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15;
         const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma);
-        if ((M & 2) && (rc = launch_hessian(state, a.pos_traj, a.vel_traj, a.T, p, am_shift, 1, st->R, h->ws_hess, s, nullptr, 0,
-                                            stats ? &so : nullptr, tables ? st->f_tab_hess : nullptr, nullptr, h->status_dev, begin, dbg)))
-            return rc;  // :134-185
+        HessianDesc hd;
+        hd.state = state;
+        hd.pos_traj = a.pos_traj;
+        hd.vel_traj = a.vel_traj;
+        hd.T = a.T;
+        hd.params = &p;
+        hd.a_mean = am_shift;
+        hd.R = st->R;
+        hd.stats = stats ? &so : nullptr;
+        hd.f_tab = tables ? st->f_tab_hess : nullptr;
+        hd.status_dev = h->status_dev;
+        hd.begin = begin;
+        if ((M & 2) && (rc = launch_hessian(hd, h->ws_hess, s, dbg))) return rc;  // :134-185
         float *Sig = a.a_cov ? a.a_cov : st->Sigma;
         // epsilon needs only the act key: it is drawn under the chain's single-workgroup finalize launch, the GEMM loads it
         const bool ahead = st->eps_tiled != nullptr && (M & 4) && dbg.sigma_stages >= 4;
@@ -256,27 +274,33 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
         sg.nanp = covo_propagate_nan(h) ? 1 : 0;
         const bool want_stream = h->opt.stream_gemm && (M & 4) && (M & 8) && dbg.sigma_stages >= 4;
         bool streamed = false;
-        if ((M & 4) && (rc = launch_sigma_ns(h->opt, st->R, 1, a.sample_sigma, Sig, st->L, h->ws_sigma, s, &gen, h->status_dev,
-                                             (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0, defer ? &cov : nullptr, stats,
-                                             want_stream ? &sg : nullptr, &streamed, dbg))) return rc;
-        if (streamed) {
-        } else if (ahead) {
-            if ((M & 8) && (rc = launch_noise_gemm(st->L, am_shift, reinterpret_cast<const float *>(st->eps_tiled), 0, 0,
-                                                   a.sample_offset, N, a.a, s, nullptr, nullptr, 0, 1, true, &cov, covo_propagate_nan(h))))
-                return rc;
-        } else if ((M & 8) && (rc = launch_noise_gemm(st->L, am_shift, nullptr, 0, 0, a.sample_offset, N, a.a, s, st->dyn, nullptr, 0,
-                                                      1, false, &cov, covo_propagate_nan(h))))
-            return rc;
+        SigmaNsDesc sd;
+        sd.R = st->R;
+        sd.sample_sigma = a.sample_sigma;
+        sd.Sigma = Sig;
+        sd.L = st->L;
+        sd.gen = &gen;
+        sd.status = h->status_dev;
+        sd.persistent_ok = (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0;
+        sd.cov = defer ? &cov : nullptr;
+        sd.r_has_stats = stats;
+        sd.stream = want_stream ? &sg : nullptr;
+        sd.streamed = &streamed;
+        if ((M & 4) && (rc = launch_sigma_ns(h->opt, sd, h->ws_sigma, s, dbg))) return rc;
+        nd.L = st->L;
+        nd.eps = ahead ? reinterpret_cast<const float *>(st->eps_tiled) : nullptr;  // (else the GEMM draws from st->dyn)
+        nd.eps_tiled = ahead;
+        nd.cov = &cov;
+        if (!streamed && (M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
     } else if (a.mode == COVO_MODE_COVO_OFFLINE) {
-        if ((M & 8) && (rc = launch_noise_gemm(a.L_table, am_shift, nullptr, 0, 0, a.sample_offset, N, a.a, s, st->dyn, state,
-                                    a.n_table, 1, false, nullptr, covo_propagate_nan(h))))
-            return rc;
+        nd.L = a.L_table;
+        nd.state_for_time = state;
+        nd.n_table = a.n_table;
+        if ((M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
     } else {  // MPPI: shift a_cov, factor the 4x4 blocks, per-step draws (mppi.py:43-66)
-        // (a_cov was shifted and factored into st->Ls by the begin launch)
-        if ((rc = launch_noise_blockdiag(st->Ls, am_shift, nullptr, 0, 0, a.sample_offset, N, a.a, s, st->dyn, covo_propagate_nan(h))))
-            return rc;
+        nd.L = st->Ls;  // (a_cov was shifted and factored there by the begin launch)
+        if ((rc = launch_noise_blockdiag(nd, s))) return rc;
     }
-    const bool clipped = true;  // a comes straight from the noise kernels above
     // the rollout's workgroups leave the softmax update's stage-1 records themselves when they fit the merge (rollout.hip:
     // rollout_record); otherwise the stand-alone stage-1 kernel runs over the costs
     const int G = rollout_workgroups(N, a.pos_stats != nullptr);
@@ -285,28 +309,53 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     const bool records = G <= h->max_red_blocks && !cov_adapt;
     // the step's sampling diagnostics (covo_set_step_diag): the diagnostic variants of the same launches; a sharded step has none
     float *dg = a.partial_out == nullptr ? covo_diag_target(h) : nullptr;
-    if ((M & 16) && (rc = launch_rollout(state, a.pos_traj, a.vel_traj, a.T, p, nullptr, a.a, N, h->cfg.discount, clipped, a.cost,
-                                         records ? nullptr : a.groupmin, a.pos_stats, h->ws_stats, s, fdev,
-                                         records ? h->ws_partials : nullptr, h->cfg.lam, tables ? st->f_tab_rollout : nullptr,
-                                         a.mode == COVO_MODE_MPPI ? 4 : 0, false,  // MPPI's block-diagonal kernel: 256 samples per workgroup
-                                         (records && dg) ? h->ws_diag_rec : nullptr)))
-        return rc;
+    RolloutDesc ro;
+    ro.state = state;
+    ro.pos_traj = a.pos_traj;
+    ro.vel_traj = a.vel_traj;
+    ro.T = a.T;
+    ro.params = &p;
+    ro.f_shared_dev = fdev;
+    ro.f_tab = tables ? st->f_tab_rollout : nullptr;
+    ro.a = a.a;
+    ro.N = N;
+    ro.discount = h->cfg.discount;
+    ro.cost = a.cost;
+    ro.groupmin = records ? nullptr : a.groupmin;
+    ro.pos_stats = a.pos_stats;
+    ro.stats_ws = h->ws_stats;
+    ro.records = records ? h->ws_partials : nullptr;
+    ro.lam = h->cfg.lam;
+    ro.diag_rec = (records && dg) ? h->ws_diag_rec : nullptr;
+    ro.xcd_groups = a.mode == COVO_MODE_MPPI ? 4 : 0;  // MPPI's block-diagonal kernel: 256 samples per workgroup
+    ro.clip = ROLLOUT_CLIP_TRUSTED;                    // a comes straight from the noise kernels above
+    if ((M & 16) && (rc = launch_rollout(ro, s))) return rc;
     if (!(M & 32)) return 0;
-    if (cov_adapt && a.partial_out != nullptr)  // a sample-sharded rank: its record with the second moments (836-float kind)
-        return launch_softmax_reduce_cov(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, am_shift, a.partial_out, s);
-    if (cov_adapt)  // mppi.py:109-125: new mean, then a_cov (already shifted by the begin launch) adapted in place
-        return launch_softmax_update_cov(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, am_shift, a.gamma_mean, a.a_cov, a.gamma_sigma,
-                                         a.a_mean, a.a_cov, s, dg);
-    if (records) {
-        if (a.partial_out != nullptr) return launch_merge(h->ws_partials, G, h->cfg.lam, nullptr, 1.0f, nullptr, s, a.partial_out);
-        return launch_merge(h->ws_partials, G, h->cfg.lam, am_shift, a.gamma_mean, a.a_mean, s, nullptr, 1, COVO_PARTIAL_FLOATS,
-                            h->ws_diag_rec, dg, N);
+    // weights + update: finish locally (blend with am_shift, diagnostics), or -- a sample-sharded rank -- leave this shard's
+    // record for the all-gather (covo.py:266-275)
+    UpdateDesc up;
+    up.cost = a.cost;
+    up.a = a.a;
+    up.N = N;
+    up.blockmin = a.groupmin;
+    up.n_blockmin = (N + 63) / 64;
+    up.partials = h->ws_partials;  // (the rollout's records, if it left them)
+    up.G = G;
+    const bool sharded = a.partial_out != nullptr;
+    up.a_mean_old = am_shift;
+    up.gamma_mean = a.gamma_mean;
+    up.a_mean_out = sharded ? nullptr : a.a_mean;
+    up.partial_out = a.partial_out;
+    up.diag_rec = h->ws_diag_rec;
+    up.diag_out = dg;
+    if (cov_adapt) {  // mppi.py:109-125: new mean, then a_cov (already shifted by the begin launch) adapted in place; a sharded
+                      // rank: its record with the second moments (836-float kind)
+        up.a_cov_old = a.a_cov;
+        up.gamma_sigma = a.gamma_sigma;
+        up.a_cov_out = sharded ? nullptr : a.a_cov;
+        return launch_softmax_update_cov(h, up, s);
     }
-    // weights + update: finish locally, or leave this shard's record for the all-gather (covo.py:266-275)
-    if (a.partial_out != nullptr)
-        return launch_softmax_reduce(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, a.partial_out, nullptr, 1.0f, nullptr, s);
-    return launch_softmax_reduce(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, nullptr, am_shift, a.gamma_mean,
-                                 a.a_mean, s, nullptr, 1, h->ws_diag_rec, dg);
+    return records ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
 }
 
 // a debug setter since the last step changed what a captured graph baked in (launch set, deflation switch, diagnostics target)
@@ -689,12 +738,24 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     if ((M & 1) && b->tables && (rc = launch_disturb_tables_batched(b->models, a.states, b->dyn, E, 1, b->tab_rollout, b->tab_hess, s)))
         return rc;
     // as in the single step: the Hessian's last launch leaves every instance's Sigma-chain input statistics, no prep launch
-    const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15 && hessian_leaves_stats(b->params[0]);
+    const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15;
     const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma, E);
-    if ((M & 2) && (rc = launch_hessian(a.states, a.pos_traj, a.vel_traj, a.T, b->params[0], b->a_mean_shift, E, b->R, h->ws_hess, s,
-                                        b->consts, (size_t)a.T * 3, stats ? &so : nullptr, b->tables ? b->tab_hess : nullptr, b->models,
-                                        h->status_dev, nullptr, dbg)))
-        return rc;
+    HessianDesc hd;
+    hd.state = a.states;
+    hd.pos_traj = a.pos_traj;
+    hd.vel_traj = a.vel_traj;
+    hd.T = a.T;
+    hd.params = &b->params[0];
+    hd.a_mean = b->a_mean_shift;
+    hd.batch = E;
+    hd.R = b->R;
+    hd.consts_dev = b->consts;
+    hd.traj_stride = (size_t)a.T * 3;
+    hd.stats = stats ? &so : nullptr;
+    hd.f_tab = b->tables ? b->tab_hess : nullptr;
+    hd.models_dev = b->models;
+    hd.status_dev = h->status_dev;
+    if ((M & 2) && (rc = launch_hessian(hd, h->ws_hess, s, dbg))) return rc;
     float *Sig = a.a_cov ? a.a_cov : b->Sigma;
     // epsilon needs only the act keys: every instance's is drawn under the chain's finalize launch (32 of 256 CUs factor), the GEMM
     // loads it -- the in-kernel Philox costs the batched GEMM ~9 us, its matrix pipe hides no vector work
@@ -707,24 +768,48 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     gen.n_inst = E;
     gen.dyn_stride = 12;
     gen.eps_stride = (size_t)((N + 31) / 32) * 16 * 64;
-    if ((M & 4) && (rc = launch_sigma_ns(h->opt, b->R, E, a.sample_sigma, Sig, b->L, h->ws_sigma, s, &gen, h->status_dev,
-                                         (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0, nullptr, stats, nullptr, nullptr, dbg))) return rc;
-    if (ahead) {
-        if ((rc = launch_noise_gemm(b->L, b->a_mean_shift, reinterpret_cast<const float *>(b->eps_tiled), 0, 0, 0, N, a.a, s, nullptr,
-                                    nullptr, 0, E, true, nullptr, covo_propagate_nan(h))))
-            return rc;
-    } else if ((M & 8) && (rc = launch_noise_gemm(b->L, b->a_mean_shift, nullptr, 0, 0, 0, N, a.a, s, b->dyn, nullptr, 0, E, false,
-                                                  nullptr, covo_propagate_nan(h))))
-        return rc;
+    SigmaNsDesc sd;
+    sd.R = b->R;
+    sd.batch = E;
+    sd.sample_sigma = a.sample_sigma;
+    sd.Sigma = Sig;
+    sd.L = b->L;
+    sd.gen = &gen;
+    sd.status = h->status_dev;
+    sd.persistent_ok = (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0;
+    sd.r_has_stats = stats;
+    if ((M & 4) && (rc = launch_sigma_ns(h->opt, sd, h->ws_sigma, s, dbg))) return rc;
+    NoiseDesc nd;
+    nd.L = b->L;
+    nd.mu = b->a_mean_shift;
+    nd.eps = ahead ? reinterpret_cast<const float *>(b->eps_tiled) : nullptr;  // (else the GEMM draws from b->dyn)
+    nd.eps_tiled = ahead;
+    nd.dyn = b->dyn;
+    nd.N = N;
+    nd.a = a.a;
+    nd.batch = E;
+    nd.propagate_nan = covo_propagate_nan(h);
+    if ((M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
     if ((M & 16) && (rc = launch_rollout_batched(b->ro_args_host.data(), b->ro_args, E, s))) return rc;
     if (!(M & 32)) return 0;
     const int G = rollout_workgroups(N, false, E);
-    float *dg = covo_diag_target(h);  // row e of the caller's diagnostic buffer is instance e's
-    if (G <= h->max_red_blocks)  // the rollout's workgroups have left the records (rollout_record): instance e's are [e][G]
-        return launch_merge(b->partials, G, h->cfg.lam, b->a_mean_shift, a.gamma_mean, a.a_mean, s, nullptr, E, COVO_PARTIAL_FLOATS,
-                            b->diag_rec, dg, N);
-    return launch_softmax_reduce(h, a.cost, a.a, N, a.groupmin, (N + 63) / 64, nullptr, b->a_mean_shift, a.gamma_mean, a.a_mean, s,
-                                 b->partials, E, b->diag_rec, dg);
+    UpdateDesc up;
+    up.cost = a.cost;
+    up.a = a.a;
+    up.N = N;
+    up.blockmin = a.groupmin;
+    up.n_blockmin = (N + 63) / 64;
+    up.partials_ws = b->partials;
+    up.partials = b->partials;
+    up.G = G;
+    up.a_mean_old = b->a_mean_shift;
+    up.gamma_mean = a.gamma_mean;
+    up.a_mean_out = a.a_mean;
+    up.batch = E;
+    up.diag_rec = b->diag_rec;
+    up.diag_out = covo_diag_target(h);  // row e of the caller's diagnostic buffer is instance e's
+    // the rollout's workgroups have left the records when they fit the merge (rollout_record): instance e's are [e][G]
+    return G <= h->max_red_blocks ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
 }
 
 // profiling aid (bench.py --config envs): `reps` copies of the selected launch groups of the LAST covo_mpc_step_batched call in
@@ -786,11 +871,24 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         const bool brec = bG <= h->max_red_blocks;
         for (int e = 0; e < E; ++e) {
             const BatchInst i = batch_inst(*args, e);
-            rollout_fill_args(b->ro_args_host.data(), e, i.state, i.pos_traj, i.vel_traj, args->T, params[e], i.a, N, h->cfg.discount,
-                              i.cost, brec ? nullptr : i.groupmin, reinterpret_cast<const float *>(b->dyn + 12 * e + 2),
-                              brec ? b->partials + (size_t)e * bG * COVO_PARTIAL_FLOATS : nullptr, h->cfg.lam, true,
-                              b->tables ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr,
-                              (brec && covo_diag_target(h)) ? b->diag_rec + (size_t)e * bG * 4 : nullptr);
+            RolloutDesc ro;
+            ro.state = i.state;
+            ro.pos_traj = i.pos_traj;
+            ro.vel_traj = i.vel_traj;
+            ro.T = args->T;
+            ro.params = &params[e];
+            ro.f_shared_dev = reinterpret_cast<const float *>(b->dyn + 12 * e + 2);
+            ro.f_tab = b->tables ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
+            ro.a = i.a;
+            ro.N = N;
+            ro.discount = h->cfg.discount;
+            ro.cost = i.cost;
+            ro.groupmin = brec ? nullptr : i.groupmin;
+            ro.records = brec ? b->partials + (size_t)e * bG * COVO_PARTIAL_FLOATS : nullptr;
+            ro.lam = h->cfg.lam;
+            ro.diag_rec = (brec && covo_diag_target(h)) ? b->diag_rec + (size_t)e * bG * 4 : nullptr;
+            ro.clip = ROLLOUT_CLIP_TRUSTED;  // a comes straight from the noise GEMM
+            rollout_fill_args(b->ro_args_host.data(), e, ro);
         }
         COVO_CHECK_HIP(hipMemcpy(b->ro_args, b->ro_args_host.data(), b->ro_args_host.size(), hipMemcpyHostToDevice));
         {

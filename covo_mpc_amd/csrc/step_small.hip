@@ -295,17 +295,26 @@ static void fill_small_args(SmallStepArgs &P, covo_ctx *h, const covo_env_params
                             unsigned *ticket, float *records, float *diag_rec, float *diag_out)
 {
     std::memset(&P, 0, sizeof(P));
-    const int N = a.n_samples;
-    fill_rollout_args(P.R, state, a.pos_traj, a.vel_traj, a.T, p, nullptr, a.a, N, h->cfg.discount, a.cost, nullptr, nullptr, nullptr,
-                      nullptr, a.mode == COVO_MODE_MPPI ? 4 : 0);
-    P.R.clip = 0;  // the stripes come straight from this launch's own clipped draw
-    P.R.records = records;
-    P.R.inv_lam = 1.0f / h->cfg.lam;
+    RolloutDesc ro;
+    ro.state = state;
+    ro.pos_traj = a.pos_traj;
+    ro.vel_traj = a.vel_traj;
+    ro.T = a.T;
+    ro.params = &p;
+    ro.a = a.a;
+    ro.N = a.n_samples;
+    ro.discount = h->cfg.discount;
+    ro.cost = a.cost;
+    ro.records = records;
+    ro.lam = h->cfg.lam;
+    ro.diag_rec = diag_out ? diag_rec : nullptr;
+    ro.xcd_groups = a.mode == COVO_MODE_MPPI ? 4 : 0;
+    ro.clip = ROLLOUT_CLIP_TRUSTED;  // the stripes come straight from this launch's own clipped draw
+    fill_rollout_args(P.R, ro, 1);
     P.R.merge_ticket = ticket;
     P.R.merge_final = a.partial_out == nullptr;
     P.R.merge_out = a.partial_out ? a.partial_out : a.a_mean;
     P.R.merge_gamma = a.gamma_mean;
-    P.R.diag_rec = diag_out ? diag_rec : nullptr;
     P.R.diag_out = diag_out;
     P.a_mean_in = a.a_mean_in ? a.a_mean_in : a.a_mean;
     P.a_mean_shift_out = a_mean_shift;

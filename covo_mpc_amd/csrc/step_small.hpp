@@ -34,6 +34,5 @@ const char *step_small_refusal(const covo_ctx *h, const covo_env_params &p, cons
 // caller's diagnostic buffer (diag_out null: diagnostics off).  The device copy of the array is the launch's `args_dev`.
 size_t step_small_args_bytes(int n);
 void step_small_fill_args(covo_ctx *h, void *out, int index, const covo_env_params &p, const covo_step_args &a, const uint32_t *raw_key_mem,
-                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec = nullptr,
-                          float *diag_out = nullptr);
+                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec, float *diag_out);
 int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s);

@@ -37,13 +37,25 @@ int main(int argc, char **argv)
     hipLaunchKernelGGL(gen_kernel, dim3(512), dim3(256), 0, 0, G);
     hipDeviceSynchronize();
     hipEvent_t e0, e1;
+    const hipStream_t stream = nullptr;  // the events below are recorded on the null stream too
     hipEventCreate(&e0); hipEventCreate(&e1);
     for (int variant = 0; variant < 2; ++variant) {
+        NoiseDesc nd;
+        nd.L = dL;
+        nd.mu = dmu;
+        nd.N = N;
+        nd.a = da;
+        if (variant == 0) {
+            nd.key[0] = 123u;
+            nd.key[1] = 456u;
+        } else {
+            nd.eps = reinterpret_cast<const float *>(deps);
+            nd.eps_tiled = true;
+        }
         float best = 1e9f;
         for (int it = 0; it < 6; ++it) {
             hipEventRecord(e0);
-            if (variant == 0) launch_noise_gemm(dL, dmu, nullptr, 123u, 456u, 0, N, da, 0);
-            else launch_noise_gemm(dL, dmu, reinterpret_cast<const float *>(deps), 0, 0, 0, N, da, 0, nullptr, nullptr, 0, 1, true);
+            launch_noise_gemm(nd, stream);
             hipEventRecord(e1);
             hipDeviceSynchronize();
             float ms; hipEventElapsedTime(&ms, e0, e1);

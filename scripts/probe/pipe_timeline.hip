@@ -39,8 +39,18 @@ int main(int argc, char **argv)
     hipMalloc(&dtl, (size_t)nwg * 3 * 8 * 8);
     hipMemset(dtl, 0, (size_t)nwg * 3 * 8 * 8);
     hipMemcpyToSymbol(HIP_SYMBOL(g_rp_tl), &dtl, sizeof(dtl));
+    RolloutDesc rd;
+    rd.state = dst;
+    rd.pos_traj = dpt;
+    rd.vel_traj = dvt;
+    rd.T = T;
+    rd.params = &prm;
+    rd.a = da;
+    rd.N = N;
+    rd.cost = dc;
+    rd.groupmin = dg;
     RolloutArgs A;
-    fill_rollout_args(A, dst, dpt, dvt, T, prm, nullptr, da, N, 1.0f, dc, dg, nullptr, nullptr);
+    fill_rollout_args(A, rd, 1);
     for (int it = 0; it < 4; ++it) hipLaunchKernelGGL((rollout_pipe3_kernel<true, false, TL_CH, 1>), dim3(nwg), dim3(192), 0, 0, A, nullptr);
     hipDeviceSynchronize();
     std::vector<unsigned long long> tl((size_t)nwg * 3 * 8);

@@ -104,11 +104,22 @@ int main(int argc, char **argv)
         hipMalloc(&da, a.size() * 4); hipMalloc(&dc, (size_t)N * 4); hipMalloc(&dc2, (size_t)N * 4);
         hipMalloc(&dg, (size_t)(N / 64 + 1) * 4);
         hipMemcpy(da, a.data(), a.size() * 4, hipMemcpyHostToDevice);
+        RolloutDesc rd;
+        rd.state = dst;
+        rd.pos_traj = dpt;
+        rd.vel_traj = dvt;
+        rd.T = T;
+        rd.params = &prm;
+        rd.f_shared = fsh;
+        rd.a = da;
+        rd.N = N;
+        rd.cost = dc;
+        rd.groupmin = dg;
+        rd.clip = ROLLOUT_CLIP_TRUSTED;
         RolloutArgs A;
-        fill_rollout_args(A, dst, dpt, dvt, T, prm, fsh, da, N, 1.0f, dc, dg, nullptr, nullptr, nullptr);
+        fill_rollout_args(A, rd, 1);
         RolloutArgs A2 = A;
         A2.cost = dc2;
-        A.clip = A2.clip = 0;
         const int grid = (N + RO_BLOCK - 1) / RO_BLOCK;
         std::vector<float> ref(N), out(N);
         auto report = [&](const char *name, const std::function<void()> &fn, bool check) {
