@@ -170,20 +170,41 @@ template <int MI, int MJ>
 struct TileBlock {
     double a[MI][8], b[MJ][8];
 };
-// issue the operand loads of this wave's K-quarter (callers issue them BEFORE looking at any flag: every launch of the chain then
-// pays one memory latency, not one per dependent scalar).  Left and right tiles alternate: the launched 2 x 2 Y'Z' keeps 5 waves per SIMD.
+// issue the operand loads of this wave's K-quarter.  Callers issue them BEFORE looking at any flag: every launch of the chain then
+// pays one memory latency, not one per dependent scalar -- and they ASK for their flags and scalars before calling this: loads
+// return in issue order, so a scalar asked for behind the operands is there only when all of them are, and the check on it would
+// hold the first MFMA back until the last operand has landed.
+// TILE-MAJOR order: the loads go out in the order block_mma_reduce consumes them -- tile 0's operands first (in two K-halves:
+// a[0][0..3], b[0][0..3], a[0][4..7], b[0][4..7]), then what every later tile t = MJ ia + ib adds (a[ia] when ib == 0, b[ib] when
+// ia == 0; 2 x 2: b[1], then a[1]).  The chain of tile t then waits with a counted s_waitcnt vmcnt(n) for ITS operands only (hipcc
+// places those waits by itself, from the registers each MFMA reads: checked in the ISA) and runs under the loads of the tiles behind
+// it.  (The k-major order this replaces had a[0][7] and b[0][7] among the last loads: load latency and MFMA time added up.)
+template <int COH, class F>
+__device__ __forceinline__ void tile_col_load(double (&o)[8], const double *M, int col, int kq, int hi, int kk0, int kk1, F f)
+{
+#pragma unroll
+    for (int kk = kk0; kk < kk1; ++kk) {
+        const int k = 32 * kq + 4 * kk + hi;
+        o[kk] = f(gld<COH>(M + (size_t)k * SN + col), k, col);
+    }
+}
 template <int COH, int MI, int MJ, class F>
 __device__ __forceinline__ void block_load(TileBlock<MI, MJ> &o, const double *At, const double *B, int bi, int bj, int lane, int kq, F f)
 {
     const int lo = lane & 15, hi = lane >> 4;
+    const int ca = 16 * MI * bi + lo, cb = 16 * MJ * bj + lo;
 #pragma unroll
-    for (int kk = 0; kk < 8; ++kk) {
-        const int k = 32 * kq + 4 * kk + hi;
+    for (int half = 0; half < 2; ++half) {
+        tile_col_load<COH>(o.a[0], At, ca, kq, hi, 4 * half, 4 * half + 4, f);
+        tile_col_load<COH>(o.b[0], B, cb, kq, hi, 4 * half, 4 * half + 4, f);
+        __builtin_amdgcn_sched_barrier(0);  // (plain loads -- COH_NONE -- are hipcc's to reorder: it went back to k-major)
+    }
 #pragma unroll
-        for (int h = 0; h < (MI > MJ ? MI : MJ); ++h) {
-            if (h < MI) o.a[h][kk] = f(gld<COH>(At + (size_t)k * SN + 16 * MI * bi + 16 * h + lo), k, 16 * MI * bi + 16 * h + lo);
-            if (h < MJ) o.b[h][kk] = f(gld<COH>(B + (size_t)k * SN + 16 * MJ * bj + 16 * h + lo), k, 16 * MJ * bj + 16 * h + lo);
-        }
+    for (int t = 1; t < MI * MJ; ++t) {
+        const int ia = t / MJ, ib = t % MJ;
+        if (ib == 0) tile_col_load<COH>(o.a[ia], At, ca + 16 * ia, kq, hi, 0, 8, f);
+        if (ia == 0) tile_col_load<COH>(o.b[ib], B, cb + 16 * ib, kq, hi, 0, 8, f);
+        __builtin_amdgcn_sched_barrier(0);
     }
 }
 // tile t = MJ ia + ib of the block: this wave's element (row (lane >> 4) + 4 wv, col lane & 15) of it in v[t], summed over the four
@@ -200,6 +221,9 @@ __device__ __forceinline__ void block_mma_reduce(const TileBlock<MI, MJ> &o, dou
         for (int kk = 0; kk < 8; ++kk) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(o.a[t / MJ][kk], o.b[t % MJ][kk], acc, 0, 0, 0);
 #pragma unroll
         for (int r = 0; r < 4; ++r) red[t][wv][r][lane] = acc[r];
+        // one chain after the other, in the order their operands land (interleaved, every tile's chain waits for the last tile's
+        // operands, and four live accumulators cost the launched 2 x 2 kernel its fifth wave per SIMD)
+        __builtin_amdgcn_sched_barrier(0);
     }
     __syncthreads();
 #pragma unroll
@@ -390,6 +414,14 @@ __device__ __forceinline__ bool ns_square_pair_body(const double *X, double *O, 
     }
     if (!FIRST && ns_batch_done<COH>(s, SC_SQ_DONE)) return false;
     TileBlock<MI, 1> ops;
+    // (the norm partials and t_in are asked for ahead of the operands -- see block_load -- and looked at behind them)
+    double done = 0.0, p1 = 0.0, p0 = 0.0;
+    if (!FIRST) {
+        done = (COH == COH_NONE) ? gld<COH>(s + SC_SQ_DONE) : 0.0;
+        p1 = (lane < NS_TILES) ? gld<COH>(s + SC_SQN + step * 64 + lane) : 0.0;
+        p0 = (lane < NS_TILES && step >= 2) ? gld<COH>(s + SC_SQN + (step - 1) * 64 + lane) : 0.0;
+        t_in = gld<COH>(s + SC_SQN + step * 64 + 63);
+    }
     // (the operands of A are asked for BEFORE the statistics that make Y0 = alpha I - beta A out of them: the chain's first round
     // trip -- A comes from memory, the Hessian's launches wrote it from other XCDs -- runs under the statistics' two barriers)
     block_load<COH>(ops, X, X, m, tj, lane, wv, LoadPlain{});
@@ -406,10 +438,6 @@ __device__ __forceinline__ bool ns_square_pair_body(const double *X, double *O, 
         }
     }
     if (!FIRST) {
-        const double done = (COH == COH_NONE) ? gld<COH>(s + SC_SQ_DONE) : 0.0;
-        const double p1 = (lane < NS_TILES) ? gld<COH>(s + SC_SQN + step * 64 + lane) : 0.0;
-        const double p0 = (lane < NS_TILES && step >= 2) ? gld<COH>(s + SC_SQN + (step - 1) * 64 + lane) : 0.0;
-        t_in = gld<COH>(s + SC_SQN + step * 64 + 63);
         if (done != 0.0) return false;
         nrm = wr::wave64_allsum(p1);
         if (step >= 2 && t_in > NS_SQ_TGUARD) {
@@ -1098,14 +1126,24 @@ __device__ __forceinline__ void ns_coef_table(double *s)
     }
 }
 
+// the convergence test of a phase in two halves: ns_converged_ask issues its two loads (before the phase's operand loads:
+// block_load), ns_converged looks at them (behind the operand loads' issue, before the first MFMA)
+struct NsConvAsk {
+    double done, e;
+};
 template <int COH>
-__device__ __forceinline__ bool ns_converged(double *s, int iter, int lane, bool writer)
+__device__ __forceinline__ NsConvAsk ns_converged_ask(const double *s, int iter, int lane)
 {
-    // both loads are issued before either is looked at
-    const double done = gld<COH>(s + SC_NS_DONE);
-    const double e = (iter >= 2) ? gld<COH>(s + SC_ERR + (iter - 1) * 64 + lane) : 0.0;
-    if (done != 0.0) return true;
-    if (iter >= 2 && wr::wave64_allsum(e) < NS_TOL2) {
+    NsConvAsk c;
+    c.done = gld<COH>(s + SC_NS_DONE);
+    c.e = (iter >= 2) ? gld<COH>(s + SC_ERR + (iter - 1) * 64 + lane) : 0.0;
+    return c;
+}
+template <int COH>
+__device__ __forceinline__ bool ns_converged(const NsConvAsk c, double *s, int iter, bool writer)
+{
+    if (c.done != 0.0) return true;
+    if (iter >= 2 && wr::wave64_allsum(c.e) < NS_TOL2) {
         if (writer) gst<COH>(s + SC_NS_DONE, 1.0);
         return true;
     }
@@ -1155,10 +1193,11 @@ __device__ __forceinline__ bool ns_T_block_body(const double *Y, const double *Z
     const int bi = w / NJ, bj = w % NJ;
     if (ns_batch_done<COH>(s, SC_NS_DONE)) return false;
     TileBlock<MI, MJ> ops;
-    block_load<COH>(ops, Zt, Y, bi, bj, lane, wv, LoadPlain{});  // (Z^T)^T . Y = Z.Y
+    const NsConvAsk conv = ns_converged_ask<COH>(s, iter, lane);
     // (the table: ns_first_elem_kernel's extra workgroup, or a workgroup of the one-matrix persistent launch)
     const double a = gld<COH>(s + SC_COEF + 2 * iter), bq = gld<COH>(s + SC_COEF + 2 * iter + 1);
-    if (ns_converged<COH>(s, iter, lane, w == 0 && tid == 0)) return false;  // Y, Z are final
+    block_load<COH>(ops, Zt, Y, bi, bj, lane, wv, LoadPlain{});  // (Z^T)^T . Y = Z.Y
+    if (ns_converged<COH>(conv, s, iter, w == 0 && tid == 0)) return false;  // Y, Z are final
     double v[MI * MJ];
     block_mma_reduce(ops, red, wv, lane, v);
 #pragma unroll
@@ -1195,8 +1234,9 @@ __device__ __forceinline__ bool ns_YZ_block_body(const double *Yt, const double 
     if (ns_batch_done<COH>(s, SC_NS_DONE)) return false;
     TileBlock<MI, MJ> ops;
     // Y' = Y.T : left factor Y -> pass Y^T;   Z' = T.Z : left factor T -> pass T^T
+    const NsConvAsk conv = ns_converged_ask<COH>(s, iter, lane);
     block_load<COH>(ops, isZ ? Tt : Yt, isZ ? Z : T, bi, bj, lane, wv, LoadPlain{});
-    if (ns_converged<COH>(s, iter, lane, false)) return false;  // part 1 of this iteration raised the flag
+    if (ns_converged<COH>(conv, s, iter, false)) return false;  // part 1 of this iteration raised the flag
     if (w == 0 && tid == 0) {
         gst<COH>(s + SC_ZBUF, (double)zbuf_out);  // which Z buffer holds the newest iterate
         gst<COH>(s + SC_ITERS, (double)(iter + 1));
