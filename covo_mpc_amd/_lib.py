@@ -27,6 +27,8 @@ COVO_DIAG_FLOATS = 8  # per-step sampling diagnostics of one instance (covo_set_
 DIAG_FIELDS = ("ess", "cost_min", "cost_weighted", "cost_mean", "weight_sum", "n_samples")
 COVO_PLAN_FLOATS = 100   # the plan of a step: {cost_plan, 0, 0, 0, pos_plan[H][3]} (covo_set_step_plan)
 COVO_TRACE_FLOATS = 168  # a trace row: true state[32], noisy state[32], u[4], the step's plan row (covo_set_episode_trace)
+COVO_LAM_FLOATS = 4  # the ESS floor's solver row of one instance: lam_eff, 1 / lam_eff, ESS(lam0), evaluations (covo_set_step_ess_floor)
+LAM_FIELDS = ("lam_eff", "inv_lam_eff", "ess_lam0", "evaluations")
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -156,6 +158,8 @@ _SIGS = {
     "covo_debug_set_ns_merged": (C.c_int, [_P, C.c_int]),
     "covo_set_step_diag": (C.c_int, [_P, _P, C.c_int32]),             # per-step sampling diagnostics (covo_hip.h)
     "covo_set_episode_diag_log": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_set_step_ess_floor": (C.c_int, [_P, C.c_float, _P, C.c_int32]),  # the ESS floor (covo_hip.h: COVO_HAS_ESS_FLOOR)
+    "covo_ess_lambda": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "covo_set_step_plan": (C.c_int, [_P, _P, C.c_int32]),             # the flight recorder (covo_hip.h: COVO_HAS_PLAN_TRACE)
     "covo_set_episode_trace": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,

@@ -53,8 +53,13 @@ class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
-                 compute_plan: bool = False):
+                 compute_plan: bool = False, ess_min=None):
         import torch
+        if ess_min is not None and float(ess_min) != 0.0 and process_group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(process_group) > 1:
+                raise NotImplementedError(f"ess_min={ess_min} on sample-sharded ranks: a rank sees only its shard's costs "
+                                          "(covo_set_step_ess_floor refuses sample-sharded steps)")
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -161,6 +166,15 @@ class SamplingCore:
                                           "exchange (covo_set_step_plan refuses sample-sharded steps)")
             self.plan = torch.zeros((int(diag_rows), _lib.COVO_PLAN_FLOATS), **f32)
             check(self.lib.covo_set_step_plan(self.h, ptr(self.plan), int(diag_rows)), "covo_set_step_plan")
+        # ess_min: the ESS floor -- every step solves its temperature on the device from its own costs so that the weights' effective
+        # sample size is at least ess_min (1 <= ess_min <= N / 2; lam stays the configured one whenever ESS(lam) >= ess_min already), and
+        # leaves {lam_eff, 1 / lam_eff, ESS(lam), evaluations} in self.lam_eff (row e = instance e of a batched step)
+        # (covo_set_step_ess_floor, csrc/ess_lambda.hip); off by default, and off changes nothing
+        self.ess_min = float(ess_min) if ess_min is not None else 0.0
+        self.lam_eff = None
+        if self.ess_min != 0.0:
+            self.lam_eff = torch.zeros((int(diag_rows), _lib.COVO_LAM_FLOATS), **f32)
+            check(self.lib.covo_set_step_ess_floor(self.h, self.ess_min, ptr(self.lam_eff), int(diag_rows)), "covo_set_step_ess_floor")
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -309,6 +323,13 @@ class SamplingCore:
             return {}
         return {"pos_plan": self.plan[0, 4:].view(COVO_H, 3), "cost_plan": self.plan[0, 0]}
 
+    def lam_info(self) -> dict:
+        """{"lam_eff", "ess_lam0"} of the last step as 0-d views of self.lam_eff (no sync, no copy); {} when the core was built
+        without ess_min."""
+        if self.lam_eff is None:
+            return {}
+        return {"lam_eff": self.lam_eff[0, 0], "ess_lam0": self.lam_eff[0, 2]}
+
     def attach_trace(self, episode, rows_left: int):
         """Bind `episode`'s trace (allocated on first use) for the segment that starts at episode.n_steps."""
         if not self.compute_plan:
@@ -318,6 +339,9 @@ class SamplingCore:
         check(self.lib.covo_set_episode_trace(self.h, ptr(episode.trace_view()), int(rows_left)), "covo_set_episode_trace")
 
     def require_fused_for_diag(self):
+        if self.ess_min != 0.0:
+            raise NotImplementedError("ess_min acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') updates at the configured lam")
         if self.compute_plan:
             raise NotImplementedError("compute_plan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")

@@ -29,7 +29,11 @@ class BatchedCoVOController:
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
-                 compute_plan: bool = False):
+                 compute_plan: bool = False, ess_min=None):
+        if ess_min is not None and float(ess_min) != 0.0 and (self.MODE is not None or mode != "online"):
+            raise NotImplementedError(f"ess_min={ess_min}: the ESS floor is not available for the env-batched MPPI / covo-offline step "
+                                      "(one fused launch: it needs the temperature before all costs exist); "
+                                      "BatchedCoVOController(mode=\"online\") and the single controllers take it")
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -47,7 +51,9 @@ class BatchedCoVOController:
         # 150-270 us of host time per call)
         # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
-                                 compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan)
+                                 compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min)
+        # ess_min: after a call, self.lam_eff [E, 4] holds every instance's {lam_eff, 1 / lam_eff, ESS(lam), evaluations} of that step
+        self.lam_eff = self.core.lam_eff
         self.diag = self.core.diag
         # compute_plan: after a call, self.plan [E, 100] holds every instance's plan of that step {cost_plan, 0, 0, 0, pos_plan[H][3]}
         self.plan = self.core.plan
@@ -215,13 +221,14 @@ class BatchedMPPIController(BatchedCoVOController):
     MODE = _lib.MODE_MPPI
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
-                 gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False):
+                 gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
+                 ess_min=None):
         if float(gamma_sigma) != 0.0:
             raise NotImplementedError(f"gamma_sigma={gamma_sigma}: MPPI's covariance adaptation (mppi.py:119-125) is not batched; "
                                       "the batched fused launch needs gamma_sigma == 0 (the reference's default)")
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
-                         a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan)
+                         a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

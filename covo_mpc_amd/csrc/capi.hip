@@ -91,6 +91,7 @@ int covo_create(const covo_config *cfg, covo_handle_t *out)
     COVO_CHECK_HIP(hipMalloc(&h->ws_diag_rec, (size_t)h->max_red_blocks * 4 * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->diag_scratch, (size_t)COVO_MAX_ENVS * COVO_DIAG_FLOATS * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->ws_blockmin, (size_t)ng * sizeof(float)));
+    COVO_CHECK_HIP(hipMalloc(&h->lam_own, (size_t)COVO_MAX_ENVS * COVO_LAM_FLOATS * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->ws_stats, (size_t)(nb > 256 ? nb : 256) * COVO_H * 6 * sizeof(double)));  // one row per rollout workgroup
     h->ws_sigma_bytes = sigma_ns_workspace_bytes(1);
     COVO_CHECK_HIP(hipMalloc(&h->ws_sigma, h->ws_sigma_bytes));
@@ -127,6 +128,7 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->ws_diag_rec));
     DESTROY(hipFree(h->diag_scratch));
     DESTROY(hipFree(h->ws_blockmin));
+    DESTROY(hipFree(h->lam_own));
     DESTROY(hipFree(h->ws_stats));
     DESTROY(hipFree(h->ws_sigma));
     DESTROY(hipFree(h->ws_hess));
@@ -692,6 +694,51 @@ int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride)
             "%s: sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log) are not available for sample-sharded "   \
             "steps (partial_out != NULL): the rank records carry no diagnostic sums; detach the buffer", what)
 
+// ---- the ESS floor (ess_lambda.hip).  The captured step graphs bake in the staged launch set, ess_min and where the solver writes:
+// any change bumps the epoch.  The valid range of ess_min depends on the step's sample count: checked at the step (CHECK_ESS_FLOOR)
+int covo_set_step_ess_floor(covo_handle_t h, float ess_min, float *lam_out, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_ess_floor: null handle");
+    REQUIRE(ess_min >= 0.0f && ess_min < __builtin_inff(), "covo_set_step_ess_floor: ess_min=%g is not a finite number >= 0 (0 = off)",
+            (double)ess_min);
+    REQUIRE(lam_out == nullptr || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_ess_floor: n_inst=%d outside (0, %d]", n_inst,
+            COVO_MAX_ENVS);
+    if (ess_min != h->ess_min || lam_out != h->lam_out) ++h->opt.epoch;
+    h->ess_min = ess_min;
+    h->lam_out = lam_out;
+    h->lam_n = lam_out ? n_inst : 0;
+    return 0;
+}
+
+int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, float lam0, float ess_min, float *out,
+                    void *stream)
+{
+    REQUIRE(h, "covo_ess_lambda: null handle");
+    CHECK_DEVICE(h, "covo_ess_lambda");
+    REQUIRE(cost && out && n_samples > 0 && n_inst > 0 && n_inst <= 65535, "covo_ess_lambda: bad argument");
+    REQUIRE(lam0 > 0.0f && lam0 < __builtin_inff(), "covo_ess_lambda: lam0=%g", (double)lam0);
+    REQUIRE(ess_min >= 1.0f && ess_min <= 0.5f * (float)n_samples, "covo_ess_lambda: ess_min=%g outside [1, n_samples / 2 = %g]",
+            (double)ess_min, 0.5 * n_samples);
+    return launch_ess_lambda(cost, n_samples, n_inst, nullptr, lam0, ess_min, out, (hipStream_t)stream);
+}
+
+// a step of n_samples samples for n_inst instances with a floor attached: ess_min in the range the solver's bracket covers, a row
+// per instance; a sample-sharded step has no floor
+#define CHECK_ESS_FLOOR(h, n_samples, n_inst, what)                                                                        \
+    do {                                                                                                                   \
+        if (covo_lam_target(h) != nullptr) {                                                                               \
+            REQUIRE((h)->ess_min >= 1.0f && (h)->ess_min <= 0.5f * (float)(n_samples),                                      \
+                    "%s: ess_min=%g (covo_set_step_ess_floor) outside [1, n_samples / 2 = %g]", what, (double)(h)->ess_min, \
+                    0.5 * (n_samples));                                                                                    \
+            REQUIRE((n_inst) <= covo_lam_capacity(h), "%s: %d instances, the temperature buffer (covo_set_step_ess_floor) has %d rows", \
+                    what, (int)(n_inst), covo_lam_capacity(h));                                                            \
+        }                                                                                                                  \
+    } while (0)
+#define REFUSE_SHARDED_ESS_FLOOR(h, args, what)                                                                            \
+    REQUIRE((args)->partial_out == nullptr || covo_lam_target(h) == nullptr,                                               \
+            "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for sample-sharded steps (partial_out != NULL): "  \
+            "a rank sees only its shard's costs; turn it off (ess_min = 0)", what, (double)(h)->ess_min)
+
 // ---- the flight recorder (plan_trace.hip).  Its launch is eager and follows the step: attaching or detaching a buffer changes no
 // captured step graph
 int covo_set_step_plan(covo_handle_t h, float *plan, int32_t n_inst)
@@ -794,6 +841,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     REQUIRE(h->diag_log == nullptr || n_steps <= h->diag_log_stride, "covo_run_episode: %d steps, the diagnostic log "
             "(covo_set_episode_diag_log) has %d rows", n_steps, h->diag_log_stride);
     REFUSE_SHARDED_PLAN(h, args, "covo_run_episode");
+    REFUSE_SHARDED_ESS_FLOOR(h, args, "covo_run_episode");
+    CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_run_episode");
     REQUIRE(h->trace == nullptr || n_steps <= h->trace_stride, "covo_run_episode: %d steps, the episode trace "
             "(covo_set_episode_trace) has %d rows", n_steps, h->trace_stride);
     hipStream_t s = (hipStream_t)stream;
@@ -896,6 +945,11 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
                 "%s: all instances must share reward_kind, rollover_terminate and disturb_kind (one kernel "
                 "variant per launch); disturb_params / period / scale may differ", what);
     }
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_lam_target(h) == nullptr,
+            "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for the env-batched MPPI / covo-offline step: its "
+            "one fused launch needs the temperature before all costs exist, and there is no staged batched fallback; turn it off "
+            "(ess_min = 0)", what, (double)h->ess_min);
+    CHECK_ESS_FLOOR(h, args->n_samples, args->n_envs, what);
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
     REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),
@@ -1085,6 +1139,8 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
             "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
     REFUSE_SHARDED_DIAG(h, args, "covo_mpc_step");
     REFUSE_SHARDED_PLAN(h, args, "covo_mpc_step");
+    REFUSE_SHARDED_ESS_FLOOR(h, args, "covo_mpc_step");
+    CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_mpc_step");
     const int rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);
     if (rc) return rc;
     return covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream);

@@ -60,7 +60,15 @@ struct covo_ctx {
     float *trace;             // caller's [n_inst][trace_stride][COVO_TRACE_FLOATS]: the episode drivers' steps write their rows there
     int trace_stride;
     void *plan;               // PlanState (plan_trace.hip): the device copy of a batched step's argument blocks
+    // the ESS floor (covo_set_step_ess_floor; ess_lambda.hip); ess_min == 0: off
+    float ess_min;
+    float *lam_out;           // caller's [lam_n][COVO_LAM_FLOATS]: instance e's solver row of every step; null: lam_own
+    int lam_n;
+    float *lam_own;           // [COVO_MAX_ENVS][COVO_LAM_FLOATS]
 };
+// where the solver of this handle's steps writes the instances' temperatures (null: no floor) and for how many instances
+static inline float *covo_lam_target(const covo_ctx *h) { return h->ess_min > 0.0f ? (h->lam_out ? h->lam_out : h->lam_own) : nullptr; }
+static inline int covo_lam_capacity(const covo_ctx *h) { return h->lam_out ? h->lam_n : COVO_MAX_ENVS; }
 static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->trace != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->diag_log ? h->diag_scratch : nullptr); }
@@ -272,8 +280,17 @@ struct UpdateDesc {
     // the sampling diagnostics, with a final update only
     float *diag_rec = nullptr;        // stage-1 diagnostic records [batch][blocks or G][4] (scratch of launch_softmax_reduce, input of launch_merge)
     float *diag_out = nullptr;        // [batch][COVO_DIAG_FLOATS]
+    // the ESS floor (launch_softmax_reduce / launch_softmax_update_cov, final updates only): instance e takes 1 / lambda from
+    // lam_rows[e][1] in device memory -- the solver's output, ess_lambda.hip -- instead of the handle's configured temperature
+    const float *lam_rows = nullptr;  // [batch][COVO_LAM_FLOATS]
 };
+// the ESS floor's solver (ess_lambda.hip): out [n_inst][COVO_LAM_FLOATS] from cost [n_inst][N]; groupmin [n_inst][ceil(N/64)] as the
+// rollout leaves it, or null (the minimum is then formed from the costs)
+int launch_ess_lambda(const float *cost, int N, int n_inst, const float *groupmin, float lam0, float ess_min, float *out, hipStream_t s);
 int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
+// reduce_lam.hip: what the two launch functions do with d.lam_rows set
+int launch_softmax_reduce_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
+int launch_softmax_update_cov_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 int launch_merge(const UpdateDesc &d, float lam, hipStream_t s);
 // exchange.hip: the rank records of a sample-sharded step and their peer-write exchange
 int launch_rank_stats_sum(const float *records, int G, int record_floats, double *out, hipStream_t s);  // COVO_RANK_RECORD_[COV_]FLOATS

@@ -607,8 +607,8 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 
 
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
-                   compute_info=True, compute_diag=False, compute_plan=False):
-    """quadrotor.py:670-752."""
+                   compute_info=True, compute_diag=False, compute_plan=False, ess_min=None):
+    """quadrotor.py:670-752.  ess_min (sampling controllers): the ESS floor, see SamplingCore."""
     import torch
 
     def parse_sample_params(param_text):
@@ -636,7 +636,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info,
-                                          compute_diag=compute_diag, compute_plan=compute_plan), control_params
+                                          compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -649,7 +649,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group,
                                           compute_info=compute_info, compute_diag=compute_diag,
-                                          compute_plan=compute_plan), control_params
+                                          compute_plan=compute_plan, ess_min=ess_min), control_params
     raise NotImplementedError(controller_name)
 
 

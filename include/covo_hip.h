@@ -440,6 +440,30 @@ int covo_debug_hess_workspace(covo_handle_t h, double *out, int64_t offset_doubl
 int covo_set_step_diag(covo_handle_t h, float *diag, int32_t n_inst);
 int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride);
 
+/* The ESS floor: a per-step temperature solved on the device from the step's costs (additive to ABI 10: COVO_HAS_ESS_FLOOR; off
+ * by default, and off changes nothing a caller can observe).  With the handle's configured temperature lam0 (covo_config.lam),
+ * costs c_n as the rollout wrote them, m = min c_n, w_n(lam) = expf((m - c_n) * (1 / lam)) in fp32 and
+ * ESS(lam) = (sum w)^2 / sum w^2 (non-decreasing in lam):
+ *   ESS(lam0) >= ess_min   lam_eff = lam0 exactly: the floor is inactive
+ *   otherwise              lam_eff solves ESS(lam) = ess_min on (lam0, 3 (max finite c - m)], to the resolution of fp32 temperatures
+ * The bracket holds the solution for 1 <= ess_min <= N / 2; a step whose ess_min lies outside is refused.  The step's weights,
+ * its mean update, MPPI's covariance adaptation and the diagnostics use lam_eff; actions, costs, Sigma, L and the key chain are those
+ * of the same step without a floor.  Per instance the solver leaves float[COVO_LAM_FLOATS]:
+ *   [0] lam_eff   [1] 1 / lam_eff (what the update's launches multiply by)   [2] ESS(lam0)   [3] ESS evaluations taken (<= 64)
+ * covo_set_step_ess_floor: ess_min = 0 turns the floor off; lam_out = DEVICE float[n_inst][COVO_LAM_FLOATS] (row e = instance e of a
+ *   batched step, a single step writes row 0), or NULL for a buffer the handle owns.  Covered: covo_mpc_step (all modes, eager and
+ *   graph), covo_mpc_step_batched and the episode drivers that call them; such a step runs staged -- rollout, solver, stage 1 and
+ *   merge reading 1 / lam_eff from device memory -- so one captured graph serves every step.  Attaching, detaching or changing
+ *   ess_min makes the handle re-capture its step graphs, like covo_set_step_diag.  Refused before any launch: a sample-sharded step
+ *   (partial_out != NULL), and covo_mpc_step_batched_mode / covo_run_episode_batched_mode in the MPPI and covo-offline modes (their
+ *   fused launch needs the temperature before all costs exist, and there is no staged batched fallback).
+ * covo_ess_lambda: the solver alone on the caller's costs, DEVICE float[n_inst][n_samples] -> out = DEVICE
+ *   float[n_inst][COVO_LAM_FLOATS]; it forms the cost minima itself. */
+#define COVO_HAS_ESS_FLOOR 1
+#define COVO_LAM_FLOATS 4
+int covo_set_step_ess_floor(covo_handle_t h, float ess_min, float *lam_out, int32_t n_inst);
+int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, float lam0, float ess_min, float *out, void *stream);
+
 /* The flight recorder: the plan of a control step and the trace of an episode (additive to ABI 10: COVO_HAS_PLAN_TRACE; off by
  * default, and off changes nothing a caller can observe).
  * The PLAN of a step, for one instance: a_plan = clip(a_new, -1, 1), a_new the mean the step leaves in a_mean (covo.py:275,
