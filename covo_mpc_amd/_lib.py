@@ -28,6 +28,9 @@ DIAG_FIELDS = ("ess", "cost_min", "cost_weighted", "cost_mean", "weight_sum", "n
 COVO_PLAN_FLOATS = 100   # the plan of a step: {cost_plan, 0, 0, 0, pos_plan[H][3]} (covo_set_step_plan)
 COVO_TRACE_FLOATS = 168  # a trace row: true state[32], noisy state[32], u[4], the step's plan row (covo_set_episode_trace)
 COVO_LAM_FLOATS = 4  # the ESS floor's solver row of one instance: lam_eff, 1 / lam_eff, ESS(lam0), evaluations (covo_set_step_ess_floor)
+COVO_HAS_SAMPLE_FAN = 1
+COVO_FAN_FLOATS = 100  # a fan row: {cost_s, bits(int32 n_s), 0, 0, pos_s[H][3]} (covo_set_step_fan): the layout of a plan row
+COVO_FAN_MAX = 64      # rows of a fan: one 64-sample group of the rollout
 LAM_FIELDS = ("lam_eff", "inv_lam_eff", "ess_lam0", "evaluations")
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
@@ -162,6 +165,10 @@ _SIGS = {
     "covo_ess_lambda": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "covo_set_step_plan": (C.c_int, [_P, _P, C.c_int32]),             # the flight recorder (covo_hip.h: COVO_HAS_PLAN_TRACE)
     "covo_set_episode_trace": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_rollout_fan": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P,
+                                   C.c_int32, _P, C.c_int32, _P, _P]),  # the sample fan (covo_hip.h: COVO_HAS_SAMPLE_FAN)
+    "covo_set_step_fan": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
+    "covo_set_episode_fan": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),
@@ -206,6 +213,19 @@ def check(rc: int, what: str = "") -> None:
     if rc != 0:
         msg = load_library().covo_last_error()
         raise CovoError(f"{what} failed with code {rc}: {msg.decode() if msg else ''}")
+
+
+def check_fan(compute_fan, N) -> int:
+    """compute_fan= of the controllers -> the fan size K (0: off): None / False / 0 given as the default mean off; anything else
+    must be an integer in [1, COVO_FAN_MAX] and <= N."""
+    if compute_fan is None or compute_fan is False:
+        return 0
+    K = int(compute_fan)
+    if isinstance(compute_fan, bool) or K != compute_fan or not 1 <= K <= COVO_FAN_MAX:
+        raise ValueError(f"compute_fan={compute_fan!r} outside [1, {COVO_FAN_MAX}] (the fan size K; None = off)")
+    if K > int(N):
+        raise ValueError(f"compute_fan={K} > N={N}: the fan takes K of the step's N samples")
+    return K
 
 
 def ptr(t):

@@ -53,8 +53,14 @@ class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
-                 compute_plan: bool = False, ess_min=None):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None):
         import torch
+        fan_K = _lib.check_fan(compute_fan, N)
+        if fan_K and process_group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(process_group) > 1:
+                raise NotImplementedError("compute_fan on sample-sharded ranks: a rank's action buffer holds its shard only "
+                                          "(covo_set_step_fan refuses sample-sharded steps)")
         if ess_min is not None and float(ess_min) != 0.0 and process_group is not None:
             import torch.distributed as dist
             if dist.get_world_size(process_group) > 1:
@@ -166,6 +172,18 @@ class SamplingCore:
                                           "exchange (covo_set_step_plan refuses sample-sharded steps)")
             self.plan = torch.zeros((int(diag_rows), _lib.COVO_PLAN_FLOATS), **f32)
             check(self.lib.covo_set_step_plan(self.h, ptr(self.plan), int(diag_rows)), "covo_set_step_plan")
+        # compute_fan = K: every step also leaves K of its N sampled rollouts -- rows {cost_s, bits(n_s), 0, 0, pos_s[H][3]} of the
+        # samples self.fan_idx names (pre-filled with the stride (s N) / K; a caller may overwrite it between steps; the launch clamps
+        # it into [0, N)) -- in self.fan (row e = instance e of a batched step), by one extra launch behind the step
+        # (covo_set_step_fan, csrc/sample_fan.hip); off by default, and off changes nothing
+        self.compute_fan = fan_K
+        self.fan = self.fan_idx = None
+        if fan_K:
+            rows = int(diag_rows)
+            self.fan = torch.zeros((rows, fan_K, _lib.COVO_FAN_FLOATS), **f32)
+            stride = (torch.arange(fan_K, dtype=torch.int64) * self.n_local) // fan_K
+            self.fan_idx = stride.to(torch.int32).reshape(1, fan_K).repeat(rows, 1).to(self.device).contiguous()
+            check(self.lib.covo_set_step_fan(self.h, ptr(self.fan), ptr(self.fan_idx), fan_K, rows), "covo_set_step_fan")
         # ess_min: the ESS floor -- every step solves its temperature on the device from its own costs so that the weights' effective
         # sample size is at least ess_min (1 <= ess_min <= N / 2; lam stays the configured one whenever ESS(lam) >= ess_min already), and
         # leaves {lam_eff, 1 / lam_eff, ESS(lam), evaluations} in self.lam_eff (row e = instance e of a batched step)
@@ -323,6 +341,41 @@ class SamplingCore:
             return {}
         return {"pos_plan": self.plan[0, 4:].view(COVO_H, 3), "cost_plan": self.plan[0, 0]}
 
+    def fan_info(self) -> dict:
+        """{"fan_pos" [K, H, 3], "fan_cost" [K], "fan_idx" [K] int32} of the last step as views of self.fan (no sync, no copy); {}
+        when the core was built without compute_fan."""
+        if self.fan is None:
+            return {}
+        K = self.compute_fan
+        return {"fan_pos": self.fan[0, :, 4:].view(K, COVO_H, 3), "fan_cost": self.fan[0, :, 0],
+                "fan_idx": self.fan[0, :, 1].view(self.torch.int32)}
+
+    def attach_fan_log(self, episode, rows_left: int):
+        """Bind `episode`'s fan log (allocated on first use) for the segment that starts at episode.n_steps."""
+        if not self.compute_fan:
+            return
+        if getattr(episode, "fanlog", None) is None:
+            episode.alloc_fan_log(self.compute_fan)
+        check(self.lib.covo_set_episode_fan(self.h, ptr(episode.fan_log_view()), int(rows_left)), "covo_set_episode_fan")
+
+    def rollout_fan(self, dstate, params_c, idx, f_shared=None, f_steps=None, K=None):
+        """covo_rollout_fan on self.a: the trajectories of the samples `idx` (int32 device tensor [K], clamped into [0, n_local) by
+        the launch; None: K -- default compute_fan or 16 -- samples at the stride) with the inputs of rollout() -> float32 [K, 100] rows
+        {cost_s, bits(n_s), 0, 0, pos_s[H][3]}.  The K best samples of a step: idx = torch.topk(-core.cost, K).indices.int()
+        together with the step's own f_shared / f_steps."""
+        torch = self.torch
+        if idx is None:
+            K, ip = int(K) if K is not None else min(self.compute_fan or 16, self.n_local), None
+        else:
+            idx = idx.to(device=self.device, dtype=torch.int32).contiguous()
+            K, ip = int(idx.numel()), ptr(idx)
+        out = torch.empty((K, _lib.COVO_FAN_FLOATS), dtype=torch.float32, device=self.device)
+        fs = (C.c_float * 3)(*[float(x) for x in f_shared]) if f_shared is not None else None
+        check(self.lib.covo_rollout_fan(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                        C.byref(params_c), fs, ptr(f_steps), ptr(self.a), self.n_local, ip, K, ptr(out),
+                                        self.stream()), "covo_rollout_fan")
+        return out
+
     def lam_info(self) -> dict:
         """{"lam_eff", "ess_lam0"} of the last step as 0-d views of self.lam_eff (no sync, no copy); {} when the core was built
         without ess_min."""
@@ -344,6 +397,9 @@ class SamplingCore:
                                       "(materialize_eps / noise_stream='jax') updates at the configured lam")
         if self.compute_plan:
             raise NotImplementedError("compute_plan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') does not produce it")
+        if self.compute_fan:
+            raise NotImplementedError("compute_fan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")
         if self.compute_diag:
             raise NotImplementedError("compute_diag is formed by the fused step (covo_mpc_step); the kernel-by-kernel path "
@@ -571,6 +627,8 @@ class SamplingCore:
         self.attach_diag_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # compute_plan: and row n_steps + k of its [T + 1, 168] trace (true state, noisy state, u, plan)
         self.attach_trace(episode, int(episode.log.shape[0]) - int(episode.n_steps))
+        # compute_fan: and row n_steps + k of its [T + 1, K, 100] fan log
+        self.attach_fan_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # the env step's auto-reset (base.py:22-40) is a property of the EPISODE, the model constants come from the controller
         params_c = type(params_c).from_buffer_copy(params_c)
         for f in ("reset_traj", "reset_dt", "reset_disturb_scale"):

@@ -46,7 +46,9 @@ class CoVOParams:
 class CoVOController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, mode: str = "online", *, device=None,
                  process_group=None, compute_info: bool = True, propagate_nan=None, compute_diag: bool = False,
-                 compute_plan: bool = False, ess_min=None) -> None:
+                 compute_plan: bool = False, ess_min=None, compute_fan=None) -> None:
+        from .. import _lib
+        _lib.check_fan(compute_fan, N)  # ValueError before anything is built
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -66,7 +68,8 @@ class CoVOController(BaseController):
         # propagate_nan: jnp.clip's NaN semantics in the sampling clip (covo.py:224) -- see SamplingCore
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
                                  compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan,
-                                 compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min)
+                                 compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
+                                 compute_fan=compute_fan)
 
     def _needs_table(self, params_c) -> bool:
         """periodic / sin / drag / mixed (free.py:10-58): quadjax's deterministic=True only zeroes dyn_noise_scale
@@ -213,6 +216,7 @@ class CoVOController(BaseController):
             out_info = core.info(dstate) if core.compute_info else {}
             out_info.update(core.diag_info())  # compute_diag: ess / cost_min / cost_weighted / cost_mean, views of core.diag
             out_info.update(core.plan_info())  # compute_plan: pos_plan [H, 3] / cost_plan, views of core.plan
+            out_info.update(core.fan_info())   # compute_fan: fan_pos [K, H, 3] / fan_cost [K] / fan_idx [K], views of core.fan
             out_info.update(core.lam_info())   # ess_min: lam_eff / ess_lam0, views of core.lam_eff
             return a_mean_new[0], control_params, out_info
 

@@ -113,6 +113,7 @@ int covo_destroy(covo_handle_t h)
     step_state_destroy(h);
     batch_state_destroy(h);
     plan_state_destroy(h);
+    fan_state_destroy(h);
     exchange_destroy(h);
     int rc = 0;
 #define DESTROY(expr)                                                                                   \
@@ -769,6 +770,85 @@ int covo_set_episode_trace(covo_handle_t h, float *trace, int32_t stride)
             "%s: the plan / episode trace (covo_set_step_plan / covo_set_episode_trace) is not available for sample-sharded "   \
             "steps (partial_out != NULL): a rank holds only its shard's record until the exchange; detach the buffer", what)
 
+// ---- the sample fan (sample_fan.hip).  Like the plan's, its launch is eager and follows the step: no captured step graph changes
+int covo_set_step_fan(covo_handle_t h, float *fan, const int32_t *idx, int32_t K, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_fan: null handle");
+    if (fan == nullptr && K == 0) {  // off, the log with it
+        h->fan_out = nullptr;
+        h->fan_idx = nullptr;
+        h->fan_K = h->fan_n = 0;
+        h->fanlog = nullptr;
+        h->fanlog_stride = 0;
+        return 0;
+    }
+    REQUIRE(K >= 1 && K <= COVO_FAN_MAX, "covo_set_step_fan: K=%d outside [1, %d]", K, COVO_FAN_MAX);
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_fan: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(K <= h->cfg.n_local, "covo_set_step_fan: K=%d > n_samples: the handle has n_local=%d samples", K, h->cfg.n_local);
+    REQUIRE(h->fanlog == nullptr || K == h->fan_K, "covo_set_step_fan: K=%d differs from the attached episode log's K=%d "
+            "(detach it first: covo_set_episode_fan(h, NULL, 0))", K, h->fan_K);
+    h->fan_out = fan;
+    h->fan_idx = idx;
+    h->fan_K = K;
+    h->fan_n = n_inst;
+    return 0;
+}
+
+int covo_set_episode_fan(covo_handle_t h, float *fanlog, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_fan: null handle");
+    REQUIRE(fanlog == nullptr || stride > 0, "covo_set_episode_fan: stride=%d", stride);
+    REQUIRE(fanlog == nullptr || h->fan_K > 0, "covo_set_episode_fan: no fan size: call covo_set_step_fan (K, idx, n_inst) first");
+    h->fanlog = fanlog;
+    h->fanlog_stride = fanlog ? stride : 0;
+    return 0;
+}
+
+// a step of n_samples samples for n_inst instances with a fan attached
+#define CHECK_FAN(h, n_samples, n_inst, what)                                                                              \
+    do {                                                                                                                   \
+        if (covo_fan_on(h)) {                                                                                              \
+            REQUIRE((h)->fan_K <= (n_samples), "%s: the sample fan (covo_set_step_fan) has K=%d > n_samples=%d", what,     \
+                    (h)->fan_K, (int)(n_samples));                                                                         \
+            REQUIRE((n_inst) <= (h)->fan_n, "%s: %d instances, the fan buffer (covo_set_step_fan) has n_inst=%d", what,    \
+                    (int)(n_inst), (h)->fan_n);                                                                            \
+        }                                                                                                                  \
+    } while (0)
+#define REFUSE_SHARDED_FAN(h, args, what)                                                                                  \
+    REQUIRE((args)->partial_out == nullptr || !covo_fan_on(h),                                                             \
+            "%s: the sample fan (covo_set_step_fan / covo_set_episode_fan) is not available for sample-sharded steps "      \
+            "(partial_out != NULL): a rank's action buffer holds its shard only; detach the buffer", what)
+
+int covo_rollout_fan(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                     const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                     const float *a, int32_t N, const int32_t *idx, int32_t K, float *fan_out, void *stream)
+{
+    REQUIRE(h, "covo_rollout_fan: null handle");
+    CHECK_DEVICE(h, "covo_rollout_fan");
+    REQUIRE(state && pos_traj && vel_traj && params && a && fan_out && T > 0, "covo_rollout_fan: bad argument");
+    REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_rollout_fan: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
+    REQUIRE(K >= 1 && K <= COVO_FAN_MAX, "covo_rollout_fan: K=%d outside [1, %d]", K, COVO_FAN_MAX);
+    REQUIRE(K <= N, "covo_rollout_fan: K=%d > n_samples=%d", K, N);
+    CHECK_MODEL(params, "covo_rollout_fan");
+    REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_rollout_fan: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
+            params->disturb_kind);
+    PlanInstDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a = a;
+    d.N = N;
+    d.f_tab = f_disturb_steps;
+    for (int i = 0; i < 3; ++i) d.f_shared[i] = f_disturb_shared ? f_disturb_shared[i] : 0.0f;
+    d.derive_keys = 0;  // the shared vector is the caller's
+    RolloutClip clip = ROLLOUT_CLIP_TRUSTED;  // as covo_rollout_cost treats the stripes
+    if ((h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) == 0) clip = covo_propagate_nan(h) ? ROLLOUT_CLIP_REAPPLY_NAN : ROLLOUT_CLIP_REAPPLY;
+    return launch_sample_fan_one(h, d, clip, idx, K, fan_out, (hipStream_t)stream);
+}
+
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)
 {
     REQUIRE(h && out, "covo_debug_sigma_workspace: bad argument");
@@ -845,6 +925,10 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_run_episode");
     REQUIRE(h->trace == nullptr || n_steps <= h->trace_stride, "covo_run_episode: %d steps, the episode trace "
             "(covo_set_episode_trace) has %d rows", n_steps, h->trace_stride);
+    REFUSE_SHARDED_FAN(h, args, "covo_run_episode");
+    CHECK_FAN(h, args->n_samples, 1, "covo_run_episode");
+    REQUIRE(h->fanlog == nullptr || n_steps <= h->fanlog_stride, "covo_run_episode: %d steps, the episode fan log "
+            "(covo_set_episode_fan) has %d rows", n_steps, h->fanlog_stride);
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -997,6 +1081,10 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     REQUIRE(h->trace == nullptr || (log_index >= 0 && log_index + n_steps <= h->trace_stride),
             "%s: episode trace rows [%d, %d) outside [0, %d) (covo_set_episode_trace)", what, log_index, log_index + n_steps,
             h->trace_stride);
+    CHECK_FAN(h, args->n_samples, E, what);
+    REQUIRE(h->fanlog == nullptr || (log_index >= 0 && log_index + n_steps <= h->fanlog_stride),
+            "%s: episode fan log rows [%d, %d) outside [0, %d) (covo_set_episode_fan)", what, log_index, log_index + n_steps,
+            h->fanlog_stride);
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -1059,6 +1147,7 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     if (rc) return rc;
     CHECK_DIAG(h, args->n_envs, "covo_mpc_step_batched");
     CHECK_PLAN(h, args->n_envs, "covo_mpc_step_batched");
+    CHECK_FAN(h, args->n_samples, args->n_envs, "covo_mpc_step_batched");
     if ((rc = covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream))) return rc;
     return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, (hipStream_t)stream);
 }
@@ -1074,6 +1163,7 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     if (rc) return rc;
     CHECK_DIAG(h, args->base.n_envs, "covo_mpc_step_batched_mode");
     CHECK_PLAN(h, args->base.n_envs, "covo_mpc_step_batched_mode");
+    CHECK_FAN(h, args->base.n_samples, args->base.n_envs, "covo_mpc_step_batched_mode");
     rc = args->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream)
                                              : covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
     if (rc) return rc;
@@ -1139,6 +1229,8 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
             "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
     REFUSE_SHARDED_DIAG(h, args, "covo_mpc_step");
     REFUSE_SHARDED_PLAN(h, args, "covo_mpc_step");
+    REFUSE_SHARDED_FAN(h, args, "covo_mpc_step");
+    CHECK_FAN(h, args->n_samples, 1, "covo_mpc_step");
     REFUSE_SHARDED_ESS_FLOOR(h, args, "covo_mpc_step");
     CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_mpc_step");
     const int rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);

@@ -60,6 +60,13 @@ struct covo_ctx {
     float *trace;             // caller's [n_inst][trace_stride][COVO_TRACE_FLOATS]: the episode drivers' steps write their rows there
     int trace_stride;
     void *plan;               // PlanState (plan_trace.hip): the device copy of a batched step's argument blocks
+    // the sample fan (covo_set_step_fan / covo_set_episode_fan; sample_fan.hip); all null / 0: off
+    float *fan_out;           // caller's [fan_n][fan_K][COVO_FAN_FLOATS]: instance e's fan of every step
+    const int32_t *fan_idx;   // caller's [fan_n][fan_K] sample indices, or null: the stride
+    int fan_K, fan_n;
+    float *fanlog;            // caller's [n_inst][fanlog_stride][fan_K][COVO_FAN_FLOATS]: the episode drivers' steps write their rows there
+    int fanlog_stride;
+    void *fan_state;          // FanState (sample_fan.hip): the device copy of a batched step's argument blocks
     // the ESS floor (covo_set_step_ess_floor; ess_lambda.hip); ess_min == 0: off
     float ess_min;
     float *lam_out;           // caller's [lam_n][COVO_LAM_FLOATS]: instance e's solver row of every step; null: lam_own
@@ -70,6 +77,7 @@ struct covo_ctx {
 static inline float *covo_lam_target(const covo_ctx *h) { return h->ess_min > 0.0f ? (h->lam_out ? h->lam_out : h->lam_own) : nullptr; }
 static inline int covo_lam_capacity(const covo_ctx *h) { return h->lam_out ? h->lam_n : COVO_MAX_ENVS; }
 static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->trace != nullptr; }
+static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->fanlog != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->diag_log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->diag_log ? COVO_MAX_ENVS : 0); }
@@ -170,7 +178,7 @@ __device__ __forceinline__ float wave_sum(float v)
 // launch entry points implemented in the .hip files (host functions)
 int launch_randn(uint32_t k0, uint32_t k1, int64_t off, int n_samples, int n_cols, float *out, hipStream_t s);
 int launch_randn_jax(uint32_t k0, uint32_t k1, int64_t n_total, int64_t off, int n_samples, int mppi, float *out, hipStream_t s);
-// Host-side launch descriptors (DESIGN.md 4.10): one per kernel family, filled field by field; every field has a default and a null /
+// Host-side launch descriptors (DESIGN.md 4.11): one per kernel family, filled field by field; every field has a default and a null /
 // zero field means "off".  Kernel-argument structs (RolloutArgs, AdjArgs, ...) are built from them inside the launch functions.
 //
 // threads per workgroup the noise GEMM launches with for (N, batch) (noise_gemm.hip: 512 once a launch fills the chip, else 256);
@@ -409,7 +417,7 @@ int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, 
 int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_t s, const void **inst_dev);  // step.hip
 // the episode drivers: row e of the step's diagnostics -> row `index` of instance e's diagnostic log
 int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s);
-// plan_trace.hip: what the recorder needs to know about ONE instance of the step that has just been enqueued -- the inputs its
+// plan_trace.hip, sample_fan.hip: what the recorder needs to know about ONE instance of the step that has just been enqueued -- the inputs its
 // sample rollouts had.  key_mem (batched steps): the instance's raw rng_act in device memory; else key / f_shared as covo_mpc_step got them
 struct PlanInstDesc {
     const float *state;       // the noisy state the step planned from [32]
@@ -417,6 +425,8 @@ struct PlanInstDesc {
     int T;
     const covo_env_params *params;
     const float *a_mean;      // [128] the mean the step leaves
+    const float *a;           // [H][N][4] the step's action stripes (the sample fan)
+    int N;
     const float *f_tab;       // the step's per-step disturbance table [H][4] (periodic / sin / drag / mixed), else null
     const uint32_t *key_mem;
     uint32_t key[2];
@@ -427,6 +437,11 @@ struct PlanInstDesc {
 int launch_plan_trace(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, const float *states_true, int trace_index,
                       hipStream_t s);
 void plan_state_destroy(covo_ctx *h);
+// sample_fan.hip: the fan of the step that has just been enqueued (no-op with nothing attached); log_index >= 0: an episode
+// driver's step, which also writes its row of the fan log.  launch_sample_fan_one: covo_rollout_fan
+int launch_sample_fan(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s);
+int launch_sample_fan_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const int32_t *idx, int K, float *fan_out, hipStream_t s);
+void fan_state_destroy(covo_ctx *h);
 // step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
 // states_true + trace_index >= 0: an episode driver's step, which also writes its trace row
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,

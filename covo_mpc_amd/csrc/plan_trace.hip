@@ -120,7 +120,7 @@ __global__ __launch_bounds__(PT_BLOCK) void plan_trace_kernel(const PlanArgs P_,
     float cost = 0.0f;
     bool valid = false;
     int n = 0;
-    rp3_stages<false, ROLL, PT_CH, -1, false, true, REWARD, FDIST, true, PlanPos, COVO_H, true>(A, S.rings, S.p, wave, 0, 0, lane,
+    rp3_stages<false, ROLL, PT_CH, -1, false, true, REWARD, FDIST, true, PlanPos, COVO_H, 1>(A, S.rings, S.p, wave, 0, 0, lane,
                                                                                                 &S.a[0][0], cost, valid, n);
     if (wave == 2 && lane == 0) S.cost = cost;
     __syncthreads();

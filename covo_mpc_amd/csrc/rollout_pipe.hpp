@@ -108,11 +108,13 @@ __device__ __forceinline__ float rp3_atan2abs(float y, float x)
 // (role 2), its sample index n and whether the sample exists.  KEEP_ALL: the A and T waves come back too (the caller has an
 // epilogue for every wave: softmax records, position statistics); otherwise they leave the launch when their stage is done.
 // KSTEPS (scripts/probe/rollout_lab.hip only): the stages stop after KSTEPS steps -- the timing bound of a split-horizon launch.
-// PLAN (plan_trace.hip only; off everywhere else): stage T's lane 0 also stores its new position of every step to
-// lds_st.pos[k][0..2] (`lds_st` is then the caller's position image, not the statistics scratch) -- covo.py:234-237's poses for
-// the one sample of a plan rollout.
+// PLAN (the flight recorder only; 0 = off everywhere else): stage T also stores its new position of every step to the caller's
+// position image (`lds_st` is then that image, not the statistics scratch) -- covo.py:234-237's poses.
+//   1 (plan_trace.hip)  lane 0 only, lds_st.pos[k][0..2]: the one sample of a plan rollout
+//   2 (sample_fan.hip)  every lane, lds_st.pos[k][0..2][lane]: the 64 samples of a fan; stage R then leaves the costs to its
+//                       caller (`cost`) instead of storing them to A.cost / A.groupmin
 template <bool DISC1, bool ROLL, int CH, int ONLY, bool STATS, bool KEEP_ALL, int REWARD, int FDIST, bool A_LDS, class StatsLds,
-          int KSTEPS = COVO_H, bool PLAN = false>
+          int KSTEPS = COVO_H, int PLAN = 0>
 __device__ __forceinline__ void rp3_stages(const RolloutArgs &A, Rp3Lds<CH> &lds, StatsLds &lds_st, const int role, const int gsub,
                                            const int group, const int lane, const float4 *__restrict__ a_lds, float &cost, bool &valid_out,
                                            int &n_out)
@@ -353,17 +355,23 @@ __device__ __forceinline__ void rp3_stages(const RolloutArgs &A, Rp3Lds<CH> &lds
                     else { vx += csx; vy += csy; vz += csz; }
                 }
                 if (STATS) stats_step(k, px, py, pz);
-                if constexpr (PLAN) {
+                if constexpr (PLAN == 1) {
                     if (lane == 0) { lds_st.pos[k][0] = px; lds_st.pos[k][1] = py; lds_st.pos[k][2] = pz; }
+                } else if constexpr (PLAN == 2) {
+                    lds_st.pos[k][0][lane] = px; lds_st.pos[k][1][lane] = py; lds_st.pos[k][2][lane] = pz;
                 }
             } else if (STATS) {  // the last step's new position enters no cost, only the statistics
                 stats_step(k, __builtin_fmaf(vx, c.dt, px), __builtin_fmaf(vy, c.dt, py), __builtin_fmaf(vz, c.dt, pz));
-            } else if constexpr (PLAN) {
+            } else if constexpr (PLAN == 1) {
                 if (lane == 0) {
                     lds_st.pos[k][0] = __builtin_fmaf(vx, c.dt, px);
                     lds_st.pos[k][1] = __builtin_fmaf(vy, c.dt, py);
                     lds_st.pos[k][2] = __builtin_fmaf(vz, c.dt, pz);
                 }
+            } else if constexpr (PLAN == 2) {
+                lds_st.pos[k][0][lane] = __builtin_fmaf(vx, c.dt, px);
+                lds_st.pos[k][1][lane] = __builtin_fmaf(vy, c.dt, py);
+                lds_st.pos[k][2][lane] = __builtin_fmaf(vz, c.dt, pz);
             }
             if ((k + 1) % CH == 0) {
                 if (k + 1 == CH) RP3_STAMP(1);
@@ -421,10 +429,12 @@ __device__ __forceinline__ void rp3_stages(const RolloutArgs &A, Rp3Lds<CH> &lds
     }
     RP3_FLUSH(2);
     cost = -acc;  // covo.py:263
-    if (valid) A.cost[n] = cost;
-    if (A.groupmin != nullptr) {
-        const float wm = wave_min(valid ? cost : __builtin_inff());
-        if (lane == 0 && group * COVO_WAVE < A.N) A.groupmin[group] = wm;
+    if constexpr (PLAN != 2) {
+        if (valid) A.cost[n] = cost;
+        if (A.groupmin != nullptr) {
+            const float wm = wave_min(valid ? cost : __builtin_inff());
+            if (lane == 0 && group * COVO_WAVE < A.N) A.groupmin[group] = wm;
+        }
     }
     }
 }

@@ -1,0 +1,290 @@
+// sample_fan.hip -- the sample fan of a control step (gfx950): K of the step's N sampled rollouts as trajectories
+// (covo_rollout_fan / covo_set_step_fan / covo_set_episode_fan, include/covo_hip.h).
+//
+// The fan of one instance: K rows {cost_s, bits(int32 n_s), 0, 0, pos_s[H][3]}, the layout of a plan row.  n_s is the local sample
+// the row was taken from (the caller's idx clamped into [0, N), or the stride (s N) / K), pos_s[k] its position after rollout step k
+// (the reference's poses[k, n_s], covo.py:234-237 / mppi.py:77-80; they keep integrating after done), cost_s what the rollout's
+// stage functions give the action stripe a[:, n_s, :] with the step's own inputs -- the value the step's rollout left in cost[n_s],
+// bit for bit.
+//
+// One launch, one workgroup of three waves per instance, eager, behind the step (and behind the plan launch, if attached):
+//   phase 0  the per-step scalars from the raw controller key (step_begin.hpp: step_begin_derive; the stand-alone entry passes its
+//            shared vector through with derive_keys = 0), the sample of every lane, and the gather a[t][n_lane] into the LDS action
+//            image [H][64] float4.  Lanes >= K take lane K - 1's stripe and are never stored.
+//   phase 1  the rollout's own three stage waves on the image (rollout_pipe.hpp: rp3_stages with A_LDS, N = 64, the general
+//            discount path as in plan_trace.hip; PLAN = 2: stage T stores every lane's new position per step to an LDS tile
+//            [H][3][64], stage R hands its costs back instead of storing them)
+//   phase 2  the K rows, coalesced, to the step's fan buffer and / or row `log_index` of the episode's fan log.
+// The row index travels as a kernel argument, so nothing is captured and no step graph changes.  BATCHED: workgroup e takes its
+// argument block from device memory (pointers through rebase_global, as plan_trace_kernel does).
+#include <cstring>
+#include <vector>
+#include "rollout_common.hpp"
+#include "step_begin.hpp"
+
+constexpr int SF_BLOCK = 3 * COVO_WAVE;
+constexpr int SF_CH = 2;
+
+struct FanArgs {
+    RolloutArgs R;            // the step's sample rollout: noisy state, trajectories, model, discount, disturbance table, a and N;
+                              // R.clip: how phase 0 clips the gathered stripes (the stages then trust the image)
+    const uint32_t *key_mem;  // the raw rng_act of the step in device memory (batched steps), or null: FanDyn's
+    const int32_t *idx;       // [K] the caller's sample indices, or null: the stride
+    float *fan_out;           // this instance's [K][COVO_FAN_FLOATS] of the fan buffer, or null
+    float *fanlog;            // this instance's [stride][K][COVO_FAN_FLOATS] of the episode log, or null
+    int derive_keys;
+    float shared_noise_scale;
+    int K;
+    int pad_;
+};
+// what changes from step to step: kernel arguments of the eager launch
+struct FanDyn {
+    uint32_t key[2];       // single step: the raw rng_act
+    uint32_t f_shared[3];  // derive_keys = 0: the caller's shared vector (float bits)
+    int log_index;         // row of the episode log this step writes; < 0: no log row
+};
+
+// what rp3_stages<..., PLAN = 2> takes in place of the statistics scratch: stage T's lane l writes pos[k][.][l]; the subscript
+// only lets the (never instantiated at run time, STATS = false) statistics code of the stage compile
+struct FanPos {
+    float pos[COVO_H][3][COVO_WAVE];  // 24 KiB: conflict-free stores (lane = bank), phase 2 reads them row by row
+    float unused_[1][9];
+    __device__ float (&operator[](int))[1][9] { return unused_; }
+};
+struct FanLds {
+    float4 a[COVO_H][COVO_WAVE];  // 32 KiB: the action image of the fan's one 64-sample group
+    Rp3Lds<SF_CH> rings;          // 9 KiB
+    FanPos p;
+    uint32_t dyn[12];
+    DynBlock kb[4];
+    float cost[COVO_WAVE];
+    int n[COVO_WAVE];
+};
+
+template <bool ROLL, int REWARD, int FDIST, bool BATCHED>
+__global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, const FanArgs *__restrict__ batch, const FanDyn dyn)
+{
+    FanArgs Pb;
+    if (BATCHED) {
+        Pb = batch[blockIdx.x];
+        Pb.R.state = rebase_global(P_.R.state, Pb.R.state);
+        Pb.R.pos_traj = rebase_global(P_.R.pos_traj, Pb.R.pos_traj);
+        Pb.R.vel_traj = rebase_global(P_.R.vel_traj, Pb.R.vel_traj);
+        Pb.R.f_tab = rebase_global(P_.R.f_tab, Pb.R.f_tab);
+        Pb.R.a = rebase_global(P_.R.a, Pb.R.a);
+        Pb.key_mem = rebase_global(P_.key_mem, Pb.key_mem);
+        Pb.idx = rebase_global(P_.idx, Pb.idx);
+        Pb.fan_out = rebase_global(P_.fan_out, Pb.fan_out);
+        Pb.fanlog = rebase_global(P_.fanlog, Pb.fanlog);
+    }
+    const FanArgs &P = BATCHED ? Pb : P_;
+    __shared__ FanLds S;
+    const int tid = threadIdx.x, lane = tid & (COVO_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int K = P_.K, N = P_.R.N;  // (all instances alike)
+    const bool has_fan = P_.fan_out != nullptr, has_log = P_.fanlog != nullptr && dyn.log_index >= 0;
+    const bool has_idx = P_.idx != nullptr;
+
+    // ---- phase 0
+    if (tid < 4) {
+        DynBlock &kb = S.kb[tid];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) kb.w[i] = 0u;
+        if (BATCHED) {
+            kb.w[0] = P.key_mem[0];
+            kb.w[1] = P.key_mem[1];
+        } else {
+            kb.w[0] = dyn.key[0];
+            kb.w[1] = dyn.key[1];
+            kb.w[2] = dyn.f_shared[0];
+            kb.w[3] = dyn.f_shared[1];
+            kb.w[4] = dyn.f_shared[2];
+        }
+        step_begin_derive(tid, kb, P.derive_keys, P.shared_noise_scale, S.dyn);
+    }
+    if (wave == 1) {  // the sample of every lane: lanes >= K repeat lane K - 1's
+        const int s = lane < K ? lane : K - 1;
+        int n;
+        if (has_idx) {
+            n = P.idx[s];
+            n = n < 0 ? 0 : (n > N - 1 ? N - 1 : n);
+        } else {
+            n = (int)(((long long)s * N) / K);
+        }
+        S.n[lane] = n;
+    }
+    __syncthreads();
+    {
+        const float4 *__restrict__ a4 = P.R.a;
+        const int clip = P_.R.clip;
+        for (int i = tid; i < COVO_H * COVO_WAVE; i += SF_BLOCK) {
+            const int k = i >> 6, l = i & (COVO_WAVE - 1);
+            float4 v = a4[(size_t)k * N + S.n[l]];
+            if (clip == 1) { v.x = qm::clip11_(v.x); v.y = qm::clip11_(v.y); v.z = qm::clip11_(v.z); v.w = qm::clip11_(v.w); }
+            else if (clip == 2) { v.x = qm::clip11_nan_(v.x); v.y = qm::clip11_nan_(v.y); v.z = qm::clip11_nan_(v.z); v.w = qm::clip11_nan_(v.w); }
+            S.a[k][l] = v;
+        }
+    }
+    __syncthreads();
+    RolloutArgs A = P.R;
+    A.N = COVO_WAVE;  // the image holds one full group: every lane is a sample of its own
+    A.clip = 0;
+    A.cost = nullptr;  // (PLAN = 2: stage R stores nothing)
+    A.groupmin = nullptr;
+    A.f_shared_dev = nullptr;
+    A.f_shared[0] = __uint_as_float(S.dyn[2]);
+    A.f_shared[1] = __uint_as_float(S.dyn[3]);
+    A.f_shared[2] = __uint_as_float(S.dyn[4]);
+
+    // ---- phase 1: the fan's rollouts (covo.py:227-263 for the samples n_lane)
+    float cost = 0.0f;
+    bool valid = false;
+    int n = 0;
+    rp3_stages<false, ROLL, SF_CH, -1, false, true, REWARD, FDIST, true, FanPos, COVO_H, 2>(A, S.rings, S.p, wave, 0, 0, lane,
+                                                                                             &S.a[0][0], cost, valid, n);
+    if (wave == 2) S.cost[lane] = cost;
+    __syncthreads();
+
+    // ---- phase 2: the rows
+    float *lrow = has_log ? P.fanlog + (size_t)dyn.log_index * K * COVO_FAN_FLOATS : nullptr;
+    for (int i = tid; i < K * COVO_FAN_FLOATS; i += SF_BLOCK) {
+        const int s = i / COVO_FAN_FLOATS, j = i - s * COVO_FAN_FLOATS;
+        float v;
+        if (j == 0) v = S.cost[s];
+        else if (j == 1) v = __int_as_float(S.n[s]);
+        else if (j < 4) v = 0.0f;
+        else v = S.p.pos[(j - 4) / 3][(j - 4) % 3][s];
+        if (has_fan) P.fan_out[i] = v;
+        if (has_log) lrow[i] = v;
+    }
+}
+
+// ---- host
+struct FanState {
+    void *args_dev = nullptr;  // FanArgs[COVO_MAX_ENVS]
+    std::vector<char> host;    // what args_dev holds
+};
+
+void fan_state_destroy(covo_ctx *h)
+{
+    FanState *fs = reinterpret_cast<FanState *>(h->fan_state);
+    if (!fs) return;
+    (void)hipFree(fs->args_dev);
+    delete fs;
+    h->fan_state = nullptr;
+}
+
+template <bool BATCHED>
+static int fan_go(const FanArgs &P, const FanArgs *batch, int n, const FanDyn &dyn, hipStream_t s)
+{
+#define SF_GO3(ROLL, REWARD, FDIST) hipLaunchKernelGGL((sample_fan_kernel<ROLL, REWARD, FDIST, BATCHED>), dim3(n), dim3(SF_BLOCK), 0, s, P, batch, dyn)
+#define SF_GO2(ROLL, REWARD) do { if (P.R.fdist == 0) SF_GO3(ROLL, REWARD, 0); else if (P.R.fdist == 1) SF_GO3(ROLL, REWARD, 1); else SF_GO3(ROLL, REWARD, 2); } while (0)
+#define SF_GO1(ROLL) do { if (P.R.reward == COVO_REWARD_REALWORLD) SF_GO2(ROLL, 1); else SF_GO2(ROLL, 0); } while (0)
+    if (P.R.rollover) SF_GO1(true);
+    else SF_GO1(false);
+#undef SF_GO1
+#undef SF_GO2
+#undef SF_GO3
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+static void fill_fan_args(FanArgs &P, covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const int32_t *idx, int K, float *fan_out,
+                          float *fanlog)
+{
+    std::memset(&P, 0, sizeof(P));
+    RolloutDesc ro;  // the kernel leaves no costs, minima or records
+    ro.state = d.state;
+    ro.pos_traj = d.pos_traj;
+    ro.vel_traj = d.vel_traj;
+    ro.T = d.T;
+    ro.params = d.params;
+    ro.f_tab = d.f_tab;
+    ro.a = d.a;
+    ro.N = d.N;
+    ro.discount = h->cfg.discount;
+    ro.xcd_groups = 1;
+    ro.clip = clip;
+    fill_rollout_args(P.R, ro, 1);
+    P.R.xcd_remap = 0;
+    P.key_mem = d.key_mem;
+    P.idx = idx;
+    P.fan_out = fan_out;
+    P.fanlog = fanlog;
+    P.derive_keys = d.derive_keys;
+    P.shared_noise_scale = d.shared_noise_scale;
+    P.K = K;
+}
+
+static int fan_check_tables(const PlanInstDesc *inst, int n_inst)
+{
+    for (int e = 0; e < n_inst; ++e) {
+        if (inst[e].params->disturb_kind >= COVO_DISTURB_PERIODIC && inst[e].f_tab == nullptr) {
+            covo_set_error("sample fan: disturb_kind=%d needs the step's per-step disturbance table", inst[e].params->disturb_kind);
+            return COVO_E_BADARG;
+        }
+    }
+    return 0;
+}
+
+// covo_rollout_fan: one instance, the caller's buffers and shared vector (d.derive_keys = 0), the clip covo_rollout_cost applies
+int launch_sample_fan_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const int32_t *idx, int K, float *fan_out, hipStream_t s)
+{
+    int rc = fan_check_tables(&d, 1);
+    if (rc) return rc;
+    FanArgs P;
+    fill_fan_args(P, h, d, clip, idx, K, fan_out, nullptr);
+    FanDyn dyn;
+    std::memset(&dyn, 0, sizeof(dyn));
+    dyn.log_index = -1;
+    dyn.key[0] = d.key[0];
+    dyn.key[1] = d.key[1];
+    for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &d.f_shared[i], 4);
+    return fan_go<false>(P, nullptr, 1, dyn, s);
+}
+
+// inst: n_inst instances of ONE step that has just been enqueued (launch_plan_trace's descriptors, with a and N).  The stripes
+// come from the step's own noise launch: already clipped.  batched: the argument blocks go through device memory, re-uploaded
+// (behind a stream synchronisation, outside the steady state) only when they differ from the last launch's.
+int launch_sample_fan(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s)
+{
+    const bool log = h->fanlog != nullptr && log_index >= 0;
+    if (h->fan_out == nullptr && !log) return 0;
+    const int K = h->fan_K;
+    int rc = fan_check_tables(inst, n_inst);
+    if (rc) return rc;
+    FanDyn dyn;
+    std::memset(&dyn, 0, sizeof(dyn));
+    dyn.log_index = log ? log_index : -1;
+    auto fill = [&](FanArgs &P, int e) {
+        fill_fan_args(P, h, inst[e], ROLLOUT_CLIP_TRUSTED, h->fan_idx ? h->fan_idx + (size_t)e * K : nullptr, K,
+                      h->fan_out ? h->fan_out + (size_t)e * K * COVO_FAN_FLOATS : nullptr,
+                      h->fanlog ? h->fanlog + (size_t)e * h->fanlog_stride * K * COVO_FAN_FLOATS : nullptr);
+    };
+    if (!batched) {
+        FanArgs P;
+        fill(P, 0);
+        dyn.key[0] = inst[0].key[0];
+        dyn.key[1] = inst[0].key[1];
+        for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &inst[0].f_shared[i], 4);
+        return fan_go<false>(P, nullptr, 1, dyn, s);
+    }
+    FanState *fs = reinterpret_cast<FanState *>(h->fan_state);
+    if (!fs) {
+        fs = new FanState();
+        h->fan_state = fs;
+    }
+    std::vector<char> now((size_t)n_inst * sizeof(FanArgs), 0);
+    FanArgs *pa = reinterpret_cast<FanArgs *>(now.data());
+    for (int e = 0; e < n_inst; ++e) fill(pa[e], e);
+    if (fs->host.size() != now.size() || std::memcmp(fs->host.data(), now.data(), now.size()) != 0) {
+        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old blocks are done
+        if (fs->args_dev == nullptr) {
+            fs->host.clear();
+            COVO_CHECK_HIP(hipMalloc(&fs->args_dev, (size_t)COVO_MAX_ENVS * sizeof(FanArgs)));
+        }
+        COVO_CHECK_HIP(hipMemcpy(fs->args_dev, now.data(), now.size(), hipMemcpyHostToDevice));
+        fs->host = now;
+    }
+    return fan_go<true>(pa[0], reinterpret_cast<const FanArgs *>(fs->args_dev), n_inst, dyn, s);
+}

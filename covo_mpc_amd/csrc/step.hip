@@ -442,7 +442,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                          const float *f_shared, const float *state_true, int trace_index, hipStream_t s)
 {
-    if (!covo_plan_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
     PlanInstDesc d;
     std::memset(&d, 0, sizeof(d));
@@ -452,13 +452,17 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
     d.T = args->T;
     d.params = params;
     d.a_mean = args->a_mean;
+    d.a = args->a;
+    d.N = args->n_samples;
     d.f_tab = (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr;
     d.key[0] = key0;
     d.key[1] = key1;
     for (int i = 0; i < 3; ++i) d.f_shared[i] = f_shared ? f_shared[i] : 0.0f;
     d.derive_keys = args->derive_keys;
     d.shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
-    return launch_plan_trace(h, &d, 1, false, state_true, trace_index, s);
+    const int rc = launch_plan_trace(h, &d, 1, false, state_true, trace_index, s);
+    if (rc) return rc;
+    return launch_sample_fan(h, &d, 1, false, trace_index, s);  // (the episode's row index: the fan log counts like the trace)
 }
 
 
@@ -1017,7 +1021,7 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
                             const float *states_true, int trace_index, hipStream_t s)
 {
-    if (!covo_plan_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
@@ -1031,13 +1035,17 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
         d[e].T = args->T;
         d[e].params = &params[e];
         d[e].a_mean = i.a_mean;
+        d[e].a = i.a;
+        d[e].N = args->n_samples;
         d[e].f_tab = (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
         // the instance's raw rng_act: covo-online's begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone
         d[e].key_mem = online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e;
         d[e].derive_keys = 1;
         d[e].shared_noise_scale = covo_shared_noise_scale(params[e], mode != COVO_MODE_MPPI);  // (CoVO's rollouts are deterministic)
     }
-    return launch_plan_trace(h, d, E, true, states_true, trace_index, s);
+    const int rc = launch_plan_trace(h, d, E, true, states_true, trace_index, s);
+    if (rc) return rc;
+    return launch_sample_fan(h, d, E, true, trace_index, s);
 }
 
 // test hook: the Hessians of the LAST batched step (E x 128 x 128 doubles), device -> host

@@ -267,6 +267,14 @@ def split_trace_rows(rows: np.ndarray) -> dict:
             "pos_plan": rows[..., 72:].reshape(rows.shape[:-1] + (H, 3))}
 
 
+def split_fan_rows(rows: np.ndarray) -> dict:
+    """Fan rows [.., K, 100] (include/covo_hip.h: covo_set_step_fan) -> {pos [.., K, H, 3], cost [.., K], idx [.., K] int32} (numpy;
+    pos and cost are views)."""
+    H = (rows.shape[-1] - 4) // 3
+    return {"pos": rows[..., 4:].reshape(rows.shape[:-1] + (H, 3)), "cost": rows[..., 0],
+            "idx": np.ascontiguousarray(rows[..., 1]).view(np.int32)}
+
+
 def unpack_state_row(row: np.ndarray) -> dict:
     """One packed state float32[32] (include/covo_hip.h "Data layouts") -> the EnvState3D fields it carries."""
     return {"pos": row[0:3].copy(), "vel": row[3:6].copy(), "quat": row[6:10].copy(), "omega": row[10:13].copy(),
@@ -305,6 +313,23 @@ class DeviceEpisode:
         self.n_steps = 0
         self.diag_log = None  # [T + 1, 8], allocated when a controller with compute_diag runs the episode
         self.trace = None     # [T + 1, 168], allocated when a controller with compute_plan runs the episode
+        self.fanlog = None    # [T + 1, K, 100], allocated when a controller with compute_fan runs the episode
+
+    def alloc_fan_log(self, K: int):
+        import torch
+        self.fanlog = torch.zeros((int(self.log.shape[0]), int(K), self._lib.COVO_FAN_FLOATS), dtype=torch.float32, device=self.device)
+
+    def fan_log_view(self):
+        """the rows of the fan log the next segment writes (covo_run_episode counts its rows from 0)"""
+        return self.fanlog[self.n_steps:]
+
+    def read_fan(self):
+        """-> {pos [n, K, H, 3], cost [n, K], idx [n, K]} (numpy): per enqueued step the K sampled rollouts of its fan (include/covo_hip.h:
+        covo_set_step_fan), under a controller built with compute_fan; synchronises and checks the device status like read_log."""
+        if self.fanlog is None:
+            raise RuntimeError("no fan log: run_episode under a controller built with compute_fan=K")
+        self.read_log()
+        return split_fan_rows(self.fanlog[:self.n_steps].cpu().numpy())
 
     def alloc_diag_log(self):
         import torch
@@ -420,6 +445,23 @@ class BatchedDeviceEpisode:
         self.n_steps = 0
         self.diag_log = None  # [E, T + 1, 8], allocated when a controller with compute_diag runs the episode
         self.trace = None     # [E, T + 1, 168], allocated when a controller with compute_plan runs the episode
+        self.fanlog = None    # [E, T + 1, K, 100], allocated when a controller with compute_fan runs the episode
+
+    def alloc_fan_log(self, K: int):
+        import torch
+        self.fanlog = torch.zeros((self.E, int(self.log.shape[1]), int(K), self._lib.COVO_FAN_FLOATS), dtype=torch.float32,
+                                  device=self.device)
+
+    def fan_log_view(self):
+        return self.fanlog  # (the batched drivers take the first row of a segment as log_index)
+
+    def read_fan(self):
+        """-> {pos [E, n, K, H, 3], cost [E, n, K], idx [E, n, K]} (numpy) of the enqueued steps (controller built with compute_fan);
+        synchronises and checks the device status like read_log."""
+        if self.fanlog is None:
+            raise RuntimeError("no fan log: run_episode under a controller built with compute_fan=K")
+        self.read_log()
+        return split_fan_rows(self.fanlog[:, :self.n_steps].cpu().numpy())
 
     def alloc_trace(self):
         import torch
@@ -477,11 +519,12 @@ class BatchedDeviceEpisode:
 
 
 def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H32_lam0.01", n_steps=None, seed: int = 1, device=None,
-                     verbose: bool = True, diag: bool = False, trace: bool = False):
+                     verbose: bool = True, diag: bool = False, trace: bool = False, fan=None):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]; with trace=True
-    -> (that, ep.read_trace()): every instance's states, actions and plans of the episode."""
+    -> (that, ep.read_trace()): every instance's states, actions and plans of the episode; with fan=K ep.read_fan() -- K sampled
+    rollouts of every step of every instance -- is appended to the returned tuple."""
     from .. import controllers
     rng = crandom.PRNGKey(seed)
     ks = crandom.split(rng, 3 * n_envs + 1)
@@ -491,7 +534,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     cp0 = c0.init_control_params
     b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                           sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device,
-                                          compute_diag=diag, compute_plan=trace)
+                                          compute_diag=diag, compute_plan=trace, compute_fan=fan)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
@@ -508,9 +551,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
             blind = (ess > 0.9 * N).sum(axis=1)
             print("ESS median per instance: " + " ".join(f"{v:.0f}" for v in np.median(ess, axis=1)) +
                   f"; steps with ess > 0.9 N per instance: {' '.join(str(int(v)) for v in blind)} (of {T})")
-    if trace:
-        return log[:, :, 1].mean(axis=1), ep.read_trace()
-    return log[:, :, 1].mean(axis=1)
+    out = (log[:, :, 1].mean(axis=1),) + ((ep.read_trace(),) if trace else ()) + ((ep.read_fan(),) if fan else ())
+    return out if len(out) > 1 else out[0]
 
 
 def eval_env_device(env: Quad3D, controller, total_steps=30000, num_trajs=4, seed=1, verbose=True):
@@ -607,8 +649,9 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 
 
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
-                   compute_info=True, compute_diag=False, compute_plan=False, ess_min=None):
-    """quadrotor.py:670-752.  ess_min (sampling controllers): the ESS floor, see SamplingCore."""
+                   compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None):
+    """quadrotor.py:670-752.  ess_min (sampling controllers): the ESS floor, see SamplingCore; compute_fan=K (sampling controllers): K
+    sampled rollouts of every step in info["fan_pos"] / ["fan_cost"] / ["fan_idx"], see SamplingCore."""
     import torch
 
     def parse_sample_params(param_text):
@@ -636,7 +679,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info,
-                                          compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min), control_params
+                                          compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
+                                          compute_fan=compute_fan), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -649,7 +693,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group,
                                           compute_info=compute_info, compute_diag=compute_diag,
-                                          compute_plan=compute_plan, ess_min=ess_min), control_params
+                                          compute_plan=compute_plan, ess_min=ess_min, compute_fan=compute_fan), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -659,7 +703,8 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
     (relative to the working directory): a list with one dict per step, the env state ENTERING that step (:616), up to and
     including the step whose `done` fires (`repeat_times` of them).  The dicts are keyed by EnvState3D's field names (s.__dict__,
     :656; the device handle `traj_dev` left out) plus `reward`, and -- under a controller built with compute_plan -- `u`,
-    `pos_plan` [H, 3] and `cost_plan`: the action the step applied and the controller's own plan (include/covo_hip.h).  No plotting
+    `pos_plan` [H, 3] and `cost_plan`: the action the step applied and the controller's own plan (include/covo_hip.h); under one built with compute_fan=K also
+    `fan_pos` [K, H, 3], `fan_cost` [K] and `fan_idx` [K]: K of the step's sampled rollouts around that plan.  No plotting
     (utils.plot_states, :661, stays out of scope).
     Host path (controllers without a `core` or without compute_plan, host_env=True, repeat_times > 1): the Python loop with the
     reference's per-step keys (rng, rng_act, rng_step = split(rng, 3), :617); on `done` the parameters are re-sampled and the
@@ -685,6 +730,7 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
         control_params = controller.reset(ep.state0, env_params, controller.init_control_params, rng_control)
         controller.run_episode(ep, env_params, control_params, rng, env_params.max_steps_in_episode + 1)
         tr = ep.read_trace()
+        fan = ep.read_fan() if getattr(core, "compute_fan", 0) else None
         log = ep.read_log()
         dones = np.nonzero(log[:, 3] > 0.5)[0]
         n = int(dones[0]) + 1 if len(dones) else int(log.shape[0])
@@ -693,6 +739,8 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
             d = unpack_state_row(tr["state"][k])
             d.update(pos_traj=s0.pos_traj, vel_traj=s0.vel_traj, acc_traj=s0.acc_traj, reward=float(log[k, 0]),
                      u=tr["u"][k].copy(), pos_plan=tr["pos_plan"][k].copy(), cost_plan=float(tr["cost_plan"][k]))
+            if fan is not None:
+                d.update(fan_pos=fan["pos"][k].copy(), fan_cost=fan["cost"][k].copy(), fan_idx=fan["idx"][k].copy())
             seq.append(d)
     else:
         obs, info, env_state = env.reset(rng_reset, env_params)
@@ -710,6 +758,9 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
             if isinstance(control_info, dict) and "pos_plan" in control_info:
                 d.update(u=np.array(action, copy=True), pos_plan=to_np(control_info["pos_plan"]).copy(),
                          cost_plan=float(to_np(control_info["cost_plan"])))
+            if isinstance(control_info, dict) and "fan_pos" in control_info:
+                d.update(fan_pos=to_np(control_info["fan_pos"]).copy(), fan_cost=to_np(control_info["fan_cost"]).copy(),
+                         fan_idx=to_np(control_info["fan_idx"]).copy())
             seq.append(d)
             if done:
                 rng, rng_params = crandom.split(rng)
@@ -742,6 +793,7 @@ class Args:
     disturb_type: str = "gaussian"
     name: str = ""
     host_env: bool = False  # (not in quadjax) eval with the Python env step instead of the device one
+    fan: int = 0            # (not in quadjax) render: K sampled rollouts of every step next to the plan (compute_fan); 0 = off
 
 
 def main(args: Args):
@@ -754,7 +806,7 @@ def main(args: Args):
     # (quadrotor.py:523-538), here the per-step position statistics are simply not requested
     render = args.mode == "render"
     controller, control_params = get_controller(env, args.controller, args.controller_params, compute_info=args.mode != "eval",
-                                                compute_plan=render)
+                                                compute_plan=render, compute_fan=(args.fan or None) if render else None)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)

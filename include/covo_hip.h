@@ -493,6 +493,36 @@ int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32
                                    [68..167] the step's plan row (COVO_PLAN_FLOATS) */
 int covo_set_step_plan(covo_handle_t h, float *plan, int32_t n_inst);       /* DEVICE float[n_inst][COVO_PLAN_FLOATS];  NULL = off */
 int covo_set_episode_trace(covo_handle_t h, float *trace, int32_t stride);  /* DEVICE float[n_inst][stride][COVO_TRACE_FLOATS]; NULL = off */
+/* The sample fan: K of a step's N sampled rollouts as trajectories (additive to ABI 10: COVO_HAS_SAMPLE_FAN; off by default, and
+ * off changes nothing a caller can observe).  For one instance, a step with N samples and a fan size 1 <= K <= min(COVO_FAN_MAX, N):
+ *   fan       float[K][COVO_FAN_FLOATS], row s = {cost_s, bits(int32 n_s), 0, 0, pos_s[COVO_H][3]} -- the layout of a plan row.
+ *             n_s: the local sample the row was taken from -- idx[s] clamped into [0, N) (duplicates allowed), or, with idx = NULL,
+ *             the stride (s * N) / K in integer arithmetic.  pos_s[k]: the position of sample n_s AFTER rollout step k
+ *             (covo.py:234-237's poses[k, n_s]; they keep integrating after done).  cost_s: what the rollout kernel's own stage
+ *             functions give the action stripe a[:, n_s, :] with exactly the inputs of the step's sample rollouts (noisy state,
+ *             trajectory window, covo_env_params, discount, the same disturbance as for the plan) -- equal to cost[n_s] bit for bit.
+ * One extra eager launch per step for all instances (csrc/sample_fan.hip), behind the step and the plan launch; no captured step
+ * graph changes, and every other output of a step is bit-identical with the fan attached or not.
+ * covo_rollout_fan: stateless, the arguments of covo_rollout_cost; idx = DEVICE int32[K] or NULL; fan_out = DEVICE
+ *   float[K][COVO_FAN_FLOATS].  Run it behind covo_rollout_cost on the same `a` to get the trajectories of chosen samples.
+ * covo_set_step_fan: fan = DEVICE float[n_inst][K][COVO_FAN_FLOATS], idx = DEVICE int32[n_inst][K] or NULL (read by every step's
+ *   launch: the caller may rewrite it between steps); every control step of the handle -- covo_mpc_step (all modes, staged and
+ *   fused, eager and graph), covo_mpc_step_batched, covo_mpc_step_batched_mode and the steps of the three episode drivers -- also
+ *   writes instance e's fan (a single step: instance 0); fan = NULL: off.
+ * covo_set_episode_fan: fanlog = DEVICE float[n_inst][stride][K][COVO_FAN_FLOATS] with the K (and idx) of covo_set_step_fan, which
+ *   must be called first (fan = NULL there with K > 0 keeps K and idx for the log alone); step k of an episode driver's segment
+ *   writes instance e's fan to fanlog[e][log_index + k] (covo_run_episode: log_index = 0, one instance); NULL = off.
+ * Refused before any launch, with a message that names the condition: K outside [1, COVO_FAN_MAX]; a step with n_samples < K; a
+ * batched step with more instances than n_inst; an episode segment that would leave the log; a sample-sharded step
+ * (partial_out != NULL) -- a rank's `a` holds its shard only. */
+#define COVO_HAS_SAMPLE_FAN 1
+#define COVO_FAN_FLOATS 100   /* {cost_s, bits(int32 n_s), 0, 0, pos_s[COVO_H][3]} */
+#define COVO_FAN_MAX    64
+int covo_rollout_fan(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                     const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                     const float *a, int32_t N, const int32_t *idx, int32_t K, float *fan_out, void *stream);
+int covo_set_step_fan(covo_handle_t h, float *fan, const int32_t *idx, int32_t K, int32_t n_inst);
+int covo_set_episode_fan(covo_handle_t h, float *fanlog, int32_t stride);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);
