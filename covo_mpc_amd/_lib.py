@@ -31,6 +31,9 @@ COVO_LAM_FLOATS = 4  # the ESS floor's solver row of one instance: lam_eff, 1 / 
 COVO_HAS_SAMPLE_FAN = 1
 COVO_FAN_FLOATS = 100  # a fan row: {cost_s, bits(int32 n_s), 0, 0, pos_s[H][3]} (covo_set_step_fan): the layout of a plan row
 COVO_FAN_MAX = 64      # rows of a fan: one 64-sample group of the rollout
+COVO_HAS_UPDATE_ARBITER = 1
+COVO_ARB_FLOATS = 8  # an arbiter row: {cost_softmax, cost_nominal, cost_best, cost_chosen, bits(int32 choice), bits(int32 n_best), 0, 0}
+UPDATE_MASKS = {"softmax": 0, "best": 0b110, "guarded": 0b111}  # update= of the controllers -> the arbiter's candidate mask (0: detached)
 LAM_FIELDS = ("lam_eff", "inv_lam_eff", "ess_lam0", "evaluations")
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
@@ -169,6 +172,10 @@ _SIGS = {
                                    C.c_int32, _P, C.c_int32, _P, _P]),  # the sample fan (covo_hip.h: COVO_HAS_SAMPLE_FAN)
     "covo_set_step_fan": (C.c_int, [_P, _P, _P, C.c_int32, C.c_int32]),
     "covo_set_episode_fan": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_set_step_arbiter": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),  # the update arbiter (covo_hip.h: COVO_HAS_UPDATE_ARBITER)
+    "covo_set_episode_arbiter_log": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_arbitrate": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, C.c_int32,
+                                 _P, _P, C.c_int32, _P, _P]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),
@@ -226,6 +233,14 @@ def check_fan(compute_fan, N) -> int:
     if K > int(N):
         raise ValueError(f"compute_fan={K} > N={N}: the fan takes K of the step's N samples")
     return K
+
+
+def check_update(update) -> int:
+    """update= of the controllers -> the arbiter's candidate mask (0: "softmax", nothing attached); anything but "softmax" / "best" /
+    "guarded" raises ValueError."""
+    if not isinstance(update, str) or update not in UPDATE_MASKS:
+        raise ValueError(f"update={update!r} (softmax | best | guarded)")
+    return UPDATE_MASKS[update]
 
 
 def ptr(t):

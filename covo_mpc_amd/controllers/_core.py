@@ -53,9 +53,15 @@ class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax"):
         import torch
         fan_K = _lib.check_fan(compute_fan, N)
+        arb_mask = _lib.check_update(update)
+        if arb_mask and process_group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(process_group) > 1:
+                raise NotImplementedError(f"update={update!r} on sample-sharded ranks: a rank's action and cost buffers hold its shard "
+                                          "only (covo_set_step_arbiter refuses sample-sharded steps)")
         if fan_K and process_group is not None:
             import torch.distributed as dist
             if dist.get_world_size(process_group) > 1:
@@ -184,6 +190,17 @@ class SamplingCore:
             stride = (torch.arange(fan_K, dtype=torch.int64) * self.n_local) // fan_K
             self.fan_idx = stride.to(torch.int32).reshape(1, fan_K).repeat(rows, 1).to(self.device).contiguous()
             check(self.lib.covo_set_step_fan(self.h, ptr(self.fan), ptr(self.fan_idx), fan_K, rows), "covo_set_step_fan")
+        # update = "best" / "guarded": every step ends with the update arbiter -- the softmax mean (guarded only), the shifted old mean and
+        # the best sample are rolled out with the step's own inputs and the cheapest becomes a_mean -- and leaves {cost_softmax,
+        # cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0} in self.arbiter (row e = instance e of a batched
+        # step), by one extra launch behind the step and ahead of the plan / fan launches (covo_set_step_arbiter,
+        # csrc/update_arbiter.hip); "softmax" (default): nothing attached, and that changes nothing
+        self.update_rule = update  # (self.update is the kernel-by-kernel softmax update below)
+        self.arb_mask = arb_mask
+        self.arbiter = None
+        if arb_mask:
+            self.arbiter = torch.zeros((int(diag_rows), _lib.COVO_ARB_FLOATS), **f32)
+            check(self.lib.covo_set_step_arbiter(self.h, ptr(self.arbiter), arb_mask, int(diag_rows)), "covo_set_step_arbiter")
         # ess_min: the ESS floor -- every step solves its temperature on the device from its own costs so that the weights' effective
         # sample size is at least ess_min (1 <= ess_min <= N / 2; lam stays the configured one whenever ESS(lam) >= ess_min already), and
         # leaves {lam_eff, 1 / lam_eff, ESS(lam), evaluations} in self.lam_eff (row e = instance e of a batched step)
@@ -376,6 +393,43 @@ class SamplingCore:
                                         self.stream()), "covo_rollout_fan")
         return out
 
+    def arbiter_info(self) -> dict:
+        """{"arb_cost" [3], "arb_choice", "arb_best" (0-d int32), "arb_cost_chosen"} of the last step as views of self.arbiter (no sync,
+        no copy); {} when the core was built with update="softmax"."""
+        if self.arbiter is None:
+            return {}
+        row = self.arbiter[0]
+        return {"arb_cost": row[0:3], "arb_cost_chosen": row[3], "arb_choice": row[4:5].view(self.torch.int32)[0],
+                "arb_best": row[5:6].view(self.torch.int32)[0]}
+
+    def attach_arbiter_log(self, episode, rows_left: int):
+        """Bind `episode`'s arbiter log (allocated on first use) for the segment that starts at episode.n_steps."""
+        if not self.arb_mask:
+            return
+        if getattr(episode, "arblog", None) is None:
+            episode.alloc_arbiter_log()
+        check(self.lib.covo_set_episode_arbiter_log(self.h, ptr(episode.arbiter_log_view()), int(rows_left)),
+              "covo_set_episode_arbiter_log")
+
+    def arbitrate(self, dstate, params_c, a_nominal, a_mean, mask=0b111, f_shared=None, f_steps=None, cost=None, a=None):
+        """covo_arbitrate (the stand-alone update arbiter) on self.a / self.cost (or `a` [H, N, 4] / `cost` [N]) with the inputs of
+        rollout(): the candidates `a_mean` (softmax mean), `a_nominal` and the best sample are rolled out, the cheapest one `mask`
+        enables is written into `a_mean` IN PLACE (float32 device tensor, 128 elements) -> float32 [8] row {cost_softmax,
+        cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0}."""
+        torch = self.torch
+        a = self.a if a is None else a
+        cost = self.cost if cost is None else cost
+        N = int(cost.numel())
+        for t in (a, cost, a_nominal, a_mean):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert a.numel() == COVO_H * N * 4 and a_nominal.numel() == COVO_NA and a_mean.numel() == COVO_NA
+        out = torch.empty((_lib.COVO_ARB_FLOATS,), dtype=torch.float32, device=self.device)
+        fs = (C.c_float * 3)(*[float(x) for x in f_shared]) if f_shared is not None else None
+        check(self.lib.covo_arbitrate(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                      C.byref(params_c), fs, ptr(f_steps), ptr(a), ptr(cost), N, ptr(a_nominal), ptr(a_mean),
+                                      int(mask), ptr(out), self.stream()), "covo_arbitrate")
+        return out
+
     def lam_info(self) -> dict:
         """{"lam_eff", "ess_lam0"} of the last step as 0-d views of self.lam_eff (no sync, no copy); {} when the core was built
         without ess_min."""
@@ -401,6 +455,9 @@ class SamplingCore:
         if self.compute_fan:
             raise NotImplementedError("compute_fan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")
+        if getattr(self, "arb_mask", 0):
+            raise NotImplementedError(f"update={self.update_rule!r} follows the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') updates with the softmax mean only")
         if self.compute_diag:
             raise NotImplementedError("compute_diag is formed by the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")
@@ -629,6 +686,8 @@ class SamplingCore:
         self.attach_trace(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # compute_fan: and row n_steps + k of its [T + 1, K, 100] fan log
         self.attach_fan_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
+        # update = "best" / "guarded": and row n_steps + k of its [T + 1, 8] arbiter log
+        self.attach_arbiter_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # the env step's auto-reset (base.py:22-40) is a property of the EPISODE, the model constants come from the controller
         params_c = type(params_c).from_buffer_copy(params_c)
         for f in ("reset_traj", "reset_dt", "reset_disturb_scale"):

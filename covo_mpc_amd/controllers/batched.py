@@ -29,8 +29,9 @@ class BatchedCoVOController:
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax"):
         _lib.check_fan(compute_fan, N)
+        _lib.check_update(update)
         if ess_min is not None and float(ess_min) != 0.0 and (self.MODE is not None or mode != "online"):
             raise NotImplementedError(f"ess_min={ess_min}: the ESS floor is not available for the env-batched MPPI / covo-offline step "
                                       "(one fused launch: it needs the temperature before all costs exist); "
@@ -53,7 +54,10 @@ class BatchedCoVOController:
         # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan)
+                                 compute_fan=compute_fan, update=update)
+        # update = "best" / "guarded": after a call, self.arbiter [E, 8] holds every instance's arbiter row of that step: {cost_softmax,
+        # cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0} (include/covo_hip.h); None under "softmax"
+        self.arbiter = self.core.arbiter
         # compute_fan = K: after a call, self.fan [E, K, 100] holds every instance's fan of that step: rows {cost_s, bits(n_s), 0, 0,
         # pos_s[H][3]} of the samples self.core.fan_idx [E, K] names (include/covo_hip.h)
         self.fan = self.core.fan
@@ -209,6 +213,7 @@ class BatchedCoVOController:
         self.core.attach_diag_log(episode, int(episode.log.shape[1]))  # compute_diag: rows n_steps .. of the [E, T + 1, 8] log
         self.core.attach_trace(episode, int(episode.log.shape[1]))  # compute_plan: rows n_steps .. of the [E, T + 1, 168] trace
         self.core.attach_fan_log(episode, int(episode.log.shape[1]))  # compute_fan: rows n_steps .. of the [E, T + 1, K, 100] fan log
+        self.core.attach_arbiter_log(episode, int(episode.log.shape[1]))  # update: rows n_steps .. of the [E, T + 1, 8] arbiter log
         online = self.mode == _lib.MODE_COVO_ONLINE
         fn = self.core.lib.covo_run_episode_batched if online else self.core.lib.covo_run_episode_batched_mode
         check(fn(
@@ -228,15 +233,16 @@ class BatchedMPPIController(BatchedCoVOController):
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None):
+                 ess_min=None, compute_fan=None, update: str = "softmax"):
         _lib.check_fan(compute_fan, N)
+        _lib.check_update(update)
         if float(gamma_sigma) != 0.0:
             raise NotImplementedError(f"gamma_sigma={gamma_sigma}: MPPI's covariance adaptation (mppi.py:119-125) is not batched; "
                                       "the batched fused launch needs gamma_sigma == 0 (the reference's default)")
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
                          a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                         compute_fan=compute_fan)
+                         compute_fan=compute_fan, update=update)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

@@ -114,6 +114,7 @@ int covo_destroy(covo_handle_t h)
     batch_state_destroy(h);
     plan_state_destroy(h);
     fan_state_destroy(h);
+    arbiter_state_destroy(h);
     exchange_destroy(h);
     int rc = 0;
 #define DESTROY(expr)                                                                                   \
@@ -849,6 +850,80 @@ int covo_rollout_fan(covo_handle_t h, const float *state, const float *pos_traj,
     return launch_sample_fan_one(h, d, clip, idx, K, fan_out, (hipStream_t)stream);
 }
 
+// ---- the update arbiter (update_arbiter.hip).  Like the plan's and the fan's, its launch is eager and follows the step: no captured
+// step graph changes
+int covo_set_step_arbiter(covo_handle_t h, float *rows, int32_t mask, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_arbiter: null handle");
+    if (rows == nullptr) {  // off, the log with it
+        h->arb_out = nullptr;
+        h->arb_mask = h->arb_n = 0;
+        h->arblog = nullptr;
+        h->arblog_stride = 0;
+        return 0;
+    }
+    REQUIRE(mask >= 1 && mask <= 7, "covo_set_step_arbiter: mask=%d outside [1, 7] (bit 0: softmax mean, 1: nominal, 2: best sample)", mask);
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_arbiter: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    h->arb_out = rows;
+    h->arb_mask = mask;
+    h->arb_n = n_inst;
+    return 0;
+}
+
+int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_arbiter_log: null handle");
+    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_arbiter_log: stride=%d", stride);
+    REQUIRE(log == nullptr || covo_arb_on(h), "covo_set_episode_arbiter_log: no arbiter attached: call covo_set_step_arbiter first");
+    h->arblog = log;
+    h->arblog_stride = log ? stride : 0;
+    return 0;
+}
+
+// a step for n_inst instances with the arbiter attached: the buffer has a row for each
+#define CHECK_ARBITER(h, n_inst, what)                                                                                     \
+    REQUIRE(!covo_arb_on(h) || (n_inst) <= (h)->arb_n, "%s: %d instances, the arbiter buffer (covo_set_step_arbiter) has n_inst=%d", \
+            what, (int)(n_inst), (h)->arb_n)
+#define REFUSE_SHARDED_ARBITER(h, args, what)                                                                              \
+    REQUIRE((args)->partial_out == nullptr || !covo_arb_on(h),                                                             \
+            "%s: the update arbiter (covo_set_step_arbiter) is not available for sample-sharded steps (partial_out != NULL): " \
+            "a rank's action and cost buffers hold its shard only; detach it", what)
+
+int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                   const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
+                   const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
+                   void *stream)
+{
+    REQUIRE(h, "covo_arbitrate: null handle");
+    CHECK_DEVICE(h, "covo_arbitrate");
+    REQUIRE(state && pos_traj && vel_traj && params && a && cost && a_nominal && a_mean_inout && row_out && T > 0,
+            "covo_arbitrate: bad argument");
+    REQUIRE(N > 0 && N <= h->cfg.n_local, "covo_arbitrate: N=%d outside (0, n_local=%d]", N, h->cfg.n_local);
+    REQUIRE(mask >= 1 && mask <= 7, "covo_arbitrate: mask=%d outside [1, 7] (bit 0: softmax mean, 1: nominal, 2: best sample)", mask);
+    CHECK_MODEL(params, "covo_arbitrate");
+    REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_arbitrate: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
+            params->disturb_kind);
+    PlanInstDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a = a;
+    d.N = N;
+    d.cost = cost;
+    d.a_nominal = a_nominal;
+    d.a_mean = a_mean_inout;
+    d.a_mean_out = a_mean_inout;
+    d.f_tab = f_disturb_steps;
+    for (int i = 0; i < 3; ++i) d.f_shared[i] = f_disturb_shared ? f_disturb_shared[i] : 0.0f;
+    d.derive_keys = 0;  // the shared vector is the caller's
+    RolloutClip clip = ROLLOUT_CLIP_TRUSTED;  // as covo_rollout_cost treats the stripes
+    if ((h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) == 0) clip = covo_propagate_nan(h) ? ROLLOUT_CLIP_REAPPLY_NAN : ROLLOUT_CLIP_REAPPLY;
+    return launch_update_arbiter_one(h, d, clip, mask, row_out, (hipStream_t)stream);
+}
+
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)
 {
     REQUIRE(h && out, "covo_debug_sigma_workspace: bad argument");
@@ -929,6 +1004,10 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     CHECK_FAN(h, args->n_samples, 1, "covo_run_episode");
     REQUIRE(h->fanlog == nullptr || n_steps <= h->fanlog_stride, "covo_run_episode: %d steps, the episode fan log "
             "(covo_set_episode_fan) has %d rows", n_steps, h->fanlog_stride);
+    REFUSE_SHARDED_ARBITER(h, args, "covo_run_episode");
+    CHECK_ARBITER(h, 1, "covo_run_episode");
+    REQUIRE(h->arblog == nullptr || n_steps <= h->arblog_stride, "covo_run_episode: %d steps, the episode arbiter log "
+            "(covo_set_episode_arbiter_log) has %d rows", n_steps, h->arblog_stride);
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -1085,6 +1164,10 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     REQUIRE(h->fanlog == nullptr || (log_index >= 0 && log_index + n_steps <= h->fanlog_stride),
             "%s: episode fan log rows [%d, %d) outside [0, %d) (covo_set_episode_fan)", what, log_index, log_index + n_steps,
             h->fanlog_stride);
+    CHECK_ARBITER(h, E, what);
+    REQUIRE(h->arblog == nullptr || (log_index >= 0 && log_index + n_steps <= h->arblog_stride),
+            "%s: episode arbiter log rows [%d, %d) outside [0, %d) (covo_set_episode_arbiter_log)", what, log_index,
+            log_index + n_steps, h->arblog_stride);
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -1148,6 +1231,7 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     CHECK_DIAG(h, args->n_envs, "covo_mpc_step_batched");
     CHECK_PLAN(h, args->n_envs, "covo_mpc_step_batched");
     CHECK_FAN(h, args->n_samples, args->n_envs, "covo_mpc_step_batched");
+    CHECK_ARBITER(h, args->n_envs, "covo_mpc_step_batched");
     if ((rc = covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream))) return rc;
     return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, (hipStream_t)stream);
 }
@@ -1164,6 +1248,7 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     CHECK_DIAG(h, args->base.n_envs, "covo_mpc_step_batched_mode");
     CHECK_PLAN(h, args->base.n_envs, "covo_mpc_step_batched_mode");
     CHECK_FAN(h, args->base.n_samples, args->base.n_envs, "covo_mpc_step_batched_mode");
+    CHECK_ARBITER(h, args->base.n_envs, "covo_mpc_step_batched_mode");
     rc = args->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream)
                                              : covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
     if (rc) return rc;
@@ -1231,6 +1316,8 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
     REFUSE_SHARDED_PLAN(h, args, "covo_mpc_step");
     REFUSE_SHARDED_FAN(h, args, "covo_mpc_step");
     CHECK_FAN(h, args->n_samples, 1, "covo_mpc_step");
+    REFUSE_SHARDED_ARBITER(h, args, "covo_mpc_step");
+    CHECK_ARBITER(h, 1, "covo_mpc_step");
     REFUSE_SHARDED_ESS_FLOOR(h, args, "covo_mpc_step");
     CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_mpc_step");
     const int rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);

@@ -72,12 +72,19 @@ struct covo_ctx {
     float *lam_out;           // caller's [lam_n][COVO_LAM_FLOATS]: instance e's solver row of every step; null: lam_own
     int lam_n;
     float *lam_own;           // [COVO_MAX_ENVS][COVO_LAM_FLOATS]
+    // the update arbiter (covo_set_step_arbiter / covo_set_episode_arbiter_log; update_arbiter.hip); arb_out null: off
+    float *arb_out;           // caller's [arb_n][COVO_ARB_FLOATS]: instance e's arbiter row of every step
+    int arb_mask, arb_n;      // enabled candidates (bits 0..2), rows of arb_out
+    float *arblog;            // caller's [n_inst][arblog_stride][COVO_ARB_FLOATS]: the episode drivers' steps write their rows there
+    int arblog_stride;
+    void *arb_state;          // ArbState (update_arbiter.hip): a batched step's argument blocks and nominals on the device
 };
 // where the solver of this handle's steps writes the instances' temperatures (null: no floor) and for how many instances
 static inline float *covo_lam_target(const covo_ctx *h) { return h->ess_min > 0.0f ? (h->lam_out ? h->lam_out : h->lam_own) : nullptr; }
 static inline int covo_lam_capacity(const covo_ctx *h) { return h->lam_out ? h->lam_n : COVO_MAX_ENVS; }
 static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->trace != nullptr; }
 static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->fanlog != nullptr; }
+static inline bool covo_arb_on(const covo_ctx *h) { return h->arb_out != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->diag_log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->diag_log ? COVO_MAX_ENVS : 0); }
@@ -425,8 +432,11 @@ struct PlanInstDesc {
     int T;
     const covo_env_params *params;
     const float *a_mean;      // [128] the mean the step leaves
-    const float *a;           // [H][N][4] the step's action stripes (the sample fan)
+    const float *a;           // [H][N][4] the step's action stripes (the sample fan, the update arbiter)
     int N;
+    const float *cost;        // [N] the step's costs (the update arbiter)
+    const float *a_nominal;   // [128] the shifted mean the step sampled around (the update arbiter)
+    float *a_mean_out;        // a_mean, writable: the arbiter commits its choice there
     const float *f_tab;       // the step's per-step disturbance table [H][4] (periodic / sin / drag / mixed), else null
     const uint32_t *key_mem;
     uint32_t key[2];
@@ -442,6 +452,14 @@ void plan_state_destroy(covo_ctx *h);
 int launch_sample_fan(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s);
 int launch_sample_fan_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const int32_t *idx, int K, float *fan_out, hipStream_t s);
 void fan_state_destroy(covo_ctx *h);
+// update_arbiter.hip: the arbiter of the step that has just been enqueued (no-op with nothing attached), ahead of the plan and fan
+// launches, which then see the arbitrated mean; log_index as for the fan.  launch_update_arbiter_one: covo_arbitrate.
+// launch_arbiter_nominal: shift(a_mean) of n_inst instances into the handle's nominal buffer (a_mean null: only its address) -- the
+// env-batched fused step keeps its shifted mean in LDS, so the nominal is formed ahead of it
+int launch_update_arbiter(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s);
+int launch_update_arbiter_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, int mask, float *row_out, hipStream_t s);
+int launch_arbiter_nominal(covo_ctx *h, const float *a_mean, int n_inst, hipStream_t s, const float **nominal_out);
+void arbiter_state_destroy(covo_ctx *h);
 // step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
 // states_true + trace_index >= 0: an episode driver's step, which also writes its trace row
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,

@@ -113,6 +113,7 @@ __device__ __forceinline__ float rp3_atan2abs(float y, float x)
 //   1 (plan_trace.hip)  lane 0 only, lds_st.pos[k][0..2]: the one sample of a plan rollout
 //   2 (sample_fan.hip)  every lane, lds_st.pos[k][0..2][lane]: the 64 samples of a fan; stage R then leaves the costs to its
 //                       caller (`cost`) instead of storing them to A.cost / A.groupmin
+//   3 (update_arbiter.hip)  no positions at all (`lds_st` is a dummy); the costs go back to the caller as with 2
 template <bool DISC1, bool ROLL, int CH, int ONLY, bool STATS, bool KEEP_ALL, int REWARD, int FDIST, bool A_LDS, class StatsLds,
           int KSTEPS = COVO_H, int PLAN = 0>
 __device__ __forceinline__ void rp3_stages(const RolloutArgs &A, Rp3Lds<CH> &lds, StatsLds &lds_st, const int role, const int gsub,
@@ -429,7 +430,7 @@ __device__ __forceinline__ void rp3_stages(const RolloutArgs &A, Rp3Lds<CH> &lds
     }
     RP3_FLUSH(2);
     cost = -acc;  // covo.py:263
-    if constexpr (PLAN != 2) {
+    if constexpr (PLAN < 2) {
         if (valid) A.cost[n] = cost;
         if (A.groupmin != nullptr) {
             const float wm = wave_min(valid ? cost : __builtin_inff());

@@ -442,7 +442,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                          const float *f_shared, const float *state_true, int trace_index, hipStream_t s)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
     PlanInstDesc d;
     std::memset(&d, 0, sizeof(d));
@@ -454,14 +454,18 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
     d.a_mean = args->a_mean;
     d.a = args->a;
     d.N = args->n_samples;
+    d.cost = args->cost;
+    d.a_nominal = args->a_mean_shift ? args->a_mean_shift : (st ? st->a_mean_shift : nullptr);
+    d.a_mean_out = args->a_mean;
     d.f_tab = (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr;
     d.key[0] = key0;
     d.key[1] = key1;
     for (int i = 0; i < 3; ++i) d.f_shared[i] = f_shared ? f_shared[i] : 0.0f;
     d.derive_keys = args->derive_keys;
     d.shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
-    const int rc = launch_plan_trace(h, &d, 1, false, state_true, trace_index, s);
+    int rc = launch_update_arbiter(h, &d, 1, false, trace_index, s);  // first: the plan, the trace's u and the env step see its mean
     if (rc) return rc;
+    if ((rc = launch_plan_trace(h, &d, 1, false, state_true, trace_index, s))) return rc;
     return launch_sample_fan(h, &d, 1, false, trace_index, s);  // (the episode's row index: the fan log counts like the trace)
 }
 
@@ -975,6 +979,10 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
                                  hipStream_t s)
 {
     const int E = m->base.n_envs, N = m->base.n_samples, ng = (N + COVO_WAVE - 1) / COVO_WAVE;
+    if (covo_arb_on(h)) {  // the update arbiter's nominal: the fused launch keeps its shifted mean in LDS only
+        const int rc = launch_arbiter_nominal(h, m->base.a_mean, E, s, nullptr);
+        if (rc) return rc;
+    }
     step_sync_epoch(h);
     BatchSmall *q = &batch_state(h)->small;
     const bool same = q->cache.have_key && q->n_envs == E && std::memcmp(&q->key, m, sizeof(*m)) == 0 && q->stream == s &&
@@ -1021,12 +1029,17 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
                             const float *states_true, int trace_index, hipStream_t s)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
     PlanInstDesc d[COVO_MAX_ENVS];
     std::memset(d, 0, sizeof(d));
+    const float *nominal = nullptr;  // the update arbiter's: covo-online's begin launch leaves it, the fused launch's was formed ahead of it
+    if (covo_arb_on(h)) {
+        if (online) nominal = b->a_mean_shift;
+        else if (int rc = launch_arbiter_nominal(h, nullptr, E, s, &nominal)) return rc;
+    }
     for (int e = 0; e < E; ++e) {
         const BatchInst i = batch_inst(*args, e);
         d[e].state = i.state;
@@ -1037,14 +1050,18 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
         d[e].a_mean = i.a_mean;
         d[e].a = i.a;
         d[e].N = args->n_samples;
+        d[e].cost = i.cost;
+        d[e].a_nominal = nominal ? nominal + (size_t)e * COVO_NA : nullptr;
+        d[e].a_mean_out = i.a_mean;
         d[e].f_tab = (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
         // the instance's raw rng_act: covo-online's begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone
         d[e].key_mem = online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e;
         d[e].derive_keys = 1;
         d[e].shared_noise_scale = covo_shared_noise_scale(params[e], mode != COVO_MODE_MPPI);  // (CoVO's rollouts are deterministic)
     }
-    const int rc = launch_plan_trace(h, d, E, true, states_true, trace_index, s);
+    int rc = launch_update_arbiter(h, d, E, true, trace_index, s);  // first: the plan, the trace's u and the env step see its mean
     if (rc) return rc;
+    if ((rc = launch_plan_trace(h, d, E, true, states_true, trace_index, s))) return rc;
     return launch_sample_fan(h, d, E, true, trace_index, s);
 }
 

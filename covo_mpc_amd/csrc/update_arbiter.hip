@@ -1,0 +1,383 @@
+// update_arbiter.hip -- the update arbiter of a control step (gfx950): the step commits the best of {softmax mean, old plan, best
+// sample} instead of the softmax mean unchecked (covo_arbitrate / covo_set_step_arbiter / covo_set_episode_arbiter_log,
+// include/covo_hip.h).
+//
+// Three candidates per instance, each [H][4]:
+//   0  the softmax mean the step has just left in a_mean (covo.py:275, mppi.py:116)
+//   1  the nominal: the shifted mean the step sampled around (covo.py:201-203)
+//   2  the best sample a[:, n*, :], n* = argmin_n cost[n] over the step's own costs (NaN skipped, equal costs -> lowest n; all NaN:
+//      the candidate is absent, n* = -1)
+// Candidates 0 and 1 are clipped to [-1, 1] for evaluation only (as the plan is, plan_trace.hip); every candidate is rolled out by
+// the rollout's own stage functions with exactly the inputs the step's sample rollouts had.  mask bit c enables candidate c; a
+// masked-out or absent candidate costs +inf, a NaN cost counts as +inf, equal costs resolve to the lowest candidate, all +inf -> 0.
+// Choice 0 leaves a_mean alone, 1 writes the nominal (unclipped), 2 writes a[:, n*, :].
+//
+// One launch, one workgroup of three waves per instance, eager, behind the step and ahead of the plan / fan launches:
+//   phase 0  the per-step scalars from the raw controller key (step_begin.hpp: step_begin_derive); the argmin over cost[0..N): 16-byte
+//            loads where aligned, one 64-bit key {order-preserving cost bits, index} per sample so that one `min` carries the
+//            tie-break, reduced in the wave (wave_reduce.hpp) and across the three waves through LDS; the LDS action image [H][64]
+//            float4: lane 0 = clip(candidate 0), lane 1 = clip(candidate 1), lanes >= 2 = candidate 2
+//   phase 1  the rollout's three stage waves on the image (rollout_pipe.hpp: rp3_stages with A_LDS, N = 64, the general discount
+//            path as in plan_trace.hip; PLAN = 3: no positions, stage R hands its costs back)
+//   phase 2  one lane decides; the workgroup writes the chosen candidate's 128 floats into a_mean (nothing for choice 0) and the
+//            arbiter row {cost_softmax, cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0}.
+// The row index of the episode log travels as a kernel argument: nothing is captured, no step graph changes.  BATCHED: workgroup e
+// takes its argument block from device memory (pointers through rebase_global, as sample_fan_kernel does).
+#include <cstring>
+#include <vector>
+#include "rollout_common.hpp"
+#include "step_begin.hpp"
+#include "wave_reduce.hpp"
+
+constexpr int UA_BLOCK = 3 * COVO_WAVE;
+constexpr int UA_CH = 2;
+
+struct ArbArgs {
+    RolloutArgs R;            // the step's sample rollout: noisy state, trajectories, model, discount, disturbance table, a and N;
+                              // R.clip: how phase 0 clips candidate 2's stripe (the stages then trust the image)
+    const float *cost;        // [N] the step's costs
+    const float *a_nominal;   // [128] the shifted mean the step sampled around
+    float *a_mean;            // [128] in: the softmax mean; out: the chosen candidate
+    const uint32_t *key_mem;  // the raw rng_act of the step in device memory (batched steps), or null: ArbDyn's
+    float *row_out;           // this instance's [COVO_ARB_FLOATS] of the arbiter buffer, or null
+    float *arblog;            // this instance's [stride][COVO_ARB_FLOATS] of the episode log, or null
+    int derive_keys;
+    float shared_noise_scale;
+    int mask;
+    int nanp;
+};
+// what changes from step to step: kernel arguments of the eager launch
+struct ArbDyn {
+    uint32_t key[2];       // single step: the raw rng_act
+    uint32_t f_shared[3];  // derive_keys = 0: the caller's shared vector (float bits)
+    int log_index;         // row of the episode log this step writes; < 0: no log row
+};
+
+// what rp3_stages<..., PLAN = 3> takes in place of the statistics scratch: never touched; the subscript only lets the (never
+// instantiated at run time, STATS = false) statistics code of the stage compile
+struct ArbNoPos {
+    float unused_[1][9];
+    __device__ float (&operator[](int))[1][9] { return unused_; }
+};
+struct ArbLds {
+    float4 a[COVO_H][COVO_WAVE];  // 32 KiB: the action image of the one 64-sample group
+    Rp3Lds<UA_CH> rings;          // 9 KiB
+    ArbNoPos p;
+    float4 raw[3][COVO_H];        // the candidates as they are committed (unclipped)
+    uint32_t dyn[12];
+    DynBlock kb[4];
+    unsigned long long red[3];
+    float cost[COVO_WAVE];
+    int choice;
+};
+
+// the argmin key of sample i: cost bits in an order-preserving unsigned form above the index; NaN -> the largest key
+__device__ __forceinline__ unsigned long long arb_key(float v, int i)
+{
+    if (!(v == v)) return ~0ull;
+    if (v == 0.0f) v = 0.0f;  // -0 and +0 are one cost
+    uint32_t u = __float_as_uint(v);
+    u = (u >> 31) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)u << 32) | (uint32_t)i;
+}
+__device__ __forceinline__ unsigned long long arb_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+template <bool ROLL, int REWARD, int FDIST, bool BATCHED>
+__global__ __launch_bounds__(UA_BLOCK) void update_arbiter_kernel(const ArbArgs P_, const ArbArgs *__restrict__ batch, const ArbDyn dyn)
+{
+    ArbArgs Pb;
+    if (BATCHED) {
+        Pb = batch[blockIdx.x];
+        Pb.R.state = rebase_global(P_.R.state, Pb.R.state);
+        Pb.R.pos_traj = rebase_global(P_.R.pos_traj, Pb.R.pos_traj);
+        Pb.R.vel_traj = rebase_global(P_.R.vel_traj, Pb.R.vel_traj);
+        Pb.R.f_tab = rebase_global(P_.R.f_tab, Pb.R.f_tab);
+        Pb.R.a = rebase_global(P_.R.a, Pb.R.a);
+        Pb.cost = rebase_global(P_.cost, Pb.cost);
+        Pb.a_nominal = rebase_global(P_.a_nominal, Pb.a_nominal);
+        Pb.a_mean = rebase_global(P_.a_mean, Pb.a_mean);
+        Pb.key_mem = rebase_global(P_.key_mem, Pb.key_mem);
+        Pb.row_out = rebase_global(P_.row_out, Pb.row_out);
+        Pb.arblog = rebase_global(P_.arblog, Pb.arblog);
+    }
+    const ArbArgs &P = BATCHED ? Pb : P_;
+    __shared__ ArbLds S;
+    const int tid = threadIdx.x, lane = tid & (COVO_WAVE - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int N = P_.R.N, mask = P_.mask;  // (all instances alike)
+    const bool has_row = P_.row_out != nullptr, has_log = P_.arblog != nullptr && dyn.log_index >= 0;
+
+    // ---- phase 0
+    if (tid < 4) {
+        DynBlock &kb = S.kb[tid];
+#pragma unroll
+        for (int i = 0; i < 12; ++i) kb.w[i] = 0u;
+        if (BATCHED) {
+            kb.w[0] = P.key_mem[0];
+            kb.w[1] = P.key_mem[1];
+        } else {
+            kb.w[0] = dyn.key[0];
+            kb.w[1] = dyn.key[1];
+            kb.w[2] = dyn.f_shared[0];
+            kb.w[3] = dyn.f_shared[1];
+            kb.w[4] = dyn.f_shared[2];
+        }
+        step_begin_derive(tid, kb, P.derive_keys, P.shared_noise_scale, S.dyn);
+    }
+    {  // the argmin of the step's costs
+        const float *__restrict__ c = P.cost;
+        int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(c) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte line
+        head = head < N ? head : N;
+        const int nb = (N - head) >> 2, tail = head + 4 * nb;
+        unsigned long long best = ~0ull;
+        if (tid < head) best = arb_key(c[tid], tid);
+        const float4 *__restrict__ c4 = reinterpret_cast<const float4 *>(c + head);
+        constexpr int UA_INFLIGHT = 8;  // 16-byte loads a lane issues before it looks at the first: one workgroup has to cover the latency itself
+        const float qnan = __builtin_nanf("");
+        for (int j0 = tid; j0 < nb; j0 += UA_BLOCK * UA_INFLIGHT) {
+            float4 v[UA_INFLIGHT];
+#pragma unroll
+            for (int u = 0; u < UA_INFLIGHT; ++u) {
+                const int j = j0 + u * UA_BLOCK;
+                v[u] = j < nb ? c4[j] : make_float4(qnan, qnan, qnan, qnan);
+            }
+#pragma unroll
+            for (int u = 0; u < UA_INFLIGHT; ++u) {
+                const int i = head + 4 * (j0 + u * UA_BLOCK);
+                best = arb_min(best, arb_min(arb_min(arb_key(v[u].x, i), arb_key(v[u].y, i + 1)),
+                                             arb_min(arb_key(v[u].z, i + 2), arb_key(v[u].w, i + 3))));
+            }
+        }
+        if (tail + tid < N) best = arb_min(best, arb_key(c[tail + tid], tail + tid));
+        best = wr::wave64_allmin_u64(best);
+        if (lane == 0) S.red[wave] = best;
+    }
+    __syncthreads();
+    const unsigned long long best = arb_min(S.red[0], arb_min(S.red[1], S.red[2]));
+    const int n_best = best == ~0ull ? -1 : (int)(uint32_t)best;
+    {
+        const float4 *__restrict__ am4 = reinterpret_cast<const float4 *>(P.a_mean);
+        const float4 *__restrict__ nom4 = reinterpret_cast<const float4 *>(P.a_nominal);
+        const float4 *__restrict__ a4 = P.R.a;
+        const int clip = P_.R.clip, nanp = P_.nanp;
+        for (int i = tid; i < COVO_H * COVO_WAVE; i += UA_BLOCK) {
+            const int k = i >> 6, l = i & (COVO_WAVE - 1);
+            float4 v;
+            if (l == 0) v = am4[k];
+            else if (l == 1) v = nom4[k];
+            else if (n_best >= 0) v = a4[(size_t)k * N + n_best];
+            else v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+            if (l < 3) S.raw[l][k] = v;
+            const int how = l < 2 ? (nanp ? 2 : 1) : clip;
+            if (how == 1) { v.x = qm::clip11_(v.x); v.y = qm::clip11_(v.y); v.z = qm::clip11_(v.z); v.w = qm::clip11_(v.w); }
+            else if (how == 2) { v.x = qm::clip11_nan_(v.x); v.y = qm::clip11_nan_(v.y); v.z = qm::clip11_nan_(v.z); v.w = qm::clip11_nan_(v.w); }
+            S.a[k][l] = v;
+        }
+    }
+    __syncthreads();
+    RolloutArgs A = P.R;
+    A.N = COVO_WAVE;  // the image holds one full group: every lane is a sample of its own
+    A.clip = 0;
+    A.cost = nullptr;  // (PLAN = 3: stage R stores nothing)
+    A.groupmin = nullptr;
+    A.f_shared_dev = nullptr;
+    A.f_shared[0] = __uint_as_float(S.dyn[2]);
+    A.f_shared[1] = __uint_as_float(S.dyn[3]);
+    A.f_shared[2] = __uint_as_float(S.dyn[4]);
+
+    // ---- phase 1: the candidates' rollouts (covo.py:227-263)
+    float cost = 0.0f;
+    bool valid = false;
+    int n = 0;
+    rp3_stages<false, ROLL, UA_CH, -1, false, true, REWARD, FDIST, true, ArbNoPos, COVO_H, 3>(A, S.rings, S.p, wave, 0, 0, lane,
+                                                                                               &S.a[0][0], cost, valid, n);
+    if (wave == 2) S.cost[lane] = cost;
+    __syncthreads();
+
+    // ---- phase 2: the decision, the mean, the row
+    float *lrow = has_log ? P.arblog + (size_t)dyn.log_index * COVO_ARB_FLOATS : nullptr;
+    if (tid == 0) {
+        const float inf = __builtin_inff();
+        float c[3];
+        c[0] = (mask & 1) ? S.cost[0] : inf;
+        c[1] = (mask & 2) ? S.cost[1] : inf;
+        c[2] = ((mask & 4) && n_best >= 0) ? S.cost[2] : inf;
+        int choice = 0;
+        float cb = inf;
+#pragma unroll
+        for (int q = 0; q < 3; ++q) {
+            if (c[q] < cb) {  // (a NaN cost never wins; equal costs keep the lower candidate)
+                cb = c[q];
+                choice = q;
+            }
+        }
+        S.choice = choice;
+        const float row[COVO_ARB_FLOATS] = {c[0], c[1], c[2], c[choice], __int_as_float(choice), __int_as_float(n_best), 0.0f, 0.0f};
+#pragma unroll
+        for (int j = 0; j < COVO_ARB_FLOATS; ++j) {
+            if (has_row) P.row_out[j] = row[j];
+            if (has_log) lrow[j] = row[j];
+        }
+    }
+    __syncthreads();
+    const int choice = S.choice;
+    if (choice != 0 && tid < COVO_H) reinterpret_cast<float4 *>(P.a_mean)[tid] = S.raw[choice][tid];
+}
+
+// the nominal of the env-batched fused step (step_small.hip keeps its shifted mean in LDS only): shift(a_mean) (covo.py:201-203)
+// per instance, ahead of the step
+__global__ void arbiter_nominal_kernel(const float *__restrict__ a_mean, float *__restrict__ nominal)
+{
+    const int e = blockIdx.x, i = threadIdx.x;
+    nominal[e * COVO_NA + i] = (i < COVO_NA - COVO_DU) ? a_mean[e * COVO_NA + i + COVO_DU] : a_mean[e * COVO_NA + i];
+}
+
+// ---- host
+struct ArbState {
+    void *args_dev = nullptr;   // ArbArgs[COVO_MAX_ENVS]
+    float *nominal = nullptr;   // [COVO_MAX_ENVS][128]
+    std::vector<char> host;     // what args_dev holds
+};
+
+static ArbState *arb_state(covo_ctx *h)
+{
+    ArbState *as = reinterpret_cast<ArbState *>(h->arb_state);
+    if (!as) {
+        as = new ArbState();
+        h->arb_state = as;
+    }
+    return as;
+}
+
+void arbiter_state_destroy(covo_ctx *h)
+{
+    ArbState *as = reinterpret_cast<ArbState *>(h->arb_state);
+    if (!as) return;
+    (void)hipFree(as->args_dev);
+    (void)hipFree(as->nominal);
+    delete as;
+    h->arb_state = nullptr;
+}
+
+int launch_arbiter_nominal(covo_ctx *h, const float *a_mean, int n_inst, hipStream_t s, const float **nominal_out)
+{
+    ArbState *as = arb_state(h);
+    if (as->nominal == nullptr) COVO_CHECK_HIP(hipMalloc(&as->nominal, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(float)));
+    if (a_mean != nullptr) {
+        hipLaunchKernelGGL(arbiter_nominal_kernel, dim3(n_inst), dim3(COVO_NA), 0, s, a_mean, as->nominal);
+        COVO_CHECK_HIP(hipGetLastError());
+    }
+    if (nominal_out) *nominal_out = as->nominal;
+    return 0;
+}
+
+template <bool BATCHED>
+static int arb_go(const ArbArgs &P, const ArbArgs *batch, int n, const ArbDyn &dyn, hipStream_t s)
+{
+#define UA_GO3(ROLL, REWARD, FDIST) hipLaunchKernelGGL((update_arbiter_kernel<ROLL, REWARD, FDIST, BATCHED>), dim3(n), dim3(UA_BLOCK), 0, s, P, batch, dyn)
+#define UA_GO2(ROLL, REWARD) do { if (P.R.fdist == 0) UA_GO3(ROLL, REWARD, 0); else if (P.R.fdist == 1) UA_GO3(ROLL, REWARD, 1); else UA_GO3(ROLL, REWARD, 2); } while (0)
+#define UA_GO1(ROLL) do { if (P.R.reward == COVO_REWARD_REALWORLD) UA_GO2(ROLL, 1); else UA_GO2(ROLL, 0); } while (0)
+    if (P.R.rollover) UA_GO1(true);
+    else UA_GO1(false);
+#undef UA_GO1
+#undef UA_GO2
+#undef UA_GO3
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
+}
+
+static void fill_arb_args(ArbArgs &P, covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, int mask, float *row_out, float *arblog)
+{
+    std::memset(&P, 0, sizeof(P));
+    RolloutDesc ro;  // the kernel leaves no costs, minima or records
+    ro.state = d.state;
+    ro.pos_traj = d.pos_traj;
+    ro.vel_traj = d.vel_traj;
+    ro.T = d.T;
+    ro.params = d.params;
+    ro.f_tab = d.f_tab;
+    ro.a = d.a;
+    ro.N = d.N;
+    ro.discount = h->cfg.discount;
+    ro.xcd_groups = 1;
+    ro.clip = clip;
+    fill_rollout_args(P.R, ro, 1);
+    P.R.xcd_remap = 0;
+    P.cost = d.cost;
+    P.a_nominal = d.a_nominal;
+    P.a_mean = d.a_mean_out;
+    P.key_mem = d.key_mem;
+    P.row_out = row_out;
+    P.arblog = arblog;
+    P.derive_keys = d.derive_keys;
+    P.shared_noise_scale = d.shared_noise_scale;
+    P.mask = mask;
+    P.nanp = covo_propagate_nan(h) ? 1 : 0;
+}
+
+static int arb_check_tables(const PlanInstDesc *inst, int n_inst)
+{
+    for (int e = 0; e < n_inst; ++e) {
+        if (inst[e].params->disturb_kind >= COVO_DISTURB_PERIODIC && inst[e].f_tab == nullptr) {
+            covo_set_error("update arbiter: disturb_kind=%d needs the step's per-step disturbance table", inst[e].params->disturb_kind);
+            return COVO_E_BADARG;
+        }
+    }
+    return 0;
+}
+
+// covo_arbitrate: one instance, the caller's buffers and shared vector (d.derive_keys = 0), the clip covo_rollout_cost applies
+int launch_update_arbiter_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, int mask, float *row_out, hipStream_t s)
+{
+    int rc = arb_check_tables(&d, 1);
+    if (rc) return rc;
+    ArbArgs P;
+    fill_arb_args(P, h, d, clip, mask, row_out, nullptr);
+    ArbDyn dyn;
+    std::memset(&dyn, 0, sizeof(dyn));
+    dyn.log_index = -1;
+    dyn.key[0] = d.key[0];
+    dyn.key[1] = d.key[1];
+    for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &d.f_shared[i], 4);
+    return arb_go<false>(P, nullptr, 1, dyn, s);
+}
+
+// inst: n_inst instances of ONE step that has just been enqueued (launch_plan_trace's descriptors, with a, N, cost, a_nominal and
+// a_mean_out).  The stripes come from the step's own noise launch: already clipped.  batched: the argument blocks go through device
+// memory, re-uploaded (behind a stream synchronisation, outside the steady state) only when they differ from the last launch's.
+int launch_update_arbiter(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s)
+{
+    if (!covo_arb_on(h)) return 0;
+    const bool log = h->arblog != nullptr && log_index >= 0;
+    int rc = arb_check_tables(inst, n_inst);
+    if (rc) return rc;
+    ArbDyn dyn;
+    std::memset(&dyn, 0, sizeof(dyn));
+    dyn.log_index = log ? log_index : -1;
+    auto fill = [&](ArbArgs &P, int e) {
+        fill_arb_args(P, h, inst[e], ROLLOUT_CLIP_TRUSTED, h->arb_mask, h->arb_out + (size_t)e * COVO_ARB_FLOATS,
+                      h->arblog ? h->arblog + (size_t)e * h->arblog_stride * COVO_ARB_FLOATS : nullptr);
+    };
+    if (!batched) {
+        ArbArgs P;
+        fill(P, 0);
+        dyn.key[0] = inst[0].key[0];
+        dyn.key[1] = inst[0].key[1];
+        for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &inst[0].f_shared[i], 4);
+        return arb_go<false>(P, nullptr, 1, dyn, s);
+    }
+    ArbState *as = arb_state(h);
+    std::vector<char> now((size_t)n_inst * sizeof(ArbArgs), 0);
+    ArbArgs *pa = reinterpret_cast<ArbArgs *>(now.data());
+    for (int e = 0; e < n_inst; ++e) fill(pa[e], e);
+    if (as->host.size() != now.size() || std::memcmp(as->host.data(), now.data(), now.size()) != 0) {
+        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old blocks are done
+        if (as->args_dev == nullptr) {
+            as->host.clear();
+            COVO_CHECK_HIP(hipMalloc(&as->args_dev, (size_t)COVO_MAX_ENVS * sizeof(ArbArgs)));
+        }
+        COVO_CHECK_HIP(hipMemcpy(as->args_dev, now.data(), now.size(), hipMemcpyHostToDevice));
+        as->host = now;
+    }
+    return arb_go<true>(pa[0], reinterpret_cast<const ArbArgs *>(as->args_dev), n_inst, dyn, s);
+}

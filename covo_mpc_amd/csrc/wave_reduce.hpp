@@ -76,6 +76,33 @@ __device__ __forceinline__ double wave64_allmax(double v)
     const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
     return fmax(__hiloint2double((int)rh[0], (int)rl[0]), __hiloint2double((int)rh[1], (int)rl[1]));
 }
+// every lane of the wave receives the wave minimum of an unsigned 64-bit key (same data path as wave64_allsum)
+template <int CTRL>
+__device__ __forceinline__ unsigned long long dpp_u64(unsigned long long v)
+{
+    int lo = (int)(unsigned)v, hi = (int)(unsigned)(v >> 32);
+    lo = __builtin_amdgcn_update_dpp(0, lo, CTRL, 0xf, 0xf, false);
+    hi = __builtin_amdgcn_update_dpp(0, hi, CTRL, 0xf, 0xf, false);
+    return ((unsigned long long)(unsigned)hi << 32) | (unsigned)lo;
+}
+__device__ __forceinline__ unsigned long long min_u64(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+__device__ __forceinline__ unsigned long long wave64_allmin_u64(unsigned long long v)
+{
+    v = min_u64(v, dpp_u64<0x128>(v));
+    v = min_u64(v, dpp_u64<0x124>(v));
+    v = min_u64(v, dpp_u64<0x122>(v));
+    v = min_u64(v, dpp_u64<0x121>(v));
+    {
+        const unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+        const auto rl = __builtin_amdgcn_permlane16_swap(lo, lo, false, false);
+        const auto rh = __builtin_amdgcn_permlane16_swap(hi, hi, false, false);
+        v = min_u64(((unsigned long long)rh[0] << 32) | rl[0], ((unsigned long long)rh[1] << 32) | rl[1]);
+    }
+    const unsigned lo = (unsigned)v, hi = (unsigned)(v >> 32);
+    const auto rl = __builtin_amdgcn_permlane32_swap(lo, lo, false, false);
+    const auto rh = __builtin_amdgcn_permlane32_swap(hi, hi, false, false);
+    return min_u64(((unsigned long long)rh[0] << 32) | rl[0], ((unsigned long long)rh[1] << 32) | rl[1]);
+}
 __device__ __forceinline__ double bcast_lane(double v, int lane)  // wave-uniform `lane`
 {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), lane);

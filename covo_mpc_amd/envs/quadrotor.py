@@ -275,6 +275,13 @@ def split_fan_rows(rows: np.ndarray) -> dict:
             "idx": np.ascontiguousarray(rows[..., 1]).view(np.int32)}
 
 
+def split_arbiter_rows(rows: np.ndarray) -> dict:
+    """Arbiter rows [.., 8] (include/covo_hip.h: covo_set_step_arbiter) -> {cost [.., 3] (softmax mean, nominal, best sample; +inf:
+    masked out or absent), cost_chosen [..], choice [..] int32, best [..] int32 (the best sample's index, -1: none)} (numpy)."""
+    return {"cost": rows[..., 0:3], "cost_chosen": rows[..., 3], "choice": np.ascontiguousarray(rows[..., 4]).view(np.int32),
+            "best": np.ascontiguousarray(rows[..., 5]).view(np.int32)}
+
+
 def unpack_state_row(row: np.ndarray) -> dict:
     """One packed state float32[32] (include/covo_hip.h "Data layouts") -> the EnvState3D fields it carries."""
     return {"pos": row[0:3].copy(), "vel": row[3:6].copy(), "quat": row[6:10].copy(), "omega": row[10:13].copy(),
@@ -314,6 +321,24 @@ class DeviceEpisode:
         self.diag_log = None  # [T + 1, 8], allocated when a controller with compute_diag runs the episode
         self.trace = None     # [T + 1, 168], allocated when a controller with compute_plan runs the episode
         self.fanlog = None    # [T + 1, K, 100], allocated when a controller with compute_fan runs the episode
+        self.arblog = None    # [T + 1, 8], allocated when a controller with update="best" / "guarded" runs the episode
+
+    def alloc_arbiter_log(self):
+        import torch
+        self.arblog = torch.zeros((int(self.log.shape[0]), self._lib.COVO_ARB_FLOATS), dtype=torch.float32, device=self.device)
+
+    def arbiter_log_view(self):
+        """the rows of the arbiter log the next segment writes (covo_run_episode counts its rows from 0)"""
+        return self.arblog[self.n_steps:]
+
+    def read_arbiter(self):
+        """-> {cost [n, 3], cost_chosen [n], choice [n], best [n]} (numpy): per enqueued step the update arbiter's row (include/covo_hip.h:
+        covo_set_step_arbiter), under a controller built with update="best" / "guarded"; synchronises and checks the device status
+        like read_log."""
+        if self.arblog is None:
+            raise RuntimeError("no arbiter log: run_episode under a controller built with update='best' or 'guarded'")
+        self.read_log()
+        return split_arbiter_rows(self.arblog[:self.n_steps].cpu().numpy())
 
     def alloc_fan_log(self, K: int):
         import torch
@@ -446,6 +471,22 @@ class BatchedDeviceEpisode:
         self.diag_log = None  # [E, T + 1, 8], allocated when a controller with compute_diag runs the episode
         self.trace = None     # [E, T + 1, 168], allocated when a controller with compute_plan runs the episode
         self.fanlog = None    # [E, T + 1, K, 100], allocated when a controller with compute_fan runs the episode
+        self.arblog = None    # [E, T + 1, 8], allocated when a controller with update="best" / "guarded" runs the episode
+
+    def alloc_arbiter_log(self):
+        import torch
+        self.arblog = torch.zeros((self.E, int(self.log.shape[1]), self._lib.COVO_ARB_FLOATS), dtype=torch.float32, device=self.device)
+
+    def arbiter_log_view(self):
+        return self.arblog  # (the batched drivers take the first row of a segment as log_index)
+
+    def read_arbiter(self):
+        """-> {cost [E, n, 3], cost_chosen [E, n], choice [E, n], best [E, n]} (numpy) of the enqueued steps (controller built with
+        update="best" / "guarded"); synchronises and checks the device status like read_log."""
+        if self.arblog is None:
+            raise RuntimeError("no arbiter log: run_episode under a controller built with update='best' or 'guarded'")
+        self.read_log()
+        return split_arbiter_rows(self.arblog[:, :self.n_steps].cpu().numpy())
 
     def alloc_fan_log(self, K: int):
         import torch
@@ -519,12 +560,16 @@ class BatchedDeviceEpisode:
 
 
 def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H32_lam0.01", n_steps=None, seed: int = 1, device=None,
-                     verbose: bool = True, diag: bool = False, trace: bool = False, fan=None):
+                     verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
+                     arbiter: bool = False):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]; with trace=True
     -> (that, ep.read_trace()): every instance's states, actions and plans of the episode; with fan=K ep.read_fan() -- K sampled
-    rollouts of every step of every instance -- is appended to the returned tuple."""
+    rollouts of every step of every instance -- is appended to the returned tuple.  update: the controller's update rule ("softmax" |
+    "best" | "guarded"); arbiter=True (with "best" / "guarded") appends ep.read_arbiter(), every step's arbiter row."""
+    if arbiter and update == "softmax":
+        raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
     rng = crandom.PRNGKey(seed)
     ks = crandom.split(rng, 3 * n_envs + 1)
@@ -534,7 +579,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     cp0 = c0.init_control_params
     b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                           sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device,
-                                          compute_diag=diag, compute_plan=trace, compute_fan=fan)
+                                          compute_diag=diag, compute_plan=trace, compute_fan=fan, update=update)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
@@ -551,7 +596,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
             blind = (ess > 0.9 * N).sum(axis=1)
             print("ESS median per instance: " + " ".join(f"{v:.0f}" for v in np.median(ess, axis=1)) +
                   f"; steps with ess > 0.9 N per instance: {' '.join(str(int(v)) for v in blind)} (of {T})")
-    out = (log[:, :, 1].mean(axis=1),) + ((ep.read_trace(),) if trace else ()) + ((ep.read_fan(),) if fan else ())
+    out = ((log[:, :, 1].mean(axis=1),) + ((ep.read_trace(),) if trace else ()) + ((ep.read_fan(),) if fan else ()) +
+           ((ep.read_arbiter(),) if arbiter else ()))
     return out if len(out) > 1 else out[0]
 
 
@@ -649,10 +695,14 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 
 
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
-                   compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None):
+                   compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax"):
     """quadrotor.py:670-752.  ess_min (sampling controllers): the ESS floor, see SamplingCore; compute_fan=K (sampling controllers): K
-    sampled rollouts of every step in info["fan_pos"] / ["fan_cost"] / ["fan_idx"], see SamplingCore."""
+    sampled rollouts of every step in info["fan_pos"] / ["fan_cost"] / ["fan_idx"], see SamplingCore; update (sampling controllers):
+    "softmax" (default) | "best" | "guarded" -- the update arbiter, info["arb_cost"] / ["arb_choice"] / ["arb_best"] /
+    ["arb_cost_chosen"], see SamplingCore."""
     import torch
+    from .. import _lib
+    _lib.check_update(update)
 
     def parse_sample_params(param_text):
         if not param_text:
@@ -680,7 +730,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info,
                                           compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                          compute_fan=compute_fan), control_params
+                                          compute_fan=compute_fan, update=update), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -693,7 +743,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group,
                                           compute_info=compute_info, compute_diag=compute_diag,
-                                          compute_plan=compute_plan, ess_min=ess_min, compute_fan=compute_fan), control_params
+                                          compute_plan=compute_plan, ess_min=ess_min, compute_fan=compute_fan,
+                                          update=update), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -794,6 +845,7 @@ class Args:
     name: str = ""
     host_env: bool = False  # (not in quadjax) eval with the Python env step instead of the device one
     fan: int = 0            # (not in quadjax) render: K sampled rollouts of every step next to the plan (compute_fan); 0 = off
+    update: str = "softmax"  # (not in quadjax) the sampling controllers' update rule: softmax | best | guarded (the update arbiter)
 
 
 def main(args: Args):
@@ -806,7 +858,8 @@ def main(args: Args):
     # (quadrotor.py:523-538), here the per-step position statistics are simply not requested
     render = args.mode == "render"
     controller, control_params = get_controller(env, args.controller, args.controller_params, compute_info=args.mode != "eval",
-                                                compute_plan=render, compute_fan=(args.fan or None) if render else None)
+                                                compute_plan=render, compute_fan=(args.fan or None) if render else None,
+                                                update=args.update)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -823,6 +876,8 @@ def _cli():
     for f, default in Args().__dict__.items():
         if isinstance(default, bool):
             ap.add_argument(f"--{f}", action="store_true")
+        elif f == "update":
+            ap.add_argument("--update", choices=("softmax", "best", "guarded"), default=default)
         else:
             ap.add_argument(f"--{f}", type=type(default), default=default)
     main(Args(**vars(ap.parse_args())))

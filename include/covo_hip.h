@@ -523,6 +523,39 @@ int covo_rollout_fan(covo_handle_t h, const float *state, const float *pos_traj,
                      const float *a, int32_t N, const int32_t *idx, int32_t K, float *fan_out, void *stream);
 int covo_set_step_fan(covo_handle_t h, float *fan, const int32_t *idx, int32_t K, int32_t n_inst);
 int covo_set_episode_fan(covo_handle_t h, float *fanlog, int32_t stride);
+/* The update arbiter: a control step commits the best of {softmax mean, old plan, best sample} (additive to ABI 10:
+ * COVO_HAS_UPDATE_ARBITER; off by default, and off changes nothing a caller can observe).  Per instance and control step, three
+ * candidates, each [COVO_H][4]:
+ *   0  softmax mean  the a_mean the step has just written (covo.py:275 / mppi.py:116)
+ *   1  nominal       the shifted mean the step sampled around (what covo_shift_mean gives the step's input mean)
+ *   2  best sample   a[:, n*, :] with n* = argmin_n cost[n] over the step's own costs; NaN costs are skipped, equal costs resolve to
+ *                    the lowest index; all NaN: the candidate is absent and n* = -1
+ * Candidates 0 and 1 are clipped to [-1, 1] for evaluation only.  Every enabled candidate is rolled out by the rollout kernel's own
+ * stage functions with exactly the inputs of the step's sample rollouts (noisy state, trajectory window, covo_env_params, discount,
+ * the same disturbance as for the plan).  mask bit c enables candidate c; a masked-out or absent candidate has cost +inf.  choice =
+ * the enabled candidate of least cost (a NaN cost counts as +inf, equal costs resolve to the lowest candidate number, all +inf: 0).
+ * Choice 0 leaves a_mean untouched; 1 writes the nominal, unclipped; 2 writes a[:, n*, :].  Nothing else of the step changes.
+ *   row  float[COVO_ARB_FLOATS] = {cost_softmax, cost_nominal, cost_best, cost_chosen, bits(int32 choice), bits(int32 n_best), 0, 0}
+ * One extra eager launch per step for all instances (csrc/update_arbiter.hip), behind the step and ahead of the plan and fan
+ * launches: the plan, the trace's u and an episode driver's env step see the arbitrated mean.  No captured step graph changes.
+ * covo_arbitrate: stateless, the arguments of covo_rollout_fan plus cost = DEVICE float[N], a_nominal = DEVICE float[128],
+ *   a_mean_inout = DEVICE float[128], row_out = DEVICE float[COVO_ARB_FLOATS].
+ * covo_set_step_arbiter: rows = DEVICE float[n_inst][COVO_ARB_FLOATS]; every control step of the handle -- covo_mpc_step (all modes,
+ *   staged and fused, eager and graph), covo_mpc_step_batched, covo_mpc_step_batched_mode and the steps of the three episode
+ *   drivers -- arbitrates and writes instance e's row (a single step: instance 0); rows = NULL: off, the episode log with it.
+ * covo_set_episode_arbiter_log: log = DEVICE float[n_inst][stride][COVO_ARB_FLOATS], after covo_set_step_arbiter; step k of an
+ *   episode driver's segment writes instance e's row to log[e][log_index + k] (covo_run_episode: log_index = 0); NULL = off.
+ * Refused before any launch, with a message that names the condition: mask outside [1, 7]; n_inst outside (0, COVO_MAX_ENVS]; a
+ * batched step with more instances than n_inst; an episode segment that would leave the log; a sample-sharded step
+ * (partial_out != NULL) -- a rank's `a` and `cost` hold its shard only. */
+#define COVO_HAS_UPDATE_ARBITER 1
+#define COVO_ARB_FLOATS 8
+int covo_set_step_arbiter(covo_handle_t h, float *rows, int32_t mask, int32_t n_inst);
+int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride);
+int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                   const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
+                   const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
+                   void *stream);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);
