@@ -32,7 +32,9 @@ COVO_HAS_SAMPLE_FAN = 1
 COVO_FAN_FLOATS = 100  # a fan row: {cost_s, bits(int32 n_s), 0, 0, pos_s[H][3]} (covo_set_step_fan): the layout of a plan row
 COVO_FAN_MAX = 64      # rows of a fan: one 64-sample group of the rollout
 COVO_HAS_UPDATE_ARBITER = 1
+COVO_HAS_STEP_ITERS = 1
 COVO_ARB_FLOATS = 8  # an arbiter row: {cost_softmax, cost_nominal, cost_best, cost_chosen, bits(int32 choice), bits(int32 n_best), 0, 0}
+COVO_MAX_STEP_ITERS = 16  # iters= of the controllers: sample-rollout-update passes per control step (covo_hip.h: COVO_HAS_STEP_ITERS)
 UPDATE_MASKS = {"softmax": 0, "best": 0b110, "guarded": 0b111}  # update= of the controllers -> the arbiter's candidate mask (0: detached)
 LAM_FIELDS = ("lam_eff", "inv_lam_eff", "ess_lam0", "evaluations")
 COVO_FLAG_ACTIONS_CLIPPED = 1
@@ -174,6 +176,7 @@ _SIGS = {
     "covo_set_episode_fan": (C.c_int, [_P, _P, C.c_int32]),
     "covo_set_step_arbiter": (C.c_int, [_P, _P, C.c_int32, C.c_int32]),  # the update arbiter (covo_hip.h: COVO_HAS_UPDATE_ARBITER)
     "covo_set_episode_arbiter_log": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_set_step_iters": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # iterations per control step (covo_hip.h: COVO_HAS_STEP_ITERS)
     "covo_arbitrate": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, C.c_int32,
                                  _P, _P, C.c_int32, _P, _P]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
@@ -241,6 +244,15 @@ def check_update(update) -> int:
     if not isinstance(update, str) or update not in UPDATE_MASKS:
         raise ValueError(f"update={update!r} (softmax | best | guarded)")
     return UPDATE_MASKS[update]
+
+
+def check_iters(iters) -> int:
+    """iters= of the controllers -> the number of sample-rollout-update passes per control step: an integer in
+    [1, COVO_MAX_STEP_ITERS] (1, the default: today's step); anything else raises ValueError."""
+    import numbers
+    if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= int(iters) <= COVO_MAX_STEP_ITERS:
+        raise ValueError(f"iters={iters!r} outside [1, {COVO_MAX_STEP_ITERS}] (an integer number of passes per control step; 1 = off)")
+    return int(iters)
 
 
 def ptr(t):

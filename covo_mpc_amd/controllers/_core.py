@@ -53,10 +53,16 @@ class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax"):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1):
         import torch
         fan_K = _lib.check_fan(compute_fan, N)
         arb_mask = _lib.check_update(update)
+        iters = _lib.check_iters(iters)
+        if iters > 1 and process_group is not None:
+            import torch.distributed as dist
+            if dist.get_world_size(process_group) > 1:
+                raise NotImplementedError(f"iters={iters} on sample-sharded ranks: every pass would need its own exchange of the rank "
+                                          "records (covo_set_step_iters refuses sample-sharded steps)")
         if arb_mask and process_group is not None:
             import torch.distributed as dist
             if dist.get_world_size(process_group) > 1:
@@ -210,6 +216,15 @@ class SamplingCore:
         if self.ess_min != 0.0:
             self.lam_eff = torch.zeros((int(diag_rows), _lib.COVO_LAM_FLOATS), **f32)
             check(self.lib.covo_set_step_ess_floor(self.h, self.ess_min, ptr(self.lam_eff), int(diag_rows)), "covo_set_step_ess_floor")
+        # iters = k > 1: every control step runs k sample-rollout-update passes on its one state -- pass 0 is today's step, pass
+        # j >= 1 starts from the mean pass j - 1 committed (no shift) with the raw key split(split(key_{j-1})[0])[0], walked on the
+        # device -- and leaves the minimum sample cost of every pass in self.iter_cost_min (row e = instance e of a batched step)
+        # (covo_set_step_iters); 1 (default): nothing attached, and that changes nothing
+        self.iters = iters
+        self.iter_cost_min = None
+        if iters > 1:
+            self.iter_cost_min = torch.zeros((int(diag_rows), iters), **f32)
+            check(self.lib.covo_set_step_iters(self.h, iters, ptr(self.iter_cost_min), int(diag_rows)), "covo_set_step_iters")
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -430,6 +445,13 @@ class SamplingCore:
                                       int(mask), ptr(out), self.stream()), "covo_arbitrate")
         return out
 
+    def iter_info(self) -> dict:
+        """{"iter_cost_min" [iters]} of the last step -- entry j: the minimum sample cost of pass j -- as a view of self.iter_cost_min
+        (no sync, no copy); {} when the core was built with iters=1."""
+        if self.iter_cost_min is None:
+            return {}
+        return {"iter_cost_min": self.iter_cost_min[0]}
+
     def lam_info(self) -> dict:
         """{"lam_eff", "ess_lam0"} of the last step as 0-d views of self.lam_eff (no sync, no copy); {} when the core was built
         without ess_min."""
@@ -458,6 +480,9 @@ class SamplingCore:
         if getattr(self, "arb_mask", 0):
             raise NotImplementedError(f"update={self.update_rule!r} follows the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') updates with the softmax mean only")
+        if getattr(self, "iters", 1) > 1:
+            raise NotImplementedError(f"iters={self.iters} follows the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') runs one pass per call")
         if self.compute_diag:
             raise NotImplementedError("compute_diag is formed by the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")

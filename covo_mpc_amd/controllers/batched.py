@@ -29,9 +29,14 @@ class BatchedCoVOController:
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax"):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1):
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
+        _lib.check_iters(iters)
+        if iters > 1 and update != "softmax" and (self.MODE is not None or mode != "online"):
+            raise NotImplementedError(f"iters={iters} with update={update!r}: not available for the env-batched MPPI / covo-offline step "
+                                      "(its fused launch keeps each pass's starting mean in LDS only); "
+                                      "BatchedCoVOController(mode=\"online\") and the single controllers take both")
         if ess_min is not None and float(ess_min) != 0.0 and (self.MODE is not None or mode != "online"):
             raise NotImplementedError(f"ess_min={ess_min}: the ESS floor is not available for the env-batched MPPI / covo-offline step "
                                       "(one fused launch: it needs the temperature before all costs exist); "
@@ -54,7 +59,9 @@ class BatchedCoVOController:
         # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update)
+                                 compute_fan=compute_fan, update=update, iters=iters)
+        # iters = k > 1: after a call, self.iter_cost_min [E, k] holds the minimum sample cost of every pass of every instance; None under 1
+        self.iter_cost_min = self.core.iter_cost_min
         # update = "best" / "guarded": after a call, self.arbiter [E, 8] holds every instance's arbiter row of that step: {cost_softmax,
         # cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0} (include/covo_hip.h); None under "softmax"
         self.arbiter = self.core.arbiter
@@ -233,16 +240,17 @@ class BatchedMPPIController(BatchedCoVOController):
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None, update: str = "softmax"):
+                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1):
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
+        _lib.check_iters(iters)
         if float(gamma_sigma) != 0.0:
             raise NotImplementedError(f"gamma_sigma={gamma_sigma}: MPPI's covariance adaptation (mppi.py:119-125) is not batched; "
                                       "the batched fused launch needs gamma_sigma == 0 (the reference's default)")
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
                          a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                         compute_fan=compute_fan, update=update)
+                         compute_fan=compute_fan, update=update, iters=iters)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

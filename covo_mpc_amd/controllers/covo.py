@@ -46,10 +46,11 @@ class CoVOParams:
 class CoVOController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, mode: str = "online", *, device=None,
                  process_group=None, compute_info: bool = True, propagate_nan=None, compute_diag: bool = False,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax") -> None:
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1) -> None:
         from .. import _lib
         _lib.check_fan(compute_fan, N)  # ValueError before anything is built
         _lib.check_update(update)
+        _lib.check_iters(iters)
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -70,7 +71,7 @@ class CoVOController(BaseController):
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
                                  compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan,
                                  compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update)
+                                 compute_fan=compute_fan, update=update, iters=iters)
 
     def _needs_table(self, params_c) -> bool:
         """periodic / sin / drag / mixed (free.py:10-58): quadjax's deterministic=True only zeroes dyn_noise_scale
@@ -220,6 +221,7 @@ class CoVOController(BaseController):
             out_info.update(core.fan_info())   # compute_fan: fan_pos [K, H, 3] / fan_cost [K] / fan_idx [K], views of core.fan
             out_info.update(core.lam_info())   # ess_min: lam_eff / ess_lam0, views of core.lam_eff
             out_info.update(core.arbiter_info())  # update: arb_cost [3] / arb_choice / arb_best / arb_cost_chosen, views of core.arbiter
+            out_info.update(core.iter_info())  # iters: iter_cost_min [iters], a view of core.iter_cost_min
             return a_mean_new[0], control_params, out_info
 
         # ---- kernel-by-kernel path with epsilon materialised in HBM (identical values; parity/debug)

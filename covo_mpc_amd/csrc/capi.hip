@@ -889,6 +889,37 @@ int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride)
             "%s: the update arbiter (covo_set_step_arbiter) is not available for sample-sharded steps (partial_out != NULL): " \
             "a rank's action and cost buffers hold its shard only; detach it", what)
 
+// ---- iterations per control step: K sample-rollout-update passes per call on the step's one state (step.hip enqueues them).  The
+// captured step graphs hold all K passes and the log's address: a change bumps the epoch like a debug switch
+int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_iters: null handle");
+    REQUIRE(iters >= 1 && iters <= COVO_MAX_STEP_ITERS, "covo_set_step_iters: iters=%d outside [1, %d]", iters, COVO_MAX_STEP_ITERS);
+    const bool on = iters > 1 && iter_log != nullptr;
+    REQUIRE(!on || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_iters: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    const int before = covo_step_iters(h);
+    const float *log_before = before > 1 ? h->iter_log : nullptr;
+    h->iters = on ? iters : 1;
+    h->iter_log = on ? iter_log : nullptr;
+    h->iter_n = on ? n_inst : 0;
+    if (covo_step_iters(h) != before || h->iter_log != log_before) ++h->opt.epoch;
+    return 0;
+}
+
+// a step for n_inst instances on a handle with iterations attached: a row of the log for each; a sample-sharded step would need
+// one exchange per pass; the key chain is walked from the raw controller key
+#define CHECK_ITERS(h, n_inst, what)                                                                                       \
+    REQUIRE(covo_step_iters(h) == 1 || (n_inst) <= (h)->iter_n, "%s: %d instances, the iteration log (covo_set_step_iters) has n_inst=%d", \
+            what, (int)(n_inst), (h)->iter_n)
+#define REFUSE_SHARDED_ITERS(h, args, what)                                                                                \
+    REQUIRE((args)->partial_out == nullptr || covo_step_iters(h) == 1,                                                     \
+            "%s: iterations per step (covo_set_step_iters, iters=%d) are not available for sample-sharded steps (partial_out != NULL): " \
+            "every pass would need its own exchange of the rank records; set iters = 1", what, covo_step_iters(h))
+#define CHECK_ITERS_KEYS(h, args, what)                                                                                    \
+    REQUIRE((args)->derive_keys == 1 || covo_step_iters(h) == 1,                                                           \
+            "%s: iterations per step (covo_set_step_iters, iters=%d) need derive_keys = 1 (every pass derives its keys from the raw " \
+            "controller key on the device)", what, covo_step_iters(h))
+
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
@@ -1006,6 +1037,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
             "(covo_set_episode_fan) has %d rows", n_steps, h->fanlog_stride);
     REFUSE_SHARDED_ARBITER(h, args, "covo_run_episode");
     CHECK_ARBITER(h, 1, "covo_run_episode");
+    REFUSE_SHARDED_ITERS(h, args, "covo_run_episode");
+    CHECK_ITERS(h, 1, "covo_run_episode");
     REQUIRE(h->arblog == nullptr || n_steps <= h->arblog_stride, "covo_run_episode: %d steps, the episode arbiter log "
             "(covo_set_episode_arbiter_log) has %d rows", n_steps, h->arblog_stride);
     hipStream_t s = (hipStream_t)stream;
@@ -1113,6 +1146,11 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
             "one fused launch needs the temperature before all costs exist, and there is no staged batched fallback; turn it off "
             "(ess_min = 0)", what, (double)h->ess_min);
     CHECK_ESS_FLOOR(h, args->n_samples, args->n_envs, what);
+    CHECK_ITERS(h, args->n_envs, what);
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_step_iters(h) == 1 || !covo_arb_on(h),
+            "%s: iterations per step (covo_set_step_iters, iters=%d) together with the update arbiter (covo_set_step_arbiter) are not "
+            "available for the env-batched MPPI / covo-offline step: its fused launch keeps each pass's starting mean in LDS only; "
+            "detach one of them", what, covo_step_iters(h));
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
     REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),
@@ -1217,6 +1255,8 @@ int covo_debug_time_batched(covo_handle_t h, int32_t step_mask, int32_t reps, fl
 {
     REQUIRE(h && us_out && reps > 0, "covo_debug_time_batched: bad argument");
     CHECK_DEVICE(h, "covo_debug_time_batched");
+    REQUIRE(covo_step_iters(h) == 1, "covo_debug_time_batched: the phase timers replay ONE pass; iterations per step are on "
+            "(covo_set_step_iters, iters=%d): set iters = 1", covo_step_iters(h));
     return covo_debug_time_batched_impl(h, step_mask, reps, us_out, (hipStream_t)stream);
 }
 
@@ -1259,6 +1299,8 @@ int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const c
                          int32_t hess_mask, int32_t sigma_stages, int32_t reps, float *us_out, void *stream)
 {
     REQUIRE(h && params && args && us_out && reps > 0, "covo_debug_time_step: bad argument");
+    REQUIRE(covo_step_iters(h) == 1, "covo_debug_time_step: the phase timers replay ONE pass; iterations per step are on "
+            "(covo_set_step_iters, iters=%d): set iters = 1", covo_step_iters(h));
     return covo_debug_time_step_impl(h, params, args, step_mask, hess_mask, sigma_stages, reps, us_out, (hipStream_t)stream);
 }
 
@@ -1318,6 +1360,9 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
     CHECK_FAN(h, args->n_samples, 1, "covo_mpc_step");
     REFUSE_SHARDED_ARBITER(h, args, "covo_mpc_step");
     CHECK_ARBITER(h, 1, "covo_mpc_step");
+    REFUSE_SHARDED_ITERS(h, args, "covo_mpc_step");
+    CHECK_ITERS(h, 1, "covo_mpc_step");
+    CHECK_ITERS_KEYS(h, args, "covo_mpc_step");
     REFUSE_SHARDED_ESS_FLOOR(h, args, "covo_mpc_step");
     CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_mpc_step");
     const int rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);

@@ -78,7 +78,14 @@ struct covo_ctx {
     float *arblog;            // caller's [n_inst][arblog_stride][COVO_ARB_FLOATS]: the episode drivers' steps write their rows there
     int arblog_stride;
     void *arb_state;          // ArbState (update_arbiter.hip): a batched step's argument blocks and nominals on the device
+    // iterations per control step (covo_set_step_iters); iters <= 1 or iter_log null: off
+    int iters;                // sample-rollout-update passes per control step
+    float *iter_log;          // caller's [iter_n][iters]: entry (e, j) = the minimum sample cost of instance e's pass j
+    int iter_n;
 };
+// passes per control step of this handle (1: today's step) and where pass j of instance 0 logs its cost minimum (instance e: + e * iters)
+static inline int covo_step_iters(const covo_ctx *h) { return (h->iter_log != nullptr && h->iters > 1) ? h->iters : 1; }
+static inline float *covo_iter_slot(const covo_ctx *h, int pass) { return covo_step_iters(h) > 1 ? h->iter_log + pass : nullptr; }
 // where the solver of this handle's steps writes the instances' temperatures (null: no floor) and for how many instances
 static inline float *covo_lam_target(const covo_ctx *h) { return h->ess_min > 0.0f ? (h->lam_out ? h->lam_out : h->lam_own) : nullptr; }
 static inline int covo_lam_capacity(const covo_ctx *h) { return h->lam_out ? h->lam_n : COVO_MAX_ENVS; }
@@ -298,6 +305,10 @@ struct UpdateDesc {
     // the ESS floor (launch_softmax_reduce / launch_softmax_update_cov, final updates only): instance e takes 1 / lambda from
     // lam_rows[e][1] in device memory -- the solver's output, ess_lambda.hip -- instead of the handle's configured temperature
     const float *lam_rows = nullptr;  // [batch][COVO_LAM_FLOATS]
+    // an iterated step (covo_set_step_iters), final updates only: the merge also stores its cost minimum m, instance e's at
+    // iter_out[e * iter_stride] (the caller has added the pass index)
+    float *iter_out = nullptr;
+    int iter_stride = 0;
 };
 // the ESS floor's solver (ess_lambda.hip): out [n_inst][COVO_LAM_FLOATS] from cost [n_inst][N]; groupmin [n_inst][ceil(N/64)] as the
 // rollout leaves it, or null (the minimum is then formed from the costs)
@@ -328,6 +339,7 @@ struct SymStatsOut;  // sym_stats.hpp
 // the step's begin work folded into the Hessian's first launch (eager covo-online steps; hessian_adj.hip: AdjArgs): the
 // caller's unshifted mean, where the per-step scalars and the sequence number live, and the 48-byte block of step_begin.hpp
 struct HessBegin {
+    int pass;                 // > 0 (covo_set_step_iters): no shift, the raw key is the advanced one of dyn_out[10..11]
     const float *a_mean_raw;
     uint32_t *dyn_out;
     unsigned *seq;
@@ -462,10 +474,11 @@ int launch_arbiter_nominal(covo_ctx *h, const float *a_mean, int n_inst, hipStre
 void arbiter_state_destroy(covo_ctx *h);
 // step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
 // states_true + trace_index >= 0: an episode driver's step, which also writes its trace row
+// arbiter_only: the arbiter's launch between two passes of an iterated step (covo_set_step_iters)
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s);
+                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only = false);
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
-                            const float *states_true, int trace_index, hipStream_t s);
+                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only = false);
 int launch_env_step(float *state, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,
                     const covo_env_params &p, const float *action, const uint32_t *step_key, int noisy_on,
                     float obs_noise_scale, float *log, int log_index, hipStream_t s);

@@ -68,6 +68,7 @@ struct AdjArgs {
     DynBlock blk;
     int derive_keys;
     float shared_noise_scale;
+    int begin_pass;  // > 0 (pass of an iterated step, covo_set_step_iters): a_mean_raw is read as it lies, the raw key is dyn_out[10..11] advanced
     int scan_prefix;                 // KB forms its primal prefix by parallel scans (adj13; COVO_HESS_SCAN=0: the sequential rollout)
 };
 
@@ -134,6 +135,7 @@ int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const D
     std::memset(&A.blk, 0, sizeof(A.blk));
     A.derive_keys = 0;
     A.shared_noise_scale = 0.0f;
+    A.begin_pass = 0;
     if (begin != nullptr && batch == 1 && (dbg.hess & 1)) {
         A.a_mean_raw = begin->a_mean_raw;
         A.dyn_out = begin->dyn_out;
@@ -141,6 +143,7 @@ int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const D
         std::memcpy(&A.blk, begin->blk, sizeof(A.blk));
         A.derive_keys = begin->derive_keys;
         A.shared_noise_scale = begin->shared_noise_scale;
+        A.begin_pass = begin->pass;
     }
     static const int scan_prefix = [] { const char *v = std::getenv("COVO_HESS_SCAN"); return v ? std::atoi(v) : 1; }();
     A.scan_prefix = scan_prefix;

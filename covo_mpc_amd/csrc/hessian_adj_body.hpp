@@ -269,12 +269,21 @@ __global__ __launch_bounds__(64) void adj_jac_kernel(const AdjArgs A)
     // the shift's index map -- entry i of the shifted mean is entry i + 4 of the old one, the last four repeat (covo.py:201-203)
     const bool raw = A.a_mean_raw != nullptr;
     const float *__restrict__ am_base = raw ? A.a_mean_raw : A.a_mean + (size_t)b * NA;
-    auto am = [&](int i) { return am_base[(raw && i < NA - 4) ? i + 4 : i]; };
+    const bool shift = raw && A.begin_pass == 0;  // (pass >= 1 of an iterated step starts from the previous pass's mean, unshifted)
+    auto am = [&](int i) { return am_base[(shift && i < NA - 4) ? i + 4 : i]; };
     if (raw && k == 0) {  // what step_begin_kernel leaves for the launches behind this one
         float *shift_out = const_cast<float *>(A.a_mean);
         shift_out[lane] = am(lane);
         shift_out[lane + 64] = am(lane + 64);
-        if (lane < 4) step_begin_derive(lane, A.blk, A.derive_keys, A.shared_noise_scale, A.dyn_out);
+        if (lane < 4) {
+            if (A.begin_pass > 0) {  // the previous pass's raw key, advanced (all four lanes load it before lane 0 stores the new one)
+                const uint32_t p0 = A.dyn_out[10], p1 = A.dyn_out[11];
+                uint32_t rk[2];
+                step_begin_derive_next(lane, p0, p1, A.shared_noise_scale, A.dyn_out, rk);
+            } else {
+                step_begin_derive(lane, A.blk, A.derive_keys, A.shared_noise_scale, A.dyn_out);
+            }
+        }
         if (lane == 4 && A.seq != nullptr) A.seq[0] = A.seq[0] + 1u;
     }
     double *__restrict__ ws = A.ws + (size_t)b * WS_COUNT;

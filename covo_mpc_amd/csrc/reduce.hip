@@ -57,9 +57,9 @@ __global__ __launch_bounds__(MG_THREADS) void merge_cov_kernel(const float *__re
                                                                const float *__restrict__ a_mean_old, float gamma_mean,
                                                                const float *__restrict__ a_cov_old, float gamma_sigma,
                                                                float *__restrict__ a_mean_out, float *__restrict__ a_cov_out,
-                                                               int stride)
+                                                               int stride, float *__restrict__ iter_out)
 {
-    merge_cov_body<FINAL>(partials, G, inv_lam, a_mean_old, gamma_mean, a_cov_old, gamma_sigma, a_mean_out, a_cov_out, stride);
+    merge_cov_body<FINAL>(partials, G, inv_lam, a_mean_old, gamma_mean, a_cov_old, gamma_sigma, a_mean_out, a_cov_out, stride, iter_out);
 }
 
 // Merges G records {m, s, v[128]} with 1024 threads = 8 record-slices x 128 columns (softmax_merge.hpp: the body is shared
@@ -71,7 +71,8 @@ __global__ __launch_bounds__(MG_THREADS) void merge_cov_kernel(const float *__re
 template <bool FINAL>
 __global__ __launch_bounds__(MG_THREADS) void merge_kernel(const float *__restrict__ partials, int G, float inv_lam,
                                                            const float *__restrict__ a_mean_old, float gamma_mean,
-                                                           float *__restrict__ out, int stride)
+                                                           float *__restrict__ out, int stride, float *__restrict__ iter_out,
+                                                           int iter_stride)
 {
     __shared__ MergeLds lds;
     {   // blockIdx.x (env-batched step): instance x merges its own G records into its own mean
@@ -81,6 +82,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_kernel(const float *__restri
         out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
     }
     merge_body<MG_THREADS, FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds);
+    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
 }
 
 // the same, and the diagnostic records dpart [instances][G][MG_DIAG_REC] merged into row x of diag_out [instances][COVO_DIAG_FLOATS]
@@ -88,7 +90,8 @@ template <bool FINAL>
 __global__ __launch_bounds__(MG_THREADS) void merge_diag_kernel(const float *__restrict__ partials, int G, float inv_lam,
                                                                 const float *__restrict__ a_mean_old, float gamma_mean,
                                                                 float *__restrict__ out, int stride, const float *__restrict__ dpart,
-                                                                float *__restrict__ diag_out, float n_samples)
+                                                                float *__restrict__ diag_out, float n_samples, float *__restrict__ iter_out,
+                                                                int iter_stride)
 {
     __shared__ MergeLds lds;
     __shared__ float dred[3][MG_VWAVES];
@@ -102,6 +105,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_diag_kernel(const float *__r
     D.n = n_samples;
     D.red = dred;
     merge_body<MG_THREADS, FINAL, false, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds, D);
+    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
 }
 
 // the episode drivers (capi.hip): the step's diagnostics [n_inst][COVO_DIAG_FLOATS] -> row `index` of every instance's log
@@ -156,7 +160,7 @@ int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
         hipLaunchKernelGGL(softmax_partial_diag_kernel<false>, dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
                            st.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr, d.diag_rec);
         hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam, d.a_mean_old,
-                           d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, (const float *)d.diag_rec, d.diag_out, (float)d.N);
+                           d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, (const float *)d.diag_rec, d.diag_out, (float)d.N, d.iter_out, d.iter_stride);
         COVO_CHECK_HIP(hipGetLastError());
         return 0;
     }
@@ -164,10 +168,10 @@ int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
                        st.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr);
     if (d.a_mean_out != nullptr)
         hipLaunchKernelGGL(merge_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam, d.a_mean_old,
-                           d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS);
+                           d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, d.iter_out, d.iter_stride);
     else
         hipLaunchKernelGGL(merge_kernel<false>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam,
-                           (const float *)nullptr, 1.0f, d.partial_out, COVO_PARTIAL_FLOATS);
+                           (const float *)nullptr, 1.0f, d.partial_out, COVO_PARTIAL_FLOATS, (float *)nullptr, 0);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -193,13 +197,13 @@ int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
     if (diag)
         hipLaunchKernelGGL(merge_diag_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam,
                            (const float *)nullptr, 1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, d.diag_out,
-                           (float)d.N);
+                           (float)d.N, (float *)nullptr, 0);
     if (d.a_cov_out != nullptr)
         hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam, d.a_mean_old,
-                           d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS);
+                           d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS, d.iter_out);
     else  // a sample-sharded rank: its record {m, s, v, pad, S2}, unnormalised and unblended
         hipLaunchKernelGGL(merge_cov_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam, d.a_mean_old,
-                           1.0f, (const float *)nullptr, 0.0f, d.partial_out, (float *)nullptr, RD_COV_RECORD_FLOATS);
+                           1.0f, (const float *)nullptr, 0.0f, d.partial_out, (float *)nullptr, RD_COV_RECORD_FLOATS, (float *)nullptr);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -209,7 +213,7 @@ int launch_merge_cov(const UpdateDesc &d, float lam, hipStream_t s)
 {
     if (d.G > MG_MAXG) { covo_set_error("covo_merge_ranks_cov: G=%d > %d", d.G, MG_MAXG); return COVO_E_BADARG; }
     hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam, d.a_mean_old, d.gamma_mean,
-                       d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, d.stride);
+                       d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, d.stride, d.iter_out);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -219,13 +223,13 @@ int launch_merge(const UpdateDesc &d, float lam, hipStream_t s)
     if (d.G > MG_MAXG) { covo_set_error("covo_merge: G=%d > %d", d.G, MG_MAXG); return COVO_E_BADARG; }
     if (d.a_mean_out != nullptr && d.diag_out != nullptr)
         hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam, d.a_mean_old,
-                           d.gamma_mean, d.a_mean_out, d.stride, (const float *)d.diag_rec, d.diag_out, (float)d.N);
+                           d.gamma_mean, d.a_mean_out, d.stride, (const float *)d.diag_rec, d.diag_out, (float)d.N, d.iter_out, d.iter_stride);
     else if (d.a_mean_out != nullptr)
         hipLaunchKernelGGL(merge_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam, d.a_mean_old,
-                           d.gamma_mean, d.a_mean_out, d.stride);
+                           d.gamma_mean, d.a_mean_out, d.stride, d.iter_out, d.iter_stride);
     else
         hipLaunchKernelGGL(merge_kernel<false>, dim3(d.batch), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam,
-                           (const float *)nullptr, 1.0f, d.partial_out, d.stride);
+                           (const float *)nullptr, 1.0f, d.partial_out, d.stride, (float *)nullptr, 0);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

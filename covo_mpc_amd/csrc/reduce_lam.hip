@@ -23,7 +23,8 @@ template <bool FINAL>
 __global__ __launch_bounds__(MG_THREADS) void merge_lam_kernel(const float *__restrict__ partials, int G,
                                                                const float *__restrict__ lam_rows,
                                                                const float *__restrict__ a_mean_old, float gamma_mean,
-                                                               float *__restrict__ out, int stride)
+                                                               float *__restrict__ out, int stride, float *__restrict__ iter_out,
+                                                               int iter_stride)
 {
     __shared__ MergeLds lds;
     const size_t x = blockIdx.x;
@@ -32,6 +33,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_lam_kernel(const float *__re
     if (FINAL) a_mean_old += x * COVO_NA;
     out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
     merge_body<MG_THREADS, FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds);
+    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
 }
 template <bool FINAL>
 __global__ __launch_bounds__(MG_THREADS) void merge_diag_lam_kernel(const float *__restrict__ partials, int G,
@@ -39,7 +41,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_diag_lam_kernel(const float 
                                                                     const float *__restrict__ a_mean_old, float gamma_mean,
                                                                     float *__restrict__ out, int stride,
                                                                     const float *__restrict__ dpart, float *__restrict__ diag_out,
-                                                                    float n_samples)
+                                                                    float n_samples, float *__restrict__ iter_out, int iter_stride)
 {
     __shared__ MergeLds lds;
     __shared__ float dred[3][MG_VWAVES];
@@ -54,6 +56,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_diag_lam_kernel(const float 
     D.n = n_samples;
     D.red = dred;
     merge_body<MG_THREADS, FINAL, false, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds, D);
+    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
 }
 
 // the ESS floor: 1 / lambda from row 0 of the solver's output (the covariance update is a single-instance launch)
@@ -62,9 +65,9 @@ __global__ __launch_bounds__(MG_THREADS) void merge_cov_lam_kernel(const float *
                                                                    const float *__restrict__ a_mean_old, float gamma_mean,
                                                                    const float *__restrict__ a_cov_old, float gamma_sigma,
                                                                    float *__restrict__ a_mean_out, float *__restrict__ a_cov_out,
-                                                                   int stride)
+                                                                   int stride, float *__restrict__ iter_out)
 {
-    merge_cov_body<true>(partials, G, lam_rows[1], a_mean_old, gamma_mean, a_cov_old, gamma_sigma, a_mean_out, a_cov_out, stride);
+    merge_cov_body<true>(partials, G, lam_rows[1], a_mean_old, gamma_mean, a_cov_old, gamma_sigma, a_mean_out, a_cov_out, stride, iter_out);
 }
 
 
@@ -95,12 +98,12 @@ int launch_softmax_reduce_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
                            st.blockmin, st.n_blockmin, d.lam_rows, partials_ws, (const float4 *)nullptr, d.diag_rec);
         hipLaunchKernelGGL(merge_diag_lam_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, d.lam_rows,
                            d.a_mean_old, d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, (const float *)d.diag_rec, d.diag_out,
-                           (float)d.N);
+                           (float)d.N, d.iter_out, d.iter_stride);
     } else {
         hipLaunchKernelGGL((softmax_partial_lam_kernel<false, false>), dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N,
                            st.blockmin, st.n_blockmin, d.lam_rows, partials_ws, (const float4 *)nullptr, (float *)nullptr);
         hipLaunchKernelGGL(merge_lam_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, d.lam_rows,
-                           d.a_mean_old, d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS);
+                           d.a_mean_old, d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, d.iter_out, d.iter_stride);
     }
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
@@ -120,13 +123,13 @@ int launch_softmax_update_cov_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t 
                            st.n_blockmin, d.lam_rows, h->ws_partials_cov, mean4, h->ws_diag_rec);
         hipLaunchKernelGGL(merge_diag_lam_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, d.lam_rows,
                            (const float *)nullptr, 1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, d.diag_out,
-                           (float)d.N);
+                           (float)d.N, (float *)nullptr, 0);
     } else {
         hipLaunchKernelGGL((softmax_partial_lam_kernel<true, false>), dim3(st.grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
                            st.n_blockmin, d.lam_rows, h->ws_partials_cov, mean4, (float *)nullptr);
     }
     hipLaunchKernelGGL(merge_cov_lam_kernel, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, d.lam_rows, d.a_mean_old,
-                       d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS);
+                       d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS, d.iter_out);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

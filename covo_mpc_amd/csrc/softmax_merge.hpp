@@ -39,6 +39,17 @@ struct MergeDiag {
     float (*red)[MG_VWAVES] = nullptr;  // LDS [3][MG_VWAVES]: the virtual waves' sums
 };
 
+// An iterated step (covo_set_step_iters): after merge_body, the cost minimum m it formed -- the minimum over its waves' minima in
+// L.redm (phase 1; nothing overwrites them) -- to the pass's slot of the iteration log.  Called by thread 0 behind the body's barriers.
+template <int THREADS>
+__device__ __forceinline__ void merge_log_min(const MergeLds &L, float *__restrict__ slot)
+{
+    float m = L.redm[0];
+#pragma unroll
+    for (int i = 1; i < THREADS / 64; ++i) m = fminf(m, L.redm[i]);
+    *slot = m;
+}
+
 template <bool COH>
 __device__ __forceinline__ float mg_load(const float *p)
 {

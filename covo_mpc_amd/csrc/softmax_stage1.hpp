@@ -179,7 +179,8 @@ template <bool FINAL>
 __device__ __forceinline__ void merge_cov_body(const float *__restrict__ partials, int G, float inv_lam,
                                                const float *__restrict__ a_mean_old, float gamma_mean,
                                                const float *__restrict__ a_cov_old, float gamma_sigma,
-                                               float *__restrict__ a_mean_out, float *__restrict__ a_cov_out, int stride)
+                                               float *__restrict__ a_mean_out, float *__restrict__ a_cov_out, int stride,
+                                               float *__restrict__ iter_out = nullptr)  // (an iterated step: m goes there too)
 {
     __shared__ float scale[MG_MAXG];
     __shared__ float redm[MG_THREADS / 64];
@@ -197,6 +198,7 @@ __device__ __forceinline__ void merge_cov_body(const float *__restrict__ partial
     m = redm[0];
 #pragma unroll
     for (int i = 1; i < MG_THREADS / 64; ++i) m = fminf(m, redm[i]);
+    if (iter_out != nullptr && tid == 0) *iter_out = m;
     float s = 0.0f;
     for (int g = tid; g < G; g += MG_THREADS) {
         const float *rec = partials + (size_t)g * REC;

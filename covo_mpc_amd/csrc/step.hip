@@ -27,13 +27,26 @@
 __global__ void step_begin_kernel(const float *__restrict__ a_mean, float *__restrict__ a_mean_shift,
                                   uint32_t *__restrict__ dyn, float *__restrict__ state_buf, int derive_keys,
                                   float shared_noise_scale, const DynBlock blk, float *__restrict__ mppi_cov,
-                                  float *__restrict__ mppi_Ls, unsigned *__restrict__ seq)
+                                  float *__restrict__ mppi_Ls, unsigned *__restrict__ seq, const int pass)
 {
     if (threadIdx.x == 0 && seq != nullptr) seq[0] = seq[0] + 1u;  // the step's sequence number (the streamed finalize launch's flags)
     // MPPI (mppi_cov != null): the covariance shift + the 4x4 block factors ride in this launch (one launch less on a path
     // that is host bound at small N)
-    if (mppi_cov != nullptr) mppi_prep(mppi_cov, mppi_Ls);
+    if (mppi_cov != nullptr) mppi_prep(mppi_cov, mppi_Ls, pass == 0);
     const int i = threadIdx.x;  // 128 + 32 + 4 threads
+    if (pass > 0) {
+        // pass j >= 1 of an iterated step (covo_set_step_iters), enqueued inside the step's graph: the starting mean is what the
+        // previous pass's merge (and arbiter) left in a_mean, unshifted; the state stays; the raw key is the previous pass's
+        // (dyn[10..11]) advanced -- the four deriving threads are lanes of one wave: all have loaded it before thread 0 stores
+        if (i < COVO_NA) {
+            a_mean_shift[i] = a_mean[i];
+        } else if (i >= COVO_NA + COVO_STATE_FLOATS) {
+            const uint32_t p0 = dyn[10], p1 = dyn[11];
+            uint32_t raw[2];
+            step_begin_derive_next(i - (COVO_NA + COVO_STATE_FLOATS), p0, p1, shared_noise_scale, dyn, raw);
+        }
+        return;
+    }
     if (i < COVO_NA) {
         a_mean_shift[i] = (i < COVO_NA - COVO_DU) ? a_mean[i + COVO_DU] : a_mean[i];
     } else if (i < COVO_NA + COVO_STATE_FLOATS) {
@@ -204,9 +217,10 @@ CovoOpts covo_default_opts()
 // begin launch is not part of the graph).
 static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, const covo_step_args &a, hipStream_t s,
                         const DebugMasks &dbg = DebugMasks(),
-                        const HessBegin *begin = nullptr, const float *state_direct = nullptr)
+                        const HessBegin *begin = nullptr, const float *state_direct = nullptr, const int pass = 0)
 {
     const int M = dbg.step;
+    float *iter_out = covo_iter_slot(h, pass);  // an iterated step: this pass's merge logs its cost minimum there
     const int N = a.n_samples;
     const float *fdev = reinterpret_cast<const float *>(st->dyn + 2);
     float *am_shift = a.a_mean_shift ? a.a_mean_shift : st->a_mean_shift;
@@ -216,7 +230,7 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     // scalars in st->dyn and the state in st->state_buf; MPPI: it has NOT touched a_cov, the fused launch shifts and factors)
     float *lam_rows = covo_lam_target(h);  // the ESS floor: the update's temperature is solved from this step's costs
     if (M == 63 && h->opt.fuse_small && step_small_eligible(h, p, a) && lam_rows == nullptr)
-        return launch_step_small(h, p, a, state, am_shift, nullptr, st->dyn, 0.0f, st->ticket, s);
+        return launch_step_small(h, p, a, state, am_shift, nullptr, st->dyn, 0.0f, st->ticket, s, pass, nullptr, iter_out);
     // periodic / sin / drag / mixed (free.py:10-58): the wave-uniform part of every rollout step's force, for the sampling
     // rollouts (shared step key) and for the Hessian's deterministic rollout (per-step keys), resolved once per control step
     const bool tables = covo_needs_tables(p);
@@ -353,6 +367,7 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     up.diag_rec = h->ws_diag_rec;
     up.diag_out = dg;
     up.lam_rows = lam_rows;
+    up.iter_out = sharded ? nullptr : iter_out;
     if (cov_adapt) {  // mppi.py:109-125: new mean, then a_cov (already shifted by the begin launch) adapted in place; a sharded
                       // rank: its record with the second moments (836-float kind)
         up.a_cov_old = a.a_cov;
@@ -393,30 +408,66 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     const float shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
     // control_params.a_mean of this call: the handle's own buffer (a carried mean) or the caller's input (args->a_mean_in)
     const bool small = h->opt.fuse_small && step_small_eligible(h, *params, *args) && covo_lam_target(h) == nullptr;
+    // covo_set_step_iters: K passes on this state.  Pass j >= 1 starts from the mean pass j - 1 committed (args->a_mean, never the
+    // caller's a_mean_in) and walks the raw key on the device; with the update arbiter attached its launch sits between the passes
+    // (and the passes are enqueued eagerly: the arbiter's launch is not part of any captured graph)
+    const int K = covo_step_iters(h);
+    covo_step_args later = *args;
+    later.a_mean_in = nullptr;
+    auto between = [&](int j) -> int {
+        return (j + 1 < K && covo_arb_on(h)) ? covo_plan_after_step(h, params, args, key0, key1, f_shared, nullptr, -1, s, true) : 0;
+    };
     if (small && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0) {
         // an eager handle: the WHOLE step is one launch, the begin launch's work included (per workgroup, step_small.hip)
         st->cache.have_key = false;  // (st->dyn / st->state_buf are not refreshed: a later graph capture starts from an eager call)
-        return launch_step_small(h, *params, *args, args->state, args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift, &blk,
-                                 nullptr, shared_noise_scale, st->ticket, s);
+        for (int j = 0; j < K; ++j) {
+            // (an iterated step: the last workgroup of every pass parks the pass's raw key at st->dyn[10..11] for the next one)
+            int rc = launch_step_small(h, *params, j ? later : *args, args->state, args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift,
+                                       &blk, nullptr, shared_noise_scale, st->ticket, s, j, K > 1 ? st->dyn + 10 : nullptr,
+                                       covo_iter_slot(h, j));
+            if (rc || (rc = between(j))) return rc;
+        }
+        return 0;
     }
     // eager covo-online steps (no per-step force tables, whose launch precedes the Hessian and reads the scalars): the begin work
     // rides in the Hessian's first launch -- one launch boundary less (COVO_FOLD_BEGIN=0 keeps the begin launch)
     if (h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
         !covo_needs_tables(*params)) {
-        HessBegin hb;
-        hb.a_mean_raw = args->a_mean_in ? args->a_mean_in : args->a_mean;
-        hb.dyn_out = st->dyn;
-        hb.seq = st->sync;
-        hb.blk = &blk;
-        hb.derive_keys = args->derive_keys;
-        hb.shared_noise_scale = shared_noise_scale;
         st->cache.have_key = false;
-        return enqueue_step(h, st, *params, *args, s, DebugMasks(), &hb, args->state);
+        for (int j = 0; j < K; ++j) {
+            HessBegin hb;
+            hb.pass = j;
+            hb.a_mean_raw = j ? args->a_mean : (args->a_mean_in ? args->a_mean_in : args->a_mean);
+            hb.dyn_out = st->dyn;
+            hb.seq = st->sync;
+            hb.blk = &blk;
+            hb.derive_keys = args->derive_keys;
+            hb.shared_noise_scale = shared_noise_scale;
+            int rc = enqueue_step(h, st, *params, *args, s, DebugMasks(), &hb, args->state, j);
+            if (rc || (rc = between(j))) return rc;
+        }
+        return 0;
     }
+    float *mppi_cov = (args->mode == COVO_MODE_MPPI && !small) ? args->a_cov : (float *)nullptr;
+    float *am_shift = args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift;
     hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, s,
-                       args->a_mean_in ? args->a_mean_in : args->a_mean,
-                       args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift, st->dyn, st->state_buf, args->derive_keys,
-                       shared_noise_scale, blk, (args->mode == COVO_MODE_MPPI && !small) ? args->a_cov : (float *)nullptr, st->Ls, st->sync);
+                       args->a_mean_in ? args->a_mean_in : args->a_mean, am_shift, st->dyn, st->state_buf, args->derive_keys,
+                       shared_noise_scale, blk, mppi_cov, st->Ls, st->sync, 0);
+    // the passes behind the begin launch: pass j >= 1 starts with a begin launch of its own, inside the graph
+    auto passes = [&](hipStream_t on, bool with_arbiter) -> int {
+        for (int j = 0; j < K; ++j) {
+            if (j > 0)
+                hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, on, (const float *)args->a_mean,
+                                   am_shift, st->dyn, st->state_buf, 1, shared_noise_scale, DynBlock(), mppi_cov, st->Ls, st->sync, j);
+            int rc = enqueue_step(h, st, *params, *args, on, DebugMasks(), nullptr, nullptr, j);
+            if (rc || (with_arbiter && (rc = between(j)))) return rc;
+        }
+        return 0;
+    };
+    if (K > 1 && covo_arb_on(h)) {
+        st->cache.forget();
+        return passes(s, true);
+    }
 
     StepKey k;
     std::memset(&k, 0, sizeof(k));
@@ -432,18 +483,20 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
         st->key = k;
         st->cache.have_key = true;
     }
-    return graph_cache_run(h, st->cache, s, same, "covo_mpc_step",
-                           [&](hipStream_t on) { return enqueue_step(h, st, *params, *args, on); });
+    return graph_cache_run(h, st->cache, s, same, "covo_mpc_step", [&](hipStream_t on) { return passes(on, false); });
 }
 
 // ---- the flight recorder behind a step (plan_trace.hip): one eager launch that rolls the new mean out with the inputs the step's
 // sample rollouts had.  The shared vector is re-derived from the raw key by the launch itself (every step path forms it from the
 // same device function); the per-step tables are the ones the step has just built in its own scratch.
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s)
+                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
     if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
+    // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
+    // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
+    const bool iterated = covo_step_iters(h) > 1 && st != nullptr;
     PlanInstDesc d;
     std::memset(&d, 0, sizeof(d));
     d.state = args->state;
@@ -460,13 +513,14 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
     d.f_tab = (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr;
     d.key[0] = key0;
     d.key[1] = key1;
+    d.key_mem = iterated ? st->dyn + 10 : nullptr;
     for (int i = 0; i < 3; ++i) d.f_shared[i] = f_shared ? f_shared[i] : 0.0f;
     d.derive_keys = args->derive_keys;
     d.shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
-    int rc = launch_update_arbiter(h, &d, 1, false, trace_index, s);  // first: the plan, the trace's u and the env step see its mean
-    if (rc) return rc;
-    if ((rc = launch_plan_trace(h, &d, 1, false, state_true, trace_index, s))) return rc;
-    return launch_sample_fan(h, &d, 1, false, trace_index, s);  // (the episode's row index: the fan log counts like the trace)
+    int rc = launch_update_arbiter(h, &d, 1, iterated, trace_index, s);  // first: the plan, the trace's u and the env step see its mean
+    if (rc || arbiter_only) return rc;
+    if ((rc = launch_plan_trace(h, &d, 1, iterated, state_true, trace_index, s))) return rc;
+    return launch_sample_fan(h, &d, 1, iterated, trace_index, s);  // (the episode's row index: the fan log counts like the trace)
 }
 
 
@@ -534,7 +588,7 @@ int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const 
         hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, run,
                            args->a_mean_in ? args->a_mean_in : args->a_mean,
                            args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift, st->dyn, st->state_buf, args->derive_keys, 0.0f,
-                           blk, args->mode == COVO_MODE_MPPI ? args->a_cov : (float *)nullptr, st->Ls, st->sync);
+                           blk, args->mode == COVO_MODE_MPPI ? args->a_cov : (float *)nullptr, st->Ls, st->sync, 0);
         COVO_CHECK_HIP(hipStreamSynchronize(run));
     }
     DebugMasks dbg;
@@ -575,15 +629,18 @@ static void batch_upload_keys(uint32_t *dyn, const uint32_t *keys, int E, hipStr
     hipLaunchKernelGGL(batch_set_dyn_kernel, dim3(1), dim3(256), 0, s, dyn, blk, E);
 }
 // per instance: shift the mean (covo.py:201-203); act_key = split(rng_act)[1] (covo.py:212); f_shared = 0 (deterministic)
-__global__ void batch_begin_kernel(const float *__restrict__ a_mean, float *__restrict__ a_mean_shift, uint32_t *__restrict__ dyn)
+// pass >= 1 of an iterated step (covo_set_step_iters): no shift, and the raw key is the previous pass's (d[10..11]) advanced
+__global__ void batch_begin_kernel(const float *__restrict__ a_mean, float *__restrict__ a_mean_shift, uint32_t *__restrict__ dyn,
+                                   const int pass)
 {
     const int e = blockIdx.x, i = threadIdx.x;
     uint32_t *d = dyn + 12 * e;
-    const uint32_t raw[2] = {d[0], d[1]};
+    uint32_t raw[2] = {d[pass ? 10 : 0], d[pass ? 11 : 1]};
     __syncthreads();
     if (i < COVO_NA) {
-        a_mean_shift[e * COVO_NA + i] = (i < COVO_NA - COVO_DU) ? a_mean[e * COVO_NA + i + COVO_DU] : a_mean[e * COVO_NA + i];
+        a_mean_shift[e * COVO_NA + i] = (pass == 0 && i < COVO_NA - COVO_DU) ? a_mean[e * COVO_NA + i + COVO_DU] : a_mean[e * COVO_NA + i];
     } else if (i == COVO_NA) {
+        if (pass) step_begin_advance(raw);
         uint32_t k[2];
         host_split(raw, 1u, k);
         d[0] = k[0];
@@ -741,12 +798,13 @@ void batch_state_destroy(covo_ctx *h)
 // chain of the two halves of the instances on two forked branches, every phase its own launch: 72 700 control-steps/s against
 // 71 200 unforked with the same launches and 76 300 with the persistent tails -- which must not run side by side: two persistent
 // launches can starve each other of workgroup slots, the barriers then time out.)
-static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, hipStream_t s, const DebugMasks &dbg = DebugMasks())
+static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, hipStream_t s, const DebugMasks &dbg = DebugMasks(),
+                         const int pass = 0)
 {
     const int E = a.n_envs, N = a.n_samples;
     const int M = dbg.step;  // 63 outside covo_debug_time_batched (which replays selected launch groups)
     int rc;
-    if (M & 1) hipLaunchKernelGGL(batch_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, b->a_mean_shift, b->dyn);
+    if (M & 1) hipLaunchKernelGGL(batch_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, b->a_mean_shift, b->dyn, pass);
     // covo.py:231: CoVO's sampling rollouts run step_env(deterministic=True); get_hessian likewise (covo.py:152)
     if ((M & 1) && b->tables && (rc = launch_disturb_tables_batched(b->models, a.states, b->dyn, E, 1, b->tab_rollout, b->tab_hess, s)))
         return rc;
@@ -824,6 +882,8 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     // the ESS floor: the rollouts left costs and per-wave minima, no records (covo_step_batched_impl); row e of the solver's output
     // is instance e's temperature
     up.lam_rows = covo_lam_target(h);
+    up.iter_out = covo_iter_slot(h, pass);  // an iterated step: instance e's cost minimum of this pass to iter_log[e][pass]
+    up.iter_stride = covo_step_iters(h);
     if (up.lam_rows != nullptr) {
         if ((rc = launch_ess_lambda(a.cost, N, E, a.groupmin, h->cfg.lam, h->ess_min, covo_lam_target(h), s))) return rc;
         return launch_softmax_reduce(h, up, s);
@@ -928,8 +988,23 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         b->cache.have_key = true;
     }
     batch_upload_keys(b->dyn, keys, E, s);
-    return graph_cache_run(h, b->cache, s, same, "covo_mpc_step_batched",
-                           [&](hipStream_t on) { return batch_enqueue(h, b, *args, on); });
+    // covo_set_step_iters: K passes in one graph; with the update arbiter attached its (eager) launch sits between them and the
+    // passes are enqueued eagerly
+    const int K = covo_step_iters(h);
+    auto passes = [&](hipStream_t on, bool with_arbiter) -> int {
+        for (int j = 0; j < K; ++j) {
+            int rc = batch_enqueue(h, b, *args, on, DebugMasks(), j);
+            if (rc == 0 && with_arbiter && j + 1 < K)
+                rc = covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, on, true);
+            if (rc) return rc;
+        }
+        return 0;
+    };
+    if (K > 1 && covo_arb_on(h)) {
+        b->cache.drop();
+        return passes(s, true);
+    }
+    return graph_cache_run(h, b->cache, s, same, "covo_mpc_step_batched", [&](hipStream_t on) { return passes(on, false); });
 }
 
 // MPPI / covo-offline for E instances: key upload + ONE fused launch (no begin launch: every workgroup shifts its instance's mean
@@ -1010,7 +1085,8 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
             step_small_fill_args(h, q->args_host.data(), e, params[e], sa, q->dyn + 12 * e,
                                  covo_shared_noise_scale(params[e], sa.rollout_deterministic), q->tickets + e,
                                  q->records + (size_t)e * ng * COVO_PARTIAL_FLOATS, q->diag_rec + (size_t)e * ng * 4,
-                                 dg ? dg + (size_t)e * COVO_DIAG_FLOATS : nullptr);
+                                 dg ? dg + (size_t)e * COVO_DIAG_FLOATS : nullptr,
+                                 covo_step_iters(h) > 1 ? h->iter_log + (size_t)e * covo_step_iters(h) : nullptr);
         }
         COVO_CHECK_HIP(hipMemcpy(q->args, q->args_host.data(), q->args_host.size(), hipMemcpyHostToDevice));
         std::memset(&q->key, 0, sizeof(q->key));
@@ -1020,14 +1096,21 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
     }
     batch_upload_keys(q->dyn, keys, E, s);
     const bool mppi = m->mode == COVO_MODE_MPPI;
+    // covo_set_step_iters: K launches of the same kernel in one graph (the last workgroup of instance e's pass leaves the pass's raw
+    // key at q->dyn[12 e + 0..1] for the next pass and for the recorder's launches)
+    const int K = covo_step_iters(h);
     return graph_cache_run(h, q->cache, s, same, "covo_mpc_step_batched_mode", [&](hipStream_t on) {
-        return launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, on);
+        for (int j = 0; j < K; ++j) {
+            const int rc = launch_step_small_batched(h, q->args_host.data(), q->args, E, mppi, on, j);
+            if (rc) return rc;
+        }
+        return 0;
     });
 }
 
 // mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run) or MPPI / COVO_OFFLINE (covo_step_batched_small_impl)
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
-                            const float *states_true, int trace_index, hipStream_t s)
+                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
     if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
@@ -1060,7 +1143,7 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
         d[e].shared_noise_scale = covo_shared_noise_scale(params[e], mode != COVO_MODE_MPPI);  // (CoVO's rollouts are deterministic)
     }
     int rc = launch_update_arbiter(h, d, E, true, trace_index, s);  // first: the plan, the trace's u and the env step see its mean
-    if (rc) return rc;
+    if (rc || arbiter_only) return rc;
     if ((rc = launch_plan_trace(h, d, E, true, states_true, trace_index, s))) return rc;
     return launch_sample_fan(h, d, E, true, trace_index, s);
 }

@@ -36,19 +36,23 @@ __device__ __forceinline__ void mppi_factor_block(const float (&blk)[16], float 
         for (int c = 0; c < 4; ++c) Lt[4 * r + c] = (c <= r) ? (float)A[c][r] : 0.0f;
 }
 
-__device__ __forceinline__ void mppi_prep(float *__restrict__ a_cov, float *__restrict__ Ls)
+// shift = false (pass >= 1 of an iterated step, covo_set_step_iters): a_cov stays where pass 0 shifted it (and where the
+// previous pass's update may have adapted it); only the factors are formed again
+__device__ __forceinline__ void mppi_prep(float *__restrict__ a_cov, float *__restrict__ Ls, const bool shift = true)
 {
     const int t = threadIdx.x;  // >= 32 threads, H = 32 active
     float blk[16];
     if (t < COVO_H) {
-        const float *src = a_cov + 16 * ((t < COVO_H - 1) ? t + 1 : t);
+        const float *src = a_cov + 16 * ((shift && t < COVO_H - 1) ? t + 1 : t);
 #pragma unroll
         for (int i = 0; i < 16; ++i) blk[i] = src[i];
     }
     __syncthreads();  // every block is read before any is overwritten
     if (t >= COVO_H) return;
+    if (shift) {
 #pragma unroll
-    for (int i = 0; i < 16; ++i) a_cov[16 * t + i] = blk[i];
+        for (int i = 0; i < 16; ++i) a_cov[16 * t + i] = blk[i];
+    }
     mppi_factor_block(blk, Ls + 16 * t);
 }
 
@@ -59,6 +63,14 @@ __device__ __forceinline__ void host_split(const uint32_t (&key)[2], uint32_t i,
     rngd::philox4x32_10(i, 0u, 0u, 0x5EEDu, key[0], key[1], r);
     child[0] = r[0];
     child[1] = r[1];
+}
+// The raw key of pass j >= 1 of an iterated control step (covo_set_step_iters): what is left of the previous pass's raw key after
+// that pass has taken act_key and step_key from it (covo.py:212,225): key_j = split(split(key_{j-1})[0])[0], in place
+__device__ __forceinline__ void step_begin_advance(uint32_t (&raw)[2])
+{
+    uint32_t t[2];
+    host_split(raw, 0u, t);
+    host_split(t, 0u, raw);
 }
 __device__ __forceinline__ float host_normal3(const uint32_t (&key)[2], int i)
 {
@@ -117,5 +129,23 @@ __device__ __forceinline__ void step_begin_derive(const int q, const DynBlock &b
             dyn[2 + (q - 1)] = __float_as_uint(f);
         }
     }
+}
+
+// Virtual thread q of pass j >= 1 of an iterated control step (covo_set_step_iters): the per-step scalars derived from the raw key that
+// follows the previous pass's (prev0, prev1) -- passed BY VALUE: the caller has the previous key in registers before this function
+// stores anything, so dyn may be the very block the previous key was loaded from (q = 0 stores the new raw key to dyn[10..11]).
+// raw (out): the pass's raw key.
+__device__ __forceinline__ void step_begin_derive_next(const int q, const uint32_t prev0, const uint32_t prev1, const float shared_noise_scale,
+                                                       uint32_t *__restrict__ dyn, uint32_t (&raw)[2])
+{
+    raw[0] = prev0;
+    raw[1] = prev1;
+    step_begin_advance(raw);
+    DynBlock kb;
+#pragma unroll
+    for (int w = 0; w < 12; ++w) kb.w[w] = 0u;
+    kb.w[0] = raw[0];
+    kb.w[1] = raw[1];
+    step_begin_derive(q, kb, 1, shared_noise_scale, dyn);
 }
 

@@ -81,6 +81,7 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
         Pb.mppi_cov = rebase_global(P_.mppi_cov, Pb.mppi_cov);
         Pb.dyn_mem = rebase_global(P_.dyn_mem, Pb.dyn_mem);
         Pb.a_mean_shift_out = nullptr;  // (the merge blends with the shifted mean in LDS; nobody else reads it)
+        Pb.pass = P_.pass;
     }
     const SmallStepArgs &P = BATCHED ? Pb : P_;
     extern __shared__ __attribute__((aligned(16))) unsigned char ss_raw[];
@@ -94,11 +95,16 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
 
     // ---- phase 0
     const float *__restrict__ a_mean = P.a_mean_in;
+    const int pass = P.pass;  // (wave-uniform: a kernel argument)
+    // the raw key of this pass where no begin launch has left the step's scalars: the caller's (pass 0), or the previous pass's
+    // advanced.  Every deriving thread of every workgroup has loaded it before any workgroup takes its ticket, and only the workgroup
+    // with the last ticket stores the pass's key back
+    uint32_t raw_key[2] = {0u, 0u};
     if (tid < COVO_NA) {
         if (!BATCHED && P.dyn_mem != nullptr) {  // (a captured graph: the begin launch has shifted the mean of THIS replay; a_mean_in is not baked in)
             S.mus[tid] = P.a_mean_shift_out[tid];
         } else {
-            const float v = (tid < COVO_NA - COVO_DU) ? a_mean[tid + COVO_DU] : a_mean[tid];  // covo.py:201-203
+            const float v = (pass == 0 && tid < COVO_NA - COVO_DU) ? a_mean[tid + COVO_DU] : a_mean[tid];  // covo.py:201-203
             S.mus[tid] = v;
             if (blockIdx.x == 0 && P.a_mean_shift_out != nullptr) P.a_mean_shift_out[tid] = v;
         }
@@ -107,21 +113,32 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
             DynBlock kb;
 #pragma unroll
             for (int i = 0; i < 12; ++i) kb.w[i] = 0u;
-            kb.w[0] = P.dyn_mem[0];
-            kb.w[1] = P.dyn_mem[1];
-            step_begin_derive(tid - COVO_NA, kb, 1, P.shared_noise_scale, S.dyn);
+            const uint32_t p0 = P.dyn_mem[0], p1 = P.dyn_mem[1];
+            if (pass > 0) {
+                step_begin_derive_next(tid - COVO_NA, p0, p1, P.shared_noise_scale, S.dyn, raw_key);
+            } else {
+                raw_key[0] = kb.w[0] = p0;
+                raw_key[1] = kb.w[1] = p1;
+                step_begin_derive(tid - COVO_NA, kb, 1, P.shared_noise_scale, S.dyn);
+            }
         } else if (P.dyn_mem != nullptr) {  // a captured graph: the begin launch has left the step's scalars in device memory
             const int q = tid - COVO_NA;
             if (q == 0) { S.dyn[0] = P.dyn_mem[0]; S.dyn[1] = P.dyn_mem[1]; }
             else S.dyn[1 + q] = P.dyn_mem[1 + q];
+        } else if (pass > 0) {  // an eager iterated step: the previous pass's last workgroup has left its raw key at key_io
+            const uint32_t p0 = P.key_io[0], p1 = P.key_io[1];
+            step_begin_derive_next(tid - COVO_NA, p0, p1, P.shared_noise_scale, S.dyn, raw_key);
         } else {
+            raw_key[0] = P.blk.w[0];
+            raw_key[1] = P.blk.w[1];
             step_begin_derive(tid - COVO_NA, P.blk, P.derive_keys, P.shared_noise_scale, S.dyn);
         }
     }
     if (MPPI) {
         if (tid >= SS_BLOCK - COVO_H) {  // the last 32 threads: block t of the SHIFTED covariance = old block t + 1 (mppi.py:43-49)
             const int t = tid - (SS_BLOCK - COVO_H);
-            const float *src = P.mppi_cov + 16 * ((t < COVO_H - 1) ? t + 1 : t);
+            // (pass >= 1 of an iterated step: pass 0's last workgroup has shifted the blocks already)
+            const float *src = P.mppi_cov + 16 * ((pass == 0 && t < COVO_H - 1) ? t + 1 : t);
             float blk[16];
 #pragma unroll
             for (int i = 0; i < 16; ++i) blk[i] = src[i];
@@ -254,7 +271,19 @@ __global__ __launch_bounds__(SS_BLOCK) void step_small_kernel(const SmallStepArg
     if (DIAG) rollout_merge_last_diag<SS_BLOCK>(A, M, S.last, diag_red);
     else rollout_merge_last<SS_BLOCK>(A, M, S.last);
     if (!S.last) return;
-    if (MPPI) {  // the in-place shift of a_cov (mppi.py:43-49): every workgroup took its factors from the old blocks long ago
+    // an iterated step: the merge's cost minimum (the minimum over the merging waves' minima, softmax_merge.hpp phase 1) to this
+    // pass's slot of the iteration log, and the pass's raw key to where the next pass and the recorder's launches read it
+    if (P.iter_out != nullptr && tid == 0) {
+        float m = M.redm[0];
+#pragma unroll
+        for (int i = 1; i < SS_BLOCK / COVO_WAVE; ++i) m = fminf(m, M.redm[i]);
+        P.iter_out[pass] = m;
+    }
+    if (P.key_io != nullptr && tid == COVO_NA) {
+        P.key_io[0] = raw_key[0];
+        P.key_io[1] = raw_key[1];
+    }
+    if (MPPI && pass == 0) {  // the in-place shift of a_cov (mppi.py:43-49): every workgroup took its factors from the old blocks long ago
         float blk[16];
         const int t = tid;
         if (t < COVO_H) {
@@ -292,9 +321,12 @@ bool step_small_eligible(const covo_ctx *h, const covo_env_params &p, const covo
 
 static void fill_small_args(SmallStepArgs &P, covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state,
                             float *a_mean_shift, const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale,
-                            unsigned *ticket, float *records, float *diag_rec, float *diag_out)
+                            unsigned *ticket, float *records, float *diag_rec, float *diag_out, int pass, uint32_t *key_io, float *iter_out)
 {
     std::memset(&P, 0, sizeof(P));
+    P.pass = pass;
+    P.key_io = key_io;
+    P.iter_out = iter_out;
     RolloutDesc ro;
     ro.state = state;
     ro.pos_traj = a.pos_traj;
@@ -369,11 +401,12 @@ static int small_go(const SmallStepArgs &P, const SmallStepArgs *batch, int nb, 
 }
 
 int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state, float *a_mean_shift,
-                      const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s)
+                      const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s,
+                      int pass, uint32_t *key_io, float *iter_slot)
 {
     SmallStepArgs P;
     fill_small_args(P, h, p, a, state, a_mean_shift, blk, dyn_mem, shared_noise_scale, ticket, h->ws_partials, h->ws_diag_rec,
-                    a.partial_out == nullptr ? covo_diag_target(h) : nullptr);
+                    a.partial_out == nullptr ? covo_diag_target(h) : nullptr, pass, key_io, iter_slot ? iter_slot - pass : nullptr);
     int rc = small_attrs_once();
     if (rc) return rc;
     return small_go<false>(P, nullptr, 1, a.mode == COVO_MODE_MPPI, h->cfg.discount == 1.0f, s);
@@ -383,18 +416,20 @@ int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_arg
 size_t step_small_args_bytes(int n) { return (size_t)n * sizeof(SmallStepArgs); }
 
 void step_small_fill_args(covo_ctx *h, void *out, int index, const covo_env_params &p, const covo_step_args &a, const uint32_t *raw_key_mem,
-                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec, float *diag_out)
+                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec, float *diag_out, float *iter_out)
 {
+    // (an iterated step walks the instance's raw key in place: the key upload of the next step overwrites it)
     fill_small_args(reinterpret_cast<SmallStepArgs *>(out)[index], h, p, a, a.state, nullptr, nullptr, raw_key_mem, shared_noise_scale,
-                    ticket, records, diag_rec, diag_out);
+                    ticket, records, diag_rec, diag_out, 0, iter_out ? const_cast<uint32_t *>(raw_key_mem) : nullptr, iter_out);
 }
 
 // all instances alike in mode, sample count, reward, rollover flag and disturbance kind (the caller has checked): instance 0 picks
 // the variant
-int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s)
+int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s, int pass)
 {
     int rc = small_attrs_once();
     if (rc) return rc;
-    return small_go<true>(*reinterpret_cast<const SmallStepArgs *>(args_host), reinterpret_cast<const SmallStepArgs *>(args_dev), n, mppi,
-                          h->cfg.discount == 1.0f, s);
+    SmallStepArgs P0 = *reinterpret_cast<const SmallStepArgs *>(args_host);
+    P0.pass = pass;
+    return small_go<true>(P0, reinterpret_cast<const SmallStepArgs *>(args_dev), n, mppi, h->cfg.discount == 1.0f, s);
 }

@@ -18,13 +18,20 @@ struct SmallStepArgs {
     int derive_keys;
     float shared_noise_scale;
     int nanp;
+    // an iterated step (covo_set_step_iters; pass 0 with key_io and iter_out null is today's launch).  The BATCHED kernel reads `pass`
+    // from its kernel argument (instance 0's block, patched per launch), the rest from the instance's own block
+    int pass;                   // >= 1: no shift -- the starting mean is a_mean_in as it lies; MPPI's covariances stay as pass 0 shifted them
+    uint32_t *key_io;           // where the step's raw key is walked in device memory: pass >= 1 reads the previous pass's raw key there
+                                // and advances it (step_begin_advance); the last workgroup of every pass stores the pass's own
+    float *iter_out;            // [iters]: the last workgroup stores the merge's cost minimum at [pass]
 };
 
 // can the step (args, params) run as the one fused launch?
 bool step_small_eligible(const covo_ctx *h, const covo_env_params &p, const covo_step_args &a);
 // state: the noisy state this launch reads (args.state, or the graph's fixed-address copy); blk / dyn_mem: exactly one non-null
 int launch_step_small(covo_ctx *h, const covo_env_params &p, const covo_step_args &a, const float *state, float *a_mean_shift,
-                      const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s);
+                      const DynBlock *blk, const uint32_t *dyn_mem, float shared_noise_scale, unsigned *ticket, hipStream_t s,
+                      int pass = 0, uint32_t *key_io = nullptr, float *iter_slot = nullptr);
 // why not, in words a caller can act on (null: eligible)
 const char *step_small_refusal(const covo_ctx *h, const covo_env_params &p, const covo_step_args &a);
 // The env-batched form (grid = groups per instance x instances): instance `index`'s argument block, described like a single step
@@ -34,5 +41,6 @@ const char *step_small_refusal(const covo_ctx *h, const covo_env_params &p, cons
 // caller's diagnostic buffer (diag_out null: diagnostics off).  The device copy of the array is the launch's `args_dev`.
 size_t step_small_args_bytes(int n);
 void step_small_fill_args(covo_ctx *h, void *out, int index, const covo_env_params &p, const covo_step_args &a, const uint32_t *raw_key_mem,
-                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec, float *diag_out);
-int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s);
+                          float shared_noise_scale, unsigned *ticket, float *records, float *diag_rec, float *diag_out,
+                          float *iter_out = nullptr);
+int launch_step_small_batched(covo_ctx *h, const void *args_host, const void *args_dev, int n, bool mppi, hipStream_t s, int pass = 0);

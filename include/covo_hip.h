@@ -552,6 +552,27 @@ int covo_set_episode_fan(covo_handle_t h, float *fanlog, int32_t stride);
 #define COVO_ARB_FLOATS 8
 int covo_set_step_arbiter(covo_handle_t h, float *rows, int32_t mask, int32_t n_inst);
 int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride);
+
+/* Iterations per control step: K sample-rollout-update passes per call (additive to ABI 10: COVO_HAS_STEP_ITERS; off by default,
+ * and off changes nothing a caller can observe, graph cache keys included).  A control step with raw key rng_act runs K passes on
+ * its one noisy state, trajectory window and parameter set:
+ *   pass 0      today's step with key_0 = rng_act: it shifts the mean (MPPI: and a_cov).
+ *   pass j >= 1 today's step without the shift -- its starting mean is the mean pass j - 1 committed (after the ESS floor and the
+ *               arbiter, where attached), MPPI's a_cov is not shifted again -- with the raw key
+ *               key_j = split(split(key_{j-1})[0])[0] (what is left of the previous raw key after a pass has taken act_key and
+ *               step_key from it), walked in device memory, and with the gamma_mean blend against its own starting mean.
+ * covo-online recomputes Hessian, Sigma and L at every pass's starting mean; covo-offline reuses L_table[clamp(time)]; MPPI with
+ * gamma_sigma != 0 adapts a_cov in every pass.  The ESS floor and the update arbiter run in every pass (the arbiter's nominal is
+ * the pass's starting mean); a_mean, a_cov, a, cost, the diagnostics, plan, fan, temperature and arbiter rows describe the LAST pass.
+ * iter_log = DEVICE float[n_inst][iters]: entry (e, j) is the minimum sample cost of instance e's pass j, stored by that pass's merge.
+ * iters = 1 or iter_log = NULL: off.  Every step entry point enqueues the K passes (one captured graph holds all of them; with the
+ * arbiter attached the passes are enqueued eagerly around its launch); the episode drivers enqueue K passes, then the env step.
+ * Refused with COVO_E_BADARG before any launch: iters outside [1, COVO_MAX_STEP_ITERS]; a sample-sharded step (partial_out != NULL)
+ * with iters > 1; derive_keys = 0 with iters > 1; covo_debug_time_* with iters > 1; the env-batched MPPI / covo-offline step with
+ * iters > 1 AND the arbiter. */
+#define COVO_HAS_STEP_ITERS 1
+#define COVO_MAX_STEP_ITERS 16
+int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t n_inst);
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
