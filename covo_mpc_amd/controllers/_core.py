@@ -58,26 +58,21 @@ class SamplingCore:
         fan_K = _lib.check_fan(compute_fan, N)
         arb_mask = _lib.check_update(update)
         iters = _lib.check_iters(iters)
-        if iters > 1 and process_group is not None:
+        if process_group is not None:  # what sample-sharded ranks cannot have, refused before the device is looked for
             import torch.distributed as dist
-            if dist.get_world_size(process_group) > 1:
-                raise NotImplementedError(f"iters={iters} on sample-sharded ranks: every pass would need its own exchange of the rank "
-                                          "records (covo_set_step_iters refuses sample-sharded steps)")
-        if arb_mask and process_group is not None:
-            import torch.distributed as dist
-            if dist.get_world_size(process_group) > 1:
-                raise NotImplementedError(f"update={update!r} on sample-sharded ranks: a rank's action and cost buffers hold its shard "
-                                          "only (covo_set_step_arbiter refuses sample-sharded steps)")
-        if fan_K and process_group is not None:
-            import torch.distributed as dist
-            if dist.get_world_size(process_group) > 1:
-                raise NotImplementedError("compute_fan on sample-sharded ranks: a rank's action buffer holds its shard only "
-                                          "(covo_set_step_fan refuses sample-sharded steps)")
-        if ess_min is not None and float(ess_min) != 0.0 and process_group is not None:
-            import torch.distributed as dist
-            if dist.get_world_size(process_group) > 1:
-                raise NotImplementedError(f"ess_min={ess_min} on sample-sharded ranks: a rank sees only its shard's costs "
-                                          "(covo_set_step_ess_floor refuses sample-sharded steps)")
+            sharded = dist.get_world_size(process_group) > 1
+            for is_on, message in (
+                    (iters > 1, f"iters={iters} on sample-sharded ranks: every pass would need its own exchange of the rank "
+                                "records (covo_set_step_iters refuses sample-sharded steps)"),
+                    (arb_mask, f"update={update!r} on sample-sharded ranks: a rank's action and cost buffers hold its shard "
+                               "only (covo_set_step_arbiter refuses sample-sharded steps)"),
+                    (fan_K, "compute_fan on sample-sharded ranks: a rank's action buffer holds its shard only "
+                            "(covo_set_step_fan refuses sample-sharded steps)"),
+                    (ess_min is not None and float(ess_min) != 0.0,
+                     f"ess_min={ess_min} on sample-sharded ranks: a rank sees only its shard's costs "
+                     "(covo_set_step_ess_floor refuses sample-sharded steps)")):
+                if is_on and sharded:
+                    raise NotImplementedError(message)
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -358,6 +353,22 @@ class SamplingCore:
                                             ptr(self.stats_total) if self.compute_info else None, self.stream()),
               "covo_merge_ranks_cov")
         return out_mean, out_cov
+
+    def step_info(self) -> dict:
+        """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
+        lam_info (ess_min), arbiter_info (update) and iter_info (iters) -- views of the core's buffers, no sync, no copy."""
+        out = {}
+        for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info):
+            out.update(info())
+        return out
+
+    def attach_episode_logs(self, episode, rows_left: int):
+        """Bind every log of `episode` this core fills -- diagnostic log (compute_diag), trace (compute_plan), fan log (compute_fan),
+        arbiter log (update) -- for the segment that starts at episode.n_steps: step k of it writes row n_steps + k of each."""
+        self.attach_diag_log(episode, rows_left)
+        self.attach_trace(episode, rows_left)
+        self.attach_fan_log(episode, rows_left)
+        self.attach_arbiter_log(episode, rows_left)
 
     def diag_info(self) -> dict:
         """{"ess", "cost_min", "cost_weighted", "cost_mean"} of the last step as 0-d views of self.diag (no sync, no copy); {} when
@@ -705,14 +716,9 @@ class SamplingCore:
         args, am, _, cov_out = self._prepare_step(mode, episode.noisy_state, a_mean, derive_keys=True, carry_only=True, **kw)
         key = (C.c_uint32 * 2)(int(rng[0]), int(rng[1]))
         env = episode.env
-        # compute_diag: step k of the segment also writes row n_steps + k of the episode's [T + 1, 8] diagnostic log
-        self.attach_diag_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
-        # compute_plan: and row n_steps + k of its [T + 1, 168] trace (true state, noisy state, u, plan)
-        self.attach_trace(episode, int(episode.log.shape[0]) - int(episode.n_steps))
-        # compute_fan: and row n_steps + k of its [T + 1, K, 100] fan log
-        self.attach_fan_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
-        # update = "best" / "guarded": and row n_steps + k of its [T + 1, 8] arbiter log
-        self.attach_arbiter_log(episode, int(episode.log.shape[0]) - int(episode.n_steps))
+        # step k of the segment also writes row n_steps + k of the episode's [T + 1, 8] diagnostic log, [T + 1, 168] trace (true
+        # state, noisy state, u, plan), [T + 1, K, 100] fan log and [T + 1, 8] arbiter log
+        self.attach_episode_logs(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # the env step's auto-reset (base.py:22-40) is a property of the EPISODE, the model constants come from the controller
         params_c = type(params_c).from_buffer_copy(params_c)
         for f in ("reset_traj", "reset_dt", "reset_disturb_scale"):

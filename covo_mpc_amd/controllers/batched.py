@@ -217,10 +217,8 @@ class BatchedCoVOController:
         self._check_ready()
         env = self.env
         keys = np.ascontiguousarray(np.asarray(rngs, dtype=np.uint32).reshape(self.E, 2)).copy()
-        self.core.attach_diag_log(episode, int(episode.log.shape[1]))  # compute_diag: rows n_steps .. of the [E, T + 1, 8] log
-        self.core.attach_trace(episode, int(episode.log.shape[1]))  # compute_plan: rows n_steps .. of the [E, T + 1, 168] trace
-        self.core.attach_fan_log(episode, int(episode.log.shape[1]))  # compute_fan: rows n_steps .. of the [E, T + 1, K, 100] fan log
-        self.core.attach_arbiter_log(episode, int(episode.log.shape[1]))  # update: rows n_steps .. of the [E, T + 1, 8] arbiter log
+        # rows n_steps .. of the [E, T + 1, 8] diagnostic log, [E, T + 1, 168] trace, [E, T + 1, K, 100] fan log, [E, T + 1, 8] arbiter log
+        self.core.attach_episode_logs(episode, int(episode.log.shape[1]))
         online = self.mode == _lib.MODE_COVO_ONLINE
         fn = self.core.lib.covo_run_episode_batched if online else self.core.lib.covo_run_episode_batched_mode
         check(fn(

@@ -216,12 +216,7 @@ class CoVOController(BaseController):
                 a_cov = a_cov.clone() if self.mode == "online" else a_cov
             control_params = control_params.replace(a_mean=a_mean_new, a_cov=a_cov)
             out_info = core.info(dstate) if core.compute_info else {}
-            out_info.update(core.diag_info())  # compute_diag: ess / cost_min / cost_weighted / cost_mean, views of core.diag
-            out_info.update(core.plan_info())  # compute_plan: pos_plan [H, 3] / cost_plan, views of core.plan
-            out_info.update(core.fan_info())   # compute_fan: fan_pos [K, H, 3] / fan_cost [K] / fan_idx [K], views of core.fan
-            out_info.update(core.lam_info())   # ess_min: lam_eff / ess_lam0, views of core.lam_eff
-            out_info.update(core.arbiter_info())  # update: arb_cost [3] / arb_choice / arb_best / arb_cost_chosen, views of core.arbiter
-            out_info.update(core.iter_info())  # iters: iter_cost_min [iters], a view of core.iter_cost_min
+            out_info.update(core.step_info())  # whatever compute_diag / _plan / _fan, ess_min, update and iters attached
             return a_mean_new[0], control_params, out_info
 
         # ---- kernel-by-kernel path with epsilon materialised in HBM (identical values; parity/debug)

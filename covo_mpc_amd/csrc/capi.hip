@@ -112,9 +112,7 @@ int covo_destroy(covo_handle_t h)
     if (!h) return COVO_E_NOHANDLE;
     step_state_destroy(h);
     batch_state_destroy(h);
-    plan_state_destroy(h);
-    fan_state_destroy(h);
-    arbiter_state_destroy(h);
+    after_state_destroy(h);
     exchange_destroy(h);
     int rc = 0;
 #define DESTROY(expr)                                                                                   \
@@ -235,6 +233,13 @@ int covo_noise_blockdiag_philox(covo_handle_t h, const float *Ls, const float *m
     return launch_noise_blockdiag(d, (hipStream_t)stream);
 }
 
+// how the stand-alone entry points treat the caller's action stripes: trusted only under COVO_FLAG_ACTIONS_CLIPPED
+static RolloutClip rollout_clip(const covo_ctx *h)
+{
+    if ((h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) != 0) return ROLLOUT_CLIP_TRUSTED;
+    return covo_propagate_nan(h) ? ROLLOUT_CLIP_REAPPLY_NAN : ROLLOUT_CLIP_REAPPLY;
+}
+
 int covo_rollout_cost(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                       const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
                       const float *a, int32_t N, float *cost_out, float *groupmin, double *pos_stats, void *stream)
@@ -261,8 +266,7 @@ int covo_rollout_cost(covo_handle_t h, const float *state, const float *pos_traj
     d.groupmin = groupmin;
     d.pos_stats = pos_stats;
     d.stats_ws = h->ws_stats;
-    if ((h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) != 0) d.clip = ROLLOUT_CLIP_TRUSTED;
-    else d.clip = covo_propagate_nan(h) ? ROLLOUT_CLIP_REAPPLY_NAN : ROLLOUT_CLIP_REAPPLY;
+    d.clip = rollout_clip(h);
     return launch_rollout(d, (hipStream_t)stream);
 }
 
@@ -312,7 +316,6 @@ int covo_debug_time_rollout(covo_handle_t h, const float *state, const float *po
     CHECK_MODEL(params, "covo_debug_time_rollout");
     REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_debug_time_rollout: disturb_kind=%d needs f_disturb_steps", params->disturb_kind);
     hipStream_t s = (hipStream_t)stream;
-    const bool clipped = (h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) != 0;
     // with_records: the variant the fused step runs (every workgroup also leaves its online-softmax record), when the launch
     // shape allows it there (step.hip: enqueue_step)
     const bool rec = with_records && rollout_workgroups(N, false) <= h->max_red_blocks;
@@ -336,7 +339,7 @@ int covo_debug_time_rollout(covo_handle_t h, const float *state, const float *po
     d.stats_ws = h->ws_stats;
     d.records = rec ? h->ws_partials : nullptr;
     d.lam = h->cfg.lam;
-    d.clip = clipped ? ROLLOUT_CLIP_TRUSTED : ROLLOUT_CLIP_REAPPLY;
+    d.clip = rollout_clip(h);
     auto launch = [&]() { return launch_rollout(d, s); };
     for (int i = 0; i < 3 && !rc && err == hipSuccess; ++i) rc = launch();
     constexpr int BATCHES = 3;
@@ -687,17 +690,8 @@ int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride)
     return 0;
 }
 
-// a step for n_inst instances with diagnostics attached: the buffer has a row for each
-#define CHECK_DIAG(h, n_inst, what)                                                                                       \
-    REQUIRE(covo_diag_target(h) == nullptr || (n_inst) <= covo_diag_capacity(h),                                          \
-            "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, (int)(n_inst), covo_diag_capacity(h))
-#define REFUSE_SHARDED_DIAG(h, args, what)                                                                                \
-    REQUIRE((args)->partial_out == nullptr || covo_diag_target(h) == nullptr,                                             \
-            "%s: sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log) are not available for sample-sharded "   \
-            "steps (partial_out != NULL): the rank records carry no diagnostic sums; detach the buffer", what)
-
 // ---- the ESS floor (ess_lambda.hip).  The captured step graphs bake in the staged launch set, ess_min and where the solver writes:
-// any change bumps the epoch.  The valid range of ess_min depends on the step's sample count: checked at the step (CHECK_ESS_FLOOR)
+// any change bumps the epoch.  The valid range of ess_min depends on the step's sample count: checked at the step (check_step_attachments)
 int covo_set_step_ess_floor(covo_handle_t h, float ess_min, float *lam_out, int32_t n_inst)
 {
     REQUIRE(h, "covo_set_step_ess_floor: null handle");
@@ -724,23 +718,6 @@ int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32
     return launch_ess_lambda(cost, n_samples, n_inst, nullptr, lam0, ess_min, out, (hipStream_t)stream);
 }
 
-// a step of n_samples samples for n_inst instances with a floor attached: ess_min in the range the solver's bracket covers, a row
-// per instance; a sample-sharded step has no floor
-#define CHECK_ESS_FLOOR(h, n_samples, n_inst, what)                                                                        \
-    do {                                                                                                                   \
-        if (covo_lam_target(h) != nullptr) {                                                                               \
-            REQUIRE((h)->ess_min >= 1.0f && (h)->ess_min <= 0.5f * (float)(n_samples),                                      \
-                    "%s: ess_min=%g (covo_set_step_ess_floor) outside [1, n_samples / 2 = %g]", what, (double)(h)->ess_min, \
-                    0.5 * (n_samples));                                                                                    \
-            REQUIRE((n_inst) <= covo_lam_capacity(h), "%s: %d instances, the temperature buffer (covo_set_step_ess_floor) has %d rows", \
-                    what, (int)(n_inst), covo_lam_capacity(h));                                                            \
-        }                                                                                                                  \
-    } while (0)
-#define REFUSE_SHARDED_ESS_FLOOR(h, args, what)                                                                            \
-    REQUIRE((args)->partial_out == nullptr || covo_lam_target(h) == nullptr,                                               \
-            "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for sample-sharded steps (partial_out != NULL): "  \
-            "a rank sees only its shard's costs; turn it off (ess_min = 0)", what, (double)(h)->ess_min)
-
 // ---- the flight recorder (plan_trace.hip).  Its launch is eager and follows the step: attaching or detaching a buffer changes no
 // captured step graph
 int covo_set_step_plan(covo_handle_t h, float *plan, int32_t n_inst)
@@ -761,15 +738,6 @@ int covo_set_episode_trace(covo_handle_t h, float *trace, int32_t stride)
     h->trace_stride = trace ? stride : 0;
     return 0;
 }
-
-// a step for n_inst instances with a plan buffer attached: the buffer has a row for each
-#define CHECK_PLAN(h, n_inst, what)                                                                                       \
-    REQUIRE((h)->plan_out == nullptr || (n_inst) <= (h)->plan_n,                                                          \
-            "%s: %d instances, the plan buffer (covo_set_step_plan) has %d rows", what, (int)(n_inst), (h)->plan_n)
-#define REFUSE_SHARDED_PLAN(h, args, what)                                                                                \
-    REQUIRE((args)->partial_out == nullptr || !covo_plan_on(h),                                                           \
-            "%s: the plan / episode trace (covo_set_step_plan / covo_set_episode_trace) is not available for sample-sharded "   \
-            "steps (partial_out != NULL): a rank holds only its shard's record until the exchange; detach the buffer", what)
 
 // ---- the sample fan (sample_fan.hip).  Like the plan's, its launch is eager and follows the step: no captured step graph changes
 int covo_set_step_fan(covo_handle_t h, float *fan, const int32_t *idx, int32_t K, int32_t n_inst)
@@ -805,20 +773,23 @@ int covo_set_episode_fan(covo_handle_t h, float *fanlog, int32_t stride)
     return 0;
 }
 
-// a step of n_samples samples for n_inst instances with a fan attached
-#define CHECK_FAN(h, n_samples, n_inst, what)                                                                              \
-    do {                                                                                                                   \
-        if (covo_fan_on(h)) {                                                                                              \
-            REQUIRE((h)->fan_K <= (n_samples), "%s: the sample fan (covo_set_step_fan) has K=%d > n_samples=%d", what,     \
-                    (h)->fan_K, (int)(n_samples));                                                                         \
-            REQUIRE((n_inst) <= (h)->fan_n, "%s: %d instances, the fan buffer (covo_set_step_fan) has n_inst=%d", what,    \
-                    (int)(n_inst), (h)->fan_n);                                                                            \
-        }                                                                                                                  \
-    } while (0)
-#define REFUSE_SHARDED_FAN(h, args, what)                                                                                  \
-    REQUIRE((args)->partial_out == nullptr || !covo_fan_on(h),                                                             \
-            "%s: the sample fan (covo_set_step_fan / covo_set_episode_fan) is not available for sample-sharded steps "      \
-            "(partial_out != NULL): a rank's action buffer holds its shard only; detach the buffer", what)
+// covo_rollout_fan, covo_arbitrate: the caller's buffers and shared vector (derive_keys = 0) as the descriptor of a step's instance
+static PlanInstDesc standalone_inst(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params *params,
+                                    const float *f_disturb_shared, const float *f_disturb_steps, const float *a, int N)
+{
+    PlanInstDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a = a;
+    d.N = N;
+    d.f_tab = f_disturb_steps;
+    for (int i = 0; i < 3; ++i) d.f_shared[i] = f_disturb_shared ? f_disturb_shared[i] : 0.0f;
+    return d;
+}
 
 int covo_rollout_fan(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                      const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
@@ -833,21 +804,8 @@ int covo_rollout_fan(covo_handle_t h, const float *state, const float *pos_traj,
     CHECK_MODEL(params, "covo_rollout_fan");
     REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_rollout_fan: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
             params->disturb_kind);
-    PlanInstDesc d;
-    std::memset(&d, 0, sizeof(d));
-    d.state = state;
-    d.pos_traj = pos_traj;
-    d.vel_traj = vel_traj;
-    d.T = T;
-    d.params = params;
-    d.a = a;
-    d.N = N;
-    d.f_tab = f_disturb_steps;
-    for (int i = 0; i < 3; ++i) d.f_shared[i] = f_disturb_shared ? f_disturb_shared[i] : 0.0f;
-    d.derive_keys = 0;  // the shared vector is the caller's
-    RolloutClip clip = ROLLOUT_CLIP_TRUSTED;  // as covo_rollout_cost treats the stripes
-    if ((h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) == 0) clip = covo_propagate_nan(h) ? ROLLOUT_CLIP_REAPPLY_NAN : ROLLOUT_CLIP_REAPPLY;
-    return launch_sample_fan_one(h, d, clip, idx, K, fan_out, (hipStream_t)stream);
+    const PlanInstDesc d = standalone_inst(state, pos_traj, vel_traj, T, params, f_disturb_shared, f_disturb_steps, a, N);
+    return launch_sample_fan_one(h, d, rollout_clip(h), idx, K, fan_out, (hipStream_t)stream);  // the clip covo_rollout_cost applies
 }
 
 // ---- the update arbiter (update_arbiter.hip).  Like the plan's and the fan's, its launch is eager and follows the step: no captured
@@ -880,15 +838,6 @@ int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride)
     return 0;
 }
 
-// a step for n_inst instances with the arbiter attached: the buffer has a row for each
-#define CHECK_ARBITER(h, n_inst, what)                                                                                     \
-    REQUIRE(!covo_arb_on(h) || (n_inst) <= (h)->arb_n, "%s: %d instances, the arbiter buffer (covo_set_step_arbiter) has n_inst=%d", \
-            what, (int)(n_inst), (h)->arb_n)
-#define REFUSE_SHARDED_ARBITER(h, args, what)                                                                              \
-    REQUIRE((args)->partial_out == nullptr || !covo_arb_on(h),                                                             \
-            "%s: the update arbiter (covo_set_step_arbiter) is not available for sample-sharded steps (partial_out != NULL): " \
-            "a rank's action and cost buffers hold its shard only; detach it", what)
-
 // ---- iterations per control step: K sample-rollout-update passes per call on the step's one state (step.hip enqueues them).  The
 // captured step graphs hold all K passes and the log's address: a change bumps the epoch like a debug switch
 int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t n_inst)
@@ -906,19 +855,76 @@ int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t
     return 0;
 }
 
-// a step for n_inst instances on a handle with iterations attached: a row of the log for each; a sample-sharded step would need
-// one exchange per pass; the key chain is walked from the raw controller key
-#define CHECK_ITERS(h, n_inst, what)                                                                                       \
-    REQUIRE(covo_step_iters(h) == 1 || (n_inst) <= (h)->iter_n, "%s: %d instances, the iteration log (covo_set_step_iters) has n_inst=%d", \
-            what, (int)(n_inst), (h)->iter_n)
-#define REFUSE_SHARDED_ITERS(h, args, what)                                                                                \
-    REQUIRE((args)->partial_out == nullptr || covo_step_iters(h) == 1,                                                     \
-            "%s: iterations per step (covo_set_step_iters, iters=%d) are not available for sample-sharded steps (partial_out != NULL): " \
-            "every pass would need its own exchange of the rank records; set iters = 1", what, covo_step_iters(h))
-#define CHECK_ITERS_KEYS(h, args, what)                                                                                    \
-    REQUIRE((args)->derive_keys == 1 || covo_step_iters(h) == 1,                                                           \
-            "%s: iterations per step (covo_set_step_iters, iters=%d) need derive_keys = 1 (every pass derives its keys from the raw " \
-            "controller key on the device)", what, covo_step_iters(h))
+// ---- what a step checks about everything attached to its handle -- diagnostics, plan / trace, sample fan, update arbiter, ESS floor,
+// iterations -- for every entry point alike (covo_mpc_step, covo_run_episode and, through check_batch_step, the four env-batched
+// ones): a step of n_samples samples for n_inst instances.  The order is fixed: first what a sample-sharded step
+// (partial_out != NULL) cannot have at all, in the order above; then, in the same order, each attachment's own ranges and the rows
+// of its buffer.  A new attachment adds its lines here (and its log to check_episode_logs), nowhere else.
+static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, const char *what)
+{
+    if (sharded) {
+        REQUIRE(covo_diag_target(h) == nullptr,
+                "%s: sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log) are not available for sample-sharded "
+                "steps (partial_out != NULL): the rank records carry no diagnostic sums; detach the buffer", what);
+        REQUIRE(!covo_plan_on(h),
+                "%s: the plan / episode trace (covo_set_step_plan / covo_set_episode_trace) is not available for sample-sharded "
+                "steps (partial_out != NULL): a rank holds only its shard's record until the exchange; detach the buffer", what);
+        REQUIRE(!covo_fan_on(h),
+                "%s: the sample fan (covo_set_step_fan / covo_set_episode_fan) is not available for sample-sharded steps "
+                "(partial_out != NULL): a rank's action buffer holds its shard only; detach the buffer", what);
+        REQUIRE(!covo_arb_on(h),
+                "%s: the update arbiter (covo_set_step_arbiter) is not available for sample-sharded steps (partial_out != NULL): "
+                "a rank's action and cost buffers hold its shard only; detach it", what);
+        REQUIRE(covo_lam_target(h) == nullptr,
+                "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for sample-sharded steps (partial_out != NULL): "
+                "a rank sees only its shard's costs; turn it off (ess_min = 0)", what, (double)h->ess_min);
+        REQUIRE(covo_step_iters(h) == 1,
+                "%s: iterations per step (covo_set_step_iters, iters=%d) are not available for sample-sharded steps (partial_out != NULL): "
+                "every pass would need its own exchange of the rank records; set iters = 1", what, covo_step_iters(h));
+    }
+    REQUIRE(covo_diag_target(h) == nullptr || n_inst <= covo_diag_capacity(h),
+            "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, n_inst, covo_diag_capacity(h));
+    REQUIRE(h->plan_out == nullptr || n_inst <= h->plan_n, "%s: %d instances, the plan buffer (covo_set_step_plan) has %d rows", what,
+            n_inst, h->plan_n);
+    if (covo_fan_on(h)) {
+        REQUIRE(h->fan_K <= n_samples, "%s: the sample fan (covo_set_step_fan) has K=%d > n_samples=%d", what, h->fan_K, n_samples);
+        REQUIRE(n_inst <= h->fan_n, "%s: %d instances, the fan buffer (covo_set_step_fan) has n_inst=%d", what, n_inst, h->fan_n);
+    }
+    REQUIRE(!covo_arb_on(h) || n_inst <= h->arb_n, "%s: %d instances, the arbiter buffer (covo_set_step_arbiter) has n_inst=%d", what,
+            n_inst, h->arb_n);
+    if (covo_lam_target(h) != nullptr) {  // ess_min in the range the solver's bracket covers
+        REQUIRE(h->ess_min >= 1.0f && h->ess_min <= 0.5f * (float)n_samples,
+                "%s: ess_min=%g (covo_set_step_ess_floor) outside [1, n_samples / 2 = %g]", what, (double)h->ess_min, 0.5 * n_samples);
+        REQUIRE(n_inst <= covo_lam_capacity(h), "%s: %d instances, the temperature buffer (covo_set_step_ess_floor) has %d rows", what,
+                n_inst, covo_lam_capacity(h));
+    }
+    if (covo_step_iters(h) > 1) {  // the key chain of the passes is walked from the raw controller key
+        REQUIRE(n_inst <= h->iter_n, "%s: %d instances, the iteration log (covo_set_step_iters) has n_inst=%d", what, n_inst, h->iter_n);
+        REQUIRE(derive_keys == 1,
+                "%s: iterations per step (covo_set_step_iters, iters=%d) need derive_keys = 1 (every pass derives its keys from the raw "
+                "controller key on the device)", what, covo_step_iters(h));
+    }
+    return 0;
+}
+
+// an episode driver that writes rows [first_row, first_row + n_steps) of every attached log (the single driver: first_row = 0)
+static int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, const char *what)
+{
+    const struct {
+        const char *name, *setter;
+        bool on;
+        int rows;
+    } logs[] = {
+        {"diagnostic log", "covo_set_episode_diag_log", h->diag_log != nullptr, h->diag_log_stride},
+        {"episode trace", "covo_set_episode_trace", h->trace != nullptr, h->trace_stride},
+        {"episode fan log", "covo_set_episode_fan", h->fanlog != nullptr, h->fanlog_stride},
+        {"episode arbiter log", "covo_set_episode_arbiter_log", h->arblog != nullptr, h->arblog_stride},
+    };
+    for (const auto &l : logs)
+        REQUIRE(!l.on || (first_row >= 0 && first_row + n_steps <= l.rows), "%s: %s rows [%d, %d) outside [0, %d) (%s)", what, l.name,
+                first_row, first_row + n_steps, l.rows, l.setter);
+    return 0;
+}
 
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
@@ -934,25 +940,12 @@ int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, c
     CHECK_MODEL(params, "covo_arbitrate");
     REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_arbitrate: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
             params->disturb_kind);
-    PlanInstDesc d;
-    std::memset(&d, 0, sizeof(d));
-    d.state = state;
-    d.pos_traj = pos_traj;
-    d.vel_traj = vel_traj;
-    d.T = T;
-    d.params = params;
-    d.a = a;
-    d.N = N;
+    PlanInstDesc d = standalone_inst(state, pos_traj, vel_traj, T, params, f_disturb_shared, f_disturb_steps, a, N);
     d.cost = cost;
     d.a_nominal = a_nominal;
     d.a_mean = a_mean_inout;
     d.a_mean_out = a_mean_inout;
-    d.f_tab = f_disturb_steps;
-    for (int i = 0; i < 3; ++i) d.f_shared[i] = f_disturb_shared ? f_disturb_shared[i] : 0.0f;
-    d.derive_keys = 0;  // the shared vector is the caller's
-    RolloutClip clip = ROLLOUT_CLIP_TRUSTED;  // as covo_rollout_cost treats the stripes
-    if ((h->cfg.flags & COVO_FLAG_ACTIONS_CLIPPED) == 0) clip = covo_propagate_nan(h) ? ROLLOUT_CLIP_REAPPLY_NAN : ROLLOUT_CLIP_REAPPLY;
-    return launch_update_arbiter_one(h, d, clip, mask, row_out, (hipStream_t)stream);
+    return launch_update_arbiter_one(h, d, rollout_clip(h), mask, row_out, (hipStream_t)stream);  // the clip covo_rollout_cost applies
 }
 
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)
@@ -1023,24 +1016,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin &&
                 args->T > 0 && args->mode >= 0 && args->mode <= 2,
             "covo_run_episode: bad step arguments");
-    REFUSE_SHARDED_DIAG(h, args, "covo_run_episode");
-    REQUIRE(h->diag_log == nullptr || n_steps <= h->diag_log_stride, "covo_run_episode: %d steps, the diagnostic log "
-            "(covo_set_episode_diag_log) has %d rows", n_steps, h->diag_log_stride);
-    REFUSE_SHARDED_PLAN(h, args, "covo_run_episode");
-    REFUSE_SHARDED_ESS_FLOOR(h, args, "covo_run_episode");
-    CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_run_episode");
-    REQUIRE(h->trace == nullptr || n_steps <= h->trace_stride, "covo_run_episode: %d steps, the episode trace "
-            "(covo_set_episode_trace) has %d rows", n_steps, h->trace_stride);
-    REFUSE_SHARDED_FAN(h, args, "covo_run_episode");
-    CHECK_FAN(h, args->n_samples, 1, "covo_run_episode");
-    REQUIRE(h->fanlog == nullptr || n_steps <= h->fanlog_stride, "covo_run_episode: %d steps, the episode fan log "
-            "(covo_set_episode_fan) has %d rows", n_steps, h->fanlog_stride);
-    REFUSE_SHARDED_ARBITER(h, args, "covo_run_episode");
-    CHECK_ARBITER(h, 1, "covo_run_episode");
-    REFUSE_SHARDED_ITERS(h, args, "covo_run_episode");
-    CHECK_ITERS(h, 1, "covo_run_episode");
-    REQUIRE(h->arblog == nullptr || n_steps <= h->arblog_stride, "covo_run_episode: %d steps, the episode arbiter log "
-            "(covo_set_episode_arbiter_log) has %d rows", n_steps, h->arblog_stride);
+    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, "covo_run_episode");
+    if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -1049,8 +1026,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
         host_philox_split(key, 0u, nrng);
         host_philox_split(key, 1u, rng_act);
         host_philox_split(key, 2u, rng_step);
-        int rc = covo_step_impl(h, params, args, rng_act[0], rng_act[1], nullptr, s);
-        if (rc) return rc;
+        if ((rc = covo_step_impl(h, params, args, rng_act[0], rng_act[1], nullptr, s))) return rc;
         if (args->partial_out != nullptr) {
             // sample-sharded: every rank's record to every rank (peer writes, exchange.hip), then the same merge on all of them.
             // partial_out is this rank's RANK record: {m, s, v} there, its position sums (if any) at + COVO_PARTIAL_FLOATS
@@ -1085,17 +1061,17 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     return 0;
 }
 
-static int check_batch_models(const covo_env_params *params, int E, const char *what)
+// the per-instance models of one env-batched launch: valid selectors, and one kernel variant for all of them.  env_step: the launch
+// also steps the environments (covo_env_step_batched, the episode drivers), whose variant hangs on two more fields
+static int check_batch_models(const covo_env_params *params, int E, bool env_step, const char *what)
 {
     for (int e = 0; e < E; ++e) {
         CHECK_MODEL(&params[e], what);
-        if (params[e].reward_kind != params[0].reward_kind || params[e].rollover_terminate != params[0].rollover_terminate ||
-            params[e].disturb_kind != params[0].disturb_kind || params[e].max_steps_in_episode != params[0].max_steps_in_episode ||
-            params[e].reset_traj != params[0].reset_traj) {
-            covo_set_error("%s: instance %d differs from instance 0 in reward_kind / rollover_terminate / disturb_kind / "
-                           "max_steps_in_episode / reset_traj (one kernel variant per launch)", what, e);
-            return COVO_E_BADARG;
-        }
+        bool same = params[e].reward_kind == params[0].reward_kind && params[e].rollover_terminate == params[0].rollover_terminate &&
+                    params[e].disturb_kind == params[0].disturb_kind;
+        if (env_step) same = same && params[e].max_steps_in_episode == params[0].max_steps_in_episode && params[e].reset_traj == params[0].reset_traj;
+        REQUIRE(same, "%s: instance %d differs from instance 0 in reward_kind / rollover_terminate / disturb_kind%s (one kernel variant "
+                "per launch); disturb_params / period / scale may differ", what, e, env_step ? " / max_steps_in_episode / reset_traj" : "");
     }
     return 0;
 }
@@ -1112,7 +1088,7 @@ int covo_env_step_batched(covo_handle_t h, int32_t n_envs, float *states, float 
             "covo_env_step_batched: bad argument");
     REQUIRE(log == nullptr || (log_index >= 0 && log_index < log_stride), "covo_env_step_batched: log_index=%d outside [0, %d)",
             log_index, log_stride);
-    int rc = check_batch_models(params, n_envs, "covo_env_step_batched");
+    int rc = check_batch_models(params, n_envs, true, "covo_env_step_batched");
     if (rc) return rc;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, n_envs, (hipStream_t)stream, &inst))) return rc;
@@ -1120,10 +1096,11 @@ int covo_env_step_batched(covo_handle_t h, int32_t n_envs, float *states, float 
                                    noisy_on, obs_noise_scale, log, log_stride, log_index, (hipStream_t)stream);
 }
 
-// every argument check of a batched step in `mode` (covo_mpc_step_batched / _mode, covo_run_episode_batched / _mode): nothing
-// is launched before all of them have passed.  *norm: the argument block with its padding zeroed (it is a cache key)
+// every argument check of a batched step in `mode` (covo_mpc_step_batched / _mode, and with episode set covo_run_episode_batched /
+// _mode, whose launches also step the environments): nothing is launched before all of them have passed.  *norm: the argument
+// block with its padding zeroed (it is a cache key)
 static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *m, const covo_env_params *params,
-                            const char *what, covo_batch_mode_args *norm)
+                            bool episode, const char *what, covo_batch_mode_args *norm)
 {
     REQUIRE(args->n_envs > 0 && args->n_envs <= COVO_MAX_ENVS, "%s: n_envs=%d outside (0, %d]", what, args->n_envs, COVO_MAX_ENVS);
     REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "%s: n_samples=%d outside (0, %d]", what, args->n_samples,
@@ -1134,23 +1111,17 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
     REQUIRE(args->states && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost &&
                 (args->groupmin || mode != COVO_MODE_COVO_ONLINE) && args->T > 0,
             "%s: null buffer", what);
-    for (int e = 0; e < args->n_envs; ++e) {
-        CHECK_MODEL(&params[e], what);
-        REQUIRE(params[e].reward_kind == params[0].reward_kind && params[e].rollover_terminate == params[0].rollover_terminate &&
-                    params[e].disturb_kind == params[0].disturb_kind,
-                "%s: all instances must share reward_kind, rollover_terminate and disturb_kind (one kernel "
-                "variant per launch); disturb_params / period / scale may differ", what);
-    }
+    int rc = check_batch_models(params, args->n_envs, episode, what);
+    if (rc) return rc;
     REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_lam_target(h) == nullptr,
             "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for the env-batched MPPI / covo-offline step: its "
             "one fused launch needs the temperature before all costs exist, and there is no staged batched fallback; turn it off "
             "(ess_min = 0)", what, (double)h->ess_min);
-    CHECK_ESS_FLOOR(h, args->n_samples, args->n_envs, what);
-    CHECK_ITERS(h, args->n_envs, what);
     REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_step_iters(h) == 1 || !covo_arb_on(h),
             "%s: iterations per step (covo_set_step_iters, iters=%d) together with the update arbiter (covo_set_step_arbiter) are not "
             "available for the env-batched MPPI / covo-offline step: its fused launch keeps each pass's starting mean in LDS only; "
             "detach one of them", what, covo_step_iters(h));
+    if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, what))) return rc;  // (batched steps derive their keys)
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
     REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),
@@ -1183,29 +1154,12 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     REQUIRE(args && params && states_true && acc_traj && rngs && n_steps > 0, "%s: bad argument", what);
     const int E = args->n_envs;
     covo_batch_mode_args norm;
-    int rc = check_batch_step(h, args, m, params, what, &norm);
+    int rc = check_batch_step(h, args, m, params, true, what, &norm);
     if (rc) return rc;
     const bool online = !m || m->mode == COVO_MODE_COVO_ONLINE;
     REQUIRE(log == nullptr || (log_index >= 0 && log_index + n_steps <= log_stride),
             "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
-    rc = check_batch_models(params, E, what);
-    if (rc) return rc;
-    CHECK_DIAG(h, E, what);
-    REQUIRE(h->diag_log == nullptr || (log_index >= 0 && log_index + n_steps <= h->diag_log_stride),
-            "%s: diagnostic log rows [%d, %d) outside [0, %d) (covo_set_episode_diag_log)", what, log_index, log_index + n_steps,
-            h->diag_log_stride);
-    CHECK_PLAN(h, E, what);
-    REQUIRE(h->trace == nullptr || (log_index >= 0 && log_index + n_steps <= h->trace_stride),
-            "%s: episode trace rows [%d, %d) outside [0, %d) (covo_set_episode_trace)", what, log_index, log_index + n_steps,
-            h->trace_stride);
-    CHECK_FAN(h, args->n_samples, E, what);
-    REQUIRE(h->fanlog == nullptr || (log_index >= 0 && log_index + n_steps <= h->fanlog_stride),
-            "%s: episode fan log rows [%d, %d) outside [0, %d) (covo_set_episode_fan)", what, log_index, log_index + n_steps,
-            h->fanlog_stride);
-    CHECK_ARBITER(h, E, what);
-    REQUIRE(h->arblog == nullptr || (log_index >= 0 && log_index + n_steps <= h->arblog_stride),
-            "%s: episode arbiter log rows [%d, %d) outside [0, %d) (covo_set_episode_arbiter_log)", what, log_index,
-            log_index + n_steps, h->arblog_stride);
+    if ((rc = check_episode_logs(h, log_index, n_steps, what))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -1266,12 +1220,8 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     REQUIRE(h, "covo_mpc_step_batched: null handle");
     CHECK_DEVICE(h, "covo_mpc_step_batched");
     REQUIRE(args && params && keys, "covo_mpc_step_batched: null argument");
-    int rc = check_batch_step(h, args, nullptr, params, "covo_mpc_step_batched", nullptr);
+    int rc = check_batch_step(h, args, nullptr, params, false, "covo_mpc_step_batched", nullptr);
     if (rc) return rc;
-    CHECK_DIAG(h, args->n_envs, "covo_mpc_step_batched");
-    CHECK_PLAN(h, args->n_envs, "covo_mpc_step_batched");
-    CHECK_FAN(h, args->n_samples, args->n_envs, "covo_mpc_step_batched");
-    CHECK_ARBITER(h, args->n_envs, "covo_mpc_step_batched");
     if ((rc = covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream))) return rc;
     return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, (hipStream_t)stream);
 }
@@ -1283,12 +1233,8 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     CHECK_DEVICE(h, "covo_mpc_step_batched_mode");
     REQUIRE(args && params && keys, "covo_mpc_step_batched_mode: null argument");
     covo_batch_mode_args norm;
-    int rc = check_batch_step(h, &args->base, args, params, "covo_mpc_step_batched_mode", &norm);
+    int rc = check_batch_step(h, &args->base, args, params, false, "covo_mpc_step_batched_mode", &norm);
     if (rc) return rc;
-    CHECK_DIAG(h, args->base.n_envs, "covo_mpc_step_batched_mode");
-    CHECK_PLAN(h, args->base.n_envs, "covo_mpc_step_batched_mode");
-    CHECK_FAN(h, args->base.n_samples, args->base.n_envs, "covo_mpc_step_batched_mode");
-    CHECK_ARBITER(h, args->base.n_envs, "covo_mpc_step_batched_mode");
     rc = args->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream)
                                              : covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
     if (rc) return rc;
@@ -1354,19 +1300,9 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
             "covo_mpc_step: gamma_sigma != 0 is MPPI's covariance adaptation (mppi.py:119-125)");
     REQUIRE(!covo_needs_tables(*params) || args->derive_keys == 1, "covo_mpc_step: disturb_kind=%d needs derive_keys = 1 (the per-step "
             "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
-    REFUSE_SHARDED_DIAG(h, args, "covo_mpc_step");
-    REFUSE_SHARDED_PLAN(h, args, "covo_mpc_step");
-    REFUSE_SHARDED_FAN(h, args, "covo_mpc_step");
-    CHECK_FAN(h, args->n_samples, 1, "covo_mpc_step");
-    REFUSE_SHARDED_ARBITER(h, args, "covo_mpc_step");
-    CHECK_ARBITER(h, 1, "covo_mpc_step");
-    REFUSE_SHARDED_ITERS(h, args, "covo_mpc_step");
-    CHECK_ITERS(h, 1, "covo_mpc_step");
-    CHECK_ITERS_KEYS(h, args, "covo_mpc_step");
-    REFUSE_SHARDED_ESS_FLOOR(h, args, "covo_mpc_step");
-    CHECK_ESS_FLOOR(h, args->n_samples, 1, "covo_mpc_step");
-    const int rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream);
+    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, "covo_mpc_step");
     if (rc) return rc;
+    if ((rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream))) return rc;
     return covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream);
 }
 

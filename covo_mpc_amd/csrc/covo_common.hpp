@@ -59,14 +59,12 @@ struct covo_ctx {
     int plan_n;
     float *trace;             // caller's [n_inst][trace_stride][COVO_TRACE_FLOATS]: the episode drivers' steps write their rows there
     int trace_stride;
-    void *plan;               // PlanState (plan_trace.hip): the device copy of a batched step's argument blocks
     // the sample fan (covo_set_step_fan / covo_set_episode_fan; sample_fan.hip); all null / 0: off
     float *fan_out;           // caller's [fan_n][fan_K][COVO_FAN_FLOATS]: instance e's fan of every step
     const int32_t *fan_idx;   // caller's [fan_n][fan_K] sample indices, or null: the stride
     int fan_K, fan_n;
     float *fanlog;            // caller's [n_inst][fanlog_stride][fan_K][COVO_FAN_FLOATS]: the episode drivers' steps write their rows there
     int fanlog_stride;
-    void *fan_state;          // FanState (sample_fan.hip): the device copy of a batched step's argument blocks
     // the ESS floor (covo_set_step_ess_floor; ess_lambda.hip); ess_min == 0: off
     float ess_min;
     float *lam_out;           // caller's [lam_n][COVO_LAM_FLOATS]: instance e's solver row of every step; null: lam_own
@@ -77,7 +75,8 @@ struct covo_ctx {
     int arb_mask, arb_n;      // enabled candidates (bits 0..2), rows of arb_out
     float *arblog;            // caller's [n_inst][arblog_stride][COVO_ARB_FLOATS]: the episode drivers' steps write their rows there
     int arblog_stride;
-    void *arb_state;          // ArbState (update_arbiter.hip): a batched step's argument blocks and nominals on the device
+    // what the three launches that follow a step keep on the device (plan_trace.hip, sample_fan.hip, update_arbiter.hip)
+    void *after;              // AfterState (after_step.hpp): a batched step's argument blocks per launch, the arbiter's nominals
     // iterations per control step (covo_set_step_iters); iters <= 1 or iter_log null: off
     int iters;                // sample-rollout-update passes per control step
     float *iter_log;          // caller's [iter_n][iters]: entry (e, j) = the minimum sample cost of instance e's pass j
@@ -436,8 +435,8 @@ int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, 
 int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_t s, const void **inst_dev);  // step.hip
 // the episode drivers: row e of the step's diagnostics -> row `index` of instance e's diagnostic log
 int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s);
-// plan_trace.hip, sample_fan.hip: what the recorder needs to know about ONE instance of the step that has just been enqueued -- the inputs its
-// sample rollouts had.  key_mem (batched steps): the instance's raw rng_act in device memory; else key / f_shared as covo_mpc_step got them
+// after_step.hpp, plan_trace.hip, sample_fan.hip, update_arbiter.hip: what the launches behind a step need to know about ONE instance of
+// the step that has just been enqueued -- the inputs its sample rollouts had.  key_mem (batched steps): the instance's raw rng_act in device memory; else key / f_shared as covo_mpc_step got them
 struct PlanInstDesc {
     const float *state;       // the noisy state the step planned from [32]
     const float *pos_traj, *vel_traj;
@@ -458,12 +457,10 @@ struct PlanInstDesc {
 };
 int launch_plan_trace(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, const float *states_true, int trace_index,
                       hipStream_t s);
-void plan_state_destroy(covo_ctx *h);
 // sample_fan.hip: the fan of the step that has just been enqueued (no-op with nothing attached); log_index >= 0: an episode
 // driver's step, which also writes its row of the fan log.  launch_sample_fan_one: covo_rollout_fan
 int launch_sample_fan(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s);
 int launch_sample_fan_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const int32_t *idx, int K, float *fan_out, hipStream_t s);
-void fan_state_destroy(covo_ctx *h);
 // update_arbiter.hip: the arbiter of the step that has just been enqueued (no-op with nothing attached), ahead of the plan and fan
 // launches, which then see the arbitrated mean; log_index as for the fan.  launch_update_arbiter_one: covo_arbitrate.
 // launch_arbiter_nominal: shift(a_mean) of n_inst instances into the handle's nominal buffer (a_mean null: only its address) -- the
@@ -471,7 +468,7 @@ void fan_state_destroy(covo_ctx *h);
 int launch_update_arbiter(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s);
 int launch_update_arbiter_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, int mask, float *row_out, hipStream_t s);
 int launch_arbiter_nominal(covo_ctx *h, const float *a_mean, int n_inst, hipStream_t s, const float **nominal_out);
-void arbiter_state_destroy(covo_ctx *h);
+void after_state_destroy(covo_ctx *h);  // (update_arbiter.hip) the three launches' device state: AfterState, after_step.hpp
 // step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
 // states_true + trace_index >= 0: an episode driver's step, which also writes its trace row
 // arbiter_only: the arbiter's launch between two passes of an iterated step (covo_set_step_iters)

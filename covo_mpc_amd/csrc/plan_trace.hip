@@ -18,31 +18,19 @@
 //            state[32], u = a_new[0][0..3], plan row}: the PRE-step state of the env step that follows.
 // The row index travels as a kernel argument, so nothing is captured and no step graph changes.  BATCHED: workgroup e takes its
 // argument block from device memory (pointers through rebase_global, as step_small_kernel<..., BATCHED> does).
-#include <cstring>
-#include <vector>
-#include "rollout_common.hpp"
-#include "step_begin.hpp"
+#include "after_step.hpp"
 
 constexpr int PT_BLOCK = 3 * COVO_WAVE;
 constexpr int PT_CH = 2;
 
 struct PlanArgs {
-    RolloutArgs R;            // the plan rollout: noisy state, trajectories, model, discount, disturbance table; N = 1
+    AfterHead head;           // R: the plan rollout, N = 1
     const float *a_mean;      // [128] the mean the step left
-    const uint32_t *key_mem;  // the raw rng_act of the step in device memory (batched steps), or null: PlanDyn's
     const float *state_true;  // trace: the true state [32], or null
     float *plan_out;          // this instance's row of the plan buffer [COVO_PLAN_FLOATS], or null
     float *trace;             // this instance's trace rows [stride][COVO_TRACE_FLOATS], or null
-    int derive_keys;
-    float shared_noise_scale;
     int nanp;
     int pad_;
-};
-// what changes from step to step: kernel arguments of the eager launch
-struct PlanDyn {
-    uint32_t key[2];       // single step: the raw rng_act
-    uint32_t f_shared[3];  // single step with derive_keys = 0: the caller's shared vector (float bits)
-    int trace_index;       // row of the trace this step writes; < 0: no trace row
 };
 
 // what rp3_stages<..., PLAN> takes in place of the statistics scratch: stage T's lane 0 writes pos[k]; the subscript only lets
@@ -57,22 +45,18 @@ struct PlanLds {
     Rp3Lds<PT_CH> rings;          // 9 KiB
     PlanPos p;
     uint32_t dyn[12];
-    DynBlock kb[4];               // the per-step scalars' input block, one copy per deriving thread (indexed at run time: not in registers)
+    DynBlock kb[4];               // after_derive's
     float cost;
 };
 
 template <bool ROLL, int REWARD, int FDIST, bool BATCHED>
-__global__ __launch_bounds__(PT_BLOCK) void plan_trace_kernel(const PlanArgs P_, const PlanArgs *__restrict__ batch, const PlanDyn dyn)
+__global__ __launch_bounds__(PT_BLOCK) void plan_trace_kernel(const PlanArgs P_, const PlanArgs *__restrict__ batch, const AfterDyn dyn)
 {
     PlanArgs Pb;
     if (BATCHED) {
         Pb = batch[blockIdx.x];
-        Pb.R.state = rebase_global(P_.R.state, Pb.R.state);
-        Pb.R.pos_traj = rebase_global(P_.R.pos_traj, Pb.R.pos_traj);
-        Pb.R.vel_traj = rebase_global(P_.R.vel_traj, Pb.R.vel_traj);
-        Pb.R.f_tab = rebase_global(P_.R.f_tab, Pb.R.f_tab);
+        after_rebase_head(P_.head, Pb.head);
         Pb.a_mean = rebase_global(P_.a_mean, Pb.a_mean);
-        Pb.key_mem = rebase_global(P_.key_mem, Pb.key_mem);
         Pb.state_true = rebase_global(P_.state_true, Pb.state_true);
         Pb.plan_out = rebase_global(P_.plan_out, Pb.plan_out);
         Pb.trace = rebase_global(P_.trace, Pb.trace);
@@ -81,26 +65,11 @@ __global__ __launch_bounds__(PT_BLOCK) void plan_trace_kernel(const PlanArgs P_,
     __shared__ PlanLds S;
     const int tid = threadIdx.x, lane = tid & (COVO_WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const bool has_plan = P_.plan_out != nullptr, has_trace = P_.trace != nullptr && dyn.trace_index >= 0;  // (all instances alike)
-    float *trow = has_trace ? P.trace + (size_t)dyn.trace_index * COVO_TRACE_FLOATS : nullptr;
+    const bool has_plan = P_.plan_out != nullptr, has_trace = P_.trace != nullptr && dyn.row >= 0;  // (all instances alike)
+    float *trow = has_trace ? P.trace + (size_t)dyn.row * COVO_TRACE_FLOATS : nullptr;
 
     // ---- phase 0
-    if (tid < 4) {
-        DynBlock &kb = S.kb[tid];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) kb.w[i] = 0u;
-        if (BATCHED) {
-            kb.w[0] = P.key_mem[0];
-            kb.w[1] = P.key_mem[1];
-        } else {
-            kb.w[0] = dyn.key[0];
-            kb.w[1] = dyn.key[1];
-            kb.w[2] = dyn.f_shared[0];
-            kb.w[3] = dyn.f_shared[1];
-            kb.w[4] = dyn.f_shared[2];
-        }
-        step_begin_derive(tid, kb, P.derive_keys, P.shared_noise_scale, S.dyn);
-    }
+    after_derive(tid, P.head, dyn, BATCHED, S.kb, S.dyn);
     const float4 *__restrict__ am4 = reinterpret_cast<const float4 *>(P.a_mean);
     for (int i = tid; i < COVO_H * COVO_WAVE; i += PT_BLOCK) {
         float4 v = am4[i >> 6];
@@ -109,11 +78,7 @@ __global__ __launch_bounds__(PT_BLOCK) void plan_trace_kernel(const PlanArgs P_,
         S.a[i >> 6][i & (COVO_WAVE - 1)] = v;
     }
     __syncthreads();
-    RolloutArgs A = P.R;
-    A.f_shared_dev = nullptr;
-    A.f_shared[0] = __uint_as_float(S.dyn[2]);
-    A.f_shared[1] = __uint_as_float(S.dyn[3]);
-    A.f_shared[2] = __uint_as_float(S.dyn[4]);
+    RolloutArgs A = after_rollout_args(P.head, S.dyn);
     A.cost = has_plan ? P.plan_out : trow + 68;  // (stage R stores the one cost itself; phase 2 writes the same value again)
 
     // ---- phase 1: the plan rollout (covo.py:227-263 for the one sample a_plan)
@@ -143,60 +108,15 @@ __global__ __launch_bounds__(PT_BLOCK) void plan_trace_kernel(const PlanArgs P_,
 }
 
 // ---- host
-struct PlanState {
-    void *args_dev = nullptr;  // PlanArgs[cap]
-    int cap = 0;
-    std::vector<char> host;    // what args_dev holds
-};
-
-void plan_state_destroy(covo_ctx *h)
-{
-    PlanState *ps = reinterpret_cast<PlanState *>(h->plan);
-    if (!ps) return;
-    (void)hipFree(ps->args_dev);
-    delete ps;
-    h->plan = nullptr;
-}
-
 static void fill_plan_args(PlanArgs &P, covo_ctx *h, const PlanInstDesc &d, int e, const float *states_true)
 {
     std::memset(&P, 0, sizeof(P));
-    RolloutDesc ro;  // one sample; the kernel sets A.cost and leaves no records
-    ro.state = d.state;
-    ro.pos_traj = d.pos_traj;
-    ro.vel_traj = d.vel_traj;
-    ro.T = d.T;
-    ro.params = d.params;
-    ro.f_tab = d.f_tab;
-    ro.N = 1;
-    ro.discount = h->cfg.discount;
-    ro.xcd_groups = 1;
-    ro.clip = ROLLOUT_CLIP_TRUSTED;  // the image is clipped in phase 0
-    fill_rollout_args(P.R, ro, 1);
-    P.R.xcd_remap = 0;
+    after_fill_head(P.head, h, d, ROLLOUT_CLIP_TRUSTED, false);  // one sample, its image is clipped in phase 0; the kernel sets A.cost
     P.a_mean = d.a_mean;
-    P.key_mem = d.key_mem;
     P.state_true = states_true ? states_true + (size_t)e * COVO_STATE_FLOATS : nullptr;
     P.plan_out = h->plan_out ? h->plan_out + (size_t)e * COVO_PLAN_FLOATS : nullptr;
     P.trace = h->trace ? h->trace + (size_t)e * h->trace_stride * COVO_TRACE_FLOATS : nullptr;
-    P.derive_keys = d.derive_keys;
-    P.shared_noise_scale = d.shared_noise_scale;
     P.nanp = covo_propagate_nan(h) ? 1 : 0;
-}
-
-template <bool BATCHED>
-static int plan_go(const PlanArgs &P, const PlanArgs *batch, int n, const PlanDyn &dyn, hipStream_t s)
-{
-#define PT_GO3(ROLL, REWARD, FDIST) hipLaunchKernelGGL((plan_trace_kernel<ROLL, REWARD, FDIST, BATCHED>), dim3(n), dim3(PT_BLOCK), 0, s, P, batch, dyn)
-#define PT_GO2(ROLL, REWARD) do { if (P.R.fdist == 0) PT_GO3(ROLL, REWARD, 0); else if (P.R.fdist == 1) PT_GO3(ROLL, REWARD, 1); else PT_GO3(ROLL, REWARD, 2); } while (0)
-#define PT_GO1(ROLL) do { if (P.R.reward == COVO_REWARD_REALWORLD) PT_GO2(ROLL, 1); else PT_GO2(ROLL, 0); } while (0)
-    if (P.R.rollover) PT_GO1(true);
-    else PT_GO1(false);
-#undef PT_GO1
-#undef PT_GO2
-#undef PT_GO3
-    COVO_CHECK_HIP(hipGetLastError());
-    return 0;
 }
 
 // inst: n_inst instances of ONE step, all alike in reward, rollover switch and disturbance kind (the step's own checks);
@@ -207,43 +127,19 @@ int launch_plan_trace(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool ba
 {
     const bool trace = h->trace != nullptr && trace_index >= 0;
     if (h->plan_out == nullptr && !trace) return 0;
-    PlanDyn dyn;
-    std::memset(&dyn, 0, sizeof(dyn));
-    dyn.trace_index = trace ? trace_index : -1;
-    for (int e = 0; e < n_inst; ++e) {
-        if (inst[e].params->disturb_kind >= COVO_DISTURB_PERIODIC && inst[e].f_tab == nullptr) {
-            covo_set_error("plan trace: disturb_kind=%d needs the step's per-step disturbance table", inst[e].params->disturb_kind);
-            return COVO_E_BADARG;
-        }
-    }
+    const int row = trace ? trace_index : -1;
+    if (int rc = after_check_tables(inst, n_inst, "plan trace")) return rc;
     if (!batched) {
         PlanArgs P;
         fill_plan_args(P, h, inst[0], 0, trace ? states_true : nullptr);
-        dyn.key[0] = inst[0].key[0];
-        dyn.key[1] = inst[0].key[1];
-        for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &inst[0].f_shared[i], 4);
-        return plan_go<false>(P, nullptr, 1, dyn, s);
+        AFTER_DISPATCH(plan_trace_kernel, PT_BLOCK, P, (const PlanArgs *)nullptr, 1, after_dyn_single(inst[0], row), s);
+    } else {
+        std::vector<PlanArgs> now(n_inst);
+        for (int e = 0; e < n_inst; ++e) fill_plan_args(now[e], h, inst[e], e, trace ? states_true : nullptr);
+        ArgBlockCache &c = after_state(h)->plan;
+        if (int rc = c.sync_upload(now.data(), now.size() * sizeof(PlanArgs), sizeof(PlanArgs), s)) return rc;
+        AFTER_DISPATCH(plan_trace_kernel, PT_BLOCK, now[0], (const PlanArgs *)c.dev, n_inst, after_dyn_batched(row), s);
     }
-    PlanState *ps = reinterpret_cast<PlanState *>(h->plan);
-    if (!ps) {
-        ps = new PlanState();
-        h->plan = ps;
-    }
-    std::vector<char> now((size_t)n_inst * sizeof(PlanArgs), 0);
-    PlanArgs *pa = reinterpret_cast<PlanArgs *>(now.data());
-    for (int e = 0; e < n_inst; ++e) fill_plan_args(pa[e], h, inst[e], e, trace ? states_true : nullptr);
-    if (ps->host.size() != now.size() || std::memcmp(ps->host.data(), now.data(), now.size()) != 0) {
-        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old blocks are done
-        if (ps->cap < n_inst) {
-            (void)hipFree(ps->args_dev);
-            ps->args_dev = nullptr;
-            ps->cap = 0;
-            ps->host.clear();
-            COVO_CHECK_HIP(hipMalloc(&ps->args_dev, (size_t)COVO_MAX_ENVS * sizeof(PlanArgs)));
-            ps->cap = COVO_MAX_ENVS;
-        }
-        COVO_CHECK_HIP(hipMemcpy(ps->args_dev, now.data(), now.size(), hipMemcpyHostToDevice));
-        ps->host = now;
-    }
-    return plan_go<true>(pa[0], reinterpret_cast<const PlanArgs *>(ps->args_dev), n_inst, dyn, s);
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
 }

@@ -17,31 +17,18 @@
 //   phase 2  the K rows, coalesced, to the step's fan buffer and / or row `log_index` of the episode's fan log.
 // The row index travels as a kernel argument, so nothing is captured and no step graph changes.  BATCHED: workgroup e takes its
 // argument block from device memory (pointers through rebase_global, as plan_trace_kernel does).
-#include <cstring>
-#include <vector>
-#include "rollout_common.hpp"
-#include "step_begin.hpp"
+#include "after_step.hpp"
 
 constexpr int SF_BLOCK = 3 * COVO_WAVE;
 constexpr int SF_CH = 2;
 
 struct FanArgs {
-    RolloutArgs R;            // the step's sample rollout: noisy state, trajectories, model, discount, disturbance table, a and N;
-                              // R.clip: how phase 0 clips the gathered stripes (the stages then trust the image)
-    const uint32_t *key_mem;  // the raw rng_act of the step in device memory (batched steps), or null: FanDyn's
-    const int32_t *idx;       // [K] the caller's sample indices, or null: the stride
-    float *fan_out;           // this instance's [K][COVO_FAN_FLOATS] of the fan buffer, or null
-    float *fanlog;            // this instance's [stride][K][COVO_FAN_FLOATS] of the episode log, or null
-    int derive_keys;
-    float shared_noise_scale;
+    AfterHead head;      // R: the step's sample rollout with a and N
+    const int32_t *idx;  // [K] the caller's sample indices, or null: the stride
+    float *fan_out;      // this instance's [K][COVO_FAN_FLOATS] of the fan buffer, or null
+    float *fanlog;       // this instance's [stride][K][COVO_FAN_FLOATS] of the episode log, or null
     int K;
     int pad_;
-};
-// what changes from step to step: kernel arguments of the eager launch
-struct FanDyn {
-    uint32_t key[2];       // single step: the raw rng_act
-    uint32_t f_shared[3];  // derive_keys = 0: the caller's shared vector (float bits)
-    int log_index;         // row of the episode log this step writes; < 0: no log row
 };
 
 // what rp3_stages<..., PLAN = 2> takes in place of the statistics scratch: stage T's lane l writes pos[k][.][l]; the subscript
@@ -62,17 +49,13 @@ struct FanLds {
 };
 
 template <bool ROLL, int REWARD, int FDIST, bool BATCHED>
-__global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, const FanArgs *__restrict__ batch, const FanDyn dyn)
+__global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, const FanArgs *__restrict__ batch, const AfterDyn dyn)
 {
     FanArgs Pb;
     if (BATCHED) {
         Pb = batch[blockIdx.x];
-        Pb.R.state = rebase_global(P_.R.state, Pb.R.state);
-        Pb.R.pos_traj = rebase_global(P_.R.pos_traj, Pb.R.pos_traj);
-        Pb.R.vel_traj = rebase_global(P_.R.vel_traj, Pb.R.vel_traj);
-        Pb.R.f_tab = rebase_global(P_.R.f_tab, Pb.R.f_tab);
-        Pb.R.a = rebase_global(P_.R.a, Pb.R.a);
-        Pb.key_mem = rebase_global(P_.key_mem, Pb.key_mem);
+        after_rebase_head(P_.head, Pb.head);
+        Pb.head.R.a = rebase_global(P_.head.R.a, Pb.head.R.a);
         Pb.idx = rebase_global(P_.idx, Pb.idx);
         Pb.fan_out = rebase_global(P_.fan_out, Pb.fan_out);
         Pb.fanlog = rebase_global(P_.fanlog, Pb.fanlog);
@@ -81,27 +64,12 @@ __global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, 
     __shared__ FanLds S;
     const int tid = threadIdx.x, lane = tid & (COVO_WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int K = P_.K, N = P_.R.N;  // (all instances alike)
-    const bool has_fan = P_.fan_out != nullptr, has_log = P_.fanlog != nullptr && dyn.log_index >= 0;
+    const int K = P_.K, N = P_.head.R.N;  // (all instances alike)
+    const bool has_fan = P_.fan_out != nullptr, has_log = P_.fanlog != nullptr && dyn.row >= 0;
     const bool has_idx = P_.idx != nullptr;
 
     // ---- phase 0
-    if (tid < 4) {
-        DynBlock &kb = S.kb[tid];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) kb.w[i] = 0u;
-        if (BATCHED) {
-            kb.w[0] = P.key_mem[0];
-            kb.w[1] = P.key_mem[1];
-        } else {
-            kb.w[0] = dyn.key[0];
-            kb.w[1] = dyn.key[1];
-            kb.w[2] = dyn.f_shared[0];
-            kb.w[3] = dyn.f_shared[1];
-            kb.w[4] = dyn.f_shared[2];
-        }
-        step_begin_derive(tid, kb, P.derive_keys, P.shared_noise_scale, S.dyn);
-    }
+    after_derive(tid, P.head, dyn, BATCHED, S.kb, S.dyn);
     if (wave == 1) {  // the sample of every lane: lanes >= K repeat lane K - 1's
         const int s = lane < K ? lane : K - 1;
         int n;
@@ -115,8 +83,8 @@ __global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, 
     }
     __syncthreads();
     {
-        const float4 *__restrict__ a4 = P.R.a;
-        const int clip = P_.R.clip;
+        const float4 *__restrict__ a4 = P.head.R.a;
+        const int clip = P_.head.R.clip;
         for (int i = tid; i < COVO_H * COVO_WAVE; i += SF_BLOCK) {
             const int k = i >> 6, l = i & (COVO_WAVE - 1);
             float4 v = a4[(size_t)k * N + S.n[l]];
@@ -126,15 +94,11 @@ __global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, 
         }
     }
     __syncthreads();
-    RolloutArgs A = P.R;
+    RolloutArgs A = after_rollout_args(P.head, S.dyn);
     A.N = COVO_WAVE;  // the image holds one full group: every lane is a sample of its own
     A.clip = 0;
     A.cost = nullptr;  // (PLAN = 2: stage R stores nothing)
     A.groupmin = nullptr;
-    A.f_shared_dev = nullptr;
-    A.f_shared[0] = __uint_as_float(S.dyn[2]);
-    A.f_shared[1] = __uint_as_float(S.dyn[3]);
-    A.f_shared[2] = __uint_as_float(S.dyn[4]);
 
     // ---- phase 1: the fan's rollouts (covo.py:227-263 for the samples n_lane)
     float cost = 0.0f;
@@ -146,7 +110,7 @@ __global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, 
     __syncthreads();
 
     // ---- phase 2: the rows
-    float *lrow = has_log ? P.fanlog + (size_t)dyn.log_index * K * COVO_FAN_FLOATS : nullptr;
+    float *lrow = has_log ? P.fanlog + (size_t)dyn.row * K * COVO_FAN_FLOATS : nullptr;
     for (int i = tid; i < K * COVO_FAN_FLOATS; i += SF_BLOCK) {
         const int s = i / COVO_FAN_FLOATS, j = i - s * COVO_FAN_FLOATS;
         float v;
@@ -160,87 +124,26 @@ __global__ __launch_bounds__(SF_BLOCK) void sample_fan_kernel(const FanArgs P_, 
 }
 
 // ---- host
-struct FanState {
-    void *args_dev = nullptr;  // FanArgs[COVO_MAX_ENVS]
-    std::vector<char> host;    // what args_dev holds
-};
-
-void fan_state_destroy(covo_ctx *h)
-{
-    FanState *fs = reinterpret_cast<FanState *>(h->fan_state);
-    if (!fs) return;
-    (void)hipFree(fs->args_dev);
-    delete fs;
-    h->fan_state = nullptr;
-}
-
-template <bool BATCHED>
-static int fan_go(const FanArgs &P, const FanArgs *batch, int n, const FanDyn &dyn, hipStream_t s)
-{
-#define SF_GO3(ROLL, REWARD, FDIST) hipLaunchKernelGGL((sample_fan_kernel<ROLL, REWARD, FDIST, BATCHED>), dim3(n), dim3(SF_BLOCK), 0, s, P, batch, dyn)
-#define SF_GO2(ROLL, REWARD) do { if (P.R.fdist == 0) SF_GO3(ROLL, REWARD, 0); else if (P.R.fdist == 1) SF_GO3(ROLL, REWARD, 1); else SF_GO3(ROLL, REWARD, 2); } while (0)
-#define SF_GO1(ROLL) do { if (P.R.reward == COVO_REWARD_REALWORLD) SF_GO2(ROLL, 1); else SF_GO2(ROLL, 0); } while (0)
-    if (P.R.rollover) SF_GO1(true);
-    else SF_GO1(false);
-#undef SF_GO1
-#undef SF_GO2
-#undef SF_GO3
-    COVO_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 static void fill_fan_args(FanArgs &P, covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const int32_t *idx, int K, float *fan_out,
                           float *fanlog)
 {
     std::memset(&P, 0, sizeof(P));
-    RolloutDesc ro;  // the kernel leaves no costs, minima or records
-    ro.state = d.state;
-    ro.pos_traj = d.pos_traj;
-    ro.vel_traj = d.vel_traj;
-    ro.T = d.T;
-    ro.params = d.params;
-    ro.f_tab = d.f_tab;
-    ro.a = d.a;
-    ro.N = d.N;
-    ro.discount = h->cfg.discount;
-    ro.xcd_groups = 1;
-    ro.clip = clip;
-    fill_rollout_args(P.R, ro, 1);
-    P.R.xcd_remap = 0;
-    P.key_mem = d.key_mem;
+    after_fill_head(P.head, h, d, clip, true);
     P.idx = idx;
     P.fan_out = fan_out;
     P.fanlog = fanlog;
-    P.derive_keys = d.derive_keys;
-    P.shared_noise_scale = d.shared_noise_scale;
     P.K = K;
-}
-
-static int fan_check_tables(const PlanInstDesc *inst, int n_inst)
-{
-    for (int e = 0; e < n_inst; ++e) {
-        if (inst[e].params->disturb_kind >= COVO_DISTURB_PERIODIC && inst[e].f_tab == nullptr) {
-            covo_set_error("sample fan: disturb_kind=%d needs the step's per-step disturbance table", inst[e].params->disturb_kind);
-            return COVO_E_BADARG;
-        }
-    }
-    return 0;
 }
 
 // covo_rollout_fan: one instance, the caller's buffers and shared vector (d.derive_keys = 0), the clip covo_rollout_cost applies
 int launch_sample_fan_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const int32_t *idx, int K, float *fan_out, hipStream_t s)
 {
-    int rc = fan_check_tables(&d, 1);
-    if (rc) return rc;
+    if (int rc = after_check_tables(&d, 1, "sample fan")) return rc;
     FanArgs P;
     fill_fan_args(P, h, d, clip, idx, K, fan_out, nullptr);
-    FanDyn dyn;
-    std::memset(&dyn, 0, sizeof(dyn));
-    dyn.log_index = -1;
-    dyn.key[0] = d.key[0];
-    dyn.key[1] = d.key[1];
-    for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &d.f_shared[i], 4);
-    return fan_go<false>(P, nullptr, 1, dyn, s);
+    AFTER_DISPATCH(sample_fan_kernel, SF_BLOCK, P, (const FanArgs *)nullptr, 1, after_dyn_single(d, -1), s);
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 // inst: n_inst instances of ONE step that has just been enqueued (launch_plan_trace's descriptors, with a and N).  The stripes
@@ -250,12 +153,8 @@ int launch_sample_fan(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool ba
 {
     const bool log = h->fanlog != nullptr && log_index >= 0;
     if (h->fan_out == nullptr && !log) return 0;
-    const int K = h->fan_K;
-    int rc = fan_check_tables(inst, n_inst);
-    if (rc) return rc;
-    FanDyn dyn;
-    std::memset(&dyn, 0, sizeof(dyn));
-    dyn.log_index = log ? log_index : -1;
+    const int K = h->fan_K, row = log ? log_index : -1;
+    if (int rc = after_check_tables(inst, n_inst, "sample fan")) return rc;
     auto fill = [&](FanArgs &P, int e) {
         fill_fan_args(P, h, inst[e], ROLLOUT_CLIP_TRUSTED, h->fan_idx ? h->fan_idx + (size_t)e * K : nullptr, K,
                       h->fan_out ? h->fan_out + (size_t)e * K * COVO_FAN_FLOATS : nullptr,
@@ -264,27 +163,14 @@ int launch_sample_fan(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool ba
     if (!batched) {
         FanArgs P;
         fill(P, 0);
-        dyn.key[0] = inst[0].key[0];
-        dyn.key[1] = inst[0].key[1];
-        for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &inst[0].f_shared[i], 4);
-        return fan_go<false>(P, nullptr, 1, dyn, s);
+        AFTER_DISPATCH(sample_fan_kernel, SF_BLOCK, P, (const FanArgs *)nullptr, 1, after_dyn_single(inst[0], row), s);
+    } else {
+        std::vector<FanArgs> now(n_inst);
+        for (int e = 0; e < n_inst; ++e) fill(now[e], e);
+        ArgBlockCache &c = after_state(h)->fan;
+        if (int rc = c.sync_upload(now.data(), now.size() * sizeof(FanArgs), sizeof(FanArgs), s)) return rc;
+        AFTER_DISPATCH(sample_fan_kernel, SF_BLOCK, now[0], (const FanArgs *)c.dev, n_inst, after_dyn_batched(row), s);
     }
-    FanState *fs = reinterpret_cast<FanState *>(h->fan_state);
-    if (!fs) {
-        fs = new FanState();
-        h->fan_state = fs;
-    }
-    std::vector<char> now((size_t)n_inst * sizeof(FanArgs), 0);
-    FanArgs *pa = reinterpret_cast<FanArgs *>(now.data());
-    for (int e = 0; e < n_inst; ++e) fill(pa[e], e);
-    if (fs->host.size() != now.size() || std::memcmp(fs->host.data(), now.data(), now.size()) != 0) {
-        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old blocks are done
-        if (fs->args_dev == nullptr) {
-            fs->host.clear();
-            COVO_CHECK_HIP(hipMalloc(&fs->args_dev, (size_t)COVO_MAX_ENVS * sizeof(FanArgs)));
-        }
-        COVO_CHECK_HIP(hipMemcpy(fs->args_dev, now.data(), now.size(), hipMemcpyHostToDevice));
-        fs->host = now;
-    }
-    return fan_go<true>(pa[0], reinterpret_cast<const FanArgs *>(fs->args_dev), n_inst, dyn, s);
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
 }

@@ -23,34 +23,21 @@
 //            arbiter row {cost_softmax, cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0}.
 // The row index of the episode log travels as a kernel argument: nothing is captured, no step graph changes.  BATCHED: workgroup e
 // takes its argument block from device memory (pointers through rebase_global, as sample_fan_kernel does).
-#include <cstring>
-#include <vector>
-#include "rollout_common.hpp"
-#include "step_begin.hpp"
+#include "after_step.hpp"
 #include "wave_reduce.hpp"
 
 constexpr int UA_BLOCK = 3 * COVO_WAVE;
 constexpr int UA_CH = 2;
 
 struct ArbArgs {
-    RolloutArgs R;            // the step's sample rollout: noisy state, trajectories, model, discount, disturbance table, a and N;
-                              // R.clip: how phase 0 clips candidate 2's stripe (the stages then trust the image)
-    const float *cost;        // [N] the step's costs
-    const float *a_nominal;   // [128] the shifted mean the step sampled around
-    float *a_mean;            // [128] in: the softmax mean; out: the chosen candidate
-    const uint32_t *key_mem;  // the raw rng_act of the step in device memory (batched steps), or null: ArbDyn's
-    float *row_out;           // this instance's [COVO_ARB_FLOATS] of the arbiter buffer, or null
-    float *arblog;            // this instance's [stride][COVO_ARB_FLOATS] of the episode log, or null
-    int derive_keys;
-    float shared_noise_scale;
+    AfterHead head;          // R: the step's sample rollout with a and N; R.clip applies to candidate 2's stripe
+    const float *cost;       // [N] the step's costs
+    const float *a_nominal;  // [128] the shifted mean the step sampled around
+    float *a_mean;           // [128] in: the softmax mean; out: the chosen candidate
+    float *row_out;          // this instance's [COVO_ARB_FLOATS] of the arbiter buffer, or null
+    float *arblog;           // this instance's [stride][COVO_ARB_FLOATS] of the episode log, or null
     int mask;
     int nanp;
-};
-// what changes from step to step: kernel arguments of the eager launch
-struct ArbDyn {
-    uint32_t key[2];       // single step: the raw rng_act
-    uint32_t f_shared[3];  // derive_keys = 0: the caller's shared vector (float bits)
-    int log_index;         // row of the episode log this step writes; < 0: no log row
 };
 
 // what rp3_stages<..., PLAN = 3> takes in place of the statistics scratch: never touched; the subscript only lets the (never
@@ -83,20 +70,16 @@ __device__ __forceinline__ unsigned long long arb_key(float v, int i)
 __device__ __forceinline__ unsigned long long arb_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
 
 template <bool ROLL, int REWARD, int FDIST, bool BATCHED>
-__global__ __launch_bounds__(UA_BLOCK) void update_arbiter_kernel(const ArbArgs P_, const ArbArgs *__restrict__ batch, const ArbDyn dyn)
+__global__ __launch_bounds__(UA_BLOCK) void update_arbiter_kernel(const ArbArgs P_, const ArbArgs *__restrict__ batch, const AfterDyn dyn)
 {
     ArbArgs Pb;
     if (BATCHED) {
         Pb = batch[blockIdx.x];
-        Pb.R.state = rebase_global(P_.R.state, Pb.R.state);
-        Pb.R.pos_traj = rebase_global(P_.R.pos_traj, Pb.R.pos_traj);
-        Pb.R.vel_traj = rebase_global(P_.R.vel_traj, Pb.R.vel_traj);
-        Pb.R.f_tab = rebase_global(P_.R.f_tab, Pb.R.f_tab);
-        Pb.R.a = rebase_global(P_.R.a, Pb.R.a);
+        after_rebase_head(P_.head, Pb.head);
+        Pb.head.R.a = rebase_global(P_.head.R.a, Pb.head.R.a);
         Pb.cost = rebase_global(P_.cost, Pb.cost);
         Pb.a_nominal = rebase_global(P_.a_nominal, Pb.a_nominal);
         Pb.a_mean = rebase_global(P_.a_mean, Pb.a_mean);
-        Pb.key_mem = rebase_global(P_.key_mem, Pb.key_mem);
         Pb.row_out = rebase_global(P_.row_out, Pb.row_out);
         Pb.arblog = rebase_global(P_.arblog, Pb.arblog);
     }
@@ -104,26 +87,11 @@ __global__ __launch_bounds__(UA_BLOCK) void update_arbiter_kernel(const ArbArgs 
     __shared__ ArbLds S;
     const int tid = threadIdx.x, lane = tid & (COVO_WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int N = P_.R.N, mask = P_.mask;  // (all instances alike)
-    const bool has_row = P_.row_out != nullptr, has_log = P_.arblog != nullptr && dyn.log_index >= 0;
+    const int N = P_.head.R.N, mask = P_.mask;  // (all instances alike)
+    const bool has_row = P_.row_out != nullptr, has_log = P_.arblog != nullptr && dyn.row >= 0;
 
     // ---- phase 0
-    if (tid < 4) {
-        DynBlock &kb = S.kb[tid];
-#pragma unroll
-        for (int i = 0; i < 12; ++i) kb.w[i] = 0u;
-        if (BATCHED) {
-            kb.w[0] = P.key_mem[0];
-            kb.w[1] = P.key_mem[1];
-        } else {
-            kb.w[0] = dyn.key[0];
-            kb.w[1] = dyn.key[1];
-            kb.w[2] = dyn.f_shared[0];
-            kb.w[3] = dyn.f_shared[1];
-            kb.w[4] = dyn.f_shared[2];
-        }
-        step_begin_derive(tid, kb, P.derive_keys, P.shared_noise_scale, S.dyn);
-    }
+    after_derive(tid, P.head, dyn, BATCHED, S.kb, S.dyn);
     {  // the argmin of the step's costs
         const float *__restrict__ c = P.cost;
         int head = (int)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(c) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte line
@@ -158,8 +126,8 @@ __global__ __launch_bounds__(UA_BLOCK) void update_arbiter_kernel(const ArbArgs 
     {
         const float4 *__restrict__ am4 = reinterpret_cast<const float4 *>(P.a_mean);
         const float4 *__restrict__ nom4 = reinterpret_cast<const float4 *>(P.a_nominal);
-        const float4 *__restrict__ a4 = P.R.a;
-        const int clip = P_.R.clip, nanp = P_.nanp;
+        const float4 *__restrict__ a4 = P.head.R.a;
+        const int clip = P_.head.R.clip, nanp = P_.nanp;
         for (int i = tid; i < COVO_H * COVO_WAVE; i += UA_BLOCK) {
             const int k = i >> 6, l = i & (COVO_WAVE - 1);
             float4 v;
@@ -175,15 +143,11 @@ __global__ __launch_bounds__(UA_BLOCK) void update_arbiter_kernel(const ArbArgs 
         }
     }
     __syncthreads();
-    RolloutArgs A = P.R;
+    RolloutArgs A = after_rollout_args(P.head, S.dyn);
     A.N = COVO_WAVE;  // the image holds one full group: every lane is a sample of its own
     A.clip = 0;
     A.cost = nullptr;  // (PLAN = 3: stage R stores nothing)
     A.groupmin = nullptr;
-    A.f_shared_dev = nullptr;
-    A.f_shared[0] = __uint_as_float(S.dyn[2]);
-    A.f_shared[1] = __uint_as_float(S.dyn[3]);
-    A.f_shared[2] = __uint_as_float(S.dyn[4]);
 
     // ---- phase 1: the candidates' rollouts (covo.py:227-263)
     float cost = 0.0f;
@@ -195,7 +159,7 @@ __global__ __launch_bounds__(UA_BLOCK) void update_arbiter_kernel(const ArbArgs 
     __syncthreads();
 
     // ---- phase 2: the decision, the mean, the row
-    float *lrow = has_log ? P.arblog + (size_t)dyn.log_index * COVO_ARB_FLOATS : nullptr;
+    float *lrow = has_log ? P.arblog + (size_t)dyn.row * COVO_ARB_FLOATS : nullptr;
     if (tid == 0) {
         const float inf = __builtin_inff();
         float c[3];
@@ -233,35 +197,20 @@ __global__ void arbiter_nominal_kernel(const float *__restrict__ a_mean, float *
 }
 
 // ---- host
-struct ArbState {
-    void *args_dev = nullptr;   // ArbArgs[COVO_MAX_ENVS]
-    float *nominal = nullptr;   // [COVO_MAX_ENVS][128]
-    std::vector<char> host;     // what args_dev holds
-};
-
-static ArbState *arb_state(covo_ctx *h)
+// the handle's after-step state (after_step.hpp) goes: the three launches' argument blocks and the nominals
+void after_state_destroy(covo_ctx *h)
 {
-    ArbState *as = reinterpret_cast<ArbState *>(h->arb_state);
-    if (!as) {
-        as = new ArbState();
-        h->arb_state = as;
-    }
-    return as;
-}
-
-void arbiter_state_destroy(covo_ctx *h)
-{
-    ArbState *as = reinterpret_cast<ArbState *>(h->arb_state);
+    AfterState *as = reinterpret_cast<AfterState *>(h->after);
     if (!as) return;
-    (void)hipFree(as->args_dev);
+    for (ArgBlockCache *c : {&as->arbiter, &as->plan, &as->fan}) (void)hipFree(c->dev);
     (void)hipFree(as->nominal);
     delete as;
-    h->arb_state = nullptr;
+    h->after = nullptr;
 }
 
 int launch_arbiter_nominal(covo_ctx *h, const float *a_mean, int n_inst, hipStream_t s, const float **nominal_out)
 {
-    ArbState *as = arb_state(h);
+    AfterState *as = after_state(h);
     if (as->nominal == nullptr) COVO_CHECK_HIP(hipMalloc(&as->nominal, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(float)));
     if (a_mean != nullptr) {
         hipLaunchKernelGGL(arbiter_nominal_kernel, dim3(n_inst), dim3(COVO_NA), 0, s, a_mean, as->nominal);
@@ -271,75 +220,28 @@ int launch_arbiter_nominal(covo_ctx *h, const float *a_mean, int n_inst, hipStre
     return 0;
 }
 
-template <bool BATCHED>
-static int arb_go(const ArbArgs &P, const ArbArgs *batch, int n, const ArbDyn &dyn, hipStream_t s)
-{
-#define UA_GO3(ROLL, REWARD, FDIST) hipLaunchKernelGGL((update_arbiter_kernel<ROLL, REWARD, FDIST, BATCHED>), dim3(n), dim3(UA_BLOCK), 0, s, P, batch, dyn)
-#define UA_GO2(ROLL, REWARD) do { if (P.R.fdist == 0) UA_GO3(ROLL, REWARD, 0); else if (P.R.fdist == 1) UA_GO3(ROLL, REWARD, 1); else UA_GO3(ROLL, REWARD, 2); } while (0)
-#define UA_GO1(ROLL) do { if (P.R.reward == COVO_REWARD_REALWORLD) UA_GO2(ROLL, 1); else UA_GO2(ROLL, 0); } while (0)
-    if (P.R.rollover) UA_GO1(true);
-    else UA_GO1(false);
-#undef UA_GO1
-#undef UA_GO2
-#undef UA_GO3
-    COVO_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 static void fill_arb_args(ArbArgs &P, covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, int mask, float *row_out, float *arblog)
 {
     std::memset(&P, 0, sizeof(P));
-    RolloutDesc ro;  // the kernel leaves no costs, minima or records
-    ro.state = d.state;
-    ro.pos_traj = d.pos_traj;
-    ro.vel_traj = d.vel_traj;
-    ro.T = d.T;
-    ro.params = d.params;
-    ro.f_tab = d.f_tab;
-    ro.a = d.a;
-    ro.N = d.N;
-    ro.discount = h->cfg.discount;
-    ro.xcd_groups = 1;
-    ro.clip = clip;
-    fill_rollout_args(P.R, ro, 1);
-    P.R.xcd_remap = 0;
+    after_fill_head(P.head, h, d, clip, true);
     P.cost = d.cost;
     P.a_nominal = d.a_nominal;
     P.a_mean = d.a_mean_out;
-    P.key_mem = d.key_mem;
     P.row_out = row_out;
     P.arblog = arblog;
-    P.derive_keys = d.derive_keys;
-    P.shared_noise_scale = d.shared_noise_scale;
     P.mask = mask;
     P.nanp = covo_propagate_nan(h) ? 1 : 0;
-}
-
-static int arb_check_tables(const PlanInstDesc *inst, int n_inst)
-{
-    for (int e = 0; e < n_inst; ++e) {
-        if (inst[e].params->disturb_kind >= COVO_DISTURB_PERIODIC && inst[e].f_tab == nullptr) {
-            covo_set_error("update arbiter: disturb_kind=%d needs the step's per-step disturbance table", inst[e].params->disturb_kind);
-            return COVO_E_BADARG;
-        }
-    }
-    return 0;
 }
 
 // covo_arbitrate: one instance, the caller's buffers and shared vector (d.derive_keys = 0), the clip covo_rollout_cost applies
 int launch_update_arbiter_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, int mask, float *row_out, hipStream_t s)
 {
-    int rc = arb_check_tables(&d, 1);
-    if (rc) return rc;
+    if (int rc = after_check_tables(&d, 1, "update arbiter")) return rc;
     ArbArgs P;
     fill_arb_args(P, h, d, clip, mask, row_out, nullptr);
-    ArbDyn dyn;
-    std::memset(&dyn, 0, sizeof(dyn));
-    dyn.log_index = -1;
-    dyn.key[0] = d.key[0];
-    dyn.key[1] = d.key[1];
-    for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &d.f_shared[i], 4);
-    return arb_go<false>(P, nullptr, 1, dyn, s);
+    AFTER_DISPATCH(update_arbiter_kernel, UA_BLOCK, P, (const ArbArgs *)nullptr, 1, after_dyn_single(d, -1), s);
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
 }
 
 // inst: n_inst instances of ONE step that has just been enqueued (launch_plan_trace's descriptors, with a, N, cost, a_nominal and
@@ -348,12 +250,8 @@ int launch_update_arbiter_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip cl
 int launch_update_arbiter(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s)
 {
     if (!covo_arb_on(h)) return 0;
-    const bool log = h->arblog != nullptr && log_index >= 0;
-    int rc = arb_check_tables(inst, n_inst);
-    if (rc) return rc;
-    ArbDyn dyn;
-    std::memset(&dyn, 0, sizeof(dyn));
-    dyn.log_index = log ? log_index : -1;
+    const int row = (h->arblog != nullptr && log_index >= 0) ? log_index : -1;
+    if (int rc = after_check_tables(inst, n_inst, "update arbiter")) return rc;
     auto fill = [&](ArbArgs &P, int e) {
         fill_arb_args(P, h, inst[e], ROLLOUT_CLIP_TRUSTED, h->arb_mask, h->arb_out + (size_t)e * COVO_ARB_FLOATS,
                       h->arblog ? h->arblog + (size_t)e * h->arblog_stride * COVO_ARB_FLOATS : nullptr);
@@ -361,23 +259,14 @@ int launch_update_arbiter(covo_ctx *h, const PlanInstDesc *inst, int n_inst, boo
     if (!batched) {
         ArbArgs P;
         fill(P, 0);
-        dyn.key[0] = inst[0].key[0];
-        dyn.key[1] = inst[0].key[1];
-        for (int i = 0; i < 3; ++i) std::memcpy(&dyn.f_shared[i], &inst[0].f_shared[i], 4);
-        return arb_go<false>(P, nullptr, 1, dyn, s);
+        AFTER_DISPATCH(update_arbiter_kernel, UA_BLOCK, P, (const ArbArgs *)nullptr, 1, after_dyn_single(inst[0], row), s);
+    } else {
+        std::vector<ArbArgs> now(n_inst);
+        for (int e = 0; e < n_inst; ++e) fill(now[e], e);
+        ArgBlockCache &c = after_state(h)->arbiter;
+        if (int rc = c.sync_upload(now.data(), now.size() * sizeof(ArbArgs), sizeof(ArbArgs), s)) return rc;
+        AFTER_DISPATCH(update_arbiter_kernel, UA_BLOCK, now[0], (const ArbArgs *)c.dev, n_inst, after_dyn_batched(row), s);
     }
-    ArbState *as = arb_state(h);
-    std::vector<char> now((size_t)n_inst * sizeof(ArbArgs), 0);
-    ArbArgs *pa = reinterpret_cast<ArbArgs *>(now.data());
-    for (int e = 0; e < n_inst; ++e) fill(pa[e], e);
-    if (as->host.size() != now.size() || std::memcmp(as->host.data(), now.data(), now.size()) != 0) {
-        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old blocks are done
-        if (as->args_dev == nullptr) {
-            as->host.clear();
-            COVO_CHECK_HIP(hipMalloc(&as->args_dev, (size_t)COVO_MAX_ENVS * sizeof(ArbArgs)));
-        }
-        COVO_CHECK_HIP(hipMemcpy(as->args_dev, now.data(), now.size(), hipMemcpyHostToDevice));
-        as->host = now;
-    }
-    return arb_go<true>(pa[0], reinterpret_cast<const ArbArgs *>(as->args_dev), n_inst, dyn, s);
+    COVO_CHECK_HIP(hipGetLastError());
+    return 0;
 }

@@ -378,6 +378,46 @@ def test_batched_arbiter_equals_single(name, update):
     b.core.close()
 
 
+@pytest.mark.parametrize("name", ["mppi", "covo-online"])
+def test_batched_after_step_launches_follow_rebound_instances(name):
+    """The three launches behind an env-batched step (arbiter, plan, fan) read their argument blocks from device copies that are
+    re-uploaded only when they change.  E = 2, N = 64 (one 64-sample group: the smallest the fan and the arbiter's argmin take with
+    K = 4), plan + fan + update="guarded": two steps, set_instances with freshly allocated trajectories of another task -- every
+    launch's blocks change -- two more.  After every step a_mean[e], plan[e], fan[e] and arbiter[e] equal the single controller's on
+    instance e alone, bit for bit."""
+    import covo_mpc_amd as cm
+    N, E, K = 64, 2, 4
+    env, params, reset_keys = _batch_setup(E)
+    other = _env(task="tracking_zigzag", randomizer=True)
+    starts = [[e_.reset(reset_keys[e], params[e]) for e in range(E)] for e_ in (env, other)]  # [phase][e] = (obs, info, state)
+    act = [np.stack([np.asarray(cr.PRNGKey(60 + 10 * k + e)) for e in range(E)]) for k in range(4)]
+    kw = dict(compute_plan=True, compute_fan=K, update="guarded")
+    want = []  # [e][k] = (a_mean, plan row, fan rows, arbiter row)
+    for e in range(E):
+        c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam0.01", device=DEV, compute_info=False, **kw)
+        cp, w = c.init_control_params, []
+        for k in range(4):
+            _, cp, _ = c(None, None, params[e], act[k][e], cp, {"noisy_state": starts[k // 2][e][1]["noisy_state"]})
+            torch.cuda.synchronize()
+            w.append((cp.a_mean.reshape(-1).clone(), c.core.plan[0].clone(), c.core.fan[0].clone(), c.core.arbiter[0].clone()))
+        want.append(w)
+        cp0 = c.init_control_params
+        c.core.close()
+    b = _batched(env, name, cp0, E, N, **kw)
+    assert tuple(b.plan.shape) == (E, _lib.COVO_PLAN_FLOATS) and tuple(b.fan.shape) == (E, K, _lib.COVO_FAN_FLOATS)
+    for k in range(4):
+        if k % 2 == 0:
+            b.set_instances([s[2] for s in starts[k // 2]], params)
+        b([s[1]["noisy_state"] for s in starts[k // 2]], act[k])
+        torch.cuda.synchronize()
+        for e in range(E):
+            got = (b.a_mean[e].reshape(-1), b.plan[e], b.fan[e], b.arbiter[e])
+            for what, g, w in zip(("a_mean", "plan", "fan", "arbiter"), got, want[e][k]):
+                assert torch.equal(g, w), (name, k, e, what, g, w)
+    assert b.core.device_status() == 0
+    b.core.close()
+
+
 def _set_time(ep, e, t):
     bits = torch.tensor([t], dtype=torch.int32, device=DEV).view(torch.float32)
     ep.true[e, ST_TIME:ST_TIME + 1] = bits
