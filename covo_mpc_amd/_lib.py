@@ -37,6 +37,9 @@ COVO_ARB_FLOATS = 8  # an arbiter row: {cost_softmax, cost_nominal, cost_best, c
 COVO_MAX_STEP_ITERS = 16  # iters= of the controllers: sample-rollout-update passes per control step (covo_hip.h: COVO_HAS_STEP_ITERS)
 UPDATE_MASKS = {"softmax": 0, "best": 0b110, "guarded": 0b111}  # update= of the controllers -> the arbiter's candidate mask (0: detached)
 LAM_FIELDS = ("lam_eff", "inv_lam_eff", "ess_lam0", "evaluations")
+COVO_HAS_ELITE_UPDATE = 1
+COVO_ELITE_FLOATS = 8  # the elite-set update's selector row of one instance (covo_set_step_elite)
+ELITE_FIELDS = ("threshold_cost_word", "threshold_index_word", "cost_min", "cost_kth", "K", "ties")  # words: uint32 bits
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -168,6 +171,8 @@ _SIGS = {
     "covo_set_episode_diag_log": (C.c_int, [_P, _P, C.c_int32]),
     "covo_set_step_ess_floor": (C.c_int, [_P, C.c_float, _P, C.c_int32]),  # the ESS floor (covo_hip.h: COVO_HAS_ESS_FLOOR)
     "covo_ess_lambda": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
+    "covo_set_step_elite": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # the elite-set update (covo_hip.h: COVO_HAS_ELITE_UPDATE)
+    "covo_elite_select": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "covo_set_step_plan": (C.c_int, [_P, _P, C.c_int32]),             # the flight recorder (covo_hip.h: COVO_HAS_PLAN_TRACE)
     "covo_set_episode_trace": (C.c_int, [_P, _P, C.c_int32]),
     "covo_rollout_fan": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P,
@@ -253,6 +258,24 @@ def check_iters(iters) -> int:
     if isinstance(iters, bool) or not isinstance(iters, numbers.Integral) or not 1 <= int(iters) <= COVO_MAX_STEP_ITERS:
         raise ValueError(f"iters={iters!r} outside [1, {COVO_MAX_STEP_ITERS}] (an integer number of passes per control step; 1 = off)")
     return int(iters)
+
+
+def check_elite(elite, N, ess_min=None, gamma_sigma=None) -> int:
+    """elite= of the controllers -> the elite count K (0: off): None / False / 0 mean off; anything else must be an integer in [1, N].
+    With ess_min set as well: ValueError (both define the update's weights).  gamma_sigma (MPPI): a full refit, gamma_sigma >= 1,
+    from K < 5 samples raises ValueError -- a 4 x 4 block refitted from K samples about their own mean has rank <= K - 1."""
+    import numbers
+    if elite is None or elite is False or (isinstance(elite, numbers.Integral) and not isinstance(elite, bool) and int(elite) == 0):
+        return 0
+    if isinstance(elite, bool) or not isinstance(elite, numbers.Integral) or not 1 <= int(elite) <= int(N):
+        raise ValueError(f"elite={elite!r} outside [1, N={N}] (an integer number of elite samples; None = off)")
+    K = int(elite)
+    if ess_min is not None and float(ess_min) != 0.0:
+        raise ValueError(f"elite={K} together with ess_min={ess_min}: both define the update's weights; give one of them")
+    if gamma_sigma is not None and float(gamma_sigma) >= 1.0 and K < 5:
+        raise ValueError(f"elite={K} with gamma_sigma={gamma_sigma}: a 4 x 4 covariance block refitted from K < 5 samples about their "
+                         "own mean is singular (rank <= K - 1); take K >= 5 or gamma_sigma < 1")
+    return K
 
 
 def ptr(t):

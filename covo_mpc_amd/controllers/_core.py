@@ -53,11 +53,12 @@ class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None):
         import torch
         fan_K = _lib.check_fan(compute_fan, N)
         arb_mask = _lib.check_update(update)
         iters = _lib.check_iters(iters)
+        elite_K = _lib.check_elite(elite, N, ess_min)
         if process_group is not None:  # what sample-sharded ranks cannot have, refused before the device is looked for
             import torch.distributed as dist
             sharded = dist.get_world_size(process_group) > 1
@@ -70,7 +71,9 @@ class SamplingCore:
                             "(covo_set_step_fan refuses sample-sharded steps)"),
                     (ess_min is not None and float(ess_min) != 0.0,
                      f"ess_min={ess_min} on sample-sharded ranks: a rank sees only its shard's costs "
-                     "(covo_set_step_ess_floor refuses sample-sharded steps)")):
+                     "(covo_set_step_ess_floor refuses sample-sharded steps)"),
+                    (elite_K, f"elite={elite_K} on sample-sharded ranks: a rank sees only its shard's costs "
+                              "(covo_set_step_elite refuses sample-sharded steps)")):
                 if is_on and sharded:
                     raise NotImplementedError(message)
         if H != COVO_H:
@@ -211,6 +214,16 @@ class SamplingCore:
         if self.ess_min != 0.0:
             self.lam_eff = torch.zeros((int(diag_rows), _lib.COVO_LAM_FLOATS), **f32)
             check(self.lib.covo_set_step_ess_floor(self.h, self.ess_min, ptr(self.lam_eff), int(diag_rows)), "covo_set_step_ess_floor")
+        # elite = K: the elite-set update, the cross-entropy method's rule -- every step (every pass of an iterated one) selects the K
+        # samples of smallest key {cost, index} on the device, exactly, and updates with weight 1 on them and 0 on the rest: the new
+        # mean is their average (blended by gamma_mean), MPPI with gamma_sigma != 0 refits a_cov to them -- and leaves {bits(threshold
+        # cost word), bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0} in self.elite_rows (row e = instance
+        # e of a batched step) (covo_set_step_elite, csrc/elite_select.hip, csrc/reduce_elite.hip); off by default, and off changes nothing
+        self.elite = elite_K
+        self.elite_rows = None
+        if elite_K:
+            self.elite_rows = torch.zeros((int(diag_rows), _lib.COVO_ELITE_FLOATS), **f32)
+            check(self.lib.covo_set_step_elite(self.h, elite_K, ptr(self.elite_rows), int(diag_rows)), "covo_set_step_elite")
         # iters = k > 1: every control step runs k sample-rollout-update passes on its one state -- pass 0 is today's step, pass
         # j >= 1 starts from the mean pass j - 1 committed (no shift) with the raw key split(split(key_{j-1})[0])[0], walked on the
         # device -- and leaves the minimum sample cost of every pass in self.iter_cost_min (row e = instance e of a batched step)
@@ -356,9 +369,10 @@ class SamplingCore:
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
-        lam_info (ess_min), arbiter_info (update) and iter_info (iters) -- views of the core's buffers, no sync, no copy."""
+        lam_info (ess_min), arbiter_info (update), iter_info (iters) and elite_info (elite) -- views of the core's buffers, no sync, no
+        copy."""
         out = {}
-        for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info):
+        for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info, self.elite_info):
             out.update(info())
         return out
 
@@ -463,6 +477,25 @@ class SamplingCore:
             return {}
         return {"iter_cost_min": self.iter_cost_min[0]}
 
+    def elite_info(self) -> dict:
+        """{"elite_cost_max" (the K-th smallest cost), "elite_cost_min", "elite_count"} of the last step as 0-d views of self.elite_rows
+        (no sync, no copy); {} when the core was built without elite."""
+        if self.elite_rows is None:
+            return {}
+        return {"elite_cost_max": self.elite_rows[0, 3], "elite_cost_min": self.elite_rows[0, 2], "elite_count": self.elite_rows[0, 4]}
+
+    def elite_select(self, cost, K):
+        """covo_elite_select (the stand-alone selector): cost float32 device tensor [N] or [E, N] -> float32 [E, 8] rows
+        {bits(threshold cost word), bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0}; the elite set of
+        instance e is {n : key(n) <= threshold}, key(n) = (u(cost[e, n]) << 32) | n (include/covo_hip.h)."""
+        torch = self.torch
+        assert cost.is_cuda and cost.dtype == torch.float32 and cost.is_contiguous()
+        c2 = cost.reshape(1, -1) if cost.dim() == 1 else cost
+        E, N = int(c2.shape[0]), int(c2.shape[1])
+        out = torch.empty((E, _lib.COVO_ELITE_FLOATS), dtype=torch.float32, device=self.device)
+        check(self.lib.covo_elite_select(self.h, ptr(cost), N, E, int(K), ptr(out), self.stream()), "covo_elite_select")
+        return out
+
     def lam_info(self) -> dict:
         """{"lam_eff", "ess_lam0"} of the last step as 0-d views of self.lam_eff (no sync, no copy); {} when the core was built
         without ess_min."""
@@ -482,6 +515,9 @@ class SamplingCore:
         if self.ess_min != 0.0:
             raise NotImplementedError("ess_min acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') updates at the configured lam")
+        if getattr(self, "elite", 0):
+            raise NotImplementedError(f"elite={self.elite} acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') updates with the softmax weights")
         if self.compute_plan:
             raise NotImplementedError("compute_plan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")

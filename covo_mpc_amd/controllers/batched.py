@@ -29,10 +29,14 @@ class BatchedCoVOController:
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None):
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)
+        if _lib.check_elite(elite, N, ess_min) and (self.MODE is not None or mode != "online"):
+            raise NotImplementedError(f"elite={elite}: the elite-set update is not available for the env-batched MPPI / covo-offline step "
+                                      "(one fused launch: it needs the weights before all costs exist); "
+                                      "BatchedCoVOController(mode=\"online\") and the single controllers take it")
         if iters > 1 and update != "softmax" and (self.MODE is not None or mode != "online"):
             raise NotImplementedError(f"iters={iters} with update={update!r}: not available for the env-batched MPPI / covo-offline step "
                                       "(its fused launch keeps each pass's starting mean in LDS only); "
@@ -59,7 +63,10 @@ class BatchedCoVOController:
         # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters)
+                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite)
+        # elite = K: after a call, self.elite [E, 8] holds every instance's selector row of that step: {bits(threshold cost word),
+        # bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0} (include/covo_hip.h); None without it
+        self.elite = self.core.elite_rows
         # iters = k > 1: after a call, self.iter_cost_min [E, k] holds the minimum sample cost of every pass of every instance; None under 1
         self.iter_cost_min = self.core.iter_cost_min
         # update = "best" / "guarded": after a call, self.arbiter [E, 8] holds every instance's arbiter row of that step: {cost_softmax,
@@ -238,7 +245,7 @@ class BatchedMPPIController(BatchedCoVOController):
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1):
+                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None):
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)
@@ -248,7 +255,7 @@ class BatchedMPPIController(BatchedCoVOController):
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
                          a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                         compute_fan=compute_fan, update=update, iters=iters)
+                         compute_fan=compute_fan, update=update, iters=iters, elite=elite)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

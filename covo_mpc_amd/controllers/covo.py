@@ -46,11 +46,13 @@ class CoVOParams:
 class CoVOController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, mode: str = "online", *, device=None,
                  process_group=None, compute_info: bool = True, propagate_nan=None, compute_diag: bool = False,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1) -> None:
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1,
+                 elite=None) -> None:
         from .. import _lib
         _lib.check_fan(compute_fan, N)  # ValueError before anything is built
         _lib.check_update(update)
         _lib.check_iters(iters)
+        _lib.check_elite(elite, N, ess_min)
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -71,7 +73,7 @@ class CoVOController(BaseController):
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
                                  compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan,
                                  compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters)
+                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite)
 
     def _needs_table(self, params_c) -> bool:
         """periodic / sin / drag / mixed (free.py:10-58): quadjax's deterministic=True only zeroes dyn_noise_scale
@@ -216,7 +218,7 @@ class CoVOController(BaseController):
                 a_cov = a_cov.clone() if self.mode == "online" else a_cov
             control_params = control_params.replace(a_mean=a_mean_new, a_cov=a_cov)
             out_info = core.info(dstate) if core.compute_info else {}
-            out_info.update(core.step_info())  # whatever compute_diag / _plan / _fan, ess_min, update and iters attached
+            out_info.update(core.step_info())  # whatever compute_diag / _plan / _fan, ess_min, update, iters and elite attached
             return a_mean_new[0], control_params, out_info
 
         # ---- kernel-by-kernel path with epsilon materialised in HBM (identical values; parity/debug)

@@ -33,11 +33,12 @@ class MPPIParams:
 class MPPIController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, *, device=None, process_group=None,
                  compute_info: bool = True, propagate_nan=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1) -> None:
+                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None) -> None:
         from .. import _lib
         _lib.check_fan(compute_fan, N)  # ValueError before anything is built
         _lib.check_update(update)
         _lib.check_iters(iters)
+        _lib.check_elite(elite, N, ess_min, getattr(control_params, "gamma_sigma", 0.0))
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -50,13 +51,16 @@ class MPPIController(BaseController):
                                  compute_info=compute_info, trust_clipped=True,
                                  cov_records=float(getattr(control_params, "gamma_sigma", 0.0)) != 0.0, propagate_nan=propagate_nan,
                                  compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters)
+                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite)
 
     def _check_gamma_sigma(self, control_params):
         """A controller built with gamma_sigma = 0 exchanges the 516-float records: on sharded ranks a later gamma_sigma != 0 needs
         a controller built for it (the record size is fixed at construction: exchange buffers, captured graphs)."""
         if control_params.gamma_sigma != 0.0 and self.core.world > 1:
             self.core._need_cov_records()
+        if self.core.elite:  # (a full refit from K < 5 elites is singular)
+            from .. import _lib
+            _lib.check_elite(self.core.elite, self.N, None, control_params.gamma_sigma)
 
     def run_episode(self, episode, env_params, control_params, rng, n_steps):
         """n_steps closed-loop steps (this controller + the device env step) enqueued by one C call; keys threaded like
@@ -96,7 +100,7 @@ class MPPIController(BaseController):
                 a_mean_new, cov = a_mean_new.clone(), cov.clone()
             control_params = control_params.replace(a_mean=a_mean_new, a_cov=cov)
             out_info = core.info(dstate) if core.compute_info else {}
-            out_info.update(core.step_info())  # whatever compute_diag / _plan / _fan, ess_min, update and iters attached
+            out_info.update(core.step_info())  # whatever compute_diag / _plan / _fan, ess_min, update, iters and elite attached
             return a_mean_new[0], control_params, out_info
 
         # ---- kernel-by-kernel path with epsilon materialised in HBM (identical values; parity/debug)

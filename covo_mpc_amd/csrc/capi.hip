@@ -92,6 +92,7 @@ int covo_create(const covo_config *cfg, covo_handle_t *out)
     COVO_CHECK_HIP(hipMalloc(&h->diag_scratch, (size_t)COVO_MAX_ENVS * COVO_DIAG_FLOATS * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->ws_blockmin, (size_t)ng * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->lam_own, (size_t)COVO_MAX_ENVS * COVO_LAM_FLOATS * sizeof(float)));
+    COVO_CHECK_HIP(hipMalloc(&h->elite_own, (size_t)COVO_MAX_ENVS * COVO_ELITE_FLOATS * sizeof(float)));
     COVO_CHECK_HIP(hipMalloc(&h->ws_stats, (size_t)(nb > 256 ? nb : 256) * COVO_H * 6 * sizeof(double)));  // one row per rollout workgroup
     h->ws_sigma_bytes = sigma_ns_workspace_bytes(1);
     COVO_CHECK_HIP(hipMalloc(&h->ws_sigma, h->ws_sigma_bytes));
@@ -129,6 +130,7 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->diag_scratch));
     DESTROY(hipFree(h->ws_blockmin));
     DESTROY(hipFree(h->lam_own));
+    DESTROY(hipFree(h->elite_own));
     DESTROY(hipFree(h->ws_stats));
     DESTROY(hipFree(h->ws_sigma));
     DESTROY(hipFree(h->ws_hess));
@@ -718,6 +720,32 @@ int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32
     return launch_ess_lambda(cost, n_samples, n_inst, nullptr, lam0, ess_min, out, (hipStream_t)stream);
 }
 
+// ---- the elite-set update (elite_select.hip, reduce_elite.hip).  The captured step graphs bake in the staged launch set, K and where
+// the selector writes: any change bumps the epoch.  The valid range of K depends on the step's sample count: checked at the step
+// (check_step_attachments)
+int covo_set_step_elite(covo_handle_t h, int32_t K, float *rows_out, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_elite: null handle");
+    REQUIRE(K >= 0, "covo_set_step_elite: K=%d is negative (0 = off; a step takes K in [1, n_samples])", K);
+    REQUIRE(rows_out == nullptr || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_elite: n_inst=%d outside (0, %d]", n_inst,
+            COVO_MAX_ENVS);
+    if (K != h->elite_K || rows_out != h->elite_out) ++h->opt.epoch;
+    h->elite_K = K;
+    h->elite_out = rows_out;
+    h->elite_n = rows_out ? n_inst : 0;
+    return 0;
+}
+
+int covo_elite_select(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, int32_t K, float *out, void *stream)
+{
+    REQUIRE(h, "covo_elite_select: null handle");
+    CHECK_DEVICE(h, "covo_elite_select");
+    REQUIRE(cost && out && n_samples > 0, "covo_elite_select: bad argument");
+    REQUIRE(n_inst > 0 && n_inst <= 65535, "covo_elite_select: n_inst=%d outside (0, 65535]", n_inst);
+    REQUIRE(K >= 1 && K <= n_samples, "covo_elite_select: K=%d outside [1, n_samples = %d]", K, n_samples);
+    return launch_elite_select(cost, n_samples, n_inst, K, out, (hipStream_t)stream);
+}
+
 // ---- the flight recorder (plan_trace.hip).  Its launch is eager and follows the step: attaching or detaching a buffer changes no
 // captured step graph
 int covo_set_step_plan(covo_handle_t h, float *plan, int32_t n_inst)
@@ -856,7 +884,7 @@ int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t
 }
 
 // ---- what a step checks about everything attached to its handle -- diagnostics, plan / trace, sample fan, update arbiter, ESS floor,
-// iterations -- for every entry point alike (covo_mpc_step, covo_run_episode and, through check_batch_step, the four env-batched
+// iterations, elite set -- for every entry point alike (covo_mpc_step, covo_run_episode and, through check_batch_step, the four env-batched
 // ones): a step of n_samples samples for n_inst instances.  The order is fixed: first what a sample-sharded step
 // (partial_out != NULL) cannot have at all, in the order above; then, in the same order, each attachment's own ranges and the rows
 // of its buffer.  A new attachment adds its lines here (and its log to check_episode_logs), nowhere else.
@@ -881,6 +909,9 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(covo_step_iters(h) == 1,
                 "%s: iterations per step (covo_set_step_iters, iters=%d) are not available for sample-sharded steps (partial_out != NULL): "
                 "every pass would need its own exchange of the rank records; set iters = 1", what, covo_step_iters(h));
+        REQUIRE(covo_elite_target(h) == nullptr,
+                "%s: the elite-set update (covo_set_step_elite, K=%d) is not available for sample-sharded steps (partial_out != NULL): "
+                "a rank sees only its shard's costs; turn it off (K = 0)", what, h->elite_K);
     }
     REQUIRE(covo_diag_target(h) == nullptr || n_inst <= covo_diag_capacity(h),
             "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, n_inst, covo_diag_capacity(h));
@@ -897,6 +928,15 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                 "%s: ess_min=%g (covo_set_step_ess_floor) outside [1, n_samples / 2 = %g]", what, (double)h->ess_min, 0.5 * n_samples);
         REQUIRE(n_inst <= covo_lam_capacity(h), "%s: %d instances, the temperature buffer (covo_set_step_ess_floor) has %d rows", what,
                 n_inst, covo_lam_capacity(h));
+    }
+    if (covo_elite_target(h) != nullptr) {
+        REQUIRE(covo_lam_target(h) == nullptr,
+                "%s: the elite-set update (covo_set_step_elite, K=%d) together with the ESS floor (covo_set_step_ess_floor, ess_min=%g): "
+                "both define the update's weights; turn one of them off", what, h->elite_K, (double)h->ess_min);
+        REQUIRE(h->elite_K >= 1 && h->elite_K <= n_samples, "%s: K=%d (covo_set_step_elite) outside [1, n_samples = %d]", what,
+                h->elite_K, n_samples);
+        REQUIRE(n_inst <= covo_elite_capacity(h), "%s: %d instances, the elite buffer (covo_set_step_elite) has %d rows", what, n_inst,
+                covo_elite_capacity(h));
     }
     if (covo_step_iters(h) > 1) {  // the key chain of the passes is walked from the raw controller key
         REQUIRE(n_inst <= h->iter_n, "%s: %d instances, the iteration log (covo_set_step_iters) has n_inst=%d", what, n_inst, h->iter_n);
@@ -1117,6 +1157,10 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
             "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for the env-batched MPPI / covo-offline step: its "
             "one fused launch needs the temperature before all costs exist, and there is no staged batched fallback; turn it off "
             "(ess_min = 0)", what, (double)h->ess_min);
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_elite_target(h) == nullptr,
+            "%s: the elite-set update (covo_set_step_elite, K=%d) is not available for the env-batched MPPI / covo-offline step: its "
+            "one fused launch needs the weights before all costs exist, and there is no staged batched fallback; turn it off "
+            "(K = 0)", what, h->elite_K);
     REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_step_iters(h) == 1 || !covo_arb_on(h),
             "%s: iterations per step (covo_set_step_iters, iters=%d) together with the update arbiter (covo_set_step_arbiter) are not "
             "available for the env-batched MPPI / covo-offline step: its fused launch keeps each pass's starting mean in LDS only; "

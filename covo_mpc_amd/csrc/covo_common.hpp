@@ -70,6 +70,11 @@ struct covo_ctx {
     float *lam_out;           // caller's [lam_n][COVO_LAM_FLOATS]: instance e's solver row of every step; null: lam_own
     int lam_n;
     float *lam_own;           // [COVO_MAX_ENVS][COVO_LAM_FLOATS]
+    // the elite-set update (covo_set_step_elite; elite_select.hip, reduce_elite.hip); elite_K == 0: off
+    int elite_K;              // elites per instance and pass
+    float *elite_out;         // caller's [elite_n][COVO_ELITE_FLOATS]: instance e's selector row of every step; null: elite_own
+    int elite_n;
+    float *elite_own;         // [COVO_MAX_ENVS][COVO_ELITE_FLOATS]
     // the update arbiter (covo_set_step_arbiter / covo_set_episode_arbiter_log; update_arbiter.hip); arb_out null: off
     float *arb_out;           // caller's [arb_n][COVO_ARB_FLOATS]: instance e's arbiter row of every step
     int arb_mask, arb_n;      // enabled candidates (bits 0..2), rows of arb_out
@@ -88,6 +93,11 @@ static inline float *covo_iter_slot(const covo_ctx *h, int pass) { return covo_s
 // where the solver of this handle's steps writes the instances' temperatures (null: no floor) and for how many instances
 static inline float *covo_lam_target(const covo_ctx *h) { return h->ess_min > 0.0f ? (h->lam_out ? h->lam_out : h->lam_own) : nullptr; }
 static inline int covo_lam_capacity(const covo_ctx *h) { return h->lam_out ? h->lam_n : COVO_MAX_ENVS; }
+// where the selector of this handle's steps writes the instances' rows (null: no elite-set update) and for how many instances
+static inline float *covo_elite_target(const covo_ctx *h) { return h->elite_K > 0 ? (h->elite_out ? h->elite_out : h->elite_own) : nullptr; }
+static inline int covo_elite_capacity(const covo_ctx *h) { return h->elite_out ? h->elite_n : COVO_MAX_ENVS; }
+// a step whose update waits for all costs (ESS floor, elite set): rollout without in-launch records, no one-launch small step
+static inline bool covo_update_staged(const covo_ctx *h) { return covo_lam_target(h) != nullptr || covo_elite_target(h) != nullptr; }
 static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->trace != nullptr; }
 static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->fanlog != nullptr; }
 static inline bool covo_arb_on(const covo_ctx *h) { return h->arb_out != nullptr; }
@@ -304,6 +314,9 @@ struct UpdateDesc {
     // the ESS floor (launch_softmax_reduce / launch_softmax_update_cov, final updates only): instance e takes 1 / lambda from
     // lam_rows[e][1] in device memory -- the solver's output, ess_lambda.hip -- instead of the handle's configured temperature
     const float *lam_rows = nullptr;  // [batch][COVO_LAM_FLOATS]
+    // the elite-set update (launch_elite_reduce / launch_elite_update_cov, final updates only): instance e's weights are 1 for the
+    // samples whose key is at most the threshold in elite_rows[e] -- the selector's output, elite_select.hip -- and 0 otherwise
+    const float *elite_rows = nullptr;  // [batch][COVO_ELITE_FLOATS]
     // an iterated step (covo_set_step_iters), final updates only: the merge also stores its cost minimum m, instance e's at
     // iter_out[e * iter_stride] (the caller has added the pass index)
     float *iter_out = nullptr;
@@ -317,6 +330,11 @@ int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 int launch_softmax_reduce_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 int launch_softmax_update_cov_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 int launch_merge(const UpdateDesc &d, float lam, hipStream_t s);
+// the elite-set update: the selector (elite_select.hip): out [n_inst][COVO_ELITE_FLOATS] from cost [n_inst][N], 1 <= K <= N; and
+// what takes the place of launch_softmax_reduce / launch_softmax_update_cov with d.elite_rows set (reduce_elite.hip)
+int launch_elite_select(const float *cost, int N, int n_inst, int K, float *out, hipStream_t s);
+int launch_elite_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
+int launch_elite_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 // exchange.hip: the rank records of a sample-sharded step and their peer-write exchange
 int launch_rank_stats_sum(const float *records, int G, int record_floats, double *out, hipStream_t s);  // COVO_RANK_RECORD_[COV_]FLOATS
 int exchange_create(covo_ctx *h, int world, int rank, void *handle_out);

@@ -229,7 +229,9 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     // covo-offline / MPPI at small N: noise -> rollout -> records -> merge as ONE launch (the begin launch has left the step's
     // scalars in st->dyn and the state in st->state_buf; MPPI: it has NOT touched a_cov, the fused launch shifts and factors)
     float *lam_rows = covo_lam_target(h);  // the ESS floor: the update's temperature is solved from this step's costs
-    if (M == 63 && h->opt.fuse_small && step_small_eligible(h, p, a) && lam_rows == nullptr)
+    float *elite_rows = covo_elite_target(h);  // the elite-set update: the weights are selected from this step's costs
+    const bool staged = covo_update_staged(h);
+    if (M == 63 && h->opt.fuse_small && step_small_eligible(h, p, a) && !staged)
         return launch_step_small(h, p, a, state, am_shift, nullptr, st->dyn, 0.0f, st->ticket, s, pass, nullptr, iter_out);
     // periodic / sin / drag / mixed (free.py:10-58): the wave-uniform part of every rollout step's force, for the sampling
     // rollouts (shared step key) and for the Hessian's deterministic rollout (per-step keys), resolved once per control step
@@ -321,8 +323,9 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     const int G = rollout_workgroups(N, a.pos_stats != nullptr);
     // MPPI's covariance adaptation needs second moments the in-rollout records do not carry: its own stage 1 (reduce.hip)
     const bool cov_adapt = a.mode == COVO_MODE_MPPI && a.gamma_sigma != 0.0f;
-    // the ESS floor: the rollout's in-launch records are formed at a temperature fixed before the costs exist -- staged, like cov_adapt
-    const bool records = G <= h->max_red_blocks && !cov_adapt && lam_rows == nullptr;
+    // the ESS floor, the elite set: the rollout's in-launch records are formed with weights fixed before the costs exist -- staged, like
+    // cov_adapt
+    const bool records = G <= h->max_red_blocks && !cov_adapt && !staged;
     // the step's sampling diagnostics (covo_set_step_diag): the diagnostic variants of the same launches; a sharded step has none
     float *dg = a.partial_out == nullptr ? covo_diag_target(h) : nullptr;
     RolloutDesc ro;
@@ -349,6 +352,8 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     if (!(M & 32)) return 0;
     // rollout (costs + per-wave minima) -> solver -> stage 1 and merge reading 1 / lam_eff from lam_rows
     if (lam_rows != nullptr && (rc = launch_ess_lambda(a.cost, N, 1, a.groupmin, h->cfg.lam, h->ess_min, lam_rows, s))) return rc;
+    // the elite set, in the floor's place: rollout (costs) -> selector -> stage 1 with 0/1 weights off elite_rows -> the same merges
+    if (elite_rows != nullptr && (rc = launch_elite_select(a.cost, N, 1, h->elite_K, elite_rows, s))) return rc;
     // weights + update: finish locally (blend with am_shift, diagnostics), or -- a sample-sharded rank -- leave this shard's
     // record for the all-gather (covo.py:266-275)
     UpdateDesc up;
@@ -367,14 +372,16 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     up.diag_rec = h->ws_diag_rec;
     up.diag_out = dg;
     up.lam_rows = lam_rows;
+    up.elite_rows = elite_rows;
     up.iter_out = sharded ? nullptr : iter_out;
     if (cov_adapt) {  // mppi.py:109-125: new mean, then a_cov (already shifted by the begin launch) adapted in place; a sharded
                       // rank: its record with the second moments (836-float kind)
         up.a_cov_old = a.a_cov;
         up.gamma_sigma = a.gamma_sigma;
         up.a_cov_out = sharded ? nullptr : a.a_cov;
-        return launch_softmax_update_cov(h, up, s);
+        return elite_rows != nullptr ? launch_elite_update_cov(h, up, s) : launch_softmax_update_cov(h, up, s);
     }
+    if (elite_rows != nullptr) return launch_elite_reduce(h, up, s);
     return records ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
 }
 
@@ -407,7 +414,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     std::memcpy(&blk.w[8], &args->state, sizeof(const float *));
     const float shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
     // control_params.a_mean of this call: the handle's own buffer (a carried mean) or the caller's input (args->a_mean_in)
-    const bool small = h->opt.fuse_small && step_small_eligible(h, *params, *args) && covo_lam_target(h) == nullptr;
+    const bool small = h->opt.fuse_small && step_small_eligible(h, *params, *args) && !covo_update_staged(h);
     // covo_set_step_iters: K passes on this state.  Pass j >= 1 starts from the mean pass j - 1 committed (args->a_mean, never the
     // caller's a_mean_in) and walks the raw key on the device; with the update arbiter attached its launch sits between the passes
     // (and the passes are enqueued eagerly: the arbiter's launch is not part of any captured graph)
@@ -577,7 +584,7 @@ int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const 
     }
     StepState *st = reinterpret_cast<StepState *>(h->step);
     const bool folded_online = h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && !covo_needs_tables(*params);
-    if (((h->opt.fuse_small && step_small_eligible(h, *params, *args) && covo_lam_target(h) == nullptr) || folded_online) && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
+    if (((h->opt.fuse_small && step_small_eligible(h, *params, *args) && !covo_update_staged(h)) || folded_online) && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
         args->state != nullptr) {
         // the last step ran without a begin launch (the one-launch small step; covo-online with the begin work folded into the
         // Hessian) and never filled the scratch the replayed launches read (state copy, shifted mean, keys; MPPI: shifted
@@ -888,6 +895,12 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
         if ((rc = launch_ess_lambda(a.cost, N, E, a.groupmin, h->cfg.lam, h->ess_min, covo_lam_target(h), s))) return rc;
         return launch_softmax_reduce(h, up, s);
     }
+    // the elite set, likewise: row e of the selector's output is instance e's threshold
+    if (float *elite_rows = covo_elite_target(h)) {
+        up.elite_rows = elite_rows;
+        if ((rc = launch_elite_select(a.cost, N, E, h->elite_K, elite_rows, s))) return rc;
+        return launch_elite_reduce(h, up, s);
+    }
     // the rollout's workgroups have left the records when they fit the merge (rollout_record): instance e's are [e][G]
     return G <= h->max_red_blocks ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
 }
@@ -948,7 +961,7 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         b->ro_args_host.assign(rollout_args_bytes(E), 0);
         const int N = args->n_samples;
         const int bG = rollout_workgroups(N, false, E);
-        const bool brec = bG <= h->max_red_blocks && covo_lam_target(h) == nullptr;  // (a floor: staged update, see batch_enqueue)
+        const bool brec = bG <= h->max_red_blocks && !covo_update_staged(h);  // (a floor, an elite set: staged update, see batch_enqueue)
         for (int e = 0; e < E; ++e) {
             const BatchInst i = batch_inst(*args, e);
             RolloutDesc ro;

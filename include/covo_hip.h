@@ -464,6 +464,39 @@ int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride);
 int covo_set_step_ess_floor(covo_handle_t h, float ess_min, float *lam_out, int32_t n_inst);
 int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, float lam0, float ess_min, float *out, void *stream);
 
+/* The elite-set update: exact top-K selection on the device, the cross-entropy method's update rule (additive to ABI 10:
+ * COVO_HAS_ELITE_UPDATE; off by default, and off changes nothing a caller can observe).  Per instance and per pass, with the costs
+ * c_n as the rollout wrote them, key(n) = (u(c_n) << 32) | n: u is the order-preserving unsigned form of the fp32 bits (sign bit
+ * set for c >= 0, all bits inverted for c < 0; -0 and +0 are one cost), a NaN cost has u = 0xFFFFFFFF; the index in the low word
+ * makes the keys distinct.  The ELITE SET is the K samples of smallest key: equal costs go to the lowest indices, NaN costs last,
+ * +inf is an ordinary large cost, and the set has exactly K members for every input.  The update is the step's own update with the
+ * weights w_n = 1 for the elites and 0 otherwise:
+ *   new mean   gamma_mean * (sum over the elites of a_n / K) + (1 - gamma_mean) * shifted old mean
+ *   MPPI with gamma_sigma != 0: the elites' second moments through the same covariance merge as the softmax weights' -- the
+ *              cross-entropy method's refit, smoothed by gamma_sigma; covo-online / covo-offline keep their Sigma / L
+ * Actions, costs, Sigma, L, the key chain and sampling are those of the same step without it.  With diagnostics attached: ess and
+ * weight_sum are K, cost_weighted is the elites' mean cost, cost_min / cost_mean are as before.  The arbiter's candidate 0 is the
+ * elite mean; with iterations per step every pass selects again.  If the smallest cost is not finite the new mean is NaN.
+ * Per instance the selector leaves float[COVO_ELITE_FLOATS]:
+ *   [0] bits(uint32: the threshold key's cost word)   [1] bits(uint32: the threshold key's index word)   [2] cost_min
+ *   [3] cost_kth, the K-th smallest cost   [4] K   [5] the elites whose cost word is the threshold's   [6..7] 0
+ * so that the elite set is {n : key(n) <= threshold}.
+ * covo_set_step_elite: K = 0 turns it off; rows_out = DEVICE float[n_inst][COVO_ELITE_FLOATS] (row e = instance e of a batched
+ *   step, a single step writes row 0), or NULL for a buffer the handle owns.  Covered: covo_mpc_step (all modes, eager and graph),
+ *   covo_mpc_step_batched and the episode drivers that call them; such a step runs staged -- rollout, selector, stage 1 with 0/1
+ *   weights, the merges of the softmax update -- so one captured graph serves every step.  Attaching, detaching or another K makes
+ *   the handle re-capture its step graphs, like covo_set_step_ess_floor.  Refused before any launch, with a message that names the
+ *   condition: K outside [1, n_samples]; n_inst outside (0, COVO_MAX_ENVS]; the elite set together with an ESS floor (both define
+ *   the weights); a sample-sharded step (partial_out != NULL); covo_mpc_step_batched_mode / covo_run_episode_batched_mode in the
+ *   MPPI and covo-offline modes (their fused launch needs the weights before all costs exist, and there is no staged batched
+ *   fallback).
+ * covo_elite_select: the selector alone on the caller's costs, DEVICE float[n_inst][n_samples] -> out = DEVICE
+ *   float[n_inst][COVO_ELITE_FLOATS]. */
+#define COVO_HAS_ELITE_UPDATE 1
+#define COVO_ELITE_FLOATS 8
+int covo_set_step_elite(covo_handle_t h, int32_t K, float *rows_out, int32_t n_inst);
+int covo_elite_select(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, int32_t K, float *out, void *stream);
+
 /* The flight recorder: the plan of a control step and the trace of an episode (additive to ABI 10: COVO_HAS_PLAN_TRACE; off by
  * default, and off changes nothing a caller can observe).
  * The PLAN of a step, for one instance: a_plan = clip(a_new, -1, 1), a_new the mean the step leaves in a_mean (covo.py:275,

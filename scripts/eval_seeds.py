@@ -3,9 +3,12 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 from covo_mpc_amd.envs import quadrotor as Q
 name = sys.argv[1]
+# python scripts/eval_seeds.py covo-online [elite=512]: the elite-set update with K elites instead of the softmax weights
+opts = {k: int(v) for k, v in (arg.split("=") for arg in sys.argv[2:])}
+assert set(opts) <= {"elite"}, opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
-ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01")
+ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **opts)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 for seed in range(1, 13):
