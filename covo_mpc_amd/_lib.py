@@ -40,6 +40,8 @@ LAM_FIELDS = ("lam_eff", "inv_lam_eff", "ess_lam0", "evaluations")
 COVO_HAS_ELITE_UPDATE = 1
 COVO_ELITE_FLOATS = 8  # the elite-set update's selector row of one instance (covo_set_step_elite)
 ELITE_FIELDS = ("threshold_cost_word", "threshold_index_word", "cost_min", "cost_kth", "K", "ties")  # words: uint32 bits
+COVO_HAS_SIGMA_PERIOD = 1
+COVO_MAX_SIGMA_PERIOD = 64  # sigma_period= of the covo-online controllers: every m-th step refreshes Sigma (covo_set_step_sigma_period)
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -173,6 +175,10 @@ _SIGS = {
     "covo_ess_lambda": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "covo_set_step_elite": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # the elite-set update (covo_hip.h: COVO_HAS_ELITE_UPDATE)
     "covo_elite_select": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
+    "covo_set_step_sigma_period": (C.c_int, [_P, C.c_int32]),  # the Sigma period (covo_hip.h: COVO_HAS_SIGMA_PERIOD)
+    "covo_step_sigma_age": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "covo_sigma_shift": (C.c_int, [_P, _P, C.c_int32, C.c_float, _P, _P, _P]),
+    "covo_debug_sigma_factor": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     "covo_set_step_plan": (C.c_int, [_P, _P, C.c_int32]),             # the flight recorder (covo_hip.h: COVO_HAS_PLAN_TRACE)
     "covo_set_episode_trace": (C.c_int, [_P, _P, C.c_int32]),
     "covo_rollout_fan": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P,
@@ -276,6 +282,22 @@ def check_elite(elite, N, ess_min=None, gamma_sigma=None) -> int:
         raise ValueError(f"elite={K} with gamma_sigma={gamma_sigma}: a 4 x 4 covariance block refitted from K < 5 samples about their "
                          "own mean is singular (rank <= K - 1); take K >= 5 or gamma_sigma < 1")
     return K
+
+
+def check_sigma_period(sigma_period, mode="online") -> int:
+    """sigma_period= of the controllers -> the period m: an integer in [1, COVO_MAX_SIGMA_PERIOD] (1, the default: every step computes
+    its own Sigma); anything else raises ValueError.  mode: what the controller is ("online", "offline", "mppi", ...): m > 1 with
+    anything but covo-online raises ValueError -- only covo-online decides a Sigma per step."""
+    import numbers
+    if (isinstance(sigma_period, bool) or not isinstance(sigma_period, numbers.Integral) or
+            not 1 <= int(sigma_period) <= COVO_MAX_SIGMA_PERIOD):
+        raise ValueError(f"sigma_period={sigma_period!r} outside [1, {COVO_MAX_SIGMA_PERIOD}] (an integer number of control steps per "
+                         "Sigma refresh; 1 = off)")
+    m = int(sigma_period)
+    if m > 1 and mode != "online":
+        raise ValueError(f"sigma_period={m} with {mode}: the Sigma period belongs to covo-online, the one mode that computes a Sigma per "
+                         "step (CoVOController(mode=\"online\"), BatchedCoVOController(mode=\"online\")); give sigma_period=1")
+    return m
 
 
 def ptr(t):

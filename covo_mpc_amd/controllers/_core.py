@@ -53,8 +53,10 @@ class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
+                 sigma_period: int = 1):
         import torch
+        sigma_period = _lib.check_sigma_period(sigma_period)
         fan_K = _lib.check_fan(compute_fan, N)
         arb_mask = _lib.check_update(update)
         iters = _lib.check_iters(iters)
@@ -73,7 +75,9 @@ class SamplingCore:
                      f"ess_min={ess_min} on sample-sharded ranks: a rank sees only its shard's costs "
                      "(covo_set_step_ess_floor refuses sample-sharded steps)"),
                     (elite_K, f"elite={elite_K} on sample-sharded ranks: a rank sees only its shard's costs "
-                              "(covo_set_step_elite refuses sample-sharded steps)")):
+                              "(covo_set_step_elite refuses sample-sharded steps)"),
+                    (sigma_period > 1, f"sigma_period={sigma_period} on sample-sharded ranks: every rank would have to keep and shift "
+                                       "the same factor (covo_set_step_sigma_period refuses sample-sharded steps)")):
                 if is_on and sharded:
                     raise NotImplementedError(message)
         if H != COVO_H:
@@ -233,6 +237,12 @@ class SamplingCore:
         if iters > 1:
             self.iter_cost_min = torch.zeros((int(diag_rows), iters), **f32)
             check(self.lib.covo_set_step_iters(self.h, iters, ptr(self.iter_cost_min), int(diag_rows)), "covo_set_step_iters")
+        # sigma_period = m > 1 (covo-online steps only): every m-th control step is today's step and refreshes Sigma; the m - 1 between
+        # skip the Hessian and the Sigma chain and sample from the previous step's factor moved one stage down the horizon on the
+        # device (covo_set_step_sigma_period, csrc/sigma_shift.hip); 1 (default): nothing attached, and that changes nothing
+        self.sigma_period = sigma_period
+        if sigma_period > 1:
+            check(self.lib.covo_set_step_sigma_period(self.h, sigma_period), "covo_set_step_sigma_period")
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -372,7 +382,8 @@ class SamplingCore:
         lam_info (ess_min), arbiter_info (update), iter_info (iters) and elite_info (elite) -- views of the core's buffers, no sync, no
         copy."""
         out = {}
-        for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info, self.elite_info):
+        for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info, self.elite_info,
+                     self.sigma_info):
             out.update(info())
         return out
 
@@ -484,6 +495,55 @@ class SamplingCore:
             return {}
         return {"elite_cost_max": self.elite_rows[0, 3], "elite_cost_min": self.elite_rows[0, 2], "elite_count": self.elite_rows[0, 4]}
 
+    def _sigma_ages(self):
+        nxt, last = C.c_int32(0), C.c_int32(0)
+        check(self.lib.covo_step_sigma_age(self.h, C.byref(nxt), C.byref(last)), "covo_step_sigma_age")
+        return int(nxt.value), int(last.value)
+
+    @property
+    def sigma_age(self) -> int:
+        """The age the NEXT covo-online step is scheduled at: 0 = it refreshes Sigma, 1 .. sigma_period - 1 = it shifts the last factor."""
+        return self._sigma_ages()[0]
+
+    def sigma_info(self) -> dict:
+        """{"sigma_age": the age the last step ran at, a Python int: 0 = it refreshed Sigma}; {} when the core was built with
+        sigma_period=1."""
+        if self.sigma_period == 1:
+            return {}
+        return {"sigma_age": self._sigma_ages()[1]}
+
+    def set_sigma_period(self, sigma_period: int):
+        """Another period (1 = off) from the next step on; the age goes back to 0: the next step refreshes.  Calling it with the
+        current period is how a controller's reset() restarts the schedule."""
+        m = _lib.check_sigma_period(sigma_period)
+        if m > 1 and self.world > 1:
+            raise NotImplementedError(f"sigma_period={m} on sample-sharded ranks: every rank would have to keep and shift the same "
+                                      "factor (covo_set_step_sigma_period refuses sample-sharded steps)")
+        check(self.lib.covo_set_step_sigma_period(self.h, m), "covo_set_step_sigma_period")
+        self.sigma_period = m
+
+    def sigma_factor(self, n_envs=None):
+        """The factor L [128, 128] the last single covo-online step of this core sampled from (n_envs=E: [E, 128, 128], the last
+        env-batched step's) -- what the next reuse step of a Sigma period shifts (covo_debug_sigma_factor; a copy)."""
+        shape = (COVO_NA, COVO_NA) if n_envs is None else (int(n_envs), COVO_NA, COVO_NA)
+        out = self.torch.empty(shape, dtype=self.torch.float32, device=self.device)
+        check(self.lib.covo_debug_sigma_factor(self.h, 0 if n_envs is None else 1, ptr(out), out.numel(), self.stream()),
+              "covo_debug_sigma_factor")
+        return out
+
+    def sigma_shift(self, L, sample_sigma=0.5):
+        """covo_sigma_shift (the stand-alone shift of a reuse step): L float32 device tensor [128, 128] or [E, 128, 128], the lower
+        Cholesky factor of a covariance Sigma -> (Sigma', L') of the same shape: Sigma' = c S(Sigma) -- the trailing 124 x 124 block of
+        Sigma moved up, the last stage's 4 x 4 marginal repeated, no cross terms, c such that log det Sigma' = 2 n log sample_sigma --
+        and its lower factor (include/covo_hip.h)."""
+        torch = self.torch
+        assert L.is_cuda and L.dtype == torch.float32 and L.is_contiguous() and tuple(L.shape[-2:]) == (COVO_NA, COVO_NA)
+        E = 1 if L.dim() == 2 else int(L.shape[0])
+        Sigma_out, L_out = torch.empty_like(L), torch.empty_like(L)
+        check(self.lib.covo_sigma_shift(self.h, ptr(L), E, float(sample_sigma), ptr(Sigma_out), ptr(L_out), self.stream()),
+              "covo_sigma_shift")
+        return Sigma_out, L_out
+
     def elite_select(self, cost, K):
         """covo_elite_select (the stand-alone selector): cost float32 device tensor [N] or [E, N] -> float32 [E, 8] rows
         {bits(threshold cost word), bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0}; the elite set of
@@ -512,6 +572,9 @@ class SamplingCore:
         check(self.lib.covo_set_episode_trace(self.h, ptr(episode.trace_view()), int(rows_left)), "covo_set_episode_trace")
 
     def require_fused_for_diag(self):
+        if getattr(self, "sigma_period", 1) > 1:
+            raise NotImplementedError(f"sigma_period={self.sigma_period} acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') computes its Sigma in every step")
         if self.ess_min != 0.0:
             raise NotImplementedError("ess_min acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') updates at the configured lam")

@@ -29,7 +29,10 @@ class BatchedCoVOController:
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
-                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None):
+                 compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
+                 sigma_period: int = 1):
+        _lib.check_sigma_period(sigma_period, "online" if (self.MODE is None and mode == "online") else
+                                "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)
@@ -63,7 +66,9 @@ class BatchedCoVOController:
         # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite)
+                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite, sigma_period=sigma_period)
+        # sigma_period = m > 1 (online): every m-th call refreshes every instance's Sigma, the calls between shift the last factors; the
+        # batch shares one age: self.sigma_age is the age the last call ran at (0 = refresh), reset() restarts the schedule
         # elite = K: after a call, self.elite [E, 8] holds every instance's selector row of that step: {bits(threshold cost word),
         # bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0} (include/covo_hip.h); None without it
         self.elite = self.core.elite_rows
@@ -137,6 +142,8 @@ class BatchedCoVOController:
         through CoVOController.reset_a_cov_offline (covo.py:58-104; once per episode, a host loop over the instances).
         -> (a_cov_offline, a_chol_offline) [E, T, 128, 128].  The other modes have nothing to build."""
         if self.mode != _lib.MODE_COVO_OFFLINE:
+            if self.core.sigma_period > 1:  # the schedule restarts: the episode's first step refreshes Sigma
+                self.core.set_sigma_period(self.core.sigma_period)
             return None
         from .covo import CoVOController, CoVOParams
         torch = self.core.torch
@@ -195,6 +202,11 @@ class BatchedCoVOController:
                   "covo_mpc_step_batched_mode")
         return self.a_mean.view(self.E, COVO_H, 4)[:, 0]
 
+    @property
+    def sigma_age(self) -> int:
+        """The age the last call ran at under sigma_period (0 = it refreshed every instance's Sigma; always 0 without a period)."""
+        return self.core._sigma_ages()[1]
+
     def time_phases(self, step_mask: int, reps: int = 10) -> float:
         """GPU microseconds of the selected launch groups of the LAST batched step (2 Hessian, 4 Sigma, 8 GEMM, 16 rollout,
         32 update), replayed `reps` times from one graph (covo_debug_time_batched)."""
@@ -245,7 +257,8 @@ class BatchedMPPIController(BatchedCoVOController):
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None):
+                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1):
+        _lib.check_sigma_period(sigma_period, "the env-batched MPPI controller")
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)

@@ -33,9 +33,10 @@ class MPPIParams:
 class MPPIController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, *, device=None, process_group=None,
                  compute_info: bool = True, propagate_nan=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None) -> None:
+                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1) -> None:
         from .. import _lib
-        _lib.check_fan(compute_fan, N)  # ValueError before anything is built
+        _lib.check_sigma_period(sigma_period, "MPPI")  # ValueError before anything is built (MPPI computes no Sigma per step)
+        _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)
         _lib.check_elite(elite, N, ess_min, getattr(control_params, "gamma_sigma", 0.0))

@@ -883,12 +883,46 @@ int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t
     return 0;
 }
 
+// ---- the Sigma period (sigma_shift.hip): every m-th covo-online step is today's step, the m - 1 between shift the previous step's
+// factor (step.hip: the reuse branch of enqueue_step / batch_enqueue, with a graph of its own next to the step's: no epoch bump).
+// Which modes may carry a period is checked at the step (check_step_attachments)
+int covo_set_step_sigma_period(covo_handle_t h, int32_t period)
+{
+    REQUIRE(h, "covo_set_step_sigma_period: null handle");
+    REQUIRE(period >= 1 && period <= COVO_MAX_SIGMA_PERIOD, "covo_set_step_sigma_period: period=%d outside [1, %d] (1 = off: every step "
+            "computes its own Sigma)", period, COVO_MAX_SIGMA_PERIOD);
+    h->sigma_period = period;
+    h->sigma_age = 0;
+    return 0;
+}
+
+int covo_step_sigma_age(covo_handle_t h, int32_t *next_age, int32_t *last_age)
+{
+    REQUIRE(h, "covo_step_sigma_age: null handle");
+    if (next_age) *next_age = covo_sigma_period(h) > 1 ? h->sigma_age : 0;
+    if (last_age) *last_age = h->sigma_last_age;
+    return 0;
+}
+
+int covo_sigma_shift(covo_handle_t h, const float *L_in, int32_t batch, float sample_sigma, float *Sigma_out, float *L_out, void *stream)
+{
+    REQUIRE(h, "covo_sigma_shift: null handle");
+    CHECK_DEVICE(h, "covo_sigma_shift");
+    REQUIRE(L_in && Sigma_out && L_out && batch > 0 && batch <= 65535, "covo_sigma_shift: bad argument");
+    REQUIRE(sample_sigma > 0.0f && sample_sigma < __builtin_inff(), "covo_sigma_shift: sample_sigma=%g", (double)sample_sigma);
+    REQUIRE((((uintptr_t)L_in | (uintptr_t)Sigma_out | (uintptr_t)L_out) & 15) == 0, "covo_sigma_shift: L_in / Sigma_out / L_out must be "
+            "16-byte aligned");
+    REQUIRE((const float *)Sigma_out != L_in && Sigma_out != L_out, "covo_sigma_shift: Sigma_out must not be L_in or L_out (L_out may be L_in)");
+    return launch_sigma_shift(L_in, batch, sample_sigma, Sigma_out, L_out, (hipStream_t)stream);
+}
+
 // ---- what a step checks about everything attached to its handle -- diagnostics, plan / trace, sample fan, update arbiter, ESS floor,
 // iterations, elite set -- for every entry point alike (covo_mpc_step, covo_run_episode and, through check_batch_step, the four env-batched
 // ones): a step of n_samples samples for n_inst instances.  The order is fixed: first what a sample-sharded step
 // (partial_out != NULL) cannot have at all, in the order above; then, in the same order, each attachment's own ranges and the rows
 // of its buffer.  A new attachment adds its lines here (and its log to check_episode_logs), nowhere else.
-static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, const char *what)
+static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, int mode, const float *a_cov,
+                                  const char *what)
 {
     if (sharded) {
         REQUIRE(covo_diag_target(h) == nullptr,
@@ -912,6 +946,9 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(covo_elite_target(h) == nullptr,
                 "%s: the elite-set update (covo_set_step_elite, K=%d) is not available for sample-sharded steps (partial_out != NULL): "
                 "a rank sees only its shard's costs; turn it off (K = 0)", what, h->elite_K);
+        REQUIRE(covo_sigma_period(h) == 1,
+                "%s: the Sigma period (covo_set_step_sigma_period, period=%d) is not available for sample-sharded steps (partial_out != NULL): "
+                "every rank would have to keep and shift the same factor; set period = 1", what, covo_sigma_period(h));
     }
     REQUIRE(covo_diag_target(h) == nullptr || n_inst <= covo_diag_capacity(h),
             "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, n_inst, covo_diag_capacity(h));
@@ -943,6 +980,12 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(derive_keys == 1,
                 "%s: iterations per step (covo_set_step_iters, iters=%d) need derive_keys = 1 (every pass derives its keys from the raw "
                 "controller key on the device)", what, covo_step_iters(h));
+    }
+    if (covo_sigma_period(h) > 1) {  // only covo-online decides a Sigma per step
+        REQUIRE(mode == COVO_MODE_COVO_ONLINE,
+                "%s: the Sigma period (covo_set_step_sigma_period, period=%d) belongs to covo-online steps; this step's mode is %s, which "
+                "computes no Sigma per step; set period = 1", what, covo_sigma_period(h), mode == COVO_MODE_MPPI ? "MPPI" : "covo-offline");
+        REQUIRE(((uintptr_t)a_cov & 15) == 0, "%s: a_cov must be 16-byte aligned under a Sigma period (covo_set_step_sigma_period)", what);
     }
     return 0;
 }
@@ -1056,7 +1099,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin &&
                 args->T > 0 && args->mode >= 0 && args->mode <= 2,
             "covo_run_episode: bad step arguments");
-    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, "covo_run_episode");
+    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov,
+                                    "covo_run_episode");
     if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
@@ -1165,7 +1209,7 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
             "%s: iterations per step (covo_set_step_iters, iters=%d) together with the update arbiter (covo_set_step_arbiter) are not "
             "available for the env-batched MPPI / covo-offline step: its fused launch keeps each pass's starting mean in LDS only; "
             "detach one of them", what, covo_step_iters(h));
-    if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, what))) return rc;  // (batched steps derive their keys)
+    if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, what))) return rc;  // (batched steps derive their keys)
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
     REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),
@@ -1291,7 +1335,7 @@ int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const c
     REQUIRE(h && params && args && us_out && reps > 0, "covo_debug_time_step: bad argument");
     REQUIRE(covo_step_iters(h) == 1, "covo_debug_time_step: the phase timers replay ONE pass; iterations per step are on "
             "(covo_set_step_iters, iters=%d): set iters = 1", covo_step_iters(h));
-    return covo_debug_time_step_impl(h, params, args, step_mask, hess_mask, sigma_stages, reps, us_out, (hipStream_t)stream);
+    return covo_debug_time_step_impl(h, params, args, step_mask, hess_mask, sigma_stages, reps, us_out, (hipStream_t)stream);  // (a refresh step's launches)
 }
 
 int covo_debug_hess_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)
@@ -1307,6 +1351,12 @@ int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_dou
 {
     REQUIRE(h && out && offset_doubles >= 0 && count > 0, "covo_debug_batched_hessians: bad argument");
     return covo_debug_batched_hessians_impl(h, out, offset_doubles, count, (hipStream_t)stream);
+}
+
+int covo_debug_sigma_factor(covo_handle_t h, int32_t batched, float *out, int64_t count, void *stream)
+{
+    REQUIRE(h && out && count > 0, "covo_debug_sigma_factor: bad argument");
+    return covo_debug_sigma_factor_impl(h, batched, out, count, (hipStream_t)stream);
 }
 
 int covo_sigma_jacobi(covo_handle_t h, const double *R, int32_t batch, float sample_sigma, float *Sigma_out, float *L_out,
@@ -1344,7 +1394,8 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
             "covo_mpc_step: gamma_sigma != 0 is MPPI's covariance adaptation (mppi.py:119-125)");
     REQUIRE(!covo_needs_tables(*params) || args->derive_keys == 1, "covo_mpc_step: disturb_kind=%d needs derive_keys = 1 (the per-step "
             "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
-    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, "covo_mpc_step");
+    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov,
+                                    "covo_mpc_step");
     if (rc) return rc;
     if ((rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream))) return rc;
     return covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream);

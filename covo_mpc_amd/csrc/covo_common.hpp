@@ -86,8 +86,33 @@ struct covo_ctx {
     int iters;                // sample-rollout-update passes per control step
     float *iter_log;          // caller's [iter_n][iters]: entry (e, j) = the minimum sample cost of instance e's pass j
     int iter_n;
+    // the Sigma period (covo_set_step_sigma_period; sigma_shift.hip); sigma_period <= 1: off
+    int sigma_period;         // every sigma_period-th covo-online step refreshes Sigma; the steps between shift the last factor
+    int sigma_age;            // the age the NEXT step runs at: 0 = refresh, 1 .. sigma_period - 1 = reuse
+    int sigma_last_age;       // the age the last enqueued step ran at
+    const float *sigma_L;     // the factor buffer (the single step's or the batch's) that holds the last step's L; null: none yet
+    float sigma_L_sigma;      // the sample_sigma it was built for ...
+    int sigma_L_n;            // ... and for how many instances
 };
 // passes per control step of this handle (1: today's step) and where pass j of instance 0 logs its cost minimum (instance e: + e * iters)
+static inline int covo_sigma_period(const covo_ctx *h) { return h->sigma_period > 1 ? h->sigma_period : 1; }
+// the age this covo-online step of n_inst instances runs at, given where its factor lives: 0 (refresh) unless the period is on, the
+// schedule says reuse and L holds the previous step's factor for the same sample_sigma and instance count
+static inline int covo_sigma_step_age(const covo_ctx *h, const float *L, float sample_sigma, int n_inst)
+{
+    if (covo_sigma_period(h) == 1 || h->sigma_age == 0) return 0;
+    return (h->sigma_L == L && L != nullptr && h->sigma_L_sigma == sample_sigma && h->sigma_L_n == n_inst) ? h->sigma_age : 0;
+}
+// the step that ran at `age` has been enqueued and left its factor in L: advance the schedule
+static inline void covo_sigma_step_done(covo_ctx *h, int age, const float *L, float sample_sigma, int n_inst)
+{
+    h->sigma_last_age = age;
+    if (covo_sigma_period(h) == 1) return;
+    h->sigma_L = L;
+    h->sigma_L_sigma = sample_sigma;
+    h->sigma_L_n = n_inst;
+    h->sigma_age = (age + 1) % covo_sigma_period(h);
+}
 static inline int covo_step_iters(const covo_ctx *h) { return (h->iter_log != nullptr && h->iters > 1) ? h->iters : 1; }
 static inline float *covo_iter_slot(const covo_ctx *h, int pass) { return covo_step_iters(h) > 1 ? h->iter_log + pass : nullptr; }
 // where the solver of this handle's steps writes the instances' temperatures (null: no floor) and for how many instances
@@ -435,6 +460,7 @@ int covo_grow_workspace(covo_ctx *h, void **ws, size_t *bytes, size_t need, hipS
 void batch_state_destroy(covo_ctx *h);
 int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us_out, hipStream_t run);
 int covo_debug_batched_hessians_impl(covo_ctx *h, double *out, int64_t offset_doubles, int64_t count, hipStream_t s);
+int covo_debug_sigma_factor_impl(covo_ctx *h, int batched, float *out, int64_t count, hipStream_t s);
 int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
                            hipStream_t s);
 int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
@@ -444,6 +470,9 @@ const char *batch_small_refusal(const covo_ctx *h, const covo_batch_mode_args *m
 int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                    const float *f_shared, hipStream_t s);
 int launch_cholesky(const float *A, int n, int batch, float *L, hipStream_t s);
+// sigma_shift.hip: the covariance of a reuse step from the previous step's factor L_in [batch][128][128] (fp32, lower): L_out its
+// shifted, volume-normalised factor (may be L_in), Sigma_out = L_out L_out^T; all three 16-byte aligned
+int launch_sigma_shift(const float *L_in, int batch, float sample_sigma, float *Sigma_out, float *L_out, hipStream_t s);
 size_t env_step_inst_bytes(int n);
 void env_step_fill_inst(const covo_env_params *params, int n, void *out);  // host: EnvInst[n] (to be copied to the device)
 int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,

@@ -143,8 +143,11 @@ struct StepState {
     float *f_tab_rollout, *f_tab_hess;  // [H][4] per-step disturbance tables of the sampling rollouts / the Hessian (disturb.hip)
     unsigned *ticket;     // arrival counter of the fused small step (step_small.hip); 0 between launches
     unsigned *sync;       // [16] the streamed finalize launch's sequence number and panel flags (StreamGemmArgs::sync)
-    GraphCache cache;
-    StepKey key;  // normalised arguments + parameters + stream; recorded by eager calls only
+    // [0] the step, [1] the reuse step of a Sigma period (covo_set_step_sigma_period: another launch set, its own graph), each with
+    // its key: normalised arguments + parameters + stream; recorded by eager calls only
+    GraphCache cache[2];
+    StepKey key[2];
+    void forget_graphs() { cache[0].forget(), cache[1].forget(); }
 };
 constexpr int DYN_BYTES = 48;
 // up to this many samples per GPU the step's epsilon is drawn by passenger workgroups of the Sigma chain's last launch
@@ -178,7 +181,7 @@ void step_state_destroy(covo_ctx *h)
 {
     StepState *st = reinterpret_cast<StepState *>(h->step);
     if (!st) return;
-    st->cache.drop();
+    st->forget_graphs();
     free_and_null(st->dyn, st->state_buf, st->a_mean_shift, st->R, st->Sigma, st->L, st->Ls, st->eps_tiled, st->f_tab_rollout,
                   st->f_tab_hess, st->ticket, st->sync);
     delete st;
@@ -217,7 +220,7 @@ CovoOpts covo_default_opts()
 // begin launch is not part of the graph).
 static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, const covo_step_args &a, hipStream_t s,
                         const DebugMasks &dbg = DebugMasks(),
-                        const HessBegin *begin = nullptr, const float *state_direct = nullptr, const int pass = 0)
+                        const HessBegin *begin = nullptr, const float *state_direct = nullptr, const int pass = 0, const bool reuse = false)
 {
     const int M = dbg.step;
     float *iter_out = covo_iter_slot(h, pass);  // an iterated step: this pass's merge logs its cost minimum there
@@ -237,7 +240,7 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     // rollouts (shared step key) and for the Hessian's deterministic rollout (per-step keys), resolved once per control step
     const bool tables = covo_needs_tables(p);
     if (tables && (rc = launch_disturb_tables_step(p, state, st->dyn, a.rollout_deterministic, st->f_tab_rollout,
-                                                   a.mode == COVO_MODE_COVO_ONLINE ? st->f_tab_hess : nullptr, s))) return rc;
+                                                   (a.mode == COVO_MODE_COVO_ONLINE && !reuse) ? st->f_tab_hess : nullptr, s))) return rc;
     // a = clip(am_shift + L eps): what the three modes' noise launches share (epsilon drawn in-kernel from the step's key in st->dyn)
     NoiseDesc nd;
     nd.mu = am_shift;
@@ -246,7 +249,14 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     nd.N = N;
     nd.a = a.a;
     nd.propagate_nan = covo_propagate_nan(h);
-    if (a.mode == COVO_MODE_COVO_ONLINE) {
+    if (a.mode == COVO_MODE_COVO_ONLINE && reuse) {
+        // a reuse step of a Sigma period: no Hessian, no Sigma chain -- the previous step's factor is shifted in place (sigma_shift.hip),
+        // a_cov is its Sigma', and the samples are drawn from it as covo-offline draws from a table row (in-kernel Philox); the later
+        // passes of an iterated step sample from the same L'
+        if (pass == 0 && (rc = launch_sigma_shift(st->L, 1, a.sample_sigma, a.a_cov ? a.a_cov : st->Sigma, st->L, s))) return rc;
+        nd.L = st->L;
+        if ((rc = launch_noise_gemm(nd, s))) return rc;
+    } else if (a.mode == COVO_MODE_COVO_ONLINE) {
         // the Hessian's last launch leaves the Sigma chain's input statistics in the chain's workspace: no prep launch
         const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15;
         const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma);
@@ -393,15 +403,10 @@ static void step_sync_epoch(covo_ctx *h)
     h->dbg_epoch = h->opt.epoch;
 }
 
-int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                   const float *f_shared, hipStream_t s)
+// reuse: a reuse step of a Sigma period (covo_set_step_sigma_period): enqueue_step's reuse branch, with a graph of its own
+static int step_enqueue_all(covo_ctx *h, StepState *st, const covo_env_params *params, const covo_step_args *args, uint32_t key0,
+                            uint32_t key1, const float *f_shared, hipStream_t s, const bool reuse)
 {
-    if (!h->step) {
-        int rc = step_state_init(h);
-        if (rc) return rc;
-    }
-    step_sync_epoch(h);
-    StepState *st = reinterpret_cast<StepState *>(h->step);
     // per-step scalars: kernel arguments of the begin launch
     DynBlock blk;
     std::memset(&blk, 0, sizeof(blk));
@@ -426,7 +431,7 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     };
     if (small && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0) {
         // an eager handle: the WHOLE step is one launch, the begin launch's work included (per workgroup, step_small.hip)
-        st->cache.have_key = false;  // (st->dyn / st->state_buf are not refreshed: a later graph capture starts from an eager call)
+        st->cache[0].have_key = false;  // (st->dyn / st->state_buf are not refreshed: a later graph capture starts from an eager call)
         for (int j = 0; j < K; ++j) {
             // (an iterated step: the last workgroup of every pass parks the pass's raw key at st->dyn[10..11] for the next one)
             int rc = launch_step_small(h, *params, j ? later : *args, args->state, args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift,
@@ -438,9 +443,10 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     }
     // eager covo-online steps (no per-step force tables, whose launch precedes the Hessian and reads the scalars): the begin work
     // rides in the Hessian's first launch -- one launch boundary less (COVO_FOLD_BEGIN=0 keeps the begin launch)
+    // (a reuse step has no Hessian launch to fold into: it keeps the begin launch)
     if (h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
-        !covo_needs_tables(*params)) {
-        st->cache.have_key = false;
+        !covo_needs_tables(*params) && !reuse) {
+        st->cache[0].have_key = false;
         for (int j = 0; j < K; ++j) {
             HessBegin hb;
             hb.pass = j;
@@ -466,13 +472,13 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
             if (j > 0)
                 hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, on, (const float *)args->a_mean,
                                    am_shift, st->dyn, st->state_buf, 1, shared_noise_scale, DynBlock(), mppi_cov, st->Ls, st->sync, j);
-            int rc = enqueue_step(h, st, *params, *args, on, DebugMasks(), nullptr, nullptr, j);
+            int rc = enqueue_step(h, st, *params, *args, on, DebugMasks(), nullptr, nullptr, j, reuse);
             if (rc || (with_arbiter && (rc = between(j)))) return rc;
         }
         return 0;
     };
     if (K > 1 && covo_arb_on(h)) {
-        st->cache.forget();
+        st->forget_graphs();
         return passes(s, true);
     }
 
@@ -485,12 +491,31 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     k.params.reset_traj = 0;  // the env step's auto-reset switches: no launch of the control step reads them
     k.params.reset_dt = k.params.reset_disturb_scale = 0.0;
     k.stream = s;
-    const bool same = st->cache.have_key && std::memcmp(&k, &st->key, sizeof(k)) == 0;
+    GraphCache &cache = st->cache[reuse ? 1 : 0];
+    StepKey &key = st->key[reuse ? 1 : 0];
+    const bool same = cache.have_key && std::memcmp(&k, &key, sizeof(k)) == 0;
     if (!same) {
-        st->key = k;
-        st->cache.have_key = true;
+        key = k;
+        cache.have_key = true;
     }
-    return graph_cache_run(h, st->cache, s, same, "covo_mpc_step", [&](hipStream_t on) { return passes(on, false); });
+    return graph_cache_run(h, cache, s, same, "covo_mpc_step", [&](hipStream_t on) { return passes(on, false); });
+}
+
+int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
+                   const float *f_shared, hipStream_t s)
+{
+    if (!h->step) {
+        int rc = step_state_init(h);
+        if (rc) return rc;
+    }
+    step_sync_epoch(h);
+    StepState *st = reinterpret_cast<StepState *>(h->step);
+    // covo_set_step_sigma_period: the age this step runs at -- 0: today's step, which leaves its factor in st->L; else a reuse step
+    const bool online = args->mode == COVO_MODE_COVO_ONLINE;
+    const int age = online ? covo_sigma_step_age(h, st->L, args->sample_sigma, 1) : 0;
+    const int rc = step_enqueue_all(h, st, params, args, key0, key1, f_shared, s, age != 0);
+    if (rc == 0 && online) covo_sigma_step_done(h, age, st->L, args->sample_sigma, 1);
+    return rc;
 }
 
 // ---- the flight recorder behind a step (plan_trace.hip): one eager launch that rolls the new mean out with the inputs the step's
@@ -703,6 +728,7 @@ struct BatchState {
     covo_batch_args key;  // with `stream` and `params`: what the cached scratch and graph were built for
     hipStream_t stream = nullptr;
     GraphCache cache{};
+    GraphCache cache_reuse{};  // the reuse step of a Sigma period (covo_set_step_sigma_period): another launch set, its own graph
     float4 *eps_tiled = nullptr;  // [E][ceil(N/32)][16][64]: the step's epsilon of every instance, drawn under the Sigma chain's
     size_t eps_cap = 0;           // finalize launch (eps_tiles.hpp), as in the single step
 };
@@ -712,6 +738,7 @@ struct BatchState {
 static void batch_state_free(BatchState *b)
 {
     b->cache.drop();
+    b->cache_reuse.forget();
     free_and_null(b->dyn, b->a_mean_shift, b->R, b->Sigma, b->L, b->consts, b->ro_args, b->partials, b->diag_rec, b->models,
                   b->tab_rollout, b->tab_hess);
 }
@@ -722,8 +749,9 @@ void step_graphs_drop(covo_ctx *h)
 {
     StepState *st = reinterpret_cast<StepState *>(h->step);
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (st) st->cache.forget();
+    if (st) st->forget_graphs();
     if (b) b->cache.forget();
+    if (b) b->cache_reuse.forget();
     if (b) b->small.cache.forget();
 }
 
@@ -806,7 +834,7 @@ void batch_state_destroy(covo_ctx *h)
 // 71 200 unforked with the same launches and 76 300 with the persistent tails -- which must not run side by side: two persistent
 // launches can starve each other of workgroup slots, the barriers then time out.)
 static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, hipStream_t s, const DebugMasks &dbg = DebugMasks(),
-                         const int pass = 0)
+                         const int pass = 0, const bool reuse = false)
 {
     const int E = a.n_envs, N = a.n_samples;
     const int M = dbg.step;  // 63 outside covo_debug_time_batched (which replays selected launch groups)
@@ -815,6 +843,20 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     // covo.py:231: CoVO's sampling rollouts run step_env(deterministic=True); get_hessian likewise (covo.py:152)
     if ((M & 1) && b->tables && (rc = launch_disturb_tables_batched(b->models, a.states, b->dyn, E, 1, b->tab_rollout, b->tab_hess, s)))
         return rc;
+    NoiseDesc nd;
+    nd.L = b->L;
+    nd.mu = b->a_mean_shift;
+    nd.dyn = b->dyn;
+    nd.N = N;
+    nd.a = a.a;
+    nd.batch = E;
+    nd.propagate_nan = covo_propagate_nan(h);
+    if (reuse) {
+        // a reuse step of a Sigma period: every instance's factor is shifted in place (sigma_shift.hip; pass 0 only), a_cov is its
+        // Sigma', the GEMM draws its epsilon itself
+        if (pass == 0 && (rc = launch_sigma_shift(b->L, E, a.sample_sigma, a.a_cov ? a.a_cov : b->Sigma, b->L, s))) return rc;
+        if ((rc = launch_noise_gemm(nd, s))) return rc;
+    } else {
     // as in the single step: the Hessian's last launch leaves every instance's Sigma-chain input statistics, no prep launch
     const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15;
     const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma, E);
@@ -857,17 +899,10 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     sd.persistent_ok = (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0;
     sd.r_has_stats = stats;
     if ((M & 4) && (rc = launch_sigma_ns(h->opt, sd, h->ws_sigma, s, dbg))) return rc;
-    NoiseDesc nd;
-    nd.L = b->L;
-    nd.mu = b->a_mean_shift;
     nd.eps = ahead ? reinterpret_cast<const float *>(b->eps_tiled) : nullptr;  // (else the GEMM draws from b->dyn)
     nd.eps_tiled = ahead;
-    nd.dyn = b->dyn;
-    nd.N = N;
-    nd.a = a.a;
-    nd.batch = E;
-    nd.propagate_nan = covo_propagate_nan(h);
     if ((M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
+    }
     if ((M & 16) && (rc = launch_rollout_batched(b->ro_args_host.data(), b->ro_args, E, s))) return rc;
     if (!(M & 32)) return 0;
     const int G = rollout_workgroups(N, false, E);
@@ -933,8 +968,10 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         // new buffers / parameters / instance count: (re)allocate scratch and drop the stale graph (outside the steady state)
         COVO_CHECK_HIP(hipStreamSynchronize(s));
         b->cache.drop();
+        b->cache_reuse.forget();
         if (b->n_envs != E) {
             batch_state_free(b);
+            h->sigma_L = nullptr;  // (the factor buffer goes: the next step of a Sigma period refreshes)
             const size_t M = (size_t)COVO_NA * COVO_NA;
             COVO_CHECK_HIP(hipMalloc(&b->dyn, (size_t)E * 12 * sizeof(uint32_t)));
             COVO_CHECK_HIP(hipMalloc(&b->a_mean_shift, (size_t)E * COVO_NA * sizeof(float)));
@@ -1004,20 +1041,32 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
     // covo_set_step_iters: K passes in one graph; with the update arbiter attached its (eager) launch sits between them and the
     // passes are enqueued eagerly
     const int K = covo_step_iters(h);
+    // covo_set_step_sigma_period: the batch shares one age -- 0: today's step, which leaves the factors in b->L; else a reuse step
+    const int age = covo_sigma_step_age(h, b->L, args->sample_sigma, E);
+    const bool reuse = age != 0;
     auto passes = [&](hipStream_t on, bool with_arbiter) -> int {
         for (int j = 0; j < K; ++j) {
-            int rc = batch_enqueue(h, b, *args, on, DebugMasks(), j);
+            int rc = batch_enqueue(h, b, *args, on, DebugMasks(), j, reuse);
             if (rc == 0 && with_arbiter && j + 1 < K)
                 rc = covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, on, true);
             if (rc) return rc;
         }
         return 0;
     };
+    int rc;
     if (K > 1 && covo_arb_on(h)) {
         b->cache.drop();
-        return passes(s, true);
+        b->cache_reuse.forget();
+        rc = passes(s, true);
+    } else if (reuse) {  // the reuse graph's key is the step's: its first call with these buffers runs eagerly, the second captures
+        const bool same_reuse = same && b->cache_reuse.have_key;
+        b->cache_reuse.have_key = true;
+        rc = graph_cache_run(h, b->cache_reuse, s, same_reuse, "covo_mpc_step_batched", [&](hipStream_t on) { return passes(on, false); });
+    } else {
+        rc = graph_cache_run(h, b->cache, s, same, "covo_mpc_step_batched", [&](hipStream_t on) { return passes(on, false); });
     }
-    return graph_cache_run(h, b->cache, s, same, "covo_mpc_step_batched", [&](hipStream_t on) { return passes(on, false); });
+    if (rc == 0) covo_sigma_step_done(h, age, b->L, args->sample_sigma, E);
+    return rc;
 }
 
 // MPPI / covo-offline for E instances: key upload + ONE fused launch (no begin launch: every workgroup shifts its instance's mean
@@ -1159,6 +1208,23 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
     if (rc || arbiter_only) return rc;
     if ((rc = launch_plan_trace(h, d, E, true, states_true, trace_index, s))) return rc;
     return launch_sample_fan(h, d, E, true, trace_index, s);
+}
+
+// test hook: the factor(s) the LAST single (batched = 0) / env-batched step sampled from -- what the next reuse step of a Sigma period
+// shifts -- device -> device
+int covo_debug_sigma_factor_impl(covo_ctx *h, int batched, float *out, int64_t count, hipStream_t s)
+{
+    StepState *st = reinterpret_cast<StepState *>(h->step);
+    BatchState *b = reinterpret_cast<BatchState *>(h->batch);
+    const float *src = batched ? (b ? b->L : nullptr) : (st ? st->L : nullptr);
+    const int64_t have = (int64_t)COVO_NA * COVO_NA * (batched ? (b ? b->n_envs : 0) : 1);
+    if (src == nullptr || count > have) {
+        covo_set_error("covo_debug_sigma_factor: no %s step has run on this handle, or count=%lld exceeds its %lld floats",
+                       batched ? "batched" : "single", (long long)count, (long long)have);
+        return COVO_E_BADARG;
+    }
+    COVO_CHECK_HIP(hipMemcpyAsync(out, src, (size_t)count * sizeof(float), hipMemcpyDeviceToDevice, s));
+    return 0;
 }
 
 // test hook: the Hessians of the LAST batched step (E x 128 x 128 doubles), device -> host

@@ -606,6 +606,41 @@ int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride);
 #define COVO_HAS_STEP_ITERS 1
 #define COVO_MAX_STEP_ITERS 16
 int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t n_inst);
+
+/* The Sigma period: covo-online reuses a shifted Sigma between refreshes (additive to ABI 10: COVO_HAS_SIGMA_PERIOD; off by default,
+ * and off changes nothing a caller can observe: every launch is the one made without it).  With period = m the handle keeps an AGE:
+ *   age 0            a REFRESH step: exactly the covo-online step (Hessian, Sigma chain, factor); it leaves its factor L on the handle.
+ *   age 1 .. m - 1   a REUSE step: no Hessian, no Sigma chain.  With Sigma = L L^T the covariance the previous step sampled from
+ *                    (n = 128 = 32 stages of 4 actions), it samples from Sigma' = c S(Sigma):
+ *                      S(Sigma)[s][t] = Sigma[s + 1][t + 1] for stages s, t <= 30 (the trailing 124 x 124 block, moved up as the mean is),
+ *                      S(Sigma)[31][31] = Sigma[31][31] (the new last stage takes the old last stage's marginal),
+ *                      S(Sigma)[31][t] = S(Sigma)[t][31] = 0 for t <= 30,
+ *                      c the scalar with log det Sigma' = 2 n log sample_sigma (optimize_sigma's volume constraint).
+ *                    Its factor L' is the rank-4 Cholesky update of L[4:, 4:] by the columns of L[4:, 0:4], next to the factor of
+ *                    L[124:, :] L[124:, :]^T, scaled by sqrt(c) (sigma_shift.hip); a_cov of the step is Sigma', the actions are
+ *                    clip(shifted mean + L' eps) with the in-kernel Philox draw of the step's act key; rollout and update are the
+ *                    step's own.  Under iterations per step no pass of a reuse step runs a Hessian or a Sigma chain: all sample from L'.
+ * The age advances with every enqueued step (the episode drivers advance it as they enqueue; an env-batched step shares one age) and
+ * wraps at m.  A handle without a valid factor -- no step yet, another sample_sigma, another instance count -- refreshes.  A device-side
+ * auto-reset of an instance does not force a refresh: its next samples come from a stale but valid covariance.
+ * covo_set_step_sigma_period: 1 <= period <= COVO_MAX_SIGMA_PERIOD (1 = off); sets the age to 0.  Refused before any launch, at the
+ *   step: a period above 1 on a step whose mode is not covo-online (covo_mpc_step, covo_run_episode, covo_mpc_step_batched_mode,
+ *   covo_run_episode_batched_mode); a sample-sharded step (partial_out != NULL).  The refresh step and the reuse step each have their
+ *   captured graph.  The phase timers (covo_debug_time_*) replay a refresh step's launches.
+ * covo_step_sigma_age: *next_age = the age the next step is scheduled at, *last_age = the age the last enqueued step ran at (either
+ *   may be NULL).
+ * covo_sigma_shift: the shift alone.  L_in = DEVICE float[batch][128][128] (the lower triangle is read), Sigma_out, L_out = DEVICE
+ *   float[batch][128][128], all 16-byte aligned; L_out may be L_in.  L_out's strict upper triangle and Sigma_out's cross block are
+ *   exact zeros, Sigma_out is symmetric bit for bit.
+ * covo_debug_sigma_factor (test hook): the factor(s) L the last single (batched = 0) or env-batched (batched = 1) covo-online step of
+ *   the handle sampled from -- what the next reuse step shifts -- copied to the DEVICE buffer out (count floats, at most 128 * 128 per
+ *   instance). */
+#define COVO_HAS_SIGMA_PERIOD 1
+#define COVO_MAX_SIGMA_PERIOD 64
+int covo_set_step_sigma_period(covo_handle_t h, int32_t period);
+int covo_step_sigma_age(covo_handle_t h, int32_t *next_age, int32_t *last_age);
+int covo_sigma_shift(covo_handle_t h, const float *L_in, int32_t batch, float sample_sigma, float *Sigma_out, float *L_out, void *stream);
+int covo_debug_sigma_factor(covo_handle_t h, int32_t batched, float *out, int64_t count, void *stream);
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,

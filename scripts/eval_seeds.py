@@ -4,8 +4,13 @@ import numpy as np
 from covo_mpc_amd.envs import quadrotor as Q
 name = sys.argv[1]
 # python scripts/eval_seeds.py covo-online [elite=512]: the elite-set update with K elites instead of the softmax weights
-opts = {k: int(v) for k, v in (arg.split("=") for arg in sys.argv[2:])}
-assert set(opts) <= {"elite"}, opts
+# python scripts/eval_seeds.py covo-online --sigma-period 4 (or sigma_period=4): Sigma refreshed every 4th control step
+rest = sys.argv[2:]
+while "--sigma-period" in rest:
+    i = rest.index("--sigma-period")
+    rest[i:i + 2] = [f"sigma_period={rest[i + 1]}"]
+opts = {k: int(v) for k, v in (arg.split("=") for arg in rest)}
+assert set(opts) <= {"elite", "sigma_period"}, opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
 ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **opts)

@@ -1,0 +1,271 @@
+"""CPU: the ABI of the Sigma period (covo_set_step_sigma_period, covo_step_sigma_age, covo_sigma_shift; include/covo_hip.h), the
+`sigma_period` keyword of the Python surface, and the numpy restatement of a reuse step's covariance with its known
+answers.  The restatement is written from the definition; tests/test_gpu_sigma_period.py holds the kernel against it."""
+import ctypes as C
+import inspect
+import os
+import re
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+N_A, DU = 128, 4
+
+
+# ---------------------------------------------------------------------------------------------- the restatement (fp64 numpy)
+def shift_S(Sigma):
+    """S(Sigma): the trailing 124 x 124 block moved up, the old last stage's 4 x 4 marginal as the new last stage, no cross terms."""
+    S = np.zeros_like(Sigma, dtype=np.float64)
+    S[:N_A - DU, :N_A - DU] = Sigma[DU:, DU:]
+    S[N_A - DU:, N_A - DU:] = Sigma[N_A - DU:, N_A - DU:]
+    return S
+
+
+def volume_scalar(S, sample_sigma):
+    """c with log det (c S) = 2 n log sample_sigma."""
+    sign, logdet = np.linalg.slogdet(S)
+    assert sign > 0
+    return float(np.exp((2.0 * N_A * np.log(float(sample_sigma)) - logdet) / N_A))
+
+
+def shift_sigma_ref(Sigma, sample_sigma):
+    """Sigma' = c S(Sigma) from the covariance itself."""
+    S = shift_S(np.asarray(Sigma, dtype=np.float64))
+    return volume_scalar(S, sample_sigma) * S
+
+
+def rank_update(Lmat, X):
+    """The lower factor of Lmat Lmat^T + X X^T by one rotation per column and update vector (the issue's recurrence):
+    r = sqrt(L_kk^2 + x_k^2), c = r / L_kk, s = x_k / L_kk, L_ik <- (L_ik + s x_i) / c, x_i <- c x_i - s L_ik."""
+    Lw = np.array(Lmat, dtype=np.float64)
+    n = Lw.shape[0]
+    for j in range(X.shape[1]):
+        x = np.array(X[:, j], dtype=np.float64)
+        for k in range(n):
+            r = np.hypot(Lw[k, k], x[k])
+            c, s = r / Lw[k, k], x[k] / Lw[k, k]
+            Lw[k, k] = r
+            if k + 1 < n:
+                Lw[k + 1:, k] = (Lw[k + 1:, k] + s * x[k + 1:]) / c
+                x[k + 1:] = c * x[k + 1:] - s * Lw[k + 1:, k]
+    return Lw
+
+
+def shift_factor_ref(L, sample_sigma):
+    """(Sigma', L') from the factor alone, as the kernel forms them: the rank-4 update of L22 by the columns of L21, the factor of
+    L[124:, :] L[124:, :]^T, c from the diagonal."""
+    L = np.tril(np.asarray(L, dtype=np.float64))
+    Lp = np.zeros((N_A, N_A))
+    Lp[:N_A - DU, :N_A - DU] = rank_update(L[DU:, DU:], L[DU:, :DU])
+    Lp[N_A - DU:, N_A - DU:] = np.linalg.cholesky(L[N_A - DU:, :] @ L[N_A - DU:, :].T)
+    logdet = 2.0 * np.log(np.diag(Lp)).sum()
+    c = np.exp((2.0 * N_A * np.log(float(sample_sigma)) - logdet) / N_A)
+    Lp *= np.sqrt(c)
+    return Lp @ Lp.T, Lp
+
+
+def random_spd(rng, cond=1e3):
+    w = np.exp(np.linspace(0.0, np.log(cond), N_A)) * 1e-2
+    U, _ = np.linalg.qr(rng.normal(size=(N_A, N_A)))
+    A = (U * w) @ U.T
+    return 0.5 * (A + A.T)  # exactly symmetric
+
+
+# ---------------------------------------------------------------------------------------------- known answers of the restatement
+def test_sigma_squared_identity_is_a_fixed_point():
+    for sigma in (0.5, 0.3):
+        S = shift_sigma_ref(sigma ** 2 * np.eye(N_A), sigma)
+        assert np.abs(S - sigma ** 2 * np.eye(N_A)).max() < 1e-14
+        S2, Lp = shift_factor_ref(sigma * np.eye(N_A), sigma)
+        assert np.abs(S2 - sigma ** 2 * np.eye(N_A)).max() < 1e-14 and np.abs(Lp - sigma * np.eye(N_A)).max() < 1e-14
+    # another input volume: the constraint brings it back
+    S = shift_sigma_ref(4.0 * np.eye(N_A), 0.5)
+    assert np.abs(S - 0.25 * np.eye(N_A)).max() < 1e-14
+
+
+def test_block_diagonal_blocks_move_up_and_the_last_repeats():
+    rng = np.random.default_rng(5)
+    blocks = []
+    for t in range(32):
+        A = rng.normal(size=(4, 4))
+        blocks.append(A @ A.T + (0.5 + 0.1 * t) * np.eye(4))
+    Sigma = np.zeros((N_A, N_A))
+    for t, B in enumerate(blocks):
+        Sigma[4 * t:4 * t + 4, 4 * t:4 * t + 4] = B
+    sigma = 0.5
+    Sp = shift_sigma_ref(Sigma, sigma)
+    moved = blocks[1:] + [blocks[-1]]
+    c = Sp[0, 0] / moved[0][0, 0]
+    for t, B in enumerate(moved):
+        assert np.abs(Sp[4 * t:4 * t + 4, 4 * t:4 * t + 4] - c * B).max() < 1e-12 * np.abs(B).max() * max(c, 1.0)
+    off = Sp.copy()
+    for t in range(32):
+        off[4 * t:4 * t + 4, 4 * t:4 * t + 4] = 0.0
+    assert np.all(off == 0.0)
+    assert abs(np.linalg.slogdet(Sp)[1] - 2 * N_A * np.log(sigma)) < 1e-10
+    # the factor route gives the same matrix
+    S2, Lp = shift_factor_ref(np.linalg.cholesky(Sigma), sigma)
+    assert np.abs(S2 - Sp).max() < 1e-12 * np.abs(Sp).max()
+
+
+def test_shift_of_a_random_spd_matrix_has_the_zero_block_and_is_spd():
+    rng = np.random.default_rng(11)
+    Sigma = random_spd(rng)
+    S = shift_S(Sigma)
+    assert np.all(S[N_A - DU:, :N_A - DU] == 0.0) and np.all(S[:N_A - DU, N_A - DU:] == 0.0)
+    assert np.array_equal(S, S.T)
+    assert np.array_equal(S[:N_A - DU, :N_A - DU], Sigma[DU:, DU:]) and np.array_equal(S[N_A - DU:, N_A - DU:], Sigma[N_A - DU:, N_A - DU:])
+    assert np.linalg.eigvalsh(S).min() > 0.0
+    Sp = shift_sigma_ref(Sigma, 0.5)
+    assert abs(np.linalg.slogdet(Sp)[1] - 2 * N_A * np.log(0.5)) < 1e-9
+    # Sigma' from the factor == Sigma' from the covariance
+    S2, Lp = shift_factor_ref(np.linalg.cholesky(Sigma), 0.5)
+    assert np.abs(S2 - Sp).max() < 1e-11 * np.abs(Sp).max()
+    assert np.all(np.triu(Lp, 1) == 0.0) and np.all(np.diag(Lp) > 0.0)
+
+
+def test_rank4_update_equals_the_cholesky_of_the_trailing_block():
+    rng = np.random.default_rng(12)
+    for cond in (6e2, 7e4):
+        Sigma = random_spd(rng, cond)
+        L = np.linalg.cholesky(Sigma)
+        up = rank_update(L[DU:, DU:], L[DU:, :DU])
+        ref = np.linalg.cholesky(Sigma[DU:, DU:])
+        assert np.abs(up - ref).max() < 1e-11 * np.abs(ref).max(), cond
+        assert np.all(np.triu(up, 1) == 0.0)
+
+
+# ---------------------------------------------------------------------------------------------- the ABI and the keyword
+@pytest.fixture(scope="module")
+def built():
+    import __graft_entry__ as g
+    g.build()
+    from covo_mpc_amd import _lib
+    return _lib
+
+
+def test_sigma_period_entry_points_exist_with_the_declared_types(built):
+    lib = built.load_library()
+    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    assert re.search(r"#define COVO_HAS_SIGMA_PERIOD 1\b", hdr) and built.COVO_HAS_SIGMA_PERIOD == 1
+    assert int(re.search(r"#define COVO_MAX_SIGMA_PERIOD\s+(\d+)", hdr).group(1)) == 64 == built.COVO_MAX_SIGMA_PERIOD
+    assert re.search(r"\bint covo_set_step_sigma_period\(covo_handle_t h, int32_t period\);", hdr)
+    assert re.search(r"\bint covo_step_sigma_age\(covo_handle_t h, int32_t \*next_age, int32_t \*last_age\);", hdr)
+    assert re.search(r"\bint covo_sigma_shift\(covo_handle_t h, const float \*L_in, int32_t batch, float sample_sigma, float \*Sigma_out, "
+                     r"float \*L_out, void \*stream\);", hdr)
+    fn = lib.covo_set_step_sigma_period
+    assert fn.restype is C.c_int and list(fn.argtypes) == [C.c_void_p, C.c_int32]
+    fn = lib.covo_sigma_shift
+    assert fn.restype is C.c_int and list(fn.argtypes) == [C.c_void_p, C.c_void_p, C.c_int32, C.c_float, C.c_void_p, C.c_void_p, C.c_void_p]
+    assert lib.covo_step_sigma_age.restype is C.c_int
+    for name in ("covo_set_step_sigma_period", "covo_step_sigma_age", "covo_sigma_shift"):
+        assert name in built.EXPORTS
+    v = int(re.search(r"#define COVO_ABI_VERSION (\d+)", hdr).group(1))
+    assert v == 10 == built.ABI_VERSION == lib.covo_abi_version()  # additive
+    # a null handle is refused before anything else happens (no GPU needed)
+    assert lib.covo_set_step_sigma_period(None, 2) != 0 and b"null handle" in lib.covo_last_error()
+    assert lib.covo_sigma_shift(None, None, 1, 0.5, None, None, None) != 0 and b"null handle" in lib.covo_last_error()
+    assert lib.covo_step_sigma_age(None, None, None) != 0 and b"null handle" in lib.covo_last_error()
+
+
+def test_sigma_period_is_a_keyword_defaulting_to_one(built):
+    from covo_mpc_amd import controllers
+    from covo_mpc_amd.controllers._core import SamplingCore
+    from covo_mpc_amd.envs.quadrotor import Args, eval_env_batched, get_controller
+    for fn in (SamplingCore.__init__, controllers.MPPIController.__init__, controllers.CoVOController.__init__,
+               controllers.BatchedCoVOController.__init__, controllers.BatchedMPPIController.__init__, get_controller,
+               eval_env_batched):
+        p = inspect.signature(fn).parameters
+        assert "sigma_period" in p and p["sigma_period"].default == 1, fn
+    assert Args().sigma_period == 1
+    assert callable(SamplingCore.sigma_info) and callable(SamplingCore.sigma_shift) and callable(SamplingCore.set_sigma_period)
+    assert [built.check_sigma_period(m) for m in (1, 2, 64)] == [1, 2, 64]
+    assert built.check_sigma_period(1, "offline") == 1 and built.check_sigma_period(1, "MPPI") == 1
+
+
+def _env(device=None):
+    import covo_mpc_amd as cm
+    return cm.envs.Quad3D(task="tracking_zigzag", disturb_type="gaussian", enable_randomizer=False, disable_rollover_terminate=True,
+                          generate_noisy_state=True, device=device)
+
+
+@pytest.mark.parametrize("bad", [0, 65, 2.5, -1, None, "2", True])
+def test_constructors_refuse_sigma_period_out_of_range(built, bad):
+    """ValueError before anything is built: no device is needed."""
+    from covo_mpc_amd import controllers
+    from covo_mpc_amd.controllers._core import SamplingCore
+    from covo_mpc_amd.envs.quadrotor import eval_env_batched, get_controller
+    env = _env()
+    with pytest.raises(ValueError, match="sigma_period="):
+        SamplingCore(256, 32, 0.01, 1.0, sigma_period=bad)
+    with pytest.raises(ValueError, match="sigma_period="):
+        controllers.BatchedCoVOController(None, 3, 256, 32, 0.01, sigma_period=bad)
+    with pytest.raises(ValueError, match="sigma_period="):
+        controllers.BatchedMPPIController(None, 3, 256, 32, 0.01, sigma_period=bad)
+    with pytest.raises(ValueError, match="sigma_period="):
+        eval_env_batched(env, 2, "N256_H32_lam0.01", sigma_period=bad)
+    for name in ("mppi", "covo-online", "covo-offline"):
+        with pytest.raises(ValueError, match="sigma_period="):
+            get_controller(env, name, "N256_H32_lam0.01", device="cpu", sigma_period=bad)
+
+
+def test_modes_without_a_sigma_per_step_refuse_a_period(built):
+    """MPPI, covo-offline and the env-batched offline / MPPI controllers: ValueError in words, before anything is built."""
+    from covo_mpc_amd import controllers
+    from covo_mpc_amd.envs.quadrotor import get_controller
+    env = _env()
+    with pytest.raises(ValueError, match="sigma_period=2 with mppi"):
+        get_controller(env, "mppi", "N256_H32_lam0.01", device="cpu", sigma_period=2)
+    with pytest.raises(ValueError, match="sigma_period=2 with covo-offline"):
+        get_controller(env, "covo-offline", "N256_H32_lam0.01", device="cpu", sigma_period=2)
+    with pytest.raises(ValueError, match="sigma_period=3 with MPPI"):
+        controllers.MPPIController(env, None, 256, 32, 0.01, sigma_period=3)
+    with pytest.raises(ValueError, match="sigma_period=3 with offline"):
+        controllers.CoVOController(env, None, 256, 32, 0.01, "offline", sigma_period=3)
+    with pytest.raises(ValueError, match="sigma_period=2 with the env-batched covo-offline controller"):
+        controllers.BatchedCoVOController(None, 3, 256, 32, 0.01, mode="offline", sigma_period=2)
+    with pytest.raises(ValueError, match="sigma_period=2 with the env-batched MPPI controller"):
+        controllers.BatchedMPPIController(None, 3, 256, 32, 0.01, sigma_period=2)
+
+
+def test_sigma_period_in_range_passes_the_keyword_check(built):
+    """Without a device the construction gets as far as the device check (CovoError, not ValueError): the keyword was accepted."""
+    import torch
+    from covo_mpc_amd.envs.quadrotor import get_controller
+    if not torch.cuda.is_available():
+        with pytest.raises(built.CovoError, match="needs a ROCm GPU"):
+            get_controller(_env(), "covo-online", "N256_H32_lam0.01", device="cpu", sigma_period=4)
+        return
+    c, _ = get_controller(_env("cuda:0"), "covo-online", "N256_H32_lam0.01", device="cuda:0")
+    assert c.core.sigma_period == 1 and c.core.sigma_info() == {} and c.core.sigma_age == 0
+    c.core.close()
+    c, _ = get_controller(_env("cuda:0"), "covo-online", "N256_H32_lam0.01", device="cuda:0", sigma_period=4)
+    assert c.core.sigma_period == 4 and c.core.sigma_info() == {"sigma_age": 0} and c.core.sigma_age == 0
+    c.core.close()
+
+
+def test_sharded_core_refuses_a_sigma_period_without_a_device(built, monkeypatch):
+    """A process group of two ranks: NotImplementedError, worded like iters', before the device is looked for."""
+    import torch.distributed as dist
+    from covo_mpc_amd.controllers._core import SamplingCore
+    group = object()
+    monkeypatch.setattr(dist, "get_world_size", lambda g=None: 2 if g is group else 1)
+    monkeypatch.setattr(dist, "get_rank", lambda g=None: 0)
+    with pytest.raises(NotImplementedError, match="sigma_period=2 on sample-sharded ranks"):
+        SamplingCore(256, 32, 0.01, 1.0, process_group=group, sigma_period=2)
+    with pytest.raises(ValueError, match="sigma_period="):  # the range check comes first
+        SamplingCore(256, 32, 0.01, 1.0, process_group=group, sigma_period=65)
+
+
+def test_debug_path_refuses_a_sigma_period(built):
+    from covo_mpc_amd.controllers._core import SamplingCore
+
+    class Stub:
+        ess_min, compute_plan, compute_diag, compute_fan, arb_mask, update_rule, iters, elite, sigma_period = (
+            0.0, False, False, 0, 0, "softmax", 1, 0, 2)
+
+    with pytest.raises(NotImplementedError, match="sigma_period=2 acts in the fused step"):
+        SamplingCore.require_fused_for_diag(Stub())
+    Stub.sigma_period = 1
+    SamplingCore.require_fused_for_diag(Stub())  # no period: the kernel-by-kernel path is free to run
