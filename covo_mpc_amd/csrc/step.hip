@@ -16,6 +16,7 @@
 #include "rng_device.hpp"
 #include "step_begin.hpp"
 #include "step_small.hpp"
+#include "step_graph.hpp"
 
 // the ONE eager launch of every step, ahead of the replayed graph.  What changes per step travels in its kernel
 // arguments (48 bytes; an async H2D copy of the same block runs as a ~5 us copy kernel on this stack): the controller's
@@ -61,61 +62,6 @@ __global__ void step_begin_kernel(const float *__restrict__ a_mean, float *__res
 // covo_debug_time_step's copies of a step have no begin launch between them: the streamed finalize launch's flags would still
 // carry the previous copy's sequence number (its workers would not wait for anything): one bump per copy
 __global__ void stream_seq_bump_kernel(unsigned *seq) { seq[0] = seq[0] + 1u; }
-
-// ---- the capture-once / replay cache every step path embeds (StepState, BatchState, BatchSmall).  The owner compares and records
-// its key itself (the three keys differ) and tells graph_cache_run whether it is unchanged:
-//   unchanged, graph present                    hipGraphLaunch on the caller's stream, nothing else
-//   unchanged, no graph, COVO_FLAG_NO_GRAPH clear   capture the step on h->side_stream, instantiate, launch on the caller's stream
-//   otherwise                                   a changed key drops the graph before anything is enqueued; eager on the caller's stream
-// so the first call with new buffers runs eagerly (all one-time attribute calls / allocations happen there), the second captures,
-// later ones replay.
-struct GraphCache {
-    bool have_key, have_graph;
-    hipGraph_t graph;
-    hipGraphExec_t exec;
-    void drop()
-    {
-        if (!have_graph) return;
-        (void)hipGraphExecDestroy(exec);
-        (void)hipGraphDestroy(graph);
-        have_graph = false;
-    }
-    void forget()  // the next call runs eagerly, the one after captures again
-    {
-        drop();
-        have_key = false;
-    }
-};
-
-// enqueue(stream) enqueues the step.  Capture is on the library's own stream (the caller's may be the legacy default stream, which
-// cannot capture); nothing executes during capture, the graph is then launched on the caller's stream.  A failed capture leaves
-// the cache without a graph.
-template <class Enqueue>
-static int graph_cache_run(covo_ctx *h, GraphCache &c, hipStream_t s, bool same, const char *name, Enqueue enqueue)
-{
-    if (!same) c.drop();
-    if (c.have_graph) {
-        COVO_CHECK_HIP(hipGraphLaunch(c.exec, s));
-        return 0;
-    }
-    if (!same || (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0) return enqueue(s);
-    hipStream_t cs = h->side_stream;
-    COVO_CHECK_HIP(hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal));
-    const int rc = enqueue(cs);
-    hipGraph_t g = nullptr;
-    hipError_t e = hipStreamEndCapture(cs, &g);
-    if (rc == 0 && e != hipSuccess) covo_set_error("%s: stream capture failed: %s", name, hipGetErrorString(e));
-    if (rc == 0 && e == hipSuccess && (e = hipGraphInstantiate(&c.exec, g, nullptr, nullptr, 0)) != hipSuccess)
-        covo_set_error("%s: hipGraphInstantiate failed: %s", name, hipGetErrorString(e));
-    if (rc != 0 || e != hipSuccess) {
-        if (g) (void)hipGraphDestroy(g);
-        return rc ? rc : (int)e;
-    }
-    c.graph = g;
-    c.have_graph = true;
-    COVO_CHECK_HIP(hipGraphLaunch(c.exec, s));
-    return 0;
-}
 
 // hipFree + null for every pointer given
 template <class... T>
@@ -214,7 +160,136 @@ CovoOpts covo_default_opts()
     return o;
 }
 
-// the launch sequence of one step (everything reads per-step scalars from st->dyn)
+// ---- the covo-online chain of a step, single or env-batched: Hessian -> Sigma chain (epsilon drawn ahead, under its finalize launch)
+// -> noise GEMM; a reuse step of a Sigma period: factor shift -> GEMM.  The single step is the batched one at E = 1 plus what only
+// one matrix may have (sync, defer_cov, hess.begin).  A host-only view in the style of covo_common.hpp's descriptors: filled field by
+// field at the two call sites (enqueue_step, batch_enqueue); a null / zero switches the feature off.
+struct OnlineChainView {
+    int E = 1;                    // instances
+    uint32_t *dyn = nullptr;      // the per-step scalars; instance e's at dyn + e * dyn_stride ...
+    int dyn_stride = 0;           // ... 0 (single) / 12
+    int64_t sample_offset = 0;    // global id of local sample 0 (a sample-sharded single step)
+    int N = 0;
+    const float *mu = nullptr;    // [E][128] the shifted mean
+    double *R = nullptr;          // [E][128][128] the Hessian
+    float sample_sigma = 0.0f;
+    float *Sigma = nullptr, *L = nullptr;  // [E][128][128] a_cov out and its factor
+    float4 *eps_tiled = nullptr;  // the step's epsilon in tile order (eps_tiles.hpp), instance e's eps_stride float4 on; null: the
+    size_t eps_stride = 0;        // GEMM draws in-kernel
+    float *a = nullptr;           // [E][H][N][4] action stripes out
+    // the caller's part of the Hessian's descriptor: state, trajectories, T, params, f_tab (the step's Hessian table, or null) and
+    // begin (single) / consts_dev, models_dev, traj_stride (batch); enqueue_online_chain fills the rest
+    HessianDesc hess;
+    // epsilon is drawn ahead when ALL of these launch groups (DebugMasks::step) are selected -- 4 (single) / 4 | 8 (batch).  The masks
+    // only differ inside the two phase timers, whose "Sigma alone" (mask 4) is not the same thing: covo_debug_time_step keeps the draw
+    // under the finalize launch (bench.py's GEMM-as-its-own-launch figure is T(4 | 8) - T(4): the draw must be on both sides),
+    // covo_debug_time_batched times the chain without passengers (bench.py --config envs lists sigma_us next to a mask-8 GEMM that
+    // draws in-kernel).  Mask 4 is reachable from Python on both, so the two stay apart.
+    int ahead_groups = 4;
+    // one matrix only
+    unsigned *sync = nullptr;     // the streamed finalize launch's flags: the GEMM may run inside the chain's last launch
+    bool defer_cov = false;       // a_cov may be left to the GEMM's first workgroups (CovDeferred)
+};
+
+static int enqueue_online_chain(covo_ctx *h, const OnlineChainView &v, hipStream_t s, const DebugMasks &dbg, int pass, bool reuse)
+{
+    const int M = dbg.step;
+    int rc;
+    NoiseDesc nd;
+    nd.L = v.L;
+    nd.mu = v.mu;
+    nd.dyn = v.dyn;
+    nd.sample_offset = v.sample_offset;
+    nd.N = v.N;
+    nd.a = v.a;
+    nd.batch = v.E;
+    nd.propagate_nan = covo_propagate_nan(h);
+    if (reuse) {
+        // a reuse step of a Sigma period: no Hessian, no Sigma chain -- every instance's factor of the previous step is shifted in
+        // place (sigma_shift.hip), a_cov is its Sigma', and the samples are drawn from it as covo-offline draws from a table row
+        // (in-kernel Philox); the later passes of an iterated step sample from the same L'
+        if (pass == 0 && (rc = launch_sigma_shift(v.L, v.E, v.sample_sigma, v.Sigma, v.L, s))) return rc;
+        return launch_noise_gemm(nd, s);
+    }
+    // the Hessian's last launch leaves the Sigma chain's input statistics in the chain's workspace: no prep launch
+    const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15;
+    const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma, v.E);
+    HessianDesc hd = v.hess;
+    hd.a_mean = v.mu;
+    hd.batch = v.E;
+    hd.R = v.R;
+    hd.stats = stats ? &so : nullptr;
+    hd.status_dev = h->status_dev;
+    if ((M & 2) && (rc = launch_hessian(hd, h->ws_hess, s, dbg))) return rc;  // :134-185
+    const bool finalize = dbg.sigma_stages >= 4;
+    // epsilon needs only the act keys: it is drawn under the chain's finalize launch (one workgroup per matrix factors), the GEMM loads
+    // it -- the in-kernel Philox costs the batched GEMM ~9 us, its matrix pipe hides no vector work
+    const bool ahead = v.eps_tiled != nullptr && (M & v.ahead_groups) == v.ahead_groups && finalize;
+    EpsGenArgs gen;
+    gen.eps_tiled = ahead ? v.eps_tiled : nullptr;
+    gen.dyn = v.dyn;
+    gen.sample_offset = v.sample_offset;
+    gen.N = v.N;
+    gen.n_inst = v.E;
+    gen.dyn_stride = v.dyn_stride;
+    gen.eps_stride = v.eps_stride;
+    // a_cov is written by the GEMM's first workgroups, not by the chain's one-workgroup finalize launch (CovDeferred)
+    CovDeferred cov;
+    std::memset(&cov, 0, sizeof(cov));
+    const bool defer = v.defer_cov && (M & 8) && finalize;
+    // the GEMM streamed under the factorisation, inside the chain's last launch (one matrix, persistent launches allowed)
+    StreamGemmArgs sg;
+    sg.mu = v.mu;
+    sg.dyn = v.dyn;
+    sg.sample_offset = v.sample_offset;
+    sg.N = v.N;
+    sg.a_out = v.a;
+    sg.L_stream = v.L;
+    sg.sync = v.sync;
+    sg.a_cov_out = v.Sigma;
+    sg.nanp = covo_propagate_nan(h) ? 1 : 0;
+    const bool want_stream = v.sync != nullptr && h->opt.stream_gemm && (M & 4) && (M & 8) && finalize;
+    bool streamed = false;
+    SigmaNsDesc sd;
+    sd.R = v.R;
+    sd.batch = v.E;
+    sd.sample_sigma = v.sample_sigma;
+    sd.Sigma = v.Sigma;
+    sd.L = v.L;
+    sd.gen = &gen;
+    sd.status = h->status_dev;
+    sd.persistent_ok = (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0;
+    sd.cov = defer ? &cov : nullptr;
+    sd.r_has_stats = stats;
+    sd.stream = want_stream ? &sg : nullptr;
+    sd.streamed = &streamed;
+    if ((M & 4) && (rc = launch_sigma_ns(h->opt, sd, h->ws_sigma, s, dbg))) return rc;
+    nd.eps = ahead ? reinterpret_cast<const float *>(v.eps_tiled) : nullptr;  // (else the GEMM draws from v.dyn)
+    nd.eps_tiled = ahead;
+    nd.cov = v.defer_cov ? &cov : nullptr;
+    return (!streamed && (M & 8)) ? launch_noise_gemm(nd, s) : 0;
+}
+
+// ---- the update behind the rollout, single or env-batched.  The caller has filled `up` with its layout (costs, stripes, records and
+// their scratch, the blend, batch; MPPI's covariance adaptation: gamma_sigma != 0 with a_cov_old / a_cov_out); this adds the targets
+// of the staged updates and runs: the ESS floor's solver (rollout costs + per-wave minima -> 1 / lam_eff in lam_rows) or the elite
+// selector (costs -> 0/1 weights off elite_rows) when attached -- never both (refused at the C boundary) --, then the ONE update
+// launch set.  records: the rollout's workgroups left the stage-1 records (never with a staged update or the covariance adaptation).
+static int enqueue_update(covo_ctx *h, UpdateDesc &up, bool records, hipStream_t s)
+{
+    int rc;
+    float *lam_rows = covo_lam_target(h), *elite_rows = covo_elite_target(h);
+    up.n_blockmin = (up.N + 63) / 64;
+    up.lam_rows = lam_rows;
+    up.elite_rows = elite_rows;
+    if (lam_rows != nullptr && (rc = launch_ess_lambda(up.cost, up.N, up.batch, up.blockmin, h->cfg.lam, h->ess_min, lam_rows, s))) return rc;
+    if (elite_rows != nullptr && (rc = launch_elite_select(up.cost, up.N, up.batch, h->elite_K, elite_rows, s))) return rc;
+    if (up.gamma_sigma != 0.0f) return elite_rows != nullptr ? launch_elite_update_cov(h, up, s) : launch_softmax_update_cov(h, up, s);
+    if (elite_rows != nullptr) return launch_elite_reduce(h, up, s);
+    return records ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
+}
+
+// the launch sequence of one pass of a single step (everything reads per-step scalars from st->dyn)
 // begin != null (eager covo-online steps): no begin launch ran -- the Hessian's first launch does its work (HessBegin) and every
 // launch reads the caller's state where it lies (state_direct) instead of the fixed-address copy.  dbg.step bit 1 is unused here (the
 // begin launch is not part of the graph).
@@ -231,102 +306,53 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     const float *state = state_direct ? state_direct : st->state_buf;
     // covo-offline / MPPI at small N: noise -> rollout -> records -> merge as ONE launch (the begin launch has left the step's
     // scalars in st->dyn and the state in st->state_buf; MPPI: it has NOT touched a_cov, the fused launch shifts and factors)
-    float *lam_rows = covo_lam_target(h);  // the ESS floor: the update's temperature is solved from this step's costs
-    float *elite_rows = covo_elite_target(h);  // the elite-set update: the weights are selected from this step's costs
-    const bool staged = covo_update_staged(h);
-    if (M == 63 && h->opt.fuse_small && step_small_eligible(h, p, a) && !staged)
+    if (M == 63 && step_takes_small(h, p, a))
         return launch_step_small(h, p, a, state, am_shift, nullptr, st->dyn, 0.0f, st->ticket, s, pass, nullptr, iter_out);
     // periodic / sin / drag / mixed (free.py:10-58): the wave-uniform part of every rollout step's force, for the sampling
     // rollouts (shared step key) and for the Hessian's deterministic rollout (per-step keys), resolved once per control step
     const bool tables = covo_needs_tables(p);
     if (tables && (rc = launch_disturb_tables_step(p, state, st->dyn, a.rollout_deterministic, st->f_tab_rollout,
                                                    (a.mode == COVO_MODE_COVO_ONLINE && !reuse) ? st->f_tab_hess : nullptr, s))) return rc;
-    // a = clip(am_shift + L eps): what the three modes' noise launches share (epsilon drawn in-kernel from the step's key in st->dyn)
-    NoiseDesc nd;
-    nd.mu = am_shift;
-    nd.dyn = st->dyn;
-    nd.sample_offset = a.sample_offset;
-    nd.N = N;
-    nd.a = a.a;
-    nd.propagate_nan = covo_propagate_nan(h);
-    if (a.mode == COVO_MODE_COVO_ONLINE && reuse) {
-        // a reuse step of a Sigma period: no Hessian, no Sigma chain -- the previous step's factor is shifted in place (sigma_shift.hip),
-        // a_cov is its Sigma', and the samples are drawn from it as covo-offline draws from a table row (in-kernel Philox); the later
-        // passes of an iterated step sample from the same L'
-        if (pass == 0 && (rc = launch_sigma_shift(st->L, 1, a.sample_sigma, a.a_cov ? a.a_cov : st->Sigma, st->L, s))) return rc;
-        nd.L = st->L;
-        if ((rc = launch_noise_gemm(nd, s))) return rc;
-    } else if (a.mode == COVO_MODE_COVO_ONLINE) {
-        // the Hessian's last launch leaves the Sigma chain's input statistics in the chain's workspace: no prep launch
-        const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15;
-        const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma);
-        HessianDesc hd;
-        hd.state = state;
-        hd.pos_traj = a.pos_traj;
-        hd.vel_traj = a.vel_traj;
-        hd.T = a.T;
-        hd.params = &p;
-        hd.a_mean = am_shift;
-        hd.R = st->R;
-        hd.stats = stats ? &so : nullptr;
-        hd.f_tab = tables ? st->f_tab_hess : nullptr;
-        hd.status_dev = h->status_dev;
-        hd.begin = begin;
-        if ((M & 2) && (rc = launch_hessian(hd, h->ws_hess, s, dbg))) return rc;  // :134-185
-        float *Sig = a.a_cov ? a.a_cov : st->Sigma;
-        // epsilon needs only the act key: it is drawn under the chain's single-workgroup finalize launch, the GEMM loads it
-        const bool ahead = st->eps_tiled != nullptr && (M & 4) && dbg.sigma_stages >= 4;
-        EpsGenArgs gen;
-        gen.eps_tiled = ahead ? st->eps_tiled : nullptr;
-        gen.dyn = st->dyn;
-        gen.sample_offset = a.sample_offset;
-        gen.N = N;
-        gen.n_inst = 1;
-        gen.dyn_stride = 0;
-        gen.eps_stride = 0;
-        // a_cov is written by the GEMM's first workgroups, not by the chain's one-workgroup finalize launch (CovDeferred)
-        CovDeferred cov;
-        std::memset(&cov, 0, sizeof(cov));
-        const bool defer = (M & 8) && dbg.sigma_stages >= 4;
-        // the GEMM streamed under the factorisation, inside the chain's last launch (one matrix, persistent launches allowed)
-        StreamGemmArgs sg;
-        sg.mu = am_shift;
-        sg.dyn = st->dyn;
-        sg.sample_offset = a.sample_offset;
-        sg.N = N;
-        sg.a_out = a.a;
-        sg.L_stream = st->L;
-        sg.sync = st->sync;
-        sg.a_cov_out = Sig;
-        sg.nanp = covo_propagate_nan(h) ? 1 : 0;
-        const bool want_stream = h->opt.stream_gemm && (M & 4) && (M & 8) && dbg.sigma_stages >= 4;
-        bool streamed = false;
-        SigmaNsDesc sd;
-        sd.R = st->R;
-        sd.sample_sigma = a.sample_sigma;
-        sd.Sigma = Sig;
-        sd.L = st->L;
-        sd.gen = &gen;
-        sd.status = h->status_dev;
-        sd.persistent_ok = (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0;
-        sd.cov = defer ? &cov : nullptr;
-        sd.r_has_stats = stats;
-        sd.stream = want_stream ? &sg : nullptr;
-        sd.streamed = &streamed;
-        if ((M & 4) && (rc = launch_sigma_ns(h->opt, sd, h->ws_sigma, s, dbg))) return rc;
-        nd.L = st->L;
-        nd.eps = ahead ? reinterpret_cast<const float *>(st->eps_tiled) : nullptr;  // (else the GEMM draws from st->dyn)
-        nd.eps_tiled = ahead;
-        nd.cov = &cov;
-        if (!streamed && (M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
-    } else if (a.mode == COVO_MODE_COVO_OFFLINE) {
-        nd.L = a.L_table;
-        nd.state_for_time = state;
-        nd.n_table = a.n_table;
-        if ((M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
-    } else {  // MPPI: shift a_cov, factor the 4x4 blocks, per-step draws (mppi.py:43-66)
-        nd.L = st->Ls;  // (a_cov was shifted and factored there by the begin launch)
-        if ((rc = launch_noise_blockdiag(nd, s))) return rc;
+    if (a.mode == COVO_MODE_COVO_ONLINE) {
+        OnlineChainView v;
+        v.dyn = st->dyn;
+        v.sample_offset = a.sample_offset;
+        v.N = N;
+        v.mu = am_shift;
+        v.R = st->R;
+        v.sample_sigma = a.sample_sigma;
+        v.Sigma = a.a_cov ? a.a_cov : st->Sigma;
+        v.L = st->L;
+        v.eps_tiled = st->eps_tiled;
+        v.a = a.a;
+        v.hess.state = state;
+        v.hess.pos_traj = a.pos_traj;
+        v.hess.vel_traj = a.vel_traj;
+        v.hess.T = a.T;
+        v.hess.params = &p;
+        v.hess.f_tab = tables ? st->f_tab_hess : nullptr;
+        v.hess.begin = begin;
+        v.sync = st->sync;
+        v.defer_cov = true;
+        if ((rc = enqueue_online_chain(h, v, s, dbg, pass, reuse))) return rc;
+    } else {
+        // a = clip(am_shift + L eps), epsilon drawn in-kernel from the step's key in st->dyn
+        NoiseDesc nd;
+        nd.mu = am_shift;
+        nd.dyn = st->dyn;
+        nd.sample_offset = a.sample_offset;
+        nd.N = N;
+        nd.a = a.a;
+        nd.propagate_nan = covo_propagate_nan(h);
+        if (a.mode == COVO_MODE_COVO_OFFLINE) {
+            nd.L = a.L_table;
+            nd.state_for_time = state;
+            nd.n_table = a.n_table;
+            if ((M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
+        } else {  // MPPI: shift a_cov, factor the 4x4 blocks, per-step draws (mppi.py:43-66)
+            nd.L = st->Ls;  // (a_cov was shifted and factored there by the begin launch)
+            if ((rc = launch_noise_blockdiag(nd, s))) return rc;
+        }
     }
     // the rollout's workgroups leave the softmax update's stage-1 records themselves when they fit the merge (rollout.hip:
     // rollout_record); otherwise the stand-alone stage-1 kernel runs over the costs
@@ -335,7 +361,7 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     const bool cov_adapt = a.mode == COVO_MODE_MPPI && a.gamma_sigma != 0.0f;
     // the ESS floor, the elite set: the rollout's in-launch records are formed with weights fixed before the costs exist -- staged, like
     // cov_adapt
-    const bool records = G <= h->max_red_blocks && !cov_adapt && !staged;
+    const bool records = G <= h->max_red_blocks && !cov_adapt && !covo_update_staged(h);
     // the step's sampling diagnostics (covo_set_step_diag): the diagnostic variants of the same launches; a sharded step has none
     float *dg = a.partial_out == nullptr ? covo_diag_target(h) : nullptr;
     RolloutDesc ro;
@@ -360,10 +386,6 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     ro.clip = ROLLOUT_CLIP_TRUSTED;                    // a comes straight from the noise kernels above
     if ((M & 16) && (rc = launch_rollout(ro, s))) return rc;
     if (!(M & 32)) return 0;
-    // rollout (costs + per-wave minima) -> solver -> stage 1 and merge reading 1 / lam_eff from lam_rows
-    if (lam_rows != nullptr && (rc = launch_ess_lambda(a.cost, N, 1, a.groupmin, h->cfg.lam, h->ess_min, lam_rows, s))) return rc;
-    // the elite set, in the floor's place: rollout (costs) -> selector -> stage 1 with 0/1 weights off elite_rows -> the same merges
-    if (elite_rows != nullptr && (rc = launch_elite_select(a.cost, N, 1, h->elite_K, elite_rows, s))) return rc;
     // weights + update: finish locally (blend with am_shift, diagnostics), or -- a sample-sharded rank -- leave this shard's
     // record for the all-gather (covo.py:266-275)
     UpdateDesc up;
@@ -371,7 +393,6 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     up.a = a.a;
     up.N = N;
     up.blockmin = a.groupmin;
-    up.n_blockmin = (N + 63) / 64;
     up.partials = h->ws_partials;  // (the rollout's records, if it left them)
     up.G = G;
     const bool sharded = a.partial_out != nullptr;
@@ -381,18 +402,14 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     up.partial_out = a.partial_out;
     up.diag_rec = h->ws_diag_rec;
     up.diag_out = dg;
-    up.lam_rows = lam_rows;
-    up.elite_rows = elite_rows;
     up.iter_out = sharded ? nullptr : iter_out;
     if (cov_adapt) {  // mppi.py:109-125: new mean, then a_cov (already shifted by the begin launch) adapted in place; a sharded
                       // rank: its record with the second moments (836-float kind)
         up.a_cov_old = a.a_cov;
         up.gamma_sigma = a.gamma_sigma;
         up.a_cov_out = sharded ? nullptr : a.a_cov;
-        return elite_rows != nullptr ? launch_elite_update_cov(h, up, s) : launch_softmax_update_cov(h, up, s);
     }
-    if (elite_rows != nullptr) return launch_elite_reduce(h, up, s);
-    return records ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
+    return enqueue_update(h, up, records, s);
 }
 
 // a debug setter since the last step changed what a captured graph baked in (launch set, deflation switch, diagnostics target)
@@ -403,7 +420,19 @@ static void step_sync_epoch(covo_ctx *h)
     h->dbg_epoch = h->opt.epoch;
 }
 
-// reuse: a reuse step of a Sigma period (covo_set_step_sigma_period): enqueue_step's reuse branch, with a graph of its own
+// the launches of step_begin_kernel: a step's first pass (eager, ahead of the graph; a_mean_in: the caller's input mean of this call, else
+// the handle's own carried one), pass >= 1 of an iterated step (inside the graph: the mean the previous pass committed, the raw key
+// walked on the device -- blk is not read), the phase timer's scratch fill.  mppi_cov: MPPI's a_cov, shifted and factored here
+static void launch_step_begin(StepState *st, const covo_step_args &a, const DynBlock &blk, float shared_noise_scale, float *mppi_cov,
+                              int pass, hipStream_t s)
+{
+    hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, s,
+                       (pass == 0 && a.a_mean_in) ? a.a_mean_in : (const float *)a.a_mean,
+                       a.a_mean_shift ? a.a_mean_shift : st->a_mean_shift, st->dyn, st->state_buf, pass ? 1 : a.derive_keys,
+                       shared_noise_scale, blk, mppi_cov, st->Ls, st->sync, pass);
+}
+
+// reuse: a reuse step of a Sigma period (covo_set_step_sigma_period): the chain's reuse form, with a graph of its own
 static int step_enqueue_all(covo_ctx *h, StepState *st, const covo_env_params *params, const covo_step_args *args, uint32_t key0,
                             uint32_t key1, const float *f_shared, hipStream_t s, const bool reuse)
 {
@@ -418,36 +447,27 @@ static int step_enqueue_all(covo_ctx *h, StepState *st, const covo_env_params *p
     }
     std::memcpy(&blk.w[8], &args->state, sizeof(const float *));
     const float shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
-    // control_params.a_mean of this call: the handle's own buffer (a carried mean) or the caller's input (args->a_mean_in)
-    const bool small = h->opt.fuse_small && step_small_eligible(h, *params, *args) && !covo_update_staged(h);
-    // covo_set_step_iters: K passes on this state.  Pass j >= 1 starts from the mean pass j - 1 committed (args->a_mean, never the
-    // caller's a_mean_in) and walks the raw key on the device; with the update arbiter attached its launch sits between the passes
-    // (and the passes are enqueued eagerly: the arbiter's launch is not part of any captured graph)
+    const bool small = step_takes_small(h, *params, *args);
+    // covo_set_step_iters: pass j >= 1 starts from the mean pass j - 1 committed (args->a_mean, never the caller's a_mean_in) and
+    // walks the raw key on the device; the update arbiter's launch between two passes (step_run_passes)
     const int K = covo_step_iters(h);
-    covo_step_args later = *args;
-    later.a_mean_in = nullptr;
-    auto between = [&](int j) -> int {
-        return (j + 1 < K && covo_arb_on(h)) ? covo_plan_after_step(h, params, args, key0, key1, f_shared, nullptr, -1, s, true) : 0;
-    };
-    if (small && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0) {
-        // an eager handle: the WHOLE step is one launch, the begin launch's work included (per workgroup, step_small.hip)
-        st->cache[0].have_key = false;  // (st->dyn / st->state_buf are not refreshed: a later graph capture starts from an eager call)
-        for (int j = 0; j < K; ++j) {
-            // (an iterated step: the last workgroup of every pass parks the pass's raw key at st->dyn[10..11] for the next one)
-            int rc = launch_step_small(h, *params, j ? later : *args, args->state, args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift,
-                                       &blk, nullptr, shared_noise_scale, st->ticket, s, j, K > 1 ? st->dyn + 10 : nullptr,
-                                       covo_iter_slot(h, j));
-            if (rc || (rc = between(j))) return rc;
-        }
-        return 0;
+    auto between = [&](hipStream_t on, int) { return covo_plan_after_step(h, params, args, key0, key1, f_shared, nullptr, -1, on, true); };
+    const char *name = "covo_mpc_step";
+    switch (step_form(h, small, *params, *args, reuse)) {
+    case STEP_ONE_LAUNCH: {
+        // the WHOLE step is one launch, the begin launch's work included (per workgroup, step_small.hip).  An iterated step: the
+        // last workgroup of every pass parks the pass's raw key at st->dyn[10..11] for the next one
+        covo_step_args later = *args;
+        later.a_mean_in = nullptr;
+        float *am_shift = args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift;
+        return step_run_passes(h, st->cache, false, false, s, name, [&](hipStream_t on, int j) {
+            return launch_step_small(h, *params, j ? later : *args, args->state, am_shift, &blk, nullptr, shared_noise_scale, st->ticket,
+                                     on, j, K > 1 ? st->dyn + 10 : nullptr, covo_iter_slot(h, j));
+        }, between);
     }
-    // eager covo-online steps (no per-step force tables, whose launch precedes the Hessian and reads the scalars): the begin work
-    // rides in the Hessian's first launch -- one launch boundary less (COVO_FOLD_BEGIN=0 keeps the begin launch)
-    // (a reuse step has no Hessian launch to fold into: it keeps the begin launch)
-    if (h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
-        !covo_needs_tables(*params) && !reuse) {
-        st->cache[0].have_key = false;
-        for (int j = 0; j < K; ++j) {
+    case STEP_FOLDED_ONLINE:
+        // the begin work rides in the Hessian's first launch -- one launch boundary less
+        return step_run_passes(h, st->cache, false, false, s, name, [&](hipStream_t on, int j) {
             HessBegin hb;
             hb.pass = j;
             hb.a_mean_raw = j ? args->a_mean : (args->a_mean_in ? args->a_mean_in : args->a_mean);
@@ -456,32 +476,13 @@ static int step_enqueue_all(covo_ctx *h, StepState *st, const covo_env_params *p
             hb.blk = &blk;
             hb.derive_keys = args->derive_keys;
             hb.shared_noise_scale = shared_noise_scale;
-            int rc = enqueue_step(h, st, *params, *args, s, DebugMasks(), &hb, args->state, j);
-            if (rc || (rc = between(j))) return rc;
-        }
-        return 0;
+            return enqueue_step(h, st, *params, *args, on, DebugMasks(), &hb, args->state, j);
+        }, between);
+    case STEP_BEGIN_PASSES:
+        break;
     }
     float *mppi_cov = (args->mode == COVO_MODE_MPPI && !small) ? args->a_cov : (float *)nullptr;
-    float *am_shift = args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift;
-    hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, s,
-                       args->a_mean_in ? args->a_mean_in : args->a_mean, am_shift, st->dyn, st->state_buf, args->derive_keys,
-                       shared_noise_scale, blk, mppi_cov, st->Ls, st->sync, 0);
-    // the passes behind the begin launch: pass j >= 1 starts with a begin launch of its own, inside the graph
-    auto passes = [&](hipStream_t on, bool with_arbiter) -> int {
-        for (int j = 0; j < K; ++j) {
-            if (j > 0)
-                hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, on, (const float *)args->a_mean,
-                                   am_shift, st->dyn, st->state_buf, 1, shared_noise_scale, DynBlock(), mppi_cov, st->Ls, st->sync, j);
-            int rc = enqueue_step(h, st, *params, *args, on, DebugMasks(), nullptr, nullptr, j, reuse);
-            if (rc || (with_arbiter && (rc = between(j)))) return rc;
-        }
-        return 0;
-    };
-    if (K > 1 && covo_arb_on(h)) {
-        st->forget_graphs();
-        return passes(s, true);
-    }
-
+    launch_step_begin(st, *args, blk, shared_noise_scale, mppi_cov, 0, s);
     StepKey k;
     std::memset(&k, 0, sizeof(k));
     k.args = *args;
@@ -493,12 +494,13 @@ static int step_enqueue_all(covo_ctx *h, StepState *st, const covo_env_params *p
     k.stream = s;
     GraphCache &cache = st->cache[reuse ? 1 : 0];
     StepKey &key = st->key[reuse ? 1 : 0];
-    const bool same = cache.have_key && std::memcmp(&k, &key, sizeof(k)) == 0;
-    if (!same) {
-        key = k;
-        cache.have_key = true;
-    }
-    return graph_cache_run(h, cache, s, same, "covo_mpc_step", [&](hipStream_t on) { return passes(on, false); });
+    const bool same = graph_cache_seen(cache, std::memcmp(&k, &key, sizeof(k)) == 0);
+    if (!same) key = k;
+    // the passes behind the begin launch: pass j >= 1 starts with a begin launch of its own, inside the graph
+    return step_run_passes(h, st->cache, reuse, same, s, name, [&](hipStream_t on, int j) {
+        if (j > 0) launch_step_begin(st, *args, DynBlock(), shared_noise_scale, mppi_cov, j, on);
+        return enqueue_step(h, st, *params, *args, on, DebugMasks(), nullptr, nullptr, j, reuse);
+    }, between);
 }
 
 int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
@@ -517,44 +519,6 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     if (rc == 0 && online) covo_sigma_step_done(h, age, st->L, args->sample_sigma, 1);
     return rc;
 }
-
-// ---- the flight recorder behind a step (plan_trace.hip): one eager launch that rolls the new mean out with the inputs the step's
-// sample rollouts had.  The shared vector is re-derived from the raw key by the launch itself (every step path forms it from the
-// same device function); the per-step tables are the ones the step has just built in its own scratch.
-int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only)
-{
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
-    StepState *st = reinterpret_cast<StepState *>(h->step);
-    // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
-    // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
-    const bool iterated = covo_step_iters(h) > 1 && st != nullptr;
-    PlanInstDesc d;
-    std::memset(&d, 0, sizeof(d));
-    d.state = args->state;
-    d.pos_traj = args->pos_traj;
-    d.vel_traj = args->vel_traj;
-    d.T = args->T;
-    d.params = params;
-    d.a_mean = args->a_mean;
-    d.a = args->a;
-    d.N = args->n_samples;
-    d.cost = args->cost;
-    d.a_nominal = args->a_mean_shift ? args->a_mean_shift : (st ? st->a_mean_shift : nullptr);
-    d.a_mean_out = args->a_mean;
-    d.f_tab = (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr;
-    d.key[0] = key0;
-    d.key[1] = key1;
-    d.key_mem = iterated ? st->dyn + 10 : nullptr;
-    for (int i = 0; i < 3; ++i) d.f_shared[i] = f_shared ? f_shared[i] : 0.0f;
-    d.derive_keys = args->derive_keys;
-    d.shared_noise_scale = covo_shared_noise_scale(*params, args->rollout_deterministic);
-    int rc = launch_update_arbiter(h, &d, 1, iterated, trace_index, s);  // first: the plan, the trace's u and the env step see its mean
-    if (rc || arbiter_only) return rc;
-    if ((rc = launch_plan_trace(h, &d, 1, iterated, state_true, trace_index, s))) return rc;
-    return launch_sample_fan(h, &d, 1, iterated, trace_index, s);  // (the episode's row index: the fan log counts like the trace)
-}
-
 
 // ---- profiling aids: `reps` copies of the selected part of one step captured into ONE graph and replayed; the average time per
 // copy (GPU time between two events around the replay, the best of the last three of four replays).  Inside a graph the launches
@@ -608,19 +572,14 @@ int covo_debug_time_step_impl(covo_ctx *h, const covo_env_params *params, const 
         if (rc) return rc;
     }
     StepState *st = reinterpret_cast<StepState *>(h->step);
-    const bool folded_online = h->opt.fold_begin && args->mode == COVO_MODE_COVO_ONLINE && !covo_needs_tables(*params);
-    if (((h->opt.fuse_small && step_small_eligible(h, *params, *args) && !covo_update_staged(h)) || folded_online) && (h->cfg.flags & COVO_FLAG_NO_GRAPH) != 0 &&
-        args->state != nullptr) {
+    if (step_form(h, step_takes_small(h, *params, *args), *params, *args, false) != STEP_BEGIN_PASSES && args->state != nullptr) {
         // the last step ran without a begin launch (the one-launch small step; covo-online with the begin work folded into the
         // Hessian) and never filled the scratch the replayed launches read (state copy, shifted mean, keys; MPPI: shifted
         // covariance + block factors): one begin launch does, with the key the step would derive from (0, 0)
         DynBlock blk;
         std::memset(&blk, 0, sizeof(blk));
         std::memcpy(&blk.w[8], &args->state, sizeof(const float *));
-        hipLaunchKernelGGL(step_begin_kernel, dim3(1), dim3(COVO_NA + COVO_STATE_FLOATS + 4), 0, run,
-                           args->a_mean_in ? args->a_mean_in : args->a_mean,
-                           args->a_mean_shift ? args->a_mean_shift : st->a_mean_shift, st->dyn, st->state_buf, args->derive_keys, 0.0f,
-                           blk, args->mode == COVO_MODE_MPPI ? args->a_cov : (float *)nullptr, st->Ls, st->sync, 0);
+        launch_step_begin(st, *args, blk, 0.0f, args->mode == COVO_MODE_MPPI ? args->a_cov : (float *)nullptr, 0, run);
         COVO_CHECK_HIP(hipStreamSynchronize(run));
     }
     DebugMasks dbg;
@@ -725,10 +684,11 @@ struct BatchState {
     std::vector<covo_env_params> env_inst_params;
     std::vector<char> ro_args_host;
     std::vector<covo_env_params> params;
-    covo_batch_args key;  // with `stream` and `params`: what the cached scratch and graph were built for
+    covo_batch_args key;  // with `stream`, `params` and `n_envs`: what the scratch was built for, while have_key
     hipStream_t stream = nullptr;
-    GraphCache cache{};
-    GraphCache cache_reuse{};  // the reuse step of a Sigma period (covo_set_step_sigma_period): another launch set, its own graph
+    bool have_key = false;
+    GraphCache cache[2] = {};  // [0] the step, [1] the reuse step of a Sigma period, as in StepState; both are keyed by `key`
+    void forget_graphs() { cache[0].forget(), cache[1].forget(); }
     float4 *eps_tiled = nullptr;  // [E][ceil(N/32)][16][64]: the step's epsilon of every instance, drawn under the Sigma chain's
     size_t eps_cap = 0;           // finalize launch (eps_tiles.hpp), as in the single step
 };
@@ -737,8 +697,8 @@ struct BatchState {
 // batch_env_inst and the env step launch that reads env_inst; eps_tiled only ever grows)
 static void batch_state_free(BatchState *b)
 {
-    b->cache.drop();
-    b->cache_reuse.forget();
+    b->forget_graphs();
+    b->have_key = false;
     free_and_null(b->dyn, b->a_mean_shift, b->R, b->Sigma, b->L, b->consts, b->ro_args, b->partials, b->diag_rec, b->models,
                   b->tab_rollout, b->tab_hess);
 }
@@ -750,9 +710,10 @@ void step_graphs_drop(covo_ctx *h)
     StepState *st = reinterpret_cast<StepState *>(h->step);
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     if (st) st->forget_graphs();
-    if (b) b->cache.forget();
-    if (b) b->cache_reuse.forget();
-    if (b) b->small.cache.forget();
+    if (!b) return;
+    b->forget_graphs();
+    b->have_key = false;  // (the cold block of covo_step_batched_impl rebuilds the rollout's argument blocks: they bake the launch set in too)
+    b->small.cache.forget();
 }
 
 int covo_grow_workspace(covo_ctx *h, void **ws, size_t *bytes, size_t need, hipStream_t s)
@@ -843,101 +804,51 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     // covo.py:231: CoVO's sampling rollouts run step_env(deterministic=True); get_hessian likewise (covo.py:152)
     if ((M & 1) && b->tables && (rc = launch_disturb_tables_batched(b->models, a.states, b->dyn, E, 1, b->tab_rollout, b->tab_hess, s)))
         return rc;
-    NoiseDesc nd;
-    nd.L = b->L;
-    nd.mu = b->a_mean_shift;
-    nd.dyn = b->dyn;
-    nd.N = N;
-    nd.a = a.a;
-    nd.batch = E;
-    nd.propagate_nan = covo_propagate_nan(h);
-    if (reuse) {
-        // a reuse step of a Sigma period: every instance's factor is shifted in place (sigma_shift.hip; pass 0 only), a_cov is its
-        // Sigma', the GEMM draws its epsilon itself
-        if (pass == 0 && (rc = launch_sigma_shift(b->L, E, a.sample_sigma, a.a_cov ? a.a_cov : b->Sigma, b->L, s))) return rc;
-        if ((rc = launch_noise_gemm(nd, s))) return rc;
-    } else {
-    // as in the single step: the Hessian's last launch leaves every instance's Sigma-chain input statistics, no prep launch
-    const bool stats = (M & 2) && (M & 4) && (dbg.hess & 15) == 15;
-    const SymStatsOut so = sigma_ns_stats_out(h->ws_sigma, E);
-    HessianDesc hd;
-    hd.state = a.states;
-    hd.pos_traj = a.pos_traj;
-    hd.vel_traj = a.vel_traj;
-    hd.T = a.T;
-    hd.params = &b->params[0];
-    hd.a_mean = b->a_mean_shift;
-    hd.batch = E;
-    hd.R = b->R;
-    hd.consts_dev = b->consts;
-    hd.traj_stride = (size_t)a.T * 3;
-    hd.stats = stats ? &so : nullptr;
-    hd.f_tab = b->tables ? b->tab_hess : nullptr;
-    hd.models_dev = b->models;
-    hd.status_dev = h->status_dev;
-    if ((M & 2) && (rc = launch_hessian(hd, h->ws_hess, s, dbg))) return rc;
-    float *Sig = a.a_cov ? a.a_cov : b->Sigma;
-    // epsilon needs only the act keys: every instance's is drawn under the chain's finalize launch (32 of 256 CUs factor), the GEMM
-    // loads it -- the in-kernel Philox costs the batched GEMM ~9 us, its matrix pipe hides no vector work
-    const bool ahead = b->eps_tiled != nullptr && (M & 4) && (M & 8) && dbg.sigma_stages >= 4;
-    EpsGenArgs gen;
-    gen.eps_tiled = ahead ? b->eps_tiled : nullptr;
-    gen.dyn = b->dyn;
-    gen.sample_offset = 0;
-    gen.N = N;
-    gen.n_inst = E;
-    gen.dyn_stride = 12;
-    gen.eps_stride = (size_t)((N + 31) / 32) * 16 * 64;
-    SigmaNsDesc sd;
-    sd.R = b->R;
-    sd.batch = E;
-    sd.sample_sigma = a.sample_sigma;
-    sd.Sigma = Sig;
-    sd.L = b->L;
-    sd.gen = &gen;
-    sd.status = h->status_dev;
-    sd.persistent_ok = (h->cfg.flags & COVO_FLAG_SHARED_DEVICE) == 0;
-    sd.r_has_stats = stats;
-    if ((M & 4) && (rc = launch_sigma_ns(h->opt, sd, h->ws_sigma, s, dbg))) return rc;
-    nd.eps = ahead ? reinterpret_cast<const float *>(b->eps_tiled) : nullptr;  // (else the GEMM draws from b->dyn)
-    nd.eps_tiled = ahead;
-    if ((M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
-    }
+    OnlineChainView v;
+    v.E = E;
+    v.dyn = b->dyn;
+    v.dyn_stride = 12;
+    v.N = N;
+    v.mu = b->a_mean_shift;
+    v.R = b->R;
+    v.sample_sigma = a.sample_sigma;
+    v.Sigma = a.a_cov ? a.a_cov : b->Sigma;
+    v.L = b->L;
+    v.eps_tiled = b->eps_tiled;
+    v.eps_stride = (size_t)((N + 31) / 32) * 16 * 64;
+    v.a = a.a;
+    v.hess.state = a.states;
+    v.hess.pos_traj = a.pos_traj;
+    v.hess.vel_traj = a.vel_traj;
+    v.hess.T = a.T;
+    v.hess.params = &b->params[0];
+    v.hess.consts_dev = b->consts;
+    v.hess.traj_stride = (size_t)a.T * 3;
+    v.hess.f_tab = b->tables ? b->tab_hess : nullptr;
+    v.hess.models_dev = b->models;
+    v.ahead_groups = 4 | 8;
+    if ((rc = enqueue_online_chain(h, v, s, dbg, pass, reuse))) return rc;
     if ((M & 16) && (rc = launch_rollout_batched(b->ro_args_host.data(), b->ro_args, E, s))) return rc;
     if (!(M & 32)) return 0;
+    // row e of the diagnostic buffer, of the solver's / the selector's output and of iter_log is instance e's
     const int G = rollout_workgroups(N, false, E);
     UpdateDesc up;
     up.cost = a.cost;
     up.a = a.a;
     up.N = N;
     up.blockmin = a.groupmin;
-    up.n_blockmin = (N + 63) / 64;
     up.partials_ws = b->partials;
-    up.partials = b->partials;
+    up.partials = b->partials;  // the rollout's workgroups have left the records when they fit the merge: instance e's are [e][G]
     up.G = G;
     up.a_mean_old = b->a_mean_shift;
     up.gamma_mean = a.gamma_mean;
     up.a_mean_out = a.a_mean;
     up.batch = E;
     up.diag_rec = b->diag_rec;
-    up.diag_out = covo_diag_target(h);  // row e of the caller's diagnostic buffer is instance e's
-    // the ESS floor: the rollouts left costs and per-wave minima, no records (covo_step_batched_impl); row e of the solver's output
-    // is instance e's temperature
-    up.lam_rows = covo_lam_target(h);
+    up.diag_out = covo_diag_target(h);
     up.iter_out = covo_iter_slot(h, pass);  // an iterated step: instance e's cost minimum of this pass to iter_log[e][pass]
     up.iter_stride = covo_step_iters(h);
-    if (up.lam_rows != nullptr) {
-        if ((rc = launch_ess_lambda(a.cost, N, E, a.groupmin, h->cfg.lam, h->ess_min, covo_lam_target(h), s))) return rc;
-        return launch_softmax_reduce(h, up, s);
-    }
-    // the elite set, likewise: row e of the selector's output is instance e's threshold
-    if (float *elite_rows = covo_elite_target(h)) {
-        up.elite_rows = elite_rows;
-        if ((rc = launch_elite_select(a.cost, N, E, h->elite_K, elite_rows, s))) return rc;
-        return launch_elite_reduce(h, up, s);
-    }
-    // the rollout's workgroups have left the records when they fit the merge (rollout_record): instance e's are [e][G]
-    return G <= h->max_red_blocks ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
+    return enqueue_update(h, up, G <= h->max_red_blocks && !covo_update_staged(h), s);  // (as the cold block told the rollout: brec)
 }
 
 // profiling aid (bench.py --config envs): `reps` copies of the selected launch groups of the LAST covo_mpc_step_batched call in
@@ -946,7 +857,7 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
 int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us_out, hipStream_t run)
 {
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (!b || !b->cache.have_key) {
+    if (!b || !b->have_key) {
         covo_set_error("covo_debug_time_batched: call covo_mpc_step_batched first");
         return COVO_E_BADARG;
     }
@@ -962,13 +873,13 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
     const int E = args->n_envs;
     step_sync_epoch(h);
     BatchState *b = batch_state(h);
-    const bool same = b->cache.have_key && b->n_envs == E && std::memcmp(&b->key, args, sizeof(*args)) == 0 && b->stream == s &&
+    const bool same = b->have_key && b->n_envs == E && std::memcmp(&b->key, args, sizeof(*args)) == 0 && b->stream == s &&
                       std::memcmp(b->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
     if (!same) {
         // new buffers / parameters / instance count: (re)allocate scratch and drop the stale graph (outside the steady state)
         COVO_CHECK_HIP(hipStreamSynchronize(s));
-        b->cache.drop();
-        b->cache_reuse.forget();
+        b->forget_graphs();
+        b->have_key = false;
         if (b->n_envs != E) {
             batch_state_free(b);
             h->sigma_L = nullptr;  // (the factor buffer goes: the next step of a Sigma period refreshes)
@@ -1035,36 +946,17 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         if ((rc = covo_grow_workspace(h, &h->ws_hess, &h->ws_hess_bytes, hessian_workspace_bytes(E), s))) return rc;
         b->key = *args;
         b->stream = s;
-        b->cache.have_key = true;
+        b->have_key = true;
     }
     batch_upload_keys(b->dyn, keys, E, s);
-    // covo_set_step_iters: K passes in one graph; with the update arbiter attached its (eager) launch sits between them and the
-    // passes are enqueued eagerly
-    const int K = covo_step_iters(h);
     // covo_set_step_sigma_period: the batch shares one age -- 0: today's step, which leaves the factors in b->L; else a reuse step
     const int age = covo_sigma_step_age(h, b->L, args->sample_sigma, E);
     const bool reuse = age != 0;
-    auto passes = [&](hipStream_t on, bool with_arbiter) -> int {
-        for (int j = 0; j < K; ++j) {
-            int rc = batch_enqueue(h, b, *args, on, DebugMasks(), j, reuse);
-            if (rc == 0 && with_arbiter && j + 1 < K)
-                rc = covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, on, true);
-            if (rc) return rc;
-        }
-        return 0;
-    };
-    int rc;
-    if (K > 1 && covo_arb_on(h)) {
-        b->cache.drop();
-        b->cache_reuse.forget();
-        rc = passes(s, true);
-    } else if (reuse) {  // the reuse graph's key is the step's: its first call with these buffers runs eagerly, the second captures
-        const bool same_reuse = same && b->cache_reuse.have_key;
-        b->cache_reuse.have_key = true;
-        rc = graph_cache_run(h, b->cache_reuse, s, same_reuse, "covo_mpc_step_batched", [&](hipStream_t on) { return passes(on, false); });
-    } else {
-        rc = graph_cache_run(h, b->cache, s, same, "covo_mpc_step_batched", [&](hipStream_t on) { return passes(on, false); });
-    }
+    // both graphs are keyed by the step's key; each one's first call with these buffers runs eagerly, the second captures
+    const int rc = step_run_passes(
+        h, b->cache, reuse, graph_cache_seen(b->cache[reuse ? 1 : 0], same), s, "covo_mpc_step_batched",
+        [&](hipStream_t on, int j) { return batch_enqueue(h, b, *args, on, DebugMasks(), j, reuse); },
+        [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, on, true); });
     if (rc == 0) covo_sigma_step_done(h, age, b->L, args->sample_sigma, E);
     return rc;
 }
@@ -1170,6 +1062,62 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
     });
 }
 
+// ---- the launches behind a step (after_step.hpp: the update arbiter, the flight recorder's plan and trace, the sample fan), eager.
+// What they need to know about ONE instance of the step that has just been enqueued: the inputs its sample rollouts had.  The shared
+// vector is re-derived from the raw key by the launches themselves (every step path forms it from the same device function); the
+// per-step tables are the ones the step has just built in its own scratch.  key_mem: the instance's raw rng_act in device memory;
+// null (a single step that is not iterated): the caller sets key / f_shared as covo_mpc_step got them
+static PlanInstDesc plan_inst(const BatchInst &i, int T, int N, const covo_env_params *params, int derive_keys, bool deterministic,
+                              const float *nominal, const float *f_tab, const uint32_t *key_mem)
+{
+    PlanInstDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.state = i.state;
+    d.pos_traj = i.pos_traj;
+    d.vel_traj = i.vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a_mean = i.a_mean;
+    d.a = i.a;
+    d.N = N;
+    d.cost = i.cost;
+    d.a_nominal = nominal;
+    d.a_mean_out = i.a_mean;
+    d.f_tab = f_tab;
+    d.key_mem = key_mem;
+    d.derive_keys = derive_keys;
+    d.shared_noise_scale = covo_shared_noise_scale(*params, deterministic);
+    return d;
+}
+// the arbiter first: the plan, the trace's u and the env step see its mean; trace_index: the episode's row index (the fan log counts
+// like the trace)
+static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const float *states_true, int trace_index, hipStream_t s,
+                      bool arbiter_only)
+{
+    int rc = launch_update_arbiter(h, d, n, batched, trace_index, s);
+    if (rc || arbiter_only) return rc;
+    if ((rc = launch_plan_trace(h, d, n, batched, states_true, trace_index, s))) return rc;
+    return launch_sample_fan(h, d, n, batched, trace_index, s);
+}
+
+int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
+                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only)
+{
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
+    StepState *st = reinterpret_cast<StepState *>(h->step);
+    // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
+    // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
+    const bool iterated = covo_step_iters(h) > 1 && st != nullptr;
+    const BatchInst i = {args->state, args->pos_traj, args->vel_traj, args->a_mean, args->a, args->cost, args->groupmin};
+    PlanInstDesc d = plan_inst(i, args->T, args->n_samples, params, args->derive_keys, args->rollout_deterministic,
+                               args->a_mean_shift ? args->a_mean_shift : (st ? st->a_mean_shift : nullptr),
+                               (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr, iterated ? st->dyn + 10 : nullptr);
+    d.key[0] = key0;
+    d.key[1] = key1;
+    for (int c = 0; c < 3; ++c) d.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
+    return plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only);
+}
+
 // mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run) or MPPI / COVO_OFFLINE (covo_step_batched_small_impl)
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
                             const float *states_true, int trace_index, hipStream_t s, bool arbiter_only)
@@ -1179,35 +1127,19 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
     PlanInstDesc d[COVO_MAX_ENVS];
-    std::memset(d, 0, sizeof(d));
     const float *nominal = nullptr;  // the update arbiter's: covo-online's begin launch leaves it, the fused launch's was formed ahead of it
     if (covo_arb_on(h)) {
         if (online) nominal = b->a_mean_shift;
         else if (int rc = launch_arbiter_nominal(h, nullptr, E, s, &nominal)) return rc;
     }
-    for (int e = 0; e < E; ++e) {
-        const BatchInst i = batch_inst(*args, e);
-        d[e].state = i.state;
-        d[e].pos_traj = i.pos_traj;
-        d[e].vel_traj = i.vel_traj;
-        d[e].T = args->T;
-        d[e].params = &params[e];
-        d[e].a_mean = i.a_mean;
-        d[e].a = i.a;
-        d[e].N = args->n_samples;
-        d[e].cost = i.cost;
-        d[e].a_nominal = nominal ? nominal + (size_t)e * COVO_NA : nullptr;
-        d[e].a_mean_out = i.a_mean;
-        d[e].f_tab = (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
-        // the instance's raw rng_act: covo-online's begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone
-        d[e].key_mem = online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e;
-        d[e].derive_keys = 1;
-        d[e].shared_noise_scale = covo_shared_noise_scale(params[e], mode != COVO_MODE_MPPI);  // (CoVO's rollouts are deterministic)
-    }
-    int rc = launch_update_arbiter(h, d, E, true, trace_index, s);  // first: the plan, the trace's u and the env step see its mean
-    if (rc || arbiter_only) return rc;
-    if ((rc = launch_plan_trace(h, d, E, true, states_true, trace_index, s))) return rc;
-    return launch_sample_fan(h, d, E, true, trace_index, s);
+    // the instance's raw rng_act: covo-online's begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone;
+    // CoVO's rollouts are deterministic
+    for (int e = 0; e < E; ++e)
+        d[e] = plan_inst(batch_inst(*args, e), args->T, args->n_samples, &params[e], 1, mode != COVO_MODE_MPPI,
+                         nominal ? nominal + (size_t)e * COVO_NA : nullptr,
+                         (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr,
+                         online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e);
+    return plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only);
 }
 
 // test hook: the factor(s) the LAST single (batched = 0) / env-batched step sampled from -- what the next reuse step of a Sigma period

@@ -370,3 +370,84 @@ def test_batched_mode_refusals_name_the_condition_and_leave_the_handle_usable():
         assert c.core.device_status() == 0
     u2 = b(noisy, keys)
     assert torch.isfinite(u2).all()
+
+
+# (step_mask, hess_mask, sigma_stages) of every CovoCore.time_phases call in bench.py and scripts/phase_times.py, the whole step last
+SINGLE_MASKS = [(4,), (4 | 8,), (4 | 8 | 16,), (2 | 4,), (8 | 16 | 32,), (8,), (8 | 16,),                     # bench.py
+                (63,), (2,), (2, 1), (2, 2), (2, 8), (4, 15, 1), (4, 15, 2), (4, 15, 3), (16,), (32,), (0,),  # scripts/phase_times.py
+                (24,), (56,), (48,), (63,)]
+BATCHED_MASKS = [2 | 4 | 8 | 16 | 32, 2, 4, 8, 16, 32, 63]  # bench.py --config envs; 63
+
+
+@pytest.mark.parametrize("graph", ["graph", "eager"])
+def test_masked_launch_groups_of_the_phase_timers(graph, monkeypatch):
+    """covo-online, N = 256 single and E = 2 x N = 256 env-batched, on a graph-replaying and on an eager handle: after one full step,
+    covo_debug_time_step / covo_debug_time_batched with every mask bench.py and scripts/phase_times.py use (bench.py's two with the
+    GEMM as a launch of its own included) and with 63 return a finite positive time and leave device_status() 0; a following
+    ordinary step then gives the same a_mean, bit for bit, as on a fresh controller with the same keys that never ran the timers.
+    No timing is asserted: the masked forms of the step's launch sequence must be something the runtime accepts, and must leave the
+    handle (scratch, graph caches, keys) as a step expects it.
+    The update group (mask 32) writes the caller's a_mean by definition, mask 63 of the batched timer also runs the begin launch,
+    which shifts the in/out mean once more per copy, and on an eager handle covo_debug_time_step refills the step's scratch with
+    the key derived from (0, 0): the mean the timers leave in the CALLER's buffer is not the step's.  Both controllers therefore
+    start the following step from the mean the first step returned (saved before the timers); everything the handle owns is left
+    as the timers left it."""
+    import covo_mpc_amd as cm
+    monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
+    N, lam, E = 256, "0.01", 2
+    env = _env()
+
+    def timed_ok(us, what):
+        assert np.isfinite(us) and us > 0.0, (graph, what, us)
+
+    # ---- single: two identical controllers on instance 0, the first one runs the timers between its two steps
+    runs = [_instances(env, "covo-online", N, lam, 1)[0] for _ in range(2)]
+    assert runs[0]["c"].core.uses_graph == (graph == "graph")
+    for step in range(2):
+        for r, i in enumerate(runs):
+            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
+            u, i["cp"], _ = i["c"](i["obs"], i["state"], i["params"], k_act, i["cp"], i["info"])
+            if step == 0 and r == 0:
+                saved = i["cp"].a_mean.clone()
+                core = i["c"].core
+                for m in SINGLE_MASKS:
+                    timed_ok(core.time_phases(*m, reps=4), ("single", m))
+                _lib.check(core.lib.covo_debug_set_stream_gemm(core.h, 0), "stream_gemm")
+                for m in ((4,), (4 | 8,)):
+                    timed_ok(core.time_phases(*m, reps=4), ("single, stream_gemm=0", m))
+                _lib.check(core.lib.covo_debug_set_stream_gemm(core.h, 1), "stream_gemm")
+                timed_ok(core.time_phases(63, reps=4), ("single", 63))
+                assert core.device_status() == 0
+                i["cp"] = i["cp"].replace(a_mean=saved)
+            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u.cpu().numpy(), i["params"])
+        print(f"{graph} single step {step}: max |a_mean difference| {(runs[0]['cp'].a_mean - runs[1]['cp'].a_mean).abs().max():.3g}")
+        assert torch.equal(runs[0]["cp"].a_mean, runs[1]["cp"].a_mean), (graph, "single", step)
+    assert all(i["c"].core.device_status() == 0 for i in runs)
+
+    # ---- env-batched: two identical controllers on E instances
+    inst = _instances(env, "covo-online", N, lam, E)
+    cp0 = inst[0]["cp"]
+    bs = [cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
+                                               sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV) for _ in range(2)]
+    for b in bs:
+        b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
+    assert bs[0].core.uses_graph == (graph == "graph")
+    for step in range(2):
+        k_acts = []
+        for i in inst:
+            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
+            k_acts.append(np.asarray(k_act))
+        noisy = [i["info"]["noisy_state"] for i in inst]
+        for r, b in enumerate(bs):
+            u = b(noisy, np.stack(k_acts)).clone()
+            if step == 0 and r == 0:
+                saved = b.a_mean.clone()
+                for m in BATCHED_MASKS:
+                    timed_ok(b.time_phases(m, reps=4), ("batched", m))
+                assert b.core.device_status() == 0
+                b.a_mean.copy_(saved)
+        print(f"{graph} batched step {step}: max |a_mean difference| {(bs[0].a_mean - bs[1].a_mean).abs().max():.3g}")
+        assert torch.equal(bs[0].a_mean, bs[1].a_mean), (graph, "batched", step)
+        for e, i in enumerate(inst):
+            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u[e].cpu().numpy(), i["params"])
+    assert all(b.core.device_status() == 0 for b in bs) and torch.isfinite(bs[0].a_mean).all()

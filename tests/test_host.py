@@ -204,3 +204,16 @@ def test_bench_spread_indices_cover_the_episode():
     idx = b.spread_indices(200, 300)
     assert len(idx) == 200 and idx[0] == 0 and idx[-1] == 299 and all(b2 - a2 in (1, 2) for a2, b2 in zip(idx, idx[1:]))
     assert b.spread_indices(650, 300)[:301] == list(range(300)) + [0] and b.spread_indices(0, 300) == []
+
+
+def test_step_graph_state_machines_under_a_sanitizer(tmp_path):
+    """csrc/step_graph.hpp (graph cache + key bookkeeping, pass driver, form selector) against stubbed HIP entry points, built with
+    -fsanitize=address,undefined as a stand-alone program (tests/host/step_graph_check.cpp): for K in {1, 3}, arbiter on / off,
+    reuse on / off, COVO_FLAG_NO_GRAPH set / clear -- eager -> capture -> replay per graph, the two graphs independent, a changed key
+    or a drop starts again; and every combination the form selector distinguishes."""
+    exe = str(tmp_path / "step_graph_check")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-O1", "-g", "-std=c++17", os.path.join(ROOT, "tests", "host", "step_graph_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "step_graph_check: ok" in out.stdout, out.stdout + out.stderr
