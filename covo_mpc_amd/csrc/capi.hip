@@ -467,42 +467,40 @@ int covo_merge_ranks_cov(covo_handle_t h, const float *records, int32_t G, const
     return rc;
 }
 
+// covo_merge, covo_merge_ranks and covo_merge_ranks_wide (`who`, for the messages): the merge over G records `stride` floats apart
+// (rank_stride: the caller's own record_floats, one of the two rank-record sizes), then (pos_stats_out != null) the sum of the ranks'
+// position sums
+static int merge_records(covo_handle_t h, const char *who, const float *records, int G, int stride, bool rank_stride,
+                         const float *a_mean_old, float gamma_mean, float *a_mean_out, double *pos_stats_out, void *stream)
+{
+    REQUIRE(h, "%s: null handle", who);
+    CHECK_DEVICE(h, who);
+    REQUIRE(records && a_mean_old && a_mean_out && G > 0, "%s: bad argument", who);
+    REQUIRE(!rank_stride || stride == COVO_RANK_RECORD_FLOATS || stride == COVO_RANK_RECORD_COV_FLOATS,
+            "%s: record_floats=%d is neither COVO_RANK_RECORD_FLOATS nor COVO_RANK_RECORD_COV_FLOATS", who, stride);
+    int rc = launch_merge(update_from_records(records, G, stride, a_mean_old, gamma_mean, a_mean_out), h->cfg.lam, (hipStream_t)stream);
+    if (rc == 0 && pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, stride, pos_stats_out, (hipStream_t)stream);
+    return rc;
+}
+
 int covo_merge(covo_handle_t h, const float *partials, int32_t G, const float *a_mean_old, float gamma_mean,
                float *a_mean_out, void *stream)
 {
-    REQUIRE(h, "covo_merge: null handle");
-    CHECK_DEVICE(h, "covo_merge");
-    REQUIRE(partials && a_mean_old && a_mean_out && G > 0, "covo_merge: bad argument");
-    return launch_merge(update_from_records(partials, G, COVO_PARTIAL_FLOATS, a_mean_old, gamma_mean, a_mean_out), h->cfg.lam,
-                        (hipStream_t)stream);
+    return merge_records(h, "covo_merge", partials, G, COVO_PARTIAL_FLOATS, false, a_mean_old, gamma_mean, a_mean_out, nullptr, stream);
 }
 
 int covo_merge_ranks(covo_handle_t h, const float *records, int32_t G, const float *a_mean_old, float gamma_mean,
                      float *a_mean_out, double *pos_stats_out, void *stream)
 {
-    REQUIRE(h, "covo_merge_ranks: null handle");
-    CHECK_DEVICE(h, "covo_merge_ranks");
-    REQUIRE(records && a_mean_old && a_mean_out && G > 0, "covo_merge_ranks: bad argument");
-    int rc = launch_merge(update_from_records(records, G, COVO_RANK_RECORD_FLOATS, a_mean_old, gamma_mean, a_mean_out), h->cfg.lam,
-                          (hipStream_t)stream);
-    if (rc) return rc;
-    if (pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, COVO_RANK_RECORD_FLOATS, pos_stats_out, (hipStream_t)stream);
-    return rc;
+    return merge_records(h, "covo_merge_ranks", records, G, COVO_RANK_RECORD_FLOATS, false, a_mean_old, gamma_mean, a_mean_out,
+                         pos_stats_out, stream);
 }
 
 int covo_merge_ranks_wide(covo_handle_t h, const float *records, int32_t G, int32_t record_floats, const float *a_mean_old,
                           float gamma_mean, float *a_mean_out, double *pos_stats_out, void *stream)
 {
-    REQUIRE(h, "covo_merge_ranks_wide: null handle");
-    CHECK_DEVICE(h, "covo_merge_ranks_wide");
-    REQUIRE(records && a_mean_old && a_mean_out && G > 0, "covo_merge_ranks_wide: bad argument");
-    REQUIRE(record_floats == COVO_RANK_RECORD_FLOATS || record_floats == COVO_RANK_RECORD_COV_FLOATS,
-            "covo_merge_ranks_wide: record_floats=%d is neither COVO_RANK_RECORD_FLOATS nor COVO_RANK_RECORD_COV_FLOATS", record_floats);
-    int rc = launch_merge(update_from_records(records, G, record_floats, a_mean_old, gamma_mean, a_mean_out), h->cfg.lam,
-                          (hipStream_t)stream);
-    if (rc) return rc;
-    if (pos_stats_out != nullptr) rc = launch_rank_stats_sum(records, G, record_floats, pos_stats_out, (hipStream_t)stream);
-    return rc;
+    return merge_records(h, "covo_merge_ranks_wide", records, G, record_floats, true, a_mean_old, gamma_mean, a_mean_out, pos_stats_out,
+                         stream);
 }
 
 int covo_exchange_create(covo_handle_t h, int32_t world, int32_t rank, void *handle_out)

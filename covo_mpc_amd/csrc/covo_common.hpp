@@ -375,6 +375,8 @@ size_t softmax_cov_workspace_floats(int max_blocks);
 // COVO_PARTIAL_FLOATS + 320 floats of a COVO_RANK_RECORD_COV_FLOATS rank record
 int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 int launch_merge_cov(const UpdateDesc &d, float lam, hipStream_t s);
+// the diagnostics of a covariance update: the G records of ws_partials_cov and ws_diag_rec -> diag_out (reduce.hip; N: the sample count)
+void launch_merge_cov_diag(covo_ctx *h, int G, float inv_lam, float *diag_out, int N, hipStream_t s);
 int launch_shift_mean(const float *in, float *out, hipStream_t s);
 size_t hessian_workspace_bytes(int batch);
 struct SymStatsOut;  // sym_stats.hpp

@@ -39,7 +39,7 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_kernel(const float *
                                                                    float inv_lam, float *__restrict__ partials,
                                                                    const float4 *__restrict__ mu)
 {
-    softmax_partial_body<COV, false>(cost, a, N, blockmin, nbm, inv_lam, partials, mu, nullptr);
+    softmax_partial_body<COV, false>(cost, a, N, SoftmaxWeights{blockmin, nbm, inv_lam}, partials, mu, nullptr);
 }
 template <bool COV>
 __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_diag_kernel(const float *__restrict__ cost,
@@ -48,7 +48,7 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_diag_kernel(const fl
                                                                         float inv_lam, float *__restrict__ partials,
                                                                         const float4 *__restrict__ mu, float *__restrict__ dpart)
 {
-    softmax_partial_body<COV, true>(cost, a, N, blockmin, nbm, inv_lam, partials, mu, dpart);
+    softmax_partial_body<COV, true>(cost, a, N, SoftmaxWeights{blockmin, nbm, inv_lam}, partials, mu, dpart);
 }
 
 
@@ -63,7 +63,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_cov_kernel(const float *__re
 }
 
 // Merges G records {m, s, v[128]} with 1024 threads = 8 record-slices x 128 columns (softmax_merge.hpp: the body is shared
-// with the launches that finish their own update).
+// with the launches that finish their own update); blockIdx.x (env-batched step): instance x merges its own G records into its own mean.
 // FINAL: a_mean_out = gamma * v/s + (1-gamma) * a_mean_old (covo.py:270-275); otherwise writes the
 // merged record to out.  Fixed summation order -> bit-reproducible.
 // stride: floats between consecutive records (COVO_PARTIAL_FLOATS, or COVO_RANK_RECORD_FLOATS for the all-gathered rank records
@@ -74,15 +74,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_kernel(const float *__restri
                                                            float *__restrict__ out, int stride, float *__restrict__ iter_out,
                                                            int iter_stride)
 {
-    __shared__ MergeLds lds;
-    {   // blockIdx.x (env-batched step): instance x merges its own G records into its own mean
-        const size_t x = blockIdx.x;
-        partials += x * G * stride;
-        if (FINAL) a_mean_old += x * COVO_NA;
-        out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
-    }
-    merge_body<MG_THREADS, FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds);
-    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
+    merge_instance<FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, nullptr, nullptr, 0.0f, iter_out, iter_stride);
 }
 
 // the same, and the diagnostic records dpart [instances][G][MG_DIAG_REC] merged into row x of diag_out [instances][COVO_DIAG_FLOATS]
@@ -93,19 +85,7 @@ __global__ __launch_bounds__(MG_THREADS) void merge_diag_kernel(const float *__r
                                                                 float *__restrict__ diag_out, float n_samples, float *__restrict__ iter_out,
                                                                 int iter_stride)
 {
-    __shared__ MergeLds lds;
-    __shared__ float dred[3][MG_VWAVES];
-    const size_t x = blockIdx.x;
-    partials += x * G * stride;
-    if (FINAL) a_mean_old += x * COVO_NA;
-    out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
-    MergeDiag D;
-    D.rec = dpart + x * G * MG_DIAG_REC;
-    D.out = diag_out + x * COVO_DIAG_FLOATS;
-    D.n = n_samples;
-    D.red = dred;
-    merge_body<MG_THREADS, FINAL, false, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds, D);
-    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
+    merge_instance<FINAL, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, dpart, diag_out, n_samples, iter_out, iter_stride);
 }
 
 // the episode drivers (capi.hip): the step's diagnostics [n_inst][COVO_DIAG_FLOATS] -> row `index` of every instance's log
@@ -132,21 +112,17 @@ __global__ void shift_mean_kernel(const float *__restrict__ in, float *__restric
     out[i] = (i < COVO_NA - COVO_DU) ? in[i + COVO_DU] : in[i];
 }
 
-// stage 1's launch shape and cost minima, shared by the two entry points below: d's own minima, or formed over the costs first
-struct Stage1 {
+// stage 1's cost minima, for the two entry points below: d's own per-wave minima, or formed over the costs first (only this file
+// forms them itself: reduce_lam.hip refuses a step without them, reduce_elite.hip does not read them)
+struct Minima {
     const float *blockmin;
-    int n_blockmin, grid;
+    int n_blockmin;
 };
-static Stage1 update_stage1(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
+static Minima stage1_minima(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
 {
-    Stage1 st{d.blockmin, d.n_blockmin, ((d.N + 63) / 64 + RD_WAVES - 1) / RD_WAVES};
-    if (st.blockmin == nullptr) {
-        st.n_blockmin = (d.N + 63) / 64;
-        hipLaunchKernelGGL(groupmin_kernel, dim3((d.N + 255) / 256), dim3(256), 0, s, d.cost, d.N, h->ws_blockmin);
-        st.blockmin = h->ws_blockmin;
-    }
-    if (st.grid > h->max_red_blocks) st.grid = h->max_red_blocks;
-    return st;
+    if (d.blockmin != nullptr) return {d.blockmin, d.n_blockmin};
+    hipLaunchKernelGGL(groupmin_kernel, dim3((d.N + 255) / 256), dim3(256), 0, s, d.cost, d.N, h->ws_blockmin);
+    return {h->ws_blockmin, (d.N + 63) / 64};
 }
 
 int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
@@ -154,23 +130,24 @@ int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
     if (d.lam_rows != nullptr) return launch_softmax_reduce_lam(h, d, s);  // (reduce_lam.hip)
     const float inv_lam = 1.0f / h->cfg.lam;
     float *partials_ws = d.partials_ws ? d.partials_ws : h->ws_partials;
-    const Stage1 st = update_stage1(h, d, s);
+    const Minima mn = stage1_minima(h, d, s);
+    const int grid = stage1_grid(h, d.N);
     const float4 *a4 = reinterpret_cast<const float4 *>(d.a);
     if (d.diag_out != nullptr && d.a_mean_out != nullptr) {  // the same two launches in their diagnostic variants
-        hipLaunchKernelGGL(softmax_partial_diag_kernel<false>, dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
-                           st.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr, d.diag_rec);
-        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam, d.a_mean_old,
+        hipLaunchKernelGGL(softmax_partial_diag_kernel<false>, dim3(grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
+                           mn.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr, d.diag_rec);
+        hipLaunchKernelGGL(merge_diag_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, grid, inv_lam, d.a_mean_old,
                            d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, (const float *)d.diag_rec, d.diag_out, (float)d.N, d.iter_out, d.iter_stride);
         COVO_CHECK_HIP(hipGetLastError());
         return 0;
     }
-    hipLaunchKernelGGL(softmax_partial_kernel<false>, dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
-                       st.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr);
+    hipLaunchKernelGGL(softmax_partial_kernel<false>, dim3(grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
+                       mn.n_blockmin, inv_lam, partials_ws, (const float4 *)nullptr);
     if (d.a_mean_out != nullptr)
-        hipLaunchKernelGGL(merge_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam, d.a_mean_old,
+        hipLaunchKernelGGL(merge_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, grid, inv_lam, d.a_mean_old,
                            d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, d.iter_out, d.iter_stride);
     else
-        hipLaunchKernelGGL(merge_kernel<false>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, inv_lam,
+        hipLaunchKernelGGL(merge_kernel<false>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, grid, inv_lam,
                            (const float *)nullptr, 1.0f, d.partial_out, COVO_PARTIAL_FLOATS, (float *)nullptr, 0);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
@@ -184,28 +161,33 @@ int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
     if (d.lam_rows != nullptr) return launch_softmax_update_cov_lam(h, d, s);  // (reduce_lam.hip)
     const float inv_lam = 1.0f / h->cfg.lam;
     const bool diag = d.diag_out != nullptr && d.a_cov_out != nullptr;
-    const Stage1 st = update_stage1(h, d, s);
+    const Minima mn = stage1_minima(h, d, s);
+    const int grid = stage1_grid(h, d.N);
     const float4 *a4 = reinterpret_cast<const float4 *>(d.a), *mean4 = reinterpret_cast<const float4 *>(d.a_mean_old);
     if (diag)
-        hipLaunchKernelGGL(softmax_partial_diag_kernel<true>, dim3(st.grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
-                           st.n_blockmin, inv_lam, h->ws_partials_cov, mean4, h->ws_diag_rec);
+        hipLaunchKernelGGL(softmax_partial_diag_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
+                           mn.n_blockmin, inv_lam, h->ws_partials_cov, mean4, h->ws_diag_rec);
     else
-        hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(st.grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
-                           st.n_blockmin, inv_lam, h->ws_partials_cov, mean4);
-    // the covariance merge below has its own body: the diagnostics come from one more merge launch over the same headers {m_g, s_g}
-    // (its merged record goes to the idle ws_partials), off the path of a step without diagnostics
-    if (diag)
-        hipLaunchKernelGGL(merge_diag_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam,
-                           (const float *)nullptr, 1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, d.diag_out,
-                           (float)d.N, (float *)nullptr, 0);
+        hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
+                           mn.n_blockmin, inv_lam, h->ws_partials_cov, mean4);
+    if (diag) launch_merge_cov_diag(h, grid, inv_lam, d.diag_out, d.N, s);
     if (d.a_cov_out != nullptr)
-        hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam, d.a_mean_old,
+        hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam, d.a_mean_old,
                            d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS, d.iter_out);
     else  // a sample-sharded rank: its record {m, s, v, pad, S2}, unnormalised and unblended
-        hipLaunchKernelGGL(merge_cov_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, inv_lam, d.a_mean_old,
+        hipLaunchKernelGGL(merge_cov_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam, d.a_mean_old,
                            1.0f, (const float *)nullptr, 0.0f, d.partial_out, (float *)nullptr, RD_COV_RECORD_FLOATS, (float *)nullptr);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
+}
+
+// The covariance merge has its own body: the diagnostics of MPPI's covariance update come from one more merge launch over the headers
+// {m_g, s_g} of the G 452-float records in ws_partials_cov and their diagnostic records in ws_diag_rec (its merged record goes to the
+// idle ws_partials), off the path of a step without diagnostics.  Also the elite-set update's, at 1 / lambda = 1 (reduce_elite.hip).
+void launch_merge_cov_diag(covo_ctx *h, int G, float inv_lam, float *diag_out, int N, hipStream_t s)
+{
+    hipLaunchKernelGGL(merge_diag_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, G, inv_lam, (const float *)nullptr,
+                       1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, diag_out, (float)N, (float *)nullptr, 0);
 }
 
 // the G all-gathered rank records (stride floats apart) -> new mean and adapted covariances, identically on every rank

@@ -15,7 +15,7 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_lam_kernel(const flo
                                                                        const float4 *__restrict__ mu, float *__restrict__ dpart)
 {
     const float inv_lam = lam_rows[(size_t)blockIdx.y * COVO_LAM_FLOATS + 1];
-    softmax_partial_body<COV, DIAG>(cost, a, N, blockmin, nbm, inv_lam, partials, mu, dpart);
+    softmax_partial_body<COV, DIAG>(cost, a, N, SoftmaxWeights{blockmin, nbm, inv_lam}, partials, mu, dpart);
 }
 
 // The ESS floor: the two merges above with 1 / lambda read from row blockIdx.x of the solver's output
@@ -26,14 +26,8 @@ __global__ __launch_bounds__(MG_THREADS) void merge_lam_kernel(const float *__re
                                                                float *__restrict__ out, int stride, float *__restrict__ iter_out,
                                                                int iter_stride)
 {
-    __shared__ MergeLds lds;
-    const size_t x = blockIdx.x;
-    const float inv_lam = lam_rows[x * COVO_LAM_FLOATS + 1];
-    partials += x * G * stride;
-    if (FINAL) a_mean_old += x * COVO_NA;
-    out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
-    merge_body<MG_THREADS, FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds);
-    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
+    const float inv_lam = lam_rows[(size_t)blockIdx.x * COVO_LAM_FLOATS + 1];
+    merge_instance<FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, nullptr, nullptr, 0.0f, iter_out, iter_stride);
 }
 template <bool FINAL>
 __global__ __launch_bounds__(MG_THREADS) void merge_diag_lam_kernel(const float *__restrict__ partials, int G,
@@ -43,20 +37,8 @@ __global__ __launch_bounds__(MG_THREADS) void merge_diag_lam_kernel(const float 
                                                                     const float *__restrict__ dpart, float *__restrict__ diag_out,
                                                                     float n_samples, float *__restrict__ iter_out, int iter_stride)
 {
-    __shared__ MergeLds lds;
-    __shared__ float dred[3][MG_VWAVES];
-    const size_t x = blockIdx.x;
-    const float inv_lam = lam_rows[x * COVO_LAM_FLOATS + 1];
-    partials += x * G * stride;
-    if (FINAL) a_mean_old += x * COVO_NA;
-    out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
-    MergeDiag D;
-    D.rec = dpart + x * G * MG_DIAG_REC;
-    D.out = diag_out + x * COVO_DIAG_FLOATS;
-    D.n = n_samples;
-    D.red = dred;
-    merge_body<MG_THREADS, FINAL, false, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds, D);
-    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
+    const float inv_lam = lam_rows[(size_t)blockIdx.x * COVO_LAM_FLOATS + 1];
+    merge_instance<FINAL, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, dpart, diag_out, n_samples, iter_out, iter_stride);
 }
 
 // the ESS floor: 1 / lambda from row 0 of the solver's output (the covariance update is a single-instance launch)
@@ -71,18 +53,6 @@ __global__ __launch_bounds__(MG_THREADS) void merge_cov_lam_kernel(const float *
 }
 
 
-// stage 1's launch shape, as reduce.hip's update_stage1 with the caller's per-wave minima (a step with a floor always has them)
-struct LamStage1 {
-    const float *blockmin;
-    int n_blockmin, grid;
-};
-static LamStage1 lam_stage1(const covo_ctx *h, const UpdateDesc &d)
-{
-    LamStage1 st{d.blockmin, d.n_blockmin, ((d.N + 63) / 64 + RD_WAVES - 1) / RD_WAVES};
-    if (st.grid > h->max_red_blocks) st.grid = h->max_red_blocks;
-    return st;
-}
-
 // the ESS floor's variant of launch_softmax_reduce: d.lam_rows [batch][COVO_LAM_FLOATS] in device memory, a final update only
 int launch_softmax_reduce_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
 {
@@ -91,18 +61,18 @@ int launch_softmax_reduce_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
         return COVO_E_BADARG;
     }
     float *partials_ws = d.partials_ws ? d.partials_ws : h->ws_partials;
-    const LamStage1 st = lam_stage1(h, d);
+    const int grid = stage1_grid(h, d.N);  // (the caller's per-wave minima: a step with a floor always has them)
     const float4 *a4 = reinterpret_cast<const float4 *>(d.a);
     if (d.diag_out != nullptr) {
-        hipLaunchKernelGGL((softmax_partial_lam_kernel<false, true>), dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N,
-                           st.blockmin, st.n_blockmin, d.lam_rows, partials_ws, (const float4 *)nullptr, d.diag_rec);
-        hipLaunchKernelGGL(merge_diag_lam_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, d.lam_rows,
+        hipLaunchKernelGGL((softmax_partial_lam_kernel<false, true>), dim3(grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N,
+                           d.blockmin, d.n_blockmin, d.lam_rows, partials_ws, (const float4 *)nullptr, d.diag_rec);
+        hipLaunchKernelGGL(merge_diag_lam_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, grid, d.lam_rows,
                            d.a_mean_old, d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, (const float *)d.diag_rec, d.diag_out,
                            (float)d.N, d.iter_out, d.iter_stride);
     } else {
-        hipLaunchKernelGGL((softmax_partial_lam_kernel<false, false>), dim3(st.grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N,
-                           st.blockmin, st.n_blockmin, d.lam_rows, partials_ws, (const float4 *)nullptr, (float *)nullptr);
-        hipLaunchKernelGGL(merge_lam_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, st.grid, d.lam_rows,
+        hipLaunchKernelGGL((softmax_partial_lam_kernel<false, false>), dim3(grid, d.batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N,
+                           d.blockmin, d.n_blockmin, d.lam_rows, partials_ws, (const float4 *)nullptr, (float *)nullptr);
+        hipLaunchKernelGGL(merge_lam_kernel<true>, dim3(d.batch), dim3(MG_THREADS), 0, s, partials_ws, grid, d.lam_rows,
                            d.a_mean_old, d.gamma_mean, d.a_mean_out, COVO_PARTIAL_FLOATS, d.iter_out, d.iter_stride);
     }
     COVO_CHECK_HIP(hipGetLastError());
@@ -116,19 +86,19 @@ int launch_softmax_update_cov_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t 
         covo_set_error("launch_softmax_update_cov: a device temperature needs a final update and the per-wave cost minima");
         return COVO_E_BADARG;
     }
-    const LamStage1 st = lam_stage1(h, d);
+    const int grid = stage1_grid(h, d.N);  // (the caller's per-wave minima: a step with a floor always has them)
     const float4 *a4 = reinterpret_cast<const float4 *>(d.a), *mean4 = reinterpret_cast<const float4 *>(d.a_mean_old);
     if (d.diag_out != nullptr) {  // (the diagnostics' own merge over the same headers, as in launch_softmax_update_cov)
-        hipLaunchKernelGGL((softmax_partial_lam_kernel<true, true>), dim3(st.grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
-                           st.n_blockmin, d.lam_rows, h->ws_partials_cov, mean4, h->ws_diag_rec);
-        hipLaunchKernelGGL(merge_diag_lam_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, d.lam_rows,
+        hipLaunchKernelGGL((softmax_partial_lam_kernel<true, true>), dim3(grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, d.blockmin,
+                           d.n_blockmin, d.lam_rows, h->ws_partials_cov, mean4, h->ws_diag_rec);
+        hipLaunchKernelGGL(merge_diag_lam_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, d.lam_rows,
                            (const float *)nullptr, 1.0f, h->ws_partials, RD_COV_RECORD_FLOATS, (const float *)h->ws_diag_rec, d.diag_out,
                            (float)d.N, (float *)nullptr, 0);
     } else {
-        hipLaunchKernelGGL((softmax_partial_lam_kernel<true, false>), dim3(st.grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, st.blockmin,
-                           st.n_blockmin, d.lam_rows, h->ws_partials_cov, mean4, (float *)nullptr);
+        hipLaunchKernelGGL((softmax_partial_lam_kernel<true, false>), dim3(grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, d.blockmin,
+                           d.n_blockmin, d.lam_rows, h->ws_partials_cov, mean4, (float *)nullptr);
     }
-    hipLaunchKernelGGL(merge_cov_lam_kernel, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, st.grid, d.lam_rows, d.a_mean_old,
+    hipLaunchKernelGGL(merge_cov_lam_kernel, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, d.lam_rows, d.a_mean_old,
                        d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS, d.iter_out);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;

@@ -197,3 +197,28 @@ __device__ __forceinline__ void merge_body(const float *__restrict__ partials, i
         }
     }
 }
+
+// The stand-alone merge launch (reduce.hip, reduce_lam.hip): workgroup blockIdx.x of MG_THREADS threads merges instance x's G
+// records into its own mean (FINAL) or merged record, DIAG: and the diagnostic records dpart [instances][G][MG_DIAG_REC] into row x
+// of diag_out [instances][COVO_DIAG_FLOATS]; iter_out != null (an iterated step): the cost minimum to slot x * iter_stride.
+template <bool FINAL, bool DIAG>
+__device__ __forceinline__ void merge_instance(const float *partials, int G, float inv_lam, const float *a_mean_old, float gamma_mean,
+                                               float *out, int stride, const float *dpart, float *diag_out, float n_samples,
+                                               float *iter_out, int iter_stride)
+{
+    __shared__ MergeLds lds;
+    const size_t x = blockIdx.x;
+    partials += x * G * stride;
+    if (FINAL) a_mean_old += x * COVO_NA;
+    out += x * (FINAL ? COVO_NA : COVO_PARTIAL_FLOATS);
+    MergeDiag D;
+    if constexpr (DIAG) {
+        __shared__ float dred[3][MG_VWAVES];
+        D.rec = dpart + x * G * MG_DIAG_REC;
+        D.out = diag_out + x * COVO_DIAG_FLOATS;
+        D.n = n_samples;
+        D.red = dred;
+    }
+    merge_body<MG_THREADS, FINAL, false, DIAG>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, lds, D);
+    if (iter_out != nullptr && threadIdx.x == 0) merge_log_min<MG_THREADS>(lds, iter_out + blockIdx.x * (size_t)iter_stride);
+}

@@ -1,5 +1,6 @@
-// softmax_stage1.hpp -- the device bodies of the softmax update's stage 1 and of MPPI's covariance merge (see reduce.hip), shared by
-// the kernels of reduce.hip (1 / lambda as a kernel argument) and of reduce_lam.hip (1 / lambda read from device memory: the ESS floor).
+// softmax_stage1.hpp -- the device bodies of the weighted update's stage 1 and of MPPI's covariance merge (see reduce.hip), shared by
+// the kernels of reduce.hip (1 / lambda as a kernel argument), of reduce_lam.hip (1 / lambda read from device memory: the ESS floor)
+// and of reduce_elite.hip (0/1 weights off the selector's threshold: the elite set).
 #pragma once
 #include "covo_common.hpp"
 #include "softmax_merge.hpp"
@@ -7,21 +8,53 @@
 constexpr int RD_BLOCK = 256;
 constexpr int RD_WAVES = RD_BLOCK / 64;
 
+// stage 1's grid for N samples: one wave per 64-sample group, capped at the handle's max_red_blocks (the waves then stride)
+static inline int stage1_grid(const covo_ctx *h, int N)
+{
+    const int grid = ((N + 63) / 64 + RD_WAVES - 1) / RD_WAVES;
+    return grid > h->max_red_blocks ? h->max_red_blocks : grid;
+}
+
 // COV (MPPI's covariance adaptation, mppi.py:119-125): the record also carries the weighted second moments of d = a - mu
 // about the SHIFTED OLD mean mu (known before sampling; d is the clipped L eps, so no cancellation against mean^2):
 // rec[COVO_PARTIAL_FLOATS + 10 t + j] = sum_n w_n d_i d_j for the 10 pairs i <= j of step t (cov_pair below).
 constexpr int RD_COV_FLOATS = COVO_H * 10;                                   // 320
 constexpr int RD_COV_RECORD_FLOATS = COVO_PARTIAL_FLOATS + RD_COV_FLOATS;    // 452
+
+// The weights of stage 1 are a policy, passed by value: RED_FLOATS (the LDS floats begin() folds through), begin(red) -> the
+// record's m for instance blockIdx.y, weight(c, m, n, N) -> w_n, and the diagnostic sums' terms diag_w2(w), diag_wdc(w, c - m).
+// SoftmaxWeights (covo.py:266): w = exp((m - c) / lambda), m the exact global minimum of the costs from the per-wave minima the
+// rollout left -- weights formed exactly like the reference's `cost - jnp.min(cost)`.  (The elite set's 0/1 weights: reduce_elite.hip.)
+struct SoftmaxWeights {
+    const float *__restrict__ blockmin;  // [instances][nbm]
+    int nbm;
+    float inv_lam;
+    static constexpr int RED_FLOATS = RD_WAVES;
+    __device__ __forceinline__ float begin(float *red) const
+    {
+        const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+        const float *mins = blockmin + (size_t)blockIdx.y * nbm;
+        float m = __builtin_inff();
+        for (int i = tid; i < nbm; i += RD_BLOCK) m = fminf(m, mins[i]);
+        m = wave_min(m);
+        if (lane == 0) red[wave] = m;
+        __syncthreads();
+        return fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    }
+    __device__ __forceinline__ float weight(float c, float m, int, int) const { return expf((m - c) * inv_lam); }
+    // every product rounded on its own: no contraction into the sums
+    __device__ __forceinline__ float diag_w2(float w) const { return __fmul_rn(w, w); }
+    __device__ __forceinline__ float diag_wdc(float w, float dc) const { return __fmul_rn(w, dc); }
+};
+
 // DIAG (covo_set_step_diag): the workgroup also leaves its diagnostic record {sum w^2, sum w (c - m), sum (c - m), samples}
-// (softmax_merge.hpp: MergeDiag; m is the global minimum here) in dpart[workgroup].
-template <bool COV, bool DIAG>
-__device__ __forceinline__ void softmax_partial_body(const float *__restrict__ cost, const float4 *__restrict__ a, int N,
-                                                     const float *__restrict__ blockmin, int nbm, float inv_lam,
+// (softmax_merge.hpp: MergeDiag; m is the policy's m here) in dpart[workgroup].
+template <bool COV, bool DIAG, class Weights>
+__device__ __forceinline__ void softmax_partial_body(const float *__restrict__ cost, const float4 *__restrict__ a, int N, Weights wt,
                                                      float *__restrict__ partials, const float4 *__restrict__ mu,
                                                      float *__restrict__ dpart)
 {
     constexpr int REC = COV ? RD_COV_RECORD_FLOATS : COVO_PARTIAL_FLOATS;
-    __shared__ float red[RD_WAVES];
     __shared__ float sv[RD_WAVES][COVO_NA];
     __shared__ float sv2[COV ? RD_WAVES : 1][COV ? RD_COV_FLOATS : 1];
     __shared__ float ss[RD_WAVES];
@@ -30,18 +63,16 @@ __device__ __forceinline__ void softmax_partial_body(const float *__restrict__ c
         const size_t y = blockIdx.y;
         cost += y * N;
         a += y * ((size_t)COVO_H * N);
-        blockmin += y * nbm;
         partials += y * gridDim.x * REC;
         if (DIAG) dpart += y * gridDim.x * MG_DIAG_REC;
     }
-
-    // ---- exact global minimum of cost from the per-block minima
-    float m = __builtin_inff();
-    for (int i = tid; i < nbm; i += RD_BLOCK) m = fminf(m, blockmin[i]);
-    m = wave_min(m);
-    if (lane == 0) red[wave] = m;
-    __syncthreads();
-    m = fminf(fminf(red[0], red[1]), fminf(red[2], red[3]));
+    float m;
+    if constexpr (Weights::RED_FLOATS > 0) {
+        __shared__ float red[Weights::RED_FLOATS];
+        m = wt.begin(red);
+    } else {
+        m = wt.begin(nullptr);
+    }
 
     const int ngroups = (N + 63) / 64;
     const int sub = lane & 7, tq = lane >> 3;
@@ -68,12 +99,12 @@ __device__ __forceinline__ void softmax_partial_body(const float *__restrict__ c
     for (int g = blockIdx.x * RD_WAVES + wave; g < ngroups; g += gridDim.x * RD_WAVES) {
         const int n = g * 64 + lane;
         const float c = (n < N) ? cost[n] : __builtin_inff();
-        const float w = expf((m - c) * inv_lam);  // covo.py:266
+        const float w = wt.weight(c, m, n, N);
         s_lane += w;
-        if (DIAG && n < N) {  // every product rounded on its own: no contraction into the sums
+        if (DIAG && n < N) {
             const float dc = c - m;
-            d_lane[0] += __fmul_rn(w, w);
-            d_lane[1] += __fmul_rn(w, dc);
+            d_lane[0] += wt.diag_w2(w);
+            d_lane[1] += wt.diag_wdc(w, dc);
             d_lane[2] += dc;
             d_lane[3] += 1.0f;
         }

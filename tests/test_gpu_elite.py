@@ -242,6 +242,34 @@ def test_one_step_mppi_covariance_refit(monkeypatch):
         c.core.close()
 
 
+@pytest.mark.parametrize("N,K,gamma_sigma", [(65, 8, 0.0), (65600, 4000, 0.0), (65600, 4000, 0.3)])
+def test_stage1_sample_tail_and_second_grid_trip(N, K, gamma_sigma, monkeypatch):
+    """The shapes at which the stage 1 shared with the softmax update walks its stripes differently, MPPI with diagnostics, one step.
+    N = 65: one full 64-sample group and a one-sample tail (the sample clamp is live in the second group, two waves have no group).
+    N = 65 600: 1 025 groups on the 256 x 4 waves of the capped grid -- one wave takes a second trip, over a full group; once more
+    with gamma_sigma = 0.3 for the second-moment records.  Mean, a_cov and diagnostics against the fp64 elite update (K^2 < 2^24)."""
+    monkeypatch.setenv("COVO_NO_GRAPH", "1")
+    env = _env()
+    c, cp, obs, info, state, params = _controller(env, "mppi", N, elite=K, compute_diag=True)
+    cp = cp.replace(gamma_sigma=gamma_sigma)
+    _, cp2, _ = c(obs, state, params, cr.PRNGKey(3), cp, info)
+    torch.cuda.synchronize()
+    shift = R.shift_mean(cp.a_mean.cpu().numpy().astype(np.float64))
+    mean, elites, a = elite_mean_ref(c.core, K, shift, cp.gamma_mean)
+    cov = R.mppi_cov_update(np.full(K, 1.0 / K), a[elites], mean, R.shift_mean(cp.a_cov.cpu().numpy().astype(np.float64)), gamma_sigma)
+    cost = c.core.cost.cpu().numpy()
+    d = c.core.diag[0].cpu().numpy()
+    e_mean, e_cov = rel(cp2.a_mean.cpu().numpy(), mean), rel(cp2.a_cov.cpu().numpy(), cov)
+    cw, cm = rel(d[2], cost[elites].astype(np.float64).mean()), rel(d[3], cost.astype(np.float64).mean())
+    print(f"  mppi N={N} K={K} gamma_sigma={gamma_sigma}: mean err {e_mean:.2e}, a_cov err {e_cov:.2e}, ess {d[0]!r}, weight_sum {d[4]!r}, "
+          f"cost_weighted err {cw:.2e}, cost_mean err {cm:.2e}, elites in the last group {int((elites >= 64 * ((N - 1) // 64)).sum())}")
+    assert e_mean <= BAR and e_cov <= BAR, (N, gamma_sigma, e_mean, e_cov)
+    assert d[0] == K and d[4] == K and d[5] == N, d
+    assert cw <= BAR and cm <= BAR and d[1] == cost.min(), d
+    assert c.core.device_status() == 0
+    c.core.close()
+
+
 @pytest.mark.parametrize("name", ["mppi", "covo-offline", "covo-online"])
 def test_one_elite_is_the_best_sample_and_all_elites_the_plain_average(name, monkeypatch):
     """K = 1, gamma_mean = 1: a_mean is a[:, n*, :] bit for bit, n* the arbiter's arb_best on the same step.  K = N: the plain average."""
