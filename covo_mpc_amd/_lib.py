@@ -42,6 +42,8 @@ COVO_ELITE_FLOATS = 8  # the elite-set update's selector row of one instance (co
 ELITE_FIELDS = ("threshold_cost_word", "threshold_index_word", "cost_min", "cost_kth", "K", "ties")  # words: uint32 bits
 COVO_HAS_SIGMA_PERIOD = 1
 COVO_MAX_SIGMA_PERIOD = 64  # sigma_period= of the covo-online controllers: every m-th step refreshes Sigma (covo_set_step_sigma_period)
+COVO_HAS_POST_COV = 1
+COVO_POST_AUX_FLOATS = 132  # the posterior covariance's side row of one instance: {shift d[128], W, 0, 0, 0} (covo_set_step_post_cov)
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -179,6 +181,8 @@ _SIGS = {
     "covo_step_sigma_age": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "covo_sigma_shift": (C.c_int, [_P, _P, C.c_int32, C.c_float, _P, _P, _P]),
     "covo_debug_sigma_factor": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
+    "covo_set_step_post_cov": (C.c_int, [_P, _P, _P, C.c_int32]),  # the posterior covariance (covo_hip.h: COVO_HAS_POST_COV)
+    "covo_weighted_cov": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P]),
     "covo_set_step_plan": (C.c_int, [_P, _P, C.c_int32]),             # the flight recorder (covo_hip.h: COVO_HAS_PLAN_TRACE)
     "covo_set_episode_trace": (C.c_int, [_P, _P, C.c_int32]),
     "covo_rollout_fan": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P,

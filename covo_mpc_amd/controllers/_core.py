@@ -54,7 +54,7 @@ class SamplingCore:
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
-                 sigma_period: int = 1):
+                 sigma_period: int = 1, compute_post_cov: bool = False):
         import torch
         sigma_period = _lib.check_sigma_period(sigma_period)
         fan_K = _lib.check_fan(compute_fan, N)
@@ -77,7 +77,9 @@ class SamplingCore:
                     (elite_K, f"elite={elite_K} on sample-sharded ranks: a rank sees only its shard's costs "
                               "(covo_set_step_elite refuses sample-sharded steps)"),
                     (sigma_period > 1, f"sigma_period={sigma_period} on sample-sharded ranks: every rank would have to keep and shift "
-                                       "the same factor (covo_set_step_sigma_period refuses sample-sharded steps)")):
+                                       "the same factor (covo_set_step_sigma_period refuses sample-sharded steps)"),
+                    (compute_post_cov, "compute_post_cov on sample-sharded ranks: a rank's action and cost buffers hold its shard "
+                                       "only (covo_set_step_post_cov refuses sample-sharded steps)")):
                 if is_on and sharded:
                     raise NotImplementedError(message)
         if H != COVO_H:
@@ -243,6 +245,18 @@ class SamplingCore:
         self.sigma_period = sigma_period
         if sigma_period > 1:
             check(self.lib.covo_set_step_sigma_period(self.h, sigma_period), "covo_set_step_sigma_period")
+        # compute_post_cov: every step also leaves the weighted 128 x 128 covariance of its own samples under its own update's weights,
+        # centred on the mean it sampled around, in self.post_cov (row e = instance e of a batched step) and {shift d[128], W, 0, 0, 0}
+        # in self.post_aux, by two extra launches behind the step (covo_set_step_post_cov, csrc/post_cov.hip); off by default, and off
+        # changes nothing
+        self.compute_post_cov = bool(compute_post_cov)
+        self.post_cov = self.post_aux = None
+        if self.compute_post_cov:
+            rows = int(diag_rows)
+            self.post_cov = torch.zeros((rows, COVO_NA, COVO_NA), **f32)
+            self.post_aux = torch.zeros((rows, _lib.COVO_POST_AUX_FLOATS), **f32)
+            with torch.cuda.device(self.device):
+                check(self.lib.covo_set_step_post_cov(self.h, ptr(self.post_cov), ptr(self.post_aux), rows), "covo_set_step_post_cov")
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -379,11 +393,11 @@ class SamplingCore:
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
-        lam_info (ess_min), arbiter_info (update), iter_info (iters) and elite_info (elite) -- views of the core's buffers, no sync, no
-        copy."""
+        lam_info (ess_min), arbiter_info (update), iter_info (iters), elite_info (elite) and post_cov_info (compute_post_cov) -- views of
+        the core's buffers, no sync, no copy."""
         out = {}
         for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info, self.elite_info,
-                     self.sigma_info):
+                     self.sigma_info, self.post_cov_info):
             out.update(info())
         return out
 
@@ -408,6 +422,37 @@ class SamplingCore:
         if self.plan is None:
             return {}
         return {"pos_plan": self.plan[0, 4:].view(COVO_H, 3), "cost_plan": self.plan[0, 0]}
+
+    def post_cov_info(self) -> dict:
+        """{"post_cov" [128, 128], "post_shift" [128] (d: posterior mean minus the mean the step sampled around), "post_weight" 0-d (W)}
+        of the last step as views of self.post_cov / self.post_aux (no sync, no copy); {} when the core was built without
+        compute_post_cov."""
+        if self.post_cov is None:
+            return {}
+        return {"post_cov": self.post_cov[0], "post_shift": self.post_aux[0, :COVO_NA], "post_weight": self.post_aux[0, COVO_NA]}
+
+    def weighted_cov(self, a, cost, mu, lam=None, elite=None):
+        """covo_weighted_cov: the weighted sample covariance of the stripes a [H, N, 4] (or [B, H, N, 4]) about mu [128] ([B, 128])
+        under the weights of cost [N] ([B, N]) -- softmax at lam (default: the core's), or 1 on the elite set of `elite` samples and 0
+        elsewhere; a cost that is not finite weighs 0 -> (C [128, 128], d [128], W 0-d), each with a leading B for batched input:
+        C = sum w y y^T / W - d d^T with y = x - mu, d = sum w y / W, W = sum w.  No sync."""
+        torch = self.torch
+        f32 = dict(dtype=torch.float32, device=self.device)
+        a, cost, mu = (torch.as_tensor(t, **f32).contiguous() for t in (a, cost, mu))
+        batched = a.dim() == 4
+        B = int(a.shape[0]) if batched else 1
+        N = int(a.shape[-2])
+        if tuple(a.shape[-3:]) != (COVO_H, N, 4) or cost.numel() != B * N or mu.numel() != B * COVO_NA:
+            raise ValueError(f"weighted_cov: a {tuple(a.shape)}, cost {tuple(cost.shape)}, mu {tuple(mu.shape)} are not "
+                             f"[B,] {COVO_H} x N x 4, [B,] N and [B,] {COVO_NA}")
+        K = _lib.check_elite(elite, N)
+        cov = torch.empty((B, COVO_NA, COVO_NA), **f32)
+        aux = torch.empty((B, _lib.COVO_POST_AUX_FLOATS), **f32)
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_weighted_cov(self.h, ptr(a), ptr(cost), ptr(mu), N, B, float(self.lam if lam is None else lam), K,
+                                             ptr(cov), ptr(aux), self.stream()), "covo_weighted_cov")
+        d, W = aux[:, :COVO_NA], aux[:, COVO_NA]
+        return (cov, d, W) if batched else (cov[0], d[0], W[0])
 
     def fan_info(self) -> dict:
         """{"fan_pos" [K, H, 3], "fan_cost" [K], "fan_idx" [K] int32} of the last step as views of self.fan (no sync, no copy); {}
@@ -586,6 +631,9 @@ class SamplingCore:
                                       "(materialize_eps / noise_stream='jax') does not produce it")
         if self.compute_fan:
             raise NotImplementedError("compute_fan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') does not produce it")
+        if getattr(self, "compute_post_cov", False):
+            raise NotImplementedError("compute_post_cov follows the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') does not produce it")
         if getattr(self, "arb_mask", 0):
             raise NotImplementedError(f"update={self.update_rule!r} follows the fused step (covo_mpc_step); the kernel-by-kernel path "

@@ -30,7 +30,7 @@ class BatchedCoVOController:
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
-                 sigma_period: int = 1):
+                 sigma_period: int = 1, compute_post_cov: bool = False):
         _lib.check_sigma_period(sigma_period, "online" if (self.MODE is None and mode == "online") else
                                 "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
         _lib.check_fan(compute_fan, N)
@@ -39,6 +39,10 @@ class BatchedCoVOController:
         if _lib.check_elite(elite, N, ess_min) and (self.MODE is not None or mode != "online"):
             raise NotImplementedError(f"elite={elite}: the elite-set update is not available for the env-batched MPPI / covo-offline step "
                                       "(one fused launch: it needs the weights before all costs exist); "
+                                      "BatchedCoVOController(mode=\"online\") and the single controllers take it")
+        if compute_post_cov and (self.MODE is not None or mode != "online"):
+            raise NotImplementedError("compute_post_cov: the posterior covariance is not available for the env-batched MPPI / covo-offline "
+                                      "step (one fused launch: it keeps the samples in LDS and never stores them); "
                                       "BatchedCoVOController(mode=\"online\") and the single controllers take it")
         if iters > 1 and update != "softmax" and (self.MODE is not None or mode != "online"):
             raise NotImplementedError(f"iters={iters} with update={update!r}: not available for the env-batched MPPI / covo-offline step "
@@ -66,7 +70,8 @@ class BatchedCoVOController:
         # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite, sigma_period=sigma_period)
+                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite, sigma_period=sigma_period,
+                                 compute_post_cov=compute_post_cov)
         # sigma_period = m > 1 (online): every m-th call refreshes every instance's Sigma, the calls between shift the last factors; the
         # batch shares one age: self.sigma_age is the age the last call ran at (0 = refresh), reset() restarts the schedule
         # elite = K: after a call, self.elite [E, 8] holds every instance's selector row of that step: {bits(threshold cost word),
@@ -80,6 +85,9 @@ class BatchedCoVOController:
         # compute_fan = K: after a call, self.fan [E, K, 100] holds every instance's fan of that step: rows {cost_s, bits(n_s), 0, 0,
         # pos_s[H][3]} of the samples self.core.fan_idx [E, K] names (include/covo_hip.h)
         self.fan = self.core.fan
+        # compute_post_cov: after a call, self.post_cov [E, 128, 128] holds every instance's posterior covariance of that step and
+        # self.post_aux [E, 132] its {shift d[128], W, 0, 0, 0} (include/covo_hip.h); None without it
+        self.post_cov, self.post_aux = self.core.post_cov, self.core.post_aux
         # ess_min: after a call, self.lam_eff [E, 4] holds every instance's {lam_eff, 1 / lam_eff, ESS(lam), evaluations} of that step
         self.lam_eff = self.core.lam_eff
         self.diag = self.core.diag
@@ -257,7 +265,8 @@ class BatchedMPPIController(BatchedCoVOController):
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1):
+                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
+                 compute_post_cov: bool = False):
         _lib.check_sigma_period(sigma_period, "the env-batched MPPI controller")
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
@@ -268,7 +277,7 @@ class BatchedMPPIController(BatchedCoVOController):
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
                          a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                         compute_fan=compute_fan, update=update, iters=iters, elite=elite)
+                         compute_fan=compute_fan, update=update, iters=iters, elite=elite, compute_post_cov=compute_post_cov)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

@@ -33,7 +33,8 @@ class MPPIParams:
 class MPPIController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, *, device=None, process_group=None,
                  compute_info: bool = True, propagate_nan=None, compute_diag: bool = False, compute_plan: bool = False,
-                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1) -> None:
+                 ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
+                 compute_post_cov: bool = False) -> None:
         from .. import _lib
         _lib.check_sigma_period(sigma_period, "MPPI")  # ValueError before anything is built (MPPI computes no Sigma per step)
         _lib.check_fan(compute_fan, N)
@@ -52,7 +53,7 @@ class MPPIController(BaseController):
                                  compute_info=compute_info, trust_clipped=True,
                                  cov_records=float(getattr(control_params, "gamma_sigma", 0.0)) != 0.0, propagate_nan=propagate_nan,
                                  compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite)
+                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite, compute_post_cov=compute_post_cov)
 
     def _check_gamma_sigma(self, control_params):
         """A controller built with gamma_sigma = 0 exchanges the 516-float records: on sharded ranks a later gamma_sigma != 0 needs

@@ -114,6 +114,7 @@ int covo_destroy(covo_handle_t h)
     step_state_destroy(h);
     batch_state_destroy(h);
     after_state_destroy(h);
+    post_cov_state_destroy(h);
     exchange_destroy(h);
     int rc = 0;
 #define DESTROY(expr)                                                                                   \
@@ -864,6 +865,51 @@ int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride)
     return 0;
 }
 
+// ---- the posterior covariance (post_cov.hip).  Like the plan's and the fan's, its launches are eager and follow the step: no captured
+// step graph changes.  The stage-1 partials of n_inst instances are reserved here, so that no step allocates
+int covo_set_step_post_cov(covo_handle_t h, float *cov, float *aux, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_post_cov: null handle");
+    if (cov == nullptr) {  // off
+        h->post_cov_out = h->post_aux_out = nullptr;
+        h->post_n = 0;
+        return 0;
+    }
+    REQUIRE(aux != nullptr, "covo_set_step_post_cov: aux is null (float[n_inst][%d])", COVO_POST_AUX_FLOATS);
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_post_cov: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    CHECK_DEVICE(h, "covo_set_step_post_cov");
+    if (int rc = post_cov_reserve(h, n_inst)) return rc;
+    h->post_cov_out = cov;
+    h->post_aux_out = aux;
+    h->post_n = n_inst;
+    return 0;
+}
+
+int covo_weighted_cov(covo_handle_t h, const float *a, const float *cost, const float *mu, int32_t n_samples, int32_t n_inst, float lam,
+                      int32_t elite_K, float *cov_out, float *aux_out, void *stream)
+{
+    REQUIRE(h, "covo_weighted_cov: null handle");
+    CHECK_DEVICE(h, "covo_weighted_cov");
+    REQUIRE(a && cost && mu && cov_out && aux_out, "covo_weighted_cov: null buffer");
+    REQUIRE(n_samples > 0, "covo_weighted_cov: n_samples=%d", n_samples);
+    REQUIRE(n_inst > 0 && n_inst <= 65535, "covo_weighted_cov: n_inst=%d outside (0, 65535]", n_inst);
+    REQUIRE(((uintptr_t)a & 15) == 0, "covo_weighted_cov: a must be 16-byte aligned");
+    REQUIRE(elite_K >= 0 && elite_K <= n_samples, "covo_weighted_cov: elite_K=%d outside [0, n_samples = %d]", elite_K, n_samples);
+    REQUIRE(elite_K == 0 || n_inst <= COVO_MAX_ENVS, "covo_weighted_cov: n_inst=%d above %d with an elite set", n_inst, COVO_MAX_ENVS);
+    REQUIRE(elite_K > 0 || (lam > 0.0f && lam < __builtin_inff()), "covo_weighted_cov: lam=%g", (double)lam);
+    PostCovDesc d;
+    d.a = a;
+    d.cost = cost;
+    d.mu = mu;
+    d.N = n_samples;
+    d.n_inst = n_inst;
+    d.lam = lam;
+    d.elite_K = elite_K;
+    d.cov_out = cov_out;
+    d.aux_out = aux_out;
+    return launch_weighted_cov(h, d, (hipStream_t)stream);
+}
+
 // ---- iterations per control step: K sample-rollout-update passes per call on the step's one state (step.hip enqueues them).  The
 // captured step graphs hold all K passes and the log's address: a change bumps the epoch like a debug switch
 int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t n_inst)
@@ -947,6 +993,9 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(covo_sigma_period(h) == 1,
                 "%s: the Sigma period (covo_set_step_sigma_period, period=%d) is not available for sample-sharded steps (partial_out != NULL): "
                 "every rank would have to keep and shift the same factor; set period = 1", what, covo_sigma_period(h));
+        REQUIRE(!covo_post_cov_on(h),
+                "%s: the posterior covariance (covo_set_step_post_cov) is not available for sample-sharded steps (partial_out != NULL): "
+                "a rank's action and cost buffers hold its shard only; detach the buffer", what);
     }
     REQUIRE(covo_diag_target(h) == nullptr || n_inst <= covo_diag_capacity(h),
             "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, n_inst, covo_diag_capacity(h));
@@ -985,6 +1034,8 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                 "computes no Sigma per step; set period = 1", what, covo_sigma_period(h), mode == COVO_MODE_MPPI ? "MPPI" : "covo-offline");
         REQUIRE(((uintptr_t)a_cov & 15) == 0, "%s: a_cov must be 16-byte aligned under a Sigma period (covo_set_step_sigma_period)", what);
     }
+    REQUIRE(!covo_post_cov_on(h) || n_inst <= h->post_n, "%s: %d instances, the posterior covariance buffer (covo_set_step_post_cov) has "
+            "n_inst=%d", what, n_inst, h->post_n);
     return 0;
 }
 
@@ -1207,6 +1258,10 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
             "%s: iterations per step (covo_set_step_iters, iters=%d) together with the update arbiter (covo_set_step_arbiter) are not "
             "available for the env-batched MPPI / covo-offline step: its fused launch keeps each pass's starting mean in LDS only; "
             "detach one of them", what, covo_step_iters(h));
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || !covo_post_cov_on(h),
+            "%s: the posterior covariance (covo_set_step_post_cov) is not available for the env-batched MPPI / covo-offline step: its "
+            "one fused launch keeps the samples in LDS and never stores them, and there is no staged batched fallback; detach the "
+            "buffer", what);
     if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, what))) return rc;  // (batched steps derive their keys)
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);

@@ -93,7 +93,13 @@ struct covo_ctx {
     const float *sigma_L;     // the factor buffer (the single step's or the batch's) that holds the last step's L; null: none yet
     float sigma_L_sigma;      // the sample_sigma it was built for ...
     int sigma_L_n;            // ... and for how many instances
+    // the posterior covariance (covo_set_step_post_cov; post_cov.hip); post_cov_out null: off
+    float *post_cov_out;      // caller's [post_n][128][128]: instance e's weighted sample covariance of every step
+    float *post_aux_out;      // caller's [post_n][COVO_POST_AUX_FLOATS]: {shift d[128], W, 0, 0, 0}
+    int post_n;
+    void *post_cov;           // PostCovState (post_cov.hip): the stage-1 partials, the stand-alone entry's selector rows
 };
+static inline bool covo_post_cov_on(const covo_ctx *h) { return h->post_cov_out != nullptr; }
 // passes per control step of this handle (1: today's step) and where pass j of instance 0 logs its cost minimum (instance e: + e * iters)
 static inline int covo_sigma_period(const covo_ctx *h) { return h->sigma_period > 1 ? h->sigma_period : 1; }
 // the age this covo-online step of n_inst instances runs at, given where its factor lives: 0 (refresh) unless the period is on, the
@@ -377,6 +383,25 @@ int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 int launch_merge_cov(const UpdateDesc &d, float lam, hipStream_t s);
 // the diagnostics of a covariance update: the G records of ws_partials_cov and ws_diag_rec -> diag_out (reduce.hip; N: the sample count)
 void launch_merge_cov_diag(covo_ctx *h, int G, float inv_lam, float *diag_out, int N, hipStream_t s);
+// post_cov.hip: the weighted 128 x 128 sample covariance of n_inst dense instances (covo_weighted_cov, covo_set_step_post_cov).  The
+// weights: elite_rows (the selector's rows of the step) or, with elite_rows null, elite_K > 0 (the selector runs first); else
+// lam_rows (the ESS solver's rows); else softmax at lam
+struct PostCovDesc {
+    const float *a = nullptr;     // [n_inst][H][N][4]
+    const float *cost = nullptr;  // [n_inst][N]
+    const float *mu = nullptr;    // [n_inst][128] the mean the samples were drawn around
+    int N = 0, n_inst = 1;
+    float lam = 0.0f;
+    const float *lam_rows = nullptr;
+    const float *elite_rows = nullptr;
+    int elite_K = 0;
+    float *cov_out = nullptr;     // [n_inst][128][128]
+    float *aux_out = nullptr;     // [n_inst][COVO_POST_AUX_FLOATS]
+};
+int launch_weighted_cov(covo_ctx *h, const PostCovDesc &d, hipStream_t s);
+int launch_post_cov_after(covo_ctx *h, const float *a, const float *cost, const float *mu, int N, int n_inst, hipStream_t s);
+int post_cov_reserve(covo_ctx *h, int n_inst);
+void post_cov_state_destroy(covo_ctx *h);
 int launch_shift_mean(const float *in, float *out, hipStream_t s);
 size_t hessian_workspace_bytes(int batch);
 struct SymStatsOut;  // sym_stats.hpp

@@ -1103,7 +1103,7 @@ static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, c
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                          const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
     // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
     // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
@@ -1115,14 +1115,16 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
     d.key[0] = key0;
     d.key[1] = key1;
     for (int c = 0; c < 3; ++c) d.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
-    return plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only);
+    if (int rc = plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only)) return rc;
+    // the posterior covariance: behind the (last pass's) update and the launches above; d.a_nominal is the mean that pass sampled around
+    return arbiter_only ? 0 : launch_post_cov_after(h, d.a, d.cost, d.a_nominal, d.N, 1, s);
 }
 
 // mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run) or MPPI / COVO_OFFLINE (covo_step_batched_small_impl)
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
                             const float *states_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
@@ -1139,7 +1141,9 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
                          nominal ? nominal + (size_t)e * COVO_NA : nullptr,
                          (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr,
                          online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e);
-    return plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only);
+    if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only)) return rc;
+    // the posterior covariance of every instance (covo-online only: check_batch_step): dense slices, the begin launch's shifted means
+    return arbiter_only ? 0 : launch_post_cov_after(h, args->a, args->cost, online ? b->a_mean_shift : nullptr, args->n_samples, E, s);
 }
 
 // test hook: the factor(s) the LAST single (batched = 0) / env-batched step sampled from -- what the next reuse step of a Sigma period

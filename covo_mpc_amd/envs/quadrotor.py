@@ -702,7 +702,7 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
-                   iters=1, elite=None, sigma_period=1):
+                   iters=1, elite=None, sigma_period=1, compute_post_cov=False):
     """quadrotor.py:670-752.  ess_min (sampling controllers): the ESS floor, see SamplingCore; compute_fan=K (sampling controllers): K
     sampled rollouts of every step in info["fan_pos"] / ["fan_cost"] / ["fan_idx"], see SamplingCore; update (sampling controllers):
     "softmax" (default) | "best" | "guarded" -- the update arbiter, info["arb_cost"] / ["arb_choice"] / ["arb_best"] /
@@ -710,7 +710,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     info["iter_cost_min"] [k], see SamplingCore; elite=K (sampling controllers): the elite-set update -- the K cheapest samples with
     weight 1, info["elite_cost_max"] / ["elite_cost_min"] / ["elite_count"], see SamplingCore; sigma_period=m (covo-online only): every
     m-th control step refreshes Sigma, the m - 1 between sample from the last factor shifted on the device, info["sigma_age"], see
-    SamplingCore."""
+    SamplingCore; compute_post_cov (sampling controllers): the weighted 128 x 128 covariance of every step's own samples under its own
+    update's weights, info["post_cov"] / ["post_shift"] / ["post_weight"], see SamplingCore."""
     import torch
     from .. import _lib
     _lib.check_update(update)
@@ -743,7 +744,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info,
                                           compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                          compute_fan=compute_fan, update=update, iters=iters, elite=elite), control_params
+                                          compute_fan=compute_fan, update=update, iters=iters, elite=elite,
+                                          compute_post_cov=compute_post_cov), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -757,7 +759,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                           device=device, process_group=process_group,
                                           compute_info=compute_info, compute_diag=compute_diag,
                                           compute_plan=compute_plan, ess_min=ess_min, compute_fan=compute_fan,
-                                          update=update, iters=iters, elite=elite, sigma_period=sigma_period), control_params
+                                          update=update, iters=iters, elite=elite, sigma_period=sigma_period,
+                                          compute_post_cov=compute_post_cov), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -768,7 +771,9 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
     including the step whose `done` fires (`repeat_times` of them).  The dicts are keyed by EnvState3D's field names (s.__dict__,
     :656; the device handle `traj_dev` left out) plus `reward`, and -- under a controller built with compute_plan -- `u`,
     `pos_plan` [H, 3] and `cost_plan`: the action the step applied and the controller's own plan (include/covo_hip.h); under one built with compute_fan=K also
-    `fan_pos` [K, H, 3], `fan_cost` [K] and `fan_idx` [K]: K of the step's sampled rollouts around that plan.  No plotting
+    `fan_pos` [K, H, 3], `fan_cost` [K] and `fan_idx` [K]: K of the step's sampled rollouts around that plan; under one built with
+    compute_post_cov also `post_cov` [128, 128] and `post_shift` [128] (such a controller takes the host path: the episode drivers keep
+    no log of the matrices).  No plotting
     (utils.plot_states, :661, stays out of scope).
     Host path (controllers without a `core` or without compute_plan, host_env=True, repeat_times > 1): the Python loop with the
     reference's per-step keys (rng, rng_act, rng_step = split(rng, 3), :617); on `done` the parameters are re-sampled and the
@@ -785,7 +790,7 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
     rng, rng_reset = crandom.split(rng)
     core = getattr(controller, "core", None)
     device_path = (not host_env and repeat_times == 1 and core is not None and getattr(core, "compute_plan", False)
-                   and hasattr(controller, "run_episode") and core.world == 1)
+                   and hasattr(controller, "run_episode") and core.world == 1 and not getattr(core, "compute_post_cov", False))
     t0 = time_module.time()
     seq = []
     if device_path:
@@ -825,6 +830,8 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
             if isinstance(control_info, dict) and "fan_pos" in control_info:
                 d.update(fan_pos=to_np(control_info["fan_pos"]).copy(), fan_cost=to_np(control_info["fan_cost"]).copy(),
                          fan_idx=to_np(control_info["fan_idx"]).copy())
+            if isinstance(control_info, dict) and "post_cov" in control_info:
+                d.update(post_cov=to_np(control_info["post_cov"]).copy(), post_shift=to_np(control_info["post_shift"]).copy())
             seq.append(d)
             if done:
                 rng, rng_params = crandom.split(rng)
@@ -862,6 +869,7 @@ class Args:
     iters: int = 1          # (not in quadjax) the sampling controllers' sample-rollout-update passes per control step; 1 = one pass
     elite: int = 0          # (not in quadjax) the sampling controllers' elite-set update: the K cheapest samples with weight 1; 0 = off
     sigma_period: int = 1   # (not in quadjax) covo-online: every m-th control step refreshes Sigma, the others shift the last factor; 1 = off
+    post_cov: bool = False  # (not in quadjax) render: the posterior covariance of every step next to the plan (compute_post_cov)
 
 
 def main(args: Args):
@@ -876,7 +884,7 @@ def main(args: Args):
     controller, control_params = get_controller(env, args.controller, args.controller_params, compute_info=args.mode != "eval",
                                                 compute_plan=render, compute_fan=(args.fan or None) if render else None,
                                                 update=args.update, iters=args.iters, elite=args.elite or None,
-                                                sigma_period=args.sigma_period)
+                                                sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -891,7 +899,9 @@ def main(args: Args):
 def _cli():
     ap = argparse.ArgumentParser(description="quadjax-compatible driver (same flag names as quadrotor.py:755-766)")
     for f, default in Args().__dict__.items():
-        if isinstance(default, bool):
+        if f == "post_cov":
+            ap.add_argument("--post-cov", "--post_cov", dest="post_cov", action="store_true")
+        elif isinstance(default, bool):
             ap.add_argument(f"--{f}", action="store_true")
         elif f == "update":
             ap.add_argument("--update", choices=("softmax", "best", "guarded"), default=default)

@@ -641,6 +641,32 @@ int covo_set_step_sigma_period(covo_handle_t h, int32_t period);
 int covo_step_sigma_age(covo_handle_t h, int32_t *next_age, int32_t *last_age);
 int covo_sigma_shift(covo_handle_t h, const float *L_in, int32_t batch, float sample_sigma, float *Sigma_out, float *L_out, void *stream);
 int covo_debug_sigma_factor(covo_handle_t h, int32_t batched, float *out, int64_t count, void *stream);
+
+/* The posterior covariance: the weighted 128 x 128 sample covariance of a step's own samples under the step's own weights (additive
+ * to ABI 10: COVO_HAS_POST_COV; off by default, and off changes nothing a caller can observe: no launch is added).  Per instance, with
+ *   x_i[4 t + d] = a[t][i][d]  the step's clipped samples, the ones its update used,
+ *   mu                         the mean the step sampled around (the shifted mean; a later pass of an iterated step: the mean the pass
+ *                              before it committed),
+ *   w_i                        the weight the step's own update gave sample i -- exp(-(c_i - c_min) / lam), at lam_eff under the ESS
+ *                              floor, 1 on the selector's set and 0 elsewhere under the elite-set update -- and 0 for a cost that is
+ *                              not finite,
+ *   W = sum w_i, y_i = x_i - mu, d = sum w_i y_i / W:      C = sum w_i y_i y_i^T / W - d d^T.
+ * C is symmetric bit for bit; mu + d is the softmax mean the step forms at gamma_mean = 1; W = 0 gives C = 0 and d = 0.  For a locally
+ * quadratic cost with Hessian H and samples from N(mu, Sigma), C estimates (Sigma^-1 + H / lam)^-1.
+ * covo_set_step_post_cov: cov = DEVICE float[n_inst][128][128] (NULL = off), aux = DEVICE float[n_inst][COVO_POST_AUX_FLOATS]:
+ *   {d[128], W, 0, 0, 0}.  Every later step of the handle fills row e with instance e's matrix by two eager launches behind the step
+ *   and its update arbiter, plan and fan launches (no captured step graph changes); under iterations per step the last pass's.  Refused
+ *   before any launch, at the step: a sample-sharded step (partial_out != NULL); the env-batched MPPI / covo-offline step
+ *   (covo_mpc_step_batched_mode, covo_run_episode_batched_mode), whose one fused launch keeps the samples in LDS; more instances than
+ *   n_inst.
+ * covo_weighted_cov: the same two launches on the caller's buffers.  a = DEVICE float[n_inst][H][n_samples][4] (16-byte aligned), cost =
+ *   DEVICE float[n_inst][n_samples], mu = DEVICE float[n_inst][128]; elite_K = 0: softmax weights at lam > 0; 1 <= elite_K <= n_samples:
+ *   the elite set of covo_elite_select (lam is not read; n_inst <= COVO_MAX_ENVS). */
+#define COVO_HAS_POST_COV 1
+#define COVO_POST_AUX_FLOATS 132
+int covo_set_step_post_cov(covo_handle_t h, float *cov, float *aux, int32_t n_inst);
+int covo_weighted_cov(covo_handle_t h, const float *a, const float *cost, const float *mu, int32_t n_samples, int32_t n_inst, float lam,
+                      int32_t elite_K, float *cov_out, float *aux_out, void *stream);
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
