@@ -44,6 +44,8 @@ COVO_HAS_SIGMA_PERIOD = 1
 COVO_MAX_SIGMA_PERIOD = 64  # sigma_period= of the covo-online controllers: every m-th step refreshes Sigma (covo_set_step_sigma_period)
 COVO_HAS_POST_COV = 1
 COVO_POST_AUX_FLOATS = 132  # the posterior covariance's side row of one instance: {shift d[128], W, 0, 0, 0} (covo_set_step_post_cov)
+COVO_HAS_SIGMA_ADAPT = 1
+COVO_SIGMA_ADAPT_FLOATS = 4  # Sigma adapt's row of one instance: {fallback, c, log det M, 0} (covo_set_step_sigma_adapt)
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -183,6 +185,8 @@ _SIGS = {
     "covo_debug_sigma_factor": (C.c_int, [_P, C.c_int32, _P, C.c_int64, _P]),
     "covo_set_step_post_cov": (C.c_int, [_P, _P, _P, C.c_int32]),  # the posterior covariance (covo_hip.h: COVO_HAS_POST_COV)
     "covo_weighted_cov": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P]),
+    "covo_set_step_sigma_adapt": (C.c_int, [_P, C.c_float, _P, C.c_int32]),  # Sigma adapt (covo_hip.h: COVO_HAS_SIGMA_ADAPT)
+    "covo_sigma_adapt": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P]),
     "covo_set_step_plan": (C.c_int, [_P, _P, C.c_int32]),             # the flight recorder (covo_hip.h: COVO_HAS_PLAN_TRACE)
     "covo_set_episode_trace": (C.c_int, [_P, _P, C.c_int32]),
     "covo_rollout_fan": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P,
@@ -302,6 +306,27 @@ def check_sigma_period(sigma_period, mode="online") -> int:
         raise ValueError(f"sigma_period={m} with {mode}: the Sigma period belongs to covo-online, the one mode that computes a Sigma per "
                          "step (CoVOController(mode=\"online\"), BatchedCoVOController(mode=\"online\")); give sigma_period=1")
     return m
+
+
+def check_sigma_adapt(sigma_adapt, sigma_period=None, mode="online") -> float:
+    """sigma_adapt= of the controllers -> gamma, the weight of the posterior covariance in a reuse step's Sigma': a real number in
+    [0, 1) (0.0, the default: off); anything else raises ValueError.  gamma > 0 with a mode other than "online" raises ValueError --
+    only covo-online has reuse steps -- and so does gamma > 0 with sigma_period == 1 (given): every step refreshes, nothing would
+    ever adapt."""
+    import math
+    import numbers
+    if (isinstance(sigma_adapt, bool) or not isinstance(sigma_adapt, numbers.Real) or math.isnan(float(sigma_adapt)) or
+            not 0.0 <= float(sigma_adapt) < 1.0):
+        raise ValueError(f"sigma_adapt={sigma_adapt!r} outside [0, 1) (the weight gamma of the posterior covariance in a reuse step's "
+                         "Sigma', a real number; 0 = off)")
+    g = float(sigma_adapt)
+    if g > 0.0 and mode != "online":
+        raise ValueError(f"sigma_adapt={g} with {mode}: Sigma adapt belongs to the reuse steps of covo-online "
+                         "(CoVOController(mode=\"online\"), BatchedCoVOController(mode=\"online\")); give sigma_adapt=0")
+    if g > 0.0 and sigma_period is not None and int(sigma_period) == 1:
+        raise ValueError(f"sigma_adapt={g} with sigma_period=1: every step refreshes Sigma and nothing would ever adapt; give "
+                         "sigma_period > 1 or sigma_adapt=0")
+    return g
 
 
 def ptr(t):

@@ -54,9 +54,11 @@ class SamplingCore:
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
-                 sigma_period: int = 1, compute_post_cov: bool = False):
+                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0):
         import torch
         sigma_period = _lib.check_sigma_period(sigma_period)
+        sigma_adapt = _lib.check_sigma_adapt(sigma_adapt, sigma_period)
+        compute_post_cov = bool(compute_post_cov) or sigma_adapt > 0.0  # a reuse step reads the previous step's posterior covariance
         fan_K = _lib.check_fan(compute_fan, N)
         arb_mask = _lib.check_update(update)
         iters = _lib.check_iters(iters)
@@ -78,6 +80,8 @@ class SamplingCore:
                               "(covo_set_step_elite refuses sample-sharded steps)"),
                     (sigma_period > 1, f"sigma_period={sigma_period} on sample-sharded ranks: every rank would have to keep and shift "
                                        "the same factor (covo_set_step_sigma_period refuses sample-sharded steps)"),
+                    (sigma_adapt > 0.0, f"sigma_adapt={sigma_adapt} on sample-sharded ranks: it needs the Sigma period and the posterior "
+                                        "covariance (covo_set_step_sigma_adapt refuses sample-sharded steps)"),
                     (compute_post_cov, "compute_post_cov on sample-sharded ranks: a rank's action and cost buffers hold its shard "
                                        "only (covo_set_step_post_cov refuses sample-sharded steps)")):
                 if is_on and sharded:
@@ -257,6 +261,17 @@ class SamplingCore:
             self.post_aux = torch.zeros((rows, _lib.COVO_POST_AUX_FLOATS), **f32)
             with torch.cuda.device(self.device):
                 check(self.lib.covo_set_step_post_cov(self.h, ptr(self.post_cov), ptr(self.post_aux), rows), "covo_set_step_post_cov")
+        # sigma_adapt = gamma in (0, 1) (covo-online under a Sigma period): a reuse step samples from the shifted blend
+        # c ((1 - gamma) S(Sigma) + gamma S(C)) of the covariance the previous step sampled from and the posterior covariance C it left
+        # in self.post_cov (covo_set_step_sigma_adapt, csrc/sigma_adapt.hip); self.sigma_adapt_rows [rows, 4] = {fallback, c,
+        # log det M, 0} of every instance's last step ({0, 1, 0, 0} after a refresh step); 0.0 (default): nothing attached
+        self.sigma_adapt_gamma = sigma_adapt
+        self.sigma_adapt_rows = None
+        if sigma_adapt > 0.0:
+            self.sigma_adapt_rows = torch.zeros((int(diag_rows), _lib.COVO_SIGMA_ADAPT_FLOATS), **f32)
+            self.sigma_adapt_rows[:, 1] = 1.0
+            check(self.lib.covo_set_step_sigma_adapt(self.h, sigma_adapt, ptr(self.sigma_adapt_rows), int(diag_rows)),
+                  "covo_set_step_sigma_adapt")
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -393,11 +408,11 @@ class SamplingCore:
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
-        lam_info (ess_min), arbiter_info (update), iter_info (iters), elite_info (elite) and post_cov_info (compute_post_cov) -- views of
-        the core's buffers, no sync, no copy."""
+        lam_info (ess_min), arbiter_info (update), iter_info (iters), elite_info (elite), post_cov_info (compute_post_cov) and
+        sigma_adapt_info (sigma_adapt) -- views of the core's buffers, no sync, no copy."""
         out = {}
         for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info, self.elite_info,
-                     self.sigma_info, self.post_cov_info):
+                     self.sigma_info, self.post_cov_info, self.sigma_adapt_info):
             out.update(info())
         return out
 
@@ -589,6 +604,46 @@ class SamplingCore:
               "covo_sigma_shift")
         return Sigma_out, L_out
 
+    def sigma_adapt_info(self) -> dict:
+        """{"sigma_adapt_fallback" (1: the blend was not positive definite and the step took the plain shift), "sigma_adapt_scale" (c)}
+        of the last step as 0-d views of self.sigma_adapt_rows (no sync, no copy); 0 and 1 after a refresh step; {} when the core was
+        built with sigma_adapt=0."""
+        if self.sigma_adapt_rows is None:
+            return {}
+        return {"sigma_adapt_fallback": self.sigma_adapt_rows[0, 0], "sigma_adapt_scale": self.sigma_adapt_rows[0, 1]}
+
+    def set_sigma_adapt(self, gamma: float):
+        """Another gamma (0 = off) from the next step on, on a core built with sigma_adapt > 0 (it owns the rows and the posterior
+        covariance target); the age goes back to 0 and the step graphs are captured again."""
+        g = _lib.check_sigma_adapt(gamma, self.sigma_period)
+        if self.sigma_adapt_rows is None:
+            raise ValueError("set_sigma_adapt: the core was built with sigma_adapt=0 (no rows, no posterior covariance target)")
+        rows = self.sigma_adapt_rows
+        check(self.lib.covo_set_step_sigma_adapt(self.h, g, ptr(rows) if g > 0.0 else None, int(rows.shape[0]) if g > 0.0 else 0),
+              "covo_set_step_sigma_adapt")
+        self.sigma_adapt_gamma = g
+
+    def sigma_adapt(self, L, C, gamma, sample_sigma=0.5, L_out=None):
+        """covo_sigma_adapt (the stand-alone covariance of a reuse step that adapts): L, C float32 device tensors [128, 128] or
+        [E, 128, 128] -- the lower Cholesky factor of Sigma and a posterior covariance (the lower triangles are read) -- and
+        0 <= gamma < 1 -> (Sigma', L', rows): Sigma' = c ((1 - gamma) S(L L^T) + gamma S(C)) with the Sigma period's shift S and c such
+        that log det Sigma' = 2 n log sample_sigma, its lower factor, and rows [E, 4] = {fallback, c, log det M, 0} ([4] for one
+        matrix); an instance whose blend is not positive definite gets its gamma = 0 result and fallback = 1 (include/covo_hip.h).
+        L_out: where L' goes (may be L itself)."""
+        torch = self.torch
+        g = _lib.check_sigma_adapt(gamma)
+        for t in (L, C):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape[-2:]) == (COVO_NA, COVO_NA)
+        assert L.shape == C.shape
+        E = 1 if L.dim() == 2 else int(L.shape[0])
+        Sigma_out = torch.empty_like(L)
+        L_out = torch.empty_like(L) if L_out is None else L_out
+        rows = torch.empty((E, _lib.COVO_SIGMA_ADAPT_FLOATS), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_sigma_adapt(self.h, ptr(L), ptr(C), E, g, float(sample_sigma), ptr(Sigma_out), ptr(L_out), ptr(rows),
+                                            self.stream()), "covo_sigma_adapt")
+        return Sigma_out, L_out, (rows[0] if L.dim() == 2 else rows)
+
     def elite_select(self, cost, K):
         """covo_elite_select (the stand-alone selector): cost float32 device tensor [N] or [E, N] -> float32 [E, 8] rows
         {bits(threshold cost word), bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0}; the elite set of
@@ -619,6 +674,9 @@ class SamplingCore:
     def require_fused_for_diag(self):
         if getattr(self, "sigma_period", 1) > 1:
             raise NotImplementedError(f"sigma_period={self.sigma_period} acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
+                                      "(materialize_eps / noise_stream='jax') computes its Sigma in every step")
+        if getattr(self, "sigma_adapt_gamma", 0.0) > 0.0:  # (the attribute: core.sigma_adapt is the stand-alone kernel's method)
+            raise NotImplementedError(f"sigma_adapt={self.sigma_adapt_gamma} acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
                                       "(materialize_eps / noise_stream='jax') computes its Sigma in every step")
         if self.ess_min != 0.0:
             raise NotImplementedError("ess_min acts in the fused step (covo_mpc_step); the kernel-by-kernel path "

@@ -30,9 +30,11 @@ class BatchedCoVOController:
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
-                 sigma_period: int = 1, compute_post_cov: bool = False):
-        _lib.check_sigma_period(sigma_period, "online" if (self.MODE is None and mode == "online") else
-                                "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
+                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0):
+        what = ("online" if (self.MODE is None and mode == "online") else
+                "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
+        _lib.check_sigma_period(sigma_period, what)
+        _lib.check_sigma_adapt(sigma_adapt, sigma_period, what)
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)
@@ -71,7 +73,11 @@ class BatchedCoVOController:
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min,
                                  compute_fan=compute_fan, update=update, iters=iters, elite=elite, sigma_period=sigma_period,
-                                 compute_post_cov=compute_post_cov)
+                                 compute_post_cov=compute_post_cov, sigma_adapt=sigma_adapt)
+        # sigma_adapt = gamma > 0 (online, sigma_period > 1): the reuse calls blend every instance's posterior covariance into the
+        # covariance they shift; after a call, self.sigma_adapt_rows [E, 4] holds every instance's {fallback, c, log det M, 0} of that
+        # step ({0, 1, 0, 0} after a refresh); None without it
+        self.sigma_adapt_rows = self.core.sigma_adapt_rows
         # sigma_period = m > 1 (online): every m-th call refreshes every instance's Sigma, the calls between shift the last factors; the
         # batch shares one age: self.sigma_age is the age the last call ran at (0 = refresh), reset() restarts the schedule
         # elite = K: after a call, self.elite [E, 8] holds every instance's selector row of that step: {bits(threshold cost word),
@@ -266,8 +272,9 @@ class BatchedMPPIController(BatchedCoVOController):
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
                  ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
-                 compute_post_cov: bool = False):
+                 compute_post_cov: bool = False, sigma_adapt: float = 0.0):
         _lib.check_sigma_period(sigma_period, "the env-batched MPPI controller")
+        _lib.check_sigma_adapt(sigma_adapt, sigma_period, "the env-batched MPPI controller")
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)

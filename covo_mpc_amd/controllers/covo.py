@@ -47,9 +47,10 @@ class CoVOController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, mode: str = "online", *, device=None,
                  process_group=None, compute_info: bool = True, propagate_nan=None, compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1,
-                 elite=None, sigma_period: int = 1, compute_post_cov: bool = False) -> None:
+                 elite=None, sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0) -> None:
         from .. import _lib
         _lib.check_sigma_period(sigma_period, mode if mode in ("online", "offline") else "online")  # ValueError before anything is built
+        _lib.check_sigma_adapt(sigma_adapt, sigma_period, mode if mode in ("online", "offline") else "online")
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)
@@ -75,7 +76,7 @@ class CoVOController(BaseController):
                                  compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan,
                                  compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
                                  compute_fan=compute_fan, update=update, iters=iters, elite=elite, sigma_period=sigma_period,
-                                 compute_post_cov=compute_post_cov)
+                                 compute_post_cov=compute_post_cov, sigma_adapt=sigma_adapt)
 
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start (covo-online; covo-offline's reset builds its table): with a Sigma period the schedule restarts -- the first

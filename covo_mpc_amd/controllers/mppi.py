@@ -34,9 +34,10 @@ class MPPIController(BaseController):
     def __init__(self, env, control_params, N: int, H: int, lam: float, *, device=None, process_group=None,
                  compute_info: bool = True, propagate_nan=None, compute_diag: bool = False, compute_plan: bool = False,
                  ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
-                 compute_post_cov: bool = False) -> None:
+                 compute_post_cov: bool = False, sigma_adapt: float = 0.0) -> None:
         from .. import _lib
         _lib.check_sigma_period(sigma_period, "MPPI")  # ValueError before anything is built (MPPI computes no Sigma per step)
+        _lib.check_sigma_adapt(sigma_adapt, sigma_period, "MPPI")
         _lib.check_fan(compute_fan, N)
         _lib.check_update(update)
         _lib.check_iters(iters)

@@ -882,6 +882,10 @@ int covo_set_step_post_cov(covo_handle_t h, float *cov, float *aux, int32_t n_in
     h->post_cov_out = cov;
     h->post_aux_out = aux;
     h->post_n = n_inst;
+    if (covo_sigma_adapt_on(h)) {  // a reuse step must never read a C that no step of this schedule wrote; its graph holds C's address
+        h->sigma_age = 0;
+        ++h->opt.epoch;
+    }
     return 0;
 }
 
@@ -960,6 +964,41 @@ int covo_sigma_shift(covo_handle_t h, const float *L_in, int32_t batch, float sa
     return launch_sigma_shift(L_in, batch, sample_sigma, Sigma_out, L_out, (hipStream_t)stream);
 }
 
+// ---- Sigma adapt (sigma_adapt.hip): a reuse step of the Sigma period blends the previous step's posterior covariance, which the
+// after-step frame left in the attached post_cov target, into the covariance it shifts.  The reuse step's captured graph holds gamma
+// and the rows' address: a change bumps the epoch like a debug switch; the schedule restarts.  What the step needs next to it (a
+// post_cov target, covo-online, a period above 1) is checked at the step (check_step_attachments)
+int covo_set_step_sigma_adapt(covo_handle_t h, float gamma, float *rows_out, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_sigma_adapt: null handle");
+    const bool on = rows_out != nullptr && gamma != 0.0f;
+    REQUIRE(!on || (gamma > 0.0f && gamma < 1.0f), "covo_set_step_sigma_adapt: gamma=%g outside (0, 1) (0 or rows_out = NULL: off)",
+            (double)gamma);
+    REQUIRE(!on || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_sigma_adapt: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(!on || ((uintptr_t)rows_out & 15) == 0, "covo_set_step_sigma_adapt: rows_out must be 16-byte aligned");
+    h->adapt_gamma = on ? gamma : 0.0f;
+    h->adapt_rows = on ? rows_out : nullptr;
+    h->adapt_n = on ? n_inst : 0;
+    h->sigma_age = 0;
+    ++h->opt.epoch;
+    return 0;
+}
+
+int covo_sigma_adapt(covo_handle_t h, const float *L_in, const float *C, int32_t batch, float gamma, float sample_sigma, float *Sigma_out,
+                     float *L_out, float *rows_out, void *stream)
+{
+    REQUIRE(h, "covo_sigma_adapt: null handle");
+    CHECK_DEVICE(h, "covo_sigma_adapt");
+    REQUIRE(L_in && C && Sigma_out && L_out && batch > 0 && batch <= 65535, "covo_sigma_adapt: bad argument");
+    REQUIRE(gamma >= 0.0f && gamma < 1.0f, "covo_sigma_adapt: gamma=%g outside [0, 1)", (double)gamma);
+    REQUIRE(sample_sigma > 0.0f && sample_sigma < __builtin_inff(), "covo_sigma_adapt: sample_sigma=%g", (double)sample_sigma);
+    REQUIRE((((uintptr_t)L_in | (uintptr_t)C | (uintptr_t)Sigma_out | (uintptr_t)L_out | (uintptr_t)rows_out) & 15) == 0,
+            "covo_sigma_adapt: L_in / C / Sigma_out / L_out / rows_out must be 16-byte aligned");
+    REQUIRE((const float *)Sigma_out != L_in && Sigma_out != L_out && (const float *)Sigma_out != C && (const float *)L_out != C,
+            "covo_sigma_adapt: Sigma_out must not be L_in, L_out or C, and L_out must not be C (L_out may be L_in)");
+    return launch_sigma_adapt(L_in, C, batch, gamma, sample_sigma, Sigma_out, L_out, rows_out, (hipStream_t)stream);
+}
+
 // ---- what a step checks about everything attached to its handle -- diagnostics, plan / trace, sample fan, update arbiter, ESS floor,
 // iterations, elite set -- for every entry point alike (covo_mpc_step, covo_run_episode and, through check_batch_step, the four env-batched
 // ones): a step of n_samples samples for n_inst instances.  The order is fixed: first what a sample-sharded step
@@ -996,6 +1035,10 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(!covo_post_cov_on(h),
                 "%s: the posterior covariance (covo_set_step_post_cov) is not available for sample-sharded steps (partial_out != NULL): "
                 "a rank's action and cost buffers hold its shard only; detach the buffer", what);
+        REQUIRE(!covo_sigma_adapt_on(h),
+                "%s: Sigma adapt (covo_set_step_sigma_adapt, gamma=%g) is not available for sample-sharded steps (partial_out != NULL): "
+                "it needs the Sigma period and the posterior covariance, which sample-sharded steps cannot have; turn it off (gamma = 0)",
+                what, (double)h->adapt_gamma);
     }
     REQUIRE(covo_diag_target(h) == nullptr || n_inst <= covo_diag_capacity(h),
             "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, n_inst, covo_diag_capacity(h));
@@ -1036,6 +1079,22 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
     }
     REQUIRE(!covo_post_cov_on(h) || n_inst <= h->post_n, "%s: %d instances, the posterior covariance buffer (covo_set_step_post_cov) has "
             "n_inst=%d", what, n_inst, h->post_n);
+    if (covo_sigma_adapt_on(h)) {  // a reuse step reads the previous step's posterior covariance
+        REQUIRE(mode == COVO_MODE_COVO_ONLINE,
+                "%s: Sigma adapt (covo_set_step_sigma_adapt, gamma=%g) belongs to the reuse steps of covo-online; this step's mode is %s, "
+                "which computes no Sigma per step; turn it off (gamma = 0)", what, (double)h->adapt_gamma,
+                mode == COVO_MODE_MPPI ? "MPPI" : "covo-offline");
+        REQUIRE(covo_sigma_period(h) > 1,
+                "%s: Sigma adapt (covo_set_step_sigma_adapt, gamma=%g) with a Sigma period of 1: every step refreshes Sigma and nothing "
+                "would ever adapt; set a period above 1 (covo_set_step_sigma_period) or turn it off (gamma = 0)", what,
+                (double)h->adapt_gamma);
+        REQUIRE(covo_post_cov_on(h),
+                "%s: Sigma adapt (covo_set_step_sigma_adapt, gamma=%g) without a posterior covariance target: a reuse step blends the "
+                "covariance the previous step left there; attach one (covo_set_step_post_cov) or turn it off (gamma = 0)", what,
+                (double)h->adapt_gamma);
+        REQUIRE(n_inst <= h->adapt_n, "%s: %d instances, the Sigma adapt rows (covo_set_step_sigma_adapt) have n_inst=%d", what, n_inst,
+                h->adapt_n);
+    }
     return 0;
 }
 

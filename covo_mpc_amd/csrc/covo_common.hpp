@@ -98,8 +98,13 @@ struct covo_ctx {
     float *post_aux_out;      // caller's [post_n][COVO_POST_AUX_FLOATS]: {shift d[128], W, 0, 0, 0}
     int post_n;
     void *post_cov;           // PostCovState (post_cov.hip): the stage-1 partials, the stand-alone entry's selector rows
+    // Sigma adapt (covo_set_step_sigma_adapt; sigma_adapt.hip); adapt_rows null: off
+    float adapt_gamma;        // the weight of the previous step's posterior covariance in a reuse step's Sigma', in (0, 1)
+    float *adapt_rows;        // caller's [adapt_n][COVO_SIGMA_ADAPT_FLOATS]: instance e's {fallback, c, log det M, 0} of every reuse step
+    int adapt_n;
 };
 static inline bool covo_post_cov_on(const covo_ctx *h) { return h->post_cov_out != nullptr; }
+static inline bool covo_sigma_adapt_on(const covo_ctx *h) { return h->adapt_rows != nullptr && h->adapt_gamma > 0.0f; }
 // passes per control step of this handle (1: today's step) and where pass j of instance 0 logs its cost minimum (instance e: + e * iters)
 static inline int covo_sigma_period(const covo_ctx *h) { return h->sigma_period > 1 ? h->sigma_period : 1; }
 // the age this covo-online step of n_inst instances runs at, given where its factor lives: 0 (refresh) unless the period is on, the
@@ -500,6 +505,12 @@ int launch_cholesky(const float *A, int n, int batch, float *L, hipStream_t s);
 // sigma_shift.hip: the covariance of a reuse step from the previous step's factor L_in [batch][128][128] (fp32, lower): L_out its
 // shifted, volume-normalised factor (may be L_in), Sigma_out = L_out L_out^T; all three 16-byte aligned
 int launch_sigma_shift(const float *L_in, int batch, float sample_sigma, float *Sigma_out, float *L_out, hipStream_t s);
+// sigma_adapt.hip: the same step with the previous step's posterior covariance C [batch][128][128] blended in at weight gamma in
+// [0, 1) (0: C is not read): Sigma' = c ((1 - gamma) S(L L^T) + gamma S(C)) and its factor; rows_out [batch][4] = {fallback, c,
+// log det M, 0} or null; L_out may be L_in; all 16-byte aligned
+int launch_sigma_adapt(const float *L_in, const float *C, int batch, float gamma, float sample_sigma, float *Sigma_out, float *L_out,
+                       float *rows_out, hipStream_t s);
+int launch_sigma_adapt_idle(float *rows_out, int n_inst, hipStream_t s);  // a refresh step's rows {0, 1, 0, 0}
 size_t env_step_inst_bytes(int n);
 void env_step_fill_inst(const covo_env_params *params, int n, void *out);  // host: EnvInst[n] (to be copied to the device)
 int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,

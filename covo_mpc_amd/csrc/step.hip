@@ -207,8 +207,14 @@ static int enqueue_online_chain(covo_ctx *h, const OnlineChainView &v, hipStream
     if (reuse) {
         // a reuse step of a Sigma period: no Hessian, no Sigma chain -- every instance's factor of the previous step is shifted in
         // place (sigma_shift.hip), a_cov is its Sigma', and the samples are drawn from it as covo-offline draws from a table row
-        // (in-kernel Philox); the later passes of an iterated step sample from the same L'
-        if (pass == 0 && (rc = launch_sigma_shift(v.L, v.E, v.sample_sigma, v.Sigma, v.L, s))) return rc;
+        // (in-kernel Philox); the later passes of an iterated step sample from the same L'.  Under covo_set_step_sigma_adapt the shift
+        // also blends in the posterior covariance the previous step's after-step launches left in the attached target (sigma_adapt.hip)
+        if (pass == 0) {
+            rc = covo_sigma_adapt_on(h) ? launch_sigma_adapt(v.L, h->post_cov_out, v.E, h->adapt_gamma, v.sample_sigma, v.Sigma, v.L,
+                                                             h->adapt_rows, s)
+                                        : launch_sigma_shift(v.L, v.E, v.sample_sigma, v.Sigma, v.L, s);
+            if (rc) return rc;
+        }
         return launch_noise_gemm(nd, s);
     }
     // the Hessian's last launch leaves the Sigma chain's input statistics in the chain's workspace: no prep launch
@@ -515,8 +521,9 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     // covo_set_step_sigma_period: the age this step runs at -- 0: today's step, which leaves its factor in st->L; else a reuse step
     const bool online = args->mode == COVO_MODE_COVO_ONLINE;
     const int age = online ? covo_sigma_step_age(h, st->L, args->sample_sigma, 1) : 0;
-    const int rc = step_enqueue_all(h, st, params, args, key0, key1, f_shared, s, age != 0);
+    int rc = step_enqueue_all(h, st, params, args, key0, key1, f_shared, s, age != 0);
     if (rc == 0 && online) covo_sigma_step_done(h, age, st->L, args->sample_sigma, 1);
+    if (rc == 0 && online && age == 0 && covo_sigma_adapt_on(h)) rc = launch_sigma_adapt_idle(h->adapt_rows, 1, s);  // (eager, behind the step)
     return rc;
 }
 
@@ -958,6 +965,7 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         [&](hipStream_t on, int j) { return batch_enqueue(h, b, *args, on, DebugMasks(), j, reuse); },
         [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, on, true); });
     if (rc == 0) covo_sigma_step_done(h, age, b->L, args->sample_sigma, E);
+    if (rc == 0 && !reuse && covo_sigma_adapt_on(h)) return launch_sigma_adapt_idle(h->adapt_rows, E, s);  // (eager, behind the step)
     return rc;
 }
 

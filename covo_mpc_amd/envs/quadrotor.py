@@ -561,7 +561,7 @@ class BatchedDeviceEpisode:
 
 def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H32_lam0.01", n_steps=None, seed: int = 1, device=None,
                      verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
-                     arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1):
+                     arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]; with trace=True
@@ -569,10 +569,12 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     rollouts of every step of every instance -- is appended to the returned tuple.  update: the controller's update rule ("softmax" |
     "best" | "guarded"); arbiter=True (with "best" / "guarded") appends ep.read_arbiter(), every step's arbiter row.  iters=k: k
     sample-rollout-update passes per control step (SamplingCore).  elite=K: the elite-set update with K elites per instance
-    (SamplingCore).  sigma_period=m: every m-th control step refreshes Sigma, the steps between shift the last factor (SamplingCore)."""
+    (SamplingCore).  sigma_period=m: every m-th control step refreshes Sigma, the steps between shift the last factor (SamplingCore).
+    sigma_adapt=gamma: those steps blend the posterior covariance into the covariance they shift (SamplingCore)."""
     from .. import _lib
     _lib.check_iters(iters)
     _lib.check_sigma_period(sigma_period)
+    _lib.check_sigma_adapt(sigma_adapt, sigma_period)
     if arbiter and update == "softmax":
         raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
@@ -585,7 +587,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                           sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device,
                                           compute_diag=diag, compute_plan=trace, compute_fan=fan, update=update, iters=iters,
-                                          elite=elite, sigma_period=sigma_period)
+                                          elite=elite, sigma_period=sigma_period, sigma_adapt=sigma_adapt)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
@@ -702,7 +704,7 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
-                   iters=1, elite=None, sigma_period=1, compute_post_cov=False):
+                   iters=1, elite=None, sigma_period=1, compute_post_cov=False, sigma_adapt=0.0):
     """quadrotor.py:670-752.  ess_min (sampling controllers): the ESS floor, see SamplingCore; compute_fan=K (sampling controllers): K
     sampled rollouts of every step in info["fan_pos"] / ["fan_cost"] / ["fan_idx"], see SamplingCore; update (sampling controllers):
     "softmax" (default) | "best" | "guarded" -- the update arbiter, info["arb_cost"] / ["arb_choice"] / ["arb_best"] /
@@ -711,11 +713,15 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     weight 1, info["elite_cost_max"] / ["elite_cost_min"] / ["elite_count"], see SamplingCore; sigma_period=m (covo-online only): every
     m-th control step refreshes Sigma, the m - 1 between sample from the last factor shifted on the device, info["sigma_age"], see
     SamplingCore; compute_post_cov (sampling controllers): the weighted 128 x 128 covariance of every step's own samples under its own
-    update's weights, info["post_cov"] / ["post_shift"] / ["post_weight"], see SamplingCore."""
+    update's weights, info["post_cov"] / ["post_shift"] / ["post_weight"], see SamplingCore; sigma_adapt=gamma in [0, 1) (covo-online
+    with sigma_period > 1): a reuse step samples from the shifted blend of the covariance the previous step sampled from and that
+    step's posterior covariance (it implies compute_post_cov), info["sigma_adapt_fallback"] / ["sigma_adapt_scale"], see SamplingCore."""
     import torch
     from .. import _lib
     _lib.check_update(update)
-    _lib.check_sigma_period(sigma_period, "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name)
+    online_name = "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name
+    _lib.check_sigma_period(sigma_period, online_name)
+    _lib.check_sigma_adapt(sigma_adapt, sigma_period, online_name)
     _lib.check_iters(iters)
 
     def parse_sample_params(param_text):
@@ -760,7 +766,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                           compute_info=compute_info, compute_diag=compute_diag,
                                           compute_plan=compute_plan, ess_min=ess_min, compute_fan=compute_fan,
                                           update=update, iters=iters, elite=elite, sigma_period=sigma_period,
-                                          compute_post_cov=compute_post_cov), control_params
+                                          compute_post_cov=compute_post_cov, sigma_adapt=sigma_adapt), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -870,6 +876,7 @@ class Args:
     elite: int = 0          # (not in quadjax) the sampling controllers' elite-set update: the K cheapest samples with weight 1; 0 = off
     sigma_period: int = 1   # (not in quadjax) covo-online: every m-th control step refreshes Sigma, the others shift the last factor; 1 = off
     post_cov: bool = False  # (not in quadjax) render: the posterior covariance of every step next to the plan (compute_post_cov)
+    sigma_adapt: float = 0.0  # (not in quadjax) covo-online under a Sigma period: the posterior covariance's weight in a reuse step's Sigma'; 0 = off
 
 
 def main(args: Args):
@@ -884,7 +891,8 @@ def main(args: Args):
     controller, control_params = get_controller(env, args.controller, args.controller_params, compute_info=args.mode != "eval",
                                                 compute_plan=render, compute_fan=(args.fan or None) if render else None,
                                                 update=args.update, iters=args.iters, elite=args.elite or None,
-                                                sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render)
+                                                sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render,
+                                                sigma_adapt=args.sigma_adapt)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -907,6 +915,8 @@ def _cli():
             ap.add_argument("--update", choices=("softmax", "best", "guarded"), default=default)
         elif f == "sigma_period":
             ap.add_argument("--sigma-period", "--sigma_period", dest="sigma_period", type=int, default=default)
+        elif f == "sigma_adapt":
+            ap.add_argument("--sigma-adapt", "--sigma_adapt", dest="sigma_adapt", type=float, default=default)
         else:
             ap.add_argument(f"--{f}", type=type(default), default=default)
     main(Args(**vars(ap.parse_args())))

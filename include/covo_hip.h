@@ -667,6 +667,36 @@ int covo_debug_sigma_factor(covo_handle_t h, int32_t batched, float *out, int64_
 int covo_set_step_post_cov(covo_handle_t h, float *cov, float *aux, int32_t n_inst);
 int covo_weighted_cov(covo_handle_t h, const float *a, const float *cost, const float *mu, int32_t n_samples, int32_t n_inst, float lam,
                       int32_t elite_K, float *cov_out, float *aux_out, void *stream);
+
+/* Sigma adapt: the reuse steps of a Sigma period blend the posterior covariance into the covariance they shift (additive to ABI 10:
+ * COVO_HAS_SIGMA_ADAPT; off by default, and off changes nothing a caller can observe: every launch is the one made without it).  With
+ * L the factor on the handle the previous step sampled from, Sigma = L L^T, C the posterior covariance the previous step's after-step
+ * launches left in the attached covo_set_step_post_cov target, S the shift of the Sigma period and 0 < gamma < 1, a reuse step samples
+ * from
+ *   Sigma' = c M,   M = (1 - gamma) S(Sigma) + gamma S(C),   c the scalar with log det Sigma' = 2 n log sample_sigma
+ * -- S applied to C exactly as to Sigma -- and L' is the lower Cholesky factor of Sigma' (sigma_adapt.hip: M formed in fp64 from the
+ * handle's L, never from the caller's a_cov; factored in LDS; L' and Sigma' rounded to fp32 once each).  This is the full-matrix form
+ * of MPPI's per-block gamma_sigma blend and of CMA's rank-mu update.  C is used as it stands: it is central about mu + d, the
+ * posterior mean at gamma_mean = 1, and no d d^T correction is made for gamma_mean != 1 or for an arbitrated mean.  The lower triangle
+ * of C is read, rows and columns 4 .. 127 of it.  W = 0 in the previous step gives C = 0 and hence the plain shift (c absorbs 1 - gamma).
+ * Guard: M is positive definite whenever C is positive semidefinite.  If the factorisation of M leaves a pivot that is not finite or
+ * not positive, or a log det that is not finite (C not finite, or indefinite), the instance's output is exactly that of gamma = 0,
+ * its row records the fallback, and the other instances of the batch are unaffected.  Refresh steps do not adapt.
+ * covo_set_step_sigma_adapt: 0 < gamma < 1 and rows_out = DEVICE float[n_inst][COVO_SIGMA_ADAPT_FLOATS] (16-byte aligned), instance
+ *   e's {fallback (0 / 1), c, log det M, 0} of every reuse step, {0, 1, 0, 0} after a refresh step; gamma = 0 or rows_out = NULL: off.
+ *   Sets the age to 0 and drops the captured step graphs; so does (re-)attaching the covo_set_step_post_cov target while it is on.
+ *   Refused before any launch, at the step: no covo_set_step_post_cov target, or fewer instances there or in rows_out than the step
+ *   has; a step whose mode is not covo-online; a sample-sharded step; a period of 1.  Under iterations per step the passes j >= 1
+ *   sample from the same L', and the next reuse step reads the last pass's C.
+ * covo_sigma_adapt: the kernel alone.  L_in, C = DEVICE float[batch][128][128] (the lower triangles are read), 0 <= gamma < 1 (0: C is
+ *   not read -- the fallback's own result, the same matrix as covo_sigma_shift's by another route), Sigma_out, L_out = DEVICE
+ *   float[batch][128][128], rows_out = DEVICE float[batch][COVO_SIGMA_ADAPT_FLOATS] or NULL, all 16-byte aligned; L_out may be L_in.
+ *   L_out's strict upper triangle and Sigma_out's cross block are exact zeros, Sigma_out is symmetric bit for bit. */
+#define COVO_HAS_SIGMA_ADAPT 1
+#define COVO_SIGMA_ADAPT_FLOATS 4
+int covo_set_step_sigma_adapt(covo_handle_t h, float gamma, float *rows_out /* DEVICE float[n_inst][4]; NULL = off */, int32_t n_inst);
+int covo_sigma_adapt(covo_handle_t h, const float *L_in, const float *C, int32_t batch, float gamma, float sample_sigma, float *Sigma_out,
+                     float *L_out, float *rows_out, void *stream);
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
