@@ -22,6 +22,12 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
+from ._options import check_kernel_path, check_step_options, sharded_refusal, take
+
+# the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
+# that attribute's value is the log's extra allocation argument: the fan's K)
+EPISODE_LOGS = {"diag_log": ("compute_diag", "covo_set_episode_diag_log", False), "trace": ("compute_plan", "covo_set_episode_trace", False),
+                "fanlog": ("compute_fan", "covo_set_episode_fan", True), "arblog": ("arb_mask", "covo_set_episode_arbiter_log", False)}
 
 
 def shard_range(N: int, rank: int, world: int):
@@ -55,37 +61,13 @@ class SamplingCore:
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0):
+        opts = take(locals())
         import torch
-        sigma_period = _lib.check_sigma_period(sigma_period)
-        sigma_adapt = _lib.check_sigma_adapt(sigma_adapt, sigma_period)
-        compute_post_cov = bool(compute_post_cov) or sigma_adapt > 0.0  # a reuse step reads the previous step's posterior covariance
-        fan_K = _lib.check_fan(compute_fan, N)
-        arb_mask = _lib.check_update(update)
-        iters = _lib.check_iters(iters)
-        elite_K = _lib.check_elite(elite, N, ess_min)
-        if process_group is not None:  # what sample-sharded ranks cannot have, refused before the device is looked for
+        sharded = False
+        if process_group is not None:  # what sample-sharded ranks cannot have is refused before the device is looked for
             import torch.distributed as dist
             sharded = dist.get_world_size(process_group) > 1
-            for is_on, message in (
-                    (iters > 1, f"iters={iters} on sample-sharded ranks: every pass would need its own exchange of the rank "
-                                "records (covo_set_step_iters refuses sample-sharded steps)"),
-                    (arb_mask, f"update={update!r} on sample-sharded ranks: a rank's action and cost buffers hold its shard "
-                               "only (covo_set_step_arbiter refuses sample-sharded steps)"),
-                    (fan_K, "compute_fan on sample-sharded ranks: a rank's action buffer holds its shard only "
-                            "(covo_set_step_fan refuses sample-sharded steps)"),
-                    (ess_min is not None and float(ess_min) != 0.0,
-                     f"ess_min={ess_min} on sample-sharded ranks: a rank sees only its shard's costs "
-                     "(covo_set_step_ess_floor refuses sample-sharded steps)"),
-                    (elite_K, f"elite={elite_K} on sample-sharded ranks: a rank sees only its shard's costs "
-                              "(covo_set_step_elite refuses sample-sharded steps)"),
-                    (sigma_period > 1, f"sigma_period={sigma_period} on sample-sharded ranks: every rank would have to keep and shift "
-                                       "the same factor (covo_set_step_sigma_period refuses sample-sharded steps)"),
-                    (sigma_adapt > 0.0, f"sigma_adapt={sigma_adapt} on sample-sharded ranks: it needs the Sigma period and the posterior "
-                                        "covariance (covo_set_step_sigma_adapt refuses sample-sharded steps)"),
-                    (compute_post_cov, "compute_post_cov on sample-sharded ranks: a rank's action and cost buffers hold its shard "
-                                       "only (covo_set_step_post_cov refuses sample-sharded steps)")):
-                if is_on and sharded:
-                    raise NotImplementedError(message)
+        opt = check_step_options(N, "online", sharded=sharded, **opts)
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -170,108 +152,59 @@ class SamplingCore:
         self.stats = self.record[n_part:].view(torch.float64)  # this shard's sums (528- / 1 808-byte offset: 8-aligned)
         self.gathered = torch.zeros((self.world * self.rec_floats,), **f32) if self.world > 1 else None
         self.stats_total = torch.zeros((COVO_POS_STATS_DOUBLES,), dtype=torch.float64, device=self.device) if self.world > 1 else self.stats
-        # compute_diag: every step also leaves its sampling diagnostics {ess, cost_min, cost_weighted, cost_mean, weight_sum,
-        # n_samples, 0, 0} in self.diag (row e = instance e of a batched step) -- formed by the update's own launches
-        # (covo_set_step_diag); off by default, and off changes nothing
-        self.compute_diag = bool(compute_diag)
-        self.diag = None
-        if self.compute_diag:
-            if self.world > 1:
-                raise NotImplementedError("compute_diag on sample-sharded ranks: the rank records carry no diagnostic sums "
-                                          "(covo_set_step_diag refuses sample-sharded steps)")
-            self.diag = torch.zeros((int(diag_rows), _lib.COVO_DIAG_FLOATS), **f32)
-            check(self.lib.covo_set_step_diag(self.h, ptr(self.diag), int(diag_rows)), "covo_set_step_diag")
-        # compute_plan: every step also leaves its plan -- the rollout of the new mean itself with the step's own inputs, {cost_plan,
-        # 0, 0, 0, pos_plan[H][3]} -- in self.plan (row e = instance e of a batched step), by one extra launch behind the step
-        # (covo_set_step_plan, csrc/plan_trace.hip); off by default, and off changes nothing
-        self.compute_plan = bool(compute_plan)
-        self.plan = None
-        if self.compute_plan:
-            if self.world > 1:
-                raise NotImplementedError("compute_plan on sample-sharded ranks: a rank holds only its shard's record until the "
-                                          "exchange (covo_set_step_plan refuses sample-sharded steps)")
-            self.plan = torch.zeros((int(diag_rows), _lib.COVO_PLAN_FLOATS), **f32)
-            check(self.lib.covo_set_step_plan(self.h, ptr(self.plan), int(diag_rows)), "covo_set_step_plan")
-        # compute_fan = K: every step also leaves K of its N sampled rollouts -- rows {cost_s, bits(n_s), 0, 0, pos_s[H][3]} of the
-        # samples self.fan_idx names (pre-filled with the stride (s N) / K; a caller may overwrite it between steps; the launch clamps
-        # it into [0, N)) -- in self.fan (row e = instance e of a batched step), by one extra launch behind the step
-        # (covo_set_step_fan, csrc/sample_fan.hip); off by default, and off changes nothing
-        self.compute_fan = fan_K
+        # the step options' attachments (what each option does: _options.py).  Every buffer holds one row per instance of an env-batched
+        # step (diag_rows; 1 for a single controller), stays None while its option is off, and is written by the step's own launches
+        self._rows = int(diag_rows)
+        # self.diag [rows, 8]: {ess, cost_min, cost_weighted, cost_mean, weight_sum, n_samples, 0, 0}
+        self.compute_diag = opt.diag
+        self.diag = self._attach_rows(_lib.COVO_DIAG_FLOATS, "covo_set_step_diag") if opt.diag else None
+        # self.plan [rows, 100]: {cost_plan, 0, 0, 0, pos_plan[H][3]}
+        self.compute_plan = opt.plan
+        self.plan = self._attach_rows(_lib.COVO_PLAN_FLOATS, "covo_set_step_plan") if opt.plan else None
+        # self.fan [rows, K, 100]: rows {cost_s, bits(n_s), 0, 0, pos_s[H][3]} of the samples self.fan_idx [rows, K] (int32) names
+        self.compute_fan = fan_K = opt.fan_K
         self.fan = self.fan_idx = None
         if fan_K:
-            rows = int(diag_rows)
-            self.fan = torch.zeros((rows, fan_K, _lib.COVO_FAN_FLOATS), **f32)
+            self.fan = torch.zeros((self._rows, fan_K, _lib.COVO_FAN_FLOATS), **f32)
             stride = (torch.arange(fan_K, dtype=torch.int64) * self.n_local) // fan_K
-            self.fan_idx = stride.to(torch.int32).reshape(1, fan_K).repeat(rows, 1).to(self.device).contiguous()
-            check(self.lib.covo_set_step_fan(self.h, ptr(self.fan), ptr(self.fan_idx), fan_K, rows), "covo_set_step_fan")
-        # update = "best" / "guarded": every step ends with the update arbiter -- the softmax mean (guarded only), the shifted old mean and
-        # the best sample are rolled out with the step's own inputs and the cheapest becomes a_mean -- and leaves {cost_softmax,
-        # cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0} in self.arbiter (row e = instance e of a batched
-        # step), by one extra launch behind the step and ahead of the plan / fan launches (covo_set_step_arbiter,
-        # csrc/update_arbiter.hip); "softmax" (default): nothing attached, and that changes nothing
-        self.update_rule = update  # (self.update is the kernel-by-kernel softmax update below)
-        self.arb_mask = arb_mask
+            self.fan_idx = stride.to(torch.int32).reshape(1, fan_K).repeat(self._rows, 1).to(self.device).contiguous()
+            check(self.lib.covo_set_step_fan(self.h, ptr(self.fan), ptr(self.fan_idx), fan_K, self._rows), "covo_set_step_fan")
+        # self.arbiter [rows, 8]: {cost_softmax, cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0}
+        self.update_rule = opt.update  # (self.update is the kernel-by-kernel softmax update below)
+        self.arb_mask = opt.arb_mask
         self.arbiter = None
-        if arb_mask:
-            self.arbiter = torch.zeros((int(diag_rows), _lib.COVO_ARB_FLOATS), **f32)
-            check(self.lib.covo_set_step_arbiter(self.h, ptr(self.arbiter), arb_mask, int(diag_rows)), "covo_set_step_arbiter")
-        # ess_min: the ESS floor -- every step solves its temperature on the device from its own costs so that the weights' effective
-        # sample size is at least ess_min (1 <= ess_min <= N / 2; lam stays the configured one whenever ESS(lam) >= ess_min already), and
-        # leaves {lam_eff, 1 / lam_eff, ESS(lam), evaluations} in self.lam_eff (row e = instance e of a batched step)
-        # (covo_set_step_ess_floor, csrc/ess_lambda.hip); off by default, and off changes nothing
-        self.ess_min = float(ess_min) if ess_min is not None else 0.0
-        self.lam_eff = None
-        if self.ess_min != 0.0:
-            self.lam_eff = torch.zeros((int(diag_rows), _lib.COVO_LAM_FLOATS), **f32)
-            check(self.lib.covo_set_step_ess_floor(self.h, self.ess_min, ptr(self.lam_eff), int(diag_rows)), "covo_set_step_ess_floor")
-        # elite = K: the elite-set update, the cross-entropy method's rule -- every step (every pass of an iterated one) selects the K
-        # samples of smallest key {cost, index} on the device, exactly, and updates with weight 1 on them and 0 on the rest: the new
-        # mean is their average (blended by gamma_mean), MPPI with gamma_sigma != 0 refits a_cov to them -- and leaves {bits(threshold
-        # cost word), bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0} in self.elite_rows (row e = instance
-        # e of a batched step) (covo_set_step_elite, csrc/elite_select.hip, csrc/reduce_elite.hip); off by default, and off changes nothing
-        self.elite = elite_K
-        self.elite_rows = None
-        if elite_K:
-            self.elite_rows = torch.zeros((int(diag_rows), _lib.COVO_ELITE_FLOATS), **f32)
-            check(self.lib.covo_set_step_elite(self.h, elite_K, ptr(self.elite_rows), int(diag_rows)), "covo_set_step_elite")
-        # iters = k > 1: every control step runs k sample-rollout-update passes on its one state -- pass 0 is today's step, pass
-        # j >= 1 starts from the mean pass j - 1 committed (no shift) with the raw key split(split(key_{j-1})[0])[0], walked on the
-        # device -- and leaves the minimum sample cost of every pass in self.iter_cost_min (row e = instance e of a batched step)
-        # (covo_set_step_iters); 1 (default): nothing attached, and that changes nothing
-        self.iters = iters
-        self.iter_cost_min = None
-        if iters > 1:
-            self.iter_cost_min = torch.zeros((int(diag_rows), iters), **f32)
-            check(self.lib.covo_set_step_iters(self.h, iters, ptr(self.iter_cost_min), int(diag_rows)), "covo_set_step_iters")
-        # sigma_period = m > 1 (covo-online steps only): every m-th control step is today's step and refreshes Sigma; the m - 1 between
-        # skip the Hessian and the Sigma chain and sample from the previous step's factor moved one stage down the horizon on the
-        # device (covo_set_step_sigma_period, csrc/sigma_shift.hip); 1 (default): nothing attached, and that changes nothing
-        self.sigma_period = sigma_period
-        if sigma_period > 1:
-            check(self.lib.covo_set_step_sigma_period(self.h, sigma_period), "covo_set_step_sigma_period")
-        # compute_post_cov: every step also leaves the weighted 128 x 128 covariance of its own samples under its own update's weights,
-        # centred on the mean it sampled around, in self.post_cov (row e = instance e of a batched step) and {shift d[128], W, 0, 0, 0}
-        # in self.post_aux, by two extra launches behind the step (covo_set_step_post_cov, csrc/post_cov.hip); off by default, and off
-        # changes nothing
-        self.compute_post_cov = bool(compute_post_cov)
+        if opt.arb_mask:
+            self.arbiter = torch.zeros((self._rows, _lib.COVO_ARB_FLOATS), **f32)
+            check(self.lib.covo_set_step_arbiter(self.h, ptr(self.arbiter), opt.arb_mask, self._rows), "covo_set_step_arbiter")
+        # self.lam_eff [rows, 4]: {lam_eff, 1 / lam_eff, ESS(lam), evaluations}
+        self.ess_min = opt.ess_min
+        self.lam_eff = self._attach_rows(_lib.COVO_LAM_FLOATS, "covo_set_step_ess_floor", opt.ess_min) if opt.ess_min != 0.0 else None
+        # self.elite_rows [rows, 8]: {bits(threshold cost word), bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0}
+        self.elite = opt.elite_K
+        self.elite_rows = self._attach_rows(_lib.COVO_ELITE_FLOATS, "covo_set_step_elite", opt.elite_K) if opt.elite_K else None
+        # self.iter_cost_min [rows, iters]: the minimum sample cost of every pass
+        self.iters = opt.iters
+        self.iter_cost_min = self._attach_rows(opt.iters, "covo_set_step_iters", opt.iters) if opt.iters > 1 else None
+        self.sigma_period = opt.sigma_period
+        if opt.sigma_period > 1:
+            check(self.lib.covo_set_step_sigma_period(self.h, opt.sigma_period), "covo_set_step_sigma_period")
+        # self.post_cov [rows, 128, 128]: the posterior covariance; self.post_aux [rows, 132]: {shift d[128], W, 0, 0, 0}
+        self.compute_post_cov = opt.post_cov
         self.post_cov = self.post_aux = None
-        if self.compute_post_cov:
-            rows = int(diag_rows)
-            self.post_cov = torch.zeros((rows, COVO_NA, COVO_NA), **f32)
-            self.post_aux = torch.zeros((rows, _lib.COVO_POST_AUX_FLOATS), **f32)
+        if opt.post_cov:
+            self.post_cov = torch.zeros((self._rows, COVO_NA, COVO_NA), **f32)
+            self.post_aux = torch.zeros((self._rows, _lib.COVO_POST_AUX_FLOATS), **f32)
             with torch.cuda.device(self.device):
-                check(self.lib.covo_set_step_post_cov(self.h, ptr(self.post_cov), ptr(self.post_aux), rows), "covo_set_step_post_cov")
-        # sigma_adapt = gamma in (0, 1) (covo-online under a Sigma period): a reuse step samples from the shifted blend
-        # c ((1 - gamma) S(Sigma) + gamma S(C)) of the covariance the previous step sampled from and the posterior covariance C it left
-        # in self.post_cov (covo_set_step_sigma_adapt, csrc/sigma_adapt.hip); self.sigma_adapt_rows [rows, 4] = {fallback, c,
-        # log det M, 0} of every instance's last step ({0, 1, 0, 0} after a refresh step); 0.0 (default): nothing attached
-        self.sigma_adapt_gamma = sigma_adapt
+                check(self.lib.covo_set_step_post_cov(self.h, ptr(self.post_cov), ptr(self.post_aux), self._rows), "covo_set_step_post_cov")
+        # self.sigma_adapt_rows [rows, 4]: {fallback, c, log det M, 0} of every instance's last step ({0, 1, 0, 0} after a refresh step)
+        self.sigma_adapt_gamma = opt.sigma_adapt
         self.sigma_adapt_rows = None
-        if sigma_adapt > 0.0:
-            self.sigma_adapt_rows = torch.zeros((int(diag_rows), _lib.COVO_SIGMA_ADAPT_FLOATS), **f32)
+        if opt.sigma_adapt > 0.0:
+            self.sigma_adapt_rows = torch.zeros((self._rows, _lib.COVO_SIGMA_ADAPT_FLOATS), **f32)
             self.sigma_adapt_rows[:, 1] = 1.0
-            check(self.lib.covo_set_step_sigma_adapt(self.h, sigma_adapt, ptr(self.sigma_adapt_rows), int(diag_rows)),
+            check(self.lib.covo_set_step_sigma_adapt(self.h, opt.sigma_adapt, ptr(self.sigma_adapt_rows), self._rows),
                   "covo_set_step_sigma_adapt")
+        self._list_infos()
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -406,23 +339,46 @@ class SamplingCore:
               "covo_merge_ranks_cov")
         return out_mean, out_cov
 
+    def _attach_rows(self, width, setter, *ahead):
+        """zeros [rows, width], handed to the covo_set_step_* call `setter` (ahead: what it takes in front of the buffer)."""
+        rows = self.torch.zeros((self._rows, width), dtype=self.torch.float32, device=self.device)
+        check(getattr(self.lib, setter)(self.h, *ahead, ptr(rows), self._rows), setter)
+        return rows
+
+    def _list_infos(self):
+        """The info functions of what is attached, listed once: step_info sits on the per-step host path."""
+        self._infos = [info for on, info in (
+            (self.diag is not None, self.diag_info), (self.plan is not None, self.plan_info), (self.fan is not None, self.fan_info),
+            (self.lam_eff is not None, self.lam_info), (self.arbiter is not None, self.arbiter_info),
+            (self.iter_cost_min is not None, self.iter_info), (self.elite_rows is not None, self.elite_info),
+            (self.sigma_period > 1, self.sigma_info), (self.post_cov is not None, self.post_cov_info),
+            (self.sigma_adapt_rows is not None, self.sigma_adapt_info)) if on]
+
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
-        lam_info (ess_min), arbiter_info (update), iter_info (iters), elite_info (elite), post_cov_info (compute_post_cov) and
-        sigma_adapt_info (sigma_adapt) -- views of the core's buffers, no sync, no copy."""
+        lam_info (ess_min), arbiter_info (update), iter_info (iters), elite_info (elite), sigma_info (sigma_period), post_cov_info
+        (compute_post_cov) and sigma_adapt_info (sigma_adapt) -- views of the core's buffers, no sync, no copy."""
         out = {}
-        for info in (self.diag_info, self.plan_info, self.fan_info, self.lam_info, self.arbiter_info, self.iter_info, self.elite_info,
-                     self.sigma_info, self.post_cov_info, self.sigma_adapt_info):
+        for info in self._infos:
             out.update(info())
         return out
+
+    def attach_log(self, name, episode, rows_left: int):
+        """Bind `episode`'s log `name` (EPISODE_LOGS; allocated on first use) for the segment that starts at episode.n_steps, when this
+        core fills it."""
+        option, setter, sized = EPISODE_LOGS[name]
+        on = getattr(self, option)
+        if not on:
+            return
+        if getattr(episode, name, None) is None:
+            episode.alloc_log(name, *((on,) if sized else ()))
+        check(getattr(self.lib, setter)(self.h, ptr(episode.log_segment(name)), int(rows_left)), setter)
 
     def attach_episode_logs(self, episode, rows_left: int):
         """Bind every log of `episode` this core fills -- diagnostic log (compute_diag), trace (compute_plan), fan log (compute_fan),
         arbiter log (update) -- for the segment that starts at episode.n_steps: step k of it writes row n_steps + k of each."""
-        self.attach_diag_log(episode, rows_left)
-        self.attach_trace(episode, rows_left)
-        self.attach_fan_log(episode, rows_left)
-        self.attach_arbiter_log(episode, rows_left)
+        for name in EPISODE_LOGS:
+            self.attach_log(name, episode, rows_left)
 
     def diag_info(self) -> dict:
         """{"ess", "cost_min", "cost_weighted", "cost_mean"} of the last step as 0-d views of self.diag (no sync, no copy); {} when
@@ -478,14 +434,6 @@ class SamplingCore:
         return {"fan_pos": self.fan[0, :, 4:].view(K, COVO_H, 3), "fan_cost": self.fan[0, :, 0],
                 "fan_idx": self.fan[0, :, 1].view(self.torch.int32)}
 
-    def attach_fan_log(self, episode, rows_left: int):
-        """Bind `episode`'s fan log (allocated on first use) for the segment that starts at episode.n_steps."""
-        if not self.compute_fan:
-            return
-        if getattr(episode, "fanlog", None) is None:
-            episode.alloc_fan_log(self.compute_fan)
-        check(self.lib.covo_set_episode_fan(self.h, ptr(episode.fan_log_view()), int(rows_left)), "covo_set_episode_fan")
-
     def rollout_fan(self, dstate, params_c, idx, f_shared=None, f_steps=None, K=None):
         """covo_rollout_fan on self.a: the trajectories of the samples `idx` (int32 device tensor [K], clamped into [0, n_local) by
         the launch; None: K -- default compute_fan or 16 -- samples at the stride) with the inputs of rollout() -> float32 [K, 100] rows
@@ -512,15 +460,6 @@ class SamplingCore:
         row = self.arbiter[0]
         return {"arb_cost": row[0:3], "arb_cost_chosen": row[3], "arb_choice": row[4:5].view(self.torch.int32)[0],
                 "arb_best": row[5:6].view(self.torch.int32)[0]}
-
-    def attach_arbiter_log(self, episode, rows_left: int):
-        """Bind `episode`'s arbiter log (allocated on first use) for the segment that starts at episode.n_steps."""
-        if not self.arb_mask:
-            return
-        if getattr(episode, "arblog", None) is None:
-            episode.alloc_arbiter_log()
-        check(self.lib.covo_set_episode_arbiter_log(self.h, ptr(episode.arbiter_log_view()), int(rows_left)),
-              "covo_set_episode_arbiter_log")
 
     def arbitrate(self, dstate, params_c, a_nominal, a_mean, mask=0b111, f_shared=None, f_steps=None, cost=None, a=None):
         """covo_arbitrate (the stand-alone update arbiter) on self.a / self.cost (or `a` [H, N, 4] / `cost` [N]) with the inputs of
@@ -577,10 +516,10 @@ class SamplingCore:
         current period is how a controller's reset() restarts the schedule."""
         m = _lib.check_sigma_period(sigma_period)
         if m > 1 and self.world > 1:
-            raise NotImplementedError(f"sigma_period={m} on sample-sharded ranks: every rank would have to keep and shift the same "
-                                      "factor (covo_set_step_sigma_period refuses sample-sharded steps)")
+            raise sharded_refusal("sigma_period", m)
         check(self.lib.covo_set_step_sigma_period(self.h, m), "covo_set_step_sigma_period")
         self.sigma_period = m
+        self._list_infos()
 
     def sigma_factor(self, n_envs=None):
         """The factor L [128, 128] the last single covo-online step of this core sampled from (n_envs=E: [E, 128, 128], the last
@@ -663,53 +602,9 @@ class SamplingCore:
             return {}
         return {"lam_eff": self.lam_eff[0, 0], "ess_lam0": self.lam_eff[0, 2]}
 
-    def attach_trace(self, episode, rows_left: int):
-        """Bind `episode`'s trace (allocated on first use) for the segment that starts at episode.n_steps."""
-        if not self.compute_plan:
-            return
-        if getattr(episode, "trace", None) is None:
-            episode.alloc_trace()
-        check(self.lib.covo_set_episode_trace(self.h, ptr(episode.trace_view()), int(rows_left)), "covo_set_episode_trace")
-
     def require_fused_for_diag(self):
-        if getattr(self, "sigma_period", 1) > 1:
-            raise NotImplementedError(f"sigma_period={self.sigma_period} acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') computes its Sigma in every step")
-        if getattr(self, "sigma_adapt_gamma", 0.0) > 0.0:  # (the attribute: core.sigma_adapt is the stand-alone kernel's method)
-            raise NotImplementedError(f"sigma_adapt={self.sigma_adapt_gamma} acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') computes its Sigma in every step")
-        if self.ess_min != 0.0:
-            raise NotImplementedError("ess_min acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') updates at the configured lam")
-        if getattr(self, "elite", 0):
-            raise NotImplementedError(f"elite={self.elite} acts in the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') updates with the softmax weights")
-        if self.compute_plan:
-            raise NotImplementedError("compute_plan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') does not produce it")
-        if self.compute_fan:
-            raise NotImplementedError("compute_fan follows the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') does not produce it")
-        if getattr(self, "compute_post_cov", False):
-            raise NotImplementedError("compute_post_cov follows the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') does not produce it")
-        if getattr(self, "arb_mask", 0):
-            raise NotImplementedError(f"update={self.update_rule!r} follows the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') updates with the softmax mean only")
-        if getattr(self, "iters", 1) > 1:
-            raise NotImplementedError(f"iters={self.iters} follows the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') runs one pass per call")
-        if self.compute_diag:
-            raise NotImplementedError("compute_diag is formed by the fused step (covo_mpc_step); the kernel-by-kernel path "
-                                      "(materialize_eps / noise_stream='jax') does not produce it")
-
-    def attach_diag_log(self, episode, rows_left: int):
-        """Bind `episode`'s diagnostic log (allocated on first use) for the segment that starts at episode.n_steps."""
-        if not self.compute_diag:
-            return
-        if getattr(episode, "diag_log", None) is None:
-            episode.alloc_diag_log()
-        check(self.lib.covo_set_episode_diag_log(self.h, ptr(episode.diag_log_view()), int(rows_left)), "covo_set_episode_diag_log")
+        """The kernel-by-kernel path honours no attachment: NotImplementedError for the first one that is on."""
+        check_kernel_path(self)
 
     def device_status(self, clear: bool = False) -> int:
         """Sticky COVO_DEVSTAT_* bits raised by kernels of earlier calls (0 = fine); no synchronisation."""

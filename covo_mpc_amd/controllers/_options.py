@@ -1,0 +1,200 @@
+"""The step options of the sampling controllers: the one place that knows their list.
+
+Every entry point -- SamplingCore, CoVOController, MPPIController, BatchedCoVOController, BatchedMPPIController, get_controller and (under
+three renames) eval_env_batched -- carries the keywords of STEP_OPTION_DEFAULTS in its signature, gathers them with take(locals()),
+has them checked by check_step_options() and forwards them as **opts.  What cannot be combined is listed here too: the refusals of the
+env-batched fused step, of sample-sharded ranks and of the kernel-by-kernel debug path.  A new option is a keyword in those
+signatures, an entry here, and its own attachment block in SamplingCore.__init__ (tests/test_options_abi.py holds the signatures to
+this table).  The C side's counterpart is check_step_attachments (csrc/capi.hip).
+
+Each option is off by default, and off changes nothing.  "info[...]" names what a single controller's __call__ then returns in its
+info dict (SamplingCore.*_info: views of the core's buffers, no sync, no copy); the batched controllers expose the same buffers with
+one row per instance.
+"""
+from __future__ import annotations
+
+from dataclasses import dataclass
+
+from .. import _lib
+
+STEP_OPTION_DEFAULTS = {
+    # every step also leaves its sampling diagnostics {ess, cost_min, cost_weighted, cost_mean, weight_sum, n_samples}, formed by the
+    # update's own launches (covo_set_step_diag): info["ess"] / ["cost_min"] / ["cost_weighted"] / ["cost_mean"]
+    "compute_diag": False,
+    # every step also leaves its plan -- the rollout of the new mean itself with the step's own inputs, {cost_plan, pos_plan[H][3]} -- by
+    # one extra launch behind the step (covo_set_step_plan, csrc/plan_trace.hip): info["pos_plan"] / ["cost_plan"]; an episode driver
+    # records the trace with it
+    "compute_plan": False,
+    # the ESS floor: every step solves its temperature on the device from its own costs so that the weights' effective sample size is
+    # at least ess_min (1 <= ess_min <= N / 2; lam stays the configured one whenever ESS(lam) >= ess_min already)
+    # (covo_set_step_ess_floor, csrc/ess_lambda.hip): info["lam_eff"] / ["ess_lam0"]; None / 0: off
+    "ess_min": None,
+    # = K: every step also leaves K of its N sampled rollouts -- of the samples core.fan_idx names (pre-filled with the stride (s N) / K;
+    # a caller may overwrite it between steps; the launch clamps it into [0, N)) -- by one extra launch behind the step
+    # (covo_set_step_fan, csrc/sample_fan.hip): info["fan_pos"] / ["fan_cost"] / ["fan_idx"]; None / False: off
+    "compute_fan": None,
+    # "softmax" | "best" | "guarded".  "best" / "guarded": every step ends with the update arbiter -- the softmax mean (guarded only), the
+    # shifted old mean and the best sample are rolled out with the step's own inputs and the cheapest becomes a_mean -- by one extra
+    # launch behind the step and ahead of the plan / fan launches (covo_set_step_arbiter, csrc/update_arbiter.hip): info["arb_cost"] /
+    # ["arb_choice"] / ["arb_best"] / ["arb_cost_chosen"]; "softmax": nothing attached
+    "update": "softmax",
+    # = k > 1: every control step runs k sample-rollout-update passes on its one state -- pass 0 is the plain step, pass j >= 1 starts
+    # from the mean pass j - 1 committed (no shift) with the raw key split(split(key_{j-1})[0])[0], walked on the device
+    # (covo_set_step_iters): info["iter_cost_min"] [k], the minimum sample cost of every pass; 1: nothing attached
+    "iters": 1,
+    # = K: the elite-set update, the cross-entropy method's rule -- every step (every pass of an iterated one) selects the K samples of
+    # smallest key {cost, index} on the device, exactly, and updates with weight 1 on them and 0 on the rest: the new mean is their
+    # average (blended by gamma_mean), MPPI with gamma_sigma != 0 refits a_cov to them (covo_set_step_elite, csrc/elite_select.hip,
+    # csrc/reduce_elite.hip): info["elite_cost_max"] / ["elite_cost_min"] / ["elite_count"]; None / False / 0: off
+    "elite": None,
+    # = m > 1 (covo-online only): every m-th control step is the plain step and refreshes Sigma; the m - 1 between skip the Hessian and
+    # the Sigma chain and sample from the previous step's factor moved one stage down the horizon on the device
+    # (covo_set_step_sigma_period, csrc/sigma_shift.hip): info["sigma_age"]; 1: nothing attached
+    "sigma_period": 1,
+    # every step also leaves the weighted 128 x 128 covariance of its own samples under its own update's weights, centred on the mean
+    # it sampled around, by two extra launches behind the step (covo_set_step_post_cov, csrc/post_cov.hip): info["post_cov"] /
+    # ["post_shift"] / ["post_weight"]
+    "compute_post_cov": False,
+    # = gamma in (0, 1) (covo-online with sigma_period > 1): a reuse step samples from the shifted blend
+    # c ((1 - gamma) S(Sigma) + gamma S(C)) of the covariance the previous step sampled from and the posterior covariance C that step
+    # left (it implies compute_post_cov) (covo_set_step_sigma_adapt, csrc/sigma_adapt.hip): info["sigma_adapt_fallback"] /
+    # ["sigma_adapt_scale"]; 0.0: nothing attached
+    "sigma_adapt": 0.0,
+}
+
+
+def take(namespace) -> dict:
+    """The step options out of an entry point's locals(), ready to be checked and forwarded as **opts."""
+    return {k: namespace[k] for k in STEP_OPTION_DEFAULTS}
+
+
+@dataclass(frozen=True)
+class StepOptions:
+    """The step options, checked and normalised (check_step_options).  fan_K / elite_K are None when N was not known yet."""
+    diag: bool
+    plan: bool
+    ess_min: float      # 0.0: off
+    fan_K: int          # 0: off
+    update: str
+    arb_mask: int       # the arbiter's candidate mask (0: "softmax", nothing attached)
+    iters: int
+    elite_K: int        # 0: off
+    sigma_period: int
+    post_cov: bool      # forced on by sigma_adapt > 0: a reuse step reads the previous step's posterior covariance
+    sigma_adapt: float
+
+
+_BATCHED_TAKES = "BatchedCoVOController(mode=\"online\") and the single controllers take "
+# the env-batched MPPI / covo-offline step: (is on, message); {o}: the keywords as given
+FUSED_BATCHED_REFUSALS = (
+    (lambda s, o: s.elite_K,
+     "elite={o[elite]}: the elite-set update is not available for the env-batched MPPI / covo-offline step "
+     "(one fused launch: it needs the weights before all costs exist); " + _BATCHED_TAKES + "it"),
+    (lambda s, o: s.post_cov,
+     "compute_post_cov: the posterior covariance is not available for the env-batched MPPI / covo-offline "
+     "step (one fused launch: it keeps the samples in LDS and never stores them); " + _BATCHED_TAKES + "it"),
+    (lambda s, o: s.iters > 1 and s.update != "softmax",
+     "iters={o[iters]} with update={o[update]!r}: not available for the env-batched MPPI / covo-offline step "
+     "(its fused launch keeps each pass's starting mean in LDS only); " + _BATCHED_TAKES + "both"),
+    (lambda s, o: s.ess_min != 0.0,
+     "ess_min={o[ess_min]}: the ESS floor is not available for the env-batched MPPI / covo-offline step "
+     "(one fused launch: it needs the temperature before all costs exist); " + _BATCHED_TAKES + "it"),
+)
+
+# sample-sharded ranks: option -> (is on, the value the message shows as {v}, message); s: the normalised record, o: the keywords as given
+SHARDED_REFUSALS = {
+    "iters": (lambda s: s.iters > 1, lambda s, o: s.iters,
+              "iters={v} on sample-sharded ranks: every pass would need its own exchange of the rank "
+              "records (covo_set_step_iters refuses sample-sharded steps)"),
+    "update": (lambda s: s.arb_mask, lambda s, o: s.update,
+               "update={v!r} on sample-sharded ranks: a rank's action and cost buffers hold its shard "
+               "only (covo_set_step_arbiter refuses sample-sharded steps)"),
+    "compute_fan": (lambda s: s.fan_K, None,
+                    "compute_fan on sample-sharded ranks: a rank's action buffer holds its shard only "
+                    "(covo_set_step_fan refuses sample-sharded steps)"),
+    "ess_min": (lambda s: s.ess_min != 0.0, lambda s, o: o["ess_min"],
+                "ess_min={v} on sample-sharded ranks: a rank sees only its shard's costs "
+                "(covo_set_step_ess_floor refuses sample-sharded steps)"),
+    "elite": (lambda s: s.elite_K, lambda s, o: s.elite_K,
+              "elite={v} on sample-sharded ranks: a rank sees only its shard's costs "
+              "(covo_set_step_elite refuses sample-sharded steps)"),
+    "sigma_period": (lambda s: s.sigma_period > 1, lambda s, o: s.sigma_period,
+                     "sigma_period={v} on sample-sharded ranks: every rank would have to keep and shift "
+                     "the same factor (covo_set_step_sigma_period refuses sample-sharded steps)"),
+    "sigma_adapt": (lambda s: s.sigma_adapt > 0.0, lambda s, o: s.sigma_adapt,
+                    "sigma_adapt={v} on sample-sharded ranks: it needs the Sigma period and the posterior "
+                    "covariance (covo_set_step_sigma_adapt refuses sample-sharded steps)"),
+    "compute_post_cov": (lambda s: s.post_cov, None,
+                         "compute_post_cov on sample-sharded ranks: a rank's action and cost buffers hold its shard "
+                         "only (covo_set_step_post_cov refuses sample-sharded steps)"),
+    "compute_diag": (lambda s: s.diag, None,
+                     "compute_diag on sample-sharded ranks: the rank records carry no diagnostic sums "
+                     "(covo_set_step_diag refuses sample-sharded steps)"),
+    "compute_plan": (lambda s: s.plan, None,
+                     "compute_plan on sample-sharded ranks: a rank holds only its shard's record until the "
+                     "exchange (covo_set_step_plan refuses sample-sharded steps)"),
+}
+
+
+def sharded_refusal(option, v=None) -> NotImplementedError:
+    """The refusal of `option`, given as `v`, on sample-sharded ranks."""
+    return NotImplementedError(SHARDED_REFUSALS[option][2].format(v=v))
+
+
+_DEBUG_PATH = " (covo_mpc_step); the kernel-by-kernel path (materialize_eps / noise_stream='jax') "
+# the kernel-by-kernel path: (core attribute, its value when off, the attribute the message shows as {v}, message).  The off value
+# doubles as the default for cores that lack the attribute: the *_abi tests pass partial stand-ins of SamplingCore
+KERNEL_PATH_REFUSALS = (
+    ("sigma_period", 1, "sigma_period", "sigma_period={v} acts in the fused step" + _DEBUG_PATH + "computes its Sigma in every step"),
+    # (the attribute: core.sigma_adapt is the stand-alone kernel's method)
+    ("sigma_adapt_gamma", 0.0, "sigma_adapt_gamma", "sigma_adapt={v} acts in the fused step" + _DEBUG_PATH + "computes its Sigma in every step"),
+    ("ess_min", 0.0, "ess_min", "ess_min acts in the fused step" + _DEBUG_PATH + "updates at the configured lam"),
+    ("elite", 0, "elite", "elite={v} acts in the fused step" + _DEBUG_PATH + "updates with the softmax weights"),
+    ("compute_plan", False, "compute_plan", "compute_plan follows the fused step" + _DEBUG_PATH + "does not produce it"),
+    ("compute_fan", 0, "compute_fan", "compute_fan follows the fused step" + _DEBUG_PATH + "does not produce it"),
+    ("compute_post_cov", False, "compute_post_cov", "compute_post_cov follows the fused step" + _DEBUG_PATH + "does not produce it"),
+    ("arb_mask", 0, "update_rule", "update={v!r} follows the fused step" + _DEBUG_PATH + "updates with the softmax mean only"),
+    ("iters", 1, "iters", "iters={v} follows the fused step" + _DEBUG_PATH + "runs one pass per call"),
+    ("compute_diag", False, "compute_diag", "compute_diag is formed by the fused step" + _DEBUG_PATH + "does not produce it"),
+)
+
+
+def check_kernel_path(core) -> None:
+    """NotImplementedError for the first attachment of `core` the kernel-by-kernel path cannot honour."""
+    for attr, off, shown, message in KERNEL_PATH_REFUSALS:
+        if getattr(core, attr, off) != off:
+            raise NotImplementedError(message.format(v=getattr(core, shown)))
+
+
+def check_step_options(N, what, *, gamma_sigma=None, fused_batched=False, sharded=False, **raw) -> StepOptions:
+    """The step options as given (**raw: the keywords of STEP_OPTION_DEFAULTS, missing ones at their defaults) -> StepOptions, or the
+    first objection, in a fixed order:
+    1. each keyword's own range and mode check (_lib.check_*: ValueError).  `what` names the controller in the mode clauses: "online"
+       for covo-online, the one mode that takes sigma_period / sigma_adapt.  N=None (not parsed yet) skips compute_fan and elite, the
+       two that need it.  gamma_sigma (MPPI): see _lib.check_elite;
+    2. fused_batched -- the env-batched MPPI / covo-offline step, one fused launch: NotImplementedError for elite, compute_post_cov,
+       iters with an update other than "softmax", ess_min;
+    3. sharded -- sample-sharded ranks: NotImplementedError for whatever of SHARDED_REFUSALS is on, in its order."""
+    unknown = set(raw) - set(STEP_OPTION_DEFAULTS)
+    if unknown:
+        raise TypeError(f"check_step_options: unknown step options {sorted(unknown)}")
+    o = {**STEP_OPTION_DEFAULTS, **raw}
+    sigma_period = _lib.check_sigma_period(o["sigma_period"], what)
+    sigma_adapt = _lib.check_sigma_adapt(o["sigma_adapt"], sigma_period, what)
+    fan_K = _lib.check_fan(o["compute_fan"], N) if N is not None else None
+    arb_mask = _lib.check_update(o["update"])
+    iters = _lib.check_iters(o["iters"])
+    elite_K = _lib.check_elite(o["elite"], N, o["ess_min"], gamma_sigma) if N is not None else None
+    s = StepOptions(diag=bool(o["compute_diag"]), plan=bool(o["compute_plan"]),
+                    ess_min=float(o["ess_min"]) if o["ess_min"] is not None else 0.0, fan_K=fan_K, update=o["update"],
+                    arb_mask=arb_mask, iters=iters, elite_K=elite_K, sigma_period=sigma_period,
+                    post_cov=bool(o["compute_post_cov"]) or sigma_adapt > 0.0, sigma_adapt=sigma_adapt)
+    if fused_batched:
+        for is_on, message in FUSED_BATCHED_REFUSALS:
+            if is_on(s, o):
+                raise NotImplementedError(message.format(o=o))
+    if sharded:
+        for option, (is_on, shown, _) in SHARDED_REFUSALS.items():
+            if is_on(s):
+                raise sharded_refusal(option, shown(s, o) if shown else None)
+    return s

@@ -20,6 +20,12 @@ from .. import _lib
 from .._lib import COVO_H, COVO_NA, check
 from ..dynamics.dataclass import as_device_state
 from ._core import SamplingCore
+from ._options import check_step_options, take
+
+# (controller attribute, core attribute) of the attachment buffers the batched controllers hand out
+CORE_BUFFERS = (("diag", "diag"), ("plan", "plan"), ("fan", "fan"), ("arbiter", "arbiter"), ("lam_eff", "lam_eff"), ("elite", "elite_rows"),
+                ("iter_cost_min", "iter_cost_min"), ("post_cov", "post_cov"), ("post_aux", "post_aux"),
+                ("sigma_adapt_rows", "sigma_adapt_rows"))
 
 
 class BatchedCoVOController:
@@ -31,29 +37,11 @@ class BatchedCoVOController:
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0):
-        what = ("online" if (self.MODE is None and mode == "online") else
+        opts = take(locals())
+        fused = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step: one fused launch for all instances
+        what = ("online" if not fused else
                 "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
-        _lib.check_sigma_period(sigma_period, what)
-        _lib.check_sigma_adapt(sigma_adapt, sigma_period, what)
-        _lib.check_fan(compute_fan, N)
-        _lib.check_update(update)
-        _lib.check_iters(iters)
-        if _lib.check_elite(elite, N, ess_min) and (self.MODE is not None or mode != "online"):
-            raise NotImplementedError(f"elite={elite}: the elite-set update is not available for the env-batched MPPI / covo-offline step "
-                                      "(one fused launch: it needs the weights before all costs exist); "
-                                      "BatchedCoVOController(mode=\"online\") and the single controllers take it")
-        if compute_post_cov and (self.MODE is not None or mode != "online"):
-            raise NotImplementedError("compute_post_cov: the posterior covariance is not available for the env-batched MPPI / covo-offline "
-                                      "step (one fused launch: it keeps the samples in LDS and never stores them); "
-                                      "BatchedCoVOController(mode=\"online\") and the single controllers take it")
-        if iters > 1 and update != "softmax" and (self.MODE is not None or mode != "online"):
-            raise NotImplementedError(f"iters={iters} with update={update!r}: not available for the env-batched MPPI / covo-offline step "
-                                      "(its fused launch keeps each pass's starting mean in LDS only); "
-                                      "BatchedCoVOController(mode=\"online\") and the single controllers take both")
-        if ess_min is not None and float(ess_min) != 0.0 and (self.MODE is not None or mode != "online"):
-            raise NotImplementedError(f"ess_min={ess_min}: the ESS floor is not available for the env-batched MPPI / covo-offline step "
-                                      "(one fused launch: it needs the temperature before all costs exist); "
-                                      "BatchedCoVOController(mode=\"online\") and the single controllers take it")
+        check_step_options(N, what, fused_batched=fused, **opts)
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -69,36 +57,13 @@ class BatchedCoVOController:
         # instance's per-step tables (csrc/disturb.hip) from its state, raw key and disturb_params inside the graph
         # one call advances all instances: the ~56 launches are worth a graph (same GPU time as eager, 40 us instead of
         # 150-270 us of host time per call)
-        # compute_diag: after a call, self.diag [E, 8] holds every instance's sampling diagnostics of that step (include/covo_hip.h)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
-                                 compute_diag=compute_diag, diag_rows=int(n_envs), compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite, sigma_period=sigma_period,
-                                 compute_post_cov=compute_post_cov, sigma_adapt=sigma_adapt)
-        # sigma_adapt = gamma > 0 (online, sigma_period > 1): the reuse calls blend every instance's posterior covariance into the
-        # covariance they shift; after a call, self.sigma_adapt_rows [E, 4] holds every instance's {fallback, c, log det M, 0} of that
-        # step ({0, 1, 0, 0} after a refresh); None without it
-        self.sigma_adapt_rows = self.core.sigma_adapt_rows
-        # sigma_period = m > 1 (online): every m-th call refreshes every instance's Sigma, the calls between shift the last factors; the
-        # batch shares one age: self.sigma_age is the age the last call ran at (0 = refresh), reset() restarts the schedule
-        # elite = K: after a call, self.elite [E, 8] holds every instance's selector row of that step: {bits(threshold cost word),
-        # bits(threshold index word), cost_min, cost_kth, K, elites at cost_kth, 0, 0} (include/covo_hip.h); None without it
-        self.elite = self.core.elite_rows
-        # iters = k > 1: after a call, self.iter_cost_min [E, k] holds the minimum sample cost of every pass of every instance; None under 1
-        self.iter_cost_min = self.core.iter_cost_min
-        # update = "best" / "guarded": after a call, self.arbiter [E, 8] holds every instance's arbiter row of that step: {cost_softmax,
-        # cost_nominal, cost_best, cost_chosen, bits(choice), bits(n_best), 0, 0} (include/covo_hip.h); None under "softmax"
-        self.arbiter = self.core.arbiter
-        # compute_fan = K: after a call, self.fan [E, K, 100] holds every instance's fan of that step: rows {cost_s, bits(n_s), 0, 0,
-        # pos_s[H][3]} of the samples self.core.fan_idx [E, K] names (include/covo_hip.h)
-        self.fan = self.core.fan
-        # compute_post_cov: after a call, self.post_cov [E, 128, 128] holds every instance's posterior covariance of that step and
-        # self.post_aux [E, 132] its {shift d[128], W, 0, 0, 0} (include/covo_hip.h); None without it
-        self.post_cov, self.post_aux = self.core.post_cov, self.core.post_aux
-        # ess_min: after a call, self.lam_eff [E, 4] holds every instance's {lam_eff, 1 / lam_eff, ESS(lam), evaluations} of that step
-        self.lam_eff = self.core.lam_eff
-        self.diag = self.core.diag
-        # compute_plan: after a call, self.plan [E, 100] holds every instance's plan of that step {cost_plan, 0, 0, 0, pos_plan[H][3]}
-        self.plan = self.core.plan
+                                 diag_rows=int(n_envs), **opts)
+        # after a call, row e of each of the core's attachment buffers holds instance e's result of that step; None for what is off
+        # (the options: _options.py; the rows: where SamplingCore allocates them; include/covo_hip.h).  sigma_period: the batch shares
+        # one age -- self.sigma_age is the age the last call ran at (0 = refresh), reset() restarts the schedule
+        for mine, cores in CORE_BUFFERS:
+            setattr(self, mine, getattr(self.core, cores))
         torch = self.core.torch
         f32 = dict(dtype=torch.float32, device=self.core.device)
         E, n = self.E, self.N
@@ -273,18 +238,14 @@ class BatchedMPPIController(BatchedCoVOController):
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
                  ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
                  compute_post_cov: bool = False, sigma_adapt: float = 0.0):
-        _lib.check_sigma_period(sigma_period, "the env-batched MPPI controller")
-        _lib.check_sigma_adapt(sigma_adapt, sigma_period, "the env-batched MPPI controller")
-        _lib.check_fan(compute_fan, N)
-        _lib.check_update(update)
-        _lib.check_iters(iters)
+        opts = take(locals())
+        check_step_options(N, "the env-batched MPPI controller", fused_batched=True, **opts)  # (ahead of gamma_sigma's refusal)
         if float(gamma_sigma) != 0.0:
             raise NotImplementedError(f"gamma_sigma={gamma_sigma}: MPPI's covariance adaptation (mppi.py:119-125) is not batched; "
                                       "the batched fused launch needs gamma_sigma == 0 (the reference's default)")
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
-                         a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                         compute_fan=compute_fan, update=update, iters=iters, elite=elite, compute_post_cov=compute_post_cov)
+                         a_mean_init=a_mean_init, device=device, **opts)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

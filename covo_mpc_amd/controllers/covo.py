@@ -23,6 +23,7 @@ from ..dynamics.dataclass import as_device_state
 from .base import BaseController
 from .pid import PIDController, PIDParams
 from ._core import SamplingCore
+from ._options import check_step_options, take
 
 
 @dataclass(frozen=True)
@@ -48,13 +49,8 @@ class CoVOController(BaseController):
                  process_group=None, compute_info: bool = True, propagate_nan=None, compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1,
                  elite=None, sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0) -> None:
-        from .. import _lib
-        _lib.check_sigma_period(sigma_period, mode if mode in ("online", "offline") else "online")  # ValueError before anything is built
-        _lib.check_sigma_adapt(sigma_adapt, sigma_period, mode if mode in ("online", "offline") else "online")
-        _lib.check_fan(compute_fan, N)
-        _lib.check_update(update)
-        _lib.check_iters(iters)
-        _lib.check_elite(elite, N, ess_min)
+        opts = take(locals())
+        check_step_options(N, mode if mode in ("online", "offline") else "online", **opts)  # ValueError before anything is built
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -73,10 +69,7 @@ class CoVOController(BaseController):
         self.mode = mode
         # propagate_nan: jnp.clip's NaN semantics in the sampling clip (covo.py:224) -- see SamplingCore
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
-                                 compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan,
-                                 compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite, sigma_period=sigma_period,
-                                 compute_post_cov=compute_post_cov, sigma_adapt=sigma_adapt)
+                                 compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan, **opts)
 
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start (covo-online; covo-offline's reset builds its table): with a Sigma period the schedule restarts -- the first
@@ -228,7 +221,7 @@ class CoVOController(BaseController):
                 a_cov = a_cov.clone() if self.mode == "online" else a_cov
             control_params = control_params.replace(a_mean=a_mean_new, a_cov=a_cov)
             out_info = core.info(dstate) if core.compute_info else {}
-            out_info.update(core.step_info())  # whatever compute_diag / _plan / _fan, ess_min, update, iters and elite attached
+            out_info.update(core.step_info())  # whatever the step options attached (_options.py)
             return a_mean_new[0], control_params, out_info
 
         # ---- kernel-by-kernel path with epsilon materialised in HBM (identical values; parity/debug)

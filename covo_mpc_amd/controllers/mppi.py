@@ -14,6 +14,7 @@ from typing import Any
 from ..dynamics.dataclass import as_device_state
 from .base import BaseController
 from ._core import SamplingCore
+from ._options import check_step_options, take
 
 
 @dataclass(frozen=True)
@@ -35,13 +36,9 @@ class MPPIController(BaseController):
                  compute_info: bool = True, propagate_nan=None, compute_diag: bool = False, compute_plan: bool = False,
                  ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
                  compute_post_cov: bool = False, sigma_adapt: float = 0.0) -> None:
-        from .. import _lib
-        _lib.check_sigma_period(sigma_period, "MPPI")  # ValueError before anything is built (MPPI computes no Sigma per step)
-        _lib.check_sigma_adapt(sigma_adapt, sigma_period, "MPPI")
-        _lib.check_fan(compute_fan, N)
-        _lib.check_update(update)
-        _lib.check_iters(iters)
-        _lib.check_elite(elite, N, ess_min, getattr(control_params, "gamma_sigma", 0.0))
+        opts = take(locals())
+        # ValueError before anything is built (MPPI computes no Sigma per step: sigma_period / sigma_adapt stay at their defaults)
+        check_step_options(N, "MPPI", gamma_sigma=getattr(control_params, "gamma_sigma", 0.0), **opts)
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -53,8 +50,7 @@ class MPPIController(BaseController):
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
                                  compute_info=compute_info, trust_clipped=True,
                                  cov_records=float(getattr(control_params, "gamma_sigma", 0.0)) != 0.0, propagate_nan=propagate_nan,
-                                 compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                 compute_fan=compute_fan, update=update, iters=iters, elite=elite, compute_post_cov=compute_post_cov)
+                                 **opts)
 
     def _check_gamma_sigma(self, control_params):
         """A controller built with gamma_sigma = 0 exchanges the 516-float records: on sharded ranks a later gamma_sigma != 0 needs
@@ -103,7 +99,7 @@ class MPPIController(BaseController):
                 a_mean_new, cov = a_mean_new.clone(), cov.clone()
             control_params = control_params.replace(a_mean=a_mean_new, a_cov=cov)
             out_info = core.info(dstate) if core.compute_info else {}
-            out_info.update(core.step_info())  # whatever compute_diag / _plan / _fan, ess_min, update, iters and elite attached
+            out_info.update(core.step_info())  # whatever the step options attached (_options.py)
             return a_mean_new[0], control_params, out_info
 
         # ---- kernel-by-kernel path with epsilon materialised in HBM (identical values; parity/debug)

@@ -20,6 +20,7 @@ import numpy as np
 
 from .. import controllers
 from .. import random as crandom
+from ..controllers._options import STEP_OPTION_DEFAULTS, check_step_options, take
 from ..dynamics import utils
 from ..dynamics.dataclass import Action3D, DeviceState, EnvParams3D, EnvState3D
 from ..dynamics.free import get_quadrotor_1st_order_dyn
@@ -289,7 +290,63 @@ def unpack_state_row(row: np.ndarray) -> dict:
             "acc_tar": row[22:25].copy(), "time": int(np.ascontiguousarray(row[25:26]).view(np.int32)[0])}
 
 
-class DeviceEpisode:
+class _EpisodeLogs:
+    """The four logs an episode driver can fill next to the env log, one row per enqueued step: `diag_log` (sampling diagnostics),
+    `trace` (the flight recorder), `fanlog` (the sample fan), `arblog` (the update arbiter).  Each is None until a controller built
+    with its option runs the episode (SamplingCore.attach_log allocates it on first use), shaped like the env log `self.log` with
+    the log's own row in place of the 4 floats: [T + 1, ...] for one instance, [E, T + 1, ...] for E (STEP_AXIS: the step axis)."""
+    STEP_AXIS = 0
+    # attribute: (the row's width in _lib, what splits the rows read back, what the log is called, the option that fills it)
+    LOGS = {"diag_log": ("COVO_DIAG_FLOATS", None, "diagnostic log", "compute_diag=True"),         # rows [8]
+            "trace": ("COVO_TRACE_FLOATS", split_trace_rows, "trace", "compute_plan=True"),          # rows [168]
+            "fanlog": ("COVO_FAN_FLOATS", split_fan_rows, "fan log", "compute_fan=K"),               # rows [K, 100]: alloc_log("fanlog", K)
+            "arblog": ("COVO_ARB_FLOATS", split_arbiter_rows, "arbiter log", "update='best' or 'guarded'")}  # rows [8]
+
+    def alloc_log(self, name, *inner):
+        import torch
+        shape = tuple(self.log.shape[:-1]) + tuple(int(n) for n in inner) + (getattr(self._lib, self.LOGS[name][0]),)
+        setattr(self, name, torch.zeros(shape, dtype=torch.float32, device=self.device))
+
+    def log_segment(self, name):
+        """What the episode driver binds of log `name` for the next segment: one instance -- the rows from n_steps on (covo_run_episode
+        counts its rows from 0); E instances -- the whole buffer (the batched drivers take the first row of a segment as log_index)."""
+        buf = getattr(self, name)
+        return buf if self.STEP_AXIS else buf[self.n_steps:]
+
+    def _read(self, name):
+        _, split, label, option = self.LOGS[name]
+        buf = getattr(self, name)
+        if buf is None:
+            raise RuntimeError(f"no {label}: run_episode under a controller built with {option}")
+        self.read_log()  # synchronises and checks the device status
+        rows = buf.narrow(self.STEP_AXIS, 0, self.n_steps).cpu().numpy()
+        return split(rows) if split else rows
+
+    # the read_* below: numpy, n = n_steps rows per instance ([E, n, ...] for E instances), synchronising and checking the device status
+    # like read_log
+    def read_diag(self):
+        """-> float32 [n, 8]: per enqueued step its sampling diagnostics (include/covo_hip.h: covo_set_step_diag), under a controller
+        built with compute_diag."""
+        return self._read("diag_log")
+
+    def read_trace(self):
+        """-> {state [n, 32], noisy [n, 32], u [n, 4], cost_plan [n], pos_plan [n, H, 3]}: per enqueued step the true and the noisy
+        state ENTERING its env step, the action it received and the controller's plan (include/covo_hip.h: covo_set_episode_trace),
+        under a controller built with compute_plan."""
+        return self._read("trace")
+
+    def read_fan(self):
+        """-> {pos [n, K, H, 3], cost [n, K], idx [n, K]}: per enqueued step the K sampled rollouts of its fan (include/covo_hip.h:
+        covo_set_step_fan), under a controller built with compute_fan."""
+        return self._read("fanlog")
+
+    def read_arbiter(self):
+        """-> {cost [n, 3], cost_chosen [n], choice [n], best [n]}: per enqueued step the update arbiter's row (include/covo_hip.h:
+        covo_set_step_arbiter), under a controller built with update="best" / "guarded"."""
+        return self._read("arblog")
+
+
+class DeviceEpisode(_EpisodeLogs):
     """One episode whose env state lives on the device: the true state, its noisy copy (what the
     controller plans from), the reference trajectory and the per-step log {reward, err_pos, err_vel, done}.
     `reset` is host plumbing (trajectory generation, quadrotor.py:265-312) followed by one upload; `step` launches
@@ -318,77 +375,8 @@ class DeviceEpisode:
         # incl. the env's reward, disturbance model and reset generator (env_step.hip runs all of them)
         self.params_c = env_model_params_c(env, params, auto_reset=auto_reset)
         self.n_steps = 0
-        self.diag_log = None  # [T + 1, 8], allocated when a controller with compute_diag runs the episode
-        self.trace = None     # [T + 1, 168], allocated when a controller with compute_plan runs the episode
-        self.fanlog = None    # [T + 1, K, 100], allocated when a controller with compute_fan runs the episode
-        self.arblog = None    # [T + 1, 8], allocated when a controller with update="best" / "guarded" runs the episode
-
-    def alloc_arbiter_log(self):
-        import torch
-        self.arblog = torch.zeros((int(self.log.shape[0]), self._lib.COVO_ARB_FLOATS), dtype=torch.float32, device=self.device)
-
-    def arbiter_log_view(self):
-        """the rows of the arbiter log the next segment writes (covo_run_episode counts its rows from 0)"""
-        return self.arblog[self.n_steps:]
-
-    def read_arbiter(self):
-        """-> {cost [n, 3], cost_chosen [n], choice [n], best [n]} (numpy): per enqueued step the update arbiter's row (include/covo_hip.h:
-        covo_set_step_arbiter), under a controller built with update="best" / "guarded"; synchronises and checks the device status
-        like read_log."""
-        if self.arblog is None:
-            raise RuntimeError("no arbiter log: run_episode under a controller built with update='best' or 'guarded'")
-        self.read_log()
-        return split_arbiter_rows(self.arblog[:self.n_steps].cpu().numpy())
-
-    def alloc_fan_log(self, K: int):
-        import torch
-        self.fanlog = torch.zeros((int(self.log.shape[0]), int(K), self._lib.COVO_FAN_FLOATS), dtype=torch.float32, device=self.device)
-
-    def fan_log_view(self):
-        """the rows of the fan log the next segment writes (covo_run_episode counts its rows from 0)"""
-        return self.fanlog[self.n_steps:]
-
-    def read_fan(self):
-        """-> {pos [n, K, H, 3], cost [n, K], idx [n, K]} (numpy): per enqueued step the K sampled rollouts of its fan (include/covo_hip.h:
-        covo_set_step_fan), under a controller built with compute_fan; synchronises and checks the device status like read_log."""
-        if self.fanlog is None:
-            raise RuntimeError("no fan log: run_episode under a controller built with compute_fan=K")
-        self.read_log()
-        return split_fan_rows(self.fanlog[:self.n_steps].cpu().numpy())
-
-    def alloc_diag_log(self):
-        import torch
-        self.diag_log = torch.zeros((int(self.log.shape[0]), self._lib.COVO_DIAG_FLOATS), dtype=torch.float32, device=self.device)
-
-    def alloc_trace(self):
-        import torch
-        self.trace = torch.zeros((int(self.log.shape[0]), self._lib.COVO_TRACE_FLOATS), dtype=torch.float32, device=self.device)
-
-    def trace_view(self):
-        """the rows of the trace the next segment writes (covo_run_episode counts its rows from 0)"""
-        return self.trace[self.n_steps:]
-
-    def read_trace(self):
-        """-> {state [n, 32], noisy [n, 32], u [n, 4], cost_plan [n], pos_plan [n, H, 3]} (numpy): per enqueued step the true and
-        the noisy state ENTERING its env step, the action it received and the controller's plan (include/covo_hip.h:
-        covo_set_episode_trace), under a controller built with compute_plan; synchronises and checks the device status like
-        read_log."""
-        if self.trace is None:
-            raise RuntimeError("no trace: run_episode under a controller built with compute_plan=True")
-        self.read_log()
-        return split_trace_rows(self.trace[:self.n_steps].cpu().numpy())
-
-    def diag_log_view(self):
-        """the rows of the diagnostic log the next segment writes (covo_run_episode counts its rows from 0)"""
-        return self.diag_log[self.n_steps:]
-
-    def read_diag(self):
-        """-> float32[n_steps, 8]: the sampling diagnostics (include/covo_hip.h: covo_set_step_diag) of the steps run_episode has
-        enqueued under a controller with compute_diag; synchronises and checks the device status like read_log."""
-        if self.diag_log is None:
-            raise RuntimeError("no diagnostic log: run_episode under a controller built with compute_diag=True")
-        self.read_log()
-        return self.diag_log[:self.n_steps].cpu().numpy()
+        for name in self.LOGS:  # allocated when a controller with the log's option runs the episode
+            setattr(self, name, None)
 
     @property
     def noisy_state(self) -> DeviceState:
@@ -431,11 +419,12 @@ class DeviceEpisode:
         return out
 
 
-class BatchedDeviceEpisode:
+class BatchedDeviceEpisode(_EpisodeLogs):
     """E independent env instances on the device (BASELINE configs[4]): instance e has its own (domain-randomised,
     quadrotor.py:132-171) parameters, reset key, true state, noisy copy, reference trajectory and log.  `step` launches
     covo_env_step_batched -- every instance's Quad3D.step in ONE launch; BatchedCoVOController.run_episode enqueues whole
     episodes (control step + env step for all instances) from one C call.  auto_reset: as DeviceEpisode, per instance."""
+    STEP_AXIS = 1
 
     def __init__(self, env: "Quad3D", keys, params_list, lib_handle, device, auto_reset: bool = True):
         import torch
@@ -468,71 +457,8 @@ class BatchedDeviceEpisode:
         self.log = torch.zeros((self.E, self.params[0].max_steps_in_episode + 1, 4), dtype=torch.float32, device=device)
         self.params_c = (_lib.EnvParamsC * self.E)(*[env_model_params_c(env, p, auto_reset=auto_reset) for p in self.params])
         self.n_steps = 0
-        self.diag_log = None  # [E, T + 1, 8], allocated when a controller with compute_diag runs the episode
-        self.trace = None     # [E, T + 1, 168], allocated when a controller with compute_plan runs the episode
-        self.fanlog = None    # [E, T + 1, K, 100], allocated when a controller with compute_fan runs the episode
-        self.arblog = None    # [E, T + 1, 8], allocated when a controller with update="best" / "guarded" runs the episode
-
-    def alloc_arbiter_log(self):
-        import torch
-        self.arblog = torch.zeros((self.E, int(self.log.shape[1]), self._lib.COVO_ARB_FLOATS), dtype=torch.float32, device=self.device)
-
-    def arbiter_log_view(self):
-        return self.arblog  # (the batched drivers take the first row of a segment as log_index)
-
-    def read_arbiter(self):
-        """-> {cost [E, n, 3], cost_chosen [E, n], choice [E, n], best [E, n]} (numpy) of the enqueued steps (controller built with
-        update="best" / "guarded"); synchronises and checks the device status like read_log."""
-        if self.arblog is None:
-            raise RuntimeError("no arbiter log: run_episode under a controller built with update='best' or 'guarded'")
-        self.read_log()
-        return split_arbiter_rows(self.arblog[:, :self.n_steps].cpu().numpy())
-
-    def alloc_fan_log(self, K: int):
-        import torch
-        self.fanlog = torch.zeros((self.E, int(self.log.shape[1]), int(K), self._lib.COVO_FAN_FLOATS), dtype=torch.float32,
-                                  device=self.device)
-
-    def fan_log_view(self):
-        return self.fanlog  # (the batched drivers take the first row of a segment as log_index)
-
-    def read_fan(self):
-        """-> {pos [E, n, K, H, 3], cost [E, n, K], idx [E, n, K]} (numpy) of the enqueued steps (controller built with compute_fan);
-        synchronises and checks the device status like read_log."""
-        if self.fanlog is None:
-            raise RuntimeError("no fan log: run_episode under a controller built with compute_fan=K")
-        self.read_log()
-        return split_fan_rows(self.fanlog[:, :self.n_steps].cpu().numpy())
-
-    def alloc_trace(self):
-        import torch
-        self.trace = torch.zeros((self.E, int(self.log.shape[1]), self._lib.COVO_TRACE_FLOATS), dtype=torch.float32, device=self.device)
-
-    def trace_view(self):
-        return self.trace  # (the batched drivers take the first row of a segment as log_index)
-
-    def read_trace(self):
-        """-> {state [E, n, 32], noisy [E, n, 32], u [E, n, 4], cost_plan [E, n], pos_plan [E, n, H, 3]} (numpy) of the enqueued
-        steps (controller built with compute_plan); synchronises and checks the device status like read_log."""
-        if self.trace is None:
-            raise RuntimeError("no trace: run_episode under a controller built with compute_plan=True")
-        self.read_log()
-        return split_trace_rows(self.trace[:, :self.n_steps].cpu().numpy())
-
-    def alloc_diag_log(self):
-        import torch
-        self.diag_log = torch.zeros((self.E, int(self.log.shape[1]), self._lib.COVO_DIAG_FLOATS), dtype=torch.float32, device=self.device)
-
-    def diag_log_view(self):
-        return self.diag_log  # (the batched drivers take the first row of a segment as log_index)
-
-    def read_diag(self):
-        """-> float32 [E, n_steps, 8]: every instance's sampling diagnostics of the enqueued steps (controller built with
-        compute_diag); synchronises and checks the device status like read_log."""
-        if self.diag_log is None:
-            raise RuntimeError("no diagnostic log: run_episode under a controller built with compute_diag=True")
-        self.read_log()
-        return self.diag_log[:, :self.n_steps].cpu().numpy()
+        for name in self.LOGS:  # allocated when a controller with the log's option runs the episode
+            setattr(self, name, None)
 
     def step(self, step_keys, a_mean, stream=None):
         """step_keys: uint32 [E, 2] (the key Quad3D.step receives, per instance); a_mean: float32 [E, 128] device tensor whose first
@@ -567,14 +493,11 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]; with trace=True
     -> (that, ep.read_trace()): every instance's states, actions and plans of the episode; with fan=K ep.read_fan() -- K sampled
     rollouts of every step of every instance -- is appended to the returned tuple.  update: the controller's update rule ("softmax" |
-    "best" | "guarded"); arbiter=True (with "best" / "guarded") appends ep.read_arbiter(), every step's arbiter row.  iters=k: k
-    sample-rollout-update passes per control step (SamplingCore).  elite=K: the elite-set update with K elites per instance
-    (SamplingCore).  sigma_period=m: every m-th control step refreshes Sigma, the steps between shift the last factor (SamplingCore).
-    sigma_adapt=gamma: those steps blend the posterior covariance into the covariance they shift (SamplingCore)."""
-    from .. import _lib
-    _lib.check_iters(iters)
-    _lib.check_sigma_period(sigma_period)
-    _lib.check_sigma_adapt(sigma_adapt, sigma_period)
+    "best" | "guarded"); arbiter=True (with "best" / "guarded") appends ep.read_arbiter(), every step's arbiter row.  diag / trace / fan
+    are the step options compute_diag / compute_plan / compute_fan, update / iters / elite / sigma_period / sigma_adapt the options of
+    those names (controllers/_options.py)."""
+    opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
+    check_step_options(None, "online", **opts)  # ValueError before anything is built
     if arbiter and update == "softmax":
         raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
@@ -585,9 +508,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     c0, cp0 = get_controller(env, "covo-online", controller_params, device=device, compute_info=False)
     cp0 = c0.init_control_params
     b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                          sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device,
-                                          compute_diag=diag, compute_plan=trace, compute_fan=fan, update=update, iters=iters,
-                                          elite=elite, sigma_period=sigma_period, sigma_adapt=sigma_adapt)
+                                          sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device, **opts)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
@@ -705,24 +626,13 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
                    iters=1, elite=None, sigma_period=1, compute_post_cov=False, sigma_adapt=0.0):
-    """quadrotor.py:670-752.  ess_min (sampling controllers): the ESS floor, see SamplingCore; compute_fan=K (sampling controllers): K
-    sampled rollouts of every step in info["fan_pos"] / ["fan_cost"] / ["fan_idx"], see SamplingCore; update (sampling controllers):
-    "softmax" (default) | "best" | "guarded" -- the update arbiter, info["arb_cost"] / ["arb_choice"] / ["arb_best"] /
-    ["arb_cost_chosen"], see SamplingCore; iters=k (sampling controllers): k sample-rollout-update passes per control step,
-    info["iter_cost_min"] [k], see SamplingCore; elite=K (sampling controllers): the elite-set update -- the K cheapest samples with
-    weight 1, info["elite_cost_max"] / ["elite_cost_min"] / ["elite_count"], see SamplingCore; sigma_period=m (covo-online only): every
-    m-th control step refreshes Sigma, the m - 1 between sample from the last factor shifted on the device, info["sigma_age"], see
-    SamplingCore; compute_post_cov (sampling controllers): the weighted 128 x 128 covariance of every step's own samples under its own
-    update's weights, info["post_cov"] / ["post_shift"] / ["post_weight"], see SamplingCore; sigma_adapt=gamma in [0, 1) (covo-online
-    with sigma_period > 1): a reuse step samples from the shifted blend of the covariance the previous step sampled from and that
-    step's posterior covariance (it implies compute_post_cov), info["sigma_adapt_fallback"] / ["sigma_adapt_scale"], see SamplingCore."""
+    """quadrotor.py:670-752.  compute_diag, compute_plan, ess_min, compute_fan, update, iters, elite, sigma_period, compute_post_cov and
+    sigma_adapt are the sampling controllers' step options -- what each does and what it adds to the controller's info dict:
+    controllers/_options.py."""
+    opts = take(locals())
     import torch
-    from .. import _lib
-    _lib.check_update(update)
-    online_name = "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name
-    _lib.check_sigma_period(sigma_period, online_name)
-    _lib.check_sigma_adapt(sigma_adapt, sigma_period, online_name)
-    _lib.check_iters(iters)
+    # ValueError before anything is built; the controller's own check, with N, follows
+    check_step_options(None, "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name, **opts)
 
     def parse_sample_params(param_text):
         if not param_text:
@@ -748,10 +658,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         control_params = controllers.MPPIParams(gamma_mean=1.0, gamma_sigma=0.0, discount=1.0, sample_sigma=sigma,
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
-                                          process_group=process_group, compute_info=compute_info,
-                                          compute_diag=compute_diag, compute_plan=compute_plan, ess_min=ess_min,
-                                          compute_fan=compute_fan, update=update, iters=iters, elite=elite,
-                                          compute_post_cov=compute_post_cov), control_params
+                                          process_group=process_group, compute_info=compute_info, **opts), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -762,11 +669,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
             a_cov=torch.eye(H * env.action_dim, dtype=torch.float32, device=device) * sigma ** 2,
             a_cov_offline=torch.zeros((H, env.action_dim, env.action_dim), dtype=torch.float32, device=device))
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
-                                          device=device, process_group=process_group,
-                                          compute_info=compute_info, compute_diag=compute_diag,
-                                          compute_plan=compute_plan, ess_min=ess_min, compute_fan=compute_fan,
-                                          update=update, iters=iters, elite=elite, sigma_period=sigma_period,
-                                          compute_post_cov=compute_post_cov, sigma_adapt=sigma_adapt), control_params
+                                          device=device, process_group=process_group, compute_info=compute_info,
+                                          **opts), control_params
     raise NotImplementedError(controller_name)
 
 

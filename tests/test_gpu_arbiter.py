@@ -553,14 +553,14 @@ def test_arbiter_refusals_leave_the_handle_usable():
     c.alias_outputs = True
     ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(41), params, (lib, h), DEV)
     cpe = c.reset(ep.state0, params, cp, cr.PRNGKey(42))
-    attach = core.attach_arbiter_log
-    core.attach_arbiter_log = lambda episode, rows_left: attach(episode, 5)
+    attach = core.attach_log
+    core.attach_log = lambda name, episode, rows_left: attach(name, episode, 5 if name == "arblog" else rows_left)
     before = ep.true.clone()
     with pytest.raises(CovoError, match="episode arbiter log"):
         c.run_episode(ep, params, cpe, cr.PRNGKey(43), 6)
     torch.cuda.synchronize()
     assert torch.equal(ep.true, before) and bool((ep.arblog == 0).all())
-    core.attach_arbiter_log = attach
+    del core.attach_log
     check(lib.covo_set_episode_arbiter_log(h, None, 0), "covo_set_episode_arbiter_log")
     fresh = SamplingCore(N, H, 0.01, 1.0, device=DEV, compute_info=False)
     with pytest.raises(CovoError, match="covo_set_step_arbiter"):

@@ -411,14 +411,14 @@ def test_fan_refusals_leave_the_handle_usable():
     c.alias_outputs = True
     ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(41), params, (lib, h), DEV)
     cpe = c.reset(ep.state0, params, cp, cr.PRNGKey(42))
-    attach = core.attach_fan_log
-    core.attach_fan_log = lambda episode, rows_left: attach(episode, 5)
+    attach = core.attach_log
+    core.attach_log = lambda name, episode, rows_left: attach(name, episode, 5 if name == "fanlog" else rows_left)
     before = ep.true.clone()
     with pytest.raises(CovoError, match="episode fan log"):
         c.run_episode(ep, params, cpe, cr.PRNGKey(43), 6)
     torch.cuda.synchronize()
     assert torch.equal(ep.true, before) and bool((ep.fanlog == 0).all())
-    core.attach_fan_log = attach
+    del core.attach_log
     check(lib.covo_set_episode_fan(h, None, 0), "covo_set_episode_fan")
     # the log needs a fan size
     fresh = SamplingCore(N, H, 0.01, 1.0, device=DEV, compute_info=False)

@@ -363,11 +363,11 @@ def test_refusals():
     c.alias_outputs = True
     ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(41), params, (core.lib, core.h), DEV)
     cp = c.reset(ep.state0, params, cp, cr.PRNGKey(42))
-    ep.alloc_trace()
-    real_view = ep.trace_view
-    ep.trace_view = lambda: real_view()[:5]
-    attach = core.attach_trace
-    core.attach_trace = lambda episode, rows_left: attach(episode, 5)
+    ep.alloc_log("trace")
+    real_segment = ep.log_segment
+    ep.log_segment = lambda name: real_segment(name)[:5] if name == "trace" else real_segment(name)
+    attach = core.attach_log
+    core.attach_log = lambda name, episode, rows_left: attach(name, episode, 5 if name == "trace" else rows_left)
     before = ep.true.clone()
     with pytest.raises(CovoError, match="episode trace"):
         c.run_episode(ep, params, cp, cr.PRNGKey(43), 6)
