@@ -829,8 +829,17 @@ typedef struct covo_batch_mode_args {
 int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params,
                                const uint32_t *keys, void *stream);
 
-/* Lower Cholesky factors of `batch` symmetric PD n x n fp32 matrices (n <= 128), the
- * factorisation inside jax.random.multivariate_normal (covo.py:216, mppi.py:59). */
+/* Lower Cholesky factors of `batch` symmetric PD n x n fp32 matrices (1 <= n <= 128, row-major, densely packed), the
+ * factorisation inside jax.random.multivariate_normal (covo.py:216, mppi.py:59).
+ *  - The input is symmetrised as (A + A^T)/2 in fp64, so BOTH triangles of A are read; the factorisation runs in fp64 and
+ *    is rounded once to fp32.  L_out receives the full n x n matrix: the factor in the lower triangle, +0.0f above it.
+ *  - A and L_out must not alias (nor overlap between matrices of the batch); A is not written.
+ *  - An input that is not positive definite is NOT detected: the status is 0 and non-finite entries appear from the failing
+ *    pivot's column on, in that matrix only; the columns before it and the other matrices of the batch are unaffected.
+ *  - n outside [1, 128], batch <= 0 or a null pointer: refused with a non-zero status, nothing is launched.
+ * Pinned for every n and dispatch path by tests/test_gpu_cholesky.py against LAPACK on the same symmetrised fp64 image, rounded
+ * to fp32: every entry within one fp32 ulp (plus a floor of 3.2e-12 max|L|), >= 99.9 % of the entries bit-identical (measured
+ * on the MI355X: 2 790 700 entries of 2 004 matrices, one of them 1 ulp off, all others bit-identical). */
 int covo_cholesky(covo_handle_t h, const float *A, int32_t n, int32_t batch, float *L_out, void *stream);
 
 /* One closed-loop ENVIRONMENT step on the device: Quad3D.step_env + get_info for the controllers'
