@@ -101,10 +101,7 @@ CASES = [("mppi", 1024, "0.01", False), ("mppi", 100, "5.0", True), ("covo-offli
          ("covo-offline", 40, "0.01", True)]
 
 
-@pytest.mark.parametrize("name,N,lam,rollover", CASES)
-@pytest.mark.parametrize("E", [1, 5, 32])
-@pytest.mark.parametrize("graph", ["graph", "eager"])
-def test_batched_mode_step_equals_replicas(name, N, lam, rollover, E, graph, monkeypatch):
+def _mode_step_equals_replicas(name, N, lam, rollover, E, graph, monkeypatch):
     """3 consecutive batched steps (eager first call, capture, replay -- or three eager calls) on E domain-randomised instances,
     each with its own mid-episode state, trajectory and key, under the GAUSSIAN disturbance (MPPI: every instance draws its own
     shared vector from its own key), with and without rollover termination: a_mean, the action buffer, the costs and MPPI's
@@ -138,6 +135,16 @@ def test_batched_mode_step_equals_replicas(name, N, lam, rollover, E, graph, mon
     assert b.core.device_status() == 0 and torch.isfinite(b.a_mean).all()
     if E > 1:
         assert (b.a_mean[0] - b.a_mean[1]).abs().max() > 1e-4  # different plants, different plans
+    b.core.close()
+    for i in inst:
+        i["c"].core.close()
+
+
+@pytest.mark.parametrize("name,N,lam,rollover", CASES)
+@pytest.mark.parametrize("E", [1, 5, 32])
+@pytest.mark.parametrize("graph", ["graph", "eager"])
+def test_batched_mode_step_equals_replicas(name, N, lam, rollover, E, graph, monkeypatch):
+    _mode_step_equals_replicas(name, N, lam, rollover, E, graph, monkeypatch)
 
 
 @pytest.mark.parametrize("name", ["covo-online", "mppi"])

@@ -215,14 +215,12 @@ def _batched(env, name, inst, N, **kw):
                                                 mode=name.split("-")[1], **kw)
 
 
-@pytest.mark.parametrize("E", [1, 5])
-@pytest.mark.parametrize("name,N", [("mppi", 100), ("covo-offline", 40), ("covo-online", 256)])
-def test_batched_iters_equal_replicas(name, N, E):
-    """Instance e of the env-batched step with iters=2 against a single-instance controller with iters=2 stepped on instance e
+def _batched_iters_case(name, N, E, k):
+    """Instance e of the env-batched step with iters=k against a single-instance controller with iters=k stepped on instance e
     alone, 3 steps (eager, capture, replay): torch.equal, the iteration log included."""
     env = _benv()
-    inst = _instances(env, name, N, E, iters=2)
-    b = _batched(env, name, inst, N, iters=2)
+    inst = _instances(env, name, N, E, iters=k)
+    b = _batched(env, name, inst, N, iters=k)
     b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
     if name == "covo-offline":
         tabs = []
@@ -231,7 +229,7 @@ def test_batched_iters_equal_replicas(name, N, E):
             i["cp"] = i["cp"].replace(a_cov_offline=cp.a_cov_offline, a_chol_offline=cp.a_chol_offline)
             tabs.append((cp.a_cov_offline, cp.a_chol_offline))
         b.set_tables(torch.stack([t[0] for t in tabs]), torch.stack([t[1] for t in tabs]))
-    assert tuple(b.iter_cost_min.shape) == (E, 2)
+    assert tuple(b.iter_cost_min.shape) == (E, k)
     for step in range(3):
         k_acts = []
         for i in inst:
@@ -245,7 +243,7 @@ def test_batched_iters_equal_replicas(name, N, E):
             assert torch.equal(b._a[e], i["c"].core.a) and torch.equal(b._cost[e], i["c"].core.cost), where
             assert torch.equal(u_b[e], u), where
             assert torch.equal(b.iter_cost_min[e], info["iter_cost_min"]), where
-            assert torch.equal(b.iter_cost_min[e, 1], b._cost[e].min()), where
+            assert torch.equal(b.iter_cost_min[e, k - 1], b._cost[e].min()), where
             if name == "mppi":
                 assert torch.equal(b.a_cov[e], i["cp"].a_cov), where
             i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u.cpu().numpy(), i["params"])
@@ -255,14 +253,20 @@ def test_batched_iters_equal_replicas(name, N, E):
         i["c"].core.close()
 
 
-def test_run_episode_with_iters_equals_the_python_loop():
-    """covo_run_episode, 8 steps of MPPI N = 256 with iters=2, against the Python loop of 8 __call__ / env step pairs with the same
+@pytest.mark.parametrize("E", [1, 5])
+@pytest.mark.parametrize("name,N", [("mppi", 100), ("covo-offline", 40), ("covo-online", 256)])
+def test_batched_iters_equal_replicas(name, N, E):
+    _batched_iters_case(name, N, E, 2)
+
+
+def _run_episode_case(k, n):
+    """covo_run_episode, n steps of MPPI N = 256 with iters=k, against the Python loop of n __call__ / env step pairs with the same
     keys: same log, final mean and rng."""
     env = _env("mppi")
     params = env.default_params
-    n, outs = 8, []
+    outs = []
     for fused in (False, True):
-        c = _controller(env, "mppi", 256, iters=2)
+        c = _controller(env, "mppi", 256, iters=k)
         c.alias_outputs = True
         ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(41), params, (c.core.lib, c.core.h), DEV)
         cp = c.reset(ep.state0, params, c.init_control_params, cr.PRNGKey(42))
@@ -280,7 +284,11 @@ def test_run_episode_with_iters_equals_the_python_loop():
         c.core.close()
     for x, y in zip(outs[0], outs[1]):
         assert np.array_equal(x, y)
-    assert outs[0][0].shape == (n, 4)
+    assert outs[0][0].shape == (n, 4) and outs[0][4].shape == (1, k)
+
+
+def test_run_episode_with_iters_equals_the_python_loop():
+    _run_episode_case(2, 8)
 
 
 def test_run_episode_batched_with_iters_equals_per_instance_loops():

@@ -627,13 +627,12 @@ def test_env_instances_with_domain_randomisation():
     assert np.abs(means[0] - means[1]).max() > 1e-4    # ... and get different plans
 
 
-def test_batched_step_equals_replicas():
-    """covo_mpc_step_batched (one graph, ONE Hessian + Sigma launch set for all env instances; BASELINE configs[4]
-    reduced to 3 instances, N = 4096) against 3 separate covo-online controllers on the same states / keys: plans and
-    Sigmas bit-identical at every step -- eager first call, capture on the second, graph replay afterwards."""
+def _batched_step_equals_replicas(N, E, steps):
+    """covo_mpc_step_batched (one graph, ONE Hessian + Sigma launch set for all env instances) against E separate covo-online
+    controllers on the same states / keys: plans and Sigmas bit-identical at every step -- eager first call, capture on the second,
+    graph replay afterwards."""
     import covo_mpc_amd as cm
     from covo_mpc_amd import random as cr
-    N, E = 4096, 3
     env = cm.envs.Quad3D(task="tracking", obs_type="quad_params", enable_randomizer=True, disturb_type="gaussian",
                          disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
     inst = []
@@ -647,7 +646,7 @@ def test_batched_step_equals_replicas():
     batched = cm.controllers.BatchedCoVOController(env, E, N, 32, 0.01, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                                    sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV)
     batched.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
-    for step in range(5):
+    for step in range(steps):
         k_acts = []
         for i in inst:
             i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
@@ -660,6 +659,15 @@ def test_batched_step_equals_replicas():
             assert torch.equal(u_b[e], u), (step, e)
             i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u.cpu().numpy(), i["params"])
     assert (batched.a_mean[0] - batched.a_mean[1]).abs().max() > 1e-4  # different plants, different plans
+    assert batched.core.device_status() == 0
+    batched.core.close()
+    for i in inst:
+        i["controller"].core.close()
+
+
+def test_batched_step_equals_replicas():
+    """BASELINE configs[4] reduced to 3 instances, N = 4096, five steps."""
+    _batched_step_equals_replicas(4096, 3, 5)
 
 
 def core_scalars(core, batch, count=24):

@@ -140,42 +140,60 @@ def test_period_one_equals_a_controller_without_the_argument(monkeypatch):
     cb.core.close()
 
 
-def test_period_three_refresh_reuse_reuse_refresh(monkeypatch):
-    """Step 0 is the plain step; step 1 and 2 shift the factor the step before left, report a_cov = Sigma' and sample clip(shifted mean
-    + L' eps) with the step's act key; step 3 is a plain controller's step from the same mean, state and key."""
-    monkeypatch.setenv("COVO_NO_GRAPH", "1")
+def _period_case(m, steps, graph, monkeypatch, gamma=0.0):
+    """`steps` steps at period m.  A refresh step (age 0) is a plain controller's step from the same mean, state and key; a reuse step
+    shifts -- with gamma > 0: adapts, from the posterior covariance the step before left -- the factor that step left, reports a_cov =
+    Sigma' and samples clip(shifted mean + L' eps) with the step's act key."""
+    monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
     N = 256
     env = _env()
-    ca, cpa, obs, info, state, params = _controller(env, N, sigma_period=3)
+    kw = dict(sigma_adapt=gamma) if gamma else {}
+    ca, cpa, obs, info, state, params = _controller(env, N, sigma_period=m, **kw)
     cb, cpb = _controller(env, N)[:2]
+    assert ca.core.uses_graph == (graph == "graph")
     helper = SamplingCore(N, 32, 0.01, 1.0, device=DEV, use_graph=False, compute_info=False)
     key = cr.PRNGKey(7)
-    L_prev = None
-    for step in range(4):
+    L_prev = C_prev = None
+    for step in range(steps):
         key, k_act, k_step = cr.split(key, 3)
         ua, cpa2, ia = ca(obs, state, params, k_act, cpa, info)
         torch.cuda.synchronize()
         age = ia["sigma_age"]
-        assert isinstance(age, int) and age == step % 3, (step, age)
+        assert isinstance(age, int) and age == step % m, (step, age)
         L_now = ca.core.sigma_factor()
         if age == 0:
             ub, cpb2, _ = cb(obs, state, params, k_act, cpa, info)  # the plain controller from the SAME mean
             torch.cuda.synchronize()
             assert torch.equal(ua, ub) and torch.equal(cpa2.a_mean, cpb2.a_mean) and torch.equal(cpa2.a_cov, cpb2.a_cov), step
             assert torch.equal(ca.core.a, cb.core.a) and torch.equal(ca.core.cost, cb.core.cost), step
+            if gamma:
+                assert (float(ia["sigma_adapt_fallback"]), float(ia["sigma_adapt_scale"])) == (0.0, 1.0), step
         else:
-            Sp, Lp = ca.core.sigma_shift(L_prev, cpa.sample_sigma)
+            if gamma:
+                Sp, Lp, rows = ca.core.sigma_adapt(L_prev, C_prev, gamma, cpa.sample_sigma)
+                assert float(ia["sigma_adapt_fallback"]) == float(rows[0]) and float(ia["sigma_adapt_scale"]) == float(rows[1]), step
+                assert float(rows[0]) in (0.0, 1.0), step
+            else:
+                Sp, Lp = ca.core.sigma_shift(L_prev, cpa.sample_sigma)
             assert torch.equal(cpa2.a_cov, Sp) and torch.equal(L_now, Lp), step
             _, act_key = cr.split(k_act)  # covo.py:212
             a_ref = helper.noise_gemm_philox(Lp, ca.core._bufs["a_mean_shift"], act_key)
             torch.cuda.synchronize()
             assert torch.equal(ca.core.a, a_ref), step
-            assert bool(torch.isfinite(cpa2.a_mean).all())
+        assert bool(torch.isfinite(cpa2.a_mean).all()), step
         L_prev, cpa = L_now, cpa2
+        if gamma:
+            C_prev = ia["post_cov"].clone()
         obs, state, _, _, info = env.step(k_step, state, ua.cpu().numpy(), params)
-    assert ca.core.sigma_age == 1 and ca.core.device_status() == 0
+    assert ca.core.sigma_age == steps % m and ca.core.device_status() == 0
     for c in (ca.core, cb.core, helper):
         c.close()
+
+
+def test_period_three_refresh_reuse_reuse_refresh(monkeypatch):
+    """Step 0 is the plain step; step 1 and 2 shift the factor the step before left, report a_cov = Sigma' and sample clip(shifted mean
+    + L' eps) with the step's act key; step 3 is a plain controller's step from the same mean, state and key."""
+    _period_case(3, 4, "eager", monkeypatch)
 
 
 def test_graph_equals_eager_over_three_periods(monkeypatch):
@@ -204,10 +222,9 @@ def test_graph_equals_eager_over_three_periods(monkeypatch):
     ce.core.close()
 
 
-def test_batched_online_equals_single():
-    """E = 2, N = 256, m = 2, four steps: row e of a_mean, a_cov, the costs and the factor is torch.equal to the single controller on
-    instance e alone; the batch shares one age."""
-    E, N, m = 2, 256, 2
+def _batched_period_case(E, N, m, steps):
+    """Row e of a_mean, a_cov, the costs and the factor is torch.equal to the single controller on instance e alone; the batch shares
+    one age."""
     env = _env(randomizer=True, task="tracking")
     inst = []
     for e in range(E):
@@ -219,7 +236,7 @@ def test_batched_online_equals_single():
     b = cm.controllers.BatchedCoVOController(env, E, N, 32, 0.01, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                              sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, sigma_period=m)
     b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
-    for step in range(4):
+    for step in range(steps):
         k_acts = []
         for i in inst:
             i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
@@ -240,6 +257,12 @@ def test_batched_online_equals_single():
     for i in inst:
         i["c"].core.close()
     b.core.close()
+
+
+def test_batched_online_equals_single():
+    """E = 2, N = 256, m = 2, four steps: row e of a_mean, a_cov, the costs and the factor is torch.equal to the single controller on
+    instance e alone; the batch shares one age."""
+    _batched_period_case(2, 256, 2, 4)
 
 
 @pytest.mark.parametrize("graph", ["graph", "eager"])

@@ -65,11 +65,78 @@ def shift_factor_ref(L, sample_sigma):
     return Lp @ Lp.T, Lp
 
 
+def shift_power_ref(Sigma, k, sample_sigma):
+    """c_k S^k(Sigma) written down directly: k shifts leave the trailing 128 - 4 k rows and columns of Sigma in the corner and k
+    copies of its last stage's 4 x 4 marginal B = Sigma[124:, 124:] below them, no cross terms; from k = 31 on that is 32 copies of
+    B, whatever k."""
+    Sigma = np.asarray(Sigma, dtype=np.float64)
+    j = min(int(k), N_A // DU - 1)
+    m = N_A - DU * j
+    S = np.zeros((N_A, N_A))
+    S[:m, :m] = Sigma[DU * j:, DU * j:]
+    for t in range(j):
+        S[m + DU * t:m + DU * t + DU, m + DU * t:m + DU * t + DU] = Sigma[N_A - DU:, N_A - DU:]
+    return volume_scalar(S, sample_sigma) * S
+
+
+def shift_chain_ref(L, k, sample_sigma, rounded=True, every=False):
+    """(Sigma', L') after k reuse steps in a row: shift_factor_ref applied k times, each step fed the previous one's L' rounded to
+    fp32 -- what the device keeps between steps (rounded=False: the fp64 L' as it is).  every=True: the list of all k results."""
+    out = []
+    for _ in range(int(k)):
+        Sp, Lp = shift_factor_ref(L, sample_sigma)
+        out.append((Sp, Lp))
+        L = Lp.astype(np.float32) if rounded else Lp
+    return out if every else out[-1]
+
+
+def decoupled_rows(k):
+    """After k shifts the rows from here on hold decoupled 4 x 4 stages only."""
+    return N_A - DU * min(int(k), N_A // DU - 1)
+
+
+BAR_L, BAR_SIGMA, BAR_LOGDET = 3e-6, 1e-6, 2 * N_A * 2.0 ** -24  # one reuse step's bars (tests/test_gpu_sigma_period.py)
+
+
+def off_structure(k):
+    """True where Sigma' and L' are exactly zero after k shifts: everything outside the leading corner and the decoupled 4 x 4 stages."""
+    m = decoupled_rows(k)
+    off = np.ones((N_A, N_A), dtype=bool)
+    off[:m, :m] = False
+    for t in range(m, N_A, DU):
+        off[t:t + DU, t:t + DU] = False
+    return off
+
+
+def chain_ratios(Sp, Lp, Sref, Lref, sample_sigma):
+    """(log det, L', Sigma') errors of an fp32 (Sigma', L') against a reference, each over its one-step bar."""
+    Sp64, Lp64 = np.asarray(Sp, dtype=np.float64), np.asarray(Lp, dtype=np.float64)
+    e_ld = abs(2.0 * np.log(np.diag(Lp64)).sum() - 2.0 * N_A * np.log(float(sample_sigma)))
+    e_L = np.abs(Lp64 - Lref).max() / np.abs(Lref).max()
+    e_S = np.abs(Sp64 - Sref).max() / np.abs(Sref).max()
+    return np.array([e_ld / BAR_LOGDET, e_L / BAR_L, e_S / BAR_SIGMA])
+
+
 def random_spd(rng, cond=1e3):
     w = np.exp(np.linspace(0.0, np.log(cond), N_A)) * 1e-2
     U, _ = np.linalg.qr(rng.normal(size=(N_A, N_A)))
     A = (U * w) @ U.T
     return 0.5 * (A + A.T)  # exactly symmetric
+
+
+def random_spd_factors():
+    """The fp32 factors of random_spd at cond 6e2 and 7e4 (the matrices of test_rank4_update_equals_the_cholesky_of_the_trailing_block)."""
+    rng = np.random.default_rng(12)
+    return [np.linalg.cholesky(random_spd(rng, cond)).astype(np.float32) for cond in (6e2, 7e4)]
+
+
+def golden_factors(sample_sigma, which=(0, 5, 9, 13)):
+    """The fp32 factors of covo.py's Sigma (oracle/ref_np.py::optimize_sigma) of matrices `which` of tests/golden/hessians_r03.npz."""
+    from oracle import ref_np as R
+    g = np.load(os.path.join(ROOT, "tests", "golden", "hessians_r03.npz"))
+    Rm = [m for k in g.files for m in g[k]]
+    return [np.linalg.cholesky(R.optimize_sigma(np.asarray(Rm[i], dtype=np.float64), sample_sigma, N_A // DU, DU)).astype(np.float32)
+            for i in which]
 
 
 # ---------------------------------------------------------------------------------------------- known answers of the restatement
@@ -134,6 +201,103 @@ def test_rank4_update_equals_the_cholesky_of_the_trailing_block():
         ref = np.linalg.cholesky(Sigma[DU:, DU:])
         assert np.abs(up - ref).max() < 1e-11 * np.abs(ref).max(), cond
         assert np.all(np.triu(up, 1) == 0.0)
+
+
+# ---------------------------------------------------------------------------------------------- k reuse steps in a row (m <= 64: k <= 63)
+def test_k_unrounded_steps_equal_the_closed_form():
+    rng = np.random.default_rng(13)
+    Sigma = random_spd(rng, 7e4)
+    chain = shift_chain_ref(np.linalg.cholesky(Sigma), 63, 0.5, rounded=False, every=True)
+    for k, (Sp, Lp) in enumerate(chain, start=1):
+        ref = shift_power_ref(Sigma, k, 0.5)
+        assert np.abs(Sp - ref).max() <= 1e-10 * np.abs(ref).max(), k
+        assert np.abs(Lp - np.linalg.cholesky(ref)).max() <= 1e-10 * np.abs(Lp).max(), k
+        assert abs(np.linalg.slogdet(ref)[1] - 2 * N_A * np.log(0.5)) < 1e-9, k
+        assert not Sp[off_structure(k)].any() and not Lp[off_structure(k)].any(), k
+        # ... and one more S of the previous closed form is the next one
+        if k > 1:
+            assert np.abs(shift_sigma_ref(shift_power_ref(Sigma, k - 1, 0.5), 0.5) - ref).max() <= 1e-12 * np.abs(ref).max(), k
+
+
+def test_closed_form_does_not_change_from_k_31_on():
+    rng = np.random.default_rng(14)
+    Sigma = random_spd(rng)
+    at31 = shift_power_ref(Sigma, 31, 0.5)
+    for k in (32, 33, 40, 63, 64, 1000):
+        assert np.array_equal(shift_power_ref(Sigma, k, 0.5), at31), k
+    assert not np.array_equal(shift_power_ref(Sigma, 30, 0.5), at31)
+    B = at31[N_A - DU:, N_A - DU:]
+    for t in range(N_A // DU):
+        assert np.array_equal(at31[DU * t:DU * t + DU, DU * t:DU * t + DU], B), t
+    assert not at31[off_structure(31)].any() and off_structure(31).sum() == N_A * N_A - 32 * 16
+    assert np.array_equal(off_structure(40), off_structure(31)) and decoupled_rows(63) == DU
+
+
+@pytest.mark.parametrize("k", [5, 40])
+def test_block_diagonal_blocks_move_up_k_times(k):
+    """test_block_diagonal_blocks_move_up_and_the_last_repeats carried to k shifts: block t of the result is c times block
+    min(t + k, 31) of the input -- by the closed form, by k applications of S, and by the factor route with fp32 between steps."""
+    rng = np.random.default_rng(5)
+    blocks = []
+    for t in range(32):
+        A = rng.normal(size=(4, 4))
+        blocks.append(A @ A.T + (0.5 + 0.1 * t) * np.eye(4))
+    Sigma = np.zeros((N_A, N_A))
+    for t, B in enumerate(blocks):
+        Sigma[4 * t:4 * t + 4, 4 * t:4 * t + 4] = B
+    sigma = 0.5
+    moved = [blocks[min(t + k, 31)] for t in range(32)]
+    want = np.zeros((N_A, N_A))
+    for t, B in enumerate(moved):
+        want[4 * t:4 * t + 4, 4 * t:4 * t + 4] = B
+    want *= volume_scalar(want, sigma)
+    Sp = shift_power_ref(Sigma, k, sigma)
+    assert np.abs(Sp - want).max() < 1e-12 * np.abs(want).max()
+    off = np.ones((N_A, N_A), dtype=bool)
+    for t in range(32):
+        off[4 * t:4 * t + 4, 4 * t:4 * t + 4] = False
+    assert not Sp[off].any()
+    assert abs(np.linalg.slogdet(Sp)[1] - 2 * N_A * np.log(sigma)) < 1e-10
+    it = Sigma
+    for _ in range(k):
+        it = shift_sigma_ref(it, sigma)
+    assert np.abs(it - want).max() < 1e-12 * np.abs(want).max() and not it[off].any()
+    S2, Lp = shift_chain_ref(np.linalg.cholesky(Sigma), k, sigma, rounded=False)
+    assert np.abs(S2 - want).max() < 1e-11 * np.abs(want).max() and not S2[off].any() and not Lp[off].any()
+
+
+def chain_against_the_closed_form(L32, sigma, where):
+    """The worst (log det, L', Sigma') ratio over k = 1 .. 63 of the fp32-rounded chain from the fp32 factor L32 against the closed
+    form of Sigma = L32 L32^T, and the k of each; asserts the exact zero structure of every step."""
+    Sigma = L32.astype(np.float64) @ L32.astype(np.float64).T
+    worst, at = np.zeros(3), np.zeros(3, dtype=int)
+    for k, (Sp, Lp) in enumerate(shift_chain_ref(L32, 63, sigma, every=True), start=1):
+        Sref = shift_power_ref(Sigma, k, sigma)
+        S32, Lp32 = Sp.astype(np.float32), Lp.astype(np.float32)
+        m = decoupled_rows(k)
+        assert np.all(Lp32[m:, :m] == 0.0) and not Lp32[off_structure(k)].any() and not S32[off_structure(k)].any(), (where, k)
+        assert np.all(np.triu(Lp32, 1) == 0.0) and np.array_equal(S32, S32.T), (where, k)
+        r = chain_ratios(S32, Lp32, Sref, np.linalg.cholesky(Sref), sigma)
+        at = np.where(r > worst, k, at)
+        worst = np.maximum(worst, r)
+    print(f"  {where}: fp32 chain against the closed form, worst ratio to the one-step bars over k <= 63: "
+          f"log det {worst[0]:.2f} (k = {at[0]}), L' {worst[1]:.2f} (k = {at[1]}), Sigma' {worst[2]:.2f} (k = {at[2]})")
+    return worst
+
+
+def test_fp32_chain_stays_within_the_one_step_bars_of_the_closed_form():
+    """63 reuse steps with L' rounded to fp32 between them do not drift: every step renormalises the volume, and a stage that has
+    decoupled is only ever copied and rescaled.  random_spd at cond 6e2 and 7e4: all three one-step bars hold at every k (worst
+    ratios 0.30 log det, 0.06 L', 0.30 Sigma').  Sigma of golden Hessians 0, 5, 9 and 13: the log det bar is a bound, not an
+    estimate -- the fp64 L' has log det 2 n log sigma and each diagonal entry moves by at most 2^-24 relative when rounded, all in
+    the same direction at worst, which k >= 30 comes close to (four diagonal values, each 31 times: 0.86 at k = 30) -- and is
+    asserted; the roundings of L' between the steps do add up in L' and Sigma' (worst 0.18 and 1.12 of the one-step bars, at
+    k = 28 and 25 of Hessian 13), which is why tests/test_gpu_ceilings.py holds the kernel's chain to a bar that includes this
+    chain's own error at the same k."""
+    for i, L32 in enumerate(random_spd_factors()):
+        assert np.all(chain_against_the_closed_form(L32, 0.5, ("random_spd", i)) <= 1.0)
+    for i, L32 in zip((0, 5, 9, 13), golden_factors(0.5)):
+        assert chain_against_the_closed_form(L32, 0.5, ("golden", i))[0] <= 1.0
 
 
 # ---------------------------------------------------------------------------------------------- the ABI and the keyword
