@@ -46,6 +46,13 @@ COVO_HAS_POST_COV = 1
 COVO_POST_AUX_FLOATS = 132  # the posterior covariance's side row of one instance: {shift d[128], W, 0, 0, 0} (covo_set_step_post_cov)
 COVO_HAS_SIGMA_ADAPT = 1
 COVO_SIGMA_ADAPT_FLOATS = 4  # Sigma adapt's row of one instance: {fallback, c, log det M, 0} (covo_set_step_sigma_adapt)
+COVO_HAS_EPISODE_ROWS = 1
+# the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
+COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
+COVO_EPLOG_KINDS = 6
+COVO_SIGMA_LOG_FLOATS = 4
+SIGMA_LOG_FIELDS = ("age", "fallback", "scale", "logdet")
+COVO_POST_COV_FLOATS = COVO_NA * COVO_NA  # a row of the posterior covariance log: the matrix [128][128]
 COVO_FLAG_ACTIONS_CLIPPED = 1
 
 
@@ -187,6 +194,7 @@ _SIGS = {
     "covo_weighted_cov": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P]),
     "covo_set_step_sigma_adapt": (C.c_int, [_P, C.c_float, _P, C.c_int32]),  # Sigma adapt (covo_hip.h: COVO_HAS_SIGMA_ADAPT)
     "covo_sigma_adapt": (C.c_int, [_P, _P, _P, C.c_int32, C.c_float, C.c_float, _P, _P, _P, _P]),
+    "covo_set_episode_rows": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # the attachments' episode logs (covo_hip.h: COVO_HAS_EPISODE_ROWS)
     "covo_set_step_plan": (C.c_int, [_P, _P, C.c_int32]),             # the flight recorder (covo_hip.h: COVO_HAS_PLAN_TRACE)
     "covo_set_episode_trace": (C.c_int, [_P, _P, C.c_int32]),
     "covo_rollout_fan": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P,

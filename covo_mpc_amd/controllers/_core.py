@@ -25,9 +25,19 @@ from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_
 from ._options import check_kernel_path, check_step_options, sharded_refusal, take
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
-# that attribute's value is the log's extra allocation argument: the fan's K)
-EPISODE_LOGS = {"diag_log": ("compute_diag", "covo_set_episode_diag_log", False), "trace": ("compute_plan", "covo_set_episode_trace", False),
-                "fanlog": ("compute_fan", "covo_set_episode_fan", True), "arblog": ("arb_mask", "covo_set_episode_arbiter_log", False)}
+# that attribute's value is the log's extra allocation argument: the fan's K, the iteration log's row width; covo_set_episode_rows' kind
+# or None for a log with a setter of its own; the episode attribute that has to ask for the log, or None: every episode keeps it)
+_ROWS = "covo_set_episode_rows"
+EPISODE_LOGS = {"diag_log": ("compute_diag", "covo_set_episode_diag_log", False, None, None),
+                "trace": ("compute_plan", "covo_set_episode_trace", False, None, None),
+                "fanlog": ("compute_fan", "covo_set_episode_fan", True, None, None),
+                "arblog": ("arb_mask", "covo_set_episode_arbiter_log", False, None, None),
+                "lamlog": ("ess_min", _ROWS, False, _lib.COVO_EPLOG_LAM, None),
+                "elitelog": ("elite", _ROWS, False, _lib.COVO_EPLOG_ELITE, None),
+                "iterlog": ("iters_logged", _ROWS, True, _lib.COVO_EPLOG_ITERS, None),
+                "sigmalog": ("sigma_logged", _ROWS, False, _lib.COVO_EPLOG_SIGMA, None),
+                "postlog": ("compute_post_cov", _ROWS, False, _lib.COVO_EPLOG_POST_AUX, None),
+                "postcovlog": ("compute_post_cov", _ROWS, False, _lib.COVO_EPLOG_POST_COV, "log_post_cov")}
 
 
 def shard_range(N: int, rank: int, world: int):
@@ -366,19 +376,35 @@ class SamplingCore:
     def attach_log(self, name, episode, rows_left: int):
         """Bind `episode`'s log `name` (EPISODE_LOGS; allocated on first use) for the segment that starts at episode.n_steps, when this
         core fills it."""
-        option, setter, sized = EPISODE_LOGS[name]
+        option, setter, sized, kind, asked = EPISODE_LOGS[name]
         on = getattr(self, option)
         if not on:
             return
+        ahead = () if kind is None else (kind,)
+        if asked is not None and not getattr(episode, asked, False):  # another episode's log must not stay bound
+            check(getattr(self.lib, setter)(self.h, *ahead, None, 0), setter)
+            return
         if getattr(episode, name, None) is None:
             episode.alloc_log(name, *((on,) if sized else ()))
-        check(getattr(self.lib, setter)(self.h, ptr(episode.log_segment(name)), int(rows_left)), setter)
+        check(getattr(self.lib, setter)(self.h, *ahead, ptr(episode.log_segment(name)), int(rows_left)), setter)
 
     def attach_episode_logs(self, episode, rows_left: int):
         """Bind every log of `episode` this core fills -- diagnostic log (compute_diag), trace (compute_plan), fan log (compute_fan),
-        arbiter log (update) -- for the segment that starts at episode.n_steps: step k of it writes row n_steps + k of each."""
+        arbiter log (update), temperature log (ess_min), elite log (elite), iteration log (iters), Sigma log (sigma_period), the
+        posterior covariance's side-row log (compute_post_cov) and, for an episode built with log_post_cov, its matrix log -- for the
+        segment that starts at episode.n_steps: step k of it writes row n_steps + k of each."""
         for name in EPISODE_LOGS:
             self.attach_log(name, episode, rows_left)
+
+    @property
+    def iters_logged(self) -> int:
+        """The width of the iteration log's rows: iters, or 0 when the core runs one pass per step (no rows)."""
+        return self.iters if self.iters > 1 else 0
+
+    @property
+    def sigma_logged(self) -> bool:
+        """A Sigma period is on: the steps have an age to log."""
+        return self.sigma_period > 1
 
     def diag_info(self) -> dict:
         """{"ess", "cost_min", "cost_weighted", "cost_mean"} of the last step as 0-d views of self.diag (no sync, no copy); {} when
@@ -817,7 +843,7 @@ class SamplingCore:
         key = (C.c_uint32 * 2)(int(rng[0]), int(rng[1]))
         env = episode.env
         # step k of the segment also writes row n_steps + k of the episode's [T + 1, 8] diagnostic log, [T + 1, 168] trace (true
-        # state, noisy state, u, plan), [T + 1, K, 100] fan log and [T + 1, 8] arbiter log
+        # state, noisy state, u, plan), [T + 1, K, 100] fan log, [T + 1, 8] arbiter log and the logs of the attachments' rows
         self.attach_episode_logs(episode, int(episode.log.shape[0]) - int(episode.n_steps))
         # the env step's auto-reset (base.py:22-40) is a property of the EPISODE, the model constants come from the controller
         params_c = type(params_c).from_buffer_copy(params_c)

@@ -216,6 +216,7 @@ class BatchedCoVOController:
         env = self.env
         keys = np.ascontiguousarray(np.asarray(rngs, dtype=np.uint32).reshape(self.E, 2)).copy()
         # rows n_steps .. of the [E, T + 1, 8] diagnostic log, [E, T + 1, 168] trace, [E, T + 1, K, 100] fan log, [E, T + 1, 8] arbiter log
+        # and the logs of the attachments' rows (temperature, elite, iterations, Sigma, posterior covariance)
         self.core.attach_episode_logs(episode, int(episode.log.shape[1]))
         online = self.mode == _lib.MODE_COVO_ONLINE
         fn = self.core.lib.covo_run_episode_batched if online else self.core.lib.covo_run_episode_batched_mode

@@ -704,6 +704,7 @@ int covo_set_step_ess_floor(covo_handle_t h, float ess_min, float *lam_out, int3
     h->ess_min = ess_min;
     h->lam_out = lam_out;
     h->lam_n = lam_out ? n_inst : 0;
+    if (covo_lam_target(h) == nullptr) covo_eprow_drop(h, COVO_EPLOG_LAM);  // off, the log with it
     return 0;
 }
 
@@ -732,6 +733,7 @@ int covo_set_step_elite(covo_handle_t h, int32_t K, float *rows_out, int32_t n_i
     h->elite_K = K;
     h->elite_out = rows_out;
     h->elite_n = rows_out ? n_inst : 0;
+    if (covo_elite_target(h) == nullptr) covo_eprow_drop(h, COVO_EPLOG_ELITE);  // off, the log with it
     return 0;
 }
 
@@ -873,6 +875,8 @@ int covo_set_step_post_cov(covo_handle_t h, float *cov, float *aux, int32_t n_in
     if (cov == nullptr) {  // off
         h->post_cov_out = h->post_aux_out = nullptr;
         h->post_n = 0;
+        covo_eprow_drop(h, COVO_EPLOG_POST_AUX);  // the logs with it
+        covo_eprow_drop(h, COVO_EPLOG_POST_COV);
         return 0;
     }
     REQUIRE(aux != nullptr, "covo_set_step_post_cov: aux is null (float[n_inst][%d])", COVO_POST_AUX_FLOATS);
@@ -928,6 +932,7 @@ int covo_set_step_iters(covo_handle_t h, int32_t iters, float *iter_log, int32_t
     h->iter_log = on ? iter_log : nullptr;
     h->iter_n = on ? n_inst : 0;
     if (covo_step_iters(h) != before || h->iter_log != log_before) ++h->opt.epoch;
+    if (covo_step_iters(h) != before) covo_eprow_drop(h, COVO_EPLOG_ITERS);  // off or another row width: the log goes
     return 0;
 }
 
@@ -941,6 +946,7 @@ int covo_set_step_sigma_period(covo_handle_t h, int32_t period)
             "computes its own Sigma)", period, COVO_MAX_SIGMA_PERIOD);
     h->sigma_period = period;
     h->sigma_age = 0;
+    if (covo_sigma_period(h) == 1) covo_eprow_drop(h, COVO_EPLOG_SIGMA);  // off, the log with it
     return 0;
 }
 
@@ -999,6 +1005,32 @@ int covo_sigma_adapt(covo_handle_t h, const float *L_in, const float *C, int32_t
     return launch_sigma_adapt(L_in, C, batch, gamma, sample_sigma, Sigma_out, L_out, rows_out, (hipStream_t)stream);
 }
 
+// ---- the episode logs of the attachments' rows (episode_rows.hip).  The copy is one eager launch of the episode drivers behind the
+// step: attaching or detaching a log changes no captured step graph
+int covo_set_episode_rows(covo_handle_t h, int32_t kind, float *log, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_rows: null handle");
+    REQUIRE(kind >= 0 && kind < COVO_EPLOG_KINDS, "covo_set_episode_rows: kind=%d outside [0, %d) (COVO_EPLOG_*)", kind, COVO_EPLOG_KINDS);
+    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_rows: stride=%d", stride);
+    if (log != nullptr) {
+        const struct {
+            bool on;
+            const char *what;
+        } needs[COVO_EPLOG_KINDS] = {
+            {covo_lam_target(h) != nullptr, "no ESS floor attached: call covo_set_step_ess_floor (ess_min > 0) first"},
+            {covo_elite_target(h) != nullptr, "no elite-set update attached: call covo_set_step_elite (K > 0) first"},
+            {covo_step_iters(h) > 1, "no iteration log attached: call covo_set_step_iters (iters > 1, iter_log) first"},
+            {covo_sigma_period(h) > 1, "no Sigma period: call covo_set_step_sigma_period (period > 1) first"},
+            {covo_post_cov_on(h), "no posterior covariance attached: call covo_set_step_post_cov first"},
+            {covo_post_cov_on(h), "no posterior covariance attached: call covo_set_step_post_cov first"},
+        };
+        REQUIRE(needs[kind].on, "covo_set_episode_rows: kind=%d: %s", kind, needs[kind].what);
+    }
+    h->eprow_log[kind] = log;
+    h->eprow_stride[kind] = log ? stride : 0;
+    return 0;
+}
+
 // ---- what a step checks about everything attached to its handle -- diagnostics, plan / trace, sample fan, update arbiter, ESS floor,
 // iterations, elite set -- for every entry point alike (covo_mpc_step, covo_run_episode and, through check_batch_step, the four env-batched
 // ones): a step of n_samples samples for n_inst instances.  The order is fixed: first what a sample-sharded step
@@ -1039,6 +1071,9 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                 "%s: Sigma adapt (covo_set_step_sigma_adapt, gamma=%g) is not available for sample-sharded steps (partial_out != NULL): "
                 "it needs the Sigma period and the posterior covariance, which sample-sharded steps cannot have; turn it off (gamma = 0)",
                 what, (double)h->adapt_gamma);
+        REQUIRE(!covo_eprow_any(h),
+                "%s: the episode logs of the attachments' rows (covo_set_episode_rows) are not available for sample-sharded steps "
+                "(partial_out != NULL): none of the attachments they follow is; detach them", what);
     }
     REQUIRE(covo_diag_target(h) == nullptr || n_inst <= covo_diag_capacity(h),
             "%s: %d instances, the diagnostic buffer (covo_set_step_diag) has %d rows", what, n_inst, covo_diag_capacity(h));
@@ -1110,6 +1145,14 @@ static int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, con
         {"episode trace", "covo_set_episode_trace", h->trace != nullptr, h->trace_stride},
         {"episode fan log", "covo_set_episode_fan", h->fanlog != nullptr, h->fanlog_stride},
         {"episode arbiter log", "covo_set_episode_arbiter_log", h->arblog != nullptr, h->arblog_stride},
+        {"episode temperature log", "covo_set_episode_rows, COVO_EPLOG_LAM", h->eprow_log[COVO_EPLOG_LAM] != nullptr, h->eprow_stride[COVO_EPLOG_LAM]},
+        {"episode elite log", "covo_set_episode_rows, COVO_EPLOG_ELITE", h->eprow_log[COVO_EPLOG_ELITE] != nullptr, h->eprow_stride[COVO_EPLOG_ELITE]},
+        {"episode iteration log", "covo_set_episode_rows, COVO_EPLOG_ITERS", h->eprow_log[COVO_EPLOG_ITERS] != nullptr, h->eprow_stride[COVO_EPLOG_ITERS]},
+        {"episode Sigma log", "covo_set_episode_rows, COVO_EPLOG_SIGMA", h->eprow_log[COVO_EPLOG_SIGMA] != nullptr, h->eprow_stride[COVO_EPLOG_SIGMA]},
+        {"episode posterior side-row log", "covo_set_episode_rows, COVO_EPLOG_POST_AUX", h->eprow_log[COVO_EPLOG_POST_AUX] != nullptr,
+         h->eprow_stride[COVO_EPLOG_POST_AUX]},
+        {"episode posterior covariance log", "covo_set_episode_rows, COVO_EPLOG_POST_COV", h->eprow_log[COVO_EPLOG_POST_COV] != nullptr,
+         h->eprow_stride[COVO_EPLOG_POST_COV]},
     };
     for (const auto &l : logs)
         REQUIRE(!l.on || (first_row >= 0 && first_row + n_steps <= l.rows), "%s: %s rows [%d, %d) outside [0, %d) (%s)", what, l.name,
@@ -1243,6 +1286,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
         }
         if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, 1, h->diag_log_stride, t, s))) return rc;
         if ((rc = covo_plan_after_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, t, s))) return rc;
+        // (behind the after-step frame: the posterior covariance's rows are formed there)
+        if (covo_eprow_any(h) && (rc = launch_episode_rows(h, 1, t, h->sigma_last_age, s))) return rc;
         rc = launch_env_step(state_true, const_cast<float *>(args->state), args->pos_traj, args->vel_traj, acc_traj, args->T,
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
@@ -1380,6 +1425,7 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             return rc;
         if ((rc = covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : norm.mode, params, states_true, log_index + t, s)))
             return rc;
+        if (covo_eprow_any(h) && (rc = launch_episode_rows(h, E, log_index + t, h->sigma_last_age, s))) return rc;
         if ((rc = launch_env_step_batched(states_true, const_cast<float *>(args->states), args->pos_traj, args->vel_traj, acc_traj,
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
                                           log_stride, log_index + t, s)))

@@ -102,7 +102,21 @@ struct covo_ctx {
     float adapt_gamma;        // the weight of the previous step's posterior covariance in a reuse step's Sigma', in (0, 1)
     float *adapt_rows;        // caller's [adapt_n][COVO_SIGMA_ADAPT_FLOATS]: instance e's {fallback, c, log det M, 0} of every reuse step
     int adapt_n;
+    // the episode logs of the attachments' rows (covo_set_episode_rows; episode_rows.hip), by COVO_EPLOG_* kind; null: off
+    float *eprow_log[COVO_EPLOG_KINDS];   // caller's [n_inst][eprow_stride[k]][width of kind k]: the episode drivers copy each step's rows there
+    int eprow_stride[COVO_EPLOG_KINDS];
 };
+static inline void covo_eprow_drop(covo_ctx *h, int kind)
+{
+    h->eprow_log[kind] = nullptr;
+    h->eprow_stride[kind] = 0;
+}
+static inline bool covo_eprow_any(const covo_ctx *h)
+{
+    for (int k = 0; k < COVO_EPLOG_KINDS; ++k)
+        if (h->eprow_log[k] != nullptr) return true;
+    return false;
+}
 static inline bool covo_post_cov_on(const covo_ctx *h) { return h->post_cov_out != nullptr; }
 static inline bool covo_sigma_adapt_on(const covo_ctx *h) { return h->adapt_rows != nullptr && h->adapt_gamma > 0.0f; }
 // passes per control step of this handle (1: today's step) and where pass j of instance 0 logs its cost minimum (instance e: + e * iters)
@@ -520,6 +534,9 @@ int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, 
 int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_t s, const void **inst_dev);  // step.hip
 // the episode drivers: row e of the step's diagnostics -> row `index` of instance e's diagnostic log
 int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s);
+// episode_rows.hip: the rows the step that has just been enqueued (the one that ran at Sigma age `age`) left in its attachments ->
+// row `index` of every instance's attached covo_set_episode_rows log (no-op with none attached)
+int launch_episode_rows(const covo_ctx *h, int n_inst, int index, int age, hipStream_t s);
 // after_step.hpp, plan_trace.hip, sample_fan.hip, update_arbiter.hip: what the launches behind a step need to know about ONE instance of
 // the step that has just been enqueued -- the inputs its sample rollouts had.  key_mem (batched steps): the instance's raw rng_act in device memory; else key / f_shared as covo_mpc_step got them
 struct PlanInstDesc {

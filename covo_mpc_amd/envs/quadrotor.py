@@ -283,6 +283,42 @@ def split_arbiter_rows(rows: np.ndarray) -> dict:
             "best": np.ascontiguousarray(rows[..., 5]).view(np.int32)}
 
 
+def _split_fields(rows: np.ndarray, fields, words=()) -> dict:
+    """Rows [.., len(fields) or more] -> {field: rows[.., i]}; the fields named in `words` hold uint32 bits and come back as such."""
+    out = {}
+    for i, name in enumerate(fields):
+        col = rows[..., i]
+        out[name] = np.ascontiguousarray(col).view(np.uint32) if name in words else col
+    return out
+
+
+def split_lam_rows(rows: np.ndarray) -> dict:
+    """Temperature rows [.., 4] (include/covo_hip.h: covo_set_step_ess_floor) -> {lam_eff, inv_lam_eff, ess_lam0, evaluations}, each [..]."""
+    from .. import _lib
+    return _split_fields(rows, _lib.LAM_FIELDS)
+
+
+def split_elite_rows(rows: np.ndarray) -> dict:
+    """Selector rows [.., 8] (include/covo_hip.h: covo_set_step_elite) -> {threshold_cost_word, threshold_index_word (uint32), cost_min,
+    cost_kth, K, ties}, each [..]."""
+    from .. import _lib
+    return _split_fields(rows, _lib.ELITE_FIELDS, words=("threshold_cost_word", "threshold_index_word"))
+
+
+def split_sigma_rows(rows: np.ndarray) -> dict:
+    """Sigma log rows [.., 4] (include/covo_hip.h: covo_set_episode_rows) -> {age (int32: 0 = the step refreshed Sigma), fallback, scale,
+    logdet}, each [..]; {fallback, scale, logdet} are Sigma adapt's {fallback, c, log det M}, {0, 1, 0} without it."""
+    from .. import _lib
+    out = _split_fields(rows, _lib.SIGMA_LOG_FIELDS)
+    out["age"] = out["age"].astype(np.int32)
+    return out
+
+
+def split_post_rows(rows: np.ndarray) -> dict:
+    """Side rows [.., 132] (include/covo_hip.h: covo_set_step_post_cov) -> {shift [.., 128], weight [..]}."""
+    return {"shift": rows[..., :128], "weight": rows[..., 128]}
+
+
 def unpack_state_row(row: np.ndarray) -> dict:
     """One packed state float32[32] (include/covo_hip.h "Data layouts") -> the EnvState3D fields it carries."""
     return {"pos": row[0:3].copy(), "vel": row[3:6].copy(), "quat": row[6:10].copy(), "omega": row[10:13].copy(),
@@ -291,20 +327,33 @@ def unpack_state_row(row: np.ndarray) -> dict:
 
 
 class _EpisodeLogs:
-    """The four logs an episode driver can fill next to the env log, one row per enqueued step: `diag_log` (sampling diagnostics),
-    `trace` (the flight recorder), `fanlog` (the sample fan), `arblog` (the update arbiter).  Each is None until a controller built
-    with its option runs the episode (SamplingCore.attach_log allocates it on first use), shaped like the env log `self.log` with
+    """The logs an episode driver can fill next to the env log, one row per enqueued step: `diag_log` (sampling diagnostics),
+    `trace` (the flight recorder), `fanlog` (the sample fan), `arblog` (the update arbiter), and the rows of the step attachments
+    (covo_set_episode_rows): `lamlog` (the ESS floor's temperature), `elitelog` (the elite set's selector), `iterlog` (the passes' cost
+    minima), `sigmalog` (the Sigma period's age, Sigma adapt's row), `postlog` (the posterior covariance's side row) and `postcovlog`
+    (its matrix: 64 KiB per step and instance, kept only by an episode built with log_post_cov=True).  Each is None until a controller
+    built with its option runs the episode (SamplingCore.attach_log allocates it on first use), shaped like the env log `self.log` with
     the log's own row in place of the 4 floats: [T + 1, ...] for one instance, [E, T + 1, ...] for E (STEP_AXIS: the step axis)."""
     STEP_AXIS = 0
-    # attribute: (the row's width in _lib, what splits the rows read back, what the log is called, the option that fills it)
+    log_post_cov = False
+    # attribute: (the row's width in _lib -- None: alloc_log's argument is the width --, what splits the rows read back, what the log is
+    # called, the option that fills it)
     LOGS = {"diag_log": ("COVO_DIAG_FLOATS", None, "diagnostic log", "compute_diag=True"),         # rows [8]
             "trace": ("COVO_TRACE_FLOATS", split_trace_rows, "trace", "compute_plan=True"),          # rows [168]
             "fanlog": ("COVO_FAN_FLOATS", split_fan_rows, "fan log", "compute_fan=K"),               # rows [K, 100]: alloc_log("fanlog", K)
-            "arblog": ("COVO_ARB_FLOATS", split_arbiter_rows, "arbiter log", "update='best' or 'guarded'")}  # rows [8]
+            "arblog": ("COVO_ARB_FLOATS", split_arbiter_rows, "arbiter log", "update='best' or 'guarded'"),  # rows [8]
+            "lamlog": ("COVO_LAM_FLOATS", split_lam_rows, "temperature log", "ess_min"),            # rows [4]
+            "elitelog": ("COVO_ELITE_FLOATS", split_elite_rows, "elite log", "elite=K"),              # rows [8]
+            "iterlog": (None, None, "iteration log", "iters=k > 1"),                                  # rows [k]: alloc_log("iterlog", k)
+            "sigmalog": ("COVO_SIGMA_LOG_FLOATS", split_sigma_rows, "Sigma log", "sigma_period=m > 1"),  # rows [4]
+            "postlog": ("COVO_POST_AUX_FLOATS", split_post_rows, "posterior side-row log", "compute_post_cov=True"),  # rows [132]
+            "postcovlog": ("COVO_POST_COV_FLOATS", None, "posterior covariance log",
+                           "compute_post_cov=True, in an episode built with log_post_cov=True")}      # rows [128 * 128]
 
     def alloc_log(self, name, *inner):
         import torch
-        shape = tuple(self.log.shape[:-1]) + tuple(int(n) for n in inner) + (getattr(self._lib, self.LOGS[name][0]),)
+        width = self.LOGS[name][0]
+        shape = tuple(self.log.shape[:-1]) + tuple(int(n) for n in inner) + ((getattr(self._lib, width),) if width else ())
         setattr(self, name, torch.zeros(shape, dtype=torch.float32, device=self.device))
 
     def log_segment(self, name):
@@ -345,6 +394,38 @@ class _EpisodeLogs:
         covo_set_step_arbiter), under a controller built with update="best" / "guarded"."""
         return self._read("arblog")
 
+    def read_lam(self):
+        """-> {lam_eff [n], inv_lam_eff [n], ess_lam0 [n], evaluations [n]}: per enqueued step the ESS floor's solver row
+        (include/covo_hip.h: covo_set_step_ess_floor), under a controller built with ess_min."""
+        return self._read("lamlog")
+
+    def read_elite(self):
+        """-> {threshold_cost_word [n], threshold_index_word [n] (uint32), cost_min [n], cost_kth [n], K [n], ties [n]}: per enqueued
+        step the elite set's selector row (include/covo_hip.h: covo_set_step_elite; the last pass's under iters), under a controller
+        built with elite."""
+        return self._read("elitelog")
+
+    def read_iters(self):
+        """-> float32 [n, k]: per enqueued step the minimum sample cost of each of its k passes (include/covo_hip.h:
+        covo_set_step_iters), under a controller built with iters=k > 1."""
+        return self._read("iterlog")
+
+    def read_sigma(self):
+        """-> {age [n] (int32: 0 = the step refreshed Sigma), fallback [n], scale [n], logdet [n]}: per enqueued step the age it ran at
+        and Sigma adapt's row (include/covo_hip.h: covo_set_episode_rows; {0, 1, 0} without sigma_adapt), under a controller built with
+        sigma_period > 1."""
+        return self._read("sigmalog")
+
+    def read_post(self):
+        """-> {shift [n, 128], weight [n]} and, in an episode built with log_post_cov=True, cov [n, 128, 128]: per enqueued step the
+        posterior covariance's side row and matrix (include/covo_hip.h: covo_set_step_post_cov), under a controller built with
+        compute_post_cov (or sigma_adapt)."""
+        out = self._read("postlog")
+        if self.postcovlog is not None:
+            cov = self._read("postcovlog")
+            out["cov"] = cov.reshape(cov.shape[:-1] + (128, 128))
+        return out
+
 
 class DeviceEpisode(_EpisodeLogs):
     """One episode whose env state lives on the device: the true state, its noisy copy (what the
@@ -356,10 +437,11 @@ class DeviceEpisode(_EpisodeLogs):
     stores reset_env(key_reset)'s state, noisy copy and a NEW trajectory (written over pos_traj / vel_traj / acc_traj in place);
     the log row then carries the reset state's errors and done = 1.  `state0` keeps the first reset's host state."""
 
-    def __init__(self, env: "Quad3D", key, params, lib_handle, device, auto_reset: bool = True):
+    def __init__(self, env: "Quad3D", key, params, lib_handle, device, auto_reset: bool = True, log_post_cov: bool = False):
         import torch
         from .. import _lib
         self.env, self.params, self.device = env, params, device
+        self.log_post_cov = bool(log_post_cov)  # also keep every step's posterior covariance matrix (19.7 MB per 300 steps)
         self.lib, self.h = lib_handle
         self._lib = _lib
         obs, info, state = env.reset(key, params)
@@ -426,11 +508,12 @@ class BatchedDeviceEpisode(_EpisodeLogs):
     episodes (control step + env step for all instances) from one C call.  auto_reset: as DeviceEpisode, per instance."""
     STEP_AXIS = 1
 
-    def __init__(self, env: "Quad3D", keys, params_list, lib_handle, device, auto_reset: bool = True):
+    def __init__(self, env: "Quad3D", keys, params_list, lib_handle, device, auto_reset: bool = True, log_post_cov: bool = False):
         import torch
         from .. import _lib
         from ..controllers.base import env_model_params_c
         self.env, self.params, self.device = env, list(params_list), device
+        self.log_post_cov = bool(log_post_cov)  # also keep every step's posterior covariance matrices (19.7 MB per instance and 300 steps)
         self.lib, self.h = lib_handle
         self._lib = _lib
         self.E = len(self.params)
@@ -487,7 +570,8 @@ class BatchedDeviceEpisode(_EpisodeLogs):
 
 def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H32_lam0.01", n_steps=None, seed: int = 1, device=None,
                      verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
-                     arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0):
+                     arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0,
+                     rows: bool = False):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]; with trace=True
@@ -495,7 +579,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     rollouts of every step of every instance -- is appended to the returned tuple.  update: the controller's update rule ("softmax" |
     "best" | "guarded"); arbiter=True (with "best" / "guarded") appends ep.read_arbiter(), every step's arbiter row.  diag / trace / fan
     are the step options compute_diag / compute_plan / compute_fan, update / iters / elite / sigma_period / sigma_adapt the options of
-    those names (controllers/_options.py)."""
+    those names (controllers/_options.py).  rows=True appends one dict {"elite": ep.read_elite(), "iters": ep.read_iters(), "sigma":
+    ep.read_sigma(), "post": ep.read_post()} -- every step's rows of the attachments -- holding the entries whose option is on."""
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
     check_step_options(None, "online", **opts)  # ValueError before anything is built
     if arbiter and update == "softmax":
@@ -527,13 +612,18 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                   f"; steps with ess > 0.9 N per instance: {' '.join(str(int(v)) for v in blind)} (of {T})")
     out = ((log[:, :, 1].mean(axis=1),) + ((ep.read_trace(),) if trace else ()) + ((ep.read_fan(),) if fan else ()) +
            ((ep.read_arbiter(),) if arbiter else ()))
+    if rows:
+        reads = {"elite": ("elitelog", ep.read_elite), "iters": ("iterlog", ep.read_iters), "sigma": ("sigmalog", ep.read_sigma),
+                 "post": ("postlog", ep.read_post)}
+        out += ({name: read() for name, (attr, read) in reads.items() if getattr(ep, attr) is not None},)
     return out if len(out) > 1 else out[0]
 
 
-def eval_env_device(env: Quad3D, controller, total_steps=30000, num_trajs=4, seed=1, verbose=True):
+def eval_env_device(env: Quad3D, controller, total_steps=30000, num_trajs=4, seed=1, verbose=True, on_episode=None):
     """eval_env (quadrotor.py:506-591) with the env step on the device: same key threading, same protocol (num_trajs
     reset keys x episodes x max_steps_in_episode steps, mean/std over episodes of the mean position error), one host
-    sync per EPISODE instead of one per step."""
+    sync per EPISODE instead of one per step.  on_episode(ep): called with every finished DeviceEpisode, its log read -- where a caller
+    reads the episode's other logs (read_lam, read_sigma, read_iters, ...)."""
     rng = crandom.PRNGKey(seed)
     T = env.default_params.max_steps_in_episode
     core = controller.core
@@ -556,6 +646,8 @@ def eval_env_device(env: Quad3D, controller, total_steps=30000, num_trajs=4, see
                 ep.step(rng_step, action)
                 rng, rng_control = crandom.split(rng)
         log = ep.read_log()
+        if on_episode is not None:
+            on_episode(ep)
         # info["err_pos"] of step t is the error of the state BEFORE that step (quadrotor.py:352); the host loop
         # records it after each env.step, i.e. rows 0..T-1 of the log
         return rng, log[:, 1]
@@ -682,8 +774,8 @@ def render_env(env: Quad3D, controller, control_params, repeat_times=1, filename
     :656; the device handle `traj_dev` left out) plus `reward`, and -- under a controller built with compute_plan -- `u`,
     `pos_plan` [H, 3] and `cost_plan`: the action the step applied and the controller's own plan (include/covo_hip.h); under one built with compute_fan=K also
     `fan_pos` [K, H, 3], `fan_cost` [K] and `fan_idx` [K]: K of the step's sampled rollouts around that plan; under one built with
-    compute_post_cov also `post_cov` [128, 128] and `post_shift` [128] (such a controller takes the host path: the episode drivers keep
-    no log of the matrices).  No plotting
+    compute_post_cov also `post_cov` [128, 128] and `post_shift` [128] (such a controller takes the host path: moving it onto the
+    episode drivers' matrix log would change the noise realisation of the command, see DEVIATION below).  No plotting
     (utils.plot_states, :661, stays out of scope).
     Host path (controllers without a `core` or without compute_plan, host_env=True, repeat_times > 1): the Python loop with the
     reference's per-step keys (rng, rng_act, rng_step = split(rng, 3), :617); on `done` the parameters are re-sampled and the

@@ -697,6 +697,39 @@ int covo_weighted_cov(covo_handle_t h, const float *a, const float *cost, const 
 int covo_set_step_sigma_adapt(covo_handle_t h, float gamma, float *rows_out /* DEVICE float[n_inst][4]; NULL = off */, int32_t n_inst);
 int covo_sigma_adapt(covo_handle_t h, const float *L_in, const float *C, int32_t batch, float gamma, float sample_sigma, float *Sigma_out,
                      float *L_out, float *rows_out, void *stream);
+
+/* Episode logs of the rows the step attachments above leave on the handle (additive to ABI 10: COVO_HAS_EPISODE_ROWS; off by
+ * default, and off changes nothing a caller can observe: no launch is added).  Every step overwrites its attachments' rows; an episode
+ * driver (covo_run_episode, covo_run_episode_batched, covo_run_episode_batched_mode) with one of these logs attached copies the rows of
+ * every step it enqueues into the log, bit for bit, by ONE eager launch per step for all attached kinds and instances
+ * (csrc/episode_rows.hip), behind the step and its after-step launches and ahead of the env step.  No captured step graph changes.
+ *   kind                  row                                  the step attachment it follows
+ *   COVO_EPLOG_LAM        float[COVO_LAM_FLOATS]               covo_set_step_ess_floor's solver row
+ *   COVO_EPLOG_ELITE      float[COVO_ELITE_FLOATS]             covo_set_step_elite's selector row
+ *   COVO_EPLOG_ITERS      float[iters]                         covo_set_step_iters' row (the width is the attached iters)
+ *   COVO_EPLOG_SIGMA      float[COVO_SIGMA_LOG_FLOATS]         {age the step ran at (covo_step_sigma_age's last_age, as a float), fallback,
+ *                                                              c, log det M}: the last three are covo_set_step_sigma_adapt's row, {0, 1, 0}
+ *                                                              without Sigma adapt; needs a Sigma period above 1
+ *   COVO_EPLOG_POST_AUX   float[COVO_POST_AUX_FLOATS]          covo_set_step_post_cov's side row
+ *   COVO_EPLOG_POST_COV   float[128][128]                      covo_set_step_post_cov's matrix
+ * Under iterations per step the rows are the last pass's (the iters row holds every pass).
+ * covo_set_episode_rows: log = DEVICE float[n_inst][stride][width]; step k of an episode driver's segment writes instance e's row to
+ *   log[e][log_index + k] (covo_run_episode: log_index = 0); NULL = off.  A row is copied with 16-byte accesses when its width is a
+ *   multiple of 4 floats and both addresses are 16-byte aligned, else float by float.
+ * Refused before any launch, with a message that names the condition: kind outside [0, COVO_EPLOG_KINDS); stride <= 0 with a log; a
+ * kind whose step attachment is off (the message names the covo_set_step_* call to make first); an episode segment that would leave
+ * the log; a sample-sharded step (partial_out != NULL).  Detaching a step attachment drops its log; so does covo_set_step_iters with
+ * another iters. */
+#define COVO_HAS_EPISODE_ROWS 1
+#define COVO_SIGMA_LOG_FLOATS 4
+#define COVO_EPLOG_LAM       0
+#define COVO_EPLOG_ELITE     1
+#define COVO_EPLOG_ITERS     2
+#define COVO_EPLOG_SIGMA     3
+#define COVO_EPLOG_POST_AUX  4
+#define COVO_EPLOG_POST_COV  5
+#define COVO_EPLOG_KINDS     6
+int covo_set_episode_rows(covo_handle_t h, int32_t kind, float *log, int32_t stride);
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,

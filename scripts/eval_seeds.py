@@ -7,21 +7,45 @@ name = sys.argv[1]
 # python scripts/eval_seeds.py covo-online --sigma-period 4 (or sigma_period=4): Sigma refreshed every 4th control step
 # python scripts/eval_seeds.py covo-online --sigma-period 4 --sigma-adapt 0.1 (or sigma_adapt=0.1): the reuse steps blend the posterior
 # covariance into the covariance they shift
+# python scripts/eval_seeds.py covo-online ess_min=64 / iters=2: the ESS floor / two passes per control step
+# Under ess_min, sigma_adapt and iters every seed's line also carries what the episode logs of the attachments' rows say (read_lam,
+# read_sigma, read_iters): the share of steps the floor raised the temperature in, the number of reuse steps that fell back to the plain
+# shift, the share of steps whose last pass found a cheaper sample than the first
 rest = sys.argv[2:]
 for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_adapt")):
     while flag in rest:
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
-opts = {k: (float(v) if k == "sigma_adapt" else int(v)) for k, v in (arg.split("=") for arg in rest)}
-assert set(opts) <= {"elite", "sigma_period", "sigma_adapt"}, opts
+opts = {k: (float(v) if k in ("sigma_adapt", "ess_min") else int(v)) for k, v in (arg.split("=") for arg in rest)}
+assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"}, opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
 ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **opts)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
+core = getattr(ctrl, "core", None)
+
+
+def rows_of(ep):
+    """what the episode's row logs say, summed into `rows` ({} for a controller without them)"""
+    if ep.lamlog is not None:
+        rows["floor"] = rows.get("floor", 0) + int((ep.read_lam()["lam_eff"] > np.float32(core.lam)).sum())
+    if ep.sigmalog is not None and core.sigma_adapt_gamma > 0.0:
+        rows["fallback"] = rows.get("fallback", 0) + int((ep.read_sigma()["fallback"] != 0.0).sum())
+    if ep.iterlog is not None:
+        it = ep.read_iters()
+        rows["improved"] = rows.get("improved", 0) + int((it[:, -1] < it[:, 0]).sum())
+    rows["steps"] = rows.get("steps", 0) + ep.n_steps
+
+
 for seed in range(1, 13):
-    errs = Q.eval_env_device(env, controller=ctrl, total_steps=300*4*10, seed=seed, verbose=False)
+    rows = {}
+    errs = Q.eval_env_device(env, controller=ctrl, total_steps=300*4*10, seed=seed, verbose=False, on_episode=rows_of if core else None)
     allerr.append(errs)
-    print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()), flush=True)
+    n = max(rows.get("steps", 0), 1)
+    extra = "".join(text % (rows[k] / d) for k, text, d in (("floor", "  lam_eff>lam: %.3f", n), ("fallback", "  adapt fallbacks: %d", 1),
+                                                           ("improved", "  last pass beat first: %.3f", n)) if k in rows)
+    print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()) + extra,
+          flush=True)
 allerr = np.concatenate(allerr)
 print(name, "TOTAL n", len(allerr), "crashes(>0.3)", (allerr > 0.3).sum(), "outliers(>0.06)", (allerr > 0.06).sum(), "median %.4f" % np.median(allerr), "mean-noncrash %.4f" % allerr[allerr<0.3].mean())
