@@ -47,6 +47,7 @@ COVO_POST_AUX_FLOATS = 132  # the posterior covariance's side row of one instanc
 COVO_HAS_SIGMA_ADAPT = 1
 COVO_SIGMA_ADAPT_FLOATS = 4  # Sigma adapt's row of one instance: {fallback, c, log det M, 0} (covo_set_step_sigma_adapt)
 COVO_HAS_EPISODE_ROWS = 1
+COVO_HAS_BATCHED_STAGED = 1  # staged= of the env-batched MPPI / covo-offline controllers (covo_set_step_batched_staged)
 # the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
 COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
 COVO_EPLOG_KINDS = 6
@@ -182,6 +183,7 @@ _SIGS = {
     "covo_debug_set_ns_merged": (C.c_int, [_P, C.c_int]),
     "covo_set_step_diag": (C.c_int, [_P, _P, C.c_int32]),             # per-step sampling diagnostics (covo_hip.h)
     "covo_set_episode_diag_log": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_set_step_batched_staged": (C.c_int, [_P, C.c_int32]),  # the staged batched step (covo_hip.h: COVO_HAS_BATCHED_STAGED)
     "covo_set_step_ess_floor": (C.c_int, [_P, C.c_float, _P, C.c_int32]),  # the ESS floor (covo_hip.h: COVO_HAS_ESS_FLOOR)
     "covo_ess_lambda": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "covo_set_step_elite": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # the elite-set update (covo_hip.h: COVO_HAS_ELITE_UPDATE)

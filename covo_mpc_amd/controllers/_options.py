@@ -3,7 +3,9 @@
 Every entry point -- SamplingCore, CoVOController, MPPIController, BatchedCoVOController, BatchedMPPIController, get_controller and (under
 three renames) eval_env_batched -- carries the keywords of STEP_OPTION_DEFAULTS in its signature, gathers them with take(locals()),
 has them checked by check_step_options() and forwards them as **opts.  What cannot be combined is listed here too: the refusals of the
-env-batched fused step, of sample-sharded ranks and of the kernel-by-kernel debug path.  A new option is a keyword in those
+env-batched fused step (lifted by staged=True of BatchedMPPIController / BatchedCoVOController(mode="offline"): their constructors then
+check with fused_batched=False; staged is a switch of those two controllers, not a step option), of sample-sharded ranks and of the
+kernel-by-kernel debug path.  A new option is a keyword in those
 signatures, an entry here, and its own attachment block in SamplingCore.__init__ (tests/test_options_abi.py holds the signatures to
 this table).  The C side's counterpart is check_step_attachments (csrc/capi.hip).
 
@@ -85,20 +87,21 @@ class StepOptions:
 
 
 _BATCHED_TAKES = "BatchedCoVOController(mode=\"online\") and the single controllers take "
+_OR_STAGED = ", or pass staged=True (the staged batched step takes it)"
 # the env-batched MPPI / covo-offline step: (is on, message); {o}: the keywords as given
 FUSED_BATCHED_REFUSALS = (
     (lambda s, o: s.elite_K,
      "elite={o[elite]}: the elite-set update is not available for the env-batched MPPI / covo-offline step "
-     "(one fused launch: it needs the weights before all costs exist); " + _BATCHED_TAKES + "it"),
+     "(one fused launch: it needs the weights before all costs exist); " + _BATCHED_TAKES + "it" + _OR_STAGED),
     (lambda s, o: s.post_cov,
      "compute_post_cov: the posterior covariance is not available for the env-batched MPPI / covo-offline "
-     "step (one fused launch: it keeps the samples in LDS and never stores them); " + _BATCHED_TAKES + "it"),
+     "step (one fused launch: it keeps the samples in LDS and never stores them); " + _BATCHED_TAKES + "it" + _OR_STAGED),
     (lambda s, o: s.iters > 1 and s.update != "softmax",
      "iters={o[iters]} with update={o[update]!r}: not available for the env-batched MPPI / covo-offline step "
-     "(its fused launch keeps each pass's starting mean in LDS only); " + _BATCHED_TAKES + "both"),
+     "(its fused launch keeps each pass's starting mean in LDS only); " + _BATCHED_TAKES + "both" + _OR_STAGED),
     (lambda s, o: s.ess_min != 0.0,
      "ess_min={o[ess_min]}: the ESS floor is not available for the env-batched MPPI / covo-offline step "
-     "(one fused launch: it needs the temperature before all costs exist); " + _BATCHED_TAKES + "it"),
+     "(one fused launch: it needs the temperature before all costs exist); " + _BATCHED_TAKES + "it" + _OR_STAGED),
 )
 
 # sample-sharded ranks: option -> (is on, the value the message shows as {v}, message); s: the normalised record, o: the keywords as given
@@ -172,8 +175,8 @@ def check_step_options(N, what, *, gamma_sigma=None, fused_batched=False, sharde
     1. each keyword's own range and mode check (_lib.check_*: ValueError).  `what` names the controller in the mode clauses: "online"
        for covo-online, the one mode that takes sigma_period / sigma_adapt.  N=None (not parsed yet) skips compute_fan and elite, the
        two that need it.  gamma_sigma (MPPI): see _lib.check_elite;
-    2. fused_batched -- the env-batched MPPI / covo-offline step, one fused launch: NotImplementedError for elite, compute_post_cov,
-       iters with an update other than "softmax", ess_min;
+    2. fused_batched -- the env-batched MPPI / covo-offline step, one fused launch (not under the controllers' staged=True):
+       NotImplementedError for elite, compute_post_cov, iters with an update other than "softmax", ess_min;
     3. sharded -- sample-sharded ranks: NotImplementedError for whatever of SHARDED_REFUSALS is on, in its order."""
     unknown = set(raw) - set(STEP_OPTION_DEFAULTS)
     if unknown:

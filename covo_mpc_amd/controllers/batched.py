@@ -4,7 +4,9 @@ The reference runs its `--mode render` / eval loop on one env instance and reach
 `jax.vmap` of the whole controller (quadjax/envs/quadrotor.py:497-538 is written per instance and vmap-clean).
 Here that is `covo_mpc_step_batched` / `covo_mpc_step_batched_mode` (include/covo_hip.h, csrc/step.hip):
   covo-online   one hipGraph holding ONE batched Hessian + Sigma launch set for all instances and the per-instance sampling path;
-  covo-offline, MPPI   the key upload plus ONE fused launch for all instances (csrc/step_small.hip, instance = grid dimension).
+  covo-offline, MPPI   the key upload plus ONE fused launch for all instances (csrc/step_small.hip, instance = grid dimension);
+                       with staged=True the launch sequence of a single staged step with the instance as a grid dimension
+                       (covo_set_step_batched_staged), which takes every step option and disturbance model the single controllers take.
 Every instance has its own state, reference trajectory, (domain-randomised) parameters, mean, key (and, per mode, Sigma table or
 block covariances); instance e's result is bit-identical to the single controller's `__call__` on that instance alone
 (tests/test_gpu_parity.py::test_batched_step_equals_replicas, tests/test_gpu_batched_modes.py).
@@ -36,10 +38,18 @@ class BatchedCoVOController:
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, discount: float = 1.0, gamma_mean: float = 1.0,
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
-                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0):
+                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, staged: bool = False):
         opts = take(locals())
-        fused = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step: one fused launch for all instances
-        what = ("online" if not fused else
+        moded = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step
+        if staged and not moded:
+            raise ValueError("staged=True with mode=\"online\": the env-batched covo-online step is a staged launch sequence already; "
+                             "staged= belongs to BatchedMPPIController and BatchedCoVOController(mode=\"offline\")")
+        # staged (not a step option: a switch of these two controllers, off by default): the step runs as the launch sequence of a
+        # single staged step with the instance as a grid dimension instead of the one fused launch -- also where the fused launch
+        # would do -- and takes what that launch refuses
+        self.staged = bool(staged)
+        fused = moded and not self.staged  # one fused launch for all instances
+        what = ("online" if not moded else
                 "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
         check_step_options(N, what, fused_batched=fused, **opts)
         if self.MODE is not None:
@@ -59,6 +69,8 @@ class BatchedCoVOController:
         # 150-270 us of host time per call)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  diag_rows=int(n_envs), **opts)
+        if moded:
+            check(self.core.lib.covo_set_step_batched_staged(self.core.h, int(self.staged)), "covo_set_step_batched_staged")
         # after a call, row e of each of the core's attachment buffers holds instance e's result of that step; None for what is off
         # (the options: _options.py; the rows: where SamplingCore allocates them; include/covo_hip.h).  sigma_period: the batch shares
         # one age -- self.sigma_age is the age the last call ran at (0 = refresh), reset() restarts the schedule
@@ -238,15 +250,23 @@ class BatchedMPPIController(BatchedCoVOController):
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0,
                  gamma_sigma: float = 0.0, a_mean_init=None, device=None, compute_diag: bool = False, compute_plan: bool = False,
                  ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
-                 compute_post_cov: bool = False, sigma_adapt: float = 0.0):
+                 compute_post_cov: bool = False, sigma_adapt: float = 0.0, staged: bool = False):
         opts = take(locals())
-        check_step_options(N, "the env-batched MPPI controller", fused_batched=True, **opts)  # (ahead of gamma_sigma's refusal)
-        if float(gamma_sigma) != 0.0:
+        # (ahead of gamma_sigma's refusal; under staged gamma_sigma is taken and has its say in the elite check, as for MPPIController)
+        s = check_step_options(N, "the env-batched MPPI controller", fused_batched=not staged,
+                               gamma_sigma=gamma_sigma if staged else None, **opts)
+        if float(gamma_sigma) != 0.0 and not staged:
             raise NotImplementedError(f"gamma_sigma={gamma_sigma}: MPPI's covariance adaptation (mppi.py:119-125) is not batched; "
-                                      "the batched fused launch needs gamma_sigma == 0 (the reference's default)")
+                                      "the batched fused launch needs gamma_sigma == 0 (the reference's default), or pass staged=True")
+        if float(gamma_sigma) != 0.0 and (s.elite_K or s.ess_min != 0.0):
+            with_what = f"elite={elite}" if s.elite_K else f"ess_min={ess_min}"
+            raise NotImplementedError(f"gamma_sigma={gamma_sigma} together with {with_what}: the staged env-batched MPPI step adapts "
+                                      "a_cov under the softmax weights at the configured lam only (that covariance update has no "
+                                      "instance dimension); MPPIController takes both")
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,)).copy()
         super().__init__(env, n_envs, N, H, lam, discount=discount, gamma_mean=gamma_mean, sample_sigma=float(sig[0]),
-                         a_mean_init=a_mean_init, device=device, **opts)
+                         a_mean_init=a_mean_init, device=device, staged=staged, **opts)
+        self.gamma_sigma = float(gamma_sigma)  # (non-zero under staged only: a_cov[e] is adapted in place, mppi.py:119-125)
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))

@@ -665,6 +665,17 @@ int covo_debug_set_ns_coherence(covo_handle_t h, int force_agent)
     return 0;
 }
 
+// ---- the staged env-batched MPPI / covo-offline step (step.hip: covo_step_batched_staged_impl).  A switch of the handle like the ones
+// above: the captured batched graphs hold the other launch set
+int covo_set_step_batched_staged(covo_handle_t h, int32_t on)
+{
+    REQUIRE(h, "covo_set_step_batched_staged: null handle");
+    const int v = on ? 1 : 0;
+    if (v != h->batched_staged) ++h->opt.epoch;
+    h->batched_staged = v;
+    return 0;
+}
+
 // ---- per-step sampling diagnostics.  The captured step graphs bake in where the steps write: a change of that target bumps the
 // epoch like a debug switch (attaching the episode log next to a step buffer changes no launch of a step: its rows are copied by
 // an eager launch of the episode drivers)
@@ -1350,19 +1361,22 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
             "%s: null buffer", what);
     int rc = check_batch_models(params, args->n_envs, episode, what);
     if (rc) return rc;
-    REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_lam_target(h) == nullptr,
+    // covo_set_step_batched_staged: the MPPI / covo-offline batch runs its staged launch sequence, which takes what the fused launch
+    // refuses below and has its own short list further down
+    const bool staged = mode != COVO_MODE_COVO_ONLINE && covo_batched_staged(h);
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || staged || covo_lam_target(h) == nullptr,
             "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for the env-batched MPPI / covo-offline step: its "
             "one fused launch needs the temperature before all costs exist, and there is no staged batched fallback; turn it off "
             "(ess_min = 0)", what, (double)h->ess_min);
-    REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_elite_target(h) == nullptr,
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || staged || covo_elite_target(h) == nullptr,
             "%s: the elite-set update (covo_set_step_elite, K=%d) is not available for the env-batched MPPI / covo-offline step: its "
             "one fused launch needs the weights before all costs exist, and there is no staged batched fallback; turn it off "
             "(K = 0)", what, h->elite_K);
-    REQUIRE(mode == COVO_MODE_COVO_ONLINE || covo_step_iters(h) == 1 || !covo_arb_on(h),
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || staged || covo_step_iters(h) == 1 || !covo_arb_on(h),
             "%s: iterations per step (covo_set_step_iters, iters=%d) together with the update arbiter (covo_set_step_arbiter) are not "
             "available for the env-batched MPPI / covo-offline step: its fused launch keeps each pass's starting mean in LDS only; "
             "detach one of them", what, covo_step_iters(h));
-    REQUIRE(mode == COVO_MODE_COVO_ONLINE || !covo_post_cov_on(h),
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || staged || !covo_post_cov_on(h),
             "%s: the posterior covariance (covo_set_step_post_cov) is not available for the env-batched MPPI / covo-offline step: its "
             "one fused launch keeps the samples in LDS and never stores them, and there is no staged batched fallback; detach the "
             "buffer", what);
@@ -1382,6 +1396,19 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
         norm->n_table = m->n_table;
         norm->L_table = m->L_table;
         norm->L_table_stride = m->L_table_stride;
+    }
+    if (staged) {
+        REQUIRE(args->groupmin != nullptr, "%s: the staged batched step (covo_set_step_batched_staged) needs base.groupmin "
+                "(float[n_envs][ceil(n_samples / 64)]): its update reads the per-wave cost minima the rollout leaves there", what);
+        REQUIRE(m->gamma_sigma == 0.0f || mode == COVO_MODE_MPPI, "%s: gamma_sigma != 0 is MPPI's covariance adaptation "
+                "(mppi.py:119-125); this step's mode is covo-offline", what);
+        REQUIRE(m->gamma_sigma == 0.0f || !covo_update_staged(h), "%s: gamma_sigma != 0 together with %s is not available for the "
+                "staged batched step (covo_set_step_batched_staged): that covariance update has no instance dimension; set "
+                "gamma_sigma = 0 or detach it", what,
+                covo_elite_target(h) ? "the elite-set update (covo_set_step_elite)" : "the ESS floor (covo_set_step_ess_floor)");
+        REQUIRE(!exchange_ready(h), "%s: the staged batched step (covo_set_step_batched_staged) is not available on a sample-sharded "
+                "handle (covo_exchange_connect): the instances of a batch are whole", what);
+        return 0;
     }
     int which = 0;
     const char *why = batch_small_refusal(h, norm, params, &which);
@@ -1419,7 +1446,9 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             host_philox_split(key, 2u, &step_keys[2 * e]);
             host_philox_split(nrng, 0u, &next[2 * e]);
         }
-        if ((rc = online ? covo_step_batched_impl(h, args, params, act_keys, s) : covo_step_batched_small_impl(h, &norm, params, act_keys, s)))
+        if ((rc = online                  ? covo_step_batched_impl(h, args, params, act_keys, s)
+                  : covo_batched_staged(h) ? covo_step_batched_staged_impl(h, &norm, params, act_keys, s)
+                                           : covo_step_batched_small_impl(h, &norm, params, act_keys, s)))
             return rc;
         if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, E, h->diag_log_stride, log_index + t, s)))
             return rc;
@@ -1482,6 +1511,7 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     int rc = check_batch_step(h, &args->base, args, params, false, "covo_mpc_step_batched_mode", &norm);
     if (rc) return rc;
     rc = args->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream)
+         : covo_batched_staged(h)            ? covo_step_batched_staged_impl(h, &norm, params, keys, (hipStream_t)stream)
                                              : covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
     if (rc) return rc;
     return covo_plan_after_batched(h, &args->base, args->mode, params, nullptr, -1, (hipStream_t)stream);

@@ -47,6 +47,7 @@ struct covo_ctx {
     int *status_dev;          // its device address
     void *exchange;           // Exchange (exchange.hip): peer-write exchange of the rank records, or null
     int dbg_epoch;            // opt.epoch when this handle's step graphs were captured (a debug setter since then: re-capture)
+    int batched_staged;       // covo_set_step_batched_staged: the env-batched MPPI / covo-offline step runs its staged launch sequence
     // per-step sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log); all null / 0: off
     float *diag_out;          // caller's [diag_n][COVO_DIAG_FLOATS]: instance e's row of every step
     int diag_n;
@@ -266,7 +267,7 @@ struct CovDeferred {
     float *out;                  // a_cov [128][128]; null: nothing deferred
 };
 // a = clip(mu + L eps): launch_noise_gemm (dense L [128][128]) and launch_noise_blockdiag (MPPI's Ls [H][4][4]; it has no
-// eps_tiled / state_for_time / batch / cov)
+// eps_tiled / state_for_time / cov; batch > 1 with the in-kernel draw and dyn only)
 struct NoiseDesc {
     const float *L = nullptr;
     const float *mu = nullptr;
@@ -280,6 +281,11 @@ struct NoiseDesc {
     const float *state_for_time = nullptr;  // non-null: L is a table [n_table][128][128], row state.time is used (covo-offline)
     int n_table = 0;
     int batch = 1;                     // batch > 1 (in-kernel Philox or tiled eps only): dense per-instance L, mu, dyn, a
+    // batch_table (launch_noise_gemm, in-kernel Philox; the staged env-batched covo-offline step): L is instance 0's table
+    // [n_table][128][128], instance y's lies table_stride floats on (0: one shared table) and its row is picked by the time of
+    // state_for_time + y * COVO_STATE_FLOATS -- instead of a dense per-instance L and one state
+    bool batch_table = false;
+    int64_t table_stride = 0;
     // cov != null (fused covo-online step): a_cov = cz sym(Z) is NOT written by the chain's finalize launch -- one workgroup that
     // everything after it waits for -- but by the first workgroups of the noise GEMM that follows (same expression, same bits);
     // launch_sigma_ns fills *cov with where Z, its transpose and the scalars live.
@@ -324,7 +330,7 @@ int launch_disturb_table(const covo_env_params &p, const float *state, int batch
 int launch_disturb_tables_step(const covo_env_params &p, const float *state, const uint32_t *dyn, int rollout_deterministic,
                                float *tab_rollout, float *tab_hess, hipStream_t s);
 // env-batched step: per-instance models (dm::Model[n], host-filled, copied to the device by the caller) and both tables of
-// every instance in one launch ([n][H][4] each; raw keys at dyn[12 e + 10..11])
+// every instance in one launch ([n][H][4] each; raw keys at dyn[12 e + 10..11]; tab_hess null: the rollouts' tables only)
 size_t disturb_models_bytes(int n);
 void disturb_fill_models(const covo_env_params *params, int n, void *out);
 int launch_disturb_tables_batched(const void *models_dev, const float *states, const uint32_t *dyn, int n_envs,
@@ -358,6 +364,12 @@ struct UpdateDesc {
     float gamma_sigma = 0.0f;
     float *a_cov_out = nullptr;
     int batch = 1;                    // batch > 1: dense per-instance slices, own partials_ws
+    // launch_softmax_update_cov with an instance dimension (the staged env-batched MPPI step): the records with second moments
+    // [batch][blocks][452] and where the diagnostics' merge leaves its merged records [batch][COVO_PARTIAL_FLOATS]; with them
+    // batch, diag_rec, a_mean_old / a_cov_old / a_cov_out [batch][...] and iter_stride are read.  null: one instance, the handle's
+    // own ws_partials_cov / ws_diag_rec / ws_partials
+    float *partials_cov_ws = nullptr;
+    float *diag_merge_ws = nullptr;
     // the sampling diagnostics, with a final update only
     float *diag_rec = nullptr;        // stage-1 diagnostic records [batch][blocks or G][4] (scratch of launch_softmax_reduce, input of launch_merge)
     float *diag_out = nullptr;        // [batch][COVO_DIAG_FLOATS]
@@ -396,6 +408,7 @@ int exchange_world(const covo_ctx *h);
 int exchange_records(covo_ctx *h, const float *record, float *gathered_dst, const float **gathered_out, hipStream_t s,
                      int nfloats = COVO_RANK_RECORD_FLOATS);
 size_t softmax_cov_workspace_floats(int max_blocks);
+int softmax_stage1_blocks(const covo_ctx *h, int N);  // workgroups (= records) of the stand-alone stage 1 over N samples
 // a_cov_out == null: this rank's record {m, s, v[128], pad[2], S2[320]} (unnormalised) goes to partial_out -- the first
 // COVO_PARTIAL_FLOATS + 320 floats of a COVO_RANK_RECORD_COV_FLOATS rank record
 int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
@@ -511,6 +524,11 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
                            hipStream_t s);
 int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
                                  hipStream_t s);
+// the same step as its staged launch sequence (covo_set_step_batched_staged): begin | tables | sampling | rollout | update per pass
+int covo_step_batched_staged_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
+                                  hipStream_t s);
+// which of the two the handle's MPPI / covo-offline batch runs
+static inline bool covo_batched_staged(const covo_ctx *h) { return h->batched_staged != 0; }
 // null: every instance of the batch can take the fused launch; else why not (instance index in *which)
 const char *batch_small_refusal(const covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, int *which);
 int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,

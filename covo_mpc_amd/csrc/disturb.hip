@@ -146,7 +146,8 @@ void disturb_fill_models(const covo_env_params *params, int n, void *out)
 int launch_disturb_tables_batched(const void *models_dev, const float *states, const uint32_t *dyn, int n_envs,
                                   int rollout_deterministic, float *tab_rollout, float *tab_hess, hipStream_t s)
 {
-    hipLaunchKernelGGL(disturb_tables_batched_kernel, dim3(n_envs, 2), dim3(64), 0, s, states, dyn,
+    // (tab_hess null -- the staged MPPI / covo-offline batch has no Hessian --: the rollouts' tables only)
+    hipLaunchKernelGGL(disturb_tables_batched_kernel, dim3(n_envs, tab_hess ? 2 : 1), dim3(64), 0, s, states, dyn,
                        reinterpret_cast<const dm::Model *>(models_dev), rollout_deterministic,
                        reinterpret_cast<float4 *>(tab_rollout), reinterpret_cast<float4 *>(tab_hess));
     COVO_CHECK_HIP(hipGetLastError());

@@ -51,13 +51,16 @@ __device__ unsigned long long *g_ng_probe;
 // SPLIT (launches of <= 512 tiles, i.e. N <= 16 384: fewer tiles than half the chip's SIMDs): a tile is shared by TWO waves -- row
 // tiles {0, 3} and {1, 2}, 80 of the 160 MFMAs each -- so that twice as many SIMDs work and a wave's serial MFMA time halves
 // (N = 8 192: 256 tiles on 1 024 SIMDs).  Same dot products, same order: bit-identical to the unsplit kernel.
-template <bool PHILOX, bool TILED = false, int NG_BLOCK = 256, bool SPLIT = false>
+// BTABLE (the staged env-batched covo-offline step, csrc/step.hip): instance y reads row clamp(time_y) of ITS table -- L + y * table_stride
+// floats (0: all instances share one table), time_y from state_for_time + y * COVO_STATE_FLOATS -- instead of a dense [batch][128][128]
+// factor and one state; everything behind the choice of L is the same code: the same dot products in the same order.
+template <bool PHILOX, bool TILED = false, int NG_BLOCK = 256, bool SPLIT = false, bool BTABLE = false>
 __global__ __launch_bounds__(NG_BLOCK, 512 / NG_BLOCK) void noise_gemm_kernel(const float *__restrict__ L, const float *__restrict__ mu,
                                                               const float *__restrict__ eps, uint32_t k0, uint32_t k1,
                                                               int64_t sample_offset, int N, int ntiles,
                                                               float4 *__restrict__ a_out, const uint32_t *__restrict__ dyn,
                                                               const float *__restrict__ state_for_time, int n_table,
-                                                              const CovDeferred cov, int nanp)
+                                                              const CovDeferred cov, int nanp, int64_t table_stride)
 {
     // dyn (nullable): {key0, key1} in device memory -- lets a captured graph see a fresh key every replay.
     // state_for_time (nullable): L is a table [n_table][128][128]; use row state.time (covo.py:107-108, clamped
@@ -65,7 +68,12 @@ __global__ __launch_bounds__(NG_BLOCK, 512 / NG_BLOCK) void noise_gemm_kernel(co
     // blockIdx.y (env-batched step): instance y has its own factor, mean, key block and action stripes, all dense
     {
         const size_t y = blockIdx.y;
-        L += y * (COVO_NA * COVO_NA);
+        if (BTABLE) {
+            L += y * (size_t)table_stride;
+            state_for_time += y * COVO_STATE_FLOATS;
+        } else {
+            L += y * (COVO_NA * COVO_NA);
+        }
         mu += y * COVO_NA;
         a_out += y * ((size_t)COVO_H * N);
         if (dyn != nullptr) dyn += y * 12;
@@ -273,12 +281,21 @@ __global__ __launch_bounds__(NG_BLOCK, 512 / NG_BLOCK) void noise_gemm_kernel(co
 // PHILOX (the product path: nothing is read): workgroup row y = step t, consecutive lanes = consecutive samples -- a wave stores
 // 1 KiB contiguous runs of stripe t.  (Round 3; the first mapping, consecutive lanes = consecutive t of one sample, suits the eps
 // READ of the other variant but scattered the stores as 64 partial lines per wave: 19.2 us at N = 65 536.)
-template <bool PHILOX>
+// BATCHED (PHILOX only; the staged env-batched MPPI step, csrc/step.hip): blockIdx.z = instance z with its own factors, shifted mean, key
+// block (dyn + 12 z) and action stripes, all dense
+template <bool PHILOX, bool BATCHED = false>
 __global__ __launch_bounds__(256) void noise_blockdiag_kernel(const float *__restrict__ Ls, const float *__restrict__ mu,
                                                               const float4 *__restrict__ eps, uint32_t k0, uint32_t k1,
                                                               int64_t sample_offset, int N, float4 *__restrict__ a_out,
                                                               const uint32_t *__restrict__ dyn, int nanp)
 {
+    if (BATCHED) {
+        const size_t z = blockIdx.z;
+        Ls += z * (COVO_H * 16);
+        mu += z * COVO_NA;
+        a_out += z * ((size_t)COVO_H * N);
+        dyn += z * 12;
+    }
     if (dyn != nullptr) { k0 = dyn[0]; k1 = dyn[1]; }
     int t;
     size_t n;
@@ -350,25 +367,31 @@ int launch_noise_gemm(const NoiseDesc &d, hipStream_t s)
         NG_ATTR(false, false, 256); NG_ATTR(true, false, 256); NG_ATTR(false, true, 256);
         NG_ATTR(false, false, 512); NG_ATTR(true, false, 512); NG_ATTR(false, true, 512);
         NG_ATTR(false, false, 256, true); NG_ATTR(true, false, 256, true); NG_ATTR(false, true, 256, true);
+        NG_ATTR(true, false, 256, false, true); NG_ATTR(true, false, 512, false, true); NG_ATTR(true, false, 256, true, true);
 #undef NG_ATTR
     }
-#define NG_GO(...)                                                                                                             \
+    const int64_t no_stride = 0;
+#define NG_GO(BLK, SPL)                                                                                                            \
     do {                                                                                                                         \
         if (eps != nullptr && d.eps_tiled)                                                                                         \
-            hipLaunchKernelGGL((noise_gemm_kernel<false, true, __VA_ARGS__>), dim3(grid, batch), dim3(block), lds, s, L, mu, eps, 0u, 0u, (int64_t)0, \
-                               N, ntiles, reinterpret_cast<float4 *>(d.a), (const uint32_t *)nullptr, state_for_time, n_table, cv, nanp); \
+            hipLaunchKernelGGL((noise_gemm_kernel<false, true, BLK, SPL>), dim3(grid, batch), dim3(block), lds, s, L, mu, eps, 0u, 0u, (int64_t)0, \
+                               N, ntiles, reinterpret_cast<float4 *>(d.a), (const uint32_t *)nullptr, state_for_time, n_table, cv, nanp, no_stride); \
         else if (eps != nullptr)                                                                                                 \
-            hipLaunchKernelGGL((noise_gemm_kernel<false, false, __VA_ARGS__>), dim3(grid), dim3(block), lds, s, L, mu, eps, 0u, 0u,          \
+            hipLaunchKernelGGL((noise_gemm_kernel<false, false, BLK, SPL>), dim3(grid), dim3(block), lds, s, L, mu, eps, 0u, 0u,          \
                                (int64_t)0, N, ntiles, reinterpret_cast<float4 *>(d.a), (const uint32_t *)nullptr, state_for_time, \
-                               n_table, cv, nanp);                                                                               \
-        else                                                                                                                     \
-            hipLaunchKernelGGL((noise_gemm_kernel<true, false, __VA_ARGS__>), dim3(grid, batch), dim3(block), lds, s, L, mu,                 \
+                               n_table, cv, nanp, no_stride);                                                                    \
+        else if (d.batch_table)                                                                                                  \
+            hipLaunchKernelGGL((noise_gemm_kernel<true, false, BLK, SPL, true>), dim3(grid, batch), dim3(block), lds, s, L, mu,         \
                                (const float *)nullptr, d.key[0], d.key[1], d.sample_offset, N, ntiles,                        \
-                               reinterpret_cast<float4 *>(d.a), d.dyn, state_for_time, n_table, cv, nanp);                       \
+                               reinterpret_cast<float4 *>(d.a), d.dyn, state_for_time, n_table, cv, nanp, d.table_stride);      \
+        else                                                                                                                     \
+            hipLaunchKernelGGL((noise_gemm_kernel<true, false, BLK, SPL>), dim3(grid, batch), dim3(block), lds, s, L, mu,                 \
+                               (const float *)nullptr, d.key[0], d.key[1], d.sample_offset, N, ntiles,                        \
+                               reinterpret_cast<float4 *>(d.a), d.dyn, state_for_time, n_table, cv, nanp, no_stride);           \
     } while (0)
-    if (block == 512) NG_GO(512);
+    if (block == 512) NG_GO(512, false);
     else if (split) NG_GO(256, true);
-    else NG_GO(256);
+    else NG_GO(256, false);
 #undef NG_GO
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
@@ -380,10 +403,17 @@ int launch_noise_blockdiag(const NoiseDesc &d, hipStream_t s)
     const int nanp = d.propagate_nan ? 1 : 0;
     const size_t total = (size_t)N * COVO_H;
     const int grid = (int)((total + 255) / 256);
+    if (d.batch > 1 && (d.eps != nullptr || d.dyn == nullptr)) {  // (the instance form reads instance z's key at dyn + 12 z)
+        covo_set_error("noise_blockdiag: batch=%d needs the in-kernel draw with the keys in device memory (eps == NULL, dyn != NULL)", d.batch);
+        return COVO_E_BADARG;
+    }
     if (d.eps != nullptr)
         hipLaunchKernelGGL(noise_blockdiag_kernel<false>, dim3(grid), dim3(256), 0, s, d.L, d.mu,
                            reinterpret_cast<const float4 *>(d.eps), 0u, 0u, (int64_t)0, N, reinterpret_cast<float4 *>(d.a),
                            (const uint32_t *)nullptr, nanp);
+    else if (d.batch > 1)
+        hipLaunchKernelGGL((noise_blockdiag_kernel<true, true>), dim3((N + 255) / 256, COVO_H, d.batch), dim3(256), 0, s, d.L, d.mu,
+                           (const float4 *)nullptr, 0u, 0u, d.sample_offset, N, reinterpret_cast<float4 *>(d.a), d.dyn, nanp);
     else
         hipLaunchKernelGGL(noise_blockdiag_kernel<true>, dim3((N + 255) / 256, COVO_H), dim3(256), 0, s, d.L, d.mu,
                            (const float4 *)nullptr, d.key[0], d.key[1], d.sample_offset, N, reinterpret_cast<float4 *>(d.a), d.dyn,

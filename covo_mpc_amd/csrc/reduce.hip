@@ -52,13 +52,24 @@ __global__ __launch_bounds__(RD_BLOCK) void softmax_partial_diag_kernel(const fl
 }
 
 
-template <bool FINAL>
+template <bool FINAL, bool INST = false>
 __global__ __launch_bounds__(MG_THREADS) void merge_cov_kernel(const float *__restrict__ partials, int G, float inv_lam,
                                                                const float *__restrict__ a_mean_old, float gamma_mean,
                                                                const float *__restrict__ a_cov_old, float gamma_sigma,
                                                                float *__restrict__ a_mean_out, float *__restrict__ a_cov_out,
-                                                               int stride, float *__restrict__ iter_out)
+                                                               int stride, float *__restrict__ iter_out, int iter_stride)
 {
+    // INST (FINAL; the staged env-batched MPPI step): workgroup x = instance x merges its own G records into its own mean and adapts
+    // its own covariance blocks in place; its cost minimum to iter_out[x * iter_stride]
+    if (INST) {
+        const size_t x = blockIdx.x;
+        partials += x * G * stride;
+        a_mean_old += x * COVO_NA;
+        a_cov_old += x * (COVO_H * 16);
+        a_mean_out += x * COVO_NA;
+        a_cov_out += x * (COVO_H * 16);
+        if (iter_out != nullptr) iter_out += x * (size_t)iter_stride;
+    }
     merge_cov_body<FINAL>(partials, G, inv_lam, a_mean_old, gamma_mean, a_cov_old, gamma_sigma, a_mean_out, a_cov_out, stride, iter_out);
 }
 
@@ -153,9 +164,12 @@ int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
     return 0;
 }
 
-// MPPI's update with covariance adaptation (mppi.py:109-125): stage 1 with second moments, then merge_cov_kernel; single shard
-// (one instance, the handle's own ws_partials_cov / ws_diag_rec: d.batch, d.partials_ws and d.diag_rec are not read)
+// MPPI's update with covariance adaptation (mppi.py:109-125): stage 1 with second moments, then merge_cov_kernel.  Single shard: one
+// instance on the handle's own ws_partials_cov / ws_diag_rec (d.batch, d.partials_ws and d.diag_rec are not read); with
+// d.partials_cov_ws (the staged env-batched MPPI step, final updates only): d.batch instances, instance y's records [grid][452] behind
+// those of instance y - 1, every instance's sums in the single launch's order
 size_t softmax_cov_workspace_floats(int max_blocks) { return (size_t)max_blocks * RD_COV_RECORD_FLOATS; }
+int softmax_stage1_blocks(const covo_ctx *h, int N) { return stage1_grid(h, N); }
 int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
 {
     if (d.lam_rows != nullptr) return launch_softmax_update_cov_lam(h, d, s);  // (reduce_lam.hip)
@@ -164,19 +178,30 @@ int launch_softmax_update_cov(covo_ctx *h, const UpdateDesc &d, hipStream_t s)
     const Minima mn = stage1_minima(h, d, s);
     const int grid = stage1_grid(h, d.N);
     const float4 *a4 = reinterpret_cast<const float4 *>(d.a), *mean4 = reinterpret_cast<const float4 *>(d.a_mean_old);
+    const bool inst = d.partials_cov_ws != nullptr;
+    const int batch = inst ? d.batch : 1;
+    float *recs = inst ? d.partials_cov_ws : h->ws_partials_cov, *drec = inst ? d.diag_rec : h->ws_diag_rec;
     if (diag)
-        hipLaunchKernelGGL(softmax_partial_diag_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
-                           mn.n_blockmin, inv_lam, h->ws_partials_cov, mean4, h->ws_diag_rec);
+        hipLaunchKernelGGL(softmax_partial_diag_kernel<true>, dim3(grid, batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
+                           mn.n_blockmin, inv_lam, recs, mean4, drec);
     else
-        hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(grid, 1), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
-                           mn.n_blockmin, inv_lam, h->ws_partials_cov, mean4);
-    if (diag) launch_merge_cov_diag(h, grid, inv_lam, d.diag_out, d.N, s);
-    if (d.a_cov_out != nullptr)
-        hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam, d.a_mean_old,
-                           d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS, d.iter_out);
+        hipLaunchKernelGGL(softmax_partial_kernel<true>, dim3(grid, batch), dim3(RD_BLOCK), 0, s, d.cost, a4, d.N, mn.blockmin,
+                           mn.n_blockmin, inv_lam, recs, mean4);
+    if (diag && inst)  // launch_merge_cov_diag's launch with an instance per workgroup
+        hipLaunchKernelGGL(merge_diag_kernel<false>, dim3(batch), dim3(MG_THREADS), 0, s, recs, grid, inv_lam, (const float *)nullptr, 1.0f,
+                           d.diag_merge_ws, RD_COV_RECORD_FLOATS, (const float *)drec, d.diag_out, (float)d.N, (float *)nullptr, 0);
+    else if (diag)
+        launch_merge_cov_diag(h, grid, inv_lam, d.diag_out, d.N, s);
+    if (d.a_cov_out != nullptr && inst)
+        hipLaunchKernelGGL((merge_cov_kernel<true, true>), dim3(batch), dim3(MG_THREADS), 0, s, recs, grid, inv_lam, d.a_mean_old,
+                           d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS, d.iter_out,
+                           d.iter_stride);
+    else if (d.a_cov_out != nullptr)
+        hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, recs, grid, inv_lam, d.a_mean_old,
+                           d.gamma_mean, d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, RD_COV_RECORD_FLOATS, d.iter_out, 0);
     else  // a sample-sharded rank: its record {m, s, v, pad, S2}, unnormalised and unblended
         hipLaunchKernelGGL(merge_cov_kernel<false>, dim3(1), dim3(MG_THREADS), 0, s, h->ws_partials_cov, grid, inv_lam, d.a_mean_old,
-                           1.0f, (const float *)nullptr, 0.0f, d.partial_out, (float *)nullptr, RD_COV_RECORD_FLOATS, (float *)nullptr);
+                           1.0f, (const float *)nullptr, 0.0f, d.partial_out, (float *)nullptr, RD_COV_RECORD_FLOATS, (float *)nullptr, 0);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }
@@ -195,7 +220,7 @@ int launch_merge_cov(const UpdateDesc &d, float lam, hipStream_t s)
 {
     if (d.G > MG_MAXG) { covo_set_error("covo_merge_ranks_cov: G=%d > %d", d.G, MG_MAXG); return COVO_E_BADARG; }
     hipLaunchKernelGGL(merge_cov_kernel<true>, dim3(1), dim3(MG_THREADS), 0, s, d.partials, d.G, 1.0f / lam, d.a_mean_old, d.gamma_mean,
-                       d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, d.stride, d.iter_out);
+                       d.a_cov_old, d.gamma_sigma, d.a_mean_out, d.a_cov_out, d.stride, d.iter_out, 0);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

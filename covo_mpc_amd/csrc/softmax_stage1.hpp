@@ -65,6 +65,7 @@ __device__ __forceinline__ void softmax_partial_body(const float *__restrict__ c
         a += y * ((size_t)COVO_H * N);
         partials += y * gridDim.x * REC;
         if (DIAG) dpart += y * gridDim.x * MG_DIAG_REC;
+        if (COV) mu += y * (COVO_NA / 4);  // (the mean instance y's second moments are centred on)
     }
     float m;
     if constexpr (Weights::RED_FLOATS > 0) {

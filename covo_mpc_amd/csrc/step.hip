@@ -649,6 +649,40 @@ __global__ void batch_begin_kernel(const float *__restrict__ a_mean, float *__re
     }
 }
 
+// the begin launch of the STAGED env-batched MPPI / covo-offline step (covo_set_step_batched_staged): per instance what
+// step_begin_kernel does for one -- shift the mean (pass 0), the step's scalars through step_begin_derive / _next from the instance's
+// raw key (dyn[12 e + 0..1] as uploaded; pass >= 1: the previous pass's at [10..11]) with the instance's own shared_noise_scale, so that
+// MPPI's shared gaussian vector lands in dyn[12 e + 2..4] and the raw key at [10..11]; MPPI: the covariance shift (pass 0) + block
+// factors of a_cov[e] into Ls[e]
+struct BatchScales {
+    float v[COVO_MAX_ENVS];  // instance e's covo_shared_noise_scale
+};
+__global__ void batch_mode_begin_kernel(const float *__restrict__ a_mean, float *__restrict__ a_mean_shift, uint32_t *__restrict__ dyn,
+                                        const BatchScales scales, float *__restrict__ mppi_cov, float *__restrict__ mppi_Ls, const int pass)
+{
+    const int e = blockIdx.x, i = threadIdx.x;  // 128 + 64 threads
+    uint32_t *d = dyn + 12 * e;
+    if (mppi_cov != nullptr) mppi_prep(mppi_cov + (size_t)e * COVO_H * 16, mppi_Ls + (size_t)e * COVO_H * 16, pass == 0);
+    const uint32_t p0 = d[pass ? 10 : 0], p1 = d[pass ? 11 : 1];  // every deriving thread holds the key before any of them stores
+    __syncthreads();
+    if (i < COVO_NA) {
+        a_mean_shift[e * COVO_NA + i] = (pass == 0 && i < COVO_NA - COVO_DU) ? a_mean[e * COVO_NA + i + COVO_DU] : a_mean[e * COVO_NA + i];
+    } else if (i < COVO_NA + 4) {
+        const int q = i - COVO_NA;
+        if (pass) {
+            uint32_t raw[2];
+            step_begin_derive_next(q, p0, p1, scales.v[e], d, raw);
+        } else {
+            DynBlock blk;
+#pragma unroll
+            for (int w = 0; w < 12; ++w) blk.w[w] = 0u;
+            blk.w[0] = p0;
+            blk.w[1] = p1;
+            step_begin_derive(q, blk, 1, scales.v[e], d);
+        }
+    }
+}
+
 // the env-batched MPPI / covo-offline step (covo_mpc_step_batched_mode): ONE fused launch for all instances (step_small.hip,
 // grid = groups x instances) behind the key upload; scratch and graph cache of its own, next to the covo-online batch's
 struct BatchSmall {
@@ -672,8 +706,45 @@ static void batch_small_free(BatchSmall *m)
     m->n_envs = m->groups = 0;
 }
 
+// the STAGED form of the same step (covo_set_step_batched_staged): begin | tables | sampling | rollout | update for all instances per
+// pass, one linear stream of launches; scratch and graph caches of its own, like BatchSmall
+struct BatchStaged {
+    int n_envs = 0;
+    uint32_t *dyn = nullptr;        // [E][12] as the covo-online batch's
+    float *a_mean_shift = nullptr;  // [E][128]
+    float *Ls = nullptr;            // [E][H][4][4] MPPI's block factors
+    void *ro_args = nullptr;        // RolloutArgs[E]
+    float *partials = nullptr;      // [E][max_red_blocks][COVO_PARTIAL_FLOATS]
+    float *diag_rec = nullptr;      // [E][max_red_blocks][4]
+    float *diag_merge = nullptr;    // [E][COVO_PARTIAL_FLOATS]: the merged records the covariance update's diagnostics merge leaves
+    float *partials_cov = nullptr;  // [E][stage-1 grid][452]: MPPI's covariance adaptation; grown on demand
+    size_t partials_cov_cap = 0;
+    void *models = nullptr;         // dm::Model[E]
+    float *tab_rollout = nullptr;   // [E][H][4]
+    bool tables = false;
+    BatchScales scales;
+    std::vector<char> ro_args_host;
+    std::vector<covo_env_params> params;
+    covo_batch_mode_args key;  // with `stream` and `params`: what the scratch, the argument blocks and the graph were built for
+    hipStream_t stream = nullptr;
+    bool have_key = false;
+    GraphCache cache[2] = {};  // ([1] is never used: step_run_passes takes the pair)
+    void forget_graphs() { cache[0].forget(), cache[1].forget(); }
+};
+
+static void batch_staged_free(BatchStaged *q)
+{
+    q->forget_graphs();
+    q->have_key = false;
+    free_and_null(q->dyn, q->a_mean_shift, q->Ls, q->ro_args, q->partials, q->diag_rec, q->diag_merge, q->partials_cov, q->models,
+                  q->tab_rollout);
+    q->partials_cov_cap = 0;
+    q->n_envs = 0;
+}
+
 struct BatchState {
     BatchSmall small;
+    BatchStaged staged;
     int n_envs = 0;
     uint32_t *dyn = nullptr;        // [E][12]
     float *a_mean_shift = nullptr;  // [E][128]
@@ -721,6 +792,8 @@ void step_graphs_drop(covo_ctx *h)
     b->forget_graphs();
     b->have_key = false;  // (the cold block of covo_step_batched_impl rebuilds the rollout's argument blocks: they bake the launch set in too)
     b->small.cache.forget();
+    b->staged.forget_graphs();
+    b->staged.have_key = false;  // (its rollout argument blocks bake the launch set in, like the covo-online batch's)
 }
 
 int covo_grow_workspace(covo_ctx *h, void **ws, size_t *bytes, size_t need, hipStream_t s)
@@ -789,6 +862,7 @@ void batch_state_destroy(covo_ctx *h)
     if (!b) return;
     batch_state_free(b);
     batch_small_free(&b->small);
+    batch_staged_free(&b->staged);
     free_and_null(b->eps_tiled, b->env_inst);
     delete b;
     h->batch = nullptr;
@@ -1070,6 +1144,150 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
     });
 }
 
+// ---- the STAGED env-batched MPPI / covo-offline step (covo_set_step_batched_staged): what the fused launch refuses -- per-step
+// disturbance tables, the realworld reward, MPPI's covariance adaptation, more than 16 384 samples, the staged updates (ESS floor, elite
+// set), the posterior covariance, arbitrated passes -- runs as the launch sequence of a single staged step with the instance as a grid
+// dimension.  Instance e computes what enqueue_step computes for it alone: the same device functions on the same data in the same
+// order.  One pass:
+static int batch_staged_enqueue(covo_ctx *h, BatchStaged *q, const covo_batch_mode_args &m, hipStream_t s, const int pass)
+{
+    const covo_batch_args &a = m.base;
+    const int E = a.n_envs, N = a.n_samples;
+    const bool mppi = m.mode == COVO_MODE_MPPI;
+    int rc;
+    hipLaunchKernelGGL(batch_mode_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, q->a_mean_shift, q->dyn, q->scales,
+                       mppi ? a.a_cov : (float *)nullptr, q->Ls, pass);
+    // mppi.py:74: MPPI's sampling rollouts are non-deterministic, CoVO's deterministic (covo.py:231); no Hessian, no Hessian table
+    if (q->tables && (rc = launch_disturb_tables_batched(q->models, a.states, q->dyn, E, mppi ? 0 : 1, q->tab_rollout, nullptr, s))) return rc;
+    NoiseDesc nd;
+    nd.mu = q->a_mean_shift;
+    nd.dyn = q->dyn;
+    nd.N = N;
+    nd.a = a.a;
+    nd.batch = E;
+    nd.propagate_nan = covo_propagate_nan(h);
+    if (mppi) {
+        nd.L = q->Ls;
+        if ((rc = launch_noise_blockdiag(nd, s))) return rc;
+    } else {
+        nd.L = m.L_table;
+        nd.state_for_time = a.states;
+        nd.n_table = m.n_table;
+        nd.batch_table = true;
+        nd.table_stride = m.L_table_stride;
+        if ((rc = launch_noise_gemm(nd, s))) return rc;
+    }
+    if ((rc = launch_rollout_batched(q->ro_args_host.data(), q->ro_args, E, s))) return rc;
+    const int G = rollout_workgroups(N, false, E);
+    const bool cov_adapt = mppi && m.gamma_sigma != 0.0f;
+    UpdateDesc up;
+    up.cost = a.cost;
+    up.a = a.a;
+    up.N = N;
+    up.blockmin = a.groupmin;
+    up.partials_ws = q->partials;
+    up.partials = q->partials;
+    up.G = G;
+    up.a_mean_old = q->a_mean_shift;
+    up.gamma_mean = a.gamma_mean;
+    up.a_mean_out = a.a_mean;
+    up.batch = E;
+    up.diag_rec = q->diag_rec;
+    up.diag_out = covo_diag_target(h);
+    up.iter_out = covo_iter_slot(h, pass);
+    up.iter_stride = covo_step_iters(h);
+    if (cov_adapt) {  // mppi.py:109-125 per instance: a_cov[e] (shifted by the begin launch) adapted in place
+        up.a_cov_old = a.a_cov;
+        up.gamma_sigma = m.gamma_sigma;
+        up.a_cov_out = a.a_cov;
+        up.partials_cov_ws = q->partials_cov;
+        up.diag_merge_ws = q->diag_merge;
+    }
+    return enqueue_update(h, up, G <= h->max_red_blocks && !cov_adapt && !covo_update_staged(h), s);  // (as the cold block told the rollout)
+}
+
+int covo_step_batched_staged_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
+                                  hipStream_t s)
+{
+    const covo_batch_args *args = &m->base;
+    const int E = args->n_envs, N = args->n_samples;
+    const bool mppi = m->mode == COVO_MODE_MPPI, cov_adapt = mppi && m->gamma_sigma != 0.0f;
+    step_sync_epoch(h);
+    BatchStaged *q = &batch_state(h)->staged;
+    const bool same = q->have_key && q->n_envs == E && std::memcmp(&q->key, m, sizeof(*m)) == 0 && q->stream == s &&
+                      std::memcmp(q->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
+    if (!same) {
+        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old argument blocks are done
+        q->forget_graphs();
+        q->have_key = false;
+        if (q->n_envs != E) {
+            batch_staged_free(q);
+            COVO_CHECK_HIP(hipMalloc(&q->dyn, (size_t)E * 12 * sizeof(uint32_t)));
+            COVO_CHECK_HIP(hipMalloc(&q->a_mean_shift, (size_t)E * COVO_NA * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&q->Ls, (size_t)E * COVO_H * 16 * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&q->ro_args, rollout_args_bytes(E)));
+            COVO_CHECK_HIP(hipMalloc(&q->partials, (size_t)E * h->max_red_blocks * COVO_PARTIAL_FLOATS * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&q->diag_rec, (size_t)E * h->max_red_blocks * 4 * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&q->diag_merge, (size_t)E * COVO_PARTIAL_FLOATS * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&q->models, disturb_models_bytes(E)));
+            COVO_CHECK_HIP(hipMalloc(&q->tab_rollout, (size_t)E * COVO_H * 4 * sizeof(float)));
+            q->n_envs = E;
+        }
+        if (cov_adapt) {  // the records with second moments: grown like the covo-online batch's epsilon image
+            const size_t need = (size_t)E * softmax_cov_workspace_floats(softmax_stage1_blocks(h, N));
+            if (need > q->partials_cov_cap) {
+                free_and_null(q->partials_cov);
+                q->partials_cov_cap = 0;
+                COVO_CHECK_HIP(hipMalloc(&q->partials_cov, need * sizeof(float)));
+                q->partials_cov_cap = need;
+            }
+        }
+        q->params.assign(params, params + E);
+        std::vector<char> tmp(disturb_models_bytes(E), 0);
+        disturb_fill_models(params, E, tmp.data());
+        COVO_CHECK_HIP(hipMemcpy(q->models, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
+        q->tables = covo_needs_tables(params[0]);
+        q->ro_args_host.assign(rollout_args_bytes(E), 0);
+        const int bG = rollout_workgroups(N, false, E);
+        const bool brec = bG <= h->max_red_blocks && !cov_adapt && !covo_update_staged(h);
+        std::memset(&q->scales, 0, sizeof(q->scales));
+        for (int e = 0; e < E; ++e) {
+            const BatchInst i = batch_inst(*args, e);
+            q->scales.v[e] = covo_shared_noise_scale(params[e], !mppi);
+            RolloutDesc ro;
+            ro.state = i.state;
+            ro.pos_traj = i.pos_traj;
+            ro.vel_traj = i.vel_traj;
+            ro.T = args->T;
+            ro.params = &params[e];
+            ro.f_shared_dev = reinterpret_cast<const float *>(q->dyn + 12 * e + 2);  // (MPPI: the instance's own shared vector)
+            ro.f_tab = q->tables ? q->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
+            ro.a = i.a;
+            ro.N = N;
+            ro.discount = h->cfg.discount;
+            ro.cost = i.cost;
+            ro.groupmin = brec ? nullptr : i.groupmin;
+            ro.records = brec ? q->partials + (size_t)e * bG * COVO_PARTIAL_FLOATS : nullptr;
+            ro.lam = h->cfg.lam;
+            ro.diag_rec = (brec && covo_diag_target(h)) ? q->diag_rec + (size_t)e * bG * 4 : nullptr;
+            ro.xcd_groups = mppi ? 4 : 0;  // (as the single step tells its rollout)
+            ro.clip = ROLLOUT_CLIP_TRUSTED;
+            rollout_fill_args(q->ro_args_host.data(), e, ro);
+        }
+        COVO_CHECK_HIP(hipMemcpy(q->ro_args, q->ro_args_host.data(), q->ro_args_host.size(), hipMemcpyHostToDevice));
+        std::memset(&q->key, 0, sizeof(q->key));
+        q->key = *m;
+        q->stream = s;
+        q->have_key = true;
+    }
+    batch_upload_keys(q->dyn, keys, E, s);
+    // covo_set_step_iters: the K passes in the one graph, the arbiter's launch between two of them eager (step_run_passes)
+    return step_run_passes(
+        h, q->cache, false, graph_cache_seen(q->cache[0], same), s, "covo_mpc_step_batched_mode",
+        [&](hipStream_t on, int j) { return batch_staged_enqueue(h, q, *m, on, j); },
+        [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, m->mode, params, nullptr, -1, on, true); });
+}
+
 // ---- the launches behind a step (after_step.hpp: the update arbiter, the flight recorder's plan and trace, the sample fan), eager.
 // What they need to know about ONE instance of the step that has just been enqueued: the inputs its sample rollouts had.  The shared
 // vector is re-derived from the raw key by the launches themselves (every step path forms it from the same device function); the
@@ -1136,22 +1354,28 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
+    // the staged MPPI / covo-offline step (covo_set_step_batched_staged) leaves what covo-online's leaves, in its own scratch
+    const BatchStaged *q = (!online && covo_batched_staged(h)) ? &b->staged : nullptr;
+    const bool begun = online || q != nullptr;  // a begin launch has left the shifted means and parked the raw keys
+    const float *shifted = online ? b->a_mean_shift : (q ? q->a_mean_shift : nullptr);
+    const float *tabs = online ? (b->tables ? b->tab_rollout : nullptr) : ((q && q->tables) ? q->tab_rollout : nullptr);
+    const uint32_t *dyn = online ? b->dyn : (q ? q->dyn : b->small.dyn);
     PlanInstDesc d[COVO_MAX_ENVS];
-    const float *nominal = nullptr;  // the update arbiter's: covo-online's begin launch leaves it, the fused launch's was formed ahead of it
+    const float *nominal = nullptr;  // the update arbiter's: a begin launch leaves it, the fused launch's was formed ahead of it
     if (covo_arb_on(h)) {
-        if (online) nominal = b->a_mean_shift;
+        if (begun) nominal = shifted;
         else if (int rc = launch_arbiter_nominal(h, nullptr, E, s, &nominal)) return rc;
     }
-    // the instance's raw rng_act: covo-online's begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone;
+    // the instance's raw rng_act: a begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone;
     // CoVO's rollouts are deterministic
     for (int e = 0; e < E; ++e)
         d[e] = plan_inst(batch_inst(*args, e), args->T, args->n_samples, &params[e], 1, mode != COVO_MODE_MPPI,
-                         nominal ? nominal + (size_t)e * COVO_NA : nullptr,
-                         (online && b->tables) ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr,
-                         online ? b->dyn + 12 * e + 10 : b->small.dyn + 12 * e);
+                         nominal ? nominal + (size_t)e * COVO_NA : nullptr, tabs ? tabs + (size_t)e * COVO_H * 4 : nullptr,
+                         begun ? dyn + 12 * e + 10 : dyn + 12 * e);
     if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only)) return rc;
-    // the posterior covariance of every instance (covo-online only: check_batch_step): dense slices, the begin launch's shifted means
-    return arbiter_only ? 0 : launch_post_cov_after(h, args->a, args->cost, online ? b->a_mean_shift : nullptr, args->n_samples, E, s);
+    // the posterior covariance of every instance (never behind the fused launch: check_batch_step): dense slices, the begin launch's
+    // shifted means
+    return arbiter_only ? 0 : launch_post_cov_after(h, args->a, args->cost, shifted, args->n_samples, E, s);
 }
 
 // test hook: the factor(s) the LAST single (batched = 0) / env-batched step sampled from -- what the next reuse step of a Sigma period

@@ -571,18 +571,26 @@ class BatchedDeviceEpisode(_EpisodeLogs):
 def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H32_lam0.01", n_steps=None, seed: int = 1, device=None,
                      verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
                      arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0,
-                     rows: bool = False):
+                     rows: bool = False, staged: bool = False, controller: str = "covo-online"):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
-    covo-online, controller and env on the device, ONE host sync.  -> mean position error per instance [n_envs]; with trace=True
+    `controller` (covo-online by default), controller and env on the device, ONE host sync.  -> mean position error per instance
+    [n_envs]; with trace=True
     -> (that, ep.read_trace()): every instance's states, actions and plans of the episode; with fan=K ep.read_fan() -- K sampled
     rollouts of every step of every instance -- is appended to the returned tuple.  update: the controller's update rule ("softmax" |
     "best" | "guarded"); arbiter=True (with "best" / "guarded") appends ep.read_arbiter(), every step's arbiter row.  diag / trace / fan
     are the step options compute_diag / compute_plan / compute_fan, update / iters / elite / sigma_period / sigma_adapt the options of
     those names (controllers/_options.py).  rows=True appends one dict {"elite": ep.read_elite(), "iters": ep.read_iters(), "sigma":
-    ep.read_sigma(), "post": ep.read_post()} -- every step's rows of the attachments -- holding the entries whose option is on."""
+    ep.read_sigma(), "post": ep.read_post()} -- every step's rows of the attachments -- holding the entries whose option is on.
+    controller: "covo-online" (the default), or one of the two baselines on the same instances and keys -- "mppi"
+    (BatchedMPPIController) and "covo-offline" (BatchedCoVOController(mode="offline"), every instance's Sigma table built by its
+    reset() from the episode's start states).  staged=True runs the baselines' staged batched step, which takes elite / update with
+    iters / every disturb_type / tracking_slow (controllers/batched.py); with "covo-online", whose batch is staged already, it is a
+    ValueError."""
+    if controller not in ("covo-online", "mppi", "covo-offline"):
+        raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi' or 'covo-offline'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
-    check_step_options(None, "online", **opts)  # ValueError before anything is built
+    check_step_options(None, "online" if controller == "covo-online" else controller, **opts)  # ValueError before anything is built
     if arbiter and update == "softmax":
         raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
@@ -590,12 +598,18 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     ks = crandom.split(rng, 3 * n_envs + 1)
     params = [env.sample_params(ks[e]) for e in range(n_envs)]
     N, H, lam = (lambda p: (int(p[0][1:]), int(p[1][1:]), float(p[2][3:])))(controller_params.split("_"))
-    c0, cp0 = get_controller(env, "covo-online", controller_params, device=device, compute_info=False)
+    c0, cp0 = get_controller(env, controller, controller_params, device=device, compute_info=False)
     cp0 = c0.init_control_params
-    b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                          sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=c0.core.device, **opts)
+    kw = dict(discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=c0.core.device, staged=staged, **opts)
+    if controller == "mppi":
+        b = controllers.BatchedMPPIController(env, n_envs, N, H, lam, sigmas=cp0.sample_sigma, **kw)
+    else:
+        b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, sample_sigma=cp0.sample_sigma,
+                                              mode="offline" if controller == "covo-offline" else "online", **kw)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
+    if controller == "covo-offline":  # (the table keys: children of the instances' control keys, which stay what they were)
+        b.reset(ep.states0, params, [crandom.split(k)[1] for k in ks[2 * n_envs:3 * n_envs]])
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
     t0 = time_module.time()
     b.run_episode(ep, ks[2 * n_envs:3 * n_envs], T)

@@ -842,9 +842,10 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
  * MPPI and covo-offline run as ONE fused launch for all instances (csrc/step_small.hip with the instance as a grid dimension)
  * behind the key upload -- two launches per batched step, the fused one replayed from a hipGraph; instance e's new mean, action
  * buffer, costs (and MPPI's covariances) are bit-identical to covo_mpc_step on instance e alone.  base.groupmin is not used by
- * them (may be NULL).  There is no staged fallback: what the fused launch does not take is refused before anything is launched,
- * with a message that names the condition -- for every instance: reward_kind = COVO_REWARD_PENYAW, disturb_kind NONE or GAUSSIAN,
- * gamma_sigma == 0, n_samples <= 16 384 (256 groups of 64); all instances share reward_kind, rollover_terminate and disturb_kind.
+ * them (may be NULL).  Unless covo_set_step_batched_staged (below) is on there is no staged fallback: what the fused launch does
+ * not take is refused before anything is launched, with a message that names the condition -- for every instance: reward_kind =
+ * COVO_REWARD_PENYAW, disturb_kind NONE or GAUSSIAN, gamma_sigma == 0, n_samples <= 16 384 (256 groups of 64); all instances share
+ * reward_kind, rollover_terminate and disturb_kind.
  * covo_debug_time_batched is refused after a step in these two modes (it replays covo-online's launch groups only; time the
  * fused launch with events around covo_mpc_step_batched_mode).
  * covo_run_episode_batched_mode = covo_run_episode_batched with the batched step in the chosen mode (same key threading, same
@@ -855,12 +856,31 @@ typedef struct covo_batch_mode_args {
     int32_t n_table;         /* offline: rows of every instance's L_table */
     const float *L_table;    /* offline: see above */
     int64_t L_table_stride;  /* offline: floats between consecutive instances' tables; 0 = one shared table */
-    float gamma_sigma;       /* MPPI: must be 0 (the covariance adaptation is not batched) */
+    float gamma_sigma;       /* MPPI: must be 0 (the fused launch has no covariance adaptation) unless covo_set_step_batched_staged */
     int32_t pad_;
 } covo_batch_mode_args;
 
 int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params,
                                const uint32_t *keys, void *stream);
+
+/* The staged env-batched MPPI / covo-offline step (additive to ABI 10: COVO_HAS_BATCHED_STAGED; off by default, and off changes
+ * nothing a caller can observe).  on != 0: covo_mpc_step_batched_mode and covo_run_episode_batched_mode run these two modes as the
+ * launch sequence of a single staged step with the instance as a grid dimension -- per pass: begin | per-step disturbance tables |
+ * sampling | rollout | update, one linear stream of launches behind the key upload, captured into a hipGraph on the second identical
+ * call -- ALSO for a configuration the fused launch would take: one switch, one behaviour.  Instance e's new mean, action buffer,
+ * costs, MPPI covariances and attachment rows are bit-identical to covo_mpc_step on instance e alone (and so, where the fused launch
+ * applies, to the fused batched step) while the batched and the single rollout choose the same workgroup shape: n_envs *
+ * ceil(n_samples / 64) < 1024, as for covo_mpc_step_batched; above, the update's sums are formed over other record boundaries and
+ * agree to fp32 rounding.  It takes what the fused launch refuses: disturb_kind PERIODIC / SIN / DRAG / MIXED, the
+ * realworld reward, MPPI's gamma_sigma != 0 (covo_batch_mode_args.gamma_sigma; a_cov[e] adapted in place, mppi.py:119-125),
+ * n_samples up to the handle's n_local, the ESS floor, the elite-set update, the posterior covariance, and iterations per step
+ * together with the update arbiter.  Its own refusals (COVO_E_BADARG before any launch, the message names the condition):
+ * base.groupmin == NULL (the update reads the per-wave minima); gamma_sigma != 0 outside COVO_MODE_MPPI; gamma_sigma != 0 together
+ * with the ESS floor or the elite-set update (those two covariance updates have no instance dimension); a sample-sharded handle;
+ * instances that differ in reward_kind / rollover_terminate / disturb_kind, as for covo_mpc_step_batched.  covo_debug_time_batched
+ * stays refused after such a step.  Changing the switch drops the handle's captured step graphs.  COVO_MODE_COVO_ONLINE ignores it. */
+#define COVO_HAS_BATCHED_STAGED 1
+int covo_set_step_batched_staged(covo_handle_t h, int32_t on);
 
 /* Lower Cholesky factors of `batch` symmetric PD n x n fp32 matrices (1 <= n <= 128, row-major, densely packed), the
  * factorisation inside jax.random.multivariate_normal (covo.py:216, mppi.py:59).
