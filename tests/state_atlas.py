@@ -1,0 +1,124 @@
+"""Start states off hover (a plain helper module, like tests/chol_cases.py): tests/conftest.py::make_problem always gives a level
+vehicle (yaw 0.04 rad, |omega| 0.3 rad/s) within 5 cm of its target.  atlas_state(name) takes that problem and overrides the attitude,
+the body rates or the position / velocity with the upset states the controller exists to recover from: every octant of the reward's
+yaw atan2 (utils.py:289-290), the yaw sign change inside the horizon, the near-singular attitude (both atan2 arguments ~ 0), inverted
+and tumbling attitudes (rollover-terminal at step 0), a far / fast departure, a visibly non-unit stored quaternion and the double
+cover (-q: the same attitude, quat[3] < 0).
+
+Quaternions are the project's (x, y, z, w); attitudes are ZYX Euler angles (yaw about z first), so that the reward's
+yaw = atan2(2 (w z + x y), 1 - 2 (y^2 + z^2)) of the noise-free quaternion IS the entry's yaw.  1e-3 of normal noise is added to the
+quaternion (covo.py:198 plans from the noisy, un-normalised one) and every input is rounded to fp32, as make_problem does.
+"""
+import numpy as np
+
+from tests.conftest import make_problem
+
+PI = np.pi
+DEG = np.pi / 180.0
+
+
+def euler_quat(roll=0.0, pitch=0.0, yaw=0.0):
+    """ZYX Euler angles -> unit quaternion (x, y, z, w)"""
+    cr, sr = np.cos(roll / 2), np.sin(roll / 2)
+    cp, sp = np.cos(pitch / 2), np.sin(pitch / 2)
+    cy, sy = np.cos(yaw / 2), np.sin(yaw / 2)
+    return np.array([sr * cp * cy - cr * sp * sy, cr * sp * cy + sr * cp * sy, cr * cp * sy - sr * sp * cy,
+                     cr * cp * cy + sr * sp * sy])
+
+
+# name -> overrides.  euler: (roll, pitch, yaw); scale: factor on the unit quaternion; noise: sigma of the quaternion noise;
+# omega: body rates; dpos / dvel: added to make_problem's position / velocity; negate: make_problem's own quaternion, negated
+ATLAS = {
+    "yaw_pi_minus": dict(euler=(0.0, 0.0, PI - 1e-3)),          # yd < 0, yn > 0
+    "yaw_pi_plus": dict(euler=(0.0, 0.0, -PI + 1e-3)),          # yd < 0, yn < 0
+    "yaw_half_pi": dict(euler=(0.0, 0.0, PI / 2)),              # yd ~ 0: |yn| > |yd|
+    "yaw_quarter": dict(euler=(0.0, 0.0, PI / 4)),              # |yn| ~ |yd|: the octant boundary
+    "yaw_3quarter_neg": dict(euler=(0.0, 0.0, -3 * PI / 4)),
+    "yaw_cross": dict(euler=(0.0, 0.0, 0.02), noise=1e-4, omega=(0.0, 0.0, -2.5)),  # the yaw changes sign inside the horizon
+    "near_singular": dict(euler=(0.0, 89 * DEG, 0.3)),          # yn, yd both ~ 0.017
+    "inverted": dict(euler=(PI - 0.05, 0.0, 0.2)),
+    "roll_120_spin": dict(euler=(120 * DEG, 0.0, 0.0), omega=(25.0, -18.0, 6.0)),
+    "far_fast": dict(euler=(0.4, -0.3, 1.0), dpos=(1.2, -0.9, 0.7), dvel=(3.0, -2.5, 1.5)),
+    "unnorm_q": dict(euler=(0.3, 0.2, -2.0), scale=1.3),
+    "double_cover": dict(negate=True),                          # qw ~ -0.99: same attitude, rollover-terminal
+}
+NAMES = tuple(ATLAS)
+BENIGN = tuple(n for n in NAMES if n != "near_singular")
+ROLLOVER_AT_0 = ("inverted", "roll_120_spin", "double_cover")
+
+
+def atlas_state(name, seed=0, time=37):
+    """make_problem(seed, time) with the overrides of ATLAS[name] -> (s, p, rng): oracle state (fp64 fields holding fp32 numbers),
+    parameters and the generator to go on drawing from."""
+    o = ATLAS[name]
+    s, p, rng = make_problem(seed, time)
+    z = rng.normal(size=4)  # drawn for every entry: the generator leaves every entry in the same place
+    if o.get("negate"):
+        quat = -s.quat
+    else:
+        quat = o.get("scale", 1.0) * euler_quat(*o["euler"]) + o.get("noise", 1e-3) * z
+    kw = dict(quat=quat)
+    if "omega" in o:
+        kw["omega"] = np.asarray(o["omega"], dtype=np.float64)
+    if "dpos" in o:
+        kw["pos"] = s.pos + np.asarray(o["dpos"])
+    if "dvel" in o:
+        kw["vel"] = s.vel + np.asarray(o["dvel"])
+    s = s.replace(**kw).astype(np.float32).astype(np.float64)
+    return s, p, rng
+
+
+# The seed of the rollout cases (actions of tests/test_gpu_state_atlas.py (a), sigma = 0.5).  roll_120_spin at seed 0 holds ONE sample
+# (876 of 1024) that tumbles through the yaw term's singular attitude for eight steps (hypot(yn, yd) down to 1.3e-3): the fp64 cost
+# of that sample moves by 2.4e-5 relative when every input moves by one fp32 ulp -- the level of near_singular, 4 x any other
+# sample of any benign entry (one_ulp_shift below; asserted in tests/test_state_atlas.py) -- so no fp32 evaluation of it is held to
+# 1e-5.  Seed 1 is the first whose samples are all as well conditioned as the other entries'.
+ROLLOUT_SEED = {"roll_120_spin": 1}
+
+
+def rollout_case(name, N=1024, sigma=0.5):
+    """(s, p, a): the entry's state and N action sequences around hover (the formula of tests/test_gpu_parity.py::sample_actions,
+    a GPU-only module) -- the inputs of the rollout comparisons, on the CPU and on the GPU"""
+    from oracle import ref_np as R
+    s, p, rng = atlas_state(name, seed=ROLLOUT_SEED.get(name, 0))
+    a = np.clip(R.hover_action(p, 32, np.float64)[None] + sigma * rng.normal(size=(N, 32, 4)), -1, 1).astype(np.float32)
+    return s, p, a
+
+
+def one_ulp_shift(s, p, a, discount):
+    """Conditioning of the rollout cost in fp64 alone: per sample, the sum over its 141 inputs (position, velocity, quaternion, body
+    rates, 128 actions) of |c64(that input one fp32 ulp up) - c64|, relative to max(1, |c64|): what one fp32 ulp on every input
+    moves the exact cost by, to first order."""
+    from oracle import c_oracle as CO
+    up = lambda x: np.nextafter(np.asarray(x, np.float32), np.float32(np.inf)).astype(np.float64)
+    d, z = float(np.float32(discount)), np.zeros(3)
+    a = a.astype(np.float64)
+    N = a.shape[0]
+    base = CO.rollout(s, p, a, d, z, dtype=np.float64)
+    tot = np.zeros(N)
+    for f in ("pos", "vel", "quat", "omega"):
+        for i in range(len(getattr(s, f))):
+            v = getattr(s, f).copy()
+            v[i] = up(v[i])
+            tot += np.abs(CO.rollout(s.replace(**{f: v}), p, a, d, z, dtype=np.float64) - base)
+    flat = a.reshape(N, 128)
+    upf = np.minimum(up(flat), 1.0)
+    for i in range(128):
+        b = flat.copy()
+        b[:, i] = upf[:, i]
+        tot += np.abs(CO.rollout(s, p, b.reshape(N, 32, 4), d, z, dtype=np.float64) - base)
+    return tot / np.maximum(1.0, np.abs(base))
+
+
+def yaw_args(q):
+    """(yn, yd) of the reward's yaw = atan2(yn, yd) (utils.py:289-290) on the stored quaternion"""
+    return 2 * (q[3] * q[2] + q[0] * q[1]), 1 - 2 * (q[1] ** 2 + q[2] ** 2)
+
+
+def rel_err(x, ref):
+    return np.abs(x - ref) / np.maximum(np.abs(ref), 1.0)
+
+
+def loss3(e):
+    """(max, q99, median) of an error sample"""
+    return np.array([np.max(e), np.quantile(e, 0.99), np.median(e)])

@@ -5,6 +5,9 @@ the same seeded inputs.  Tolerances (north_star: 1e-5 relative fp32):
   softmax update            <= 1e-5 absolute on a_mean in [-1,1]
   Hessian                   <= 1e-9 absolute vs the fp64 AD oracle
   Sigma / chol(Sigma)       <= 1e-6 relative Frobenius vs fp64 LAPACK
+Start states come from two sources: tests/conftest.py::make_problem (level, yaw 0.04 rad, within 5 cm of the target: every test
+of this file) and tests/state_atlas.py (yaw octants, near-singular, inverted, tumbling, far / fast, non-unit and negated quaternions:
+tests/test_gpu_state_atlas.py runs the same kernels from those).
 """
 import ctypes as C
 import os
@@ -1237,7 +1240,11 @@ def _oracle_check_of_a_fused_step(name, env, params, ns, a_mean_before, k_act, c
             assert (rel < 1e-5).mean() > 0.995 and np.median(rel) < 2e-6, (name, N, (rel < 1e-5).mean())
             rel = np.where(rel < 1e-5, rel, 0.0)
         bar = max(bar, 1.5 * rel_err(c32, cost_ref).max())
+        print(f"  {name} N={N}: {int((rel >= 1e-5).sum())} of {len(rel)} samples needed the widened bar {bar:.2e} "
+              f"(worst {rel.max():.2e}; allowed {max(2, N // 4096)})")
         assert (rel >= 1e-5).sum() <= max(2, N // 4096), (name, N, int((rel >= 1e-5).sum()))
+    else:
+        print(f"  {name} N={N}: 0 of {len(rel)} samples needed a widened bar (worst {rel.max():.2e})")
     assert rel.max() < bar, (name, N, rel.max(), bar)
     if name == "covo-online":
         Sref = R.optimize_sigma(CO.hessian(so, po, am.reshape(-1), 32), 0.5, 32, 4)

@@ -122,14 +122,34 @@ def test_plan_cost_is_the_rollout_kernels(name, N, disturb, task, rollover, disc
     core1.close()
 
 
+def check_plan_against_oracle(env, name, params, ns, k_act, cp, cinfo, where):
+    """The plan row of one step (cinfo of a compute_plan controller, cp its new control params) against oracle.c_oracle.rollout in
+    fp64 on clip(a_mean_new) from the noisy state `ns` with the step's shared vector: positions within 2e-5, cost within 1e-5
+    relative.  -> (rewards, poses) of the oracle."""
+    from oracle import c_oracle as CO
+    from oracle import ref_np as R
+    fs = np.zeros(3)
+    if name == "mppi":
+        step_key = cr.split(cr.split(k_act)[0])[1]
+        fs = np.asarray(env.rollout_disturbance(step_key, params, deterministic=False), dtype=np.float64)
+    so = R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
+                 vel_tar=ns.vel_tar, acc_tar=ns.acc_tar, time=ns.time, pos_traj=ns.pos_traj, vel_traj=ns.vel_traj,
+                 acc_traj=ns.acc_traj).astype(np.float64)
+    a = cp.a_mean.clamp(-1.0, 1.0).cpu().numpy().astype(np.float64)[None]
+    cost_ref, rew, poses = CO.rollout(so, R.Params().fp32(), a, 1.0, fs, dtype=np.float64, want_rewards=True, want_poses=True)
+    dpos = np.abs(cinfo["pos_plan"].cpu().numpy() - poses[:, 0]).max()
+    dcost = rel_err(cinfo["cost_plan"].cpu().numpy(), cost_ref[0])
+    print(f"  {where}: |pos_plan - poses| {dpos:.2e}, cost rel {dcost:.2e}")
+    assert dpos < 2e-5 and dcost < 1e-5, (where, dpos, dcost)
+    return rew, poses
+
+
 @pytest.mark.parametrize("name,N,time0", [("covo-online", 1024, None), ("covo-offline", 1024, None), ("mppi", 1024, None),
                                           ("covo-online", 65536, 290), ("mppi", 65536, 290)])
 def test_plan_against_the_fp64_oracle(name, N, time0):
     """oracle.c_oracle.rollout in fp64 on clip(a_mean_new) from the same noisy state with the same shared vector: positions within
     2e-5, cost within 1e-5 relative.  time0 = 290: the plan terminates inside the horizon (time >= 300 from rollout step 10), so
     the reward freeze is exercised while the positions keep integrating."""
-    from oracle import c_oracle as CO
-    from oracle import ref_np as R
     env = _env("gaussian", False, "tracking_zigzag")
     c, cp = _build(env, name, N)
     cp, obs, info, state, params = _start(env, c, cp, name)
@@ -142,19 +162,7 @@ def test_plan_against_the_fp64_oracle(name, N, time0):
             info = dict(info, noisy_state=ns)
         u, cp, cinfo = c(obs, state, params, k_act, cp, info)
         torch.cuda.synchronize()
-        fs = np.zeros(3)
-        if name == "mppi":
-            step_key = cr.split(cr.split(k_act)[0])[1]
-            fs = np.asarray(env.rollout_disturbance(step_key, params, deterministic=False), dtype=np.float64)
-        so = R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
-                     vel_tar=ns.vel_tar, acc_tar=ns.acc_tar, time=ns.time, pos_traj=ns.pos_traj, vel_traj=ns.vel_traj,
-                     acc_traj=ns.acc_traj).astype(np.float64)
-        a = cp.a_mean.clamp(-1.0, 1.0).cpu().numpy().astype(np.float64)[None]
-        cost_ref, rew, poses = CO.rollout(so, R.Params().fp32(), a, 1.0, fs, dtype=np.float64, want_rewards=True, want_poses=True)
-        dpos = np.abs(cinfo["pos_plan"].cpu().numpy() - poses[:, 0]).max()
-        dcost = rel_err(cinfo["cost_plan"].cpu().numpy(), cost_ref[0])
-        print(f"  {name} N={N} time0={time0} step {step}: |pos_plan - poses| {dpos:.2e}, cost rel {dcost:.2e}")
-        assert dpos < 2e-5 and dcost < 1e-5, (name, N, time0, step, dpos, dcost)
+        rew, poses = check_plan_against_oracle(env, name, params, ns, k_act, cp, cinfo, f"{name} N={N} time0={time0} step {step}")
         if time0 is not None:
             assert rew[0, -1] == rew[0, -2] and not np.array_equal(poses[-1, 0], poses[-2, 0])  # frozen rewards, moving positions
         obs, state, _, _, info = env.step(k_step, state, u.cpu().numpy(), params)
