@@ -276,13 +276,77 @@ static int enqueue_online_chain(covo_ctx *h, const OnlineChainView &v, hipStream
     return (!streamed && (M & 8)) ? launch_noise_gemm(nd, s) : 0;
 }
 
-// ---- the update behind the rollout, single or env-batched.  The caller has filled `up` with its layout (costs, stripes, records and
-// their scratch, the blend, batch; MPPI's covariance adaptation: gamma_sigma != 0 with a_cov_old / a_cov_out); this adds the targets
-// of the staged updates and runs: the ESS floor's solver (rollout costs + per-wave minima -> 1 / lam_eff in lam_rows) or the elite
-// selector (costs -> 0/1 weights off elite_rows) when attached -- never both (refused at the C boundary) --, then the ONE update
-// launch set.  records: the rollout's workgroups left the stage-1 records (never with a staged update or the covariance adaptation).
-static int enqueue_update(covo_ctx *h, UpdateDesc &up, bool records, hipStream_t s)
+// ---- one description of a step's rollout and update, single or env-batched.  BatchInst: the buffers of one instance (the single
+// step's own; instance e of a batched step's argument block)
+struct BatchInst {
+    const float *state, *pos_traj, *vel_traj;
+    float *a_mean, *a, *cost, *groupmin;
+};
+// Do the rollout's G workgroups leave the softmax update's stage-1 records themselves (rollout.hip: rollout_record)?  When they fit the
+// merge; never with MPPI's covariance adaptation (second moments: its own stage 1, reduce.hip) or a staged update (ESS floor, elite
+// set: weights that exist only after the costs).  Asked by the two builders below and nobody else: they must agree, or the merge reads
+// records nobody wrote.
+static bool rollout_leaves_records(const covo_ctx *h, int G, bool cov_adapt)
 {
+    return G <= h->max_red_blocks && !cov_adapt && !covo_update_staged(h);
+}
+// one instance's rollout on G workgroups; records / diag_rec (null: no diagnostics): where they would leave their records.  The
+// caller adds xcd_groups (the single step: its position statistics)
+static RolloutDesc rollout_desc(const covo_ctx *h, const BatchInst &i, int T, int N, const covo_env_params *params,
+                                const float *f_shared_dev, const float *f_tab, int G, bool cov_adapt, float *records, float *diag_rec)
+{
+    const bool rec = rollout_leaves_records(h, G, cov_adapt);
+    RolloutDesc ro;
+    ro.state = i.state;
+    ro.pos_traj = i.pos_traj;
+    ro.vel_traj = i.vel_traj;
+    ro.T = T;
+    ro.params = params;
+    ro.f_shared_dev = f_shared_dev;
+    ro.f_tab = f_tab;
+    ro.a = i.a;
+    ro.N = N;
+    ro.discount = h->cfg.discount;
+    ro.cost = i.cost;
+    ro.groupmin = rec ? nullptr : i.groupmin;
+    ro.records = rec ? records : nullptr;
+    ro.lam = h->cfg.lam;
+    ro.diag_rec = rec ? diag_rec : nullptr;
+    ro.clip = ROLLOUT_CLIP_TRUSTED;  // a comes straight from the noise kernels
+    return ro;
+}
+// the update behind that rollout (records: it left u.up.partials).  i: the single step's buffers / instance 0's of a batch (dense
+// slices); the caller adds its layout (batch_update_desc) and, under cov_adapt, gamma_sigma != 0 with a_cov_old / a_cov_out
+struct StepUpdate {
+    UpdateDesc up;
+    bool records;
+};
+static StepUpdate update_desc(const covo_ctx *h, const BatchInst &i, int N, int G, bool cov_adapt, const float *partials,
+                              const float *a_mean_old, float gamma_mean, float *diag_rec, float *diag_out, float *iter_out)
+{
+    StepUpdate u;
+    u.records = rollout_leaves_records(h, G, cov_adapt);
+    u.up.cost = i.cost;
+    u.up.a = i.a;
+    u.up.N = N;
+    u.up.blockmin = i.groupmin;
+    u.up.partials = partials;  // (the rollout's records, if it left them)
+    u.up.G = G;
+    u.up.a_mean_old = a_mean_old;
+    u.up.gamma_mean = gamma_mean;
+    u.up.a_mean_out = i.a_mean;
+    u.up.diag_rec = diag_rec;
+    u.up.diag_out = diag_out;
+    u.up.iter_out = iter_out;
+    return u;
+}
+
+// adds the targets of the staged updates and runs: the ESS floor's solver (rollout costs + per-wave minima -> 1 / lam_eff in lam_rows)
+// or the elite selector (costs -> 0/1 weights off elite_rows) when attached -- never both (refused at the C boundary) --, then the ONE
+// update launch set
+static int enqueue_update(covo_ctx *h, StepUpdate &u, hipStream_t s)
+{
+    UpdateDesc &up = u.up;
     int rc;
     float *lam_rows = covo_lam_target(h), *elite_rows = covo_elite_target(h);
     up.n_blockmin = (up.N + 63) / 64;
@@ -292,7 +356,7 @@ static int enqueue_update(covo_ctx *h, UpdateDesc &up, bool records, hipStream_t
     if (elite_rows != nullptr && (rc = launch_elite_select(up.cost, up.N, up.batch, h->elite_K, elite_rows, s))) return rc;
     if (up.gamma_sigma != 0.0f) return elite_rows != nullptr ? launch_elite_update_cov(h, up, s) : launch_softmax_update_cov(h, up, s);
     if (elite_rows != nullptr) return launch_elite_reduce(h, up, s);
-    return records ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
+    return u.records ? launch_merge(up, h->cfg.lam, s) : launch_softmax_reduce(h, up, s);
 }
 
 // the launch sequence of one pass of a single step (everything reads per-step scalars from st->dyn)
@@ -360,62 +424,36 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
             if ((rc = launch_noise_blockdiag(nd, s))) return rc;
         }
     }
-    // the rollout's workgroups leave the softmax update's stage-1 records themselves when they fit the merge (rollout.hip:
-    // rollout_record); otherwise the stand-alone stage-1 kernel runs over the costs
+    // the rollout's workgroups leave the softmax update's stage-1 records themselves when they may (rollout_leaves_records); otherwise
+    // the stand-alone stage-1 kernel runs over the costs
     const int G = rollout_workgroups(N, a.pos_stats != nullptr);
-    // MPPI's covariance adaptation needs second moments the in-rollout records do not carry: its own stage 1 (reduce.hip)
     const bool cov_adapt = a.mode == COVO_MODE_MPPI && a.gamma_sigma != 0.0f;
-    // the ESS floor, the elite set: the rollout's in-launch records are formed with weights fixed before the costs exist -- staged, like
-    // cov_adapt
-    const bool records = G <= h->max_red_blocks && !cov_adapt && !covo_update_staged(h);
     // the step's sampling diagnostics (covo_set_step_diag): the diagnostic variants of the same launches; a sharded step has none
     float *dg = a.partial_out == nullptr ? covo_diag_target(h) : nullptr;
-    RolloutDesc ro;
-    ro.state = state;
-    ro.pos_traj = a.pos_traj;
-    ro.vel_traj = a.vel_traj;
-    ro.T = a.T;
-    ro.params = &p;
-    ro.f_shared_dev = fdev;
-    ro.f_tab = tables ? st->f_tab_rollout : nullptr;
-    ro.a = a.a;
-    ro.N = N;
-    ro.discount = h->cfg.discount;
-    ro.cost = a.cost;
-    ro.groupmin = records ? nullptr : a.groupmin;
+    const BatchInst inst = {state, a.pos_traj, a.vel_traj, a.a_mean, a.a, a.cost, a.groupmin};
+    RolloutDesc ro = rollout_desc(h, inst, a.T, N, &p, fdev, tables ? st->f_tab_rollout : nullptr, G, cov_adapt, h->ws_partials,
+                                  dg ? h->ws_diag_rec : nullptr);
     ro.pos_stats = a.pos_stats;
     ro.stats_ws = h->ws_stats;
-    ro.records = records ? h->ws_partials : nullptr;
-    ro.lam = h->cfg.lam;
-    ro.diag_rec = (records && dg) ? h->ws_diag_rec : nullptr;
     ro.xcd_groups = a.mode == COVO_MODE_MPPI ? 4 : 0;  // MPPI's block-diagonal kernel: 256 samples per workgroup
-    ro.clip = ROLLOUT_CLIP_TRUSTED;                    // a comes straight from the noise kernels above
     if ((M & 16) && (rc = launch_rollout(ro, s))) return rc;
     if (!(M & 32)) return 0;
     // weights + update: finish locally (blend with am_shift, diagnostics), or -- a sample-sharded rank -- leave this shard's
     // record for the all-gather (covo.py:266-275)
-    UpdateDesc up;
-    up.cost = a.cost;
-    up.a = a.a;
-    up.N = N;
-    up.blockmin = a.groupmin;
-    up.partials = h->ws_partials;  // (the rollout's records, if it left them)
-    up.G = G;
+    StepUpdate u = update_desc(h, inst, N, G, cov_adapt, h->ws_partials, am_shift, a.gamma_mean, h->ws_diag_rec, dg, iter_out);
     const bool sharded = a.partial_out != nullptr;
-    up.a_mean_old = am_shift;
-    up.gamma_mean = a.gamma_mean;
-    up.a_mean_out = sharded ? nullptr : a.a_mean;
-    up.partial_out = a.partial_out;
-    up.diag_rec = h->ws_diag_rec;
-    up.diag_out = dg;
-    up.iter_out = sharded ? nullptr : iter_out;
+    if (sharded) {
+        u.up.partial_out = a.partial_out;
+        u.up.a_mean_out = nullptr;
+        u.up.iter_out = nullptr;
+    }
     if (cov_adapt) {  // mppi.py:109-125: new mean, then a_cov (already shifted by the begin launch) adapted in place; a sharded
                       // rank: its record with the second moments (836-float kind)
-        up.a_cov_old = a.a_cov;
-        up.gamma_sigma = a.gamma_sigma;
-        up.a_cov_out = sharded ? nullptr : a.a_cov;
+        u.up.a_cov_old = a.a_cov;
+        u.up.gamma_sigma = a.gamma_sigma;
+        u.up.a_cov_out = sharded ? nullptr : a.a_cov;
     }
-    return enqueue_update(h, up, records, s);
+    return enqueue_update(h, u, s);
 }
 
 // a debug setter since the last step changed what a captured graph baked in (launch set, deflation switch, diagnostics target)
@@ -626,34 +664,12 @@ static void batch_upload_keys(uint32_t *dyn, const uint32_t *keys, int E, hipStr
     }
     hipLaunchKernelGGL(batch_set_dyn_kernel, dim3(1), dim3(256), 0, s, dyn, blk, E);
 }
-// per instance: shift the mean (covo.py:201-203); act_key = split(rng_act)[1] (covo.py:212); f_shared = 0 (deterministic)
-// pass >= 1 of an iterated step (covo_set_step_iters): no shift, and the raw key is the previous pass's (d[10..11]) advanced
-__global__ void batch_begin_kernel(const float *__restrict__ a_mean, float *__restrict__ a_mean_shift, uint32_t *__restrict__ dyn,
-                                   const int pass)
-{
-    const int e = blockIdx.x, i = threadIdx.x;
-    uint32_t *d = dyn + 12 * e;
-    uint32_t raw[2] = {d[pass ? 10 : 0], d[pass ? 11 : 1]};
-    __syncthreads();
-    if (i < COVO_NA) {
-        a_mean_shift[e * COVO_NA + i] = (pass == 0 && i < COVO_NA - COVO_DU) ? a_mean[e * COVO_NA + i + COVO_DU] : a_mean[e * COVO_NA + i];
-    } else if (i == COVO_NA) {
-        if (pass) step_begin_advance(raw);
-        uint32_t k[2];
-        host_split(raw, 1u, k);
-        d[0] = k[0];
-        d[1] = k[1];
-        d[2] = d[3] = d[4] = 0u;
-        d[10] = raw[0];  // the raw controller key, for the step's disturbance tables (disturb.hip)
-        d[11] = raw[1];
-    }
-}
 
-// the begin launch of the STAGED env-batched MPPI / covo-offline step (covo_set_step_batched_staged): per instance what
-// step_begin_kernel does for one -- shift the mean (pass 0), the step's scalars through step_begin_derive / _next from the instance's
-// raw key (dyn[12 e + 0..1] as uploaded; pass >= 1: the previous pass's at [10..11]) with the instance's own shared_noise_scale, so that
-// MPPI's shared gaussian vector lands in dyn[12 e + 2..4] and the raw key at [10..11]; MPPI: the covariance shift (pass 0) + block
-// factors of a_cov[e] into Ls[e]
+// the begin launch of the env-batched steps with launches of their own (covo-online; MPPI / covo-offline under
+// covo_set_step_batched_staged): per instance what step_begin_kernel does for one -- shift the mean (pass 0; covo.py:201-203), the
+// step's scalars through step_begin_derive / _next from the instance's raw key (dyn[12 e + 0..1] as uploaded; pass >= 1: the previous
+// pass's at [10..11]) with its own shared_noise_scale: act_key to [0..1] (covo.py:212), MPPI's shared gaussian vector to [2..4] (scale
+// 0, CoVO's deterministic rollouts: zero bits), the raw key to [10..11]; MPPI (mppi_cov != null): shift (pass 0) + factor a_cov[e] into Ls[e]
 struct BatchScales {
     float v[COVO_MAX_ENVS];  // instance e's covo_shared_noise_scale
 };
@@ -684,7 +700,7 @@ __global__ void batch_mode_begin_kernel(const float *__restrict__ a_mean, float 
 }
 
 // the env-batched MPPI / covo-offline step (covo_mpc_step_batched_mode): ONE fused launch for all instances (step_small.hip,
-// grid = groups x instances) behind the key upload; scratch and graph cache of its own, next to the covo-online batch's
+// grid = groups x instances) behind the key upload; scratch and graph cache of its own, next to the staged batches'
 struct BatchSmall {
     int n_envs = 0, groups = 0;
     uint32_t *dyn = nullptr;     // [E][12]: the instances' raw rng_act of the current step (batch_set_dyn_kernel)
@@ -706,80 +722,63 @@ static void batch_small_free(BatchSmall *m)
     m->n_envs = m->groups = 0;
 }
 
-// the STAGED form of the same step (covo_set_step_batched_staged): begin | tables | sampling | rollout | update for all instances per
-// pass, one linear stream of launches; scratch and graph caches of its own, like BatchSmall
-struct BatchStaged {
-    int n_envs = 0;
-    uint32_t *dyn = nullptr;        // [E][12] as the covo-online batch's
+// What an env-batched step with launches of its own keeps (begin | tables | sampling | rollout | update for all instances per pass, one
+// linear stream): their scratch and the graphs over them.  BatchState holds TWO -- covo-online's (covo_mpc_step_batched) and the staged
+// MPPI / covo-offline step's (covo_set_step_batched_staged) --: a handle stepped alternately through both keeps either's scratch and graphs
+struct BatchCommon {
+    int n_envs = 0;                 // the instance count the device arrays were allocated for
+    uint32_t *dyn = nullptr;        // [E][12] the instances' per-step scalars (batch_set_dyn_kernel, batch_mode_begin_kernel)
     float *a_mean_shift = nullptr;  // [E][128]
-    float *Ls = nullptr;            // [E][H][4][4] MPPI's block factors
-    void *ro_args = nullptr;        // RolloutArgs[E]
-    float *partials = nullptr;      // [E][max_red_blocks][COVO_PARTIAL_FLOATS]
-    float *diag_rec = nullptr;      // [E][max_red_blocks][4]
-    float *diag_merge = nullptr;    // [E][COVO_PARTIAL_FLOATS]: the merged records the covariance update's diagnostics merge leaves
-    float *partials_cov = nullptr;  // [E][stage-1 grid][452]: MPPI's covariance adaptation; grown on demand
-    size_t partials_cov_cap = 0;
-    void *models = nullptr;         // dm::Model[E]
-    float *tab_rollout = nullptr;   // [E][H][4]
-    bool tables = false;
-    BatchScales scales;
-    std::vector<char> ro_args_host;
-    std::vector<covo_env_params> params;
-    covo_batch_mode_args key;  // with `stream` and `params`: what the scratch, the argument blocks and the graph were built for
-    hipStream_t stream = nullptr;
-    bool have_key = false;
-    GraphCache cache[2] = {};  // ([1] is never used: step_run_passes takes the pair)
-    void forget_graphs() { cache[0].forget(), cache[1].forget(); }
-};
-
-static void batch_staged_free(BatchStaged *q)
-{
-    q->forget_graphs();
-    q->have_key = false;
-    free_and_null(q->dyn, q->a_mean_shift, q->Ls, q->ro_args, q->partials, q->diag_rec, q->diag_merge, q->partials_cov, q->models,
-                  q->tab_rollout);
-    q->partials_cov_cap = 0;
-    q->n_envs = 0;
-}
-
-struct BatchState {
-    BatchSmall small;
-    BatchStaged staged;
-    int n_envs = 0;
-    uint32_t *dyn = nullptr;        // [E][12]
-    float *a_mean_shift = nullptr;  // [E][128]
-    double *R = nullptr;            // [E][128][128]
-    float *Sigma = nullptr, *L = nullptr;  // [E][128][128]
-    void *consts = nullptr;         // qm::Consts<double>[E]   (Hessian)
     void *ro_args = nullptr;        // RolloutArgs[E]          (rollout)
     float *partials = nullptr;      // [E][max_red_blocks][COVO_PARTIAL_FLOATS]: the instances' softmax stage-1 records
     float *diag_rec = nullptr;      // [E][max_red_blocks][4]: their diagnostic records (covo_set_step_diag)
     void *models = nullptr;         // dm::Model[E]            (disturbance tables, drag / mixed Hessian)
-    float *tab_rollout = nullptr, *tab_hess = nullptr;  // [E][H][4] the step's disturbance tables (periodic / sin / drag / mixed)
+    float *tab_rollout = nullptr;   // [E][H][4] the step's disturbance tables of the sampling rollouts (periodic / sin / drag / mixed)
     bool tables = false;            // the instances' disturbance model needs them
+    std::vector<char> ro_args_host;
+    std::vector<covo_env_params> params;
+    // with `stream` and `params`: what scratch, argument blocks and graphs were built for, while have_key (covo-online: `base` and
+    // mode = COVO_MODE_COVO_ONLINE in a zeroed struct)
+    covo_batch_mode_args key;
+    hipStream_t stream = nullptr;
+    bool have_key = false;
+    GraphCache cache[2] = {};  // [0] the step, [1] the reuse step of a Sigma period (covo-online only), as in StepState; both keyed by `key`
+    // (the key with the graphs: the rollout's argument blocks, which the cold block rebuilds, bake the launch set in as they do)
+    void forget() { cache[0].forget(), cache[1].forget(), have_key = false; }
+    void record(const covo_batch_mode_args &m, hipStream_t s) { key = m, stream = s, have_key = true; }
+};
+static void batch_common_free(BatchCommon *c)
+{
+    c->forget();
+    free_and_null(c->dyn, c->a_mean_shift, c->ro_args, c->partials, c->diag_rec, c->models, c->tab_rollout);
+    c->n_envs = 0;
+}
+
+// what the staged MPPI / covo-offline batch keeps next to its BatchCommon
+struct BatchStagedExtras {
+    float *Ls = nullptr;            // [E][H][4][4] MPPI's block factors
+    float *diag_merge = nullptr;    // [E][COVO_PARTIAL_FLOATS]: the merged records the covariance update's diagnostics merge leaves
+    float *partials_cov = nullptr;  // [E][stage-1 grid][452]: MPPI's covariance adaptation; only ever grows
+    size_t partials_cov_cap = 0;
+    BatchScales scales;             // the instances' shared_noise_scale (the begin launch's kernel argument)
+};
+
+struct BatchState {
+    BatchSmall small;
+    BatchCommon online, staged;
+    BatchStagedExtras sx;
+    // covo-online's own
+    double *R = nullptr;            // [E][128][128]
+    float *Sigma = nullptr, *L = nullptr;  // [E][128][128]
+    void *consts = nullptr;         // qm::Consts<double>[E]   (Hessian)
+    float *tab_hess = nullptr;      // [E][H][4] the Hessian's disturbance tables
+    float4 *eps_tiled = nullptr;    // [E][ceil(N/32)][16][64]: the step's epsilon of every instance, drawn under the Sigma chain's
+    size_t eps_cap = 0;             // finalize launch (eps_tiles.hpp), as in the single step; only ever grows
     void *env_inst = nullptr;       // EnvInst[env_inst_n] (env_step.hip): the per-instance constants of covo_env_step_batched
     int env_inst_n = 0;
     std::vector<covo_env_params> env_inst_params;
-    std::vector<char> ro_args_host;
-    std::vector<covo_env_params> params;
-    covo_batch_args key;  // with `stream`, `params` and `n_envs`: what the scratch was built for, while have_key
-    hipStream_t stream = nullptr;
-    bool have_key = false;
-    GraphCache cache[2] = {};  // [0] the step, [1] the reuse step of a Sigma period, as in StepState; both are keyed by `key`
-    void forget_graphs() { cache[0].forget(), cache[1].forget(); }
-    float4 *eps_tiled = nullptr;  // [E][ceil(N/32)][16][64]: the step's epsilon of every instance, drawn under the Sigma chain's
-    size_t eps_cap = 0;           // finalize launch (eps_tiles.hpp), as in the single step
 };
 
-// (not env_inst and eps_tiled: the batched step re-allocates its scratch when the instance count changes, possibly between
-// batch_env_inst and the env step launch that reads env_inst; eps_tiled only ever grows)
-static void batch_state_free(BatchState *b)
-{
-    b->forget_graphs();
-    b->have_key = false;
-    free_and_null(b->dyn, b->a_mean_shift, b->R, b->Sigma, b->L, b->consts, b->ro_args, b->partials, b->diag_rec, b->models,
-                  b->tab_rollout, b->tab_hess);
-}
 // The captured graphs (fused step, env-batched steps) hold the addresses of h->ws_sigma / h->ws_hess in their kernel nodes and bake
 // the handle's launch set in: whoever re-allocates a workspace (covo_grow_workspace) or meets a moved debug epoch calls this
 // first, so that a later step re-captures instead of replaying launches that point into freed memory.
@@ -789,11 +788,21 @@ void step_graphs_drop(covo_ctx *h)
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     if (st) st->forget_graphs();
     if (!b) return;
-    b->forget_graphs();
-    b->have_key = false;  // (the cold block of covo_step_batched_impl rebuilds the rollout's argument blocks: they bake the launch set in too)
+    b->online.forget();
+    b->staged.forget();
     b->small.cache.forget();
-    b->staged.forget_graphs();
-    b->staged.have_key = false;  // (its rollout argument blocks bake the launch set in, like the covo-online batch's)
+}
+
+// a device array that only ever grows: at least `need` elements
+template <class T>
+static int grow_device(T *&p, size_t &cap, size_t need)
+{
+    if (need <= cap) return 0;
+    free_and_null(p);
+    cap = 0;
+    COVO_CHECK_HIP(hipMalloc(&p, need * sizeof(T)));
+    cap = need;
+    return 0;
 }
 
 int covo_grow_workspace(covo_ctx *h, void **ws, size_t *bytes, size_t need, hipStream_t s)
@@ -815,10 +824,6 @@ static BatchState *batch_state(covo_ctx *h)
 }
 
 // instance e of a batched step's argument block
-struct BatchInst {
-    const float *state, *pos_traj, *vel_traj;
-    float *a_mean, *a, *cost, *groupmin;
-};
 static BatchInst batch_inst(const covo_batch_args &a, int e)
 {
     const int N = a.n_samples;
@@ -856,16 +861,88 @@ int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_
     return 0;
 }
 
+// (eps_tiled and env_inst outlive a change of the instance count: see covo_step_batched_impl)
 void batch_state_destroy(covo_ctx *h)
 {
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     if (!b) return;
-    batch_state_free(b);
+    batch_common_free(&b->online);
+    batch_common_free(&b->staged);
     batch_small_free(&b->small);
-    batch_staged_free(&b->staged);
-    free_and_null(b->eps_tiled, b->env_inst);
+    free_and_null(b->R, b->Sigma, b->L, b->consts, b->tab_hess, b->eps_tiled, b->env_inst, b->sx.Ls, b->sx.diag_merge, b->sx.partials_cov);
     delete b;
     h->batch = nullptr;
+}
+
+// a batch's update: instance e's records are [e][G] of c.partials; row e of the diagnostic buffer, of the solver's / the selector's
+// output and of iter_log ([e][pass]) is instance e's
+static StepUpdate batch_update_desc(const covo_ctx *h, const BatchCommon &c, const covo_batch_args &a, int pass, bool cov_adapt)
+{
+    StepUpdate u = update_desc(h, batch_inst(a, 0), a.n_samples, rollout_workgroups(a.n_samples, false, a.n_envs), cov_adapt, c.partials,
+                               c.a_mean_shift, a.gamma_mean, c.diag_rec, covo_diag_target(h), covo_iter_slot(h, pass));
+    u.up.partials_ws = c.partials;
+    u.up.batch = a.n_envs;
+    u.up.iter_stride = covo_step_iters(h);
+    return u;
+}
+
+// does the key an env-batched scratch was built for (valid: it has one) describe this call?
+static bool batch_key_same(bool valid, const covo_batch_mode_args &key, hipStream_t stream, const std::vector<covo_env_params> &have,
+                           const covo_batch_mode_args &m, const covo_env_params *params, hipStream_t s)
+{
+    const size_t E = (size_t)m.base.n_envs;
+    return valid && std::memcmp(&key, &m, sizeof(m)) == 0 && stream == s && have.size() == E &&
+           std::memcmp(have.data(), params, E * sizeof(covo_env_params)) == 0;
+}
+
+// ---- the cold block of both batches: new buffers / parameters / instance count (outside the steady state).  What differs:
+struct BatchColdDiff {
+    int xcd_groups;       // RolloutDesc::xcd_groups: 4 behind MPPI's block-diagonal kernel (as the single step tells its rollout), else 0
+    bool cov_adapt;       // MPPI's covariance adaptation rules the in-rollout records out
+    bool deterministic;   // the sampling rollouts' (covo.py:231 / mppi.py:74): with params[e] instance e's shared_noise_scale ...
+    BatchScales *scales;  // ... which goes here (null: not wanted)
+};
+// *same: nothing changed.  Else stale graphs are dropped, the scratch is (re)allocated on a new E and filled, and the key stays unset:
+// the caller adds its own allocations and ends with c->record()
+static int batch_cold(covo_ctx *h, BatchCommon *c, const covo_batch_mode_args &m, const covo_env_params *params, hipStream_t s,
+                      const BatchColdDiff &d, bool *same)
+{
+    const covo_batch_args &a = m.base;
+    const int E = a.n_envs, N = a.n_samples;
+    if ((*same = batch_key_same(c->have_key, c->key, c->stream, c->params, m, params, s))) return 0;
+    COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old argument blocks are done
+    c->forget();
+    if (c->n_envs != E) {
+        batch_common_free(c);
+        COVO_CHECK_HIP(hipMalloc(&c->dyn, (size_t)E * 12 * sizeof(uint32_t)));
+        COVO_CHECK_HIP(hipMalloc(&c->a_mean_shift, (size_t)E * COVO_NA * sizeof(float)));
+        COVO_CHECK_HIP(hipMalloc(&c->ro_args, rollout_args_bytes(E)));
+        COVO_CHECK_HIP(hipMalloc(&c->partials, (size_t)E * h->max_red_blocks * COVO_PARTIAL_FLOATS * sizeof(float)));
+        COVO_CHECK_HIP(hipMalloc(&c->diag_rec, (size_t)E * h->max_red_blocks * 4 * sizeof(float)));
+        COVO_CHECK_HIP(hipMalloc(&c->models, disturb_models_bytes(E)));
+        COVO_CHECK_HIP(hipMalloc(&c->tab_rollout, (size_t)E * COVO_H * 4 * sizeof(float)));
+        c->n_envs = E;
+    }
+    c->params.assign(params, params + E);
+    std::vector<char> tmp(disturb_models_bytes(E), 0);
+    disturb_fill_models(params, E, tmp.data());
+    COVO_CHECK_HIP(hipMemcpy(c->models, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
+    c->tables = covo_needs_tables(params[0]);
+    c->ro_args_host.assign(rollout_args_bytes(E), 0);
+    const int G = rollout_workgroups(N, false, E);
+    if (d.scales) std::memset(d.scales, 0, sizeof(*d.scales));
+    for (int e = 0; e < E; ++e) {
+        if (d.scales) d.scales->v[e] = covo_shared_noise_scale(params[e], d.deterministic);
+        // (f_shared_dev: MPPI's own shared vector of the instance, as the begin launch leaves it)
+        RolloutDesc ro = rollout_desc(h, batch_inst(a, e), a.T, N, &params[e], reinterpret_cast<const float *>(c->dyn + 12 * e + 2),
+                                      c->tables ? c->tab_rollout + (size_t)e * COVO_H * 4 : nullptr, G, d.cov_adapt,
+                                      c->partials + (size_t)e * G * COVO_PARTIAL_FLOATS,
+                                      covo_diag_target(h) ? c->diag_rec + (size_t)e * G * 4 : nullptr);
+        ro.xcd_groups = d.xcd_groups;
+        rollout_fill_args(c->ro_args_host.data(), e, ro);
+    }
+    COVO_CHECK_HIP(hipMemcpy(c->ro_args, c->ro_args_host.data(), c->ro_args_host.size(), hipMemcpyHostToDevice));
+    return 0;
 }
 
 // Seven batched launch sets for all E instances: begin, Hessian (4 kernels), Sigma chain (~47), noise GEMM, rollout,
@@ -878,19 +955,23 @@ void batch_state_destroy(covo_ctx *h)
 static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, hipStream_t s, const DebugMasks &dbg = DebugMasks(),
                          const int pass = 0, const bool reuse = false)
 {
+    const BatchCommon &c = b->online;
     const int E = a.n_envs, N = a.n_samples;
     const int M = dbg.step;  // 63 outside covo_debug_time_batched (which replays selected launch groups)
     int rc;
-    if (M & 1) hipLaunchKernelGGL(batch_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, b->a_mean_shift, b->dyn, pass);
-    // covo.py:231: CoVO's sampling rollouts run step_env(deterministic=True); get_hessian likewise (covo.py:152)
-    if ((M & 1) && b->tables && (rc = launch_disturb_tables_batched(b->models, a.states, b->dyn, E, 1, b->tab_rollout, b->tab_hess, s)))
+    // covo.py:231: CoVO's sampling rollouts run step_env(deterministic=True): no shared vector (every scale 0), no covariance blocks
+    if (M & 1)
+        hipLaunchKernelGGL(batch_mode_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, c.a_mean_shift, c.dyn, BatchScales(),
+                           (float *)nullptr, (float *)nullptr, pass);
+    // get_hessian is deterministic likewise (covo.py:152)
+    if ((M & 1) && c.tables && (rc = launch_disturb_tables_batched(c.models, a.states, c.dyn, E, 1, c.tab_rollout, b->tab_hess, s)))
         return rc;
     OnlineChainView v;
     v.E = E;
-    v.dyn = b->dyn;
+    v.dyn = c.dyn;
     v.dyn_stride = 12;
     v.N = N;
-    v.mu = b->a_mean_shift;
+    v.mu = c.a_mean_shift;
     v.R = b->R;
     v.sample_sigma = a.sample_sigma;
     v.Sigma = a.a_cov ? a.a_cov : b->Sigma;
@@ -902,34 +983,17 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     v.hess.pos_traj = a.pos_traj;
     v.hess.vel_traj = a.vel_traj;
     v.hess.T = a.T;
-    v.hess.params = &b->params[0];
+    v.hess.params = &c.params[0];
     v.hess.consts_dev = b->consts;
     v.hess.traj_stride = (size_t)a.T * 3;
-    v.hess.f_tab = b->tables ? b->tab_hess : nullptr;
-    v.hess.models_dev = b->models;
+    v.hess.f_tab = c.tables ? b->tab_hess : nullptr;
+    v.hess.models_dev = c.models;
     v.ahead_groups = 4 | 8;
     if ((rc = enqueue_online_chain(h, v, s, dbg, pass, reuse))) return rc;
-    if ((M & 16) && (rc = launch_rollout_batched(b->ro_args_host.data(), b->ro_args, E, s))) return rc;
+    if ((M & 16) && (rc = launch_rollout_batched(c.ro_args_host.data(), c.ro_args, E, s))) return rc;
     if (!(M & 32)) return 0;
-    // row e of the diagnostic buffer, of the solver's / the selector's output and of iter_log is instance e's
-    const int G = rollout_workgroups(N, false, E);
-    UpdateDesc up;
-    up.cost = a.cost;
-    up.a = a.a;
-    up.N = N;
-    up.blockmin = a.groupmin;
-    up.partials_ws = b->partials;
-    up.partials = b->partials;  // the rollout's workgroups have left the records when they fit the merge: instance e's are [e][G]
-    up.G = G;
-    up.a_mean_old = b->a_mean_shift;
-    up.gamma_mean = a.gamma_mean;
-    up.a_mean_out = a.a_mean;
-    up.batch = E;
-    up.diag_rec = b->diag_rec;
-    up.diag_out = covo_diag_target(h);
-    up.iter_out = covo_iter_slot(h, pass);  // an iterated step: instance e's cost minimum of this pass to iter_log[e][pass]
-    up.iter_stride = covo_step_iters(h);
-    return enqueue_update(h, up, G <= h->max_red_blocks && !covo_update_staged(h), s);  // (as the cold block told the rollout: brec)
+    StepUpdate u = batch_update_desc(h, c, a, pass, false);
+    return enqueue_update(h, u, s);
 }
 
 // profiling aid (bench.py --config envs): `reps` copies of the selected launch groups of the LAST covo_mpc_step_batched call in
@@ -938,14 +1002,14 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
 int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us_out, hipStream_t run)
 {
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
-    if (!b || !b->have_key) {
+    if (!b || !b->online.have_key) {
         covo_set_error("covo_debug_time_batched: call covo_mpc_step_batched first");
         return COVO_E_BADARG;
     }
     COVO_CHECK_HIP(hipStreamSynchronize(run));
     DebugMasks dbg;
     dbg.step = step_mask;
-    return time_graph_replays(h, run, reps, us_out, [&](hipStream_t cs) { return batch_enqueue(h, b, b->key, cs, dbg); });
+    return time_graph_replays(h, run, reps, us_out, [&](hipStream_t cs) { return batch_enqueue(h, b, b->online.key.base, cs, dbg); });
 }
 
 int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
@@ -954,88 +1018,44 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
     const int E = args->n_envs;
     step_sync_epoch(h);
     BatchState *b = batch_state(h);
-    const bool same = b->have_key && b->n_envs == E && std::memcmp(&b->key, args, sizeof(*args)) == 0 && b->stream == s &&
-                      std::memcmp(b->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
+    BatchCommon *c = &b->online;
+    covo_batch_mode_args m;  // the scratch's key: this entry's part of it
+    std::memset(&m, 0, sizeof(m));
+    m.base = *args;
+    m.mode = COVO_MODE_COVO_ONLINE;
+    const bool new_E = c->n_envs != E;
+    bool same;
+    int rc;
+    if ((rc = batch_cold(h, c, m, params, s, BatchColdDiff{0, false, true, nullptr}, &same))) return rc;
     if (!same) {
-        // new buffers / parameters / instance count: (re)allocate scratch and drop the stale graph (outside the steady state)
-        COVO_CHECK_HIP(hipStreamSynchronize(s));
-        b->forget_graphs();
-        b->have_key = false;
-        if (b->n_envs != E) {
-            batch_state_free(b);
+        // (not eps_tiled and env_inst: the instance count may change between batch_env_inst and the env step launch that reads
+        // env_inst; eps_tiled only ever grows)
+        if (new_E || b->tab_hess == nullptr) {  // (null: an earlier attempt failed half way)
+            free_and_null(b->R, b->Sigma, b->L, b->consts, b->tab_hess);
             h->sigma_L = nullptr;  // (the factor buffer goes: the next step of a Sigma period refreshes)
             const size_t M = (size_t)COVO_NA * COVO_NA;
-            COVO_CHECK_HIP(hipMalloc(&b->dyn, (size_t)E * 12 * sizeof(uint32_t)));
-            COVO_CHECK_HIP(hipMalloc(&b->a_mean_shift, (size_t)E * COVO_NA * sizeof(float)));
             COVO_CHECK_HIP(hipMalloc(&b->R, (size_t)E * M * sizeof(double)));
             COVO_CHECK_HIP(hipMalloc(&b->Sigma, (size_t)E * M * sizeof(float)));
             COVO_CHECK_HIP(hipMalloc(&b->L, (size_t)E * M * sizeof(float)));
             COVO_CHECK_HIP(hipMalloc(&b->consts, hessian_consts_bytes(E)));
-            COVO_CHECK_HIP(hipMalloc(&b->ro_args, rollout_args_bytes(E)));
-            COVO_CHECK_HIP(hipMalloc(&b->partials, (size_t)E * h->max_red_blocks * COVO_PARTIAL_FLOATS * sizeof(float)));
-            COVO_CHECK_HIP(hipMalloc(&b->diag_rec, (size_t)E * h->max_red_blocks * 4 * sizeof(float)));
-            COVO_CHECK_HIP(hipMalloc(&b->models, disturb_models_bytes(E)));
-            COVO_CHECK_HIP(hipMalloc(&b->tab_rollout, (size_t)E * COVO_H * 4 * sizeof(float)));
             COVO_CHECK_HIP(hipMalloc(&b->tab_hess, (size_t)E * COVO_H * 4 * sizeof(float)));
-            b->n_envs = E;
         }
-        b->params.assign(params, params + E);
         std::vector<char> tmp(hessian_consts_bytes(E));
         hessian_fill_consts(params, E, tmp.data());
         COVO_CHECK_HIP(hipMemcpy(b->consts, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-        tmp.assign(disturb_models_bytes(E), 0);
-        disturb_fill_models(params, E, tmp.data());
-        COVO_CHECK_HIP(hipMemcpy(b->models, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-        b->tables = covo_needs_tables(params[0]);
-        b->ro_args_host.assign(rollout_args_bytes(E), 0);
-        const int N = args->n_samples;
-        const int bG = rollout_workgroups(N, false, E);
-        const bool brec = bG <= h->max_red_blocks && !covo_update_staged(h);  // (a floor, an elite set: staged update, see batch_enqueue)
-        for (int e = 0; e < E; ++e) {
-            const BatchInst i = batch_inst(*args, e);
-            RolloutDesc ro;
-            ro.state = i.state;
-            ro.pos_traj = i.pos_traj;
-            ro.vel_traj = i.vel_traj;
-            ro.T = args->T;
-            ro.params = &params[e];
-            ro.f_shared_dev = reinterpret_cast<const float *>(b->dyn + 12 * e + 2);
-            ro.f_tab = b->tables ? b->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
-            ro.a = i.a;
-            ro.N = N;
-            ro.discount = h->cfg.discount;
-            ro.cost = i.cost;
-            ro.groupmin = brec ? nullptr : i.groupmin;
-            ro.records = brec ? b->partials + (size_t)e * bG * COVO_PARTIAL_FLOATS : nullptr;
-            ro.lam = h->cfg.lam;
-            ro.diag_rec = (brec && covo_diag_target(h)) ? b->diag_rec + (size_t)e * bG * 4 : nullptr;
-            ro.clip = ROLLOUT_CLIP_TRUSTED;  // a comes straight from the noise GEMM
-            rollout_fill_args(b->ro_args_host.data(), e, ro);
-        }
-        COVO_CHECK_HIP(hipMemcpy(b->ro_args, b->ro_args_host.data(), b->ro_args_host.size(), hipMemcpyHostToDevice));
-        {
-            const size_t need_e = (size_t)E * ((N + 31) / 32) * 16 * 64;
-            if (need_e > b->eps_cap) {
-                free_and_null(b->eps_tiled);
-                b->eps_cap = 0;
-                COVO_CHECK_HIP(hipMalloc(&b->eps_tiled, need_e * sizeof(float4)));
-                b->eps_cap = need_e;
-            }
-        }
-        int rc;  // (a grown workspace forgets every graph and key of the handle: this block records the key after it)
+        if ((rc = grow_device(b->eps_tiled, b->eps_cap, (size_t)E * ((args->n_samples + 31) / 32) * 16 * 64))) return rc;
+        // (a grown workspace forgets every graph and key of the handle: the key is recorded after it)
         if ((rc = covo_grow_workspace(h, &h->ws_sigma, &h->ws_sigma_bytes, sigma_ns_workspace_bytes(E), s))) return rc;
         if ((rc = covo_grow_workspace(h, &h->ws_hess, &h->ws_hess_bytes, hessian_workspace_bytes(E), s))) return rc;
-        b->key = *args;
-        b->stream = s;
-        b->have_key = true;
+        c->record(m, s);
     }
-    batch_upload_keys(b->dyn, keys, E, s);
+    batch_upload_keys(c->dyn, keys, E, s);
     // covo_set_step_sigma_period: the batch shares one age -- 0: today's step, which leaves the factors in b->L; else a reuse step
     const int age = covo_sigma_step_age(h, b->L, args->sample_sigma, E);
     const bool reuse = age != 0;
     // both graphs are keyed by the step's key; each one's first call with these buffers runs eagerly, the second captures
-    const int rc = step_run_passes(
-        h, b->cache, reuse, graph_cache_seen(b->cache[reuse ? 1 : 0], same), s, "covo_mpc_step_batched",
+    rc = step_run_passes(
+        h, c->cache, reuse, graph_cache_seen(c->cache[reuse ? 1 : 0], same), s, "covo_mpc_step_batched",
         [&](hipStream_t on, int j) { return batch_enqueue(h, b, *args, on, DebugMasks(), j, reuse); },
         [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, on, true); });
     if (rc == 0) covo_sigma_step_done(h, age, b->L, args->sample_sigma, E);
@@ -1096,8 +1116,7 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
     }
     step_sync_epoch(h);
     BatchSmall *q = &batch_state(h)->small;
-    const bool same = q->cache.have_key && q->n_envs == E && std::memcmp(&q->key, m, sizeof(*m)) == 0 && q->stream == s &&
-                      std::memcmp(q->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
+    const bool same = batch_key_same(q->cache.have_key, q->key, q->stream, q->params, *m, params, s);
     if (!same) {
         COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old argument blocks are done
         q->cache.drop();
@@ -1125,7 +1144,6 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
                                  covo_step_iters(h) > 1 ? h->iter_log + (size_t)e * covo_step_iters(h) : nullptr);
         }
         COVO_CHECK_HIP(hipMemcpy(q->args, q->args_host.data(), q->args_host.size(), hipMemcpyHostToDevice));
-        std::memset(&q->key, 0, sizeof(q->key));
         q->key = *m;
         q->stream = s;
         q->cache.have_key = true;
@@ -1149,25 +1167,27 @@ int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, con
 // set), the posterior covariance, arbitrated passes -- runs as the launch sequence of a single staged step with the instance as a grid
 // dimension.  Instance e computes what enqueue_step computes for it alone: the same device functions on the same data in the same
 // order.  One pass:
-static int batch_staged_enqueue(covo_ctx *h, BatchStaged *q, const covo_batch_mode_args &m, hipStream_t s, const int pass)
+static int batch_staged_enqueue(covo_ctx *h, BatchState *b, const covo_batch_mode_args &m, hipStream_t s, const int pass)
 {
+    const BatchCommon &c = b->staged;
+    const BatchStagedExtras &x = b->sx;
     const covo_batch_args &a = m.base;
     const int E = a.n_envs, N = a.n_samples;
     const bool mppi = m.mode == COVO_MODE_MPPI;
     int rc;
-    hipLaunchKernelGGL(batch_mode_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, q->a_mean_shift, q->dyn, q->scales,
-                       mppi ? a.a_cov : (float *)nullptr, q->Ls, pass);
+    hipLaunchKernelGGL(batch_mode_begin_kernel, dim3(E), dim3(COVO_NA + 64), 0, s, a.a_mean, c.a_mean_shift, c.dyn, x.scales,
+                       mppi ? a.a_cov : (float *)nullptr, x.Ls, pass);
     // mppi.py:74: MPPI's sampling rollouts are non-deterministic, CoVO's deterministic (covo.py:231); no Hessian, no Hessian table
-    if (q->tables && (rc = launch_disturb_tables_batched(q->models, a.states, q->dyn, E, mppi ? 0 : 1, q->tab_rollout, nullptr, s))) return rc;
+    if (c.tables && (rc = launch_disturb_tables_batched(c.models, a.states, c.dyn, E, mppi ? 0 : 1, c.tab_rollout, nullptr, s))) return rc;
     NoiseDesc nd;
-    nd.mu = q->a_mean_shift;
-    nd.dyn = q->dyn;
+    nd.mu = c.a_mean_shift;
+    nd.dyn = c.dyn;
     nd.N = N;
     nd.a = a.a;
     nd.batch = E;
     nd.propagate_nan = covo_propagate_nan(h);
     if (mppi) {
-        nd.L = q->Ls;
+        nd.L = x.Ls;
         if ((rc = launch_noise_blockdiag(nd, s))) return rc;
     } else {
         nd.L = m.L_table;
@@ -1177,33 +1197,17 @@ static int batch_staged_enqueue(covo_ctx *h, BatchStaged *q, const covo_batch_mo
         nd.table_stride = m.L_table_stride;
         if ((rc = launch_noise_gemm(nd, s))) return rc;
     }
-    if ((rc = launch_rollout_batched(q->ro_args_host.data(), q->ro_args, E, s))) return rc;
-    const int G = rollout_workgroups(N, false, E);
+    if ((rc = launch_rollout_batched(c.ro_args_host.data(), c.ro_args, E, s))) return rc;
     const bool cov_adapt = mppi && m.gamma_sigma != 0.0f;
-    UpdateDesc up;
-    up.cost = a.cost;
-    up.a = a.a;
-    up.N = N;
-    up.blockmin = a.groupmin;
-    up.partials_ws = q->partials;
-    up.partials = q->partials;
-    up.G = G;
-    up.a_mean_old = q->a_mean_shift;
-    up.gamma_mean = a.gamma_mean;
-    up.a_mean_out = a.a_mean;
-    up.batch = E;
-    up.diag_rec = q->diag_rec;
-    up.diag_out = covo_diag_target(h);
-    up.iter_out = covo_iter_slot(h, pass);
-    up.iter_stride = covo_step_iters(h);
+    StepUpdate u = batch_update_desc(h, c, a, pass, cov_adapt);
     if (cov_adapt) {  // mppi.py:109-125 per instance: a_cov[e] (shifted by the begin launch) adapted in place
-        up.a_cov_old = a.a_cov;
-        up.gamma_sigma = m.gamma_sigma;
-        up.a_cov_out = a.a_cov;
-        up.partials_cov_ws = q->partials_cov;
-        up.diag_merge_ws = q->diag_merge;
+        u.up.a_cov_old = a.a_cov;
+        u.up.gamma_sigma = m.gamma_sigma;
+        u.up.a_cov_out = a.a_cov;
+        u.up.partials_cov_ws = x.partials_cov;
+        u.up.diag_merge_ws = x.diag_merge;
     }
-    return enqueue_update(h, up, G <= h->max_red_blocks && !cov_adapt && !covo_update_staged(h), s);  // (as the cold block told the rollout)
+    return enqueue_update(h, u, s);
 }
 
 int covo_step_batched_staged_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
@@ -1213,78 +1217,29 @@ int covo_step_batched_staged_impl(covo_ctx *h, const covo_batch_mode_args *m, co
     const int E = args->n_envs, N = args->n_samples;
     const bool mppi = m->mode == COVO_MODE_MPPI, cov_adapt = mppi && m->gamma_sigma != 0.0f;
     step_sync_epoch(h);
-    BatchStaged *q = &batch_state(h)->staged;
-    const bool same = q->have_key && q->n_envs == E && std::memcmp(&q->key, m, sizeof(*m)) == 0 && q->stream == s &&
-                      std::memcmp(q->params.data(), params, (size_t)E * sizeof(covo_env_params)) == 0;
+    BatchState *b = batch_state(h);
+    BatchCommon *c = &b->staged;
+    BatchStagedExtras *x = &b->sx;
+    const bool new_E = c->n_envs != E;
+    bool same;
+    int rc;
+    if ((rc = batch_cold(h, c, *m, params, s, BatchColdDiff{mppi ? 4 : 0, cov_adapt, !mppi, &x->scales}, &same))) return rc;
     if (!same) {
-        COVO_CHECK_HIP(hipStreamSynchronize(s));  // launches that read the old argument blocks are done
-        q->forget_graphs();
-        q->have_key = false;
-        if (q->n_envs != E) {
-            batch_staged_free(q);
-            COVO_CHECK_HIP(hipMalloc(&q->dyn, (size_t)E * 12 * sizeof(uint32_t)));
-            COVO_CHECK_HIP(hipMalloc(&q->a_mean_shift, (size_t)E * COVO_NA * sizeof(float)));
-            COVO_CHECK_HIP(hipMalloc(&q->Ls, (size_t)E * COVO_H * 16 * sizeof(float)));
-            COVO_CHECK_HIP(hipMalloc(&q->ro_args, rollout_args_bytes(E)));
-            COVO_CHECK_HIP(hipMalloc(&q->partials, (size_t)E * h->max_red_blocks * COVO_PARTIAL_FLOATS * sizeof(float)));
-            COVO_CHECK_HIP(hipMalloc(&q->diag_rec, (size_t)E * h->max_red_blocks * 4 * sizeof(float)));
-            COVO_CHECK_HIP(hipMalloc(&q->diag_merge, (size_t)E * COVO_PARTIAL_FLOATS * sizeof(float)));
-            COVO_CHECK_HIP(hipMalloc(&q->models, disturb_models_bytes(E)));
-            COVO_CHECK_HIP(hipMalloc(&q->tab_rollout, (size_t)E * COVO_H * 4 * sizeof(float)));
-            q->n_envs = E;
+        if (new_E || x->diag_merge == nullptr) {  // (null: an earlier attempt failed half way)
+            free_and_null(x->Ls, x->diag_merge);
+            COVO_CHECK_HIP(hipMalloc(&x->Ls, (size_t)E * COVO_H * 16 * sizeof(float)));
+            COVO_CHECK_HIP(hipMalloc(&x->diag_merge, (size_t)E * COVO_PARTIAL_FLOATS * sizeof(float)));
         }
-        if (cov_adapt) {  // the records with second moments: grown like the covo-online batch's epsilon image
-            const size_t need = (size_t)E * softmax_cov_workspace_floats(softmax_stage1_blocks(h, N));
-            if (need > q->partials_cov_cap) {
-                free_and_null(q->partials_cov);
-                q->partials_cov_cap = 0;
-                COVO_CHECK_HIP(hipMalloc(&q->partials_cov, need * sizeof(float)));
-                q->partials_cov_cap = need;
-            }
-        }
-        q->params.assign(params, params + E);
-        std::vector<char> tmp(disturb_models_bytes(E), 0);
-        disturb_fill_models(params, E, tmp.data());
-        COVO_CHECK_HIP(hipMemcpy(q->models, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-        q->tables = covo_needs_tables(params[0]);
-        q->ro_args_host.assign(rollout_args_bytes(E), 0);
-        const int bG = rollout_workgroups(N, false, E);
-        const bool brec = bG <= h->max_red_blocks && !cov_adapt && !covo_update_staged(h);
-        std::memset(&q->scales, 0, sizeof(q->scales));
-        for (int e = 0; e < E; ++e) {
-            const BatchInst i = batch_inst(*args, e);
-            q->scales.v[e] = covo_shared_noise_scale(params[e], !mppi);
-            RolloutDesc ro;
-            ro.state = i.state;
-            ro.pos_traj = i.pos_traj;
-            ro.vel_traj = i.vel_traj;
-            ro.T = args->T;
-            ro.params = &params[e];
-            ro.f_shared_dev = reinterpret_cast<const float *>(q->dyn + 12 * e + 2);  // (MPPI: the instance's own shared vector)
-            ro.f_tab = q->tables ? q->tab_rollout + (size_t)e * COVO_H * 4 : nullptr;
-            ro.a = i.a;
-            ro.N = N;
-            ro.discount = h->cfg.discount;
-            ro.cost = i.cost;
-            ro.groupmin = brec ? nullptr : i.groupmin;
-            ro.records = brec ? q->partials + (size_t)e * bG * COVO_PARTIAL_FLOATS : nullptr;
-            ro.lam = h->cfg.lam;
-            ro.diag_rec = (brec && covo_diag_target(h)) ? q->diag_rec + (size_t)e * bG * 4 : nullptr;
-            ro.xcd_groups = mppi ? 4 : 0;  // (as the single step tells its rollout)
-            ro.clip = ROLLOUT_CLIP_TRUSTED;
-            rollout_fill_args(q->ro_args_host.data(), e, ro);
-        }
-        COVO_CHECK_HIP(hipMemcpy(q->ro_args, q->ro_args_host.data(), q->ro_args_host.size(), hipMemcpyHostToDevice));
-        std::memset(&q->key, 0, sizeof(q->key));
-        q->key = *m;
-        q->stream = s;
-        q->have_key = true;
+        // the records with second moments
+        if (cov_adapt && (rc = grow_device(x->partials_cov, x->partials_cov_cap,
+                                           (size_t)E * softmax_cov_workspace_floats(softmax_stage1_blocks(h, N))))) return rc;
+        c->record(*m, s);
     }
-    batch_upload_keys(q->dyn, keys, E, s);
+    batch_upload_keys(c->dyn, keys, E, s);
     // covo_set_step_iters: the K passes in the one graph, the arbiter's launch between two of them eager (step_run_passes)
     return step_run_passes(
-        h, q->cache, false, graph_cache_seen(q->cache[0], same), s, "covo_mpc_step_batched_mode",
-        [&](hipStream_t on, int j) { return batch_staged_enqueue(h, q, *m, on, j); },
+        h, c->cache, false, graph_cache_seen(c->cache[0], same), s, "covo_mpc_step_batched_mode",
+        [&](hipStream_t on, int j) { return batch_staged_enqueue(h, b, *m, on, j); },
         [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, m->mode, params, nullptr, -1, on, true); });
 }
 
@@ -1354,12 +1309,13 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
-    // the staged MPPI / covo-offline step (covo_set_step_batched_staged) leaves what covo-online's leaves, in its own scratch
-    const BatchStaged *q = (!online && covo_batched_staged(h)) ? &b->staged : nullptr;
-    const bool begun = online || q != nullptr;  // a begin launch has left the shifted means and parked the raw keys
-    const float *shifted = online ? b->a_mean_shift : (q ? q->a_mean_shift : nullptr);
-    const float *tabs = online ? (b->tables ? b->tab_rollout : nullptr) : ((q && q->tables) ? q->tab_rollout : nullptr);
-    const uint32_t *dyn = online ? b->dyn : (q ? q->dyn : b->small.dyn);
+    // the batch whose begin launch has left the shifted means and parked the raw keys: covo-online's, the staged MPPI / covo-offline
+    // step's (covo_set_step_batched_staged), or none behind the fused launch
+    const BatchCommon *c = online ? &b->online : (covo_batched_staged(h) ? &b->staged : nullptr);
+    const bool begun = c != nullptr;
+    const float *shifted = c ? c->a_mean_shift : nullptr;
+    const float *tabs = (c && c->tables) ? c->tab_rollout : nullptr;
+    const uint32_t *dyn = c ? c->dyn : b->small.dyn;
     PlanInstDesc d[COVO_MAX_ENVS];
     const float *nominal = nullptr;  // the update arbiter's: a begin launch leaves it, the fused launch's was formed ahead of it
     if (covo_arb_on(h)) {
@@ -1385,7 +1341,7 @@ int covo_debug_sigma_factor_impl(covo_ctx *h, int batched, float *out, int64_t c
     StepState *st = reinterpret_cast<StepState *>(h->step);
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const float *src = batched ? (b ? b->L : nullptr) : (st ? st->L : nullptr);
-    const int64_t have = (int64_t)COVO_NA * COVO_NA * (batched ? (b ? b->n_envs : 0) : 1);
+    const int64_t have = (int64_t)COVO_NA * COVO_NA * (batched ? (b ? b->online.n_envs : 0) : 1);
     if (src == nullptr || count > have) {
         covo_set_error("covo_debug_sigma_factor: no %s step has run on this handle, or count=%lld exceeds its %lld floats",
                        batched ? "batched" : "single", (long long)count, (long long)have);

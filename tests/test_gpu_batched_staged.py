@@ -17,8 +17,11 @@ tests/test_gpu_batched_modes.py.
      For gamma_sigma = 0.2 the new mean and a_cov against ref_np.softmax_update + ref_np.mppi_cov_update in fp64, at the bars of the
      single controller's covariance-adaptation test, tests/test_gpu_models.py::test_mppi_covariance_adaptation_vs_oracle: 1e-5 on
      the mean and 1e-5 on a_cov;
-  7. eval_env_batched(controller="mppi" | "covo-offline", staged=True): the driver reaches the baselines.
+  7. eval_env_batched(controller="mppi" | "covo-offline", staged=True): the driver reaches the baselines;
+  8. one handle stepped alternately through covo_mpc_step_batched and the staged covo_mpc_step_batched_mode == two handles.
 """
+import ctypes as C
+
 import numpy as np
 import pytest
 
@@ -32,6 +35,7 @@ import covo_mpc_amd as cm  # noqa: E402
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers.batched import CORE_BUFFERS  # noqa: E402
+from covo_mpc_amd.dynamics.dataclass import as_device_state  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from tests import test_gpu_batched_modes as M  # noqa: E402
@@ -396,3 +400,85 @@ def test_eval_env_batched_runs_the_baselines_staged(controller, opts):
         assert rows["iters"].shape == (2, 4, 2) and np.all(np.isfinite(rows["iters"]))
     with pytest.raises(ValueError, match='staged=True with mode="online"'):
         cm.envs.quadrotor.eval_env_batched(env, 2, "N256_H32_lam0.01", n_steps=1, device=DEV, verbose=False, staged=True)
+
+
+# ---- 8. one handle, both batched entry points -------------------------------------------------------------------------------------
+@pytest.mark.parametrize("sigma_period", [1, 2])
+def test_one_handle_through_both_batched_entry_points(sigma_period, monkeypatch):
+    """The covo-online batch and the staged MPPI batch keep separate scratch, keys and graphs on one handle.  A: the covo-online batch,
+    E = 3, N = 256; B: the staged MPPI batch, E = 2, N = 100 (another instance count: a scratch the two shared would be re-allocated by
+    every call).  Reference: four steps of each on its own handle (eager, capture, two replays), open loop on the instances' states,
+    a_mean / the action buffer / the costs / a_cov and A's sigma_age recorded after every step.  Then both are rebuilt from the same
+    initial state and both argument blocks are driven through A's handle alternately, with the same keys: every recorded tensor is
+    torch.equal to the two-handle run, step by step.
+
+    sigma_period = 1: both entries run.  After every MPPI step the factors covo-online left in its scratch (covo_debug_sigma_factor)
+    are still those of the two-handle run: the other entry has neither freed nor rewritten them.
+    sigma_period = 2 on A: check_step_attachments refuses an MPPI / covo-offline step on a handle that carries a Sigma period ("belongs
+    to covo-online steps") before anything is launched, so B's half of the alternation cannot run there; every B call must be refused
+    with that message, and A's steps between the refused calls go on through refresh and reuse -- sigma_age 0, 1, 0, 1 -- equal to A
+    alone."""
+    monkeypatch.setenv("COVO_GRAPH", "1")
+    env = _env()
+    inst_a = M._instances(env, "covo-online", 256, "0.01", 3, seed=20)
+    inst_b = _instances(env, "mppi", 100, "0.01", 2, seed=30)  # (lam and the discount are the handle's: one value for both)
+    _close(inst_a + inst_b)  # (only the instances' states, parameters and keys are used)
+    keys = {}
+    for tag, inst in (("A", inst_a), ("B", inst_b)):
+        keys[tag] = []
+        for step in range(4):
+            row = []
+            for i in inst:
+                i["key"], k_act, _ = cr.split(i["key"], 3)
+                row.append(np.asarray(k_act))
+            keys[tag].append(np.ascontiguousarray(np.stack(row), dtype=np.uint32))
+    noisy = {"A": [i["info"]["noisy_state"] for i in inst_a], "B": [i["info"]["noisy_state"] for i in inst_b]}
+
+    def build():
+        cp0 = inst_a[0]["cp"]
+        A = cm.controllers.BatchedCoVOController(env, 3, 256, 32, 0.01, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
+                                                 sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV,
+                                                 sigma_period=sigma_period)
+        A.set_instances([i["state"] for i in inst_a], [i["params"] for i in inst_a])
+        B = _batched(env, "mppi", inst_b, 100, "0.01")
+        assert A.core.uses_graph and B.core.uses_graph and B.staged
+        return A, B
+
+    def record(c):
+        return dict(a_mean=c.a_mean.clone(), a=c._a.clone(), cost=c._cost.clone(), a_cov=c.a_cov.clone())
+
+    A, B = build()
+    ref = {"A": [], "B": [], "age": [], "L": []}
+    for step in range(4):
+        A(noisy["A"], keys["A"][step])
+        ref["A"].append(record(A))
+        ref["age"].append(A.sigma_age)
+        ref["L"].append(A.core.sigma_factor(3))
+        if sigma_period == 1:
+            B(noisy["B"], keys["B"][step])
+            ref["B"].append(record(B))
+    assert ref["age"] == [step % sigma_period for step in range(4)]
+    assert A.core.device_status() == 0 and B.core.device_status() == 0
+    _close([], A, B)
+
+    A, B = build()
+    lib, h = A.core.lib, A.core.h
+    _lib.check(lib.covo_set_step_batched_staged(h, 1), "covo_set_step_batched_staged")
+    for step in range(4):
+        for tag, c in (("A", A), ("B", B)):
+            torch.stack([as_device_state(s, DEV).packed for s in noisy[tag]], out=c._states_buf)
+            k = keys[tag][step].ctypes.data_as(C.POINTER(C.c_uint32))
+            if tag == "A":
+                _lib.check(lib.covo_mpc_step_batched(h, C.byref(A._args.base), A._params, k, A.core.stream()), "covo_mpc_step_batched")
+                assert A.sigma_age == ref["age"][step], step
+            elif sigma_period == 1:
+                _lib.check(lib.covo_mpc_step_batched_mode(h, C.byref(B._args), B._params, k, A.core.stream()), "covo_mpc_step_batched_mode")
+                assert torch.equal(A.core.sigma_factor(3), ref["L"][step]), step
+            else:
+                with pytest.raises(_lib.CovoError, match="the Sigma period .* belongs to covo-online steps"):
+                    _lib.check(lib.covo_mpc_step_batched_mode(h, C.byref(B._args), B._params, k, A.core.stream()), "covo_mpc_step_batched_mode")
+                continue
+            for name, t in record(c).items():
+                assert torch.equal(t, ref[tag][step][name]), (tag, step, name)
+    assert A.core.device_status() == 0
+    _close([], A, B)
