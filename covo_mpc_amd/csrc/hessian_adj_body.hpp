@@ -516,6 +516,12 @@ __global__ __launch_bounds__(256) void adj_chain_kernel(const AdjArgs A)
     const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, lo = lane & 15, hi = lane >> 4;
     const int w = blockIdx.x;  // 0..7: column tile of S, 8: costate, 9..40: the hyper-dual steps of KM (see adj_hd_pairs)
     double *__restrict__ ws = A.ws + (size_t)b * WS_COUNT;
+    // -DKC_STAMPS (like KD_PROF: a measuring build, the product kernel stores nothing extra): 10 ns wall-clock ticks from the
+    // chain workgroup's entry to its own LDS stores done / past the barrier (wave 0's first MFMA may issue) / the chain's end,
+    // printed by the first and the last sensitivity tile and by the costate
+#ifdef KC_STAMPS
+    const long long kc0 = wall_clock64();
+#endif
     if (w >= 9) {
         adj_hd_padding(A, w - 9, b, tid, 256);
         adj_hd_pairs(A, w - 9, b, tid);
@@ -535,7 +541,21 @@ __global__ __launch_bounds__(256) void adj_chain_kernel(const AdjArgs A)
         sgl[256 + tid] = vg1;
         if (tid == 0) sjf[NJ] = 0.0;
     }
+#ifdef KC_STAMPS
+    const long long kc1 = wall_clock64();
+#endif
     __syncthreads();
+#ifdef KC_STAMPS
+    const long long kc2 = wall_clock64();
+#define KC_STAMP_END()                                                                                                       \
+    do {                                                                                                                     \
+        if (tid == 0 && b == 0 && (w == 0 || w == 7 || w == 8))                                                              \
+            printf("KC wg %d: filled %lld first-mfma %lld end %lld (10 ns ticks from entry)\n", w, kc1 - kc0, kc2 - kc0,      \
+                   (long long)wall_clock64() - kc0);                                                                         \
+    } while (0)
+#else
+#define KC_STAMP_END() do { } while (0)
+#endif
     if (tid >= 64) return;
     // The chains are fully unrolled (k is a compile-time constant: every LDS / global address is base + immediate) and the lanes
     // outside the 13 x 13 block read a zero slot instead of being masked off: as a rolled loop with `cond ? sjf[..] : 0` operands
@@ -593,6 +613,7 @@ __global__ __launch_bounds__(256) void adj_chain_kernel(const AdjArgs A)
                 for (int r = 0; r < 4; ++r) __hip_atomic_store(&L[16 * k + hi + 4 * r], lam[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
+        KC_STAMP_END();
         return;
     }
     // ---- sensitivities: tile w = columns 16w .. 16w+15 = the actions of steps 4w .. 4w+3; S_k tile = 0 for k <= 4w
@@ -643,7 +664,9 @@ __global__ __launch_bounds__(256) void adj_chain_kernel(const AdjArgs A)
 #pragma unroll
         for (int r = 0; r < 4; ++r) Sp[((size_t)(k + 1) * 16 + 4 * r) * NA] = sv[r];
     }
+    KC_STAMP_END();
 }
+#undef KC_STAMP_END
 
 // ---- KD: R = -( sum_k S_k^T Mxx_k S_k  +  action blocks ), one lower 16x16 tile per workgroup, k split over 8 waves
 __device__ __forceinline__ void adj_tri_tile(int w, int &ti, int &tj)

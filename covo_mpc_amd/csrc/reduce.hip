@@ -85,7 +85,26 @@ __global__ __launch_bounds__(MG_THREADS) void merge_kernel(const float *__restri
                                                            float *__restrict__ out, int stride, float *__restrict__ iter_out,
                                                            int iter_stride)
 {
+    // -DMERGE_STAMPS (a measuring build; the product kernel stores nothing extra): 10 ns wall-clock ticks from entry to "records
+    // in hand" -- this thread's share of the records (the v rows and headers merge_body asks for first) pulled once ahead of the
+    // merge, which then finds them in the caches: the first-touch round trip on its own -- and to "done"
+#ifdef MERGE_STAMPS
+    const long long mt0 = wall_clock64();
+    float touch = 0.0f;
+    {
+        const float *p = partials + (size_t)blockIdx.x * G * stride;
+        const int col = threadIdx.x & (COVO_NA - 1), slice = threadIdx.x >> 7;
+        for (int g = slice; g < G; g += MG_SLICES) touch += p[(size_t)g * stride + 2 + col];
+        if ((int)threadIdx.x < G) touch += p[(size_t)threadIdx.x * stride] + p[(size_t)threadIdx.x * stride + 1];
+    }
+    asm volatile("s_waitcnt vmcnt(0)" : "+v"(touch)::"memory");
+    const long long mt1 = wall_clock64();
+#endif
     merge_instance<FINAL, false>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, nullptr, nullptr, 0.0f, iter_out, iter_stride);
+#ifdef MERGE_STAMPS
+    if (threadIdx.x == 0 && blockIdx.x == 0)
+        printf("merge G %d: records-in-hand %lld done %lld (10 ns ticks from entry)\n", G, mt1 - mt0, (long long)wall_clock64() - mt0);
+#endif
 }
 
 // the same, and the diagnostic records dpart [instances][G][MG_DIAG_REC] merged into row x of diag_out [instances][COVO_DIAG_FLOATS]

@@ -1786,6 +1786,57 @@ __device__ void ns_logdetB_workgroup(const double *__restrict__ A, double *__res
     }
 }
 
+// ---- what every finalize path does with log det B: ONE copy of the wait and ONE of the expression (ns_finalize_kernel, the streamed
+// launch's factoring workgroup and its a_cov workers must agree in every bit of cz).
+// One thread's wait for SC_LDFLAG: SC_SUMLOGB is there, to be read with gld<COH_AGENT> BEHIND this call.  `flag` is the caller's
+// FIRST look at the flag, asked for with the launch's first loads so that it costs no round trip of its own.  true: 0.2 s without
+// the flag -- the workgroup that owes it never ran (a starved launch); the caller fails in NaNs, loudly.
+// ns_logdet_fence: what the caller puts between this wait and its load of the sum -- the two are relaxed accesses to different
+// addresses, which the compiler may otherwise reorder (the hardware returns a wave's loads in the order it issued them).
+__device__ __forceinline__ void ns_logdet_fence() { asm volatile("" ::: "memory"); }
+__device__ __forceinline__ bool ns_logdet_timed_out(const double *s, double flag)
+{
+    const long long t0 = wall_clock64();
+    bool timed_out = false;
+    while (flag == 0.0) {
+        __builtin_amdgcn_s_sleep(1);
+        if (wall_clock64() - t0 > 20000000LL) {
+            timed_out = true;
+            break;
+        }
+        flag = gld<COH_AGENT>(s + SC_LDFLAG);
+    }
+    ns_logdet_fence();
+    return timed_out;
+}
+// covo.py:124-128: log_s = 0.5 log_const - 0.5 log_o, log_const = (2 n 2 log(sigma) + sum log o)/n, i.e. Sigma = c B^(-1/2) with
+// log c = 2 log(sigma) + log det B / (2n); Z = sqrt(scale) B^(-1/2), so Sigma = cz Z with cz = c / sqrt(scale)
+// = sigma^2 exp(sumlogB / n) / sqrt(scale), sumlogB = sum_i log diag(chol B) = log det B / 2 (ns_logdetB_workgroup).
+// bad: a timed-out grid barrier (ns_grid_barrier) left Z unconverged, or log det B never came: fail like the reference's numerical
+// failures do, in NaNs.
+__device__ __forceinline__ double ns_cz(bool bad, float sample_sigma, double sumlogB, double scale)
+{
+    const double poison = bad ? __builtin_nan("") : 1.0;
+    return poison * ((double)sample_sigma * (double)sample_sigma) * exp(sumlogB / (double)SN) * qm::rsq64_(scale);
+}
+// The 36 lower tiles in the order the streamed launch's factoring workgroup asks for them: tile 4 round + g for the 128-thread group
+// g of round `round` (0 .. 8), column panel 0 first (rounds 0, 1: tiles (0..7, 0), what the factorisation's first panel reads), then
+// the rest row by row.  `round` is a compile-time number where this is called (an unrolled loop), g is known per wave only: no
+// branch and no loop on it (tri_tile's scalar loop sat between one tile's loads and the next's).
+__device__ __forceinline__ void tri_tile_panel0_first(int round, int g, int &ti, int &tj)
+{
+    if (round < 2) {
+        ti = 4 * round + g;
+        tj = 0;
+    } else {
+        // the 28 tiles with 1 <= tj <= ti <= 7: a 7 x 7 triangle, one down and one right
+        const int k = 4 * (round - 2) + g;
+        const int t7 = (k >= 1) + (k >= 3) + (k >= 6) + (k >= 10) + (k >= 15) + (k >= 21);
+        ti = t7 + 1;
+        tj = k - t7 * (t7 + 1) / 2 + 1;
+    }
+}
+
 // ---- one workgroup per matrix: Z ~ sqrt(s) B^(-1/2), symmetrised.  ONE Cholesky serves both needs:
 //   Lz = chol(Z)  ->  log det B = n log s - 2 log det Z = n log s - 4 sum log diag(Lz);
 //   Sigma = cz Z (cz = c / sqrt(s))  ->  chol(Sigma) = sqrt(cz) Lz.
@@ -1828,12 +1879,14 @@ __global__ __launch_bounds__(512) void ns_finalize_kernel(const double *__restri
     const double uv_mine = (tid < SN) ? s[SC_U + tid] : 0.0;
     const bool z1 = s[SC_ZBUF] != 0.0;
     const double zc = s[SC_ZCOEF];         // deflation: Z = Z~ + zc u u^T (0: off)
+    // (so do the two scalars cz is made of -- written launches ago; asked for behind the factorisation, after the wait for
+    // log det B, they were one more dependent round trip at the launch's end)
+    const double barfail = s[SC_BARFAIL], scale = s[SC_SCALE];
     if (tid < SN) suv[tid] = uv_mine;
     const double *uv = suv;
     const double2 *Z = reinterpret_cast<const double2 *>((z1 ? Z1all : Z0all) + (size_t)b * SN * SN);
     const double2 *Zt = reinterpret_cast<const double2 *>((z1 ? Zt1all : Zt0all) + (size_t)b * SN * SN);
     constexpr int LD = SN + 1;
-    const double n = (double)SN;
     long long tk[5];
     tk[0] = clock64();
     // Only the 36 lower 16x16 tiles are fetched (Z and its stored transpose, both coalesced: 8 lanes x 16 B per tile row) and
@@ -1876,31 +1929,18 @@ __global__ __launch_bounds__(512) void ns_finalize_kernel(const double *__restri
     tk[1] = clock64();
     chol128_lds_mfma<LD>(sm, tid);
     tk[2] = clock64();
-    // covo.py:124-128: log_s = 0.5 log_const - 0.5 log_o, log_const = (2 n 2 log(sigma) + sum log o)/n, i.e. Sigma = c B^(-1/2) with
-    // log c = 2 log(sigma) + log det B / (2n); Z = sqrt(scale) B^(-1/2), so Sigma = cz Z with cz = c / sqrt(scale)
-    // = sigma^2 exp(sumlogB / n) / sqrt(scale), sumlogB = sum_i log diag(chol B) = log det B / 2 (ns_logdetB_workgroup: a sibling
-    // workgroup of this launch, or -- one matrix -- a passenger of the Newton-Schulz launch, long done)
+    // cz (ns_cz) from log det B: the work of a sibling workgroup of this launch, or -- one matrix -- of a passenger of the
+    // Newton-Schulz launch, long done
     if (tid == 0) {
-        const long long t0 = wall_clock64();
-        int good = 1;
-        while (gld<COH_AGENT>(s + SC_LDFLAG) == 0.0) {
-            __builtin_amdgcn_s_sleep(1);
-            if (wall_clock64() - t0 > 20000000LL) {  // 0.2 s: the sibling never ran (a starved launch): fail in NaNs, loudly
-                good = 0;
-                break;
-            }
-        }
+        const bool timed_out = ns_logdet_timed_out(s, gld<COH_AGENT>(s + SC_LDFLAG));
         red[0] = gld<COH_AGENT>(s + SC_SUMLOGB);
-        red[1] = good ? 0.0 : 1.0;
+        red[1] = timed_out ? 1.0 : 0.0;
     }
     __syncthreads();
-    const double sumlogB = red[0];
-    const bool ld_failed = red[1] != 0.0;
-    // a timed-out grid barrier (ns_grid_barrier) left Z unconverged: fail like the reference's numerical failures do, in NaNs
-    const double poison = (s[SC_BARFAIL] != 0.0 || ld_failed) ? __builtin_nan("") : 1.0;
-    if (tid == 0 && (s[SC_BARFAIL] != 0.0 || ld_failed) && status != nullptr)  // ... and loudly: the next C call on this handle fails (capi.hip)
+    const bool bad = barfail != 0.0 || red[1] != 0.0;
+    if (tid == 0 && bad && status != nullptr)  // ... and loudly: the next C call on this handle fails (capi.hip)
         __hip_atomic_fetch_or(status, COVO_DEVSTAT_GRID_BARRIER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-    const double cz = poison * ((double)sample_sigma * (double)sample_sigma) * exp(sumlogB / n) * qm::rsq64_(s[SC_SCALE]);
+    const double cz = ns_cz(bad, sample_sigma, red[0], scale);
     const double sq = cz * qm::rsq64_(cz);
     if (tid == 0) s[SC_CZ] = cz;
     tk[3] = clock64();
@@ -1960,7 +2000,12 @@ __global__ __launch_bounds__(512) void ns_finalize_kernel(const double *__restri
 // 8 MFMAs per tile instead of a whole 18 us GEMM launch.
 struct StreamHook {
     const double *sm;
-    double sq;
+    double *s;       // the matrix's scalar slots
+    double *czq;     // LDS [2]: cz and sqrt(cz), there from the barrier that ends panel 0's F phase on
+    double sumlogB, barfail, scale;  // thread CZ_TID's: what cz is made of, asked for at the launch's entry
+    bool ld_timed_out;
+    float sample_sigma;
+    int *status;
     float *Lg;
     unsigned *sync;
     unsigned seq;
@@ -1968,6 +2013,20 @@ struct StreamHook {
     double *stamps;
     int tid;
     static constexpr int LD = SN + 1;
+    // cz is formed by ONE thread of a wave that only waits while wave 0 factors the first diagonal block (the panel writers need
+    // sqrt(cz) two barriers later): no wave computes it, and nobody waits for log det B, ahead of the factorisation's first
+    // instruction
+    static constexpr int CZ_TID = 64;
+    __device__ __forceinline__ void form_cz() const
+    {
+        const bool bad = barfail != 0.0 || ld_timed_out;
+        if (bad && status != nullptr)
+            __hip_atomic_fetch_or(status, COVO_DEVSTAT_GRID_BARRIER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+        const double cz = ns_cz(bad, sample_sigma, sumlogB, scale);
+        czq[0] = cz;
+        czq[1] = cz * qm::rsq64_(cz);
+        s[SC_CZ] = cz;
+    }
     __device__ __forceinline__ void panel_done(int p) const
     {
         const int wave = tid >> 6, lane = tid & 63;
@@ -1975,6 +2034,7 @@ struct StreamHook {
         if (tid == 0) stamps[2 + p] = (double)wall_clock64();
 #endif
         if (wave == 0) return;  // (wave 0 goes straight on to the next diagonal block)
+        const double sq = czq[1];
         const int rr = lane >> 4, kk = lane & 15, j0 = 16 * p, c = j0 + kk;
         for (int i0 = j0 + 4 * (wave - 1); i0 < SN; i0 += 28) {
             const int i = i0 + rr;
@@ -1986,6 +2046,7 @@ struct StreamHook {
     __device__ __forceinline__ void before_barrier(int p) const
     {
         const int wave = tid >> 6, lane = tid & 63;
+        if (p == 0 && tid == CZ_TID) form_cz();
         if (p == 0 || wave == 0) return;
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         if (lane == 0) {
@@ -2047,30 +2108,6 @@ __global__ __launch_bounds__(512) void ns_finalize_stream_kernel(const double *_
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     constexpr int LD = SN + 1;
-    const double n = (double)SN;
-    // ---- cz, every workgroup for itself from the same numbers (ns_finalize_kernel's expression: the same bits)
-    if (tid == 0) {
-        const long long t0 = wall_clock64();
-        int good = 1;
-        while (gld<COH_AGENT>(s + SC_LDFLAG) == 0.0) {
-            __builtin_amdgcn_s_sleep(1);
-            if (wall_clock64() - t0 > 20000000LL) {
-                good = 0;
-                break;
-            }
-        }
-        red[0] = gld<COH_AGENT>(s + SC_SUMLOGB);
-        red[1] = good ? 0.0 : 1.0;
-    }
-    __syncthreads();
-    const double sumlogB = red[0];
-    const bool bad = s[SC_BARFAIL] != 0.0 || red[1] != 0.0;
-    const double poison = bad ? __builtin_nan("") : 1.0;
-    const double cz = poison * ((double)sample_sigma * (double)sample_sigma) * exp(sumlogB / n) * qm::rsq64_(s[SC_SCALE]);
-    const double sq = cz * qm::rsq64_(cz);
-    const unsigned seq = __hip_atomic_load(S.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool z1 = s[SC_ZBUF] != 0.0;
-    const double zc = s[SC_ZCOEF];  // deflation: Z = Z~ + zc u u^T (0: off)
     // time stamps of the launch (100 MHz wall clock, scripts/stream_timeline.py): workgroup 0 [0] entry, [1] Z in LDS, [2 + p] panel p
     // final, [10] factorisation over, [11 + p] flag p raised; the first and the last worker's wave 0 [24 / 56 + ...]: entry, then per
     // panel {flag seen, staged, multiplied (and stored)}
@@ -2084,36 +2121,52 @@ __global__ __launch_bounds__(512) void ns_finalize_stream_kernel(const double *_
 
     if (blockIdx.x == 0) {
         // ================================================================ the factoring workgroup
+        // Everything this launch reads from the slots was written by EARLIER launches and is valid at entry, and of all of it only
+        // SC_ZBUF stands between the entry and the Z loads.  So: every scalar is asked for in ONE round trip, SC_ZBUF first; the 36
+        // tiles go out the moment it is back; the wait for log det B, the deflation vector and cz happen under them, and the
+        // barrier at the head of chol128_lds_mfma is the prologue's only one.  (Round 5 walked four dependent round trips here --
+        // flag, sum, barrier, scalars + exp, tiles -- and three barriers.)
         STREAM_STAMP(0);
-        if (tid == 0 && bad && status != nullptr)
-            __hip_atomic_fetch_or(status, COVO_DEVSTAT_GRID_BARRIER, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-        if (tid == 0) s[SC_CZ] = cz;
+        const bool z1 = s[SC_ZBUF] != 0.0;
+        const double zc = s[SC_ZCOEF];  // deflation: Z = Z~ + zc u u^T (0: off)
+        const double ldflag = gld<COH_AGENT>(s + SC_LDFLAG);
+        const double barfail = s[SC_BARFAIL], scale = s[SC_SCALE];
+        const double uv_mine = (tid < SN) ? s[SC_U + tid] : 0.0;
+        const unsigned seq = __hip_atomic_load(S.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         __shared__ double suv[SN];
         __shared__ int wcnt[8];
-        if (tid < SN) suv[tid] = s[SC_U + tid];
-        if (tid < 8) wcnt[tid] = 0;
         const double2 *Z = reinterpret_cast<const double2 *>(z1 ? Z1 : Z0);
         const double2 *Zt = reinterpret_cast<const double2 *>(z1 ? Zt1 : Zt0);
         long long tk[3];
         tk[0] = clock64();
+        StreamHook hook;
+        hook.ld_timed_out = false;
         {
             constexpr int TR = NS_TILES * 128 / 512;  // 9 double2 per thread and matrix: all loads in flight first
             double2 za[TR], zt[TR];
 #pragma unroll
             for (int t = 0; t < TR; ++t) {
-                const int w = __builtin_amdgcn_readfirstlane((tid >> 7) + 4 * t), in = tid & 127;
+                const int g = __builtin_amdgcn_readfirstlane(tid >> 7), in = tid & 127;
                 int ti, tj;
-                tri_tile(w, ti, tj);
+                tri_tile_panel0_first(t, g, ti, tj);
                 const int e2 = ((16 * ti + (in >> 3)) * SN + 16 * tj + 2 * (in & 7)) >> 1;
                 za[t] = Z[e2];
                 zt[t] = Zt[e2];
             }
-            __syncthreads();  // suv
+            if (tid < SN) suv[tid] = uv_mine;
+            if (tid < 8) wcnt[tid] = 0;
+            // log det B: the flag came with the first round trip; the sum comes in behind the tiles and is wanted in form_cz (every
+            // thread asks, thread CZ_TID's answer counts: a load inside its branch is waited for at the branch's end, before the
+            // wave has stored one tile)
+            if (tid == StreamHook::CZ_TID) hook.ld_timed_out = ns_logdet_timed_out(s, ldflag);
+            ns_logdet_fence();  // (the load below stays behind the branch above)
+            hook.sumlogB = gld<COH_AGENT>(s + SC_SUMLOGB);
+            if (zc != 0.0) __syncthreads();  // suv (nobody waits for a tile here; without deflation nobody reads suv)
 #pragma unroll
             for (int t = 0; t < TR; ++t) {
-                const int w = __builtin_amdgcn_readfirstlane((tid >> 7) + 4 * t), in = tid & 127;
+                const int g = __builtin_amdgcn_readfirstlane(tid >> 7), in = tid & 127;
                 int ti, tj;
-                tri_tile(w, ti, tj);
+                tri_tile_panel0_first(t, g, ti, tj);
                 const int r = 16 * ti + (in >> 3), c = 16 * tj + 2 * (in & 7);
                 double v0 = 0.5 * (za[t].x + zt[t].x), v1 = 0.5 * (za[t].y + zt[t].y);  // covo.py:132 symmetrise
                 if (zc != 0.0) {
@@ -2129,12 +2182,18 @@ __global__ __launch_bounds__(512) void ns_finalize_stream_kernel(const double *_
                 }
             }
         }
-        __syncthreads();
         tk[1] = clock64();
+#ifdef NS_STREAM_STAMPS
+        __syncthreads();  // stamp [1] means what it always did: EVERY tile in LDS (the product build's barrier is the factorisation's)
+#endif
         STREAM_STAMP(1);
-        StreamHook hook;
         hook.sm = sm;
-        hook.sq = sq;
+        hook.s = s;
+        hook.czq = red;
+        hook.barfail = barfail;
+        hook.scale = scale;
+        hook.sample_sigma = sample_sigma;
+        hook.status = status;
         hook.Lg = S.L_stream;
         hook.sync = S.sync;
         hook.seq = seq;
@@ -2167,6 +2226,19 @@ __global__ __launch_bounds__(512) void ns_finalize_stream_kernel(const double *_
     float *mus = Ls + COVO_NA * NG_LDA;          // [128]
     float4 *epsx = reinterpret_cast<float4 *>(mus + COVO_NA);  // [16][64]: the hosted tile's epsilon in B-operand order (16 KiB)
     const int b = (int)blockIdx.x, W = (int)gridDim.x - 1;
+    const unsigned seq = __hip_atomic_load(S.sync, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    // the first 32 workers write a_cov = cz sym(Z): what that takes from the slots is asked for here, with the launch's first loads,
+    // and waited for behind the epsilon draw (the other workers need none of it)
+    const bool cov_writer = S.a_cov_out != nullptr && b - 1 < SN * SN / 512;
+    bool z1 = false;
+    double zc = 0.0, ldflag = 0.0, barfail = 0.0, scale = 0.0;
+    if (cov_writer) {
+        z1 = s[SC_ZBUF] != 0.0;
+        zc = s[SC_ZCOEF];  // deflation: Z = Z~ + zc u u^T (0: off)
+        ldflag = gld<COH_AGENT>(s + SC_LDFLAG);
+        barfail = s[SC_BARFAIL];
+        scale = s[SC_SCALE];
+    }
 #ifdef NS_STREAM_STAMPS
     double *wst = (tid == 0 && (b == 1 || b == W)) ? stamps + (b == 1 ? 24 : 56) : nullptr;
 #else
@@ -2202,7 +2274,14 @@ __global__ __launch_bounds__(512) void ns_finalize_stream_kernel(const double *_
     }
     const int xrole = ex >= 0 ? wave : 0;  // 1: row tile 3, 2: row tile 2, 3: row tiles 0 and 1 of the hosted tile
     // a_cov = cz sym(Z) (+ the deflated eigenpair): covo.py:132, the expression of ns_finalize_kernel / the noise GEMM's CovDeferred
-    if (S.a_cov_out != nullptr && b - 1 < SN * SN / 512) {
+    if (cov_writer) {
+        if (tid == 0) {
+            const bool timed_out = ns_logdet_timed_out(s, ldflag);
+            red[0] = gld<COH_AGENT>(s + SC_SUMLOGB);
+            red[1] = timed_out ? 1.0 : 0.0;
+        }
+        __syncthreads();
+        const double cz = ns_cz(barfail != 0.0 || red[1] != 0.0, sample_sigma, red[0], scale);
         const double *Zb = z1 ? Z1 : Z0, *Ztb = z1 ? Zt1 : Zt0;
         const int wstride = W < SN * SN / 512 ? W : SN * SN / 512;  // (small launches: the workers there are stride over the matrix)
         for (int e = (b - 1) * 512 + tid; e < SN * SN; e += wstride * 512) {
@@ -2281,7 +2360,7 @@ __global__ __launch_bounds__(512) void ns_finalize_stream_kernel(const double *_
     STREAM_PANEL(6);
     STREAM_PANEL(7);
 #undef STREAM_PANEL
-    if (!ok && S.a_cov_out != nullptr && b - 1 < SN * SN / 512) {
+    if (!ok && cov_writer) {
         // a panel flag timed out: this launch's actions are NaN -- so is the a_cov part this worker wrote before it knew (ADVICE r05:
         // the outputs of a failed step must not disagree; the sticky device status below makes the next call fail)
         const int wstride = W < SN * SN / 512 ? W : SN * SN / 512;

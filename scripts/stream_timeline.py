@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Timeline of the streamed finalize launch (sigma_ns.hip: ns_finalize_stream_kernel): its 100 MHz wall-clock stamps after a few
-covo-online steps at N (default 65536), in microseconds from the factoring workgroup's entry."""
+covo-online steps at N (default 65536), in microseconds from the factoring workgroup's entry (its first instruction)."""
 import sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
