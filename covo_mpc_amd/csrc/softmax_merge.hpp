@@ -1,9 +1,11 @@
 // softmax_merge.hpp -- stage 2 of the exp(-cost/lambda)-weighted aggregation (covo.py:266-275) as a device function: merges G
-// online-softmax records {m, s, v[128]} into the new mean (or into one merged record).  ONE body for its three callers, so that
+// online-softmax records {m, s, v[128]} into the new mean (or into one merged record).  ONE body for its callers, so that
 // they agree bit for bit whatever their workgroup size:
-//   merge_kernel (reduce.hip, 1 024 threads)          the stand-alone launch; also merges the all-gathered rank records
-//   the last workgroup of the fused small step         (step_small.hip, 256 threads: the launch finishes its own update)
-//   the last workgroup of the record-leaving rollout   (rollout_pipe.hpp, 192 .. 768 threads, fused single-GPU steps)
+//   merge_kernel (reduce.hip, reduce_lam.hip; 1 024 threads)   the stand-alone launch: the records of the record-leaving rollout or of
+//                                                      the stand-alone stage 1; also merges the all-gathered rank records
+//   the last workgroup of the fused small step         (step_small.hip, 256 threads: the launch finishes its own update;
+//                                                      rollout_common.hpp: rollout_merge_last)
+// (The merge inside the product rollout launch -- its last workgroup, 192 .. 768 threads -- was removed in round 6: DESIGN 4.7.)
 // The arithmetic is laid out over VIRTUAL lanes, not over the caller's threads: record g is "thread g" of a 1 024-thread
 // workgroup (its 64-record virtual waves are summed with the wave butterfly, the 16 wave sums in ascending order), column c of
 // slice q sums the records g = q, q + 8, q + 16, ... in ascending order with one fma each, the 8 slices are added in ascending

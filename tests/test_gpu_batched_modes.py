@@ -24,6 +24,7 @@ from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
+from tests.update_oracle import check_update  # noqa: E402
 
 DEV = "cuda:0"
 ST_TIME = 25  # packed state: the step counter's int32 bits (include/covo_hip.h)
@@ -232,7 +233,9 @@ def _oracle_check_instance(name, env, params, ns, a_mean_before, k_act, a_dev_t,
     gap = np.diff(np.sort(cost_ref)[:2])[0]
     err = np.abs(a_mean_new_t.cpu().numpy().reshape(32, 4) - a_ref).max()
     print(f"  {name} N={N}: max rel cost err {rel.max():.3e}, mean err {err:.3e}, top-2 gap {gap:.3e}")
+    print(f"  batched {name} N={N} lam {lam}: mean vs oracle costs: err {err:.3e}, gap {gap:.3e}, passed by {'err' if err < 1e-4 else 'gap'}")
     assert err < 1e-4 or gap < 1e-3 * float(lam) / 0.01, (name, N, err, gap)
+    check_update((cost_dev_t, a_dev_t), a_mean_before, 1.0, float(lam), a_mean_new_t, where=f"batched {name} N={N}")  # own costs: no hatch
     return used
 
 

@@ -40,6 +40,7 @@ from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from tests import test_gpu_batched_modes as M  # noqa: E402
 from tests.test_gpu_models import disturb_key  # noqa: E402
+from tests.update_oracle import check_update  # noqa: E402
 
 DEV = M.DEV
 GRAPHS = ["graph", "eager"]
@@ -251,7 +252,11 @@ def test_staged_step_against_the_oracle(name, disturb):
         gap = np.diff(np.sort(cost_ref)[:2])[0]
         err = np.abs(b.a_mean[e].cpu().numpy().reshape(32, 4) - a_ref).max()
         print(f"  {name} {disturb} instance {e}: max rel cost err {rel.max():.3e}, mean err {err:.3e}, top-2 gap {gap:.3e}")
+        print(f"  batched staged {name} {disturb} instance {e}: mean vs oracle costs: err {err:.3e}, gap {gap:.3e}, "
+              f"passed by {'err' if err < 1e-4 else 'gap'}")
         assert err < 1e-4 or gap < 1e-3 * float(lam) / 0.01, (name, e, err, gap)
+        check_update((b._cost[e], b._a[e]), am_before[e], 1.0, float(lam), b.a_mean[e],
+                     where=f"batched staged {name} {disturb} instance {e}")  # the same mean on the step's own costs: no hatch
     _close(inst, b)
 
 

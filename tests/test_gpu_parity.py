@@ -28,6 +28,7 @@ from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from oracle import rng_np  # noqa: E402
 from tests.conftest import make_problem  # noqa: E402
+from tests.update_oracle import check_update  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 DEV = "cuda:0"
@@ -346,7 +347,10 @@ def test_tiny_and_ragged_sample_counts(N):
     out = core.update(torch.from_numpy(am.reshape(-1)).to(DEV), 1.0).cpu().numpy().reshape(32, 4)
     upd, w = R.softmax_update(ref, a_dev.astype(np.float64), 0.01, 1.0, am.astype(np.float64))
     gap = np.diff(np.sort(ref)[:2])[0] if N > 1 else 1.0
+    err = np.abs(out - upd).max()
+    print(f"  tiny N={N}: mean vs oracle costs: err {err:.3e}, gap {gap:.3e}, passed by {'err' if err < 1e-4 else 'gap'}")
     assert np.abs(out - upd).max() < 1e-4 or gap < 1e-3
+    check_update(core, am, 1.0, 0.01, out, where=f"tiny N={N}", shifted=True)  # the same mean on the device's own costs: no hatch
 
 
 # ------------------------------------------------------------------------------------------ reduce
@@ -515,7 +519,9 @@ def test_controller_step_teacher_forced(name, task, N):
         a_new_ref, w = R.softmax_update(cost_ref, a_dev.astype(np.float64), 0.01, 1.0, a_mean_shift)
         gap = np.diff(np.sort(cost_ref)[:2])[0]
         err = np.abs(cp_new.a_mean.cpu().numpy() - a_new_ref).max()
+        print(f"  teacher-forced {name} step {step}: mean vs oracle costs: err {err:.3e}, gap {gap:.3e}, passed by {'err' if err < 1e-4 else 'gap'}")
         assert err < 1e-4 or gap < 1e-3, (step, err, gap)
+        check_update(core, cp.a_mean, 1.0, 0.01, cp_new.a_mean, where=f"teacher-forced {name} step {step}")
         assert np.array_equal(u.cpu().numpy(), cp_new.a_mean[0].cpu().numpy())
         assert cinfo["pos_mean"].shape == (32, 3) and cinfo["pos_std"].shape == (32, 3)
         cp = cp_new
@@ -1254,7 +1260,10 @@ def _oracle_check_of_a_fused_step(name, env, params, ns, a_mean_before, k_act, c
         a_ref, _ = R.softmax_update(cost_ref, a_dev, float(lam), float(gamma_mean), am)
         gap = np.diff(np.sort(cost_ref)[:2])[0]
         err = np.abs(cp_new.a_mean.cpu().numpy() - a_ref).max()
+        print(f"  fused step {name} N={N} lam {lam}: mean vs oracle costs: err {err:.3e}, gap {gap:.3e}, passed by {'err' if err < 1e-4 else 'gap'}")
         assert err < 1e-4 or gap < 1e-3 * float(lam) / 0.01, (name, N, err, gap)
+    # the same mean against fp64 on the step's OWN costs, at every N: no hatch, 1e-5
+    check_update(core, a_mean_before, float(gamma_mean), float(lam), cp_new.a_mean, where=f"fused step {name} N={N}")
 
 
 @pytest.mark.parametrize("name,N,lam", [("covo-offline", 8192, "0.01"), ("covo-offline", 1000, "0.5"), ("covo-offline", 16384, "0.01"),
