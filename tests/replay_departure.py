@@ -20,6 +20,7 @@ import json
 import sys
 
 import numpy as np
+from tests.oracle_support import oracle_params, oracle_state_packed
 
 
 def find_and_replay(window=60, out=None, seeds=(1000, 5000, 6000), E=32, N=4096, verbose=True, max_instances=1):
@@ -28,7 +29,6 @@ def find_and_replay(window=60, out=None, seeds=(1000, 5000, 6000), E=32, N=4096,
     from covo_mpc_amd import random as cr
     from oracle import c_oracle as CO
     from oracle import ref_np as R
-    from tests.test_gpu_models import _oracle_params, _oracle_state
     dev = "cuda:0"
     lam = 0.01
     env = cm.envs.Quad3D(task="tracking", obs_type="quad_params", enable_randomizer=True, disturb_type="gaussian",
@@ -73,7 +73,7 @@ def find_and_replay(window=60, out=None, seeds=(1000, 5000, 6000), E=32, N=4096,
         # pass 2: the same episode step by step (bit-identical: same kernels, same keys), oracle on instance e in the window
         b, ep, rngs = fresh()
         traj = (ep.states0[e].pos_traj, ep.states0[e].vel_traj, ep.states0[e].acc_traj)
-        po = _oracle_params(p)
+        po = oracle_params(p)
         rows, ok_all = [], True
         for t in range(t_end):
             noisy = ep.noisy[e].cpu().numpy().copy()
@@ -82,7 +82,7 @@ def find_and_replay(window=60, out=None, seeds=(1000, 5000, 6000), E=32, N=4096,
             if t < t_beg:
                 continue
             torch.cuda.synchronize()
-            so = _oracle_state(noisy, traj)
+            so = oracle_state_packed(noisy, traj)
             a_dev = b._a[e].permute(1, 0, 2).contiguous().cpu().numpy().astype(np.float64)
             cost_dev = b._cost[e].cpu().numpy()
             cost_ref = CO.rollout(so, po, a_dev, 1.0, np.zeros(3), dtype=np.float64)

@@ -12,6 +12,7 @@ quaternion (covo.py:198 plans from the noisy, un-normalised one) and every input
 import numpy as np
 
 from tests.conftest import make_problem
+from tests.oracle_support import rel_err  # noqa: F401  (re-exported: the atlas tests take it from here)
 
 PI = np.pi
 DEG = np.pi / 180.0
@@ -113,10 +114,6 @@ def one_ulp_shift(s, p, a, discount):
 def yaw_args(q):
     """(yn, yd) of the reward's yaw = atan2(yn, yd) (utils.py:289-290) on the stored quaternion"""
     return 2 * (q[3] * q[2] + q[0] * q[1]), 1 - 2 * (q[1] ** 2 + q[2] ** 2)
-
-
-def rel_err(x, ref):
-    return np.abs(x - ref) / np.maximum(np.abs(ref), 1.0)
 
 
 def loss3(e):

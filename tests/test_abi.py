@@ -6,19 +6,13 @@ import re
 
 import pytest
 
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
-
-
 def test_library_exports_every_declared_symbol(built):
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     declared = set(re.findall(r"^(?:const char \*|int )\s*(covo_\w+)\s*\(", hdr, flags=re.M))
     assert len(declared) >= 15
     lib = ctypes.CDLL(built.lib_path())

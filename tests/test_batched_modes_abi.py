@@ -11,15 +11,9 @@ import tempfile
 
 import pytest
 
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
 
 
 def _header_layout(structs):
@@ -63,7 +57,7 @@ def test_zeroed_batch_args_still_mean_covo_online(built):
     a = built.BatchArgsC()
     assert a.pad_ == 0 and not hasattr(a, "mode")
     assert built.MODE_MPPI == 0 and built.MODE_COVO_ONLINE == 1 and built.MODE_COVO_OFFLINE == 2
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     body = re.search(r"typedef struct covo_batch_args \{(.*?)\} covo_batch_args;", hdr, flags=re.S).group(1)
     assert "pad_" in body and "mode" not in re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     lib = built.load_library()
@@ -79,7 +73,7 @@ def test_zeroed_batch_args_still_mean_covo_online(built):
 
 
 def test_abi_versions_agree(built):
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     v = int(re.search(r"#define COVO_ABI_VERSION (\d+)", hdr).group(1))
     assert v == built.ABI_VERSION == built.load_library().covo_abi_version() >= 9
 

@@ -3,24 +3,15 @@ staged= of BatchedMPPIController / BatchedCoVOController / eval_env_batched): he
 does not move, the keyword is in the three signatures and is no step option, and the refusals that need no device.  No GPU call."""
 import ctypes
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
 
 
 def test_header_binding_and_library_agree(built):
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"^#define COVO_HAS_BATCHED_STAGED 1$", hdr, flags=re.M)
     assert re.search(r"^int covo_set_step_batched_staged\(covo_handle_t h, int32_t on\);$", hdr, flags=re.M)
     assert built.COVO_HAS_BATCHED_STAGED == 1

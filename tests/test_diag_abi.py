@@ -2,25 +2,14 @@
 `compute_diag` keyword of the Python surface."""
 import ctypes as C
 import inspect
-import os
 import re
 
-import pytest
-
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
 
 
 def test_diag_entry_points_exist_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"int covo_set_step_diag\(covo_handle_t h, float \*diag, int32_t n_inst\);", hdr)
     assert re.search(r"int covo_set_episode_diag_log\(covo_handle_t h, float \*log, int32_t stride\);", hdr)
     for name in ("covo_set_step_diag", "covo_set_episode_diag_log"):
@@ -33,7 +22,7 @@ def test_diag_entry_points_exist_with_the_declared_types(built):
 
 
 def test_abi_10_everywhere(built):
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     v = int(re.search(r"#define COVO_ABI_VERSION (\d+)", hdr).group(1))
     assert v == 10 == built.ABI_VERSION == built.load_library().covo_abi_version()
     assert int(re.search(r"#define COVO_DIAG_FLOATS (\d+)", hdr).group(1)) == 8 == built.COVO_DIAG_FLOATS

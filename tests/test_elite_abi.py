@@ -2,25 +2,16 @@
 Python surface: what _lib.check_elite accepts and refuses, and every refusal a constructor makes before anything touches a GPU."""
 import ctypes as C
 import inspect
-import os
 import re
 import types
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
 
 
 def test_header_declares_the_prototypes_and_macros(built):
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"int covo_set_step_elite\(covo_handle_t h, int32_t K, float \*rows_out, int32_t n_inst\);", hdr)
     assert re.search(r"int covo_elite_select\(covo_handle_t h, const float \*cost, int32_t n_samples, int32_t n_inst, int32_t K, "
                      r"float \*out, void \*stream\);", hdr)
@@ -48,7 +39,7 @@ def test_null_handle_is_an_error_with_a_message(built):
 
 def test_abi_version_did_not_move(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     v = int(re.search(r"#define COVO_ABI_VERSION (\d+)", hdr).group(1))
     assert v == 10 == built.ABI_VERSION == lib.covo_abi_version()
 

@@ -2,28 +2,20 @@
 and their Python surface: EPISODE_LOGS, the episodes' read_* and eval_env_batched(rows=)."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
+
 KINDS = ("LAM", "ELITE", "ITERS", "SIGMA", "POST_AUX", "POST_COV")
 NAMES = ("diag_log", "trace", "fanlog", "arblog", "lamlog", "elitelog", "iterlog", "sigmalog", "postlog", "postcovlog")
 
 
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
-
-
 def test_the_entry_point_exists_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"#define COVO_HAS_EPISODE_ROWS 1\b", hdr) and built.COVO_HAS_EPISODE_ROWS == 1
     for k, name in enumerate(KINDS):
         assert int(re.search(r"#define COVO_EPLOG_%s\s+(\d+)" % name, hdr).group(1)) == k == getattr(built, "COVO_EPLOG_" + name)

@@ -2,24 +2,15 @@
 Python surface, including the two env-batched modes that refuse it before anything touches a GPU."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
 
 
 def test_header_declares_the_prototypes_and_macros(built):
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"int covo_set_step_ess_floor\(covo_handle_t h, float ess_min, float \*lam_out, int32_t n_inst\);", hdr)
     assert re.search(r"int covo_ess_lambda\(covo_handle_t h, const float \*cost, int32_t n_samples, int32_t n_inst, float lam0, "
                      r"float ess_min, float \*out, void \*stream\);", hdr)
@@ -47,7 +38,7 @@ def test_null_handle_is_an_error_with_a_message(built):
 
 def test_abi_version_did_not_move(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     v = int(re.search(r"#define COVO_ABI_VERSION (\d+)", hdr).group(1))
     assert v == 10 == built.ABI_VERSION == lib.covo_abi_version()
 

@@ -2,25 +2,16 @@
 `compute_fan` keyword of the Python surface."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
 
 
 def test_fan_entry_points_exist_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"#define COVO_HAS_SAMPLE_FAN 1\b", hdr) and built.COVO_HAS_SAMPLE_FAN == 1
     assert int(re.search(r"#define COVO_FAN_FLOATS\s+(\d+)", hdr).group(1)) == 100 == built.COVO_FAN_FLOATS
     assert int(re.search(r"#define COVO_FAN_MAX\s+(\d+)", hdr).group(1)) == 64 == built.COVO_FAN_MAX

@@ -27,14 +27,12 @@ from covo_mpc_amd.dynamics.dataclass import as_device_state  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from tests.conftest import make_problem  # noqa: E402
-from tests.test_gpu_models import DP, disturb_key, params_c  # noqa: E402
-from tests.test_gpu_parity import DEV, dev_state, sample_actions, to_stripes  # noqa: E402
-from tests.test_gpu_trace import _batched, _env, _start, _step_inputs  # noqa: E402
+from tests.gpu_support import (DEV, DP, H, batched_controller, dev_state, disturb_key, params_c, quad_env, sample_actions,  # noqa: E402
+                               set_time, start_episode, step_inputs, to_stripes)
+from tests.oracle_support import oracle_state  # noqa: E402
 
-H = 32
 AF = _lib.COVO_ARB_FLOATS
 COST_BAR = 1e-5
-ST_TIME = 25
 
 
 def split_row(row):
@@ -213,7 +211,7 @@ def _check_step(env, name, params, k_act, dstate, cp_in, ca, cpa, ia, ua, cb, cp
     if core.plan is not None:
         # the plan row is the chosen candidate's: its cost is cost_chosen, its positions those of the candidate's own rollout
         assert torch.equal(core.plan[0, 0:1], core.arbiter[0, 3:4]), (where, float(core.plan[0, 0]))
-        fs, tab = _step_inputs(env, ca, name, params, k_act, dstate, one)
+        fs, tab = step_inputs(env, ca, name, params, k_act, dstate, one)
         one.a.copy_(cand.clamp(-1, 1).reshape(H, 1, 4))
         fan = one.rollout_fan(dstate, ca._params_c(params), None, f_shared=fs, f_steps=tab, K=1)
         assert torch.equal(core.plan[0, 4:], fan[0, 4:]) and torch.equal(core.plan[0, 0:1], fan[0, 0:1]), where
@@ -232,12 +230,12 @@ def test_step_arbiter_on_every_path(name, N, graph, extras, update, monkeypatch)
     inputs."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
     monkeypatch.setenv("COVO_SHARED_DEVICE", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     ca, cpa = _controller(env, name, N, update, extras)
     cb, cpb = _controller(env, name, N, "softmax", extras, plan=True)
     assert ca.core.shared_device and ca.core.uses_graph == (graph == "graph") and cb.core.arbiter is None
     one = SamplingCore(1, H, 0.01, 1.0, device=DEV, compute_info=False)
-    cp, obs, info, state, params = _start(env, ca, cpa, name)
+    cp, obs, info, state, params = start_episode(env, ca, cpa, name)
     key = cr.PRNGKey(11)
     for step in range(3):
         key, k_act, k_step = cr.split(key, 3)
@@ -257,12 +255,12 @@ def test_step_arbiter_on_every_path(name, N, graph, extras, update, monkeypatch)
 
 def test_step_arbiter_headline_size():
     """one covo-online step at N = 65 536 (the cost scan over 1 024 cache lines), guarded, with the plan attached"""
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     name, N = "covo-online", 65536
     ca, cpa = _controller(env, name, N, "guarded", False, plan=True)
     cb, cpb = _controller(env, name, N, "softmax", False, plan=True)
     one = SamplingCore(1, H, 0.01, 1.0, device=DEV, compute_info=False)
-    cp, obs, info, state, params = _start(env, ca, cpa, name)
+    cp, obs, info, state, params = start_episode(env, ca, cpa, name)
     k_act = cr.PRNGKey(12)
     dstate = as_device_state(info["noisy_state"], DEV)
     ua, cpa, ia = ca(obs, state, params, k_act, cp, info)
@@ -273,13 +271,6 @@ def test_step_arbiter_headline_size():
         c.close()
 
 
-# ------------------------------------------------------------------------------------------ 4: all three choices occur
-def _oracle_state(ns):
-    return R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
-                   vel_tar=ns.vel_tar, acc_tar=ns.acc_tar, time=ns.time, pos_traj=ns.pos_traj, vel_traj=ns.vel_traj,
-                   acc_traj=ns.acc_traj).astype(np.float64)
-
-
 SCENARIOS = {
     # name: (controller, N, lam, task, sample sigma of MPPI's covariance, offset of the start position [m], expected choice)
     "hover-on-target-wide-noise": ("mppi", 64, "0.01", "hovering", 1.0, 0.0, 1),
@@ -288,6 +279,7 @@ SCENARIOS = {
 }
 
 
+# ------------------------------------------------------------------------------------------ 4: all three choices occur
 @pytest.mark.parametrize("scenario", list(SCENARIOS))
 def test_all_three_choices_occur(scenario):
     """Three named scenarios, the issue's suggested starting points, disturbance off (one shared vector would move all three costs
@@ -301,10 +293,10 @@ def test_all_three_choices_occur(scenario):
     candidates the step formed and must separate winner and runner-up by >= 1e-3 relative before the expected choice is asserted."""
     import covo_mpc_amd as cm
     name, N, lam, task, sigma, off, want = SCENARIOS[scenario]
-    env = _env(disturb="none", task=task)
+    env = quad_env(task=task, disturb="none")
     ca, cp0 = _controller(env, name, N, "guarded", False, lam=lam)
     cb, _ = _controller(env, name, N, "softmax", False, lam=lam)
-    cp, obs, info, state, params = _start(env, ca, cp0, name)
+    cp, obs, info, state, params = start_episode(env, ca, cp0, name)
     if name == "mppi":
         cp = cp.replace(a_cov=(torch.eye(4, dtype=torch.float32, device=DEV) * sigma ** 2).repeat(H, 1, 1))
     ns = info["noisy_state"]
@@ -318,7 +310,7 @@ def test_all_three_choices_occur(scenario):
     cost3, chosen, choice, n_best, _ = split_row(ca.core.arbiter[0])
     nominal = ca.core.shift_mean(cp.a_mean.reshape(-1).contiguous()).view(H, 4)
     cands = torch.stack([cpb.a_mean.view(H, 4).clamp(-1, 1), nominal.clamp(-1, 1), ca.core.a[:, n_best, :]])
-    ref = CO.rollout(_oracle_state(ns), R.Params().fp32(), cands.cpu().numpy().astype(np.float64), 1.0, np.zeros(3), dtype=np.float64)
+    ref = CO.rollout(oracle_state(ns), R.Params().fp32(), cands.cpu().numpy().astype(np.float64), 1.0, np.zeros(3), dtype=np.float64)
     order = np.argsort(ref, kind="stable")
     margin = (ref[order[1]] - ref[order[0]]) / max(abs(ref[order[0]]), 1e-30)
     print(f"  {scenario}: oracle costs {ref}, device row {cost3}, margin {margin:.3e}, choice {choice}")
@@ -330,7 +322,7 @@ def test_all_three_choices_occur(scenario):
 
 # ------------------------------------------------------------------------------------------ 5: the env-batched controllers
 def _batch_setup(E):
-    env = _env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     return env, params, reset_keys
@@ -362,7 +354,7 @@ def test_batched_arbiter_equals_single(name, update):
         means.append(m)
         cp0 = c.init_control_params
         c.core.close()
-    b = _batched(env, name, cp0, E, N, update=update)
+    b = batched_controller(env, name, cp0, E, N, 0.01, update=update)
     assert tuple(b.arbiter.shape) == (E, AF)
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     b.bind_episode(ep)
@@ -388,7 +380,7 @@ def test_batched_after_step_launches_follow_rebound_instances(name):
     import covo_mpc_amd as cm
     N, E, K = 64, 2, 4
     env, params, reset_keys = _batch_setup(E)
-    other = _env(task="tracking_zigzag", randomizer=True)
+    other = quad_env(task="tracking_zigzag", randomizer=True)
     starts = [[e_.reset(reset_keys[e], params[e]) for e in range(E)] for e_ in (env, other)]  # [phase][e] = (obs, info, state)
     act = [np.stack([np.asarray(cr.PRNGKey(60 + 10 * k + e)) for e in range(E)]) for k in range(4)]
     kw = dict(compute_plan=True, compute_fan=K, update="guarded")
@@ -403,7 +395,7 @@ def test_batched_after_step_launches_follow_rebound_instances(name):
         want.append(w)
         cp0 = c.init_control_params
         c.core.close()
-    b = _batched(env, name, cp0, E, N, **kw)
+    b = batched_controller(env, name, cp0, E, N, 0.01, **kw)
     assert tuple(b.plan.shape) == (E, _lib.COVO_PLAN_FLOATS) and tuple(b.fan.shape) == (E, K, _lib.COVO_FAN_FLOATS)
     for k in range(4):
         if k % 2 == 0:
@@ -416,12 +408,6 @@ def test_batched_after_step_launches_follow_rebound_instances(name):
                 assert torch.equal(g, w), (name, k, e, what, g, w)
     assert b.core.device_status() == 0
     b.core.close()
-
-
-def _set_time(ep, e, t):
-    bits = torch.tensor([t], dtype=torch.int32, device=DEV).view(torch.float32)
-    ep.true[e, ST_TIME:ST_TIME + 1] = bits
-    ep.noisy[e, ST_TIME:ST_TIME + 1] = bits
 
 
 @pytest.mark.parametrize("update", ["best", "guarded"])
@@ -439,9 +425,9 @@ def test_batched_episode_arbiter_log(name, update):
     c0.core.close()
     got = {}
     for mode in ("fused", "hand"):
-        b = _batched(env, name, cp0, E, N, update=update)
+        b = batched_controller(env, name, cp0, E, N, 0.01, update=update)
         ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
-        _set_time(ep, 1, 294)
+        set_time(ep, 1, 294)
         if mode == "hand":
             b.bind_episode(ep)
             rngs, rows = [rngs0[e] for e in range(E)], []
@@ -474,7 +460,7 @@ def test_batched_episode_arbiter_log(name, update):
 def test_single_episode_arbiter_log_and_eval_env_batched():
     """covo_run_episode (6 steps, 4 + 2) against the hand-stepped loop; eval_env_batched(update=, arbiter=True) returns the log."""
     import covo_mpc_amd as cm
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     got = {}
     for mode in ("fused", "hand"):
@@ -502,7 +488,7 @@ def test_single_episode_arbiter_log_and_eval_env_batched():
     assert got["fused"][0][:6].tobytes() == got["hand"][0].tobytes() and np.all(got["fused"][0][6:] == 0.0)
     assert np.array_equal(got["fused"][1], got["hand"][1])
     assert got["fused"][2]["cost"].shape == (6, 3)
-    envr = _env(task="tracking", randomizer=True)
+    envr = quad_env(task="tracking", randomizer=True)
     err, arb = cm.envs.quadrotor.eval_env_batched(envr, 2, "N256_H32_lam0.01", n_steps=3, device=DEV, verbose=False, update="best",
                                                   arbiter=True)
     assert err.shape == (2,) and arb["cost"].shape == (2, 3, 3) and arb["choice"].shape == (2, 3) and np.all(arb["choice"] > 0)
@@ -515,7 +501,7 @@ def test_arbiter_refusals_leave_the_handle_usable():
     """Every refusal at the C boundary, matched on its message, nothing launched; afterwards the status is clean and a normal step
     is finite."""
     import covo_mpc_amd as cm
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     N = 256
     c, _ = cm.envs.get_controller(env, "mppi", f"N{N}_H32_lam0.01", device=DEV, compute_info=False, update="guarded")
@@ -580,12 +566,12 @@ def test_arbiter_refusals_leave_the_handle_usable():
     core.close()
     # (f) a batched step with more instances than n_inst
     E = 3
-    envr = _env(task="tracking", randomizer=True)
+    envr = quad_env(task="tracking", randomizer=True)
     c0, _ = cm.envs.get_controller(envr, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
     cp0 = c0.init_control_params
     c0.core.close()
     for name in ("covo-online", "mppi"):
-        b = _batched(envr, name, cp0, E, N, update="best")
+        b = batched_controller(envr, name, cp0, E, N, 0.01, update="best")
         check(b.core.lib.covo_set_step_arbiter(b.core.h, ptr(b.arbiter), 6, 2), "covo_set_step_arbiter")
         ps = [envr.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
         ep = cm.envs.BatchedDeviceEpisode(envr, [cr.PRNGKey(50 + e) for e in range(E)], ps, (b.core.lib, b.core.h), DEV)

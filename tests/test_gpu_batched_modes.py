@@ -4,12 +4,11 @@ instance as a grid dimension; controllers/batched.py: BatchedMPPIController, Bat
     and one record set per instance);
   * against oracle/ directly: per-sample costs (C fp64 rollout with the instance's own parameters, 1e-5) and the new mean
     (ref_np.softmax_update, 1e-4 unless the two best costs are closer than 1e-3 * lam / 0.01) -- the bars of
-    tests/test_gpu_parity.py::_oracle_check_of_a_fused_step, including its cap of max(2, N // 4096) samples per call that may
+    tests/gpu_cases.py::_oracle_check_of_a_fused_step, including its cap of max(2, N // 4096) samples per call that may
     use the widened bar (1.5 x what the fp32 C oracle loses against the fp64 one on the same samples);
   * whole episodes (control step + env step on the device) against per-instance episodes;
   * refusals: argument checks that return before any launch.
 """
-import types
 
 import numpy as np
 import pytest
@@ -24,121 +23,10 @@ from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
+from tests.gpu_cases import CASES, _mode_step_equals_replicas  # noqa: E402
+from tests.gpu_support import DEV, ST_TIME, batched_controller, instances, quad_env  # noqa: E402
+from tests.oracle_support import oracle_params, oracle_state, rel_err  # noqa: E402
 from tests.update_oracle import check_update  # noqa: E402
-
-DEV = "cuda:0"
-ST_TIME = 25  # packed state: the step counter's int32 bits (include/covo_hip.h)
-
-
-def rel_err(x, ref):
-    return np.abs(x - ref) / np.maximum(np.abs(ref), 1.0)
-
-
-def _env(rollover=False, disturb="gaussian", **kw):
-    import covo_mpc_amd as cm
-    return cm.envs.Quad3D(task="tracking", obs_type="quad_params", enable_randomizer=True, disturb_type=disturb,
-                          disable_rollover_terminate=not rollover, generate_noisy_state=True, device=DEV, **kw)
-
-
-def _oracle_params(params):
-    return R.Params(m=float(params.m), action_scale=float(params.action_scale), alpha_bodyrate=float(params.alpha_bodyrate),
-                    disturb_params=tuple(float(x) for x in params.disturb_params)).fp32()
-
-
-def _oracle_state(ns):
-    return R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
-                   vel_tar=ns.vel_tar, acc_tar=ns.acc_tar, time=ns.time, pos_traj=ns.pos_traj, vel_traj=ns.vel_traj,
-                   acc_traj=ns.acc_traj).astype(np.float64)
-
-
-def _instances(env, name, N, lam, E, seed=0, warm=True):
-    """E domain-randomised instances, each with its own trajectory (reset key), a state a few steps into the episode (reached
-    with its own random actions), its own key chain and its own single-instance controller."""
-    import covo_mpc_amd as cm
-    inst = []
-    for e in range(E):
-        params = env.sample_params(cr.PRNGKey(seed + 100 + e))
-        c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam}", device=DEV, compute_info=False)
-        obs, info, state = env.reset(cr.PRNGKey(seed + 200 + e), params)
-        rng = np.random.default_rng(seed + 1000 + e)
-        for k in range((2 + e % 4) if warm else 0):
-            u = (0.3 * rng.standard_normal(4)).clip(-1, 1).astype(np.float32)
-            obs, state, _, _, info = env.step(cr.PRNGKey(seed + 5000 + 10 * e + k), state, u, params)
-        inst.append(dict(params=params, c=c, cp=c.init_control_params, obs=obs, info=info, state=state,
-                         key=cr.PRNGKey(seed + 300 + e), reset_key=cr.PRNGKey(seed + 400 + e)))
-    return inst
-
-
-_TABLES = {}
-
-
-def _offline_tables(env, inst, tag):
-    """Every instance's Sigma table from a single CoVOController.reset on it (cached: the same instances come back in every case)."""
-    out = []
-    for e, i in enumerate(inst):
-        k = (tag, e)
-        if k not in _TABLES:
-            cp = i["c"].reset(i["state"], i["params"], i["c"].init_control_params, i["reset_key"])
-            _TABLES[k] = (cp.a_cov_offline, cp.a_chol_offline)
-        out.append(_TABLES[k])
-        i["cp"] = i["cp"].replace(a_cov_offline=out[-1][0], a_chol_offline=out[-1][1])
-    return torch.stack([o[0] for o in out]), torch.stack([o[1] for o in out])
-
-
-def _batched(env, name, inst, N, lam):
-    import covo_mpc_amd as cm
-    E, cp0 = len(inst), inst[0]["cp"]
-    if name == "mppi":
-        b = cm.controllers.BatchedMPPIController(env, E, N, 32, float(lam), sigmas=cp0.sample_sigma, discount=cp0.discount,
-                                                 gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=DEV)
-        assert torch.equal(b.a_cov[0], cp0.a_cov)  # quadrotor.py:705-720: diag(sigma^2) tiled over H, as the single factory's
-    else:
-        b = cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                                 sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, mode="offline")
-    return b
-
-
-CASES = [("mppi", 1024, "0.01", False), ("mppi", 100, "5.0", True), ("covo-offline", 4096, "0.01", False),
-         ("covo-offline", 40, "0.01", True)]
-
-
-def _mode_step_equals_replicas(name, N, lam, rollover, E, graph, monkeypatch):
-    """3 consecutive batched steps (eager first call, capture, replay -- or three eager calls) on E domain-randomised instances,
-    each with its own mid-episode state, trajectory and key, under the GAUSSIAN disturbance (MPPI: every instance draws its own
-    shared vector from its own key), with and without rollover termination: a_mean, the action buffer, the costs and MPPI's
-    a_cov of instance e are torch.equal to those of a single-instance controller stepped on instance e alone."""
-    monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env(rollover=rollover)
-    inst = _instances(env, name, N, lam, E)
-    b = _batched(env, name, inst, N, lam)
-    b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
-    if name == "covo-offline":
-        with pytest.raises(RuntimeError, match="call controller.reset"):
-            b([i["info"]["noisy_state"] for i in inst], np.zeros((E, 2), dtype=np.uint32))
-        b.set_tables(*_offline_tables(env, inst, (N, rollover)))
-    assert b.core.uses_graph == (graph == "graph")
-    for step in range(3):
-        k_acts = []
-        for i in inst:
-            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
-            k_acts.append(np.asarray(k_act))
-        u_b = b([i["info"]["noisy_state"] for i in inst], np.stack(k_acts)).clone()
-        for e, i in enumerate(inst):
-            u, i["cp"], _ = i["c"](i["obs"], i["state"], i["params"], k_acts[e], i["cp"], i["info"])
-            where = (name, N, E, graph, step, e)
-            assert torch.equal(b.a_mean[e].view(32, 4), i["cp"].a_mean), where
-            assert torch.equal(b._a[e], i["c"].core.a), where
-            assert torch.equal(b._cost[e], i["c"].core.cost), where
-            assert torch.equal(u_b[e], u), where
-            if name == "mppi":
-                assert torch.equal(b.a_cov[e], i["cp"].a_cov), where
-            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u.cpu().numpy(), i["params"])
-    assert b.core.device_status() == 0 and torch.isfinite(b.a_mean).all()
-    if E > 1:
-        assert (b.a_mean[0] - b.a_mean[1]).abs().max() > 1e-4  # different plants, different plans
-    b.core.close()
-    for i in inst:
-        i["c"].core.close()
 
 
 @pytest.mark.parametrize("name,N,lam,rollover", CASES)
@@ -160,13 +48,13 @@ def test_batched_graph_caches_are_dropped_by_growth_new_buffers_and_debug_setter
       after step 5: a covo_debug_set_* switch flipped and restored (the handle's epoch moves on)."""
     import covo_mpc_amd as cm
     N, lam, E, B = 1024, "0.01", 3, 5
-    env = _env()
-    inst = _instances(env, name, N, lam, E)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, name, N, lam, E)
     cp0 = inst[0]["cp"]
 
     def build():
         if name == "mppi":
-            return _batched(env, name, inst, N, lam)
+            return batched_controller(env, name, inst, len(inst), N, lam, check_cov=True)
         return cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                                     sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV)
     monkeypatch.setenv("COVO_GRAPH", "1")
@@ -207,10 +95,10 @@ def test_batched_graph_caches_are_dropped_by_growth_new_buffers_and_debug_setter
 
 
 def _oracle_check_instance(name, env, params, ns, a_mean_before, k_act, a_dev_t, cost_dev_t, a_mean_new_t, lam, rollover=False):
-    """The checks and bars of tests/test_gpu_parity.py::_oracle_check_of_a_fused_step for one instance of a batch, with the
+    """The checks and bars of tests/gpu_cases.py::_oracle_check_of_a_fused_step for one instance of a batch, with the
     instance's own parameters.  -> how many samples used the widened bar (at most max(2, N // 4096) may)."""
     N = a_dev_t.shape[1]
-    so, po = _oracle_state(ns), _oracle_params(params)
+    so, po = oracle_state(ns), oracle_params(params)
     am = R.shift_mean(np.asarray(a_mean_before, dtype=np.float64).reshape(32, 4))
     fs = np.zeros(3)
     if name == "mppi":  # mppi.py:69,74: one shared non-deterministic draw for every sample and step
@@ -246,9 +134,9 @@ def test_batched_mode_step_against_the_oracle(name, N):
     against ref_np.softmax_update of the oracle's costs.  covo-offline builds its tables through the batched controller's own
     reset()."""
     lam, E = "0.01", 6
-    env = _env()
-    inst = _instances(env, name, N, lam, E, seed=7)
-    b = _batched(env, name, inst, N, lam)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, name, N, lam, E, seed=7)
+    b = batched_controller(env, name, inst, len(inst), N, lam, check_cov=True)
     b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
     if name == "covo-offline":
         b.reset([i["state"] for i in inst], [i["params"] for i in inst], [i["reset_key"] for i in inst])
@@ -277,10 +165,10 @@ def test_run_episode_batched_mode_equals_per_instance_episodes(name, N):
     equal those of 8 single CoVOController.reset calls."""
     import covo_mpc_amd as cm
     E, n, lam = 8, 40, "0.01"
-    env = _env()
-    inst = _instances(env, name, N, lam, E, seed=50, warm=False)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, name, N, lam, E, seed=50, warm=False)
     params = [i["params"] for i in inst]
-    b = _batched(env, name, inst, N, lam)
+    b = batched_controller(env, name, inst, len(inst), N, lam, check_cov=True)
     reset_keys = [cr.PRNGKey(150 + e) for e in range(E)]
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     late = torch.tensor([285], dtype=torch.int32, device=DEV).view(torch.float32)
@@ -323,7 +211,7 @@ def test_batched_mode_refusals_name_the_condition_and_leave_the_handle_usable():
     N, lam, E = 256, "0.01", 2
 
     def build(env, name="mppi", n=N, **kw):
-        inst = _instances(env, name, n, lam, E, warm=False)
+        inst = instances(env, name, n, lam, E, warm=False)
         cp0 = inst[0]["cp"]
         if name == "mppi":
             b = cm.controllers.BatchedMPPIController(env, E, n, 32, 0.01, sigmas=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, **kw)
@@ -335,8 +223,8 @@ def test_batched_mode_refusals_name_the_condition_and_leave_the_handle_usable():
     keys = np.arange(2 * E, dtype=np.uint32).reshape(E, 2) + 1
     # gamma_sigma != 0: the constructor, and the C boundary for a caller that sets the field itself
     with pytest.raises(NotImplementedError, match="gamma_sigma"):
-        cm.controllers.BatchedMPPIController(_env(), E, N, 32, 0.01, gamma_sigma=0.2, device=DEV)
-    b, inst = build(_env())
+        cm.controllers.BatchedMPPIController(quad_env(task="tracking", randomizer=True), E, N, 32, 0.01, gamma_sigma=0.2, device=DEV)
+    b, inst = build(quad_env(task="tracking", randomizer=True))
     noisy = [i["info"]["noisy_state"] for i in inst]
     b._args.gamma_sigma = 0.2
     with pytest.raises(_lib.CovoError, match="gamma_sigma != 0"):
@@ -344,7 +232,7 @@ def test_batched_mode_refusals_name_the_condition_and_leave_the_handle_usable():
     b._args.gamma_sigma = 0.0
     # more instances than COVO_MAX_ENVS
     with pytest.raises(ValueError, match="n_envs"):
-        cm.controllers.BatchedMPPIController(_env(), _lib.COVO_MAX_ENVS + 1, N, 32, 0.01, device=DEV)
+        cm.controllers.BatchedMPPIController(quad_env(task="tracking", randomizer=True), _lib.COVO_MAX_ENVS + 1, N, 32, 0.01, device=DEV)
     b._args.base.n_envs = _lib.COVO_MAX_ENVS + 1
     with pytest.raises(_lib.CovoError, match="n_envs=65"):
         b(noisy, keys)
@@ -353,21 +241,21 @@ def test_batched_mode_refusals_name_the_condition_and_leave_the_handle_usable():
     u = b(noisy, keys).clone()
     assert torch.isfinite(u).all() and b.core.device_status() == 0
     # the realworld reward
-    env_r = _env()
+    env_r = quad_env(task="tracking", randomizer=True)
     env_r.reward_fn = utils.tracking_realworld_reward_fn
     br, inst_r = build(env_r)
     with pytest.raises(_lib.CovoError, match="realworld reward"):
         br([i["info"]["noisy_state"] for i in inst_r], keys)
     # a disturbance model with per-step tables
-    bp, inst_p = build(_env(disturb="periodic"))
+    bp, inst_p = build(quad_env(task="tracking", randomizer=True, disturb="periodic"))
     with pytest.raises(_lib.CovoError, match="per-step tables"):
         bp([i["info"]["noisy_state"] for i in inst_p], keys)
     # N > 16 384
-    bn, inst_n = build(_env(), n=16384 + 64)
+    bn, inst_n = build(quad_env(task="tracking", randomizer=True), n=16384 + 64)
     with pytest.raises(_lib.CovoError, match="16384"):
         bn([i["info"]["noisy_state"] for i in inst_n], keys)
     # covo-offline without a table: the controller, and the C boundary
-    bo, inst_o = build(_env(), name="covo-offline")
+    bo, inst_o = build(quad_env(task="tracking", randomizer=True), name="covo-offline")
     with pytest.raises(RuntimeError, match="a_cov_offline table missing"):
         bo([i["info"]["noisy_state"] for i in inst_o], keys)
     bo.a_chol_offline = torch.zeros(1, device=DEV)  # (past the controller's own check; the argument block still has no table)
@@ -405,13 +293,13 @@ def test_masked_launch_groups_of_the_phase_timers(graph, monkeypatch):
     import covo_mpc_amd as cm
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
     N, lam, E = 256, "0.01", 2
-    env = _env()
+    env = quad_env(task="tracking", randomizer=True)
 
     def timed_ok(us, what):
         assert np.isfinite(us) and us > 0.0, (graph, what, us)
 
     # ---- single: two identical controllers on instance 0, the first one runs the timers between its two steps
-    runs = [_instances(env, "covo-online", N, lam, 1)[0] for _ in range(2)]
+    runs = [instances(env, "covo-online", N, lam, 1)[0] for _ in range(2)]
     assert runs[0]["c"].core.uses_graph == (graph == "graph")
     for step in range(2):
         for r, i in enumerate(runs):
@@ -435,7 +323,7 @@ def test_masked_launch_groups_of_the_phase_timers(graph, monkeypatch):
     assert all(i["c"].core.device_status() == 0 for i in runs)
 
     # ---- env-batched: two identical controllers on E instances
-    inst = _instances(env, "covo-online", N, lam, E)
+    inst = instances(env, "covo-online", N, lam, E)
     cp0 = inst[0]["cp"]
     bs = [cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
                                                sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV) for _ in range(2)]

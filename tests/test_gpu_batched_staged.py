@@ -38,11 +38,10 @@ from covo_mpc_amd.controllers.batched import CORE_BUFFERS  # noqa: E402
 from covo_mpc_amd.dynamics.dataclass import as_device_state  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
-from tests import test_gpu_batched_modes as M  # noqa: E402
-from tests.test_gpu_models import disturb_key  # noqa: E402
+from tests.gpu_support import DEV, ST_TIME, batched_controller, disturb_key, instances, offline_tables, quad_env  # noqa: E402
+from tests.oracle_support import oracle_params, oracle_state, rel_err  # noqa: E402
 from tests.update_oracle import check_update  # noqa: E402
 
-DEV = M.DEV
 GRAPHS = ["graph", "eager"]
 
 
@@ -50,46 +49,12 @@ def _bits(t):
     return t.contiguous().view(torch.int32).reshape(-1)
 
 
-def _env(disturb="gaussian", rollover=False, task="tracking"):
-    if task == "tracking":
-        return M._env(rollover=rollover, disturb=disturb)
-    return cm.envs.Quad3D(task=task, obs_type="quad_params", enable_randomizer=True, disturb_type=disturb,
-                          disable_rollover_terminate=not rollover, generate_noisy_state=True, device=DEV)
-
-
-def _instances(env, name, N, lam, E, seed=0, warm=True, gamma_sigma=0.0, **opts):
-    """M._instances; with step options, every instance's single controller is rebuilt with them."""
-    inst = M._instances(env, name, N, lam, E, seed=seed, warm=warm)
-    for i in inst:
-        if opts:
-            i["c"].core.close()
-            i["c"], _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam}", device=DEV, compute_info=False, **opts)
-            i["cp"] = i["c"].init_control_params
-        if gamma_sigma:
-            i["cp"] = i["cp"].replace(gamma_sigma=gamma_sigma)
-    return inst
-
-
-def _batched(env, name, inst, N, lam, staged=True, gamma_sigma=0.0, **opts):
-    E, cp0 = len(inst), inst[0]["cp"]
-    if name == "mppi":
-        b = cm.controllers.BatchedMPPIController(env, E, N, 32, float(lam), sigmas=cp0.sample_sigma, discount=cp0.discount,
-                                                 gamma_mean=cp0.gamma_mean, gamma_sigma=gamma_sigma, a_mean_init=cp0.a_mean,
-                                                 device=DEV, staged=staged, **opts)
-    else:
-        b = cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                                 sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, mode="offline",
-                                                 staged=staged, **opts)
-    b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
-    return b
-
-
 def _tables(env, name, inst, bs, shared=False):
     """covo-offline: every instance's table (one set for the whole file: both sides of a comparison read the same factors, whatever
     they were built from); shared: all instances read instance 0's through L_table_stride = 0."""
     if name != "covo-offline":
         return
-    Sig, L = M._offline_tables(env, inst, "staged")
+    Sig, L = offline_tables(env, inst, "staged")
     for b in bs:
         b.set_tables(Sig, L)
         if shared:
@@ -146,11 +111,13 @@ def _close(inst, *bs):
 def _case(name, N, lam, graph, monkeypatch, E=3, disturb="gaussian", rollover=False, task="tracking", gamma_sigma=0.0, shared=False,
           fused_twin=False, **opts):
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env(disturb, rollover, task)
-    inst = _instances(env, name, N, lam, E, gamma_sigma=gamma_sigma, **opts)
-    b = _batched(env, name, inst, N, lam, gamma_sigma=gamma_sigma, **opts)
+    env = quad_env(task=task, randomizer=True, rollover=rollover, disturb=disturb)
+    inst = instances(env, name, N, lam, E, gamma_sigma=gamma_sigma, **opts)
+    b = batched_controller(env, name, inst, len(inst), N, lam, set_instances=True, staged=True, gamma_sigma=gamma_sigma, **opts)
     assert b.staged and b.core.uses_graph == (graph == "graph")
-    twins = [_batched(env, name, inst, N, lam, staged=False)] if fused_twin else []
+    twins = []
+    if fused_twin:
+        twins = [batched_controller(env, name, inst, len(inst), N, lam, set_instances=True, staged=False, gamma_sigma=0.0)]
     _tables(env, name, inst, [b] + twins, shared)
     _steps(env, name, inst, b, twins, where=(name, N, graph, disturb, task))
     if gamma_sigma:
@@ -219,9 +186,9 @@ def test_staged_step_against_the_oracle(name, disturb):
     max(2, N // 4096) samples per instance may use the widened bar, 1.5 x what the fp32 C oracle loses against the fp64 one), the new
     mean against ref_np.softmax_update of the oracle's costs (1e-4 unless the two best costs are closer than 1e-3 * lam / 0.01)."""
     N, lam, E = 1024, "0.01", 3
-    env = _env(disturb)
-    inst = _instances(env, name, N, lam, E, seed=7)
-    b = _batched(env, name, inst, N, lam)
+    env = quad_env(task="tracking", randomizer=True, disturb=disturb)
+    inst = instances(env, name, N, lam, E, seed=7)
+    b = batched_controller(env, name, inst, len(inst), N, lam, set_instances=True, staged=True, gamma_sigma=0.0)
     _tables(env, name, inst, [b])
     k_acts = [np.asarray(cr.split(i["key"], 3)[1]) for i in inst]
     am_before = b.a_mean.cpu().numpy().copy()
@@ -230,19 +197,19 @@ def test_staged_step_against_the_oracle(name, disturb):
     torch.cuda.synchronize()
     for e, i in enumerate(inst):
         p = i["params"]
-        so = M._oracle_state(noisy[e])
-        po = M._oracle_params(p).replace(disturb_period=int(p.disturb_period), disturb_scale=float(p.disturb_scale))
+        so = oracle_state(noisy[e])
+        po = oracle_params(p).replace(disturb_period=int(p.disturb_period), disturb_scale=float(p.disturb_scale))
         step_key = cr.split(cr.split(k_acts[e])[0])[1]
         draw = cr.uniform(disturb_key(step_key), (3,), -po.disturb_scale, po.disturb_scale).astype(np.float64)
         d = R.Disturb(disturb, draw, name != "mppi")
         a_dev = b._a[e].permute(1, 0, 2).contiguous().cpu().numpy().astype(np.float64)
         cost_dev = b._cost[e].cpu().numpy()
         cost_ref = CO.rollout(so, po, a_dev, 1.0, dtype=np.float64, disturb=d)
-        rel = M.rel_err(cost_dev, cost_ref)
+        rel = rel_err(cost_dev, cost_ref)
         bar = 1e-5
         if rel.max() >= bar:
             c32 = CO.rollout(so.astype(np.float32), po, a_dev.astype(np.float32), 1.0, dtype=np.float32, disturb=d)
-            bar = max(bar, 1.5 * M.rel_err(c32, cost_ref).max())
+            bar = max(bar, 1.5 * rel_err(c32, cost_ref).max())
             used = int((rel >= 1e-5).sum())
             print(f"  {name} {disturb} instance {e}: {used} samples beyond 1e-5 (max {rel.max():.3e})")
             assert used <= max(2, N // 4096), (name, e, used)
@@ -267,9 +234,9 @@ def test_staged_covariance_adaptation_against_the_oracle(N, lam):
     covariances about the NEW mean and blended into the SHIFTED old ones (mppi.py:43-49, 109-125) -- the reference, the inputs and
     the bars (1e-5 and 1e-5) of tests/test_gpu_models.py::test_mppi_covariance_adaptation_vs_oracle."""
     E, gs = 3, 0.2
-    env = _env()
-    inst = _instances(env, "mppi", N, lam, E, seed=11, gamma_sigma=gs)
-    b = _batched(env, "mppi", inst, N, lam, gamma_sigma=gs)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, "mppi", N, lam, E, seed=11, gamma_sigma=gs)
+    b = batched_controller(env, "mppi", inst, len(inst), N, lam, set_instances=True, staged=True, gamma_sigma=gs)
     moved = 0.0
     for step in range(2):
         k_acts = []
@@ -304,15 +271,15 @@ def test_run_episode_staged_equals_per_instance_episodes():
     per-instance DeviceEpisodes of the single controller with the same keys: env logs, elite logs, means, covariances, final states
     and key chains bit-identical.  Instance 1 starts at max_steps - 3: it terminates and auto-resets inside the segment."""
     E, n, N, lam, name = 3, 8, 256, "0.01", "mppi"
-    env = _env("periodic")
-    inst = _instances(env, name, N, lam, E, seed=50, warm=False, elite=8)
+    env = quad_env(task="tracking", randomizer=True, disturb="periodic")
+    inst = instances(env, name, N, lam, E, seed=50, warm=False, elite=8)
     params = [i["params"] for i in inst]
-    b = _batched(env, name, inst, N, lam, elite=8)
+    b = batched_controller(env, name, inst, len(inst), N, lam, set_instances=True, staged=True, gamma_sigma=0.0, elite=8)
     reset_keys = [cr.PRNGKey(150 + e) for e in range(E)]
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     late = torch.tensor([int(params[1].max_steps_in_episode) - 3], dtype=torch.int32, device=DEV).view(torch.float32)
-    ep.true[1, M.ST_TIME:M.ST_TIME + 1] = late
-    ep.noisy[1, M.ST_TIME:M.ST_TIME + 1] = late
+    ep.true[1, ST_TIME:ST_TIME + 1] = late
+    ep.noisy[1, ST_TIME:ST_TIME + 1] = late
     rngs0 = np.stack([np.asarray(cr.PRNGKey(160 + e)) for e in range(E)])
     rngs = b.run_episode(ep, rngs0, n // 2)
     rngs = b.run_episode(ep, rngs, n - n // 2)
@@ -325,8 +292,8 @@ def test_run_episode_staged_equals_per_instance_episodes():
         c.alias_outputs = True
         se = cm.envs.DeviceEpisode(env, reset_keys[e], params[e], (c.core.lib, c.core.h), DEV)
         if e == 1:
-            se.true[M.ST_TIME:M.ST_TIME + 1] = late
-            se.noisy[M.ST_TIME:M.ST_TIME + 1] = late
+            se.true[ST_TIME:ST_TIME + 1] = late
+            se.noisy[ST_TIME:ST_TIME + 1] = late
         cp = c.reset(se.state0, params[e], c.init_control_params, cr.PRNGKey(250 + e))
         cp, rng = c.run_episode(se, params[e], cp, rngs0[e], n)
         assert np.array_equal(se.read_log(), log[e]), e
@@ -345,11 +312,11 @@ def test_run_episode_staged_equals_per_instance_episodes():
 # ---- 6. refusals under staged -----------------------------------------------------------------------------------------------------
 def test_staged_refusals_name_the_condition_and_leave_the_handle_usable():
     N, lam, E = 256, "0.01", 2
-    env = _env()
-    inst = _instances(env, "mppi", N, lam, E, warm=False)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, "mppi", N, lam, E, warm=False)
     noisy = [i["info"]["noisy_state"] for i in inst]
     keys = np.arange(2 * E, dtype=np.uint32).reshape(E, 2) + 1
-    b = _batched(env, "mppi", inst, N, lam, gamma_sigma=0.2)
+    b = batched_controller(env, "mppi", inst, len(inst), N, lam, set_instances=True, staged=True, gamma_sigma=0.2)
     assert b._args.gamma_sigma == np.float32(0.2)
     # the update reads the per-wave minima
     gm = b._args.base.groupmin
@@ -366,8 +333,8 @@ def test_staged_refusals_name_the_condition_and_leave_the_handle_usable():
     _lib.check(b.core.lib.covo_set_step_elite(b.core.h, 0, None, 0), "covo_set_step_elite")
     assert torch.isfinite(b(noisy, keys)).all() and b.core.device_status() == 0
     # gamma_sigma is MPPI's
-    inst_o = _instances(env, "covo-offline", 64, lam, E, warm=False)
-    bo = _batched(env, "covo-offline", inst_o, 64, lam)
+    inst_o = instances(env, "covo-offline", 64, lam, E, warm=False)
+    bo = batched_controller(env, "covo-offline", inst_o, len(inst_o), 64, lam, set_instances=True, staged=True, gamma_sigma=0.0)
     _tables(env, "covo-offline", inst_o, [bo])
     noisy_o = [i["info"]["noisy_state"] for i in inst_o]
     bo._args.gamma_sigma = 0.2
@@ -392,7 +359,7 @@ def test_staged_refusals_name_the_condition_and_leave_the_handle_usable():
 def test_eval_env_batched_runs_the_baselines_staged(controller, opts):
     """eval_env_batched on the two baseline controllers under the periodic disturbance with an option the fused launch refuses: it runs
     under staged=True (finite errors, the rows of the option come back) and is refused without it, as the controllers are."""
-    env = _env("periodic")
+    env = quad_env(task="tracking", randomizer=True, disturb="periodic")
     run = lambda **kw: cm.envs.quadrotor.eval_env_batched(env, 2, "N256_H32_lam0.01", n_steps=4, device=DEV, verbose=False,
                                                           controller=controller, rows=True, **opts, **kw)
     with pytest.raises(NotImplementedError, match="staged=True"):
@@ -424,9 +391,9 @@ def test_one_handle_through_both_batched_entry_points(sigma_period, monkeypatch)
     with that message, and A's steps between the refused calls go on through refresh and reuse -- sigma_age 0, 1, 0, 1 -- equal to A
     alone."""
     monkeypatch.setenv("COVO_GRAPH", "1")
-    env = _env()
-    inst_a = M._instances(env, "covo-online", 256, "0.01", 3, seed=20)
-    inst_b = _instances(env, "mppi", 100, "0.01", 2, seed=30)  # (lam and the discount are the handle's: one value for both)
+    env = quad_env(task="tracking", randomizer=True)
+    inst_a = instances(env, "covo-online", 256, "0.01", 3, seed=20)
+    inst_b = instances(env, "mppi", 100, "0.01", 2, seed=30)  # (lam and the discount are the handle's: one value for both)
     _close(inst_a + inst_b)  # (only the instances' states, parameters and keys are used)
     keys = {}
     for tag, inst in (("A", inst_a), ("B", inst_b)):
@@ -445,7 +412,7 @@ def test_one_handle_through_both_batched_entry_points(sigma_period, monkeypatch)
                                                  sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV,
                                                  sigma_period=sigma_period)
         A.set_instances([i["state"] for i in inst_a], [i["params"] for i in inst_a])
-        B = _batched(env, "mppi", inst_b, 100, "0.01")
+        B = batched_controller(env, "mppi", inst_b, len(inst_b), 100, "0.01", set_instances=True, staged=True, gamma_sigma=0.0)
         assert A.core.uses_graph and B.core.uses_graph and B.staged
         return A, B
 

@@ -8,7 +8,7 @@ Bars.  Everything in a step is equality of bits, as in the modules the bodies co
               (L' 3e-6, Sigma' 1e-6), at k = 1, 2, 3, 16, 30, 31, 32, 63
   log det     |2 sum log L'_ii - 2 n log sigma| <= 2 n 2^-24 at EVERY k: the bar is derived per step (each diagonal entry of the
               fp32 L' within 2^-24 relative of an fp64 one whose log det is exact) and every step renormalises -- nothing accumulates
-  k shifts    against the closed form c_k S^k(Sigma) of the ORIGINAL fp32 factor (tests/test_sigma_period_abi.py::shift_power_ref):
+  k shifts    against the closed form c_k S^k(Sigma) of the ORIGINAL fp32 factor (tests/sigma_shift_oracle.py::shift_power_ref):
               one one-step bar plus twice what the restatement's own fp32 chain (shift_chain_ref) is off by at the same k.  Two
               chains that round L' to fp32 at every step, each started from the same factor, are both that far from the exact answer;
               the kernel gets one more one-step bar for its own arithmetic.  The bar is computed, not chosen: the module fixture
@@ -29,18 +29,14 @@ import covo_mpc_amd as cm  # noqa: E402
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
-from tests.test_gpu_batched_modes import CASES as MODE_CASES  # noqa: E402
-from tests.test_gpu_batched_modes import ST_TIME, _mode_step_equals_replicas  # noqa: E402
-from tests.test_gpu_iters import _batched, _batched_iters_case, _benv, _definition_case, _instances, _run_episode_case  # noqa: E402
-from tests.test_gpu_parity import _batched_step_equals_replicas  # noqa: E402
-from tests.test_gpu_sigma_adapt import check_structure, errors, g32  # noqa: E402
-from tests.test_gpu_sigma_period import _batched_period_case, _period_case, check_shift  # noqa: E402
-from tests.test_sigma_adapt_abi import adapt_ref  # noqa: E402
-from tests.test_sigma_period_abi import (BAR_L, BAR_LOGDET, BAR_SIGMA, N_A, chain_ratios, decoupled_rows, off_structure,  # noqa: E402
-                                         random_spd_factors, shift_chain_ref, shift_factor_ref, shift_power_ref)
+from tests.gpu_cases import (CASES, _batched_iters_case, _batched_period_case, _batched_step_equals_replicas,  # noqa: E402
+                             _definition_case, _mode_step_equals_replicas, _period_case, _run_episode_case, check_shift,
+                             check_structure, errors, g32)
+from tests.gpu_support import DEV, ST_TIME, batched_controller, instances, quad_env  # noqa: E402
+from tests.sigma_shift_oracle import (BAR_L, BAR_LOGDET, BAR_SIGMA, N_A, adapt_ref, chain_ratios, decoupled_rows,  # noqa: E402
+                                      off_structure, random_spd_factors, shift_chain_ref, shift_factor_ref, shift_power_ref)
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEV = "cuda:0"
 SIGMA = 0.5
 E_MAX, K_MAX, M_MAX, FAN_MAX = _lib.COVO_MAX_ENVS, _lib.COVO_MAX_STEP_ITERS, _lib.COVO_MAX_SIGMA_PERIOD, _lib.COVO_FAN_MAX
 CHAIN = M_MAX - 1                       # reuse steps in a row at the largest period
@@ -235,7 +231,7 @@ def test_run_episode_with_16_passes_equals_the_python_loop():
 
 # ---- e: 64 (and 33) env instances ------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("E", [33, E_MAX])
-@pytest.mark.parametrize("name,N,lam,rollover", [c for c in MODE_CASES if c[1] <= 100])
+@pytest.mark.parametrize("name,N,lam,rollover", [c for c in CASES if c[1] <= 100])
 def test_batched_mode_step_equals_replicas_at_the_ceiling(name, N, lam, rollover, E, monkeypatch):
     """MPPI N = 100 and covo-offline N = 40: instance e of 3 batched steps (eager, capture, replay) is the single controller's."""
     _mode_step_equals_replicas(name, N, lam, rollover, E, "graph", monkeypatch)
@@ -249,7 +245,7 @@ def test_batched_online_step_equals_replicas_at_the_ceiling(E):
 def test_batched_env_step_of_64_equals_the_single_kernel():
     """covo_env_step_batched, E = 64, 4 steps: every instance's true and noisy state and log equal covo_env_step on it alone."""
     E = E_MAX
-    env = _benv()
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(900 + e)) for e in range(E)]
     core = SamplingCore(256, 32, 0.01, 1.0, device=DEV)
     keys0 = [cr.PRNGKey(1000 + e) for e in range(E)]
@@ -281,7 +277,7 @@ def test_run_episode_batched_of_64_equals_per_instance_episodes():
     """covo_run_episode_batched, covo-online N = 256, E = 64, 8 steps; instance 40 starts at step 294 of its episode, terminates
     and auto-resets inside the run.  Per instance: log, mean, Sigma, state, trajectory and key chain of covo_run_episode alone."""
     E, N, n, late_e = E_MAX, 256, 8, 40
-    env = _benv()
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     c0, _ = cm.envs.get_controller(env, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
     cp0 = c0.init_control_params
@@ -329,9 +325,9 @@ def test_one_step_of_64_with_every_attachment(weights):
     actions of instance e are the single controller's with the same options on instance e alone, bit for bit."""
     E, N = E_MAX, 256
     opts = dict(ATTACHED, **weights)
-    env = _benv()
-    inst = _instances(env, "covo-online", N, E, **opts)
-    b = _batched(env, "covo-online", inst, N, **opts)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, "covo-online", N, "0.01", E, **opts)
+    b = batched_controller(env, "covo-online", inst, len(inst), N, 0.01, **opts)
     b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
     assert tuple(b.fan.shape) == (E, FAN_MAX, _lib.COVO_FAN_FLOATS) == (64, 64, 100) and tuple(b.core.fan_idx.shape) == (E, FAN_MAX)
     assert tuple(b.post_cov.shape) == (E, N_A, N_A) and tuple(b.arbiter.shape) == (E, _lib.COVO_ARB_FLOATS) and b.diag.shape[0] == E

@@ -41,9 +41,9 @@ from covo_mpc_amd._lib import ptr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
 from tests import chol_cases as CC  # noqa: E402
 from tests.conftest import make_problem  # noqa: E402
+from tests.gpu_support import DEV  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEV = "cuda:0"
 SHARE = 0.999
 
 

@@ -20,20 +20,10 @@ if not torch.cuda.is_available():
 
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
+from tests.gpu_support import DEV, batched_controller, instances, quad_env, set_time, single_controller  # noqa: E402
+from tests.oracle_support import rel_err_scalar  # noqa: E402
 
-DEV = "cuda:0"
-ST_TIME = 25
 BARS = {"ess": 3e-5, "cost_weighted": 1e-5, "cost_mean": 1e-5, "weight_sum": 1e-5}
-
-
-def rel_err(x, ref):
-    return abs(float(x) - float(ref)) / max(abs(float(ref)), 1.0)
-
-
-def _env(rollover=False, randomizer=False, task="tracking_zigzag"):
-    import covo_mpc_amd as cm
-    return cm.envs.Quad3D(task=task, obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type="gaussian", disable_rollover_terminate=not rollover, generate_noisy_state=True, device=DEV)
 
 
 def _reference(cost_f32, lam):
@@ -51,32 +41,13 @@ def _check_against_fp64(diag_row, cost, lam, where):
     c = cost.cpu().numpy()
     ref = _reference(c, lam)
     got = dict(zip(_lib.DIAG_FIELDS, d[:6]))
-    errs = {k: rel_err(got[k], ref[k]) for k in BARS}
+    errs = {k: rel_err_scalar(got[k], ref[k]) for k in BARS}
     print(f"  {where}: ess {got['ess']:.6g} (ref {ref['ess']:.6g}) errs " + " ".join(f"{k} {v:.2e}" for k, v in errs.items()))
     assert np.float32(ref["cost_min"]) == got["cost_min"], (where, got["cost_min"], ref["cost_min"])
     for k, bar in BARS.items():
         assert errs[k] <= bar, (where, k, errs[k], bar, got[k], ref[k])
     assert got["n_samples"] == float(c.size) and d[6] == 0.0 and d[7] == 0.0, (where, d)
     return errs
-
-
-_OFFLINE = {}
-
-
-def _controller(env, name, N, lam, diag=True, seed=1):
-    """A single controller mid-episode: (controller, control params, obs, info, state, params)."""
-    import covo_mpc_amd as cm
-    c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam}", device=DEV, compute_info=False, compute_diag=diag)
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(seed), params)
-    cp = c.init_control_params
-    if name == "covo-offline":  # the Sigma table depends on neither N nor lambda: built once per env variant
-        k = (env.disable_rollover_terminate, seed)
-        if k not in _OFFLINE:
-            t = c.reset(state, params, cp, cr.PRNGKey(seed + 1))
-            _OFFLINE[k] = (t.a_cov_offline, t.a_chol_offline)
-        cp = cp.replace(a_cov_offline=_OFFLINE[k][0], a_chol_offline=_OFFLINE[k][1])
-    return c, cp, obs, info, state, params
 
 
 SIZES = {"mppi": [40, 1024, 8192, 65536], "covo-offline": [40, 1024, 8192, 65536], "covo-online": [40, 1024, 8192, 65536]}
@@ -93,8 +64,8 @@ def test_diag_against_fp64_on_the_device_costs(name, N, lam, rollover, graph, mo
     covo-offline) and the record-leaving rollout (covo-online); N = 65 536: the record-leaving rollout for all three.  The
     stand-alone stage 1 (more workgroups than records) is test_diag_standalone_stage1.  Measured maxima: DESIGN 4.7."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env(rollover=rollover)
-    c, cp, obs, info, state, params = _controller(env, name, N, lam)
+    env = quad_env(task="tracking_zigzag", rollover=rollover)
+    c, cp, obs, info, state, params = single_controller(env, name, N, lam=lam, compute_diag=True)
     key = cr.PRNGKey(3)
     for step in range(3):
         key, k_act, k_step = cr.split(key, 3)
@@ -115,8 +86,8 @@ def test_diag_standalone_stage1(name, lam, monkeypatch):
     (reduce.hip: softmax_partial_diag_kernel) forms the sums."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     N = 300000
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, name, N, lam)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, name, N, lam=lam, compute_diag=True)
     key = cr.PRNGKey(5)
     for step in range(2):
         key, k_act, k_step = cr.split(key, 3)
@@ -130,8 +101,8 @@ def test_diag_standalone_stage1(name, lam, monkeypatch):
 def test_diag_mppi_covariance_adaptation(monkeypatch):
     """MPPI with gamma_sigma != 0 runs its own stage 1 and merge (second moments): the diagnostics come from the same records."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, "mppi", 4096, "0.01")
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "mppi", 4096, compute_diag=True)
     cp = cp.replace(gamma_sigma=0.1)
     u, cp, _ = c(obs, state, params, cr.PRNGKey(9), cp, info)
     torch.cuda.synchronize()
@@ -144,8 +115,8 @@ def test_known_answer_frozen_rewards(name, N, monkeypatch):
     """A state outside the 3 m box: every rollout terminates at step 0, every reward is frozen, all costs are equal --
     ess == N, weight_sum == N (sums of ones, exact below 2^24), cost_min == cost_weighted == cost_mean, exactly."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, name, N, "0.01")
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, name, N, compute_diag=True)
     ns = info["noisy_state"]
     info = dict(info, noisy_state=ns.replace(pos=np.array([5.0, 0.0, 0.0], dtype=np.float32)))
     c(obs, state, params, cr.PRNGKey(4), cp, info)
@@ -162,8 +133,8 @@ def test_known_answer_frozen_rewards(name, N, monkeypatch):
 @pytest.mark.parametrize("name", ["mppi", "covo-offline", "covo-online"])
 def test_known_answer_one_sample(name, monkeypatch):
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, name, 1, "0.01")
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, name, 1, compute_diag=True)
     c(obs, state, params, cr.PRNGKey(4), cp, info)
     torch.cuda.synchronize()
     d = c.core.diag[0].cpu().numpy()
@@ -178,9 +149,9 @@ def test_nothing_else_moves(name, N, graph, monkeypatch):
     """Two controllers on the same inputs, one with compute_diag: a_mean, the actions, the costs and a_cov are torch.equal over
     three consecutive steps."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env()
-    A = _controller(env, name, N, "0.01", diag=True)
-    B = _controller(env, name, N, "0.01", diag=False)
+    env = quad_env(task="tracking_zigzag")
+    A = single_controller(env, name, N, compute_diag=True)
+    B = single_controller(env, name, N)
     ca, cpa, obs, info, state, params = A
     cb, cpb = B[0], B[1]
     key = cr.PRNGKey(11)
@@ -198,35 +169,6 @@ def test_nothing_else_moves(name, N, graph, monkeypatch):
     assert ca.core.device_status() == 0
     ca.core.close()
     cb.core.close()
-
-
-def _instances(env, name, N, lam, E, seed=0):
-    """E domain-randomised instances mid-episode, each with its own single controller with diagnostics (the builder of
-    tests/test_gpu_batched_modes.py)."""
-    import covo_mpc_amd as cm
-    inst = []
-    for e in range(E):
-        params = env.sample_params(cr.PRNGKey(seed + 100 + e))
-        c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam}", device=DEV, compute_info=False, compute_diag=True)
-        obs, info, state = env.reset(cr.PRNGKey(seed + 200 + e), params)
-        rng = np.random.default_rng(seed + 1000 + e)
-        for k in range(2 + e % 4):
-            u = (0.3 * rng.standard_normal(4)).clip(-1, 1).astype(np.float32)
-            obs, state, _, _, info = env.step(cr.PRNGKey(seed + 5000 + 10 * e + k), state, u, params)
-        inst.append(dict(params=params, c=c, cp=c.init_control_params, obs=obs, info=info, state=state,
-                         key=cr.PRNGKey(seed + 300 + e), reset_key=cr.PRNGKey(seed + 400 + e)))
-    return inst
-
-
-def _batched(env, name, inst, N, lam, diag=True):
-    import covo_mpc_amd as cm
-    E, cp0 = len(inst), inst[0]["cp"]
-    if name == "mppi":
-        return cm.controllers.BatchedMPPIController(env, E, N, 32, float(lam), sigmas=cp0.sample_sigma, discount=cp0.discount,
-                                                    gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=DEV, compute_diag=diag)
-    return cm.controllers.BatchedCoVOController(env, E, N, 32, float(lam), discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                                sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV,
-                                                mode="offline" if name == "covo-offline" else "online", compute_diag=diag)
 
 
 _TABLES = {}
@@ -249,9 +191,9 @@ def test_batched_diag_equals_single(name, N, E):
     """Row e of the batched controller's `diag` is torch.equal to the single controller's diagnostics on instance e alone, over
     three steps (eager call, capture, replay)."""
     lam = "0.01"
-    env = _env(randomizer=True, task="tracking")
-    inst = _instances(env, name, N, lam, E)
-    b = _batched(env, name, inst, N, lam)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, name, N, lam, E, compute_diag=True)
+    b = batched_controller(env, name, inst, len(inst), N, lam, compute_diag=True)
     b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
     if name == "covo-offline":
         b.set_tables(*_offline_tables(inst, E))
@@ -275,13 +217,6 @@ def test_batched_diag_equals_single(name, N, E):
     b.core.close()
 
 
-def _set_time(ep, e, t):
-    """Instance e of a batched episode starts at step t (true and noisy state: the counter's int32 bits)."""
-    bits = torch.tensor([t], dtype=torch.int32, device=DEV).view(torch.float32)
-    ep.true[e, ST_TIME:ST_TIME + 1] = bits
-    ep.noisy[e, ST_TIME:ST_TIME + 1] = bits
-
-
 @pytest.mark.parametrize("name", ["covo-online", "mppi"])
 def test_closed_loop_batched_diag_log(name):
     """run_episode for 40 steps on 3 instances, instance 1 starting at step 285 (frozen-reward tail from `time + k >= 300`, then
@@ -297,8 +232,8 @@ def test_closed_loop_batched_diag_log(name):
     the reset row instead, the maximum would lie IN that row, not before it: the finding is recorded in DESIGN 4.7."""
     from covo_mpc_amd.envs.quadrotor import BatchedDeviceEpisode
     E, N, lam, T = 3, 1024, "0.01", 40
-    env = _env(randomizer=True, task="tracking")
-    inst = _instances(env, name, N, lam, E, seed=3)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, name, N, lam, E, seed=3, compute_diag=True)
     for i in inst:
         i["c"].core.close()
     keys = np.stack([np.asarray(cr.PRNGKey(50 + e)) for e in range(E)])
@@ -306,9 +241,9 @@ def test_closed_loop_batched_diag_log(name):
     params = [i["params"] for i in inst]
     out = {}
     for kind in ("episode", "steps", "plain"):
-        b = _batched(env, name, inst, N, lam, diag=kind != "plain")
+        b = batched_controller(env, name, inst, len(inst), N, lam, compute_diag=kind != "plain")
         ep = BatchedDeviceEpisode(env, keys, params, (b.core.lib, b.core.h), b.core.device)
-        _set_time(ep, 1, 285)
+        set_time(ep, 1, 285)
         if kind == "steps":
             b.bind_episode(ep)
             ks, rows = rngs.copy(), []
@@ -360,11 +295,11 @@ def test_closed_loop_single_diag_log(monkeypatch):
     __call__ + episode.step; the [.., 4] log equals the log without diagnostics."""
     from covo_mpc_amd.envs.quadrotor import DeviceEpisode
     monkeypatch.setenv("COVO_GRAPH", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     T, N = 40, 2048
     out = {}
     for kind in ("episode", "steps", "plain"):
-        c, cp, _, _, _, params = _controller(env, "covo-online", N, "0.01", diag=kind != "plain")
+        c, cp, _, _, _, params = single_controller(env, "covo-online", N, compute_diag=kind != "plain")
         c.alias_outputs = True
         ep = DeviceEpisode(env, cr.PRNGKey(21), params, (c.core.lib, c.core.h), c.core.device)
         cp = c.reset(ep.state0, params, cp, cr.PRNGKey(22))
@@ -395,9 +330,9 @@ def test_attach_detach(name, N, monkeypatch):
     """Diagnostics turned on after the graph was captured, off again, on with another buffer: every call returns correct values,
     the device status stays 0, the outputs stay bit-identical to a handle that never had them."""
     monkeypatch.setenv("COVO_GRAPH", "1")
-    env = _env()
-    ca, cpa, obs, info, state, params = _controller(env, name, N, "0.01", diag=False)
-    cb, cpb = _controller(env, name, N, "0.01", diag=False)[:2]
+    env = quad_env(task="tracking_zigzag")
+    ca, cpa, obs, info, state, params = single_controller(env, name, N)
+    cb, cpb = single_controller(env, name, N)[:2]
     lib, h = ca.core.lib, ca.core.h
     bufs = [torch.full((1, 8), -1.0, device=DEV), torch.full((1, 8), -1.0, device=DEV)]
     # steps 0-2 off (eager, capture, replay), 3-4 on (buffer 0), 5-6 off, 7-9 on (buffer 1)
@@ -433,7 +368,7 @@ def test_sharded_step_with_diag_is_refused():
     from covo_mpc_amd.controllers._core import SamplingCore
     from covo_mpc_amd.dynamics.dataclass import as_device_state
     core = SamplingCore(4096, 32, 0.01, 1.0, device=DEV, use_graph=False, compute_diag=True)
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     obs, info, state = env.reset(cr.PRNGKey(3), params)
     dstate = as_device_state(info["noisy_state"], DEV)

@@ -21,8 +21,8 @@ import covo_mpc_amd as cm  # noqa: E402
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
+from tests.gpu_support import DEV, finite_step, quad_env, single_controller  # noqa: E402
 
-DEV = "cuda:0"
 BAR = 1e-5
 
 
@@ -149,28 +149,6 @@ def test_selector_refuses_bad_arguments(core):
 
 
 # ---- the steps ------------------------------------------------------------------------------------------------------------------
-def _env(randomizer=False, task="tracking_zigzag"):
-    return cm.envs.Quad3D(task=task, obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-_OFFLINE = {}
-
-
-def _controller(env, name, N, seed=1, **kw):
-    """A single controller at the start of an episode: (controller, control params, obs, info, state, params)."""
-    c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam0.01", device=DEV, compute_info=False, **kw)
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(seed), params)
-    cp = c.init_control_params
-    if name == "covo-offline":  # the Sigma table depends on neither N nor the update: built once
-        if seed not in _OFFLINE:
-            t = c.reset(state, params, cp, cr.PRNGKey(seed + 1))
-            _OFFLINE[seed] = (t.a_cov_offline, t.a_chol_offline)
-        cp = cp.replace(a_cov_offline=_OFFLINE[seed][0], a_chol_offline=_OFFLINE[seed][1])
-    return c, cp, obs, info, state, params
-
-
 def elite_mean_ref(core, K, start, gamma_mean):
     """The fp64 elite update on the core's own fp32 costs and actions around `start` [32, 4] (fp64) -> (mean, elites, a [N, H, 4])."""
     a = core.a.permute(1, 0, 2).contiguous().cpu().numpy().astype(np.float64)
@@ -188,9 +166,9 @@ def test_one_step_three_modes(name, N, gamma_mean, monkeypatch):
     new mean is the fp64 elite average (gamma_mean = 0.7: blended with the shifted old mean), the diagnostics count K."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     K = N // 8
-    env = _env()
-    ca, cpa, obs, info, state, params = _controller(env, name, N, elite=K, compute_diag=True)
-    cb, cpb = _controller(env, name, N)[:2]
+    env = quad_env(task="tracking_zigzag")
+    ca, cpa, obs, info, state, params = single_controller(env, name, N, elite=K, compute_diag=True)
+    cb, cpb = single_controller(env, name, N)[:2]
     cpa, cpb = cpa.replace(gamma_mean=gamma_mean), cpb.replace(gamma_mean=gamma_mean)
     k_act = cr.PRNGKey(3)
     ua, cpa2, ia = ca(obs, state, params, k_act, cpa, info)
@@ -222,9 +200,9 @@ def test_one_step_mppi_covariance_refit(monkeypatch):
     """MPPI with gamma_sigma = 0.3, N = 1 024, K = 128: mean and a_cov against the fp64 refit to the elites."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     N, K = 1024, 128
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     for diag in (False, True):
-        c, cp, obs, info, state, params = _controller(env, "mppi", N, elite=K, compute_diag=diag)
+        c, cp, obs, info, state, params = single_controller(env, "mppi", N, elite=K, compute_diag=diag)
         cp = cp.replace(gamma_sigma=0.3)
         _, cp2, _ = c(obs, state, params, cr.PRNGKey(3), cp, info)
         torch.cuda.synchronize()
@@ -249,8 +227,8 @@ def test_stage1_sample_tail_and_second_grid_trip(N, K, gamma_sigma, monkeypatch)
     N = 65 600: 1 025 groups on the 256 x 4 waves of the capped grid -- one wave takes a second trip, over a full group; once more
     with gamma_sigma = 0.3 for the second-moment records.  Mean, a_cov and diagnostics against the fp64 elite update (K^2 < 2^24)."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, "mppi", N, elite=K, compute_diag=True)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "mppi", N, elite=K, compute_diag=True)
     cp = cp.replace(gamma_sigma=gamma_sigma)
     _, cp2, _ = c(obs, state, params, cr.PRNGKey(3), cp, info)
     torch.cuda.synchronize()
@@ -275,10 +253,10 @@ def test_one_elite_is_the_best_sample_and_all_elites_the_plain_average(name, mon
     """K = 1, gamma_mean = 1: a_mean is a[:, n*, :] bit for bit, n* the arbiter's arb_best on the same step.  K = N: the plain average."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     N = 1024
-    env = _env()
-    c1, cp, obs, info, state, params = _controller(env, name, N, elite=1)
-    cn = _controller(env, name, N, elite=N)[0]
-    cg = _controller(env, name, N, update="guarded")[0]
+    env = quad_env(task="tracking_zigzag")
+    c1, cp, obs, info, state, params = single_controller(env, name, N, elite=1)
+    cn = single_controller(env, name, N, elite=N)[0]
+    cg = single_controller(env, name, N, update="guarded")[0]
     k_act = cr.PRNGKey(3)
     _, cp1, _ = c1(obs, state, params, k_act, cp, info)
     _, cpn, _ = cn(obs, state, params, k_act, cp, info)
@@ -300,12 +278,12 @@ def test_one_elite_is_the_best_sample_and_all_elites_the_plain_average(name, mon
 def test_graph_equals_eager(name, monkeypatch):
     """Three closed-loop steps (the graph handle: eager call, capture, replay): mean, selector row and diagnostics bit-identical."""
     N, K = 1024, 128
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     monkeypatch.setenv("COVO_GRAPH", "1")
-    cg, cpg, obs, info, state, params = _controller(env, name, N, elite=K, compute_diag=True)
+    cg, cpg, obs, info, state, params = single_controller(env, name, N, elite=K, compute_diag=True)
     monkeypatch.delenv("COVO_GRAPH")
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    ce, cpe = _controller(env, name, N, elite=K, compute_diag=True)[:2]
+    ce, cpe = single_controller(env, name, N, elite=K, compute_diag=True)[:2]
     assert cg.core.uses_graph and not ce.core.uses_graph
     key = cr.PRNGKey(11)
     for step in range(3):
@@ -327,7 +305,7 @@ def test_batched_online_equals_single():
     """E = 3, N = 256, K = 32: row e of the selector rows, a_mean and a_cov is torch.equal to the single controller on instance e, over
     three steps (eager call, capture, replay)."""
     E, N, K = 3, 256, 32
-    env = _env(randomizer=True, task="tracking")
+    env = quad_env(task="tracking", randomizer=True)
     inst = []
     for e in range(E):
         params = env.sample_params(cr.PRNGKey(100 + e))
@@ -369,10 +347,10 @@ def test_three_passes_select_again_in_every_pass(name, graph, monkeypatch):
     costs around the mean the pass before committed; iter_cost_min holds every pass's true minimum."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
     N, K = 256, 32
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     cs = []
     for j in (1, 2, 3):
-        c, cp, obs, info, state, params = _controller(env, name, N, elite=K, iters=j)
+        c, cp, obs, info, state, params = single_controller(env, name, N, elite=K, iters=j)
         cs.append(c)
     cp = cp.replace(gamma_mean=0.7)
     key = cr.PRNGKey(6)
@@ -402,9 +380,9 @@ def test_guarded_arbiter_sees_the_elite_mean(monkeypatch):
     without the arbiter."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     N, K = 1024, 128
-    env = _env()
-    cg, cp, obs, info, state, params = _controller(env, "covo-online", N, elite=K, update="guarded", compute_plan=True)
-    ct = _controller(env, "covo-online", N, elite=K, compute_plan=True)[0]
+    env = quad_env(task="tracking_zigzag")
+    cg, cp, obs, info, state, params = single_controller(env, "covo-online", N, elite=K, update="guarded", compute_plan=True)
+    ct = single_controller(env, "covo-online", N, elite=K, compute_plan=True)[0]
     k_act = cr.PRNGKey(3)
     _, cpg, ig = cg(obs, state, params, k_act, cp, info)
     _, cpt, it = ct(obs, state, params, k_act, cp, info)
@@ -422,11 +400,11 @@ def test_closed_loop_run_episode(monkeypatch):
     chain equal a Python loop of single steps bit for bit; every row's ess is K."""
     from covo_mpc_amd.envs.quadrotor import DeviceEpisode
     monkeypatch.setenv("COVO_GRAPH", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     T, N, K = 12, 1024, 64
     out = {}
     for kind in ("episode", "steps"):
-        c, cp, _, _, _, params = _controller(env, "mppi", N, elite=K, compute_diag=True)
+        c, cp, _, _, _, params = single_controller(env, "mppi", N, elite=K, compute_diag=True)
         c.alias_outputs = True
         ep = DeviceEpisode(env, cr.PRNGKey(21), params, (c.core.lib, c.core.h), c.core.device)
         cp = c.reset(ep.state0, params, cp, cr.PRNGKey(22))
@@ -458,13 +436,6 @@ def test_closed_loop_run_episode(monkeypatch):
 
 
 # ---- 5. refusals ------------------------------------------------------------------------------------------------------------------
-def _finite_step(core, pc, args):
-    _lib.check(core.lib.covo_mpc_step(core.h, C.byref(pc), C.byref(args), 7, 9, None, core.stream()), "covo_mpc_step")
-    torch.cuda.synchronize()
-    assert core.device_status() == 0
-    assert bool(torch.isfinite(core._bufs["a_mean"]).all())
-
-
 def test_refusals_single_step():
     """A sharded step, K > N, elite next to an ESS floor, n_inst outside (0, 64], K < 0: an error naming the condition, nothing
     launched, the handle works after."""
@@ -472,7 +443,7 @@ def test_refusals_single_step():
     from covo_mpc_amd.dynamics.dataclass import as_device_state
     N = 4096
     core = SamplingCore(N, 32, 0.01, 1.0, device=DEV, use_graph=False, elite=64)
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     obs, info, state = env.reset(cr.PRNGKey(3), params)
     dstate = as_device_state(info["noisy_state"], DEV)
@@ -490,28 +461,28 @@ def test_refusals_single_step():
         step()
     args.partial_out = None
     assert core.device_status() == 0
-    _finite_step(core, pc, args)
+    finite_step(core, pc, args)
     attach(N + 1)
     with pytest.raises(_lib.CovoError, match=r"K=4097 .*outside \[1, n_samples = 4096\]"):
         step()
     attach(64)
-    _finite_step(core, pc, args)
+    finite_step(core, pc, args)
     lam = torch.zeros(_lib.COVO_LAM_FLOATS, device=DEV)
     _lib.check(core.lib.covo_set_step_ess_floor(core.h, 32.0, _lib.ptr(lam), 1), "covo_set_step_ess_floor")
     with pytest.raises(_lib.CovoError, match=r"elite-set update.*together with the ESS floor"):
         step()
     _lib.check(core.lib.covo_set_step_ess_floor(core.h, 0.0, None, 0), "covo_set_step_ess_floor")
-    _finite_step(core, pc, args)
+    finite_step(core, pc, args)
     for n_inst in (0, 65):
         assert core.lib.covo_set_step_elite(core.h, 64, _lib.ptr(core.elite_rows), n_inst) != 0
         assert b"n_inst" in core.lib.covo_last_error()
     assert core.lib.covo_set_step_elite(core.h, -1, None, 0) != 0 and b"K=-1" in core.lib.covo_last_error()
-    _finite_step(core, pc, args)  # (the refused setters changed nothing)
+    finite_step(core, pc, args)  # (the refused setters changed nothing)
     check_row(core.elite_rows[0].cpu().numpy(), core.cost.cpu().numpy(), 64, "after the refusals")
     # detached: the same handle steps with the softmax update again
     attach(0)
     core.elite_rows.zero_()
-    _finite_step(core, pc, args)
+    finite_step(core, pc, args)
     assert not bool(core.elite_rows.any())
     core.close()
 
@@ -520,7 +491,7 @@ def test_refusal_batched_mode():
     """covo_mpc_step_batched_mode (env-batched MPPI: one fused launch) with elite attached to the handle: CovoError naming it;
     detached, the same controller steps."""
     E, N = 2, 256
-    env = _env(randomizer=True, task="tracking")
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(100 + e)) for e in range(E)]
     states = [env.reset(cr.PRNGKey(200 + e), p) for e, p in enumerate(params)]
     c0, cp0 = cm.envs.get_controller(env, "mppi", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
@@ -542,8 +513,8 @@ def test_refusal_batched_mode():
 
 def test_python_refusals_on_the_device():
     """The kernel-by-kernel path raises NotImplementedError with elite attached."""
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, "covo-offline", 256, elite=32)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-offline", 256, elite=32)
     c.materialize_eps = True
     with pytest.raises(NotImplementedError, match="elite=32"):
         c(obs, state, params, cr.PRNGKey(3), cp, info)

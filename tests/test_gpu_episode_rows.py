@@ -19,21 +19,7 @@ from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd._lib import CovoError, check, ptr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
-
-DEV = "cuda:0"
-H = 32
-
-
-def _env(randomizer=False):
-    return cm.envs.Quad3D(task="tracking_zigzag", obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-def bits(x):
-    """float32 array or device tensor -> its uint32 words (numpy)"""
-    x = x.detach().cpu().numpy() if torch.is_tensor(x) else np.asarray(x)
-    assert x.dtype == np.float32
-    return np.ascontiguousarray(x).view(np.uint32)
+from tests.gpu_support import DEV, H, bits, quad_env  # noqa: E402
 
 
 def same_bits(got, want, where):
@@ -88,7 +74,7 @@ def test_single_covo_online_logs_equal_the_python_loop(graph, monkeypatch):
     """N = 256, ess_min = 8, iters = 3, m = 3, gamma = 0.2, the matrix log on; 7 steps as 2 + 5.  The second segment's iteration log
     starts 2 x 3 floats into the buffer: 24 bytes, the float-by-float path at an address that is not 16-byte aligned."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     m, T = 3, 7
 
     def rows_of(core, ci):
@@ -125,7 +111,7 @@ def test_single_covo_online_logs_equal_the_python_loop(graph, monkeypatch):
 
 
 def test_single_episode_without_log_post_cov_keeps_the_side_row_only():
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     c, cp, params = _single(env, "covo-online", 256, compute_post_cov=True)
     ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(21), params, (c.core.lib, c.core.h), c.core.device)
     cp = c.reset(ep.state0, params, cp, cr.PRNGKey(22))
@@ -141,7 +127,7 @@ def test_single_episode_without_log_post_cov_keeps_the_side_row_only():
 
 # ---- 2. single MPPI: a ragged N, the elite set, width 5 ----------------------------------------------------------------------------
 def test_single_mppi_elite_and_iteration_logs_equal_the_python_loop():
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     T = 5
 
     def rows_of(core, ci):
@@ -162,7 +148,7 @@ def test_single_mppi_elite_and_iteration_logs_equal_the_python_loop():
 
 # ---- 3. batched covo-online ----------------------------------------------------------------------------------------------------------
 def _batch_setup(E):
-    env = _env(randomizer=True)
+    env = quad_env(task="tracking_zigzag", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     rngs0 = np.stack([np.asarray(cr.PRNGKey(60 + e)) for e in range(E)])
@@ -270,7 +256,7 @@ def test_refusals_name_the_condition_and_a_detached_log_stays_untouched():
     check(lib.covo_set_episode_rows(h, _lib.COVO_EPLOG_SIGMA, ptr(rows), 8), "covo_set_episode_rows")
     fresh.close()
 
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     c, cp, params = _single(env, "mppi", 128, elite=8, iters=3)
     core = c.core
     lib, h = core.lib, core.h
@@ -313,7 +299,7 @@ def test_refusals_name_the_condition_and_a_detached_log_stays_untouched():
 
 # ---- 6. the batched driver function ------------------------------------------------------------------------------------------------------
 def test_eval_env_batched_returns_the_rows():
-    env = _env(randomizer=True)
+    env = quad_env(task="tracking_zigzag", randomizer=True)
     err, rows = cm.envs.quadrotor.eval_env_batched(env, 2, "N256_H32_lam0.01", n_steps=5, device=DEV, verbose=False, sigma_period=2,
                                                    sigma_adapt=0.1, iters=2, rows=True)
     assert err.shape == (2,) and sorted(rows) == ["iters", "post", "sigma"]

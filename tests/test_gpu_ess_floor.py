@@ -26,14 +26,10 @@ if not torch.cuda.is_available():
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
+from tests.gpu_support import DEV, finite_step, quad_env, single_controller  # noqa: E402
+from tests.oracle_support import rel_err_scalar  # noqa: E402
 
-DEV = "cuda:0"
-ST_TIME = 25
 BAR_ROOT, BAR_ESS, BAR_MEAN, MAX_SENS = 1e-4, 3e-5, 1e-5, 50.0
-
-
-def rel_err(x, ref):
-    return abs(float(x) - float(ref)) / max(abs(float(ref)), 1.0)
 
 
 def ess64(cost_f32, lam, exact_inverse=False):
@@ -58,7 +54,7 @@ def check_row(row, cost, lam0, ess_min, where):
     lam_eff, inv, e0, evals = (np.float32(v) for v in row)
     ref0 = ess64(cost, lam0)
     assert 1.0 <= evals <= 64.0, (where, evals)
-    assert rel_err(e0, ref0) <= BAR_ESS, (where, e0, ref0)
+    assert rel_err_scalar(e0, ref0) <= BAR_ESS, (where, e0, ref0)
     assert inv == np.float32(1.0) / lam_eff, (where, inv, lam_eff)
     active = lam_eff != lam0
     # the fp32 decision may differ from the fp64 one only within the ESS bar of the threshold
@@ -182,30 +178,6 @@ def test_solver_refuses_ess_min_outside_its_range(core):
 
 
 # ---- the steps ------------------------------------------------------------------------------------------------------------------
-def _env(randomizer=False, task="tracking_zigzag"):
-    import covo_mpc_amd as cm
-    return cm.envs.Quad3D(task=task, obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-_OFFLINE = {}
-
-
-def _controller(env, name, N, lam, ess_min=None, diag=False, seed=1):
-    """A single controller at the start of an episode: (controller, control params, obs, info, state, params)."""
-    import covo_mpc_amd as cm
-    c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam}", device=DEV, compute_info=False, compute_diag=diag, ess_min=ess_min)
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(seed), params)
-    cp = c.init_control_params
-    if name == "covo-offline":  # the Sigma table depends on neither N nor lambda: built once
-        if seed not in _OFFLINE:
-            t = c.reset(state, params, cp, cr.PRNGKey(seed + 1))
-            _OFFLINE[seed] = (t.a_cov_offline, t.a_chol_offline)
-        cp = cp.replace(a_cov_offline=_OFFLINE[seed][0], a_chol_offline=_OFFLINE[seed][1])
-    return c, cp, obs, info, state, params
-
-
 def _mean_ref(c, cp_before, lam, gamma_sigma=0.0):
     """The fp64 update on the step's own fp32 costs and actions at temperature `lam` -> (mean [32, 4], a_cov or None)."""
     a = c.core.a.permute(1, 0, 2).contiguous().cpu().numpy().astype(np.float64)  # (N, H, 4)
@@ -226,9 +198,9 @@ def test_one_step_three_modes(name, N, monkeypatch):
     solved temperature meets the floor, the new mean is the fp64 update at lam_eff, the diagnostics' ess is the floor."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     lam0, ess_min = "0.01", N / 8
-    env = _env()
-    ca, cpa, obs, info, state, params = _controller(env, name, N, lam0, ess_min=ess_min, diag=True)
-    cb, cpb = _controller(env, name, N, lam0)[:2]
+    env = quad_env(task="tracking_zigzag")
+    ca, cpa, obs, info, state, params = single_controller(env, name, N, lam=lam0, ess_min=ess_min, compute_diag=True)
+    cb, cpb = single_controller(env, name, N, lam=lam0)[:2]
     k_act = cr.PRNGKey(3)
     ua, cpa2, ia = ca(obs, state, params, k_act, cpa, info)
     ub, cpb2, ib = cb(obs, state, params, k_act, cpb, info)
@@ -245,9 +217,9 @@ def test_one_step_three_modes(name, N, monkeypatch):
     print(f"  {name} N={N}: mean err {err:.2e}, diag ess {d[0]:.6g} (floor {ess_min:g})")
     assert err <= BAR_MEAN, (name, N, err)
     if active:
-        assert rel_err(d[0], ess_min) <= BAR_ESS, (name, N, d[0], ess_min)
+        assert rel_err_scalar(d[0], ess_min) <= BAR_ESS, (name, N, d[0], ess_min)
         assert not torch.equal(cpa2.a_mean, cpb2.a_mean)
-    assert rel_err(d[0], ess64(cost, row[0])) <= BAR_ESS
+    assert rel_err_scalar(d[0], ess64(cost, row[0])) <= BAR_ESS
     assert ca.core.device_status() == 0
     ca.core.close()
     cb.core.close()
@@ -257,8 +229,8 @@ def test_one_step_mppi_covariance_adaptation(monkeypatch):
     """MPPI with gamma_sigma = 0.3: mean and a_cov against the fp64 update at lam_eff."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     N, lam0, ess_min = 1024, "0.01", 128.0
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, "mppi", N, lam0, ess_min=ess_min, diag=True)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "mppi", N, lam=lam0, ess_min=ess_min, compute_diag=True)
     cp = cp.replace(gamma_sigma=0.3)
     _, cp2, _ = c(obs, state, params, cr.PRNGKey(3), cp, info)
     torch.cuda.synchronize()
@@ -271,7 +243,7 @@ def test_one_step_mppi_covariance_adaptation(monkeypatch):
     print(f"  mppi gamma_sigma=0.3: mean err {e_mean:.2e}, a_cov err {e_cov:.2e}")
     assert e_mean <= BAR_MEAN and e_cov <= BAR_MEAN, (e_mean, e_cov)
     if active:
-        assert rel_err(c.core.diag[0, 0].item(), ess_min) <= BAR_ESS
+        assert rel_err_scalar(c.core.diag[0, 0].item(), ess_min) <= BAR_ESS
     c.core.close()
 
 
@@ -281,8 +253,8 @@ def test_inactive_floor(name, monkeypatch):
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
     N, lam0 = 1024, "5.0"
     ess_min = N / 64
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, name, N, lam0, ess_min=ess_min)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, name, N, lam=lam0, ess_min=ess_min)
     _, cp2, ci = c(obs, state, params, cr.PRNGKey(3), cp, info)
     torch.cuda.synchronize()
     cost = c.core.cost.cpu().numpy()
@@ -300,12 +272,12 @@ def test_inactive_floor(name, monkeypatch):
 def test_graph_equals_eager(name, monkeypatch):
     """Three closed-loop steps (the graph handle: eager call, capture, replay): mean, solver row and diagnostics bit-identical."""
     N, lam0, ess_min = 1024, "0.01", 128.0
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     monkeypatch.setenv("COVO_GRAPH", "1")
-    cg, cpg, obs, info, state, params = _controller(env, name, N, lam0, ess_min=ess_min, diag=True)
+    cg, cpg, obs, info, state, params = single_controller(env, name, N, lam=lam0, ess_min=ess_min, compute_diag=True)
     monkeypatch.delenv("COVO_GRAPH")
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    ce, cpe = _controller(env, name, N, lam0, ess_min=ess_min, diag=True)[:2]
+    ce, cpe = single_controller(env, name, N, lam=lam0, ess_min=ess_min, compute_diag=True)[:2]
     assert cg.core.uses_graph and not ce.core.uses_graph
     key = cr.PRNGKey(11)
     for step in range(3):
@@ -331,7 +303,7 @@ def test_batched_online_equals_single():
     three steps (eager call, capture, replay)."""
     import covo_mpc_amd as cm
     E, N, lam0 = 3, 256, "1.0"  # (at lam0 = 0.01 every instance's ESS is 1.00..: no floor would separate them)
-    env = _env(randomizer=True, task="tracking")
+    env = quad_env(task="tracking", randomizer=True)
     inst = []
     for e in range(E):
         params = env.sample_params(cr.PRNGKey(100 + e))
@@ -390,11 +362,11 @@ def test_closed_loop_run_episode(monkeypatch):
     holds the floor; log, diagnostics, final mean and key chain equal a Python loop of single steps bit for bit."""
     from covo_mpc_amd.envs.quadrotor import DeviceEpisode
     monkeypatch.setenv("COVO_GRAPH", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     T, N, ess_min = 40, 1024, 32.0
     out = {}
     for kind in ("episode", "steps"):
-        c, cp, _, _, _, params = _controller(env, "mppi", N, "0.01", ess_min=ess_min, diag=True)
+        c, cp, _, _, _, params = single_controller(env, "mppi", N, ess_min=ess_min, compute_diag=True)
         c.alias_outputs = True
         ep = DeviceEpisode(env, cr.PRNGKey(21), params, (c.core.lib, c.core.h), c.core.device)
         cp = c.reset(ep.state0, params, cp, cr.PRNGKey(22))
@@ -428,20 +400,13 @@ def test_closed_loop_run_episode(monkeypatch):
 
 
 # ---- 7. refusals ------------------------------------------------------------------------------------------------------------------
-def _finite_step(core, pc, args):
-    _lib.check(core.lib.covo_mpc_step(core.h, C.byref(pc), C.byref(args), 7, 9, None, core.stream()), "covo_mpc_step")
-    torch.cuda.synchronize()
-    assert core.device_status() == 0
-    assert bool(torch.isfinite(core._bufs["a_mean"]).all())
-
-
 def test_refusals_single_step():
     """A sharded step, ess_min > N / 2 and ess_min < 1: CovoError naming the condition, nothing launched, the handle works after."""
     from covo_mpc_amd.controllers._core import SamplingCore
     from covo_mpc_amd.dynamics.dataclass import as_device_state
     N = 4096
     core = SamplingCore(N, 32, 0.01, 1.0, device=DEV, use_graph=False, ess_min=64.0)
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     obs, info, state = env.reset(cr.PRNGKey(3), params)
     dstate = as_device_state(info["noisy_state"], DEV)
@@ -458,14 +423,14 @@ def test_refusals_single_step():
         step()
     args.partial_out = None
     assert core.device_status() == 0
-    _finite_step(core, pc, args)
+    finite_step(core, pc, args)
     for bad, pat in ((N / 2 + 1, r"ess_min=2049 .*outside \[1, n_samples / 2"), (0.5, r"ess_min=0\.5 .*outside \[1, n_samples / 2")):
         _lib.check(core.lib.covo_set_step_ess_floor(core.h, bad, _lib.ptr(core.lam_eff), 1), "covo_set_step_ess_floor")
         with pytest.raises(_lib.CovoError, match=pat):
             step()
         assert core.device_status() == 0
         _lib.check(core.lib.covo_set_step_ess_floor(core.h, 64.0, _lib.ptr(core.lam_eff), 1), "covo_set_step_ess_floor")
-        _finite_step(core, pc, args)
+        finite_step(core, pc, args)
     assert core.lam_eff[0, 0].item() >= float(np.float32(0.01))
     # a negative or non-finite floor is refused by the setter itself
     for bad in (-1.0, float("nan"), float("inf")):
@@ -478,7 +443,7 @@ def test_refusal_batched_mode():
     detached, the same controller steps."""
     import covo_mpc_amd as cm
     E, N = 2, 256
-    env = _env(randomizer=True, task="tracking")
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(100 + e)) for e in range(E)]
     states = [env.reset(cr.PRNGKey(200 + e), p) for e, p in enumerate(params)]
     c0, cp0 = cm.envs.get_controller(env, "mppi", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)

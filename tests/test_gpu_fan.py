@@ -25,25 +25,11 @@ from covo_mpc_amd.dynamics.dataclass import as_device_state  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from tests.conftest import make_problem  # noqa: E402
-from tests.test_gpu_models import DP, disturb_key, params_c  # noqa: E402
-from tests.test_gpu_parity import DEV, dev_state, sample_actions, to_stripes  # noqa: E402
-from tests.test_gpu_trace import _batched, _env, _start  # noqa: E402
+from tests.gpu_support import (DEV, DP, H, POS_BAR, batched_controller, dev_state, disturb_key, params_c, quad_env,  # noqa: E402
+                               sample_actions, shared_vector, split_rows, start_episode, to_stripes, want_idx)
+from tests.oracle_support import oracle_params, oracle_state  # noqa: E402
 
-H = 32
 FF = _lib.COVO_FAN_FLOATS
-POS_BAR = 2e-5
-
-
-def split_rows(rows):
-    """fan rows [K, 100] (device tensor) -> (cost [K] f32, idx [K] i32, words 2..3 [K, 2], pos [K, H, 3]) as numpy"""
-    r = rows.detach().cpu().numpy()
-    return r[:, 0].copy(), np.ascontiguousarray(r[:, 1]).view(np.int32).copy(), r[:, 2:4], r[:, 4:].reshape(-1, H, 3)
-
-
-def want_idx(N, K, idx=None):
-    if idx is None:
-        return np.asarray([(s * N) // K for s in range(K)], dtype=np.int32)
-    return np.clip(np.asarray(idx, dtype=np.int64), 0, N - 1).astype(np.int32)
 
 
 def check_rows(rows, N, K, idx, cost_dev, poses, where):
@@ -127,20 +113,6 @@ def _controller(env, name, N, fan, extras):
     return c, c.init_control_params
 
 
-def _oracle_state(ns):
-    return R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
-                   vel_tar=ns.vel_tar, acc_tar=ns.acc_tar, time=ns.time, pos_traj=ns.pos_traj, vel_traj=ns.vel_traj,
-                   acc_traj=ns.acc_traj).astype(np.float64)
-
-
-def _shared_vector(env, name, params, k_act):
-    """the one shared vector of a step's sample rollouts under the gaussian model: MPPI's draw, 0 for CoVO (deterministic)"""
-    if name != "mppi":
-        return np.zeros(3)
-    step_key = cr.split(cr.split(k_act)[0])[1]
-    return np.asarray(env.rollout_disturbance(step_key, params, deterministic=False), dtype=np.float64)
-
-
 @pytest.mark.parametrize("extras", [False, True], ids=["fan", "fan+plan+diag+ess"])
 @pytest.mark.parametrize("graph", ["graph", "eager"])
 @pytest.mark.parametrize("name,N", [("mppi", 256), ("covo-offline", 256), ("covo-online", 256), ("covo-online", 1024)])
@@ -153,11 +125,11 @@ def test_step_fan_on_every_path(name, N, graph, extras, monkeypatch):
     K = 8
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
     monkeypatch.setenv("COVO_SHARED_DEVICE", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     ca, cpa = _controller(env, name, N, K, extras)
     cb, cpb = _controller(env, name, N, None, extras)
     assert ca.core.shared_device and ca.core.uses_graph == (graph == "graph")
-    cpa, obs, info, state, params = _start(env, ca, cpa, name)
+    cpa, obs, info, state, params = start_episode(env, ca, cpa, name)
     if name == "covo-offline":
         cpb = cpb.replace(a_cov_offline=cpa.a_cov_offline, a_chol_offline=cpa.a_chol_offline)
     key = cr.PRNGKey(11)
@@ -173,7 +145,7 @@ def test_step_fan_on_every_path(name, N, graph, extras, monkeypatch):
         assert not any(k.startswith("fan_") for k in ib)
         assert torch.equal(ia["fan_idx"].cpu(), ca.core.fan_idx[0].cpu()), where
         a64 = ca.core.a.permute(1, 0, 2).contiguous().cpu().numpy().astype(np.float64)
-        _, poses = CO.rollout(_oracle_state(ns), R.Params().fp32(), a64, 1.0, _shared_vector(env, name, params, k_act),
+        _, poses = CO.rollout(oracle_state(ns), R.Params().fp32(), a64, 1.0, shared_vector(env, name, params, k_act),
                               dtype=np.float64, want_poses=True)
         check_rows(ca.core.fan[0], N, K, None, ca.core.cost, poses, where)
         assert torch.equal(ua, ub) and torch.equal(cpa.a_mean, cpb.a_mean) and torch.equal(cpa.a_cov, cpb.a_cov), where
@@ -193,9 +165,8 @@ def test_batched_fan_equals_single(name):
     """E = 2 domain-randomised instances, N = 256, K = 8, one step from a BatchedDeviceEpisode's states: controller.fan[e] equals the
     single controller's fan on instance e alone bit for bit, and instance 1's fan is the oracle's as in test 1."""
     import covo_mpc_amd as cm
-    from tests.test_gpu_batched_modes import _oracle_params
     N, E, K = 256, 2, 8
-    env = _env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     act_keys = np.stack([np.asarray(cr.PRNGKey(60 + e)) for e in range(E)])
@@ -211,7 +182,7 @@ def test_batched_fan_equals_single(name):
         singles.append(c.core.fan[0].clone())
         cp0 = c.init_control_params
         c.core.close()
-    b = _batched(env, name, cp0, E, N, compute_fan=K)
+    b = batched_controller(env, name, cp0, E, N, 0.01, compute_fan=K)
     assert tuple(b.fan.shape) == (E, K, FF) and tuple(b.core.fan_idx.shape) == (E, K)
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     b.bind_episode(ep)
@@ -228,7 +199,7 @@ def test_batched_fan_equals_single(name):
                  vel_tar=row[19:22], acc_tar=row[22:25], time=int(row[25:26].view(np.int32)[0]), pos_traj=s0.pos_traj,
                  vel_traj=s0.vel_traj, acc_traj=s0.acc_traj).astype(np.float64)
     a64 = b._a[e].permute(1, 0, 2).contiguous().cpu().numpy().astype(np.float64)
-    _, poses = CO.rollout(so, _oracle_params(params[e]), a64, 1.0, _shared_vector(env, name, params[e], act_keys[e]),
+    _, poses = CO.rollout(so, oracle_params(params[e]), a64, 1.0, shared_vector(env, name, params[e], act_keys[e]),
                           dtype=np.float64, want_poses=True)
     check_rows(b.fan[e], N, K, None, b._cost[e], poses, f"batched {name} instance {e}")
     assert b.core.device_status() == 0
@@ -240,7 +211,7 @@ def _episode_fan_log_single():
     """run_episode for 6 steps in two segments (4 + 2): read_fan() row k is what a Python loop of __call__ + env step collects, rows
     beyond n_steps stay untouched, and the env log and the trace are those of the same episode without the fan."""
     import covo_mpc_amd as cm
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     K, N, name = 8, 256, "mppi"
     got = {}
@@ -285,7 +256,7 @@ def _episode_fan_log_batched(name):
     """The same for E = 2 instances through covo_run_episode_batched[_mode]."""
     import covo_mpc_amd as cm
     N, E, K = 256, 2, 8
-    env = _env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     rngs0 = np.stack([np.asarray(cr.PRNGKey(60 + e)) for e in range(E)])
@@ -294,7 +265,7 @@ def _episode_fan_log_batched(name):
     c0.core.close()
     got = {}
     for mode in ("fused", "hand", "nofan"):
-        b = _batched(env, name, cp0, E, N, compute_plan=True, compute_fan=None if mode == "nofan" else K)
+        b = batched_controller(env, name, cp0, E, N, 0.01, compute_plan=True, compute_fan=None if mode == "nofan" else K)
         ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
         if mode == "hand":
             b.bind_episode(ep)
@@ -336,7 +307,7 @@ def test_episode_fan_log(which):
 
 def test_eval_env_batched_fan_shapes():
     import covo_mpc_amd as cm
-    env = _env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True)
     err, fan = cm.envs.quadrotor.eval_env_batched(env, 2, "N256_H32_lam0.01", n_steps=3, device=DEV, verbose=False, fan=4)
     assert err.shape == (2,) and fan["pos"].shape == (2, 3, 4, H, 3) and fan["cost"].shape == (2, 3, 4) and fan["idx"].shape == (2, 3, 4)
     assert np.all(np.isfinite(fan["pos"])) and np.all(np.isfinite(fan["cost"]))
@@ -363,7 +334,7 @@ def test_fan_refusals_leave_the_handle_usable():
     """Every refusal at the C boundary, matched on its message, nothing launched; afterwards the status is clean and a normal step
     is finite."""
     import covo_mpc_amd as cm
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     N, K = 256, 8
     c, _ = cm.envs.get_controller(env, "mppi", f"N{N}_H32_lam0.01", device=DEV, compute_info=False, compute_fan=K)
@@ -434,12 +405,12 @@ def test_fan_refusals_leave_the_handle_usable():
     core.close()
     # (e) a batched step with more instances than n_inst
     E = 3
-    envr = _env(task="tracking", randomizer=True)
+    envr = quad_env(task="tracking", randomizer=True)
     c0, _ = cm.envs.get_controller(envr, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
     cp0 = c0.init_control_params
     c0.core.close()
     for name in ("covo-online", "mppi"):
-        b = _batched(envr, name, cp0, E, N, compute_fan=K)
+        b = batched_controller(envr, name, cp0, E, N, 0.01, compute_fan=K)
         check(b.core.lib.covo_set_step_fan(b.core.h, ptr(b.fan), ptr(b.core.fan_idx), K, 2), "covo_set_step_fan")
         ps = [envr.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
         ep = cm.envs.BatchedDeviceEpisode(envr, [cr.PRNGKey(50 + e) for e in range(E)], ps, (b.core.lib, b.core.h), DEV)

@@ -27,70 +27,13 @@ from covo_mpc_amd.dynamics.dataclass import as_device_state  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from tests import iters_oracle as IO  # noqa: E402
+from tests.gpu_cases import _batched_iters_case, _definition_case, _run_episode_case, iters_controller, iters_start  # noqa: E402
+from tests.gpu_support import DEV, batched_controller, instances, quad_env  # noqa: E402
+from tests.oracle_support import rel_err  # noqa: E402
 
-DEV = "cuda:0"
-H = 32
 MEAN_BAR = 5e-6  # test_fused_step_ragged_sizes_and_warm_lambda's (ragged sizes)
 MEAN_BAR_4096 = 2e-6  # test_fused_step_equals_kernel_by_kernel's, which runs at N = 4096
 SIZES = [("mppi", 100), ("mppi", 1024), ("covo-offline", 40), ("covo-offline", 4096), ("covo-online", 256)]
-
-
-def _env(name, disturb="gaussian"):
-    task = "hovering" if name == "mppi" else "tracking_zigzag"
-    return cm.envs.Quad3D(task=task, enable_randomizer=False, disturb_type=disturb, disable_rollover_terminate=True,
-                          generate_noisy_state=True, device=DEV)
-
-
-def _controller(env, name, N, **kw):
-    c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam0.01", device=DEV, compute_info=False, **kw)
-    return c
-
-
-def next_raw_key(key):
-    """key_j from key_{j-1}: what is left of a raw key after a pass has taken act_key and step_key (covo.py:212,225)"""
-    return cr.split(cr.split(key)[0])[0]
-
-
-def ref_pass(c, name, env, params, dstate, cp, start, a_cov, raw_key):
-    """One pass of the definition from the core's own kernel-by-kernel calls on c.core, around the starting mean `start` [128] (and
-    MPPI's current blocks `a_cov`), with the raw key `raw_key` -> (new mean [128], a_cov the pass leaves)."""
-    core = c.core
-    pc = c._params_c(params)
-    tables = pc.disturb_kind in _lib.TABLE_DISTURB_KINDS
-    rng, act_key = cr.split(raw_key)
-    rng, step_key = cr.split(rng)
-    if name == "mppi":
-        Ls = core.cholesky(a_cov, 4, H)
-        core.randn(act_key)
-        core.noise_blockdiag(Ls, start)
-        if tables:
-            fs, tab = (0.0, 0.0, 0.0), core.disturb_table(pc, dstate.packed, key=step_key, key_mode=_lib.DISTURB_KEYS_SHARED, deterministic=False)
-        else:
-            fs, tab = env.rollout_disturbance(step_key, params, deterministic=False), None
-        core.rollout(dstate, pc, fs, False, f_steps=tab)
-        if cp.gamma_sigma != 0.0:
-            return core.update_cov(start, cp.gamma_mean, a_cov, cp.gamma_sigma)
-        return core.update(start, cp.gamma_mean), a_cov
-    if name == "covo-online":
-        tab_h = core.disturb_table(pc, dstate.packed, key=raw_key, key_mode=_lib.DISTURB_KEYS_HESSIAN, deterministic=True) if tables else None
-        R = core.hessian(dstate.packed, dstate, pc, start, f_steps=tab_h)
-        Sigma, L = core.sigma(R, cp.sample_sigma)
-        a_cov, L = Sigma[0], L[0]
-    else:
-        t = dstate.packed[25:26].view(torch.int32).long().clamp(0, cp.a_cov_offline.shape[0] - 1)
-        a_cov, L = cp.a_cov_offline.index_select(0, t)[0], cp.a_chol_offline.index_select(0, t)[0]
-    core.randn(act_key)
-    core.noise_gemm(L, start)
-    tab_r = core.disturb_table(pc, dstate.packed, key=step_key, key_mode=_lib.DISTURB_KEYS_SHARED, deterministic=True) if tables else None
-    core.rollout(dstate, pc, (0.0, 0.0, 0.0), False, f_steps=tab_r)
-    return core.update(start, cp.gamma_mean), a_cov
-
-
-def _start(env, c, name):
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(4), params)
-    cp = c.reset(state, params, c.init_control_params, cr.PRNGKey(5))
-    return cp, obs, info, state, params
 
 
 @pytest.mark.parametrize("graph", ["graph", "eager"])
@@ -98,10 +41,10 @@ def _start(env, c, name):
 def test_iters_1_is_todays_step(name, N, graph, monkeypatch):
     """A controller built with iters=1 against one built without the argument, 3 consecutive steps: everything torch.equal."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env(name)
-    ca, cb = _controller(env, name, N, iters=1), _controller(env, name, N)
+    env = quad_env(task="hovering" if name == "mppi" else "tracking_zigzag")
+    ca, cb = iters_controller(env, name, N, iters=1), iters_controller(env, name, N)
     assert ca.core.iter_cost_min is None and ca.core.uses_graph == (graph == "graph")
-    cp, obs, info, state, params = _start(env, cb, name)
+    cp, obs, info, state, params = iters_start(env, cb, name)
     cpa = cpb = cp
     key = cr.PRNGKey(6)
     for step in range(3):
@@ -116,55 +59,6 @@ def test_iters_1_is_todays_step(name, N, graph, monkeypatch):
         obs, state, _, _, info = env.step(k_step, state, ua.cpu().numpy(), params)
     assert ca.core.device_status() == 0
     ca.core.close(), cb.core.close()
-
-
-def _definition_case(name, N, k, graph, monkeypatch, disturb="gaussian", gamma_sigma=0.0):
-    monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env(name, disturb)
-    cs = [_controller(env, name, N, iters=j) for j in range(1, k + 1)]  # cs[j - 1]: the mean after pass j - 1
-    ref = _controller(env, name, N)
-    cp, obs, info, state, params = _start(env, ref, name)
-    if gamma_sigma:
-        cp = cp.replace(gamma_sigma=gamma_sigma)
-    key = cr.PRNGKey(6)
-    for step in range(3):  # call 1 eager, call 2 captures, call 3 replays
-        key, k_act, k_step = cr.split(key, 3)
-        dstate = as_device_state(info["noisy_state"], DEV)
-        outs = [c(obs, state, params, k_act, cp, info) for c in cs]
-        torch.cuda.synchronize()
-        start = ref.core.shift_mean(cp.a_mean.reshape(-1).contiguous())
-        a_cov = torch.cat([cp.a_cov[1:], cp.a_cov[-1:]], dim=0).contiguous() if name == "mppi" else None
-        raw = np.asarray(k_act)
-        for j in range(k):
-            where = f"{name} N={N} k={k} {graph} {disturb} gs={gamma_sigma} step {step} pass {j}"
-            mean_ref, cov_ref = ref_pass(ref, name, env, params, dstate, cp, start, a_cov, raw)
-            u, cpj, ij = outs[j]
-            core = cs[j].core
-            err = float((cpj.a_mean.reshape(-1) - mean_ref).abs().max())
-            print(f"{where}: |mean - kernel-by-kernel| = {err:.3g}, cost min {float(ref.core.cost.min()):.6g}")
-            assert torch.equal(core.a, ref.core.a), where
-            assert torch.equal(core.cost, ref.core.cost), where
-            assert err <= (MEAN_BAR_4096 if N == 4096 else MEAN_BAR), (where, err)
-            assert torch.equal(u, cpj.a_mean[0]), where
-            if name == "mppi" and gamma_sigma:
-                cerr = float((cpj.a_cov - cov_ref).abs().max())
-                print(f"{where}: |a_cov - kernel-by-kernel| = {cerr:.3g}")
-                assert cerr <= MEAN_BAR, (where, cerr)
-                assert not torch.equal(cpj.a_cov, a_cov), where  # the pass has adapted it
-            elif name != "covo-offline":
-                assert torch.equal(cpj.a_cov, cov_ref), where
-            for jj in range(max(j, 1), k):  # the log of every controller with more than j passes holds this pass's minimum in slot j
-                assert torch.equal(outs[jj][2]["iter_cost_min"][j], ref.core.cost.min()), (where, jj)
-            # the next pass starts from the mean (and blocks) the fused controller committed, with the advanced raw key
-            start = cpj.a_mean.reshape(-1).contiguous().clone()
-            a_cov = cpj.a_cov.contiguous().clone() if name == "mppi" else None
-            raw = next_raw_key(raw)
-        u, cp, _ = outs[k - 1]
-        cp = cp.replace(a_mean=cp.a_mean.clone(), a_cov=cp.a_cov.clone())
-        obs, state, _, _, info = env.step(k_step, state, u.cpu().numpy(), params)
-    for c in cs + [ref]:
-        assert c.core.device_status() == 0
-        c.core.close()
 
 
 @pytest.mark.parametrize("graph", ["graph", "eager"])
@@ -185,106 +79,10 @@ def test_k_pass_step_adapts_mppi_covariances_in_every_pass(graph, monkeypatch):
     _definition_case("mppi", 100, 2, graph, monkeypatch, gamma_sigma=0.2)
 
 
-def _benv():
-    return cm.envs.Quad3D(task="tracking", obs_type="quad_params", enable_randomizer=True, disturb_type="gaussian",
-                          disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-def _instances(env, name, N, E, **kw):
-    inst = []
-    for e in range(E):
-        params = env.sample_params(cr.PRNGKey(100 + e))
-        c = _controller(env, name, N, **kw)
-        obs, info, state = env.reset(cr.PRNGKey(200 + e), params)
-        rng = np.random.default_rng(1000 + e)
-        for q in range(2 + e % 4):
-            u = (0.3 * rng.standard_normal(4)).clip(-1, 1).astype(np.float32)
-            obs, state, _, _, info = env.step(cr.PRNGKey(5000 + 10 * e + q), state, u, params)
-        inst.append(dict(params=params, c=c, cp=c.init_control_params, obs=obs, info=info, state=state, key=cr.PRNGKey(300 + e),
-                         reset_key=cr.PRNGKey(400 + e)))
-    return inst
-
-
-def _batched(env, name, inst, N, **kw):
-    E, cp0 = len(inst), inst[0]["cp"]
-    if name == "mppi":
-        return cm.controllers.BatchedMPPIController(env, E, N, H, 0.01, sigmas=cp0.sample_sigma, discount=cp0.discount,
-                                                    gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=DEV, **kw)
-    return cm.controllers.BatchedCoVOController(env, E, N, H, 0.01, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                                sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV,
-                                                mode=name.split("-")[1], **kw)
-
-
-def _batched_iters_case(name, N, E, k):
-    """Instance e of the env-batched step with iters=k against a single-instance controller with iters=k stepped on instance e
-    alone, 3 steps (eager, capture, replay): torch.equal, the iteration log included."""
-    env = _benv()
-    inst = _instances(env, name, N, E, iters=k)
-    b = _batched(env, name, inst, N, iters=k)
-    b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
-    if name == "covo-offline":
-        tabs = []
-        for i in inst:
-            cp = i["c"].reset(i["state"], i["params"], i["c"].init_control_params, i["reset_key"])
-            i["cp"] = i["cp"].replace(a_cov_offline=cp.a_cov_offline, a_chol_offline=cp.a_chol_offline)
-            tabs.append((cp.a_cov_offline, cp.a_chol_offline))
-        b.set_tables(torch.stack([t[0] for t in tabs]), torch.stack([t[1] for t in tabs]))
-    assert tuple(b.iter_cost_min.shape) == (E, k)
-    for step in range(3):
-        k_acts = []
-        for i in inst:
-            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
-            k_acts.append(np.asarray(k_act))
-        u_b = b([i["info"]["noisy_state"] for i in inst], np.stack(k_acts)).clone()
-        for e, i in enumerate(inst):
-            u, i["cp"], info = i["c"](i["obs"], i["state"], i["params"], k_acts[e], i["cp"], i["info"])
-            where = (name, N, E, step, e)
-            assert torch.equal(b.a_mean[e].view(H, 4), i["cp"].a_mean), where
-            assert torch.equal(b._a[e], i["c"].core.a) and torch.equal(b._cost[e], i["c"].core.cost), where
-            assert torch.equal(u_b[e], u), where
-            assert torch.equal(b.iter_cost_min[e], info["iter_cost_min"]), where
-            assert torch.equal(b.iter_cost_min[e, k - 1], b._cost[e].min()), where
-            if name == "mppi":
-                assert torch.equal(b.a_cov[e], i["cp"].a_cov), where
-            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u.cpu().numpy(), i["params"])
-    assert b.core.device_status() == 0 and torch.isfinite(b.a_mean).all()
-    b.core.close()
-    for i in inst:
-        i["c"].core.close()
-
-
 @pytest.mark.parametrize("E", [1, 5])
 @pytest.mark.parametrize("name,N", [("mppi", 100), ("covo-offline", 40), ("covo-online", 256)])
 def test_batched_iters_equal_replicas(name, N, E):
     _batched_iters_case(name, N, E, 2)
-
-
-def _run_episode_case(k, n):
-    """covo_run_episode, n steps of MPPI N = 256 with iters=k, against the Python loop of n __call__ / env step pairs with the same
-    keys: same log, final mean and rng."""
-    env = _env("mppi")
-    params = env.default_params
-    outs = []
-    for fused in (False, True):
-        c = _controller(env, "mppi", 256, iters=k)
-        c.alias_outputs = True
-        ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(41), params, (c.core.lib, c.core.h), DEV)
-        cp = c.reset(ep.state0, params, c.init_control_params, cr.PRNGKey(42))
-        rng = cr.PRNGKey(43)
-        if fused:
-            cp, rng = c.run_episode(ep, params, cp, rng, n)
-        else:
-            for _ in range(n):  # eval_env's run_one_step (quadrotor.py:520-538)
-                rng, rng_act, rng_step, rng_control = cr.split(rng, 4)
-                u, cp, _ = c(None, None, params, rng_act, cp, {"noisy_state": ep.noisy_state})
-                ep.step(rng_step, u)
-                rng, rng_control = cr.split(rng)
-        outs.append((ep.read_log().copy(), cp.a_mean.cpu().numpy().copy(), ep.true.cpu().numpy().copy(), np.asarray(rng).copy(),
-                     c.core.iter_cost_min.cpu().numpy().copy()))
-        c.core.close()
-    for x, y in zip(outs[0], outs[1]):
-        assert np.array_equal(x, y)
-    assert outs[0][0].shape == (n, 4) and outs[0][4].shape == (1, k)
 
 
 def test_run_episode_with_iters_equals_the_python_loop():
@@ -295,10 +93,10 @@ def test_run_episode_batched_with_iters_equals_per_instance_loops():
     """covo_run_episode_batched_mode, 8 steps of MPPI N = 256 on E = 2 instances with iters=2, against per-instance Python loops of
     the single controller with iters=2 and the same keys: logs, final means, states and key chains bit-identical."""
     E, n, N = 2, 8, 256
-    env = _benv()
-    inst = _instances(env, "mppi", N, E, iters=2)
+    env = quad_env(task="tracking", randomizer=True)
+    inst = instances(env, "mppi", N, "0.01", E, iters=2)
     params = [i["params"] for i in inst]
-    b = _batched(env, "mppi", inst, N, iters=2)
+    b = batched_controller(env, "mppi", inst, len(inst), N, 0.01, iters=2)
     reset_keys = [cr.PRNGKey(150 + e) for e in range(E)]
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     rngs0 = np.stack([np.asarray(cr.PRNGKey(160 + e)) for e in range(E)])
@@ -330,10 +128,10 @@ def test_iters_next_to_the_other_options(graph, monkeypatch):
     pass, whose nominal is the mean pass 0 committed."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
     name, N = "covo-online", 256
-    env = _env(name)
+    env = quad_env(task="hovering" if name == "mppi" else "tracking_zigzag")
     opts = dict(update="guarded", ess_min=16.0, compute_diag=True, compute_plan=True, compute_fan=4)
-    c2, c1 = _controller(env, name, N, iters=2, **opts), _controller(env, name, N, iters=1, **opts)
-    cp, obs, info, state, params = _start(env, c1, name)
+    c2, c1 = iters_controller(env, name, N, iters=2, **opts), iters_controller(env, name, N, iters=1, **opts)
+    cp, obs, info, state, params = iters_start(env, c1, name)
     key = cr.PRNGKey(6)
     for step in range(3):
         key, k_act, k_step = cr.split(key, 3)
@@ -364,13 +162,13 @@ def test_iters_next_to_the_other_options(graph, monkeypatch):
 
 
 def test_refusals_name_the_condition_and_leave_the_handle_usable():
-    env = _env("mppi")
-    c = _controller(env, "mppi", 256, iters=2)
+    env = quad_env(task="hovering")
+    c = iters_controller(env, "mppi", 256, iters=2)
     lib, h = c.core.lib, c.core.h
     for bad in (0, 17, -3):
         assert lib.covo_set_step_iters(h, bad, _lib.ptr(c.core.iter_cost_min), 1) != 0
         assert b"outside [1, 16]" in lib.covo_last_error()
-    cp, obs, info, state, params = _start(env, c, "mppi")
+    cp, obs, info, state, params = iters_start(env, c, "mppi")
     u, cp, i = c(obs, state, params, cr.PRNGKey(9), cp, info)
     with pytest.raises(_lib.CovoError, match="covo_set_step_iters"):
         c.core.time_phases()
@@ -378,10 +176,6 @@ def test_refusals_name_the_condition_and_leave_the_handle_usable():
     c.core.time_phases()
     assert c.core.device_status() == 0
     c.core.close()
-
-
-def _rel(x, ref):
-    return np.abs(x - ref) / np.maximum(np.abs(ref), 1.0)
 
 
 @pytest.mark.parametrize("name", list(IO.CASES))
@@ -402,7 +196,7 @@ def test_two_pass_step_against_the_oracle(name):
     env = IO.make_env(name, DEV)
     obs, info, state, key = IO.problem(env, case["seed"])
     ns, params = info["noisy_state"], env.default_params
-    c1, c2 = _controller(env, name, N, iters=1), _controller(env, name, N, iters=2)
+    c1, c2 = iters_controller(env, name, N, iters=1), iters_controller(env, name, N, iters=2)
     cp = c1.init_control_params.replace(gamma_mean=IO.GAMMA)
     assert np.array_equal(cp.a_mean.cpu().numpy(), IO.hover_mean(env)) and float(cp.sample_sigma) == IO.SIGMA
     if name == "covo-offline":
@@ -425,11 +219,11 @@ def test_two_pass_step_against_the_oracle(name):
         aerr = float(np.abs(a_dev - a_ref).max())
         _, fs = IO.pass_inputs(name, env, key if j == 0 else IO.next_raw_key(key), N)
         cost_own = CO.rollout(so, po, a_dev, 1.0, fs, dtype=np.float64)
-        rel = _rel(cost_dev, cost_own)
+        rel = rel_err(cost_dev, cost_own)
         bar = 1e-5
         if rel.max() >= bar:
             c32 = CO.rollout(so.astype(np.float32), po, a_dev.astype(np.float32), 1.0, fs.astype(np.float32), dtype=np.float32)
-            bar = max(bar, 1.5 * _rel(c32, cost_own).max())
+            bar = max(bar, 1.5 * rel_err(c32, cost_own).max())
             assert int((rel >= 1e-5).sum()) <= max(2, N // 4096), (name, j, int((rel >= 1e-5).sum()))
         gap = float(np.diff(np.sort(cost_ref)[:2])[0])
         merr = float(np.abs(cpj.a_mean.cpu().numpy() - mean_ref).max())
@@ -441,7 +235,7 @@ def test_two_pass_step_against_the_oracle(name):
         assert merr < 1e-4, (name, j, merr, gap)
         assert torch.equal(u, cpj.a_mean[0])
     icm = outs[1][2]["iter_cost_min"].cpu().numpy()
-    assert _rel(icm, np.array([ref[0][1].min(), ref[1][1].min()])).max() < 1e-5, icm
+    assert rel_err(icm, np.array([ref[0][1].min(), ref[1][1].min()])).max() < 1e-5, icm
     # the passes are distinguishable: pass 1 did not shift (its start is pass 0's mean) and drew from the advanced key
     assert np.abs(ref[1][2] - ref[0][2]).max() > 1e-3 and np.abs(ref[0][0] - ref[1][0]).max() > 0.1
     c1.core.close(), c2.core.close()
@@ -450,9 +244,9 @@ def test_two_pass_step_against_the_oracle(name):
 def test_sharded_step_is_refused_by_the_library():
     """covo_mpc_step on a handle with iterations attached and partial_out != NULL (a sample-sharded step): COVO_E_BADARG naming the
     condition, before any launch; the handle steps on once the log is detached."""
-    env = _env("mppi")
-    c = _controller(env, "mppi", 256, iters=2)
-    cp, obs, info, state, params = _start(env, c, "mppi")
+    env = quad_env(task="hovering")
+    c = iters_controller(env, "mppi", 256, iters=2)
+    cp, obs, info, state, params = iters_start(env, c, "mppi")
     c(obs, state, params, cr.PRNGKey(9), cp, info)
     pc, args = c.core._last_step
     import ctypes as C

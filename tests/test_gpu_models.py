@@ -16,47 +16,14 @@ if not torch.cuda.is_available():
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
-from covo_mpc_amd.dynamics.dataclass import EnvParams3D  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from tests.conftest import make_problem, table_ref  # noqa: E402
-from tests.test_gpu_parity import DEV, dev_state, rel_err, sample_actions, to_stripes  # noqa: E402
+from tests.gpu_support import (DEV, DP, dev_state, disturb_key, params_c, quad_env, sample_actions, step_keys, to_stripes,  # noqa: E402
+                               uniform_draws)
+from tests.oracle_support import oracle_params, oracle_state_packed, rel_err  # noqa: E402
 
 KINDS = ["periodic", "sin", "drag", "mixed"]
-# disturb_params: every component live (dataclass.py:88; DR / reset draw them); fp32 numbers, like every parameter of the reference
-DP = tuple(float(np.float32(x)) for x in (0.7, -0.4, 0.9, 0.15, -0.35, 0.6))
-
-
-def params_c(p: R.Params, kind="none", reward="penyaw", rollover=False):
-    e = EnvParams3D(disturb_params=np.asarray(p.disturb_params, dtype=np.float32), disturb_period=p.disturb_period,
-                    disturb_scale=p.disturb_scale, dyn_noise_scale=p.dyn_noise_scale)
-    return e.to_c(rollover_terminate=rollover, reward=reward, disturb_type=kind)
-
-
-def disturb_key(k):
-    """disturb_key of step_env(k): quadrotor.py:262, free.py:136,144"""
-    return cr.split(cr.split(cr.split(k)[1])[0])[0]
-
-
-def step_keys(key, mode, H=32):
-    """the key step_env receives at every rollout step (include/covo_hip.h: COVO_DISTURB_KEYS_*)"""
-    out = []
-    for _ in range(H):
-        if mode == _lib.DISTURB_KEYS_SHARED:
-            out.append(key)
-        elif mode == _lib.DISTURB_KEYS_HESSIAN:  # covo.py:151
-            rk, key = cr.split(key)
-            out.append(rk)
-        else:  # covo.py:60,66
-            _, key = cr.split(key)
-            rs, key = cr.split(key)
-            out.append(rs)
-    return out
-
-
-def uniform_draws(p, key, mode, H=32):
-    """(H,3): uniform(disturb_key, (3,), -scale, scale) of every step (free.py:16-21)"""
-    return np.stack([cr.uniform(disturb_key(k), (3,), -p.disturb_scale, p.disturb_scale) for k in step_keys(key, mode, H)])
 
 
 # ------------------------------------------------------------------------------------------ the table
@@ -496,14 +463,6 @@ def test_tracking_slow_closed_loop_sanity():
 
 
 # ------------------------------------------------------------------------------------------ f1 / f3 against oracle/ directly
-def _oracle_state(packed, traj):
-    """ref_np.State (fp64) from a packed float[32] state and the episode's (pos, vel, acc) trajectories"""
-    st = np.asarray(packed, dtype=np.float32)
-    return R.State(pos=st[0:3], vel=st[3:6], quat=st[6:10], omega=st[10:13], f_disturb=st[13:16], pos_tar=st[16:19],
-                   vel_tar=st[19:22], acc_tar=st[22:25], time=int(st[25:26].view(np.int32)[0]), pos_traj=traj[0],
-                   vel_traj=traj[1], acc_traj=traj[2]).astype(np.float64)
-
-
 def _pack_oracle(s):
     x = np.zeros(32)
     x[0:3], x[3:6], x[6:10], x[10:13], x[13:16] = s.pos, s.vel, s.quat, s.omega, s.f_disturb
@@ -541,7 +500,7 @@ def test_env_step_kernel_vs_oracle_step_env(task, kind, rollover):
         ep.step(k_step, torch.from_numpy(u).to(DEV))
         kd, kp, kv, kq, ko = cm.envs.DeviceEpisode.leaf_keys(k_step)
         draw = cr.normal(kd, (3,)) if kind == "gaussian" else cr.uniform(kd, (3,), -p.disturb_scale, p.disturb_scale)
-        s = _oracle_state(before, traj)
+        s = oracle_state_packed(before, traj)
         nxt, r, done = R.step_env(s, u.astype(np.float64), p, R.Disturb(kind, draw.astype(np.float64)), rollover, reward_fn)
         noisy = R.noisy_state(nxt, p, cr.normal(kp, (3,)).astype(np.float64), cr.normal(kv, (3,)).astype(np.float64),
                               cr.normal(kq, (4,)).astype(np.float64), cr.normal(ko, (3,)).astype(np.float64))
@@ -572,7 +531,7 @@ def test_pid_nominal_vs_oracle_pid_action():
     traj = (state.pos_traj, state.vel_traj, state.acc_traj)
     worst_chain = worst_mean = 0.0
     for t in list(range(0, 60)) + [137, 250, 298]:
-        s = _oracle_state(pd[t], traj)
+        s = oracle_state_packed(pd[t], traj)
         # the chain step (covo.py:80-90): rng_step, key = split(key) [PID]; rng_step, key = split(key) [env step, deterministic=False]
         _, k1 = cr.split(kd[t])
         rs, _ = cr.split(k1)
@@ -641,19 +600,6 @@ def test_mppi_step_with_covariance_adaptation(graph, monkeypatch):
 
 
 # ------------------------------------------------------------------------------------------ BASELINE configs[4] end to end (round 4)
-def _dr_env():
-    import covo_mpc_amd as cm
-    return cm.envs.Quad3D(task="tracking", obs_type="quad_params", enable_randomizer=True, disturb_type="gaussian",
-                          disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-def _oracle_params(params):
-    """ref_np.Params of one domain-randomised instance (quadrotor.py:135-160 varies m, I, action_scale, alpha_bodyrate,
-    disturb_params; I does not enter the body-rate model)."""
-    return R.Params(m=float(params.m), action_scale=float(params.action_scale), alpha_bodyrate=float(params.alpha_bodyrate),
-                    disturb_params=tuple(float(x) for x in params.disturb_params)).fp32()
-
-
 def test_env_instances_32_batched_step_vs_fp64_oracle():
     """BASELINE configs[4] at its per-GPU shape: E = 32 domain-randomised `tracking` instances x N = 4096 in
     ONE covo_mpc_step_batched call; three sampled instances are checked against the fp64 oracle run with THEIR OWN parameters:
@@ -661,7 +607,7 @@ def test_env_instances_32_batched_step_vs_fp64_oracle():
     (oracle softmax of the oracle costs)."""
     import covo_mpc_amd as cm
     N, E = 4096, 32
-    env = _dr_env()
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(500 + e)) for e in range(E)]
     ep = None
     c0, cp0 = cm.envs.get_controller(env, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
@@ -682,8 +628,8 @@ def test_env_instances_32_batched_step_vs_fp64_oracle():
     torch.cuda.synchronize()
     for e in (0, 13, 31):
         traj = (ep.states0[e].pos_traj, ep.states0[e].vel_traj, ep.states0[e].acc_traj)
-        so = _oracle_state(noisy[e], traj)
-        po = _oracle_params(params[e])
+        so = oracle_state_packed(noisy[e], traj)
+        po = oracle_params(params[e])
         a_dev = b._a[e].permute(1, 0, 2).contiguous().cpu().numpy()
         cost_ref = CO.rollout(so, po, a_dev.astype(np.float64), 1.0, np.zeros(3), dtype=np.float64)
         assert rel_err(b._cost[e].cpu().numpy(), cost_ref).max() < 1e-5, e
@@ -705,7 +651,7 @@ def test_batched_closed_loop_sigma_tracks_lapack_on_its_own_hessians():
     iterate passes first, step after step, on the matrices a closed loop really produces."""
     import covo_mpc_amd as cm
     N, E = 4096, 32
-    env = _dr_env()
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(1000 + e)) for e in range(E)]
     c0, _ = cm.envs.get_controller(env, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
     cp0 = c0.init_control_params
@@ -737,7 +683,7 @@ def test_batched_env_step_vs_oracle_and_single_instance_kernel():
     step keys give) put them."""
     import covo_mpc_amd as cm
     E = 32
-    env = _dr_env()
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(900 + e)) for e in range(E)]
     core = SamplingCore(256, 32, 0.01, 1.0, device=DEV)
     keys0 = [cr.PRNGKey(1000 + e) for e in range(E)]
@@ -758,9 +704,9 @@ def test_batched_env_step_vs_oracle_and_single_instance_kernel():
             se.step(step_keys[e], torch.from_numpy(u[e]).to(DEV))
             assert torch.equal(se.true, ep.true[e]) and torch.equal(se.noisy, ep.noisy[e]), (t, e)
             kd, kp, kv, kq, ko = cm.envs.DeviceEpisode.leaf_keys(step_keys[e])
-            p = _oracle_params(params[e])
+            p = oracle_params(params[e])
             traj = (ep.states0[e].pos_traj, ep.states0[e].vel_traj, ep.states0[e].acc_traj)
-            s = _oracle_state(before[e], traj)
+            s = oracle_state_packed(before[e], traj)
             nxt, r, done = R.step_env(s, u[e].astype(np.float64), p, R.Disturb("gaussian", cr.normal(kd, (3,)).astype(np.float64)),
                                       False, R.REWARD_FNS["penyaw"])
             noisy = R.noisy_state(nxt, p, cr.normal(kp, (3,)).astype(np.float64), cr.normal(kv, (3,)).astype(np.float64),
@@ -779,7 +725,7 @@ def test_run_episode_batched_equals_per_instance_episodes():
     bit-identical per instance (the batched step is bit-identical to the single step, the batched env step to the single one)."""
     import covo_mpc_amd as cm
     N, E, n = 1024, 4, 20
-    env = _dr_env()
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     c0, _ = cm.envs.get_controller(env, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
     cp0 = c0.init_control_params

@@ -17,9 +17,9 @@ if not torch.cuda.is_available():
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
+from tests.gpu_support import DEV  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEV = "cuda:0"
 N_A = 128
 SC_COUNT = 3712  # doubles of per-matrix scalars behind the chain's 11 matrix buffers (sigma_ns.hip: enum SC_*)
 SC_ITERS, SC_KWIN, SC_BARFAIL = 6, 7, 26

@@ -22,9 +22,8 @@ if not torch.cuda.is_available():
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
-from tests.test_gpu_parity import DEV  # noqa: E402
-from tests.test_gpu_trace import _batched, _env, _start  # noqa: E402
-from tests.test_post_cov_abi import ref_weighted_cov  # noqa: E402
+from tests.gpu_support import DEV, batched_controller, quad_env, start_episode  # noqa: E402
+from tests.post_cov_oracle import ref_weighted_cov  # noqa: E402
 
 H, NA = 32, 128
 N_ACC = 64  # post_cov.hip: PC_NACC
@@ -191,10 +190,10 @@ def test_step_post_cov_is_the_stand_alone_call_on_the_steps_buffers(name, kw):
     option, bit for bit.  (The bar against the reference is the stand-alone tests': a closed-loop step at lam = 0.01 is all but one-hot,
     with weights and products below fp32's normal range, where a relative bar says nothing.)"""
     N = 256
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     ca, cpa = _controller(env, name, N, True, **kw)
     cb, cpb = _controller(env, name, N, False, **kw)
-    cpa, obs, info, state, params = _start(env, ca, cpa, name)
+    cpa, obs, info, state, params = start_episode(env, ca, cpa, name)
     if name == "covo-offline":
         cpb = cpb.replace(a_cov_offline=cpa.a_cov_offline, a_chol_offline=cpa.a_chol_offline)
     key = cr.PRNGKey(21)
@@ -226,7 +225,7 @@ def test_batched_online_post_cov_equals_its_instances_run_singly():
     post_aux[e] equal the single controller's on instance e alone, bit for bit."""
     import covo_mpc_amd as cm
     N, E = 256, 3
-    env = _env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     act_keys = np.stack([np.asarray(cr.PRNGKey(60 + e)) for e in range(E)])
@@ -241,7 +240,7 @@ def test_batched_online_post_cov_equals_its_instances_run_singly():
         cp0 = c.init_control_params
         assert c.core.device_status() == 0
         c.core.close()
-    b = _batched(env, "covo-online", cp0, E, N, compute_post_cov=True)
+    b = batched_controller(env, "covo-online", cp0, E, N, 0.01, compute_post_cov=True)
     assert tuple(b.post_cov.shape) == (E, NA, NA) and tuple(b.post_aux.shape) == (E, _lib.COVO_POST_AUX_FLOATS)
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     b.bind_episode(ep)

@@ -30,9 +30,9 @@ if not torch.cuda.is_available():
 
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
+from tests.gpu_support import DEV, DP, dev_state, params_c, perturbed_hover_mean  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEV = "cuda:0"
 N_A = 128
 SC_COUNT = 3712  # doubles of per-matrix scalars behind the chain's 11 matrix buffers (sigma_ns.hip: enum SC_*)
 SC_ZBUF, SC_ITERS, SC_BARFAIL, SC_ZCOEF = 5, 6, 26, 30
@@ -187,9 +187,6 @@ def test_hessian_adjoint_equals_pairs_batch_equals_single(model):
     from covo_mpc_amd import random as cr
     from covo_mpc_amd.dynamics.dataclass import EnvParams3D
     from tests.state_atlas import atlas_state
-    from tests.test_gpu_models import DP, params_c
-    from tests.test_gpu_parity import dev_state
-    from tests.test_gpu_state_atlas import _mean
     core = SamplingCore(256, 32, 0.01, 1.0, device=DEV)
     try:
         states, means, tabs, singles = [], [], [], []
@@ -200,7 +197,7 @@ def test_hessian_adjoint_equals_pairs_batch_equals_single(model):
             else:
                 p = p.replace(disturb_params=DP)
                 pc = params_c(p, *HESS_MODELS[model])
-            a = torch.from_numpy(_mean(p, rng, 0.1)).to(DEV)
+            a = torch.from_numpy(perturbed_hover_mean(p, rng, 0.1)).to(DEV)
             ds = dev_state(s)
             tab = None
             if HESS_MODELS[model] is not None:

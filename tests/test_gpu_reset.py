@@ -19,17 +19,9 @@ if not torch.cuda.is_available():
 
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
-from tests.test_gpu_parity import DEV  # noqa: E402
+from tests.gpu_support import DEV, ulps  # noqa: E402
 
 f32 = np.float32
-
-
-def _ulps(a, b):
-    """max distance in fp32 ulps between two float32 arrays (0 where both are 0)"""
-    a, b = np.asarray(a, dtype=f32), np.asarray(b, dtype=f32)
-    scale = np.spacing(np.maximum(np.abs(a), np.abs(b)).astype(f32))
-    d = np.abs(a.astype(np.float64) - b.astype(np.float64)) / scale
-    return float(np.max(np.where(a == b, 0.0, d)))
 
 
 def _push_out(ep, state, pos, vel):
@@ -64,7 +56,7 @@ def test_device_reset_vs_host_reset_env(task, kind):
         traj_d = [t.cpu().numpy() for t in (ep.pos_traj, ep.vel_traj, ep.acc_traj)]
         traj_h = [st_h.pos_traj, st_h.vel_traj, st_h.acc_traj]
         for d, h in zip(traj_d, traj_h):
-            assert d.shape == h.shape and _ulps(d, h) <= 1.0, (trial, _ulps(d, h))
+            assert d.shape == h.shape and ulps(d, h) <= 1.0, (trial, ulps(d, h))
             differing += int(np.sum(d != h))
         t_dev, n_dev = ep.true.cpu().numpy(), ep.noisy.cpu().numpy()
         want = st_h.pack()
@@ -122,7 +114,7 @@ def test_env_step_through_reset_vs_host_env():
     assert sum(dones) == 1 and dones.index(True) in (1, 2, 3)
     assert np.array_equal(log[:, 3] == 1.0, np.asarray(dones))
     assert np.abs(log[:, 1] - np.asarray(errs)).max() < 2e-5
-    assert _ulps(ep.pos_traj.cpu().numpy(), state.pos_traj) <= 1.0 and _ulps(ep.vel_traj.cpu().numpy(), state.vel_traj) <= 1.0
+    assert ulps(ep.pos_traj.cpu().numpy(), state.pos_traj) <= 1.0 and ulps(ep.vel_traj.cpu().numpy(), state.vel_traj) <= 1.0
     assert state.time == 30 - dones.index(True) - 1
 
 

@@ -28,21 +28,15 @@ import covo_mpc_amd as cm  # noqa: E402
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
-from tests.test_sigma_adapt_abi import adapt_ref  # noqa: E402
-from tests.test_sigma_period_abi import N_A  # noqa: E402
+from tests.gpu_cases import check_structure, errors, g32  # noqa: E402
+from tests.gpu_support import DEV, quad_env, single_controller  # noqa: E402
+from tests.sigma_shift_oracle import BAR_L, BAR_LOGDET, BAR_SIGMA, N_A, adapt_ref  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEV = "cuda:0"
 SIGMA = 0.5
-BAR_L, BAR_SIGMA, BAR_LOGDET = 3e-6, 1e-6, 2 * N_A * 2.0 ** -24
 GAMMAS = (0.05, 0.5, 0.9)
 CLOUDS = ((257, 0.5), (257, 0.05), (5, 0.5), (5, 0.05))  # (samples, lam) of the posterior covariances; 5 samples: rank <= 4
 NL = 15
-
-
-def g32(gamma):
-    """gamma as the kernel gets it (a C float)."""
-    return float(np.float32(gamma))
 
 
 # ---- 1. the stand-alone kernel -----------------------------------------------------------------------------------------------------
@@ -76,23 +70,6 @@ def inputs(core):
     refs = {(k, gm): [adapt_ref(Lh[i], Ch[i], g32(gm), SIGMA) for i in range(NL)]
             for k, Ch in ((k, v.cpu().numpy()) for k, v in Cs.items()) for gm in GAMMAS}
     return L, Cs, refs
-
-
-def errors(Sp, Lp, ref):
-    Sref, Lref = ref[0], ref[1]
-    Sp64, Lp64 = Sp.astype(np.float64), Lp.astype(np.float64)
-    e_ld = abs(2.0 * np.log(np.diag(Lp64)).sum() - 2.0 * N_A * np.log(SIGMA))
-    e_L = np.abs(Lp64 - Lref).max() / np.abs(Lref).max()
-    e_S = np.abs(Sp64 - Sref).max() / np.abs(Sref).max()
-    return e_ld / BAR_LOGDET, e_L / BAR_L, e_S / BAR_SIGMA
-
-
-def check_structure(Sp, Lp, where):
-    assert np.all(np.triu(Lp, 1) == 0.0), where                                  # exact zero structure
-    assert np.all(Lp[N_A - 4:, :N_A - 4] == 0.0), where
-    assert np.all(Sp[N_A - 4:, :N_A - 4] == 0.0) and np.all(Sp[:N_A - 4, N_A - 4:] == 0.0), where
-    assert np.array_equal(Sp, Sp.T), where                                        # symmetric bit for bit
-    assert np.all(np.isfinite(Sp)) and np.all(np.isfinite(Lp)) and np.all(np.diag(Lp) > 0), where
 
 
 def test_the_restatement_rounded_to_fp32_stays_inside_the_bars(inputs):
@@ -202,18 +179,6 @@ def test_adapt_alone_refuses_bad_arguments(core):
 
 
 # ---- the steps ------------------------------------------------------------------------------------------------------------------
-def _env(randomizer=False, task="tracking_zigzag"):
-    return cm.envs.Quad3D(task=task, obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-def _controller(env, N, seed=1, name="covo-online", **kw):
-    c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam0.01", device=DEV, compute_info=False, **kw)
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(seed), params)
-    return c, c.init_control_params, obs, info, state, params
-
-
 @pytest.mark.parametrize("graph", ["graph", "eager"])
 def test_period_three_adapts_on_the_reuse_steps(graph, monkeypatch):
     """N = 256, m = 3, gamma = 0.2, seven steps.  Step 0 is the step of the same controller without adaptation.  A reuse step's a_cov,
@@ -221,9 +186,9 @@ def test_period_three_adapts_on_the_reuse_steps(graph, monkeypatch):
     and its a_cov is not what the plain shift of the same factor gives.  Refresh steps report fallback 0 and scale 1."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
     N, gm = 256, 0.2
-    env = _env()
-    ca, cpa, obs, info, state, params = _controller(env, N, sigma_period=3, sigma_adapt=gm)
-    cb, cpb = _controller(env, N, sigma_period=3)[:2]
+    env = quad_env(task="tracking_zigzag")
+    ca, cpa, obs, info, state, params = single_controller(env, "covo-online", N, sigma_period=3, sigma_adapt=gm)
+    cb, cpb = single_controller(env, "covo-online", N, sigma_period=3)[:2]
     assert ca.core.compute_post_cov and ca.core.sigma_adapt_gamma == gm
     key = cr.PRNGKey(7)
     L_prev = C_prev = None
@@ -260,8 +225,8 @@ def test_two_passes_of_a_reuse_step_adapt_once_from_the_last_pass(monkeypatch):
     """iters = 2, m = 2: a reuse step's a_cov and factor are the stand-alone call on the previous step's factor and on the C its
     last pass left; both passes sample from that one L'."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, sigma_period=2, sigma_adapt=0.2, iters=2)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=2, sigma_adapt=0.2, iters=2)
     key = cr.PRNGKey(13)
     L_prev = C_prev = None
     for step in range(4):
@@ -285,11 +250,11 @@ def test_run_episode_equals_the_python_loop(graph, monkeypatch):
     bit for bit."""
     from covo_mpc_amd.envs.quadrotor import DeviceEpisode
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     m, N, T = 3, 256, 7
     out = {}
     for kind in ("episode", "steps"):
-        c, cp, _, _, _, params = _controller(env, N, sigma_period=m, sigma_adapt=0.2)
+        c, cp, _, _, _, params = single_controller(env, "covo-online", N, sigma_period=m, sigma_adapt=0.2)
         c.alias_outputs = True
         ep = DeviceEpisode(env, cr.PRNGKey(21), params, (c.core.lib, c.core.h), c.core.device)
         cp = c.reset(ep.state0, params, cp, cr.PRNGKey(22))
@@ -318,7 +283,7 @@ def test_batched_online_equals_single():
     """E = 3, N = 256, m = 2, gamma = 0.2, four steps: row e of a_mean, a_cov, the factor and the adapt rows is torch.equal to the
     single controller on instance e alone."""
     E, N, m, gm = 3, 256, 2, 0.2
-    env = _env(randomizer=True, task="tracking")
+    env = quad_env(task="tracking", randomizer=True)
     inst = []
     for e in range(E):
         params = env.sample_params(cr.PRNGKey(100 + e))
@@ -361,8 +326,8 @@ def test_batched_online_equals_single():
 # ---- refusals ---------------------------------------------------------------------------------------------------------------------
 def test_adaptation_without_a_post_cov_target_is_refused_before_any_launch(monkeypatch):
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, sigma_period=2)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=2)
     rows = torch.zeros((1, 4), device=DEV)
     lib, h = c.core.lib, c.core.h
     assert lib.covo_set_step_sigma_adapt(h, 1.0, _lib.ptr(rows), 1) != 0 and b"gamma=1" in lib.covo_last_error()
@@ -383,8 +348,8 @@ def test_adaptation_without_a_post_cov_target_is_refused_before_any_launch(monke
 
 def test_adaptation_on_an_mppi_step_is_refused_before_any_launch(monkeypatch):
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, name="mppi")
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "mppi", 256)
     rows = torch.zeros((1, 4), device=DEV)
     _lib.check(c.core.lib.covo_set_step_sigma_adapt(c.core.h, 0.2, _lib.ptr(rows), 1), "covo_set_step_sigma_adapt")
     with pytest.raises(_lib.CovoError, match=r"Sigma adapt.*belongs to the reuse steps of covo-online.*MPPI"):
@@ -398,8 +363,8 @@ def test_adaptation_on_an_mppi_step_is_refused_before_any_launch(monkeypatch):
 
 
 def test_kernel_by_kernel_path_refuses_adaptation():
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, sigma_period=2, sigma_adapt=0.2)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=2, sigma_adapt=0.2)
     c.materialize_eps = True
     with pytest.raises(NotImplementedError, match="sigma_period=2|sigma_adapt=0.2"):
         c(obs, state, params, cr.PRNGKey(3), cp, info)

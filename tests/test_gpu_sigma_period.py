@@ -12,7 +12,6 @@ rounding per entry:
           the fp64 one, whose log det is exact to fp64 rounding, and log(1 + e) ~ e
 Everything else is equality of bits: a reuse step against core.sigma_shift and covo_noise_gemm_philox, a refresh step against a plain
 controller, graph against eager, a batched row against the single controller, the device episode against the Python loop."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -24,16 +23,15 @@ torch = pytest.importorskip("torch")
 if not torch.cuda.is_available():
     pytest.skip("needs the MI355X", allow_module_level=True)
 
-import covo_mpc_amd as cm  # noqa: E402
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
-from tests.test_sigma_period_abi import N_A, shift_factor_ref  # noqa: E402
+from tests.gpu_cases import _batched_period_case, _period_case, check_shift  # noqa: E402
+from tests.gpu_support import DEV, quad_env, single_controller  # noqa: E402
+from tests.sigma_shift_oracle import N_A, shift_factor_ref  # noqa: E402
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-DEV = "cuda:0"
 SIGMA = 0.5
-BAR_L, BAR_SIGMA, BAR_LOGDET = 3e-6, 1e-6, 2 * N_A * 2.0 ** -24
 
 
 # ---- 1. the stand-alone shift ------------------------------------------------------------------------------------------------------
@@ -58,20 +56,6 @@ def factors(core):
     conds = [np.linalg.cond(l.astype(np.float64) @ l.astype(np.float64).T) ** 2 for l in L[1:]]
     assert 5e2 < min(conds) and max(conds) < 1e5, conds
     return L, [shift_factor_ref(l, SIGMA) for l in L]
-
-
-def check_shift(Sp, Lp, ref, where):
-    Sref, Lref = ref
-    Sp64, Lp64 = Sp.astype(np.float64), Lp.astype(np.float64)
-    assert np.all(np.triu(Lp, 1) == 0.0), where                                  # exact zero structure
-    assert np.all(Sp[N_A - 4:, :N_A - 4] == 0.0) and np.all(Sp[:N_A - 4, N_A - 4:] == 0.0), where
-    assert np.array_equal(Sp, Sp.T), where                                        # symmetric bit for bit
-    assert np.all(np.isfinite(Sp)) and np.all(np.isfinite(Lp)) and np.all(np.diag(Lp) > 0), where
-    e_ld = abs(2.0 * np.log(np.diag(Lp64)).sum() - 2.0 * N_A * np.log(SIGMA))
-    e_L = np.abs(Lp64 - Lref).max() / np.abs(Lref).max()
-    e_S = np.abs(Sp64 - Sref).max() / np.abs(Sp64).max()
-    print(f"  {where}: |log det - 2 n log sigma| {e_ld:.2e}, L' err {e_L:.2e}, Sigma' err {e_S:.2e}")
-    assert e_ld <= BAR_LOGDET and e_L <= BAR_L and e_S <= BAR_SIGMA, (where, e_ld, e_L, e_S)
 
 
 def test_shift_alone_against_the_fp64_restatement(core, factors):
@@ -109,23 +93,11 @@ def test_shift_alone_refuses_bad_arguments(core):
 
 
 # ---- the steps ------------------------------------------------------------------------------------------------------------------
-def _env(randomizer=False, task="tracking_zigzag"):
-    return cm.envs.Quad3D(task=task, obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-def _controller(env, N, seed=1, name="covo-online", **kw):
-    c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam0.01", device=DEV, compute_info=False, **kw)
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(seed), params)
-    return c, c.init_control_params, obs, info, state, params
-
-
 def test_period_one_equals_a_controller_without_the_argument(monkeypatch):
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    ca, cpa, obs, info, state, params = _controller(env, 256, sigma_period=1)
-    cb, cpb = _controller(env, 256)[:2]
+    env = quad_env(task="tracking_zigzag")
+    ca, cpa, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=1)
+    cb, cpb = single_controller(env, "covo-online", 256)[:2]
     key = cr.PRNGKey(5)
     for step in range(3):
         key, k_act, k_step = cr.split(key, 3)
@@ -140,56 +112,6 @@ def test_period_one_equals_a_controller_without_the_argument(monkeypatch):
     cb.core.close()
 
 
-def _period_case(m, steps, graph, monkeypatch, gamma=0.0):
-    """`steps` steps at period m.  A refresh step (age 0) is a plain controller's step from the same mean, state and key; a reuse step
-    shifts -- with gamma > 0: adapts, from the posterior covariance the step before left -- the factor that step left, reports a_cov =
-    Sigma' and samples clip(shifted mean + L' eps) with the step's act key."""
-    monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    N = 256
-    env = _env()
-    kw = dict(sigma_adapt=gamma) if gamma else {}
-    ca, cpa, obs, info, state, params = _controller(env, N, sigma_period=m, **kw)
-    cb, cpb = _controller(env, N)[:2]
-    assert ca.core.uses_graph == (graph == "graph")
-    helper = SamplingCore(N, 32, 0.01, 1.0, device=DEV, use_graph=False, compute_info=False)
-    key = cr.PRNGKey(7)
-    L_prev = C_prev = None
-    for step in range(steps):
-        key, k_act, k_step = cr.split(key, 3)
-        ua, cpa2, ia = ca(obs, state, params, k_act, cpa, info)
-        torch.cuda.synchronize()
-        age = ia["sigma_age"]
-        assert isinstance(age, int) and age == step % m, (step, age)
-        L_now = ca.core.sigma_factor()
-        if age == 0:
-            ub, cpb2, _ = cb(obs, state, params, k_act, cpa, info)  # the plain controller from the SAME mean
-            torch.cuda.synchronize()
-            assert torch.equal(ua, ub) and torch.equal(cpa2.a_mean, cpb2.a_mean) and torch.equal(cpa2.a_cov, cpb2.a_cov), step
-            assert torch.equal(ca.core.a, cb.core.a) and torch.equal(ca.core.cost, cb.core.cost), step
-            if gamma:
-                assert (float(ia["sigma_adapt_fallback"]), float(ia["sigma_adapt_scale"])) == (0.0, 1.0), step
-        else:
-            if gamma:
-                Sp, Lp, rows = ca.core.sigma_adapt(L_prev, C_prev, gamma, cpa.sample_sigma)
-                assert float(ia["sigma_adapt_fallback"]) == float(rows[0]) and float(ia["sigma_adapt_scale"]) == float(rows[1]), step
-                assert float(rows[0]) in (0.0, 1.0), step
-            else:
-                Sp, Lp = ca.core.sigma_shift(L_prev, cpa.sample_sigma)
-            assert torch.equal(cpa2.a_cov, Sp) and torch.equal(L_now, Lp), step
-            _, act_key = cr.split(k_act)  # covo.py:212
-            a_ref = helper.noise_gemm_philox(Lp, ca.core._bufs["a_mean_shift"], act_key)
-            torch.cuda.synchronize()
-            assert torch.equal(ca.core.a, a_ref), step
-        assert bool(torch.isfinite(cpa2.a_mean).all()), step
-        L_prev, cpa = L_now, cpa2
-        if gamma:
-            C_prev = ia["post_cov"].clone()
-        obs, state, _, _, info = env.step(k_step, state, ua.cpu().numpy(), params)
-    assert ca.core.sigma_age == steps % m and ca.core.device_status() == 0
-    for c in (ca.core, cb.core, helper):
-        c.close()
-
-
 def test_period_three_refresh_reuse_reuse_refresh(monkeypatch):
     """Step 0 is the plain step; step 1 and 2 shift the factor the step before left, report a_cov = Sigma' and sample clip(shifted mean
     + L' eps) with the step's act key; step 3 is a plain controller's step from the same mean, state and key."""
@@ -200,12 +122,12 @@ def test_graph_equals_eager_over_three_periods(monkeypatch):
     """m = 2, six steps: the graph handle runs its refresh step eagerly, captured and replayed (steps 0, 2, 4) and its reuse step
     likewise (1, 3, 5).  (The graph cache exposes no capture counter: that each graph is captured once is not asserted.)"""
     N = 256
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     monkeypatch.setenv("COVO_GRAPH", "1")
-    cg, cpg, obs, info, state, params = _controller(env, N, sigma_period=2)
+    cg, cpg, obs, info, state, params = single_controller(env, "covo-online", N, sigma_period=2)
     monkeypatch.delenv("COVO_GRAPH")
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    ce, cpe = _controller(env, N, sigma_period=2)[:2]
+    ce, cpe = single_controller(env, "covo-online", N, sigma_period=2)[:2]
     assert cg.core.uses_graph and not ce.core.uses_graph
     key = cr.PRNGKey(11)
     for step in range(6):
@@ -222,43 +144,6 @@ def test_graph_equals_eager_over_three_periods(monkeypatch):
     ce.core.close()
 
 
-def _batched_period_case(E, N, m, steps):
-    """Row e of a_mean, a_cov, the costs and the factor is torch.equal to the single controller on instance e alone; the batch shares
-    one age."""
-    env = _env(randomizer=True, task="tracking")
-    inst = []
-    for e in range(E):
-        params = env.sample_params(cr.PRNGKey(100 + e))
-        obs, info, state = env.reset(cr.PRNGKey(200 + e), params)
-        c, _ = cm.envs.get_controller(env, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False, sigma_period=m)
-        inst.append(dict(params=params, obs=obs, info=info, state=state, key=cr.PRNGKey(300 + e), c=c, cp=c.init_control_params))
-    cp0 = inst[0]["cp"]
-    b = cm.controllers.BatchedCoVOController(env, E, N, 32, 0.01, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                             sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, sigma_period=m)
-    b.set_instances([i["state"] for i in inst], [i["params"] for i in inst])
-    for step in range(steps):
-        k_acts = []
-        for i in inst:
-            i["key"], k_act, i["k_step"] = cr.split(i["key"], 3)
-            k_acts.append(np.asarray(k_act))
-        b([i["info"]["noisy_state"] for i in inst], np.stack(k_acts))
-        assert b.sigma_age == step % m
-        Lb = b.core.sigma_factor(E)
-        for e, i in enumerate(inst):
-            u, i["cp"], sinfo = i["c"](i["obs"], i["state"], i["params"], k_acts[e], i["cp"], i["info"])
-            where = (step, e)
-            assert sinfo["sigma_age"] == step % m, where
-            assert torch.equal(b._cost[e], i["c"].core.cost), where
-            assert torch.equal(b.a_mean[e], i["cp"].a_mean.reshape(-1)), where
-            assert torch.equal(b.a_cov[e], i["cp"].a_cov), where
-            assert torch.equal(Lb[e], i["c"].core.sigma_factor()), where
-            i["obs"], i["state"], _, _, i["info"] = env.step(i["k_step"], i["state"], u.cpu().numpy(), i["params"])
-    assert b.core.device_status() == 0
-    for i in inst:
-        i["c"].core.close()
-    b.core.close()
-
-
 def test_batched_online_equals_single():
     """E = 2, N = 256, m = 2, four steps: row e of a_mean, a_cov, the costs and the factor is torch.equal to the single controller on
     instance e alone; the batch shares one age."""
@@ -270,8 +155,8 @@ def test_two_passes_of_a_reuse_step_share_one_sigma(graph, monkeypatch):
     """iters = 2, m = 2: the reuse step shifts the refresh step's factor ONCE -- after both passes a_cov and the factor are
     core.sigma_shift of it -- and iter_cost_min has two finite entries, the last one the minimum of the last pass's costs."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, sigma_period=2, iters=2)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=2, iters=2)
     key = cr.PRNGKey(13)
     L_prev = None
     for step in range(6):
@@ -294,8 +179,9 @@ def test_two_passes_of_a_reuse_step_share_one_sigma(graph, monkeypatch):
 def test_reuse_step_next_to_the_other_options(monkeypatch):
     """update="guarded", elite = 32, compute_diag on a reuse step: it runs and every row is finite."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, sigma_period=2, update="guarded", elite=32, compute_diag=True)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=2, update="guarded", elite=32,
+                                                        compute_diag=True)
     key = cr.PRNGKey(17)
     for step in range(2):
         key, k_act, k_step = cr.split(key, 3)
@@ -316,12 +202,12 @@ def test_run_episode_equals_the_python_loop(graph, monkeypatch):
     schedule has wrapped twice: the next step refreshes, the last one ran at age m - 1."""
     from covo_mpc_amd.envs.quadrotor import DeviceEpisode
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     m, N = 3, 256
     T = 2 * m
     out = {}
     for kind in ("episode", "steps"):
-        c, cp, _, _, _, params = _controller(env, N, sigma_period=m)
+        c, cp, _, _, _, params = single_controller(env, "covo-online", N, sigma_period=m)
         c.alias_outputs = True
         ep = DeviceEpisode(env, cr.PRNGKey(21), params, (c.core.lib, c.core.h), c.core.device)
         cp = c.reset(ep.state0, params, cp, cr.PRNGKey(22))
@@ -348,8 +234,8 @@ def test_run_episode_equals_the_python_loop(graph, monkeypatch):
 
 def test_reset_and_a_period_change_set_the_age_to_zero(monkeypatch):
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, sigma_period=3)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=3)
     step = lambda cp: c(obs, state, params, cr.PRNGKey(3), cp, info)
     _, cp1, i0 = step(cp)
     assert i0["sigma_age"] == 0 and c.core.sigma_age == 1
@@ -382,8 +268,8 @@ def test_closed_loop_hovering_sixty_steps(monkeypatch):
     """N = 1 024, m = 4, 60 steps of the hovering task against the host env: every u finite, the instance never terminated, and the
     quadrotor stays near its target."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env(task="hovering")
-    c, cp, obs, info, state, params = _controller(env, 1024, sigma_period=4)
+    env = quad_env(task="hovering")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 1024, sigma_period=4)
     cp = c.reset(state, params, cp, cr.PRNGKey(2))
     key = cr.PRNGKey(31)
     us = []
@@ -407,8 +293,8 @@ def test_refusals_on_the_device(name, monkeypatch):
     """A period above 1 attached through the C entry to a handle that steps in the MPPI / covo-offline mode: CovoError naming it before
     any launch; detached, the same handle steps."""
     monkeypatch.setenv("COVO_NO_GRAPH", "1")
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, name=name)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, name, 256, offline_table=False)
     if name == "covo-offline":
         cp = c.reset(state, params, cp, cr.PRNGKey(2))
     assert c.core.lib.covo_set_step_sigma_period(c.core.h, 0) != 0 and b"period=0" in c.core.lib.covo_last_error()
@@ -425,8 +311,8 @@ def test_refusals_on_the_device(name, monkeypatch):
 
 
 def test_kernel_by_kernel_path_refuses_a_period():
-    env = _env()
-    c, cp, obs, info, state, params = _controller(env, 256, sigma_period=2)
+    env = quad_env(task="tracking_zigzag")
+    c, cp, obs, info, state, params = single_controller(env, "covo-online", 256, sigma_period=2)
     c.materialize_eps = True
     with pytest.raises(NotImplementedError, match="sigma_period=2"):
         c(obs, state, params, cr.PRNGKey(3), cp, info)

@@ -11,7 +11,7 @@ rounded (0.5 ulp), so operation for operation it may lose at most twice what the
 bars of tests/test_gpu_parity.py.  Positions (statistics, fan): max(2e-5, 2 x the fp32 oracle's own loss).  Hessian: 1e-9 relative to
 max(1, max|ref|), exactly symmetric; with a force table 1e-9 against the oracle fed the same rows and 2e-8 against the model
 functions.  Sigma: 1e-6 relative Frobenius (benign entries).  Env step: 2e-5 max(1, |x|); reset: as tests/test_gpu_reset.py.  PID
-nominal: 5e-5 states, 2e-4 means.  Production steps: tests/test_gpu_parity.py::_oracle_check_of_a_fused_step.
+nominal: 5e-5 states, 2e-4 means.  Production steps: tests/gpu_cases.py::_oracle_check_of_a_fused_step.
 """
 import functools
 
@@ -31,13 +31,11 @@ from covo_mpc_amd.dynamics.dataclass import EnvParams3D  # noqa: E402
 from oracle import c_oracle as CO  # noqa: E402
 from oracle import ref_np as R  # noqa: E402
 from tests.conftest import make_problem  # noqa: E402
+from tests.gpu_cases import _oracle_check_of_a_fused_step, _run_rollout, check_plan_against_oracle  # noqa: E402
+from tests.gpu_support import (DEV, DP, POS_BAR, build_with_discount, dev_state, params_c, perturbed_hover_mean, quad_env,  # noqa: E402
+                               sample_actions, split_rows, start_episode, to_stripes, ulps, uniform_draws, want_idx)
 from tests.state_atlas import (BENIGN, NAMES, ROLLOUT_SEED, ROLLOVER_AT_0, atlas_state, euler_quat, loss3, rel_err,  # noqa: E402
                                rollout_case)
-from tests.test_gpu_fan import POS_BAR, split_rows, want_idx  # noqa: E402
-from tests.test_gpu_models import DP, params_c, uniform_draws  # noqa: E402
-from tests.test_gpu_parity import (DEV, _oracle_check_of_a_fused_step, _run_rollout, dev_state, sample_actions,  # noqa: E402
-                                   to_stripes)
-from tests.test_gpu_reset import _ulps  # noqa: E402
 
 f32 = np.float32
 M = 2.0  # see the header
@@ -176,10 +174,9 @@ def _env_state(template, s, traj=True):
 
 def test_plan_trace_at_far_fast():
     """One step of a compute_plan controller planning from far_fast: the plan row through tests/test_gpu_trace.py's checker."""
-    from tests.test_gpu_trace import _build, _env, _start, check_plan_against_oracle
-    env = _env("gaussian", False, "tracking_zigzag")
-    c, cp = _build(env, "mppi", 1024)
-    cp, obs, info, state, params = _start(env, c, cp, "mppi")
+    env = quad_env(task="tracking_zigzag")
+    c, cp = build_with_discount(env, "mppi", 1024)
+    cp, obs, info, state, params = start_episode(env, c, cp, "mppi")
     ns = _env_state(info["noisy_state"], atlas_state("far_fast")[0])
     k_act = cr.split(cr.PRNGKey(7), 3)[1]
     u, cp, cinfo = c(obs, state, params, k_act, cp, dict(info, noisy_state=ns))
@@ -190,18 +187,11 @@ def test_plan_trace_at_far_fast():
 
 
 # ------------------------------------------------------------------------------------------ e: Hessian
-def _mean(p, rng, scale):
-    a = (R.hover_action(p, 32, np.float64) + scale * rng.normal(size=(32, 4))).astype(f32)
-    a[3, 1] = 1.0    # exact clip ties (tests/test_gpu_parity.py::test_hessian_vs_ad_oracle)
-    a[5, 2] = -1.0
-    return a.reshape(-1)
-
-
 @functools.lru_cache(maxsize=None)
 def _hessian_case(name, scale):
     """(s, a, ref, {method: device Hessian}) -- computed once, shared by the Hessian, batch and Sigma tests"""
     s, p, rng = atlas_state(name)
-    a = _mean(p, rng, scale)
+    a = perturbed_hover_mean(p, rng, scale)
     ref = CO.hessian(s, p, a.astype(np.float64), 32)
     core = _core(256, 1.0)
     ds = dev_state(s)
@@ -236,7 +226,7 @@ def test_hessian_model_variants_off_hover(name, kind, reward):
     tests/test_gpu_models.py::test_hessian_reward_and_disturbance_variants_vs_ad_oracle."""
     s, p, rng = atlas_state(name)
     p = p.replace(disturb_params=DP)
-    a = _mean(p, rng, 0.1)
+    a = perturbed_hover_mean(p, rng, 0.1)
     key = cr.PRNGKey(21)
     core = _core(256, 1.0)
     ds, pc = dev_state(s), params_c(p, kind, reward)
@@ -294,19 +284,13 @@ def test_sigma_of_the_atlas_hessians(method):
 
 
 # ------------------------------------------------------------------------------------------ g: env step
-def _quad_env(rollover=False):
-    import covo_mpc_amd as cm
-    return cm.envs.Quad3D(task="tracking_zigzag", enable_randomizer=False, disturb_type="gaussian",
-                          disable_rollover_terminate=not rollover, generate_noisy_state=True, device=DEV)
-
-
 @pytest.mark.parametrize("name", ["inverted", "roll_120_spin", "far_fast", "near_singular", "yaw_pi_minus", "yaw_3quarter_neg"])
 def test_env_step_kernel_vs_host_env_off_hover(name):
     """tests/test_gpu_parity.py::test_env_step_kernel_vs_host_env from the atlas state with actions the env's clip cuts.  The two
     yaw entries keep yd < 0 for the whole run: the logged reward is the only user of the fp32 qm::atan2abs_ (the rollouts have
     rollout_pipe.hpp's own body), and a roll or a decaying spin alone never takes it into its x < 0 branch."""
     import covo_mpc_amd as cm
-    env = _quad_env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     core = _core(256, 1.0)
     ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(11), params, (core.lib, core.h), DEV)
@@ -350,7 +334,7 @@ def test_env_step_rollover_triggers_the_auto_reset(trial, name):
     the Python env's step on the same key as tests/test_gpu_reset.py::test_device_reset_vs_host_reset_env compares its box resets
     (same keys as its trials 0, 1 and 2, hence the same new trajectories and the same cap on elements one ulp apart)."""
     import covo_mpc_amd as cm
-    env = _quad_env(rollover=True)
+    env = quad_env(task="tracking_zigzag", rollover=True)
     params = env.default_params.replace(disturb_scale=0.3)
     core = _core(256, 1.0)
     ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(11 + trial), params, (core.lib, core.h), DEV)
@@ -367,7 +351,7 @@ def test_env_step_rollover_triggers_the_auto_reset(trial, name):
     traj_d = [t.cpu().numpy() for t in (ep.pos_traj, ep.vel_traj, ep.acc_traj)]
     differing = 0
     for d, h in zip(traj_d, [st_h.pos_traj, st_h.vel_traj, st_h.acc_traj]):
-        assert d.shape == h.shape and _ulps(d, h) <= 1.0, (name, _ulps(d, h))
+        assert d.shape == h.shape and ulps(d, h) <= 1.0, (name, ulps(d, h))
         differing += int(np.sum(d != h))
     assert differing <= 2, differing
     t_dev, n_dev = ep.true.cpu().numpy(), ep.noisy.cpu().numpy()
@@ -383,7 +367,7 @@ def test_env_step_rollover_triggers_the_auto_reset(trial, name):
     assert abs(log[0, 1] - info["err_pos"]) < 1e-6 and abs(log[0, 2] - info["err_vel"]) < 1e-6  # errors of the RESET state
     assert not np.array_equal(traj_d[0], ep.state0.pos_traj)  # a NEW trajectory
     # the same state with the rollover test off is not terminal: the vehicle flies on
-    env0 = _quad_env()
+    env0 = quad_env(task="tracking_zigzag")
     ep0 = cm.envs.DeviceEpisode(env0, cr.PRNGKey(11 + trial), params, (core.lib, core.h), DEV)
     ep0.true.copy_(torch.from_numpy(state.pack()).to(DEV))
     ep0.step(k_step, torch.from_numpy(u).to(DEV))
@@ -397,7 +381,7 @@ def test_pid_nominal_device_vs_host_off_hover(name):
     and velocity replaced (its own trajectory and targets kept): the PID law with the thrust clipped at 0, a large e3 x z_d angle,
     an inverted / non-unit Q."""
     import covo_mpc_amd as cm
-    env = _quad_env()
+    env = quad_env(task="tracking_zigzag")
     controller, cp = cm.envs.get_controller(env, "covo-offline", "N1024_H32_lam0.01", device=DEV)
     params = env.default_params
     obs, info, state = env.reset(cr.PRNGKey(31), params)
@@ -424,7 +408,7 @@ def test_production_step_from_an_upset_state(name, N, state_name):
     """One fused control step (the plumbing of tests/test_gpu_parity.py::test_controller_step_teacher_forced, production path) whose
     noisy state is the atlas entry: cost, Sigma and mean through _oracle_check_of_a_fused_step."""
     import covo_mpc_amd as cm
-    env = _quad_env()
+    env = quad_env(task="tracking_zigzag")
     controller, cp = cm.envs.get_controller(env, name, f"N{N}_H32_lam0.01", device=DEV)
     params = env.default_params
     obs, info, state = env.reset(cr.PRNGKey(1), params)

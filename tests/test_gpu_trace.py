@@ -22,58 +22,8 @@ if not torch.cuda.is_available():
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.dynamics.dataclass import as_device_state  # noqa: E402
-
-DEV = "cuda:0"
-H = 32
-
-
-def rel_err(x, ref):
-    return abs(float(x) - float(ref)) / max(abs(float(ref)), 1.0)
-
-
-def _env(disturb="gaussian", rollover=False, task="tracking_zigzag", randomizer=False):
-    import covo_mpc_amd as cm
-    return cm.envs.Quad3D(task=task, obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type=disturb, disable_rollover_terminate=not rollover, generate_noisy_state=True, device=DEV)
-
-
-def _build(env, name, N, lam="0.01", discount=1.0, plan=True, diag=False):
-    """(controller, control params) with the given discount (get_controller fixes 1.0: the controller is rebuilt around it)"""
-    import covo_mpc_amd as cm
-    c, cp = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam}", device=DEV, compute_info=False, compute_diag=diag,
-                                   compute_plan=plan)
-    if discount == 1.0:
-        return c, c.init_control_params
-    c.core.close()
-    cp = cp.replace(discount=discount)
-    if name == "mppi":
-        c = cm.controllers.MPPIController(env=env, control_params=cp, N=N, H=H, lam=float(lam), device=DEV, compute_info=False,
-                                          compute_diag=diag, compute_plan=plan)
-    else:
-        c = cm.controllers.CoVOController(env=env, control_params=cp, N=N, H=H, lam=float(lam), device=DEV, compute_info=False,
-                                          mode="offline" if "offline" in name else "online", compute_diag=diag, compute_plan=plan)
-    return c, c.init_control_params
-
-
-def _start(env, c, cp, name, seed=1):
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(seed), params)
-    if name == "covo-offline":
-        cp = c.reset(state, params, cp, cr.PRNGKey(seed + 1))
-    return cp, obs, info, state, params
-
-
-def _step_inputs(env, c, name, params, k_act, dstate, core1):
-    """The disturbance inputs the sample rollouts of a step with raw key k_act had: (f_shared host 3-vector, device table or None),
-    formed as the controllers' kernel-by-kernel path forms them (covo.py:212,225,231 / mppi.py:53,69,74)."""
-    step_key = cr.split(cr.split(k_act)[0])[1]
-    pc = c._params_c(params)
-    det = name != "mppi"
-    if pc.disturb_kind in _lib.TABLE_DISTURB_KINDS:
-        return (0.0, 0.0, 0.0), core1.disturb_table(pc, dstate.packed, key=step_key, key_mode=_lib.DISTURB_KEYS_SHARED, deterministic=det)
-    if det:
-        return (0.0, 0.0, 0.0), None
-    return tuple(float(x) for x in env.rollout_disturbance(step_key, params, deterministic=False)), None
+from tests.gpu_cases import check_plan_against_oracle  # noqa: E402
+from tests.gpu_support import DEV, H, batched_controller, build_with_discount, quad_env, start_episode, step_inputs  # noqa: E402
 
 
 PLAN_CASES = [
@@ -97,9 +47,9 @@ def test_plan_cost_is_the_rollout_kernels(name, N, disturb, task, rollover, disc
     """After each of three closed-loop steps: cost_plan == covo_rollout_cost(N = 1, a = clip(a_mean_new), the step's f_disturb_shared /
     f_disturb_steps)[0], bit for bit."""
     from covo_mpc_amd.controllers._core import SamplingCore
-    env = _env(disturb, rollover, task)
-    c, cp = _build(env, name, N, discount=discount)
-    cp, obs, info, state, params = _start(env, c, cp, name)
+    env = quad_env(task=task, rollover=rollover, disturb=disturb)
+    c, cp = build_with_discount(env, name, N, discount=discount)
+    cp, obs, info, state, params = start_episode(env, c, cp, name)
     core1 = SamplingCore(1, H, 0.01, discount, device=DEV, compute_info=False)
     key = cr.PRNGKey(3)
     for step in range(3):
@@ -108,7 +58,7 @@ def test_plan_cost_is_the_rollout_kernels(name, N, disturb, task, rollover, disc
         u, cp, cinfo = c(obs, state, params, k_act, cp, info)
         assert tuple(cinfo["pos_plan"].shape) == (H, 3) and cinfo["cost_plan"].dim() == 0
         assert cinfo["cost_plan"].data_ptr() == c.core.plan.data_ptr()  # views: no copy, no sync
-        f_shared, tab = _step_inputs(env, c, name, params, k_act, dstate, core1)
+        f_shared, tab = step_inputs(env, c, name, params, k_act, dstate, core1)
         core1.a.copy_(cp.a_mean.clamp(-1.0, 1.0).view(H, 1, 4))
         ref = core1.rollout(dstate, c._params_c(params), f_shared, False, f_steps=tab)
         torch.cuda.synchronize()
@@ -122,37 +72,15 @@ def test_plan_cost_is_the_rollout_kernels(name, N, disturb, task, rollover, disc
     core1.close()
 
 
-def check_plan_against_oracle(env, name, params, ns, k_act, cp, cinfo, where):
-    """The plan row of one step (cinfo of a compute_plan controller, cp its new control params) against oracle.c_oracle.rollout in
-    fp64 on clip(a_mean_new) from the noisy state `ns` with the step's shared vector: positions within 2e-5, cost within 1e-5
-    relative.  -> (rewards, poses) of the oracle."""
-    from oracle import c_oracle as CO
-    from oracle import ref_np as R
-    fs = np.zeros(3)
-    if name == "mppi":
-        step_key = cr.split(cr.split(k_act)[0])[1]
-        fs = np.asarray(env.rollout_disturbance(step_key, params, deterministic=False), dtype=np.float64)
-    so = R.State(pos=ns.pos, vel=ns.vel, quat=ns.quat, omega=ns.omega, f_disturb=ns.f_disturb, pos_tar=ns.pos_tar,
-                 vel_tar=ns.vel_tar, acc_tar=ns.acc_tar, time=ns.time, pos_traj=ns.pos_traj, vel_traj=ns.vel_traj,
-                 acc_traj=ns.acc_traj).astype(np.float64)
-    a = cp.a_mean.clamp(-1.0, 1.0).cpu().numpy().astype(np.float64)[None]
-    cost_ref, rew, poses = CO.rollout(so, R.Params().fp32(), a, 1.0, fs, dtype=np.float64, want_rewards=True, want_poses=True)
-    dpos = np.abs(cinfo["pos_plan"].cpu().numpy() - poses[:, 0]).max()
-    dcost = rel_err(cinfo["cost_plan"].cpu().numpy(), cost_ref[0])
-    print(f"  {where}: |pos_plan - poses| {dpos:.2e}, cost rel {dcost:.2e}")
-    assert dpos < 2e-5 and dcost < 1e-5, (where, dpos, dcost)
-    return rew, poses
-
-
 @pytest.mark.parametrize("name,N,time0", [("covo-online", 1024, None), ("covo-offline", 1024, None), ("mppi", 1024, None),
                                           ("covo-online", 65536, 290), ("mppi", 65536, 290)])
 def test_plan_against_the_fp64_oracle(name, N, time0):
     """oracle.c_oracle.rollout in fp64 on clip(a_mean_new) from the same noisy state with the same shared vector: positions within
     2e-5, cost within 1e-5 relative.  time0 = 290: the plan terminates inside the horizon (time >= 300 from rollout step 10), so
     the reward freeze is exercised while the positions keep integrating."""
-    env = _env("gaussian", False, "tracking_zigzag")
-    c, cp = _build(env, name, N)
-    cp, obs, info, state, params = _start(env, c, cp, name)
+    env = quad_env(task="tracking_zigzag")
+    c, cp = build_with_discount(env, name, N)
+    cp, obs, info, state, params = start_episode(env, c, cp, name)
     key = cr.PRNGKey(7)
     for step in range(2):
         key, k_act, k_step = cr.split(key, 3)
@@ -176,10 +104,10 @@ def test_nothing_else_moves(name, N, diag, graph, monkeypatch):
     """Two controllers on the same inputs, one with compute_plan (both with diagnostics in the `diag` pairs): u, a_mean, a_cov, the
     actions, the costs and the diagnostics are torch.equal over 10 closed-loop steps."""
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env()
-    ca, cpa = _build(env, name, N, plan=True, diag=diag)
-    cb, cpb = _build(env, name, N, plan=False, diag=diag)
-    cpa, obs, info, state, params = _start(env, ca, cpa, name)
+    env = quad_env(task="tracking_zigzag")
+    ca, cpa = build_with_discount(env, name, N, plan=True, diag=diag)
+    cb, cpb = build_with_discount(env, name, N, plan=False, diag=diag)
+    cpa, obs, info, state, params = start_episode(env, ca, cpa, name)
     if name == "covo-offline":
         cpb = cpb.replace(a_cov_offline=cpa.a_cov_offline, a_chol_offline=cpa.a_chol_offline)
     key = cr.PRNGKey(11)
@@ -206,7 +134,7 @@ def test_trace_rows_are_the_episode(name):
     """run_episode for 24 steps with the trace against the same controller stepped by hand (the loop of
     test_run_episode_equals_python_loop) copying ep.true, ep.noisy and u before every env step."""
     import covo_mpc_amd as cm
-    env = _env(task="hovering" if name == "mppi" else "tracking_zigzag")
+    env = quad_env(task="hovering" if name == "mppi" else "tracking_zigzag")
     params = env.default_params
     n = 24
     got = {}
@@ -254,7 +182,7 @@ def test_trace_through_a_reset():
     """A start 5 cm inside the box with outward velocity (the scripted terminal episode of tests/test_gpu_reset.py): the row whose
     log has done = 1 holds the terminal pre-step state, the next row the reset state with time 0."""
     import covo_mpc_amd as cm
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     controller, _ = cm.envs.get_controller(env, "mppi", "N1024_H32_lam0.01", device=DEV, compute_info=False, compute_plan=True)
     controller.alias_outputs = True
@@ -276,23 +204,13 @@ def test_trace_through_a_reset():
     core.close()
 
 
-def _batched(env, name, cp0, E, N, **kw):
-    import covo_mpc_amd as cm
-    if name == "mppi":
-        return cm.controllers.BatchedMPPIController(env, E, N, H, 0.01, sigmas=cp0.sample_sigma, discount=cp0.discount,
-                                                    gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=DEV, **kw)
-    return cm.controllers.BatchedCoVOController(env, E, N, H, 0.01, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
-                                                sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV,
-                                                mode="offline" if name == "covo-offline" else "online", **kw)
-
-
 @pytest.mark.parametrize("name", ["covo-online", "covo-offline", "mppi"])
 def test_batched_trace_equals_single(name):
     """E = 4 domain-randomised instances, 8 closed-loop steps from one covo_run_episode_batched[_mode] call: instance e's trace rows
     (states, u, plan) and its row of controller.plan equal covo_run_episode on instance e alone, bit for bit."""
     import covo_mpc_amd as cm
     N, E, n = 1024, 4, 8
-    env = _env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     rngs0 = np.stack([np.asarray(cr.PRNGKey(60 + e)) for e in range(E)])
@@ -308,7 +226,7 @@ def test_batched_trace_equals_single(name):
         singles.append((se.read_trace(), se.read_log(), c.core.plan[0].cpu().numpy().copy()))
         cp0 = c.init_control_params
         c.core.close()
-    b = _batched(env, name, cp0, E, N, compute_plan=True)
+    b = batched_controller(env, name, cp0, E, N, 0.01, compute_plan=True)
     assert tuple(b.plan.shape) == (E, _lib.COVO_PLAN_FLOATS)
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     if name == "covo-offline":
@@ -330,7 +248,7 @@ def test_batched_trace_equals_single(name):
 
 def test_eval_env_batched_trace_shapes():
     import covo_mpc_amd as cm
-    env = _env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True)
     err, tr = cm.envs.quadrotor.eval_env_batched(env, 3, "N1024_H32_lam0.01", n_steps=6, device=DEV, verbose=False, trace=True)
     assert err.shape == (3,)
     assert tr["state"].shape == (3, 6, 32) and tr["noisy"].shape == (3, 6, 32) and tr["u"].shape == (3, 6, 4)
@@ -344,7 +262,7 @@ def test_refusals():
     import ctypes as C
     import covo_mpc_amd as cm
     from covo_mpc_amd._lib import CovoError, check, ptr
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     # (a) sample-sharded single step
     c, _ = cm.envs.get_controller(env, "mppi", "N1024_H32_lam0.01", device=DEV, compute_info=False, compute_plan=True)
@@ -384,11 +302,11 @@ def test_refusals():
     core.close()
     # (d) a batched step with more instances than plan rows
     E, N = 3, 1024
-    envr = _env(task="tracking", randomizer=True)
+    envr = quad_env(task="tracking", randomizer=True)
     c0, _ = cm.envs.get_controller(envr, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False)
     cp0 = c0.init_control_params
     c0.core.close()
-    b = _batched(envr, "covo-online", cp0, E, N, compute_plan=True)
+    b = batched_controller(envr, "covo-online", cp0, E, N, 0.01, compute_plan=True)
     check(b.core.lib.covo_set_step_plan(b.core.h, ptr(b.plan), 2), "covo_set_step_plan")
     ps = [envr.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     ep = cm.envs.BatchedDeviceEpisode(envr, [cr.PRNGKey(50 + e) for e in range(E)], ps, (b.core.lib, b.core.h), DEV)
@@ -408,7 +326,7 @@ def test_render_env_on_the_device_is_a_consistent_episode(tmp_path, monkeypatch)
     import covo_mpc_amd as cm
     from covo_mpc_amd.envs.quadrotor import render_env
     monkeypatch.chdir(tmp_path)
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     controller, cp = cm.envs.get_controller(env, "covo-offline", "N1024_H32_lam0.01", device=DEV, compute_info=False, compute_plan=True)
     seq = render_env(env, controller, cp, filename="dev", save=True)
     controller.core.close()

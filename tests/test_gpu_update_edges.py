@@ -25,9 +25,8 @@ if not torch.cuda.is_available():
 from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
 from tests import update_oracle as U  # noqa: E402
-from tests.test_gpu_parity import to_stripes  # noqa: E402
+from tests.gpu_support import DEV, to_stripes  # noqa: E402
 
-DEV = "cuda:0"
 N_MAX = max(U.EDGE_SIZES)
 GAMMA_SIGMA = 0.3
 COVO_E_BADARG = -1

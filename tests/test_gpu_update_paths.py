@@ -31,35 +31,10 @@ from covo_mpc_amd import _lib  # noqa: E402
 from covo_mpc_amd import random as cr  # noqa: E402
 from covo_mpc_amd.controllers._core import SamplingCore  # noqa: E402
 from tests import update_oracle as U  # noqa: E402
+from tests.gpu_support import DEV, instances, quad_env, single_controller  # noqa: E402
 
-DEV = "cuda:0"
 LAMS = (0.01, 0.1, 1.0, 1e4)
 REGIMES = ("few", "some", "all")
-
-
-def _env(randomizer=False, task="tracking_zigzag"):
-    import covo_mpc_amd as cm
-    return cm.envs.Quad3D(task=task, obs_type="quad_params" if randomizer else "quad", enable_randomizer=randomizer,
-                          disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device=DEV)
-
-
-_OFFLINE = {}
-
-
-def _controller(env, name, N, lam, seed=1):
-    """A single controller at the start of an episode: (controller, control params, obs, info, state, params).  covo-offline's Sigma
-    table depends on neither N nor lambda: built once (tests/test_gpu_diag.py::_controller)."""
-    import covo_mpc_amd as cm
-    c, _ = cm.envs.get_controller(env, name, f"N{N}_H32_lam{lam!r}", device=DEV, compute_info=False)
-    params = env.default_params
-    obs, info, state = env.reset(cr.PRNGKey(seed), params)
-    cp = c.init_control_params
-    if name == "covo-offline":
-        if seed not in _OFFLINE:
-            t = c.reset(state, params, cp, cr.PRNGKey(seed + 1))
-            _OFFLINE[seed] = (t.a_cov_offline, t.a_chol_offline)
-        cp = cp.replace(a_cov_offline=_OFFLINE[seed][0], a_chol_offline=_OFFLINE[seed][1])
-    return c, cp, obs, info, state, params
 
 
 class Coverage:
@@ -88,13 +63,13 @@ class Coverage:
 
 def _single_path(path, name, N, graph, monkeypatch, gamma_mean=1.0, gamma_sigma=0.0, fuse_small=None):
     monkeypatch.setenv("COVO_GRAPH" if graph == "graph" else "COVO_NO_GRAPH", "1")
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     cov_check = gamma_sigma != 0.0
     cover = Coverage(f"{path} {name} {graph}", N)
     first = {}
 
     def run(lam):
-        c, cp, obs, info, state, params = _controller(env, name, N, lam)
+        c, cp, obs, info, state, params = single_controller(env, name, N, lam=repr(lam))
         assert c.core.uses_graph == (graph == "graph")
         if fuse_small is not None:
             _lib.check(c.core.lib.covo_debug_set_fuse_small(c.core.h, fuse_small), "fuse_small")
@@ -158,32 +133,18 @@ def test_mppi_covariance_adaptation(N, graph, monkeypatch):
     _single_path("MPPI gamma_sigma", "mppi", N, graph, monkeypatch, gamma_sigma=0.3)
 
 
-# ------------------------------------------------------------------------------------------ env-batched steps
-def _instances(env, E, seed=0):
-    inst = []
-    for e in range(E):
-        params = env.sample_params(cr.PRNGKey(seed + 100 + e))
-        obs, info, state = env.reset(cr.PRNGKey(seed + 200 + e), params)
-        rng = np.random.default_rng(seed + 1000 + e)
-        for k in range(2 + e % 4):
-            u = (0.3 * rng.standard_normal(4)).clip(-1, 1).astype(np.float32)
-            obs, state, _, _, info = env.step(cr.PRNGKey(seed + 5000 + 10 * e + k), state, u, params)
-        inst.append(dict(params=params, obs=obs, info=info, state=state, key=cr.PRNGKey(seed + 300 + e),
-                         reset_key=cr.PRNGKey(seed + 400 + e)))
-    return inst
-
-
 _TABLES = {}
 
 
+# ------------------------------------------------------------------------------------------ env-batched steps
 def _batched_path(path, name, staged, N=1024, E=3):
     import covo_mpc_amd as cm
-    env = _env(randomizer=True, task="tracking")
+    env = quad_env(task="tracking", randomizer=True)
     cover = Coverage(f"{path} {name}", N)
     first = {}
 
     def run(lam):
-        inst = _instances(env, E)
+        inst = instances(env, None, None, None, E, controllers=False)
         hover = env.default_params.m * env.default_params.g / env.default_params.max_thrust * 2.0 - 1.0
         a0 = torch.tensor([hover, 0.0, 0.0, 0.0], dtype=torch.float32).repeat(32, 1)
         kw = dict(staged=True) if staged else {}
@@ -236,7 +197,7 @@ def test_sharded_rank_records_merged_on_one_gpu():
     covo_merge_ranks merges the two -- against mean64 on the 2 048 costs and actions of both shards."""
     from covo_mpc_amd.dynamics.dataclass import as_device_state
     n, G = 1024, 2
-    env = _env()
+    env = quad_env(task="tracking_zigzag")
     params = env.default_params
     obs, info, state = env.reset(cr.PRNGKey(3), params)
     dstate = as_device_state(info["noisy_state"], DEV)

@@ -2,25 +2,16 @@
 surface."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
 
 
 def test_iters_entry_point_exists_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"#define COVO_HAS_STEP_ITERS 1\b", hdr) and built.COVO_HAS_STEP_ITERS == 1
     assert int(re.search(r"#define COVO_MAX_STEP_ITERS\s+(\d+)", hdr).group(1)) == 16 == built.COVO_MAX_STEP_ITERS
     assert re.search(r"\bint covo_set_step_iters\(covo_handle_t h, int32_t iters, float \*iter_log, int32_t n_inst\);", hdr)

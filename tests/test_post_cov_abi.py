@@ -1,65 +1,20 @@
 """CPU: the ABI of the posterior covariance (covo_set_step_post_cov / covo_weighted_cov, include/covo_hip.h), the `compute_post_cov`
-keyword of the Python surface, and `ref_weighted_cov`: the fp64 restatement of the definition the GPU tests compare against."""
+keyword of the Python surface, and `ref_weighted_cov` (tests/post_cov_oracle.py), the fp64 restatement of the definition the GPU tests
+compare against, on hand-derived answers."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
 import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-NA = 128
-
-
-def ref_weights(cost, lam=None, elite=None):
-    """The weights of the definition, fp64: softmax exp(-(c - c_min) / lam) over the finite costs, or 1 on the `elite` samples of
-    smallest key (cost, index) -- a NaN cost sorts last, +inf is a large cost -- and 0 elsewhere; a cost that is not finite weighs 0."""
-    c = np.asarray(cost, dtype=np.float64).reshape(-1)
-    fin = np.isfinite(c)
-    w = np.zeros_like(c)
-    if elite:
-        key = np.where(np.isnan(c), np.inf, c)
-        order = np.lexsort((np.arange(c.size), np.isnan(c), key))  # cost, then NaN last, then the lowest index
-        w[order[:int(elite)]] = 1.0
-        w[~fin] = 0.0
-    elif fin.any():
-        w[fin] = np.exp(-(c[fin] - c[fin].min()) / float(lam))
-    return w
-
-
-def ref_weighted_cov(a, cost, mu, lam=None, elite=None):
-    """a [H, N, 4], cost [N], mu [128] (any float dtype, taken as they are) -> (C [128, 128], d [128], W, absS [128, 128]) in fp64:
-    x_i[4 t + j] = a[t, i, j], y_i = x_i - mu, W = sum w, d = sum w y / W, C = sum w y y^T / W - d d^T;
-    absS = sum w |y| |y|^T / W, the scale of the GPU tests' bar.  W = 0: zeros."""
-    a = np.asarray(a, dtype=np.float64)
-    N = a.shape[1]
-    x = a.transpose(1, 0, 2).reshape(N, NA)
-    y = x - np.asarray(mu, dtype=np.float64).reshape(1, NA)
-    w = ref_weights(cost, lam, elite)
-    W = w.sum()
-    if not W > 0.0:
-        z = np.zeros((NA, NA))
-        return z, np.zeros(NA), 0.0, z
-    live = w > 0.0  # a sample of weight 0 is dropped whatever it holds
-    y, w = y[live], w[live]
-    d = (w[:, None] * y).sum(axis=0) / W
-    C_ = (y * w[:, None]).T @ y / W - np.outer(d, d)
-    absS = (np.abs(y) * w[:, None]).T @ np.abs(y) / W
-    return C_, d, W, absS
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
+from tests.post_cov_oracle import NA, ref_weighted_cov, ref_weights
 
 
 def test_post_cov_entry_points_exist_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"#define COVO_HAS_POST_COV 1\b", hdr) and built.COVO_HAS_POST_COV == 1
     assert int(re.search(r"#define COVO_POST_AUX_FLOATS\s+(\d+)", hdr).group(1)) == 132 == built.COVO_POST_AUX_FLOATS
     P, I = C.c_void_p, C.c_int32

@@ -1,6 +1,6 @@
 """CPU: the ABI of Sigma adapt (covo_set_step_sigma_adapt / covo_sigma_adapt; include/covo_hip.h), the `sigma_adapt` keyword of the
 Python surface, and the numpy fp64 restatement of a reuse step's adapted covariance with its known answers.  The
-restatement is written from the definition; tests/test_gpu_sigma_adapt.py holds the kernel against it."""
+restatement (tests/sigma_shift_oracle.py) is written from the definition; tests/test_gpu_sigma_adapt.py holds the kernel against it."""
 import ctypes as C
 import inspect
 import os
@@ -9,51 +9,11 @@ import re
 import numpy as np
 import pytest
 
-from tests.test_post_cov_abi import ref_weighted_cov
-from tests.test_sigma_period_abi import DU, N_A, random_spd, shift_S, shift_sigma_ref, volume_scalar
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
+from tests.post_cov_oracle import ref_weighted_cov
+from tests.sigma_shift_oracle import DU, N_A, adapt_ref, blend_M, random_spd, shift_sigma_ref, volume_scalar
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-# ---------------------------------------------------------------------------------------------- the restatement (fp64 numpy)
-def blend_M(Sigma, Cmat, gamma):
-    """M = (1 - gamma) S(Sigma) + gamma S(C); the lower triangle of C is what counts (the kernel reads nothing else)."""
-    Cl = np.tril(np.asarray(Cmat, dtype=np.float64))
-    Cs = Cl + np.tril(Cl, -1).T
-    g = float(gamma)
-    return (1.0 - g) * shift_S(np.asarray(Sigma, dtype=np.float64)) + g * shift_S(Cs)
-
-
-def guarded_factor(M):
-    """The lower Cholesky factor of M, or None when the guard fires: a pivot that is not finite or not positive, or a log det that
-    is not finite."""
-    if not np.all(np.isfinite(M)):
-        return None
-    try:
-        Lf = np.linalg.cholesky(M)
-    except np.linalg.LinAlgError:
-        return None
-    d = np.diag(Lf)
-    if not (np.all(np.isfinite(d)) and np.all(d > 0.0) and np.isfinite(np.log(d).sum())):
-        return None
-    return Lf
-
-
-def adapt_ref(L, Cmat, gamma, sample_sigma):
-    """(Sigma', L', fallback, c, log det M) of the definition from the factor L the previous step sampled from (its lower triangle)
-    and that step's posterior covariance C: Sigma' = c M, M = (1 - gamma) S(L L^T) + gamma S(C); a blend the guard refuses gives the
-    gamma = 0 answer with fallback = 1."""
-    L = np.tril(np.asarray(L, dtype=np.float64))
-    Sigma = L @ L.T
-    fallback = 0
-    M = blend_M(Sigma, Cmat, gamma) if float(gamma) != 0.0 else shift_S(Sigma)
-    Lf = guarded_factor(M)
-    if Lf is None:
-        fallback, M = 1, shift_S(Sigma)
-        Lf = np.linalg.cholesky(M)
-    logdet = 2.0 * np.log(np.diag(Lf)).sum()
-    c = float(np.exp((2.0 * N_A * np.log(float(sample_sigma)) - logdet) / N_A))
-    return c * M, np.sqrt(c) * Lf, fallback, c, logdet
 
 
 def block_diag(blocks):
@@ -181,17 +141,9 @@ def test_a_nan_or_an_indefinite_c_gives_the_gamma_zero_answer_with_the_flag(gamm
 
 
 # ---------------------------------------------------------------------------------------------- the ABI and the keyword
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
-
-
 def test_sigma_adapt_entry_points_exist_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"#define COVO_HAS_SIGMA_ADAPT 1\b", hdr) and built.COVO_HAS_SIGMA_ADAPT == 1
     assert int(re.search(r"#define COVO_SIGMA_ADAPT_FLOATS\s+(\d+)", hdr).group(1)) == 4 == built.COVO_SIGMA_ADAPT_FLOATS
     assert re.search(r"\bint covo_set_step_sigma_adapt\(covo_handle_t h, float gamma, float \*rows_out[^,]*, int32_t n_inst\);", hdr)

@@ -1,6 +1,7 @@
 """CPU: the ABI of the Sigma period (covo_set_step_sigma_period, covo_step_sigma_age, covo_sigma_shift; include/covo_hip.h), the
 `sigma_period` keyword of the Python surface, and the numpy restatement of a reuse step's covariance with its known
-answers.  The restatement is written from the definition; tests/test_gpu_sigma_period.py holds the kernel against it."""
+answers.  The restatement (tests/sigma_shift_oracle.py) is written from the definition; tests/test_gpu_sigma_period.py holds the
+kernel against it."""
 import ctypes as C
 import inspect
 import os
@@ -9,125 +10,11 @@ import re
 import numpy as np
 import pytest
 
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
+from tests.sigma_shift_oracle import (DU, N_A, chain_ratios, decoupled_rows, off_structure, random_spd, random_spd_factors, rank_update,
+                                      shift_chain_ref, shift_factor_ref, shift_power_ref, shift_S, shift_sigma_ref, volume_scalar)
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N_A, DU = 128, 4
-
-
-# ---------------------------------------------------------------------------------------------- the restatement (fp64 numpy)
-def shift_S(Sigma):
-    """S(Sigma): the trailing 124 x 124 block moved up, the old last stage's 4 x 4 marginal as the new last stage, no cross terms."""
-    S = np.zeros_like(Sigma, dtype=np.float64)
-    S[:N_A - DU, :N_A - DU] = Sigma[DU:, DU:]
-    S[N_A - DU:, N_A - DU:] = Sigma[N_A - DU:, N_A - DU:]
-    return S
-
-
-def volume_scalar(S, sample_sigma):
-    """c with log det (c S) = 2 n log sample_sigma."""
-    sign, logdet = np.linalg.slogdet(S)
-    assert sign > 0
-    return float(np.exp((2.0 * N_A * np.log(float(sample_sigma)) - logdet) / N_A))
-
-
-def shift_sigma_ref(Sigma, sample_sigma):
-    """Sigma' = c S(Sigma) from the covariance itself."""
-    S = shift_S(np.asarray(Sigma, dtype=np.float64))
-    return volume_scalar(S, sample_sigma) * S
-
-
-def rank_update(Lmat, X):
-    """The lower factor of Lmat Lmat^T + X X^T by one rotation per column and update vector (the issue's recurrence):
-    r = sqrt(L_kk^2 + x_k^2), c = r / L_kk, s = x_k / L_kk, L_ik <- (L_ik + s x_i) / c, x_i <- c x_i - s L_ik."""
-    Lw = np.array(Lmat, dtype=np.float64)
-    n = Lw.shape[0]
-    for j in range(X.shape[1]):
-        x = np.array(X[:, j], dtype=np.float64)
-        for k in range(n):
-            r = np.hypot(Lw[k, k], x[k])
-            c, s = r / Lw[k, k], x[k] / Lw[k, k]
-            Lw[k, k] = r
-            if k + 1 < n:
-                Lw[k + 1:, k] = (Lw[k + 1:, k] + s * x[k + 1:]) / c
-                x[k + 1:] = c * x[k + 1:] - s * Lw[k + 1:, k]
-    return Lw
-
-
-def shift_factor_ref(L, sample_sigma):
-    """(Sigma', L') from the factor alone, as the kernel forms them: the rank-4 update of L22 by the columns of L21, the factor of
-    L[124:, :] L[124:, :]^T, c from the diagonal."""
-    L = np.tril(np.asarray(L, dtype=np.float64))
-    Lp = np.zeros((N_A, N_A))
-    Lp[:N_A - DU, :N_A - DU] = rank_update(L[DU:, DU:], L[DU:, :DU])
-    Lp[N_A - DU:, N_A - DU:] = np.linalg.cholesky(L[N_A - DU:, :] @ L[N_A - DU:, :].T)
-    logdet = 2.0 * np.log(np.diag(Lp)).sum()
-    c = np.exp((2.0 * N_A * np.log(float(sample_sigma)) - logdet) / N_A)
-    Lp *= np.sqrt(c)
-    return Lp @ Lp.T, Lp
-
-
-def shift_power_ref(Sigma, k, sample_sigma):
-    """c_k S^k(Sigma) written down directly: k shifts leave the trailing 128 - 4 k rows and columns of Sigma in the corner and k
-    copies of its last stage's 4 x 4 marginal B = Sigma[124:, 124:] below them, no cross terms; from k = 31 on that is 32 copies of
-    B, whatever k."""
-    Sigma = np.asarray(Sigma, dtype=np.float64)
-    j = min(int(k), N_A // DU - 1)
-    m = N_A - DU * j
-    S = np.zeros((N_A, N_A))
-    S[:m, :m] = Sigma[DU * j:, DU * j:]
-    for t in range(j):
-        S[m + DU * t:m + DU * t + DU, m + DU * t:m + DU * t + DU] = Sigma[N_A - DU:, N_A - DU:]
-    return volume_scalar(S, sample_sigma) * S
-
-
-def shift_chain_ref(L, k, sample_sigma, rounded=True, every=False):
-    """(Sigma', L') after k reuse steps in a row: shift_factor_ref applied k times, each step fed the previous one's L' rounded to
-    fp32 -- what the device keeps between steps (rounded=False: the fp64 L' as it is).  every=True: the list of all k results."""
-    out = []
-    for _ in range(int(k)):
-        Sp, Lp = shift_factor_ref(L, sample_sigma)
-        out.append((Sp, Lp))
-        L = Lp.astype(np.float32) if rounded else Lp
-    return out if every else out[-1]
-
-
-def decoupled_rows(k):
-    """After k shifts the rows from here on hold decoupled 4 x 4 stages only."""
-    return N_A - DU * min(int(k), N_A // DU - 1)
-
-
-BAR_L, BAR_SIGMA, BAR_LOGDET = 3e-6, 1e-6, 2 * N_A * 2.0 ** -24  # one reuse step's bars (tests/test_gpu_sigma_period.py)
-
-
-def off_structure(k):
-    """True where Sigma' and L' are exactly zero after k shifts: everything outside the leading corner and the decoupled 4 x 4 stages."""
-    m = decoupled_rows(k)
-    off = np.ones((N_A, N_A), dtype=bool)
-    off[:m, :m] = False
-    for t in range(m, N_A, DU):
-        off[t:t + DU, t:t + DU] = False
-    return off
-
-
-def chain_ratios(Sp, Lp, Sref, Lref, sample_sigma):
-    """(log det, L', Sigma') errors of an fp32 (Sigma', L') against a reference, each over its one-step bar."""
-    Sp64, Lp64 = np.asarray(Sp, dtype=np.float64), np.asarray(Lp, dtype=np.float64)
-    e_ld = abs(2.0 * np.log(np.diag(Lp64)).sum() - 2.0 * N_A * np.log(float(sample_sigma)))
-    e_L = np.abs(Lp64 - Lref).max() / np.abs(Lref).max()
-    e_S = np.abs(Sp64 - Sref).max() / np.abs(Sref).max()
-    return np.array([e_ld / BAR_LOGDET, e_L / BAR_L, e_S / BAR_SIGMA])
-
-
-def random_spd(rng, cond=1e3):
-    w = np.exp(np.linspace(0.0, np.log(cond), N_A)) * 1e-2
-    U, _ = np.linalg.qr(rng.normal(size=(N_A, N_A)))
-    A = (U * w) @ U.T
-    return 0.5 * (A + A.T)  # exactly symmetric
-
-
-def random_spd_factors():
-    """The fp32 factors of random_spd at cond 6e2 and 7e4 (the matrices of test_rank4_update_equals_the_cholesky_of_the_trailing_block)."""
-    rng = np.random.default_rng(12)
-    return [np.linalg.cholesky(random_spd(rng, cond)).astype(np.float32) for cond in (6e2, 7e4)]
 
 
 def golden_factors(sample_sigma, which=(0, 5, 9, 13)):
@@ -301,17 +188,9 @@ def test_fp32_chain_stays_within_the_one_step_bars_of_the_closed_form():
 
 
 # ---------------------------------------------------------------------------------------------- the ABI and the keyword
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
-
-
 def test_sigma_period_entry_points_exist_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"#define COVO_HAS_SIGMA_PERIOD 1\b", hdr) and built.COVO_HAS_SIGMA_PERIOD == 1
     assert int(re.search(r"#define COVO_MAX_SIGMA_PERIOD\s+(\d+)", hdr).group(1)) == 64 == built.COVO_MAX_SIGMA_PERIOD
     assert re.search(r"\bint covo_set_step_sigma_period\(covo_handle_t h, int32_t period\);", hdr)

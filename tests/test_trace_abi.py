@@ -2,27 +2,17 @@
 of the Python surface, and render_env (quadrotor.py:594-667 without the plots) on the host path."""
 import ctypes as C
 import inspect
-import os
 import pickle
 import re
 
 import numpy as np
-import pytest
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-@pytest.fixture(scope="module")
-def built():
-    import __graft_entry__ as g
-    g.build()
-    from covo_mpc_amd import _lib
-    return _lib
+from tests.abi_support import built, header_text  # noqa: F401  (built: a fixture)
 
 
 def test_plan_trace_entry_points_exist_with_the_declared_types(built):
     lib = built.load_library()
-    hdr = open(os.path.join(ROOT, "include", "covo_hip.h")).read()
+    hdr = header_text()
     assert re.search(r"int covo_set_step_plan\(covo_handle_t h, float \*plan, int32_t n_inst\);", hdr)
     assert re.search(r"int covo_set_episode_trace\(covo_handle_t h, float \*trace, int32_t stride\);", hdr)
     assert re.search(r"#define COVO_HAS_PLAN_TRACE 1\b", hdr)
