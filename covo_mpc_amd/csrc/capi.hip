@@ -61,6 +61,15 @@ static int check_model(const covo_env_params *p, const char *what)
         if (rc_) return rc_;               \
     } while (0)
 
+// what both episode drivers enqueue behind every control step, ahead of its env step: the after-step frame (`frame`: the single or the
+// batched one, given the step's row), then the copied episode logs (the posterior covariance's rows are formed in the frame)
+template <class Frame>
+static int episode_step_tail(covo_ctx *h, Frame frame, int n_inst, int row, hipStream_t s)
+{
+    if (int rc = frame(row)) return rc;
+    return launch_episode_rows(h, n_inst, row, h->sigma_last_age, s);
+}
+
 __global__ void raise_status_kernel(int *status, int bits)
 {
     __hip_atomic_fetch_or(status, bits, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
@@ -691,15 +700,28 @@ int covo_set_step_diag(covo_handle_t h, float *diag, int32_t n_inst)
     return 0;
 }
 
+// what the five setters of the episode logs share (covo_eplog_kinds, covo_common.hpp): with a log, stride > 0 (stride_fmt: the setter's
+// own text) and the attachment the log follows is on; the null-handle check and the setter's extras stay with the setter
+static int set_episode_log(covo_ctx *h, int kind, float *log, int stride, const char *stride_fmt)
+{
+    const covo_eplog_kind &k = covo_eplog_kinds[kind];
+    REQUIRE(log == nullptr || stride > 0, stride_fmt, stride);
+    if (log != nullptr && k.on != nullptr && !k.on(h)) {
+        if (kind < COVO_EPLOG_KINDS) covo_set_error("covo_set_episode_rows: kind=%d: %s", kind, k.off);
+        else covo_set_error("%s", k.off);
+        return COVO_E_BADARG;
+    }
+    h->eplog[kind] = {log, log ? stride : 0};
+    return 0;
+}
+
 int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride)
 {
     REQUIRE(h, "covo_set_episode_diag_log: null handle");
-    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_diag_log: stride=%d", stride);
     const float *before = covo_diag_target(h);
-    h->diag_log = log;
-    h->diag_log_stride = log ? stride : 0;
+    const int rc = set_episode_log(h, COVO_EPLOG_DIAG, log, stride, "covo_set_episode_diag_log: stride=%d");
     if (covo_diag_target(h) != before) ++h->opt.epoch;
-    return 0;
+    return rc;
 }
 
 // ---- the ESS floor (ess_lambda.hip).  The captured step graphs bake in the staged launch set, ess_min and where the solver writes:
@@ -773,10 +795,7 @@ int covo_set_step_plan(covo_handle_t h, float *plan, int32_t n_inst)
 int covo_set_episode_trace(covo_handle_t h, float *trace, int32_t stride)
 {
     REQUIRE(h, "covo_set_episode_trace: null handle");
-    REQUIRE(trace == nullptr || stride > 0, "covo_set_episode_trace: stride=%d", stride);
-    h->trace = trace;
-    h->trace_stride = trace ? stride : 0;
-    return 0;
+    return set_episode_log(h, COVO_EPLOG_TRACE, trace, stride, "covo_set_episode_trace: stride=%d");
 }
 
 // ---- the sample fan (sample_fan.hip).  Like the plan's, its launch is eager and follows the step: no captured step graph changes
@@ -787,14 +806,13 @@ int covo_set_step_fan(covo_handle_t h, float *fan, const int32_t *idx, int32_t K
         h->fan_out = nullptr;
         h->fan_idx = nullptr;
         h->fan_K = h->fan_n = 0;
-        h->fanlog = nullptr;
-        h->fanlog_stride = 0;
+        covo_eprow_drop(h, COVO_EPLOG_FAN);
         return 0;
     }
     REQUIRE(K >= 1 && K <= COVO_FAN_MAX, "covo_set_step_fan: K=%d outside [1, %d]", K, COVO_FAN_MAX);
     REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_fan: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
     REQUIRE(K <= h->cfg.n_local, "covo_set_step_fan: K=%d > n_samples: the handle has n_local=%d samples", K, h->cfg.n_local);
-    REQUIRE(h->fanlog == nullptr || K == h->fan_K, "covo_set_step_fan: K=%d differs from the attached episode log's K=%d "
+    REQUIRE(h->eplog[COVO_EPLOG_FAN].log == nullptr || K == h->fan_K, "covo_set_step_fan: K=%d differs from the attached episode log's K=%d "
             "(detach it first: covo_set_episode_fan(h, NULL, 0))", K, h->fan_K);
     h->fan_out = fan;
     h->fan_idx = idx;
@@ -806,11 +824,7 @@ int covo_set_step_fan(covo_handle_t h, float *fan, const int32_t *idx, int32_t K
 int covo_set_episode_fan(covo_handle_t h, float *fanlog, int32_t stride)
 {
     REQUIRE(h, "covo_set_episode_fan: null handle");
-    REQUIRE(fanlog == nullptr || stride > 0, "covo_set_episode_fan: stride=%d", stride);
-    REQUIRE(fanlog == nullptr || h->fan_K > 0, "covo_set_episode_fan: no fan size: call covo_set_step_fan (K, idx, n_inst) first");
-    h->fanlog = fanlog;
-    h->fanlog_stride = fanlog ? stride : 0;
-    return 0;
+    return set_episode_log(h, COVO_EPLOG_FAN, fanlog, stride, "covo_set_episode_fan: stride=%d");  // (its rows are [fan_K][COVO_FAN_FLOATS])
 }
 
 // covo_rollout_fan, covo_arbitrate: the caller's buffers and shared vector (derive_keys = 0) as the descriptor of a step's instance
@@ -856,8 +870,7 @@ int covo_set_step_arbiter(covo_handle_t h, float *rows, int32_t mask, int32_t n_
     if (rows == nullptr) {  // off, the log with it
         h->arb_out = nullptr;
         h->arb_mask = h->arb_n = 0;
-        h->arblog = nullptr;
-        h->arblog_stride = 0;
+        covo_eprow_drop(h, COVO_EPLOG_ARB);
         return 0;
     }
     REQUIRE(mask >= 1 && mask <= 7, "covo_set_step_arbiter: mask=%d outside [1, 7] (bit 0: softmax mean, 1: nominal, 2: best sample)", mask);
@@ -871,11 +884,7 @@ int covo_set_step_arbiter(covo_handle_t h, float *rows, int32_t mask, int32_t n_
 int covo_set_episode_arbiter_log(covo_handle_t h, float *log, int32_t stride)
 {
     REQUIRE(h, "covo_set_episode_arbiter_log: null handle");
-    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_arbiter_log: stride=%d", stride);
-    REQUIRE(log == nullptr || covo_arb_on(h), "covo_set_episode_arbiter_log: no arbiter attached: call covo_set_step_arbiter first");
-    h->arblog = log;
-    h->arblog_stride = log ? stride : 0;
-    return 0;
+    return set_episode_log(h, COVO_EPLOG_ARB, log, stride, "covo_set_episode_arbiter_log: stride=%d");
 }
 
 // ---- the posterior covariance (post_cov.hip).  Like the plan's and the fan's, its launches are eager and follow the step: no captured
@@ -1022,31 +1031,14 @@ int covo_set_episode_rows(covo_handle_t h, int32_t kind, float *log, int32_t str
 {
     REQUIRE(h, "covo_set_episode_rows: null handle");
     REQUIRE(kind >= 0 && kind < COVO_EPLOG_KINDS, "covo_set_episode_rows: kind=%d outside [0, %d) (COVO_EPLOG_*)", kind, COVO_EPLOG_KINDS);
-    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_rows: stride=%d", stride);
-    if (log != nullptr) {
-        const struct {
-            bool on;
-            const char *what;
-        } needs[COVO_EPLOG_KINDS] = {
-            {covo_lam_target(h) != nullptr, "no ESS floor attached: call covo_set_step_ess_floor (ess_min > 0) first"},
-            {covo_elite_target(h) != nullptr, "no elite-set update attached: call covo_set_step_elite (K > 0) first"},
-            {covo_step_iters(h) > 1, "no iteration log attached: call covo_set_step_iters (iters > 1, iter_log) first"},
-            {covo_sigma_period(h) > 1, "no Sigma period: call covo_set_step_sigma_period (period > 1) first"},
-            {covo_post_cov_on(h), "no posterior covariance attached: call covo_set_step_post_cov first"},
-            {covo_post_cov_on(h), "no posterior covariance attached: call covo_set_step_post_cov first"},
-        };
-        REQUIRE(needs[kind].on, "covo_set_episode_rows: kind=%d: %s", kind, needs[kind].what);
-    }
-    h->eprow_log[kind] = log;
-    h->eprow_stride[kind] = log ? stride : 0;
-    return 0;
+    return set_episode_log(h, kind, log, stride, "covo_set_episode_rows: stride=%d");
 }
 
 // ---- what a step checks about everything attached to its handle -- diagnostics, plan / trace, sample fan, update arbiter, ESS floor,
 // iterations, elite set -- for every entry point alike (covo_mpc_step, covo_run_episode and, through check_batch_step, the four env-batched
 // ones): a step of n_samples samples for n_inst instances.  The order is fixed: first what a sample-sharded step
 // (partial_out != NULL) cannot have at all, in the order above; then, in the same order, each attachment's own ranges and the rows
-// of its buffer.  A new attachment adds its lines here (and its log to check_episode_logs), nowhere else.
+// of its buffer.  A new attachment adds its lines here (and its log to covo_eplog_kinds, covo_common.hpp), nowhere else.
 static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, int mode, const float *a_cov,
                                   const char *what)
 {
@@ -1147,27 +1139,13 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
 // an episode driver that writes rows [first_row, first_row + n_steps) of every attached log (the single driver: first_row = 0)
 static int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, const char *what)
 {
-    const struct {
-        const char *name, *setter;
-        bool on;
-        int rows;
-    } logs[] = {
-        {"diagnostic log", "covo_set_episode_diag_log", h->diag_log != nullptr, h->diag_log_stride},
-        {"episode trace", "covo_set_episode_trace", h->trace != nullptr, h->trace_stride},
-        {"episode fan log", "covo_set_episode_fan", h->fanlog != nullptr, h->fanlog_stride},
-        {"episode arbiter log", "covo_set_episode_arbiter_log", h->arblog != nullptr, h->arblog_stride},
-        {"episode temperature log", "covo_set_episode_rows, COVO_EPLOG_LAM", h->eprow_log[COVO_EPLOG_LAM] != nullptr, h->eprow_stride[COVO_EPLOG_LAM]},
-        {"episode elite log", "covo_set_episode_rows, COVO_EPLOG_ELITE", h->eprow_log[COVO_EPLOG_ELITE] != nullptr, h->eprow_stride[COVO_EPLOG_ELITE]},
-        {"episode iteration log", "covo_set_episode_rows, COVO_EPLOG_ITERS", h->eprow_log[COVO_EPLOG_ITERS] != nullptr, h->eprow_stride[COVO_EPLOG_ITERS]},
-        {"episode Sigma log", "covo_set_episode_rows, COVO_EPLOG_SIGMA", h->eprow_log[COVO_EPLOG_SIGMA] != nullptr, h->eprow_stride[COVO_EPLOG_SIGMA]},
-        {"episode posterior side-row log", "covo_set_episode_rows, COVO_EPLOG_POST_AUX", h->eprow_log[COVO_EPLOG_POST_AUX] != nullptr,
-         h->eprow_stride[COVO_EPLOG_POST_AUX]},
-        {"episode posterior covariance log", "covo_set_episode_rows, COVO_EPLOG_POST_COV", h->eprow_log[COVO_EPLOG_POST_COV] != nullptr,
-         h->eprow_stride[COVO_EPLOG_POST_COV]},
-    };
-    for (const auto &l : logs)
-        REQUIRE(!l.on || (first_row >= 0 && first_row + n_steps <= l.rows), "%s: %s rows [%d, %d) outside [0, %d) (%s)", what, l.name,
-                first_row, first_row + n_steps, l.rows, l.setter);
+    // the first offender is reported: the four logs with setters of their own, then covo_set_episode_rows' kinds
+    static const int order[COVO_EPLOG_ALL] = {COVO_EPLOG_DIAG,  COVO_EPLOG_TRACE, COVO_EPLOG_FAN,   COVO_EPLOG_ARB,      COVO_EPLOG_LAM,
+                                              COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV};
+    for (const int k : order)
+        REQUIRE(h->eplog[k].log == nullptr || (first_row >= 0 && first_row + n_steps <= h->eplog[k].stride),
+                "%s: %s rows [%d, %d) outside [0, %d) (%s)", what, covo_eplog_kinds[k].name, first_row, first_row + n_steps,
+                h->eplog[k].stride, covo_eplog_kinds[k].setter);
     return 0;
 }
 
@@ -1245,6 +1223,25 @@ static void host_philox_split(const uint32_t key[2], uint32_t i, uint32_t child[
     child[1] = c1;
 }
 
+// every argument check of a single step (covo_mpc_step, and each step of covo_run_episode): nothing is launched before all of them
+// have passed
+static int check_single_step(const covo_ctx *h, const covo_env_params *params, const covo_step_args *args, const char *what)
+{
+    REQUIRE(args->mode >= 0 && args->mode <= 2, "%s: mode=%d", what, args->mode);
+    REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "%s: n_samples=%d outside (0, %d]", what, args->n_samples,
+            h->cfg.n_local);
+    REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin && args->T > 0,
+            "%s: null buffer", what);
+    REQUIRE(args->mode != COVO_MODE_COVO_OFFLINE || (args->L_table && args->n_table > 0), "%s: offline needs L_table", what);
+    REQUIRE(args->mode != COVO_MODE_MPPI || args->a_cov, "%s: mppi needs a_cov", what);
+    CHECK_MODEL(params, what);
+    REQUIRE(args->gamma_sigma == 0.0f || args->mode == COVO_MODE_MPPI, "%s: gamma_sigma != 0 is MPPI's covariance adaptation (mppi.py:119-125)",
+            what);
+    REQUIRE(!covo_needs_tables(*params) || args->derive_keys == 1, "%s: disturb_kind=%d needs derive_keys = 1 (the per-step "
+            "disturbance tables are derived from the raw controller key on the device)", what, params->disturb_kind);
+    return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, what);
+}
+
 int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, float *state_true,
                      const float *acc_traj, int32_t noisy_on, float obs_noise_scale, float *log, uint32_t *rng,
                      int32_t n_steps, void *stream)
@@ -1254,15 +1251,10 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     REQUIRE(params && args && state_true && acc_traj && rng && n_steps > 0, "covo_run_episode: bad argument");
     REQUIRE(args->derive_keys == 1, "covo_run_episode: args->derive_keys must be 1 (the controller key is the raw rng_act)");
     REQUIRE(args->a_mean_in == nullptr, "covo_run_episode: args->a_mean_in must be NULL (the episode carries the mean in args->a_mean)");
-    CHECK_MODEL(params, "covo_run_episode");
     REQUIRE(args->partial_out == nullptr || (exchange_ready(h) && args->a_mean_shift != nullptr),
             "covo_run_episode: a sample-sharded step (partial_out != NULL) needs the peer-write exchange (covo_exchange_create / "
             "covo_exchange_connect) and a_mean_shift");
-    REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin &&
-                args->T > 0 && args->mode >= 0 && args->mode <= 2,
-            "covo_run_episode: bad step arguments");
-    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov,
-                                    "covo_run_episode");
+    int rc = check_single_step(h, params, args, "covo_run_episode");
     if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
@@ -1295,10 +1287,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
                     return rc;
             }
         }
-        if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, 1, h->diag_log_stride, t, s))) return rc;
-        if ((rc = covo_plan_after_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, t, s))) return rc;
-        // (behind the after-step frame: the posterior covariance's rows are formed there)
-        if (covo_eprow_any(h) && (rc = launch_episode_rows(h, 1, t, h->sigma_last_age, s))) return rc;
+        auto frame = [&](int row) { return covo_plan_after_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, row, s); };
+        if ((rc = episode_step_tail(h, frame, 1, t, s))) return rc;
         rc = launch_env_step(state_true, const_cast<float *>(args->state), args->pos_traj, args->vel_traj, acc_traj, args->T,
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
@@ -1450,11 +1440,10 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
                   : covo_batched_staged(h) ? covo_step_batched_staged_impl(h, &norm, params, act_keys, s)
                                            : covo_step_batched_small_impl(h, &norm, params, act_keys, s)))
             return rc;
-        if (h->diag_log != nullptr && (rc = launch_diag_log_rows(covo_diag_target(h), h->diag_log, E, h->diag_log_stride, log_index + t, s)))
-            return rc;
-        if ((rc = covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : norm.mode, params, states_true, log_index + t, s)))
-            return rc;
-        if (covo_eprow_any(h) && (rc = launch_episode_rows(h, E, log_index + t, h->sigma_last_age, s))) return rc;
+        auto frame = [&](int row) {
+            return covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : norm.mode, params, states_true, row, s);
+        };
+        if ((rc = episode_step_tail(h, frame, E, log_index + t, s))) return rc;
         if ((rc = launch_env_step_batched(states_true, const_cast<float *>(args->states), args->pos_traj, args->vel_traj, acc_traj,
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
                                           log_stride, log_index + t, s)))
@@ -1569,21 +1558,7 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
     REQUIRE(h, "covo_mpc_step: null handle");
     CHECK_DEVICE(h, "covo_mpc_step");
     REQUIRE(params && args, "covo_mpc_step: null argument");
-    REQUIRE(args->mode >= 0 && args->mode <= 2, "covo_mpc_step: mode=%d", args->mode);
-    REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "covo_mpc_step: n_samples=%d outside (0, %d]",
-            args->n_samples, h->cfg.n_local);
-    REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin &&
-                args->T > 0,
-            "covo_mpc_step: null buffer");
-    REQUIRE(args->mode != COVO_MODE_COVO_OFFLINE || (args->L_table && args->n_table > 0), "covo_mpc_step: offline needs L_table");
-    REQUIRE(args->mode != COVO_MODE_MPPI || args->a_cov, "covo_mpc_step: mppi needs a_cov");
-    CHECK_MODEL(params, "covo_mpc_step");
-    REQUIRE(args->gamma_sigma == 0.0f || args->mode == COVO_MODE_MPPI,
-            "covo_mpc_step: gamma_sigma != 0 is MPPI's covariance adaptation (mppi.py:119-125)");
-    REQUIRE(!covo_needs_tables(*params) || args->derive_keys == 1, "covo_mpc_step: disturb_kind=%d needs derive_keys = 1 (the per-step "
-            "disturbance tables are derived from the raw controller key on the device)", params->disturb_kind);
-    int rc = check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov,
-                                    "covo_mpc_step");
+    int rc = check_single_step(h, params, args, "covo_mpc_step");
     if (rc) return rc;
     if ((rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream))) return rc;
     return covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream);

@@ -25,6 +25,10 @@ struct CovoOpts {
 };
 CovoOpts covo_default_opts();  // step.hip
 
+// the episode logs by internal kind: the six COVO_EPLOG_* kinds of covo_set_episode_rows (include/covo_hip.h), then the four with setters of
+// their own
+enum { COVO_EPLOG_DIAG = COVO_EPLOG_KINDS, COVO_EPLOG_TRACE, COVO_EPLOG_FAN, COVO_EPLOG_ARB, COVO_EPLOG_ALL };
+
 struct covo_ctx {
     covo_config cfg;
     CovoOpts opt;
@@ -51,21 +55,15 @@ struct covo_ctx {
     // per-step sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log); all null / 0: off
     float *diag_out;          // caller's [diag_n][COVO_DIAG_FLOATS]: instance e's row of every step
     int diag_n;
-    float *diag_log;          // caller's [n_inst][diag_log_stride][COVO_DIAG_FLOATS]: the episode drivers copy each step's rows there
-    int diag_log_stride;
     float *diag_scratch;      // [COVO_MAX_ENVS][COVO_DIAG_FLOATS]: where the steps write when only the log is attached
     float *ws_diag_rec;       // [max_blocks][4] stage-1 diagnostic records next to ws_partials (softmax_merge.hpp)
     // the flight recorder (covo_set_step_plan / covo_set_episode_trace; plan_trace.hip); all null / 0: off
     float *plan_out;          // caller's [plan_n][COVO_PLAN_FLOATS]: instance e's plan row of every step
     int plan_n;
-    float *trace;             // caller's [n_inst][trace_stride][COVO_TRACE_FLOATS]: the episode drivers' steps write their rows there
-    int trace_stride;
     // the sample fan (covo_set_step_fan / covo_set_episode_fan; sample_fan.hip); all null / 0: off
     float *fan_out;           // caller's [fan_n][fan_K][COVO_FAN_FLOATS]: instance e's fan of every step
     const int32_t *fan_idx;   // caller's [fan_n][fan_K] sample indices, or null: the stride
     int fan_K, fan_n;
-    float *fanlog;            // caller's [n_inst][fanlog_stride][fan_K][COVO_FAN_FLOATS]: the episode drivers' steps write their rows there
-    int fanlog_stride;
     // the ESS floor (covo_set_step_ess_floor; ess_lambda.hip); ess_min == 0: off
     float ess_min;
     float *lam_out;           // caller's [lam_n][COVO_LAM_FLOATS]: instance e's solver row of every step; null: lam_own
@@ -79,8 +77,6 @@ struct covo_ctx {
     // the update arbiter (covo_set_step_arbiter / covo_set_episode_arbiter_log; update_arbiter.hip); arb_out null: off
     float *arb_out;           // caller's [arb_n][COVO_ARB_FLOATS]: instance e's arbiter row of every step
     int arb_mask, arb_n;      // enabled candidates (bits 0..2), rows of arb_out
-    float *arblog;            // caller's [n_inst][arblog_stride][COVO_ARB_FLOATS]: the episode drivers' steps write their rows there
-    int arblog_stride;
     // what the three launches that follow a step keep on the device (plan_trace.hip, sample_fan.hip, update_arbiter.hip)
     void *after;              // AfterState (after_step.hpp): a batched step's argument blocks per launch, the arbiter's nominals
     // iterations per control step (covo_set_step_iters); iters <= 1 or iter_log null: off
@@ -103,20 +99,24 @@ struct covo_ctx {
     float adapt_gamma;        // the weight of the previous step's posterior covariance in a reuse step's Sigma', in (0, 1)
     float *adapt_rows;        // caller's [adapt_n][COVO_SIGMA_ADAPT_FLOATS]: instance e's {fallback, c, log det M, 0} of every reuse step
     int adapt_n;
-    // the episode logs of the attachments' rows (covo_set_episode_rows; episode_rows.hip), by COVO_EPLOG_* kind; null: off
-    float *eprow_log[COVO_EPLOG_KINDS];   // caller's [n_inst][eprow_stride[k]][width of kind k]: the episode drivers copy each step's rows there
-    int eprow_stride[COVO_EPLOG_KINDS];
+    // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
+    struct {
+        float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
+        int stride;
+    } eplog[COVO_EPLOG_ALL];
 };
-static inline void covo_eprow_drop(covo_ctx *h, int kind)
-{
-    h->eprow_log[kind] = nullptr;
-    h->eprow_stride[kind] = 0;
-}
+static inline void covo_eprow_drop(covo_ctx *h, int kind) { h->eplog[kind] = {nullptr, 0}; }
+// a log of covo_set_episode_rows (the six public kinds) is attached
 static inline bool covo_eprow_any(const covo_ctx *h)
 {
     for (int k = 0; k < COVO_EPLOG_KINDS; ++k)
-        if (h->eprow_log[k] != nullptr) return true;
+        if (h->eplog[k].log != nullptr) return true;
     return false;
+}
+// instance e's rows of the log of `kind` (row_floats per row), or null
+static inline float *covo_eplog_inst(const covo_ctx *h, int kind, int e, int row_floats)
+{
+    return h->eplog[kind].log ? h->eplog[kind].log + (size_t)e * h->eplog[kind].stride * row_floats : nullptr;
 }
 static inline bool covo_post_cov_on(const covo_ctx *h) { return h->post_cov_out != nullptr; }
 static inline bool covo_sigma_adapt_on(const covo_ctx *h) { return h->adapt_rows != nullptr && h->adapt_gamma > 0.0f; }
@@ -149,12 +149,52 @@ static inline float *covo_elite_target(const covo_ctx *h) { return h->elite_K > 
 static inline int covo_elite_capacity(const covo_ctx *h) { return h->elite_out ? h->elite_n : COVO_MAX_ENVS; }
 // a step whose update waits for all costs (ESS floor, elite set): rollout without in-launch records, no one-launch small step
 static inline bool covo_update_staged(const covo_ctx *h) { return covo_lam_target(h) != nullptr || covo_elite_target(h) != nullptr; }
-static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->trace != nullptr; }
-static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->fanlog != nullptr; }
+static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->eplog[COVO_EPLOG_TRACE].log != nullptr; }
+static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->eplog[COVO_EPLOG_FAN].log != nullptr; }
 static inline bool covo_arb_on(const covo_ctx *h) { return h->arb_out != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
-static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->diag_log ? h->diag_scratch : nullptr); }
-static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->diag_log ? COVO_MAX_ENVS : 0); }
+static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->eplog[COVO_EPLOG_DIAG].log ? h->diag_scratch : nullptr); }
+static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->eplog[COVO_EPLOG_DIAG].log ? COVO_MAX_ENVS : 0); }
+
+// ---- the episode logs, one entry per kind: what the setters (capi.hip: set_episode_log), check_episode_logs and launch_episode_rows
+// know about a log.  A new log adds its kind and its entry here (and its place in check_episode_logs' order), nowhere else.
+struct covo_eprows {
+    const float *src;  // [n_inst][width]: the rows the step that has just been enqueued left (the Sigma log: Sigma adapt's rows, or null)
+    int width;
+};
+struct covo_eplog_kind {
+    const char *name, *setter;        // as check_episode_logs prints them
+    bool (*on)(const covo_ctx *);     // the attachment the log follows is on (null: the log needs none) ...
+    const char *off;                  // ... and what its setter says when it is not
+    covo_eprows (*rows)(const covo_ctx *);  // what launch_episode_rows copies; null: the attachment's own launch writes the log's rows
+};
+static const covo_eplog_kind covo_eplog_kinds[COVO_EPLOG_ALL] = {
+    {"episode temperature log", "covo_set_episode_rows, COVO_EPLOG_LAM", [](const covo_ctx *h) { return covo_lam_target(h) != nullptr; },
+     "no ESS floor attached: call covo_set_step_ess_floor (ess_min > 0) first",
+     [](const covo_ctx *h) { return covo_eprows{covo_lam_target(h), COVO_LAM_FLOATS}; }},
+    {"episode elite log", "covo_set_episode_rows, COVO_EPLOG_ELITE", [](const covo_ctx *h) { return covo_elite_target(h) != nullptr; },
+     "no elite-set update attached: call covo_set_step_elite (K > 0) first",
+     [](const covo_ctx *h) { return covo_eprows{covo_elite_target(h), COVO_ELITE_FLOATS}; }},
+    {"episode iteration log", "covo_set_episode_rows, COVO_EPLOG_ITERS", [](const covo_ctx *h) { return covo_step_iters(h) > 1; },
+     "no iteration log attached: call covo_set_step_iters (iters > 1, iter_log) first",
+     [](const covo_ctx *h) { return covo_eprows{covo_step_iters(h) > 1 ? h->iter_log : nullptr, covo_step_iters(h)}; }},
+    {"episode Sigma log", "covo_set_episode_rows, COVO_EPLOG_SIGMA", [](const covo_ctx *h) { return covo_sigma_period(h) > 1; },
+     "no Sigma period: call covo_set_step_sigma_period (period > 1) first",
+     [](const covo_ctx *h) { return covo_eprows{covo_sigma_adapt_on(h) ? h->adapt_rows : nullptr, COVO_SIGMA_LOG_FLOATS}; }},
+    {"episode posterior side-row log", "covo_set_episode_rows, COVO_EPLOG_POST_AUX", covo_post_cov_on,
+     "no posterior covariance attached: call covo_set_step_post_cov first",
+     [](const covo_ctx *h) { return covo_eprows{h->post_aux_out, COVO_POST_AUX_FLOATS}; }},
+    {"episode posterior covariance log", "covo_set_episode_rows, COVO_EPLOG_POST_COV", covo_post_cov_on,
+     "no posterior covariance attached: call covo_set_step_post_cov first",
+     [](const covo_ctx *h) { return covo_eprows{h->post_cov_out, COVO_NA * COVO_NA}; }},
+    {"diagnostic log", "covo_set_episode_diag_log", nullptr, nullptr,
+     [](const covo_ctx *h) { return covo_eprows{covo_diag_target(h), COVO_DIAG_FLOATS}; }},
+    {"episode trace", "covo_set_episode_trace", nullptr, nullptr, nullptr},
+    {"episode fan log", "covo_set_episode_fan", [](const covo_ctx *h) { return h->fan_K > 0; },
+     "covo_set_episode_fan: no fan size: call covo_set_step_fan (K, idx, n_inst) first", nullptr},
+    {"episode arbiter log", "covo_set_episode_arbiter_log", covo_arb_on,
+     "covo_set_episode_arbiter_log: no arbiter attached: call covo_set_step_arbiter first", nullptr},
+};
 
 // periodic / sin / drag / mixed (free.py:10-58): the disturbance model needs per-step force tables (disturb.hip)
 static inline bool covo_needs_tables(const covo_env_params &p)
@@ -550,8 +590,6 @@ int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, 
                             const uint32_t *step_keys, int noisy_on, float obs_noise_scale, float *log, int log_stride,
                             int log_index, hipStream_t s);
 int batch_env_inst(covo_ctx *h, const covo_env_params *params, int E, hipStream_t s, const void **inst_dev);  // step.hip
-// the episode drivers: row e of the step's diagnostics -> row `index` of instance e's diagnostic log
-int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s);
 // episode_rows.hip: the rows the step that has just been enqueued (the one that ran at Sigma age `age`) left in its attachments ->
 // row `index` of every instance's attached covo_set_episode_rows log (no-op with none attached)
 int launch_episode_rows(const covo_ctx *h, int n_inst, int index, int age, hipStream_t s);

@@ -1,6 +1,7 @@
 // episode_rows.hip -- the episode logs of the rows the step attachments leave on the handle (covo_set_episode_rows, include/covo_hip.h:
-// COVO_HAS_EPISODE_ROWS).  The ESS floor, the elite set, the iterations, the Sigma period / Sigma adapt and the
-// posterior covariance each keep ONE row per instance that every step overwrites; an episode driver with a log attached copies the rows
+// COVO_HAS_EPISODE_ROWS, and covo_set_episode_diag_log).  The ESS floor, the elite set, the iterations, the Sigma period /
+// Sigma adapt, the posterior covariance and the sampling diagnostics each keep ONE row per instance that every step overwrites (the
+// copied kinds of covo_eplog_kinds, covo_common.hpp); an episode driver with a log attached copies the rows
 // of the step it has just enqueued into row `index` of every instance's log: one eager launch per step for all attached kinds, behind
 // the step's launches (its after-step frame included: that is where the posterior covariance is formed) and ahead of the env step.
 // The row index and the Sigma age are plain kernel arguments: no captured step graph knows about the logs.
@@ -20,7 +21,7 @@ struct EpRowDesc {
     int vec4;  // width % 4 == 0 and both base addresses 16-byte aligned: every row of the kind is
 };
 struct EpRowTable {
-    EpRowDesc d[COVO_EPLOG_KINDS];
+    EpRowDesc d[COVO_EPLOG_KINDS + 1];  // the copied kinds of covo_eplog_kinds: the six of covo_set_episode_rows and the diagnostic log
 };
 
 // grid (chunks, n_inst, attached kinds).  Bit copies: the floats travel as 32-bit words (a NaN keeps its payload)
@@ -63,38 +64,33 @@ static inline bool epr_aligned16(const void *p) { return ((uintptr_t)p & 15) == 
 
 int launch_episode_rows(const covo_ctx *h, int n_inst, int index, int age, hipStream_t s)
 {
-    const struct {
-        const float *src;
-        int width;
-    } kinds[COVO_EPLOG_KINDS] = {
-        {covo_lam_target(h), COVO_LAM_FLOATS},
-        {covo_elite_target(h), COVO_ELITE_FLOATS},
-        {covo_step_iters(h) > 1 ? h->iter_log : nullptr, covo_step_iters(h)},
-        {covo_sigma_adapt_on(h) ? h->adapt_rows : nullptr, COVO_SIGMA_LOG_FLOATS},
-        {h->post_aux_out, COVO_POST_AUX_FLOATS},
-        {h->post_cov_out, COVO_NA * COVO_NA},
-    };
+    constexpr int COPIED = sizeof(EpRowTable::d) / sizeof(EpRowDesc);
     EpRowTable tab;
     int n = 0;
-    for (int k = 0; k < COVO_EPLOG_KINDS; ++k) {
-        if (h->eprow_log[k] == nullptr) continue;
+    for (int k = 0; k < COVO_EPLOG_ALL; ++k) {
+        if (h->eplog[k].log == nullptr || covo_eplog_kinds[k].rows == nullptr) continue;
+        const covo_eprows rows = covo_eplog_kinds[k].rows(h);
         const bool age_col = k == COVO_EPLOG_SIGMA;
-        if (kinds[k].src == nullptr && !age_col) {  // (the setters keep a log only next to its attachment)
+        if (rows.src == nullptr && !age_col) {  // (the setters keep a log only next to its attachment)
             covo_set_error("covo_set_episode_rows: kind %d has a log but its step attachment left no rows", k);
             return COVO_E_BADARG;
         }
+        if (n == COPIED) {
+            covo_set_error("launch_episode_rows: EpRowTable holds %d of the copied kinds, kind %d is one more", COPIED, k);
+            return COVO_E_BADARG;
+        }
         EpRowDesc &d = tab.d[n++];
-        d.src = kinds[k].src;
-        d.dst = h->eprow_log[k];
-        d.width = kinds[k].width;
-        d.dst_stride_rows = h->eprow_stride[k];
+        d.src = rows.src;
+        d.dst = h->eplog[k].log;
+        d.width = rows.width;
+        d.dst_stride_rows = h->eplog[k].stride;
         d.age_col = age_col ? 1 : 0;
         // every row of the kind starts a multiple of 4 floats from its base: aligned bases make aligned rows
         d.vec4 = (d.width % 4 == 0 && epr_aligned16(d.dst) && (d.src == nullptr || epr_aligned16(d.src))) ? 1 : 0;
     }
     if (n == 0) return 0;
-    for (int k = n; k < COVO_EPLOG_KINDS; ++k) tab.d[k] = tab.d[0];  // never indexed (grid z = n); no indeterminate bytes in the argument
-    const int chunks = h->eprow_log[COVO_EPLOG_POST_COV] != nullptr ? EPR_COV_CHUNKS : 1;
+    for (int k = n; k < COPIED; ++k) tab.d[k] = tab.d[0];  // never indexed (grid z = n); no indeterminate bytes in the argument
+    const int chunks = h->eplog[COVO_EPLOG_POST_COV].log != nullptr ? EPR_COV_CHUNKS : 1;
     hipLaunchKernelGGL(episode_rows_kernel, dim3(chunks, n_inst, n), dim3(EPR_THREADS), 0, s, tab, index, (float)age);
     COVO_CHECK_HIP(hipGetLastError());
     return 0;

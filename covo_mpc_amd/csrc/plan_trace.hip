@@ -115,7 +115,7 @@ static void fill_plan_args(PlanArgs &P, covo_ctx *h, const PlanInstDesc &d, int 
     P.a_mean = d.a_mean;
     P.state_true = states_true ? states_true + (size_t)e * COVO_STATE_FLOATS : nullptr;
     P.plan_out = h->plan_out ? h->plan_out + (size_t)e * COVO_PLAN_FLOATS : nullptr;
-    P.trace = h->trace ? h->trace + (size_t)e * h->trace_stride * COVO_TRACE_FLOATS : nullptr;
+    P.trace = covo_eplog_inst(h, COVO_EPLOG_TRACE, e, COVO_TRACE_FLOATS);
     P.nanp = covo_propagate_nan(h) ? 1 : 0;
 }
 
@@ -125,7 +125,7 @@ static void fill_plan_args(PlanArgs &P, covo_ctx *h, const PlanInstDesc &d, int 
 int launch_plan_trace(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, const float *states_true, int trace_index,
                       hipStream_t s)
 {
-    const bool trace = h->trace != nullptr && trace_index >= 0;
+    const bool trace = h->eplog[COVO_EPLOG_TRACE].log != nullptr && trace_index >= 0;
     if (h->plan_out == nullptr && !trace) return 0;
     const int row = trace ? trace_index : -1;
     if (int rc = after_check_tables(inst, n_inst, "plan trace")) return rc;

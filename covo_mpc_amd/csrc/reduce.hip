@@ -118,24 +118,6 @@ __global__ __launch_bounds__(MG_THREADS) void merge_diag_kernel(const float *__r
     merge_instance<FINAL, true>(partials, G, inv_lam, a_mean_old, gamma_mean, out, stride, dpart, diag_out, n_samples, iter_out, iter_stride);
 }
 
-// the episode drivers (capi.hip): the step's diagnostics [n_inst][COVO_DIAG_FLOATS] -> row `index` of every instance's log
-__global__ void diag_log_rows_kernel(const float *__restrict__ diag, float *__restrict__ log, int n_inst, int stride, int index)
-{
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n_inst * COVO_DIAG_FLOATS) {
-        const int e = i / COVO_DIAG_FLOATS, j = i % COVO_DIAG_FLOATS;
-        log[((size_t)e * stride + index) * COVO_DIAG_FLOATS + j] = diag[i];
-    }
-}
-
-int launch_diag_log_rows(const float *diag, float *log, int n_inst, int stride, int index, hipStream_t s)
-{
-    const int n = n_inst * COVO_DIAG_FLOATS;
-    hipLaunchKernelGGL(diag_log_rows_kernel, dim3((n + 255) / 256), dim3(256), 0, s, diag, log, n_inst, stride, index);
-    COVO_CHECK_HIP(hipGetLastError());
-    return 0;
-}
-
 __global__ void shift_mean_kernel(const float *__restrict__ in, float *__restrict__ out)
 {
     const int i = threadIdx.x;  // 128 threads; covo.py:201-203

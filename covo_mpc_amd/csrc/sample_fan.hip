@@ -151,14 +151,13 @@ int launch_sample_fan_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, 
 // (behind a stream synchronisation, outside the steady state) only when they differ from the last launch's.
 int launch_sample_fan(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s)
 {
-    const bool log = h->fanlog != nullptr && log_index >= 0;
+    const bool log = h->eplog[COVO_EPLOG_FAN].log != nullptr && log_index >= 0;
     if (h->fan_out == nullptr && !log) return 0;
     const int K = h->fan_K, row = log ? log_index : -1;
     if (int rc = after_check_tables(inst, n_inst, "sample fan")) return rc;
     auto fill = [&](FanArgs &P, int e) {
         fill_fan_args(P, h, inst[e], ROLLOUT_CLIP_TRUSTED, h->fan_idx ? h->fan_idx + (size_t)e * K : nullptr, K,
-                      h->fan_out ? h->fan_out + (size_t)e * K * COVO_FAN_FLOATS : nullptr,
-                      h->fanlog ? h->fanlog + (size_t)e * h->fanlog_stride * K * COVO_FAN_FLOATS : nullptr);
+                      h->fan_out ? h->fan_out + (size_t)e * K * COVO_FAN_FLOATS : nullptr, covo_eplog_inst(h, COVO_EPLOG_FAN, e, K * COVO_FAN_FLOATS));
     };
     if (!batched) {
         FanArgs P;

@@ -250,11 +250,11 @@ int launch_update_arbiter_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip cl
 int launch_update_arbiter(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s)
 {
     if (!covo_arb_on(h)) return 0;
-    const int row = (h->arblog != nullptr && log_index >= 0) ? log_index : -1;
+    const int row = (h->eplog[COVO_EPLOG_ARB].log != nullptr && log_index >= 0) ? log_index : -1;
     if (int rc = after_check_tables(inst, n_inst, "update arbiter")) return rc;
     auto fill = [&](ArbArgs &P, int e) {
         fill_arb_args(P, h, inst[e], ROLLOUT_CLIP_TRUSTED, h->arb_mask, h->arb_out + (size_t)e * COVO_ARB_FLOATS,
-                      h->arblog ? h->arblog + (size_t)e * h->arblog_stride * COVO_ARB_FLOATS : nullptr);
+                      covo_eplog_inst(h, COVO_EPLOG_ARB, e, COVO_ARB_FLOATS));
     };
     if (!batched) {
         ArbArgs P;

@@ -4,7 +4,8 @@ and covo_run_episode_batched_mode.
 
 The logs are copies: every comparison is np.array_equal on uint32 views, against the rows cloned from the core's own buffers after every
 step of a Python loop that threads the keys as the drivers do (tests/test_gpu_sigma_adapt.py::test_run_episode_equals_the_python_loop).
-Shapes: N <= 256, at most 8 steps, tracking_zigzag under the gaussian disturbance."""
+Shapes: N <= 256, at most 8 steps, tracking_zigzag under the gaussian disturbance.  Section 7: all ten logs of the handle's one table
+at once -- the four with setters of their own (`diag_log`, `trace`, `fanlog`, `arblog`) next to the six -- at N = 1 024, 5 steps."""
 import numpy as np
 import pytest
 
@@ -55,7 +56,7 @@ def _run_single(env, name, N, segments, rows_of, opts, log_post_cov=False):
             for t in range(T):
                 rng, rng_act, rng_step, _ = cr.split(rng, 4)
                 u, cp, ci = c(None, None, params, rng_act, cp, {"noisy_state": ep.noisy_state})
-                rows.append(rows_of(c.core, ci))
+                rows.append(rows_of(c.core, dict(ci, episode=ep, u=u)))  # (the trace row holds the states entering the env step and u)
                 ep.step(rng_step, u)
                 rng, _ = cr.split(rng)
             out[kind] = (rows, ep.read_log())
@@ -310,3 +311,106 @@ def test_eval_env_batched_returns_the_rows():
     plain = cm.envs.quadrotor.eval_env_batched(env, 2, "N256_H32_lam0.01", n_steps=5, device=DEV, verbose=False, sigma_period=2,
                                                sigma_adapt=0.1, iters=2)
     assert np.array_equal(plain, err)  # the logs change nothing the episode computes
+
+
+# ---- 7. every log at once: the ten logs of one table (DESIGN.md 4.19 "One table") ---------------------------------------------------
+EVERY = dict(compute_diag=True, compute_plan=True, compute_fan=4, update="guarded", iters=2, sigma_period=2, sigma_adapt=0.25,
+             compute_post_cov=True)
+NINE = ("diag_log", "trace", "fanlog", "arblog", "elitelog", "iterlog", "sigmalog", "postlog", "postcovlog")  # (elite=K; ess_min: lamlog)
+
+
+def _every_row(core, ci):
+    """the row of every log a single step has just left, as the episode drivers would write it (the Sigma row: sigma_row)"""
+    ep, u = ci["episode"], ci["u"]
+    out = dict(diag_log=core.diag[0], trace=torch.cat([ep.true, ep.noisy, u.reshape(-1)[:4], core.plan[0]]), fanlog=core.fan[0],
+               arblog=core.arbiter[0], iterlog=core.iter_cost_min[0], postlog=core.post_aux[0], postcovlog=core.post_cov[0].reshape(-1))
+    if core.elite_rows is not None:
+        out["elitelog"] = core.elite_rows[0]
+    if core.lam_eff is not None:
+        out["lamlog"] = core.lam_eff[0]
+    out = {k: v.clone() for k, v in out.items()}
+    out["sigmalog"] = torch.from_numpy(sigma_row(int(ci["sigma_age"]), core.sigma_adapt_rows[0])).to(DEV)
+    return out
+
+
+def test_single_every_log_at_once_equals_the_python_loop():
+    """N = 1 024, 5 steps of covo_run_episode with all nine logs of `elite` attached (the diagnostic log now rides in the one copy launch,
+    behind the after-step frame), then 3 steps with `ess_min` in place of `elite` for the temperature log: every row, bit for bit, is
+    what a Python loop of controller(...) / episode.step reads from the step buffers after each step."""
+    env = quad_env(task="tracking_zigzag")
+    with_lam = tuple("lamlog" if name == "elitelog" else name for name in NINE)
+    for weights, names, T in ((dict(elite=64), NINE, 5), (dict(ess_min=16), with_lam, 3)):
+        ep, core, rows, log_ep, log_steps = _run_single(env, "covo-online", 1024, (T,), _every_row, dict(EVERY, **weights),
+                                                        log_post_cov=True)
+        assert np.array_equal(log_ep, log_steps)
+        assert (ep.lamlog is None) == ("elite" in weights) and (ep.elitelog is None) == ("ess_min" in weights)
+        for name in names:
+            log = getattr(ep, name)
+            same_bits(log[:T], torch.stack([r[name] for r in rows]), name)
+            assert not bits(log[T:]).any(), name  # rows T .. were never written
+        assert core.device_status() == 0
+        core.close()
+
+
+def test_batched_every_log_at_once_at_a_row_offset_equals_the_single_episodes():
+    """The same nine logs through covo_run_episode_batched: E = 3 domain-randomised instances, 5 steps at log_index = 2 into logs of
+    stride 8 that start out filled with a pattern.  Rows [2, 7) of instance e are the rows of covo_run_episode on instance e alone;
+    rows 0, 1 and 7 keep the pattern."""
+    E, T, first, stride, fill = 3, 5, 2, 8, -7.5
+    env, params, reset_keys, rngs0, cp0 = _batch_setup(E)
+    opts = dict(EVERY, elite=64)
+    singles = []
+    for e in range(E):
+        c, cp, _ = _single(env, "covo-online", 1024, **opts)
+        se = cm.envs.DeviceEpisode(env, reset_keys[e], params[e], (c.core.lib, c.core.h), DEV, log_post_cov=True)
+        cp = c.reset(se.state0, params[e], cp, cr.PRNGKey(2))
+        c.run_episode(se, params[e], cp, rngs0[e], T)
+        env_log = se.read_log()
+        singles.append(dict({name: getattr(se, name)[:T].clone() for name in NINE}, log=env_log))
+        assert c.core.device_status() == 0
+        c.core.close()
+    b = cm.controllers.BatchedCoVOController(env, E, 1024, H, 0.01, discount=cp0.discount, gamma_mean=cp0.gamma_mean,
+                                             sample_sigma=cp0.sample_sigma, a_mean_init=cp0.a_mean, device=DEV, **opts)
+    ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV, log_post_cov=True)
+    ep.log = torch.full((E, stride, 4), fill, dtype=torch.float32, device=DEV)  # the segment starts at row 2 of 8-row logs
+    ep.n_steps = first
+    for name in NINE:
+        ep.alloc_log(name, *({"fanlog": (4,), "iterlog": (2,)}.get(name, ())))
+        getattr(ep, name).fill_(fill)
+        assert tuple(getattr(ep, name).shape[:2]) == (E, stride)
+    b.run_episode(ep, rngs0.copy(), T)
+    torch.cuda.synchronize()
+    assert b.core.device_status() == 0
+    pattern = bits(torch.full((1,), fill))[0]
+    for name in NINE + ("log",):
+        log = getattr(ep, name)
+        for e in range(E):
+            same_bits(log[e, first:first + T], singles[e][name], (name, e))
+        untouched = bits(torch.cat([log[:, :first], log[:, first + T:]], dim=1))
+        assert (untouched == pattern).all(), name
+    b.core.close()
+
+
+def test_diag_log_at_a_base_4_bytes_off_alignment():
+    """covo_set_episode_diag_log with a base one float into a larger tensor: the 8-float rows take the copy kernel's float-by-float
+    path, which the Python surface (16-byte aligned allocations, 32-byte rows) never reaches.  Same rows as the aligned run, bit for
+    bit; the float in front of the log and the rows behind the segment stay untouched."""
+    env = quad_env(task="tracking_zigzag")
+    T, got = 5, {}
+    for kind in ("aligned", "off"):
+        c, cp, params = _single(env, "mppi", 1024, compute_diag=True)
+        ep = cm.envs.DeviceEpisode(env, cr.PRNGKey(21), params, (c.core.lib, c.core.h), DEV)
+        if kind == "off":
+            rows = int(ep.log.shape[0])
+            big = torch.full((4 + rows * 8,), -7.5, dtype=torch.float32, device=DEV)
+            ep.diag_log = big[1:1 + rows * 8].view(rows, 8)  # attach_log binds what it finds
+            assert ep.diag_log.data_ptr() % 16 == 4
+        cp = c.reset(ep.state0, params, cp, cr.PRNGKey(22))
+        c.run_episode(ep, params, cp, cr.PRNGKey(23), T)
+        got[kind] = (ep.read_diag(), ep.read_log())
+        if kind == "off":
+            assert bool((big[:1] == -7.5).all()) and bool((big[1 + T * 8:] == -7.5).all())
+        assert c.core.device_status() == 0
+        c.core.close()
+    assert got["aligned"][0].shape == (T, 8) and np.isfinite(got["aligned"][0]).all()
+    assert np.array_equal(bits(got["aligned"][0]), bits(got["off"][0])) and np.array_equal(got["aligned"][1], got["off"][1])
