@@ -48,6 +48,11 @@ COVO_HAS_SIGMA_ADAPT = 1
 COVO_SIGMA_ADAPT_FLOATS = 4  # Sigma adapt's row of one instance: {fallback, c, log det M, 0} (covo_set_step_sigma_adapt)
 COVO_HAS_EPISODE_ROWS = 1
 COVO_HAS_BATCHED_STAGED = 1  # staged= of the env-batched MPPI / covo-offline controllers (covo_set_step_batched_staged)
+COVO_HAS_NEWTON_REFINE = 1  # refine= of the covo-online controllers (covo_set_step_refine, covo_newton_refine, covo_cost_gradient)
+# a refine row: {cost_base, cost_chosen, bits(int32 choice), alpha, |g|_2, g.d, 0, bits(int32 flags)}; the candidates clip(b) and
+# clip(b + 2^(3 - j) d), j = 1 .. 16
+COVO_REFINE_FLOATS = 8
+COVO_REFINE_CANDIDATES = 17
 # the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
 COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
 COVO_EPLOG_KINDS = 6
@@ -208,6 +213,11 @@ _SIGS = {
     "covo_set_step_iters": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # iterations per control step (covo_hip.h: COVO_HAS_STEP_ITERS)
     "covo_arbitrate": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, C.c_int32,
                                  _P, _P, C.c_int32, _P, _P]),
+    # the Newton refinement (covo_hip.h: COVO_HAS_NEWTON_REFINE)
+    "covo_cost_gradient": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), _P, _P, C.c_int32, _P, _P]),
+    "covo_newton_refine": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P,
+                                     C.c_int32, _P, _P, _P]),
+    "covo_set_step_refine": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),

@@ -22,7 +22,7 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
-from ._options import check_kernel_path, check_step_options, sharded_refusal, take
+from ._options import check_refine, check_kernel_path, check_step_options, sharded_refusal, take
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
 # that attribute's value is the log's extra allocation argument: the fan's K, the iteration log's row width; covo_set_episode_rows' kind
@@ -70,7 +70,7 @@ class SamplingCore:
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
-                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0):
+                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False):
         opts = take(locals())
         import torch
         sharded = False
@@ -78,6 +78,7 @@ class SamplingCore:
             import torch.distributed as dist
             sharded = dist.get_world_size(process_group) > 1
         opt = check_step_options(N, "online", sharded=sharded, **opts)
+        refine = check_refine(refine, "online", sigma_period=opt.sigma_period, sharded=sharded)
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -214,6 +215,10 @@ class SamplingCore:
             self.sigma_adapt_rows[:, 1] = 1.0
             check(self.lib.covo_set_step_sigma_adapt(self.h, opt.sigma_adapt, ptr(self.sigma_adapt_rows), self._rows),
                   "covo_set_step_sigma_adapt")
+        # self.refine_rows [rows, 8]: {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, 0, bits(flags)} (refine=: a switch of
+        # the covo-online controllers, not a step option -- _options.check_refine)
+        self.refine = refine
+        self.refine_rows = self._attach_rows(_lib.COVO_REFINE_FLOATS, "covo_set_step_refine") if refine else None
         self._list_infos()
         self.exchange = "collective"
         if self.world > 1:
@@ -362,7 +367,7 @@ class SamplingCore:
             (self.lam_eff is not None, self.lam_info), (self.arbiter is not None, self.arbiter_info),
             (self.iter_cost_min is not None, self.iter_info), (self.elite_rows is not None, self.elite_info),
             (self.sigma_period > 1, self.sigma_info), (self.post_cov is not None, self.post_cov_info),
-            (self.sigma_adapt_rows is not None, self.sigma_adapt_info)) if on]
+            (self.sigma_adapt_rows is not None, self.sigma_adapt_info), (self.refine_rows is not None, self.refine_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -505,6 +510,57 @@ class SamplingCore:
                                       C.byref(params_c), fs, ptr(f_steps), ptr(a), ptr(cost), N, ptr(a_nominal), ptr(a_mean),
                                       int(mask), ptr(out), self.stream()), "covo_arbitrate")
         return out
+
+    def refine_info(self) -> dict:
+        """{"refine_cost_base", "refine_cost", "refine_choice" (0-d int32), "refine_alpha", "refine_grad_norm", "refine_slope"} of the
+        last step as views of self.refine_rows (no sync, no copy); {} when the core was built without refine."""
+        if self.refine_rows is None:
+            return {}
+        row = self.refine_rows[0]
+        return {"refine_cost_base": row[0], "refine_cost": row[1], "refine_choice": row[2:3].view(self.torch.int32)[0],
+                "refine_alpha": row[3], "refine_grad_norm": row[4], "refine_slope": row[5]}
+
+    def cost_gradient(self, dstate, params_c, a, f_steps=None, packed=None):
+        """covo_cost_gradient: dC/da of the Hessian's objective (covo.py:134-185) at `a` (float32 device tensor [128] or [batch, 128])
+        by the first-order adjoint (cost_gradient.hip) -> float64 [batch, 128]; rows 124 .. 127 are exactly 0.  packed: the [batch, 32]
+        states (default: dstate's, for every entry); f_steps: the [batch, H, 4] table of disturb_table(key_mode=DISTURB_KEYS_HESSIAN)
+        for periodic / sin / drag / mixed.  It has a workspace of its own: hessian() and the step's Hessian are untouched."""
+        torch = self.torch
+        a = a.reshape(-1, COVO_NA).contiguous()
+        batch = int(a.shape[0])
+        assert a.is_cuda and a.dtype == torch.float32
+        if packed is None:
+            packed = dstate.packed.reshape(1, -1).expand(batch, -1).contiguous()
+        assert packed.numel() == batch * _lib.COVO_STATE_FLOATS and packed.is_contiguous()
+        g = torch.empty((batch, COVO_NA), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_cost_gradient(self.h, ptr(packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                              C.byref(params_c), ptr(a), ptr(f_steps), batch, ptr(g), self.stream()), "covo_cost_gradient")
+        return g
+
+    def newton_refine(self, dstate, params_c, a_mean, Sigma, inv_c2, f_shared=None, f_steps=None, f_steps_hessian=None, g=None,
+                      want_costs=True):
+        """covo_newton_refine (the stand-alone Newton line search) on `a_mean` (float32 device tensor, 128 elements, refined IN
+        PLACE) with the inputs of rollout(): d = -Sigma (Sigma g) / c^2 from `Sigma` (float32 [128, 128]) and `inv_c2` (1 / c^2: a
+        float or a float64 device tensor), g = cost_gradient(a_mean) with f_steps_hessian unless given (float64 [128]); the candidates
+        clip(a_mean) and clip(a_mean + 2^(3 - j) d), j = 1 .. 16, are rolled out and the first cheapest is committed -> (float32 [8] row
+        {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, 0, bits(flags)}, float32 [17] candidate costs or None)."""
+        torch = self.torch
+        for t in (a_mean, Sigma):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
+        assert a_mean.numel() == COVO_NA and Sigma.numel() == COVO_NA * COVO_NA
+        ic = torch.as_tensor(inv_c2, dtype=torch.float64, device=self.device).reshape(1)
+        if g is not None:
+            g = g.to(device=self.device, dtype=torch.float64).contiguous()
+            assert g.numel() == COVO_NA
+        row = torch.empty((_lib.COVO_REFINE_FLOATS,), dtype=torch.float32, device=self.device)
+        costs = torch.empty((_lib.COVO_REFINE_CANDIDATES,), dtype=torch.float32, device=self.device) if want_costs else None
+        fs = (C.c_float * 3)(*[float(x) for x in f_shared]) if f_shared is not None else None
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_newton_refine(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                              C.byref(params_c), fs, ptr(f_steps), ptr(f_steps_hessian), ptr(g), ptr(a_mean), ptr(Sigma),
+                                              ptr(ic), 1, ptr(row), ptr(costs), self.stream()), "covo_newton_refine")
+        return row, costs
 
     def iter_info(self) -> dict:
         """{"iter_cost_min" [iters]} of the last step -- entry j: the minimum sample cost of pass j -- as a view of self.iter_cost_min

@@ -159,6 +159,7 @@ KERNEL_PATH_REFUSALS = (
     ("arb_mask", 0, "update_rule", "update={v!r} follows the fused step" + _DEBUG_PATH + "updates with the softmax mean only"),
     ("iters", 1, "iters", "iters={v} follows the fused step" + _DEBUG_PATH + "runs one pass per call"),
     ("compute_diag", False, "compute_diag", "compute_diag is formed by the fused step" + _DEBUG_PATH + "does not produce it"),
+    ("refine", False, "refine", "refine follows the fused step" + _DEBUG_PATH + "ends with the softmax mean"),
 )
 
 
@@ -201,3 +202,35 @@ def check_step_options(N, what, *, gamma_sigma=None, fused_batched=False, sharde
             if is_on(s):
                 raise sharded_refusal(option, shown(s, o) if shown else None)
     return s
+
+
+def check_refine(refine, what, *, sigma_period=1, sharded=False) -> bool:
+    """refine= of the covo-online controllers -> bool.  Not a step option (tests/test_options_abi.py pins their list): a switch of
+    SamplingCore, CoVOController, BatchedCoVOController, get_controller and eval_env_batched, like staged= of the env-batched MPPI /
+    covo-offline controllers, checked here by the same constructors, next to check_step_options; the C side's counterpart is the
+    refine block of check_step_attachments (csrc/capi.hip).
+
+    refine=True: every control step ends with a Newton line search on the mean it has just committed -- the gradient g of the Hessian's
+    objective at that mean (csrc/cost_gradient.hip), the direction d = -Sigma (Sigma g) / c^2 from the step's own Sigma and c, the
+    candidates clip(b + 2^(3 - j) d), j = 1 .. 16, next to clip(b) itself, judged by the step's own sampling objective
+    (covo_set_step_refine, csrc/newton_refine.hip): info["refine_cost_base"] / ["refine_cost"] / ["refine_choice"] / ["refine_alpha"] /
+    ["refine_grad_norm"] / ["refine_slope"].  False: nothing attached.
+
+    The objections, in a fixed order: anything but a bool (ValueError); `what` other than "online" -- MPPI, covo-offline and their
+    env-batched controllers have no Hessian-derived Sigma at the step's mean (ValueError); sigma_period > 1 -- a reuse step has no R,
+    and its c means something else (ValueError); sharded -- sample-sharded ranks (NotImplementedError)."""
+    if not isinstance(refine, bool):
+        raise ValueError(f"refine={refine!r} (True | False)")
+    if not refine:
+        return False
+    if what != "online":
+        raise ValueError(f"refine=True with {what}: the Newton refinement needs the Hessian-derived Sigma at the step's mean, which "
+                         "only covo-online computes (CoVOController(mode=\"online\"), BatchedCoVOController(mode=\"online\")); "
+                         "give refine=False")
+    if int(sigma_period) > 1:
+        raise ValueError(f"refine=True with sigma_period={sigma_period}: a reuse step has no R and its c means something else; give "
+                         "sigma_period=1 or refine=False")
+    if sharded:
+        raise NotImplementedError("refine=True on sample-sharded ranks: a rank's Sigma chain and costs cover its shard's step only "
+                                  "until the exchange (covo_set_step_refine refuses sample-sharded steps)")
+    return True

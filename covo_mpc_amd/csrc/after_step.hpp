@@ -1,6 +1,6 @@
 // after_step.hpp -- the frame the eager launches that follow a control step share (gfx950): the update arbiter
-// (update_arbiter.hip), the plan / episode trace (plan_trace.hip) and the sample fan (sample_fan.hip), in the order
-// covo_plan_after_step / covo_plan_after_batched (step.hip) issue them.
+// (update_arbiter.hip), the Newton refinement (newton_refine.hip), the plan / episode trace (plan_trace.hip) and the sample fan
+// (sample_fan.hip), in the order covo_plan_after_step / covo_plan_after_batched (step.hip) issue them.
 //
 // Each is one launch per control step with one workgroup of three waves per instance:
 //   phase 0  the per-step scalars from the raw controller key (after_derive) next to the kernel's own action image in LDS
@@ -20,7 +20,7 @@
 #include "rollout_common.hpp"
 #include "step_begin.hpp"
 
-// the first member of PlanArgs / FanArgs / ArbArgs
+// the first member of PlanArgs / FanArgs / ArbArgs / RefineArgs
 struct AfterHead {
     RolloutArgs R;            // the step's sample rollout: noisy state, trajectories, model, discount, disturbance table; with the
                               // samples (fan, arbiter) a, N and R.clip: how phase 0 clips the stripes it gathers
@@ -181,7 +181,7 @@ struct ArgBlockCache {
 // covo_ctx::after.  One cache per launch: with a shared one every launch of a batched step would overwrite the mirror the next
 // compares against, and every step would synchronise and upload
 struct AfterState {
-    ArgBlockCache arbiter, plan, fan;
+    ArgBlockCache arbiter, plan, fan, refine;
     float *nominal = nullptr;  // [COVO_MAX_ENVS][128] the update arbiter's nominals of the env-batched fused step
 };
 static inline AfterState *after_state(covo_ctx *h)

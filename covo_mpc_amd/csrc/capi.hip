@@ -144,6 +144,8 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->ws_stats));
     DESTROY(hipFree(h->ws_sigma));
     DESTROY(hipFree(h->ws_hess));
+    DESTROY(hipFree(h->ws_grad));
+    DESTROY(hipFree(h->refine_g));
     DESTROY(hipEventDestroy(h->ev_fork));
     DESTROY(hipEventDestroy(h->ev_join));
     DESTROY(hipStreamDestroy(h->side_stream));
@@ -1074,6 +1076,9 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                 "%s: Sigma adapt (covo_set_step_sigma_adapt, gamma=%g) is not available for sample-sharded steps (partial_out != NULL): "
                 "it needs the Sigma period and the posterior covariance, which sample-sharded steps cannot have; turn it off (gamma = 0)",
                 what, (double)h->adapt_gamma);
+        REQUIRE(!covo_refine_on(h),
+                "%s: the Newton refinement (covo_set_step_refine) is not available for sample-sharded steps (partial_out != NULL): "
+                "a rank's Sigma chain and costs cover its shard's step only until the exchange; detach it", what);
         REQUIRE(!covo_eprow_any(h),
                 "%s: the episode logs of the attachments' rows (covo_set_episode_rows) are not available for sample-sharded steps "
                 "(partial_out != NULL): none of the attachments they follow is; detach them", what);
@@ -1133,6 +1138,17 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(n_inst <= h->adapt_n, "%s: %d instances, the Sigma adapt rows (covo_set_step_sigma_adapt) have n_inst=%d", what, n_inst,
                 h->adapt_n);
     }
+    if (covo_refine_on(h)) {  // the direction is Sigma^2 g / c^2 of THIS step's Hessian
+        REQUIRE(mode == COVO_MODE_COVO_ONLINE,
+                "%s: the Newton refinement (covo_set_step_refine) belongs to covo-online steps; this step's mode is %s, which has no "
+                "Hessian-derived Sigma at the step's mean; detach it", what, mode == COVO_MODE_MPPI ? "MPPI" : "covo-offline");
+        REQUIRE(covo_sigma_period(h) == 1,
+                "%s: the Newton refinement (covo_set_step_refine) together with a Sigma period (covo_set_step_sigma_period, period=%d): a "
+                "reuse step has no R and its c means something else; set period = 1 or detach it", what, covo_sigma_period(h));
+        REQUIRE(n_inst <= h->refine_n, "%s: %d instances, the refine buffer (covo_set_step_refine) has n_inst=%d", what, n_inst,
+                h->refine_n);
+        REQUIRE(((uintptr_t)a_cov & 15) == 0, "%s: a_cov must be 16-byte aligned under the Newton refinement (covo_set_step_refine)", what);
+    }
     return 0;
 }
 
@@ -1169,6 +1185,95 @@ int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, c
     d.a_mean = a_mean_inout;
     d.a_mean_out = a_mean_inout;
     return launch_update_arbiter_one(h, d, rollout_clip(h), mask, row_out, (hipStream_t)stream);  // the clip covo_rollout_cost applies
+}
+
+// ---- the Newton refinement (cost_gradient.hip, newton_refine.hip).  Its launches are eager and follow the step: no captured step
+// graph changes
+static HessianDesc gradient_desc(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params *params,
+                                 const float *a, const float *f_tab, int batch)
+{
+    HessianDesc d;
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a_mean = a;
+    d.f_tab = f_tab;
+    d.batch = batch;
+    return d;
+}
+
+int covo_cost_gradient(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                       const covo_env_params *params, const float *a, const float *f_disturb_steps, int32_t batch, double *g_out,
+                       void *stream)
+{
+    REQUIRE(h, "covo_cost_gradient: null handle");
+    CHECK_DEVICE(h, "covo_cost_gradient");
+    REQUIRE(state && pos_traj && vel_traj && params && a && g_out && T > 0 && batch > 0, "covo_cost_gradient: bad argument");
+    CHECK_MODEL(params, "covo_cost_gradient");
+    REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_cost_gradient: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
+            params->disturb_kind);
+    const int rc = covo_grow_workspace(h, &h->ws_grad, &h->ws_grad_bytes, cost_gradient_workspace_bytes(batch), (hipStream_t)stream);
+    if (rc) return rc;
+    return launch_cost_gradient(gradient_desc(state, pos_traj, vel_traj, T, params, a, f_disturb_steps, batch), g_out, h->ws_grad,
+                                (hipStream_t)stream);
+}
+
+int covo_newton_refine(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                       const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                       const float *f_tab_hessian, const double *g, float *a_mean, const float *Sigma, const double *inv_c2,
+                       int32_t n_inst, float *rows_out, float *costs_out, void *stream)
+{
+    REQUIRE(h, "covo_newton_refine: null handle");
+    CHECK_DEVICE(h, "covo_newton_refine");
+    REQUIRE(state && pos_traj && vel_traj && params && a_mean && Sigma && inv_c2 && rows_out && T > 0, "covo_newton_refine: bad argument");
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_newton_refine: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(((uintptr_t)Sigma & 15) == 0 && ((uintptr_t)a_mean & 15) == 0, "covo_newton_refine: Sigma and a_mean must be 16-byte aligned");
+    CHECK_MODEL(params, "covo_newton_refine");
+    REQUIRE(!covo_needs_tables(*params) || (f_disturb_steps && (g || f_tab_hessian)),
+            "covo_newton_refine: disturb_kind=%d needs f_disturb_steps and f_tab_hessian (covo_disturb_table)", params->disturb_kind);
+    hipStream_t s = (hipStream_t)stream;
+    if (g == nullptr) {
+        int rc = covo_grow_workspace(h, &h->ws_grad, &h->ws_grad_bytes, cost_gradient_workspace_bytes(n_inst), s);
+        if (rc) return rc;
+        if (h->refine_g == nullptr) COVO_CHECK_HIP(hipMalloc(&h->refine_g, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(double)));
+        if ((rc = launch_cost_gradient(gradient_desc(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst), h->refine_g,
+                                       h->ws_grad, s)))
+            return rc;
+        g = h->refine_g;
+    }
+    for (int e = 0; e < n_inst; ++e) {
+        PlanInstDesc d = standalone_inst(state + (size_t)e * COVO_STATE_FLOATS, pos_traj, vel_traj, T, params, f_disturb_shared,
+                                         f_disturb_steps ? f_disturb_steps + (size_t)e * COVO_H * 4 : nullptr, nullptr, 1);
+        d.a_mean = d.a_mean_out = a_mean + (size_t)e * COVO_NA;
+        RefineDesc r;
+        r.g = g + (size_t)e * COVO_NA;
+        r.Sigma = Sigma + (size_t)e * COVO_NA * COVO_NA;
+        r.inv_c2 = inv_c2 + e;
+        r.row_out = rows_out + (size_t)e * COVO_REFINE_FLOATS;
+        r.costs_out = costs_out ? costs_out + (size_t)e * COVO_REFINE_CANDIDATES : nullptr;
+        if (int rc = launch_newton_refine_one(h, d, rollout_clip(h), r, s)) return rc;
+    }
+    return 0;
+}
+
+int covo_set_step_refine(covo_handle_t h, float *rows, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_refine: null handle");
+    if (rows == nullptr) {
+        h->refine_out = nullptr;
+        h->refine_n = 0;
+        return 0;
+    }
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_refine: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    // the step's gradient scratch, here and not in a step: a workspace never grows inside the steady state
+    const int rc = covo_grow_workspace(h, &h->ws_grad, &h->ws_grad_bytes, cost_gradient_workspace_bytes(n_inst), nullptr);
+    if (rc) return rc;
+    if (h->refine_g == nullptr) COVO_CHECK_HIP(hipMalloc(&h->refine_g, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(double)));
+    h->refine_out = rows;
+    h->refine_n = n_inst;
+    return 0;
 }
 
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)

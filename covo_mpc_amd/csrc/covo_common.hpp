@@ -99,6 +99,12 @@ struct covo_ctx {
     float adapt_gamma;        // the weight of the previous step's posterior covariance in a reuse step's Sigma', in (0, 1)
     float *adapt_rows;        // caller's [adapt_n][COVO_SIGMA_ADAPT_FLOATS]: instance e's {fallback, c, log det M, 0} of every reuse step
     int adapt_n;
+    // the Newton refinement of the committed mean (covo_set_step_refine; cost_gradient.hip, newton_refine.hip); refine_out null: off
+    float *refine_out;        // caller's [refine_n][COVO_REFINE_FLOATS]: instance e's refine row of every step
+    int refine_n;
+    void *ws_grad;            // scratch of the first-order adjoint (its own: the Sigma chain and the debug readers own ws_hess)
+    size_t ws_grad_bytes;
+    double *refine_g;         // [COVO_MAX_ENVS][128] the gradients of a step's instances at their committed means
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -152,6 +158,7 @@ static inline bool covo_update_staged(const covo_ctx *h) { return covo_lam_targe
 static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->eplog[COVO_EPLOG_TRACE].log != nullptr; }
 static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->eplog[COVO_EPLOG_FAN].log != nullptr; }
 static inline bool covo_arb_on(const covo_ctx *h) { return h->arb_out != nullptr; }
+static inline bool covo_refine_on(const covo_ctx *h) { return h->refine_out != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->eplog[COVO_EPLOG_DIAG].log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->eplog[COVO_EPLOG_DIAG].log ? COVO_MAX_ENVS : 0); }
@@ -507,6 +514,10 @@ struct HessianDesc {
     const HessBegin *begin = nullptr;    // batch 1: KB also does the step's begin work (a_mean = where the shifted mean goes)
 };
 int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const DebugMasks &dbg);
+// cost_gradient.hip: the gradient of the same objective by the first-order adjoint, g_out [batch][128] fp64; d as for launch_hessian
+// (R, stats, status_dev and begin are not read), the workspace the gradient's own (cost_gradient_workspace_bytes)
+size_t cost_gradient_workspace_bytes(int batch);
+int launch_cost_gradient(const HessianDesc &d, double *g_out, void *workspace, hipStream_t s);
 size_t hessian_consts_bytes(int n);
 void hessian_fill_consts(const covo_env_params *params, int n, void *out);
 // the per-pair hyper-dual rollout version (hessian.hip): slower, independent derivation, kept as a cross-check
@@ -551,6 +562,9 @@ struct SigmaNsDesc {
 };
 int launch_sigma_ns(const CovoOpts &opt, const SigmaNsDesc &d, void *workspace, hipStream_t s, const DebugMasks &dbg);
 SymStatsOut sigma_ns_stats_out(void *workspace, int batch = 1);
+// where the chain that last ran on `workspace` for `batch` matrices left sum_i log diag(chol(R + delta I)) of matrix 0; matrix e's lies
+// *stride_doubles further on per matrix (newton_refine.hip: c^2 of the step)
+const double *sigma_ns_sumlogB(void *workspace, int batch, size_t *stride_doubles);
 void step_state_destroy(covo_ctx *h);
 void step_graphs_drop(covo_ctx *h);  // every captured step graph of the handle goes; the next step runs eagerly, the one after captures
 // h->ws_sigma / h->ws_hess (ws, bytes) to at least `need` bytes: only for batch sizes not seen before, never inside the steady-state
@@ -626,6 +640,19 @@ int launch_sample_fan_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, 
 int launch_update_arbiter(covo_ctx *h, const PlanInstDesc *inst, int n_inst, bool batched, int log_index, hipStream_t s);
 int launch_update_arbiter_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, int mask, float *row_out, hipStream_t s);
 int launch_arbiter_nominal(covo_ctx *h, const float *a_mean, int n_inst, hipStream_t s, const float **nominal_out);
+// newton_refine.hip: the line search on the committed mean, behind the arbiter (a_mean_out: the mean, in and out).  What one instance
+// refines with: its gradient, the Sigma it sampled from, and c^2 -- the caller's reciprocal (covo_newton_refine) or the chain's slot
+struct RefineDesc {
+    const double *g = nullptr;        // [128]
+    const float *Sigma = nullptr;     // [128][128], 16-byte aligned
+    const double *inv_c2 = nullptr;   // 1 / c^2, or null: from ...
+    const double *sumlogB = nullptr;  // ... sigma_ns_sumlogB's slot of this instance and sample_sigma
+    float sample_sigma = 0.0f;
+    float *row_out = nullptr;         // [COVO_REFINE_FLOATS], nullable
+    float *costs_out = nullptr;       // [COVO_REFINE_CANDIDATES], nullable
+};
+int launch_newton_refine(covo_ctx *h, const PlanInstDesc *inst, const RefineDesc *r, int n_inst, bool batched, hipStream_t s);
+int launch_newton_refine_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const RefineDesc &r, hipStream_t s);
 void after_state_destroy(covo_ctx *h);  // (update_arbiter.hip) the three launches' device state: AfterState, after_step.hpp
 // step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
 // states_true + trace_index >= 0: an episode driver's step, which also writes its trace row

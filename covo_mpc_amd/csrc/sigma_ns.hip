@@ -2383,6 +2383,11 @@ SymStatsOut sigma_ns_stats_out(void *workspace, int batch)
     o.ready = sc + SC_READY;
     return o;
 }
+const double *sigma_ns_sumlogB(void *workspace, int batch, size_t *stride_doubles)
+{
+    *stride_doubles = SC_COUNT;
+    return reinterpret_cast<double *>(workspace) + (size_t)11 * batch * SN * SN + SC_SUMLOGB;
+}
 // 11 matrices, the slots, then the filter's history X_3 .. X_16 and X_1 (XBufs)
 size_t sigma_ns_workspace_bytes(int batch) { return (size_t)batch * ((11 + NS_SQUARINGS - 1) * SN * SN + SC_COUNT) * sizeof(double); }
 

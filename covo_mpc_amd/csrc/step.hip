@@ -1272,10 +1272,35 @@ static PlanInstDesc plan_inst(const BatchInst &i, int T, int N, const covo_env_p
 }
 // the arbiter first: the plan, the trace's u and the env step see its mean; trace_index: the episode's row index (the fan log counts
 // like the trace)
+// covo_set_step_refine: what the Newton refinement of a covo-online step's n instances needs beyond their descriptors -- the
+// Hessian's own inputs (grad: dense over the instances, a_mean = the committed means) and the Sigma the step sampled from
+struct RefineStep {
+    HessianDesc grad;
+    const float *Sigma;  // [n][128][128]
+    float sample_sigma;
+};
+// the gradient's two launches at the committed means, then the line search with c^2 from the Sigma chain's slots of this step
+static int refine_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const RefineStep &rs, hipStream_t s)
+{
+    if (int rc = launch_cost_gradient(rs.grad, h->refine_g, h->ws_grad, s)) return rc;
+    size_t stride;
+    const double *sumlogB = sigma_ns_sumlogB(h->ws_sigma, n, &stride);
+    RefineDesc r[COVO_MAX_ENVS];
+    for (int e = 0; e < n; ++e) {
+        r[e].g = h->refine_g + (size_t)e * COVO_NA;
+        r[e].Sigma = rs.Sigma + (size_t)e * COVO_NA * COVO_NA;
+        r[e].sumlogB = sumlogB + (size_t)e * stride;
+        r[e].sample_sigma = rs.sample_sigma;
+        r[e].row_out = h->refine_out + (size_t)e * COVO_REFINE_FLOATS;
+    }
+    return launch_newton_refine(h, d, r, n, batched, s);
+}
+// the refinement (rs: null for the steps that have none) directly behind the arbiter, every pass of an iterated step included
 static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const float *states_true, int trace_index, hipStream_t s,
-                      bool arbiter_only)
+                      bool arbiter_only, const RefineStep *rs)
 {
     int rc = launch_update_arbiter(h, d, n, batched, trace_index, s);
+    if (rc == 0 && rs != nullptr && covo_refine_on(h)) rc = refine_after(h, d, n, batched, *rs, s);
     if (rc || arbiter_only) return rc;
     if ((rc = launch_plan_trace(h, d, n, batched, states_true, trace_index, s))) return rc;
     return launch_sample_fan(h, d, n, batched, trace_index, s);
@@ -1284,7 +1309,7 @@ static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, c
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                          const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
     // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
     // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
@@ -1296,7 +1321,20 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
     d.key[0] = key0;
     d.key[1] = key1;
     for (int c = 0; c < 3; ++c) d.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
-    if (int rc = plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only)) return rc;
+    RefineStep rs;
+    const bool refine = covo_refine_on(h) && args->mode == COVO_MODE_COVO_ONLINE && st != nullptr;
+    if (refine) {
+        rs.grad.state = d.state;
+        rs.grad.pos_traj = d.pos_traj;
+        rs.grad.vel_traj = d.vel_traj;
+        rs.grad.T = d.T;
+        rs.grad.params = params;
+        rs.grad.a_mean = args->a_mean;
+        rs.grad.f_tab = covo_needs_tables(*params) ? st->f_tab_hess : nullptr;
+        rs.Sigma = args->a_cov ? args->a_cov : st->Sigma;
+        rs.sample_sigma = args->sample_sigma;
+    }
+    if (int rc = plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only, refine ? &rs : nullptr)) return rc;
     // the posterior covariance: behind the (last pass's) update and the launches above; d.a_nominal is the mean that pass sampled around
     return arbiter_only ? 0 : launch_post_cov_after(h, d.a, d.cost, d.a_nominal, d.N, 1, s);
 }
@@ -1305,7 +1343,7 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
                             const float *states_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
@@ -1328,7 +1366,24 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
         d[e] = plan_inst(batch_inst(*args, e), args->T, args->n_samples, &params[e], 1, mode != COVO_MODE_MPPI,
                          nominal ? nominal + (size_t)e * COVO_NA : nullptr, tabs ? tabs + (size_t)e * COVO_H * 4 : nullptr,
                          begun ? dyn + 12 * e + 10 : dyn + 12 * e);
-    if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only)) return rc;
+    RefineStep rs;
+    const bool refine = covo_refine_on(h) && online;
+    if (refine) {
+        rs.grad.state = args->states;
+        rs.grad.pos_traj = args->pos_traj;
+        rs.grad.vel_traj = args->vel_traj;
+        rs.grad.T = args->T;
+        rs.grad.params = &c->params[0];
+        rs.grad.a_mean = args->a_mean;
+        rs.grad.batch = E;
+        rs.grad.consts_dev = b->consts;
+        rs.grad.traj_stride = (size_t)args->T * 3;
+        rs.grad.f_tab = c->tables ? b->tab_hess : nullptr;
+        rs.grad.models_dev = c->models;
+        rs.Sigma = args->a_cov ? args->a_cov : b->Sigma;
+        rs.sample_sigma = args->sample_sigma;
+    }
+    if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only, refine ? &rs : nullptr)) return rc;
     // the posterior covariance of every instance (never behind the fused launch: check_batch_step): dense slices, the begin launch's
     // shifted means
     return arbiter_only ? 0 : launch_post_cov_after(h, args->a, args->cost, shifted, args->n_samples, E, s);

@@ -73,8 +73,9 @@ static int graph_cache_run(covo_ctx *h, GraphCache &c, hipStream_t s, bool same,
 
 // ---- the pass driver of the single and the env-batched covo-online step.  covo_set_step_iters: K passes on one state, all in the
 // step's graph -- cache[0], or cache[1] for the reuse step of a Sigma period (another launch set).  pass(stream, j) enqueues pass j.
-// With the update arbiter attached its launch sits between the passes: between(stream, j) enqueues it behind pass j < K - 1; it is
-// eager by nature (its arguments are the step's), so the passes are then enqueued eagerly too and both graphs are forgotten.
+// With the update arbiter or the Newton refinement attached their launches sit between the passes: between(stream, j) enqueues them
+// behind pass j < K - 1; they are eager by nature (their arguments are the step's), so the passes are then enqueued eagerly too and
+// both graphs are forgotten.
 // same: graph_cache_seen(cache[reuse], ...) of this call.
 template <class Pass, class Between>
 static int step_run_passes(covo_ctx *h, GraphCache (&cache)[2], bool reuse, bool same, hipStream_t s, const char *name, Pass pass,
@@ -89,7 +90,7 @@ static int step_run_passes(covo_ctx *h, GraphCache (&cache)[2], bool reuse, bool
         }
         return 0;
     };
-    if (K > 1 && covo_arb_on(h)) {
+    if (K > 1 && (covo_arb_on(h) || covo_refine_on(h))) {
         cache[0].forget(), cache[1].forget();
         return passes(s, true);
     }

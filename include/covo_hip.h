@@ -734,6 +734,42 @@ int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, c
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
                    void *stream);
+
+/* The Newton refinement: a gradient-based line search on the mean a covo-online step has just committed (additive to ABI 10:
+ * COVO_HAS_NEWTON_REFINE; off by default, and off changes nothing a caller can observe: no launch is added).
+ * covo-online samples from Sigma = c (R + delta I)^(-1/2), so (R + delta I)^-1 = Sigma^2 / c^2 and the regularised Newton direction at
+ * the committed mean b is d = -Sigma (Sigma g) / c^2 with g the gradient of the Hessian's own objective at b.  The candidates clip(b)
+ * and fp32(clip(b + alpha_j d)), alpha_j = 2^(3 - j), j = 1 .. 16, are rolled out with the inputs the step's sample rollouts had
+ * (csrc/newton_refine.hip); a NaN cost counts as +inf, equal costs resolve to the lowest candidate, so the mean changes only for a
+ * strictly cheaper candidate; g, d or c^2 not finite: the mean stays.
+ *   row  float[COVO_REFINE_FLOATS] = {cost_base, cost_chosen, bits(int32 choice), alpha (0 for choice 0), |g|_2, g.d, 0,
+ *        bits(int32 flags)}; flags bit 0: g not finite, bit 1: d not finite, bit 2: c^2 not finite or not positive
+ * covo_cost_gradient: g_out = DEVICE double[batch][128], the gradient of covo_hessian's objective at a = DEVICE float[batch][128]
+ *   (first-order adjoint, fp64, csrc/cost_gradient.hip; the arguments of covo_hessian).  Rows 124 .. 127 are exactly 0.  It uses a
+ *   workspace of its own: covo_hessian's results and the step's Hessian are untouched.
+ * covo_newton_refine: stateless, n_inst instances with the rollout inputs of covo_arbitrate (state = DEVICE float[n_inst][32],
+ *   f_disturb_steps / f_tab_hessian = DEVICE float[n_inst][H][4] or NULL; trajectories, params and f_disturb_shared shared);
+ *   g = DEVICE double[n_inst][128] or NULL: computed here at a_mean with f_tab_hessian (covo_cost_gradient's launches);
+ *   a_mean = DEVICE float[n_inst][128] in / out; Sigma = DEVICE float[n_inst][128][128], 16-byte aligned; inv_c2 = DEVICE double[n_inst],
+ *   1 / c^2; rows_out = DEVICE float[n_inst][COVO_REFINE_FLOATS]; costs_out = DEVICE float[n_inst][COVO_REFINE_CANDIDATES] or NULL.
+ * covo_set_step_refine: rows = DEVICE float[n_inst][COVO_REFINE_FLOATS]; every covo-online control step of the handle --
+ *   covo_mpc_step, covo_mpc_step_batched, the episode drivers -- then ends with three eager launches behind the update arbiter's
+ *   and ahead of the plan's and the fan's: the gradient's two at the committed mean with the step's Hessian table, then the line search
+ *   with the step's Sigma and c^2 = sigma^4 det(R + delta I)^(1/n) from the Sigma chain's own log-determinant.  Under iterations per
+ *   step every pass runs it and the row is the last pass's.  No captured step graph changes.
+ * Refused before any launch, with a message that names the condition: a step that is not covo-online; a Sigma period above 1 (a reuse
+ *   step has no R); a sample-sharded step (partial_out != NULL); more instances than rows; a_cov not 16-byte aligned. */
+#define COVO_HAS_NEWTON_REFINE 1
+#define COVO_REFINE_FLOATS 8
+#define COVO_REFINE_CANDIDATES 17
+int covo_cost_gradient(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                       const covo_env_params *params, const float *a, const float *f_disturb_steps, int32_t batch, double *g_out,
+                       void *stream);
+int covo_newton_refine(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                       const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                       const float *f_tab_hessian, const double *g, float *a_mean, const float *Sigma, const double *inv_c2,
+                       int32_t n_inst, float *rows_out, float *costs_out, void *stream);
+int covo_set_step_refine(covo_handle_t h, float *rows /* DEVICE [n_inst][COVO_REFINE_FLOATS]; NULL = off */, int32_t n_inst);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

@@ -11,7 +11,11 @@ name = sys.argv[1]
 # Under ess_min, sigma_adapt and iters every seed's line also carries what the episode logs of the attachments' rows say (read_lam,
 # read_sigma, read_iters): the share of steps the floor raised the temperature in, the number of reuse steps that fell back to the plain
 # shift, the share of steps whose last pass found a cheaper sample than the first
+# python scripts/eval_seeds.py covo-online --refine: every control step ends with the Newton line search on its committed mean (the
+# refine row has no episode log: compare the errors with those of the same call without the flag)
 rest = sys.argv[2:]
+refine = "--refine" in rest
+rest = [r for r in rest if r != "--refine"]
 for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_adapt")):
     while flag in rest:
         i = rest.index(flag)
@@ -20,7 +24,7 @@ opts = {k: (float(v) if k in ("sigma_adapt", "ess_min") else int(v)) for k, v in
 assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"}, opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
-ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **opts)
+ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, **opts)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
