@@ -53,6 +53,14 @@ COVO_HAS_NEWTON_REFINE = 1  # refine= of the covo-online controllers (covo_set_s
 # clip(b + 2^(3 - j) d), j = 1 .. 16
 COVO_REFINE_FLOATS = 8
 COVO_REFINE_CANDIDATES = 17
+COVO_HAS_RICCATI_REFINE = 1  # riccati= of every sampling controller (covo_set_step_riccati, covo_riccati_refine, covo_riccati)
+# a riccati row: a refine row whose last two words are {mu, bits(int32 flags | rung << 8)}; flags bit 0: g not finite, 1: d not finite,
+# 3: no rung of the ladder mu_j = reg0 4^j, j < COVO_RICCATI_RUNGS, positive definite.  The sweep's side row: COVO_RICCATI_SIDE
+# doubles {mu, rung, smallest pivot, flags}
+COVO_RICCATI_FLOATS = 8
+COVO_RICCATI_SIDE = 4
+COVO_RICCATI_RUNGS = 8
+COVO_RICCATI_REG0 = 1e-2
 # the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
 COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
 COVO_EPLOG_KINDS = 6
@@ -218,6 +226,11 @@ _SIGS = {
     "covo_newton_refine": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, _P, _P, _P,
                                      C.c_int32, _P, _P, _P]),
     "covo_set_step_refine": (C.c_int, [_P, _P, C.c_int32]),
+    # the Riccati refinement (covo_hip.h: COVO_HAS_RICCATI_REFINE)
+    "covo_riccati": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P]),
+    "covo_riccati_refine": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, C.c_double,
+                                      C.c_int32, _P, _P, _P]),
+    "covo_set_step_riccati": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),

@@ -22,7 +22,7 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
-from ._options import check_refine, check_kernel_path, check_step_options, sharded_refusal, take
+from ._options import check_refine, check_riccati, check_kernel_path, check_step_options, sharded_refusal, take
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
 # that attribute's value is the log's extra allocation argument: the fan's K, the iteration log's row width; covo_set_episode_rows' kind
@@ -70,7 +70,8 @@ class SamplingCore:
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
-                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False):
+                 sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False,
+                 riccati: bool = False):
         opts = take(locals())
         import torch
         sharded = False
@@ -79,6 +80,7 @@ class SamplingCore:
             sharded = dist.get_world_size(process_group) > 1
         opt = check_step_options(N, "online", sharded=sharded, **opts)
         refine = check_refine(refine, "online", sigma_period=opt.sigma_period, sharded=sharded)
+        riccati = check_riccati(riccati, "a sampling core", refine=refine, sharded=sharded)
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -219,6 +221,9 @@ class SamplingCore:
         # the covo-online controllers, not a step option -- _options.check_refine)
         self.refine = refine
         self.refine_rows = self._attach_rows(_lib.COVO_REFINE_FLOATS, "covo_set_step_refine") if refine else None
+        # self.riccati_rows [rows, 8]: a refine row that ends {.., mu, bits(flags | rung << 8)} (riccati=: _options.check_riccati)
+        self.riccati_on = riccati  # (riccati() is the stand-alone sweep)
+        self.riccati_rows = self._attach_rows(_lib.COVO_RICCATI_FLOATS, "covo_set_step_riccati") if riccati else None
         self._list_infos()
         self.exchange = "collective"
         if self.world > 1:
@@ -367,7 +372,8 @@ class SamplingCore:
             (self.lam_eff is not None, self.lam_info), (self.arbiter is not None, self.arbiter_info),
             (self.iter_cost_min is not None, self.iter_info), (self.elite_rows is not None, self.elite_info),
             (self.sigma_period > 1, self.sigma_info), (self.post_cov is not None, self.post_cov_info),
-            (self.sigma_adapt_rows is not None, self.sigma_adapt_info), (self.refine_rows is not None, self.refine_info)) if on]
+            (self.sigma_adapt_rows is not None, self.sigma_adapt_info), (self.refine_rows is not None, self.refine_info),
+            (self.riccati_rows is not None, self.riccati_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -519,6 +525,57 @@ class SamplingCore:
         row = self.refine_rows[0]
         return {"refine_cost_base": row[0], "refine_cost": row[1], "refine_choice": row[2:3].view(self.torch.int32)[0],
                 "refine_alpha": row[3], "refine_grad_norm": row[4], "refine_slope": row[5]}
+
+    def riccati_info(self) -> dict:
+        """{"riccati_cost_base", "riccati_cost", "riccati_choice" (0-d int32), "riccati_alpha", "riccati_grad_norm", "riccati_slope",
+        "riccati_reg" (mu), "riccati_rung" (0-d int32: flags | rung << 8, shifted down)} of the last step as views of self.riccati_rows
+        (no sync, no copy; the rung is one device op on a view); {} when the core was built without riccati."""
+        if self.riccati_rows is None:
+            return {}
+        row = self.riccati_rows[0]
+        return {"riccati_cost_base": row[0], "riccati_cost": row[1], "riccati_choice": row[2:3].view(self.torch.int32)[0],
+                "riccati_alpha": row[3], "riccati_grad_norm": row[4], "riccati_slope": row[5], "riccati_reg": row[6],
+                "riccati_rung": row[7:8].view(self.torch.int32)[0] >> 8}
+
+    def riccati(self, dstate, params_c, a, reg0=_lib.COVO_RICCATI_REG0, f_steps=None, packed=None):
+        """covo_riccati: the Riccati sweep (csrc/riccati.hip) over the stage blocks of the Hessian's objective at `a` (float32 device
+        tensor [128] or [batch, 128]) -> dict of float64 device tensors: "d" [batch, 128] = -(R + mu I)^-1 g on the lowest rung
+        mu = reg0 4^j, j < 8, at which R + mu I is positive definite; "K" [batch, 32, 4, 16] the feedback gains (columns at and above
+        the state dimension are 0), "kff" [batch, 32, 4] the feed-forward terms, "x" [batch, 32, 16] the nominal states along the plan;
+        "rows" [batch, 4] = {mu, rung, smallest pivot, flags}.  f_steps: the [batch, H, 4] table of
+        disturb_table(key_mode=DISTURB_KEYS_HESSIAN) for periodic / sin / drag / mixed; packed: the [batch, 32] states (default:
+        dstate's, for every entry).  The workspace is the sweep's own: hessian(), cost_gradient() and the step's Hessian are untouched."""
+        torch = self.torch
+        a = a.reshape(-1, COVO_NA).contiguous()
+        batch = int(a.shape[0])
+        assert a.is_cuda and a.dtype == torch.float32
+        if packed is None:
+            packed = dstate.packed.reshape(1, -1).expand(batch, -1).contiguous()
+        assert packed.numel() == batch * _lib.COVO_STATE_FLOATS and packed.is_contiguous()
+        new = lambda *shape: torch.empty((batch,) + shape, dtype=torch.float64, device=self.device)
+        out = {"d": new(COVO_NA), "K": new(COVO_H, 4, 16), "kff": new(COVO_H, 4), "x": new(COVO_H, 16), "rows": new(_lib.COVO_RICCATI_SIDE)}
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_riccati(self.h, ptr(packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T, C.byref(params_c),
+                                        ptr(a), ptr(f_steps), batch, float(reg0), ptr(out["d"]), ptr(out["K"]), ptr(out["kff"]),
+                                        ptr(out["x"]), ptr(out["rows"]), self.stream()), "covo_riccati")
+        return out
+
+    def riccati_refine(self, dstate, params_c, a_mean, reg0=_lib.COVO_RICCATI_REG0, f_shared=None, f_steps=None, f_steps_hessian=None,
+                       want_costs=True):
+        """covo_riccati_refine (the stand-alone Riccati line search) on `a_mean` (float32 device tensor, 128 elements, refined IN
+        PLACE) with the inputs of rollout(): the sweep's direction d at a_mean (f_steps_hessian: the Hessian's table), the candidates
+        clip(a_mean) and clip(a_mean + 2^(3 - j) d), j = 1 .. 16, rolled out, the first cheapest committed -> (float32 [8] row
+        {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, mu, bits(flags | rung << 8)}, float32 [17] candidate costs or None)."""
+        torch = self.torch
+        assert a_mean.is_cuda and a_mean.dtype == torch.float32 and a_mean.is_contiguous() and a_mean.numel() == COVO_NA
+        row = torch.empty((_lib.COVO_RICCATI_FLOATS,), dtype=torch.float32, device=self.device)
+        costs = torch.empty((_lib.COVO_REFINE_CANDIDATES,), dtype=torch.float32, device=self.device) if want_costs else None
+        fs = (C.c_float * 3)(*[float(x) for x in f_shared]) if f_shared is not None else None
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_riccati_refine(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                               C.byref(params_c), fs, ptr(f_steps), ptr(f_steps_hessian), ptr(a_mean), float(reg0), 1,
+                                               ptr(row), ptr(costs), self.stream()), "covo_riccati_refine")
+        return row, costs
 
     def cost_gradient(self, dstate, params_c, a, f_steps=None, packed=None):
         """covo_cost_gradient: dC/da of the Hessian's objective (covo.py:134-185) at `a` (float32 device tensor [128] or [batch, 128])

@@ -160,6 +160,7 @@ KERNEL_PATH_REFUSALS = (
     ("iters", 1, "iters", "iters={v} follows the fused step" + _DEBUG_PATH + "runs one pass per call"),
     ("compute_diag", False, "compute_diag", "compute_diag is formed by the fused step" + _DEBUG_PATH + "does not produce it"),
     ("refine", False, "refine", "refine follows the fused step" + _DEBUG_PATH + "ends with the softmax mean"),
+    ("riccati_on", False, "riccati_on", "riccati follows the fused step" + _DEBUG_PATH + "ends with the softmax mean"),
 )
 
 
@@ -233,4 +234,36 @@ def check_refine(refine, what, *, sigma_period=1, sharded=False) -> bool:
     if sharded:
         raise NotImplementedError("refine=True on sample-sharded ranks: a rank's Sigma chain and costs cover its shard's step only "
                                   "until the exchange (covo_set_step_refine refuses sample-sharded steps)")
+    return True
+
+
+def check_riccati(riccati, what, *, refine=False, sharded=False) -> bool:
+    """riccati= of every sampling controller -> bool.  Like refine=, a switch and not a step option: SamplingCore, MPPIController,
+    CoVOController (both modes), BatchedCoVOController(mode="online"), get_controller and eval_env_batched take it and check it here; the
+    C side's counterpart is the riccati block of check_step_attachments (csrc/capi.hip).
+
+    riccati=True: every control step ends with the line search of refine= along a direction that needs neither R nor Sigma -- the
+    Hessian's first two launches at the committed mean leave the stage blocks of the plan, a backward Riccati sweep over them
+    (csrc/riccati.hip) gives d = -(R + mu I)^-1 g on the lowest rung mu = 1e-2 4^j, j < 8, at which R + mu I is positive definite, and
+    clip(b + 2^(3 - j) d), j = 1 .. 16, compete with clip(b) under the step's own sampling objective (covo_set_step_riccati):
+    info["riccati_cost_base"] / ["riccati_cost"] / ["riccati_choice"] / ["riccati_alpha"] / ["riccati_grad_norm"] / ["riccati_slope"] /
+    ["riccati_reg"] / ["riccati_rung"].  It goes with MPPI, covo-offline, covo-online and every sigma_period, next to the step options;
+    under iters=k every pass runs it.  False: nothing attached.
+
+    The objections, in a fixed order: anything but a bool (ValueError); together with refine=True -- both polish the committed mean
+    (ValueError); `what` one of the env-batched MPPI / covo-offline controllers, fused or staged -- their batches carry no Hessian
+    constants (NotImplementedError); sharded -- sample-sharded ranks (NotImplementedError)."""
+    if not isinstance(riccati, bool):
+        raise ValueError(f"riccati={riccati!r} (True | False)")
+    if not riccati:
+        return False
+    if refine:
+        raise ValueError("riccati=True together with refine=True: both polish the committed mean with the same line search; give one "
+                         "of them")
+    if str(what).startswith("the env-batched"):
+        raise NotImplementedError(f"riccati=True with {what}: the env-batched MPPI / covo-offline steps, fused or staged, carry no "
+                                  "per-instance Hessian constants; run BatchedCoVOController(mode=\"online\") or single controllers")
+    if sharded:
+        raise NotImplementedError("riccati=True on sample-sharded ranks: a rank's costs cover its shard's step only until the exchange "
+                                  "(covo_set_step_riccati refuses sample-sharded steps)")
     return True

@@ -146,6 +146,9 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->ws_hess));
     DESTROY(hipFree(h->ws_grad));
     DESTROY(hipFree(h->refine_g));
+    DESTROY(hipFree(h->ws_riccati));
+    DESTROY(hipFree(h->riccati_d));
+    DESTROY(hipFree(h->riccati_tab));
     DESTROY(hipEventDestroy(h->ev_fork));
     DESTROY(hipEventDestroy(h->ev_join));
     DESTROY(hipStreamDestroy(h->side_stream));
@@ -1079,6 +1082,9 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(!covo_refine_on(h),
                 "%s: the Newton refinement (covo_set_step_refine) is not available for sample-sharded steps (partial_out != NULL): "
                 "a rank's Sigma chain and costs cover its shard's step only until the exchange; detach it", what);
+        REQUIRE(!covo_riccati_on(h),
+                "%s: the Riccati refinement (covo_set_step_riccati) is not available for sample-sharded steps (partial_out != NULL): "
+                "a rank's costs cover its shard's step only until the exchange; detach it", what);
         REQUIRE(!covo_eprow_any(h),
                 "%s: the episode logs of the attachments' rows (covo_set_episode_rows) are not available for sample-sharded steps "
                 "(partial_out != NULL): none of the attachments they follow is; detach them", what);
@@ -1148,6 +1154,13 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(n_inst <= h->refine_n, "%s: %d instances, the refine buffer (covo_set_step_refine) has n_inst=%d", what, n_inst,
                 h->refine_n);
         REQUIRE(((uintptr_t)a_cov & 15) == 0, "%s: a_cov must be 16-byte aligned under the Newton refinement (covo_set_step_refine)", what);
+    }
+    if (covo_riccati_on(h)) {  // every mode and every step of a Sigma period: the sweep needs neither R nor Sigma
+        REQUIRE(!covo_refine_on(h),
+                "%s: the Riccati refinement (covo_set_step_riccati) together with the Newton refinement (covo_set_step_refine): both "
+                "polish the committed mean; detach one of them", what);
+        REQUIRE(n_inst <= h->riccati_n, "%s: %d instances, the riccati buffer (covo_set_step_riccati) has n_inst=%d", what, n_inst,
+                h->riccati_n);
     }
     return 0;
 }
@@ -1273,6 +1286,94 @@ int covo_set_step_refine(covo_handle_t h, float *rows, int32_t n_inst)
     if (h->refine_g == nullptr) COVO_CHECK_HIP(hipMalloc(&h->refine_g, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(double)));
     h->refine_out = rows;
     h->refine_n = n_inst;
+    return 0;
+}
+
+// ---- the Riccati refinement (riccati.hip, newton_refine.hip with the direction supplied).  Like the Newton refinement's, its launches
+// are eager and follow the step: no captured step graph changes
+static int riccati_reserve(covo_ctx *h, int batch, hipStream_t s)
+{
+    if (int rc = covo_grow_workspace(h, &h->ws_riccati, &h->ws_riccati_bytes, riccati_workspace_bytes(batch), s)) return rc;
+    if (h->riccati_d == nullptr)
+        COVO_CHECK_HIP(hipMalloc(&h->riccati_d, (size_t)COVO_MAX_ENVS * (COVO_NA + COVO_RICCATI_SIDE) * sizeof(double)));
+    if (h->refine_g == nullptr) COVO_CHECK_HIP(hipMalloc(&h->refine_g, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(double)));
+    if (h->riccati_tab == nullptr) COVO_CHECK_HIP(hipMalloc(&h->riccati_tab, (size_t)COVO_H * 4 * sizeof(float)));
+    return 0;
+}
+
+int covo_riccati(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                 const covo_env_params *params, const float *a, const float *f_tab_hessian, int32_t batch, double reg0, double *d_out,
+                 double *K_out, double *kff_out, double *x_out, double *rows_out, void *stream)
+{
+    REQUIRE(h, "covo_riccati: null handle");
+    CHECK_DEVICE(h, "covo_riccati");
+    REQUIRE(state && pos_traj && vel_traj && params && a && d_out && T > 0 && batch > 0, "covo_riccati: bad argument");
+    CHECK_MODEL(params, "covo_riccati");
+    REQUIRE(!covo_needs_tables(*params) || f_tab_hessian, "covo_riccati: disturb_kind=%d needs f_tab_hessian (covo_disturb_table)",
+            params->disturb_kind);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = covo_grow_workspace(h, &h->ws_riccati, &h->ws_riccati_bytes, riccati_workspace_bytes(batch), s)) return rc;
+    HessianDesc d = gradient_desc(state, pos_traj, vel_traj, T, params, a, f_tab_hessian, batch);
+    d.status_dev = h->status_dev;
+    RiccatiOut o;
+    o.d = d_out;
+    o.K = K_out;
+    o.kff = kff_out;
+    o.x = x_out;
+    o.side = rows_out;
+    return launch_riccati(d, reg0, o, h->ws_riccati, s);
+}
+
+int covo_riccati_refine(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                        const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                        const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
+                        void *stream)
+{
+    REQUIRE(h, "covo_riccati_refine: null handle");
+    CHECK_DEVICE(h, "covo_riccati_refine");
+    REQUIRE(state && pos_traj && vel_traj && params && a_mean && rows_out && T > 0, "covo_riccati_refine: bad argument");
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_riccati_refine: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(((uintptr_t)a_mean & 15) == 0, "covo_riccati_refine: a_mean must be 16-byte aligned");
+    CHECK_MODEL(params, "covo_riccati_refine");
+    REQUIRE(!covo_needs_tables(*params) || (f_disturb_steps && f_tab_hessian),
+            "covo_riccati_refine: disturb_kind=%d needs f_disturb_steps and f_tab_hessian (covo_disturb_table)", params->disturb_kind);
+    hipStream_t s = (hipStream_t)stream;
+    if (int rc = riccati_reserve(h, n_inst, s)) return rc;
+    HessianDesc hd = gradient_desc(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst);
+    hd.status_dev = h->status_dev;
+    RiccatiOut o;
+    o.d = h->riccati_d;
+    o.g = h->refine_g;
+    o.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA;
+    if (int rc = launch_riccati(hd, reg0, o, h->ws_riccati, s)) return rc;
+    for (int e = 0; e < n_inst; ++e) {
+        PlanInstDesc d = standalone_inst(state + (size_t)e * COVO_STATE_FLOATS, pos_traj, vel_traj, T, params, f_disturb_shared,
+                                         f_disturb_steps ? f_disturb_steps + (size_t)e * COVO_H * 4 : nullptr, nullptr, 1);
+        d.a_mean = d.a_mean_out = a_mean + (size_t)e * COVO_NA;
+        RefineDesc r;
+        r.g = o.g + (size_t)e * COVO_NA;
+        r.dir = o.d + (size_t)e * COVO_NA;
+        r.dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
+        r.row_out = rows_out + (size_t)e * COVO_RICCATI_FLOATS;
+        r.costs_out = costs_out ? costs_out + (size_t)e * COVO_REFINE_CANDIDATES : nullptr;
+        if (int rc = launch_newton_refine_one(h, d, rollout_clip(h), r, s)) return rc;
+    }
+    return 0;
+}
+
+int covo_set_step_riccati(covo_handle_t h, float *rows, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_riccati: null handle");
+    if (rows == nullptr) {
+        h->riccati_out = nullptr;
+        h->riccati_n = 0;
+        return 0;
+    }
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_riccati: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    // the step's scratch, here and not in a step: a workspace never grows inside the steady state
+    if (int rc = riccati_reserve(h, n_inst, nullptr)) return rc;
+    h->riccati_out = rows;
+    h->riccati_n = n_inst;
     return 0;
 }
 
@@ -1475,6 +1576,9 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
             "%s: the posterior covariance (covo_set_step_post_cov) is not available for the env-batched MPPI / covo-offline step: its "
             "one fused launch keeps the samples in LDS and never stores them, and there is no staged batched fallback; detach the "
             "buffer", what);
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || !covo_riccati_on(h),
+            "%s: the Riccati refinement (covo_set_step_riccati) is not available for the env-batched MPPI / covo-offline step, fused or "
+            "staged: those batches carry no per-instance Hessian constants; detach it", what);
     if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, what))) return rc;  // (batched steps derive their keys)
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);

@@ -105,6 +105,13 @@ struct covo_ctx {
     void *ws_grad;            // scratch of the first-order adjoint (its own: the Sigma chain and the debug readers own ws_hess)
     size_t ws_grad_bytes;
     double *refine_g;         // [COVO_MAX_ENVS][128] the gradients of a step's instances at their committed means
+    // the Riccati refinement of the committed mean (covo_set_step_riccati; riccati.hip, newton_refine.hip); riccati_out null: off
+    float *riccati_out;       // caller's [riccati_n][COVO_RICCATI_FLOATS]: instance e's row of every step
+    int riccati_n;
+    void *ws_riccati;         // the refinement's own Hessian workspace and sweep slices (riccati_workspace_bytes)
+    size_t ws_riccati_bytes;
+    double *riccati_d;        // [COVO_MAX_ENVS][128 + COVO_RICCATI_SIDE]: the directions, then the side rows, of a step's instances
+    float *riccati_tab;       // [H][4] the Hessian's disturbance table of a single step (MPPI, covo-offline and reuse steps build none)
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -159,6 +166,7 @@ static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullp
 static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->eplog[COVO_EPLOG_FAN].log != nullptr; }
 static inline bool covo_arb_on(const covo_ctx *h) { return h->arb_out != nullptr; }
 static inline bool covo_refine_on(const covo_ctx *h) { return h->refine_out != nullptr; }
+static inline bool covo_riccati_on(const covo_ctx *h) { return h->riccati_out != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->eplog[COVO_EPLOG_DIAG].log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->eplog[COVO_EPLOG_DIAG].log ? COVO_MAX_ENVS : 0); }
@@ -518,6 +526,27 @@ int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const D
 // (R, stats, status_dev and begin are not read), the workspace the gradient's own (cost_gradient_workspace_bytes)
 size_t cost_gradient_workspace_bytes(int batch);
 int launch_cost_gradient(const HessianDesc &d, double *g_out, void *workspace, hipStream_t s);
+// where launches 1 | 2 of launch_hessian leave their results in one entry's workspace, in doubles (hessian_adj_body.hpp: WS_*): x_k
+// [32][16], df_k/dz [32][nx][nx + 4], lam_k [33][16], Mxx [32][16][16], Mxu [32][16][4], Muu [32][4][4]; entries lie `count` apart
+struct HessianWsLayout {
+    int nx;
+    size_t count, x, jf, lam, mxx, mxu, muu;
+};
+HessianWsLayout hessian_workspace_layout(bool fs);
+// riccati.hip: launches 1 | 2 of launch_hessian into `workspace` (riccati_workspace_bytes: a Hessian workspace, then the sweep's
+// slices), then the Riccati sweep over the stage blocks they leave: d = -(R + mu I)^-1 g on the lowest rung mu = reg0 4^j, j < 8,
+// at which R + mu I is positive definite, with the gains and the nominal states along the plan.  d as for launch_hessian (R, stats
+// and begin are not read)
+struct RiccatiOut {
+    double *d = nullptr;     // [batch][128]
+    double *g = nullptr;     // [batch][128], nullable: the gradient the sweep formed
+    double *K = nullptr;     // [batch][H][4][16], nullable
+    double *kff = nullptr;   // [batch][H][4], nullable
+    double *x = nullptr;     // [batch][H][16], nullable
+    double *side = nullptr;  // [batch][COVO_RICCATI_SIDE] {mu, rung, smallest pivot, flags}, nullable
+};
+size_t riccati_workspace_bytes(int batch);
+int launch_riccati(const HessianDesc &d, double reg0, const RiccatiOut &o, void *workspace, hipStream_t s);
 size_t hessian_consts_bytes(int n);
 void hessian_fill_consts(const covo_env_params *params, int n, void *out);
 // the per-pair hyper-dual rollout version (hessian.hip): slower, independent derivation, kept as a cross-check
@@ -650,6 +679,10 @@ struct RefineDesc {
     float sample_sigma = 0.0f;
     float *row_out = nullptr;         // [COVO_REFINE_FLOATS], nullable
     float *costs_out = nullptr;       // [COVO_REFINE_CANDIDATES], nullable
+    // the direction supplied (riccati.hip): d [128] and the sweep's side row [COVO_RICCATI_SIDE]; Sigma, inv_c2 and sumlogB are then
+    // not read, and the row ends {.., mu, bits(flags | rung << 8)}
+    const double *dir = nullptr;
+    const double *dir_side = nullptr;
 };
 int launch_newton_refine(covo_ctx *h, const PlanInstDesc *inst, const RefineDesc *r, int n_inst, bool batched, hipStream_t s);
 int launch_newton_refine_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const RefineDesc &r, hipStream_t s);

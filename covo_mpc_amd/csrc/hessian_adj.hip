@@ -58,6 +58,13 @@ namespace adj16 {
 
 constexpr size_t WS_COUNT_MAX = adj16::WS_COUNT > adj13::WS_COUNT ? adj16::WS_COUNT : adj13::WS_COUNT;
 size_t hessian_workspace_bytes(int batch) { return (size_t)batch * WS_COUNT_MAX * sizeof(double); }
+// where launches 1 | 2 leave what a reader of the workspace needs (riccati.hip), by instantiation
+HessianWsLayout hessian_workspace_layout(bool fs)
+{
+#define ADJ_LAYOUT(NS) HessianWsLayout{NS::NX, NS::WS_COUNT, NS::WS_X, NS::WS_JF, NS::WS_LAM, NS::WS_MXX, NS::WS_MXU, NS::WS_MUU}
+    return fs ? ADJ_LAYOUT(adj16) : ADJ_LAYOUT(adj13);
+#undef ADJ_LAYOUT
+}
 
 int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const DebugMasks &dbg)
 {

@@ -13,7 +13,9 @@
 //
 // One launch, one workgroup of three waves per instance (after_step.hpp), eager, behind the update arbiter and ahead of the plan / fan:
 //   phase 0  the per-step scalars (after_derive); g -> LDS; t = Sigma g, d = -(Sigma t) / c^2: Sigma fp32 as the step left it, row i by
-//            one lane, k ascending, fp64 fma; t and d in LDS; the action image [H][64] float4 (lanes above 16 copy lane 0)
+//            one lane, k ascending, fp64 fma; t and d in LDS; the action image [H][64] float4 (lanes above 16 copy lane 0).  With the
+//            direction supplied (RefineArgs::dir, riccati.hip: d = -(R + mu I)^-1 g by the sweep) the two mat-vecs are skipped and
+//            nothing of Sigma or c is read; the row then ends {.., mu, bits(flags | rung << 8)}, flags bit 3 the sweep's
 //   phase 1  rp3_stages with A_LDS, N = 64, PLAN = 3 on the image
 //   phase 2  one lane decides; choice j >= 1 writes the candidate as it was rolled out (clipped) into a_mean, choice 0 writes nothing;
 //            the row {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, 0, bits(flags)}.
@@ -37,6 +39,8 @@ struct RefineArgs {
     float *row_out;         // [COVO_REFINE_FLOATS] or null
     float *costs_out;       // [NR_CAND] or null
     int nanp;
+    const double *dir;      // [128] the direction supplied (riccati.hip), or null: d from Sigma and c^2 as above ...
+    const double *dir_side; // ... with the sweep's side row {mu, rung, smallest pivot, flags}
 };
 
 struct RefNoPos {  // (update_arbiter.hip: ArbNoPos)
@@ -86,6 +90,8 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
         Pb.a_mean = rebase_global(P_.a_mean, Pb.a_mean);
         Pb.row_out = rebase_global(P_.row_out, Pb.row_out);
         Pb.costs_out = rebase_global(P_.costs_out, Pb.costs_out);
+        Pb.dir = rebase_global(P_.dir, Pb.dir);
+        Pb.dir_side = rebase_global(P_.dir_side, Pb.dir_side);
     }
     const RefineArgs &P = BATCHED ? Pb : P_;
     __shared__ RefLds S;
@@ -95,8 +101,11 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
 
     // ---- phase 0
     after_derive(tid, P.head, dyn, BATCHED, S.kb, S.dyn);
+    const bool supplied = P_.dir != nullptr;  // (all instances alike)
     double inv_c2;
-    if (P_.inv_c2 != nullptr) {
+    if (supplied) {
+        inv_c2 = 1.0;  // (never used: no Sigma, no c)
+    } else if (P_.inv_c2 != nullptr) {
         inv_c2 = P.inv_c2[0];
     } else {
         const double s2 = (double)P.sample_sigma * (double)P.sample_sigma;
@@ -108,13 +117,20 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
         gi = P.g[tid];
         S.g[tid] = gi;
     }
-    __syncthreads();
-    if (row) S.t[tid] = refine_row_dot(P.Sigma, tid, S.g);
-    __syncthreads();
     double di = 0.0;
-    if (row) {
-        di = -refine_row_dot(P.Sigma, tid, S.t) * inv_c2;
-        S.d[tid] = di;
+    if (supplied) {
+        if (row) {
+            di = P.dir[tid];
+            S.d[tid] = di;
+        }
+    } else {
+        __syncthreads();
+        if (row) S.t[tid] = refine_row_dot(P.Sigma, tid, S.g);
+        __syncthreads();
+        if (row) {
+            di = -refine_row_dot(P.Sigma, tid, S.t) * inv_c2;
+            S.d[tid] = di;
+        }
     }
     if (wave < 2) {
         const double gg = wr::wave64_allsum(gi * gi), gd = wr::wave64_allsum(gi * di);
@@ -125,7 +141,7 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
     }
     // (__syncthreads_or is a logical or: one per bit; the first is also the barrier behind S.d)
     const int flags = (__syncthreads_or(row && !refine_finite(gi)) ? 1 : 0) | (__syncthreads_or(row && !refine_finite(di)) ? 2 : 0) |
-                      (!(refine_finite(inv_c2) && inv_c2 > 0.0) ? 4 : 0);
+                      (!(refine_finite(inv_c2) && inv_c2 > 0.0) ? 4 : 0) | (supplied ? ((int)P.dir_side[3] & 8) : 0);
     {
         const float4 *__restrict__ am4 = reinterpret_cast<const float4 *>(P.a_mean);
         const int nanp = P_.nanp;
@@ -183,8 +199,10 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
         if (has_row) {
             const double gg = S.red[0][0] + S.red[1][0], gd = S.red[0][1] + S.red[1][1];
             const float alpha = choice >= 1 ? __builtin_ldexpf(1.0f, 3 - choice) : 0.0f;
+            const float w6 = supplied ? (float)P.dir_side[0] : 0.0f;
+            const int w7 = supplied ? (flags | ((int)P.dir_side[1] << 8)) : flags;
             const float out[COVO_REFINE_FLOATS] = {S.cost[0], S.cost[choice], __int_as_float(choice), alpha,
-                                                   (float)sqrt(gg),  (float)gd,      0.0f,                  __int_as_float(flags)};
+                                                   (float)sqrt(gg),  (float)gd,      w6,                    __int_as_float(w7)};
 #pragma unroll
             for (int j = 0; j < COVO_REFINE_FLOATS; ++j) P.row_out[j] = out[j];
         }
@@ -209,6 +227,8 @@ static void fill_refine_args(RefineArgs &P, covo_ctx *h, const PlanInstDesc &d, 
     P.row_out = r.row_out;
     P.costs_out = r.costs_out;
     P.nanp = covo_propagate_nan(h) ? 1 : 0;
+    P.dir = r.dir;
+    P.dir_side = r.dir_side;
 }
 
 // covo_newton_refine: one instance, the caller's buffers and shared vector (d.derive_keys = 0), the clip covo_rollout_cost applies

@@ -1295,12 +1295,32 @@ static int refine_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched,
     }
     return launch_newton_refine(h, d, r, n, batched, s);
 }
-// the refinement (rs: null for the steps that have none) directly behind the arbiter, every pass of an iterated step included
+// covo_set_step_riccati: the Hessian's first two launches at the committed means into the refinement's own workspace, the sweep
+// (riccati.hip), then the line search with the direction supplied.  hd: the Hessian's inputs, dense over the n instances
+static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, HessianDesc hd, hipStream_t s)
+{
+    hd.status_dev = h->status_dev;
+    RiccatiOut o;
+    o.d = h->riccati_d;
+    o.g = h->refine_g;
+    o.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA;
+    if (int rc = launch_riccati(hd, COVO_RICCATI_REG0, o, h->ws_riccati, s)) return rc;
+    RefineDesc r[COVO_MAX_ENVS];
+    for (int e = 0; e < n; ++e) {
+        r[e].g = o.g + (size_t)e * COVO_NA;
+        r[e].dir = o.d + (size_t)e * COVO_NA;
+        r[e].dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
+        r[e].row_out = h->riccati_out + (size_t)e * COVO_RICCATI_FLOATS;
+    }
+    return launch_newton_refine(h, d, r, n, batched, s);
+}
+// the refinement (rs / ric: null for the steps that have none) directly behind the arbiter, every pass of an iterated step included
 static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const float *states_true, int trace_index, hipStream_t s,
-                      bool arbiter_only, const RefineStep *rs)
+                      bool arbiter_only, const RefineStep *rs, const HessianDesc *ric = nullptr)
 {
     int rc = launch_update_arbiter(h, d, n, batched, trace_index, s);
     if (rc == 0 && rs != nullptr && covo_refine_on(h)) rc = refine_after(h, d, n, batched, *rs, s);
+    if (rc == 0 && ric != nullptr && covo_riccati_on(h)) rc = riccati_after(h, d, n, batched, *ric, s);
     if (rc || arbiter_only) return rc;
     if ((rc = launch_plan_trace(h, d, n, batched, states_true, trace_index, s))) return rc;
     return launch_sample_fan(h, d, n, batched, trace_index, s);
@@ -1309,7 +1329,7 @@ static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, c
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                          const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
     // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
     // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
@@ -1334,7 +1354,25 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
         rs.Sigma = args->a_cov ? args->a_cov : st->Sigma;
         rs.sample_sigma = args->sample_sigma;
     }
-    if (int rc = plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only, refine ? &rs : nullptr)) return rc;
+    // the Riccati refinement: every mode, every step of a Sigma period.  The Hessian's disturbance table is formed here from the raw key
+    // (MPPI, covo-offline and reuse steps build none; a refresh step's own holds the same rows)
+    HessianDesc ric;
+    const bool riccati = covo_riccati_on(h);
+    if (riccati) {
+        ric.state = d.state;
+        ric.pos_traj = d.pos_traj;
+        ric.vel_traj = d.vel_traj;
+        ric.T = d.T;
+        ric.params = params;
+        ric.a_mean = args->a_mean;
+        if (covo_needs_tables(*params)) {
+            if (int rc = launch_disturb_table(*params, d.state, 1, d.key_mem, key0, key1, COVO_DISTURB_KEYS_HESSIAN, 1, h->riccati_tab, s))
+                return rc;
+            ric.f_tab = h->riccati_tab;
+        }
+    }
+    if (int rc = plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only, refine ? &rs : nullptr, riccati ? &ric : nullptr))
+        return rc;
     // the posterior covariance: behind the (last pass's) update and the launches above; d.a_nominal is the mean that pass sampled around
     return arbiter_only ? 0 : launch_post_cov_after(h, d.a, d.cost, d.a_nominal, d.N, 1, s);
 }
@@ -1343,7 +1381,7 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
                             const float *states_true, int trace_index, hipStream_t s, bool arbiter_only)
 {
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h)) return 0;
+    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
     const bool online = mode == COVO_MODE_COVO_ONLINE;
@@ -1383,7 +1421,23 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
         rs.Sigma = args->a_cov ? args->a_cov : b->Sigma;
         rs.sample_sigma = args->sample_sigma;
     }
-    if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only, refine ? &rs : nullptr)) return rc;
+    HessianDesc ric;
+    const bool riccati = covo_riccati_on(h) && online;  // (check_batch_step refuses the other modes)
+    if (riccati) {
+        ric.state = args->states;
+        ric.pos_traj = args->pos_traj;
+        ric.vel_traj = args->vel_traj;
+        ric.T = args->T;
+        ric.params = &c->params[0];
+        ric.a_mean = args->a_mean;
+        ric.batch = E;
+        ric.consts_dev = b->consts;
+        ric.traj_stride = (size_t)args->T * 3;
+        ric.f_tab = c->tables ? b->tab_hess : nullptr;
+        ric.models_dev = c->models;
+    }
+    if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only, refine ? &rs : nullptr, riccati ? &ric : nullptr))
+        return rc;
     // the posterior covariance of every instance (never behind the fused launch: check_batch_step): dense slices, the begin launch's
     // shifted means
     return arbiter_only ? 0 : launch_post_cov_after(h, args->a, args->cost, shifted, args->n_samples, E, s);

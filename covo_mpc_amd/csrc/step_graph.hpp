@@ -73,7 +73,7 @@ static int graph_cache_run(covo_ctx *h, GraphCache &c, hipStream_t s, bool same,
 
 // ---- the pass driver of the single and the env-batched covo-online step.  covo_set_step_iters: K passes on one state, all in the
 // step's graph -- cache[0], or cache[1] for the reuse step of a Sigma period (another launch set).  pass(stream, j) enqueues pass j.
-// With the update arbiter or the Newton refinement attached their launches sit between the passes: between(stream, j) enqueues them
+// With the update arbiter, the Newton refinement or the Riccati refinement attached their launches sit between the passes: between(stream, j) enqueues them
 // behind pass j < K - 1; they are eager by nature (their arguments are the step's), so the passes are then enqueued eagerly too and
 // both graphs are forgotten.
 // same: graph_cache_seen(cache[reuse], ...) of this call.
@@ -90,7 +90,7 @@ static int step_run_passes(covo_ctx *h, GraphCache (&cache)[2], bool reuse, bool
         }
         return 0;
     };
-    if (K > 1 && (covo_arb_on(h) || covo_refine_on(h))) {
+    if (K > 1 && (covo_arb_on(h) || covo_refine_on(h) || covo_riccati_on(h))) {
         cache[0].forget(), cache[1].forget();
         return passes(s, true);
     }

@@ -770,6 +770,49 @@ int covo_newton_refine(covo_handle_t h, const float *state, const float *pos_tra
                        const float *f_tab_hessian, const double *g, float *a_mean, const float *Sigma, const double *inv_c2,
                        int32_t n_inst, float *rows_out, float *costs_out, void *stream);
 int covo_set_step_refine(covo_handle_t h, float *rows /* DEVICE [n_inst][COVO_REFINE_FLOATS]; NULL = off */, int32_t n_inst);
+
+/* The Riccati refinement: the same line search for every sampling controller (additive to ABI 10: COVO_HAS_RICCATI_REFINE; off by
+ * default, and off changes nothing a caller can observe: no launch is added).
+ * The Hessian's first two launches leave A_k, B_k, the costate and the exact stage blocks M_k = Hess_z(r_k + lam_{k+1} . f_k) of every
+ * stage of the plan.  A backward Riccati sweep over them (csrc/riccati.hip, fp64) is the block elimination of the reduced Hessian R:
+ * its forward pass returns d = -(R + mu I)^-1 g with neither R, Sigma nor a 128 x 128 factorisation, next to the time-varying
+ * feedback gains K_k, the feed-forward terms k_k and the nominal states x_k (du_k = k_k + K_k dx_k: the ancillary LQR controller along
+ * the plan).  mu is the lowest rung of the ladder reg0 4^j, j = 0 .. COVO_RICCATI_RUNGS - 1, at which all 32 pivots Quu_k -- unpivoted
+ * 4 x 4 Cholesky factorisations -- are positive, which is exactly where R + mu I is positive definite.
+ *   side row  double[COVO_RICCATI_SIDE] = {mu, rung, smallest pivot of that rung, flags}; flags bit 0: g not finite (an entry of a that is not finite counts), bit 1: d
+ *             not finite, bit 3: no rung positive definite -- then d = 0, K = 0, k = 0, mu = 0 and rung = COVO_RICCATI_RUNGS
+ *   row       float[COVO_RICCATI_FLOATS] = {cost_base, cost_chosen, bits(int32 choice), alpha (0 for choice 0), |g|_2, g.d, mu,
+ *             bits(int32 flags | rung << 8)}: a refine row whose last two words say what the sweep did
+ * covo_riccati: the stand-alone sweep at a = DEVICE float[batch][128] with the arguments of covo_hessian (f_tab_hessian = DEVICE
+ *   float[batch][H][4] or NULL); d_out = DEVICE double[batch][128] (rows 124 .. 127 are 0; a component whose action saturates is 0);
+ *   K_out = DEVICE double[batch][H][4][16] (columns at and above the state dimension -- 13, or 16 for drag / mixed -- are 0), kff_out =
+ *   DEVICE double[batch][H][4], x_out = DEVICE double[batch][H][16], rows_out = DEVICE double[batch][COVO_RICCATI_SIDE]; each of the
+ *   four may be NULL.
+ * covo_riccati_refine: stateless, covo_newton_refine without Sigma and c: the Hessian's two launches and the sweep at a_mean, then the
+ *   line search of covo_newton_refine with that direction -- the candidates clip(a_mean) and fp32(clip(a_mean + 2^(3 - j) d)),
+ *   j = 1 .. 16, rolled out with the inputs of covo_arbitrate, the first cheapest committed to a_mean (16-byte aligned, in / out);
+ *   rows_out = DEVICE float[n_inst][COVO_RICCATI_FLOATS], costs_out = DEVICE float[n_inst][COVO_REFINE_CANDIDATES] or NULL.
+ * covo_set_step_riccati: rows = DEVICE float[n_inst][COVO_RICCATI_FLOATS]; every control step of the handle -- MPPI, covo-offline and
+ *   covo-online, refresh and reuse steps of a Sigma period alike, single and env-batched covo-online, the episode drivers -- then ends
+ *   with eager launches behind the update arbiter's and ahead of the plan's and the fan's: the Hessian's first two at the committed
+ *   mean (objective: the Hessian's -- no discount, no freeze, its disturbance table from the step's raw key), the sweep with
+ *   reg0 = COVO_RICCATI_REG0, the line search.  Under iterations per step every pass runs them and the row is the last pass's.  The
+ *   workspace is the refinement's own.  No captured step graph changes.
+ * Refused before any launch, with a message that names the condition: a sample-sharded step (partial_out != NULL); the Newton
+ *   refinement attached to the same handle; more instances than rows; the env-batched MPPI / covo-offline steps. */
+#define COVO_HAS_RICCATI_REFINE 1
+#define COVO_RICCATI_FLOATS 8
+#define COVO_RICCATI_SIDE 4
+#define COVO_RICCATI_RUNGS 8
+#define COVO_RICCATI_REG0 1e-2
+int covo_riccati(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                 const covo_env_params *params, const float *a, const float *f_tab_hessian, int32_t batch, double reg0, double *d_out,
+                 double *K_out, double *kff_out, double *x_out, double *rows_out, void *stream);
+int covo_riccati_refine(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                        const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                        const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
+                        void *stream);
+int covo_set_step_riccati(covo_handle_t h, float *rows /* DEVICE [n_inst][COVO_RICCATI_FLOATS]; NULL = off */, int32_t n_inst);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);
