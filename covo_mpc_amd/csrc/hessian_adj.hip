@@ -16,15 +16,19 @@
 // templated model (quad_model.hpp) on hyper-dual numbers, so every JAX AD convention it mirrors (clip ties,
 // |x|', the double clip of quadrotor.py:223/:258) carries over.  Three launches (KM rides in KC's):
 //   KB  32 waves: primal rollout to step k (plain fp64), then the step on first-order duals (17 seeds) -> A_k, B_k, grad r_k
-//   KC  9 waves: the sensitivity recursion (8 column tiles of S held in MFMA C/D layout, which IS the B operand
+//   KC  9 workgroups of four waves: the sensitivity recursion (8 column tiles of S held in MFMA C/D layout, which IS the B operand
 //       of the next step: four dependent v_mfma_f64_16x16x4_f64 per step, nothing leaves the registers) and
-//       the costate recursion (the same product with A^T) -- no barriers, no sparsity assumptions
+//       the costate recursion (the same product with A^T) -- no sparsity assumptions.  Both are linear, so each runs as four
+//       horizon segments (8, 8, 8, 7 steps) on the four waves of its workgroup at the same time, joined with one product per
+//       boundary through LDS (hessian_adj_body.hpp: adj_chain_kernel; adj16 keeps the costate sequential)
 //   KM  32 x 153 lanes, 32 more workgroups of KC's launch: one hyper-dual step per pair (a <= b) of step inputs, contracted with
 //       lam_{k+1} as soon as the costate chain of the same launch has stored it -> M_k = Hess_z(r_k + lam_{k+1}.f_k)
 //   KD  36 lower 16x16 tiles: sum_k S_k^T Mxx_k S_k on the matrix cores (v_mfma_f64_16x16x4_f64; the product
 //       Mxx S leaves the MFMA in exactly the register layout the next MFMA wants as its B operand), the
-//       action blocks Mxu, Muu added in the epilogue.
-// Critical path: 30 plain steps + 2 hyper-dual steps + a 31-step recursion of 13-vectors ~ 25 us.
+//       action blocks Mxu, Muu added in the epilogue.  A NaN of the costate (norm'(0)) is laid over every tile, as the reference's AD has it
+//       in every entry.
+// Critical path: the primal prefix (five scan levels; drag / mixed: 30 plain steps) + 2 hyper-dual steps + an 8-step segment of
+// each recursion, its joins and fills ~ 22 us.
 // The kernels live in hessian_adj_body.hpp and are compiled twice: adj13 (x in R^13: the force of a step is a constant of that
 // step -- none / gaussian / periodic / sin) and adj16 (x in R^16 = state + force: drag / mixed, whose next force depends on the
 // PRE-step velocity and the current force; round 3 -- these two models used to take the 80 us per-pair kernel).

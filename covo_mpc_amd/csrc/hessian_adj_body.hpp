@@ -492,39 +492,414 @@ __device__ __forceinline__ void adj_hd_padding(const AdjArgs &A, int k, int b, i
 }
 
 // ---- KC: the two linear recursions on the matrix cores.
-// S_{k+1} = A_k S_k + B_k E_k is a (13x13).(13x128) product per step: wave w keeps a 16-column tile of S in
+// S_{k+1} = A_k S_k + B_k E_k is a (13x13).(13x128) product per step: a wave keeps a 16-column tile of S in
 // the MFMA C/D layout (lane (lo, hi), register g = row 4g + hi, column lo) -- which is exactly the B operand
 // of k-group g of the next step's v_mfma_f64_16x16x4_f64, so the tile never leaves its registers; A_k
 // (zero padded to 16x16) comes from LDS as the A operand.  The costate lam_k = grad r_k + A_k^T lam_{k+1} is
-// the same product with A^T and the vector in column 0 of a tile (wave 8).  ~330 cycles per step (four
-// dependent MFMAs + the MFMA -> operand hazard), 31 steps.  (One lane per column with the vector in
+// the same product with A^T and the vector in column 0 of a tile (workgroup 8).  ~330 cycles per step (four
+// dependent MFMAs + the MFMA -> operand hazard).  (One lane per column with the vector in
 // registers: 2000 cycles per step; 16-lane rows with ds_swizzle broadcasts: 1000.)
+//
+// Both recursions are LINEAR, so their 31 dependent steps are not needed: the horizon is cut at m = 0, 8, 16, 24 into four
+// segments (8, 8, 8 and 7 steps) and the four waves of a chain workgroup -- four SIMDs, four fp64 matrix pipes -- run one segment
+// each AT THE SAME TIME; the segments are joined afterwards with one product per boundary.
+//   sensitivity tile w (forcing at steps 4w .. 4w+3, home segment jw = w / 2; segment j owns the rows S_k, m_j < k <= m_(j+1)):
+//     wave j < jw   stores the zero rows of its segment;
+//     wave jw       runs the forced chain from k0 = 4w to the end of its segment (the sequential chain's operands and order);
+//     wave j > jw   runs the transition chain Phi_j(k) = A_(k-1) ... A_(m_j) -- the same product started from A_(m_j) -- and keeps
+//                   every Phi_j(k) as an A operand (adj_cd_to_a: C/D layout -> LDS -> A layout, off the MFMA chain);
+//     join          S_(m_(j+1)) = Phi_j(m_(j+1)) S_(m_j), wave by wave, the tile handed on through 2 KiB of LDS and a barrier;
+//     fill          S_k = Phi_j(k) S_(m_j) for the other rows of segment j: independent products, every wave its own.
+//     Every tile's workgroup forms its own Phi: a hand-off between workgroups costs 1 - 2 us, more than a segment.
+//   costate (adj13): wave 3 runs the vector recursion from lam_31 down to lam_24; wave j < 3 carries the 13 x 14 tile
+//     T_k = [Psi_k | c_k] = A_k^T T_(k+1) + [0 | grad r_k] from T_(e+1) = [I | 0] through k = e .. m (e = 8j + 7) -- the four MFMAs of
+//     the vector recursion, whose other columns were idle.  lam_k = T_k (lam_(e+1); 1) joins and fills on the vector ALU
+//     (adj_cost_quarter), the vector handed down through LDS slots and flags (adj_flag_wait): a wave publishes its rows as soon as
+//     it has joined, the hyper-dual workgroups are waiting for them.
+//     A NaN reaches the rows it reached in the sequential chain: one in grad r_k[i] sits in c_k[i] (row i of lam_k) and in all of
+//     column 13 from T_(k-1) on; one in A_k[i][j] fills row j of T_k (lam_k[j]) and all of T_(k-1); a NaN lam_(e+1) spreads over
+//     every row of every lam_k below it through the zero-padded products, as A_k^T lam_(k+1) does.
+//   adj16: the sensitivities are segmented alike (Phi is 16 x 16); the costate tile would need 17 columns and keeps the sequential
+//     chain on wave 0 (as KB keeps its sequential prefix for drag / mixed).
 // batched launches (round 4): the hyper-dual workgroups as a launch of their own -- inside adj_chain_kernel every workgroup reserves the
-// chains' 59 KB of LDS (two per CU), which the 32 hyper-dual workgroups of an instance never touch; 32 instances are 1 312 workgroups
+// chains' 72 KB of LDS (two per CU), which the 32 hyper-dual workgroups of an instance never touch; 32 instances are 1 312 workgroups
 __global__ __launch_bounds__(256) void adj_hd_kernel(const AdjArgs A)
 {
     adj_hd_padding(A, (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x, 256);
     adj_hd_pairs(A, (int)blockIdx.x, (int)blockIdx.y, (int)threadIdx.x);
 }
 
+static_assert(HH == 32, "adj_chain_kernel: four horizon segments of 8, 8, 8 and 7 steps");
+constexpr int KC_ZI = (HH - 1) * NX * NZ;  // the zero slot behind the Jacobians in LDS: what the lanes outside the NX x NX block read
+constexpr int KC_TLD = 17;                 // row stride of a wave's transposition buffer (doubles): the column reads spread over the banks
+
+// LDS written by one lane of a wave and read by another of the same wave: DS operations of a wave complete in order, the compiler
+// must keep them in order too
+__device__ __forceinline__ void adj_wave_sync()
+{
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+}
+// a 16 x 16 matrix in the C/D layout (register r = M[4r + hi][lo]) -> the A operands of its four k-groups (a[g] = M[lo][4g + hi]),
+// through the wave's own LDS buffer
+__device__ __forceinline__ void adj_cd_to_a(double *__restrict__ tb, const f64x4 &t, int lo, int hi, double (&a)[4])
+{
+    adj_wave_sync();
+#pragma unroll
+    for (int r = 0; r < 4; ++r) tb[(4 * r + hi) * KC_TLD + lo] = t[r];
+    adj_wave_sync();
+#pragma unroll
+    for (int g = 0; g < 4; ++g) a[g] = tb[lo * KC_TLD + 4 * g + hi];
+}
+__device__ __forceinline__ f64x4 adj_mm(const double (&a)[4], const f64x4 &b, f64x4 acc)
+{
+#pragma unroll
+    for (int g = 0; g < 4; ++g) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(a[g], b[g], acc, 0, 0, 0);
+    return acc;
+}
+// CNT independent products pa[i] . b, issued k-group by k-group so that the matrix pipe always has an independent MFMA to take
+template <int CNT>
+__device__ __forceinline__ void adj_mm_many(const double (&pa)[8][4], const f64x4 &b, f64x4 (&out)[8])
+{
+#pragma unroll
+    for (int i = 0; i < CNT; ++i) out[i] = f64x4{0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+#pragma unroll
+        for (int i = 0; i < CNT; ++i) out[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(pa[i][g], b[g], out[i], 0, 0, 0);
+    }
+}
+
+// ---- sensitivity tile w, the wave of segment J before the joins: zero rows, then the forced chain (J == jw: -> sv = S_(M1), also
+// left in the hand-off slot) or the transition chain (J > jw: -> pa[i] = Phi_J(M0 + 1 + i) as A operands).
+// The chains are fully unrolled (k is a compile-time constant: every LDS / global address is base + immediate) and the lanes
+// outside the 13 x 13 block read a zero slot instead of being masked off: as a rolled loop with `cond ? sjf[..] : 0` operands
+// hipcc spent ~420 of a step's 755 cycles on exec-mask sequences, index arithmetic and accumulator copies around the four
+// dependent MFMAs (KC_PROF stamps; the MFMAs + their result -> operand hazard are ~330).  The wave's role is a uniform branch.
+template <int J>
+__device__ __forceinline__ void adj_sens_chain(const double *__restrict__ sjf, double *__restrict__ tb, double *__restrict__ ho,
+                                               double *__restrict__ S, int w, int lane, double (&pa)[8][4], f64x4 &sv)
+{
+    constexpr int M0 = 8 * J, M1 = J == 3 ? HH - 1 : 8 * J + 8;
+    const int lo = lane & 15, hi = lane >> 4;
+    const int col = 16 * w + lo, tcol = col >> 2, dcol = col & 3, k0 = 4 * w, jw = w >> 1;
+    double *__restrict__ Sp = S + (size_t)hi * NA + col;
+    // S_k tile = 0 for k <= 4w: the rows of this segment among them
+#pragma unroll
+    for (int k = (J == 0 ? 0 : M0 + 1); k <= M1; ++k) {
+        if (k <= k0) {  // (uniform)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Sp[((size_t)k * 16 + 4 * r) * NA] = 0.0;
+        }
+    }
+    if (J < jw) return;
+    int offA[4];  // A[lo][4g+hi]
+    bool okA[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        okA[g] = lo < NX && 4 * g + hi < NX;
+        offA[g] = lo * NZ + 4 * g + hi;
+    }
+    double an[4];
+    if (J == jw) {
+        sv = f64x4{0.0, 0.0, 0.0, 0.0};
+        f64x4 bn;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? k0 * NX * NZ + offA[g] : KC_ZI];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) bn[r] = (tcol == k0 && hi + 4 * r < NX) ? sjf[(k0 * NX + hi + 4 * r) * NZ + NX + dcol] : 0.0;  // B_k E_k
+#pragma unroll
+        for (int k = M0; k < M1; ++k) {
+            if (k < k0) continue;  // (uniform)
+            double ac[4];
+            f64x4 acc = bn;
+#pragma unroll
+            for (int g = 0; g < 4; ++g) ac[g] = an[g];
+            if (k + 1 < M1) {  // next step's operands in flight
+#pragma unroll
+                for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (k + 1) * NX * NZ + offA[g] : KC_ZI];
+                // B_k E_k is non-zero only while the tile's own four steps enter (uniform branch)
+                if (k + 1 <= k0 + 3) {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        bn[r] = (tcol == k + 1 && hi + 4 * r < NX) ? sjf[((k + 1) * NX + hi + 4 * r) * NZ + NX + dcol] : 0.0;
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) bn[r] = 0.0;
+                }
+            }
+            sv = adj_mm(ac, sv, acc);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) Sp[((size_t)(k + 1) * 16 + 4 * r) * NA] = sv[r];
+        }
+        if (J < 3) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) ho[64 * r + lane] = sv[r];
+        }
+    } else if constexpr (J > 0) {
+        // Phi(M0 + 1) = A_(M0): both layouts straight from LDS
+        f64x4 t;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) t[r] = sjf[(lo < NX && 4 * r + hi < NX) ? M0 * NX * NZ + (4 * r + hi) * NZ + lo : KC_ZI];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) pa[0][g] = sjf[okA[g] ? M0 * NX * NZ + offA[g] : KC_ZI];
+#pragma unroll
+        for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (M0 + 1) * NX * NZ + offA[g] : KC_ZI];
+#pragma unroll
+        for (int k = M0 + 1; k < M1; ++k) {
+            double ac[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) ac[g] = an[g];
+            if (k + 1 < M1) {
+#pragma unroll
+                for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (k + 1) * NX * NZ + offA[g] : KC_ZI];
+            }
+            t = adj_mm(ac, t, f64x4{0.0, 0.0, 0.0, 0.0});
+            adj_cd_to_a(tb, t, lo, hi, pa[k - M0]);
+        }
+    }
+}
+// the join of segment J (its wave, after the barrier behind the segment below): sm = S_(M0) from the slot, sv = S_(M1), handed on
+template <int J>
+__device__ __forceinline__ void adj_sens_join(const double *__restrict__ hi_slot, double *__restrict__ ho, int lane,
+                                              const double (&pa)[8][4], f64x4 &sm, f64x4 &sv)
+{
+    constexpr int CNT = J == 3 ? HH - 1 - 24 : 8;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) sm[r] = hi_slot[64 * r + lane];
+    sv = adj_mm(pa[CNT - 1], sm, f64x4{0.0, 0.0, 0.0, 0.0});
+    if (J < 3) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) ho[64 * r + lane] = sv[r];
+    }
+}
+// the rows of segment J from S_(M0): the joined end row and the fill
+template <int J>
+__device__ __forceinline__ void adj_sens_fill(double *__restrict__ S, int w, int lane, const double (&pa)[8][4], const f64x4 &sm,
+                                              const f64x4 &sv)
+{
+    constexpr int M0 = 8 * J, M1 = J == 3 ? HH - 1 : 8 * J + 8, CNT = M1 - M0;
+    double *__restrict__ Sp = S + (size_t)(lane >> 4) * NA + 16 * w + (lane & 15);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) Sp[((size_t)M1 * 16 + 4 * r) * NA] = sv[r];
+    f64x4 out[8];
+    adj_mm_many<CNT - 1>(pa, sm, out);
+#pragma unroll
+    for (int i = 0; i < CNT - 1; ++i) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) Sp[((size_t)(M0 + 1 + i) * 16 + 4 * r) * NA] = out[i][r];
+    }
+}
+
+// ---- costate: the vector recursion from lam_31 = grad r_31 down to lam_KEND, the vector in column 0 of the tile (adj13: wave 3's
+// segment, KEND = 24; adj16: the whole chain, KEND = 1).  -> lam = lam_KEND (column 0)
+template <int KEND>
+__device__ __forceinline__ void adj_cost_top(const double *__restrict__ sjf, const double *__restrict__ G, double *__restrict__ L,
+                                             int lane, f64x4 &lam)
+{
+    const int lo = lane & 15, hi = lane >> 4;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lam[r] = (lo == 0 && hi + 4 * r < NX) ? G[16 * (HH - 1) + hi + 4 * r] : 0.0;
+    // (agent-scope write-through stores: the hyper-dual workgroups of this launch poll these rows, adj_hd_pairs)
+    if (lo == 0) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            __hip_atomic_store(&L[16 * (HH - 1) + hi + 4 * r], lam[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(&L[16 * HH + hi + 4 * r], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+    int offA[4];  // A^T[lo][4g+hi] = df/dz[4g+hi][lo]
+    bool okA[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        okA[g] = lo < NX && 4 * g + hi < NX;
+        offA[g] = (4 * g + hi) * NZ + lo;
+    }
+    bool okG[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) okG[r] = lo == 0 && hi + 4 * r < NX;
+    double an[4];
+    f64x4 gn;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (HH - 2) * NX * NZ + offA[g] : KC_ZI];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) gn[r] = okG[r] ? G[16 * (HH - 2) + hi + 4 * r] : 0.0;
+#pragma unroll
+    for (int k = HH - 2; k >= KEND; --k) {
+        double ac[4];
+        f64x4 acc = gn;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) ac[g] = an[g];
+        if (k > KEND) {  // next step's operands in flight
+#pragma unroll
+            for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (k - 1) * NX * NZ + offA[g] : KC_ZI];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gn[r] = okG[r] ? G[16 * (k - 1) + hi + 4 * r] : 0.0;
+        }
+        lam = adj_mm(ac, lam, acc);
+        if (lo == 0) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) __hip_atomic_store(&L[16 * k + hi + 4 * r], lam[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+#if !ADJ_FS
+// segment J < 3 of the costate before the joins: T_k = [Psi_k | c_k], k = E .. M, -> pa[E - k] = T_k as A operands
+template <int J>
+__device__ __forceinline__ void adj_cost_chain(const double *__restrict__ sjf, const double *__restrict__ G, double *__restrict__ tb,
+                                               int lane, double (&pa)[8][4])
+{
+    constexpr int E = 8 * J + 7, M = J == 0 ? 1 : 8 * J;
+    const int lo = lane & 15, hi = lane >> 4;
+    int offA[4], offT[4];  // A^T[lo][4g+hi] = df/dz[4g+hi][lo];  A^T[4r+hi][lo] = df/dz[lo][4r+hi]
+    bool okA[4], okG[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        okA[g] = lo < NX && 4 * g + hi < NX;
+        offA[g] = (4 * g + hi) * NZ + lo;
+        offT[g] = lo * NZ + 4 * g + hi;
+        okG[g] = lo == NX && 4 * g + hi < NX;  // column 13 carries c_k
+    }
+    // T_E = [A_E^T | grad r_E]: both layouts straight from LDS
+    f64x4 t;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const double a = sjf[okA[r] ? E * NX * NZ + offT[r] : KC_ZI];
+        t[r] = okG[r] ? G[16 * E + hi + 4 * r] : a;
+    }
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const double a = sjf[okA[g] ? E * NX * NZ + offA[g] : KC_ZI];
+        pa[0][g] = (4 * g + hi == NX && lo < NX) ? G[16 * E + lo] : a;
+    }
+    double an[4];
+    f64x4 gn;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (E - 1) * NX * NZ + offA[g] : KC_ZI];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) gn[r] = okG[r] ? G[16 * (E - 1) + hi + 4 * r] : 0.0;
+#pragma unroll
+    for (int k = E - 1; k >= M; --k) {
+        double ac[4];
+        f64x4 acc = gn;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) ac[g] = an[g];
+        if (k > M) {  // next step's operands in flight
+#pragma unroll
+            for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (k - 1) * NX * NZ + offA[g] : KC_ZI];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) gn[r] = okG[r] ? G[16 * (k - 1) + hi + 4 * r] : 0.0;
+        }
+        t = adj_mm(ac, t, acc);
+        adj_cd_to_a(tb, t, lo, hi, pa[E - k]);
+    }
+}
+// lam_k = T_k (lam_(e+1); 1) on the vector ALU: with T_k as A operands (a[g] = T_k[lo][4g + hi]) and vv[g] = v[4g + hi] a lane holds a
+// quarter of row lo's dot product, the four quarters meet over hi.  (As MFMAs with the vector in column 0 a row cost four dependent
+// matrix instructions, 0.25 us a join and 0.9 us the seven rows of a fill; this is a third of that.)  A padded zero times a NaN
+// vector is a NaN here as on the matrix cores.
+__device__ __forceinline__ double adj_cost_quarter(const double (&a)[4], const double (&vv)[4])
+{
+    return fma(a[3], vv[3], fma(a[2], vv[2], fma(a[1], vv[1], a[0] * vv[0])));
+}
+__device__ __forceinline__ double adj_cost_over_hi(double p)
+{
+    p += __shfl_xor(p, 16, 64);
+    p += __shfl_xor(p, 32, 64);
+    return p;
+}
+// row k of the costate from the lanes hi == 0 (v = lam_k[lo], all 16 rows like the sequential chain's), agent scope: the hyper-dual
+// workgroups of this launch poll these rows
+__device__ __forceinline__ void adj_cost_publish(double *__restrict__ L, int k, int lane, double v)
+{
+    if (lane < 16) __hip_atomic_store(&L[16 * k + lane], v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// The hand-off between the waves of the costate workgroup: the vector in an LDS slot, then a flag the next wave polls.  A barrier
+// would keep a wave that has joined from filling (and publishing) its rows until the waves below it have joined too.  The four
+// waves of a workgroup are resident together and a producer never waits for its consumer, so the wait ends; it is bounded like
+// the hyper-dual workgroups' (adj_hd_pairs): on a time-out the rows below are wrong and the handle's COVO_DEVSTAT_ADJOINT bit is up.
+__device__ __forceinline__ void adj_flag_set(int *flag)
+{
+    // the slot is written by SOME lanes, the flag by all: without the wave-level ordering the lanes that wrote nothing may raise
+    // the flag in front of the others' stores (hipcc did place their branch first)
+    adj_wave_sync();
+    __hip_atomic_store(flag, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void adj_flag_wait(int *flag, const AdjArgs &A)
+{
+    const long long t0 = wall_clock64();
+    while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) == 0) {
+        if (wall_clock64() - t0 > 50000000LL) {
+            if (A.status != nullptr) __hip_atomic_fetch_or(A.status, COVO_DEVSTAT_ADJOINT, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+            break;
+        }
+        __builtin_amdgcn_s_sleep(1);
+    }
+}
+// the join of segment J: vv = (lam_(E+1); 1) from the slot, lam_M = T_M vv handed on and published
+template <int J>
+__device__ __forceinline__ void adj_cost_join(const double *__restrict__ hi_slot, double *__restrict__ ho, int *flag,
+                                              double *__restrict__ L, int lane, const double (&pa)[8][4], double (&vv)[4])
+{
+    constexpr int E = 8 * J + 7, M = J == 0 ? 1 : 8 * J;
+    const int hi = lane >> 4;
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const double x = hi_slot[4 * g + hi];  // (rows >= NX of the slot: padding, replaced by the 1 that takes c_k in)
+        vv[g] = 4 * g + hi < NX ? x : (4 * g + hi == NX ? 1.0 : 0.0);
+    }
+    const double lm = adj_cost_over_hi(adj_cost_quarter(pa[E - M], vv));
+    if (J > 0) {
+        if (lane < 16) ho[lane] = lm;
+        adj_flag_set(flag);
+    }
+    adj_cost_publish(L, M, lane, lm);
+}
+template <int J>
+__device__ __forceinline__ void adj_cost_fill(double *__restrict__ L, int lane, const double (&pa)[8][4], const double (&vv)[4])
+{
+    constexpr int E = 8 * J + 7, M = J == 0 ? 1 : 8 * J;
+    double q[E - M];  // pa[i] = T_(E - i), i < E - M
+#pragma unroll
+    for (int i = 0; i < E - M; ++i) q[i] = adj_cost_quarter(pa[i], vv);
+#pragma unroll
+    for (int i = 0; i < E - M; ++i) q[i] += __shfl_xor(q[i], 16, 64);
+#pragma unroll
+    for (int i = 0; i < E - M; ++i) q[i] += __shfl_xor(q[i], 32, 64);
+#pragma unroll
+    for (int i = 0; i < E - M; ++i) adj_cost_publish(L, E - i, lane, q[i]);
+}
+#endif
+
 __global__ __launch_bounds__(256) void adj_chain_kernel(const AdjArgs A)
 {
     __shared__ double sjf[(HH - 1) * NX * NZ + 1];  // + one zero: what the lanes outside the 13 x 13 block read
     __shared__ double sgl[HH * 16];
+    __shared__ double stb[4][16 * KC_TLD];  // a transposition buffer per wave (adj_cd_to_a)
+    __shared__ double sho[3][256];          // the tile (costate: the vector) handed from the wave of one segment to the next
+    __shared__ int sfl[4];                  // costate: "slot i is written"
     // one chain per WORKGROUP (the f64 MFMA pipe of a SIMD is not shared with another chain: nine chains in one
-    // workgroup put 76 steps on one SIMD); the four waves fill LDS together, wave 0 runs the chain
-    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, lo = lane & 15, hi = lane >> 4;
+    // workgroup put 76 steps on one SIMD); the four waves fill LDS together, then each runs one horizon segment of the chain
+    const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int w = blockIdx.x;  // 0..7: column tile of S, 8: costate, 9..40: the hyper-dual steps of KM (see adj_hd_pairs)
     double *__restrict__ ws = A.ws + (size_t)b * WS_COUNT;
     // -DKC_STAMPS (like KD_PROF: a measuring build, the product kernel stores nothing extra): 10 ns wall-clock ticks from the
-    // chain workgroup's entry to its own LDS stores done / past the barrier (wave 0's first MFMA may issue) / the chain's end,
-    // printed by the first and the last sensitivity tile and by the costate
+    // chain workgroup's entry to its own LDS stores done / past the barrier (the first MFMA may issue) / the wave's segment chain
+    // done / its join done / its last row stored (issued, then acknowledged), printed for every wave of the first and the last
+    // sensitivity tile and of the costate; every eighth hyper-dual workgroup and the last print their end
 #ifdef KC_STAMPS
     const long long kc0 = wall_clock64();
+    long long kc3 = 0, kc4 = 0;
+#define KC_STAMP(x) x = (long long)wall_clock64() - kc0
+#else
+#define KC_STAMP(x) do { } while (0)
 #endif
     if (w >= 9) {
         adj_hd_padding(A, w - 9, b, tid, 256);
         adj_hd_pairs(A, w - 9, b, tid);
+#ifdef KC_STAMPS
+        if (tid == 0 && b == 0 && ((w - 9) % 8 == 0 || w - 9 == HH - 1)) printf("KC hd %d: end %lld (10 ns ticks from entry)\n", w - 9, (long long)wall_clock64() - kc0);
+#endif
         return;
     }
     {
@@ -540,133 +915,107 @@ __global__ __launch_bounds__(256) void adj_chain_kernel(const AdjArgs A)
         sgl[tid] = vg0;
         sgl[256 + tid] = vg1;
         if (tid == 0) sjf[NJ] = 0.0;
+        if (tid < 4) sfl[tid] = 0;
     }
 #ifdef KC_STAMPS
     const long long kc1 = wall_clock64();
 #endif
     __syncthreads();
 #ifdef KC_STAMPS
+    // (one printf per workgroup, behind a barrier of the measuring build: a wave that printed while its neighbours still ran would
+    // disturb what they stamp)
     const long long kc2 = wall_clock64();
-#define KC_STAMP_END()                                                                                                       \
+    __shared__ long long kcs[4][4];
+#define KC_STAMP_END(ALL)                                                                                                    \
     do {                                                                                                                     \
+        const long long kc5 = (long long)wall_clock64() - kc0;                                                               \
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                     \
+        if (lane == 0) { kcs[wv][0] = kc3; kcs[wv][1] = kc4; kcs[wv][2] = kc5; kcs[wv][3] = (long long)wall_clock64() - kc0; } \
+        if (ALL) __syncthreads();                                                                                            \
         if (tid == 0 && b == 0 && (w == 0 || w == 7 || w == 8))                                                              \
-            printf("KC wg %d: filled %lld first-mfma %lld end %lld (10 ns ticks from entry)\n", w, kc1 - kc0, kc2 - kc0,      \
-                   (long long)wall_clock64() - kc0);                                                                         \
+            for (int q = 0; q < (ALL ? 4 : 1); ++q)                                                                          \
+                printf("KC wg %d wave %d: filled %lld first-mfma %lld segment %lld join %lld end %lld acked %lld (10 ns "    \
+                       "ticks from entry)\n", w, q, kc1 - kc0, kc2 - kc0, kcs[q][0], kcs[q][1], kcs[q][2], kcs[q][3]);       \
     } while (0)
 #else
-#define KC_STAMP_END() do { } while (0)
+#define KC_STAMP_END(ALL) do { } while (0)
 #endif
-    if (tid >= 64) return;
-    // The chains are fully unrolled (k is a compile-time constant: every LDS / global address is base + immediate) and the lanes
-    // outside the 13 x 13 block read a zero slot instead of being masked off: as a rolled loop with `cond ? sjf[..] : 0` operands
-    // hipcc spent ~420 of a step's 755 cycles on exec-mask sequences, index arithmetic and accumulator copies around the four
-    // dependent MFMAs (KC_PROF stamps; the MFMAs + their result -> operand hazard are ~330).
-    constexpr int ZI = (HH - 1) * NX * NZ;
+    // (barriers and flags order LDS only: the rows already stored to the workspace stay in flight across them)
+    double pa[8][4];
     if (w == 8) {
-        // ---- costate: lam_31 = grad r_31, lam_k = grad r_k + A_k^T lam_{k+1}; the vector is column 0 of the tile
-        const double *__restrict__ G = sgl;  // grad r_k, staged in LDS: a global load per step would BE the step time
         double *__restrict__ L = ws + WS_LAM;
         f64x4 lam;
+#if ADJ_FS
+        // the costate tile [Psi | c] would need 17 columns: the sequential chain on wave 0, as before
+        if (wv != 0) return;
+        adj_cost_top<1>(sjf, sgl, L, lane, lam);
+        KC_STAMP(kc3);
+#else
+        double vv[4];
+        switch (wv) {  // (uniform)
+        case 0:
+            adj_cost_chain<0>(sjf, sgl, stb[0], lane, pa);
+            KC_STAMP(kc3);
+            adj_flag_wait(&sfl[2], A);
+            adj_cost_join<0>(sho[2], sho[2], &sfl[2], L, lane, pa, vv);
+            KC_STAMP(kc4);
+            adj_cost_fill<0>(L, lane, pa, vv);
+            break;
+        case 1:
+            adj_cost_chain<1>(sjf, sgl, stb[1], lane, pa);
+            KC_STAMP(kc3);
+            adj_flag_wait(&sfl[1], A);
+            adj_cost_join<1>(sho[1], sho[2], &sfl[2], L, lane, pa, vv);
+            KC_STAMP(kc4);
+            adj_cost_fill<1>(L, lane, pa, vv);
+            break;
+        case 2:
+            adj_cost_chain<2>(sjf, sgl, stb[2], lane, pa);
+            KC_STAMP(kc3);
+            adj_flag_wait(&sfl[0], A);
+            adj_cost_join<2>(sho[0], sho[1], &sfl[1], L, lane, pa, vv);
+            KC_STAMP(kc4);
+            adj_cost_fill<2>(L, lane, pa, vv);
+            break;
+        default:
+            adj_cost_top<24>(sjf, sgl, L, lane, lam);
+            if ((lane & 15) == 0) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) lam[r] = (lo == 0 && hi + 4 * r < NX) ? G[16 * (HH - 1) + hi + 4 * r] : 0.0;
-        // (agent-scope write-through stores: the hyper-dual workgroups of this launch poll these rows, adj_hd_pairs)
-        if (lo == 0) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                __hip_atomic_store(&L[16 * (HH - 1) + hi + 4 * r], lam[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                __hip_atomic_store(&L[16 * HH + hi + 4 * r], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                for (int r = 0; r < 4; ++r) sho[0][(lane >> 4) + 4 * r] = lam[r];
             }
+            adj_flag_set(&sfl[0]);
+            KC_STAMP(kc3);
         }
-        int offA[4];  // A^T[lo][4g+hi] = df/dz[4g+hi][lo]
-        bool okA[4];
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            okA[g] = lo < NX && 4 * g + hi < NX;
-            offA[g] = (4 * g + hi) * NZ + lo;
-        }
-        bool okG[4];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) okG[r] = lo == 0 && hi + 4 * r < NX;
-        double an[4];
-        f64x4 gn;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (HH - 2) * NX * NZ + offA[g] : ZI];
-#pragma unroll
-        for (int r = 0; r < 4; ++r) gn[r] = okG[r] ? G[16 * (HH - 2) + hi + 4 * r] : 0.0;
-#pragma unroll
-        for (int k = HH - 2; k >= 1; --k) {
-            double ac[4];
-            f64x4 acc = gn;
-#pragma unroll
-            for (int g = 0; g < 4; ++g) ac[g] = an[g];
-            if (k > 1) {  // next step's operands in flight
-#pragma unroll
-                for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (k - 1) * NX * NZ + offA[g] : ZI];
-#pragma unroll
-                for (int r = 0; r < 4; ++r) gn[r] = okG[r] ? G[16 * (k - 1) + hi + 4 * r] : 0.0;
-            }
-#pragma unroll
-            for (int g = 0; g < 4; ++g) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[g], lam[g], acc, 0, 0, 0);
-            lam = acc;
-            if (lo == 0) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) __hip_atomic_store(&L[16 * k + hi + 4 * r], lam[r], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-        }
-        KC_STAMP_END();
+#endif
+        KC_STAMP_END(!ADJ_FS);
         return;
     }
     // ---- sensitivities: tile w = columns 16w .. 16w+15 = the actions of steps 4w .. 4w+3; S_k tile = 0 for k <= 4w
-    const int col = 16 * w + lo, tcol = col >> 2, dcol = col & 3, k0 = 4 * w;
     double *__restrict__ S = ws + WS_S;
-    for (int k = 0; k <= k0; ++k) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) S[((size_t)k * 16 + hi + 4 * r) * NA + col] = 0.0;
+    const int jw = w >> 1;
+    f64x4 sv, sm;
+    switch (wv) {  // (uniform)
+    case 0: adj_sens_chain<0>(sjf, stb[0], sho[0], S, w, lane, pa, sv); break;
+    case 1: adj_sens_chain<1>(sjf, stb[1], sho[1], S, w, lane, pa, sv); break;
+    case 2: adj_sens_chain<2>(sjf, stb[2], sho[2], S, w, lane, pa, sv); break;
+    default: adj_sens_chain<3>(sjf, stb[3], sho[2], S, w, lane, pa, sv);
     }
-    f64x4 sv = {0.0, 0.0, 0.0, 0.0};
-    int offA[4];  // A[lo][4g+hi]
-    bool okA[4];
-#pragma unroll
-    for (int g = 0; g < 4; ++g) {
-        okA[g] = lo < NX && 4 * g + hi < NX;
-        offA[g] = lo * NZ + 4 * g + hi;
+    KC_STAMP(kc3);
+    __syncthreads();
+    if (wv == 1 && jw < 1) { adj_sens_join<1>(sho[0], sho[1], lane, pa, sm, sv); KC_STAMP(kc4); }
+    __syncthreads();
+    if (wv == 2 && jw < 2) { adj_sens_join<2>(sho[1], sho[2], lane, pa, sm, sv); KC_STAMP(kc4); }
+    __syncthreads();
+    if (wv == 3 && jw < 3) { adj_sens_join<3>(sho[2], sho[2], lane, pa, sm, sv); KC_STAMP(kc4); }
+    if (wv > jw) {
+        if (wv == 1) adj_sens_fill<1>(S, w, lane, pa, sm, sv);
+        else if (wv == 2) adj_sens_fill<2>(S, w, lane, pa, sm, sv);
+        else adj_sens_fill<3>(S, w, lane, pa, sm, sv);
     }
-    double an[4];
-    f64x4 bn;
-#pragma unroll
-    for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? k0 * NX * NZ + offA[g] : ZI];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) bn[r] = (tcol == k0 && hi + 4 * r < NX) ? sjf[(k0 * NX + hi + 4 * r) * NZ + NX + dcol] : 0.0;  // B_k E_k
-    double *__restrict__ Sp = S + (size_t)hi * NA + col;
-#pragma unroll
-    for (int k = 0; k < HH - 1; ++k) {
-        if (k < k0) continue;  // (uniform)
-        double ac[4];
-        f64x4 acc = bn;
-#pragma unroll
-        for (int g = 0; g < 4; ++g) ac[g] = an[g];
-        if (k + 1 < HH - 1) {  // next step's operands in flight
-#pragma unroll
-            for (int g = 0; g < 4; ++g) an[g] = sjf[okA[g] ? (k + 1) * NX * NZ + offA[g] : ZI];
-            // B_k E_k is non-zero only while the tile's own four steps enter (uniform branch)
-            if (k + 1 <= k0 + 3) {
-#pragma unroll
-                for (int r = 0; r < 4; ++r)
-                    bn[r] = (tcol == k + 1 && hi + 4 * r < NX) ? sjf[((k + 1) * NX + hi + 4 * r) * NZ + NX + dcol] : 0.0;
-            } else {
-#pragma unroll
-                for (int r = 0; r < 4; ++r) bn[r] = 0.0;
-            }
-        }
-#pragma unroll
-        for (int g = 0; g < 4; ++g) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(ac[g], sv[g], acc, 0, 0, 0);
-        sv = acc;
-#pragma unroll
-        for (int r = 0; r < 4; ++r) Sp[((size_t)(k + 1) * 16 + 4 * r) * NA] = sv[r];
-    }
-    KC_STAMP_END();
+    KC_STAMP_END(true);
 }
 #undef KC_STAMP_END
+#undef KC_STAMP
 
 // ---- KD: R = -( sum_k S_k^T Mxx_k S_k  +  action blocks ), one lower 16x16 tile per workgroup, k split over 8 waves
 __device__ __forceinline__ void adj_tri_tile(int w, int &ti, int &tj)
@@ -734,6 +1083,12 @@ __global__ __launch_bounds__(512) void adj_gemm_kernel(const AdjArgs A)
         sMuu[lane] = ws[WS_MUU + (size_t)(4 * I) * 16 + lane];
     }
     if (tid < 256) sMu[wv][lane] = ws[WS_MXU + (size_t)(4 * I + wv) * 64 + lane];  // [step][m * 4 + d], m < 16 (rows 13..15 zero)
+    // A NaN of the costate (norm'(0) at a step that sits on its target) is a NaN in EVERY entry of the reference's Hessian: there
+    // every pair's rollout passes that step and multiplies its infinite slope by a zero.  Here the tiles skip the steps whose S_k is
+    // zero, so the NaN would stay in the tiles that reach the step.  lam_1 holds a NaN if any lam_k does (A_k^T lam_(k+1) spreads
+    // it downwards over every row): wave 5 turns its 16 rows into one 0-or-NaN that the epilogue lays over the tile.
+    __shared__ double sNan;
+    const double lz = (wv == 5 && lane < 16) ? ws[WS_LAM + 16 + lane] : 0.0;
 #ifdef KD_PROF
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     const long long kp1 = clock64();
@@ -747,6 +1102,14 @@ __global__ __launch_bounds__(512) void adj_gemm_kernel(const AdjArgs A)
         // Q = Mxx S_J in C layout: register g of lane (lo, hi) is row 4g + hi -- the B operand of k-group g as is
 #pragma unroll
         for (int g = 0; g < 4; ++g) acc = __builtin_amdgcn_mfma_f64_16x16x4f64(si[it][g], Q[g], acc, 0, 0, 0);
+    }
+    if (wv == 5) {
+        double pz = lz * 0.0;
+        pz += __shfl_xor(pz, 1, 64);
+        pz += __shfl_xor(pz, 2, 64);
+        pz += __shfl_xor(pz, 4, 64);
+        pz += __shfl_xor(pz, 8, 64);
+        if (lane == 0) sNan = pz;
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) red[wv][r][lane] = acc[r];
@@ -770,6 +1133,8 @@ __global__ __launch_bounds__(512) void adj_gemm_kernel(const AdjArgs A)
         } else {
             v += sMuu[(ti - 4 * I) * 16 + di * 4 + dj];
         }
+        const double pz = sNan;
+        if (pz != pz) v = pz;  // (no arithmetic on a finite v: its bits stay what they were)
         // C = -J.  Off-diagonal tiles mirror; in diagonal tiles the lower half writes both copies (exactly symmetric R)
         if (I != J || i >= j) {
             R[(size_t)i * NA + j] = -v;
