@@ -61,6 +61,16 @@ COVO_RICCATI_FLOATS = 8
 COVO_RICCATI_SIDE = 4
 COVO_RICCATI_RUNGS = 8
 COVO_RICCATI_REG0 = 1e-2
+COVO_HAS_RICCATI_FEEDBACK = 1  # riccati_feedback= on top of riccati= (covo_set_step_riccati_feedback, covo_riccati_refine_feedback, covo_feedback_rollout)
+# a feedback row: {cheapest of candidates 0 .. 16, cheapest valid closed-loop candidate (+inf: none), bits(int32 index of the former),
+# bits(int32 index of the latter, 0: none), its max |K dx|_inf, bits(int32 its clipped count), bits(int32 mask of invalid ones), 0}; the
+# candidates 17 .. 32 are the closed-loop sequences under the sweep's gains at the ladder's step sizes 2^(3 - j), j = 1 .. 16.  The
+# generator's aux row: {max |K dx|_inf, bits(int32 clipped count), bits(int32 first k with a v that is not finite, -1: none), 0}
+COVO_FEEDBACK_FLOATS = 8
+COVO_FEEDBACK_CANDIDATES = 33
+FEEDBACK_AUX_FLOATS = 4
+FEEDBACK_MAX_ALPHAS = 64
+FEEDBACK_LADDER = tuple(2.0 ** (3 - j) for j in range(1, 17))
 # the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
 COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
 COVO_EPLOG_KINDS = 6
@@ -122,6 +132,7 @@ class BatchModeArgsC(C.Structure):
 REWARD_KINDS = {"penyaw": 0, "realworld": 1}                 # COVO_REWARD_*
 DISTURB_KINDS = {"none": 0, "gaussian": 1, "periodic": 2, "sin": 3, "drag": 4, "mixed": 5}  # COVO_DISTURB_*
 TRAJ_KINDS = {None: 0, "hovering": 1, "tracking": 2, "tracking_slow": 3, "tracking_zigzag": 4}  # COVO_TRAJ_* by Quad3D task
+STATE_DISTURB_KINDS = (4, 5)                                  # drag / mixed: the force is a state (16-state plants)
 TABLE_DISTURB_KINDS = (2, 3, 4, 5)                            # models that need covo_disturb_table's per-step table
 DISTURB_KEYS_SHARED, DISTURB_KEYS_HESSIAN, DISTURB_KEYS_NOMINAL = 0, 1, 2
 COVO_MAX_ENVS = 64
@@ -231,6 +242,13 @@ _SIGS = {
     "covo_riccati_refine": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, C.c_double,
                                       C.c_int32, _P, _P, _P]),
     "covo_set_step_riccati": (C.c_int, [_P, _P, C.c_int32]),
+    # Riccati feedback (covo_hip.h: COVO_HAS_RICCATI_FEEDBACK)
+    "covo_feedback_rollout": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, _P, _P,
+                                        C.POINTER(C.c_double), C.c_int32, C.c_int32, _P, _P, _P]),
+    "covo_riccati_refine_feedback": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P,
+                                               C.c_double, C.c_int32, _P, _P, _P, _P]),
+    "covo_set_step_riccati_feedback": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_debug_feedback_gain": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),

@@ -22,7 +22,8 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
-from ._options import check_refine, check_riccati, check_kernel_path, check_step_options, sharded_refusal, take
+from ._options import (check_refine, check_riccati, check_riccati_feedback, check_kernel_path, check_step_options, sharded_refusal,
+                       take)
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
 # that attribute's value is the log's extra allocation argument: the fan's K, the iteration log's row width; covo_set_episode_rows' kind
@@ -71,7 +72,7 @@ class SamplingCore:
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False,
-                 riccati: bool = False):
+                 riccati: bool = False, riccati_feedback: bool = False):
         opts = take(locals())
         import torch
         sharded = False
@@ -81,6 +82,7 @@ class SamplingCore:
         opt = check_step_options(N, "online", sharded=sharded, **opts)
         refine = check_refine(refine, "online", sigma_period=opt.sigma_period, sharded=sharded)
         riccati = check_riccati(riccati, "a sampling core", refine=refine, sharded=sharded)
+        riccati_feedback = check_riccati_feedback(riccati_feedback, riccati=riccati, what="a sampling core")
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -224,6 +226,11 @@ class SamplingCore:
         # self.riccati_rows [rows, 8]: a refine row that ends {.., mu, bits(flags | rung << 8)} (riccati=: _options.check_riccati)
         self.riccati_on = riccati  # (riccati() is the stand-alone sweep)
         self.riccati_rows = self._attach_rows(_lib.COVO_RICCATI_FLOATS, "covo_set_step_riccati") if riccati else None
+        # self.riccati_feedback_rows [rows, 8]: {cost_open, cost_closed, bits(index open), bits(index closed), max |K dx|, bits(clipped),
+        # bits(invalid mask), 0} (riccati_feedback=: _options.check_riccati_feedback; attached behind riccati's rows, which it needs)
+        self.riccati_feedback_on = riccati_feedback
+        self.riccati_feedback_rows = (self._attach_rows(_lib.COVO_FEEDBACK_FLOATS, "covo_set_step_riccati_feedback")
+                                      if riccati_feedback else None)
         self._list_infos()
         self.exchange = "collective"
         if self.world > 1:
@@ -373,7 +380,8 @@ class SamplingCore:
             (self.iter_cost_min is not None, self.iter_info), (self.elite_rows is not None, self.elite_info),
             (self.sigma_period > 1, self.sigma_info), (self.post_cov is not None, self.post_cov_info),
             (self.sigma_adapt_rows is not None, self.sigma_adapt_info), (self.refine_rows is not None, self.refine_info),
-            (self.riccati_rows is not None, self.riccati_info)) if on]
+            (self.riccati_rows is not None, self.riccati_info),
+            (self.riccati_feedback_rows is not None, self.riccati_feedback_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -537,6 +545,51 @@ class SamplingCore:
                 "riccati_alpha": row[3], "riccati_grad_norm": row[4], "riccati_slope": row[5], "riccati_reg": row[6],
                 "riccati_rung": row[7:8].view(self.torch.int32)[0] >> 8}
 
+    def riccati_feedback_info(self) -> dict:
+        """{"riccati_closed" (0-d bool: the committed candidate is a closed-loop one, choice > 16), "riccati_cost_open" (the cheapest of
+        candidates 0 .. 16), "riccati_cost_closed" (the cheapest valid closed-loop candidate, +inf: none), "riccati_gain_max" (that
+        candidate's max |K dx|_inf)} of the last step from self.riccati_rows / self.riccati_feedback_rows (no sync, no copy; the bool is
+        one device op on a view); {} when the core was built without riccati_feedback."""
+        if self.riccati_feedback_rows is None:
+            return {}
+        row = self.riccati_feedback_rows[0]
+        return {"riccati_closed": self.riccati_rows[0, 2:3].view(self.torch.int32)[0] > _lib.COVO_REFINE_CANDIDATES - 1,
+                "riccati_cost_open": row[0], "riccati_cost_closed": row[1], "riccati_gain_max": row[4]}
+
+    def feedback_rollout(self, dstate, params_c, a, K, kff, x, alphas=None, f_shared=None, f_steps=None, packed=None):
+        """covo_feedback_rollout: the closed-loop action sequences under the sweep's gains (csrc/feedback_rollout.hip).  a (float32
+        [128] or [n_inst, 128]): the plan the sweep ran at; K [n_inst, 32, 4, 16], kff [n_inst, 32, 4], x [n_inst, 32, 16] (float64):
+        riccati()'s outputs of those names; alphas: up to 64 step sizes (default: the ladder's 16, 2^(3 - j)); f_shared / f_steps: the
+        rollout's shared vector / [n_inst, H, 4] table as for rollout(); packed: the [n_inst, 32] start states (default: dstate's, for
+        every instance -- they need not be x[:, 0]) -> (a_out float32 [n_inst, n_alpha, 128], aux float32 [n_inst, n_alpha, 4] =
+        {max |K dx|_inf, bits(clipped count), bits(first k with a v that is not finite, -1: none), 0})."""
+        torch = self.torch
+        a = a.reshape(-1, COVO_NA).contiguous()
+        n_inst = int(a.shape[0])
+        assert a.is_cuda and a.dtype == torch.float32
+        al = [float(v) for v in (_lib.FEEDBACK_LADDER if alphas is None else alphas)]
+        if not 1 <= len(al) <= _lib.FEEDBACK_MAX_ALPHAS:
+            raise ValueError(f"feedback_rollout: {len(al)} step sizes outside [1, {_lib.FEEDBACK_MAX_ALPHAS}]")
+        if params_c.disturb_kind in _lib.STATE_DISTURB_KINDS:
+            raise NotImplementedError(f"feedback_rollout: disturb_kind={params_c.disturb_kind} (drag / mixed) is a 16-state plant -- its "
+                                      "force is a state of the sweep and a per-sample quantity of the rollout")
+        gains = []
+        for t, shape in ((K, (COVO_H, 4, 16)), (kff, (COVO_H, 4)), (x, (COVO_H, 16))):
+            t = t.to(device=self.device, dtype=torch.float64).reshape((n_inst,) + shape).contiguous()
+            gains.append(t)
+        if packed is None:
+            packed = dstate.packed.reshape(1, -1).expand(n_inst, -1).contiguous()
+        assert packed.numel() == n_inst * _lib.COVO_STATE_FLOATS and packed.is_contiguous()
+        a_out = torch.empty((n_inst, len(al), COVO_NA), dtype=torch.float32, device=self.device)
+        aux = torch.empty((n_inst, len(al), _lib.FEEDBACK_AUX_FLOATS), dtype=torch.float32, device=self.device)
+        fs = (C.c_float * 3)(*[float(v) for v in f_shared]) if f_shared is not None else None
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_feedback_rollout(self.h, ptr(packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                                 C.byref(params_c), fs, ptr(f_steps), ptr(a), ptr(gains[0]), ptr(gains[1]), ptr(gains[2]),
+                                                 (C.c_double * len(al))(*al), len(al), n_inst, ptr(a_out), ptr(aux), self.stream()),
+                  "covo_feedback_rollout")
+        return a_out, aux
+
     def riccati(self, dstate, params_c, a, reg0=_lib.COVO_RICCATI_REG0, f_steps=None, packed=None):
         """covo_riccati: the Riccati sweep (csrc/riccati.hip) over the stage blocks of the Hessian's objective at `a` (float32 device
         tensor [128] or [batch, 128]) -> dict of float64 device tensors: "d" [batch, 128] = -(R + mu I)^-1 g on the lowest rung
@@ -561,16 +614,33 @@ class SamplingCore:
         return out
 
     def riccati_refine(self, dstate, params_c, a_mean, reg0=_lib.COVO_RICCATI_REG0, f_shared=None, f_steps=None, f_steps_hessian=None,
-                       want_costs=True):
+                       want_costs=True, feedback=False):
         """covo_riccati_refine (the stand-alone Riccati line search) on `a_mean` (float32 device tensor, 128 elements, refined IN
         PLACE) with the inputs of rollout(): the sweep's direction d at a_mean (f_steps_hessian: the Hessian's table), the candidates
         clip(a_mean) and clip(a_mean + 2^(3 - j) d), j = 1 .. 16, rolled out, the first cheapest committed -> (float32 [8] row
-        {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, mu, bits(flags | rung << 8)}, float32 [17] candidate costs or None)."""
+        {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, mu, bits(flags | rung << 8)}, float32 [17] candidate costs or None).
+        feedback=True (covo_riccati_refine_feedback): the 16 closed-loop sequences under the sweep's gains compete as candidates
+        17 .. 32 -> (row, float32 [33] costs or None, float32 [8] feedback row {cost_open, cost_closed, bits(index open), bits(index
+        closed), max |K dx|_inf, bits(clipped count), bits(invalid mask), 0})."""
         torch = self.torch
         assert a_mean.is_cuda and a_mean.dtype == torch.float32 and a_mean.is_contiguous() and a_mean.numel() == COVO_NA
+        if not isinstance(feedback, bool):
+            raise ValueError(f"feedback={feedback!r} (True | False)")
         row = torch.empty((_lib.COVO_RICCATI_FLOATS,), dtype=torch.float32, device=self.device)
-        costs = torch.empty((_lib.COVO_REFINE_CANDIDATES,), dtype=torch.float32, device=self.device) if want_costs else None
+        ncand = _lib.COVO_FEEDBACK_CANDIDATES if feedback else _lib.COVO_REFINE_CANDIDATES
+        costs = torch.empty((ncand,), dtype=torch.float32, device=self.device) if want_costs else None
         fs = (C.c_float * 3)(*[float(x) for x in f_shared]) if f_shared is not None else None
+        if feedback:
+            if params_c.disturb_kind in _lib.STATE_DISTURB_KINDS:
+                raise NotImplementedError(f"riccati_refine(feedback=True): disturb_kind={params_c.disturb_kind} (drag / mixed) is a "
+                                          "16-state plant -- its force is a state of the sweep and a per-sample quantity of the rollout")
+            fb_row = torch.empty((_lib.COVO_FEEDBACK_FLOATS,), dtype=torch.float32, device=self.device)
+            with torch.cuda.device(self.device):
+                check(self.lib.covo_riccati_refine_feedback(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj),
+                                                            dstate.T, C.byref(params_c), fs, ptr(f_steps), ptr(f_steps_hessian),
+                                                            ptr(a_mean), float(reg0), 1, ptr(row), ptr(costs), ptr(fb_row),
+                                                            self.stream()), "covo_riccati_refine_feedback")
+            return row, costs, fb_row
         with torch.cuda.device(self.device):
             check(self.lib.covo_riccati_refine(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
                                                C.byref(params_c), fs, ptr(f_steps), ptr(f_steps_hessian), ptr(a_mean), float(reg0), 1,

@@ -267,3 +267,32 @@ def check_riccati(riccati, what, *, refine=False, sharded=False) -> bool:
         raise NotImplementedError("riccati=True on sample-sharded ranks: a rank's costs cover its shard's step only until the exchange "
                                   "(covo_set_step_riccati refuses sample-sharded steps)")
     return True
+
+
+def check_riccati_feedback(feedback, *, riccati, disturb_type=None, what="a sampling controller") -> bool:
+    """riccati_feedback= on top of riccati= -> bool.  A switch like riccati=, taken by the same callables (SamplingCore, MPPIController,
+    CoVOController, BatchedCoVOController, get_controller, eval_env_batched) and checked here; the C side's counterpart is the feedback
+    block of check_step_attachments (csrc/capi.hip).
+
+    riccati_feedback=True: the line search behind every step judges 33 candidates instead of 17.  Candidates 0 .. 16 are riccati='s
+    own, bit for bit; 16 + j, j = 1 .. 16, is the closed-loop sequence at the same step size 2^(3 - j): the sweep's feed-forward terms
+    and gains around the nonlinear plant, u_k = clip(b_k + alpha k_k + K_k (x_k - xb_k)) -- the forward pass of DDP / iLQR
+    (covo_set_step_riccati_feedback, csrc/feedback_rollout.hip).  The first cheapest wins, so a closed-loop candidate is committed only
+    when strictly cheaper than every open-loop one: info["riccati_closed"] / ["riccati_cost_open"] / ["riccati_cost_closed"] /
+    ["riccati_gain_max"].  False: nothing attached, no launch added.
+
+    The objections, in a fixed order: anything but a bool (ValueError); True without riccati=True -- the candidates run under that
+    sweep's gains (ValueError); disturb_type drag / mixed -- the 16-state plants, whose force is a state of the sweep and a per-sample
+    quantity of the rollout (NotImplementedError; disturb_type=None: not known here, the step refuses it)."""
+    if not isinstance(feedback, bool):
+        raise ValueError(f"riccati_feedback={feedback!r} (True | False)")
+    if not feedback:
+        return False
+    if riccati is not True:
+        raise ValueError(f"riccati_feedback=True with {what} needs riccati=True: the closed-loop candidates run under the gains of "
+                         "that sweep; give riccati=True or riccati_feedback=False")
+    if disturb_type in ("drag", "mixed"):
+        raise NotImplementedError(f"riccati_feedback=True with disturb_type={disturb_type!r}: drag / mixed are 16-state plants -- their "
+                                  "force is a state of the sweep and a per-sample quantity of the rollout, and the closed-loop "
+                                  "generator carries the 13-state plants only (covo_set_step_riccati_feedback refuses them at the step)")
+    return True

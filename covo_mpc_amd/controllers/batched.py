@@ -22,12 +22,13 @@ from .. import _lib
 from .._lib import COVO_H, COVO_NA, check
 from ..dynamics.dataclass import as_device_state
 from ._core import SamplingCore
-from ._options import check_refine, check_riccati, check_step_options, take
+from ._options import check_refine, check_riccati, check_riccati_feedback, check_step_options, take
 
 # (controller attribute, core attribute) of the attachment buffers the batched controllers hand out
 CORE_BUFFERS = (("diag", "diag"), ("plan", "plan"), ("fan", "fan"), ("arbiter", "arbiter"), ("lam_eff", "lam_eff"), ("elite", "elite_rows"),
                 ("iter_cost_min", "iter_cost_min"), ("post_cov", "post_cov"), ("post_aux", "post_aux"),
-                ("sigma_adapt_rows", "sigma_adapt_rows"), ("refine", "refine_rows"), ("riccati", "riccati_rows"))
+                ("sigma_adapt_rows", "sigma_adapt_rows"), ("refine", "refine_rows"), ("riccati", "riccati_rows"),
+                ("riccati_feedback", "riccati_feedback_rows"))
 
 
 class BatchedCoVOController:
@@ -39,7 +40,7 @@ class BatchedCoVOController:
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, staged: bool = False,
-                 refine: bool = False, riccati: bool = False):
+                 refine: bool = False, riccati: bool = False, riccati_feedback: bool = False):
         opts = take(locals())
         moded = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step
         if staged and not moded:
@@ -55,6 +56,7 @@ class BatchedCoVOController:
         check_step_options(N, what, fused_batched=fused, **opts)
         check_refine(refine, what, sigma_period=sigma_period)
         check_riccati(riccati, what, refine=refine)
+        check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -71,7 +73,8 @@ class BatchedCoVOController:
         # one call advances all instances: the ~56 launches are worth a graph (same GPU time as eager, 40 us instead of
         # 150-270 us of host time per call)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
-                                 diag_rows=int(n_envs), refine=refine, riccati=riccati, **opts)
+                                 diag_rows=int(n_envs), refine=refine, riccati=riccati, riccati_feedback=riccati_feedback,
+                                 **opts)
         if moded:
             check(self.core.lib.covo_set_step_batched_staged(self.core.h, int(self.staged)), "covo_set_step_batched_staged")
         # after a call, row e of each of the core's attachment buffers holds instance e's result of that step; None for what is off

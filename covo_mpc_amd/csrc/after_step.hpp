@@ -20,7 +20,7 @@
 #include "rollout_common.hpp"
 #include "step_begin.hpp"
 
-// the first member of PlanArgs / FanArgs / ArbArgs / RefineArgs
+// the first member of PlanArgs / FanArgs / ArbArgs / RefineArgs / FeedbackArgs
 struct AfterHead {
     RolloutArgs R;            // the step's sample rollout: noisy state, trajectories, model, discount, disturbance table; with the
                               // samples (fan, arbiter) a, N and R.clip: how phase 0 clips the stripes it gathers
@@ -181,7 +181,7 @@ struct ArgBlockCache {
 // covo_ctx::after.  One cache per launch: with a shared one every launch of a batched step would overwrite the mirror the next
 // compares against, and every step would synchronise and upload
 struct AfterState {
-    ArgBlockCache arbiter, plan, fan, refine;
+    ArgBlockCache arbiter, plan, fan, refine, feedback;
     float *nominal = nullptr;  // [COVO_MAX_ENVS][128] the update arbiter's nominals of the env-batched fused step
 };
 static inline AfterState *after_state(covo_ctx *h)

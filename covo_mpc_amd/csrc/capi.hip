@@ -149,6 +149,8 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->ws_riccati));
     DESTROY(hipFree(h->riccati_d));
     DESTROY(hipFree(h->riccati_tab));
+    DESTROY(hipFree(h->feedback_gains));
+    DESTROY(hipFree(h->feedback_a));
     DESTROY(hipEventDestroy(h->ev_fork));
     DESTROY(hipEventDestroy(h->ev_join));
     DESTROY(hipStreamDestroy(h->side_stream));
@@ -1045,7 +1047,7 @@ int covo_set_episode_rows(covo_handle_t h, int32_t kind, float *log, int32_t str
 // (partial_out != NULL) cannot have at all, in the order above; then, in the same order, each attachment's own ranges and the rows
 // of its buffer.  A new attachment adds its lines here (and its log to covo_eplog_kinds, covo_common.hpp), nowhere else.
 static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, int mode, const float *a_cov,
-                                  const char *what)
+                                  const covo_env_params *params, const char *what)
 {
     if (sharded) {
         REQUIRE(covo_diag_target(h) == nullptr,
@@ -1161,6 +1163,18 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                 "polish the committed mean; detach one of them", what);
         REQUIRE(n_inst <= h->riccati_n, "%s: %d instances, the riccati buffer (covo_set_step_riccati) has n_inst=%d", what, n_inst,
                 h->riccati_n);
+    }
+    if (covo_feedback_on(h)) {  // the closed-loop candidates of the Riccati refinement's line search
+        REQUIRE(covo_riccati_on(h),
+                "%s: Riccati feedback (covo_set_step_riccati_feedback) without the Riccati refinement (covo_set_step_riccati): the "
+                "closed-loop candidates run under that sweep's gains; attach it or detach the feedback rows", what);
+        REQUIRE(n_inst <= h->feedback_n, "%s: %d instances, the feedback buffer (covo_set_step_riccati_feedback) has n_inst=%d", what,
+                n_inst, h->feedback_n);
+        for (int e = 0; e < n_inst; ++e)
+            REQUIRE(params[e].disturb_kind != COVO_DISTURB_DRAG && params[e].disturb_kind != COVO_DISTURB_MIXED,
+                    "%s: Riccati feedback (covo_set_step_riccati_feedback) with disturb_kind=%d (drag / mixed, instance %d): a 16-state "
+                    "plant, whose force is a state of the sweep and a per-sample quantity of the rollout; detach the feedback rows", what,
+                    params[e].disturb_kind, e);
     }
     return 0;
 }
@@ -1324,28 +1338,54 @@ int covo_riccati(covo_handle_t h, const float *state, const float *pos_traj, con
     return launch_riccati(d, reg0, o, h->ws_riccati, s);
 }
 
-int covo_riccati_refine(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
-                        const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
-                        const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
-                        void *stream)
+// the sweep's gains and the generator's sequences of a step's instances, here and not in a step (covo_common.hpp: the layouts)
+static int feedback_reserve(covo_ctx *h)
 {
-    REQUIRE(h, "covo_riccati_refine: null handle");
-    CHECK_DEVICE(h, "covo_riccati_refine");
-    REQUIRE(state && pos_traj && vel_traj && params && a_mean && rows_out && T > 0, "covo_riccati_refine: bad argument");
-    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_riccati_refine: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
-    REQUIRE(((uintptr_t)a_mean & 15) == 0, "covo_riccati_refine: a_mean must be 16-byte aligned");
-    CHECK_MODEL(params, "covo_riccati_refine");
+    if (h->feedback_gains == nullptr)
+        COVO_CHECK_HIP(hipMalloc(&h->feedback_gains, (size_t)COVO_MAX_ENVS * COVO_FEEDBACK_GAIN_DOUBLES * sizeof(double)));
+    if (h->feedback_a == nullptr)
+        COVO_CHECK_HIP(hipMalloc(&h->feedback_a, (size_t)COVO_MAX_ENVS * COVO_FEEDBACK_LADDER * (COVO_NA + COVO_FEEDBACK_AUX_FLOATS) * sizeof(float)));
+    return 0;
+}
+static bool feedback_refuses(const covo_env_params *p) { return p->disturb_kind == COVO_DISTURB_DRAG || p->disturb_kind == COVO_DISTURB_MIXED; }
+#define FEEDBACK_PLANT_MSG                                                                                                            \
+    "%s: disturb_kind=%d (drag / mixed) is a 16-state plant -- its force is a state of the sweep and a per-sample quantity of the "    \
+    "rollout; the closed-loop generator carries the 13-state plants only"
+
+// covo_riccati_refine (fb_rows_out null: 17 candidates) and covo_riccati_refine_feedback (33)
+static int riccati_refine_body(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                               const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                               const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
+                               float *fb_rows_out, bool feedback, const char *who, void *stream)
+{
+    REQUIRE(h, "%s: null handle", who);
+    CHECK_DEVICE(h, who);
+    REQUIRE(state && pos_traj && vel_traj && params && a_mean && rows_out && (fb_rows_out || !feedback) && T > 0, "%s: bad argument", who);
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "%s: n_inst=%d outside (0, %d]", who, n_inst, COVO_MAX_ENVS);
+    REQUIRE(((uintptr_t)a_mean & 15) == 0, "%s: a_mean must be 16-byte aligned", who);
+    CHECK_MODEL(params, who);
     REQUIRE(!covo_needs_tables(*params) || (f_disturb_steps && f_tab_hessian),
-            "covo_riccati_refine: disturb_kind=%d needs f_disturb_steps and f_tab_hessian (covo_disturb_table)", params->disturb_kind);
+            "%s: disturb_kind=%d needs f_disturb_steps and f_tab_hessian (covo_disturb_table)", who, params->disturb_kind);
+    REQUIRE(!feedback || !feedback_refuses(params), FEEDBACK_PLANT_MSG, who, params->disturb_kind);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = riccati_reserve(h, n_inst, s)) return rc;
+    if (feedback)
+        if (int rc = feedback_reserve(h)) return rc;
     HessianDesc hd = gradient_desc(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst);
     hd.status_dev = h->status_dev;
     RiccatiOut o;
     o.d = h->riccati_d;
     o.g = h->refine_g;
     o.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA;
+    if (feedback) covo_feedback_sweep_out(h, o);
     if (int rc = launch_riccati(hd, reg0, o, h->ws_riccati, s)) return rc;
+    if (feedback && h->feedback_poke_armed) {  // covo_debug_feedback_gain: once
+        h->feedback_poke_armed = 0;
+        REQUIRE(h->feedback_poke_at < n_inst * COVO_H * 64, "%s: covo_debug_feedback_gain names an instance beyond n_inst=%d", who, n_inst);
+        COVO_CHECK_HIP(hipMemcpyAsync(h->feedback_gains + h->feedback_poke_at, &h->feedback_poke, sizeof(double), hipMemcpyHostToDevice, s));
+        COVO_CHECK_HIP(hipStreamSynchronize(s));  // (the source is a member of the handle)
+    }
+    const int ncost = feedback ? COVO_FEEDBACK_CANDIDATES : COVO_REFINE_CANDIDATES;
     for (int e = 0; e < n_inst; ++e) {
         PlanInstDesc d = standalone_inst(state + (size_t)e * COVO_STATE_FLOATS, pos_traj, vel_traj, T, params, f_disturb_shared,
                                          f_disturb_steps ? f_disturb_steps + (size_t)e * COVO_H * 4 : nullptr, nullptr, 1);
@@ -1355,9 +1395,100 @@ int covo_riccati_refine(covo_handle_t h, const float *state, const float *pos_tr
         r.dir = o.d + (size_t)e * COVO_NA;
         r.dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
         r.row_out = rows_out + (size_t)e * COVO_RICCATI_FLOATS;
-        r.costs_out = costs_out ? costs_out + (size_t)e * COVO_REFINE_CANDIDATES : nullptr;
+        r.costs_out = costs_out ? costs_out + (size_t)e * ncost : nullptr;
+        if (feedback) {
+            const FeedbackDesc f = covo_feedback_desc(h, e, d.a_mean);
+            double ladder[COVO_FEEDBACK_LADDER];
+            for (int j = 1; j <= COVO_FEEDBACK_LADDER; ++j) ladder[j - 1] = std::ldexp(1.0, 3 - j);
+            if (int rc = launch_feedback_rollout_one(h, d, f, ladder, s)) return rc;
+            r.extra = f.a_out;
+            r.extra_aux = f.aux_out;
+            r.fb_row_out = fb_rows_out + (size_t)e * COVO_FEEDBACK_FLOATS;
+        }
         if (int rc = launch_newton_refine_one(h, d, rollout_clip(h), r, s)) return rc;
     }
+    return 0;
+}
+
+int covo_riccati_refine(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                        const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                        const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
+                        void *stream)
+{
+    return riccati_refine_body(h, state, pos_traj, vel_traj, T, params, f_disturb_shared, f_disturb_steps, f_tab_hessian, a_mean, reg0,
+                               n_inst, rows_out, costs_out, nullptr, false, "covo_riccati_refine", stream);
+}
+
+int covo_riccati_refine_feedback(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                                 const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                                 const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out,
+                                 float *costs_out, float *fb_rows_out, void *stream)
+{
+    return riccati_refine_body(h, state, pos_traj, vel_traj, T, params, f_disturb_shared, f_disturb_steps, f_tab_hessian, a_mean, reg0,
+                               n_inst, rows_out, costs_out, fb_rows_out, true, "covo_riccati_refine_feedback", stream);
+}
+
+int covo_feedback_rollout(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                          const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
+                          const double *K, const double *kff, const double *x, const double *alphas, int32_t n_alpha, int32_t n_inst,
+                          float *a_out, float *aux_out, void *stream)
+{
+    REQUIRE(h, "covo_feedback_rollout: null handle");
+    CHECK_DEVICE(h, "covo_feedback_rollout");
+    REQUIRE(state && pos_traj && vel_traj && params && a && K && kff && x && alphas && a_out && aux_out && T > 0,
+            "covo_feedback_rollout: bad argument");
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_feedback_rollout: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(n_alpha >= 1 && n_alpha <= COVO_FEEDBACK_MAX_ALPHAS, "covo_feedback_rollout: n_alpha=%d outside [1, %d]", n_alpha,
+            COVO_FEEDBACK_MAX_ALPHAS);
+    REQUIRE((((uintptr_t)a | (uintptr_t)K | (uintptr_t)kff | (uintptr_t)x | (uintptr_t)a_out) & 15) == 0,
+            "covo_feedback_rollout: a, K, kff, x and a_out must be 16-byte aligned");
+    CHECK_MODEL(params, "covo_feedback_rollout");
+    REQUIRE(!feedback_refuses(params), FEEDBACK_PLANT_MSG, "covo_feedback_rollout", params->disturb_kind);
+    REQUIRE(!covo_needs_tables(*params) || f_disturb_steps, "covo_feedback_rollout: disturb_kind=%d needs f_disturb_steps (covo_disturb_table)",
+            params->disturb_kind);
+    for (int e = 0; e < n_inst; ++e) {
+        const PlanInstDesc d = standalone_inst(state + (size_t)e * COVO_STATE_FLOATS, pos_traj, vel_traj, T, params, f_disturb_shared,
+                                               f_disturb_steps ? f_disturb_steps + (size_t)e * COVO_H * 4 : nullptr, nullptr, 1);
+        FeedbackDesc f;
+        f.b = a + (size_t)e * COVO_NA;
+        f.K = K + (size_t)e * COVO_H * 64;
+        f.kff = kff + (size_t)e * COVO_H * 4;
+        f.x = x + (size_t)e * COVO_H * 16;
+        f.a_out = a_out + (size_t)e * n_alpha * COVO_NA;
+        f.aux_out = aux_out + (size_t)e * n_alpha * COVO_FEEDBACK_AUX_FLOATS;
+        f.n_alpha = n_alpha;
+        if (int rc = launch_feedback_rollout_one(h, d, f, alphas, (hipStream_t)stream)) return rc;
+    }
+    return 0;
+}
+
+int covo_debug_feedback_gain(covo_handle_t h, int32_t inst, int32_t index, double value)
+{
+    REQUIRE(h, "covo_debug_feedback_gain: null handle");
+    REQUIRE(inst >= 0 && inst < COVO_MAX_ENVS && index >= 0 && index < COVO_H * 64,
+            "covo_debug_feedback_gain: inst=%d outside [0, %d) or index=%d outside [0, %d)", inst, COVO_MAX_ENVS, index, COVO_H * 64);
+    h->feedback_poke_armed = 1;
+    h->feedback_poke_at = inst * COVO_H * 64 + index;
+    h->feedback_poke = value;
+    return 0;
+}
+
+int covo_set_step_riccati_feedback(covo_handle_t h, float *fb_rows, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_riccati_feedback: null handle");
+    if (fb_rows == nullptr) {
+        h->feedback_out = nullptr;
+        h->feedback_n = 0;
+        return 0;
+    }
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_riccati_feedback: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(covo_riccati_on(h) && n_inst <= h->riccati_n,
+            "covo_set_step_riccati_feedback: n_inst=%d needs the Riccati refinement attached on the handle with at least as many "
+            "instances (covo_set_step_riccati: %d)", n_inst, h->riccati_n);
+    // the step's scratch, here and not in a step
+    if (int rc = feedback_reserve(h)) return rc;
+    h->feedback_out = fb_rows;
+    h->feedback_n = n_inst;
     return 0;
 }
 
@@ -1445,7 +1576,7 @@ static int check_single_step(const covo_ctx *h, const covo_env_params *params, c
             what);
     REQUIRE(!covo_needs_tables(*params) || args->derive_keys == 1, "%s: disturb_kind=%d needs derive_keys = 1 (the per-step "
             "disturbance tables are derived from the raw controller key on the device)", what, params->disturb_kind);
-    return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, what);
+    return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, params, what);
 }
 
 int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, float *state_true,
@@ -1579,7 +1710,7 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
     REQUIRE(mode == COVO_MODE_COVO_ONLINE || !covo_riccati_on(h),
             "%s: the Riccati refinement (covo_set_step_riccati) is not available for the env-batched MPPI / covo-offline step, fused or "
             "staged: those batches carry no per-instance Hessian constants; detach it", what);
-    if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, what))) return rc;  // (batched steps derive their keys)
+    if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, params, what))) return rc;  // (batched steps derive their keys)
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
     REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),

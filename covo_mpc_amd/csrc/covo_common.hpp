@@ -112,6 +112,14 @@ struct covo_ctx {
     size_t ws_riccati_bytes;
     double *riccati_d;        // [COVO_MAX_ENVS][128 + COVO_RICCATI_SIDE]: the directions, then the side rows, of a step's instances
     float *riccati_tab;       // [H][4] the Hessian's disturbance table of a single step (MPPI, covo-offline and reuse steps build none)
+    // the closed-loop candidates of the Riccati refinement (covo_set_step_riccati_feedback; feedback_rollout.hip); feedback_out null: off
+    float *feedback_out;      // caller's [feedback_n][COVO_FEEDBACK_FLOATS]: instance e's feedback row of every step
+    int feedback_n;
+    double *feedback_gains;   // [COVO_MAX_ENVS][COVO_FEEDBACK_GAIN_DOUBLES]: the sweep's K, kff and x of a step's instances
+    float *feedback_a;        // [COVO_MAX_ENVS][16][128 + 4]: the generator's sequences, then their aux rows
+    int feedback_poke_armed;  // test hook (covo_debug_feedback_gain): the next covo_riccati_refine_feedback overwrites one gain entry
+    int feedback_poke_at;     // ... instance * H * 64 + index into K [H][4][16]
+    double feedback_poke;     // ... with this value, between the sweep and the generator
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -167,6 +175,7 @@ static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr
 static inline bool covo_arb_on(const covo_ctx *h) { return h->arb_out != nullptr; }
 static inline bool covo_refine_on(const covo_ctx *h) { return h->refine_out != nullptr; }
 static inline bool covo_riccati_on(const covo_ctx *h) { return h->riccati_out != nullptr; }
+static inline bool covo_feedback_on(const covo_ctx *h) { return h->feedback_out != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->eplog[COVO_EPLOG_DIAG].log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->eplog[COVO_EPLOG_DIAG].log ? COVO_MAX_ENVS : 0); }
@@ -683,7 +692,48 @@ struct RefineDesc {
     // not read, and the row ends {.., mu, bits(flags | rung << 8)}
     const double *dir = nullptr;
     const double *dir_side = nullptr;
+    // the closed-loop candidates (feedback_rollout.hip): extra [16][128] clipped fp32 sequences that compete as candidates 17 .. 32, their
+    // aux rows [16][4], and where the feedback row goes [COVO_FEEDBACK_FLOATS]; costs_out then has COVO_FEEDBACK_CANDIDATES entries
+    const float *extra = nullptr;
+    const float *extra_aux = nullptr;
+    float *fb_row_out = nullptr;
 };
+// feedback_rollout.hip: the closed-loop sequences of one instance under the sweep's gains, at n_alpha step sizes (<= 64), behind
+// launch_riccati and ahead of the line search; drag / mixed (the 16-state plants) are refused
+constexpr int COVO_FEEDBACK_MAX_ALPHAS = 64;
+constexpr int COVO_FEEDBACK_LADDER = 16;      // the line search's step sizes 2^(3 - j), j = 1 .. 16
+constexpr int COVO_FEEDBACK_AUX_FLOATS = 4;
+constexpr int COVO_FEEDBACK_GAIN_DOUBLES = COVO_H * (64 + 4 + 16);  // K [H][4][16], kff [H][4], x [H][16] of one instance
+struct FeedbackDesc {
+    const float *b = nullptr;     // [128] the plan the sweep ran at, 16-byte aligned
+    const double *K = nullptr;    // [H][4][16]
+    const double *kff = nullptr;  // [H][4]
+    const double *x = nullptr;    // [H][16]
+    float *a_out = nullptr;       // [n_alpha][128]
+    float *aux_out = nullptr;     // [n_alpha][COVO_FEEDBACK_AUX_FLOATS]
+    int n_alpha = COVO_FEEDBACK_LADDER;
+};
+// the handle's buffers of a step's instances (capi.hip: feedback_reserve): where the sweep leaves the gains, dense by instance as it
+// writes them, and instance e's generator launch
+static inline void covo_feedback_sweep_out(const covo_ctx *h, RiccatiOut &o)
+{
+    o.K = h->feedback_gains;
+    o.kff = o.K + (size_t)COVO_MAX_ENVS * COVO_H * 64;
+    o.x = o.kff + (size_t)COVO_MAX_ENVS * COVO_H * 4;
+}
+static inline FeedbackDesc covo_feedback_desc(const covo_ctx *h, int e, const float *b)
+{
+    FeedbackDesc f;
+    f.b = b;
+    f.K = h->feedback_gains + (size_t)e * COVO_H * 64;
+    f.kff = h->feedback_gains + (size_t)COVO_MAX_ENVS * COVO_H * 64 + (size_t)e * COVO_H * 4;
+    f.x = h->feedback_gains + (size_t)COVO_MAX_ENVS * COVO_H * (64 + 4) + (size_t)e * COVO_H * 16;
+    f.a_out = h->feedback_a + (size_t)e * COVO_FEEDBACK_LADDER * COVO_NA;
+    f.aux_out = h->feedback_a + (size_t)COVO_MAX_ENVS * COVO_FEEDBACK_LADDER * COVO_NA + (size_t)e * COVO_FEEDBACK_LADDER * COVO_FEEDBACK_AUX_FLOATS;
+    return f;
+}
+int launch_feedback_rollout(covo_ctx *h, const PlanInstDesc *inst, const FeedbackDesc *f, int n_inst, bool batched, hipStream_t s);
+int launch_feedback_rollout_one(covo_ctx *h, const PlanInstDesc &d, const FeedbackDesc &f, const double *alphas, hipStream_t s);
 int launch_newton_refine(covo_ctx *h, const PlanInstDesc *inst, const RefineDesc *r, int n_inst, bool batched, hipStream_t s);
 int launch_newton_refine_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const RefineDesc &r, hipStream_t s);
 void after_state_destroy(covo_ctx *h);  // (update_arbiter.hip) the three launches' device state: AfterState, after_step.hpp

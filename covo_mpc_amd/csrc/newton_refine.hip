@@ -21,12 +21,20 @@
 //            the row {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, 0, bits(flags)}.
 // c^2 of a step: sigma^4 det(R + delta I)^(1/n) = sigma^4 exp(2 sumlogB / n) from the Sigma chain's own log-determinant slot of this
 // step (sigma_ns.hip: SC_SUMLOGB; the chain's scale cancels: c = cz sqrt(scale)); stand-alone: the caller's 1 / c^2.
+// With closed-loop candidates supplied (RefineArgs::extra, feedback_rollout.hip: the sweep's gains around the nonlinear plant at the
+// same 16 step sizes) image lanes 17 .. 32 take those sequences as they are -- clipped fp32 already -- and 33 candidates compete; one
+// the generator flagged invalid costs +inf.  Ties go to the lowest index: a closed-loop candidate wins only when strictly cheaper than
+// every open-loop one.  choice is then 0 .. 32, alpha = 2^(3 - j) of either family, and a second row per instance says how the two
+// families fared: {cheapest of 0 .. 16, cheapest valid closed-loop (+inf: none), bits(index of the former), bits(index of the latter,
+// 0: none), that candidate's max |K dx|_inf, bits(its clipped count), bits(16-bit mask of invalid closed-loop candidates), 0}.  Flags
+// set: no candidate beyond 0 of either family, the second row {cost_base, +inf, 0 ...}.
 #include "after_step.hpp"
 #include "wave_reduce.hpp"
 
 constexpr int NR_BLOCK = 3 * COVO_WAVE;
 constexpr int NR_CH = 2;
 constexpr int NR_CAND = COVO_REFINE_CANDIDATES;  // 17
+constexpr int NR_CAND_FB = COVO_FEEDBACK_CANDIDATES;  // 33: with the closed-loop family
 
 struct RefineArgs {
     AfterHead head;         // R: the step's sample rollout (no samples: the image is the kernel's own)
@@ -41,6 +49,9 @@ struct RefineArgs {
     int nanp;
     const double *dir;      // [128] the direction supplied (riccati.hip), or null: d from Sigma and c^2 as above ...
     const double *dir_side; // ... with the sweep's side row {mu, rung, smallest pivot, flags}
+    const float *extra;     // [16][128] the closed-loop candidates (feedback_rollout.hip), or null: 17 candidates ...
+    const float *extra_aux; // ... [16][4] their aux rows {max |K dx|_inf, bits(clipped), bits(first invalid k, -1: none), 0}
+    float *fb_row_out;      // ... [COVO_FEEDBACK_FLOATS] or null
 };
 
 struct RefNoPos {  // (update_arbiter.hip: ArbNoPos)
@@ -92,12 +103,16 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
         Pb.costs_out = rebase_global(P_.costs_out, Pb.costs_out);
         Pb.dir = rebase_global(P_.dir, Pb.dir);
         Pb.dir_side = rebase_global(P_.dir_side, Pb.dir_side);
+        Pb.extra = rebase_global(P_.extra, Pb.extra);
+        Pb.extra_aux = rebase_global(P_.extra_aux, Pb.extra_aux);
+        Pb.fb_row_out = rebase_global(P_.fb_row_out, Pb.fb_row_out);
     }
     const RefineArgs &P = BATCHED ? Pb : P_;
     __shared__ RefLds S;
     const int tid = threadIdx.x, lane = tid & (COVO_WAVE - 1);
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const bool has_row = P_.row_out != nullptr, has_costs = P_.costs_out != nullptr;  // (all instances alike)
+    const bool fb = P_.extra != nullptr, has_fb_row = fb && P_.fb_row_out != nullptr;
 
     // ---- phase 0
     after_derive(tid, P.head, dyn, BATCHED, S.kb, S.dyn);
@@ -148,7 +163,9 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
         for (int i = tid; i < COVO_H * COVO_WAVE; i += NR_BLOCK) {
             const int k = i >> 6, l = i & (COVO_WAVE - 1);
             float4 v = am4[k];
-            if (l >= 1 && l < NR_CAND && flags == 0) {
+            if (fb && l >= NR_CAND && l < NR_CAND_FB && flags == 0) {
+                v = reinterpret_cast<const float4 *>(P.extra)[(l - NR_CAND) * COVO_H + k];
+            } else if (l >= 1 && l < NR_CAND && flags == 0) {
                 const double alpha = __builtin_ldexp(1.0, 3 - l);
                 const float b[4] = {v.x, v.y, v.z, v.w};
                 float o[4];
@@ -179,7 +196,13 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
     int n = 0;
     rp3_stages<false, ROLL, NR_CH, -1, false, true, REWARD, FDIST, true, RefNoPos, COVO_H, 3>(A, S.rings, S.p, wave, 0, 0, lane,
                                                                                                &S.a[0][0], cost, valid, n);
-    if (wave == 2) S.cost[lane] = cost;
+    if (wave == 2) {
+        // (a closed-loop sequence the generator flagged: first invalid k >= 0)
+        if (fb && flags == 0 && lane >= NR_CAND && lane < NR_CAND_FB &&
+            __float_as_int(P.extra_aux[(lane - NR_CAND) * COVO_FEEDBACK_AUX_FLOATS + 2]) >= 0)
+            cost = __builtin_inff();
+        S.cost[lane] = cost;
+    }
     __syncthreads();
 
     // ---- phase 2: the decision, the row, the mean
@@ -187,7 +210,7 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
         const float inf = __builtin_inff();
         int choice = 0;
         float cb = inf;
-        const int ncand = flags == 0 ? NR_CAND : 1;
+        const int ncand = flags == 0 ? (fb ? NR_CAND_FB : NR_CAND) : 1;
         for (int q = 0; q < ncand; ++q) {
             const float c = S.cost[q];
             if (c < cb) {  // (a NaN cost never wins; equal costs keep the lower candidate)
@@ -198,7 +221,7 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
         S.choice = choice;
         if (has_row) {
             const double gg = S.red[0][0] + S.red[1][0], gd = S.red[0][1] + S.red[1][1];
-            const float alpha = choice >= 1 ? __builtin_ldexpf(1.0f, 3 - choice) : 0.0f;
+            const float alpha = choice >= 1 ? __builtin_ldexpf(1.0f, 3 - (choice >= NR_CAND ? choice - (NR_CAND - 1) : choice)) : 0.0f;
             const float w6 = supplied ? (float)P.dir_side[0] : 0.0f;
             const int w7 = supplied ? (flags | ((int)P.dir_side[1] << 8)) : flags;
             const float out[COVO_REFINE_FLOATS] = {S.cost[0], S.cost[choice], __int_as_float(choice), alpha,
@@ -206,8 +229,29 @@ __global__ __launch_bounds__(NR_BLOCK) void newton_refine_kernel(const RefineArg
 #pragma unroll
             for (int j = 0; j < COVO_REFINE_FLOATS; ++j) P.row_out[j] = out[j];
         }
+        if (has_fb_row) {  // how the two families fared, by the rule above within each
+            int io = 0, ic = 0, bad = 0;
+            float co = inf, cc = inf;
+            for (int q = 0; q < (flags == 0 ? NR_CAND : 1); ++q)
+                if (S.cost[q] < co) {
+                    co = S.cost[q];
+                    io = q;
+                }
+            for (int q = NR_CAND; q < ncand; ++q) {
+                if (__float_as_int(P.extra_aux[(q - NR_CAND) * COVO_FEEDBACK_AUX_FLOATS + 2]) >= 0) bad |= 1 << (q - NR_CAND);
+                if (S.cost[q] < cc) {
+                    cc = S.cost[q];
+                    ic = q;
+                }
+            }
+            const float *aux = P.extra_aux + (ic ? ic - NR_CAND : 0) * COVO_FEEDBACK_AUX_FLOATS;
+            const float out[COVO_FEEDBACK_FLOATS] = {co, cc, __int_as_float(io), __int_as_float(ic), ic ? aux[0] : 0.0f, ic ? aux[1] : 0.0f,
+                                                     __int_as_float(bad), 0.0f};
+#pragma unroll
+            for (int j = 0; j < COVO_FEEDBACK_FLOATS; ++j) P.fb_row_out[j] = out[j];
+        }
     }
-    if (has_costs && tid >= COVO_WAVE && tid < COVO_WAVE + NR_CAND) P.costs_out[tid - COVO_WAVE] = S.cost[tid - COVO_WAVE];
+    if (has_costs && tid >= COVO_WAVE && tid < COVO_WAVE + (fb ? NR_CAND_FB : NR_CAND)) P.costs_out[tid - COVO_WAVE] = S.cost[tid - COVO_WAVE];
     __syncthreads();
     const int choice = S.choice;
     if (choice != 0 && tid < COVO_H) reinterpret_cast<float4 *>(P.a_mean)[tid] = S.a[tid][choice];
@@ -229,6 +273,9 @@ static void fill_refine_args(RefineArgs &P, covo_ctx *h, const PlanInstDesc &d, 
     P.nanp = covo_propagate_nan(h) ? 1 : 0;
     P.dir = r.dir;
     P.dir_side = r.dir_side;
+    P.extra = r.extra;
+    P.extra_aux = r.extra_aux;
+    P.fb_row_out = r.extra ? r.fb_row_out : nullptr;
 }
 
 // covo_newton_refine: one instance, the caller's buffers and shared vector (d.derive_keys = 0), the clip covo_rollout_cost applies

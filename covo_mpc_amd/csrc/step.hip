@@ -1296,7 +1296,8 @@ static int refine_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched,
     return launch_newton_refine(h, d, r, n, batched, s);
 }
 // covo_set_step_riccati: the Hessian's first two launches at the committed means into the refinement's own workspace, the sweep
-// (riccati.hip), then the line search with the direction supplied.  hd: the Hessian's inputs, dense over the n instances
+// (riccati.hip), [the closed-loop generator (feedback_rollout.hip),] then the line search with the direction supplied.  hd: the
+// Hessian's inputs, dense over the n instances
 static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, HessianDesc hd, hipStream_t s)
 {
     hd.status_dev = h->status_dev;
@@ -1304,14 +1305,27 @@ static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched
     o.d = h->riccati_d;
     o.g = h->refine_g;
     o.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA;
+    // covo_set_step_riccati_feedback: the sweep also leaves its gains, the generator (feedback_rollout.hip) runs the closed-loop
+    // sequences under them, and the line search judges them next to its own
+    const bool feedback = covo_feedback_on(h);
+    if (feedback) covo_feedback_sweep_out(h, o);
     if (int rc = launch_riccati(hd, COVO_RICCATI_REG0, o, h->ws_riccati, s)) return rc;
     RefineDesc r[COVO_MAX_ENVS];
+    FeedbackDesc f[COVO_MAX_ENVS];
     for (int e = 0; e < n; ++e) {
         r[e].g = o.g + (size_t)e * COVO_NA;
         r[e].dir = o.d + (size_t)e * COVO_NA;
         r[e].dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
         r[e].row_out = h->riccati_out + (size_t)e * COVO_RICCATI_FLOATS;
+        if (feedback) {
+            f[e] = covo_feedback_desc(h, e, d[e].a_mean_out);
+            r[e].extra = f[e].a_out;
+            r[e].extra_aux = f[e].aux_out;
+            r[e].fb_row_out = h->feedback_out + (size_t)e * COVO_FEEDBACK_FLOATS;
+        }
     }
+    if (feedback)
+        if (int rc = launch_feedback_rollout(h, d, f, n, batched, s)) return rc;
     return launch_newton_refine(h, d, r, n, batched, s);
 }
 // the refinement (rs / ric: null for the steps that have none) directly behind the arbiter, every pass of an iterated step included

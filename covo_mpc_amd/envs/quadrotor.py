@@ -20,7 +20,8 @@ import numpy as np
 
 from .. import controllers
 from .. import random as crandom
-from ..controllers._options import STEP_OPTION_DEFAULTS, check_refine, check_riccati, check_step_options, take
+from ..controllers._options import (STEP_OPTION_DEFAULTS, check_refine, check_riccati, check_riccati_feedback, check_step_options,
+                                    take)
 from ..dynamics import utils
 from ..dynamics.dataclass import Action3D, DeviceState, EnvParams3D, EnvState3D
 from ..dynamics.free import get_quadrotor_1st_order_dyn
@@ -572,7 +573,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                      verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
                      arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0,
                      rows: bool = False, staged: bool = False, controller: str = "covo-online", refine: bool = False,
-                     riccati: bool = False):
+                     riccati: bool = False, riccati_feedback: bool = False):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     `controller` (covo-online by default), controller and env on the device, ONE host sync.  -> mean position error per instance
@@ -590,13 +591,16 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     ValueError.  refine=True ("covo-online" only; not a step option: controllers/_options.py: check_refine): every control step ends
     with the Newton line search on its committed mean; the trace's u and cost_plan then show the refined mean.  riccati=True
     ("covo-online" only here: the env-batched MPPI / covo-offline steps refuse it; check_riccati): the same line search along the
-    Riccati sweep's direction."""
+    Riccati sweep's direction; riccati_feedback=True on top of it: the closed-loop candidates under the sweep's gains compete in that
+    line search (check_riccati_feedback)."""
     if controller not in ("covo-online", "mppi", "covo-offline"):
         raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi' or 'covo-offline'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
     check_step_options(None, "online" if controller == "covo-online" else controller, **opts)  # ValueError before anything is built
     check_refine(refine, "online" if controller == "covo-online" else controller, sigma_period=sigma_period)
     check_riccati(riccati, "online" if controller == "covo-online" else f"the env-batched {controller} controller", refine=refine)
+    check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None),
+                           what=f"the env-batched {controller} controller")
     if arbiter and update == "softmax":
         raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
@@ -612,7 +616,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     else:
         b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, sample_sigma=cp0.sample_sigma,
                                               mode="offline" if controller == "covo-offline" else "online", refine=refine,
-                                              riccati=riccati, **kw)
+                                              riccati=riccati, riccati_feedback=riccati_feedback, **kw)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     if controller == "covo-offline":  # (the table keys: children of the instances' control keys, which stay what they were)
@@ -739,12 +743,13 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
                    iters=1, elite=None, sigma_period=1, compute_post_cov=False, sigma_adapt=0.0, refine=False,
-                   riccati=False):
+                   riccati=False, riccati_feedback=False):
     """quadrotor.py:670-752.  compute_diag, compute_plan, ess_min, compute_fan, update, iters, elite, sigma_period, compute_post_cov and
     sigma_adapt are the sampling controllers' step options -- what each does and what it adds to the controller's info dict:
     controllers/_options.py.  refine (covo-online only): the Newton line search behind every step -- a switch, not a step option
     (controllers/_options.py: check_refine).  riccati (mppi, covo-offline, covo-online): the same line search along the Riccati sweep's
-    direction, which needs neither R nor Sigma (controllers/_options.py: check_riccati)."""
+    direction, which needs neither R nor Sigma (controllers/_options.py: check_riccati).  riccati_feedback (on top of riccati): the
+    closed-loop candidates under the sweep's gains compete in that line search (controllers/_options.py: check_riccati_feedback)."""
     opts = take(locals())
     import torch
     # ValueError before anything is built; the controller's own check, with N, follows
@@ -752,6 +757,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     check_step_options(None, what, **opts)
     check_refine(refine, what, sigma_period=sigma_period)
     check_riccati(riccati, what, refine=refine)
+    check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
 
     def parse_sample_params(param_text):
         if not param_text:
@@ -777,7 +783,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         control_params = controllers.MPPIParams(gamma_mean=1.0, gamma_sigma=0.0, discount=1.0, sample_sigma=sigma,
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
-                                          process_group=process_group, compute_info=compute_info, riccati=riccati, **opts), control_params
+                                          process_group=process_group, compute_info=compute_info, riccati=riccati,
+                                          riccati_feedback=riccati_feedback, **opts), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -789,7 +796,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
             a_cov_offline=torch.zeros((H, env.action_dim, env.action_dim), dtype=torch.float32, device=device))
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group, compute_info=compute_info,
-                                          refine=refine, riccati=riccati, **opts), control_params
+                                          refine=refine, riccati=riccati, riccati_feedback=riccati_feedback, **opts), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -902,6 +909,7 @@ class Args:
     sigma_adapt: float = 0.0  # (not in quadjax) covo-online under a Sigma period: the posterior covariance's weight in a reuse step's Sigma'; 0 = off
     refine: bool = False    # (not in quadjax) covo-online: every control step ends with a Newton line search on its committed mean
     riccati: bool = False   # (not in quadjax) mppi / covo: every control step ends with that line search along the Riccati sweep's direction
+    riccati_feedback: bool = False  # (not in quadjax) on top of riccati: the closed-loop candidates under the sweep's gains compete too
 
 
 def main(args: Args):
@@ -918,7 +926,7 @@ def main(args: Args):
                                                 update=args.update, iters=args.iters, elite=args.elite or None,
                                                 sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render,
                                                 sigma_adapt=args.sigma_adapt, refine=args.refine,
-                                                riccati=args.riccati)
+                                                riccati=args.riccati, riccati_feedback=args.riccati_feedback)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -935,6 +943,8 @@ def _cli():
     for f, default in Args().__dict__.items():
         if f == "post_cov":
             ap.add_argument("--post-cov", "--post_cov", dest="post_cov", action="store_true")
+        elif f == "riccati_feedback":
+            ap.add_argument("--riccati-feedback", "--riccati_feedback", dest="riccati_feedback", action="store_true")
         elif isinstance(default, bool):
             ap.add_argument(f"--{f}", action="store_true")
         elif f == "update":

@@ -813,6 +813,56 @@ int covo_riccati_refine(covo_handle_t h, const float *state, const float *pos_tr
                         const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
                         void *stream);
 int covo_set_step_riccati(covo_handle_t h, float *rows /* DEVICE [n_inst][COVO_RICCATI_FLOATS]; NULL = off */, int32_t n_inst);
+
+/* Riccati feedback: closed-loop candidates under the sweep's gains (additive to ABI 10: COVO_HAS_RICCATI_FEEDBACK; off by default, and
+ * off changes nothing a caller can observe: no launch, no allocation, no captured graph).
+ * The sweep's K_k, k_k and nominal states xb_k are the forward pass of DDP / iLQR once the state deviation is taken from the nonlinear
+ * plant instead of from A_k, B_k (csrc/feedback_rollout.hip).  For a step size alpha, from x_0 = the state's (pos, vel, quat, omega)
+ * in fp32, k = 0 .. 31:
+ *     dx_j = (double)x_k[j] - xb_k[j] (raw coordinates, j = 0 .. 12);  v_i = fma(alpha, k_k[i], (double)b_k[i]), then
+ *     v_i = fma(K_k[i][j], dx_j, v_i) with j ascending;  u_k[i] = (float)clip(v_i, -1, 1);  x_{k+1} = the fp32 model step under the
+ *     force the sample rollouts apply at step k (the state's own at k = 0, then the shared vector or row k of the step table).
+ * K = 0 gives the open-loop candidate fp32(clip(b + alpha k)) bit for bit.  A v_i that is not finite makes the sequence invalid: from
+ * that k on it is clip(b), and the line search gives it cost +inf.
+ *   aux row       float[4] = {max over k of |K_k dx_k|_inf (the feedback term as it entered the action), bits(int32 number of components
+ *                 with |v| > 1), bits(int32 first k with a v that is not finite, -1: none), 0}
+ *   feedback row  float[COVO_FEEDBACK_FLOATS] = {cost of the cheapest of candidates 0 .. 16, cost of the cheapest valid closed-loop
+ *                 candidate (+inf: none), bits(int32 index of the former), bits(int32 index of the latter, 0: none), that candidate's
+ *                 max |K dx|_inf, bits(int32 its clipped count), bits(int32 16-bit mask of invalid closed-loop candidates), 0}
+ * With the switch on the line search judges COVO_FEEDBACK_CANDIDATES = 33 sequences: 0 .. 16 as before (bit-identical, costs
+ * included), 16 + j the closed-loop sequence at alpha_j = 2^(3 - j), j = 1 .. 16.  The first cheapest wins, so a closed-loop candidate
+ * is committed only when strictly cheaper than every open-loop one; choice is 0 .. 32 and alpha is 2^(3 - j) of either family.  When
+ * the sweep reports flags there are no candidates beyond 0 and the feedback row is {cost_base, +inf, 0, 0, 0, 0, 0, 0}.
+ * covo_feedback_rollout: the generator alone, n_inst instances with the rollout inputs of covo_arbitrate (state = DEVICE
+ *   float[n_inst][32] -- the start state need not be xb_0: that is the tube-MPC use; f_disturb_steps = DEVICE float[n_inst][H][4] or
+ *   NULL); a = DEVICE float[n_inst][128], 16-byte aligned; K = DEVICE double[n_inst][H][4][16], kff = DEVICE double[n_inst][H][4],
+ *   x = DEVICE double[n_inst][H][16] as covo_riccati leaves them; alphas = HOST double[n_alpha], 1 <= n_alpha <= 64;
+ *   a_out = DEVICE float[n_inst][n_alpha][128]; aux_out = DEVICE float[n_inst][n_alpha][4].
+ * covo_riccati_refine_feedback: covo_riccati_refine with the closed-loop family: the Hessian's two launches, the sweep, the generator,
+ *   the line search; costs_out = DEVICE float[n_inst][COVO_FEEDBACK_CANDIDATES] or NULL, fb_rows_out = DEVICE
+ *   float[n_inst][COVO_FEEDBACK_FLOATS].
+ * covo_set_step_riccati_feedback: fb_rows = DEVICE float[n_inst][COVO_FEEDBACK_FLOATS]; every control step that runs the Riccati
+ *   refinement then launches sweep | generator | line search, all eager.  No captured step graph changes.
+ * Refused before any launch, with a message that names the condition: attached without covo_set_step_riccati on the handle, or with
+ *   more instances than it has; drag / mixed (the 16-state plants: their force is a state of the sweep and a per-sample quantity of
+ *   the rollout), in the stand-alone calls and at the step; more instances than rows. */
+#define COVO_HAS_RICCATI_FEEDBACK 1
+#define COVO_FEEDBACK_FLOATS 8
+#define COVO_FEEDBACK_CANDIDATES 33
+int covo_feedback_rollout(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                          const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
+                          const double *K, const double *kff, const double *x, const double *alphas /* HOST [n_alpha] */,
+                          int32_t n_alpha, int32_t n_inst, float *a_out, float *aux_out, void *stream);
+int covo_riccati_refine_feedback(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                                 const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                                 const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out,
+                                 float *costs_out, float *fb_rows_out, void *stream);
+int covo_set_step_riccati_feedback(covo_handle_t h, float *fb_rows /* DEVICE [n_inst][COVO_FEEDBACK_FLOATS]; NULL = off */,
+                                   int32_t n_inst);
+/* Test hook: the NEXT covo_riccati_refine_feedback on this handle overwrites entry `index` of instance `inst`'s gains K [H][4][16]
+ * with `value` between the sweep and the generator (once) -- how a test hands the line search closed-loop candidates that are not
+ * valid. */
+int covo_debug_feedback_gain(covo_handle_t h, int32_t inst, int32_t index, double value);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

@@ -15,10 +15,13 @@ name = sys.argv[1]
 # refine row has no episode log: compare the errors with those of the same call without the flag)
 # python scripts/eval_seeds.py mppi --riccati (or covo-offline, covo-online, with any --sigma-period): every control step ends with the
 # same line search along the Riccati sweep's direction (csrc/riccati.hip); again, compare with the same call without the flag
+# python scripts/eval_seeds.py mppi --riccati --riccati-feedback: the closed-loop candidates under the sweep's gains compete in that line
+# search (csrc/feedback_rollout.hip); compare with the same call without the last flag
 rest = sys.argv[2:]
 refine = "--refine" in rest
 riccati = "--riccati" in rest
-rest = [r for r in rest if r not in ("--refine", "--riccati")]
+feedback = "--riccati-feedback" in rest
+rest = [r for r in rest if r not in ("--refine", "--riccati", "--riccati-feedback")]
 for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_adapt")):
     while flag in rest:
         i = rest.index(flag)
@@ -27,7 +30,7 @@ opts = {k: (float(v) if k in ("sigma_adapt", "ess_min") else int(v)) for k, v in
 assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"}, opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
-ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, riccati=riccati, **opts)
+ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, riccati=riccati, riccati_feedback=feedback, **opts)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
