@@ -71,6 +71,14 @@ COVO_FEEDBACK_CANDIDATES = 33
 FEEDBACK_AUX_FLOATS = 4
 FEEDBACK_MAX_ALPHAS = 64
 FEEDBACK_LADDER = tuple(2.0 ** (3 - j) for j in range(1, 17))
+COVO_HAS_PLAN_HOLD = 1  # plan_hold= on top of riccati= (covo_set_step_plan_hold, covo_plan_hold, covo_set_episode_hold_log)
+# a hold row: {bits(int32 age j), alpha, max |v - v0| (the feedback term as it entered the action), bits(int32 clipped count),
+# bits(int32 flags), |dx_pos|_2, bits(int32 the state's time word), 0}; flags bit 0: the sweep is flagged (its side row), 1: a v
+# that is not finite, 2: the state's time is not the plan's + j.  A plan step's row: {0, 0, 0, 0, 0, 0, bits(time), 0}
+COVO_HOLD_FLOATS = 8
+COVO_MAX_PLAN_HOLD = 16  # plan_hold= of the controllers: every m-th control step plans, the others hold
+HOLD_FIELDS = ("age", "alpha", "gain", "clipped", "flags", "dpos", "time")
+HOLD_FLAG_SWEEP, HOLD_FLAG_NOT_FINITE, HOLD_FLAG_TIME = 1, 2, 4
 # the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
 COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
 COVO_EPLOG_KINDS = 6
@@ -249,6 +257,12 @@ _SIGS = {
                                                C.c_double, C.c_int32, _P, _P, _P, _P]),
     "covo_set_step_riccati_feedback": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_feedback_gain": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_double]),
+    # the plan hold (covo_hip.h: COVO_HAS_PLAN_HOLD)
+    "covo_set_step_plan_hold": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),
+    "covo_step_plan_age": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "covo_plan_hold": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P]),
+    "covo_set_episode_hold_log": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_debug_plan_latch": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),

@@ -22,8 +22,8 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
-from ._options import (check_refine, check_riccati, check_riccati_feedback, check_kernel_path, check_step_options, sharded_refusal,
-                       take)
+from ._options import (check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_kernel_path, check_step_options,
+                       sharded_refusal, take)
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
 # that attribute's value is the log's extra allocation argument: the fan's K, the iteration log's row width; covo_set_episode_rows' kind
@@ -72,7 +72,7 @@ class SamplingCore:
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False,
-                 riccati: bool = False, riccati_feedback: bool = False):
+                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1):
         opts = take(locals())
         import torch
         sharded = False
@@ -83,6 +83,7 @@ class SamplingCore:
         refine = check_refine(refine, "online", sigma_period=opt.sigma_period, sharded=sharded)
         riccati = check_riccati(riccati, "a sampling core", refine=refine, sharded=sharded)
         riccati_feedback = check_riccati_feedback(riccati_feedback, riccati=riccati, what="a sampling core")
+        plan_hold = check_plan_hold(plan_hold, riccati=riccati, sigma_period=opt.sigma_period, what="a sampling core")
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -231,6 +232,13 @@ class SamplingCore:
         self.riccati_feedback_on = riccati_feedback
         self.riccati_feedback_rows = (self._attach_rows(_lib.COVO_FEEDBACK_FLOATS, "covo_set_step_riccati_feedback")
                                       if riccati_feedback else None)
+        # self.plan_hold_rows [rows, 8]: {bits(age), alpha, max |v - v0|, bits(clipped), bits(flags), |dx_pos|, bits(time), 0}
+        # (plan_hold=: _options.check_plan_hold; attached behind riccati's rows, which it needs)
+        self.plan_hold_period = plan_hold  # (plan_hold() is the stateless hold step)
+        self.plan_hold_rows = None
+        if plan_hold > 1:
+            with torch.cuda.device(self.device):
+                self.plan_hold_rows = self._attach_rows(_lib.COVO_HOLD_FLOATS, "covo_set_step_plan_hold", plan_hold)
         self._list_infos()
         self.exchange = "collective"
         if self.world > 1:
@@ -381,7 +389,8 @@ class SamplingCore:
             (self.sigma_period > 1, self.sigma_info), (self.post_cov is not None, self.post_cov_info),
             (self.sigma_adapt_rows is not None, self.sigma_adapt_info), (self.refine_rows is not None, self.refine_info),
             (self.riccati_rows is not None, self.riccati_info),
-            (self.riccati_feedback_rows is not None, self.riccati_feedback_info)) if on]
+            (self.riccati_feedback_rows is not None, self.riccati_feedback_info),
+            (self.plan_hold_rows is not None, self.plan_hold_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -414,6 +423,18 @@ class SamplingCore:
         segment that starts at episode.n_steps: step k of it writes row n_steps + k of each."""
         for name in EPISODE_LOGS:
             self.attach_log(name, episode, rows_left)
+        self.attach_hold_log(episode, rows_left)
+
+    def attach_hold_log(self, episode, rows_left: int):
+        """Bind `episode`'s hold log (episode.holdlog, [.., T + 1, 8]; allocated on first use) under plan_hold > 1: the hold launch,
+        and the latch on plan steps, write their rows themselves (covo_set_episode_hold_log) -- not one of EPISODE_LOGS, whose rows a
+        copy launch or an attachment's own setter fills."""
+        if self.plan_hold_rows is None:
+            return
+        if getattr(episode, "holdlog", None) is None:
+            episode.alloc_hold_log()
+        check(self.lib.covo_set_episode_hold_log(self.h, ptr(episode.log_segment("holdlog")), int(rows_left)),
+              "covo_set_episode_hold_log")
 
     @property
     def iters_logged(self) -> int:
@@ -555,6 +576,88 @@ class SamplingCore:
         row = self.riccati_feedback_rows[0]
         return {"riccati_closed": self.riccati_rows[0, 2:3].view(self.torch.int32)[0] > _lib.COVO_REFINE_CANDIDATES - 1,
                 "riccati_cost_open": row[0], "riccati_cost_closed": row[1], "riccati_gain_max": row[4]}
+
+    def _plan_ages(self):
+        nxt, last = C.c_int32(0), C.c_int32(0)
+        check(self.lib.covo_step_plan_age(self.h, C.byref(nxt), C.byref(last)), "covo_step_plan_age")
+        return int(nxt.value), int(last.value)
+
+    @property
+    def plan_age(self) -> int:
+        """The age the NEXT control step is scheduled at under plan_hold: 0 = it plans, 1 .. plan_hold - 1 = it holds."""
+        return self._plan_ages()[0]
+
+    def plan_hold_info(self) -> dict:
+        """{"plan_age": the age the last step ran at, a Python int (0 = it planned); "hold_gain" (max |K dx|_inf as it entered the
+        action), "hold_clipped" (0-d int32), "hold_flags" (0-d int32: 1 sweep flagged, 2 not finite, 4 time mismatch), "hold_alpha"}
+        of the last step as views of self.plan_hold_rows (no sync, no copy); {} when the core was built with plan_hold=1."""
+        if self.plan_hold_rows is None:
+            return {}
+        row = self.plan_hold_rows[0]
+        i32 = self.torch.int32
+        return {"plan_age": self._plan_ages()[1], "hold_gain": row[2], "hold_clipped": row[3:4].view(i32)[0],
+                "hold_flags": row[4:5].view(i32)[0], "hold_alpha": row[1]}
+
+    def plan_latch(self, n_envs=1):
+        """What the last plan step latched for its first n_envs instances (covo_debug_plan_latch; copies): {"b" float32 [n, 128] the mean
+        its sweep ran at, "t" int32 [n] the time word it planned from, "K" [n, 32, 4, 16], "kff" [n, 32, 4], "x" [n, 32, 16] float64
+        the sweep's outputs} -- the inputs of the hold steps that follow, as plan_hold() takes them."""
+        torch = self.torch
+        n = int(n_envs)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        out = {"b": torch.empty((n, COVO_NA), dtype=torch.float32, device=self.device),
+               "t": torch.empty((n,), dtype=torch.int32, device=self.device), "K": torch.empty((n, COVO_H, 4, 16), **f64),
+               "kff": torch.empty((n, COVO_H, 4), **f64), "x": torch.empty((n, COVO_H, 16), **f64)}
+        check(self.lib.covo_debug_plan_latch(self.h, n, ptr(out["b"]), ptr(out["t"]), ptr(out["K"]), ptr(out["kff"]), ptr(out["x"]),
+                                             self.stream()), "covo_debug_plan_latch")
+        return out
+
+    def restart_plan_hold(self):
+        """The schedule back to age 0 (a controller's reset()): the next step plans."""
+        if self.plan_hold_rows is not None:
+            check(self.lib.covo_set_step_plan_hold(self.h, self.plan_hold_period, ptr(self.plan_hold_rows), self._rows),
+                  "covo_set_step_plan_hold")
+
+    def plan_hold(self, packed, b, K, kff, x, alpha, stage, t_plan=None, a_mean=None, a_cov=None, rows=None):
+        """covo_plan_hold: the stateless hold step (csrc/plan_hold.hip) for n_inst instances.  packed: the measured states float32
+        [n_inst, 32]; b float32 [n_inst, 128]: the mean the sweep ran at; K [n_inst, 32, 4, 16], kff [n_inst, 32, 4], x [n_inst, 32, 16]
+        (float64): riccati()'s outputs of those names; alpha: a float, or a float32 device tensor with one entry per instance (the
+        committed candidate's step size); stage j in [0, 32); t_plan: int32 device tensor [n_inst], the time word the plan was made
+        at, or None (no time check); rows: riccati()'s "rows" [n_inst, 4] (float64; entry 3: the sweep's flags), or None (not flagged);
+        a_mean float32 [n_inst, 128] / a_cov float32 [n_inst, 32, 4, 4] (MPPI): shifted IN PLACE, u written
+        to a_mean[:, 0:4]; None: not touched -> (u float32 [n_inst, 4], rows float32 [n_inst, 8] = {bits(j), alpha, max |v - v0|,
+        bits(clipped), bits(flags), |dx_pos|, bits(time), 0}).  No sync."""
+        torch = self.torch
+        f32 = dict(dtype=torch.float32, device=self.device)
+        b = b.reshape(-1, COVO_NA).contiguous()
+        n_inst = int(b.shape[0])
+        assert b.is_cuda and b.dtype == torch.float32
+        packed = packed.reshape(-1, _lib.COVO_STATE_FLOATS)
+        assert packed.is_cuda and packed.dtype == torch.float32 and packed.is_contiguous() and int(packed.shape[0]) == n_inst
+        if not 0 <= int(stage) < COVO_H:
+            raise ValueError(f"plan_hold: stage={stage} outside [0, {COVO_H})")
+        gains = []
+        for t, shape in ((K, (COVO_H, 4, 16)), (kff, (COVO_H, 4)), (x, (COVO_H, 16))):
+            gains.append(t.to(device=self.device, dtype=torch.float64).reshape((n_inst,) + shape).contiguous())
+        if torch.is_tensor(alpha):
+            al = alpha.to(**f32).reshape(-1).contiguous()
+            assert al.numel() == n_inst
+        else:
+            al = torch.full((n_inst,), float(alpha), **f32)
+        if t_plan is not None:
+            t_plan = t_plan.to(device=self.device, dtype=torch.int32).reshape(-1).contiguous()
+            assert t_plan.numel() == n_inst
+        for t, n in ((a_mean, COVO_NA), (a_cov, COVO_H * 16)):
+            assert t is None or (t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n_inst * n)
+        if rows is not None:
+            rows = rows.to(device=self.device, dtype=torch.float64).reshape(n_inst, _lib.COVO_RICCATI_SIDE).contiguous()
+        side, rows = rows, torch.empty((n_inst, _lib.COVO_HOLD_FLOATS), **f32)
+        u = torch.empty((n_inst, 4), **f32)
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_plan_hold(self.h, ptr(packed), ptr(b), ptr(gains[0]), ptr(gains[1]), ptr(gains[2]), ptr(side), ptr(al), 1,
+                                          int(stage), ptr(t_plan), ptr(a_mean), ptr(a_cov), ptr(u), ptr(rows), n_inst, self.stream()),
+                  "covo_plan_hold")
+        return u, rows
 
     def feedback_rollout(self, dstate, params_c, a, K, kff, x, alphas=None, f_shared=None, f_steps=None, packed=None):
         """covo_feedback_rollout: the closed-loop action sequences under the sweep's gains (csrc/feedback_rollout.hip).  a (float32

@@ -296,3 +296,40 @@ def check_riccati_feedback(feedback, *, riccati, disturb_type=None, what="a samp
                                   "force is a state of the sweep and a per-sample quantity of the rollout, and the closed-loop "
                                   "generator carries the 13-state plants only (covo_set_step_riccati_feedback refuses them at the step)")
     return True
+
+
+def check_plan_hold(plan_hold, *, riccati, sigma_period=1, disturb_type=None, what="a sampling controller") -> int:
+    """plan_hold= on top of riccati= -> the period m.  A switch like riccati_feedback=, not a step option: SamplingCore, MPPIController,
+    CoVOController, BatchedCoVOController, get_controller and eval_env_batched take it and check it here; the C side's counterpart is
+    the plan hold block of check_step_attachments (csrc/capi.hip).
+
+    plan_hold=m > 1: every m-th control step, counted from reset(), is the control step as it is (a plan step); the m - 1 between
+    sample nothing -- one small launch (covo_set_step_plan_hold, csrc/plan_hold.hip) applies stage j of the law the plan step's Riccati
+    sweep left, u = clip(b_j + alpha k_j + K_j (x - xb_j)), to the measured state, shifts the mean (MPPI: and the covariances) as a
+    step's begin work does and puts u in front: info["plan_age"] (a Python int) / ["hold_gain"] / ["hold_clipped"] / ["hold_flags"] /
+    ["hold_alpha"].  It goes with iters (a plan step runs its k passes), riccati_feedback and every step option but sigma_period.
+    1: nothing attached, no launch added.
+
+    The objections, in a fixed order: anything but an integer in [1, COVO_MAX_PLAN_HOLD] (ValueError); m > 1 without riccati=True -- a
+    hold step applies that sweep's gains (ValueError); m > 1 with sigma_period > 1 -- both thin out the step, and sigma_adapt goes with
+    it (ValueError); disturb_type drag / mixed -- the 16-state plants, as for riccati_feedback (NotImplementedError; disturb_type=None:
+    not known here, the step refuses it).  Whatever riccati= refuses stays refused by check_riccati."""
+    import numbers
+    if (isinstance(plan_hold, bool) or not isinstance(plan_hold, numbers.Integral) or
+            not 1 <= int(plan_hold) <= _lib.COVO_MAX_PLAN_HOLD):
+        raise ValueError(f"plan_hold={plan_hold!r} outside [1, {_lib.COVO_MAX_PLAN_HOLD}] (an integer number of control steps per plan; "
+                         "1 = off)")
+    m = int(plan_hold)
+    if m == 1:
+        return 1
+    if riccati is not True:
+        raise ValueError(f"plan_hold={m} with {what} needs riccati=True: a hold step applies the gains of that sweep; give riccati=True "
+                         "or plan_hold=1")
+    if int(sigma_period) > 1:
+        raise ValueError(f"plan_hold={m} with sigma_period={sigma_period}: both thin out the step (and sigma_adapt goes with the Sigma "
+                         "period); give one of them as 1")
+    if disturb_type in ("drag", "mixed"):
+        raise NotImplementedError(f"plan_hold={m} with disturb_type={disturb_type!r}: drag / mixed are 16-state plants -- their force is "
+                                  "a state of the sweep, and the hold step carries the 13-state plants only "
+                                  "(covo_set_step_plan_hold refuses them at the step)")
+    return m

@@ -22,13 +22,13 @@ from .. import _lib
 from .._lib import COVO_H, COVO_NA, check
 from ..dynamics.dataclass import as_device_state
 from ._core import SamplingCore
-from ._options import check_refine, check_riccati, check_riccati_feedback, check_step_options, take
+from ._options import check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_step_options, take
 
 # (controller attribute, core attribute) of the attachment buffers the batched controllers hand out
 CORE_BUFFERS = (("diag", "diag"), ("plan", "plan"), ("fan", "fan"), ("arbiter", "arbiter"), ("lam_eff", "lam_eff"), ("elite", "elite_rows"),
                 ("iter_cost_min", "iter_cost_min"), ("post_cov", "post_cov"), ("post_aux", "post_aux"),
                 ("sigma_adapt_rows", "sigma_adapt_rows"), ("refine", "refine_rows"), ("riccati", "riccati_rows"),
-                ("riccati_feedback", "riccati_feedback_rows"))
+                ("riccati_feedback", "riccati_feedback_rows"), ("plan_hold_rows", "plan_hold_rows"))
 
 
 class BatchedCoVOController:
@@ -40,7 +40,7 @@ class BatchedCoVOController:
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, staged: bool = False,
-                 refine: bool = False, riccati: bool = False, riccati_feedback: bool = False):
+                 refine: bool = False, riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1):
         opts = take(locals())
         moded = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step
         if staged and not moded:
@@ -57,6 +57,7 @@ class BatchedCoVOController:
         check_refine(refine, what, sigma_period=sigma_period)
         check_riccati(riccati, what, refine=refine)
         check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
+        check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), what=what)
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -74,7 +75,7 @@ class BatchedCoVOController:
         # 150-270 us of host time per call)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  diag_rows=int(n_envs), refine=refine, riccati=riccati, riccati_feedback=riccati_feedback,
-                                 **opts)
+                                 plan_hold=plan_hold, **opts)
         if moded:
             check(self.core.lib.covo_set_step_batched_staged(self.core.h, int(self.staged)), "covo_set_step_batched_staged")
         # after a call, row e of each of the core's attachment buffers holds instance e's result of that step; None for what is off
@@ -138,6 +139,7 @@ class BatchedCoVOController:
         """covo-offline: instance e's Sigma table and its Cholesky factors from instance e's own start state, parameters and key,
         through CoVOController.reset_a_cov_offline (covo.py:58-104; once per episode, a host loop over the instances).
         -> (a_cov_offline, a_chol_offline) [E, T, 128, 128].  The other modes have nothing to build."""
+        self.core.restart_plan_hold()  # (plan_hold: the episode's first step plans)
         if self.mode != _lib.MODE_COVO_OFFLINE:
             if self.core.sigma_period > 1:  # the schedule restarts: the episode's first step refreshes Sigma
                 self.core.set_sigma_period(self.core.sigma_period)
@@ -203,6 +205,11 @@ class BatchedCoVOController:
     def sigma_age(self) -> int:
         """The age the last call ran at under sigma_period (0 = it refreshed every instance's Sigma; always 0 without a period)."""
         return self.core._sigma_ages()[1]
+
+    @property
+    def plan_age(self) -> int:
+        """The age the last call ran at under plan_hold (0 = every instance planned; always 0 without it)."""
+        return self.core._plan_ages()[1]
 
     def time_phases(self, step_mask: int, reps: int = 10) -> float:
         """GPU microseconds of the selected launch groups of the LAST batched step (2 Hessian, 4 Sigma, 8 GEMM, 16 rollout,

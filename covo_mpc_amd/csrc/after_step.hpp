@@ -182,6 +182,7 @@ struct ArgBlockCache {
 // compares against, and every step would synchronise and upload
 struct AfterState {
     ArgBlockCache arbiter, plan, fan, refine, feedback;
+    ArgBlockCache hold, hold_primitive, latch;  // plan_hold.hip: a batched hold step's blocks, covo_plan_hold's, a batched plan step's latch
     float *nominal = nullptr;  // [COVO_MAX_ENVS][128] the update arbiter's nominals of the env-batched fused step
 };
 static inline AfterState *after_state(covo_ctx *h)

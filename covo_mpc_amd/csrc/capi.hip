@@ -151,6 +151,9 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->riccati_tab));
     DESTROY(hipFree(h->feedback_gains));
     DESTROY(hipFree(h->feedback_a));
+    DESTROY(hipFree(h->hold_b));
+    DESTROY(hipFree(h->hold_t));
+    DESTROY(hipFree(h->hold_keys));
     DESTROY(hipEventDestroy(h->ev_fork));
     DESTROY(hipEventDestroy(h->ev_join));
     DESTROY(hipStreamDestroy(h->side_stream));
@@ -1176,6 +1179,29 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                     "plant, whose force is a state of the sweep and a per-sample quantity of the rollout; detach the feedback rows", what,
                     params[e].disturb_kind, e);
     }
+    if (h->plan_hold > 1) {  // the steps between two plan steps apply the sweep's law: they need the sweep, and every step a Sigma of its own
+        REQUIRE(covo_riccati_on(h),
+                "%s: the plan hold (covo_set_step_plan_hold, period=%d) without the Riccati refinement (covo_set_step_riccati): a hold "
+                "step applies the gains of that sweep; attach it or set period = 1", what, h->plan_hold);
+        REQUIRE(covo_sigma_period(h) == 1,
+                "%s: the plan hold (covo_set_step_plan_hold, period=%d) together with a Sigma period (covo_set_step_sigma_period, "
+                "period=%d): both thin out the step; set one of them to 1", what, h->plan_hold, covo_sigma_period(h));
+        for (int e = 0; e < n_inst; ++e)
+            REQUIRE(params[e].disturb_kind != COVO_DISTURB_DRAG && params[e].disturb_kind != COVO_DISTURB_MIXED,
+                    "%s: the plan hold (covo_set_step_plan_hold) with disturb_kind=%d (drag / mixed, instance %d): a 16-state plant, whose "
+                    "force is a state of the sweep; the hold step carries the 13-state plants only; set period = 1", what,
+                    params[e].disturb_kind, e);
+        REQUIRE(n_inst <= h->hold_n, "%s: %d instances, the hold rows (covo_set_step_plan_hold) have n_inst=%d", what, n_inst, h->hold_n);
+    }
+    return 0;
+}
+
+// the episode hold log (covo_set_episode_hold_log) of a driver that writes rows [first_row, first_row + n_steps)
+static int check_hold_log(const covo_ctx *h, int first_row, int n_steps, const char *what)
+{
+    REQUIRE(h->hold_log == nullptr || (first_row >= 0 && first_row + n_steps <= h->hold_log_stride),
+            "%s: episode hold log rows [%d, %d) outside [0, %d) (covo_set_episode_hold_log)", what, first_row, first_row + n_steps,
+            h->hold_log_stride);
     return 0;
 }
 
@@ -1508,6 +1534,109 @@ int covo_set_step_riccati(covo_handle_t h, float *rows, int32_t n_inst)
     return 0;
 }
 
+// ---- the plan hold (plan_hold.hip; the schedule: covo_plan_step_age / _done, covo_common.hpp).  Plan steps keep their launches and
+// graphs; a hold step is one eager launch: no epoch bump.  What the step needs next to it is checked at the step (check_step_attachments)
+int covo_set_step_plan_hold(covo_handle_t h, int32_t period, float *rows, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_plan_hold: null handle");
+    REQUIRE(period >= 1 && period <= COVO_MAX_PLAN_HOLD, "covo_set_step_plan_hold: period=%d outside [1, %d] (1 = off: every step plans)",
+            period, COVO_MAX_PLAN_HOLD);
+    h->plan_age = 0;
+    h->hold_latch_n = 0;
+    if (period == 1) {
+        h->plan_hold = 1;
+        h->hold_rows = nullptr;
+        h->hold_n = 0;
+        h->hold_log = nullptr;
+        h->hold_log_stride = 0;
+        return 0;
+    }
+    REQUIRE(rows != nullptr && n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_plan_hold: period=%d needs rows and n_inst=%d in (0, %d]",
+            period, n_inst, COVO_MAX_ENVS);
+    // the step's scratch, here and not in a step: the sweep's gains, the latch, a hold step's keys
+    if (int rc = feedback_reserve(h)) return rc;
+    if (h->hold_b == nullptr) COVO_CHECK_HIP(hipMalloc(&h->hold_b, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(float)));
+    if (h->hold_t == nullptr) COVO_CHECK_HIP(hipMalloc(&h->hold_t, (size_t)COVO_MAX_ENVS * sizeof(int)));
+    if (h->hold_keys == nullptr) {
+        COVO_CHECK_HIP(hipMalloc(&h->hold_keys, (size_t)COVO_MAX_ENVS * 12 * sizeof(uint32_t)));
+        COVO_CHECK_HIP(hipMemset(h->hold_keys, 0, (size_t)COVO_MAX_ENVS * 12 * sizeof(uint32_t)));
+    }
+    h->plan_hold = period;
+    h->hold_rows = rows;
+    h->hold_n = n_inst;
+    return 0;
+}
+
+int covo_step_plan_age(covo_handle_t h, int32_t *next_age, int32_t *last_age)
+{
+    REQUIRE(h, "covo_step_plan_age: null handle");
+    if (next_age) *next_age = covo_plan_hold(h) > 1 ? h->plan_age : 0;
+    if (last_age) *last_age = h->plan_last_age;
+    return 0;
+}
+
+int covo_set_episode_hold_log(covo_handle_t h, float *log, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_hold_log: null handle");
+    if (log == nullptr) {
+        h->hold_log = nullptr;
+        h->hold_log_stride = 0;
+        return 0;
+    }
+    REQUIRE(covo_plan_hold(h) > 1, "covo_set_episode_hold_log: no plan hold: call covo_set_step_plan_hold (period > 1) first");
+    REQUIRE(stride > 0, "covo_set_episode_hold_log: stride=%d", stride);
+    h->hold_log = log;
+    h->hold_log_stride = stride;
+    return 0;
+}
+
+int covo_plan_hold(covo_handle_t h, const float *state, const float *b, const double *K, const double *kff, const double *x,
+                   const double *side, const float *alpha, int32_t alpha_stride, int32_t stage, const int32_t *t_plan, float *a_mean,
+                   float *a_cov, float *u_out, float *rows_out, int32_t n_inst, void *stream)
+{
+    REQUIRE(h, "covo_plan_hold: null handle");
+    CHECK_DEVICE(h, "covo_plan_hold");
+    REQUIRE(state && b && K && kff && x && alpha && u_out && rows_out, "covo_plan_hold: bad argument");
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_plan_hold: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(stage >= 0 && stage < COVO_H, "covo_plan_hold: stage=%d outside [0, %d)", stage, COVO_H);
+    REQUIRE(alpha_stride >= 0, "covo_plan_hold: alpha_stride=%d", alpha_stride);
+    REQUIRE((((uintptr_t)a_mean | (uintptr_t)a_cov) & 15) == 0, "covo_plan_hold: a_mean and a_cov must be 16-byte aligned");
+    HoldDesc d[COVO_MAX_ENVS];
+    std::memset(d, 0, (size_t)n_inst * sizeof(HoldDesc));
+    for (int e = 0; e < n_inst; ++e) {
+        d[e].state = state + (size_t)e * COVO_STATE_FLOATS;
+        d[e].b = b + (size_t)e * COVO_NA;
+        d[e].K = K + (size_t)e * COVO_H * 64;
+        d[e].kff = kff + (size_t)e * COVO_H * 4;
+        d[e].x = x + (size_t)e * COVO_H * 16;
+        d[e].side = side ? side + (size_t)e * COVO_RICCATI_SIDE : nullptr;
+        d[e].alpha = alpha + (size_t)e * alpha_stride;
+        d[e].t_plan = t_plan ? t_plan + e : nullptr;
+        d[e].a_mean_src = d[e].a_mean = a_mean ? a_mean + (size_t)e * COVO_NA : nullptr;
+        d[e].a_cov = a_cov ? a_cov + (size_t)e * COVO_H * 16 : nullptr;
+        d[e].u_out = u_out + (size_t)e * COVO_DU;
+        d[e].row_out = rows_out + (size_t)e * COVO_HOLD_FLOATS;
+    }
+    return launch_plan_hold(h, d, n_inst, n_inst > 1, true, stage, -1, (hipStream_t)stream);
+}
+
+int covo_debug_plan_latch(covo_handle_t h, int32_t n_inst, float *b_out, int32_t *t_out, double *K_out, double *kff_out, double *x_out,
+                          void *stream)
+{
+    REQUIRE(h, "covo_debug_plan_latch: null handle");
+    REQUIRE(b_out && t_out && K_out && kff_out && x_out, "covo_debug_plan_latch: bad argument");
+    REQUIRE(h->hold_b != nullptr && h->hold_latch_n > 0 && n_inst > 0 && n_inst <= h->hold_latch_n,
+            "covo_debug_plan_latch: no plan step has latched on this handle, or n_inst=%d exceeds its %d instances", n_inst, h->hold_latch_n);
+    hipStream_t s = (hipStream_t)stream;
+    const FeedbackDesc f = covo_feedback_desc(h, 0, nullptr);  // (dense by instance)
+    COVO_CHECK_HIP(hipMemcpyAsync(b_out, h->hold_b, (size_t)n_inst * COVO_NA * sizeof(float), hipMemcpyDeviceToDevice, s));
+    COVO_CHECK_HIP(hipMemcpyAsync(t_out, h->hold_t, (size_t)n_inst * sizeof(int), hipMemcpyDeviceToDevice, s));
+    COVO_CHECK_HIP(hipMemcpyAsync(K_out, f.K, (size_t)n_inst * COVO_H * 64 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    COVO_CHECK_HIP(hipMemcpyAsync(kff_out, f.kff, (size_t)n_inst * COVO_H * 4 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    COVO_CHECK_HIP(hipMemcpyAsync(x_out, f.x, (size_t)n_inst * COVO_H * 16 * sizeof(double), hipMemcpyDeviceToDevice, s));
+    return 0;
+}
+
 int covo_debug_sigma_workspace(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream)
 {
     REQUIRE(h && out, "covo_debug_sigma_workspace: bad argument");
@@ -1576,7 +1705,27 @@ static int check_single_step(const covo_ctx *h, const covo_env_params *params, c
             what);
     REQUIRE(!covo_needs_tables(*params) || args->derive_keys == 1, "%s: disturb_kind=%d needs derive_keys = 1 (the per-step "
             "disturbance tables are derived from the raw controller key on the device)", what, params->disturb_kind);
+    REQUIRE(h->plan_hold <= 1 || (((uintptr_t)args->a_mean | (uintptr_t)args->a_mean_in | (uintptr_t)args->a_cov) & 15) == 0,
+            "%s: a_mean, a_mean_in and a_cov must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
     return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, params, what);
+}
+
+// ---- the plan hold's schedule, for the four step entry points alike (covo_mpc_step, covo_mpc_step_batched[_mode], covo_run_episode,
+// run_episode_batched): the control step of a single handle at the age the schedule gives it -- 0: the step and its after-step frame
+// as ever; else the hold step and its plan trace.  row: the episode's row index (< 0: none)
+static int single_step_at_age(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
+                              const float *f_shared, int age, int row, hipStream_t s)
+{
+    if (age == 0) return covo_step_impl(h, params, args, key0, key1, f_shared, s);
+    return covo_hold_step(h, args, age, row, s);
+}
+static int batched_step_at_age(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *norm, bool online,
+                               const covo_env_params *params, const uint32_t *keys, int age, int row, hipStream_t s)
+{
+    if (age != 0) return covo_hold_step_batched(h, args, age, row, s);  // (covo-online only: the others refuse the Riccati refinement)
+    return online                   ? covo_step_batched_impl(h, args, params, keys, s)
+           : covo_batched_staged(h) ? covo_step_batched_staged_impl(h, norm, params, keys, s)
+                                    : covo_step_batched_small_impl(h, norm, params, keys, s);
 }
 
 int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, float *state_true,
@@ -1592,7 +1741,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
             "covo_run_episode: a sample-sharded step (partial_out != NULL) needs the peer-write exchange (covo_exchange_create / "
             "covo_exchange_connect) and a_mean_shift");
     int rc = check_single_step(h, params, args, "covo_run_episode");
-    if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode"))) return rc;
+    if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode")) || (rc = check_hold_log(h, 0, n_steps, "covo_run_episode")))
+        return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -1601,7 +1751,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
         host_philox_split(key, 0u, nrng);
         host_philox_split(key, 1u, rng_act);
         host_philox_split(key, 2u, rng_step);
-        if ((rc = covo_step_impl(h, params, args, rng_act[0], rng_act[1], nullptr, s))) return rc;
+        const int age = covo_plan_step_age(h, 1);  // (a hold step uses no rng_act; rng_step is what it was)
+        if ((rc = single_step_at_age(h, params, args, rng_act[0], rng_act[1], nullptr, age, t, s))) return rc;
         if (args->partial_out != nullptr) {
             // sample-sharded: every rank's record to every rank (peer writes, exchange.hip), then the same merge on all of them.
             // partial_out is this rank's RANK record: {m, s, v} there, its position sums (if any) at + COVO_PARTIAL_FLOATS
@@ -1624,8 +1775,11 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
                     return rc;
             }
         }
-        auto frame = [&](int row) { return covo_plan_after_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, row, s); };
+        auto frame = [&](int row) {
+            return covo_plan_after_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, row, s, false, age != 0);
+        };
         if ((rc = episode_step_tail(h, frame, 1, t, s))) return rc;
+        covo_plan_step_done(h, age, 1);
         rc = launch_env_step(state_true, const_cast<float *>(args->state), args->pos_traj, args->vel_traj, acc_traj, args->T,
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
@@ -1710,6 +1864,8 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
     REQUIRE(mode == COVO_MODE_COVO_ONLINE || !covo_riccati_on(h),
             "%s: the Riccati refinement (covo_set_step_riccati) is not available for the env-batched MPPI / covo-offline step, fused or "
             "staged: those batches carry no per-instance Hessian constants; detach it", what);
+    REQUIRE(h->plan_hold <= 1 || ((uintptr_t)args->a_mean & 15) == 0,
+            "%s: a_mean must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
     if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, params, what))) return rc;  // (batched steps derive their keys)
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
@@ -1761,7 +1917,7 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     const bool online = !m || m->mode == COVO_MODE_COVO_ONLINE;
     REQUIRE(log == nullptr || (log_index >= 0 && log_index + n_steps <= log_stride),
             "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
-    if ((rc = check_episode_logs(h, log_index, n_steps, what))) return rc;
+    if ((rc = check_episode_logs(h, log_index, n_steps, what)) || (rc = check_hold_log(h, log_index, n_steps, what))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -1776,14 +1932,14 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             host_philox_split(key, 2u, &step_keys[2 * e]);
             host_philox_split(nrng, 0u, &next[2 * e]);
         }
-        if ((rc = online                  ? covo_step_batched_impl(h, args, params, act_keys, s)
-                  : covo_batched_staged(h) ? covo_step_batched_staged_impl(h, &norm, params, act_keys, s)
-                                           : covo_step_batched_small_impl(h, &norm, params, act_keys, s)))
-            return rc;
+        const int age = covo_plan_step_age(h, E);  // (the batch shares one age)
+        if ((rc = batched_step_at_age(h, args, &norm, online, params, act_keys, age, log_index + t, s))) return rc;
         auto frame = [&](int row) {
-            return covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : norm.mode, params, states_true, row, s);
+            return covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : norm.mode, params, states_true, row, s, false,
+                                           age != 0 ? act_keys : nullptr);
         };
         if ((rc = episode_step_tail(h, frame, E, log_index + t, s))) return rc;
+        covo_plan_step_done(h, age, E);
         if ((rc = launch_env_step_batched(states_true, const_cast<float *>(args->states), args->pos_traj, args->vel_traj, acc_traj,
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
                                           log_stride, log_index + t, s)))
@@ -1826,8 +1982,12 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     REQUIRE(args && params && keys, "covo_mpc_step_batched: null argument");
     int rc = check_batch_step(h, args, nullptr, params, false, "covo_mpc_step_batched", nullptr);
     if (rc) return rc;
-    if ((rc = covo_step_batched_impl(h, args, params, keys, (hipStream_t)stream))) return rc;
-    return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, (hipStream_t)stream);
+    const int age = covo_plan_step_age(h, args->n_envs);
+    if ((rc = batched_step_at_age(h, args, nullptr, true, params, keys, age, -1, (hipStream_t)stream))) return rc;
+    if ((rc = covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, (hipStream_t)stream, false, age != 0 ? keys : nullptr)))
+        return rc;
+    covo_plan_step_done(h, age, args->n_envs);
+    return 0;
 }
 
 int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params, const uint32_t *keys,
@@ -1839,11 +1999,13 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     covo_batch_mode_args norm;
     int rc = check_batch_step(h, &args->base, args, params, false, "covo_mpc_step_batched_mode", &norm);
     if (rc) return rc;
-    rc = args->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, &args->base, params, keys, (hipStream_t)stream)
-         : covo_batched_staged(h)            ? covo_step_batched_staged_impl(h, &norm, params, keys, (hipStream_t)stream)
-                                             : covo_step_batched_small_impl(h, &norm, params, keys, (hipStream_t)stream);
-    if (rc) return rc;
-    return covo_plan_after_batched(h, &args->base, args->mode, params, nullptr, -1, (hipStream_t)stream);
+    const int age = covo_plan_step_age(h, args->base.n_envs);
+    if ((rc = batched_step_at_age(h, &args->base, &norm, args->mode == COVO_MODE_COVO_ONLINE, params, keys, age, -1, (hipStream_t)stream)))
+        return rc;
+    if ((rc = covo_plan_after_batched(h, &args->base, args->mode, params, nullptr, -1, (hipStream_t)stream, false, age != 0 ? keys : nullptr)))
+        return rc;
+    covo_plan_step_done(h, age, args->base.n_envs);
+    return 0;
 }
 
 int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, int32_t step_mask,
@@ -1900,8 +2062,12 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
     REQUIRE(params && args, "covo_mpc_step: null argument");
     int rc = check_single_step(h, params, args, "covo_mpc_step");
     if (rc) return rc;
-    if ((rc = covo_step_impl(h, params, args, key0, key1, f_disturb_shared, (hipStream_t)stream))) return rc;
-    return covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream);
+    const int age = covo_plan_step_age(h, 1);
+    if ((rc = single_step_at_age(h, params, args, key0, key1, f_disturb_shared, age, -1, (hipStream_t)stream))) return rc;
+    if ((rc = covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream, false, age != 0)))
+        return rc;
+    covo_plan_step_done(h, age, 1);
+    return 0;
 }
 
 int covo_cholesky(covo_handle_t h, const float *A, int32_t n, int32_t batch, float *L_out, void *stream)

@@ -120,6 +120,18 @@ struct covo_ctx {
     int feedback_poke_armed;  // test hook (covo_debug_feedback_gain): the next covo_riccati_refine_feedback overwrites one gain entry
     int feedback_poke_at;     // ... instance * H * 64 + index into K [H][4][16]
     double feedback_poke;     // ... with this value, between the sweep and the generator
+    // the plan hold (covo_set_step_plan_hold; plan_hold.hip); plan_hold <= 1: off
+    int plan_hold;            // every plan_hold-th control step plans; the steps between apply the sweep's law to the measured state
+    int plan_age;             // the age the NEXT step runs at: 0 = plan, 1 .. plan_hold - 1 = hold
+    int plan_last_age;        // the age the last enqueued step ran at
+    int hold_latch_n;         // for how many instances the last plan step left its latch (0: none yet)
+    float *hold_rows;         // caller's [hold_n][COVO_HOLD_FLOATS]: instance e's hold row of every step
+    int hold_n;
+    float *hold_b;            // [COVO_MAX_ENVS][128] the latch: the mean the last plan step's sweep ran at ...
+    int *hold_t;              // [COVO_MAX_ENVS] ... and the time word of the state it planned from
+    float *hold_log;          // caller's [n_inst][hold_log_stride][COVO_HOLD_FLOATS] episode log (covo_set_episode_hold_log), or null
+    int hold_log_stride;
+    uint32_t *hold_keys;      // [COVO_MAX_ENVS][12]: a hold step's raw keys for its plan trace, laid out like a step's scalars
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -159,6 +171,22 @@ static inline void covo_sigma_step_done(covo_ctx *h, int age, const float *L, fl
     h->sigma_L_sigma = sample_sigma;
     h->sigma_L_n = n_inst;
     h->sigma_age = (age + 1) % covo_sigma_period(h);
+}
+// the plan hold, scheduled the way the Sigma period is: the age this step of n_inst instances runs at -- 0 (a plan step) unless the
+// hold is on, the schedule says hold and the last plan step left its latch for as many instances
+static inline int covo_plan_hold(const covo_ctx *h) { return (h->plan_hold > 1 && h->hold_rows != nullptr) ? h->plan_hold : 1; }
+static inline int covo_plan_step_age(const covo_ctx *h, int n_inst)
+{
+    if (covo_plan_hold(h) == 1 || h->plan_age == 0) return 0;
+    return h->hold_latch_n == n_inst ? h->plan_age : 0;
+}
+// the step that ran at `age` has been enqueued (a plan step: with its latch): advance the schedule
+static inline void covo_plan_step_done(covo_ctx *h, int age, int n_inst)
+{
+    h->plan_last_age = age;
+    if (covo_plan_hold(h) == 1) return;
+    if (age == 0) h->hold_latch_n = n_inst;
+    h->plan_age = (age + 1) % covo_plan_hold(h);
 }
 static inline int covo_step_iters(const covo_ctx *h) { return (h->iter_log != nullptr && h->iters > 1) ? h->iters : 1; }
 static inline float *covo_iter_slot(const covo_ctx *h, int pass) { return covo_step_iters(h) > 1 ? h->iter_log + pass : nullptr; }
@@ -732,6 +760,36 @@ static inline FeedbackDesc covo_feedback_desc(const covo_ctx *h, int e, const fl
     f.aux_out = h->feedback_a + (size_t)COVO_MAX_ENVS * COVO_FEEDBACK_LADDER * COVO_NA + (size_t)e * COVO_FEEDBACK_LADDER * COVO_FEEDBACK_AUX_FLOATS;
     return f;
 }
+// plan_hold.hip: one instance of a hold step / of a plan step's latch.  Both are the kernels' argument blocks as they stand (all
+// pointers: compared bytewise, no padding); what is null is null for every instance of a launch
+struct HoldDesc {
+    const float *state;       // [32] the measured (noisy) state
+    const float *b;           // [128] the mean the sweep ran at
+    const double *K, *kff, *x;  // [H][4][16], [H][4], [H][16]
+    const float *alpha;       // one float: the step size of the committed candidate
+    const int *t_plan;        // one int32: the time word the plan step planned from, or null: no time check
+    const double *side;       // the sweep's side row [COVO_RICCATI_SIDE] (entry 3: its flags), or null: not flagged
+    const float *a_mean_src;  // [128] the mean to shift (may be a_mean), 16-byte aligned; with a_mean
+    float *a_mean;            // [128] where the shifted mean with u in front goes, or null
+    float *a_cov;             // [H][4][4] MPPI's covariance blocks, shifted in place, or null
+    float *u_out;             // [4] or null
+    float *row_out;           // [COVO_HOLD_FLOATS] or null
+    float *log;               // this instance's rows of the episode hold log [stride][COVO_HOLD_FLOATS], or null
+};
+struct LatchDesc {
+    const float *a_mean;      // [128] the mean the sweep has just run at
+    const float *state;       // [32] the state the step planned from
+    float *b_out;             // [128]
+    int *t_out;               // one int32
+    float *row_out;           // [COVO_HOLD_FLOATS] or null
+    float *log;               // as HoldDesc::log
+};
+int launch_plan_hold(covo_ctx *h, const HoldDesc *d, int n_inst, bool batched, bool primitive, int stage, int log_index, hipStream_t s);
+int launch_plan_latch(covo_ctx *h, const LatchDesc *d, int n_inst, bool batched, int log_index, hipStream_t s);
+// step.hip: the hold step of a single / an env-batched schedule (age >= 1) in place of the step's own launches, and the plan trace
+// behind it (no arbiter, refinement, fan or posterior covariance: hold = true below)
+int covo_hold_step(covo_ctx *h, const covo_step_args *args, int age, int log_index, hipStream_t s);
+int covo_hold_step_batched(covo_ctx *h, const covo_batch_args *args, int age, int log_index, hipStream_t s);
 int launch_feedback_rollout(covo_ctx *h, const PlanInstDesc *inst, const FeedbackDesc *f, int n_inst, bool batched, hipStream_t s);
 int launch_feedback_rollout_one(covo_ctx *h, const PlanInstDesc &d, const FeedbackDesc &f, const double *alphas, hipStream_t s);
 int launch_newton_refine(covo_ctx *h, const PlanInstDesc *inst, const RefineDesc *r, int n_inst, bool batched, hipStream_t s);
@@ -740,10 +798,14 @@ void after_state_destroy(covo_ctx *h);  // (update_arbiter.hip) the three launch
 // step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
 // states_true + trace_index >= 0: an episode driver's step, which also writes its trace row
 // arbiter_only: the arbiter's launch between two passes of an iterated step (covo_set_step_iters)
+// hold (keys: the instances' raw rng_act, host): behind a hold step of the plan hold -- the plan trace's launch alone, with the hold
+// step's own inputs
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only = false);
+                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only = false,
+                         bool hold = false);
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
-                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only = false);
+                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only = false,
+                            const uint32_t *hold_keys = nullptr);
 int launch_env_step(float *state, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,
                     const covo_env_params &p, const float *action, const uint32_t *step_key, int noisy_on,
                     float obs_noise_scale, float *log, int log_index, hipStream_t s);

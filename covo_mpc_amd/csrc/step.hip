@@ -653,6 +653,11 @@ __global__ void batch_set_dyn_kernel(uint32_t *__restrict__ dyn, const BatchDyn 
     const int i = threadIdx.x;
     if (i < 4 * n) dyn[12 * (i >> 2) + (i & 3)] = b.w[i >> 2][i & 3];
 }
+__global__ void hold_park_keys_kernel(uint32_t *__restrict__ dyn, const BatchDyn b, int n)
+{
+    const int i = threadIdx.x;
+    if (i < 2 * n) dyn[12 * (i >> 1) + 10 + (i & 1)] = b.w[i >> 1][2 + (i & 1)];
+}
 // the eager launch in front of every batched step (its kernel arguments ARE the keys): instance e's raw rng_act to dyn[12 e + 0..1]
 static void batch_upload_keys(uint32_t *dyn, const uint32_t *keys, int E, hipStream_t s)
 {
@@ -1243,6 +1248,56 @@ int covo_step_batched_staged_impl(covo_ctx *h, const covo_batch_mode_args *m, co
         [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, m->mode, params, nullptr, -1, on, true); });
 }
 
+// ---- the hold step of the plan hold (covo_set_step_plan_hold; plan_hold.hip): ONE launch in place of the step's own -- stage `age`
+// of the law the last plan step's sweep left, on the state the step would have read, then the begin work's shift with the action in
+// front.  alpha comes from the handle's Riccati row (entry 3: the step size of the committed candidate), the sweep's flags from its side row
+static HoldDesc hold_desc(const covo_ctx *h, int e, const float *state, const float *a_mean_src, float *a_mean, float *a_cov)
+{
+    const FeedbackDesc f = covo_feedback_desc(h, e, h->hold_b + (size_t)e * COVO_NA);
+    HoldDesc d;
+    std::memset(&d, 0, sizeof(d));
+    d.state = state;
+    d.b = f.b;
+    d.K = f.K;
+    d.kff = f.kff;
+    d.x = f.x;
+    d.alpha = h->riccati_out + (size_t)e * COVO_RICCATI_FLOATS + 3;
+    d.t_plan = h->hold_t + e;
+    d.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA + (size_t)e * COVO_RICCATI_SIDE;
+    d.a_mean_src = a_mean_src;
+    d.a_mean = a_mean;
+    d.a_cov = a_cov;
+    d.row_out = h->hold_rows + (size_t)e * COVO_HOLD_FLOATS;
+    d.log = h->hold_log ? h->hold_log + (size_t)e * h->hold_log_stride * COVO_HOLD_FLOATS : nullptr;
+    return d;
+}
+int covo_hold_step(covo_ctx *h, const covo_step_args *args, int age, int log_index, hipStream_t s)
+{
+    const HoldDesc d = hold_desc(h, 0, args->state, args->a_mean_in ? args->a_mean_in : args->a_mean, args->a_mean,
+                                 args->mode == COVO_MODE_MPPI ? args->a_cov : nullptr);
+    return launch_plan_hold(h, &d, 1, false, false, age, log_index, s);
+}
+int covo_hold_step_batched(covo_ctx *h, const covo_batch_args *args, int age, int log_index, hipStream_t s)
+{
+    HoldDesc d[COVO_MAX_ENVS];
+    for (int e = 0; e < args->n_envs; ++e) {
+        float *am = args->a_mean + (size_t)e * COVO_NA;
+        d[e] = hold_desc(h, e, args->states + (size_t)e * COVO_STATE_FLOATS, am, am, nullptr);
+    }
+    return launch_plan_hold(h, d, args->n_envs, true, false, age, log_index, s);
+}
+// a hold step's raw keys where a begin launch parks a step's (dyn[12 e + 10..11]): what its plan trace and tables derive from
+static void hold_park_keys(uint32_t *dyn, const uint32_t *keys, int E, hipStream_t s)
+{
+    BatchDyn blk;
+    std::memset(&blk, 0, sizeof(blk));
+    for (int e = 0; e < E; ++e) {
+        blk.w[e][2] = keys[2 * e];
+        blk.w[e][3] = keys[2 * e + 1];
+    }
+    hipLaunchKernelGGL(hold_park_keys_kernel, dim3(1), dim3(256), 0, s, dyn, blk, E);
+}
+
 // ---- the launches behind a step (after_step.hpp: the update arbiter, the flight recorder's plan and trace, the sample fan), eager.
 // What they need to know about ONE instance of the step that has just been enqueued: the inputs its sample rollouts had.  The shared
 // vector is re-derived from the raw key by the launches themselves (every step path forms it from the same device function); the
@@ -1298,7 +1353,9 @@ static int refine_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched,
 // covo_set_step_riccati: the Hessian's first two launches at the committed means into the refinement's own workspace, the sweep
 // (riccati.hip), [the closed-loop generator (feedback_rollout.hip),] then the line search with the direction supplied.  hd: the
 // Hessian's inputs, dense over the n instances
-static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, HessianDesc hd, hipStream_t s)
+// covo_set_step_plan_hold: the sweep leaves its gains whether or not the closed-loop candidates are on, and the latch (plan_hold.hip)
+// sits between the sweep and the line search, which overwrites the mean the sweep ran at; row: the episode's row index, < 0: none
+static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, HessianDesc hd, int row, hipStream_t s)
 {
     hd.status_dev = h->status_dev;
     RiccatiOut o;
@@ -1308,8 +1365,21 @@ static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched
     // covo_set_step_riccati_feedback: the sweep also leaves its gains, the generator (feedback_rollout.hip) runs the closed-loop
     // sequences under them, and the line search judges them next to its own
     const bool feedback = covo_feedback_on(h);
-    if (feedback) covo_feedback_sweep_out(h, o);
+    const bool hold = covo_plan_hold(h) > 1;
+    if (feedback || hold) covo_feedback_sweep_out(h, o);
     if (int rc = launch_riccati(hd, COVO_RICCATI_REG0, o, h->ws_riccati, s)) return rc;
+    if (hold) {
+        LatchDesc l[COVO_MAX_ENVS];
+        for (int e = 0; e < n; ++e) {
+            l[e].a_mean = d[e].a_mean_out;
+            l[e].state = d[e].state;
+            l[e].b_out = h->hold_b + (size_t)e * COVO_NA;
+            l[e].t_out = h->hold_t + e;
+            l[e].row_out = h->hold_rows + (size_t)e * COVO_HOLD_FLOATS;
+            l[e].log = h->hold_log ? h->hold_log + (size_t)e * h->hold_log_stride * COVO_HOLD_FLOATS : nullptr;
+        }
+        if (int rc = launch_plan_latch(h, l, n, batched, row, s)) return rc;
+    }
     RefineDesc r[COVO_MAX_ENVS];
     FeedbackDesc f[COVO_MAX_ENVS];
     for (int e = 0; e < n; ++e) {
@@ -1334,15 +1404,35 @@ static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, c
 {
     int rc = launch_update_arbiter(h, d, n, batched, trace_index, s);
     if (rc == 0 && rs != nullptr && covo_refine_on(h)) rc = refine_after(h, d, n, batched, *rs, s);
-    if (rc == 0 && ric != nullptr && covo_riccati_on(h)) rc = riccati_after(h, d, n, batched, *ric, s);
+    if (rc == 0 && ric != nullptr && covo_riccati_on(h)) rc = riccati_after(h, d, n, batched, *ric, trace_index, s);
     if (rc || arbiter_only) return rc;
     if ((rc = launch_plan_trace(h, d, n, batched, states_true, trace_index, s))) return rc;
     return launch_sample_fan(h, d, n, batched, trace_index, s);
 }
 
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only)
+                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only, bool hold)
 {
+    if (hold) {
+        // behind a hold step: the plan trace alone.  The rollouts' disturbance table is formed here from the raw key, into the step's
+        // own scratch (the hold step has enqueued none of the step's launches)
+        if (!covo_plan_on(h)) return 0;
+        StepState *hs = reinterpret_cast<StepState *>(h->step);
+        const BatchInst hi = {args->state, args->pos_traj, args->vel_traj, args->a_mean, args->a, args->cost, args->groupmin};
+        const bool tables = covo_needs_tables(*params) && hs != nullptr;
+        PlanInstDesc hd = plan_inst(hi, args->T, args->n_samples, params, args->derive_keys, args->rollout_deterministic, nullptr,
+                                    tables ? hs->f_tab_rollout : nullptr, nullptr);
+        hd.key[0] = key0;
+        hd.key[1] = key1;
+        for (int c = 0; c < 3; ++c) hd.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
+        if (tables) {
+            const uint32_t raw[2] = {key0, key1};
+            hold_park_keys(h->hold_keys, raw, 1, s);
+            if (int rc = launch_disturb_tables_step(*params, args->state, h->hold_keys, args->rollout_deterministic, hs->f_tab_rollout,
+                                                    nullptr, s)) return rc;
+        }
+        return launch_plan_trace(h, &hd, 1, false, state_true, trace_index, s);
+    }
     if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
     // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
@@ -1393,8 +1483,24 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
 
 // mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run) or MPPI / COVO_OFFLINE (covo_step_batched_small_impl)
 int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
-                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only)
+                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only, const uint32_t *hold_keys)
 {
+    if (hold_keys != nullptr) {
+        // behind a hold step (covo-online batches only: the others refuse the Riccati refinement): the plan trace alone, the instances'
+        // raw keys parked where a begin launch would have left them, the rollouts' tables formed from them into the batch's scratch
+        if (!covo_plan_on(h)) return 0;
+        BatchState *hb = reinterpret_cast<BatchState *>(h->batch);
+        const BatchCommon *hc = &hb->online;
+        const int n = args->n_envs;
+        hold_park_keys(h->hold_keys, hold_keys, n, s);
+        if (hc->tables)
+            if (int rc = launch_disturb_tables_batched(hc->models, args->states, h->hold_keys, n, 1, hc->tab_rollout, nullptr, s)) return rc;
+        PlanInstDesc hd[COVO_MAX_ENVS];
+        for (int e = 0; e < n; ++e)
+            hd[e] = plan_inst(batch_inst(*args, e), args->T, args->n_samples, &params[e], 1, mode != COVO_MODE_MPPI, nullptr,
+                              hc->tables ? hc->tab_rollout + (size_t)e * COVO_H * 4 : nullptr, h->hold_keys + 12 * e + 10);
+        return launch_plan_trace(h, hd, n, true, states_true, trace_index, s);
+    }
     if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;

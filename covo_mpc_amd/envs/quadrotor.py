@@ -20,7 +20,7 @@ import numpy as np
 
 from .. import controllers
 from .. import random as crandom
-from ..controllers._options import (STEP_OPTION_DEFAULTS, check_refine, check_riccati, check_riccati_feedback, check_step_options,
+from ..controllers._options import (STEP_OPTION_DEFAULTS, check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_step_options,
                                     take)
 from ..dynamics import utils
 from ..dynamics.dataclass import Action3D, DeviceState, EnvParams3D, EnvState3D
@@ -357,6 +357,27 @@ class _EpisodeLogs:
         shape = tuple(self.log.shape[:-1]) + tuple(int(n) for n in inner) + ((getattr(self._lib, width),) if width else ())
         setattr(self, name, torch.zeros(shape, dtype=torch.float32, device=self.device))
 
+    # the hold log of plan_hold > 1 -- [.., T + 1, 8], None until such a controller runs the episode -- is not one of LOGS: the hold
+    # launch, and the latch on plan steps, write its rows themselves (SamplingCore.attach_hold_log)
+    holdlog = None
+
+    def alloc_hold_log(self):
+        import torch
+        self.holdlog = torch.zeros(tuple(self.log.shape[:-1]) + (self._lib.COVO_HOLD_FLOATS,), dtype=torch.float32, device=self.device)
+
+    def read_hold(self):
+        """-> {age [n] (int32: 0 = the step planned), alpha [n], gain [n] (max |K dx|_inf as it entered the action), clipped [n] (int32),
+        flags [n] (int32: 1 the sweep is flagged, 2 a command that is not finite, 4 the state's time is not the plan's + age),
+        dpos [n], time [n] (int32)}: per enqueued step its hold row (include/covo_hip.h: covo_set_step_plan_hold), under a controller
+        built with plan_hold > 1."""
+        if self.holdlog is None:
+            raise RuntimeError("no hold log: run_episode under a controller built with plan_hold=m > 1")
+        self.read_log()  # synchronises and checks the device status
+        rows = self.holdlog.narrow(self.STEP_AXIS, 0, self.n_steps).cpu().numpy()
+        as_int = lambda i: np.ascontiguousarray(rows[..., i]).view(np.int32)
+        return {"age": as_int(0), "alpha": rows[..., 1], "gain": rows[..., 2], "clipped": as_int(3), "flags": as_int(4),
+                "dpos": rows[..., 5], "time": as_int(6)}
+
     def log_segment(self, name):
         """What the episode driver binds of log `name` for the next segment: one instance -- the rows from n_steps on (covo_run_episode
         counts its rows from 0); E instances -- the whole buffer (the batched drivers take the first row of a segment as log_index)."""
@@ -573,7 +594,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                      verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
                      arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0,
                      rows: bool = False, staged: bool = False, controller: str = "covo-online", refine: bool = False,
-                     riccati: bool = False, riccati_feedback: bool = False):
+                     riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     `controller` (covo-online by default), controller and env on the device, ONE host sync.  -> mean position error per instance
@@ -592,7 +613,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     with the Newton line search on its committed mean; the trace's u and cost_plan then show the refined mean.  riccati=True
     ("covo-online" only here: the env-batched MPPI / covo-offline steps refuse it; check_riccati): the same line search along the
     Riccati sweep's direction; riccati_feedback=True on top of it: the closed-loop candidates under the sweep's gains compete in that
-    line search (check_riccati_feedback)."""
+    line search (check_riccati_feedback).  plan_hold=m > 1 on top of riccati: every m-th step plans, the others apply the sweep's law to
+    the measured state (check_plan_hold); rows=True then also holds "hold": ep.read_hold()."""
     if controller not in ("covo-online", "mppi", "covo-offline"):
         raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi' or 'covo-offline'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
@@ -601,6 +623,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     check_riccati(riccati, "online" if controller == "covo-online" else f"the env-batched {controller} controller", refine=refine)
     check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None),
                            what=f"the env-batched {controller} controller")
+    check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None),
+                    what=f"the env-batched {controller} controller")
     if arbiter and update == "softmax":
         raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
@@ -616,7 +640,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     else:
         b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, sample_sigma=cp0.sample_sigma,
                                               mode="offline" if controller == "covo-offline" else "online", refine=refine,
-                                              riccati=riccati, riccati_feedback=riccati_feedback, **kw)
+                                              riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold, **kw)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     if controller == "covo-offline":  # (the table keys: children of the instances' control keys, which stay what they were)
@@ -640,6 +664,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     if rows:
         reads = {"elite": ("elitelog", ep.read_elite), "iters": ("iterlog", ep.read_iters), "sigma": ("sigmalog", ep.read_sigma),
                  "post": ("postlog", ep.read_post)}
+        reads["hold"] = ("holdlog", ep.read_hold)
         out += ({name: read() for name, (attr, read) in reads.items() if getattr(ep, attr) is not None},)
     return out if len(out) > 1 else out[0]
 
@@ -743,13 +768,15 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
                    iters=1, elite=None, sigma_period=1, compute_post_cov=False, sigma_adapt=0.0, refine=False,
-                   riccati=False, riccati_feedback=False):
+                   riccati=False, riccati_feedback=False, plan_hold=1):
     """quadrotor.py:670-752.  compute_diag, compute_plan, ess_min, compute_fan, update, iters, elite, sigma_period, compute_post_cov and
     sigma_adapt are the sampling controllers' step options -- what each does and what it adds to the controller's info dict:
     controllers/_options.py.  refine (covo-online only): the Newton line search behind every step -- a switch, not a step option
     (controllers/_options.py: check_refine).  riccati (mppi, covo-offline, covo-online): the same line search along the Riccati sweep's
     direction, which needs neither R nor Sigma (controllers/_options.py: check_riccati).  riccati_feedback (on top of riccati): the
-    closed-loop candidates under the sweep's gains compete in that line search (controllers/_options.py: check_riccati_feedback)."""
+    closed-loop candidates under the sweep's gains compete in that line search (controllers/_options.py: check_riccati_feedback).
+    plan_hold (on top of riccati): every plan_hold-th control step plans, the others track the last plan under the sweep's gains
+    (controllers/_options.py: check_plan_hold)."""
     opts = take(locals())
     import torch
     # ValueError before anything is built; the controller's own check, with N, follows
@@ -758,6 +785,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     check_refine(refine, what, sigma_period=sigma_period)
     check_riccati(riccati, what, refine=refine)
     check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
+    check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), what=what)
 
     def parse_sample_params(param_text):
         if not param_text:
@@ -784,7 +812,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info, riccati=riccati,
-                                          riccati_feedback=riccati_feedback, **opts), control_params
+                                          riccati_feedback=riccati_feedback, plan_hold=plan_hold, **opts), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -796,7 +824,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
             a_cov_offline=torch.zeros((H, env.action_dim, env.action_dim), dtype=torch.float32, device=device))
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group, compute_info=compute_info,
-                                          refine=refine, riccati=riccati, riccati_feedback=riccati_feedback, **opts), control_params
+                                          refine=refine, riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold,
+                                          **opts), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -910,6 +939,7 @@ class Args:
     refine: bool = False    # (not in quadjax) covo-online: every control step ends with a Newton line search on its committed mean
     riccati: bool = False   # (not in quadjax) mppi / covo: every control step ends with that line search along the Riccati sweep's direction
     riccati_feedback: bool = False  # (not in quadjax) on top of riccati: the closed-loop candidates under the sweep's gains compete too
+    plan_hold: int = 1      # (not in quadjax) on top of riccati: every m-th control step plans, the others track the plan under the sweep's gains; 1 = off
 
 
 def main(args: Args):
@@ -926,7 +956,8 @@ def main(args: Args):
                                                 update=args.update, iters=args.iters, elite=args.elite or None,
                                                 sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render,
                                                 sigma_adapt=args.sigma_adapt, refine=args.refine,
-                                                riccati=args.riccati, riccati_feedback=args.riccati_feedback)
+                                                riccati=args.riccati, riccati_feedback=args.riccati_feedback,
+                                                plan_hold=args.plan_hold)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -945,6 +976,8 @@ def _cli():
             ap.add_argument("--post-cov", "--post_cov", dest="post_cov", action="store_true")
         elif f == "riccati_feedback":
             ap.add_argument("--riccati-feedback", "--riccati_feedback", dest="riccati_feedback", action="store_true")
+        elif f == "plan_hold":
+            ap.add_argument("--plan-hold", "--plan_hold", dest="plan_hold", type=int, default=default)
         elif isinstance(default, bool):
             ap.add_argument(f"--{f}", action="store_true")
         elif f == "update":

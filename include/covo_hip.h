@@ -863,6 +863,57 @@ int covo_set_step_riccati_feedback(covo_handle_t h, float *fb_rows /* DEVICE [n_
  * with `value` between the sweep and the generator (once) -- how a test hands the line search closed-loop candidates that are not
  * valid. */
 int covo_debug_feedback_gain(covo_handle_t h, int32_t inst, int32_t index, double value);
+
+/* Plan hold: replan every m-th control step, track the last plan under the sweep's gains between (additive to ABI 10:
+ * COVO_HAS_PLAN_HOLD; a switch on top of covo_set_step_riccati; period 1, the default: off -- no launch, buffer or captured graph
+ * differs).  Steps are counted from covo_set_step_plan_hold; the age of a step is (count) mod m, one age for all instances of a batch.
+ * Age 0, a plan step: the control step as it is, every graph, attachment and output bit for bit.  Between the sweep and the line
+ *   search one launch latches, per instance, the mean b the sweep ran at (the line search overwrites it) and the int32 time word of the
+ *   state the step planned from; the sweep leaves K, kff, xb on the handle whether or not covo_set_step_riccati_feedback is on.
+ * Age j >= 1, a hold step: no sampling step, no arbiter, refinement or fan launch; ONE launch for all instances (csrc/plan_hold.hip)
+ *   computes, on the state the step would have read,
+ *     dx_c = (double)x[c] - xb_j[c], c = 0 .. 12;  v0_i = fma(alpha, kff_j[i], (double)b_j[i]);  v_i = v0_i, then
+ *     v_i = fma(K_j[i][c], dx_c, v_i) with c ascending;  u_i = (float)clip(v_i, -1, 1)
+ *   -- stage j of covo_feedback_rollout's law, with alpha read from the handle's Riccati row (entry 3: 0 for choice 0) -- and then, in
+ *   place, what the begin work of a step does: a_mean <- [a_mean[1:], a_mean[31]], MPPI's 32 blocks of a_cov likewise, finally
+ *   a_mean[0] <- u.  The plan trace's launch runs behind it with the hold step's own inputs; every other attachment keeps the plan
+ *   step's rows, the logs covo_set_episode_rows copies repeat them, logs written by their own launches leave the row unwritten.
+ * Decided on the device, reported in the hold row, none an error (flags):
+ *   bit 0  the sweep is flagged (its side row: no rung positive definite -- K = kff = 0 then anyway --, g or d not finite): u = clip(b_j)
+ *   bit 1  a v_i that is not finite (and bit 0 clear): all four components are clip(b_j)
+ *   bit 2  the state's time word differs from the latched one + j (a device auto-reset, an episode end): the feedback term is
+ *          dropped, u = (float)clip(v0)
+ *   hold row  float[COVO_HOLD_FLOATS] = {bits(int32 j), alpha, max_i |v_i - v0_i| (0 when the feedback term is not applied),
+ *             bits(int32 number of components whose applied command exceeds 1 in magnitude), bits(int32 flags), |dx_pos|_2,
+ *             bits(int32 the state's time word), 0}; a plan step writes {0, 0, 0, 0, 0, 0, bits(time), 0} from its latch.
+ * covo_set_step_plan_hold: rows = DEVICE float[n_inst][COVO_HOLD_FLOATS] (NULL with period 1); the age goes back to 0.
+ * covo_step_plan_age: the age the next step is scheduled at and the age the last one ran at (either pointer may be NULL).
+ * covo_plan_hold: the hold step alone, stateless, n_inst instances: state = DEVICE float[n_inst][32]; b = DEVICE float[n_inst][128];
+ *   K, kff, x as covo_riccati leaves them; side = covo_riccati's rows_out, DEVICE double[n_inst][4], or NULL (not flagged); alpha = DEVICE float, instance e's at alpha[e * alpha_stride]; stage in [0, H);
+ *   t_plan = DEVICE int32[n_inst] or NULL (no time check); a_mean = DEVICE float[n_inst][128] or NULL and a_cov = DEVICE
+ *   float[n_inst][H][4][4] or NULL, both in/out and 16-byte aligned; u_out = DEVICE float[n_inst][4]; rows_out = DEVICE
+ *   float[n_inst][COVO_HOLD_FLOATS].
+ * covo_set_episode_hold_log: log = DEVICE float[n_inst][stride][COVO_HOLD_FLOATS] (NULL: off); the hold launch, and the latch on
+ *   plan steps, of an episode driver write instance e's row of step `index` to log[e][index] themselves.
+ * Refused at the step, before any launch: period > 1 without covo_set_step_riccati; together with a Sigma period; drag / mixed (the
+ *   16-state plants); more instances than rows; a_mean / a_mean_in / a_cov not 16-byte aligned; and whatever the Riccati refinement
+ *   refuses (the env-batched MPPI / covo-offline steps, sample-sharded steps). */
+#define COVO_HAS_PLAN_HOLD 1
+#define COVO_HOLD_FLOATS 8
+#define COVO_MAX_PLAN_HOLD 16
+int covo_set_step_plan_hold(covo_handle_t h, int32_t period, float *rows /* DEVICE [n_inst][COVO_HOLD_FLOATS]; NULL with period 1 */,
+                            int32_t n_inst);
+int covo_step_plan_age(covo_handle_t h, int32_t *next_age, int32_t *last_age);
+int covo_plan_hold(covo_handle_t h, const float *state, const float *b, const double *K, const double *kff, const double *x,
+                   const double *side /* DEVICE [n_inst][4] or NULL */, const float *alpha /* DEVICE, one float per instance */, int32_t alpha_stride /* in floats */, int32_t stage,
+                   const int32_t *t_plan /* DEVICE int32 per instance, or NULL: no time check */, float *a_mean /* in/out, nullable */,
+                   float *a_cov /* in/out, nullable */, float *u_out, float *rows_out, int32_t n_inst, void *stream);
+int covo_set_episode_hold_log(covo_handle_t h, float *log, int32_t stride);
+/* Test hook: what the LAST plan step of this handle latched for its first n_inst instances, device -> device: b_out = DEVICE
+ * float[n_inst][128], t_out = DEVICE int32[n_inst], and the sweep's K_out / kff_out / x_out = DEVICE double[n_inst][H][4][16] /
+ * [n_inst][H][4] / [n_inst][H][16] -- what the hold steps that follow apply. */
+int covo_debug_plan_latch(covo_handle_t h, int32_t n_inst, float *b_out, int32_t *t_out, double *K_out, double *kff_out, double *x_out,
+                          void *stream);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

@@ -17,20 +17,25 @@ name = sys.argv[1]
 # same line search along the Riccati sweep's direction (csrc/riccati.hip); again, compare with the same call without the flag
 # python scripts/eval_seeds.py mppi --riccati --riccati-feedback: the closed-loop candidates under the sweep's gains compete in that line
 # search (csrc/feedback_rollout.hip); compare with the same call without the last flag
+# python scripts/eval_seeds.py mppi --riccati --plan-hold 4: every 4th control step plans, the three between apply the sweep's law to the
+# measured state (csrc/plan_hold.hip); every seed's line also carries the share of hold steps whose plan belonged to another trajectory
+# (flag bit 2: a reset in between) and the share with a clipped component; compare the errors with --riccati alone
 rest = sys.argv[2:]
 refine = "--refine" in rest
 riccati = "--riccati" in rest
 feedback = "--riccati-feedback" in rest
 rest = [r for r in rest if r not in ("--refine", "--riccati", "--riccati-feedback")]
-for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_adapt")):
+for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_adapt"), ("--plan-hold", "plan_hold")):
     while flag in rest:
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
 opts = {k: (float(v) if k in ("sigma_adapt", "ess_min") else int(v)) for k, v in (arg.split("=") for arg in rest)}
+plan_hold = opts.pop("plan_hold", 1)
 assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"}, opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
-ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, riccati=riccati, riccati_feedback=feedback, **opts)
+ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, riccati=riccati, riccati_feedback=feedback, plan_hold=plan_hold,
+                            **opts)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
@@ -45,6 +50,12 @@ def rows_of(ep):
     if ep.iterlog is not None:
         it = ep.read_iters()
         rows["improved"] = rows.get("improved", 0) + int((it[:, -1] < it[:, 0]).sum())
+    if ep.holdlog is not None:
+        hold = ep.read_hold()
+        held = hold["age"] > 0
+        rows["held"] = rows.get("held", 0) + int(held.sum())
+        rows["stale"] = rows.get("stale", 0) + int(((hold["flags"] & 4) != 0)[held].sum())
+        rows["clipped"] = rows.get("clipped", 0) + int((hold["clipped"] > 0)[held].sum())
     rows["steps"] = rows.get("steps", 0) + ep.n_steps
 
 
@@ -53,8 +64,11 @@ for seed in range(1, 13):
     errs = Q.eval_env_device(env, controller=ctrl, total_steps=300*4*10, seed=seed, verbose=False, on_episode=rows_of if core else None)
     allerr.append(errs)
     n = max(rows.get("steps", 0), 1)
+    nh = max(rows.get("held", 0), 1)
     extra = "".join(text % (rows[k] / d) for k, text, d in (("floor", "  lam_eff>lam: %.3f", n), ("fallback", "  adapt fallbacks: %d", 1),
-                                                           ("improved", "  last pass beat first: %.3f", n)) if k in rows)
+                                                           ("improved", "  last pass beat first: %.3f", n),
+                                                           ("stale", "  hold steps on another trajectory's plan: %.3f", nh),
+                                                           ("clipped", "  hold steps with a clipped component: %.3f", nh)) if k in rows)
     print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()) + extra,
           flush=True)
 allerr = np.concatenate(allerr)
