@@ -79,6 +79,11 @@ COVO_HOLD_FLOATS = 8
 COVO_MAX_PLAN_HOLD = 16  # plan_hold= of the controllers: every m-th control step plans, the others hold
 HOLD_FIELDS = ("age", "alpha", "gain", "clipped", "flags", "dpos", "time")
 HOLD_FLAG_SWEEP, HOLD_FLAG_NOT_FINITE, HOLD_FLAG_TIME = 1, 2, 4
+COVO_HAS_ILQR = 1  # the "ilqr" controller (COVO_MODE_ILQR, covo_set_step_ilqr): Riccati sweeps and the line search, nothing sampled
+# a summary row: {row_0.cost_base, row_{k-1}.cost_chosen, bits(int32 iterations with choice != 0), bits(int32 first j with choice 0; k:
+# none), bits(int32 iterations with choice > 16), bits(OR of the rows' flag words), |g|_2 of the last iteration, 0}
+COVO_ILQR_FLOATS = 8
+ILQR_FIELDS = ("cost_first", "cost", "moved", "fixed_at", "closed", "flags", "grad_norm")
 # the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
 COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
 COVO_EPLOG_KINDS = 6
@@ -145,6 +150,7 @@ TABLE_DISTURB_KINDS = (2, 3, 4, 5)                            # models that need
 DISTURB_KEYS_SHARED, DISTURB_KEYS_HESSIAN, DISTURB_KEYS_NOMINAL = 0, 1, 2
 COVO_MAX_ENVS = 64
 MODE_MPPI, MODE_COVO_ONLINE, MODE_COVO_OFFLINE = 0, 1, 2
+MODE_ILQR = 3
 COVO_FLAG_NO_GRAPH = 2
 COVO_FLAG_SHARED_DEVICE = 4
 COVO_FLAG_PROPAGATE_NAN = 8
@@ -263,6 +269,9 @@ _SIGS = {
     "covo_plan_hold": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, _P]),
     "covo_set_episode_hold_log": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_plan_latch": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
+    # the iLQR controller's per-iteration logs (covo_hip.h: COVO_HAS_ILQR)
+    "covo_set_step_ilqr": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    "covo_debug_ilqr_costs": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),

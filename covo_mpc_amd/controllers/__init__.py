@@ -4,4 +4,5 @@ from .random import RandomController  # noqa: F401
 from .pid import PIDController, PIDParams  # noqa: F401
 from .mppi import MPPIController, MPPIParams  # noqa: F401
 from .covo import CoVOController, CoVOParams  # noqa: F401
-from .batched import BatchedCoVOController, BatchedMPPIController  # noqa: F401
+from .batched import BatchedCoVOController, BatchedILQRController, BatchedMPPIController  # noqa: F401
+from .ilqr import ILQRController, ILQRParams  # noqa: F401

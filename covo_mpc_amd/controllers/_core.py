@@ -598,6 +598,46 @@ class SamplingCore:
         return {"plan_age": self._plan_ages()[1], "hold_gain": row[2], "hold_clipped": row[3:4].view(i32)[0],
                 "hold_flags": row[4:5].view(i32)[0], "hold_alpha": row[1]}
 
+    def attach_ilqr(self):
+        """The per-iteration logs of an iLQR controller's core (covo_set_step_ilqr; the controllers of controllers/ilqr.py and
+        BatchedILQRController call this once, behind a constructor that attached riccati's rows and set iters): self.ilqr_rows /
+        self.ilqr_feedback_rows [rows, iters, 8] -- views of [rows, COVO_MAX_STEP_ITERS, 8] buffers: slot j holds iteration j's Riccati
+        / feedback row -- and self.ilqr_summary [rows, 8] = {row_0.cost_base, row_{k-1}.cost_chosen, bits(iterations with choice != 0),
+        bits(first j with choice 0; k: none), bits(iterations with choice > 16), bits(OR of the flag words), |g|_2 of the last
+        iteration, 0}.  The iteration log of iters= (which only carries the count to the C side here) leaves step_info()."""
+        torch = self.torch
+        assert self.riccati_rows is not None, "attach_ilqr: the core was built without riccati"
+        full = (self._rows, _lib.COVO_MAX_STEP_ITERS, _lib.COVO_RICCATI_FLOATS)
+        self._ilqr_rows_full = torch.zeros(full, dtype=torch.float32, device=self.device)
+        self._ilqr_fb_full = torch.zeros(full, dtype=torch.float32, device=self.device)
+        self.ilqr_rows = self._ilqr_rows_full[:, :self.iters]
+        self.ilqr_feedback_rows = self._ilqr_fb_full[:, :self.iters]
+        self.ilqr_summary = torch.zeros((self._rows, _lib.COVO_ILQR_FLOATS), dtype=torch.float32, device=self.device)
+        check(self.lib.covo_set_step_ilqr(self.h, ptr(self._ilqr_rows_full), ptr(self._ilqr_fb_full), ptr(self.ilqr_summary), self._rows),
+              "covo_set_step_ilqr")
+        self._infos = [f for f in self._infos if f != self.iter_info] + [self.ilqr_info]
+
+    def ilqr_costs(self):
+        """Test hook (covo_debug_ilqr_costs): from now on every iteration's line search also stores its candidates' costs -> the float32
+        device tensor [rows, COVO_MAX_STEP_ITERS, 33] they land in (slot j: iteration j; 17 entries without riccati_feedback)."""
+        if getattr(self, "_ilqr_costs", None) is None:
+            self._ilqr_costs = self.torch.zeros((self._rows, _lib.COVO_MAX_STEP_ITERS, _lib.COVO_FEEDBACK_CANDIDATES),
+                                                dtype=self.torch.float32, device=self.device)
+            check(self.lib.covo_debug_ilqr_costs(self.h, ptr(self._ilqr_costs), self._rows), "covo_debug_ilqr_costs")
+        return self._ilqr_costs
+
+    def ilqr_info(self) -> dict:
+        """{"ilqr_rows" [iters, 8], "ilqr_feedback_rows" [iters, 8], "ilqr_cost_first" (the cost of the shifted mean), "ilqr_cost" (of
+        the committed one), "ilqr_moved" / "ilqr_fixed_at" / "ilqr_closed" (0-d int32: iterations with choice != 0, the first iteration
+        with choice 0 or iters, iterations that committed a closed-loop candidate)} of the last plan step as views of the core's
+        buffers (no sync, no copy); {} on a core without attach_ilqr()."""
+        if getattr(self, "ilqr_summary", None) is None:
+            return {}
+        row, i32 = self.ilqr_summary[0], self.torch.int32
+        return {"ilqr_rows": self.ilqr_rows[0], "ilqr_feedback_rows": self.ilqr_feedback_rows[0], "ilqr_cost_first": row[0],
+                "ilqr_cost": row[1], "ilqr_moved": row[2:3].view(i32)[0], "ilqr_fixed_at": row[3:4].view(i32)[0],
+                "ilqr_closed": row[4:5].view(i32)[0]}
+
     def plan_latch(self, n_envs=1):
         """What the last plan step latched for its first n_envs instances (covo_debug_plan_latch; copies): {"b" float32 [n, 128] the mean
         its sweep ran at, "t" int32 [n] the time word it planned from, "K" [n, 32, 4, 16], "kff" [n, 32, 4], "x" [n, 32, 16] float64

@@ -333,3 +333,51 @@ def check_plan_hold(plan_hold, *, riccati, sigma_period=1, disturb_type=None, wh
                                   "a state of the sweep, and the hold step carries the 13-state plants only "
                                   "(covo_set_step_plan_hold refuses them at the step)")
     return m
+
+
+def check_ilqr(iters=2, *, riccati_feedback=None, plan_hold=1, disturb_type=None, refine=False, process_group=None,
+               what="the iLQR controller", **raw):
+    """The keywords of the sampling-free controllers (ILQRController, BatchedILQRController, get_controller(env, "ilqr", ...),
+    eval_env_batched(controller="ilqr")) -> (iters, riccati_feedback, plan_hold), checked and resolved.  The C side's counterpart is
+    check_ilqr_step (csrc/capi.hip).
+
+    One control step is b_0 = shift(a_mean), then iters times the Riccati line search of riccati= (with riccati_feedback: over 33
+    candidates, the closed-loop forward pass of DDP / iLQR among them) on the step's one state and raw key, a_mean <- b_iters: nothing is
+    sampled (COVO_MODE_ILQR, csrc/ilqr.hip).  info["ilqr_rows"] [iters, 8] / ["ilqr_feedback_rows"] [iters, 8] (every iteration's
+    Riccati and feedback row) / ["ilqr_cost_first"] / ["ilqr_cost"] / ["ilqr_moved"] / ["ilqr_fixed_at"] / ["ilqr_closed"], next to the
+    riccati_* keys (the last iteration) and, under plan_hold, plan_age / hold_*.  **raw: the step options (STEP_OPTION_DEFAULTS); only
+    compute_plan means anything here, and iters is this function's own first argument.
+
+    The objections, in a fixed order: iters anything but an integer in [1, COVO_MAX_STEP_ITERS] (ValueError); a sampling step option
+    away from its default -- compute_diag, ess_min, compute_fan, update, elite, sigma_period, compute_post_cov, sigma_adapt, in that
+    order: each acts on samples, weights or a Sigma, and there are none (ValueError naming it); refine=True -- its direction needs a
+    covo-online step's Sigma (ValueError); a process_group -- there are no samples to shard (NotImplementedError); riccati_feedback
+    anything but None / True / False (ValueError), True with disturb_type drag / mixed (check_riccati_feedback's NotImplementedError);
+    then whatever check_plan_hold objects to.  riccati_feedback=None resolves to True on the 13-state plants and to False on drag /
+    mixed, whose closed-loop candidates the generator refuses; an explicit False is honoured."""
+    unknown = set(raw) - set(STEP_OPTION_DEFAULTS)
+    if unknown:
+        raise TypeError(f"check_ilqr: unknown step options {sorted(unknown)}")
+    k = _lib.check_iters(iters)
+    for name, default in STEP_OPTION_DEFAULTS.items():
+        if name in ("iters", "compute_plan") or name not in raw:
+            continue
+        v = raw[name]
+        off = (not v) if default is None else v == default  # (ess_min / compute_fan / elite: None, False and 0 all mean off)
+        if not off:
+            raise ValueError(f"{name}={v!r} with {what}: a step option of the sampling controllers -- it acts on samples, weights or a "
+                             "Sigma, and an iLQR step has none; leave it at its default")
+    if not isinstance(refine, bool):
+        raise ValueError(f"refine={refine!r} (True | False)")
+    if refine:
+        raise ValueError(f"refine=True with {what}: the Newton refinement's direction needs the Sigma of a covo-online step, which an "
+                         "iLQR step does not compute (its iterations are the Riccati line search already); give refine=False")
+    if process_group is not None:
+        raise NotImplementedError(f"a process_group with {what}: sample-sharded ranks split a step's samples, and an iLQR step has "
+                                  "none; run it on one rank")
+    if riccati_feedback is None:
+        feedback = disturb_type not in ("drag", "mixed")
+    else:
+        feedback = check_riccati_feedback(riccati_feedback, riccati=True, disturb_type=disturb_type, what=what)
+    m = check_plan_hold(plan_hold, riccati=True, disturb_type=disturb_type, what=what)
+    return k, feedback, m

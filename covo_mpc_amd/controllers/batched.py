@@ -283,3 +283,52 @@ class BatchedMPPIController(BatchedCoVOController):
         torch = self.core.torch
         blk = torch.diag(torch.as_tensor(sig, dtype=torch.float32, device=self.core.device) ** 2)
         self.a_cov.copy_(blk.expand(self.E, COVO_H, 4, 4))
+
+
+class BatchedILQRController(BatchedCoVOController):
+    """iLQR (controllers/ilqr.py) for E instances: the same methods as BatchedCoVOController -- set_instances / bind_episode, __call__
+    (also as .step), run_episode, reset -- through covo_mpc_step_batched_mode / covo_run_episode_batched_mode in COVO_MODE_ILQR.  Every
+    iteration's launches take the instance as a grid dimension; instance e's result is bit-identical to ILQRController's on that
+    instance alone (tests/test_gpu_ilqr.py).  After a call: .ilqr_rows / .ilqr_feedback_rows [E, iters, 8] (every iteration's Riccati /
+    feedback row), .ilqr_summary [E, 8] (SamplingCore.attach_ilqr), .riccati / .riccati_feedback (the last iteration's rows),
+    .plan_hold_rows and .plan (None for what is off)."""
+    MODE = _lib.MODE_ILQR
+
+    def __init__(self, env, n_envs: int, H: int, *, iters: int = 2, riccati_feedback=None, plan_hold: int = 1,
+                 compute_plan: bool = False, discount: float = 1.0, a_mean_init=None, device=None):
+        from .ilqr import ILQR_N, build_ilqr_core
+        from ._options import check_ilqr
+        self.iters, self.riccati_feedback_on, self.plan_hold = check_ilqr(
+            iters, riccati_feedback=riccati_feedback, plan_hold=plan_hold, disturb_type=getattr(env, "disturb_type", None),
+            compute_plan=compute_plan, what="the env-batched iLQR controller")
+        if not 0 < n_envs <= _lib.COVO_MAX_ENVS:
+            raise ValueError(f"n_envs={n_envs} outside (0, {_lib.COVO_MAX_ENVS}]")
+        self.mode, self.staged = self.MODE, False
+        self.env, self.E, self.N, self.H = env, int(n_envs), ILQR_N, int(H)
+        self.gamma_mean, self.sample_sigma, self.gamma_sigma = 1.0, 0.5, 0.0  # (fields of the argument block an iLQR step never reads)
+        self.rollover_terminate = not getattr(env, "disable_rollover_terminate", True)
+        # (eager: the iterations are eager launches; nothing of an iLQR step is captured)
+        self.core = build_ilqr_core(self.E, H, discount, iters=self.iters, riccati_feedback=self.riccati_feedback_on,
+                                    plan_hold=self.plan_hold, compute_plan=bool(compute_plan), device=device, use_graph=False)
+        for mine, cores in CORE_BUFFERS:
+            setattr(self, mine, getattr(self.core, cores))
+        self.ilqr_rows, self.ilqr_feedback_rows, self.ilqr_summary = (self.core.ilqr_rows, self.core.ilqr_feedback_rows,
+                                                                      self.core.ilqr_summary)
+        torch = self.core.torch
+        f32 = dict(dtype=torch.float32, device=self.core.device)
+        E, n = self.E, self.N
+        self.a_mean = torch.zeros((E, COVO_NA), **f32)
+        if a_mean_init is not None:
+            self.a_mean.copy_(torch.as_tensor(a_mean_init, **f32).reshape(1, COVO_NA).expand(E, COVO_NA))
+        # the sample buffers of the argument block, at the smallest size it takes: never launched on
+        self.a_cov = torch.zeros((E, 1), **f32)
+        self.a_cov_offline = self.a_chol_offline = None
+        self._a = torch.empty((E, COVO_H, n, 4), **f32)
+        self._cost = torch.empty((E, n), **f32)
+        self._groupmin = torch.empty((E, (n + 63) // 64), **f32)
+        self._states = torch.zeros((E, _lib.COVO_STATE_FLOATS), **f32)
+        self._traj = self._params = self._args = None
+
+    def step(self, noisy_states, rng_acts):
+        """One control step of every instance (= __call__) -> first actions [E, 4] (view of a_mean)."""
+        return self(noisy_states, rng_acts)

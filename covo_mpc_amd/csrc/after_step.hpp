@@ -183,6 +183,7 @@ struct ArgBlockCache {
 struct AfterState {
     ArgBlockCache arbiter, plan, fan, refine, feedback;
     ArgBlockCache hold, hold_primitive, latch;  // plan_hold.hip: a batched hold step's blocks, covo_plan_hold's, a batched plan step's latch
+    ArgBlockCache ilqr;                         // ilqr.hip: a batched iLQR step's tally blocks
     float *nominal = nullptr;  // [COVO_MAX_ENVS][128] the update arbiter's nominals of the env-batched fused step
 };
 static inline AfterState *after_state(covo_ctx *h)

@@ -1196,6 +1196,54 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
     return 0;
 }
 
+// ---- what a step in COVO_MODE_ILQR checks ahead of check_step_attachments, for every entry point alike: the sweep it consists of is
+// attached, and nothing that belongs to a sampling step is.  The order is fixed: the sharded step, the sweep, the other refinement,
+// then the sampling attachments in check_step_attachments' order, the raw key, the rows of the logs
+static int check_ilqr_step(const covo_ctx *h, int n_inst, bool sharded, int derive_keys, const char *what)
+{
+    REQUIRE(!sharded,
+            "%s: an iLQR step (COVO_MODE_ILQR) is not available for sample-sharded steps (partial_out != NULL): it has no samples to "
+            "shard; run it on one rank", what);
+    REQUIRE(covo_riccati_on(h),
+            "%s: an iLQR step (COVO_MODE_ILQR) without the Riccati refinement (covo_set_step_riccati): its iterations are that sweep "
+            "and its line search; attach the rows", what);
+    REQUIRE(!covo_refine_on(h),
+            "%s: an iLQR step (COVO_MODE_ILQR) together with the Newton refinement (covo_set_step_refine): its direction needs the "
+            "Sigma of a covo-online step, which an iLQR step does not compute; detach it", what);
+    REQUIRE(covo_diag_target(h) == nullptr,
+            "%s: an iLQR step (COVO_MODE_ILQR) together with sampling diagnostics (covo_set_step_diag / covo_set_episode_diag_log): "
+            "nothing is sampled; detach the buffer", what);
+    REQUIRE(!covo_fan_on(h),
+            "%s: an iLQR step (COVO_MODE_ILQR) together with the sample fan (covo_set_step_fan / covo_set_episode_fan): nothing is "
+            "sampled; detach the buffer", what);
+    REQUIRE(!covo_arb_on(h),
+            "%s: an iLQR step (COVO_MODE_ILQR) together with the update arbiter (covo_set_step_arbiter): there is no softmax mean and "
+            "no best sample to arbitrate; detach it", what);
+    REQUIRE(covo_lam_target(h) == nullptr,
+            "%s: an iLQR step (COVO_MODE_ILQR) together with the ESS floor (covo_set_step_ess_floor, ess_min=%g): there are no "
+            "weights; turn it off (ess_min = 0)", what, (double)h->ess_min);
+    REQUIRE(covo_elite_target(h) == nullptr,
+            "%s: an iLQR step (COVO_MODE_ILQR) together with the elite-set update (covo_set_step_elite, K=%d): there are no samples "
+            "to select from; turn it off (K = 0)", what, h->elite_K);
+    REQUIRE(covo_sigma_period(h) == 1,
+            "%s: an iLQR step (COVO_MODE_ILQR) together with a Sigma period (covo_set_step_sigma_period, period=%d): it computes no "
+            "Sigma; set period = 1", what, covo_sigma_period(h));
+    REQUIRE(!covo_post_cov_on(h),
+            "%s: an iLQR step (COVO_MODE_ILQR) together with the posterior covariance (covo_set_step_post_cov): nothing is sampled; "
+            "detach the buffer", what);
+    REQUIRE(!covo_sigma_adapt_on(h),
+            "%s: an iLQR step (COVO_MODE_ILQR) together with Sigma adapt (covo_set_step_sigma_adapt, gamma=%g): it computes no Sigma; "
+            "turn it off (gamma = 0)", what, (double)h->adapt_gamma);
+    REQUIRE(derive_keys == 1,
+            "%s: an iLQR step (COVO_MODE_ILQR) needs derive_keys = 1 (its disturbance inputs are derived from the raw controller key "
+            "on the device)", what);
+    const bool logs = h->ilqr_rows != nullptr || h->ilqr_fb_rows != nullptr || h->ilqr_summary != nullptr;
+    REQUIRE(!logs || n_inst <= h->ilqr_n, "%s: %d instances, the iLQR logs (covo_set_step_ilqr) have n_inst=%d", what, n_inst, h->ilqr_n);
+    REQUIRE(h->ilqr_costs == nullptr || n_inst <= h->ilqr_costs_n, "%s: %d instances, the iLQR cost buffer (covo_debug_ilqr_costs) has "
+            "n_inst=%d", what, n_inst, h->ilqr_costs_n);
+    return 0;
+}
+
 // the episode hold log (covo_set_episode_hold_log) of a driver that writes rows [first_row, first_row + n_steps)
 static int check_hold_log(const covo_ctx *h, int first_row, int n_steps, const char *what)
 {
@@ -1567,6 +1615,28 @@ int covo_set_step_plan_hold(covo_handle_t h, int32_t period, float *rows, int32_
     return 0;
 }
 
+// ---- the per-iteration logs of the iLQR steps (ilqr.hip).  Their launches are eager and follow the step: no epoch bump
+int covo_set_step_ilqr(covo_handle_t h, float *rows, float *fb_rows, float *summary, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_ilqr: null handle");
+    const bool on = rows != nullptr || fb_rows != nullptr || summary != nullptr;
+    REQUIRE(!on || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_ilqr: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    h->ilqr_rows = rows;
+    h->ilqr_fb_rows = fb_rows;
+    h->ilqr_summary = summary;
+    h->ilqr_n = on ? n_inst : 0;
+    return 0;
+}
+
+int covo_debug_ilqr_costs(covo_handle_t h, float *costs, int32_t n_inst)
+{
+    REQUIRE(h, "covo_debug_ilqr_costs: null handle");
+    REQUIRE(costs == nullptr || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_debug_ilqr_costs: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    h->ilqr_costs = costs;
+    h->ilqr_costs_n = costs ? n_inst : 0;
+    return 0;
+}
+
 int covo_step_plan_age(covo_handle_t h, int32_t *next_age, int32_t *last_age)
 {
     REQUIRE(h, "covo_step_plan_age: null handle");
@@ -1693,7 +1763,7 @@ static void host_philox_split(const uint32_t key[2], uint32_t i, uint32_t child[
 // have passed
 static int check_single_step(const covo_ctx *h, const covo_env_params *params, const covo_step_args *args, const char *what)
 {
-    REQUIRE(args->mode >= 0 && args->mode <= 2, "%s: mode=%d", what, args->mode);
+    REQUIRE(args->mode >= 0 && args->mode <= COVO_MODE_ILQR, "%s: mode=%d", what, args->mode);
     REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "%s: n_samples=%d outside (0, %d]", what, args->n_samples,
             h->cfg.n_local);
     REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin && args->T > 0,
@@ -1707,6 +1777,8 @@ static int check_single_step(const covo_ctx *h, const covo_env_params *params, c
             "disturbance tables are derived from the raw controller key on the device)", what, params->disturb_kind);
     REQUIRE(h->plan_hold <= 1 || (((uintptr_t)args->a_mean | (uintptr_t)args->a_mean_in | (uintptr_t)args->a_cov) & 15) == 0,
             "%s: a_mean, a_mean_in and a_cov must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
+    if (args->mode == COVO_MODE_ILQR)
+        if (int rc = check_ilqr_step(h, 1, args->partial_out != nullptr, args->derive_keys, what)) return rc;
     return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, params, what);
 }
 
@@ -1716,13 +1788,15 @@ static int check_single_step(const covo_ctx *h, const covo_env_params *params, c
 static int single_step_at_age(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
                               const float *f_shared, int age, int row, hipStream_t s)
 {
+    if (age == 0 && args->mode == COVO_MODE_ILQR) return covo_ilqr_step_impl(h, params, args, key0, key1, s);  // (its begin work)
     if (age == 0) return covo_step_impl(h, params, args, key0, key1, f_shared, s);
     return covo_hold_step(h, args, age, row, s);
 }
 static int batched_step_at_age(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *norm, bool online,
-                               const covo_env_params *params, const uint32_t *keys, int age, int row, hipStream_t s)
+                               const covo_env_params *params, const uint32_t *keys, int age, int row, hipStream_t s, bool ilqr = false)
 {
-    if (age != 0) return covo_hold_step_batched(h, args, age, row, s);  // (covo-online only: the others refuse the Riccati refinement)
+    if (age != 0) return covo_hold_step_batched(h, args, age, row, s);  // (covo-online and iLQR only: the others refuse the Riccati refinement)
+    if (ilqr) return covo_ilqr_step_batched_impl(h, args, params, keys, s);  // (its begin work)
     return online                   ? covo_step_batched_impl(h, args, params, keys, s)
            : covo_batched_staged(h) ? covo_step_batched_staged_impl(h, norm, params, keys, s)
                                     : covo_step_batched_small_impl(h, norm, params, keys, s);
@@ -1835,13 +1909,19 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
     REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "%s: n_samples=%d outside (0, %d]", what, args->n_samples,
             h->cfg.n_local);
     const int mode = m ? m->mode : COVO_MODE_COVO_ONLINE;
-    REQUIRE(mode == COVO_MODE_MPPI || mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_COVO_OFFLINE, "%s: mode=%d is not a COVO_MODE_*",
-            what, mode);
+    REQUIRE(mode == COVO_MODE_MPPI || mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_COVO_OFFLINE || mode == COVO_MODE_ILQR,
+            "%s: mode=%d is not a COVO_MODE_*", what, mode);
     REQUIRE(args->states && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost &&
                 (args->groupmin || mode != COVO_MODE_COVO_ONLINE) && args->T > 0,
             "%s: null buffer", what);
     int rc = check_batch_models(params, args->n_envs, episode, what);
     if (rc) return rc;
+    if (mode == COVO_MODE_ILQR) {  // nothing of the sampling batches' lists applies: its own, then the attachments'
+        if ((rc = check_ilqr_step(h, args->n_envs, false, 1, what))) return rc;
+        REQUIRE(h->plan_hold <= 1 || ((uintptr_t)args->a_mean & 15) == 0,
+                "%s: a_mean must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
+        return check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, params, what);
+    }
     // covo_set_step_batched_staged: the MPPI / covo-offline batch runs its staged launch sequence, which takes what the fused launch
     // refuses below and has its own short list further down
     const bool staged = mode != COVO_MODE_COVO_ONLINE && covo_batched_staged(h);
@@ -1915,6 +1995,7 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     int rc = check_batch_step(h, args, m, params, true, what, &norm);
     if (rc) return rc;
     const bool online = !m || m->mode == COVO_MODE_COVO_ONLINE;
+    const bool ilqr = m && m->mode == COVO_MODE_ILQR;
     REQUIRE(log == nullptr || (log_index >= 0 && log_index + n_steps <= log_stride),
             "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
     if ((rc = check_episode_logs(h, log_index, n_steps, what)) || (rc = check_hold_log(h, log_index, n_steps, what))) return rc;
@@ -1933,9 +2014,9 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             host_philox_split(nrng, 0u, &next[2 * e]);
         }
         const int age = covo_plan_step_age(h, E);  // (the batch shares one age)
-        if ((rc = batched_step_at_age(h, args, &norm, online, params, act_keys, age, log_index + t, s))) return rc;
+        if ((rc = batched_step_at_age(h, args, &norm, online, params, act_keys, age, log_index + t, s, ilqr))) return rc;
         auto frame = [&](int row) {
-            return covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : norm.mode, params, states_true, row, s, false,
+            return covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : (ilqr ? COVO_MODE_ILQR : norm.mode), params, states_true, row, s, false,
                                            age != 0 ? act_keys : nullptr);
         };
         if ((rc = episode_step_tail(h, frame, E, log_index + t, s))) return rc;
@@ -2000,7 +2081,8 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     int rc = check_batch_step(h, &args->base, args, params, false, "covo_mpc_step_batched_mode", &norm);
     if (rc) return rc;
     const int age = covo_plan_step_age(h, args->base.n_envs);
-    if ((rc = batched_step_at_age(h, &args->base, &norm, args->mode == COVO_MODE_COVO_ONLINE, params, keys, age, -1, (hipStream_t)stream)))
+    if ((rc = batched_step_at_age(h, &args->base, &norm, args->mode == COVO_MODE_COVO_ONLINE, params, keys, age, -1, (hipStream_t)stream,
+                                  args->mode == COVO_MODE_ILQR)))
         return rc;
     if ((rc = covo_plan_after_batched(h, &args->base, args->mode, params, nullptr, -1, (hipStream_t)stream, false, age != 0 ? keys : nullptr)))
         return rc;
@@ -2012,6 +2094,8 @@ int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const c
                          int32_t hess_mask, int32_t sigma_stages, int32_t reps, float *us_out, void *stream)
 {
     REQUIRE(h && params && args && us_out && reps > 0, "covo_debug_time_step: bad argument");
+    REQUIRE(args->mode != COVO_MODE_ILQR, "covo_debug_time_step: the phase masks name the launches of a sampling step; an iLQR step "
+            "(COVO_MODE_ILQR) has none of them");
     REQUIRE(covo_step_iters(h) == 1, "covo_debug_time_step: the phase timers replay ONE pass; iterations per step are on "
             "(covo_set_step_iters, iters=%d): set iters = 1", covo_step_iters(h));
     return covo_debug_time_step_impl(h, params, args, step_mask, hess_mask, sigma_stages, reps, us_out, (hipStream_t)stream);  // (a refresh step's launches)

@@ -132,6 +132,14 @@ struct covo_ctx {
     float *hold_log;          // caller's [n_inst][hold_log_stride][COVO_HOLD_FLOATS] episode log (covo_set_episode_hold_log), or null
     int hold_log_stride;
     uint32_t *hold_keys;      // [COVO_MAX_ENVS][12]: a hold step's raw keys for its plan trace, laid out like a step's scalars
+    // the per-iteration logs of the iLQR steps (covo_set_step_ilqr; ilqr.hip); all null: off
+    float *ilqr_rows;         // caller's [ilqr_n][COVO_MAX_STEP_ITERS][COVO_RICCATI_FLOATS]: slot j = iteration j's Riccati row
+    float *ilqr_fb_rows;      // caller's [ilqr_n][COVO_MAX_STEP_ITERS][COVO_FEEDBACK_FLOATS]: ... and its feedback row
+    float *ilqr_summary;      // caller's [ilqr_n][COVO_ILQR_FLOATS]
+    int ilqr_n;
+    float *ilqr_costs;        // test hook (covo_debug_ilqr_costs): caller's [ilqr_costs_n][COVO_MAX_STEP_ITERS][COVO_FEEDBACK_CANDIDATES], or null
+    int ilqr_costs_n;
+    int ilqr_slot;            // 1 + the iteration an iLQR step is enqueueing; 0 outside one (riccati_after then has no cost slot)
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -786,6 +794,21 @@ struct LatchDesc {
 };
 int launch_plan_hold(covo_ctx *h, const HoldDesc *d, int n_inst, bool batched, bool primitive, int stage, int log_index, hipStream_t s);
 int launch_plan_latch(covo_ctx *h, const LatchDesc *d, int n_inst, bool batched, int log_index, hipStream_t s);
+// ilqr.hip: what frames the iterations of an iLQR step (COVO_MODE_ILQR).  IlqrTallyDesc: one instance of the tally launch behind an
+// iteration's line search, the kernel's argument block as it stands (all pointers; what is null is null for every instance)
+struct IlqrTallyDesc {
+    const float *row;         // [COVO_RICCATI_FLOATS] the handle's Riccati row of this instance: the iteration that has just run
+    const float *fb_row;      // [COVO_FEEDBACK_FLOATS] ... and its feedback row, or null
+    float *rows_log;          // [COVO_MAX_STEP_ITERS][COVO_RICCATI_FLOATS] or null
+    float *fb_log;            // [COVO_MAX_STEP_ITERS][COVO_FEEDBACK_FLOATS] or null
+    float *summary;           // [COVO_ILQR_FLOATS] or null
+};
+int launch_ilqr_begin(const float *a_mean_src, float *a_mean, uint32_t *dyn, const uint32_t *keys, int n_inst, int derive_keys,
+                      float shared_noise_scale, hipStream_t s);
+int launch_ilqr_tally(covo_ctx *h, int n_inst, bool batched, int j, int k, hipStream_t s);
+// step.hip: the begin work of an iLQR step (its iterations follow in covo_plan_after_step / covo_plan_after_batched)
+int covo_ilqr_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1, hipStream_t s);
+int covo_ilqr_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys, hipStream_t s);
 // step.hip: the hold step of a single / an env-batched schedule (age >= 1) in place of the step's own launches, and the plan trace
 // behind it (no arbiter, refinement, fan or posterior covariance: hold = true below)
 int covo_hold_step(covo_ctx *h, const covo_step_args *args, int age, int log_index, hipStream_t s);

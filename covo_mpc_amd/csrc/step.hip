@@ -1017,17 +1017,17 @@ int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us
     return time_graph_replays(h, run, reps, us_out, [&](hipStream_t cs) { return batch_enqueue(h, b, b->online.key.base, cs, dbg); });
 }
 
-int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
-                           hipStream_t s)
+// the cold block of the batches that carry per-instance Hessian constants -- covo-online's and the iLQR step's, which share b->online
+// (keyed by `mode`: a handle stepped alternately through both rebuilds, as one stepped through two argument blocks does)
+static int batch_online_cold(covo_ctx *h, BatchState *b, const covo_batch_args *args, int mode, const covo_env_params *params,
+                             hipStream_t s, bool *same_out)
 {
     const int E = args->n_envs;
-    step_sync_epoch(h);
-    BatchState *b = batch_state(h);
     BatchCommon *c = &b->online;
     covo_batch_mode_args m;  // the scratch's key: this entry's part of it
     std::memset(&m, 0, sizeof(m));
     m.base = *args;
-    m.mode = COVO_MODE_COVO_ONLINE;
+    m.mode = mode;
     const bool new_E = c->n_envs != E;
     bool same;
     int rc;
@@ -1054,6 +1054,20 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
         if ((rc = covo_grow_workspace(h, &h->ws_hess, &h->ws_hess_bytes, hessian_workspace_bytes(E), s))) return rc;
         c->record(m, s);
     }
+    *same_out = same;
+    return 0;
+}
+
+int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
+                           hipStream_t s)
+{
+    const int E = args->n_envs;
+    step_sync_epoch(h);
+    BatchState *b = batch_state(h);
+    BatchCommon *c = &b->online;
+    bool same;
+    int rc;
+    if ((rc = batch_online_cold(h, b, args, COVO_MODE_COVO_ONLINE, params, s, &same))) return rc;
     batch_upload_keys(c->dyn, keys, E, s);
     // covo_set_step_sigma_period: the batch shares one age -- 0: today's step, which leaves the factors in b->L; else a reuse step
     const int age = covo_sigma_step_age(h, b->L, args->sample_sigma, E);
@@ -1298,6 +1312,35 @@ static void hold_park_keys(uint32_t *dyn, const uint32_t *keys, int E, hipStream
     hipLaunchKernelGGL(hold_park_keys_kernel, dim3(1), dim3(256), 0, s, dyn, blk, E);
 }
 
+// ---- the iLQR step (COVO_MODE_ILQR; ilqr.hip): its begin work -- the mean shifted in place, the step's scalars from the raw key, the
+// rollouts' disturbance table.  Nothing here touches a sample buffer, and nothing is captured: the iterations follow eagerly in the
+// after-step frame (ilqr_iterations below), as riccati_after's launches always have
+int covo_ilqr_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1, hipStream_t s)
+{
+    if (!h->step) {
+        int rc = step_state_init(h);
+        if (rc) return rc;
+    }
+    StepState *st = reinterpret_cast<StepState *>(h->step);
+    const uint32_t raw[2] = {key0, key1};
+    if (int rc = launch_ilqr_begin(args->a_mean_in ? args->a_mean_in : args->a_mean, args->a_mean, st->dyn, raw, 1, args->derive_keys,
+                                   covo_shared_noise_scale(*params, args->rollout_deterministic), s)) return rc;
+    if (!covo_needs_tables(*params)) return 0;
+    return launch_disturb_tables_step(*params, args->state, st->dyn, args->rollout_deterministic, st->f_tab_rollout, nullptr, s);
+}
+// ... of E instances: covo-online's scratch (Hessian constants, disturbance models, tables), under a key of its own
+int covo_ilqr_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys, hipStream_t s)
+{
+    const int E = args->n_envs;
+    BatchState *b = batch_state(h);
+    BatchCommon *c = &b->online;
+    bool same;
+    if (int rc = batch_online_cold(h, b, args, COVO_MODE_ILQR, params, s, &same)) return rc;
+    if (int rc = launch_ilqr_begin(args->a_mean, args->a_mean, c->dyn, keys, E, 1, 0.0f, s)) return rc;  // (deterministic rollouts, as covo-online's)
+    if (!c->tables) return 0;
+    return launch_disturb_tables_batched(c->models, args->states, c->dyn, E, 1, c->tab_rollout, b->tab_hess, s);
+}
+
 // ---- the launches behind a step (after_step.hpp: the update arbiter, the flight recorder's plan and trace, the sample fan), eager.
 // What they need to know about ONE instance of the step that has just been enqueued: the inputs its sample rollouts had.  The shared
 // vector is re-derived from the raw key by the launches themselves (every step path forms it from the same device function); the
@@ -1387,6 +1430,8 @@ static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched
         r[e].dir = o.d + (size_t)e * COVO_NA;
         r[e].dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
         r[e].row_out = h->riccati_out + (size_t)e * COVO_RICCATI_FLOATS;
+        if (h->ilqr_costs != nullptr && h->ilqr_slot > 0)  // (test hook: the candidates' costs of an iLQR step's iteration)
+            r[e].costs_out = h->ilqr_costs + ((size_t)e * COVO_MAX_STEP_ITERS + (h->ilqr_slot - 1)) * COVO_FEEDBACK_CANDIDATES;
         if (feedback) {
             f[e] = covo_feedback_desc(h, e, d[e].a_mean_out);
             r[e].extra = f[e].a_out;
@@ -1408,6 +1453,21 @@ static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, c
     if (rc || arbiter_only) return rc;
     if ((rc = launch_plan_trace(h, d, n, batched, states_true, trace_index, s))) return rc;
     return launch_sample_fan(h, d, n, batched, trace_index, s);
+}
+
+// the k iterations of an iLQR step behind its begin work: riccati_after as a sampling step enqueues it, k times on the same inputs (the
+// key is not walked: one objective per step), each followed by the tally (ilqr.hip); then the plan trace of the committed mean
+static int ilqr_iterations(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const HessianDesc &ric, const float *states_true,
+                           int trace_index, hipStream_t s)
+{
+    const int K = covo_step_iters(h);
+    for (int j = 0; j < K; ++j) {
+        h->ilqr_slot = j + 1;
+        int rc = riccati_after(h, d, n, batched, ric, trace_index, s);
+        h->ilqr_slot = 0;
+        if (rc || (rc = launch_ilqr_tally(h, n, batched, j, K, s))) return rc;
+    }
+    return launch_plan_trace(h, d, n, batched, states_true, trace_index, s);
 }
 
 int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
@@ -1435,6 +1495,29 @@ int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_
     }
     if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
     StepState *st = reinterpret_cast<StepState *>(h->step);
+    if (args->mode == COVO_MODE_ILQR) {
+        // the iterations of an iLQR step: the raw key as the call got it (not walked), the Hessian's table formed from it once
+        const BatchInst li = {args->state, args->pos_traj, args->vel_traj, args->a_mean, args->a, args->cost, args->groupmin};
+        const bool tables = covo_needs_tables(*params);
+        PlanInstDesc ld = plan_inst(li, args->T, args->n_samples, params, args->derive_keys, args->rollout_deterministic, nullptr,
+                                    tables ? st->f_tab_rollout : nullptr, nullptr);
+        ld.key[0] = key0;
+        ld.key[1] = key1;
+        for (int c = 0; c < 3; ++c) ld.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
+        HessianDesc lr;
+        lr.state = ld.state;
+        lr.pos_traj = ld.pos_traj;
+        lr.vel_traj = ld.vel_traj;
+        lr.T = ld.T;
+        lr.params = params;
+        lr.a_mean = args->a_mean;
+        if (tables) {
+            if (int rc = launch_disturb_table(*params, ld.state, 1, nullptr, key0, key1, COVO_DISTURB_KEYS_HESSIAN, 1, h->riccati_tab, s))
+                return rc;
+            lr.f_tab = h->riccati_tab;
+        }
+        return ilqr_iterations(h, &ld, 1, false, lr, state_true, trace_index, s);
+    }
     // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
     // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
     const bool iterated = covo_step_iters(h) > 1 && st != nullptr;
@@ -1504,7 +1587,7 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
     if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
-    const bool online = mode == COVO_MODE_COVO_ONLINE;
+    const bool online = mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_ILQR;  // (the iLQR step runs on covo-online's scratch)
     // the batch whose begin launch has left the shifted means and parked the raw keys: covo-online's, the staged MPPI / covo-offline
     // step's (covo_set_step_batched_staged), or none behind the fused launch
     const BatchCommon *c = online ? &b->online : (covo_batched_staged(h) ? &b->staged : nullptr);
@@ -1556,6 +1639,7 @@ int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, 
         ric.f_tab = c->tables ? b->tab_hess : nullptr;
         ric.models_dev = c->models;
     }
+    if (mode == COVO_MODE_ILQR) return ilqr_iterations(h, d, E, true, ric, states_true, trace_index, s);  // (riccati: the step's own checks)
     if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only, refine ? &rs : nullptr, riccati ? &ric : nullptr))
         return rc;
     // the posterior covariance of every instance (never behind the fused launch: check_batch_step): dense slices, the begin launch's

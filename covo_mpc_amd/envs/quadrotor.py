@@ -20,7 +20,7 @@ import numpy as np
 
 from .. import controllers
 from .. import random as crandom
-from ..controllers._options import (STEP_OPTION_DEFAULTS, check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_step_options,
+from ..controllers._options import (STEP_OPTION_DEFAULTS, check_ilqr, check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_step_options,
                                     take)
 from ..dynamics import utils
 from ..dynamics.dataclass import Action3D, DeviceState, EnvParams3D, EnvState3D
@@ -615,9 +615,12 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     Riccati sweep's direction; riccati_feedback=True on top of it: the closed-loop candidates under the sweep's gains compete in that
     line search (check_riccati_feedback).  plan_hold=m > 1 on top of riccati: every m-th step plans, the others apply the sweep's law to
     the measured state (check_plan_hold); rows=True then also holds "hold": ep.read_hold()."""
-    if controller not in ("covo-online", "mppi", "covo-offline"):
-        raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi' or 'covo-offline'")
+    if controller not in ("covo-online", "mppi", "covo-offline", "ilqr"):
+        raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline' or 'ilqr'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
+    if controller == "ilqr":
+        return _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, refine,
+                                  riccati_feedback, plan_hold, opts)
     check_step_options(None, "online" if controller == "covo-online" else controller, **opts)  # ValueError before anything is built
     check_refine(refine, "online" if controller == "covo-online" else controller, sigma_period=sigma_period)
     check_riccati(riccati, "online" if controller == "covo-online" else f"the env-batched {controller} controller", refine=refine)
@@ -666,6 +669,40 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                  "post": ("postlog", ep.read_post)}
         reads["hold"] = ("holdlog", ep.read_hold)
         out += ({name: read() for name, (attr, read) in reads.items() if getattr(ep, attr) is not None},)
+    return out if len(out) > 1 else out[0]
+
+
+def _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, refine,
+                       riccati_feedback, plan_hold, opts):
+    """eval_env_batched(controller="ilqr"): the same instances, reset keys and key chains under BatchedILQRController (H from
+    controller_params; N and lam are ignored; riccati_feedback as for get_controller).  rows=True appends {"hold": ep.read_hold()}
+    under plan_hold > 1 (else {})."""
+    k, feedback, m = check_ilqr(opts["iters"], riccati_feedback=riccati_feedback or None, plan_hold=plan_hold,
+                                disturb_type=getattr(env, "disturb_type", None), refine=refine,
+                                **{o: v for o, v in opts.items() if o != "iters"})
+    if staged or arbiter:
+        raise ValueError(f"{'staged' if staged else 'arbiter'}=True with controller='ilqr': a switch of the sampling batches")
+    from .. import controllers
+    ks = crandom.split(crandom.PRNGKey(seed), 3 * n_envs + 1)
+    params = [env.sample_params(ks[e]) for e in range(n_envs)]
+    H = int(controller_params.split("_")[1][1:]) if controller_params else 32
+    dp = env.default_params
+    th = (dp.m * dp.g / dp.max_thrust) * 2.0 - 1.0
+    b = controllers.BatchedILQRController(env, n_envs, H, iters=k, riccati_feedback=feedback, plan_hold=m, compute_plan=trace,
+                                          a_mean_init=np.tile(np.array([th, 0.0, 0.0, 0.0], dtype=np.float32), H), device=device)
+    ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
+    T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
+    t0 = time_module.time()
+    b.run_episode(ep, ks[2 * n_envs:3 * n_envs], T)
+    log = ep.read_log()
+    if verbose:
+        el = time_module.time() - t0
+        print(f"{n_envs} instances x {T} steps in {el:.2f}s = {n_envs * T / el:.0f} env-steps/s; "
+              f"err_pos mean over instances: {log[:, :, 1].mean():.3f} (min {log[:, :, 1].mean(axis=1).min():.3f}, "
+              f"max {log[:, :, 1].mean(axis=1).max():.3f})")
+    out = (log[:, :, 1].mean(axis=1),) + ((ep.read_trace(),) if trace else ())
+    if rows:
+        out += ({"hold": ep.read_hold()} if ep.holdlog is not None else {},)
     return out if len(out) > 1 else out[0]
 
 
@@ -776,9 +813,26 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     direction, which needs neither R nor Sigma (controllers/_options.py: check_riccati).  riccati_feedback (on top of riccati): the
     closed-loop candidates under the sweep's gains compete in that line search (controllers/_options.py: check_riccati_feedback).
     plan_hold (on top of riccati): every plan_hold-th control step plans, the others track the last plan under the sweep's gains
-    (controllers/_options.py: check_plan_hold)."""
+    (controllers/_options.py: check_plan_hold).
+    controller_name "ilqr": the sampling-free controller (controllers/ilqr.py; controllers/_options.py: check_ilqr) -- H is taken from
+    controller_params, N and lam are ignored; iters, plan_hold and compute_plan pass through, riccati is implied, riccati_feedback=True
+    asks for the closed-loop candidates and False (this signature's default) leaves the choice to the plant (ILQRController's None);
+    every other step option away from its default is a ValueError."""
     opts = take(locals())
+    if controller_name == "ilqr":  # ValueError / NotImplementedError before anything is built
+        k, feedback, m = check_ilqr(iters, riccati_feedback=riccati_feedback or None, plan_hold=plan_hold,
+                                    disturb_type=getattr(env, "disturb_type", None), refine=refine, process_group=process_group,
+                                    **{o: v for o, v in opts.items() if o != "iters"})
     import torch
+    if controller_name == "ilqr":
+        H = int(controller_params.split("_")[1][1:]) if controller_params else 32
+        device = device if device is not None else (env.device if env.device is not None else "cuda")
+        dp = env.default_params
+        th = (dp.m * dp.g / dp.max_thrust) * 2.0 - 1.0
+        control_params = controllers.ILQRParams(
+            a_mean=torch.tensor([th, 0.0, 0.0, 0.0], dtype=torch.float32, device=device).repeat(H, 1), discount=1.0)
+        return controllers.ILQRController(env=env, control_params=control_params, H=H, iters=k, riccati_feedback=feedback,
+                                          plan_hold=m, compute_plan=compute_plan, device=device), control_params
     # ValueError before anything is built; the controller's own check, with N, follows
     what = "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name
     check_step_options(None, what, **opts)

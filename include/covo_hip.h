@@ -914,6 +914,43 @@ int covo_set_episode_hold_log(covo_handle_t h, float *log, int32_t stride);
  * [n_inst][H][4] / [n_inst][H][16] -- what the hold steps that follow apply. */
 int covo_debug_plan_latch(covo_handle_t h, int32_t n_inst, float *b_out, int32_t *t_out, double *K_out, double *kff_out, double *x_out,
                           void *stream);
+
+/* The iLQR controller: Riccati sweeps and the closed-loop line search, nothing sampled (additive to ABI 10: COVO_HAS_ILQR; a fourth
+ * step mode -- a handle never stepped in it launches, allocates and captures what it always did).  One control step in
+ * COVO_MODE_ILQR, through covo_mpc_step / covo_run_episode (covo_step_args.mode) or covo_mpc_step_batched_mode /
+ * covo_run_episode_batched_mode (covo_batch_mode_args.mode; the other fields of that struct are ignored), with k = the iteration
+ * count of covo_set_step_iters (1 without it):
+ *     b_0 = [a_mean[1:], a_mean[31]];   b_{j+1} = the Riccati line search at b_j, j = 0 .. k - 1;   a_mean <- b_k
+ *   where an iteration is what covo_set_step_riccati [+ covo_set_step_riccati_feedback] enqueues behind a sampling step, launch for
+ *   launch: Hessian blocks -> chains -> sweep -> [latch] -> [closed-loop generator] -> line search over 17 [33] candidates.  All k
+ *   iterations see the step's one state, trajectory slices and raw key (derive_keys = 1: the disturbance inputs are derived from it
+ *   on the device as a covo-online step derives them); the key is NOT walked between them as the passes of an iterated sampling step
+ *   walk it -- the objective does not change inside a step, so row_{j+1}.cost_base == row_j.cost_chosen, and once an iteration commits
+ *   choice 0 every later one does too.  a, cost, groupmin, a_cov, L_table, gamma_mean, sample_sigma are not read or written: no noise,
+ *   sample rollout, update, Hessian GEMM, Sigma chain or arbiter launch runs.  Eager launches; the plan trace follows the last
+ *   iteration.  The handle's Riccati and feedback rows describe the last iteration.
+ * Under covo_set_step_plan_hold every m-th step is the step above; the latch, gains, alpha and side row of its LAST iteration are
+ *   what the m - 1 hold steps between apply (the hold launch and its fall-backs are the ones of the sampling controllers).
+ * covo_set_step_ilqr: the per-iteration logs.  rows = DEVICE float[n_inst][COVO_MAX_STEP_ITERS][COVO_RICCATI_FLOATS], fb_rows = DEVICE
+ *   float[n_inst][COVO_MAX_STEP_ITERS][COVO_FEEDBACK_FLOATS] (slot j: iteration j's rows; zeros without the feedback rows), summary =
+ *   DEVICE float[n_inst][COVO_ILQR_FLOATS] = {row_0.cost_base, row_{k-1}.cost_chosen, bits(int32 iterations with choice != 0),
+ *   bits(int32 first j with choice 0; k: none), bits(int32 iterations with choice > 16), bits(OR of the rows' flag words),
+ *   |g|_2 of the last iteration, 0}; any of the three may be NULL, all NULL (n_inst ignored) detaches.  One launch of one wave per
+ *   instance behind every iteration's line search (csrc/ilqr.hip) fills them.
+ * Refused at the step with COVO_E_BADARG, before any launch: no covo_set_step_riccati on the handle; covo_set_step_refine; an
+ *   attached arbiter, sample fan, diagnostics buffer, ESS floor, elite set, posterior covariance, Sigma period or Sigma adapt; a
+ *   sample-sharded step (partial_out != NULL); derive_keys = 0; more instances than log rows; and whatever the attachments in use
+ *   refuse themselves (feedback rows and plan hold on drag / mixed).  covo_debug_time_step refuses the mode: its phase masks name
+ *   sampling launches. */
+#define COVO_HAS_ILQR 1
+#define COVO_MODE_ILQR 3
+#define COVO_ILQR_FLOATS 8
+int covo_set_step_ilqr(covo_handle_t h, float *rows /* DEVICE [n_inst][16][8] or NULL */, float *fb_rows /* DEVICE [n_inst][16][8] or NULL */,
+                       float *summary /* DEVICE [n_inst][COVO_ILQR_FLOATS] or NULL */, int32_t n_inst);
+/* Test hook: the line search of iteration j of every later iLQR step also stores its candidates' costs, as covo_riccati_refine[_feedback]
+ * stores them, to costs[e][j][0 .. 17 or 33) -- costs = DEVICE float[n_inst][COVO_MAX_STEP_ITERS][COVO_FEEDBACK_CANDIDATES]; NULL: off.  A
+ * batched step then uploads its line search's argument blocks in every iteration. */
+int covo_debug_ilqr_costs(covo_handle_t h, float *costs, int32_t n_inst);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

@@ -20,6 +20,10 @@ name = sys.argv[1]
 # python scripts/eval_seeds.py mppi --riccati --plan-hold 4: every 4th control step plans, the three between apply the sweep's law to the
 # measured state (csrc/plan_hold.hip); every seed's line also carries the share of hold steps whose plan belonged to another trajectory
 # (flag bit 2: a reset in between) and the share with a clipped component; compare the errors with --riccati alone
+# python scripts/eval_seeds.py ilqr [iters=k] [--plan-hold m]: the sampling-free controller (controllers/ilqr.py), k Riccati line searches
+# per control step (default 1: get_controller's); every seed's line also carries the share of plan steps that reached a fixed point
+# (ilqr_fixed_at < k) and the share that committed a closed-loop candidate in some iteration, summed on the device from the info dict
+# (the host loop of __call__ + episode.step: the summary row has no episode log)
 rest = sys.argv[2:]
 refine = "--refine" in rest
 riccati = "--riccati" in rest
@@ -39,6 +43,30 @@ ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, ricca
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
+
+
+class IlqrTally:
+    """the iLQR controller behind eval_env_device's host loop (no run_episode), counting what its info dict says on the device"""
+    def __init__(self, c):
+        import torch
+        self.c, self.core, self.init_control_params, self.alias_outputs = c, c.core, c.init_control_params, False
+        self.acc = torch.zeros(3, dtype=torch.int64, device=c.core.device)  # plan steps, of them at a fixed point, with a closed-loop commit
+
+    def reset(self, *a):
+        return self.c.reset(*a)
+
+    def __call__(self, *a):
+        self.c.alias_outputs = self.alias_outputs
+        u, cp, info = self.c(*a)
+        if info.get("plan_age", 0) == 0:
+            self.acc[0] += 1
+            self.acc[1] += info["ilqr_fixed_at"] < self.c.iters
+            self.acc[2] += info["ilqr_closed"] > 0
+        return u, cp, info
+
+
+if name == "ilqr":
+    ctrl = IlqrTally(ctrl)
 
 
 def rows_of(ep):
@@ -63,10 +91,17 @@ for seed in range(1, 13):
     rows = {}
     errs = Q.eval_env_device(env, controller=ctrl, total_steps=300*4*10, seed=seed, verbose=False, on_episode=rows_of if core else None)
     allerr.append(errs)
+    if name == "ilqr":
+        acc = ctrl.acc.cpu().numpy()
+        ctrl.acc.zero_()
+        rows["fixed"], rows["closed"], rows["plans"] = int(acc[1]), int(acc[2]), int(acc[0])
     n = max(rows.get("steps", 0), 1)
+    npl = max(rows.get("plans", 0), 1)
     nh = max(rows.get("held", 0), 1)
     extra = "".join(text % (rows[k] / d) for k, text, d in (("floor", "  lam_eff>lam: %.3f", n), ("fallback", "  adapt fallbacks: %d", 1),
                                                            ("improved", "  last pass beat first: %.3f", n),
+                                                           ("fixed", "  plan steps at a fixed point: %.3f", npl),
+                                                           ("closed", "  plan steps with a closed-loop commit: %.3f", npl),
                                                            ("stale", "  hold steps on another trajectory's plan: %.3f", nh),
                                                            ("clipped", "  hold steps with a clipped component: %.3f", nh)) if k in rows)
     print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()) + extra,
