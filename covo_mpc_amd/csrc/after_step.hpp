@@ -1,6 +1,7 @@
 // after_step.hpp -- the frame the eager launches that follow a control step share (gfx950): the update arbiter
 // (update_arbiter.hip), the Newton refinement (newton_refine.hip), the plan / episode trace (plan_trace.hip) and the sample fan
-// (sample_fan.hip), in the order covo_plan_after_step / covo_plan_after_batched (step.hip) issue them.
+// (sample_fan.hip), in the order plan_after (step.hip) issues them from the AfterFrame that covo_plan_after_step /
+// covo_plan_after_batched build for the step.
 //
 // Each is one launch per control step with one workgroup of three waves per instance:
 //   phase 0  the per-step scalars from the raw controller key (after_derive) next to the kernel's own action image in LDS

@@ -61,13 +61,52 @@ static int check_model(const covo_env_params *p, const char *what)
         if (rc_) return rc_;               \
     } while (0)
 
-// what both episode drivers enqueue behind every control step, ahead of its env step: the after-step frame (`frame`: the single or the
-// batched one, given the step's row), then the copied episode logs (the posterior covariance's rows are formed in the frame)
-template <class Frame>
-static int episode_step_tail(covo_ctx *h, Frame frame, int n_inst, int row, hipStream_t s)
+// ---- one scheduled control step, for the step entry points alike (covo_mpc_step, covo_mpc_step_batched[_mode], covo_run_episode,
+// run_episode_batched): the plan hold's schedule gives it its age -- 0: the step and its after-step frame as ever; else the hold step
+// and its plan trace -- and moves on behind it.  row: the episode's row index (< 0: none).  What an episode driver enqueues in between
+// is its own: behind_step (the sharded exchange and merge), behind_frame (the copied episode logs); the others pass step_no_extra
+static int step_no_extra() { return 0; }
+static int single_step_at_age(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
+                              const float *f_shared, int age, int row, hipStream_t s)
 {
-    if (int rc = frame(row)) return rc;
-    return launch_episode_rows(h, n_inst, row, h->sigma_last_age, s);
+    if (age == 0 && args->mode == COVO_MODE_ILQR) return covo_ilqr_step_impl(h, params, args, key0, key1, s);  // (its begin work)
+    if (age == 0) return covo_step_impl(h, params, args, key0, key1, f_shared, s);
+    return covo_hold_step(h, args, age, row, s);
+}
+template <class BehindStep, class BehindFrame>
+static int single_scheduled_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
+                                 const float *f_shared, const float *state_true, int row, hipStream_t s, BehindStep behind_step,
+                                 BehindFrame behind_frame)
+{
+    const int age = covo_plan_step_age(h, 1);  // (a hold step uses no rng_act)
+    int rc = single_step_at_age(h, params, args, key0, key1, f_shared, age, row, s);
+    if (rc || (rc = behind_step())) return rc;
+    if ((rc = covo_plan_after_step(h, age != 0 ? AFTER_HOLD : AFTER_STEP, params, args, key0, key1, f_shared, state_true, row, s))) return rc;
+    if ((rc = behind_frame())) return rc;
+    covo_plan_step_done(h, age, 1);
+    return 0;
+}
+// args: the caller's block (covo-online's and the iLQR step's scratch key themselves by it); norm: check_batch_step's, with the mode
+static int batched_step_at_age(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *norm, const covo_env_params *params,
+                               const uint32_t *keys, int age, int row, hipStream_t s)
+{
+    if (age != 0) return covo_hold_step_batched(h, args, age, row, s);  // (covo-online and iLQR only: the others refuse the Riccati refinement)
+    if (norm->mode == COVO_MODE_ILQR) return covo_ilqr_step_batched_impl(h, args, params, keys, s);  // (its begin work)
+    return norm->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, args, params, keys, s)
+           : covo_batched_staged(h)            ? covo_step_batched_staged_impl(h, norm, params, keys, s)
+                                               : covo_step_batched_small_impl(h, norm, params, keys, s);
+}
+template <class BehindFrame>
+static int batched_scheduled_step(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *norm, const covo_env_params *params,
+                                  const uint32_t *keys, const float *states_true, int row, hipStream_t s, BehindFrame behind_frame)
+{
+    const int age = covo_plan_step_age(h, args->n_envs);  // (the batch shares one age)
+    int rc = batched_step_at_age(h, args, norm, params, keys, age, row, s);
+    if (rc || (rc = covo_plan_after_batched(h, age != 0 ? AFTER_HOLD : AFTER_STEP, args, norm->mode, params, keys, states_true, row, s)))
+        return rc;
+    if ((rc = behind_frame())) return rc;
+    covo_plan_step_done(h, age, args->n_envs);
+    return 0;
 }
 
 __global__ void raise_status_kernel(int *status, int bits)
@@ -710,7 +749,7 @@ int covo_set_step_diag(covo_handle_t h, float *diag, int32_t n_inst)
     return 0;
 }
 
-// what the five setters of the episode logs share (covo_eplog_kinds, covo_common.hpp): with a log, stride > 0 (stride_fmt: the setter's
+// what the six setters of the episode logs share (covo_eplog_kinds, covo_common.hpp): with a log, stride > 0 (stride_fmt: the setter's
 // own text) and the attachment the log follows is on; the null-handle check and the setter's extras stay with the setter
 static int set_episode_log(covo_ctx *h, int kind, float *log, int stride, const char *stride_fmt)
 {
@@ -1244,21 +1283,12 @@ static int check_ilqr_step(const covo_ctx *h, int n_inst, bool sharded, int deri
     return 0;
 }
 
-// the episode hold log (covo_set_episode_hold_log) of a driver that writes rows [first_row, first_row + n_steps)
-static int check_hold_log(const covo_ctx *h, int first_row, int n_steps, const char *what)
-{
-    REQUIRE(h->hold_log == nullptr || (first_row >= 0 && first_row + n_steps <= h->hold_log_stride),
-            "%s: episode hold log rows [%d, %d) outside [0, %d) (covo_set_episode_hold_log)", what, first_row, first_row + n_steps,
-            h->hold_log_stride);
-    return 0;
-}
-
 // an episode driver that writes rows [first_row, first_row + n_steps) of every attached log (the single driver: first_row = 0)
 static int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, const char *what)
 {
-    // the first offender is reported: the four logs with setters of their own, then covo_set_episode_rows' kinds
-    static const int order[COVO_EPLOG_ALL] = {COVO_EPLOG_DIAG,  COVO_EPLOG_TRACE, COVO_EPLOG_FAN,   COVO_EPLOG_ARB,      COVO_EPLOG_LAM,
-                                              COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV};
+    // the first offender is reported: four logs with setters of their own, then covo_set_episode_rows' kinds, then the hold log
+    static const int order[COVO_EPLOG_ALL] = {COVO_EPLOG_DIAG,  COVO_EPLOG_TRACE, COVO_EPLOG_FAN,   COVO_EPLOG_ARB,      COVO_EPLOG_LAM, COVO_EPLOG_ELITE,
+                                              COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV, COVO_EPLOG_HOLD};
     for (const int k : order)
         REQUIRE(h->eplog[k].log == nullptr || (first_row >= 0 && first_row + n_steps <= h->eplog[k].stride),
                 "%s: %s rows [%d, %d) outside [0, %d) (%s)", what, covo_eplog_kinds[k].name, first_row, first_row + n_steps,
@@ -1290,21 +1320,6 @@ int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, c
 
 // ---- the Newton refinement (cost_gradient.hip, newton_refine.hip).  Its launches are eager and follow the step: no captured step
 // graph changes
-static HessianDesc gradient_desc(const float *state, const float *pos_traj, const float *vel_traj, int T, const covo_env_params *params,
-                                 const float *a, const float *f_tab, int batch)
-{
-    HessianDesc d;
-    d.state = state;
-    d.pos_traj = pos_traj;
-    d.vel_traj = vel_traj;
-    d.T = T;
-    d.params = params;
-    d.a_mean = a;
-    d.f_tab = f_tab;
-    d.batch = batch;
-    return d;
-}
-
 int covo_cost_gradient(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                        const covo_env_params *params, const float *a, const float *f_disturb_steps, int32_t batch, double *g_out,
                        void *stream)
@@ -1317,7 +1332,7 @@ int covo_cost_gradient(covo_handle_t h, const float *state, const float *pos_tra
             params->disturb_kind);
     const int rc = covo_grow_workspace(h, &h->ws_grad, &h->ws_grad_bytes, cost_gradient_workspace_bytes(batch), (hipStream_t)stream);
     if (rc) return rc;
-    return launch_cost_gradient(gradient_desc(state, pos_traj, vel_traj, T, params, a, f_disturb_steps, batch), g_out, h->ws_grad,
+    return launch_cost_gradient(covo_hessian_inputs(state, pos_traj, vel_traj, T, params, a, f_disturb_steps, batch), g_out, h->ws_grad,
                                 (hipStream_t)stream);
 }
 
@@ -1339,7 +1354,7 @@ int covo_newton_refine(covo_handle_t h, const float *state, const float *pos_tra
         int rc = covo_grow_workspace(h, &h->ws_grad, &h->ws_grad_bytes, cost_gradient_workspace_bytes(n_inst), s);
         if (rc) return rc;
         if (h->refine_g == nullptr) COVO_CHECK_HIP(hipMalloc(&h->refine_g, (size_t)COVO_MAX_ENVS * COVO_NA * sizeof(double)));
-        if ((rc = launch_cost_gradient(gradient_desc(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst), h->refine_g,
+        if ((rc = launch_cost_gradient(covo_hessian_inputs(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst), h->refine_g,
                                        h->ws_grad, s)))
             return rc;
         g = h->refine_g;
@@ -1401,7 +1416,7 @@ int covo_riccati(covo_handle_t h, const float *state, const float *pos_traj, con
             params->disturb_kind);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = covo_grow_workspace(h, &h->ws_riccati, &h->ws_riccati_bytes, riccati_workspace_bytes(batch), s)) return rc;
-    HessianDesc d = gradient_desc(state, pos_traj, vel_traj, T, params, a, f_tab_hessian, batch);
+    HessianDesc d = covo_hessian_inputs(state, pos_traj, vel_traj, T, params, a, f_tab_hessian, batch);
     d.status_dev = h->status_dev;
     RiccatiOut o;
     o.d = d_out;
@@ -1445,13 +1460,9 @@ static int riccati_refine_body(covo_handle_t h, const float *state, const float 
     if (int rc = riccati_reserve(h, n_inst, s)) return rc;
     if (feedback)
         if (int rc = feedback_reserve(h)) return rc;
-    HessianDesc hd = gradient_desc(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst);
+    HessianDesc hd = covo_hessian_inputs(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst);
     hd.status_dev = h->status_dev;
-    RiccatiOut o;
-    o.d = h->riccati_d;
-    o.g = h->refine_g;
-    o.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA;
-    if (feedback) covo_feedback_sweep_out(h, o);
+    const RiccatiOut o = covo_riccati_out(h, feedback);
     if (int rc = launch_riccati(hd, reg0, o, h->ws_riccati, s)) return rc;
     if (feedback && h->feedback_poke_armed) {  // covo_debug_feedback_gain: once
         h->feedback_poke_armed = 0;
@@ -1464,21 +1475,16 @@ static int riccati_refine_body(covo_handle_t h, const float *state, const float 
         PlanInstDesc d = standalone_inst(state + (size_t)e * COVO_STATE_FLOATS, pos_traj, vel_traj, T, params, f_disturb_shared,
                                          f_disturb_steps ? f_disturb_steps + (size_t)e * COVO_H * 4 : nullptr, nullptr, 1);
         d.a_mean = d.a_mean_out = a_mean + (size_t)e * COVO_NA;
-        RefineDesc r;
-        r.g = o.g + (size_t)e * COVO_NA;
-        r.dir = o.d + (size_t)e * COVO_NA;
-        r.dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
-        r.row_out = rows_out + (size_t)e * COVO_RICCATI_FLOATS;
-        r.costs_out = costs_out ? costs_out + (size_t)e * ncost : nullptr;
+        FeedbackDesc f;
         if (feedback) {
-            const FeedbackDesc f = covo_feedback_desc(h, e, d.a_mean);
+            f = covo_feedback_desc(h, e, d.a_mean);
             double ladder[COVO_FEEDBACK_LADDER];
             for (int j = 1; j <= COVO_FEEDBACK_LADDER; ++j) ladder[j - 1] = std::ldexp(1.0, 3 - j);
             if (int rc = launch_feedback_rollout_one(h, d, f, ladder, s)) return rc;
-            r.extra = f.a_out;
-            r.extra_aux = f.aux_out;
-            r.fb_row_out = fb_rows_out + (size_t)e * COVO_FEEDBACK_FLOATS;
         }
+        const RefineDesc r = covo_riccati_refine_desc(o, e, rows_out + (size_t)e * COVO_RICCATI_FLOATS,
+                                                      costs_out ? costs_out + (size_t)e * ncost : nullptr, feedback ? &f : nullptr,
+                                                      feedback ? fb_rows_out + (size_t)e * COVO_FEEDBACK_FLOATS : nullptr);
         if (int rc = launch_newton_refine_one(h, d, rollout_clip(h), r, s)) return rc;
     }
     return 0;
@@ -1595,8 +1601,7 @@ int covo_set_step_plan_hold(covo_handle_t h, int32_t period, float *rows, int32_
         h->plan_hold = 1;
         h->hold_rows = nullptr;
         h->hold_n = 0;
-        h->hold_log = nullptr;
-        h->hold_log_stride = 0;
+        covo_eprow_drop(h, COVO_EPLOG_HOLD);  // off, the log with it
         return 0;
     }
     REQUIRE(rows != nullptr && n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_plan_hold: period=%d needs rows and n_inst=%d in (0, %d]",
@@ -1648,16 +1653,9 @@ int covo_step_plan_age(covo_handle_t h, int32_t *next_age, int32_t *last_age)
 int covo_set_episode_hold_log(covo_handle_t h, float *log, int32_t stride)
 {
     REQUIRE(h, "covo_set_episode_hold_log: null handle");
-    if (log == nullptr) {
-        h->hold_log = nullptr;
-        h->hold_log_stride = 0;
-        return 0;
-    }
-    REQUIRE(covo_plan_hold(h) > 1, "covo_set_episode_hold_log: no plan hold: call covo_set_step_plan_hold (period > 1) first");
-    REQUIRE(stride > 0, "covo_set_episode_hold_log: stride=%d", stride);
-    h->hold_log = log;
-    h->hold_log_stride = stride;
-    return 0;
+    // (a missing plan hold is reported ahead of a bad stride)
+    REQUIRE(log == nullptr || covo_plan_hold(h) > 1, "%s", covo_eplog_kinds[COVO_EPLOG_HOLD].off);
+    return set_episode_log(h, COVO_EPLOG_HOLD, log, stride, "covo_set_episode_hold_log: stride=%d");
 }
 
 int covo_plan_hold(covo_handle_t h, const float *state, const float *b, const double *K, const double *kff, const double *x,
@@ -1782,26 +1780,6 @@ static int check_single_step(const covo_ctx *h, const covo_env_params *params, c
     return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, params, what);
 }
 
-// ---- the plan hold's schedule, for the four step entry points alike (covo_mpc_step, covo_mpc_step_batched[_mode], covo_run_episode,
-// run_episode_batched): the control step of a single handle at the age the schedule gives it -- 0: the step and its after-step frame
-// as ever; else the hold step and its plan trace.  row: the episode's row index (< 0: none)
-static int single_step_at_age(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                              const float *f_shared, int age, int row, hipStream_t s)
-{
-    if (age == 0 && args->mode == COVO_MODE_ILQR) return covo_ilqr_step_impl(h, params, args, key0, key1, s);  // (its begin work)
-    if (age == 0) return covo_step_impl(h, params, args, key0, key1, f_shared, s);
-    return covo_hold_step(h, args, age, row, s);
-}
-static int batched_step_at_age(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *norm, bool online,
-                               const covo_env_params *params, const uint32_t *keys, int age, int row, hipStream_t s, bool ilqr = false)
-{
-    if (age != 0) return covo_hold_step_batched(h, args, age, row, s);  // (covo-online and iLQR only: the others refuse the Riccati refinement)
-    if (ilqr) return covo_ilqr_step_batched_impl(h, args, params, keys, s);  // (its begin work)
-    return online                   ? covo_step_batched_impl(h, args, params, keys, s)
-           : covo_batched_staged(h) ? covo_step_batched_staged_impl(h, norm, params, keys, s)
-                                    : covo_step_batched_small_impl(h, norm, params, keys, s);
-}
-
 int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, float *state_true,
                      const float *acc_traj, int32_t noisy_on, float obs_noise_scale, float *log, uint32_t *rng,
                      int32_t n_steps, void *stream)
@@ -1815,8 +1793,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
             "covo_run_episode: a sample-sharded step (partial_out != NULL) needs the peer-write exchange (covo_exchange_create / "
             "covo_exchange_connect) and a_mean_shift");
     int rc = check_single_step(h, params, args, "covo_run_episode");
-    if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode")) || (rc = check_hold_log(h, 0, n_steps, "covo_run_episode")))
-        return rc;
+    if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -1825,9 +1802,8 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
         host_philox_split(key, 0u, nrng);
         host_philox_split(key, 1u, rng_act);
         host_philox_split(key, 2u, rng_step);
-        const int age = covo_plan_step_age(h, 1);  // (a hold step uses no rng_act; rng_step is what it was)
-        if ((rc = single_step_at_age(h, params, args, rng_act[0], rng_act[1], nullptr, age, t, s))) return rc;
-        if (args->partial_out != nullptr) {
+        auto exchange = [&]() -> int {
+            if (args->partial_out == nullptr) return 0;
             // sample-sharded: every rank's record to every rank (peer writes, exchange.hip), then the same merge on all of them.
             // partial_out is this rank's RANK record: {m, s, v} there, its position sums (if any) at + COVO_PARTIAL_FLOATS
             const float *gathered = nullptr;
@@ -1848,12 +1824,11 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
                                        h->cfg.lam, s)))
                     return rc;
             }
-        }
-        auto frame = [&](int row) {
-            return covo_plan_after_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, row, s, false, age != 0);
+            return 0;
         };
-        if ((rc = episode_step_tail(h, frame, 1, t, s))) return rc;
-        covo_plan_step_done(h, age, 1);
+        // (rng_step is what it was on a hold step too; the posterior covariance's rows are formed in the frame)
+        auto rows = [&] { return launch_episode_rows(h, 1, t, h->sigma_last_age, s); };
+        if ((rc = single_scheduled_step(h, params, args, rng_act[0], rng_act[1], nullptr, state_true, t, s, exchange, rows))) return rc;
         rc = launch_env_step(state_true, const_cast<float *>(args->state), args->pos_traj, args->vel_traj, acc_traj, args->T,
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
@@ -1914,6 +1889,19 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
     REQUIRE(args->states && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost &&
                 (args->groupmin || mode != COVO_MODE_COVO_ONLINE) && args->T > 0,
             "%s: null buffer", what);
+    // (for every mode: the callers take the mode from it.  Only the MPPI / covo-offline batches key their scratch by it)
+    std::memset(norm, 0, sizeof(*norm));
+    norm->base.n_envs = args->n_envs; norm->base.n_samples = args->n_samples; norm->base.T = args->T;
+    norm->base.states = args->states; norm->base.pos_traj = args->pos_traj; norm->base.vel_traj = args->vel_traj;
+    norm->base.a_mean = args->a_mean; norm->base.a_cov = args->a_cov; norm->base.a = args->a; norm->base.cost = args->cost;
+    norm->base.groupmin = args->groupmin; norm->base.gamma_mean = args->gamma_mean; norm->base.sample_sigma = args->sample_sigma;
+    norm->mode = mode;
+    norm->gamma_sigma = m ? m->gamma_sigma : 0.0f;
+    if (mode == COVO_MODE_COVO_OFFLINE) {
+        norm->n_table = m->n_table;
+        norm->L_table = m->L_table;
+        norm->L_table_stride = m->L_table_stride;
+    }
     int rc = check_batch_models(params, args->n_envs, episode, what);
     if (rc) return rc;
     if (mode == COVO_MODE_ILQR) {  // nothing of the sampling batches' lists applies: its own, then the attachments'
@@ -1951,18 +1939,6 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
     REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),
             "%s: covo-offline needs L_table (the per-instance Sigma factor table is missing: n_table=%d)", what, m->n_table);
-    std::memset(norm, 0, sizeof(*norm));
-    norm->base.n_envs = args->n_envs; norm->base.n_samples = args->n_samples; norm->base.T = args->T;
-    norm->base.states = args->states; norm->base.pos_traj = args->pos_traj; norm->base.vel_traj = args->vel_traj;
-    norm->base.a_mean = args->a_mean; norm->base.a_cov = args->a_cov; norm->base.a = args->a; norm->base.cost = args->cost;
-    norm->base.groupmin = args->groupmin; norm->base.gamma_mean = args->gamma_mean; norm->base.sample_sigma = args->sample_sigma;
-    norm->mode = mode;
-    norm->gamma_sigma = m->gamma_sigma;
-    if (mode == COVO_MODE_COVO_OFFLINE) {
-        norm->n_table = m->n_table;
-        norm->L_table = m->L_table;
-        norm->L_table_stride = m->L_table_stride;
-    }
     if (staged) {
         REQUIRE(args->groupmin != nullptr, "%s: the staged batched step (covo_set_step_batched_staged) needs base.groupmin "
                 "(float[n_envs][ceil(n_samples / 64)]): its update reads the per-wave cost minima the rollout leaves there", what);
@@ -1994,11 +1970,9 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     covo_batch_mode_args norm;
     int rc = check_batch_step(h, args, m, params, true, what, &norm);
     if (rc) return rc;
-    const bool online = !m || m->mode == COVO_MODE_COVO_ONLINE;
-    const bool ilqr = m && m->mode == COVO_MODE_ILQR;
     REQUIRE(log == nullptr || (log_index >= 0 && log_index + n_steps <= log_stride),
             "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
-    if ((rc = check_episode_logs(h, log_index, n_steps, what)) || (rc = check_hold_log(h, log_index, n_steps, what))) return rc;
+    if ((rc = check_episode_logs(h, log_index, n_steps, what))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -2013,14 +1987,9 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             host_philox_split(key, 2u, &step_keys[2 * e]);
             host_philox_split(nrng, 0u, &next[2 * e]);
         }
-        const int age = covo_plan_step_age(h, E);  // (the batch shares one age)
-        if ((rc = batched_step_at_age(h, args, &norm, online, params, act_keys, age, log_index + t, s, ilqr))) return rc;
-        auto frame = [&](int row) {
-            return covo_plan_after_batched(h, args, online ? COVO_MODE_COVO_ONLINE : (ilqr ? COVO_MODE_ILQR : norm.mode), params, states_true, row, s, false,
-                                           age != 0 ? act_keys : nullptr);
-        };
-        if ((rc = episode_step_tail(h, frame, E, log_index + t, s))) return rc;
-        covo_plan_step_done(h, age, E);
+        // (the posterior covariance's rows are formed in the frame)
+        auto rows = [&] { return launch_episode_rows(h, E, log_index + t, h->sigma_last_age, s); };
+        if ((rc = batched_scheduled_step(h, args, &norm, params, act_keys, states_true, log_index + t, s, rows))) return rc;
         if ((rc = launch_env_step_batched(states_true, const_cast<float *>(args->states), args->pos_traj, args->vel_traj, acc_traj,
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
                                           log_stride, log_index + t, s)))
@@ -2061,14 +2030,10 @@ int covo_mpc_step_batched(covo_handle_t h, const covo_batch_args *args, const co
     REQUIRE(h, "covo_mpc_step_batched: null handle");
     CHECK_DEVICE(h, "covo_mpc_step_batched");
     REQUIRE(args && params && keys, "covo_mpc_step_batched: null argument");
-    int rc = check_batch_step(h, args, nullptr, params, false, "covo_mpc_step_batched", nullptr);
+    covo_batch_mode_args norm;
+    const int rc = check_batch_step(h, args, nullptr, params, false, "covo_mpc_step_batched", &norm);
     if (rc) return rc;
-    const int age = covo_plan_step_age(h, args->n_envs);
-    if ((rc = batched_step_at_age(h, args, nullptr, true, params, keys, age, -1, (hipStream_t)stream))) return rc;
-    if ((rc = covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, (hipStream_t)stream, false, age != 0 ? keys : nullptr)))
-        return rc;
-    covo_plan_step_done(h, age, args->n_envs);
-    return 0;
+    return batched_scheduled_step(h, args, &norm, params, keys, nullptr, -1, (hipStream_t)stream, step_no_extra);
 }
 
 int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args, const covo_env_params *params, const uint32_t *keys,
@@ -2078,16 +2043,9 @@ int covo_mpc_step_batched_mode(covo_handle_t h, const covo_batch_mode_args *args
     CHECK_DEVICE(h, "covo_mpc_step_batched_mode");
     REQUIRE(args && params && keys, "covo_mpc_step_batched_mode: null argument");
     covo_batch_mode_args norm;
-    int rc = check_batch_step(h, &args->base, args, params, false, "covo_mpc_step_batched_mode", &norm);
+    const int rc = check_batch_step(h, &args->base, args, params, false, "covo_mpc_step_batched_mode", &norm);
     if (rc) return rc;
-    const int age = covo_plan_step_age(h, args->base.n_envs);
-    if ((rc = batched_step_at_age(h, &args->base, &norm, args->mode == COVO_MODE_COVO_ONLINE, params, keys, age, -1, (hipStream_t)stream,
-                                  args->mode == COVO_MODE_ILQR)))
-        return rc;
-    if ((rc = covo_plan_after_batched(h, &args->base, args->mode, params, nullptr, -1, (hipStream_t)stream, false, age != 0 ? keys : nullptr)))
-        return rc;
-    covo_plan_step_done(h, age, args->base.n_envs);
-    return 0;
+    return batched_scheduled_step(h, &args->base, &norm, params, keys, nullptr, -1, (hipStream_t)stream, step_no_extra);
 }
 
 int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, int32_t step_mask,
@@ -2144,14 +2102,9 @@ int covo_mpc_step(covo_handle_t h, const covo_env_params *params, const covo_ste
     REQUIRE(h, "covo_mpc_step: null handle");
     CHECK_DEVICE(h, "covo_mpc_step");
     REQUIRE(params && args, "covo_mpc_step: null argument");
-    int rc = check_single_step(h, params, args, "covo_mpc_step");
+    const int rc = check_single_step(h, params, args, "covo_mpc_step");
     if (rc) return rc;
-    const int age = covo_plan_step_age(h, 1);
-    if ((rc = single_step_at_age(h, params, args, key0, key1, f_disturb_shared, age, -1, (hipStream_t)stream))) return rc;
-    if ((rc = covo_plan_after_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream, false, age != 0)))
-        return rc;
-    covo_plan_step_done(h, age, 1);
-    return 0;
+    return single_scheduled_step(h, params, args, key0, key1, f_disturb_shared, nullptr, -1, (hipStream_t)stream, step_no_extra, step_no_extra);
 }
 
 int covo_cholesky(covo_handle_t h, const float *A, int32_t n, int32_t batch, float *L_out, void *stream)

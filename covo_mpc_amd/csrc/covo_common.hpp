@@ -25,9 +25,9 @@ struct CovoOpts {
 };
 CovoOpts covo_default_opts();  // step.hip
 
-// the episode logs by internal kind: the six COVO_EPLOG_* kinds of covo_set_episode_rows (include/covo_hip.h), then the four with setters of
+// the episode logs by internal kind: the six COVO_EPLOG_* kinds of covo_set_episode_rows (include/covo_hip.h), then the five with setters of
 // their own
-enum { COVO_EPLOG_DIAG = COVO_EPLOG_KINDS, COVO_EPLOG_TRACE, COVO_EPLOG_FAN, COVO_EPLOG_ARB, COVO_EPLOG_ALL };
+enum { COVO_EPLOG_DIAG = COVO_EPLOG_KINDS, COVO_EPLOG_TRACE, COVO_EPLOG_FAN, COVO_EPLOG_ARB, COVO_EPLOG_HOLD, COVO_EPLOG_ALL };
 
 struct covo_ctx {
     covo_config cfg;
@@ -129,8 +129,6 @@ struct covo_ctx {
     int hold_n;
     float *hold_b;            // [COVO_MAX_ENVS][128] the latch: the mean the last plan step's sweep ran at ...
     int *hold_t;              // [COVO_MAX_ENVS] ... and the time word of the state it planned from
-    float *hold_log;          // caller's [n_inst][hold_log_stride][COVO_HOLD_FLOATS] episode log (covo_set_episode_hold_log), or null
-    int hold_log_stride;
     uint32_t *hold_keys;      // [COVO_MAX_ENVS][12]: a hold step's raw keys for its plan trace, laid out like a step's scalars
     // the per-iteration logs of the iLQR steps (covo_set_step_ilqr; ilqr.hip); all null: off
     float *ilqr_rows;         // caller's [ilqr_n][COVO_MAX_STEP_ITERS][COVO_RICCATI_FLOATS]: slot j = iteration j's Riccati row
@@ -139,7 +137,6 @@ struct covo_ctx {
     int ilqr_n;
     float *ilqr_costs;        // test hook (covo_debug_ilqr_costs): caller's [ilqr_costs_n][COVO_MAX_STEP_ITERS][COVO_FEEDBACK_CANDIDATES], or null
     int ilqr_costs_n;
-    int ilqr_slot;            // 1 + the iteration an iLQR step is enqueueing; 0 outside one (riccati_after then has no cost slot)
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -254,6 +251,8 @@ static const covo_eplog_kind covo_eplog_kinds[COVO_EPLOG_ALL] = {
      "covo_set_episode_fan: no fan size: call covo_set_step_fan (K, idx, n_inst) first", nullptr},
     {"episode arbiter log", "covo_set_episode_arbiter_log", covo_arb_on,
      "covo_set_episode_arbiter_log: no arbiter attached: call covo_set_step_arbiter first", nullptr},
+    {"episode hold log", "covo_set_episode_hold_log", [](const covo_ctx *h) { return covo_plan_hold(h) > 1; },
+     "covo_set_episode_hold_log: no plan hold: call covo_set_step_plan_hold (period > 1) first", nullptr},
 };
 
 // periodic / sin / drag / mixed (free.py:10-58): the disturbance model needs per-step force tables (disturb.hip)
@@ -571,6 +570,22 @@ int launch_hessian(const HessianDesc &d, void *workspace, hipStream_t s, const D
 // (R, stats, status_dev and begin are not read), the workspace the gradient's own (cost_gradient_workspace_bytes)
 size_t cost_gradient_workspace_bytes(int batch);
 int launch_cost_gradient(const HessianDesc &d, double *g_out, void *workspace, hipStream_t s);
+// the Hessian's inputs at the means `a` of `batch` instances that share trajectories and constants: what the primitives (capi.hip) and
+// the after-step frame (step.hip) hand the gradient and the sweep
+static inline HessianDesc covo_hessian_inputs(const float *state, const float *pos_traj, const float *vel_traj, int T,
+                                              const covo_env_params *params, const float *a, const float *f_tab, int batch)
+{
+    HessianDesc d;
+    d.state = state;
+    d.pos_traj = pos_traj;
+    d.vel_traj = vel_traj;
+    d.T = T;
+    d.params = params;
+    d.a_mean = a;
+    d.f_tab = f_tab;
+    d.batch = batch;
+    return d;
+}
 // where launches 1 | 2 of launch_hessian leave their results in one entry's workspace, in doubles (hessian_adj_body.hpp: WS_*): x_k
 // [32][16], df_k/dz [32][nx][nx + 4], lam_k [33][16], Mxx [32][16][16], Mxu [32][16][4], Muu [32][4][4]; entries lie `count` apart
 struct HessianWsLayout {
@@ -768,6 +783,34 @@ static inline FeedbackDesc covo_feedback_desc(const covo_ctx *h, int e, const fl
     f.aux_out = h->feedback_a + (size_t)COVO_MAX_ENVS * COVO_FEEDBACK_LADDER * COVO_NA + (size_t)e * COVO_FEEDBACK_LADDER * COVO_FEEDBACK_AUX_FLOATS;
     return f;
 }
+// where a sweep over a step's instances leaves its results in the handle (capi.hip: riccati_reserve): the directions, the gradients,
+// the side rows behind the directions; gains: K, kff and x as well
+static inline RiccatiOut covo_riccati_out(const covo_ctx *h, bool gains)
+{
+    RiccatiOut o;
+    o.d = h->riccati_d;
+    o.g = h->refine_g;
+    o.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA;
+    if (gains) covo_feedback_sweep_out(h, o);
+    return o;
+}
+// instance e's line search on the direction of that sweep; f: its generator launch, whose sequences then compete (fb_row_out: their row), or null
+static inline RefineDesc covo_riccati_refine_desc(const RiccatiOut &o, int e, float *row_out, float *costs_out, const FeedbackDesc *f,
+                                                  float *fb_row_out)
+{
+    RefineDesc r;
+    r.g = o.g + (size_t)e * COVO_NA;
+    r.dir = o.d + (size_t)e * COVO_NA;
+    r.dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
+    r.row_out = row_out;
+    r.costs_out = costs_out;
+    if (f != nullptr) {
+        r.extra = f->a_out;
+        r.extra_aux = f->aux_out;
+        r.fb_row_out = fb_row_out;
+    }
+    return r;
+}
 // plan_hold.hip: one instance of a hold step / of a plan step's latch.  Both are the kernels' argument blocks as they stand (all
 // pointers: compared bytewise, no padding); what is null is null for every instance of a launch
 struct HoldDesc {
@@ -810,7 +853,7 @@ int launch_ilqr_tally(covo_ctx *h, int n_inst, bool batched, int j, int k, hipSt
 int covo_ilqr_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1, hipStream_t s);
 int covo_ilqr_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys, hipStream_t s);
 // step.hip: the hold step of a single / an env-batched schedule (age >= 1) in place of the step's own launches, and the plan trace
-// behind it (no arbiter, refinement, fan or posterior covariance: hold = true below)
+// behind it (no arbiter, refinement, fan or posterior covariance: AFTER_HOLD below)
 int covo_hold_step(covo_ctx *h, const covo_step_args *args, int age, int log_index, hipStream_t s);
 int covo_hold_step_batched(covo_ctx *h, const covo_batch_args *args, int age, int log_index, hipStream_t s);
 int launch_feedback_rollout(covo_ctx *h, const PlanInstDesc *inst, const FeedbackDesc *f, int n_inst, bool batched, hipStream_t s);
@@ -818,17 +861,19 @@ int launch_feedback_rollout_one(covo_ctx *h, const PlanInstDesc &d, const Feedba
 int launch_newton_refine(covo_ctx *h, const PlanInstDesc *inst, const RefineDesc *r, int n_inst, bool batched, hipStream_t s);
 int launch_newton_refine_one(covo_ctx *h, const PlanInstDesc &d, RolloutClip clip, const RefineDesc &r, hipStream_t s);
 void after_state_destroy(covo_ctx *h);  // (update_arbiter.hip) the three launches' device state: AfterState, after_step.hpp
-// step.hip: the recorder's launch behind a single / an env-batched step of this handle (no-ops with nothing attached);
-// states_true + trace_index >= 0: an episode driver's step, which also writes its trace row
-// arbiter_only: the arbiter's launch between two passes of an iterated step (covo_set_step_iters)
-// hold (keys: the instances' raw rng_act, host): behind a hold step of the plan hold -- the plan trace's launch alone, with the hold
-// step's own inputs
-int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only = false,
-                         bool hold = false);
-int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
-                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only = false,
-                            const uint32_t *hold_keys = nullptr);
+// step.hip: the after-step frame -- the launches behind a single / an env-batched step of this handle (no-ops with nothing attached);
+// states_true + trace_index >= 0: an episode driver's step, which also writes its trace row.  Its three forms (an iLQR step's
+// iterations are the fourth, chosen by the step's mode):
+enum AfterForm {
+    AFTER_BETWEEN,  // between two passes of an iterated step (covo_set_step_iters): the arbiter and the refinement alone
+    AFTER_STEP,     // behind a step: all of them
+    AFTER_HOLD,     // behind a hold step of the plan hold: the plan trace alone, on the hold step's own inputs
+};
+// keys: the instances' raw rng_act (host); read behind a hold step only
+int covo_plan_after_step(covo_ctx *h, AfterForm form, const covo_env_params *params, const covo_step_args *args, uint32_t key0,
+                         uint32_t key1, const float *f_shared, const float *state_true, int trace_index, hipStream_t s);
+int covo_plan_after_batched(covo_ctx *h, AfterForm form, const covo_batch_args *args, int mode, const covo_env_params *params,
+                            const uint32_t *keys, const float *states_true, int trace_index, hipStream_t s);
 int launch_env_step(float *state, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,
                     const covo_env_params &p, const float *action, const uint32_t *step_key, int noisy_on,
                     float obs_noise_scale, float *log, int log_index, hipStream_t s);

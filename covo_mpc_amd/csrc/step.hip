@@ -495,7 +495,7 @@ static int step_enqueue_all(covo_ctx *h, StepState *st, const covo_env_params *p
     // covo_set_step_iters: pass j >= 1 starts from the mean pass j - 1 committed (args->a_mean, never the caller's a_mean_in) and
     // walks the raw key on the device; the update arbiter's launch between two passes (step_run_passes)
     const int K = covo_step_iters(h);
-    auto between = [&](hipStream_t on, int) { return covo_plan_after_step(h, params, args, key0, key1, f_shared, nullptr, -1, on, true); };
+    auto between = [&](hipStream_t on, int) { return covo_plan_after_step(h, AFTER_BETWEEN, params, args, key0, key1, f_shared, nullptr, -1, on); };
     const char *name = "covo_mpc_step";
     switch (step_form(h, small, *params, *args, reuse)) {
     case STEP_ONE_LAUNCH: {
@@ -1076,7 +1076,7 @@ int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_
     rc = step_run_passes(
         h, c->cache, reuse, graph_cache_seen(c->cache[reuse ? 1 : 0], same), s, "covo_mpc_step_batched",
         [&](hipStream_t on, int j) { return batch_enqueue(h, b, *args, on, DebugMasks(), j, reuse); },
-        [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, COVO_MODE_COVO_ONLINE, params, nullptr, -1, on, true); });
+        [&](hipStream_t on, int) { return covo_plan_after_batched(h, AFTER_BETWEEN, args, COVO_MODE_COVO_ONLINE, params, nullptr, nullptr, -1, on); });
     if (rc == 0) covo_sigma_step_done(h, age, b->L, args->sample_sigma, E);
     if (rc == 0 && !reuse && covo_sigma_adapt_on(h)) return launch_sigma_adapt_idle(h->adapt_rows, E, s);  // (eager, behind the step)
     return rc;
@@ -1259,7 +1259,7 @@ int covo_step_batched_staged_impl(covo_ctx *h, const covo_batch_mode_args *m, co
     return step_run_passes(
         h, c->cache, false, graph_cache_seen(c->cache[0], same), s, "covo_mpc_step_batched_mode",
         [&](hipStream_t on, int j) { return batch_staged_enqueue(h, b, *m, on, j); },
-        [&](hipStream_t on, int) { return covo_plan_after_batched(h, args, m->mode, params, nullptr, -1, on, true); });
+        [&](hipStream_t on, int) { return covo_plan_after_batched(h, AFTER_BETWEEN, args, m->mode, params, nullptr, nullptr, -1, on); });
 }
 
 // ---- the hold step of the plan hold (covo_set_step_plan_hold; plan_hold.hip): ONE launch in place of the step's own -- stage `age`
@@ -1282,7 +1282,7 @@ static HoldDesc hold_desc(const covo_ctx *h, int e, const float *state, const fl
     d.a_mean = a_mean;
     d.a_cov = a_cov;
     d.row_out = h->hold_rows + (size_t)e * COVO_HOLD_FLOATS;
-    d.log = h->hold_log ? h->hold_log + (size_t)e * h->hold_log_stride * COVO_HOLD_FLOATS : nullptr;
+    d.log = covo_eplog_inst(h, COVO_EPLOG_HOLD, e, COVO_HOLD_FLOATS);
     return d;
 }
 int covo_hold_step(covo_ctx *h, const covo_step_args *args, int age, int log_index, hipStream_t s)
@@ -1341,7 +1341,8 @@ int covo_ilqr_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const 
     return launch_disturb_tables_batched(c->models, args->states, c->dyn, E, 1, c->tab_rollout, b->tab_hess, s);
 }
 
-// ---- the launches behind a step (after_step.hpp: the update arbiter, the flight recorder's plan and trace, the sample fan), eager.
+// ---- the after-step frame: the launches behind a step (after_step.hpp: the update arbiter, the flight recorder's plan and trace, the
+// sample fan; the refinements; the posterior covariance), eager.
 // What they need to know about ONE instance of the step that has just been enqueued: the inputs its sample rollouts had.  The shared
 // vector is re-derived from the raw key by the launches themselves (every step path forms it from the same device function); the
 // per-step tables are the ones the step has just built in its own scratch.  key_mem: the instance's raw rng_act in device memory;
@@ -1368,283 +1369,226 @@ static PlanInstDesc plan_inst(const BatchInst &i, int T, int N, const covo_env_p
     d.shared_noise_scale = covo_shared_noise_scale(*params, deterministic);
     return d;
 }
-// the arbiter first: the plan, the trace's u and the env step see its mean; trace_index: the episode's row index (the fan log counts
-// like the trace)
-// covo_set_step_refine: what the Newton refinement of a covo-online step's n instances needs beyond their descriptors -- the
-// Hessian's own inputs (grad: dense over the instances, a_mean = the committed means) and the Sigma the step sampled from
-struct RefineStep {
-    HessianDesc grad;
-    const float *Sigma;  // [n][128][128]
-    float sample_sigma;
+// ... and about the step of n instances as a whole, built once per call for the form it runs in (AfterForm, covo_common.hpp; an iLQR
+// step by its mode) by after_frame_single / after_frame_batched
+struct AfterFrame {
+    PlanInstDesc d[COVO_MAX_ENVS];
+    int n;
+    bool batched;          // the launches take their batched form: argument blocks in device memory, the keys from key_mem
+    HessianDesc hess;      // the Hessian's inputs at the committed means, dense over the instances; f_tab: left to the entry point,
+                           // which sets it next to the launch that forms the table
+    bool refine, riccati;  // the step runs the Newton / the Riccati refinement (never both: check_step_attachments)
+    const float *Sigma;    // [n][128][128] the Sigma the step sampled from (the Newton refinement's), with ...
+    float sample_sigma;    // ... its sample_sigma
+    const float *a, *cost, *mu;  // the posterior covariance's inputs, dense over the instances: samples, costs, the means sampled around
+    int N;
 };
-// the gradient's two launches at the committed means, then the line search with c^2 from the Sigma chain's slots of this step
-static int refine_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const RefineStep &rs, hipStream_t s)
+// something behind a step is attached
+static bool after_any(const covo_ctx *h)
 {
-    if (int rc = launch_cost_gradient(rs.grad, h->refine_g, h->ws_grad, s)) return rc;
+    return covo_plan_on(h) || covo_fan_on(h) || covo_arb_on(h) || covo_post_cov_on(h) || covo_refine_on(h) || covo_riccati_on(h);
+}
+// a single step (st: its scratch, null before the first one).  Neither a hold step nor an iLQR step has sampled: no nominal, and
+// never the batched form.  An iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose
+// raw key lies in device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
+static void after_frame_single(const covo_ctx *h, const StepState *st, AfterFrame &f, AfterForm form, const covo_env_params *params,
+                               const covo_step_args *args, uint32_t key0, uint32_t key1, const float *f_shared)
+{
+    const bool sampled = form != AFTER_HOLD && args->mode != COVO_MODE_ILQR;
+    f.n = 1;
+    f.batched = sampled && covo_step_iters(h) > 1 && st != nullptr;
+    const BatchInst i = {args->state, args->pos_traj, args->vel_traj, args->a_mean, args->a, args->cost, args->groupmin};
+    PlanInstDesc &d = f.d[0];
+    d = plan_inst(i, args->T, args->n_samples, params, args->derive_keys, args->rollout_deterministic,
+                  !sampled ? nullptr : (args->a_mean_shift ? args->a_mean_shift : (st ? st->a_mean_shift : nullptr)),
+                  (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr, f.batched ? st->dyn + 10 : nullptr);
+    d.key[0] = key0;
+    d.key[1] = key1;
+    for (int c = 0; c < 3; ++c) d.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
+    f.hess = covo_hessian_inputs(args->state, args->pos_traj, args->vel_traj, args->T, params, args->a_mean, nullptr, 1);
+    f.refine = sampled && covo_refine_on(h) && args->mode == COVO_MODE_COVO_ONLINE && st != nullptr;
+    f.riccati = form != AFTER_HOLD && covo_riccati_on(h);  // every mode, every step of a Sigma period
+    f.Sigma = !f.refine ? nullptr : (args->a_cov ? args->a_cov : st->Sigma);
+    f.sample_sigma = args->sample_sigma;
+    // (d.a_nominal is the mean the last pass sampled around)
+    f.a = d.a, f.cost = d.cost, f.mu = d.a_nominal, f.N = d.N;
+}
+// an env-batched step in `mode`.  c: the batch whose begin launch has left the shifted means and parked the raw keys at [10..11] of
+// the instances' blocks, or null behind the fused launch, which leaves [0..1] alone; a hold step's keys were parked in the handle.
+// nominal: the update arbiter's, or null.  CoVO's rollouts are deterministic
+static void after_frame_batched(const covo_ctx *h, const BatchState *b, const BatchCommon *c, AfterFrame &f, AfterForm form,
+                                const covo_batch_args *args, int mode, const covo_env_params *params, const float *nominal)
+{
+    const int E = args->n_envs;
+    f.n = E;
+    f.batched = true;
+    for (int e = 0; e < E; ++e)
+        f.d[e] = plan_inst(batch_inst(*args, e), args->T, args->n_samples, &params[e], 1, mode != COVO_MODE_MPPI,
+                           nominal ? nominal + (size_t)e * COVO_NA : nullptr,
+                           (c && c->tables) ? c->tab_rollout + (size_t)e * COVO_H * 4 : nullptr,
+                           form == AFTER_HOLD ? h->hold_keys + 12 * e + 10 : (c ? c->dyn + 12 * e + 10 : b->small.dyn + 12 * e));
+    // the refinements: the batches with per-instance Hessian constants only (check_batch_step refuses the other modes)
+    const bool online = mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_ILQR;
+    f.refine = form != AFTER_HOLD && covo_refine_on(h) && online;
+    f.riccati = form != AFTER_HOLD && covo_riccati_on(h) && online;
+    if (f.refine || f.riccati) {
+        f.hess = covo_hessian_inputs(args->states, args->pos_traj, args->vel_traj, args->T, &c->params[0], args->a_mean, nullptr, E);
+        f.hess.consts_dev = b->consts;
+        f.hess.traj_stride = (size_t)args->T * 3;
+        f.hess.models_dev = c->models;
+    }
+    f.Sigma = !f.refine ? nullptr : (args->a_cov ? args->a_cov : b->Sigma);
+    f.sample_sigma = args->sample_sigma;
+    // (never behind the fused launch: check_batch_step) dense slices, the begin launch's shifted means
+    f.a = args->a, f.cost = args->cost, f.mu = c ? c->a_mean_shift : nullptr, f.N = args->n_samples;
+}
+
+// covo_set_step_refine: the gradient's two launches at the committed means, then the line search with c^2 from the Sigma chain's slots
+// of this step
+static int refine_after(covo_ctx *h, const AfterFrame &f, hipStream_t s)
+{
+    if (int rc = launch_cost_gradient(f.hess, h->refine_g, h->ws_grad, s)) return rc;
     size_t stride;
-    const double *sumlogB = sigma_ns_sumlogB(h->ws_sigma, n, &stride);
+    const double *sumlogB = sigma_ns_sumlogB(h->ws_sigma, f.n, &stride);
     RefineDesc r[COVO_MAX_ENVS];
-    for (int e = 0; e < n; ++e) {
+    for (int e = 0; e < f.n; ++e) {
         r[e].g = h->refine_g + (size_t)e * COVO_NA;
-        r[e].Sigma = rs.Sigma + (size_t)e * COVO_NA * COVO_NA;
+        r[e].Sigma = f.Sigma + (size_t)e * COVO_NA * COVO_NA;
         r[e].sumlogB = sumlogB + (size_t)e * stride;
-        r[e].sample_sigma = rs.sample_sigma;
+        r[e].sample_sigma = f.sample_sigma;
         r[e].row_out = h->refine_out + (size_t)e * COVO_REFINE_FLOATS;
     }
-    return launch_newton_refine(h, d, r, n, batched, s);
+    return launch_newton_refine(h, f.d, r, f.n, f.batched, s);
 }
 // covo_set_step_riccati: the Hessian's first two launches at the committed means into the refinement's own workspace, the sweep
-// (riccati.hip), [the closed-loop generator (feedback_rollout.hip),] then the line search with the direction supplied.  hd: the
-// Hessian's inputs, dense over the n instances
+// (riccati.hip), [the closed-loop generator (feedback_rollout.hip),] then the line search with the direction supplied
 // covo_set_step_plan_hold: the sweep leaves its gains whether or not the closed-loop candidates are on, and the latch (plan_hold.hip)
 // sits between the sweep and the line search, which overwrites the mean the sweep ran at; row: the episode's row index, < 0: none
-static int riccati_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, HessianDesc hd, int row, hipStream_t s)
+// costs: where instance 0's candidate costs of this call go (test hook: an iteration's slot of h->ilqr_costs), or null
+static int riccati_after(covo_ctx *h, const AfterFrame &f, int row, float *costs, hipStream_t s)
 {
+    HessianDesc hd = f.hess;
     hd.status_dev = h->status_dev;
-    RiccatiOut o;
-    o.d = h->riccati_d;
-    o.g = h->refine_g;
-    o.side = h->riccati_d + (size_t)COVO_MAX_ENVS * COVO_NA;
     // covo_set_step_riccati_feedback: the sweep also leaves its gains, the generator (feedback_rollout.hip) runs the closed-loop
     // sequences under them, and the line search judges them next to its own
     const bool feedback = covo_feedback_on(h);
     const bool hold = covo_plan_hold(h) > 1;
-    if (feedback || hold) covo_feedback_sweep_out(h, o);
+    const RiccatiOut o = covo_riccati_out(h, feedback || hold);
     if (int rc = launch_riccati(hd, COVO_RICCATI_REG0, o, h->ws_riccati, s)) return rc;
     if (hold) {
         LatchDesc l[COVO_MAX_ENVS];
-        for (int e = 0; e < n; ++e) {
-            l[e].a_mean = d[e].a_mean_out;
-            l[e].state = d[e].state;
+        for (int e = 0; e < f.n; ++e) {
+            l[e].a_mean = f.d[e].a_mean_out;
+            l[e].state = f.d[e].state;
             l[e].b_out = h->hold_b + (size_t)e * COVO_NA;
             l[e].t_out = h->hold_t + e;
             l[e].row_out = h->hold_rows + (size_t)e * COVO_HOLD_FLOATS;
-            l[e].log = h->hold_log ? h->hold_log + (size_t)e * h->hold_log_stride * COVO_HOLD_FLOATS : nullptr;
+            l[e].log = covo_eplog_inst(h, COVO_EPLOG_HOLD, e, COVO_HOLD_FLOATS);
         }
-        if (int rc = launch_plan_latch(h, l, n, batched, row, s)) return rc;
+        if (int rc = launch_plan_latch(h, l, f.n, f.batched, row, s)) return rc;
     }
     RefineDesc r[COVO_MAX_ENVS];
-    FeedbackDesc f[COVO_MAX_ENVS];
-    for (int e = 0; e < n; ++e) {
-        r[e].g = o.g + (size_t)e * COVO_NA;
-        r[e].dir = o.d + (size_t)e * COVO_NA;
-        r[e].dir_side = o.side + (size_t)e * COVO_RICCATI_SIDE;
-        r[e].row_out = h->riccati_out + (size_t)e * COVO_RICCATI_FLOATS;
-        if (h->ilqr_costs != nullptr && h->ilqr_slot > 0)  // (test hook: the candidates' costs of an iLQR step's iteration)
-            r[e].costs_out = h->ilqr_costs + ((size_t)e * COVO_MAX_STEP_ITERS + (h->ilqr_slot - 1)) * COVO_FEEDBACK_CANDIDATES;
-        if (feedback) {
-            f[e] = covo_feedback_desc(h, e, d[e].a_mean_out);
-            r[e].extra = f[e].a_out;
-            r[e].extra_aux = f[e].aux_out;
-            r[e].fb_row_out = h->feedback_out + (size_t)e * COVO_FEEDBACK_FLOATS;
-        }
+    FeedbackDesc fb[COVO_MAX_ENVS];
+    for (int e = 0; e < f.n; ++e) {
+        if (feedback) fb[e] = covo_feedback_desc(h, e, f.d[e].a_mean_out);
+        r[e] = covo_riccati_refine_desc(o, e, h->riccati_out + (size_t)e * COVO_RICCATI_FLOATS,
+                                        costs ? costs + (size_t)e * COVO_MAX_STEP_ITERS * COVO_FEEDBACK_CANDIDATES : nullptr,
+                                        feedback ? &fb[e] : nullptr,
+                                        feedback ? h->feedback_out + (size_t)e * COVO_FEEDBACK_FLOATS : nullptr);
     }
     if (feedback)
-        if (int rc = launch_feedback_rollout(h, d, f, n, batched, s)) return rc;
-    return launch_newton_refine(h, d, r, n, batched, s);
+        if (int rc = launch_feedback_rollout(h, f.d, fb, f.n, f.batched, s)) return rc;
+    return launch_newton_refine(h, f.d, r, f.n, f.batched, s);
 }
-// the refinement (rs / ric: null for the steps that have none) directly behind the arbiter, every pass of an iterated step included
-static int plan_after(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const float *states_true, int trace_index, hipStream_t s,
-                      bool arbiter_only, const RefineStep *rs, const HessianDesc *ric = nullptr)
+// the arbiter first: the plan, the trace's u and the env step see its mean; trace_index: the episode's row index (the fan log counts
+// like the trace).  The refinement directly behind the arbiter, every pass of an iterated step included; the posterior covariance
+// last, behind the (last pass's) update and the launches above
+static int plan_after(covo_ctx *h, const AfterFrame &f, AfterForm form, const float *states_true, int trace_index, hipStream_t s)
 {
-    int rc = launch_update_arbiter(h, d, n, batched, trace_index, s);
-    if (rc == 0 && rs != nullptr && covo_refine_on(h)) rc = refine_after(h, d, n, batched, *rs, s);
-    if (rc == 0 && ric != nullptr && covo_riccati_on(h)) rc = riccati_after(h, d, n, batched, *ric, trace_index, s);
-    if (rc || arbiter_only) return rc;
-    if ((rc = launch_plan_trace(h, d, n, batched, states_true, trace_index, s))) return rc;
-    return launch_sample_fan(h, d, n, batched, trace_index, s);
+    int rc = launch_update_arbiter(h, f.d, f.n, f.batched, trace_index, s);
+    if (rc == 0 && f.refine) rc = refine_after(h, f, s);
+    if (rc == 0 && f.riccati) rc = riccati_after(h, f, trace_index, nullptr, s);
+    if (rc || form == AFTER_BETWEEN) return rc;
+    if ((rc = launch_plan_trace(h, f.d, f.n, f.batched, states_true, trace_index, s))) return rc;
+    if ((rc = launch_sample_fan(h, f.d, f.n, f.batched, trace_index, s))) return rc;
+    return launch_post_cov_after(h, f.a, f.cost, f.mu, f.N, f.n, s);
 }
 
 // the k iterations of an iLQR step behind its begin work: riccati_after as a sampling step enqueues it, k times on the same inputs (the
 // key is not walked: one objective per step), each followed by the tally (ilqr.hip); then the plan trace of the committed mean
-static int ilqr_iterations(covo_ctx *h, const PlanInstDesc *d, int n, bool batched, const HessianDesc &ric, const float *states_true,
-                           int trace_index, hipStream_t s)
+static int ilqr_iterations(covo_ctx *h, const AfterFrame &f, const float *states_true, int trace_index, hipStream_t s)
 {
     const int K = covo_step_iters(h);
     for (int j = 0; j < K; ++j) {
-        h->ilqr_slot = j + 1;
-        int rc = riccati_after(h, d, n, batched, ric, trace_index, s);
-        h->ilqr_slot = 0;
-        if (rc || (rc = launch_ilqr_tally(h, n, batched, j, K, s))) return rc;
+        float *costs = h->ilqr_costs ? h->ilqr_costs + (size_t)j * COVO_FEEDBACK_CANDIDATES : nullptr;
+        int rc = riccati_after(h, f, trace_index, costs, s);
+        if (rc || (rc = launch_ilqr_tally(h, f.n, f.batched, j, K, s))) return rc;
     }
-    return launch_plan_trace(h, d, n, batched, states_true, trace_index, s);
+    return launch_plan_trace(h, f.d, f.n, f.batched, states_true, trace_index, s);
 }
 
-int covo_plan_after_step(covo_ctx *h, const covo_env_params *params, const covo_step_args *args, uint32_t key0, uint32_t key1,
-                         const float *f_shared, const float *state_true, int trace_index, hipStream_t s, bool arbiter_only, bool hold)
+int covo_plan_after_step(covo_ctx *h, AfterForm form, const covo_env_params *params, const covo_step_args *args, uint32_t key0,
+                         uint32_t key1, const float *f_shared, const float *state_true, int trace_index, hipStream_t s)
 {
-    if (hold) {
-        // behind a hold step: the plan trace alone.  The rollouts' disturbance table is formed here from the raw key, into the step's
-        // own scratch (the hold step has enqueued none of the step's launches)
-        if (!covo_plan_on(h)) return 0;
-        StepState *hs = reinterpret_cast<StepState *>(h->step);
-        const BatchInst hi = {args->state, args->pos_traj, args->vel_traj, args->a_mean, args->a, args->cost, args->groupmin};
-        const bool tables = covo_needs_tables(*params) && hs != nullptr;
-        PlanInstDesc hd = plan_inst(hi, args->T, args->n_samples, params, args->derive_keys, args->rollout_deterministic, nullptr,
-                                    tables ? hs->f_tab_rollout : nullptr, nullptr);
-        hd.key[0] = key0;
-        hd.key[1] = key1;
-        for (int c = 0; c < 3; ++c) hd.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
-        if (tables) {
+    if (form == AFTER_HOLD ? !covo_plan_on(h) : !after_any(h)) return 0;
+    StepState *st = reinterpret_cast<StepState *>(h->step);
+    AfterFrame f;
+    after_frame_single(h, st, f, form, params, args, key0, key1, f_shared);
+    const bool tables = covo_needs_tables(*params);
+    if (form == AFTER_HOLD) {
+        // the plan trace alone.  The rollouts' disturbance table is formed here from the raw key, into the step's own scratch (the
+        // hold step has enqueued none of the step's launches)
+        if (tables && st != nullptr) {
             const uint32_t raw[2] = {key0, key1};
             hold_park_keys(h->hold_keys, raw, 1, s);
-            if (int rc = launch_disturb_tables_step(*params, args->state, h->hold_keys, args->rollout_deterministic, hs->f_tab_rollout,
+            if (int rc = launch_disturb_tables_step(*params, args->state, h->hold_keys, args->rollout_deterministic, st->f_tab_rollout,
                                                     nullptr, s)) return rc;
         }
-        return launch_plan_trace(h, &hd, 1, false, state_true, trace_index, s);
+        return launch_plan_trace(h, f.d, 1, false, state_true, trace_index, s);
     }
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
-    StepState *st = reinterpret_cast<StepState *>(h->step);
-    if (args->mode == COVO_MODE_ILQR) {
-        // the iterations of an iLQR step: the raw key as the call got it (not walked), the Hessian's table formed from it once
-        const BatchInst li = {args->state, args->pos_traj, args->vel_traj, args->a_mean, args->a, args->cost, args->groupmin};
-        const bool tables = covo_needs_tables(*params);
-        PlanInstDesc ld = plan_inst(li, args->T, args->n_samples, params, args->derive_keys, args->rollout_deterministic, nullptr,
-                                    tables ? st->f_tab_rollout : nullptr, nullptr);
-        ld.key[0] = key0;
-        ld.key[1] = key1;
-        for (int c = 0; c < 3; ++c) ld.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
-        HessianDesc lr;
-        lr.state = ld.state;
-        lr.pos_traj = ld.pos_traj;
-        lr.vel_traj = ld.vel_traj;
-        lr.T = ld.T;
-        lr.params = params;
-        lr.a_mean = args->a_mean;
-        if (tables) {
-            if (int rc = launch_disturb_table(*params, ld.state, 1, nullptr, key0, key1, COVO_DISTURB_KEYS_HESSIAN, 1, h->riccati_tab, s))
-                return rc;
-            lr.f_tab = h->riccati_tab;
-        }
-        return ilqr_iterations(h, &ld, 1, false, lr, state_true, trace_index, s);
+    if (f.refine && tables) f.hess.f_tab = st->f_tab_hess;  // the step's own Hessian has left it
+    if (f.riccati && tables) {
+        // the sweep's is formed here from the raw key, as the call got it or as the pass left it (MPPI, covo-offline and reuse steps
+        // build none; a refresh step's own holds the same rows)
+        if (int rc = launch_disturb_table(*params, args->state, 1, f.d[0].key_mem, key0, key1, COVO_DISTURB_KEYS_HESSIAN, 1, h->riccati_tab, s))
+            return rc;
+        f.hess.f_tab = h->riccati_tab;
     }
-    // an iterated step (covo_set_step_iters): the launches describe the pass that has just been enqueued, whose raw key lies in
-    // device memory (st->dyn[10..11]) -- they take it from there, through the argument blocks of the batched form
-    const bool iterated = covo_step_iters(h) > 1 && st != nullptr;
-    const BatchInst i = {args->state, args->pos_traj, args->vel_traj, args->a_mean, args->a, args->cost, args->groupmin};
-    PlanInstDesc d = plan_inst(i, args->T, args->n_samples, params, args->derive_keys, args->rollout_deterministic,
-                               args->a_mean_shift ? args->a_mean_shift : (st ? st->a_mean_shift : nullptr),
-                               (covo_needs_tables(*params) && st) ? st->f_tab_rollout : nullptr, iterated ? st->dyn + 10 : nullptr);
-    d.key[0] = key0;
-    d.key[1] = key1;
-    for (int c = 0; c < 3; ++c) d.f_shared[c] = f_shared ? f_shared[c] : 0.0f;
-    RefineStep rs;
-    const bool refine = covo_refine_on(h) && args->mode == COVO_MODE_COVO_ONLINE && st != nullptr;
-    if (refine) {
-        rs.grad.state = d.state;
-        rs.grad.pos_traj = d.pos_traj;
-        rs.grad.vel_traj = d.vel_traj;
-        rs.grad.T = d.T;
-        rs.grad.params = params;
-        rs.grad.a_mean = args->a_mean;
-        rs.grad.f_tab = covo_needs_tables(*params) ? st->f_tab_hess : nullptr;
-        rs.Sigma = args->a_cov ? args->a_cov : st->Sigma;
-        rs.sample_sigma = args->sample_sigma;
-    }
-    // the Riccati refinement: every mode, every step of a Sigma period.  The Hessian's disturbance table is formed here from the raw key
-    // (MPPI, covo-offline and reuse steps build none; a refresh step's own holds the same rows)
-    HessianDesc ric;
-    const bool riccati = covo_riccati_on(h);
-    if (riccati) {
-        ric.state = d.state;
-        ric.pos_traj = d.pos_traj;
-        ric.vel_traj = d.vel_traj;
-        ric.T = d.T;
-        ric.params = params;
-        ric.a_mean = args->a_mean;
-        if (covo_needs_tables(*params)) {
-            if (int rc = launch_disturb_table(*params, d.state, 1, d.key_mem, key0, key1, COVO_DISTURB_KEYS_HESSIAN, 1, h->riccati_tab, s))
-                return rc;
-            ric.f_tab = h->riccati_tab;
-        }
-    }
-    if (int rc = plan_after(h, &d, 1, iterated, state_true, trace_index, s, arbiter_only, refine ? &rs : nullptr, riccati ? &ric : nullptr))
-        return rc;
-    // the posterior covariance: behind the (last pass's) update and the launches above; d.a_nominal is the mean that pass sampled around
-    return arbiter_only ? 0 : launch_post_cov_after(h, d.a, d.cost, d.a_nominal, d.N, 1, s);
+    // the iterations of an iLQR step: the raw key as the call got it (not walked)
+    if (args->mode == COVO_MODE_ILQR) return ilqr_iterations(h, f, state_true, trace_index, s);
+    return plan_after(h, f, form, state_true, trace_index, s);
 }
 
-// mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run) or MPPI / COVO_OFFLINE (covo_step_batched_small_impl)
-int covo_plan_after_batched(covo_ctx *h, const covo_batch_args *args, int mode, const covo_env_params *params,
-                            const float *states_true, int trace_index, hipStream_t s, bool arbiter_only, const uint32_t *hold_keys)
+// mode: COVO_MODE_COVO_ONLINE (covo_step_batched_impl has run), COVO_MODE_ILQR (covo_ilqr_step_batched_impl, on covo-online's scratch)
+// or MPPI / COVO_OFFLINE (covo_step_batched_small_impl / _staged_impl)
+int covo_plan_after_batched(covo_ctx *h, AfterForm form, const covo_batch_args *args, int mode, const covo_env_params *params,
+                            const uint32_t *keys, const float *states_true, int trace_index, hipStream_t s)
 {
-    if (hold_keys != nullptr) {
-        // behind a hold step (covo-online batches only: the others refuse the Riccati refinement): the plan trace alone, the instances'
-        // raw keys parked where a begin launch would have left them, the rollouts' tables formed from them into the batch's scratch
-        if (!covo_plan_on(h)) return 0;
-        BatchState *hb = reinterpret_cast<BatchState *>(h->batch);
-        const BatchCommon *hc = &hb->online;
-        const int n = args->n_envs;
-        hold_park_keys(h->hold_keys, hold_keys, n, s);
-        if (hc->tables)
-            if (int rc = launch_disturb_tables_batched(hc->models, args->states, h->hold_keys, n, 1, hc->tab_rollout, nullptr, s)) return rc;
-        PlanInstDesc hd[COVO_MAX_ENVS];
-        for (int e = 0; e < n; ++e)
-            hd[e] = plan_inst(batch_inst(*args, e), args->T, args->n_samples, &params[e], 1, mode != COVO_MODE_MPPI, nullptr,
-                              hc->tables ? hc->tab_rollout + (size_t)e * COVO_H * 4 : nullptr, h->hold_keys + 12 * e + 10);
-        return launch_plan_trace(h, hd, n, true, states_true, trace_index, s);
-    }
-    if (!covo_plan_on(h) && !covo_fan_on(h) && !covo_arb_on(h) && !covo_post_cov_on(h) && !covo_refine_on(h) && !covo_riccati_on(h)) return 0;
+    if (form == AFTER_HOLD ? !covo_plan_on(h) : !after_any(h)) return 0;
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     const int E = args->n_envs;
-    const bool online = mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_ILQR;  // (the iLQR step runs on covo-online's scratch)
-    // the batch whose begin launch has left the shifted means and parked the raw keys: covo-online's, the staged MPPI / covo-offline
-    // step's (covo_set_step_batched_staged), or none behind the fused launch
+    // the batch with a begin launch: covo-online's (a hold step's too: the others refuse the Riccati refinement), the staged MPPI /
+    // covo-offline step's (covo_set_step_batched_staged), or none behind the fused launch
+    const bool online = mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_ILQR || form == AFTER_HOLD;
     const BatchCommon *c = online ? &b->online : (covo_batched_staged(h) ? &b->staged : nullptr);
-    const bool begun = c != nullptr;
-    const float *shifted = c ? c->a_mean_shift : nullptr;
-    const float *tabs = (c && c->tables) ? c->tab_rollout : nullptr;
-    const uint32_t *dyn = c ? c->dyn : b->small.dyn;
-    PlanInstDesc d[COVO_MAX_ENVS];
     const float *nominal = nullptr;  // the update arbiter's: a begin launch leaves it, the fused launch's was formed ahead of it
-    if (covo_arb_on(h)) {
-        if (begun) nominal = shifted;
+    if (form != AFTER_HOLD && covo_arb_on(h)) {
+        if (c != nullptr) nominal = c->a_mean_shift;
         else if (int rc = launch_arbiter_nominal(h, nullptr, E, s, &nominal)) return rc;
     }
-    // the instance's raw rng_act: a begin launch parks it at [10..11] of its block, the fused launch leaves [0..1] alone;
-    // CoVO's rollouts are deterministic
-    for (int e = 0; e < E; ++e)
-        d[e] = plan_inst(batch_inst(*args, e), args->T, args->n_samples, &params[e], 1, mode != COVO_MODE_MPPI,
-                         nominal ? nominal + (size_t)e * COVO_NA : nullptr, tabs ? tabs + (size_t)e * COVO_H * 4 : nullptr,
-                         begun ? dyn + 12 * e + 10 : dyn + 12 * e);
-    RefineStep rs;
-    const bool refine = covo_refine_on(h) && online;
-    if (refine) {
-        rs.grad.state = args->states;
-        rs.grad.pos_traj = args->pos_traj;
-        rs.grad.vel_traj = args->vel_traj;
-        rs.grad.T = args->T;
-        rs.grad.params = &c->params[0];
-        rs.grad.a_mean = args->a_mean;
-        rs.grad.batch = E;
-        rs.grad.consts_dev = b->consts;
-        rs.grad.traj_stride = (size_t)args->T * 3;
-        rs.grad.f_tab = c->tables ? b->tab_hess : nullptr;
-        rs.grad.models_dev = c->models;
-        rs.Sigma = args->a_cov ? args->a_cov : b->Sigma;
-        rs.sample_sigma = args->sample_sigma;
+    AfterFrame f;
+    after_frame_batched(h, b, c, f, form, args, mode, params, nominal);
+    if (form == AFTER_HOLD) {
+        // the plan trace alone, the instances' raw keys parked where a begin launch would have left them, the rollouts' tables formed
+        // from them into the batch's scratch
+        hold_park_keys(h->hold_keys, keys, E, s);
+        if (c->tables)
+            if (int rc = launch_disturb_tables_batched(c->models, args->states, h->hold_keys, E, 1, c->tab_rollout, nullptr, s)) return rc;
+        return launch_plan_trace(h, f.d, E, true, states_true, trace_index, s);
     }
-    HessianDesc ric;
-    const bool riccati = covo_riccati_on(h) && online;  // (check_batch_step refuses the other modes)
-    if (riccati) {
-        ric.state = args->states;
-        ric.pos_traj = args->pos_traj;
-        ric.vel_traj = args->vel_traj;
-        ric.T = args->T;
-        ric.params = &c->params[0];
-        ric.a_mean = args->a_mean;
-        ric.batch = E;
-        ric.consts_dev = b->consts;
-        ric.traj_stride = (size_t)args->T * 3;
-        ric.f_tab = c->tables ? b->tab_hess : nullptr;
-        ric.models_dev = c->models;
-    }
-    if (mode == COVO_MODE_ILQR) return ilqr_iterations(h, d, E, true, ric, states_true, trace_index, s);  // (riccati: the step's own checks)
-    if (int rc = plan_after(h, d, E, true, states_true, trace_index, s, arbiter_only, refine ? &rs : nullptr, riccati ? &ric : nullptr))
-        return rc;
-    // the posterior covariance of every instance (never behind the fused launch: check_batch_step): dense slices, the begin launch's
-    // shifted means
-    return arbiter_only ? 0 : launch_post_cov_after(h, args->a, args->cost, shifted, args->n_samples, E, s);
+    if ((f.refine || f.riccati) && c->tables) f.hess.f_tab = b->tab_hess;
+    if (mode == COVO_MODE_ILQR) return ilqr_iterations(h, f, states_true, trace_index, s);  // (riccati: the step's own checks)
+    return plan_after(h, f, form, states_true, trace_index, s);
 }
 
 // test hook: the factor(s) the LAST single (batched = 0) / env-batched step sampled from -- what the next reuse step of a Sigma period

@@ -16,7 +16,7 @@ csrc/ilqr.hip around the unchanged kernels of riccati=, riccati_feedback= and pl
 6. batched (E = 3, different parameters, states and keys) equals three singles over 4 steps, with and without plan_hold=3: means and
    all three row buffers as words.
 7. the device episode equals the host loop over 7 steps with plan_hold=3 and compute_plan: trace u, hold log, final mean; ages
-   0, 1, 2, 0, 1, 2, 0 -- single and batched.
+   0, 1, 2, 0, 1, 2, 0 -- single and batched; batched also under the periodic disturbance (per-step tables behind a hold step).
 8. the plan hold uses the last iteration: at k = 2 the latch's b is b_1, and hold step 1's u is core.plan_hold on that latch.
 9. the C side refuses a step in COVO_MODE_ILQR on a handle without the sweep or with a sampling attachment, by name, before any launch.
 """
@@ -375,8 +375,14 @@ def test_run_episode_equals_the_host_loop():
 
 
 def test_batched_run_episode_equals_the_host_loop():
+    _batched_run_episode_equals_the_host_loop("gaussian")
+    # per-step disturbance tables: the hold steps' plan trace forms its own from the instances' parked keys
+    _batched_run_episode_equals_the_host_loop("periodic")
+
+
+def _batched_run_episode_equals_the_host_loop(disturb):
     E, T, m = 3, 7, 3
-    env = quad_env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True, disturb=disturb)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     rngs0 = np.stack([np.asarray(cr.PRNGKey(60 + e)) for e in range(E)])

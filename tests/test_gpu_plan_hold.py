@@ -13,9 +13,10 @@
 5. the schedule of mppi, covo-offline and covo-online over 7 teacher-forced states: ages 0 1 2 0 1 2 0; a plan step equals a riccati=True
    controller without plan_hold on the same mean, state and key; a hold step equals the primitive on the latch; reset() restarts.
 6. plan_hold=1 is off.
-7. run_episode (12 steps, m = 4) equals the Python loop; the hold log's ages; the trace's u rows of hold steps.
-8. batched (E = 3): hold steps equal the single controllers'; an instance reset on the device during a hold segment drops its
-   feedback term (flag bit 2), the others are untouched.
+7. run_episode (12 steps, m = 4) equals the Python loop; the hold log's ages; the trace's u rows of hold steps.  Also covo-online
+   under the periodic disturbance at m = 3: the hold steps' plan trace then runs on per-step tables formed from the parked keys.
+8. batched (E = 3): hold steps equal the single controllers' -- under the periodic disturbance with the plan attached, their plan
+   rows too; an instance reset on the device during a hold segment drops its feedback term (flag bit 2), the others are untouched.
 """
 import functools
 
@@ -313,12 +314,15 @@ def test_plan_hold_one_is_off():
 
 
 # ------------------------------------------------------------------------------------------ 7: the device loop equals the Python loop
-@pytest.mark.parametrize("name", ["mppi", "covo-online"])
-def test_run_episode_equals_the_python_loop(name):
+@pytest.mark.parametrize("name, disturb, m", [pytest.param("mppi", "gaussian", 4, id="mppi"),
+                                              pytest.param("covo-online", "gaussian", 4, id="covo-online"),
+                                              # a hold step's plan trace on per-step tables formed from its parked keys, at two hold ages
+                                              pytest.param("covo-online", "periodic", 3, id="covo-online-periodic")])
+def test_run_episode_equals_the_python_loop(name, disturb, m):
     import covo_mpc_amd as cm
-    env = quad_env(task="tracking_zigzag")
+    env = quad_env(task="tracking_zigzag", disturb=disturb)
     params = env.default_params
-    T, m = 12, 4
+    T = 12
     got = {}
     for mode in ("fused", "hand"):
         c, _ = cm.envs.get_controller(env, name, "N256_H32_lam0.01", device=DEV, compute_info=False, riccati=True, plan_hold=m,
@@ -362,32 +366,40 @@ def test_run_episode_equals_the_python_loop(name):
 
 # ------------------------------------------------------------------------------------------ 8: batched
 def test_batched_hold_steps_equal_singles():
+    _batched_hold_steps_equal_singles("gaussian", plan=False)
+    # the same with the plan attached under a disturbance with per-step tables: a hold step's plan trace on the instances' parked keys
+    _batched_hold_steps_equal_singles("periodic", plan=True)
+
+
+def _batched_hold_steps_equal_singles(disturb, plan):
     import covo_mpc_amd as cm
     N, E, m, T = 256, 3, 3, 4
-    env = quad_env(task="tracking", randomizer=True)
+    env = quad_env(task="tracking", randomizer=True, disturb=disturb)
     params = [env.sample_params(cr.PRNGKey(40 + e)) for e in range(E)]
     reset_keys = [cr.PRNGKey(50 + e) for e in range(E)]
     act = [np.stack([np.asarray(cr.PRNGKey(60 + 10 * k + e)) for e in range(E)]) for k in range(T)]
     stp = [np.stack([np.asarray(cr.PRNGKey(600 + 10 * k + e)) for e in range(E)]) for k in range(T)]
-    rows, means, us = [], [], []
+    rows, means, us, plans = [], [], [], []
     for e in range(E):
-        c, _ = cm.envs.get_controller(env, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False, riccati=True, plan_hold=m)
+        c, _ = cm.envs.get_controller(env, "covo-online", f"N{N}_H32_lam0.01", device=DEV, compute_info=False, riccati=True, plan_hold=m,
+                                      compute_plan=plan)
         se = cm.envs.DeviceEpisode(env, reset_keys[e], params[e], (c.core.lib, c.core.h), DEV)
         cp = c.reset(se.state0, params[e], c.init_control_params, cr.PRNGKey(2))
-        r, mm, uu = [], [], []
+        r, mm, uu, pp = [], [], [], []
         for k in range(T):
             u, cp, info = c(None, None, params[e], act[k][e], cp, {"noisy_state": se.noisy_state})
             assert info["plan_age"] == k % m
             r.append(c.core.plan_hold_rows[0].clone())
             mm.append(cp.a_mean.reshape(-1).clone())
             uu.append(u.reshape(-1).clone())
+            pp.append(c.core.plan[0].clone() if plan else None)
             se.step(stp[k][e], u)
         torch.cuda.synchronize()
-        rows.append(r), means.append(mm), us.append(uu)
+        rows.append(r), means.append(mm), us.append(uu), plans.append(pp)
         cp0 = c.init_control_params
         assert c.core.device_status() == 0
         c.core.close()
-    b = batched_controller(env, "covo-online", cp0, E, N, 0.01, riccati=True, plan_hold=m)
+    b = batched_controller(env, "covo-online", cp0, E, N, 0.01, riccati=True, plan_hold=m, compute_plan=plan)
     assert tuple(b.plan_hold_rows.shape) == (E, HF)
     ep = cm.envs.BatchedDeviceEpisode(env, reset_keys, params, (b.core.lib, b.core.h), DEV)
     b.bind_episode(ep)
@@ -399,6 +411,8 @@ def test_batched_hold_steps_equal_singles():
             assert torch.equal(bits32(u[e].reshape(-1)), bits32(us[e][k])), (k, e)
             assert torch.equal(bits32(b.a_mean[e]), bits32(means[e][k])), (k, e)
             assert torch.equal(bits32(b.plan_hold_rows[e]), bits32(rows[e][k])), (k, e, b.plan_hold_rows[e], rows[e][k])
+            if plan and k % m != 0:
+                assert bool(torch.isfinite(b.plan[e]).all()) and torch.equal(bits32(b.plan[e]), bits32(plans[e][k])), (k, e)
         ep.step(stp[k], b.a_mean)
     print(f"  hold rows of the last hold step: gains {[float(rows[e][2][2]) for e in range(E)]} flags {[int(ints(rows[e][2])[4]) for e in range(E)]}")
     assert all(float(rows[e][1][2]) > 0.0 and (int(ints(rows[e][1])[4]) & 4) == 0 for e in range(E))
