@@ -84,6 +84,9 @@ COVO_HAS_ILQR = 1  # the "ilqr" controller (COVO_MODE_ILQR, covo_set_step_ilqr):
 # none), bits(int32 iterations with choice > 16), bits(OR of the rows' flag words), |g|_2 of the last iteration, 0}
 COVO_ILQR_FLOATS = 8
 ILQR_FIELDS = ("cost_first", "cost", "moved", "fixed_at", "closed", "flags", "grad_norm")
+# riccati_box= on top of riccati= (covo_set_step_riccati_box, covo_riccati_box, covo_riccati_refine_box): the sweep's stages solve the
+# box QP on -1 <= clip(b) + du <= 1.  A mask word per stage: bits 0-3 coordinate i clamped at the lower bound, bits 4-7 at the upper
+COVO_HAS_RICCATI_BOX = 1
 # the episode logs of the attachments' rows (covo_set_episode_rows): the kinds, and the Sigma log's row {age, fallback, c, log det M}
 COVO_EPLOG_LAM, COVO_EPLOG_ELITE, COVO_EPLOG_ITERS, COVO_EPLOG_SIGMA, COVO_EPLOG_POST_AUX, COVO_EPLOG_POST_COV = range(6)
 COVO_EPLOG_KINDS = 6
@@ -272,6 +275,13 @@ _SIGS = {
     # the iLQR controller's per-iteration logs (covo_hip.h: COVO_HAS_ILQR)
     "covo_set_step_ilqr": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
     "covo_debug_ilqr_costs": (C.c_int, [_P, _P, C.c_int32]),
+    # the Riccati box (covo_hip.h: COVO_HAS_RICCATI_BOX)
+    "covo_riccati_box": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P,
+                                   _P]),
+    "covo_riccati_refine_box": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_float), _P, _P, _P, C.c_double,
+                                          C.c_int32, _P, _P, _P, C.c_int32, _P, _P]),
+    "covo_set_step_riccati_box": (C.c_int, [_P, _P, C.c_int32]),
+    "covo_set_step_ilqr_box": (C.c_int, [_P, _P, C.c_int32]),
     "covo_debug_time_step": (C.c_int, [_P, C.POINTER(EnvParamsC), C.POINTER(StepArgsC), C.c_int32, C.c_int32, C.c_int32,
                                        C.c_int32, C.POINTER(C.c_float), _P]),
     "covo_debug_time_batched": (C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_float), _P]),

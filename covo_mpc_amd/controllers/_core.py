@@ -22,7 +22,7 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
-from ._options import (check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_kernel_path, check_step_options,
+from ._options import (check_plan_hold, check_refine, check_riccati, check_riccati_box, check_riccati_feedback, check_kernel_path, check_step_options,
                        sharded_refusal, take)
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
@@ -66,13 +66,19 @@ def exchange_records(record, gathered_flat, process_group=None):
     return gathered_flat.view(-1, record.numel())
 
 
+def _mask_count(m):
+    """The clamped coordinates of clamp masks (int32, any shape [..., 32]) -> int32 [...]: the set bits among bits 0-7, on the device"""
+    bits = (m.unsqueeze(-1) >> m.new_tensor(list(range(8)))) & 1
+    return bits.sum(dim=(-1, -2)).to(m.dtype)
+
+
 class SamplingCore:
     def __init__(self, N: int, H: int, lam: float, discount: float, device=None, process_group=None,
                  compute_info: bool = True, trust_clipped: bool = False, use_graph=None, shared_device=None, exchange=None,
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False,
-                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1):
+                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False):
         opts = take(locals())
         import torch
         sharded = False
@@ -84,6 +90,7 @@ class SamplingCore:
         riccati = check_riccati(riccati, "a sampling core", refine=refine, sharded=sharded)
         riccati_feedback = check_riccati_feedback(riccati_feedback, riccati=riccati, what="a sampling core")
         plan_hold = check_plan_hold(plan_hold, riccati=riccati, sigma_period=opt.sigma_period, what="a sampling core")
+        riccati_box = check_riccati_box(riccati_box, riccati=riccati, what="a sampling core")
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -239,6 +246,13 @@ class SamplingCore:
         if plan_hold > 1:
             with torch.cuda.device(self.device):
                 self.plan_hold_rows = self._attach_rows(_lib.COVO_HOLD_FLOATS, "covo_set_step_plan_hold", plan_hold)
+        # self.riccati_box_masks [rows, 32] int32: the clamp masks of the last sweep (riccati_box=: _options.check_riccati_box; attached
+        # behind riccati's rows, which it needs)
+        self.riccati_box_on = riccati_box
+        self.riccati_box_masks = None
+        if riccati_box:
+            self.riccati_box_masks = torch.zeros((self._rows, COVO_H), dtype=torch.int32, device=self.device)
+            check(self.lib.covo_set_step_riccati_box(self.h, ptr(self.riccati_box_masks), self._rows), "covo_set_step_riccati_box")
         self._list_infos()
         self.exchange = "collective"
         if self.world > 1:
@@ -390,7 +404,8 @@ class SamplingCore:
             (self.sigma_adapt_rows is not None, self.sigma_adapt_info), (self.refine_rows is not None, self.refine_info),
             (self.riccati_rows is not None, self.riccati_info),
             (self.riccati_feedback_rows is not None, self.riccati_feedback_info),
-            (self.plan_hold_rows is not None, self.plan_hold_info)) if on]
+            (self.plan_hold_rows is not None, self.plan_hold_info),
+            (self.riccati_box_masks is not None, self.riccati_box_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -577,6 +592,15 @@ class SamplingCore:
         return {"riccati_closed": self.riccati_rows[0, 2:3].view(self.torch.int32)[0] > _lib.COVO_REFINE_CANDIDATES - 1,
                 "riccati_cost_open": row[0], "riccati_cost_closed": row[1], "riccati_gain_max": row[4]}
 
+    def riccati_box_info(self) -> dict:
+        """{"riccati_box_mask" [32] int32 (stage k's word: bits 0-3 coordinate i clamped at the lower bound, 4-7 at the upper),
+        "riccati_box_count" (0-d: the clamped coordinates)} of the last sweep from self.riccati_box_masks (the mask is a view, the
+        count a few device ops on it; no sync); {} when the core was built without riccati_box."""
+        if self.riccati_box_masks is None:
+            return {}
+        m = self.riccati_box_masks[0]
+        return {"riccati_box_mask": m, "riccati_box_count": _mask_count(m)}
+
     def _plan_ages(self):
         nxt, last = C.c_int32(0), C.c_int32(0)
         check(self.lib.covo_step_plan_age(self.h, C.byref(nxt), C.byref(last)), "covo_step_plan_age")
@@ -615,6 +639,11 @@ class SamplingCore:
         self.ilqr_summary = torch.zeros((self._rows, _lib.COVO_ILQR_FLOATS), dtype=torch.float32, device=self.device)
         check(self.lib.covo_set_step_ilqr(self.h, ptr(self._ilqr_rows_full), ptr(self._ilqr_fb_full), ptr(self.ilqr_summary), self._rows),
               "covo_set_step_ilqr")
+        self.ilqr_box_count = None
+        if self.riccati_box_masks is not None:  # slot j: the clamped coordinates of iteration j's sweep
+            self._ilqr_box_full = torch.zeros((self._rows, _lib.COVO_MAX_STEP_ITERS), dtype=torch.int32, device=self.device)
+            self.ilqr_box_count = self._ilqr_box_full[:, :self.iters]
+            check(self.lib.covo_set_step_ilqr_box(self.h, ptr(self._ilqr_box_full), self._rows), "covo_set_step_ilqr_box")
         self._infos = [f for f in self._infos if f != self.iter_info] + [self.ilqr_info]
 
     def ilqr_costs(self):
@@ -634,7 +663,8 @@ class SamplingCore:
         if getattr(self, "ilqr_summary", None) is None:
             return {}
         row, i32 = self.ilqr_summary[0], self.torch.int32
-        return {"ilqr_rows": self.ilqr_rows[0], "ilqr_feedback_rows": self.ilqr_feedback_rows[0], "ilqr_cost_first": row[0],
+        box = {} if getattr(self, "ilqr_box_count", None) is None else {"ilqr_box_count": self.ilqr_box_count[0]}
+        return {**box, "ilqr_rows": self.ilqr_rows[0], "ilqr_feedback_rows": self.ilqr_feedback_rows[0], "ilqr_cost_first": row[0],
                 "ilqr_cost": row[1], "ilqr_moved": row[2:3].view(i32)[0], "ilqr_fixed_at": row[3:4].view(i32)[0],
                 "ilqr_closed": row[4:5].view(i32)[0]}
 
@@ -733,15 +763,19 @@ class SamplingCore:
                   "covo_feedback_rollout")
         return a_out, aux
 
-    def riccati(self, dstate, params_c, a, reg0=_lib.COVO_RICCATI_REG0, f_steps=None, packed=None):
+    def riccati(self, dstate, params_c, a, reg0=_lib.COVO_RICCATI_REG0, f_steps=None, packed=None, box=False):
         """covo_riccati: the Riccati sweep (csrc/riccati.hip) over the stage blocks of the Hessian's objective at `a` (float32 device
         tensor [128] or [batch, 128]) -> dict of float64 device tensors: "d" [batch, 128] = -(R + mu I)^-1 g on the lowest rung
         mu = reg0 4^j, j < 8, at which R + mu I is positive definite; "K" [batch, 32, 4, 16] the feedback gains (columns at and above
         the state dimension are 0), "kff" [batch, 32, 4] the feed-forward terms, "x" [batch, 32, 16] the nominal states along the plan;
         "rows" [batch, 4] = {mu, rung, smallest pivot, flags}.  f_steps: the [batch, H, 4] table of
         disturb_table(key_mode=DISTURB_KEYS_HESSIAN) for periodic / sin / drag / mixed; packed: the [batch, 32] states (default:
-        dstate's, for every entry).  The workspace is the sweep's own: hessian(), cost_gradient() and the step's Hessian are untouched."""
+        dstate's, for every entry).  The workspace is the sweep's own: hessian(), cost_gradient() and the step's Hessian are untouched.
+        box=True (covo_riccati_box): every stage solves the box QP on -1 <= clip(a) + du <= 1 (_options.check_riccati_box); the dict
+        gains "box" [batch, 32] int32, the clamp masks of the winning rung."""
         torch = self.torch
+        if not isinstance(box, bool):
+            raise ValueError(f"box={box!r} (True | False)")
         a = a.reshape(-1, COVO_NA).contiguous()
         batch = int(a.shape[0])
         assert a.is_cuda and a.dtype == torch.float32
@@ -750,6 +784,14 @@ class SamplingCore:
         assert packed.numel() == batch * _lib.COVO_STATE_FLOATS and packed.is_contiguous()
         new = lambda *shape: torch.empty((batch,) + shape, dtype=torch.float64, device=self.device)
         out = {"d": new(COVO_NA), "K": new(COVO_H, 4, 16), "kff": new(COVO_H, 4), "x": new(COVO_H, 16), "rows": new(_lib.COVO_RICCATI_SIDE)}
+        if box:
+            out["box"] = torch.empty((batch, COVO_H), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                check(self.lib.covo_riccati_box(self.h, ptr(packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                                C.byref(params_c), ptr(a), ptr(f_steps), batch, float(reg0), ptr(out["d"]), ptr(out["K"]),
+                                                ptr(out["kff"]), ptr(out["x"]), ptr(out["rows"]), ptr(out["box"]), self.stream()),
+                      "covo_riccati_box")
+            return out
         with torch.cuda.device(self.device):
             check(self.lib.covo_riccati(self.h, ptr(packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T, C.byref(params_c),
                                         ptr(a), ptr(f_steps), batch, float(reg0), ptr(out["d"]), ptr(out["K"]), ptr(out["kff"]),
@@ -757,15 +799,18 @@ class SamplingCore:
         return out
 
     def riccati_refine(self, dstate, params_c, a_mean, reg0=_lib.COVO_RICCATI_REG0, f_shared=None, f_steps=None, f_steps_hessian=None,
-                       want_costs=True, feedback=False):
+                       want_costs=True, feedback=False, box=False):
         """covo_riccati_refine (the stand-alone Riccati line search) on `a_mean` (float32 device tensor, 128 elements, refined IN
         PLACE) with the inputs of rollout(): the sweep's direction d at a_mean (f_steps_hessian: the Hessian's table), the candidates
         clip(a_mean) and clip(a_mean + 2^(3 - j) d), j = 1 .. 16, rolled out, the first cheapest committed -> (float32 [8] row
         {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, mu, bits(flags | rung << 8)}, float32 [17] candidate costs or None).
         feedback=True (covo_riccati_refine_feedback): the 16 closed-loop sequences under the sweep's gains compete as candidates
         17 .. 32 -> (row, float32 [33] costs or None, float32 [8] feedback row {cost_open, cost_closed, bits(index open), bits(index
-        closed), max |K dx|_inf, bits(clipped count), bits(invalid mask), 0})."""
+        closed), max |K dx|_inf, bits(clipped count), bits(invalid mask), 0}).
+        box=True (covo_riccati_refine_box): the same over the box sweep; the int32 [32] clamp masks follow the rows in the tuple."""
         torch = self.torch
+        if not isinstance(box, bool):
+            raise ValueError(f"box={box!r} (True | False)")
         assert a_mean.is_cuda and a_mean.dtype == torch.float32 and a_mean.is_contiguous() and a_mean.numel() == COVO_NA
         if not isinstance(feedback, bool):
             raise ValueError(f"feedback={feedback!r} (True | False)")
@@ -778,6 +823,15 @@ class SamplingCore:
                 raise NotImplementedError(f"riccati_refine(feedback=True): disturb_kind={params_c.disturb_kind} (drag / mixed) is a "
                                           "16-state plant -- its force is a state of the sweep and a per-sample quantity of the rollout")
             fb_row = torch.empty((_lib.COVO_FEEDBACK_FLOATS,), dtype=torch.float32, device=self.device)
+        if box:
+            masks = torch.empty((COVO_H,), dtype=torch.int32, device=self.device)
+            with torch.cuda.device(self.device):
+                check(self.lib.covo_riccati_refine_box(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj), dstate.T,
+                                                       C.byref(params_c), fs, ptr(f_steps), ptr(f_steps_hessian), ptr(a_mean),
+                                                       float(reg0), 1, ptr(row), ptr(costs), ptr(fb_row) if feedback else None,
+                                                       int(feedback), ptr(masks), self.stream()), "covo_riccati_refine_box")
+            return (row, costs, fb_row, masks) if feedback else (row, costs, masks)
+        if feedback:
             with torch.cuda.device(self.device):
                 check(self.lib.covo_riccati_refine_feedback(self.h, ptr(dstate.packed), ptr(dstate.pos_traj), ptr(dstate.vel_traj),
                                                             dstate.T, C.byref(params_c), fs, ptr(f_steps), ptr(f_steps_hessian),

@@ -298,6 +298,30 @@ def check_riccati_feedback(feedback, *, riccati, disturb_type=None, what="a samp
     return True
 
 
+def check_riccati_box(box, *, riccati, what="a sampling controller") -> bool:
+    """riccati_box= on top of riccati= -> bool.  A switch like riccati_feedback=, taken by the same callables (SamplingCore,
+    MPPIController, CoVOController, BatchedCoVOController, get_controller, eval_env_batched) and by the iLQR controllers (BatchedILQRController's keyword; the class ILQRBoxController), and checked
+    here; the C side's counterpart is the box block of check_step_attachments (csrc/capi.hip).
+
+    riccati_box=True: every stage of every sweep the controller runs solves the box QP of control-limited DDP instead of the
+    unconstrained 4 x 4 system -- k_k = argmin 1/2 du^T Quu du + Qu^T du on -1 <= clip(b_k) + du <= 1; a clamped coordinate's k_k is
+    the bound itself and its row of K_k is 0 (covo_set_step_riccati_box, csrc/riccati.hip).  Forward pass, candidates and judge are
+    unchanged: info["riccati_box_mask"] [32] int32 (bits 0-3: coordinate i clamped at the lower bound, 4-7: at the upper) /
+    ["riccati_box_count"] (the clamped coordinates of the last sweep).  It goes with every plant, drag / mixed included: the box lives
+    in the 4 x 4 part.  False: nothing attached, today's sweep.
+
+    The objections, in a fixed order: anything but a bool (ValueError); True without riccati=True -- it is that sweep's stage problem
+    (ValueError).  Whatever riccati= refuses stays refused by check_riccati."""
+    if not isinstance(box, bool):
+        raise ValueError(f"riccati_box={box!r} (True | False)")
+    if not box:
+        return False
+    if riccati is not True:
+        raise ValueError(f"riccati_box=True with {what} needs riccati=True: the box is the stage problem of that sweep; give "
+                         "riccati=True or riccati_box=False")
+    return True
+
+
 def check_plan_hold(plan_hold, *, riccati, sigma_period=1, disturb_type=None, what="a sampling controller") -> int:
     """plan_hold= on top of riccati= -> the period m.  A switch like riccati_feedback=, not a step option: SamplingCore, MPPIController,
     CoVOController, BatchedCoVOController, get_controller and eval_env_batched take it and check it here; the C side's counterpart is
@@ -336,7 +360,7 @@ def check_plan_hold(plan_hold, *, riccati, sigma_period=1, disturb_type=None, wh
 
 
 def check_ilqr(iters=2, *, riccati_feedback=None, plan_hold=1, disturb_type=None, refine=False, process_group=None,
-               what="the iLQR controller", **raw):
+               what="the iLQR controller", riccati_box=False, **raw):
     """The keywords of the sampling-free controllers (ILQRController, BatchedILQRController, get_controller(env, "ilqr", ...),
     eval_env_batched(controller="ilqr")) -> (iters, riccati_feedback, plan_hold), checked and resolved.  The C side's counterpart is
     check_ilqr_step (csrc/capi.hip).
@@ -353,7 +377,8 @@ def check_ilqr(iters=2, *, riccati_feedback=None, plan_hold=1, disturb_type=None
     order: each acts on samples, weights or a Sigma, and there are none (ValueError naming it); refine=True -- its direction needs a
     covo-online step's Sigma (ValueError); a process_group -- there are no samples to shard (NotImplementedError); riccati_feedback
     anything but None / True / False (ValueError), True with disturb_type drag / mixed (check_riccati_feedback's NotImplementedError);
-    then whatever check_plan_hold objects to.  riccati_feedback=None resolves to True on the 13-state plants and to False on drag /
+    then whatever check_plan_hold objects to; riccati_box anything but a bool (check_riccati_box's ValueError; the sweep is always
+    there, so True is accepted).  riccati_feedback=None resolves to True on the 13-state plants and to False on drag /
     mixed, whose closed-loop candidates the generator refuses; an explicit False is honoured."""
     unknown = set(raw) - set(STEP_OPTION_DEFAULTS)
     if unknown:
@@ -380,4 +405,5 @@ def check_ilqr(iters=2, *, riccati_feedback=None, plan_hold=1, disturb_type=None
     else:
         feedback = check_riccati_feedback(riccati_feedback, riccati=True, disturb_type=disturb_type, what=what)
     m = check_plan_hold(plan_hold, riccati=True, disturb_type=disturb_type, what=what)
+    check_riccati_box(riccati_box, riccati=True, what=what)  # (a bool, returned as given: the callers pass it on)
     return k, feedback, m

@@ -22,13 +22,14 @@ from .. import _lib
 from .._lib import COVO_H, COVO_NA, check
 from ..dynamics.dataclass import as_device_state
 from ._core import SamplingCore
-from ._options import check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_step_options, take
+from ._options import check_plan_hold, check_refine, check_riccati, check_riccati_box, check_riccati_feedback, check_step_options, take
 
 # (controller attribute, core attribute) of the attachment buffers the batched controllers hand out
 CORE_BUFFERS = (("diag", "diag"), ("plan", "plan"), ("fan", "fan"), ("arbiter", "arbiter"), ("lam_eff", "lam_eff"), ("elite", "elite_rows"),
                 ("iter_cost_min", "iter_cost_min"), ("post_cov", "post_cov"), ("post_aux", "post_aux"),
                 ("sigma_adapt_rows", "sigma_adapt_rows"), ("refine", "refine_rows"), ("riccati", "riccati_rows"),
-                ("riccati_feedback", "riccati_feedback_rows"), ("plan_hold_rows", "plan_hold_rows"))
+                ("riccati_feedback", "riccati_feedback_rows"), ("plan_hold_rows", "plan_hold_rows"),
+                ("riccati_box", "riccati_box_masks"))
 
 
 class BatchedCoVOController:
@@ -40,7 +41,8 @@ class BatchedCoVOController:
                  sample_sigma: float = 0.5, a_mean_init=None, device=None, mode: str = "online", compute_diag: bool = False,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, staged: bool = False,
-                 refine: bool = False, riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1):
+                 refine: bool = False, riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1,
+                 riccati_box: bool = False):
         opts = take(locals())
         moded = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step
         if staged and not moded:
@@ -58,6 +60,7 @@ class BatchedCoVOController:
         check_riccati(riccati, what, refine=refine)
         check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
         check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), what=what)
+        check_riccati_box(riccati_box, riccati=riccati, what=what)
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -75,7 +78,7 @@ class BatchedCoVOController:
         # 150-270 us of host time per call)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
                                  diag_rows=int(n_envs), refine=refine, riccati=riccati, riccati_feedback=riccati_feedback,
-                                 plan_hold=plan_hold, **opts)
+                                 plan_hold=plan_hold, riccati_box=riccati_box, **opts)
         if moded:
             check(self.core.lib.covo_set_step_batched_staged(self.core.h, int(self.staged)), "covo_set_step_batched_staged")
         # after a call, row e of each of the core's attachment buffers holds instance e's result of that step; None for what is off
@@ -291,16 +294,17 @@ class BatchedILQRController(BatchedCoVOController):
     iteration's launches take the instance as a grid dimension; instance e's result is bit-identical to ILQRController's on that
     instance alone (tests/test_gpu_ilqr.py).  After a call: .ilqr_rows / .ilqr_feedback_rows [E, iters, 8] (every iteration's Riccati /
     feedback row), .ilqr_summary [E, 8] (SamplingCore.attach_ilqr), .riccati / .riccati_feedback (the last iteration's rows),
-    .plan_hold_rows and .plan (None for what is off)."""
+    .plan_hold_rows and .plan (None for what is off); under riccati_box .riccati_box [E, 32] (the last sweep's clamp masks) and
+    .ilqr_box_count [E, iters] (every iteration's clamped coordinates)."""
     MODE = _lib.MODE_ILQR
 
     def __init__(self, env, n_envs: int, H: int, *, iters: int = 2, riccati_feedback=None, plan_hold: int = 1,
-                 compute_plan: bool = False, discount: float = 1.0, a_mean_init=None, device=None):
+                 compute_plan: bool = False, discount: float = 1.0, a_mean_init=None, device=None, riccati_box: bool = False):
         from .ilqr import ILQR_N, build_ilqr_core
         from ._options import check_ilqr
         self.iters, self.riccati_feedback_on, self.plan_hold = check_ilqr(
             iters, riccati_feedback=riccati_feedback, plan_hold=plan_hold, disturb_type=getattr(env, "disturb_type", None),
-            compute_plan=compute_plan, what="the env-batched iLQR controller")
+            compute_plan=compute_plan, what="the env-batched iLQR controller", riccati_box=riccati_box)
         if not 0 < n_envs <= _lib.COVO_MAX_ENVS:
             raise ValueError(f"n_envs={n_envs} outside (0, {_lib.COVO_MAX_ENVS}]")
         self.mode, self.staged = self.MODE, False
@@ -309,11 +313,13 @@ class BatchedILQRController(BatchedCoVOController):
         self.rollover_terminate = not getattr(env, "disable_rollover_terminate", True)
         # (eager: the iterations are eager launches; nothing of an iLQR step is captured)
         self.core = build_ilqr_core(self.E, H, discount, iters=self.iters, riccati_feedback=self.riccati_feedback_on,
-                                    plan_hold=self.plan_hold, compute_plan=bool(compute_plan), device=device, use_graph=False)
+                                    plan_hold=self.plan_hold, compute_plan=bool(compute_plan), device=device, use_graph=False,
+                                    riccati_box=riccati_box)
         for mine, cores in CORE_BUFFERS:
             setattr(self, mine, getattr(self.core, cores))
         self.ilqr_rows, self.ilqr_feedback_rows, self.ilqr_summary = (self.core.ilqr_rows, self.core.ilqr_feedback_rows,
                                                                       self.core.ilqr_summary)
+        self.ilqr_box_count = self.core.ilqr_box_count  # [E, iters] int32 under riccati_box, else None
         torch = self.core.torch
         f32 = dict(dtype=torch.float32, device=self.core.device)
         E, n = self.E, self.N

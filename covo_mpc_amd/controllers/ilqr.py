@@ -32,30 +32,35 @@ class ILQRParams:
         return dataclasses.replace(self, **kw)
 
 
-def build_ilqr_core(n_rows, H, discount, *, iters, riccati_feedback, plan_hold, compute_plan, device, use_graph=None):
+def build_ilqr_core(n_rows, H, discount, *, iters, riccati_feedback, plan_hold, compute_plan, device, use_graph=None, riccati_box=False):
     """The SamplingCore of an iLQR controller for n_rows instances: the Riccati rows [+ feedback rows, hold rows, plan rows] attached
     as a sampling controller attaches them, the iteration count set, the per-iteration logs attached (SamplingCore.attach_ilqr)."""
     core = SamplingCore(ILQR_N, H, 1.0, discount, device=device, compute_info=False, trust_clipped=True, use_graph=use_graph,
                         diag_rows=int(n_rows), compute_plan=compute_plan, iters=iters, riccati=True, riccati_feedback=riccati_feedback,
-                        plan_hold=plan_hold)
+                        plan_hold=plan_hold, riccati_box=riccati_box)
     core.attach_ilqr()
     return core
 
 
 class ILQRController(BaseController):
+    # riccati_box of the sampling controllers (_options.check_riccati_box): every iteration's sweep solves the control-limited stage
+    # problem.  A class attribute, not a constructor keyword -- the constructor's parameter list is a published one; ILQRBoxController
+    # below sets it, and get_controller(env, "ilqr", ..., riccati_box=True) builds that class
+    riccati_box = False
+
     def __init__(self, env, control_params, H: int, *, iters: int = 2, riccati_feedback=None, plan_hold: int = 1,
                  compute_plan: bool = False, device=None) -> None:
         # ValueError / NotImplementedError before anything is built; riccati_feedback=None: True on the 13-state plants, False on drag / mixed
         self.iters, self.riccati_feedback, self.plan_hold = check_ilqr(
             iters, riccati_feedback=riccati_feedback, plan_hold=plan_hold, disturb_type=getattr(env, "disturb_type", None),
-            compute_plan=compute_plan)
+            compute_plan=compute_plan, riccati_box=self.riccati_box)
         super().__init__(env, control_params)
         self.H = H
         self.alias_outputs = False  # True: the returned a_mean aliases the controller's buffer (no clone)
         self._params_c(env.default_params)  # raises now if env.reward_fn / disturb_type is not one the kernels evaluate
         self.core = build_ilqr_core(1, H, getattr(control_params, "discount", 1.0), iters=self.iters,
                                     riccati_feedback=self.riccati_feedback, plan_hold=self.plan_hold, compute_plan=bool(compute_plan),
-                                    device=device)
+                                    device=device, riccati_box=self.riccati_box)
 
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start: with a plan hold the schedule restarts -- the first step of the episode plans."""
@@ -81,3 +86,8 @@ class ILQRController(BaseController):
         if not self.alias_outputs:
             a_mean_new = a_mean_new.clone()
         return a_mean_new[0], control_params.replace(a_mean=a_mean_new), core.step_info()
+
+
+class ILQRBoxController(ILQRController):
+    """ILQRController over the box sweep: info also carries riccati_box_mask / riccati_box_count / ilqr_box_count"""
+    riccati_box = True

@@ -1218,6 +1218,13 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                     "plant, whose force is a state of the sweep and a per-sample quantity of the rollout; detach the feedback rows", what,
                     params[e].disturb_kind, e);
     }
+    if (covo_box_on(h)) {  // the box form of the Riccati refinement's sweep (16-state plants included: the box lives in the 4 x 4 part)
+        REQUIRE(covo_riccati_on(h),
+                "%s: the Riccati box (covo_set_step_riccati_box) without the Riccati refinement (covo_set_step_riccati): it is that "
+                "sweep's stage problem; attach it or detach the masks", what);
+        REQUIRE(n_inst <= h->box_n, "%s: %d instances, the box masks (covo_set_step_riccati_box) have n_inst=%d rows", what, n_inst,
+                h->box_n);
+    }
     if (h->plan_hold > 1) {  // the steps between two plan steps apply the sweep's law: they need the sweep, and every step a Sigma of its own
         REQUIRE(covo_riccati_on(h),
                 "%s: the plan hold (covo_set_step_plan_hold, period=%d) without the Riccati refinement (covo_set_step_riccati): a hold "
@@ -1280,6 +1287,8 @@ static int check_ilqr_step(const covo_ctx *h, int n_inst, bool sharded, int deri
     REQUIRE(!logs || n_inst <= h->ilqr_n, "%s: %d instances, the iLQR logs (covo_set_step_ilqr) have n_inst=%d", what, n_inst, h->ilqr_n);
     REQUIRE(h->ilqr_costs == nullptr || n_inst <= h->ilqr_costs_n, "%s: %d instances, the iLQR cost buffer (covo_debug_ilqr_costs) has "
             "n_inst=%d", what, n_inst, h->ilqr_costs_n);
+    REQUIRE(h->ilqr_box == nullptr || n_inst <= h->ilqr_box_n, "%s: %d instances, the iLQR box counts (covo_set_step_ilqr_box) have "
+            "n_inst=%d", what, n_inst, h->ilqr_box_n);
     return 0;
 }
 
@@ -1404,15 +1413,17 @@ static int riccati_reserve(covo_ctx *h, int batch, hipStream_t s)
     return 0;
 }
 
-int covo_riccati(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
-                 const covo_env_params *params, const float *a, const float *f_tab_hessian, int32_t batch, double reg0, double *d_out,
-                 double *K_out, double *kff_out, double *x_out, double *rows_out, void *stream)
+// covo_riccati (box false) and covo_riccati_box
+static int riccati_sweep_body(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                              const covo_env_params *params, const float *a, const float *f_tab_hessian, int32_t batch, double reg0,
+                              double *d_out, double *K_out, double *kff_out, double *x_out, double *rows_out, bool box, int32_t *masks_out,
+                              const char *who, void *stream)
 {
-    REQUIRE(h, "covo_riccati: null handle");
-    CHECK_DEVICE(h, "covo_riccati");
-    REQUIRE(state && pos_traj && vel_traj && params && a && d_out && T > 0 && batch > 0, "covo_riccati: bad argument");
-    CHECK_MODEL(params, "covo_riccati");
-    REQUIRE(!covo_needs_tables(*params) || f_tab_hessian, "covo_riccati: disturb_kind=%d needs f_tab_hessian (covo_disturb_table)",
+    REQUIRE(h, "%s: null handle", who);
+    CHECK_DEVICE(h, who);
+    REQUIRE(state && pos_traj && vel_traj && params && a && d_out && T > 0 && batch > 0, "%s: bad argument", who);
+    CHECK_MODEL(params, who);
+    REQUIRE(!covo_needs_tables(*params) || f_tab_hessian, "%s: disturb_kind=%d needs f_tab_hessian (covo_disturb_table)", who,
             params->disturb_kind);
     hipStream_t s = (hipStream_t)stream;
     if (int rc = covo_grow_workspace(h, &h->ws_riccati, &h->ws_riccati_bytes, riccati_workspace_bytes(batch), s)) return rc;
@@ -1424,7 +1435,25 @@ int covo_riccati(covo_handle_t h, const float *state, const float *pos_traj, con
     o.kff = kff_out;
     o.x = x_out;
     o.side = rows_out;
+    o.box = box;
+    o.masks = masks_out;
     return launch_riccati(d, reg0, o, h->ws_riccati, s);
+}
+
+int covo_riccati(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                 const covo_env_params *params, const float *a, const float *f_tab_hessian, int32_t batch, double reg0, double *d_out,
+                 double *K_out, double *kff_out, double *x_out, double *rows_out, void *stream)
+{
+    return riccati_sweep_body(h, state, pos_traj, vel_traj, T, params, a, f_tab_hessian, batch, reg0, d_out, K_out, kff_out, x_out,
+                              rows_out, false, nullptr, "covo_riccati", stream);
+}
+
+int covo_riccati_box(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                     const covo_env_params *params, const float *a, const float *f_tab_hessian, int32_t batch, double reg0, double *d_out,
+                     double *K_out, double *kff_out, double *x_out, double *rows_out, int32_t *masks_out, void *stream)
+{
+    return riccati_sweep_body(h, state, pos_traj, vel_traj, T, params, a, f_tab_hessian, batch, reg0, d_out, K_out, kff_out, x_out,
+                              rows_out, true, masks_out, "covo_riccati_box", stream);
 }
 
 // the sweep's gains and the generator's sequences of a step's instances, here and not in a step (covo_common.hpp: the layouts)
@@ -1441,11 +1470,12 @@ static bool feedback_refuses(const covo_env_params *p) { return p->disturb_kind 
     "%s: disturb_kind=%d (drag / mixed) is a 16-state plant -- its force is a state of the sweep and a per-sample quantity of the "    \
     "rollout; the closed-loop generator carries the 13-state plants only"
 
-// covo_riccati_refine (fb_rows_out null: 17 candidates) and covo_riccati_refine_feedback (33)
+// covo_riccati_refine (fb_rows_out null: 17 candidates), covo_riccati_refine_feedback (33) and, over the box sweep (masks_out
+// [n_inst][H] or null), covo_riccati_refine_box
 static int riccati_refine_body(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                                const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
                                const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
-                               float *fb_rows_out, bool feedback, const char *who, void *stream)
+                               float *fb_rows_out, bool feedback, bool box, int32_t *masks_out, const char *who, void *stream)
 {
     REQUIRE(h, "%s: null handle", who);
     CHECK_DEVICE(h, who);
@@ -1462,7 +1492,9 @@ static int riccati_refine_body(covo_handle_t h, const float *state, const float 
         if (int rc = feedback_reserve(h)) return rc;
     HessianDesc hd = covo_hessian_inputs(state, pos_traj, vel_traj, T, params, a_mean, f_tab_hessian, n_inst);
     hd.status_dev = h->status_dev;
-    const RiccatiOut o = covo_riccati_out(h, feedback);
+    RiccatiOut o = covo_riccati_out(h, feedback);
+    o.box = box;
+    o.masks = masks_out;
     if (int rc = launch_riccati(hd, reg0, o, h->ws_riccati, s)) return rc;
     if (feedback && h->feedback_poke_armed) {  // covo_debug_feedback_gain: once
         h->feedback_poke_armed = 0;
@@ -1496,7 +1528,7 @@ int covo_riccati_refine(covo_handle_t h, const float *state, const float *pos_tr
                         void *stream)
 {
     return riccati_refine_body(h, state, pos_traj, vel_traj, T, params, f_disturb_shared, f_disturb_steps, f_tab_hessian, a_mean, reg0,
-                               n_inst, rows_out, costs_out, nullptr, false, "covo_riccati_refine", stream);
+                               n_inst, rows_out, costs_out, nullptr, false, false, nullptr, "covo_riccati_refine", stream);
 }
 
 int covo_riccati_refine_feedback(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
@@ -1505,7 +1537,17 @@ int covo_riccati_refine_feedback(covo_handle_t h, const float *state, const floa
                                  float *costs_out, float *fb_rows_out, void *stream)
 {
     return riccati_refine_body(h, state, pos_traj, vel_traj, T, params, f_disturb_shared, f_disturb_steps, f_tab_hessian, a_mean, reg0,
-                               n_inst, rows_out, costs_out, fb_rows_out, true, "covo_riccati_refine_feedback", stream);
+                               n_inst, rows_out, costs_out, fb_rows_out, true, false, nullptr, "covo_riccati_refine_feedback", stream);
+}
+
+int covo_riccati_refine_box(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                            const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                            const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
+                            float *fb_rows_out, int32_t feedback, int32_t *masks_out, void *stream)
+{
+    return riccati_refine_body(h, state, pos_traj, vel_traj, T, params, f_disturb_shared, f_disturb_steps, f_tab_hessian, a_mean, reg0,
+                               n_inst, rows_out, costs_out, feedback ? fb_rows_out : nullptr, feedback != 0, true, masks_out,
+                               "covo_riccati_refine_box", stream);
 }
 
 int covo_feedback_rollout(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
@@ -1588,6 +1630,27 @@ int covo_set_step_riccati(covo_handle_t h, float *rows, int32_t n_inst)
     return 0;
 }
 
+// the box form of every sweep a step of this handle runs (riccati.hip).  The sweep's launches are eager and follow the step; a change
+// of the switch still bumps the epoch, so no captured step graph outlives it.  What the step needs next to it is checked at the step
+int covo_set_step_riccati_box(covo_handle_t h, int32_t *masks, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_riccati_box: null handle");
+    if (masks == nullptr) {
+        if (h->box_masks != nullptr) ++h->opt.epoch;
+        h->box_masks = nullptr;
+        h->box_n = 0;
+        return 0;
+    }
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_riccati_box: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(covo_riccati_on(h) && n_inst <= h->riccati_n,
+            "covo_set_step_riccati_box: n_inst=%d needs the Riccati refinement attached on the handle with at least as many instances "
+            "(covo_set_step_riccati: %d)", n_inst, h->riccati_n);
+    if (h->box_masks == nullptr) ++h->opt.epoch;
+    h->box_masks = masks;
+    h->box_n = n_inst;
+    return 0;
+}
+
 // ---- the plan hold (plan_hold.hip; the schedule: covo_plan_step_age / _done, covo_common.hpp).  Plan steps keep their launches and
 // graphs; a hold step is one eager launch: no epoch bump.  What the step needs next to it is checked at the step (check_step_attachments)
 int covo_set_step_plan_hold(covo_handle_t h, int32_t period, float *rows, int32_t n_inst)
@@ -1630,6 +1693,16 @@ int covo_set_step_ilqr(covo_handle_t h, float *rows, float *fb_rows, float *summ
     h->ilqr_fb_rows = fb_rows;
     h->ilqr_summary = summary;
     h->ilqr_n = on ? n_inst : 0;
+    return 0;
+}
+
+int covo_set_step_ilqr_box(covo_handle_t h, int32_t *counts, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_ilqr_box: null handle");
+    REQUIRE(counts == nullptr || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_ilqr_box: n_inst=%d outside (0, %d]", n_inst,
+            COVO_MAX_ENVS);
+    h->ilqr_box = counts;
+    h->ilqr_box_n = counts ? n_inst : 0;
     return 0;
 }
 

@@ -137,6 +137,11 @@ struct covo_ctx {
     int ilqr_n;
     float *ilqr_costs;        // test hook (covo_debug_ilqr_costs): caller's [ilqr_costs_n][COVO_MAX_STEP_ITERS][COVO_FEEDBACK_CANDIDATES], or null
     int ilqr_costs_n;
+    // the box form of the Riccati refinement's sweep (covo_set_step_riccati_box; riccati.hip); box_masks null: off
+    int *box_masks;           // caller's [box_n][H]: instance e's clamp masks of the last sweep
+    int box_n;
+    int *ilqr_box;            // caller's [ilqr_box_n][COVO_MAX_STEP_ITERS] (covo_set_step_ilqr_box): slot j = iteration j's clamped coordinates, or null
+    int ilqr_box_n;
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -209,6 +214,7 @@ static inline bool covo_arb_on(const covo_ctx *h) { return h->arb_out != nullptr
 static inline bool covo_refine_on(const covo_ctx *h) { return h->refine_out != nullptr; }
 static inline bool covo_riccati_on(const covo_ctx *h) { return h->riccati_out != nullptr; }
 static inline bool covo_feedback_on(const covo_ctx *h) { return h->feedback_out != nullptr; }
+static inline bool covo_box_on(const covo_ctx *h) { return h->box_masks != nullptr; }
 // where the steps of this handle write their diagnostics (null: off) and for how many instances
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->eplog[COVO_EPLOG_DIAG].log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->eplog[COVO_EPLOG_DIAG].log ? COVO_MAX_ENVS : 0); }
@@ -604,6 +610,9 @@ struct RiccatiOut {
     double *kff = nullptr;   // [batch][H][4], nullable
     double *x = nullptr;     // [batch][H][16], nullable
     double *side = nullptr;  // [batch][COVO_RICCATI_SIDE] {mu, rung, smallest pivot, flags}, nullable
+    // the box form: every stage solves its QP on -1 <= clip(b) + du <= 1 (riccati.hip); masks: the winning rung's clamped coordinates
+    bool box = false;
+    int *masks = nullptr;    // [batch][H] bits 0-3: coordinate i clamped at lo, 4-7: at hi; nullable (read only when box)
 };
 size_t riccati_workspace_bytes(int batch);
 int launch_riccati(const HessianDesc &d, double reg0, const RiccatiOut &o, void *workspace, hipStream_t s);
@@ -845,6 +854,8 @@ struct IlqrTallyDesc {
     float *rows_log;          // [COVO_MAX_STEP_ITERS][COVO_RICCATI_FLOATS] or null
     float *fb_log;            // [COVO_MAX_STEP_ITERS][COVO_FEEDBACK_FLOATS] or null
     float *summary;           // [COVO_ILQR_FLOATS] or null
+    const int *masks;         // [H] the clamp masks of the box sweep that has just run, or null (with box_log)
+    int *box_log;             // [COVO_MAX_STEP_ITERS] slot j: the clamped coordinates of iteration j's sweep, or null
 };
 int launch_ilqr_begin(const float *a_mean_src, float *a_mean, uint32_t *dyn, const uint32_t *keys, int n_inst, int derive_keys,
                       float shared_noise_scale, hipStream_t s);

@@ -62,6 +62,8 @@ __global__ __launch_bounds__(IL_BLOCK) void ilqr_tally_kernel(const IlqrTallyDes
         Pb.rows_log = rebase_global(P_.rows_log, Pb.rows_log);
         Pb.fb_log = rebase_global(P_.fb_log, Pb.fb_log);
         Pb.summary = rebase_global(P_.summary, Pb.summary);
+        Pb.masks = rebase_global(P_.masks, Pb.masks);
+        Pb.box_log = rebase_global(P_.box_log, Pb.box_log);
     }
     const IlqrTallyDesc &P = BATCHED ? Pb : P_;
     // (what is attached is the same for all instances)
@@ -73,6 +75,14 @@ __global__ __launch_bounds__(IL_BLOCK) void ilqr_tally_kernel(const IlqrTallyDes
     if (lane < COVO_RICCATI_FLOATS) {
         if (has_rows) P.rows_log[(size_t)j * COVO_RICCATI_FLOATS + lane] = r;
         if (has_fb_log) P.fb_log[(size_t)j * COVO_FEEDBACK_FLOATS + lane] = f;
+    }
+    // the box sweep's clamped coordinates: lane k < H holds stage k's mask, one ballot per bit
+    if (P_.box_log != nullptr) {
+        const int m = lane < COVO_H ? P.masks[lane] : 0;
+        int n = 0;
+#pragma unroll
+        for (int bit = 0; bit < 8; ++bit) n += __popcll(__ballot((m >> bit) & 1));
+        if (lane == 0) P.box_log[j] = n;
     }
     if (!has_sum) return;
     const int choice = __float_as_int(__shfl(r, 2));
@@ -110,7 +120,8 @@ int launch_ilqr_begin(const float *a_mean_src, float *a_mean, uint32_t *dyn, con
 // iteration j of k of the handle's n_inst instances (no-op with nothing attached); batched: the blocks go through device memory
 int launch_ilqr_tally(covo_ctx *h, int n_inst, bool batched, int j, int k, hipStream_t s)
 {
-    if (h->ilqr_rows == nullptr && h->ilqr_fb_rows == nullptr && h->ilqr_summary == nullptr) return 0;
+    const bool box = covo_box_on(h) && h->ilqr_box != nullptr;  // (covo_set_step_ilqr_box: the count needs the box sweep's masks)
+    if (h->ilqr_rows == nullptr && h->ilqr_fb_rows == nullptr && h->ilqr_summary == nullptr && !box) return 0;
     IlqrTallyDesc d[COVO_MAX_ENVS];
     const size_t log = (size_t)COVO_MAX_STEP_ITERS * COVO_RICCATI_FLOATS;
     for (int e = 0; e < n_inst; ++e) {
@@ -119,6 +130,8 @@ int launch_ilqr_tally(covo_ctx *h, int n_inst, bool batched, int j, int k, hipSt
         d[e].rows_log = h->ilqr_rows ? h->ilqr_rows + (size_t)e * log : nullptr;
         d[e].fb_log = h->ilqr_fb_rows ? h->ilqr_fb_rows + (size_t)e * log : nullptr;
         d[e].summary = h->ilqr_summary ? h->ilqr_summary + (size_t)e * COVO_ILQR_FLOATS : nullptr;
+        d[e].masks = box ? h->box_masks + (size_t)e * COVO_H : nullptr;
+        d[e].box_log = box ? h->ilqr_box + (size_t)e * COVO_MAX_STEP_ITERS : nullptr;
     }
     if (!batched) {
         hipLaunchKernelGGL(ilqr_tally_kernel<false>, dim3(1), dim3(IL_BLOCK), 0, s, d[0], (const IlqrTallyDesc *)nullptr, j, k);

@@ -1,5 +1,6 @@
 // riccati.hip -- the regularised Newton direction of the Hessian's objective by a backward Riccati sweep (gfx950, fp64):
-// covo_riccati / covo_riccati_refine / covo_set_step_riccati, include/covo_hip.h.
+// covo_riccati / covo_riccati_refine / covo_set_step_riccati and their box forms (covo_riccati_box / covo_riccati_refine_box /
+// covo_set_step_riccati_box), include/covo_hip.h.
 //
 // The Hessian's launches 1 | 2 (hessian_adj.hip: KB, then the chains with the hyper-dual workgroups) leave, for every stage k of the
 // plan, A_k, B_k (WS_JF), the costate lam_k (WS_LAM) and the exact stage blocks M_k = Hess_z(r_k + lam_{k+1} . f_k) (WS_MXX, WS_MXU,
@@ -24,6 +25,19 @@
 // definite: flag bit 3, d = 0, K = 0, rung = COVO_RICCATI_RUNGS.  Flag bit 0: g not finite (an entry of the plan that is not finite counts:
 // the model's clip would hide it), bit 1: d not finite.
 // Every sum has one order and every output one owner: a batch gives the bits of its singles.
+//
+// The box form (BOX; covo_riccati_box / covo_set_step_riccati_box): the stage problem is the QP  min 1/2 du^T Quu du + Qu^T du  on
+// lo <= du <= hi, lo = -1 - clip(b_k), hi = 1 - clip(b_k) (an entry of the plan that is not finite: lo = hi = 0).  A coordinate is
+// clamped when it sits on a bound and its multiplier (Quu du + Qu)_i pushes strictly outward; k_k is the bound itself there and
+// the row of K_k is 0, the free coordinates solve the Schur system of the free block.  With clamped rows of K zero the recurrences
+// of P and p above stay exact.  The rung is still judged by the pivots of the FULL Quu.  A stage whose unconstrained k_k is feasible
+// keeps it and today's arithmetic (one wave-uniform test); otherwise the 80 other active sets are tried at once, one or two per
+// lane -- a clamped row and column replaced by the identity, its entry held at the bound, the same unpivoted chain, then
+// primal feasibility of the free and the multiplier's sign of the clamped coordinates -- the wave takes the lowest passing pattern by
+// ballot (in exact arithmetic exactly one passes; none: the set the unconstrained k_k violates, and k_k clipped) and every lane
+// solves that one for its column of Qux.  The stage's mask (bits 0-3: clamped at lo, 4-7: at hi) rides in lane k of the rung's wave.
+#include <type_traits>
+
 #include "covo_common.hpp"
 
 typedef double f64x4 __attribute__((ext_vector_type(4)));
@@ -44,6 +58,9 @@ struct RicArgs {
     double *kff_out;   // [batch][H][4] or null
     double *x_out;     // [batch][H][16] or null
     double *side_out;  // [batch][COVO_RICCATI_SIDE] or null
+};
+struct RicBoxArgs : RicArgs {
+    int *masks_out;  // [batch][H] or null
 };
 
 __device__ __forceinline__ double ric_readlane(double v, int l)
@@ -115,8 +132,112 @@ __device__ __forceinline__ RicOps ric_finish(const RicOps &r, int k, int lo, int
             acc = __builtin_amdgcn_mfma_f64_16x16x4f64((A_)[g_], (B_)[g_], acc, 0, 0, 0);            \
     } while (0)
 
-template <int NX>
-__device__ __forceinline__ void riccati_body(const RicArgs &A, int b, int tid, double (*sP)[16][17], double *sx, double *sdu,
+
+// ---- the 4 x 4 part of a stage: wave-uniform or per-lane values alike
+// unpivoted lower Cholesky of q (lower triangle) with the rows and columns cl names replaced by the identity: l, inv = 1 / diagonal
+__device__ __forceinline__ void ric_chol_masked(const double (&q)[4][4], const bool (&cl)[4], double (&l)[4][4], double (&inv)[4])
+{
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double s = cl[j] ? 1.0 : q[j][j];
+#pragma unroll
+        for (int t = 0; t < j; ++t) s = fma(-l[j][t], l[j][t], s);
+        inv[j] = 1.0 / sqrt(s);
+#pragma unroll
+        for (int i = j + 1; i < 4; ++i) {
+            double r = (cl[i] || cl[j]) ? 0.0 : q[i][j];
+#pragma unroll
+            for (int t = 0; t < j; ++t) r = fma(-l[i][t], l[j][t], r);
+            l[i][j] = r * inv[j];
+        }
+    }
+}
+// sol = -(L L^T)^-1 rhs: forward, then backward substitution
+__device__ __forceinline__ void ric_solve_neg(const double (&l)[4][4], const double (&inv)[4], const double (&rhs)[4], double (&sol)[4])
+{
+    double y[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double s = rhs[i];
+#pragma unroll
+        for (int t = 0; t < i; ++t) s = fma(-l[i][t], y[t], s);
+        y[i] = s * inv[i];
+    }
+#pragma unroll
+    for (int i = 3; i >= 0; --i) {
+        double s = y[i];
+#pragma unroll
+        for (int t = i + 1; t < 4; ++t) s = fma(-l[t][i], sol[t], s);
+        sol[i] = s * inv[i];
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) sol[i] = -sol[i];
+}
+// the box QP's k under the active set cl (clamped at bd): the free block's right-hand side Qu_f + Quu_fc bd_c, the clamped entries bd
+__device__ __forceinline__ void ric_box_solve(const double (&q)[4][4], const double (&qu)[4], const bool (&cl)[4], const double (&bd)[4],
+                                              double (&l)[4][4], double (&inv)[4], double (&k)[4])
+{
+    ric_chol_masked(q, cl, l, inv);
+    double rhs[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        double s = qu[i];
+#pragma unroll
+        for (int c = 0; c < 4; ++c) s = (cl[c] && c != i) ? fma(c < i ? q[i][c] : q[c][i], bd[c], s) : s;
+        rhs[i] = cl[i] ? 0.0 : s;
+    }
+    ric_solve_neg(l, inv, rhs, k);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) k[i] = cl[i] ? bd[i] : k[i];
+}
+// The active set of a stage whose unconstrained k0 leaves the box -> its pattern sum_i t_i 3^i, t_i = 0 free | 1 at lo | 2 at hi
+// (wave-uniform); *fallback: no pattern passed.  Lane l tries patterns l + 1 and l + 65 (<= 80)
+__device__ __forceinline__ int ric_box_pattern(const double (&q)[4][4], const double (&qu)[4], const double (&lo4)[4],
+                                               const double (&hi4)[4], const double (&k0)[4], int lane, bool *fallback)
+{
+    unsigned long long pass[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int p = lane + 1 + 64 * h;
+        const int t[4] = {p % 3, (p / 3) % 3, (p / 9) % 3, (p / 27) % 3};
+        bool cl[4];
+        double bd[4], l[4][4], inv[4], k[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            cl[i] = t[i] != 0;
+            bd[i] = t[i] == 1 ? lo4[i] : hi4[i];
+        }
+        ric_box_solve(q, qu, cl, bd, l, inv, k);
+        bool okp = p <= 80;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            double m = qu[i];  // the multiplier (Quu k + Qu)_i
+#pragma unroll
+            for (int j = 0; j < 4; ++j) m = fma(j <= i ? q[i][j] : q[j][i], k[j], m);
+            const bool free_ok = k[i] >= lo4[i] && k[i] <= hi4[i];
+            okp = okp && (t[i] == 0 ? free_ok : (t[i] == 1 ? m > 0.0 : m < 0.0));
+        }
+        pass[h] = __ballot(okp);
+    }
+    int pat;
+    *fallback = false;
+    if (pass[0] != 0ull) pat = __ffsll((long long)pass[0]);            // (bit l: pattern l + 1)
+    else if (pass[1] != 0ull) pat = 64 + __ffsll((long long)pass[1]);
+    else {
+        *fallback = true;
+        pat = 0;
+        int w3 = 1;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            pat += w3 * (k0[i] < lo4[i] ? 1 : (k0[i] > hi4[i] ? 2 : 0));
+            w3 *= 3;
+        }
+    }
+    return __builtin_amdgcn_readfirstlane(pat);
+}
+
+template <int NX, bool BOX>
+__device__ __forceinline__ void riccati_body(const std::conditional_t<BOX, RicBoxArgs, RicArgs> &A, int b, int tid, double (*sP)[16][17], double *sx, double *sdu,
                                              double *spiv, int *sok)
 {
     constexpr int NZ = NX + 4, HH = COVO_H;
@@ -131,6 +252,13 @@ __device__ __forceinline__ void riccati_body(const RicArgs &A, int b, int tid, d
     f64x4 pv = {0.0, 0.0, 0.0, 0.0};  // p_{k+1}[4r + hi] on lo == 0
     bool ok = true;
     double minpiv = __builtin_inf();
+    // BOX: the plan's entries lane and lane + 64 (stage k's four are read by readlane: no load inside the sweep), lane k's stage mask
+    [[maybe_unused]] float pl0 = 0.0f, pl1 = 0.0f;
+    [[maybe_unused]] int mymask = 0;
+    if constexpr (BOX) {
+        pl0 = A.a[(size_t)b * COVO_NA + lane];
+        pl1 = A.a[(size_t)b * COVO_NA + COVO_WAVE + lane];
+    }
     RicOps raw = ric_load<NX>(ws, A.L, HH - 1, lo, hi);
     for (int k = HH - 1; k >= 0; --k) {
         const RicOps cur = ric_finish<NX>(raw, k, lo, hi);
@@ -209,6 +337,54 @@ __device__ __forceinline__ void riccati_body(const RicArgs &A, int b, int tid, d
 #pragma unroll
             for (int i = 0; i < 4; ++i) sol[c][i] = -sol[c][i];
         }
+        if constexpr (BOX) {
+            // the stage's box (wave-uniform); the unconstrained k_k inside it: nothing more to do
+            double lo4[4], hi4[4];
+            bool inside = true;
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int at = (4 * k + i) & (COVO_WAVE - 1);
+                const float pa = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(k < 16 ? pl0 : pl1), at));  // (the words: readlane is an int builtin)
+                const bool fin = ric_finite((double)pa);
+                const double bc = fmin(fmax((double)pa, -1.0), 1.0);
+                lo4[i] = fin ? -1.0 - bc : 0.0;
+                hi4[i] = fin ? 1.0 - bc : 0.0;
+                inside = inside && sol[1][i] >= lo4[i] && sol[1][i] <= hi4[i];
+            }
+            if (__builtin_amdgcn_readfirstlane((int)inside) == 0) {
+                double qf[4][4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) qf[i][j] = j <= i ? q[i][j] : 0.0;
+                }
+                bool fallback;
+                const int pat = ric_box_pattern(qf, qu, lo4, hi4, sol[1], lane, &fallback);
+                const int t[4] = {pat % 3, (pat / 3) % 3, (pat / 9) % 3, (pat / 27) % 3};
+                bool cl[4];
+                double bd[4], lm[4][4], im[4];
+                int m = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    cl[i] = t[i] != 0;
+                    bd[i] = t[i] == 1 ? lo4[i] : hi4[i];
+                    m |= t[i] == 1 ? (1 << i) : (t[i] == 2 ? (16 << i) : 0);
+                }
+                ric_box_solve(qf, qu, cl, bd, lm, im, sol[1]);
+                if (fallback) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) sol[1][i] = fmin(fmax(sol[1][i], lo4[i]), hi4[i]);
+                }
+                // the free rows of K under the same factor, the clamped ones exactly 0
+                double rk[4];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) rk[i] = cl[i] ? 0.0 : rhs[0][i];
+                ric_solve_neg(lm, im, rk, sol[0]);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) sol[0][i] = cl[i] ? 0.0 : sol[0][i];
+                mymask = lane == k ? m : mymask;
+            }
+        }
         // K[hi][lo] and k[hi] as the B operands of the rank-4 updates
         const double Kop = hi == 0 ? sol[0][0] : (hi == 1 ? sol[0][1] : (hi == 2 ? sol[0][2] : sol[0][3]));
         const double kk = hi == 0 ? sol[1][0] : (hi == 1 ? sol[1][1] : (hi == 2 ? sol[1][2] : sol[1][3]));
@@ -242,6 +418,9 @@ __device__ __forceinline__ void riccati_body(const RicArgs &A, int b, int tid, d
     // ---- the forward pass of the winning rung (no rung: the top rung's gradient, everything else zero)
     double *__restrict__ d_out = A.d_out + (size_t)b * COVO_NA;
     const double *__restrict__ jf = ws + A.L.jf;
+    if constexpr (BOX) {
+        if (A.masks_out != nullptr && lane < HH) A.masks_out[(size_t)b * HH + lane] = none ? 0 : mymask;
+    }
     // the copies first: independent loads, all in flight together
     if (A.K_out != nullptr) {
         double kv[HH];
@@ -316,13 +495,13 @@ __device__ __forceinline__ void riccati_body(const RicArgs &A, int b, int tid, d
     }
 }
 
-template <int NX>
-__global__ __launch_bounds__(RIC_BLOCK) void riccati_sweep_kernel(const RicArgs A)
+template <int NX, bool BOX>
+__global__ __launch_bounds__(RIC_BLOCK) void riccati_sweep_kernel(const std::conditional_t<BOX, RicBoxArgs, RicArgs> A)
 {
     __shared__ double sP[RIC_RUNGS][16][17];
     __shared__ double sx[16], sdu[4], spiv[RIC_RUNGS];
     __shared__ int sok[RIC_RUNGS];
-    riccati_body<NX>(A, (int)blockIdx.x, (int)threadIdx.x, sP, sx, sdu, spiv, sok);
+    riccati_body<NX, BOX>(A, (int)blockIdx.x, (int)threadIdx.x, sP, sx, sdu, spiv, sok);
 }
 
 // ---- host
@@ -344,7 +523,7 @@ int launch_riccati(const HessianDesc &d, double reg0, const RiccatiOut &o, void 
     if (int rc = launch_hessian(d, workspace, s, dbg)) return rc;
     const covo_env_params &p = *d.params;
     const bool fs = p.disturb_kind == COVO_DISTURB_DRAG || p.disturb_kind == COVO_DISTURB_MIXED;
-    RicArgs A;
+    RicBoxArgs A;
     A.ws = reinterpret_cast<const double *>(workspace);
     A.a = d.a_mean;
     A.L = hessian_workspace_layout(fs);
@@ -356,8 +535,15 @@ int launch_riccati(const HessianDesc &d, double reg0, const RiccatiOut &o, void 
     A.kff_out = o.kff;
     A.x_out = o.x;
     A.side_out = o.side;
-    if (fs) hipLaunchKernelGGL(riccati_sweep_kernel<16>, dim3(d.batch), dim3(RIC_BLOCK), 0, s, A);
-    else hipLaunchKernelGGL(riccati_sweep_kernel<13>, dim3(d.batch), dim3(RIC_BLOCK), 0, s, A);
+    A.masks_out = o.masks;
+    const RicArgs &A0 = A;
+    if (o.box) {
+        if (fs) hipLaunchKernelGGL((riccati_sweep_kernel<16, true>), dim3(d.batch), dim3(RIC_BLOCK), 0, s, A);
+        else hipLaunchKernelGGL((riccati_sweep_kernel<13, true>), dim3(d.batch), dim3(RIC_BLOCK), 0, s, A);
+    } else {
+        if (fs) hipLaunchKernelGGL((riccati_sweep_kernel<16, false>), dim3(d.batch), dim3(RIC_BLOCK), 0, s, A0);
+        else hipLaunchKernelGGL((riccati_sweep_kernel<13, false>), dim3(d.batch), dim3(RIC_BLOCK), 0, s, A0);
+    }
     COVO_CHECK_HIP(hipGetLastError());
     return 0;
 }

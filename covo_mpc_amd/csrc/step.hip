@@ -1473,7 +1473,9 @@ static int riccati_after(covo_ctx *h, const AfterFrame &f, int row, float *costs
     // sequences under them, and the line search judges them next to its own
     const bool feedback = covo_feedback_on(h);
     const bool hold = covo_plan_hold(h) > 1;
-    const RiccatiOut o = covo_riccati_out(h, feedback || hold);
+    RiccatiOut o = covo_riccati_out(h, feedback || hold);
+    o.box = covo_box_on(h);  // covo_set_step_riccati_box: the masks of the last sweep stay on the handle
+    o.masks = h->box_masks;
     if (int rc = launch_riccati(hd, COVO_RICCATI_REG0, o, h->ws_riccati, s)) return rc;
     if (hold) {
         LatchDesc l[COVO_MAX_ENVS];

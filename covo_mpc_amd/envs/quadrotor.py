@@ -20,7 +20,7 @@ import numpy as np
 
 from .. import controllers
 from .. import random as crandom
-from ..controllers._options import (STEP_OPTION_DEFAULTS, check_ilqr, check_plan_hold, check_refine, check_riccati, check_riccati_feedback, check_step_options,
+from ..controllers._options import (STEP_OPTION_DEFAULTS, check_ilqr, check_plan_hold, check_refine, check_riccati, check_riccati_box, check_riccati_feedback, check_step_options,
                                     take)
 from ..dynamics import utils
 from ..dynamics.dataclass import Action3D, DeviceState, EnvParams3D, EnvState3D
@@ -594,7 +594,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                      verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
                      arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0,
                      rows: bool = False, staged: bool = False, controller: str = "covo-online", refine: bool = False,
-                     riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1):
+                     riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     `controller` (covo-online by default), controller and env on the device, ONE host sync.  -> mean position error per instance
@@ -614,13 +614,14 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     ("covo-online" only here: the env-batched MPPI / covo-offline steps refuse it; check_riccati): the same line search along the
     Riccati sweep's direction; riccati_feedback=True on top of it: the closed-loop candidates under the sweep's gains compete in that
     line search (check_riccati_feedback).  plan_hold=m > 1 on top of riccati: every m-th step plans, the others apply the sweep's law to
-    the measured state (check_plan_hold); rows=True then also holds "hold": ep.read_hold()."""
+    the measured state (check_plan_hold); rows=True then also holds "hold": ep.read_hold().  riccati_box=True on top of riccati (implied
+    by "ilqr"): every sweep solves the control-limited stage problem (check_riccati_box)."""
     if controller not in ("covo-online", "mppi", "covo-offline", "ilqr"):
         raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline' or 'ilqr'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
     if controller == "ilqr":
         return _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, refine,
-                                  riccati_feedback, plan_hold, opts)
+                                  riccati_feedback, plan_hold, opts, riccati_box)
     check_step_options(None, "online" if controller == "covo-online" else controller, **opts)  # ValueError before anything is built
     check_refine(refine, "online" if controller == "covo-online" else controller, sigma_period=sigma_period)
     check_riccati(riccati, "online" if controller == "covo-online" else f"the env-batched {controller} controller", refine=refine)
@@ -628,6 +629,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                            what=f"the env-batched {controller} controller")
     check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None),
                     what=f"the env-batched {controller} controller")
+    check_riccati_box(riccati_box, riccati=riccati, what=f"the env-batched {controller} controller")
     if arbiter and update == "softmax":
         raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
@@ -638,12 +640,13 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     c0, cp0 = get_controller(env, controller, controller_params, device=device, compute_info=False)
     cp0 = c0.init_control_params
     kw = dict(discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=c0.core.device, staged=staged, **opts)
-    if controller == "mppi":
+    if controller == "mppi":  # (riccati_box needs riccati, which check_riccati has refused for the two baselines)
         b = controllers.BatchedMPPIController(env, n_envs, N, H, lam, sigmas=cp0.sample_sigma, **kw)
     else:
         b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, sample_sigma=cp0.sample_sigma,
                                               mode="offline" if controller == "covo-offline" else "online", refine=refine,
-                                              riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold, **kw)
+                                              riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold,
+                                              riccati_box=riccati_box, **kw)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     if controller == "covo-offline":  # (the table keys: children of the instances' control keys, which stay what they were)
@@ -673,12 +676,12 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
 
 
 def _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, refine,
-                       riccati_feedback, plan_hold, opts):
+                       riccati_feedback, plan_hold, opts, riccati_box=False):
     """eval_env_batched(controller="ilqr"): the same instances, reset keys and key chains under BatchedILQRController (H from
     controller_params; N and lam are ignored; riccati_feedback as for get_controller).  rows=True appends {"hold": ep.read_hold()}
     under plan_hold > 1 (else {})."""
     k, feedback, m = check_ilqr(opts["iters"], riccati_feedback=riccati_feedback or None, plan_hold=plan_hold,
-                                disturb_type=getattr(env, "disturb_type", None), refine=refine,
+                                disturb_type=getattr(env, "disturb_type", None), refine=refine, riccati_box=riccati_box,
                                 **{o: v for o, v in opts.items() if o != "iters"})
     if staged or arbiter:
         raise ValueError(f"{'staged' if staged else 'arbiter'}=True with controller='ilqr': a switch of the sampling batches")
@@ -689,7 +692,8 @@ def _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, ve
     dp = env.default_params
     th = (dp.m * dp.g / dp.max_thrust) * 2.0 - 1.0
     b = controllers.BatchedILQRController(env, n_envs, H, iters=k, riccati_feedback=feedback, plan_hold=m, compute_plan=trace,
-                                          a_mean_init=np.tile(np.array([th, 0.0, 0.0, 0.0], dtype=np.float32), H), device=device)
+                                          a_mean_init=np.tile(np.array([th, 0.0, 0.0, 0.0], dtype=np.float32), H), device=device,
+                                          riccati_box=riccati_box)
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
     t0 = time_module.time()
@@ -805,7 +809,7 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
                    iters=1, elite=None, sigma_period=1, compute_post_cov=False, sigma_adapt=0.0, refine=False,
-                   riccati=False, riccati_feedback=False, plan_hold=1):
+                   riccati=False, riccati_feedback=False, plan_hold=1, riccati_box=False):
     """quadrotor.py:670-752.  compute_diag, compute_plan, ess_min, compute_fan, update, iters, elite, sigma_period, compute_post_cov and
     sigma_adapt are the sampling controllers' step options -- what each does and what it adds to the controller's info dict:
     controllers/_options.py.  refine (covo-online only): the Newton line search behind every step -- a switch, not a step option
@@ -813,7 +817,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     direction, which needs neither R nor Sigma (controllers/_options.py: check_riccati).  riccati_feedback (on top of riccati): the
     closed-loop candidates under the sweep's gains compete in that line search (controllers/_options.py: check_riccati_feedback).
     plan_hold (on top of riccati): every plan_hold-th control step plans, the others track the last plan under the sweep's gains
-    (controllers/_options.py: check_plan_hold).
+    (controllers/_options.py: check_plan_hold).  riccati_box (on top of riccati; "ilqr" takes it as it is): every stage of the sweep
+    solves the control-limited box QP (controllers/_options.py: check_riccati_box).
     controller_name "ilqr": the sampling-free controller (controllers/ilqr.py; controllers/_options.py: check_ilqr) -- H is taken from
     controller_params, N and lam are ignored; iters, plan_hold and compute_plan pass through, riccati is implied, riccati_feedback=True
     asks for the closed-loop candidates and False (this signature's default) leaves the choice to the plant (ILQRController's None);
@@ -822,7 +827,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     if controller_name == "ilqr":  # ValueError / NotImplementedError before anything is built
         k, feedback, m = check_ilqr(iters, riccati_feedback=riccati_feedback or None, plan_hold=plan_hold,
                                     disturb_type=getattr(env, "disturb_type", None), refine=refine, process_group=process_group,
-                                    **{o: v for o, v in opts.items() if o != "iters"})
+                                    riccati_box=riccati_box, **{o: v for o, v in opts.items() if o != "iters"})
     import torch
     if controller_name == "ilqr":
         H = int(controller_params.split("_")[1][1:]) if controller_params else 32
@@ -831,8 +836,9 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         th = (dp.m * dp.g / dp.max_thrust) * 2.0 - 1.0
         control_params = controllers.ILQRParams(
             a_mean=torch.tensor([th, 0.0, 0.0, 0.0], dtype=torch.float32, device=device).repeat(H, 1), discount=1.0)
-        return controllers.ILQRController(env=env, control_params=control_params, H=H, iters=k, riccati_feedback=feedback,
-                                          plan_hold=m, compute_plan=compute_plan, device=device), control_params
+        cls = controllers.ILQRBoxController if riccati_box else controllers.ILQRController
+        return cls(env=env, control_params=control_params, H=H, iters=k, riccati_feedback=feedback, plan_hold=m,
+                   compute_plan=compute_plan, device=device), control_params
     # ValueError before anything is built; the controller's own check, with N, follows
     what = "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name
     check_step_options(None, what, **opts)
@@ -840,6 +846,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     check_riccati(riccati, what, refine=refine)
     check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
     check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), what=what)
+    check_riccati_box(riccati_box, riccati=riccati, what=what)
 
     def parse_sample_params(param_text):
         if not param_text:
@@ -866,7 +873,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info, riccati=riccati,
-                                          riccati_feedback=riccati_feedback, plan_hold=plan_hold, **opts), control_params
+                                          riccati_feedback=riccati_feedback, plan_hold=plan_hold, riccati_box=riccati_box,
+                                          **opts), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -879,7 +887,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
                                           device=device, process_group=process_group, compute_info=compute_info,
                                           refine=refine, riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold,
-                                          **opts), control_params
+                                          riccati_box=riccati_box, **opts), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -994,6 +1002,7 @@ class Args:
     riccati: bool = False   # (not in quadjax) mppi / covo: every control step ends with that line search along the Riccati sweep's direction
     riccati_feedback: bool = False  # (not in quadjax) on top of riccati: the closed-loop candidates under the sweep's gains compete too
     plan_hold: int = 1      # (not in quadjax) on top of riccati: every m-th control step plans, the others track the plan under the sweep's gains; 1 = off
+    riccati_box: bool = False  # (not in quadjax) on top of riccati / with ilqr: the sweep's stages solve the control-limited box QP
 
 
 def main(args: Args):
@@ -1011,7 +1020,7 @@ def main(args: Args):
                                                 sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render,
                                                 sigma_adapt=args.sigma_adapt, refine=args.refine,
                                                 riccati=args.riccati, riccati_feedback=args.riccati_feedback,
-                                                plan_hold=args.plan_hold)
+                                                plan_hold=args.plan_hold, riccati_box=args.riccati_box)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -1030,6 +1039,8 @@ def _cli():
             ap.add_argument("--post-cov", "--post_cov", dest="post_cov", action="store_true")
         elif f == "riccati_feedback":
             ap.add_argument("--riccati-feedback", "--riccati_feedback", dest="riccati_feedback", action="store_true")
+        elif f == "riccati_box":
+            ap.add_argument("--riccati-box", "--riccati_box", dest="riccati_box", action="store_true")
         elif f == "plan_hold":
             ap.add_argument("--plan-hold", "--plan_hold", dest="plan_hold", type=int, default=default)
         elif isinstance(default, bool):

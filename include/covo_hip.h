@@ -951,6 +951,38 @@ int covo_set_step_ilqr(covo_handle_t h, float *rows /* DEVICE [n_inst][16][8] or
  * stores them, to costs[e][j][0 .. 17 or 33) -- costs = DEVICE float[n_inst][COVO_MAX_STEP_ITERS][COVO_FEEDBACK_CANDIDATES]; NULL: off.  A
  * batched step then uploads its line search's argument blocks in every iteration. */
 int covo_debug_ilqr_costs(covo_handle_t h, float *costs, int32_t n_inst);
+
+/* The Riccati box: control-limited stages of the sweep (additive to ABI 10: COVO_HAS_RICCATI_BOX; off by default, and off means no
+ * launch, buffer or kernel changes).  At stage k of rung mu, with bc = clip(b_k, -1, 1), lo = -1 - bc, hi = 1 - bc (an entry of the
+ * plan that is not finite: lo = hi = 0), the sweep's 4 x 4 step becomes the box QP of control-limited DDP (Tassa, Mansard, Todorov 2014):
+ *     k_k = argmin 1/2 du^T Quu du + Qu^T du   subject to   lo <= du <= hi        (Quu includes mu I)
+ *   Coordinate i is clamped when k_k[i] sits on a bound and the multiplier (Quu k_k + Qu)[i] pushes strictly outward; there k_k[i] is
+ *   the bound itself and row i of K_k is 0.  On the free set f, K_k[f] = -Quu_ff^-1 Qux_f.  The value recursion is unchanged (it stays
+ *   exact with clamped rows of K zero), and so are the ladder's test -- the pivots of the FULL Quu -- the forward pass, d, x, the side
+ *   row and the line search.  Every rung runs its own box sweep; a stage whose unconstrained step is feasible keeps it bit for bit.
+ *   masks: int32[H] per entry, bits 0-3: coordinate i clamped at lo, bits 4-7: at hi, of the winning rung; zeros when no rung wins.
+ * covo_riccati_box: covo_riccati over the box sweep; masks_out = DEVICE int32[batch][H] or NULL.
+ * covo_riccati_refine_box: the stateless line search over the box sweep; feedback = 0: covo_riccati_refine's 17 candidates
+ *   (fb_rows_out is not read), feedback != 0: covo_riccati_refine_feedback's 33; masks_out = DEVICE int32[n_inst][H] or NULL.
+ * covo_set_step_riccati_box: a switch on top of covo_set_step_riccati; masks = DEVICE int32[n_inst][H].  Every sweep a step of the
+ *   handle runs is then the box sweep -- the refinement behind an MPPI / covo-offline / covo-online step, every pass under
+ *   covo_set_step_iters, the plan steps of covo_set_step_plan_hold, every iteration of an iLQR step, single and batched, steps and
+ *   episode drivers alike -- and the masks of the last sweep stay in the buffer.  The 16-state plants (drag / mixed) are allowed: the
+ *   box lives in the 4 x 4 part.  Refused before any launch, with a message that names the condition: attached without
+ *   covo_set_step_riccati on the handle, or a step with more instances than rows.  A change of the switch drops the captured step
+ *   graphs.
+ * covo_set_step_ilqr_box: counts = DEVICE int32[n_inst][COVO_MAX_STEP_ITERS]; the tally launch of an iLQR step also files the number
+ *   of clamped coordinates of iteration j's sweep in slot j (only while covo_set_step_riccati_box is on); NULL: off. */
+#define COVO_HAS_RICCATI_BOX 1
+int covo_riccati_box(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                     const covo_env_params *params, const float *a, const float *f_tab_hessian, int32_t batch, double reg0, double *d_out,
+                     double *K_out, double *kff_out, double *x_out, double *rows_out, int32_t *masks_out, void *stream);
+int covo_riccati_refine_box(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
+                            const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps,
+                            const float *f_tab_hessian, float *a_mean, double reg0, int32_t n_inst, float *rows_out, float *costs_out,
+                            float *fb_rows_out, int32_t feedback, int32_t *masks_out, void *stream);
+int covo_set_step_riccati_box(covo_handle_t h, int32_t *masks /* DEVICE [n_inst][H]; NULL = off */, int32_t n_inst);
+int covo_set_step_ilqr_box(covo_handle_t h, int32_t *counts /* DEVICE [n_inst][COVO_MAX_STEP_ITERS]; NULL = off */, int32_t n_inst);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

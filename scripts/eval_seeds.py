@@ -24,11 +24,15 @@ name = sys.argv[1]
 # per control step (default 1: get_controller's); every seed's line also carries the share of plan steps that reached a fixed point
 # (ilqr_fixed_at < k) and the share that committed a closed-loop candidate in some iteration, summed on the device from the info dict
 # (the host loop of __call__ + episode.step: the summary row has no episode log)
+# python scripts/eval_seeds.py ilqr iters=2 --riccati-box (or mppi --riccati --riccati-feedback --riccati-box): every sweep solves the
+# control-limited stage problem (csrc/riccati.hip, the box form); compare with the same call without the flag.  Under ilqr every seed's
+# line also carries the share of plan steps whose first sweep clamped a coordinate (the masks have no episode log)
 rest = sys.argv[2:]
 refine = "--refine" in rest
 riccati = "--riccati" in rest
 feedback = "--riccati-feedback" in rest
-rest = [r for r in rest if r not in ("--refine", "--riccati", "--riccati-feedback")]
+box = "--riccati-box" in rest
+rest = [r for r in rest if r not in ("--refine", "--riccati", "--riccati-feedback", "--riccati-box")]
 for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_adapt"), ("--plan-hold", "plan_hold")):
     while flag in rest:
         i = rest.index(flag)
@@ -39,7 +43,7 @@ assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"}
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
 ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, riccati=riccati, riccati_feedback=feedback, plan_hold=plan_hold,
-                            **opts)
+                            riccati_box=box, **opts)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
@@ -50,7 +54,8 @@ class IlqrTally:
     def __init__(self, c):
         import torch
         self.c, self.core, self.init_control_params, self.alias_outputs = c, c.core, c.init_control_params, False
-        self.acc = torch.zeros(3, dtype=torch.int64, device=c.core.device)  # plan steps, of them at a fixed point, with a closed-loop commit
+        # plan steps, of them at a fixed point, with a closed-loop commit, with a clamped coordinate in the first sweep
+        self.acc = torch.zeros(4, dtype=torch.int64, device=c.core.device)
 
     def reset(self, *a):
         return self.c.reset(*a)
@@ -62,6 +67,8 @@ class IlqrTally:
             self.acc[0] += 1
             self.acc[1] += info["ilqr_fixed_at"] < self.c.iters
             self.acc[2] += info["ilqr_closed"] > 0
+            if "ilqr_box_count" in info:
+                self.acc[3] += info["ilqr_box_count"][0] > 0
         return u, cp, info
 
 
@@ -95,6 +102,8 @@ for seed in range(1, 13):
         acc = ctrl.acc.cpu().numpy()
         ctrl.acc.zero_()
         rows["fixed"], rows["closed"], rows["plans"] = int(acc[1]), int(acc[2]), int(acc[0])
+        if box:
+            rows["boxed"] = int(acc[3])
     n = max(rows.get("steps", 0), 1)
     npl = max(rows.get("plans", 0), 1)
     nh = max(rows.get("held", 0), 1)
@@ -102,6 +111,7 @@ for seed in range(1, 13):
                                                            ("improved", "  last pass beat first: %.3f", n),
                                                            ("fixed", "  plan steps at a fixed point: %.3f", npl),
                                                            ("closed", "  plan steps with a closed-loop commit: %.3f", npl),
+                                                           ("boxed", "  plan steps with a live box: %.3f", npl),
                                                            ("stale", "  hold steps on another trajectory's plan: %.3f", nh),
                                                            ("clipped", "  hold steps with a clipped component: %.3f", nh)) if k in rows)
     print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()) + extra,
