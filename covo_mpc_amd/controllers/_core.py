@@ -22,8 +22,7 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
-from ._options import (check_plan_hold, check_refine, check_riccati, check_riccati_box, check_riccati_feedback, check_kernel_path, check_step_options,
-                       sharded_refusal, take)
+from ._options import check_kernel_path, check_step_options, check_step_switches, sharded_refusal, take, take_switches
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
 # that attribute's value is the log's extra allocation argument: the fan's K, the iteration log's row width; covo_set_episode_rows' kind
@@ -79,18 +78,15 @@ class SamplingCore:
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False,
                  riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False):
-        opts = take(locals())
+        opts, switches = take(locals()), take_switches(locals())
         import torch
         sharded = False
         if process_group is not None:  # what sample-sharded ranks cannot have is refused before the device is looked for
             import torch.distributed as dist
             sharded = dist.get_world_size(process_group) > 1
         opt = check_step_options(N, "online", sharded=sharded, **opts)
-        refine = check_refine(refine, "online", sigma_period=opt.sigma_period, sharded=sharded)
-        riccati = check_riccati(riccati, "a sampling core", refine=refine, sharded=sharded)
-        riccati_feedback = check_riccati_feedback(riccati_feedback, riccati=riccati, what="a sampling core")
-        plan_hold = check_plan_hold(plan_hold, riccati=riccati, sigma_period=opt.sigma_period, what="a sampling core")
-        riccati_box = check_riccati_box(riccati_box, riccati=riccati, what="a sampling core")
+        sw = check_step_switches("a sampling core", mode_what="online", riccati_what="a sampling core", sigma_period=opt.sigma_period,
+                                 sharded=sharded, **switches)
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -227,30 +223,29 @@ class SamplingCore:
             self.sigma_adapt_rows[:, 1] = 1.0
             check(self.lib.covo_set_step_sigma_adapt(self.h, opt.sigma_adapt, ptr(self.sigma_adapt_rows), self._rows),
                   "covo_set_step_sigma_adapt")
-        # self.refine_rows [rows, 8]: {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, 0, bits(flags)} (refine=: a switch of
-        # the covo-online controllers, not a step option -- _options.check_refine)
-        self.refine = refine
-        self.refine_rows = self._attach_rows(_lib.COVO_REFINE_FLOATS, "covo_set_step_refine") if refine else None
-        # self.riccati_rows [rows, 8]: a refine row that ends {.., mu, bits(flags | rung << 8)} (riccati=: _options.check_riccati)
-        self.riccati_on = riccati  # (riccati() is the stand-alone sweep)
-        self.riccati_rows = self._attach_rows(_lib.COVO_RICCATI_FLOATS, "covo_set_step_riccati") if riccati else None
+        # the step switches' attachments (what each switch does: _options.STEP_SWITCH_DEFAULTS), as for the options above
+        # self.refine_rows [rows, 8]: {cost_base, cost_chosen, bits(choice), alpha, |g|_2, g.d, 0, bits(flags)}
+        self.refine = sw.refine
+        self.refine_rows = self._attach_rows(_lib.COVO_REFINE_FLOATS, "covo_set_step_refine") if sw.refine else None
+        # self.riccati_rows [rows, 8]: a refine row that ends {.., mu, bits(flags | rung << 8)}
+        self.riccati_on = sw.riccati  # (riccati() is the stand-alone sweep)
+        self.riccati_rows = self._attach_rows(_lib.COVO_RICCATI_FLOATS, "covo_set_step_riccati") if sw.riccati else None
         # self.riccati_feedback_rows [rows, 8]: {cost_open, cost_closed, bits(index open), bits(index closed), max |K dx|, bits(clipped),
-        # bits(invalid mask), 0} (riccati_feedback=: _options.check_riccati_feedback; attached behind riccati's rows, which it needs)
-        self.riccati_feedback_on = riccati_feedback
+        # bits(invalid mask), 0} (attached behind riccati's rows, which it needs)
+        self.riccati_feedback_on = sw.riccati_feedback
         self.riccati_feedback_rows = (self._attach_rows(_lib.COVO_FEEDBACK_FLOATS, "covo_set_step_riccati_feedback")
-                                      if riccati_feedback else None)
+                                      if sw.riccati_feedback else None)
         # self.plan_hold_rows [rows, 8]: {bits(age), alpha, max |v - v0|, bits(clipped), bits(flags), |dx_pos|, bits(time), 0}
-        # (plan_hold=: _options.check_plan_hold; attached behind riccati's rows, which it needs)
-        self.plan_hold_period = plan_hold  # (plan_hold() is the stateless hold step)
+        # (attached behind riccati's rows, which it needs)
+        self.plan_hold_period = sw.plan_hold  # (plan_hold() is the stateless hold step)
         self.plan_hold_rows = None
-        if plan_hold > 1:
+        if sw.plan_hold > 1:
             with torch.cuda.device(self.device):
-                self.plan_hold_rows = self._attach_rows(_lib.COVO_HOLD_FLOATS, "covo_set_step_plan_hold", plan_hold)
-        # self.riccati_box_masks [rows, 32] int32: the clamp masks of the last sweep (riccati_box=: _options.check_riccati_box; attached
-        # behind riccati's rows, which it needs)
-        self.riccati_box_on = riccati_box
+                self.plan_hold_rows = self._attach_rows(_lib.COVO_HOLD_FLOATS, "covo_set_step_plan_hold", sw.plan_hold)
+        # self.riccati_box_masks [rows, 32] int32: the clamp masks of the last sweep (attached behind riccati's rows, which it needs)
+        self.riccati_box_on = sw.riccati_box
         self.riccati_box_masks = None
-        if riccati_box:
+        if sw.riccati_box:
             self.riccati_box_masks = torch.zeros((self._rows, COVO_H), dtype=torch.int32, device=self.device)
             check(self.lib.covo_set_step_riccati_box(self.h, ptr(self.riccati_box_masks), self._rows), "covo_set_step_riccati_box")
         self._list_infos()

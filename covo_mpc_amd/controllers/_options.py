@@ -9,6 +9,12 @@ kernel-by-kernel debug path.  A new option is a keyword in those
 signatures, an entry here, and its own attachment block in SamplingCore.__init__ (tests/test_options_abi.py holds the signatures to
 this table).  The C side's counterpart is check_step_attachments (csrc/capi.hip).
 
+The step switches (refine, riccati, riccati_feedback, plan_hold, riccati_box) are not step options -- that list is pinned -- but have
+the same home: SamplingCore, CoVOController, MPPIController (no refine), BatchedCoVOController, get_controller and eval_env_batched carry
+the keywords of STEP_SWITCH_DEFAULTS, gather them with take_switches(locals()), have them checked by check_step_switches() and forward
+them as **switches; the iLQR controllers take three of them through check_ilqr.  A new switch is an entry in STEP_SWITCH_DEFAULTS, a
+keyword in those signatures, its check_*, and its attachment block in SamplingCore.__init__.
+
 Each option is off by default, and off changes nothing.  "info[...]" names what a single controller's __call__ then returns in its
 info dict (SamplingCore.*_info: views of the core's buffers, no sync, no copy); the batched controllers expose the same buffers with
 one row per instance.
@@ -64,10 +70,56 @@ STEP_OPTION_DEFAULTS = {
     "sigma_adapt": 0.0,
 }
 
+# the step switches, in the order the signatures list them and check_step_switches checks them.  Each is off by default, and off attaches
+# nothing and adds no launch; the C side's counterpart of each check_* is its block of check_step_attachments (csrc/capi.hip)
+STEP_SWITCH_DEFAULTS = {
+    # (covo-online only) every control step ends with a Newton line search on the mean it has just committed -- the gradient g of the
+    # Hessian's objective at that mean (csrc/cost_gradient.hip), the direction d = -Sigma (Sigma g) / c^2 from the step's own Sigma and c,
+    # the candidates clip(b + 2^(3 - j) d), j = 1 .. 16, next to clip(b) itself, judged by the step's own sampling objective
+    # (covo_set_step_refine, csrc/newton_refine.hip): info["refine_cost_base"] / ["refine_cost"] / ["refine_choice"] / ["refine_alpha"] /
+    # ["refine_grad_norm"] / ["refine_slope"]
+    "refine": False,
+    # every control step ends with the line search of refine along a direction that needs neither R nor Sigma -- the Hessian's first
+    # two launches at the committed mean leave the stage blocks of the plan, a backward Riccati sweep over them (csrc/riccati.hip) gives
+    # d = -(R + mu I)^-1 g on the lowest rung mu = 1e-2 4^j, j < 8, at which R + mu I is positive definite, and clip(b + 2^(3 - j) d),
+    # j = 1 .. 16, compete with clip(b) under the step's own sampling objective (covo_set_step_riccati): info["riccati_cost_base"] /
+    # ["riccati_cost"] / ["riccati_choice"] / ["riccati_alpha"] / ["riccati_grad_norm"] / ["riccati_slope"] / ["riccati_reg"] /
+    # ["riccati_rung"].  It goes with MPPI, covo-offline, covo-online and every sigma_period, next to the step options; under iters=k
+    # every pass runs it
+    "riccati": False,
+    # (on top of riccati) the line search behind every step judges 33 candidates instead of 17.  Candidates 0 .. 16 are riccati's own,
+    # bit for bit; 16 + j, j = 1 .. 16, is the closed-loop sequence at the same step size 2^(3 - j): the sweep's feed-forward terms and
+    # gains around the nonlinear plant, u_k = clip(b_k + alpha k_k + K_k (x_k - xb_k)) -- the forward pass of DDP / iLQR
+    # (covo_set_step_riccati_feedback, csrc/feedback_rollout.hip).  The first cheapest wins, so a closed-loop candidate is committed only
+    # when strictly cheaper than every open-loop one: info["riccati_closed"] / ["riccati_cost_open"] / ["riccati_cost_closed"] /
+    # ["riccati_gain_max"]
+    "riccati_feedback": False,
+    # = m > 1 (on top of riccati): every m-th control step, counted from reset(), is the control step as it is (a plan step); the m - 1
+    # between sample nothing -- one small launch (covo_set_step_plan_hold, csrc/plan_hold.hip) applies stage j of the law the plan step's
+    # Riccati sweep left, u = clip(b_j + alpha k_j + K_j (x - xb_j)), to the measured state, shifts the mean (MPPI: and the covariances)
+    # as a step's begin work does and puts u in front: info["plan_age"] (a Python int) / ["hold_gain"] / ["hold_clipped"] /
+    # ["hold_flags"] / ["hold_alpha"].  It goes with iters (a plan step runs its k passes), riccati_feedback and every step option but
+    # sigma_period; 1: nothing attached
+    "plan_hold": 1,
+    # (on top of riccati; the iLQR controllers take it too: BatchedILQRController's keyword, the class ILQRBoxController) every stage of
+    # every sweep the controller runs solves the box QP of control-limited DDP instead of the unconstrained 4 x 4 system --
+    # k_k = argmin 1/2 du^T Quu du + Qu^T du on -1 <= clip(b_k) + du <= 1; a clamped coordinate's k_k is the bound itself and its row of
+    # K_k is 0 (covo_set_step_riccati_box, csrc/riccati.hip).  Forward pass, candidates and judge are unchanged: info["riccati_box_mask"]
+    # [32] int32 (bits 0-3: coordinate i clamped at the lower bound, 4-7: at the upper) / ["riccati_box_count"] (the clamped coordinates
+    # of the last sweep).  It goes with every plant, drag / mixed included: the box lives in the 4 x 4 part
+    "riccati_box": False,
+}
+
 
 def take(namespace) -> dict:
     """The step options out of an entry point's locals(), ready to be checked and forwarded as **opts."""
     return {k: namespace[k] for k in STEP_OPTION_DEFAULTS}
+
+
+def take_switches(namespace) -> dict:
+    """The step switches out of an entry point's locals(), ready to be checked and forwarded as **switches.  A name the namespace lacks
+    is taken at its default: MPPIController has no refine (there is no Sigma to refine with), the one entry point that lacks a switch."""
+    return {k: namespace.get(k, default) for k, default in STEP_SWITCH_DEFAULTS.items()}
 
 
 @dataclass(frozen=True)
@@ -206,18 +258,7 @@ def check_step_options(N, what, *, gamma_sigma=None, fused_batched=False, sharde
 
 
 def check_refine(refine, what, *, sigma_period=1, sharded=False) -> bool:
-    """refine= of the covo-online controllers -> bool.  Not a step option (tests/test_options_abi.py pins their list): a switch of
-    SamplingCore, CoVOController, BatchedCoVOController, get_controller and eval_env_batched, like staged= of the env-batched MPPI /
-    covo-offline controllers, checked here by the same constructors, next to check_step_options; the C side's counterpart is the
-    refine block of check_step_attachments (csrc/capi.hip).
-
-    refine=True: every control step ends with a Newton line search on the mean it has just committed -- the gradient g of the Hessian's
-    objective at that mean (csrc/cost_gradient.hip), the direction d = -Sigma (Sigma g) / c^2 from the step's own Sigma and c, the
-    candidates clip(b + 2^(3 - j) d), j = 1 .. 16, next to clip(b) itself, judged by the step's own sampling objective
-    (covo_set_step_refine, csrc/newton_refine.hip): info["refine_cost_base"] / ["refine_cost"] / ["refine_choice"] / ["refine_alpha"] /
-    ["refine_grad_norm"] / ["refine_slope"].  False: nothing attached.
-
-    The objections, in a fixed order: anything but a bool (ValueError); `what` other than "online" -- MPPI, covo-offline and their
+    """refine= (STEP_SWITCH_DEFAULTS) -> bool.  The objections, in a fixed order: anything but a bool (ValueError); `what` other than "online" -- MPPI, covo-offline and their
     env-batched controllers have no Hessian-derived Sigma at the step's mean (ValueError); sigma_period > 1 -- a reuse step has no R,
     and its c means something else (ValueError); sharded -- sample-sharded ranks (NotImplementedError)."""
     if not isinstance(refine, bool):
@@ -238,19 +279,7 @@ def check_refine(refine, what, *, sigma_period=1, sharded=False) -> bool:
 
 
 def check_riccati(riccati, what, *, refine=False, sharded=False) -> bool:
-    """riccati= of every sampling controller -> bool.  Like refine=, a switch and not a step option: SamplingCore, MPPIController,
-    CoVOController (both modes), BatchedCoVOController(mode="online"), get_controller and eval_env_batched take it and check it here; the
-    C side's counterpart is the riccati block of check_step_attachments (csrc/capi.hip).
-
-    riccati=True: every control step ends with the line search of refine= along a direction that needs neither R nor Sigma -- the
-    Hessian's first two launches at the committed mean leave the stage blocks of the plan, a backward Riccati sweep over them
-    (csrc/riccati.hip) gives d = -(R + mu I)^-1 g on the lowest rung mu = 1e-2 4^j, j < 8, at which R + mu I is positive definite, and
-    clip(b + 2^(3 - j) d), j = 1 .. 16, compete with clip(b) under the step's own sampling objective (covo_set_step_riccati):
-    info["riccati_cost_base"] / ["riccati_cost"] / ["riccati_choice"] / ["riccati_alpha"] / ["riccati_grad_norm"] / ["riccati_slope"] /
-    ["riccati_reg"] / ["riccati_rung"].  It goes with MPPI, covo-offline, covo-online and every sigma_period, next to the step options;
-    under iters=k every pass runs it.  False: nothing attached.
-
-    The objections, in a fixed order: anything but a bool (ValueError); together with refine=True -- both polish the committed mean
+    """riccati= (STEP_SWITCH_DEFAULTS) -> bool.  The objections, in a fixed order: anything but a bool (ValueError); together with refine=True -- both polish the committed mean
     (ValueError); `what` one of the env-batched MPPI / covo-offline controllers, fused or staged -- their batches carry no Hessian
     constants (NotImplementedError); sharded -- sample-sharded ranks (NotImplementedError)."""
     if not isinstance(riccati, bool):
@@ -270,18 +299,7 @@ def check_riccati(riccati, what, *, refine=False, sharded=False) -> bool:
 
 
 def check_riccati_feedback(feedback, *, riccati, disturb_type=None, what="a sampling controller") -> bool:
-    """riccati_feedback= on top of riccati= -> bool.  A switch like riccati=, taken by the same callables (SamplingCore, MPPIController,
-    CoVOController, BatchedCoVOController, get_controller, eval_env_batched) and checked here; the C side's counterpart is the feedback
-    block of check_step_attachments (csrc/capi.hip).
-
-    riccati_feedback=True: the line search behind every step judges 33 candidates instead of 17.  Candidates 0 .. 16 are riccati='s
-    own, bit for bit; 16 + j, j = 1 .. 16, is the closed-loop sequence at the same step size 2^(3 - j): the sweep's feed-forward terms
-    and gains around the nonlinear plant, u_k = clip(b_k + alpha k_k + K_k (x_k - xb_k)) -- the forward pass of DDP / iLQR
-    (covo_set_step_riccati_feedback, csrc/feedback_rollout.hip).  The first cheapest wins, so a closed-loop candidate is committed only
-    when strictly cheaper than every open-loop one: info["riccati_closed"] / ["riccati_cost_open"] / ["riccati_cost_closed"] /
-    ["riccati_gain_max"].  False: nothing attached, no launch added.
-
-    The objections, in a fixed order: anything but a bool (ValueError); True without riccati=True -- the candidates run under that
+    """riccati_feedback= (STEP_SWITCH_DEFAULTS) -> bool.  The objections, in a fixed order: anything but a bool (ValueError); True without riccati=True -- the candidates run under that
     sweep's gains (ValueError); disturb_type drag / mixed -- the 16-state plants, whose force is a state of the sweep and a per-sample
     quantity of the rollout (NotImplementedError; disturb_type=None: not known here, the step refuses it)."""
     if not isinstance(feedback, bool):
@@ -299,18 +317,7 @@ def check_riccati_feedback(feedback, *, riccati, disturb_type=None, what="a samp
 
 
 def check_riccati_box(box, *, riccati, what="a sampling controller") -> bool:
-    """riccati_box= on top of riccati= -> bool.  A switch like riccati_feedback=, taken by the same callables (SamplingCore,
-    MPPIController, CoVOController, BatchedCoVOController, get_controller, eval_env_batched) and by the iLQR controllers (BatchedILQRController's keyword; the class ILQRBoxController), and checked
-    here; the C side's counterpart is the box block of check_step_attachments (csrc/capi.hip).
-
-    riccati_box=True: every stage of every sweep the controller runs solves the box QP of control-limited DDP instead of the
-    unconstrained 4 x 4 system -- k_k = argmin 1/2 du^T Quu du + Qu^T du on -1 <= clip(b_k) + du <= 1; a clamped coordinate's k_k is
-    the bound itself and its row of K_k is 0 (covo_set_step_riccati_box, csrc/riccati.hip).  Forward pass, candidates and judge are
-    unchanged: info["riccati_box_mask"] [32] int32 (bits 0-3: coordinate i clamped at the lower bound, 4-7: at the upper) /
-    ["riccati_box_count"] (the clamped coordinates of the last sweep).  It goes with every plant, drag / mixed included: the box lives
-    in the 4 x 4 part.  False: nothing attached, today's sweep.
-
-    The objections, in a fixed order: anything but a bool (ValueError); True without riccati=True -- it is that sweep's stage problem
+    """riccati_box= (STEP_SWITCH_DEFAULTS) -> bool.  The objections, in a fixed order: anything but a bool (ValueError); True without riccati=True -- it is that sweep's stage problem
     (ValueError).  Whatever riccati= refuses stays refused by check_riccati."""
     if not isinstance(box, bool):
         raise ValueError(f"riccati_box={box!r} (True | False)")
@@ -323,18 +330,7 @@ def check_riccati_box(box, *, riccati, what="a sampling controller") -> bool:
 
 
 def check_plan_hold(plan_hold, *, riccati, sigma_period=1, disturb_type=None, what="a sampling controller") -> int:
-    """plan_hold= on top of riccati= -> the period m.  A switch like riccati_feedback=, not a step option: SamplingCore, MPPIController,
-    CoVOController, BatchedCoVOController, get_controller and eval_env_batched take it and check it here; the C side's counterpart is
-    the plan hold block of check_step_attachments (csrc/capi.hip).
-
-    plan_hold=m > 1: every m-th control step, counted from reset(), is the control step as it is (a plan step); the m - 1 between
-    sample nothing -- one small launch (covo_set_step_plan_hold, csrc/plan_hold.hip) applies stage j of the law the plan step's Riccati
-    sweep left, u = clip(b_j + alpha k_j + K_j (x - xb_j)), to the measured state, shifts the mean (MPPI: and the covariances) as a
-    step's begin work does and puts u in front: info["plan_age"] (a Python int) / ["hold_gain"] / ["hold_clipped"] / ["hold_flags"] /
-    ["hold_alpha"].  It goes with iters (a plan step runs its k passes), riccati_feedback and every step option but sigma_period.
-    1: nothing attached, no launch added.
-
-    The objections, in a fixed order: anything but an integer in [1, COVO_MAX_PLAN_HOLD] (ValueError); m > 1 without riccati=True -- a
+    """plan_hold= (STEP_SWITCH_DEFAULTS) -> the period m.  The objections, in a fixed order: anything but an integer in [1, COVO_MAX_PLAN_HOLD] (ValueError); m > 1 without riccati=True -- a
     hold step applies that sweep's gains (ValueError); m > 1 with sigma_period > 1 -- both thin out the step, and sigma_adapt goes with
     it (ValueError); disturb_type drag / mixed -- the 16-state plants, as for riccati_feedback (NotImplementedError; disturb_type=None:
     not known here, the step refuses it).  Whatever riccati= refuses stays refused by check_riccati."""
@@ -357,6 +353,35 @@ def check_plan_hold(plan_hold, *, riccati, sigma_period=1, disturb_type=None, wh
                                   "a state of the sweep, and the hold step carries the 13-state plants only "
                                   "(covo_set_step_plan_hold refuses them at the step)")
     return m
+
+
+@dataclass(frozen=True)
+class StepSwitches:
+    """The step switches, checked (check_step_switches)."""
+    refine: bool
+    riccati: bool
+    riccati_feedback: bool
+    plan_hold: int      # 1: off
+    riccati_box: bool
+
+
+def check_step_switches(what, *, mode_what=None, riccati_what=None, sigma_period=1, disturb_type=None, sharded=False,
+                        **raw) -> StepSwitches:
+    """The step switches as given (**raw: the keywords of STEP_SWITCH_DEFAULTS, missing ones at their defaults) -> StepSwitches, or the
+    first objection of check_refine, check_riccati, check_riccati_feedback, check_plan_hold, check_riccati_box, in the table's order.
+    The names the messages show are the entry point's own: mode_what is the one check_refine shows and tests ("online" for covo-online;
+    default: what), riccati_what the one check_riccati does (default: mode_what), `what` the one of the other three."""
+    unknown = set(raw) - set(STEP_SWITCH_DEFAULTS)
+    if unknown:
+        raise TypeError(f"check_step_switches: unknown step switches {sorted(unknown)}")
+    o = {**STEP_SWITCH_DEFAULTS, **raw}
+    mode_what = what if mode_what is None else mode_what
+    refine = check_refine(o["refine"], mode_what, sigma_period=sigma_period, sharded=sharded)
+    riccati = check_riccati(o["riccati"], mode_what if riccati_what is None else riccati_what, refine=refine, sharded=sharded)
+    feedback = check_riccati_feedback(o["riccati_feedback"], riccati=riccati, disturb_type=disturb_type, what=what)
+    m = check_plan_hold(o["plan_hold"], riccati=riccati, sigma_period=sigma_period, disturb_type=disturb_type, what=what)
+    box = check_riccati_box(o["riccati_box"], riccati=riccati, what=what)
+    return StepSwitches(refine=refine, riccati=riccati, riccati_feedback=feedback, plan_hold=m, riccati_box=box)
 
 
 def check_ilqr(iters=2, *, riccati_feedback=None, plan_hold=1, disturb_type=None, refine=False, process_group=None,

@@ -22,7 +22,7 @@ from .. import _lib
 from .._lib import COVO_H, COVO_NA, check
 from ..dynamics.dataclass import as_device_state
 from ._core import SamplingCore
-from ._options import check_plan_hold, check_refine, check_riccati, check_riccati_box, check_riccati_feedback, check_step_options, take
+from ._options import check_step_options, check_step_switches, take, take_switches
 
 # (controller attribute, core attribute) of the attachment buffers the batched controllers hand out
 CORE_BUFFERS = (("diag", "diag"), ("plan", "plan"), ("fan", "fan"), ("arbiter", "arbiter"), ("lam_eff", "lam_eff"), ("elite", "elite_rows"),
@@ -43,7 +43,7 @@ class BatchedCoVOController:
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, staged: bool = False,
                  refine: bool = False, riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1,
                  riccati_box: bool = False):
-        opts = take(locals())
+        opts, switches = take(locals()), take_switches(locals())
         moded = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step
         if staged and not moded:
             raise ValueError("staged=True with mode=\"online\": the env-batched covo-online step is a staged launch sequence already; "
@@ -56,11 +56,7 @@ class BatchedCoVOController:
         what = ("online" if not moded else
                 "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
         check_step_options(N, what, fused_batched=fused, **opts)
-        check_refine(refine, what, sigma_period=sigma_period)
-        check_riccati(riccati, what, refine=refine)
-        check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
-        check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), what=what)
-        check_riccati_box(riccati_box, riccati=riccati, what=what)
+        check_step_switches(what, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), **switches)
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -77,8 +73,7 @@ class BatchedCoVOController:
         # one call advances all instances: the ~56 launches are worth a graph (same GPU time as eager, 40 us instead of
         # 150-270 us of host time per call)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
-                                 diag_rows=int(n_envs), refine=refine, riccati=riccati, riccati_feedback=riccati_feedback,
-                                 plan_hold=plan_hold, riccati_box=riccati_box, **opts)
+                                 diag_rows=int(n_envs), **switches, **opts)
         if moded:
             check(self.core.lib.covo_set_step_batched_staged(self.core.h, int(self.staged)), "covo_set_step_batched_staged")
         # after a call, row e of each of the core's attachment buffers holds instance e's result of that step; None for what is off
@@ -312,9 +307,9 @@ class BatchedILQRController(BatchedCoVOController):
         self.gamma_mean, self.sample_sigma, self.gamma_sigma = 1.0, 0.5, 0.0  # (fields of the argument block an iLQR step never reads)
         self.rollover_terminate = not getattr(env, "disable_rollover_terminate", True)
         # (eager: the iterations are eager launches; nothing of an iLQR step is captured)
-        self.core = build_ilqr_core(self.E, H, discount, iters=self.iters, riccati_feedback=self.riccati_feedback_on,
-                                    plan_hold=self.plan_hold, compute_plan=bool(compute_plan), device=device, use_graph=False,
-                                    riccati_box=riccati_box)
+        switches = dict(riccati_feedback=self.riccati_feedback_on, plan_hold=self.plan_hold, riccati_box=riccati_box)
+        self.core = build_ilqr_core(self.E, H, discount, iters=self.iters, switches=switches, compute_plan=bool(compute_plan),
+                                    device=device, use_graph=False)
         for mine, cores in CORE_BUFFERS:
             setattr(self, mine, getattr(self.core, cores))
         self.ilqr_rows, self.ilqr_feedback_rows, self.ilqr_summary = (self.core.ilqr_rows, self.core.ilqr_feedback_rows,

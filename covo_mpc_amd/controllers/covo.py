@@ -23,7 +23,7 @@ from ..dynamics.dataclass import as_device_state
 from .base import BaseController
 from .pid import PIDController, PIDParams
 from ._core import SamplingCore
-from ._options import check_plan_hold, check_refine, check_riccati, check_riccati_box, check_riccati_feedback, check_step_options, take
+from ._options import check_step_options, check_step_switches, take, take_switches
 
 
 @dataclass(frozen=True)
@@ -51,15 +51,11 @@ class CoVOController(BaseController):
                  elite=None, sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0,
                  refine: bool = False, riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1,
                  riccati_box: bool = False) -> None:
-        opts = take(locals())
+        opts, switches = take(locals()), take_switches(locals())
         what = mode if mode in ("online", "offline") else "online"
         check_step_options(N, what, **opts)  # ValueError before anything is built
-        check_refine(refine, "online" if what == "online" else "covo-offline", sigma_period=sigma_period)
-        check_riccati(riccati, "online" if what == "online" else "covo-offline", refine=refine)
-        check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=f"covo-{what}")
-        check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None),
-                        what=f"covo-{what}")
-        check_riccati_box(riccati_box, riccati=riccati, what=f"covo-{what}")
+        check_step_switches(f"covo-{what}", mode_what="online" if what == "online" else "covo-offline", sigma_period=sigma_period,
+                            disturb_type=getattr(env, "disturb_type", None), **switches)
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -78,8 +74,7 @@ class CoVOController(BaseController):
         self.mode = mode
         # propagate_nan: jnp.clip's NaN semantics in the sampling clip (covo.py:224) -- see SamplingCore
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
-                                 compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan, refine=refine, riccati=riccati,
-                                 riccati_feedback=riccati_feedback, plan_hold=plan_hold, riccati_box=riccati_box, **opts)
+                                 compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan, **switches, **opts)
 
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start (covo-online; covo-offline's reset builds its table): with a Sigma period the schedule restarts -- the first

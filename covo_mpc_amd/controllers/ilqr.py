@@ -32,12 +32,12 @@ class ILQRParams:
         return dataclasses.replace(self, **kw)
 
 
-def build_ilqr_core(n_rows, H, discount, *, iters, riccati_feedback, plan_hold, compute_plan, device, use_graph=None, riccati_box=False):
+def build_ilqr_core(n_rows, H, discount, *, iters, switches, compute_plan, device, use_graph=None):
     """The SamplingCore of an iLQR controller for n_rows instances: the Riccati rows [+ feedback rows, hold rows, plan rows] attached
-    as a sampling controller attaches them, the iteration count set, the per-iteration logs attached (SamplingCore.attach_ilqr)."""
+    as a sampling controller attaches them, the iteration count set, the per-iteration logs attached (SamplingCore.attach_ilqr).
+    switches: the step switches check_ilqr resolved (riccati_feedback, plan_hold, riccati_box); riccati is implied."""
     core = SamplingCore(ILQR_N, H, 1.0, discount, device=device, compute_info=False, trust_clipped=True, use_graph=use_graph,
-                        diag_rows=int(n_rows), compute_plan=compute_plan, iters=iters, riccati=True, riccati_feedback=riccati_feedback,
-                        plan_hold=plan_hold, riccati_box=riccati_box)
+                        diag_rows=int(n_rows), compute_plan=compute_plan, iters=iters, riccati=True, **switches)
     core.attach_ilqr()
     return core
 
@@ -58,9 +58,9 @@ class ILQRController(BaseController):
         self.H = H
         self.alias_outputs = False  # True: the returned a_mean aliases the controller's buffer (no clone)
         self._params_c(env.default_params)  # raises now if env.reward_fn / disturb_type is not one the kernels evaluate
-        self.core = build_ilqr_core(1, H, getattr(control_params, "discount", 1.0), iters=self.iters,
-                                    riccati_feedback=self.riccati_feedback, plan_hold=self.plan_hold, compute_plan=bool(compute_plan),
-                                    device=device, riccati_box=self.riccati_box)
+        switches = dict(riccati_feedback=self.riccati_feedback, plan_hold=self.plan_hold, riccati_box=self.riccati_box)
+        self.core = build_ilqr_core(1, H, getattr(control_params, "discount", 1.0), iters=self.iters, switches=switches,
+                                    compute_plan=bool(compute_plan), device=device)
 
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start: with a plan hold the schedule restarts -- the first step of the episode plans."""

@@ -14,7 +14,7 @@ from typing import Any
 from ..dynamics.dataclass import as_device_state
 from .base import BaseController
 from ._core import SamplingCore
-from ._options import check_plan_hold, check_riccati, check_riccati_box, check_riccati_feedback, check_step_options, take
+from ._options import check_step_options, check_step_switches, take, take_switches
 
 
 @dataclass(frozen=True)
@@ -37,13 +37,10 @@ class MPPIController(BaseController):
                  ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None, sigma_period: int = 1,
                  compute_post_cov: bool = False, sigma_adapt: float = 0.0, riccati: bool = False,
                  riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False) -> None:
-        opts = take(locals())
+        opts, switches = take(locals()), take_switches(locals())  # (no refine here: taken at its default, off)
         # ValueError before anything is built (MPPI computes no Sigma per step: sigma_period / sigma_adapt stay at their defaults)
         check_step_options(N, "MPPI", gamma_sigma=getattr(control_params, "gamma_sigma", 0.0), **opts)
-        check_riccati(riccati, "MPPI")
-        check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what="MPPI")
-        check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), what="MPPI")
-        check_riccati_box(riccati_box, riccati=riccati, what="MPPI")
+        check_step_switches("MPPI", sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), **switches)
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -55,8 +52,7 @@ class MPPIController(BaseController):
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
                                  compute_info=compute_info, trust_clipped=True,
                                  cov_records=float(getattr(control_params, "gamma_sigma", 0.0)) != 0.0, propagate_nan=propagate_nan,
-                                 riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold, riccati_box=riccati_box,
-                                 **opts)
+                                 **switches, **opts)
 
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start: with a plan hold the schedule restarts -- the first step of the episode plans."""

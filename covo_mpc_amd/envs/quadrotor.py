@@ -20,8 +20,8 @@ import numpy as np
 
 from .. import controllers
 from .. import random as crandom
-from ..controllers._options import (STEP_OPTION_DEFAULTS, check_ilqr, check_plan_hold, check_refine, check_riccati, check_riccati_box, check_riccati_feedback, check_step_options,
-                                    take)
+from ..controllers._options import (STEP_OPTION_DEFAULTS, STEP_SWITCH_DEFAULTS, check_ilqr, check_step_options, check_step_switches,
+                                    take, take_switches)
 from ..dynamics import utils
 from ..dynamics.dataclass import Action3D, DeviceState, EnvParams3D, EnvState3D
 from ..dynamics.free import get_quadrotor_1st_order_dyn
@@ -619,17 +619,14 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     if controller not in ("covo-online", "mppi", "covo-offline", "ilqr"):
         raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline' or 'ilqr'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
+    switches = take_switches(locals())
     if controller == "ilqr":
-        return _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, refine,
-                                  riccati_feedback, plan_hold, opts, riccati_box)
-    check_step_options(None, "online" if controller == "covo-online" else controller, **opts)  # ValueError before anything is built
-    check_refine(refine, "online" if controller == "covo-online" else controller, sigma_period=sigma_period)
-    check_riccati(riccati, "online" if controller == "covo-online" else f"the env-batched {controller} controller", refine=refine)
-    check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None),
-                           what=f"the env-batched {controller} controller")
-    check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None),
-                    what=f"the env-batched {controller} controller")
-    check_riccati_box(riccati_box, riccati=riccati, what=f"the env-batched {controller} controller")
+        return _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, switches,
+                                  opts)
+    online, batch = controller == "covo-online", f"the env-batched {controller} controller"
+    check_step_options(None, "online" if online else controller, **opts)  # ValueError before anything is built
+    check_step_switches(batch, mode_what="online" if online else controller, riccati_what="online" if online else batch,
+                        sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), **switches)
     if arbiter and update == "softmax":
         raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
     from .. import controllers
@@ -640,13 +637,11 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     c0, cp0 = get_controller(env, controller, controller_params, device=device, compute_info=False)
     cp0 = c0.init_control_params
     kw = dict(discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=c0.core.device, staged=staged, **opts)
-    if controller == "mppi":  # (riccati_box needs riccati, which check_riccati has refused for the two baselines)
+    if controller == "mppi":  # (it takes no switch: check_riccati has refused riccati, which the others need, for the two baselines)
         b = controllers.BatchedMPPIController(env, n_envs, N, H, lam, sigmas=cp0.sample_sigma, **kw)
     else:
         b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, sample_sigma=cp0.sample_sigma,
-                                              mode="offline" if controller == "covo-offline" else "online", refine=refine,
-                                              riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold,
-                                              riccati_box=riccati_box, **kw)
+                                              mode="offline" if controller == "covo-offline" else "online", **switches, **kw)
     del c0
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     if controller == "covo-offline":  # (the table keys: children of the instances' control keys, which stay what they were)
@@ -675,14 +670,19 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     return out if len(out) > 1 else out[0]
 
 
-def _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, refine,
-                       riccati_feedback, plan_hold, opts, riccati_box=False):
+def _check_ilqr_switches(env, switches, opts, process_group=None):
+    """check_ilqr on the sampling controllers' keywords, as get_controller and eval_env_batched carry them: riccati is implied, and
+    riccati_feedback=False (those signatures' default) leaves the choice to the plant -> (iters, riccati_feedback, plan_hold)."""
+    sw = {s: v for s, v in switches.items() if s != "riccati"}
+    return check_ilqr(opts["iters"], disturb_type=getattr(env, "disturb_type", None), process_group=process_group,
+                      **{**sw, "riccati_feedback": sw["riccati_feedback"] or None}, **{o: v for o, v in opts.items() if o != "iters"})
+
+
+def _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, switches, opts):
     """eval_env_batched(controller="ilqr"): the same instances, reset keys and key chains under BatchedILQRController (H from
     controller_params; N and lam are ignored; riccati_feedback as for get_controller).  rows=True appends {"hold": ep.read_hold()}
     under plan_hold > 1 (else {})."""
-    k, feedback, m = check_ilqr(opts["iters"], riccati_feedback=riccati_feedback or None, plan_hold=plan_hold,
-                                disturb_type=getattr(env, "disturb_type", None), refine=refine, riccati_box=riccati_box,
-                                **{o: v for o, v in opts.items() if o != "iters"})
+    k, feedback, m = _check_ilqr_switches(env, switches, opts)
     if staged or arbiter:
         raise ValueError(f"{'staged' if staged else 'arbiter'}=True with controller='ilqr': a switch of the sampling batches")
     from .. import controllers
@@ -693,7 +693,7 @@ def _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, ve
     th = (dp.m * dp.g / dp.max_thrust) * 2.0 - 1.0
     b = controllers.BatchedILQRController(env, n_envs, H, iters=k, riccati_feedback=feedback, plan_hold=m, compute_plan=trace,
                                           a_mean_init=np.tile(np.array([th, 0.0, 0.0, 0.0], dtype=np.float32), H), device=device,
-                                          riccati_box=riccati_box)
+                                          riccati_box=switches["riccati_box"])
     ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
     T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
     t0 = time_module.time()
@@ -823,11 +823,9 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     controller_params, N and lam are ignored; iters, plan_hold and compute_plan pass through, riccati is implied, riccati_feedback=True
     asks for the closed-loop candidates and False (this signature's default) leaves the choice to the plant (ILQRController's None);
     every other step option away from its default is a ValueError."""
-    opts = take(locals())
+    opts, switches = take(locals()), take_switches(locals())
     if controller_name == "ilqr":  # ValueError / NotImplementedError before anything is built
-        k, feedback, m = check_ilqr(iters, riccati_feedback=riccati_feedback or None, plan_hold=plan_hold,
-                                    disturb_type=getattr(env, "disturb_type", None), refine=refine, process_group=process_group,
-                                    riccati_box=riccati_box, **{o: v for o, v in opts.items() if o != "iters"})
+        k, feedback, m = _check_ilqr_switches(env, switches, opts, process_group=process_group)
     import torch
     if controller_name == "ilqr":
         H = int(controller_params.split("_")[1][1:]) if controller_params else 32
@@ -842,11 +840,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     # ValueError before anything is built; the controller's own check, with N, follows
     what = "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name
     check_step_options(None, what, **opts)
-    check_refine(refine, what, sigma_period=sigma_period)
-    check_riccati(riccati, what, refine=refine)
-    check_riccati_feedback(riccati_feedback, riccati=riccati, disturb_type=getattr(env, "disturb_type", None), what=what)
-    check_plan_hold(plan_hold, riccati=riccati, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), what=what)
-    check_riccati_box(riccati_box, riccati=riccati, what=what)
+    check_step_switches(what, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), **switches)
 
     def parse_sample_params(param_text):
         if not param_text:
@@ -872,9 +866,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         control_params = controllers.MPPIParams(gamma_mean=1.0, gamma_sigma=0.0, discount=1.0, sample_sigma=sigma,
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
-                                          process_group=process_group, compute_info=compute_info, riccati=riccati,
-                                          riccati_feedback=riccati_feedback, plan_hold=plan_hold, riccati_box=riccati_box,
-                                          **opts), control_params
+                                          process_group=process_group, compute_info=compute_info,  # (MPPI has no refine: refused above)
+                                          **{s: v for s, v in switches.items() if s != "refine"}, **opts), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -885,9 +878,8 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
             a_cov=torch.eye(H * env.action_dim, dtype=torch.float32, device=device) * sigma ** 2,
             a_cov_offline=torch.zeros((H, env.action_dim, env.action_dim), dtype=torch.float32, device=device))
         return controllers.CoVOController(env=env, control_params=control_params, N=N, H=H, lam=lam, mode=mode,
-                                          device=device, process_group=process_group, compute_info=compute_info,
-                                          refine=refine, riccati=riccati, riccati_feedback=riccati_feedback, plan_hold=plan_hold,
-                                          riccati_box=riccati_box, **opts), control_params
+                                          device=device, process_group=process_group, compute_info=compute_info, **switches,
+                                          **opts), control_params
     raise NotImplementedError(controller_name)
 
 
@@ -1018,9 +1010,7 @@ def main(args: Args):
                                                 compute_plan=render, compute_fan=(args.fan or None) if render else None,
                                                 update=args.update, iters=args.iters, elite=args.elite or None,
                                                 sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render,
-                                                sigma_adapt=args.sigma_adapt, refine=args.refine,
-                                                riccati=args.riccati, riccati_feedback=args.riccati_feedback,
-                                                plan_hold=args.plan_hold, riccati_box=args.riccati_box)
+                                                sigma_adapt=args.sigma_adapt, **take_switches(vars(args)))
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -1037,10 +1027,8 @@ def _cli():
     for f, default in Args().__dict__.items():
         if f == "post_cov":
             ap.add_argument("--post-cov", "--post_cov", dest="post_cov", action="store_true")
-        elif f == "riccati_feedback":
-            ap.add_argument("--riccati-feedback", "--riccati_feedback", dest="riccati_feedback", action="store_true")
-        elif f == "riccati_box":
-            ap.add_argument("--riccati-box", "--riccati_box", dest="riccati_box", action="store_true")
+        elif isinstance(STEP_SWITCH_DEFAULTS.get(f), bool):  # --name-with-dashes, and --name_as_it_is where that is another spelling
+            ap.add_argument(*dict.fromkeys((f"--{f.replace('_', '-')}", f"--{f}")), dest=f, action="store_true")
         elif f == "plan_hold":
             ap.add_argument("--plan-hold", "--plan_hold", dest="plan_hold", type=int, default=default)
         elif isinstance(default, bool):

@@ -1,6 +1,7 @@
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
+from covo_mpc_amd.controllers._options import STEP_SWITCH_DEFAULTS
 from covo_mpc_amd.envs import quadrotor as Q
 name = sys.argv[1]
 # python scripts/eval_seeds.py covo-online [elite=512]: the elite-set update with K elites instead of the softmax weights
@@ -28,22 +29,20 @@ name = sys.argv[1]
 # control-limited stage problem (csrc/riccati.hip, the box form); compare with the same call without the flag.  Under ilqr every seed's
 # line also carries the share of plan steps whose first sweep clamped a coordinate (the masks have no episode log)
 rest = sys.argv[2:]
-refine = "--refine" in rest
-riccati = "--riccati" in rest
-feedback = "--riccati-feedback" in rest
-box = "--riccati-box" in rest
-rest = [r for r in rest if r not in ("--refine", "--riccati", "--riccati-feedback", "--riccati-box")]
+# the boolean step switches as flags: --refine, --riccati, --riccati-feedback, --riccati-box
+flags = {f"--{s.replace('_', '-')}": s for s, default in STEP_SWITCH_DEFAULTS.items() if isinstance(default, bool)}
+switches = {s: flag in rest for flag, s in flags.items()}
+rest = [r for r in rest if r not in flags]
 for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_adapt"), ("--plan-hold", "plan_hold")):
     while flag in rest:
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
 opts = {k: (float(v) if k in ("sigma_adapt", "ess_min") else int(v)) for k, v in (arg.split("=") for arg in rest)}
-plan_hold = opts.pop("plan_hold", 1)
+switches["plan_hold"] = opts.pop("plan_hold", 1)
 assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"}, opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
-ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", refine=refine, riccati=riccati, riccati_feedback=feedback, plan_hold=plan_hold,
-                            riccati_box=box, **opts)
+ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **switches, **opts)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
@@ -102,7 +101,7 @@ for seed in range(1, 13):
         acc = ctrl.acc.cpu().numpy()
         ctrl.acc.zero_()
         rows["fixed"], rows["closed"], rows["plans"] = int(acc[1]), int(acc[2]), int(acc[0])
-        if box:
+        if switches["riccati_box"]:
             rows["boxed"] = int(acc[3])
     n = max(rows.get("steps", 0), 1)
     npl = max(rows.get("plans", 0), 1)

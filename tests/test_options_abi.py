@@ -109,3 +109,66 @@ def test_check_step_options_objects_in_its_fixed_order():
         check_step_options(256, "online", sharded=True, ess_min=8, compute_post_cov=True, compute_plan=True)
     with pytest.raises(NotImplementedError, match="compute_diag on sample-sharded ranks"):
         check_step_options(256, "online", sharded=True, compute_diag=True, compute_plan=True)
+
+
+def test_every_entry_point_carries_the_switches():
+    """The step switches' table against the signatures, as for the step options above: names, defaults and the defaults' exact types."""
+    from covo_mpc_amd import controllers
+    from covo_mpc_amd.controllers._core import SamplingCore
+    from covo_mpc_amd.controllers._options import STEP_SWITCH_DEFAULTS
+    from covo_mpc_amd.envs.quadrotor import eval_env_batched, get_controller
+    assert list(STEP_SWITCH_DEFAULTS) == ["refine", "riccati", "riccati_feedback", "plan_hold", "riccati_box"]
+    assert STEP_SWITCH_DEFAULTS == {"refine": False, "riccati": False, "riccati_feedback": False, "plan_hold": 1, "riccati_box": False}
+    assert type(STEP_SWITCH_DEFAULTS["plan_hold"]) is int
+    for fn in (SamplingCore.__init__, controllers.CoVOController.__init__, controllers.MPPIController.__init__,
+               controllers.BatchedCoVOController.__init__, get_controller, eval_env_batched):
+        p = inspect.signature(fn).parameters
+        assert not any(q.kind in (q.VAR_KEYWORD, q.VAR_POSITIONAL) for q in p.values()), fn
+        for name, default in STEP_SWITCH_DEFAULTS.items():
+            if fn is controllers.MPPIController.__init__ and name == "refine":  # the one documented exception (take_switches)
+                assert name not in p
+                continue
+            assert name in p, (fn, name)
+            assert p[name].default == default and type(p[name].default) is type(default), (fn, name)
+        # in the table's order
+        assert [n for n in p if n in STEP_SWITCH_DEFAULTS] == [n for n in STEP_SWITCH_DEFAULTS if n in p], fn
+    # the env-batched MPPI controller carries no switch (its step refuses riccati, which the others build on)
+    p = inspect.signature(controllers.BatchedMPPIController.__init__).parameters
+    assert not set(STEP_SWITCH_DEFAULTS) & set(p) and "staged" in p
+    # the iLQR controllers: riccati is implied, refine has nothing to work with; the batched one takes the other three as keywords,
+    # the single one's published parameter list carries no riccati_box (the class ILQRBoxController)
+    p = inspect.signature(controllers.BatchedILQRController.__init__).parameters
+    assert p["riccati_feedback"].default is None and p["plan_hold"].default == 1 and type(p["plan_hold"].default) is int
+    assert p["riccati_box"].default is False and "refine" not in p and "riccati" not in p
+    p = inspect.signature(controllers.ILQRController.__init__).parameters
+    assert list(p) == ["self", "env", "control_params", "H", "iters", "riccati_feedback", "plan_hold", "compute_plan", "device"]
+    assert p["riccati_feedback"].default is None and p["plan_hold"].default == 1
+    assert not {"riccati_box", "refine", "riccati"} & set(p)
+
+
+def test_take_switches_and_unknown_keywords():
+    from covo_mpc_amd.controllers._options import STEP_SWITCH_DEFAULTS, check_step_switches, take_switches
+    ns = dict(STEP_SWITCH_DEFAULTS, self=None, N=256, riccati=True, plan_hold=3)
+    assert take_switches(ns) == dict(STEP_SWITCH_DEFAULTS, riccati=True, plan_hold=3)
+    assert list(take_switches(ns)) == list(STEP_SWITCH_DEFAULTS)
+    # a namespace without refine (MPPIController's): taken at its default
+    del ns["refine"]
+    assert take_switches(ns) == dict(STEP_SWITCH_DEFAULTS, riccati=True, plan_hold=3) and take_switches(ns)["refine"] is False
+    assert take_switches({}) == STEP_SWITCH_DEFAULTS
+    with pytest.raises(TypeError, match=r"check_step_switches: unknown step switches \['riccati_boxx'\]"):
+        check_step_switches("online", riccati_boxx=True)
+    with pytest.raises(TypeError, match="unknown step switches"):  # a step option is not a switch
+        check_step_switches("online", iters=2)
+
+
+def test_check_step_switches_returns_the_record():
+    from covo_mpc_amd.controllers._options import StepSwitches, check_step_switches
+    off = check_step_switches("online")
+    assert off == StepSwitches(refine=False, riccati=False, riccati_feedback=False, plan_hold=1, riccati_box=False)
+    assert off.refine is False and off.riccati is False and type(off.plan_hold) is int
+    on = check_step_switches("covo-offline", mode_what="covo-offline", disturb_type="gaussian", riccati=True, riccati_feedback=True,
+                             plan_hold=3, riccati_box=True)
+    assert on == StepSwitches(refine=False, riccati=True, riccati_feedback=True, plan_hold=3, riccati_box=True)
+    assert check_step_switches("a sampling core", mode_what="online", riccati_what="a sampling core", refine=True).refine is True
+    with pytest.raises(Exception):  # frozen
+        on.plan_hold = 1
