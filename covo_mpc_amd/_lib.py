@@ -37,6 +37,10 @@ COVO_ARB_FLOATS = 8  # an arbiter row: {cost_softmax, cost_nominal, cost_best, c
 COVO_MAX_STEP_ITERS = 16  # iters= of the controllers: sample-rollout-update passes per control step (covo_hip.h: COVO_HAS_STEP_ITERS)
 UPDATE_MASKS = {"softmax": 0, "best": 0b110, "guarded": 0b111}  # update= of the controllers -> the arbiter's candidate mask (0: detached)
 LAM_FIELDS = ("lam_eff", "inv_lam_eff", "ess_lam0", "evaluations")
+COVO_HAS_STEP_ANNEAL = 1  # the "dial" controller (covo_set_step_anneal, covo_cost_standardise): per-pass noise schedule, standardised weights
+# the standardising solver's row: {lam_eff, 1 / lam_eff, std, bits(int32 |F| | fallback << 31)}, F the pass's finite costs
+ANNEAL_FIELDS = ("lam_eff", "inv_lam_eff", "std", "n_finite")
+ANNEAL_FALLBACK_BIT = 0x80000000
 COVO_HAS_ELITE_UPDATE = 1
 COVO_ELITE_FLOATS = 8  # the elite-set update's selector row of one instance (covo_set_step_elite)
 ELITE_FIELDS = ("threshold_cost_word", "threshold_index_word", "cost_min", "cost_kth", "K", "ties")  # words: uint32 bits
@@ -227,6 +231,9 @@ _SIGS = {
     "covo_set_step_batched_staged": (C.c_int, [_P, C.c_int32]),  # the staged batched step (covo_hip.h: COVO_HAS_BATCHED_STAGED)
     "covo_set_step_ess_floor": (C.c_int, [_P, C.c_float, _P, C.c_int32]),  # the ESS floor (covo_hip.h: COVO_HAS_ESS_FLOOR)
     "covo_ess_lambda": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
+    # the annealed step (covo_hip.h: COVO_HAS_STEP_ANNEAL)
+    "covo_set_step_anneal": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.c_float, _P, C.c_int32]),
+    "covo_cost_standardise": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
     "covo_set_step_elite": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # the elite-set update (covo_hip.h: COVO_HAS_ELITE_UPDATE)
     "covo_elite_select": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "covo_set_step_sigma_period": (C.c_int, [_P, C.c_int32]),  # the Sigma period (covo_hip.h: COVO_HAS_SIGMA_PERIOD)

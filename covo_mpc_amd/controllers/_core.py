@@ -32,7 +32,7 @@ EPISODE_LOGS = {"diag_log": ("compute_diag", "covo_set_episode_diag_log", False,
                 "trace": ("compute_plan", "covo_set_episode_trace", False, None, None),
                 "fanlog": ("compute_fan", "covo_set_episode_fan", True, None, None),
                 "arblog": ("arb_mask", "covo_set_episode_arbiter_log", False, None, None),
-                "lamlog": ("ess_min", _ROWS, False, _lib.COVO_EPLOG_LAM, None),
+                "lamlog": ("lam_logged", _ROWS, False, _lib.COVO_EPLOG_LAM, None),
                 "elitelog": ("elite", _ROWS, False, _lib.COVO_EPLOG_ELITE, None),
                 "iterlog": ("iters_logged", _ROWS, True, _lib.COVO_EPLOG_ITERS, None),
                 "sigmalog": ("sigma_logged", _ROWS, False, _lib.COVO_EPLOG_SIGMA, None),
@@ -77,7 +77,7 @@ class SamplingCore:
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False,
-                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False):
+                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False, anneal=None):
         opts, switches = take(locals()), take_switches(locals())
         import torch
         sharded = False
@@ -87,6 +87,9 @@ class SamplingCore:
         opt = check_step_options(N, "online", sharded=sharded, **opts)
         sw = check_step_switches("a sampling core", mode_what="online", riccati_what="a sampling core", sigma_period=opt.sigma_period,
                                  sharded=sharded, **switches)
+        if anneal is not None and sharded:
+            raise NotImplementedError("anneal= on sample-sharded ranks: a rank sees only its shard's costs (covo_set_step_anneal "
+                                      "refuses sample-sharded steps)")
         if H != COVO_H:
             raise NotImplementedError(f"the fused kernels are built for H={COVO_H}, got H={H}")
         if not torch.cuda.is_available():
@@ -248,7 +251,11 @@ class SamplingCore:
         if sw.riccati_box:
             self.riccati_box_masks = torch.zeros((self._rows, COVO_H), dtype=torch.int32, device=self.device)
             check(self.lib.covo_set_step_riccati_box(self.h, ptr(self.riccati_box_masks), self._rows), "covo_set_step_riccati_box")
+        # the annealed step (not a step option: the attachment of the controllers of controllers/dial.py; _options.check_dial)
+        self.anneal = self.anneal_sigma = self.anneal_rows = None
         self._list_infos()
+        if anneal is not None:
+            self.attach_anneal(anneal)
         self.exchange = "collective"
         if self.world > 1:
             # "collective" (default): torch.distributed's all-gather = RCCL over xGMI.  "peer": the peer-write exchange
@@ -400,12 +407,14 @@ class SamplingCore:
             (self.riccati_rows is not None, self.riccati_info),
             (self.riccati_feedback_rows is not None, self.riccati_feedback_info),
             (self.plan_hold_rows is not None, self.plan_hold_info),
-            (self.riccati_box_masks is not None, self.riccati_box_info)) if on]
+            (self.riccati_box_masks is not None, self.riccati_box_info),
+            (getattr(self, "anneal_rows", None) is not None, self.anneal_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
         lam_info (ess_min), arbiter_info (update), iter_info (iters), elite_info (elite), sigma_info (sigma_period), post_cov_info
-        (compute_post_cov) and sigma_adapt_info (sigma_adapt) -- views of the core's buffers, no sync, no copy."""
+        (compute_post_cov), sigma_adapt_info (sigma_adapt) and anneal_info (the annealed controllers' attachment) -- views of the core's
+        buffers, no sync, no copy."""
         out = {}
         for info in self._infos:
             out.update(info())
@@ -616,6 +625,58 @@ class SamplingCore:
         i32 = self.torch.int32
         return {"plan_age": self._plan_ages()[1], "hold_gain": row[2], "hold_clipped": row[3:4].view(i32)[0],
                 "hold_flags": row[4:5].view(i32)[0], "hold_alpha": row[1]}
+
+    def attach_anneal(self, anneal):
+        """The annealed step's attachment (covo_set_step_anneal; anneal: the record _options.check_dial returns, its table one row per
+        pass of this core's iters): self.anneal_sigma [iters, 32] -- the schedule, a device copy of the table the handle holds -- and
+        self.anneal_rows [rows, iters, 4]: instance e's row {lam_eff, 1 / lam_eff, std, bits(|F| | fallback << 31)} of every pass,
+        written by the passes' solver launches under temp; without temp no solver runs and the rows stay {lam, 1 / lam, 0, 0}."""
+        torch = self.torch
+        sigma = np.ascontiguousarray(anneal.sigma, dtype=np.float32)
+        if sigma.shape != (self.iters, COVO_H):
+            raise ValueError(f"attach_anneal: the schedule is {sigma.shape}, this core runs iters={self.iters} passes of H={COVO_H}")
+        self.anneal = anneal
+        self.anneal_sigma = torch.from_numpy(sigma).to(self.device)
+        self.anneal_rows = torch.zeros((self._rows, self.iters, _lib.COVO_LAM_FLOATS), dtype=torch.float32, device=self.device)
+        self.anneal_rows[..., 0] = self.lam
+        self.anneal_rows[..., 1] = float(np.float32(1.0) / np.float32(self.lam))
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_set_step_anneal(self.h, sigma.ctypes.data_as(C.POINTER(C.c_float)), self.iters, float(anneal.temp),
+                                                ptr(self.anneal_rows) if anneal.temp > 0.0 else None, self._rows),
+                  "covo_set_step_anneal")
+        self._list_infos()
+
+    @property
+    def lam_logged(self) -> bool:
+        """A temperature row is written per step (the ESS floor's, or the annealed step's last pass's): the episodes keep its log."""
+        return self.ess_min != 0.0 or (self.anneal is not None and self.anneal.temp > 0.0)
+
+    def anneal_info(self) -> dict:
+        """{"anneal_sigma" [k, 32], "anneal_rows" [k, 4], "anneal_lam" [k], "anneal_std" [k], "anneal_fallback" [k] bool} of the last
+        step's k passes, and under temp "lam_eff", the last pass's -- views of self.anneal_sigma / self.anneal_rows (no sync; the bool
+        is one device op on a view); {} on a core without the attachment."""
+        if self.anneal_rows is None:
+            return {}
+        rows = self.anneal_rows[0]
+        out = {"anneal_sigma": self.anneal_sigma, "anneal_rows": rows, "anneal_lam": rows[:, 0], "anneal_std": rows[:, 2],
+               "anneal_fallback": rows[:, 3].view(self.torch.int32) < 0}
+        if self.anneal.temp > 0.0:
+            out["lam_eff"] = rows[-1, 0]
+        return out
+
+    def cost_standardise(self, cost, temp, lam0=None):
+        """covo_cost_standardise (the stand-alone standardising solver): cost float32 device tensor [N] or [E, N] -> float32 [E, 4] rows
+        {lam_eff, 1 / lam_eff, std, bits(|F| | fallback << 31)}: lam_eff = fp32(temp x the population standard deviation of the finite
+        costs), lam0 (default: the core's lam) on fallback (include/covo_hip.h)."""
+        torch = self.torch
+        assert cost.is_cuda and cost.dtype == torch.float32 and cost.is_contiguous()
+        c2 = cost.reshape(1, -1) if cost.dim() == 1 else cost
+        E, N = int(c2.shape[0]), int(c2.shape[1])
+        out = torch.empty((E, _lib.COVO_LAM_FLOATS), dtype=torch.float32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_cost_standardise(self.h, ptr(cost), N, E, float(self.lam if lam0 is None else lam0), float(temp),
+                                                 ptr(out), self.stream()), "covo_cost_standardise")
+        return out
 
     def attach_ilqr(self):
         """The per-iteration logs of an iLQR controller's core (covo_set_step_ilqr; the controllers of controllers/ilqr.py and

@@ -15,6 +15,9 @@ the keywords of STEP_SWITCH_DEFAULTS, gather them with take_switches(locals()), 
 them as **switches; the iLQR controllers take three of them through check_ilqr.  A new switch is an entry in STEP_SWITCH_DEFAULTS, a
 keyword in those signatures, its check_*, and its attachment block in SamplingCore.__init__.
 
+The annealed MPPI controllers (controllers/dial.py, BatchedDialController) are neither: like the iLQR controllers they are controllers of
+their own, checked by check_dial at the end of this file, which hands SamplingCore its one anneal= record.
+
 Each option is off by default, and off changes nothing.  "info[...]" names what a single controller's __call__ then returns in its
 info dict (SamplingCore.*_info: views of the core's buffers, no sync, no copy); the batched controllers expose the same buffers with
 one row per instance.
@@ -432,3 +435,61 @@ def check_ilqr(iters=2, *, riccati_feedback=None, plan_hold=1, disturb_type=None
     m = check_plan_hold(plan_hold, riccati=True, disturb_type=disturb_type, what=what)
     check_riccati_box(riccati_box, riccati=True, what=what)  # (a bool, returned as given: the callers pass it on)
     return k, feedback, m
+
+
+@dataclass(frozen=True)
+class Anneal:
+    """The annealed step's attachment, checked (check_dial): what SamplingCore's anneal= keyword takes."""
+    sigma: object       # float32 numpy [iters, 32]: sigma[i][h] of pass i, stage h (anneal_schedule)
+    temp: float         # 0.0: every pass updates at the configured lam, no solver runs
+    beta_pass: float
+    beta_stage: float
+
+
+def anneal_schedule(sample_sigma, iters, beta_pass, beta_stage, H=_lib.COVO_H):
+    """sigma[i][h] = fp32(sample_sigma beta_pass^i beta_stage^(H - 1 - h)), i < iters, h < H: formed in fp64, rounded once -> float32
+    numpy [iters, H].  Later passes draw from a narrower distribution; near stages of the horizon get less noise than far ones."""
+    import numpy as np
+    s0, bp, bs = float(sample_sigma), float(beta_pass), float(beta_stage)
+    return np.array([[np.float32(s0 * bp ** i * bs ** (H - 1 - h)) for h in range(H)] for i in range(int(iters))], dtype=np.float32)
+
+
+def check_dial(iters=4, *, beta_pass=0.5, beta_stage=0.9, temp=0.1, gamma_sigma=0.0, sample_sigma=0.5, materialize_eps=False,
+               noise_stream="philox", what="the annealed MPPI controller"):
+    """The keywords of the annealed MPPI controllers (DialController, BatchedDialController, get_controller(env, "dial", ...),
+    eval_env_batched(controller="dial")) -> the Anneal record SamplingCore attaches, or None for the neutral element
+    (beta_pass = beta_stage = 1 with temp=None: nothing is attached, the controller is MPPIController(iters=k) launch for launch).  The
+    C side's counterpart is covo_set_step_anneal's block of check_step_attachments (csrc/capi.hip).
+
+    One control step is iters passes of MPPI's sample-rollout-update on its one state (the key walk of iters=).  Pass i draws
+    a = clip(mu_i + sigma[i][h] eps) from the schedule of anneal_schedule (control_params.a_cov on input is ignored; on output it is
+    the last pass's blocks sigma[k-1][h]^2 I); with temp given the pass's temperature is temp x the population standard deviation of
+    its finite costs (csrc/cost_standardise.hip), the configured lam when that is no temperature: info["anneal_sigma"] [k, 32] /
+    ["anneal_rows"] [k, 4] / ["anneal_lam"] [k] / ["anneal_std"] [k] / ["anneal_fallback"] [k] bool, and with temp given
+    info["lam_eff"], the last pass's.
+
+    The objections, in a fixed order (ValueError naming the keyword): iters anything but an integer in [1, COVO_MAX_STEP_ITERS];
+    beta_pass, then beta_stage, anything but a real number in (0, 1]; temp anything but None or a finite real number > 0;
+    gamma_sigma != 0 -- the schedule owns a_cov; then materialize_eps / noise_stream="jax" (NotImplementedError): the kernel-by-kernel
+    path knows no schedule."""
+    import math
+    import numbers
+    k = _lib.check_iters(iters)
+    for name, v in (("beta_pass", beta_pass), ("beta_stage", beta_stage)):
+        if isinstance(v, bool) or not isinstance(v, numbers.Real) or math.isnan(float(v)) or not 0.0 < float(v) <= 1.0:
+            raise ValueError(f"{name}={v!r} outside (0, 1] (the factor of the noise scale per "
+                             f"{'pass' if name == 'beta_pass' else 'stage towards the front of the horizon'}, a real number; 1 = none)")
+    if temp is not None and (isinstance(temp, bool) or not isinstance(temp, numbers.Real) or not math.isfinite(float(temp)) or
+                             not float(temp) > 0.0):
+        raise ValueError(f"temp={temp!r} (None, or a finite real number > 0: the pass's temperature in units of the standard deviation "
+                         "of its costs)")
+    if float(gamma_sigma) != 0.0:
+        raise ValueError(f"gamma_sigma={gamma_sigma} with {what}: the schedule owns a_cov, MPPI's covariance adaptation would adapt "
+                         "what the next pass overwrites; give gamma_sigma=0")
+    if materialize_eps or noise_stream != "philox":
+        raise NotImplementedError(f"{what} acts in the fused step (covo_mpc_step); the kernel-by-kernel path (materialize_eps / "
+                                  "noise_stream='jax') knows no schedule and updates at the configured lam")
+    if float(beta_pass) == 1.0 and float(beta_stage) == 1.0 and temp is None:
+        return None
+    return Anneal(sigma=anneal_schedule(sample_sigma, k, beta_pass, beta_stage), temp=0.0 if temp is None else float(temp),
+                  beta_pass=float(beta_pass), beta_stage=float(beta_stage))

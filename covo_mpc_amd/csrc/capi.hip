@@ -179,6 +179,7 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->diag_scratch));
     DESTROY(hipFree(h->ws_blockmin));
     DESTROY(hipFree(h->lam_own));
+    DESTROY(hipFree(h->anneal_table));
     DESTROY(hipFree(h->elite_own));
     DESTROY(hipFree(h->ws_stats));
     DESTROY(hipFree(h->ws_sigma));
@@ -802,6 +803,60 @@ int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32
     return launch_ess_lambda(cost, n_samples, n_inst, nullptr, lam0, ess_min, out, (hipStream_t)stream);
 }
 
+// ---- the annealed step (cost_standardise.hip).  The captured step graphs bake in the schedule launches, the solver's launch, temp and
+// where the rows go, and read the table in the handle's own device memory: any change bumps the epoch, and the table is rewritten only
+// after every launch that may still read it has finished.  What the step needs next to it is checked at the step (check_step_attachments)
+int covo_set_step_anneal(covo_handle_t h, const float *sigma_table, int32_t n_pass, float temp, float *rows_out, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_anneal: null handle");
+    REQUIRE(temp >= 0.0f && temp < __builtin_inff(), "covo_set_step_anneal: temp=%g is not a finite number >= 0 (0 = the configured lam)",
+            (double)temp);
+    const bool off = sigma_table == nullptr && temp == 0.0f;
+    REQUIRE(off || (n_pass >= 1 && n_pass <= COVO_MAX_STEP_ITERS), "covo_set_step_anneal: n_pass=%d outside [1, %d]", n_pass,
+            COVO_MAX_STEP_ITERS);
+    REQUIRE(off || rows_out == nullptr || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_anneal: n_inst=%d outside (0, %d]",
+            n_inst, COVO_MAX_ENVS);
+    if (sigma_table != nullptr)
+        for (int i = 0; i < n_pass * COVO_H; ++i)
+            REQUIRE(sigma_table[i] > 0.0f && sigma_table[i] < __builtin_inff(), "covo_set_step_anneal: sigma_table[%d][%d]=%g is not a "
+                    "finite number > 0", i / COVO_H, i % COVO_H, (double)sigma_table[i]);
+    if (off) {
+        if (covo_anneal_on(h)) ++h->opt.epoch;
+        h->anneal_passes = h->anneal_sched = 0;
+        h->anneal_temp = 0.0f;
+        h->anneal_rows = nullptr;
+        h->anneal_n = 0;
+        if (covo_lam_target(h) == nullptr) covo_eprow_drop(h, COVO_EPLOG_LAM);  // no temperature row any more: the log goes
+        return 0;
+    }
+    CHECK_DEVICE(h, "covo_set_step_anneal");
+    if (sigma_table != nullptr) {
+        COVO_CHECK_HIP(hipDeviceSynchronize());  // (a setter, off the per-step path) no step in flight reads the old table
+        if (h->anneal_table == nullptr)
+            COVO_CHECK_HIP(hipMalloc(&h->anneal_table, (size_t)COVO_MAX_STEP_ITERS * COVO_H * sizeof(float)));
+        COVO_CHECK_HIP(hipMemcpy(h->anneal_table, sigma_table, (size_t)n_pass * COVO_H * sizeof(float), hipMemcpyHostToDevice));
+    }
+    ++h->opt.epoch;
+    h->anneal_passes = n_pass;
+    h->anneal_sched = sigma_table != nullptr ? 1 : 0;
+    h->anneal_temp = temp;
+    h->anneal_rows = rows_out;
+    h->anneal_n = rows_out ? n_inst : 0;
+    if (covo_lam_target(h) == nullptr) covo_eprow_drop(h, COVO_EPLOG_LAM);
+    return 0;
+}
+
+int covo_cost_standardise(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, float lam0, float temp, float *out,
+                          void *stream)
+{
+    REQUIRE(h, "covo_cost_standardise: null handle");
+    CHECK_DEVICE(h, "covo_cost_standardise");
+    REQUIRE(cost && out && n_samples > 0 && n_inst > 0 && n_inst <= 65535, "covo_cost_standardise: bad argument");
+    REQUIRE(lam0 > 0.0f && lam0 < __builtin_inff(), "covo_cost_standardise: lam0=%g", (double)lam0);
+    REQUIRE(temp > 0.0f && temp < __builtin_inff(), "covo_cost_standardise: temp=%g is not a finite number > 0", (double)temp);
+    return launch_cost_standardise(cost, n_samples, n_inst, lam0, temp, out, nullptr, 0, (hipStream_t)stream);
+}
+
 // ---- the elite-set update (elite_select.hip, reduce_elite.hip).  The captured step graphs bake in the staged launch set, K and where
 // the selector writes: any change bumps the epoch.  The valid range of K depends on the step's sample count: checked at the step
 // (check_step_attachments)
@@ -1089,7 +1144,7 @@ int covo_set_episode_rows(covo_handle_t h, int32_t kind, float *log, int32_t str
 // (partial_out != NULL) cannot have at all, in the order above; then, in the same order, each attachment's own ranges and the rows
 // of its buffer.  A new attachment adds its lines here (and its log to covo_eplog_kinds, covo_common.hpp), nowhere else.
 static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, int mode, const float *a_cov,
-                                  const covo_env_params *params, const char *what)
+                                  const covo_env_params *params, const char *what, float gamma_sigma = 0.0f, bool fused_batch = false)
 {
     if (sharded) {
         REQUIRE(covo_diag_target(h) == nullptr,
@@ -1104,7 +1159,7 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
         REQUIRE(!covo_arb_on(h),
                 "%s: the update arbiter (covo_set_step_arbiter) is not available for sample-sharded steps (partial_out != NULL): "
                 "a rank's action and cost buffers hold its shard only; detach it", what);
-        REQUIRE(covo_lam_target(h) == nullptr,
+        REQUIRE(!covo_ess_on(h),
                 "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for sample-sharded steps (partial_out != NULL): "
                 "a rank sees only its shard's costs; turn it off (ess_min = 0)", what, (double)h->ess_min);
         REQUIRE(covo_step_iters(h) == 1,
@@ -1143,14 +1198,14 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
     }
     REQUIRE(!covo_arb_on(h) || n_inst <= h->arb_n, "%s: %d instances, the arbiter buffer (covo_set_step_arbiter) has n_inst=%d", what,
             n_inst, h->arb_n);
-    if (covo_lam_target(h) != nullptr) {  // ess_min in the range the solver's bracket covers
+    if (covo_ess_on(h)) {  // ess_min in the range the solver's bracket covers
         REQUIRE(h->ess_min >= 1.0f && h->ess_min <= 0.5f * (float)n_samples,
                 "%s: ess_min=%g (covo_set_step_ess_floor) outside [1, n_samples / 2 = %g]", what, (double)h->ess_min, 0.5 * n_samples);
         REQUIRE(n_inst <= covo_lam_capacity(h), "%s: %d instances, the temperature buffer (covo_set_step_ess_floor) has %d rows", what,
                 n_inst, covo_lam_capacity(h));
     }
     if (covo_elite_target(h) != nullptr) {
-        REQUIRE(covo_lam_target(h) == nullptr,
+        REQUIRE(!covo_ess_on(h),
                 "%s: the elite-set update (covo_set_step_elite, K=%d) together with the ESS floor (covo_set_step_ess_floor, ess_min=%g): "
                 "both define the update's weights; turn one of them off", what, h->elite_K, (double)h->ess_min);
         REQUIRE(h->elite_K >= 1 && h->elite_K <= n_samples, "%s: K=%d (covo_set_step_elite) outside [1, n_samples = %d]", what,
@@ -1239,6 +1294,35 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                     params[e].disturb_kind, e);
         REQUIRE(n_inst <= h->hold_n, "%s: %d instances, the hold rows (covo_set_step_plan_hold) have n_inst=%d", what, n_inst, h->hold_n);
     }
+    if (covo_anneal_on(h)) {  // the annealed step: MPPI's block-diagonal draw under a per-pass table, weights on standardised costs
+        REQUIRE(mode == COVO_MODE_MPPI,
+                "%s: the annealed step (covo_set_step_anneal) belongs to MPPI steps (COVO_MODE_MPPI): its schedule writes the 4 x 4 block "
+                "factors only that mode samples from; this step's mode is %d; turn it off (a null table and temp = 0)", what, mode);
+        REQUIRE(h->anneal_passes == covo_step_iters(h),
+                "%s: the annealed step (covo_set_step_anneal) was set for n_pass=%d passes, this step runs iters=%d "
+                "(covo_set_step_iters): the table has one row per pass; set both to the same count", what, h->anneal_passes,
+                covo_step_iters(h));
+        REQUIRE(gamma_sigma == 0.0f,
+                "%s: the annealed step (covo_set_step_anneal) together with gamma_sigma=%g: the schedule owns a_cov, MPPI's covariance "
+                "adaptation would adapt what the next pass overwrites; set gamma_sigma = 0", what, (double)gamma_sigma);
+        REQUIRE(!covo_anneal_temp_on(h) || !covo_ess_on(h),
+                "%s: the annealed step's standardised temperature (covo_set_step_anneal, temp=%g) together with the ESS floor "
+                "(covo_set_step_ess_floor, ess_min=%g): both define the update's weights; turn one of them off", what,
+                (double)h->anneal_temp, (double)h->ess_min);
+        REQUIRE(!covo_anneal_temp_on(h) || covo_elite_target(h) == nullptr,
+                "%s: the annealed step's standardised temperature (covo_set_step_anneal, temp=%g) together with the elite-set update "
+                "(covo_set_step_elite, K=%d): both define the update's weights; turn one of them off", what, (double)h->anneal_temp,
+                h->elite_K);
+        REQUIRE(!sharded,
+                "%s: the annealed step (covo_set_step_anneal) is not available for sample-sharded steps (partial_out != NULL): a rank "
+                "sees only its shard's costs; turn it off (a null table and temp = 0)", what);
+        REQUIRE(!fused_batch,
+                "%s: the annealed step (covo_set_step_anneal) is not available for the env-batched step's one fused launch, which "
+                "shifts and factors a_cov itself and needs the temperature before all costs exist; run the staged batch "
+                "(covo_set_step_batched_staged)", what);
+        REQUIRE(h->anneal_rows == nullptr || n_inst <= h->anneal_n,
+                "%s: %d instances, the per-pass rows (covo_set_step_anneal) have n_inst=%d", what, n_inst, h->anneal_n);
+    }
     return 0;
 }
 
@@ -1265,7 +1349,7 @@ static int check_ilqr_step(const covo_ctx *h, int n_inst, bool sharded, int deri
     REQUIRE(!covo_arb_on(h),
             "%s: an iLQR step (COVO_MODE_ILQR) together with the update arbiter (covo_set_step_arbiter): there is no softmax mean and "
             "no best sample to arbitrate; detach it", what);
-    REQUIRE(covo_lam_target(h) == nullptr,
+    REQUIRE(!covo_ess_on(h),
             "%s: an iLQR step (COVO_MODE_ILQR) together with the ESS floor (covo_set_step_ess_floor, ess_min=%g): there are no "
             "weights; turn it off (ess_min = 0)", what, (double)h->ess_min);
     REQUIRE(covo_elite_target(h) == nullptr,
@@ -1850,7 +1934,8 @@ static int check_single_step(const covo_ctx *h, const covo_env_params *params, c
             "%s: a_mean, a_mean_in and a_cov must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
     if (args->mode == COVO_MODE_ILQR)
         if (int rc = check_ilqr_step(h, 1, args->partial_out != nullptr, args->derive_keys, what)) return rc;
-    return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, params, what);
+    return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, params, what,
+                                  args->gamma_sigma);
 }
 
 int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_step_args *args, float *state_true,
@@ -1986,7 +2071,7 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
     // covo_set_step_batched_staged: the MPPI / covo-offline batch runs its staged launch sequence, which takes what the fused launch
     // refuses below and has its own short list further down
     const bool staged = mode != COVO_MODE_COVO_ONLINE && covo_batched_staged(h);
-    REQUIRE(mode == COVO_MODE_COVO_ONLINE || staged || covo_lam_target(h) == nullptr,
+    REQUIRE(mode == COVO_MODE_COVO_ONLINE || staged || !covo_ess_on(h),
             "%s: the ESS floor (covo_set_step_ess_floor, ess_min=%g) is not available for the env-batched MPPI / covo-offline step: its "
             "one fused launch needs the temperature before all costs exist, and there is no staged batched fallback; turn it off "
             "(ess_min = 0)", what, (double)h->ess_min);
@@ -2007,7 +2092,8 @@ static int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo
             "staged: those batches carry no per-instance Hessian constants; detach it", what);
     REQUIRE(h->plan_hold <= 1 || ((uintptr_t)args->a_mean & 15) == 0,
             "%s: a_mean must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
-    if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, params, what))) return rc;  // (batched steps derive their keys)
+    if ((rc = check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, params, what, norm->gamma_sigma,
+                                     mode != COVO_MODE_COVO_ONLINE && !staged))) return rc;  // (batched steps derive their keys)
     if (mode == COVO_MODE_COVO_ONLINE) return 0;
     REQUIRE(mode != COVO_MODE_MPPI || args->a_cov != nullptr, "%s: MPPI needs base.a_cov (float[n_envs][H][4][4])", what);
     REQUIRE(mode != COVO_MODE_COVO_OFFLINE || (m->L_table != nullptr && m->n_table > 0 && m->L_table_stride >= 0),

@@ -69,6 +69,13 @@ struct covo_ctx {
     float *lam_out;           // caller's [lam_n][COVO_LAM_FLOATS]: instance e's solver row of every step; null: lam_own
     int lam_n;
     float *lam_own;           // [COVO_MAX_ENVS][COVO_LAM_FLOATS]
+    // the annealed step (covo_set_step_anneal; cost_standardise.hip); anneal_passes == 0: off
+    float *anneal_table;      // [COVO_MAX_STEP_ITERS][H] the handle's own: sigma[i][h] of pass i, stage h (uploaded by the setter)
+    int anneal_passes;        // the passes the attachment was set for: the step's iters must equal it
+    int anneal_sched;         // a table was given: every pass's schedule launch writes its row into the block factors and a_cov
+    float anneal_temp;        // > 0: every pass's temperature is temp x the standard deviation of its finite costs; 0: the configured lam
+    float *anneal_rows;       // caller's [anneal_n][anneal_passes][COVO_LAM_FLOATS]: instance e's solver row of every pass, or null
+    int anneal_n;
     // the elite-set update (covo_set_step_elite; elite_select.hip, reduce_elite.hip); elite_K == 0: off
     int elite_K;              // elites per instance and pass
     float *elite_out;         // caller's [elite_n][COVO_ELITE_FLOATS]: instance e's selector row of every step; null: elite_own
@@ -201,12 +208,22 @@ static inline void covo_plan_step_done(covo_ctx *h, int age, int n_inst)
 static inline int covo_step_iters(const covo_ctx *h) { return (h->iter_log != nullptr && h->iters > 1) ? h->iters : 1; }
 static inline float *covo_iter_slot(const covo_ctx *h, int pass) { return covo_step_iters(h) > 1 ? h->iter_log + pass : nullptr; }
 // where the solver of this handle's steps writes the instances' temperatures (null: no floor) and for how many instances
-static inline float *covo_lam_target(const covo_ctx *h) { return h->ess_min > 0.0f ? (h->lam_out ? h->lam_out : h->lam_own) : nullptr; }
-static inline int covo_lam_capacity(const covo_ctx *h) { return h->lam_out ? h->lam_n : COVO_MAX_ENVS; }
+// (the ESS floor, or the annealed step's standardised temperature, whose last pass's row is the handle's own temperature row)
+static inline bool covo_ess_on(const covo_ctx *h) { return h->ess_min > 0.0f; }
+static inline bool covo_anneal_on(const covo_ctx *h) { return h->anneal_passes > 0; }
+static inline bool covo_anneal_sched_on(const covo_ctx *h) { return h->anneal_passes > 0 && h->anneal_sched != 0; }
+static inline bool covo_anneal_temp_on(const covo_ctx *h) { return h->anneal_passes > 0 && h->anneal_temp > 0.0f; }
+static inline float *covo_lam_target(const covo_ctx *h)
+{
+    if (covo_ess_on(h)) return h->lam_out ? h->lam_out : h->lam_own;
+    return covo_anneal_temp_on(h) ? h->lam_own : nullptr;
+}
+static inline int covo_lam_capacity(const covo_ctx *h) { return (covo_ess_on(h) && h->lam_out) ? h->lam_n : COVO_MAX_ENVS; }
 // where the selector of this handle's steps writes the instances' rows (null: no elite-set update) and for how many instances
 static inline float *covo_elite_target(const covo_ctx *h) { return h->elite_K > 0 ? (h->elite_out ? h->elite_out : h->elite_own) : nullptr; }
 static inline int covo_elite_capacity(const covo_ctx *h) { return h->elite_out ? h->elite_n : COVO_MAX_ENVS; }
-// a step whose update waits for all costs (ESS floor, elite set): rollout without in-launch records, no one-launch small step
+// a step whose update waits for all costs (ESS floor, standardised temperature, elite set): rollout without in-launch records, no
+// one-launch small step
 static inline bool covo_update_staged(const covo_ctx *h) { return covo_lam_target(h) != nullptr || covo_elite_target(h) != nullptr; }
 static inline bool covo_plan_on(const covo_ctx *h) { return h->plan_out != nullptr || h->eplog[COVO_EPLOG_TRACE].log != nullptr; }
 static inline bool covo_fan_on(const covo_ctx *h) { return h->fan_out != nullptr || h->eplog[COVO_EPLOG_FAN].log != nullptr; }
@@ -492,6 +509,13 @@ struct UpdateDesc {
 // the ESS floor's solver (ess_lambda.hip): out [n_inst][COVO_LAM_FLOATS] from cost [n_inst][N]; groupmin [n_inst][ceil(N/64)] as the
 // rollout leaves it, or null (the minimum is then formed from the costs)
 int launch_ess_lambda(const float *cost, int N, int n_inst, const float *groupmin, float lam0, float ess_min, float *out, hipStream_t s);
+// the annealed step's launches (cost_standardise.hip).  The standardising solver: out [n_inst][COVO_LAM_FLOATS] from cost [n_inst][N] --
+// {lam_eff, 1 / lam_eff, std, bits(|F| | fallback << 31)} with lam_eff = temp x the population standard deviation of the finite costs
+// (lam0 on fallback); pass_out: instance e's row again at pass_out + e * pass_stride, or null.  The schedule launch: row `pass` of
+// table [.][H] -> Ls [n_inst][H][4][4] = sigma I and a_cov [n_inst][H][4][4] = sigma^2 I
+int launch_cost_standardise(const float *cost, int N, int n_inst, float lam0, float temp, float *out, float *pass_out, int pass_stride,
+                            hipStream_t s);
+int launch_anneal_schedule(const float *table, int pass, float *Ls, float *a_cov, int n_inst, hipStream_t s);
 int launch_softmax_reduce(covo_ctx *h, const UpdateDesc &d, hipStream_t s);
 // reduce_lam.hip: what the two launch functions do with d.lam_rows set
 int launch_softmax_reduce_lam(covo_ctx *h, const UpdateDesc &d, hipStream_t s);

@@ -320,12 +320,14 @@ static RolloutDesc rollout_desc(const covo_ctx *h, const BatchInst &i, int T, in
 struct StepUpdate {
     UpdateDesc up;
     bool records;
+    int pass;  // of an iterated step: the annealed step's solver files its row under it
 };
 static StepUpdate update_desc(const covo_ctx *h, const BatchInst &i, int N, int G, bool cov_adapt, const float *partials,
-                              const float *a_mean_old, float gamma_mean, float *diag_rec, float *diag_out, float *iter_out)
+                              const float *a_mean_old, float gamma_mean, float *diag_rec, float *diag_out, float *iter_out, int pass)
 {
     StepUpdate u;
     u.records = rollout_leaves_records(h, G, cov_adapt);
+    u.pass = pass;
     u.up.cost = i.cost;
     u.up.a = i.a;
     u.up.N = N;
@@ -341,8 +343,9 @@ static StepUpdate update_desc(const covo_ctx *h, const BatchInst &i, int N, int 
     return u;
 }
 
-// adds the targets of the staged updates and runs: the ESS floor's solver (rollout costs + per-wave minima -> 1 / lam_eff in lam_rows)
-// or the elite selector (costs -> 0/1 weights off elite_rows) when attached -- never both (refused at the C boundary) --, then the ONE
+// adds the targets of the staged updates and runs: the ESS floor's solver (rollout costs + per-wave minima -> 1 / lam_eff in lam_rows),
+// in its place the annealed step's standardising solver (costs -> the same row, and again under the pass in the per-pass rows), or the
+// elite selector (costs -> 0/1 weights off elite_rows) when attached -- never two of them (refused at the C boundary) --, then the ONE
 // update launch set
 static int enqueue_update(covo_ctx *h, StepUpdate &u, hipStream_t s)
 {
@@ -352,7 +355,12 @@ static int enqueue_update(covo_ctx *h, StepUpdate &u, hipStream_t s)
     up.n_blockmin = (up.N + 63) / 64;
     up.lam_rows = lam_rows;
     up.elite_rows = elite_rows;
-    if (lam_rows != nullptr && (rc = launch_ess_lambda(up.cost, up.N, up.batch, up.blockmin, h->cfg.lam, h->ess_min, lam_rows, s))) return rc;
+    if (lam_rows != nullptr && covo_ess_on(h) &&
+        (rc = launch_ess_lambda(up.cost, up.N, up.batch, up.blockmin, h->cfg.lam, h->ess_min, lam_rows, s))) return rc;
+    if (lam_rows != nullptr && !covo_ess_on(h) &&
+        (rc = launch_cost_standardise(up.cost, up.N, up.batch, h->cfg.lam, h->anneal_temp, lam_rows,
+                                      h->anneal_rows ? h->anneal_rows + (size_t)u.pass * COVO_LAM_FLOATS : nullptr,
+                                      h->anneal_passes * COVO_LAM_FLOATS, s))) return rc;
     if (elite_rows != nullptr && (rc = launch_elite_select(up.cost, up.N, up.batch, h->elite_K, elite_rows, s))) return rc;
     if (up.gamma_sigma != 0.0f) return elite_rows != nullptr ? launch_elite_update_cov(h, up, s) : launch_softmax_update_cov(h, up, s);
     if (elite_rows != nullptr) return launch_elite_reduce(h, up, s);
@@ -421,6 +429,8 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
             if ((M & 8) && (rc = launch_noise_gemm(nd, s))) return rc;
         } else {  // MPPI: shift a_cov, factor the 4x4 blocks, per-step draws (mppi.py:43-66)
             nd.L = st->Ls;  // (a_cov was shifted and factored there by the begin launch)
+            // covo_set_step_anneal: this pass's row of the schedule replaces both -- a_cov on input is ignored
+            if (covo_anneal_sched_on(h) && (rc = launch_anneal_schedule(h->anneal_table, pass, st->Ls, a.a_cov, 1, s))) return rc;
             if ((rc = launch_noise_blockdiag(nd, s))) return rc;
         }
     }
@@ -440,7 +450,7 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     if (!(M & 32)) return 0;
     // weights + update: finish locally (blend with am_shift, diagnostics), or -- a sample-sharded rank -- leave this shard's
     // record for the all-gather (covo.py:266-275)
-    StepUpdate u = update_desc(h, inst, N, G, cov_adapt, h->ws_partials, am_shift, a.gamma_mean, h->ws_diag_rec, dg, iter_out);
+    StepUpdate u = update_desc(h, inst, N, G, cov_adapt, h->ws_partials, am_shift, a.gamma_mean, h->ws_diag_rec, dg, iter_out, pass);
     const bool sharded = a.partial_out != nullptr;
     if (sharded) {
         u.up.partial_out = a.partial_out;
@@ -884,7 +894,7 @@ void batch_state_destroy(covo_ctx *h)
 static StepUpdate batch_update_desc(const covo_ctx *h, const BatchCommon &c, const covo_batch_args &a, int pass, bool cov_adapt)
 {
     StepUpdate u = update_desc(h, batch_inst(a, 0), a.n_samples, rollout_workgroups(a.n_samples, false, a.n_envs), cov_adapt, c.partials,
-                               c.a_mean_shift, a.gamma_mean, c.diag_rec, covo_diag_target(h), covo_iter_slot(h, pass));
+                               c.a_mean_shift, a.gamma_mean, c.diag_rec, covo_diag_target(h), covo_iter_slot(h, pass), pass);
     u.up.partials_ws = c.partials;
     u.up.batch = a.n_envs;
     u.up.iter_stride = covo_step_iters(h);
@@ -1207,6 +1217,8 @@ static int batch_staged_enqueue(covo_ctx *h, BatchState *b, const covo_batch_mod
     nd.propagate_nan = covo_propagate_nan(h);
     if (mppi) {
         nd.L = x.Ls;
+        // covo_set_step_anneal: this pass's row of the schedule into every instance's factors and a_cov, as in the single step
+        if (covo_anneal_sched_on(h) && (rc = launch_anneal_schedule(h->anneal_table, pass, x.Ls, a.a_cov, E, s))) return rc;
         if ((rc = launch_noise_blockdiag(nd, s))) return rc;
     } else {
         nd.L = m.L_table;

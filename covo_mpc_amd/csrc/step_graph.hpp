@@ -104,10 +104,11 @@ enum StepForm {
     STEP_FOLDED_ONLINE,  // covo-online: the begin work rides in the Hessian's first launch (COVO_FOLD_BEGIN=0: off)
     STEP_BEGIN_PASSES,   // the begin launch, then the passes (graph or eager)
 };
-// covo-offline / MPPI: noise -> rollout -> records -> merge fit ONE launch (a staged update -- ESS floor, elite set -- does not)
+// covo-offline / MPPI: noise -> rollout -> records -> merge fit ONE launch (a staged update -- ESS floor, standardised temperature, elite
+// set -- does not; nor does a step under the annealed schedule: that launch shifts and factors a_cov itself)
 static inline bool step_takes_small(const covo_ctx *h, const covo_env_params &p, const covo_step_args &a)
 {
-    return h->opt.fuse_small && step_small_eligible(h, p, a) && !covo_update_staged(h);
+    return h->opt.fuse_small && step_small_eligible(h, p, a) && !covo_update_staged(h) && !covo_anneal_sched_on(h);
 }
 // small: step_takes_small; reuse: a reuse step of a Sigma period has no Hessian launch to fold into; per-step force tables: their launch precedes the Hessian
 // and reads the scalars the begin launch leaves

@@ -20,7 +20,7 @@ import numpy as np
 
 from .. import controllers
 from .. import random as crandom
-from ..controllers._options import (STEP_OPTION_DEFAULTS, STEP_SWITCH_DEFAULTS, check_ilqr, check_step_options, check_step_switches,
+from ..controllers._options import (STEP_OPTION_DEFAULTS, STEP_SWITCH_DEFAULTS, check_dial, check_ilqr, check_step_options, check_step_switches,
                                     take, take_switches)
 from ..dynamics import utils
 from ..dynamics.dataclass import Action3D, DeviceState, EnvParams3D, EnvState3D
@@ -594,7 +594,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                      verbose: bool = True, diag: bool = False, trace: bool = False, fan=None, update: str = "softmax",
                      arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0,
                      rows: bool = False, staged: bool = False, controller: str = "covo-online", refine: bool = False,
-                     riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False):
+                     riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False,
+                     beta_pass: float = 0.5, beta_stage: float = 0.9, temp=0.1):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     `controller` (covo-online by default), controller and env on the device, ONE host sync.  -> mean position error per instance
@@ -615,16 +616,23 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     Riccati sweep's direction; riccati_feedback=True on top of it: the closed-loop candidates under the sweep's gains compete in that
     line search (check_riccati_feedback).  plan_hold=m > 1 on top of riccati: every m-th step plans, the others apply the sweep's law to
     the measured state (check_plan_hold); rows=True then also holds "hold": ep.read_hold().  riccati_box=True on top of riccati (implied
-    by "ilqr"): every sweep solves the control-limited stage problem (check_riccati_box)."""
-    if controller not in ("covo-online", "mppi", "covo-offline", "ilqr"):
-        raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline' or 'ilqr'")
+    by "ilqr"): every sweep solves the control-limited stage problem (check_riccati_box).  controller="dial": BatchedDialController
+    (annealed MPPI, always staged) under iters / beta_pass / beta_stage / temp (check_dial; the other controllers ignore the last three);
+    rows=True then also holds "lam": ep.read_lam(), the last pass's solver rows, when temp is given."""
+    if controller not in ("covo-online", "mppi", "covo-offline", "ilqr", "dial"):
+        raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline', 'ilqr' or 'dial'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
     switches = take_switches(locals())
     if controller == "ilqr":
         return _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, switches,
                                   opts)
+    dial = controller == "dial"
+    if dial:
+        dial_opts = _check_dial_keywords({**opts, "ess_min": None, "compute_post_cov": False}, switches, None, beta_pass, beta_stage, temp)
+        if staged:
+            raise ValueError("staged=True with controller='dial': the annealed batch is always staged")
     online, batch = controller == "covo-online", f"the env-batched {controller} controller"
-    check_step_options(None, "online" if online else controller, **opts)  # ValueError before anything is built
+    check_step_options(None, "online" if online else ("MPPI" if dial else controller), **opts)  # ValueError before anything is built
     check_step_switches(batch, mode_what="online" if online else controller, riccati_what="online" if online else batch,
                         sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), **switches)
     if arbiter and update == "softmax":
@@ -634,10 +642,14 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     ks = crandom.split(rng, 3 * n_envs + 1)
     params = [env.sample_params(ks[e]) for e in range(n_envs)]
     N, H, lam = (lambda p: (int(p[0][1:]), int(p[1][1:]), float(p[2][3:])))(controller_params.split("_"))
-    c0, cp0 = get_controller(env, controller, controller_params, device=device, compute_info=False)
+    c0, cp0 = get_controller(env, "mppi" if dial else controller, controller_params, device=device, compute_info=False)
     cp0 = c0.init_control_params
     kw = dict(discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean, device=c0.core.device, staged=staged, **opts)
-    if controller == "mppi":  # (it takes no switch: check_riccati has refused riccati, which the others need, for the two baselines)
+    if dial:
+        b = controllers.BatchedDialController(env, n_envs, N, H, lam, sigmas=cp0.sample_sigma, beta_pass=beta_pass, beta_stage=beta_stage,
+                                              temp=temp, discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean,
+                                              device=c0.core.device, **dial_opts)
+    elif controller == "mppi":  # (it takes no switch: check_riccati has refused riccati, which the others need, for the two baselines)
         b = controllers.BatchedMPPIController(env, n_envs, N, H, lam, sigmas=cp0.sample_sigma, **kw)
     else:
         b = controllers.BatchedCoVOController(env, n_envs, N, H, lam, sample_sigma=cp0.sample_sigma,
@@ -666,8 +678,30 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
         reads = {"elite": ("elitelog", ep.read_elite), "iters": ("iterlog", ep.read_iters), "sigma": ("sigmalog", ep.read_sigma),
                  "post": ("postlog", ep.read_post)}
         reads["hold"] = ("holdlog", ep.read_hold)
+        if dial:
+            reads["lam"] = ("lamlog", ep.read_lam)
         out += ({name: read() for name, (attr, read) in reads.items() if getattr(ep, attr) is not None},)
     return out if len(out) > 1 else out[0]
+
+
+def _check_dial_keywords(opts, switches, process_group, beta_pass, beta_stage, temp):
+    """check_dial on the keywords get_controller and eval_env_batched carry -> the step options DialController / BatchedDialController
+    take.  The objections, in a fixed order: check_dial's own; then ValueError for ess_min, elite, sigma_period, sigma_adapt, a step
+    switch or a process_group away from its default, naming it."""
+    check_dial(opts["iters"], beta_pass=beta_pass, beta_stage=beta_stage, temp=temp)
+    for name in ("ess_min", "elite", "sigma_period", "sigma_adapt"):
+        v, default = opts[name], STEP_OPTION_DEFAULTS[name]
+        if not ((not v) if default is None else v == default):
+            raise ValueError(f"{name}={v!r} with the annealed MPPI controller: it defines its own weights and noise scale; leave it at "
+                             "its default")
+    for name, default in STEP_SWITCH_DEFAULTS.items():
+        if switches[name] != default:
+            raise ValueError(f"{name}={switches[name]!r} with the annealed MPPI controller: it takes no step switch; leave it at its "
+                             "default")
+    if process_group is not None:
+        raise ValueError("process_group with the annealed MPPI controller: a sample-sharded rank sees only its shard's costs; run it on "
+                         "one rank")
+    return {o: opts[o] for o in ("compute_diag", "compute_plan", "compute_fan", "update", "iters", "compute_post_cov")}
 
 
 def _check_ilqr_switches(env, switches, opts, process_group=None):
@@ -809,7 +843,7 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
                    iters=1, elite=None, sigma_period=1, compute_post_cov=False, sigma_adapt=0.0, refine=False,
-                   riccati=False, riccati_feedback=False, plan_hold=1, riccati_box=False):
+                   riccati=False, riccati_feedback=False, plan_hold=1, riccati_box=False, beta_pass=0.5, beta_stage=0.9, temp=0.1):
     """quadrotor.py:670-752.  compute_diag, compute_plan, ess_min, compute_fan, update, iters, elite, sigma_period, compute_post_cov and
     sigma_adapt are the sampling controllers' step options -- what each does and what it adds to the controller's info dict:
     controllers/_options.py.  refine (covo-online only): the Newton line search behind every step -- a switch, not a step option
@@ -822,10 +856,16 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     controller_name "ilqr": the sampling-free controller (controllers/ilqr.py; controllers/_options.py: check_ilqr) -- H is taken from
     controller_params, N and lam are ignored; iters, plan_hold and compute_plan pass through, riccati is implied, riccati_feedback=True
     asks for the closed-loop candidates and False (this signature's default) leaves the choice to the plant (ILQRController's None);
-    every other step option away from its default is a ValueError."""
+    every other step option away from its default is a ValueError.
+    controller_name "dial": the annealed MPPI controller (controllers/dial.py; controllers/_options.py: check_dial) -- MPPI's control
+    parameters; iters, beta_pass, beta_stage and temp are its own keywords (every other controller name ignores the last three at
+    their defaults), compute_diag / compute_plan / compute_fan / update / compute_post_cov pass through; ess_min, elite, sigma_period,
+    sigma_adapt, a switch or a process_group away from the default is a ValueError."""
     opts, switches = take(locals()), take_switches(locals())
     if controller_name == "ilqr":  # ValueError / NotImplementedError before anything is built
         k, feedback, m = _check_ilqr_switches(env, switches, opts, process_group=process_group)
+    if controller_name == "dial":
+        dial_opts = _check_dial_keywords(opts, switches, process_group, beta_pass, beta_stage, temp)
     import torch
     if controller_name == "ilqr":
         H = int(controller_params.split("_")[1][1:]) if controller_params else 32
@@ -839,6 +879,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                    compute_plan=compute_plan, device=device), control_params
     # ValueError before anything is built; the controller's own check, with N, follows
     what = "online" if ("covo" in controller_name and "offline" not in controller_name) else controller_name
+    what = "MPPI" if controller_name == "dial" else what
     check_step_options(None, what, **opts)
     check_step_switches(what, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), **switches)
 
@@ -868,6 +909,14 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
         return controllers.MPPIController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           process_group=process_group, compute_info=compute_info,  # (MPPI has no refine: refused above)
                                           **{s: v for s, v in switches.items() if s != "refine"}, **opts), control_params
+    if controller_name == "dial":
+        N, H, lam, sigma = parse_sample_params(controller_params)
+        a_cov = (torch.eye(env.action_dim, dtype=torch.float32, device=device) * sigma ** 2).repeat(H, 1, 1)
+        control_params = controllers.MPPIParams(gamma_mean=1.0, gamma_sigma=0.0, discount=1.0, sample_sigma=sigma,
+                                                a_mean=get_sample_mean(H), a_cov=a_cov)
+        return controllers.DialController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
+                                          compute_info=compute_info, beta_pass=beta_pass, beta_stage=beta_stage, temp=temp,
+                                          **dial_opts), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -995,6 +1044,9 @@ class Args:
     riccati_feedback: bool = False  # (not in quadjax) on top of riccati: the closed-loop candidates under the sweep's gains compete too
     plan_hold: int = 1      # (not in quadjax) on top of riccati: every m-th control step plans, the others track the plan under the sweep's gains; 1 = off
     riccati_box: bool = False  # (not in quadjax) on top of riccati / with ilqr: the sweep's stages solve the control-limited box QP
+    beta_pass: float = 0.5  # (not in quadjax) --controller dial: the noise scale's factor per pass of a control step's --iters passes
+    beta_stage: float = 0.9  # (not in quadjax) --controller dial: the noise scale's factor per stage towards the front of the horizon
+    temp: float = 0.1       # (not in quadjax) --controller dial: a pass's temperature in standard deviations of its costs; 0 = the configured lam
 
 
 def main(args: Args):
@@ -1010,7 +1062,8 @@ def main(args: Args):
                                                 compute_plan=render, compute_fan=(args.fan or None) if render else None,
                                                 update=args.update, iters=args.iters, elite=args.elite or None,
                                                 sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render,
-                                                sigma_adapt=args.sigma_adapt, **take_switches(vars(args)))
+                                                sigma_adapt=args.sigma_adapt, **take_switches(vars(args)), beta_pass=args.beta_pass,
+                                                beta_stage=args.beta_stage, temp=args.temp if args.temp > 0.0 else None)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -1039,6 +1092,8 @@ def _cli():
             ap.add_argument("--sigma-period", "--sigma_period", dest="sigma_period", type=int, default=default)
         elif f == "sigma_adapt":
             ap.add_argument("--sigma-adapt", "--sigma_adapt", dest="sigma_adapt", type=float, default=default)
+        elif f in ("beta_pass", "beta_stage"):
+            ap.add_argument(f"--{f.replace('_', '-')}", f"--{f}", dest=f, type=float, default=default)
         else:
             ap.add_argument(f"--{f}", type=type(default), default=default)
     main(Args(**vars(ap.parse_args())))

@@ -464,6 +464,30 @@ int covo_set_episode_diag_log(covo_handle_t h, float *log, int32_t stride);
 int covo_set_step_ess_floor(covo_handle_t h, float ess_min, float *lam_out, int32_t n_inst);
 int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, float lam0, float ess_min, float *out, void *stream);
 
+/* The annealed MPPI step: a per-pass noise schedule and weights on standardised costs (additive to ABI 10: COVO_HAS_STEP_ANNEAL; off
+ * by default, and off changes nothing a caller can observe).  For an MPPI step of k = iters passes (covo_set_step_iters):
+ *   schedule   sigma_table = HOST float[n_pass][32], formed by the caller (the Python layer: fp32(sigma0 beta_pass^i beta_stage^(31 - h)),
+ *              in fp64, rounded once).  Pass i samples a = clip(mu_i + sigma[i][h] eps) stage by stage: one launch behind the pass's
+ *              begin launch writes the block factors sigma[i][h] I_4 and a_cov[h] = fp32(sigma[i][h]^2) I_4.  eps, the key walk and
+ *              mu_i are those of the same step without the attachment; a_cov on input is ignored, on output it is the last pass's.
+ *   temp > 0   with F the finite costs of the pass: mean = sum_F c / |F|, std = sqrt(sum_F (c - mean)^2 / |F|) (two passes, fp64),
+ *              lam_eff = fp32(temp std); the update is the softmax update at lam_eff through the ESS floor's staged launches.
+ *              Fallback to the configured lam, decided on the device: |F| < 2, std == 0, or lam_eff not a normal fp32 number.
+ *              The row: float[COVO_LAM_FLOATS] = {lam_eff, 1 / lam_eff (the correctly rounded fp32 quotient, as the ESS floor's row),
+ *              (float)std, bits(int32 |F| | fallback << 31)}.
+ *   temp = 0   every pass updates at the configured lam; no solver runs.
+ * covo_set_step_anneal: a NULL table with temp = 0 turns it off.  rows_out = DEVICE float[n_inst][n_pass][COVO_LAM_FLOATS] (row (e, i):
+ *   instance e's pass i; temp > 0 only), or NULL.  The last pass's row is also the handle's temperature row: COVO_EPLOG_LAM logs it.
+ *   The table is copied into device memory the handle owns; any change makes the handle re-capture its step graphs.
+ *   Refused at the step, before any launch: a mode other than COVO_MODE_MPPI; n_pass != the step's iters; gamma_sigma != 0 (the
+ *   schedule owns a_cov); temp > 0 together with the ESS floor or the elite-set update; a sample-sharded step; the env-batched fused
+ *   launch (the staged batch, covo_set_step_batched_staged, takes it).
+ * covo_cost_standardise: the solver alone on the caller's costs, DEVICE float[n_inst][n_samples] -> out = DEVICE
+ *   float[n_inst][COVO_LAM_FLOATS]. */
+#define COVO_HAS_STEP_ANNEAL 1
+int covo_set_step_anneal(covo_handle_t h, const float *sigma_table, int32_t n_pass, float temp, float *rows_out, int32_t n_inst);
+int covo_cost_standardise(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, float lam0, float temp, float *out, void *stream);
+
 /* The elite-set update: exact top-K selection on the device, the cross-entropy method's update rule (additive to ABI 10:
  * COVO_HAS_ELITE_UPDATE; off by default, and off changes nothing a caller can observe).  Per instance and per pass, with the costs
  * c_n as the rollout wrote them, key(n) = (u(c_n) << 32) | n: u is the order-preserving unsigned form of the fp32 bits (sign bit

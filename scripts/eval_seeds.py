@@ -28,6 +28,9 @@ name = sys.argv[1]
 # python scripts/eval_seeds.py ilqr iters=2 --riccati-box (or mppi --riccati --riccati-feedback --riccati-box): every sweep solves the
 # control-limited stage problem (csrc/riccati.hip, the box form); compare with the same call without the flag.  Under ilqr every seed's
 # line also carries the share of plan steps whose first sweep clamped a coordinate (the masks have no episode log)
+# python scripts/eval_seeds.py dial [iters=k] [beta_pass=b] [beta_stage=b] [temp=t | temp=none]: the annealed MPPI controller
+# (controllers/dial.py; defaults: get_controller's iters=1, 0.5 / 0.9 / 0.1); compare with `mppi iters=k`.  With temp every seed's line
+# also carries the share of steps whose last pass fell back to the configured temperature (the temperature log's bit 31 of entry 3)
 rest = sys.argv[2:]
 # the boolean step switches as flags: --refine, --riccati, --riccati-feedback, --riccati-box
 flags = {f"--{s.replace('_', '-')}": s for s, default in STEP_SWITCH_DEFAULTS.items() if isinstance(default, bool)}
@@ -37,9 +40,10 @@ for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_a
     while flag in rest:
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
-opts = {k: (float(v) if k in ("sigma_adapt", "ess_min") else int(v)) for k, v in (arg.split("=") for arg in rest)}
+FLOATS = ("sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp")
+opts = {k: (None if v.lower() == "none" else float(v) if k in FLOATS else int(v)) for k, v in (arg.split("=") for arg in rest)}
 switches["plan_hold"] = opts.pop("plan_hold", 1)
-assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"}, opts
+assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"} | ({"beta_pass", "beta_stage", "temp"} if name == "dial" else set()), opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
 ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **switches, **opts)
@@ -77,7 +81,10 @@ if name == "ilqr":
 
 def rows_of(ep):
     """what the episode's row logs say, summed into `rows` ({} for a controller without them)"""
-    if ep.lamlog is not None:
+    if ep.lamlog is not None and name == "dial":
+        words = np.ascontiguousarray(ep.read_lam()["evaluations"]).view(np.int32)  # (entry 3 of the row: bits(|F| | fallback << 31))
+        rows["fellback"] = rows.get("fellback", 0) + int((words < 0).sum())
+    elif ep.lamlog is not None:
         rows["floor"] = rows.get("floor", 0) + int((ep.read_lam()["lam_eff"] > np.float32(core.lam)).sum())
     if ep.sigmalog is not None and core.sigma_adapt_gamma > 0.0:
         rows["fallback"] = rows.get("fallback", 0) + int((ep.read_sigma()["fallback"] != 0.0).sum())
@@ -107,6 +114,7 @@ for seed in range(1, 13):
     npl = max(rows.get("plans", 0), 1)
     nh = max(rows.get("held", 0), 1)
     extra = "".join(text % (rows[k] / d) for k, text, d in (("floor", "  lam_eff>lam: %.3f", n), ("fallback", "  adapt fallbacks: %d", 1),
+                                                           ("fellback", "  last pass at the configured lam: %.3f", n),
                                                            ("improved", "  last pass beat first: %.3f", n),
                                                            ("fixed", "  plan steps at a fixed point: %.3f", npl),
                                                            ("closed", "  plan steps with a closed-loop commit: %.3f", npl),
