@@ -41,6 +41,7 @@ COVO_HAS_STEP_ANNEAL = 1  # the "dial" controller (covo_set_step_anneal, covo_co
 # the standardising solver's row: {lam_eff, 1 / lam_eff, std, bits(int32 |F| | fallback << 31)}, F the pass's finite costs
 ANNEAL_FIELDS = ("lam_eff", "inv_lam_eff", "std", "n_finite")
 ANNEAL_FALLBACK_BIT = 0x80000000
+COVO_HAS_STEP_NODES = 1  # the annealed controllers' nodes=M (covo_set_step_nodes, covo_noise_nodes_philox): spline-node perturbations
 COVO_HAS_ELITE_UPDATE = 1
 COVO_ELITE_FLOATS = 8  # the elite-set update's selector row of one instance (covo_set_step_elite)
 ELITE_FIELDS = ("threshold_cost_word", "threshold_index_word", "cost_min", "cost_kth", "K", "ties")  # words: uint32 bits
@@ -234,6 +235,10 @@ _SIGS = {
     # the annealed step (covo_hip.h: COVO_HAS_STEP_ANNEAL)
     "covo_set_step_anneal": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.c_float, _P, C.c_int32]),
     "covo_cost_standardise": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_float, C.c_float, _P, _P]),
+    # the spline nodes of the annealed step (covo_hip.h: COVO_HAS_STEP_NODES)
+    "covo_set_step_nodes": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.c_int32]),
+    "covo_step_nodes": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "covo_noise_nodes_philox": (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, C.c_uint32, C.c_int64, C.c_int32, _P, _P]),
     "covo_set_step_elite": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # the elite-set update (covo_hip.h: COVO_HAS_ELITE_UPDATE)
     "covo_elite_select": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "covo_set_step_sigma_period": (C.c_int, [_P, C.c_int32]),  # the Sigma period (covo_hip.h: COVO_HAS_SIGMA_PERIOD)

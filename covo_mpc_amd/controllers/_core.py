@@ -252,7 +252,7 @@ class SamplingCore:
             self.riccati_box_masks = torch.zeros((self._rows, COVO_H), dtype=torch.int32, device=self.device)
             check(self.lib.covo_set_step_riccati_box(self.h, ptr(self.riccati_box_masks), self._rows), "covo_set_step_riccati_box")
         # the annealed step (not a step option: the attachment of the controllers of controllers/dial.py; _options.check_dial)
-        self.anneal = self.anneal_sigma = self.anneal_rows = None
+        self.anneal = self.anneal_sigma = self.anneal_rows = self.anneal_node_sigma = None
         self._list_infos()
         if anneal is not None:
             self.attach_anneal(anneal)
@@ -644,6 +644,13 @@ class SamplingCore:
             check(self.lib.covo_set_step_anneal(self.h, sigma.ctypes.data_as(C.POINTER(C.c_float)), self.iters, float(anneal.temp),
                                                 ptr(self.anneal_rows) if anneal.temp > 0.0 else None, self._rows),
                   "covo_set_step_anneal")
+            if anneal.nodes is not None:  # nodes=M: the sampler's table next to the schedule, which was fed the marginals above
+                basis = np.ascontiguousarray(anneal.basis, dtype=np.float32)
+                if basis.shape != (self.iters, COVO_H, anneal.nodes):
+                    raise ValueError(f"attach_anneal: the basis table is {basis.shape}, not {(self.iters, COVO_H, anneal.nodes)}")
+                check(self.lib.covo_set_step_nodes(self.h, basis.ctypes.data_as(C.POINTER(C.c_float)), self.iters, anneal.nodes),
+                      "covo_set_step_nodes")
+                self.anneal_node_sigma = torch.from_numpy(np.asarray(anneal.node_sigma, dtype=np.float32)).to(self.device)
         self._list_infos()
 
     @property
@@ -652,7 +659,8 @@ class SamplingCore:
         return self.ess_min != 0.0 or (self.anneal is not None and self.anneal.temp > 0.0)
 
     def anneal_info(self) -> dict:
-        """{"anneal_sigma" [k, 32], "anneal_rows" [k, 4], "anneal_lam" [k], "anneal_std" [k], "anneal_fallback" [k] bool} of the last
+        """(under nodes=M also "anneal_nodes" M and "anneal_node_sigma" [k, M]; "anneal_sigma" is then sigma_e)
+        {"anneal_sigma" [k, 32], "anneal_rows" [k, 4], "anneal_lam" [k], "anneal_std" [k], "anneal_fallback" [k] bool} of the last
         step's k passes, and under temp "lam_eff", the last pass's -- views of self.anneal_sigma / self.anneal_rows (no sync; the bool
         is one device op on a view); {} on a core without the attachment."""
         if self.anneal_rows is None:
@@ -662,7 +670,16 @@ class SamplingCore:
                "anneal_fallback": rows[:, 3].view(self.torch.int32) < 0}
         if self.anneal.temp > 0.0:
             out["lam_eff"] = rows[-1, 0]
+        if self.anneal.nodes is not None:  # (anneal_sigma is then the stages' marginal sigma_e)
+            out["anneal_nodes"] = self.anneal.nodes
+            out["anneal_node_sigma"] = self.anneal_node_sigma
         return out
+
+    def step_nodes(self):
+        """covo_step_nodes: (n_pass, n_nodes) of the node table attached to the handle, (0, 0) for none."""
+        n_pass, n_nodes = C.c_int32(-1), C.c_int32(-1)
+        check(self.lib.covo_step_nodes(self.h, C.byref(n_pass), C.byref(n_nodes)), "covo_step_nodes")
+        return n_pass.value, n_nodes.value
 
     def cost_standardise(self, cost, temp, lam0=None):
         """covo_cost_standardise (the stand-alone standardising solver): cost float32 device tensor [N] or [E, N] -> float32 [E, 4] rows
@@ -1117,6 +1134,15 @@ class SamplingCore:
         check(self.lib.covo_noise_blockdiag_philox(self.h, ptr(Ls), ptr(mu), int(key[0]), int(key[1]), self.offset,
                                                    self.n_local, ptr(self.a), self.stream()),
               "covo_noise_blockdiag_philox")
+        return self.a
+
+    def noise_nodes(self, basis, mu, key):
+        """covo_noise_nodes_philox (the stand-alone spline-node sampler, csrc/noise_nodes.hip): basis float32 device [32, M],
+        2 <= M <= 32 -> self.a = clip(mu + basis @ eps[:, :M]) with eps = randn(key), an ascending-m fmaf chain per entry."""
+        assert basis.is_cuda and basis.dtype == self.torch.float32 and basis.is_contiguous() and basis.dim() == 2
+        assert int(basis.shape[0]) == COVO_H
+        check(self.lib.covo_noise_nodes_philox(self.h, ptr(basis), int(basis.shape[1]), ptr(mu), int(key[0]), int(key[1]), self.offset,
+                                               self.n_local, ptr(self.a), self.stream()), "covo_noise_nodes_philox")
         return self.a
 
     def noise_blockdiag(self, Ls, mu, eps=None):

@@ -444,6 +444,65 @@ class Anneal:
     temp: float         # 0.0: every pass updates at the configured lam, no solver runs
     beta_pass: float
     beta_stage: float
+    # nodes=M (check_dial): the perturbations are splines over M nodes; sigma above is then the stages' marginal sigma_e [iters, 32]
+    nodes: object = None        # int M in [2, 32], or None: a draw per stage
+    node_interp: str = "linear"
+    node_sigma: object = None   # float64 numpy [iters, M]: the schedule over the nodes (node_schedule)
+    basis: object = None        # float32 numpy [iters, 32, M]: B[i][h][m] = fp32(node_sigma[i][m] weights[h][m]), what the sampler reads
+    weights: object = None      # float64 numpy [32, M]: W[h][m], node m's interpolation weight at stage h (node_basis)
+
+
+NODE_INTERPS = ("linear", "cubic")
+
+
+def node_basis(M, interp="linear", H=_lib.COVO_H):
+    """W[h][m] = phi_m(h), float64 numpy [H, M]: the value at stage h of the interpolant through the unit vector e_m on the M nodes
+    t_m = m (H - 1) / (M - 1) (formed as (m * (H - 1)) / (M - 1): t_0 = 0 and t_{M-1} = H - 1 exactly).  "linear": the hat functions;
+    "cubic": the cardinal functions of the natural cubic spline (second derivatives from the tridiagonal system, zero at both ends).
+    Evaluated on the node interval [t_j, t_j+1] that holds h with s = (h - t_j) / (t_j+1 - t_j): a stage that is a node gets that
+    node's unit vector exactly, rows sum to 1 and reproduce h (sum_m W[h][m] t_m = h) up to rounding; M = H linear is the identity."""
+    import numpy as np
+    M = int(M)
+    if not 2 <= M <= H or interp not in NODE_INTERPS:
+        raise ValueError(f"node_basis: M={M} outside [2, {H}] or interp={interp!r} not one of {NODE_INTERPS}")
+    t = np.array([(m * (H - 1)) / (M - 1) for m in range(M)], dtype=np.float64)
+    d = np.diff(t)
+    z = np.zeros((M, M), dtype=np.float64)  # z[:, m]: the second derivatives at the nodes of the spline through e_m
+    if interp == "cubic" and M > 2:
+        A = np.zeros((M - 2, M - 2), dtype=np.float64)
+        for r in range(M - 2):  # row r: node r + 1
+            A[r, r] = 2.0 * (d[r] + d[r + 1])
+            if r > 0:
+                A[r, r - 1] = d[r]
+            if r < M - 3:
+                A[r, r + 1] = d[r + 1]
+        Y = np.eye(M, dtype=np.float64)
+        rhs = 6.0 * ((Y[2:] - Y[1:-1]) / d[1:, None] - (Y[1:-1] - Y[:-2]) / d[:-1, None])
+        z[1:-1] = np.linalg.solve(A, rhs)
+    W = np.zeros((H, M), dtype=np.float64)
+    for h in range(H):
+        j = min(int(np.searchsorted(t, float(h), side="right")) - 1, M - 2)
+        s = (h - t[j]) / d[j]
+        u = (t[j + 1] - h) / d[j]  # (not 1 - s: both ends of the interval are then exact)
+        W[h, j] += u
+        W[h, j + 1] += s
+        W[h] += (z[j] * (u * u * u - u) + z[j + 1] * (s * s * s - s)) * (d[j] * d[j] / 6.0)
+    return W
+
+
+def node_schedule(sample_sigma, iters, beta_pass, beta_stage, M, interp="linear", H=_lib.COVO_H):
+    """The tables of nodes=M -> (node_sigma float64 [iters, M], basis float32 [iters, H, M], sigma_e float32 [iters, H], W float64):
+    node_sigma[i][m] = sample_sigma beta_pass^i beta_stage^(M - 1 - m) -- anneal_schedule's expression with the NODES in the stages'
+    place --, basis[i][h][m] = fp32(node_sigma[i][m] W[h][m]) rounded once, and sigma_e[i][h] = fp32(sqrt(sum_m fp64(basis[i][h][m])^2)),
+    stage h's marginal standard deviation under the ROUNDED entries.  M = H linear: basis[i] = diag(anneal_schedule(...)[i]) and
+    sigma_e = that schedule, word for word (the square of an fp32 number is exact in fp64)."""
+    import numpy as np
+    s0, bp, bs, M = float(sample_sigma), float(beta_pass), float(beta_stage), int(M)
+    W = node_basis(M, interp, H)
+    node_sigma = np.array([[s0 * bp ** i * bs ** (M - 1 - m) for m in range(M)] for i in range(int(iters))], dtype=np.float64)
+    basis = (node_sigma[:, None, :] * W[None, :, :]).astype(np.float32)
+    sigma_e = np.sqrt((basis.astype(np.float64) ** 2).sum(axis=2)).astype(np.float32)
+    return node_sigma, basis, sigma_e, W
 
 
 def anneal_schedule(sample_sigma, iters, beta_pass, beta_stage, H=_lib.COVO_H):
@@ -455,7 +514,7 @@ def anneal_schedule(sample_sigma, iters, beta_pass, beta_stage, H=_lib.COVO_H):
 
 
 def check_dial(iters=4, *, beta_pass=0.5, beta_stage=0.9, temp=0.1, gamma_sigma=0.0, sample_sigma=0.5, materialize_eps=False,
-               noise_stream="philox", what="the annealed MPPI controller"):
+               noise_stream="philox", what="the annealed MPPI controller", nodes=None, node_interp="linear"):
     """The keywords of the annealed MPPI controllers (DialController, BatchedDialController, get_controller(env, "dial", ...),
     eval_env_batched(controller="dial")) -> the Anneal record SamplingCore attaches, or None for the neutral element
     (beta_pass = beta_stage = 1 with temp=None: nothing is attached, the controller is MPPIController(iters=k) launch for launch).  The
@@ -468,8 +527,17 @@ def check_dial(iters=4, *, beta_pass=0.5, beta_stage=0.9, temp=0.1, gamma_sigma=
     ["anneal_rows"] [k, 4] / ["anneal_lam"] [k] / ["anneal_std"] [k] / ["anneal_fallback"] [k] bool, and with temp given
     info["lam_eff"], the last pass's.
 
+    nodes=M (2 <= M <= 32; node_interp "linear" or "cubic"): the pass's PERTURBATIONS are splines over M nodes spread over the
+    horizon -- a[h] = clip(mu_i[h] + sum_m B[i][h][m] e_m) with the tables of node_schedule (csrc/noise_nodes.hip), beta_stage running
+    over the nodes -- drawn in 4 M dimensions; the mean stays the stage-space 128-vector, so nothing behind the sampler changes (unlike
+    DIAL-MPC, which keeps node values and re-fits them after every shift).  Anneal.sigma, info["anneal_sigma"] and the returned a_cov
+    are then the stages' marginals sigma_e -- only the 4 x 4 block diagonal of the sampled covariance (B B^T) (x) I_4 of rank 4 M;
+    info gains "anneal_nodes" and "anneal_node_sigma" [k, M].  With nodes given an Anneal is always returned (also at beta = 1,
+    temp=None); nodes=32 linear is nodes=None in every output value.
+
     The objections, in a fixed order (ValueError naming the keyword): iters anything but an integer in [1, COVO_MAX_STEP_ITERS];
     beta_pass, then beta_stage, anything but a real number in (0, 1]; temp anything but None or a finite real number > 0;
+    nodes anything but None or an integer in [2, 32]; node_interp anything but "linear" or "cubic";
     gamma_sigma != 0 -- the schedule owns a_cov; then materialize_eps / noise_stream="jax" (NotImplementedError): the kernel-by-kernel
     path knows no schedule."""
     import math
@@ -483,12 +551,21 @@ def check_dial(iters=4, *, beta_pass=0.5, beta_stage=0.9, temp=0.1, gamma_sigma=
                              not float(temp) > 0.0):
         raise ValueError(f"temp={temp!r} (None, or a finite real number > 0: the pass's temperature in units of the standard deviation "
                          "of its costs)")
+    if nodes is not None and (isinstance(nodes, bool) or not isinstance(nodes, numbers.Integral) or not 2 <= int(nodes) <= _lib.COVO_H):
+        raise ValueError(f"nodes={nodes!r} (None, or an integer in [2, {_lib.COVO_H}]: the spline nodes the perturbations of a pass are "
+                         "drawn at)")
+    if node_interp not in NODE_INTERPS:
+        raise ValueError(f"node_interp={node_interp!r} is not one of {NODE_INTERPS}")
     if float(gamma_sigma) != 0.0:
         raise ValueError(f"gamma_sigma={gamma_sigma} with {what}: the schedule owns a_cov, MPPI's covariance adaptation would adapt "
                          "what the next pass overwrites; give gamma_sigma=0")
     if materialize_eps or noise_stream != "philox":
         raise NotImplementedError(f"{what} acts in the fused step (covo_mpc_step); the kernel-by-kernel path (materialize_eps / "
                                   "noise_stream='jax') knows no schedule and updates at the configured lam")
+    if nodes is not None:
+        node_sigma, basis, sigma_e, W = node_schedule(sample_sigma, k, beta_pass, beta_stage, int(nodes), node_interp)
+        return Anneal(sigma=sigma_e, temp=0.0 if temp is None else float(temp), beta_pass=float(beta_pass), beta_stage=float(beta_stage),
+                      nodes=int(nodes), node_interp=node_interp, node_sigma=node_sigma, basis=basis, weights=W)
     if float(beta_pass) == 1.0 and float(beta_stage) == 1.0 and temp is None:
         return None
     return Anneal(sigma=anneal_schedule(sample_sigma, k, beta_pass, beta_stage), temp=0.0 if temp is None else float(temp),

@@ -341,18 +341,19 @@ class BatchedDialController(BatchedMPPIController):
     a_cov itself and needs the temperature before all costs exist).  Every instance runs the same schedule; instance e's result is
     bit-identical to DialController's on that instance alone (tests/test_gpu_anneal.py).  After a call: .anneal_rows [E, iters, 4]
     (every pass's solver row; {lam, 1 / lam, 0, 0} without temp), .anneal_sigma [iters, 32], and the step options' buffers as for
-    BatchedMPPIController.  beta_pass = beta_stage = 1 with temp=None attaches nothing: BatchedMPPIController(staged=True, iters=k)."""
+    BatchedMPPIController.  beta_pass = beta_stage = 1 with temp=None attaches nothing: BatchedMPPIController(staged=True, iters=k).
+    nodes=M / node_interp: the spline-node perturbations of check_dial, one table for all instances (.anneal_sigma is then sigma_e)."""
 
     def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, iters: int = 4, beta_pass: float = 0.5, beta_stage: float = 0.9,
                  temp=0.1, sigmas=0.5, discount: float = 1.0, gamma_mean: float = 1.0, a_mean_init=None, device=None,
                  compute_diag: bool = False, compute_plan: bool = False, compute_fan=None, update: str = "softmax",
-                 compute_post_cov: bool = False):
+                 compute_post_cov: bool = False, nodes=None, node_interp: str = "linear"):
         from ._options import check_dial
         sig = np.broadcast_to(np.asarray(sigmas, dtype=np.float32).reshape(-1), (4,))
         if not (sig == sig[0]).all():
             raise ValueError(f"sigmas={sigmas!r}: the schedule scales ONE standard deviation for all four action components")
         self.anneal = check_dial(iters, beta_pass=beta_pass, beta_stage=beta_stage, temp=temp, sample_sigma=float(sig[0]),
-                                 what="the env-batched annealed MPPI controller")
+                                 what="the env-batched annealed MPPI controller", nodes=nodes, node_interp=node_interp)
         super().__init__(env, n_envs, N, H, lam, sigmas=float(sig[0]), discount=discount, gamma_mean=gamma_mean, gamma_sigma=0.0,
                          a_mean_init=a_mean_init, device=device, compute_diag=compute_diag, compute_plan=compute_plan,
                          compute_fan=compute_fan, update=update, iters=iters, compute_post_cov=compute_post_cov, staged=True)

@@ -180,6 +180,7 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->ws_blockmin));
     DESTROY(hipFree(h->lam_own));
     DESTROY(hipFree(h->anneal_table));
+    DESTROY(hipFree(h->nodes_table));
     DESTROY(hipFree(h->elite_own));
     DESTROY(hipFree(h->ws_stats));
     DESTROY(hipFree(h->ws_sigma));
@@ -857,6 +858,56 @@ int covo_cost_standardise(covo_handle_t h, const float *cost, int32_t n_samples,
     return launch_cost_standardise(cost, n_samples, n_inst, lam0, temp, out, nullptr, 0, (hipStream_t)stream);
 }
 
+// ---- the annealed step's spline nodes (noise_nodes.hip).  As covo_set_step_anneal: the captured step graphs bake in the sampler's launch
+// and read the table in the handle's own device memory, so any change bumps the epoch and the table is rewritten only after every
+// launch that may still read it has finished.  What the step needs next to it is checked at the step (check_step_attachments)
+int covo_set_step_nodes(covo_handle_t h, const float *basis_table, int32_t n_pass, int32_t n_nodes)
+{
+    REQUIRE(h, "covo_set_step_nodes: null handle");
+    if (basis_table == nullptr) {
+        if (covo_nodes_on(h)) ++h->opt.epoch;
+        h->nodes_passes = h->nodes_M = 0;
+        return 0;
+    }
+    REQUIRE(n_pass >= 1 && n_pass <= COVO_MAX_STEP_ITERS, "covo_set_step_nodes: n_pass=%d outside [1, %d]", n_pass, COVO_MAX_STEP_ITERS);
+    REQUIRE(n_nodes >= 2 && n_nodes <= COVO_H, "covo_set_step_nodes: n_nodes=%d outside [2, %d]", n_nodes, COVO_H);
+    for (int i = 0; i < n_pass * COVO_H * n_nodes; ++i)
+        REQUIRE(__builtin_fabsf(basis_table[i]) < __builtin_inff(), "covo_set_step_nodes: basis_table[%d][%d][%d]=%g is not a finite number",
+                i / (COVO_H * n_nodes), i / n_nodes % COVO_H, i % n_nodes, (double)basis_table[i]);
+    CHECK_DEVICE(h, "covo_set_step_nodes");
+    COVO_CHECK_HIP(hipDeviceSynchronize());  // (a setter, off the per-step path) no step in flight reads the old table
+    if (h->nodes_table == nullptr)
+        COVO_CHECK_HIP(hipMalloc(&h->nodes_table, (size_t)COVO_MAX_STEP_ITERS * COVO_H * COVO_H * sizeof(float)));
+    COVO_CHECK_HIP(hipMemcpy(h->nodes_table, basis_table, (size_t)n_pass * COVO_H * n_nodes * sizeof(float), hipMemcpyHostToDevice));
+    ++h->opt.epoch;
+    h->nodes_passes = n_pass;
+    h->nodes_M = n_nodes;
+    return 0;
+}
+
+int covo_step_nodes(covo_handle_t h, int32_t *n_pass, int32_t *n_nodes)
+{
+    REQUIRE(h, "covo_step_nodes: null handle");
+    REQUIRE(n_pass && n_nodes, "covo_step_nodes: bad argument");
+    *n_pass = h->nodes_passes;
+    *n_nodes = h->nodes_M;
+    return 0;
+}
+
+int covo_noise_nodes_philox(covo_handle_t h, const float *basis, int32_t n_nodes, const float *mu, uint32_t key0, uint32_t key1,
+                            int64_t sample_offset, int32_t N, float *a_out, void *stream)
+{
+    REQUIRE(h, "covo_noise_nodes_philox: null handle");
+    CHECK_DEVICE(h, "covo_noise_nodes_philox");
+    REQUIRE(basis && mu && a_out && N > 0, "covo_noise_nodes_philox: bad argument");
+    REQUIRE(n_nodes >= 2 && n_nodes <= COVO_H, "covo_noise_nodes_philox: n_nodes=%d outside [2, %d]", n_nodes, COVO_H);
+    NoiseDesc d = noise_desc(h, nullptr, mu, N, a_out);
+    d.key[0] = key0;
+    d.key[1] = key1;
+    d.sample_offset = sample_offset;
+    return launch_noise_nodes(d, basis, 0, n_nodes, (hipStream_t)stream);
+}
+
 // ---- the elite-set update (elite_select.hip, reduce_elite.hip).  The captured step graphs bake in the staged launch set, K and where
 // the selector writes: any change bumps the epoch.  The valid range of K depends on the step's sample count: checked at the step
 // (check_step_attachments)
@@ -1293,6 +1344,16 @@ static int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, 
                     "force is a state of the sweep; the hold step carries the 13-state plants only; set period = 1", what,
                     params[e].disturb_kind, e);
         REQUIRE(n_inst <= h->hold_n, "%s: %d instances, the hold rows (covo_set_step_plan_hold) have n_inst=%d", what, n_inst, h->hold_n);
+    }
+    if (covo_nodes_on(h)) {  // the spline nodes: a sampler under the annealed schedule, nothing of their own besides
+        REQUIRE(covo_anneal_sched_on(h),
+                "%s: the spline nodes (covo_set_step_nodes, n_nodes=%d) without an attached schedule (covo_set_step_anneal with a "
+                "table): the schedule launch writes the marginals a_cov reports; attach it, or turn the nodes off (a null table)", what,
+                h->nodes_M);
+        REQUIRE(h->nodes_passes == h->anneal_passes,
+                "%s: the spline nodes (covo_set_step_nodes) were set for n_pass=%d passes, the schedule (covo_set_step_anneal) for "
+                "n_pass=%d: the basis table has one slice per pass; set both to the same count", what, h->nodes_passes, h->anneal_passes);
+        REQUIRE(h->nodes_M >= 2 && h->nodes_M <= COVO_H, "%s: n_nodes=%d (covo_set_step_nodes) outside [2, %d]", what, h->nodes_M, COVO_H);
     }
     if (covo_anneal_on(h)) {  // the annealed step: MPPI's block-diagonal draw under a per-pass table, weights on standardised costs
         REQUIRE(mode == COVO_MODE_MPPI,

@@ -76,6 +76,10 @@ struct covo_ctx {
     float anneal_temp;        // > 0: every pass's temperature is temp x the standard deviation of its finite costs; 0: the configured lam
     float *anneal_rows;       // caller's [anneal_n][anneal_passes][COVO_LAM_FLOATS]: instance e's solver row of every pass, or null
     int anneal_n;
+    // the annealed step's spline nodes (covo_set_step_nodes; noise_nodes.hip); nodes_M == 0: off
+    float *nodes_table;       // [nodes_passes][H][nodes_M] the handle's own: B[i][h][m] of pass i (uploaded by the setter)
+    int nodes_passes;         // the passes the table was set for: the schedule's must equal it
+    int nodes_M;              // nodes per pass, 2 .. H
     // the elite-set update (covo_set_step_elite; elite_select.hip, reduce_elite.hip); elite_K == 0: off
     int elite_K;              // elites per instance and pass
     float *elite_out;         // caller's [elite_n][COVO_ELITE_FLOATS]: instance e's selector row of every step; null: elite_own
@@ -212,6 +216,7 @@ static inline float *covo_iter_slot(const covo_ctx *h, int pass) { return covo_s
 static inline bool covo_ess_on(const covo_ctx *h) { return h->ess_min > 0.0f; }
 static inline bool covo_anneal_on(const covo_ctx *h) { return h->anneal_passes > 0; }
 static inline bool covo_anneal_sched_on(const covo_ctx *h) { return h->anneal_passes > 0 && h->anneal_sched != 0; }
+static inline bool covo_nodes_on(const covo_ctx *h) { return h->nodes_M > 0; }
 static inline bool covo_anneal_temp_on(const covo_ctx *h) { return h->anneal_passes > 0 && h->anneal_temp > 0.0f; }
 static inline float *covo_lam_target(const covo_ctx *h)
 {
@@ -416,6 +421,9 @@ struct NoiseDesc {
 };
 int launch_noise_gemm(const NoiseDesc &d, hipStream_t s);
 int launch_noise_blockdiag(const NoiseDesc &d, hipStream_t s);
+// noise_nodes.hip: a = clip(mu + B eps_nodes) with B = slice `pass` of table [.][H][n_nodes] and eps_nodes the first n_nodes normal4
+// of the block-diagonal kernel's stream (in-kernel draw only; d.L / eps_tiled / state_for_time / cov are not read)
+int launch_noise_nodes(const NoiseDesc &d, const float *table, int pass, int n_nodes, hipStream_t s);
 static inline bool covo_propagate_nan(const covo_ctx *h) { return (h->cfg.flags & COVO_FLAG_PROPAGATE_NAN) != 0; }
 // how the rollout treats the action stripes it reads (RolloutArgs::clip)
 enum RolloutClip {

@@ -431,7 +431,9 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
             nd.L = st->Ls;  // (a_cov was shifted and factored there by the begin launch)
             // covo_set_step_anneal: this pass's row of the schedule replaces both -- a_cov on input is ignored
             if (covo_anneal_sched_on(h) && (rc = launch_anneal_schedule(h->anneal_table, pass, st->Ls, a.a_cov, 1, s))) return rc;
-            if ((rc = launch_noise_blockdiag(nd, s))) return rc;
+            // covo_set_step_nodes: the pass's perturbations are splines over its nodes (the schedule above was fed their marginals)
+            if (covo_nodes_on(h)) { if ((rc = launch_noise_nodes(nd, h->nodes_table, pass, h->nodes_M, s))) return rc; }
+            else if ((rc = launch_noise_blockdiag(nd, s))) return rc;
         }
     }
     // the rollout's workgroups leave the softmax update's stage-1 records themselves when they may (rollout_leaves_records); otherwise
@@ -1219,7 +1221,8 @@ static int batch_staged_enqueue(covo_ctx *h, BatchState *b, const covo_batch_mod
         nd.L = x.Ls;
         // covo_set_step_anneal: this pass's row of the schedule into every instance's factors and a_cov, as in the single step
         if (covo_anneal_sched_on(h) && (rc = launch_anneal_schedule(h->anneal_table, pass, x.Ls, a.a_cov, E, s))) return rc;
-        if ((rc = launch_noise_blockdiag(nd, s))) return rc;
+        if (covo_nodes_on(h)) { if ((rc = launch_noise_nodes(nd, h->nodes_table, pass, h->nodes_M, s))) return rc; }  // (as the single step)
+        else if ((rc = launch_noise_blockdiag(nd, s))) return rc;
     } else {
         nd.L = m.L_table;
         nd.state_for_time = a.states;

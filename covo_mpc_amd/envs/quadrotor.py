@@ -595,7 +595,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                      arbiter: bool = False, iters: int = 1, elite=None, sigma_period: int = 1, sigma_adapt: float = 0.0,
                      rows: bool = False, staged: bool = False, controller: str = "covo-online", refine: bool = False,
                      riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False,
-                     beta_pass: float = 0.5, beta_stage: float = 0.9, temp=0.1):
+                     beta_pass: float = 0.5, beta_stage: float = 0.9, temp=0.1, *, nodes=None, node_interp: str = "linear"):
     """BASELINE configs[4] as a driver: `n_envs` domain-randomised instances of `env` (each with parameters from
     env.sample_params, its own reset key and key chain, quadrotor.py:132-171 + 506-591 per instance) run one episode under
     `controller` (covo-online by default), controller and env on the device, ONE host sync.  -> mean position error per instance
@@ -618,7 +618,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     the measured state (check_plan_hold); rows=True then also holds "hold": ep.read_hold().  riccati_box=True on top of riccati (implied
     by "ilqr"): every sweep solves the control-limited stage problem (check_riccati_box).  controller="dial": BatchedDialController
     (annealed MPPI, always staged) under iters / beta_pass / beta_stage / temp (check_dial; the other controllers ignore the last three);
-    rows=True then also holds "lam": ep.read_lam(), the last pass's solver rows, when temp is given."""
+    rows=True then also holds "lam": ep.read_lam(), the last pass's solver rows, when temp is given.  nodes=M / node_interp (keyword-only,
+    "dial" only): the spline-node perturbations of check_dial."""
     if controller not in ("covo-online", "mppi", "covo-offline", "ilqr", "dial"):
         raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline', 'ilqr' or 'dial'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
@@ -628,7 +629,8 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
                                   opts)
     dial = controller == "dial"
     if dial:
-        dial_opts = _check_dial_keywords({**opts, "ess_min": None, "compute_post_cov": False}, switches, None, beta_pass, beta_stage, temp)
+        dial_opts = _check_dial_keywords({**opts, "ess_min": None, "compute_post_cov": False}, switches, None, beta_pass, beta_stage, temp,
+                                         nodes, node_interp)
         if staged:
             raise ValueError("staged=True with controller='dial': the annealed batch is always staged")
     online, batch = controller == "covo-online", f"the env-batched {controller} controller"
@@ -648,7 +650,7 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     if dial:
         b = controllers.BatchedDialController(env, n_envs, N, H, lam, sigmas=cp0.sample_sigma, beta_pass=beta_pass, beta_stage=beta_stage,
                                               temp=temp, discount=cp0.discount, gamma_mean=cp0.gamma_mean, a_mean_init=cp0.a_mean,
-                                              device=c0.core.device, **dial_opts)
+                                              device=c0.core.device, nodes=nodes, node_interp=node_interp, **dial_opts)
     elif controller == "mppi":  # (it takes no switch: check_riccati has refused riccati, which the others need, for the two baselines)
         b = controllers.BatchedMPPIController(env, n_envs, N, H, lam, sigmas=cp0.sample_sigma, **kw)
     else:
@@ -684,11 +686,11 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     return out if len(out) > 1 else out[0]
 
 
-def _check_dial_keywords(opts, switches, process_group, beta_pass, beta_stage, temp):
+def _check_dial_keywords(opts, switches, process_group, beta_pass, beta_stage, temp, nodes=None, node_interp="linear"):
     """check_dial on the keywords get_controller and eval_env_batched carry -> the step options DialController / BatchedDialController
     take.  The objections, in a fixed order: check_dial's own; then ValueError for ess_min, elite, sigma_period, sigma_adapt, a step
     switch or a process_group away from its default, naming it."""
-    check_dial(opts["iters"], beta_pass=beta_pass, beta_stage=beta_stage, temp=temp)
+    check_dial(opts["iters"], beta_pass=beta_pass, beta_stage=beta_stage, temp=temp, nodes=nodes, node_interp=node_interp)
     for name in ("ess_min", "elite", "sigma_period", "sigma_adapt"):
         v, default = opts[name], STEP_OPTION_DEFAULTS[name]
         if not ((not v) if default is None else v == default):
@@ -843,7 +845,8 @@ def eval_env(env: Quad3D, controller, total_steps=30000, filename="", num_trajs=
 def get_controller(env, controller_name, controller_params=None, debug=False, device=None, process_group=None,
                    compute_info=True, compute_diag=False, compute_plan=False, ess_min=None, compute_fan=None, update="softmax",
                    iters=1, elite=None, sigma_period=1, compute_post_cov=False, sigma_adapt=0.0, refine=False,
-                   riccati=False, riccati_feedback=False, plan_hold=1, riccati_box=False, beta_pass=0.5, beta_stage=0.9, temp=0.1):
+                   riccati=False, riccati_feedback=False, plan_hold=1, riccati_box=False, beta_pass=0.5, beta_stage=0.9, temp=0.1, *,
+                   nodes=None, node_interp="linear"):
     """quadrotor.py:670-752.  compute_diag, compute_plan, ess_min, compute_fan, update, iters, elite, sigma_period, compute_post_cov and
     sigma_adapt are the sampling controllers' step options -- what each does and what it adds to the controller's info dict:
     controllers/_options.py.  refine (covo-online only): the Newton line search behind every step -- a switch, not a step option
@@ -858,14 +861,14 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     asks for the closed-loop candidates and False (this signature's default) leaves the choice to the plant (ILQRController's None);
     every other step option away from its default is a ValueError.
     controller_name "dial": the annealed MPPI controller (controllers/dial.py; controllers/_options.py: check_dial) -- MPPI's control
-    parameters; iters, beta_pass, beta_stage and temp are its own keywords (every other controller name ignores the last three at
-    their defaults), compute_diag / compute_plan / compute_fan / update / compute_post_cov pass through; ess_min, elite, sigma_period,
+    parameters; iters, beta_pass, beta_stage, temp and the keyword-only nodes / node_interp (spline-node perturbations) are its own
+    keywords (every other controller name ignores all but iters at their defaults), compute_diag / compute_plan / compute_fan / update / compute_post_cov pass through; ess_min, elite, sigma_period,
     sigma_adapt, a switch or a process_group away from the default is a ValueError."""
     opts, switches = take(locals()), take_switches(locals())
     if controller_name == "ilqr":  # ValueError / NotImplementedError before anything is built
         k, feedback, m = _check_ilqr_switches(env, switches, opts, process_group=process_group)
     if controller_name == "dial":
-        dial_opts = _check_dial_keywords(opts, switches, process_group, beta_pass, beta_stage, temp)
+        dial_opts = _check_dial_keywords(opts, switches, process_group, beta_pass, beta_stage, temp, nodes, node_interp)
     import torch
     if controller_name == "ilqr":
         H = int(controller_params.split("_")[1][1:]) if controller_params else 32
@@ -916,7 +919,7 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
                                                 a_mean=get_sample_mean(H), a_cov=a_cov)
         return controllers.DialController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
                                           compute_info=compute_info, beta_pass=beta_pass, beta_stage=beta_stage, temp=temp,
-                                          **dial_opts), control_params
+                                          nodes=nodes, node_interp=node_interp, **dial_opts), control_params
     if "covo" in controller_name:
         N, H, lam, sigma = parse_sample_params(controller_params)
         mode = "offline" if "offline" in controller_name else "online"
@@ -1047,6 +1050,8 @@ class Args:
     beta_pass: float = 0.5  # (not in quadjax) --controller dial: the noise scale's factor per pass of a control step's --iters passes
     beta_stage: float = 0.9  # (not in quadjax) --controller dial: the noise scale's factor per stage towards the front of the horizon
     temp: float = 0.1       # (not in quadjax) --controller dial: a pass's temperature in standard deviations of its costs; 0 = the configured lam
+    nodes: int = 0          # (not in quadjax) --controller dial: spline nodes the perturbations are drawn at, 2 .. 32; 0 = a draw per stage
+    node_interp: str = "linear"  # (not in quadjax) --controller dial --nodes M: "linear" or "cubic" interpolation between the nodes
 
 
 def main(args: Args):
@@ -1063,7 +1068,8 @@ def main(args: Args):
                                                 update=args.update, iters=args.iters, elite=args.elite or None,
                                                 sigma_period=args.sigma_period, compute_post_cov=args.post_cov and render,
                                                 sigma_adapt=args.sigma_adapt, **take_switches(vars(args)), beta_pass=args.beta_pass,
-                                                beta_stage=args.beta_stage, temp=args.temp if args.temp > 0.0 else None)
+                                                beta_stage=args.beta_stage, temp=args.temp if args.temp > 0.0 else None,
+                                                nodes=args.nodes or None, node_interp=args.node_interp)
     if render:  # the reference's default mode (:798-799); the plan rides along for the sampling controllers
         return render_env(env, controller=controller, control_params=control_params, repeat_times=1, filename=args.name,
                           host_env=args.host_env)
@@ -1094,6 +1100,8 @@ def _cli():
             ap.add_argument("--sigma-adapt", "--sigma_adapt", dest="sigma_adapt", type=float, default=default)
         elif f in ("beta_pass", "beta_stage"):
             ap.add_argument(f"--{f.replace('_', '-')}", f"--{f}", dest=f, type=float, default=default)
+        elif f == "node_interp":
+            ap.add_argument("--node-interp", "--node_interp", dest=f, choices=("linear", "cubic"), default=default)
         else:
             ap.add_argument(f"--{f}", type=type(default), default=default)
     main(Args(**vars(ap.parse_args())))

@@ -488,6 +488,28 @@ int covo_ess_lambda(covo_handle_t h, const float *cost, int32_t n_samples, int32
 int covo_set_step_anneal(covo_handle_t h, const float *sigma_table, int32_t n_pass, float temp, float *rows_out, int32_t n_inst);
 int covo_cost_standardise(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, float lam0, float temp, float *out, void *stream);
 
+/* Spline nodes for the annealed MPPI step: perturbations that are smooth over the horizon, drawn in 4 n_nodes dimensions instead of
+ * 128 (additive to ABI 10: COVO_HAS_STEP_NODES; off by default, and off changes nothing a caller can observe).  With M = n_nodes nodes
+ * spread over the 32 stages, W[h][m] the interpolation weight of node m at stage h and sigma_n[i][m] the schedule over the nodes,
+ *   basis_table = HOST float[n_pass][32][n_nodes], B[i][h][m] = fp32(sigma_n[i][m] W[h][m]), formed by the caller (the Python layer:
+ *              fp64, rounded once).  Pass i samples a[h] = clip(mu_i[h] + sum_m B[i][h][m] e_m), e_m = the m-th normal4 of the stream
+ *              the step without nodes draws its 32 from (same key walk), the sum an ascending-m fmaf chain from 0 per component.
+ *              The mean, the update and every later launch are untouched: only the perturbations are splines.
+ *   schedule   covo_set_step_anneal's table must then hold the stages' MARGINAL standard deviations sigma_e[i][h] =
+ *              fp32(sqrt(sum_m B[i][h][m]^2)): its launch writes a_cov[h] = fp32(sigma_e^2) I_4, which is only the 4 x 4 block diagonal
+ *              of the sampled covariance (B B^T) (x) I_4 of rank 4 n_nodes.  n_nodes = 32 with B[i] = diag(sigma[i]) is the step
+ *              without nodes, bit for bit.
+ * covo_set_step_nodes: the table is copied into device memory the handle owns; NULL turns it off; any change makes the handle
+ *   re-capture its step graphs.  Refused at the step, before any launch: no schedule attached (covo_set_step_anneal with a table);
+ *   n_pass != the schedule's; n_nodes outside [2, 32]; and whatever the schedule refuses.
+ * covo_step_nodes: what is attached -> *n_pass, *n_nodes (both 0: nothing).
+ * covo_noise_nodes_philox: the sampler alone, basis = DEVICE float[32][n_nodes], otherwise covo_noise_blockdiag_philox's arguments. */
+#define COVO_HAS_STEP_NODES 1
+int covo_set_step_nodes(covo_handle_t h, const float *basis_table, int32_t n_pass, int32_t n_nodes);
+int covo_step_nodes(covo_handle_t h, int32_t *n_pass, int32_t *n_nodes);
+int covo_noise_nodes_philox(covo_handle_t h, const float *basis, int32_t n_nodes, const float *mu, uint32_t key0, uint32_t key1,
+                            int64_t sample_offset, int32_t N, float *a_out, void *stream);
+
 /* The elite-set update: exact top-K selection on the device, the cross-entropy method's update rule (additive to ABI 10:
  * COVO_HAS_ELITE_UPDATE; off by default, and off changes nothing a caller can observe).  Per instance and per pass, with the costs
  * c_n as the rollout wrote them, key(n) = (u(c_n) << 32) | n: u is the order-preserving unsigned form of the fp32 bits (sign bit

@@ -31,6 +31,7 @@ name = sys.argv[1]
 # python scripts/eval_seeds.py dial [iters=k] [beta_pass=b] [beta_stage=b] [temp=t | temp=none]: the annealed MPPI controller
 # (controllers/dial.py; defaults: get_controller's iters=1, 0.5 / 0.9 / 0.1); compare with `mppi iters=k`.  With temp every seed's line
 # also carries the share of steps whose last pass fell back to the configured temperature (the temperature log's bit 31 of entry 3)
+# python scripts/eval_seeds.py dial iters=k nodes=M [node_interp=cubic]: the same controller with spline-node perturbations
 rest = sys.argv[2:]
 # the boolean step switches as flags: --refine, --riccati, --riccati-feedback, --riccati-box
 flags = {f"--{s.replace('_', '-')}": s for s, default in STEP_SWITCH_DEFAULTS.items() if isinstance(default, bool)}
@@ -41,9 +42,10 @@ for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_a
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
 FLOATS = ("sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp")
-opts = {k: (None if v.lower() == "none" else float(v) if k in FLOATS else int(v)) for k, v in (arg.split("=") for arg in rest)}
+opts = {k: (None if v.lower() == "none" else v if k == "node_interp" else float(v) if k in FLOATS else int(v))
+        for k, v in (arg.split("=") for arg in rest)}
 switches["plan_hold"] = opts.pop("plan_hold", 1)
-assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"} | ({"beta_pass", "beta_stage", "temp"} if name == "dial" else set()), opts
+assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"} | ({"beta_pass", "beta_stage", "temp", "nodes", "node_interp"} if name == "dial" else set()), opts
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
 ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **switches, **opts)
