@@ -7,7 +7,9 @@ env-batched fused step (lifted by staged=True of BatchedMPPIController / Batched
 check with fused_batched=False; staged is a switch of those two controllers, not a step option), of sample-sharded ranks and of the
 kernel-by-kernel debug path.  A new option is a keyword in those
 signatures, an entry here, and its own attachment block in SamplingCore.__init__ (tests/test_options_abi.py holds the signatures to
-this table).  The C side's counterpart is check_step_attachments (csrc/capi.hip).
+this table).  The C side's counterpart is check_step_attachments (csrc/step_attach.hip, walked on the CPU by
+tests/host/step_attach_check.cpp against tests/golden/step_refusals.txt): there a new attachment adds its setter, its check lines, and
+its cases in that walk with their golden lines.
 
 The step switches (refine, riccati, riccati_feedback, plan_hold, riccati_box) are not step options -- that list is pinned -- but have
 the same home: SamplingCore, CoVOController, MPPIController (no refine), BatchedCoVOController, get_controller and eval_env_batched carry
@@ -74,7 +76,7 @@ STEP_OPTION_DEFAULTS = {
 }
 
 # the step switches, in the order the signatures list them and check_step_switches checks them.  Each is off by default, and off attaches
-# nothing and adds no launch; the C side's counterpart of each check_* is its block of check_step_attachments (csrc/capi.hip)
+# nothing and adds no launch; the C side's counterpart of each check_* is its block of check_step_attachments (csrc/step_attach.hip)
 STEP_SWITCH_DEFAULTS = {
     # (covo-online only) every control step ends with a Newton line search on the mean it has just committed -- the gradient g of the
     # Hessian's objective at that mean (csrc/cost_gradient.hip), the direction d = -Sigma (Sigma g) / c^2 from the step's own Sigma and c,
@@ -391,7 +393,7 @@ def check_ilqr(iters=2, *, riccati_feedback=None, plan_hold=1, disturb_type=None
                what="the iLQR controller", riccati_box=False, **raw):
     """The keywords of the sampling-free controllers (ILQRController, BatchedILQRController, get_controller(env, "ilqr", ...),
     eval_env_batched(controller="ilqr")) -> (iters, riccati_feedback, plan_hold), checked and resolved.  The C side's counterpart is
-    check_ilqr_step (csrc/capi.hip).
+    check_ilqr_step (csrc/step_attach.hip).
 
     One control step is b_0 = shift(a_mean), then iters times the Riccati line search of riccati= (with riccati_feedback: over 33
     candidates, the closed-loop forward pass of DDP / iLQR among them) on the step's one state and raw key, a_mean <- b_iters: nothing is
@@ -518,7 +520,7 @@ def check_dial(iters=4, *, beta_pass=0.5, beta_stage=0.9, temp=0.1, gamma_sigma=
     """The keywords of the annealed MPPI controllers (DialController, BatchedDialController, get_controller(env, "dial", ...),
     eval_env_batched(controller="dial")) -> the Anneal record SamplingCore attaches, or None for the neutral element
     (beta_pass = beta_stage = 1 with temp=None: nothing is attached, the controller is MPPIController(iters=k) launch for launch).  The
-    C side's counterpart is covo_set_step_anneal's block of check_step_attachments (csrc/capi.hip).
+    C side's counterpart is covo_set_step_anneal's block of check_step_attachments (csrc/step_attach.hip).
 
     One control step is iters passes of MPPI's sample-rollout-update on its one state (the key walk of iters=).  Pass i draws
     a = clip(mu_i + sigma[i][h] eps) from the schedule of anneal_schedule (control_params.a_cov on input is ignored; on output it is

@@ -241,8 +241,9 @@ static inline bool covo_box_on(const covo_ctx *h) { return h->box_masks != nullp
 static inline float *covo_diag_target(const covo_ctx *h) { return h->diag_out ? h->diag_out : (h->eplog[COVO_EPLOG_DIAG].log ? h->diag_scratch : nullptr); }
 static inline int covo_diag_capacity(const covo_ctx *h) { return h->diag_out ? h->diag_n : (h->eplog[COVO_EPLOG_DIAG].log ? COVO_MAX_ENVS : 0); }
 
-// ---- the episode logs, one entry per kind: what the setters (capi.hip: set_episode_log), check_episode_logs and launch_episode_rows
-// know about a log.  A new log adds its kind and its entry here (and its place in check_episode_logs' order), nowhere else.
+// ---- the episode logs, one entry per kind: what the setters (step_attach.hip: set_episode_log), check_episode_logs and launch_episode_rows
+// know about a log.  A new log adds its kind and its entry here, its place in check_episode_logs' order (step_attach.hip), and its
+// cases in tests/host/step_attach_check.cpp with their lines of tests/golden/step_refusals.txt.
 struct covo_eprows {
     const float *src;  // [n_inst][width]: the rows the step that has just been enqueued left (the Sigma log: Sigma adapt's rows, or null)
     int width;
@@ -296,6 +297,34 @@ static inline float covo_shared_noise_scale(const covo_env_params &p, bool rollo
 }
 
 void covo_set_error(const char *fmt, ...);
+#define REQUIRE(cond, ...)            \
+    do {                              \
+        if (!(cond)) {                \
+            covo_set_error(__VA_ARGS__); \
+            return COVO_E_BADARG;     \
+        }                             \
+    } while (0)
+#define CHECK_MODEL(p, what)               \
+    do {                                   \
+        const int rc_ = check_model(p, what); \
+        if (rc_) return rc_;               \
+    } while (0)
+
+// step_attach.hip: everything a step checks before it launches, and the setters that touch no device.  Host code only, no HIP call:
+// tests/host/step_attach_check.cpp walks every refusal, their order and every setter's bookkeeping on the CPU against
+// tests/golden/step_refusals.txt.  A new attachment adds three things: its setter (there, or in capi.hip if it makes a HIP call),
+// its lines in check_step_attachments, and its cases in step_attach_check.cpp with their lines of the golden file
+int check_model(const covo_env_params *p, const char *what);
+int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, int mode, const float *a_cov,
+                           const covo_env_params *params, const char *what, float gamma_sigma = 0.0f, bool fused_batch = false);
+int check_ilqr_step(const covo_ctx *h, int n_inst, bool sharded, int derive_keys, const char *what);
+int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, const char *what);
+int check_single_step(const covo_ctx *h, const covo_env_params *params, const covo_step_args *args, const char *what);
+int check_batch_models(const covo_env_params *params, int E, bool env_step, const char *what);
+int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo_batch_mode_args *m, const covo_env_params *params,
+                     bool episode, const char *what, covo_batch_mode_args *norm);
+// what every setter asks of the rows of a buffer it attaches (attached: there is one): "<setter>: n_inst=%d outside (0, COVO_MAX_ENVS]"
+int check_setter_rows(const char *setter, bool attached, int n_inst);
 
 // hipFuncSetAttribute is per DEVICE: a one-time opt-in (dynamic LDS above 64 KB) guarded by a process-wide `static bool` was set on
 // the first device only.  Returns true the first time it is called for the current device with this mask.

@@ -460,7 +460,7 @@ def test_plan_hold_latches_the_last_iteration():
 
 # ------------------------------------------------------------------------------------------ 9: the C side's refusals
 def test_c_refusals_name_their_condition_before_any_launch():
-    """check_ilqr_step (csrc/capi.hip): a handle that lacks the sweep, or carries something of a sampling step, refuses a step in
+    """check_ilqr_step (csrc/step_attach.hip): a handle that lacks the sweep, or carries something of a sampling step, refuses a step in
     COVO_MODE_ILQR with a message that says which -- and the mean it was given is untouched"""
     env = quad_env(task="tracking_zigzag")
     params = env.default_params

@@ -217,3 +217,22 @@ def test_step_graph_state_machines_under_a_sanitizer(tmp_path):
                            "-O1", "-g", "-std=c++17", os.path.join(ROOT, "tests", "host", "step_graph_check.cpp"), "-o", exe])
     out = subprocess.run([exe], capture_output=True, text=True)
     assert out.returncode == 0 and "step_graph_check: ok" in out.stdout, out.stdout + out.stderr
+
+
+def test_step_attachment_checks_under_a_sanitizer(tmp_path):
+    """csrc/step_attach.hip (what a step checks before it launches, and the setters that touch no device) on hand-built handles, built
+    with -fsanitize=address,undefined as a stand-alone program (tests/host/step_attach_check.cpp) with covo_set_error, exchange_ready
+    and batch_small_refusal stubbed.  Its output -- every refusal's rc and full text, the earlier text of every pair of neighbouring
+    refusals arranged together, the clean cases, and every setter's rc / epoch bump / dropped logs / schedule fields per transition
+    -- must equal tests/golden/step_refusals.txt line for line: a reworded or reordered refusal, or a changed epoch rule, fails here."""
+    import difflib
+    exe = str(tmp_path / "step_attach_check")
+    hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
+    subprocess.check_call([hipcc, "--offload-host-only", "-Xarch_host", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                           "-O1", "-g", "-std=c++17", os.path.join(ROOT, "tests", "host", "step_attach_check.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True)
+    assert out.returncode == 0 and "step_attach_check: ok" in out.stdout, out.stdout[-3000:] + out.stderr[-3000:]
+    with open(os.path.join(ROOT, "tests", "golden", "step_refusals.txt")) as f:
+        golden = f.read()
+    diff = "\n".join(difflib.unified_diff(golden.splitlines(), out.stdout.splitlines(), "golden", "walk", lineterm="", n=0))
+    assert out.stdout == golden, diff[:6000]
