@@ -42,6 +42,12 @@ COVO_HAS_STEP_ANNEAL = 1  # the "dial" controller (covo_set_step_anneal, covo_co
 ANNEAL_FIELDS = ("lam_eff", "inv_lam_eff", "std", "n_finite")
 ANNEAL_FALLBACK_BIT = 0x80000000
 COVO_HAS_STEP_NODES = 1  # the annealed controllers' nodes=M (covo_set_step_nodes, covo_noise_nodes_philox): spline-node perturbations
+# sigma_nodes=M of the covo-online controllers (covo_set_step_sigma_nodes, covo_sigma_nodes, covo_noise_factor_philox): Sigma in node space
+COVO_HAS_SIGMA_NODES = 1
+COVO_SIGMA_NODES_MAX = 16
+COVO_SIGMA_NODES_FLOATS = 8  # the side row: {lam_min, lam_max, eig_max, eig_min of Sigma_M, log det Sigma_M, sweeps, flags, d}
+SIGMA_NODES_FIELDS = ("lam_min", "lam_max", "eig_max", "eig_min", "log_det", "sweeps", "flags", "d")
+SIGMA_NODES_NONFINITE, SIGMA_NODES_NO_CONVERGENCE, SIGMA_NODES_PIVOT = 1, 2, 4
 COVO_HAS_ELITE_UPDATE = 1
 COVO_ELITE_FLOATS = 8  # the elite-set update's selector row of one instance (covo_set_step_elite)
 ELITE_FIELDS = ("threshold_cost_word", "threshold_index_word", "cost_min", "cost_kth", "K", "ties")  # words: uint32 bits
@@ -239,6 +245,11 @@ _SIGS = {
     "covo_set_step_nodes": (C.c_int, [_P, C.POINTER(C.c_float), C.c_int32, C.c_int32]),
     "covo_step_nodes": (C.c_int, [_P, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "covo_noise_nodes_philox": (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, C.c_uint32, C.c_int64, C.c_int32, _P, _P]),
+    # Sigma in node space (covo_hip.h: COVO_HAS_SIGMA_NODES)
+    "covo_set_step_sigma_nodes": (C.c_int, [_P, C.POINTER(C.c_double), C.c_int32, _P, C.c_int32]),
+    "covo_step_sigma_nodes": (C.c_int, [_P, C.POINTER(C.c_int32), _P, _P, C.c_int32, _P]),
+    "covo_sigma_nodes": (C.c_int, [_P, _P, C.c_int32, _P, C.c_int32, C.c_float, _P, _P, _P, _P, _P]),
+    "covo_noise_factor_philox": (C.c_int, [_P, _P, C.c_int32, _P, C.c_uint32, C.c_uint32, C.c_int64, C.c_int32, _P, _P]),
     "covo_set_step_elite": (C.c_int, [_P, C.c_int32, _P, C.c_int32]),  # the elite-set update (covo_hip.h: COVO_HAS_ELITE_UPDATE)
     "covo_elite_select": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "covo_set_step_sigma_period": (C.c_int, [_P, C.c_int32]),  # the Sigma period (covo_hip.h: COVO_HAS_SIGMA_PERIOD)

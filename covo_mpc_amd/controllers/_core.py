@@ -22,7 +22,7 @@ import numpy as np
 from .. import _lib
 from .._lib import (COVO_COV_FLOATS, COVO_H, COVO_NA, COVO_PARTIAL_FLOATS, COVO_POS_STATS_DOUBLES, COVO_RANK_RECORD_COV_FLOATS,
                     COVO_RANK_RECORD_FLOATS, check, ptr)
-from ._options import check_kernel_path, check_step_options, check_step_switches, sharded_refusal, take, take_switches
+from ._options import check_kernel_path, check_sigma_nodes, check_step_options, check_step_switches, sharded_refusal, take, take_switches
 
 # the episode logs a core fills: the episode's attribute -> (the core attribute that turns it on, the C call that binds it, whether
 # that attribute's value is the log's extra allocation argument: the fan's K, the iteration log's row width; covo_set_episode_rows' kind
@@ -77,7 +77,8 @@ class SamplingCore:
                  cov_records: bool = False, propagate_nan=None, compute_diag: bool = False, diag_rows: int = 1,
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, refine: bool = False,
-                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False, anneal=None):
+                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False, anneal=None, *,
+                 sigma_nodes=None, node_interp: str = "linear"):
         opts, switches = take(locals()), take_switches(locals())
         import torch
         sharded = False
@@ -87,6 +88,8 @@ class SamplingCore:
         opt = check_step_options(N, "online", sharded=sharded, **opts)
         sw = check_step_switches("a sampling core", mode_what="online", riccati_what="a sampling core", sigma_period=opt.sigma_period,
                                  sharded=sharded, **switches)
+        sn = check_sigma_nodes(sigma_nodes, node_interp, what="online", sigma_period=opt.sigma_period, sigma_adapt=opt.sigma_adapt,
+                               refine=sw.refine, sharded=sharded)
         if anneal is not None and sharded:
             raise NotImplementedError("anneal= on sample-sharded ranks: a rank sees only its shard's costs (covo_set_step_anneal "
                                       "refuses sample-sharded steps)")
@@ -251,6 +254,18 @@ class SamplingCore:
         if sw.riccati_box:
             self.riccati_box_masks = torch.zeros((self._rows, COVO_H), dtype=torch.int32, device=self.device)
             check(self.lib.covo_set_step_riccati_box(self.h, ptr(self.riccati_box_masks), self._rows), "covo_set_step_riccati_box")
+        # covo-online in node space (not a step option either: _options.check_sigma_nodes).  self.sigma_nodes_rows [rows, 8]:
+        # {lam_min, lam_max, eig_max, eig_min, log det Sigma_M, sweeps, flags, d}; self.sigma_node_cov [rows, d, d] float64 is filled by a
+        # copy that sigma_nodes_info enqueues behind the step
+        self.sigma_nodes_M = self.sigma_nodes_rows = self.sigma_node_cov = self.sigma_nodes_weights = None
+        self.sigma_nodes_interp = node_interp
+        if sn is not None:
+            self.sigma_nodes_M, self.sigma_nodes_weights = sn.M, np.ascontiguousarray(sn.weights, dtype=np.float64)
+            self.sigma_nodes_rows = torch.zeros((self._rows, _lib.COVO_SIGMA_NODES_FLOATS), **f32)
+            self.sigma_node_cov = torch.zeros((self._rows, 4 * sn.M, 4 * sn.M), dtype=torch.float64, device=self.device)
+            with torch.cuda.device(self.device):
+                check(self.lib.covo_set_step_sigma_nodes(self.h, self.sigma_nodes_weights.ctypes.data_as(C.POINTER(C.c_double)), sn.M,
+                                                         ptr(self.sigma_nodes_rows), self._rows), "covo_set_step_sigma_nodes")
         # the annealed step (not a step option: the attachment of the controllers of controllers/dial.py; _options.check_dial)
         self.anneal = self.anneal_sigma = self.anneal_rows = self.anneal_node_sigma = None
         self._list_infos()
@@ -408,6 +423,7 @@ class SamplingCore:
             (self.riccati_feedback_rows is not None, self.riccati_feedback_info),
             (self.plan_hold_rows is not None, self.plan_hold_info),
             (self.riccati_box_masks is not None, self.riccati_box_info),
+            (getattr(self, "sigma_nodes_rows", None) is not None, self.sigma_nodes_info),
             (getattr(self, "anneal_rows", None) is not None, self.anneal_info)) if on]
 
     def step_info(self) -> dict:
@@ -1143,6 +1159,54 @@ class SamplingCore:
         assert int(basis.shape[0]) == COVO_H
         check(self.lib.covo_noise_nodes_philox(self.h, ptr(basis), int(basis.shape[1]), ptr(mu), int(key[0]), int(key[1]), self.offset,
                                                self.n_local, ptr(self.a), self.stream()), "covo_noise_nodes_philox")
+        return self.a
+
+    def sigma_nodes_info(self) -> dict:
+        """{"sigma_nodes": M, "sigma_node_cov": float64 [d, d], "sigma_node_rows": [8]} of the last step (instance 0's of a batched
+        one): the rows are a view of self.sigma_nodes_rows; Sigma_M is copied out of the handle's memory by a device-to-device copy
+        enqueued on the step's stream (covo_step_sigma_nodes) -- no sync; {} when the core was built with sigma_nodes=None."""
+        if self.sigma_nodes_rows is None:
+            return {}
+        self.read_sigma_node_cov()
+        return {"sigma_nodes": self.sigma_nodes_M, "sigma_node_cov": self.sigma_node_cov[0], "sigma_node_rows": self.sigma_nodes_rows[0]}
+
+    def read_sigma_node_cov(self, G_out=None):
+        """covo_step_sigma_nodes: every instance's Sigma_M of the last step -> self.sigma_node_cov [rows, d, d] (and, given a float32
+        device tensor [rows, 128, d], the factors G), enqueued on the current stream."""
+        M = C.c_int32(0)
+        check(self.lib.covo_step_sigma_nodes(self.h, C.byref(M), ptr(self.sigma_node_cov), ptr(G_out), self._rows, self.stream()),
+              "covo_step_sigma_nodes")
+        return self.sigma_node_cov
+
+    def sigma_nodes(self, R, M, node_interp="linear", sample_sigma=0.5):
+        """covo_sigma_nodes (the stand-alone node-space Sigma, csrc/sigma_nodes.hip): R float64 device [128, 128] or [B, 128, 128]
+        -> (Sigma_M float64 [B, d, d], G float32 [B, 128, d], Sigma_stage float32 [B, 128, 128], rows float32 [B, 8]), d = 4 M, with
+        W = node_basis(M, node_interp); one matrix in, one matrix out (no leading axis)."""
+        torch = self.torch
+        sn = check_sigma_nodes(M, node_interp)
+        if sn is None:
+            raise ValueError("sigma_nodes: M=None")
+        assert R.is_cuda and R.dtype == torch.float64 and R.is_contiguous() and tuple(R.shape[-2:]) == (COVO_NA, COVO_NA)
+        B = 1 if R.dim() == 2 else int(R.shape[0])
+        d = 4 * sn.M
+        W = torch.from_numpy(np.ascontiguousarray(sn.weights, dtype=np.float64)).to(self.device)
+        SigM = torch.empty((B, d, d), dtype=torch.float64, device=self.device)
+        G = torch.empty((B, COVO_NA, d), dtype=torch.float32, device=self.device)
+        Sig = torch.empty((B, COVO_NA, COVO_NA), dtype=torch.float32, device=self.device)
+        rows = torch.empty((B, _lib.COVO_SIGMA_NODES_FLOATS), dtype=torch.float32, device=self.device)
+        check(self.lib.covo_sigma_nodes(self.h, ptr(R), B, ptr(W), sn.M, float(sample_sigma), ptr(SigM), ptr(G), ptr(Sig), ptr(rows),
+                                        self.stream()), "covo_sigma_nodes")
+        self._sigma_nodes_keep = W  # alive until the stream has consumed it
+        if R.dim() == 2:
+            return SigM[0], G[0], Sig[0], rows[0]
+        return SigM, G, Sig, rows
+
+    def noise_factor(self, G, mu, key):
+        """covo_noise_factor_philox (the stand-alone dense-factor sampler, csrc/sigma_nodes.hip): G float32 device [128, d],
+        d = 8, 12, .., 64 -> self.a = clip(mu + G eps[:, :d]) with eps = randn(key), one ascending-c fmaf chain per entry."""
+        assert G.is_cuda and G.dtype == self.torch.float32 and G.is_contiguous() and G.dim() == 2 and int(G.shape[0]) == COVO_NA
+        check(self.lib.covo_noise_factor_philox(self.h, ptr(G), int(G.shape[1]), ptr(mu), int(key[0]), int(key[1]), self.offset,
+                                                self.n_local, ptr(self.a), self.stream()), "covo_noise_factor_philox")
         return self.a
 
     def noise_blockdiag(self, Ls, mu, eps=None):

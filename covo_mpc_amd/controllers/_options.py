@@ -18,7 +18,8 @@ them as **switches; the iLQR controllers take three of them through check_ilqr. 
 keyword in those signatures, its check_*, and its attachment block in SamplingCore.__init__.
 
 The annealed MPPI controllers (controllers/dial.py, BatchedDialController) are neither: like the iLQR controllers they are controllers of
-their own, checked by check_dial at the end of this file, which hands SamplingCore its one anneal= record.
+their own, checked by check_dial at the end of this file, which hands SamplingCore its one anneal= record.  sigma_nodes= of the covo-online
+controllers (Sigma optimised over the values of M spline nodes) is a keyword of its own too, checked by check_sigma_nodes below it.
 
 Each option is off by default, and off changes nothing.  "info[...]" names what a single controller's __call__ then returns in its
 info dict (SamplingCore.*_info: views of the core's buffers, no sync, no copy); the batched controllers expose the same buffers with
@@ -218,6 +219,7 @@ KERNEL_PATH_REFUSALS = (
     ("compute_diag", False, "compute_diag", "compute_diag is formed by the fused step" + _DEBUG_PATH + "does not produce it"),
     ("refine", False, "refine", "refine follows the fused step" + _DEBUG_PATH + "ends with the softmax mean"),
     ("riccati_on", False, "riccati_on", "riccati follows the fused step" + _DEBUG_PATH + "ends with the softmax mean"),
+    ("sigma_nodes_M", None, "sigma_nodes_M", "sigma_nodes={v} acts in the fused step" + _DEBUG_PATH + "samples from the full 128 x 128 Sigma"),
 )
 
 
@@ -572,3 +574,61 @@ def check_dial(iters=4, *, beta_pass=0.5, beta_stage=0.9, temp=0.1, gamma_sigma=
         return None
     return Anneal(sigma=anneal_schedule(sample_sigma, k, beta_pass, beta_stage), temp=0.0 if temp is None else float(temp),
                   beta_pass=float(beta_pass), beta_stage=float(beta_stage))
+
+
+@dataclass(frozen=True)
+class SigmaNodes:
+    """covo-online in node space, checked (check_sigma_nodes): what SamplingCore's sigma_nodes= keyword resolves to."""
+    M: int              # nodes, 2 .. COVO_SIGMA_NODES_MAX; d = 4 M
+    node_interp: str
+    weights: object     # float64 numpy [32, M]: W[h][m] (node_basis)
+
+
+def check_sigma_nodes(sigma_nodes, node_interp="linear", *, what="online", sigma_period=1, sigma_adapt=0.0, refine=False, sharded=False):
+    """sigma_nodes= of the covo-online controllers (CoVOController(mode="online"), BatchedCoVOController(mode="online"), SamplingCore)
+    -> the SigmaNodes record, or None for off.  Neither a step option nor a step switch -- both tables are pinned --: a keyword of its
+    own, off by default, and off attaches nothing.  The C side's counterpart is covo_set_step_sigma_nodes' block of
+    check_step_attachments (csrc/step_attach.hip).
+
+    = M: every covo-online step (every pass under iters=k) samples from the optimal covariance of the NODE-parameterised problem
+    J(mu + (W (x) I_4) e), W = node_basis(M, node_interp): R_M = P^T R P (d = 4 M), Sigma_M = optimize_sigma(R_M) in d dimensions
+    (log det Sigma_M = 2 d log sample_sigma: sample_sigma is the scale of a node value, as for dial's nodes=M), a = clip(mu + P L_M eps)
+    with eps the first M normal4 of the step's stream -- one launch of one workgroup per instance in the place of the Sigma chain and
+    its finalize launch (csrc/sigma_nodes.hip).  control_params.a_cov is then P Sigma_M P^T, of rank d.  info["sigma_nodes"] (M) /
+    ["sigma_node_cov"] float64 [d, d] / ["sigma_node_rows"] [8] = {lam_min, lam_max of R_M, largest, smallest eigenvalue of Sigma_M,
+    log det Sigma_M, sweeps, flags, d}; flags != 0: that step fell back to sigma^2 I_d (R_M not finite 1, no convergence 2, pivot 4).
+    It goes with compute_diag, compute_plan, compute_fan, update=, ess_min, elite, iters, compute_post_cov and riccati with its switches.
+
+    The objections, in a fixed order: sigma_nodes anything but None or an integer in [2, COVO_SIGMA_NODES_MAX] (ValueError);
+    node_interp anything but "linear" or "cubic" (ValueError, checked as given, also with sigma_nodes=None); `what` other than "online"
+    -- MPPI, covo-offline, dial and ilqr form no Hessian per step (ValueError); sigma_period > 1, then sigma_adapt > 0 -- a reuse step
+    shifts a 128 x 128 factor and there is none --, then refine=True -- its direction needs the full-rank Sigma (ValueError); sharded --
+    sample-sharded ranks (NotImplementedError).  The kernel-by-kernel path (materialize_eps / noise_stream='jax') refuses it at the call
+    (check_kernel_path: NotImplementedError)."""
+    import numbers
+    top = _lib.COVO_SIGMA_NODES_MAX
+    if sigma_nodes is not None and (isinstance(sigma_nodes, bool) or not isinstance(sigma_nodes, numbers.Integral) or
+                                    not 2 <= int(sigma_nodes) <= top):
+        raise ValueError(f"sigma_nodes={sigma_nodes!r} (None, or an integer in [2, {top}]: the spline nodes whose 4 M values the sampling "
+                         "covariance is optimised over)")
+    if node_interp not in NODE_INTERPS:
+        raise ValueError(f"node_interp={node_interp!r} is not one of {NODE_INTERPS}")
+    if sigma_nodes is None:
+        return None
+    M = int(sigma_nodes)
+    if what != "online":
+        raise ValueError(f"sigma_nodes={M} with {what}: the node-space Sigma is derived from the Hessian at the step's mean, which only "
+                         "covo-online forms (CoVOController(mode=\"online\"), BatchedCoVOController(mode=\"online\")); give "
+                         "sigma_nodes=None")
+    if int(sigma_period) > 1:
+        raise ValueError(f"sigma_nodes={M} with sigma_period={sigma_period}: a reuse step shifts the 128 x 128 factor of the previous "
+                         "step, and a node-space step leaves none; give sigma_period=1 or sigma_nodes=None")
+    if float(sigma_adapt) > 0.0:
+        raise ValueError(f"sigma_nodes={M} with sigma_adapt={sigma_adapt}: it belongs to the reuse steps of a Sigma period; give "
+                         "sigma_adapt=0 or sigma_nodes=None")
+    if refine is True:
+        raise ValueError(f"sigma_nodes={M} with refine=True: the Newton refinement's direction needs the full-rank Sigma, and this one "
+                         f"has rank {4 * M}; give refine=False (riccati=True needs no Sigma) or sigma_nodes=None")
+    if sharded:
+        raise NotImplementedError(f"sigma_nodes={M} on sample-sharded ranks: covo_set_step_sigma_nodes refuses sample-sharded steps")
+    return SigmaNodes(M=M, node_interp=node_interp, weights=node_basis(M, node_interp))

@@ -22,14 +22,14 @@ from .. import _lib
 from .._lib import COVO_H, COVO_NA, check
 from ..dynamics.dataclass import as_device_state
 from ._core import SamplingCore
-from ._options import check_step_options, check_step_switches, take, take_switches
+from ._options import check_sigma_nodes, check_step_options, check_step_switches, take, take_switches
 
 # (controller attribute, core attribute) of the attachment buffers the batched controllers hand out
 CORE_BUFFERS = (("diag", "diag"), ("plan", "plan"), ("fan", "fan"), ("arbiter", "arbiter"), ("lam_eff", "lam_eff"), ("elite", "elite_rows"),
                 ("iter_cost_min", "iter_cost_min"), ("post_cov", "post_cov"), ("post_aux", "post_aux"),
                 ("sigma_adapt_rows", "sigma_adapt_rows"), ("refine", "refine_rows"), ("riccati", "riccati_rows"),
                 ("riccati_feedback", "riccati_feedback_rows"), ("plan_hold_rows", "plan_hold_rows"),
-                ("riccati_box", "riccati_box_masks"))
+                ("riccati_box", "riccati_box_masks"), ("sigma_nodes_rows", "sigma_nodes_rows"))
 
 
 class BatchedCoVOController:
@@ -42,7 +42,7 @@ class BatchedCoVOController:
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1, elite=None,
                  sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0, staged: bool = False,
                  refine: bool = False, riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1,
-                 riccati_box: bool = False):
+                 riccati_box: bool = False, sigma_nodes=None, node_interp: str = "linear"):
         opts, switches = take(locals()), take_switches(locals())
         moded = self.MODE is not None or mode != "online"  # the MPPI / covo-offline step
         if staged and not moded:
@@ -57,6 +57,8 @@ class BatchedCoVOController:
                 "the env-batched MPPI controller" if self.MODE is not None else f"the env-batched covo-{mode} controller")
         check_step_options(N, what, fused_batched=fused, **opts)
         check_step_switches(what, sigma_period=sigma_period, disturb_type=getattr(env, "disturb_type", None), **switches)
+        # sigma_nodes=M (covo-online only; _options.check_sigma_nodes): .sigma_nodes_rows [E, 8] after a call
+        check_sigma_nodes(sigma_nodes, node_interp, what=what, sigma_period=sigma_period, sigma_adapt=sigma_adapt, refine=refine)
         if self.MODE is not None:
             self.mode = self.MODE
         elif mode in ("online", "offline"):
@@ -73,7 +75,7 @@ class BatchedCoVOController:
         # one call advances all instances: the ~56 launches are worth a graph (same GPU time as eager, 40 us instead of
         # 150-270 us of host time per call)
         self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
-                                 diag_rows=int(n_envs), **switches, **opts)
+                                 diag_rows=int(n_envs), **switches, **opts, sigma_nodes=sigma_nodes, node_interp=node_interp)
         if moded:
             check(self.core.lib.covo_set_step_batched_staged(self.core.h, int(self.staged)), "covo_set_step_batched_staged")
         # after a call, row e of each of the core's attachment buffers holds instance e's result of that step; None for what is off

@@ -23,7 +23,14 @@ from ..dynamics.dataclass import as_device_state
 from .base import BaseController
 from .pid import PIDController, PIDParams
 from ._core import SamplingCore
-from ._options import check_step_options, check_step_switches, take, take_switches
+from ._options import check_sigma_nodes, check_step_options, check_step_switches, take, take_switches
+
+
+def _is_sharded(process_group) -> bool:
+    if process_group is None:
+        return False
+    import torch.distributed as dist
+    return dist.get_world_size(process_group) > 1
 
 
 @dataclass(frozen=True)
@@ -50,12 +57,15 @@ class CoVOController(BaseController):
                  compute_plan: bool = False, ess_min=None, compute_fan=None, update: str = "softmax", iters: int = 1,
                  elite=None, sigma_period: int = 1, compute_post_cov: bool = False, sigma_adapt: float = 0.0,
                  refine: bool = False, riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1,
-                 riccati_box: bool = False) -> None:
+                 riccati_box: bool = False, sigma_nodes=None, node_interp: str = "linear") -> None:
         opts, switches = take(locals()), take_switches(locals())
         what = mode if mode in ("online", "offline") else "online"
         check_step_options(N, what, **opts)  # ValueError before anything is built
         check_step_switches(f"covo-{what}", mode_what="online" if what == "online" else "covo-offline", sigma_period=sigma_period,
                             disturb_type=getattr(env, "disturb_type", None), **switches)
+        # sigma_nodes=M (covo-online only; _options.check_sigma_nodes): Sigma is optimised over the 4 M values of M spline nodes
+        check_sigma_nodes(sigma_nodes, node_interp, what="online" if what == "online" else "covo-offline", sigma_period=sigma_period,
+                          sigma_adapt=sigma_adapt, refine=refine, sharded=_is_sharded(process_group))
         super().__init__(env, control_params)
         self.N, self.H, self.lam = N, H, lam
         self.materialize_eps = False  # True: epsilon is written to HBM and the kernels are called one by one (parity)
@@ -74,7 +84,8 @@ class CoVOController(BaseController):
         self.mode = mode
         # propagate_nan: jnp.clip's NaN semantics in the sampling clip (covo.py:224) -- see SamplingCore
         self.core = SamplingCore(N, H, lam, control_params.discount, device=device, process_group=process_group,
-                                 compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan, **switches, **opts)
+                                 compute_info=compute_info, trust_clipped=True, propagate_nan=propagate_nan, **switches, **opts,
+                                 sigma_nodes=sigma_nodes, node_interp=node_interp)
 
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start (covo-online; covo-offline's reset builds its table): with a Sigma period the schedule restarts -- the first

@@ -150,6 +150,9 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->lam_own));
     DESTROY(hipFree(h->anneal_table));
     DESTROY(hipFree(h->nodes_table));
+    DESTROY(hipFree(h->sn_W));
+    DESTROY(hipFree(h->sn_SigmaM));
+    DESTROY(hipFree(h->sn_G));
     DESTROY(hipFree(h->elite_own));
     DESTROY(hipFree(h->ws_stats));
     DESTROY(hipFree(h->ws_sigma));
@@ -748,6 +751,82 @@ int covo_noise_nodes_philox(covo_handle_t h, const float *basis, int32_t n_nodes
     d.key[1] = key1;
     d.sample_offset = sample_offset;
     return launch_noise_nodes(d, basis, 0, n_nodes, (hipStream_t)stream);
+}
+
+// ---- covo-online in spline-node space (sigma_nodes.hip).  As covo_set_step_nodes: the captured step graphs bake in the two launches
+// and read W, Sigma_M and G in the handle's own device memory, so any change bumps the epoch and W is rewritten only after every launch
+// that may still read it has finished.  What the step refuses next to it is checked at the step (check_step_attachments)
+int covo_set_step_sigma_nodes(covo_handle_t h, const double *W, int32_t M, float *rows, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_sigma_nodes: null handle");
+    if (W == nullptr) {
+        if (covo_sigma_nodes_on(h)) ++h->opt.epoch;
+        h->sn_M = h->sn_n = 0;
+        h->sn_rows = nullptr;
+        return 0;
+    }
+    REQUIRE(M >= 2 && M <= COVO_SIGMA_NODES_MAX, "covo_set_step_sigma_nodes: M=%d outside [2, %d]", M, COVO_SIGMA_NODES_MAX);
+    REQUIRE(rows != nullptr && n_inst > 0 && n_inst <= COVO_MAX_ENVS, "covo_set_step_sigma_nodes: null rows or n_inst=%d outside (0, %d]",
+            n_inst, COVO_MAX_ENVS);
+    for (int i = 0; i < COVO_H * M; ++i)
+        REQUIRE(__builtin_fabs(W[i]) < __builtin_inf(), "covo_set_step_sigma_nodes: W[%d][%d]=%g is not a finite number", i / M, i % M, W[i]);
+    CHECK_DEVICE(h, "covo_set_step_sigma_nodes");
+    COVO_CHECK_HIP(hipDeviceSynchronize());  // (a setter, off the per-step path) no step in flight reads the old weights
+    if (h->sn_W == nullptr) {
+        COVO_CHECK_HIP(hipMalloc(&h->sn_W, (size_t)COVO_H * COVO_SIGMA_NODES_MAX * sizeof(double)));
+        COVO_CHECK_HIP(hipMalloc(&h->sn_SigmaM, (size_t)COVO_MAX_ENVS * 64 * 64 * sizeof(double)));
+        COVO_CHECK_HIP(hipMalloc(&h->sn_G, (size_t)COVO_MAX_ENVS * COVO_NA * 64 * sizeof(float)));
+    }
+    COVO_CHECK_HIP(hipMemcpy(h->sn_W, W, (size_t)COVO_H * M * sizeof(double), hipMemcpyHostToDevice));
+    ++h->opt.epoch;
+    h->sn_M = M;
+    h->sn_rows = rows;
+    h->sn_n = n_inst;
+    return 0;
+}
+
+int covo_step_sigma_nodes(covo_handle_t h, int32_t *M, double *SigmaM_out, float *G_out, int32_t n_inst, void *stream)
+{
+    REQUIRE(h, "covo_step_sigma_nodes: null handle");
+    REQUIRE(M, "covo_step_sigma_nodes: bad argument");
+    *M = h->sn_M;
+    if (SigmaM_out == nullptr && G_out == nullptr) return 0;
+    REQUIRE(covo_sigma_nodes_on(h), "covo_step_sigma_nodes: nothing attached (covo_set_step_sigma_nodes)");
+    REQUIRE(n_inst > 0 && n_inst <= h->sn_n, "covo_step_sigma_nodes: n_inst=%d outside (0, %d]", n_inst, h->sn_n);
+    const size_t d = 4 * (size_t)h->sn_M;
+    if (SigmaM_out)
+        COVO_CHECK_HIP(hipMemcpyAsync(SigmaM_out, h->sn_SigmaM, (size_t)n_inst * d * d * sizeof(double), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream));
+    if (G_out)
+        COVO_CHECK_HIP(hipMemcpyAsync(G_out, h->sn_G, (size_t)n_inst * COVO_NA * d * sizeof(float), hipMemcpyDeviceToDevice,
+                                      (hipStream_t)stream));
+    return 0;
+}
+
+int covo_sigma_nodes(covo_handle_t h, const double *R, int32_t batch, const double *W_dev, int32_t M, float sample_sigma,
+                     double *SigmaM_out, float *G_out, float *Sigma_out, float *rows_out, void *stream)
+{
+    REQUIRE(h, "covo_sigma_nodes: null handle");
+    CHECK_DEVICE(h, "covo_sigma_nodes");
+    REQUIRE(M >= 2 && M <= COVO_SIGMA_NODES_MAX, "covo_sigma_nodes: M=%d outside [2, %d]", M, COVO_SIGMA_NODES_MAX);
+    REQUIRE(R && W_dev && SigmaM_out && G_out && batch > 0 && batch <= 65535, "covo_sigma_nodes: bad argument");
+    REQUIRE(sample_sigma > 0.0f && sample_sigma < __builtin_inff(), "covo_sigma_nodes: sample_sigma=%g", (double)sample_sigma);
+    return launch_sigma_nodes(R, batch, W_dev, M, sample_sigma, SigmaM_out, G_out, Sigma_out, rows_out, (hipStream_t)stream);
+}
+
+int covo_noise_factor_philox(covo_handle_t h, const float *G, int32_t d, const float *mu, uint32_t key0, uint32_t key1,
+                             int64_t sample_offset, int32_t N, float *a_out, void *stream)
+{
+    REQUIRE(h, "covo_noise_factor_philox: null handle");
+    CHECK_DEVICE(h, "covo_noise_factor_philox");
+    REQUIRE(G && mu && a_out && N > 0, "covo_noise_factor_philox: bad argument");
+    REQUIRE(d >= 8 && d <= 4 * COVO_SIGMA_NODES_MAX && (d & 3) == 0, "covo_noise_factor_philox: d=%d is no multiple of 4 in [8, %d]", d,
+            4 * COVO_SIGMA_NODES_MAX);
+    NoiseDesc nd = noise_desc(h, nullptr, mu, N, a_out);
+    nd.key[0] = key0;
+    nd.key[1] = key1;
+    nd.sample_offset = sample_offset;
+    return launch_noise_factor(nd, G, d / 4, (hipStream_t)stream);
 }
 
 int covo_elite_select(covo_handle_t h, const float *cost, int32_t n_samples, int32_t n_inst, int32_t K, float *out, void *stream)

@@ -80,6 +80,13 @@ struct covo_ctx {
     float *nodes_table;       // [nodes_passes][H][nodes_M] the handle's own: B[i][h][m] of pass i (uploaded by the setter)
     int nodes_passes;         // the passes the table was set for: the schedule's must equal it
     int nodes_M;              // nodes per pass, 2 .. H
+    // covo-online in spline-node space (covo_set_step_sigma_nodes; sigma_nodes.hip); sn_M == 0: off
+    double *sn_W;             // [H][sn_M] the handle's own: the interpolation weights (uploaded by the setter)
+    int sn_M;                 // nodes, 2 .. COVO_SIGMA_NODES_MAX: d = 4 sn_M
+    float *sn_rows;           // caller's [sn_n][COVO_SIGMA_NODES_FLOATS]: instance e's side row of every step
+    int sn_n;
+    double *sn_SigmaM;        // [COVO_MAX_ENVS][64][64] the handle's own: instance e's Sigma_M [d][d] of the last step, dense at e d d
+    float *sn_G;              // [COVO_MAX_ENVS][128][64] the handle's own: instance e's factor G [128][d], dense at e 128 d
     // the elite-set update (covo_set_step_elite; elite_select.hip, reduce_elite.hip); elite_K == 0: off
     int elite_K;              // elites per instance and pass
     float *elite_out;         // caller's [elite_n][COVO_ELITE_FLOATS]: instance e's selector row of every step; null: elite_own
@@ -217,6 +224,7 @@ static inline bool covo_ess_on(const covo_ctx *h) { return h->ess_min > 0.0f; }
 static inline bool covo_anneal_on(const covo_ctx *h) { return h->anneal_passes > 0; }
 static inline bool covo_anneal_sched_on(const covo_ctx *h) { return h->anneal_passes > 0 && h->anneal_sched != 0; }
 static inline bool covo_nodes_on(const covo_ctx *h) { return h->nodes_M > 0; }
+static inline bool covo_sigma_nodes_on(const covo_ctx *h) { return h->sn_M > 0; }
 static inline bool covo_anneal_temp_on(const covo_ctx *h) { return h->anneal_passes > 0 && h->anneal_temp > 0.0f; }
 static inline float *covo_lam_target(const covo_ctx *h)
 {
@@ -453,6 +461,13 @@ int launch_noise_blockdiag(const NoiseDesc &d, hipStream_t s);
 // noise_nodes.hip: a = clip(mu + B eps_nodes) with B = slice `pass` of table [.][H][n_nodes] and eps_nodes the first n_nodes normal4
 // of the block-diagonal kernel's stream (in-kernel draw only; d.L / eps_tiled / state_for_time / cov are not read)
 int launch_noise_nodes(const NoiseDesc &d, const float *table, int pass, int n_nodes, hipStream_t s);
+// sigma_nodes.hip: per matrix of R [batch][128][128], Sigma_M = optimize_sigma(P^T sym(R) P) double [batch][d][d] (P = W (x) I_4,
+// W_dev device [32][M], d = 4 M), G = fp32(P chol(Sigma_M)) [batch][128][d], Sigma = fp32(P Sigma_M P^T) [batch][128][128] (nullable)
+// and the side rows [batch][COVO_SIGMA_NODES_FLOATS] (nullable), one workgroup each; launch_noise_factor: a = clip(mu + G eps) with
+// eps the first M normal4 of the block-diagonal kernel's stream (in-kernel draw only; batch > 1: G, mu, dyn, a per instance)
+int launch_sigma_nodes(const double *R, int batch, const double *W_dev, int M, float sample_sigma, double *SigmaM, float *G, float *Sigma,
+                       float *rows, hipStream_t s);
+int launch_noise_factor(const NoiseDesc &d, const float *G, int M, hipStream_t s);
 static inline bool covo_propagate_nan(const covo_ctx *h) { return (h->cfg.flags & COVO_FLAG_PROPAGATE_NAN) != 0; }
 // how the rollout treats the action stripes it reads (RolloutArgs::clip)
 enum RolloutClip {

@@ -227,6 +227,15 @@ static int enqueue_online_chain(covo_ctx *h, const OnlineChainView &v, hipStream
     hd.stats = stats ? &so : nullptr;
     hd.status_dev = h->status_dev;
     if ((M & 2) && (rc = launch_hessian(hd, h->ws_hess, s, dbg))) return rc;  // :134-185
+    if (covo_sigma_nodes_on(h)) {
+        // covo_set_step_sigma_nodes: Sigma is the optimal covariance of the node-parameterised problem -- ONE launch of one workgroup
+        // per instance (projection, eigendecomposition, factor, stage-space factor G, a_cov = P Sigma_M P^T; sigma_nodes.hip) in the
+        // place of the Sigma chain, and the dense-factor sampler in the place of the GEMM: no finalize launch, no epsilon drawn
+        // ahead, nothing deferred or streamed
+        if ((M & 4) && (rc = launch_sigma_nodes(v.R, v.E, h->sn_W, h->sn_M, v.sample_sigma, h->sn_SigmaM, h->sn_G, v.Sigma, h->sn_rows, s)))
+            return rc;
+        return (M & 8) ? launch_noise_factor(nd, h->sn_G, h->sn_M, s) : 0;
+    }
     const bool finalize = dbg.sigma_stages >= 4;
     // epsilon needs only the act keys: it is drawn under the chain's finalize launch (one workgroup per matrix factors), the GEMM loads
     // it -- the in-kernel Philox costs the batched GEMM ~9 us, its matrix pipe hides no vector work

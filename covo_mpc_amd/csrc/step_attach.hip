@@ -192,6 +192,27 @@ int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sh
                 "n_pass=%d: the basis table has one slice per pass; set both to the same count", what, h->nodes_passes, h->anneal_passes);
         REQUIRE(h->nodes_M >= 2 && h->nodes_M <= COVO_H, "%s: n_nodes=%d (covo_set_step_nodes) outside [2, %d]", what, h->nodes_M, COVO_H);
     }
+    if (covo_sigma_nodes_on(h)) {  // covo-online in node space: its one launch stands in the place of the Sigma chain of EVERY step
+        REQUIRE(h->sn_M >= 2 && h->sn_M <= COVO_SIGMA_NODES_MAX, "%s: M=%d (covo_set_step_sigma_nodes) outside [2, %d]", what, h->sn_M,
+                COVO_SIGMA_NODES_MAX);
+        REQUIRE(covo_sigma_period(h) == 1,
+                "%s: Sigma in node space (covo_set_step_sigma_nodes, M=%d) together with a Sigma period (covo_set_step_sigma_period, "
+                "period=%d): a reuse step shifts a 128 x 128 factor, and there is none; set period = 1 or turn it off (a null W)", what,
+                h->sn_M, covo_sigma_period(h));
+        REQUIRE(!covo_sigma_adapt_on(h),
+                "%s: Sigma in node space (covo_set_step_sigma_nodes, M=%d) together with Sigma adapt (covo_set_step_sigma_adapt, gamma=%g): "
+                "it belongs to the reuse steps of a Sigma period; turn one of them off", what, h->sn_M, (double)h->adapt_gamma);
+        REQUIRE(!covo_refine_on(h),
+                "%s: Sigma in node space (covo_set_step_sigma_nodes, M=%d) together with the Newton refinement (covo_set_step_refine): its "
+                "direction needs the full-rank Sigma, and this one has rank %d; detach one of them", what, h->sn_M, 4 * h->sn_M);
+        REQUIRE(mode == COVO_MODE_COVO_ONLINE,
+                "%s: Sigma in node space (covo_set_step_sigma_nodes, M=%d) belongs to covo-online steps; this step's mode is %d, which "
+                "forms no Hessian per step; turn it off (a null W)", what, h->sn_M, mode);
+        REQUIRE(!sharded,
+                "%s: Sigma in node space (covo_set_step_sigma_nodes, M=%d) is not available for sample-sharded steps (partial_out != "
+                "NULL); turn it off (a null W)", what, h->sn_M);
+        REQUIRE(n_inst <= h->sn_n, "%s: %d instances, the side rows (covo_set_step_sigma_nodes) have n_inst=%d", what, n_inst, h->sn_n);
+    }
     if (covo_anneal_on(h)) {  // the annealed step: MPPI's block-diagonal draw under a per-pass table, weights on standardised costs
         REQUIRE(mode == COVO_MODE_MPPI,
                 "%s: the annealed step (covo_set_step_anneal) belongs to MPPI steps (COVO_MODE_MPPI): its schedule writes the 4 x 4 block "

@@ -510,6 +510,44 @@ int covo_step_nodes(covo_handle_t h, int32_t *n_pass, int32_t *n_nodes);
 int covo_noise_nodes_philox(covo_handle_t h, const float *basis, int32_t n_nodes, const float *mu, uint32_t key0, uint32_t key1,
                             int64_t sample_offset, int32_t N, float *a_out, void *stream);
 
+/* covo-online in spline-node space: the optimal covariance of the node-parameterised problem (additive to ABI 10:
+ * COVO_HAS_SIGMA_NODES; off by default, and off changes nothing a caller can observe).  With M nodes, W = double[32][M] their
+ * interpolation weights (rows sum to 1), P = W (x) I_4 [128][d] and d = 4 M <= 64, a covo-online step (every pass of an iterated one)
+ * forms, per instance and in ONE launch of one workgroup (csrc/sigma_nodes.hip), from the Hessian R at its shifted mean
+ *   R_M     = P^T ((R + R^T) / 2) P                        fp64 [d][d], symmetric bit for bit
+ *   Sigma_M = optimize_sigma(R_M) with element_num = d     eigenpairs (lam, U), o = lam - lam_min + 1e-2,
+ *             log_s = ((4 d log sigma + sum log o) / d) / 2 - (log o) / 2, Sigma_M = U diag(exp(log_s)) U^T: log det Sigma_M = 2 d log sigma
+ *   L_M     = the lower Cholesky factor of Sigma_M (fp64),  G = fp32(P L_M) float[128][d], summed in fp64 and rounded once
+ *   a_cov   = fp32(P Sigma_M P^T) float[128][128], of rank d, symmetric bit for bit
+ * and samples a[h][n][i] = clip(mu[h][i] + acc), acc ONE ascending-c fmaf chain from 0 over G[(h, i)][c] eps_c, c < d, eps_c component
+ * c mod 4 of the (c div 4)-th normal4 of the stream covo_noise_blockdiag_philox draws its 32 from (same key walk); every launch shape
+ * gives the same bits.  The Sigma chain, its finalize launch and the noise GEMM do not run in such a step; everything behind the
+ * sampler is untouched.  Fallback, decided on the device and reported in the side row, never an error: an R_M that is not finite, a
+ * Jacobi that has not converged at its sweep limit, a factor with a non-positive pivot -- that instance samples from sigma^2 I_d.
+ * rows: DEVICE float[n_inst][COVO_SIGMA_NODES_FLOATS] = {lam_min, lam_max of R_M, largest, smallest eigenvalue of Sigma_M,
+ *   log det Sigma_M, sweeps, flags (COVO_SIGMA_NODES_*), d}, instance e's row of every step (lam_* are NaN when R_M was not finite).
+ * covo_set_step_sigma_nodes: W is copied into device memory the handle owns; NULL turns it off; any change makes the handle
+ *   re-capture its step graphs.  Refused: M outside [2, COVO_SIGMA_NODES_MAX], a W entry that is not finite, n_inst outside
+ *   (0, COVO_MAX_ENVS]; at the step, before any launch: a mode other than covo-online, a Sigma period > 1, Sigma adapt, the Newton
+ *   refinement (its direction needs the full-rank Sigma), a sample-sharded step, more instances than rows.
+ * covo_step_sigma_nodes: what is attached -> *M (0: nothing); SigmaM_out / G_out (DEVICE, nullable): copies of the n_inst instances'
+ *   Sigma_M double[n_inst][d][d] and G float[n_inst][128][d] of the last step, enqueued on `stream`.
+ * covo_sigma_nodes: the first launch alone on the caller's R = DEVICE double[batch][128][128] and W_dev = DEVICE double[32][M].
+ * covo_noise_factor_philox: the sampler alone, G = DEVICE float[128][d], d = 8, 12, .., 64, otherwise covo_noise_nodes_philox's
+ *   arguments. */
+#define COVO_HAS_SIGMA_NODES 1
+#define COVO_SIGMA_NODES_MAX 16
+#define COVO_SIGMA_NODES_FLOATS 8
+#define COVO_SIGMA_NODES_NONFINITE 1
+#define COVO_SIGMA_NODES_NO_CONVERGENCE 2
+#define COVO_SIGMA_NODES_PIVOT 4
+int covo_set_step_sigma_nodes(covo_handle_t h, const double *W, int32_t M, float *rows, int32_t n_inst);
+int covo_step_sigma_nodes(covo_handle_t h, int32_t *M, double *SigmaM_out, float *G_out, int32_t n_inst, void *stream);
+int covo_sigma_nodes(covo_handle_t h, const double *R, int32_t batch, const double *W_dev, int32_t M, float sample_sigma,
+                     double *SigmaM_out, float *G_out, float *Sigma_out, float *rows_out, void *stream);
+int covo_noise_factor_philox(covo_handle_t h, const float *G, int32_t d, const float *mu, uint32_t key0, uint32_t key1,
+                             int64_t sample_offset, int32_t N, float *a_out, void *stream);
+
 /* The elite-set update: exact top-K selection on the device, the cross-entropy method's update rule (additive to ABI 10:
  * COVO_HAS_ELITE_UPDATE; off by default, and off changes nothing a caller can observe).  Per instance and per pass, with the costs
  * c_n as the rollout wrote them, key(n) = (u(c_n) << 32) | n: u is the order-preserving unsigned form of the fp32 bits (sign bit
