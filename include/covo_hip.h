@@ -30,7 +30,9 @@
  *            kernel reads one contiguous 1 KiB stripe per step.
  *   cost     float[N]
  *   partial  float[COVO_PARTIAL_FLOATS] = {m, s, v[128], pad}: online-softmax
- *            record of one shard (m = min cost, s = sum w, v = sum w*a)
+ *            record of one shard (m = min cost, s = sum w, v = sum w*a).  The two
+ *            pad floats only round the record up to 16 bytes: no entry writes them
+ *            or lets them reach a result; they keep what the caller's buffer held.
  */
 #ifndef COVO_HIP_H
 #define COVO_HIP_H
@@ -260,7 +262,7 @@ int covo_pos_info(covo_handle_t h, const double *pos_stats, const float *state, 
  * (controllers/covo.py:266-272 before normalisation): two-stage wavefront reduction.
  * groupmin (nullable): the per-64-sample minima covo_rollout_cost left for exactly this
  *   cost/N (saves one pass over cost); recomputed internally when null.
- * partial_out: float[COVO_PARTIAL_FLOATS]. */
+ * partial_out: float[COVO_PARTIAL_FLOATS]; floats 130 and 131 (the pad) are not written. */
 int covo_softmax_reduce(covo_handle_t h, const float *cost, const float *a, int32_t N, const float *groupmin,
                         float *partial_out, void *stream);
 
@@ -1101,7 +1103,8 @@ typedef struct covo_step_args {
     const float *L_table;    /* offline: float[n_table][128][128] lower Cholesky factors of a_cov_offline */
     float *a;                /* work: float[H][n_samples][4] */
     float *cost;             /* work: float[n_samples] */
-    float *groupmin;         /* work: float[ceil(n_samples/64)] */
+    float *groupmin;         /* work: float[ceil(n_samples/64)]; scratch of the staged rollout -- a step may leave it unwritten (the
+                              *    fused launches and the record-emitting rollout keep the minima in their records) */
     double *pos_stats;       /* nullable, as in covo_rollout_cost */
     float *partial_out;      /* nullable: this shard's record instead of finishing locally -- float[COVO_PARTIAL_FLOATS], or, MPPI with
                               *    gamma_sigma != 0, float[COVO_PARTIAL_FLOATS + COVO_COV_FLOATS] (with the second moments) */
@@ -1152,7 +1155,7 @@ typedef struct covo_batch_args {
     float *a_cov;            /* float[n_envs][128][128] Sigma out (nullable) */
     float *a;                /* work: float[n_envs][H][n_samples][4] */
     float *cost;             /* work: float[n_envs][n_samples] */
-    float *groupmin;         /* work: float[n_envs][ceil(n_samples/64)] */
+    float *groupmin;         /* work: float[n_envs][ceil(n_samples/64)]; scratch, as in covo_step_args: a step may leave it unwritten */
     float gamma_mean;
     float sample_sigma;
 } covo_batch_args;
