@@ -94,6 +94,8 @@ COVO_HAS_ILQR = 1  # the "ilqr" controller (COVO_MODE_ILQR, covo_set_step_ilqr):
 # a summary row: {row_0.cost_base, row_{k-1}.cost_chosen, bits(int32 iterations with choice != 0), bits(int32 first j with choice 0; k:
 # none), bits(int32 iterations with choice > 16), bits(OR of the rows' flag words), |g|_2 of the last iteration, 0}
 COVO_ILQR_FLOATS = 8
+COVO_HAS_CMA = 1  # the "cma" controller (COVO_MODE_CMA, covo_set_step_cma): a learned full covariance with step-size control
+COVO_CMA_FLOATS = 8  # its row of one instance: {s, log s, |p|, |z|, mu_eff, c_sigma, d_sigma, flags}
 ILQR_FIELDS = ("cost_first", "cost", "moved", "fixed_at", "closed", "flags", "grad_norm")
 # riccati_box= on top of riccati= (covo_set_step_riccati_box, covo_riccati_box, covo_riccati_refine_box): the sweep's stages solve the
 # box QP on -1 <= clip(b) + du <= 1.  A mask word per stage: bits 0-3 coordinate i clamped at the lower bound, bits 4-7 at the upper
@@ -165,6 +167,7 @@ DISTURB_KEYS_SHARED, DISTURB_KEYS_HESSIAN, DISTURB_KEYS_NOMINAL = 0, 1, 2
 COVO_MAX_ENVS = 64
 MODE_MPPI, MODE_COVO_ONLINE, MODE_COVO_OFFLINE = 0, 1, 2
 MODE_ILQR = 3
+MODE_CMA = 5  # the "cma" controller (COVO_MODE_CMA; 4 stays an invalid mode)
 COVO_FLAG_NO_GRAPH = 2
 COVO_FLAG_SHARED_DEVICE = 4
 COVO_FLAG_PROPAGATE_NAN = 8
@@ -297,6 +300,11 @@ _SIGS = {
     "covo_debug_plan_latch": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _P, _P]),
     # the iLQR controller's per-iteration logs (covo_hip.h: COVO_HAS_ILQR)
     "covo_set_step_ilqr": (C.c_int, [_P, _P, _P, _P, C.c_int32]),
+    # the CMA controller (covo_hip.h: COVO_HAS_CMA)
+    "covo_set_step_cma": (C.c_int, [_P, C.c_float, C.c_int32, C.c_float, C.c_float, C.c_float, _P, _P, C.c_int32]),
+    "covo_cma_reset": (C.c_int, [_P]),
+    "covo_cma_path": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
+                                C.c_float, _P, _P, _P, _P, _P, _P]),
     "covo_debug_ilqr_costs": (C.c_int, [_P, _P, C.c_int32]),
     # the Riccati box (covo_hip.h: COVO_HAS_RICCATI_BOX)
     "covo_riccati_box": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P,

@@ -424,7 +424,8 @@ class SamplingCore:
             (self.plan_hold_rows is not None, self.plan_hold_info),
             (self.riccati_box_masks is not None, self.riccati_box_info),
             (getattr(self, "sigma_nodes_rows", None) is not None, self.sigma_nodes_info),
-            (getattr(self, "anneal_rows", None) is not None, self.anneal_info)) if on]
+            (getattr(self, "anneal_rows", None) is not None, self.anneal_info),
+            (getattr(self, "cma_rows", None) is not None, self.cma_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -668,6 +669,64 @@ class SamplingCore:
                       "covo_set_step_nodes")
                 self.anneal_node_sigma = torch.from_numpy(np.asarray(anneal.node_sigma, dtype=np.float32)).to(self.device)
         self._list_infos()
+
+    def attach_cma(self, cma):
+        """The CMA controller's attachment (covo_set_step_cma; cma: the record _options.check_cma returns): self.cma_rows [rows, 8] --
+        instance e's {s, log s, |p|, |z|, mu_eff, c_sigma, d_sigma, flags} of every step, neutral {1, 0, ...} after the first step of an
+        episode -- and self.cma_p [rows, 128] float64, the evolution paths, which the handle keeps there between steps.  The core
+        must have been built with compute_post_cov and compute_diag: the next step reads what they leave."""
+        torch = self.torch
+        if self.post_cov is None or self.diag is None:
+            raise ValueError("attach_cma: the core needs compute_post_cov=True and compute_diag=True (the next step adapts to the "
+                             "covariance, the displacement and the effective sample size this one leaves)")
+        self.cma = cma
+        self.cma_rows = torch.zeros((self._rows, _lib.COVO_CMA_FLOATS), dtype=torch.float32, device=self.device)
+        self.cma_rows[:, 0] = 1.0
+        self.cma_p = torch.zeros((self._rows, COVO_NA), dtype=torch.float64, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_set_step_cma(self.h, cma.gamma, 1 if cma.step_size else 0, cma.damping, cma.s_min, cma.s_max,
+                                             ptr(self.cma_rows), ptr(self.cma_p), self._rows), "covo_set_step_cma")
+        self._list_infos()
+
+    def cma_reset(self):
+        """covo_cma_reset: the next CMA step is the first of an episode -- it samples from sample_sigma^2 I and writes the reset state."""
+        check(self.lib.covo_cma_reset(self.h), "covo_cma_reset")
+
+    def cma_info(self) -> dict:
+        """{"cma_scale" (s), "cma_path_norm" (|p|), "cma_mu_eff", "cma_flags" (a float: 1 path kept, 2 clamp hit, 4 shape fell back),
+        "cma_rows" [8]} of the last step as views of self.cma_rows (no sync, no copy); {} on a core without the attachment."""
+        if getattr(self, "cma_rows", None) is None:
+            return {}
+        row = self.cma_rows[0]
+        return {"cma_scale": row[0], "cma_path_norm": row[2], "cma_mu_eff": row[4], "cma_flags": row[7], "cma_rows": row}
+
+    def cma_path(self, L_prev, d, ess, p, log_s, L_hat, Sigma_hat, *, n_samples=None, W=None, shape_rows=None, step_size=True,
+                        damping=1.0, s_min=0.1, s_max=4.0, L_out=None, Sigma_out=None):
+        """covo_cma_path (the stand-alone step-size kernel): L_prev, L_hat, Sigma_hat
+        float32 device tensors [128, 128] or [E, 128, 128]; d float32 [E, 128] (the previous step's mean displacement), ess float32 [E],
+        W float32 [E] (the weight sums; None: 1); p float64 [E, 128] and log_s float64 [E], updated IN PLACE; shape_rows: covo_sigma_adapt's
+        rows [E, 4] or None; n_samples: N of mu_eff = clamp(ess, 1, N) (None: this core's).  -> (L', Sigma', rows [E, 8]).  L_out may be
+        L_prev and Sigma_out may be Sigma_hat."""
+        torch = self.torch
+        f32 = dict(dtype=torch.float32, device=self.device)
+        L_prev = L_prev.reshape(-1, COVO_NA, COVO_NA).contiguous()
+        E = int(L_prev.shape[0])
+        L_hat, Sigma_hat = L_hat.reshape(E, COVO_NA, COVO_NA).contiguous(), Sigma_hat.reshape(E, COVO_NA, COVO_NA).contiguous()
+        aux = torch.zeros((E, _lib.COVO_POST_AUX_FLOATS), **f32)
+        aux[:, :COVO_NA] = d.reshape(E, COVO_NA)
+        aux[:, COVO_NA] = 1.0 if W is None else W.reshape(E)
+        ess = ess.reshape(E).to(**f32).contiguous()
+        assert p.dtype == torch.float64 and log_s.dtype == torch.float64 and p.is_contiguous() and log_s.is_contiguous()
+        assert p.numel() == E * COVO_NA and log_s.numel() == E
+        L_out = torch.empty_like(L_hat) if L_out is None else L_out
+        Sigma_out = torch.empty_like(Sigma_hat) if Sigma_out is None else Sigma_out
+        rows = torch.zeros((E, _lib.COVO_CMA_FLOATS), **f32)
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_cma_path(self.h, ptr(L_prev), ptr(aux), _lib.COVO_POST_AUX_FLOATS, ptr(ess), 1, ptr(L_hat), ptr(Sigma_hat),
+                                         ptr(shape_rows), E, int(self.n_local if n_samples is None else n_samples), 1 if step_size else 0,
+                                         float(damping), float(s_min), float(s_max), ptr(p), ptr(log_s), ptr(L_out), ptr(Sigma_out),
+                                         ptr(rows), self.stream()), "covo_cma_path")
+        return L_out, Sigma_out, rows
 
     @property
     def lam_logged(self) -> bool:
@@ -1301,7 +1360,7 @@ class SamplingCore:
                 am.copy_(a_mean.reshape(-1), non_blocking=True)
         am_shift = self._persistent("a_mean_shift", (COVO_NA,))
         cov_out = None
-        if mode == _lib.MODE_COVO_ONLINE:
+        if mode in (_lib.MODE_COVO_ONLINE, _lib.MODE_CMA):
             cov_out = self._persistent("a_cov", (COVO_NA, COVO_NA))
         elif mode == _lib.MODE_MPPI:
             cov_out = self._persistent("a_cov_mppi", (COVO_H, 4, 4))

@@ -577,6 +577,76 @@ def check_dial(iters=4, *, beta_pass=0.5, beta_stage=0.9, temp=0.1, gamma_sigma=
 
 
 @dataclass(frozen=True)
+class CMA:
+    """The CMA controller's keywords, checked (check_cma): what SamplingCore.attach_cma attaches."""
+    gamma: float
+    step_size: bool
+    damping: float
+    s_min: float
+    s_max: float
+
+
+def check_cma(*, gamma=0.2, step_size=True, damping=1.0, s_min=0.1, s_max=4.0, sigma_period=1, sigma_adapt=0.0, sigma_nodes=None,
+              refine=False, riccati=False, riccati_feedback=False, plan_hold=1, riccati_box=False, process_group=None,
+              materialize_eps=False, noise_stream="philox", what="the CMA controller") -> CMA:
+    """The keywords of the CMA controllers (CMAController, BatchedCMAController, get_controller(env, "cma", ...),
+    eval_env_batched(controller="cma")) -> the CMA record SamplingCore.attach_cma attaches.  The C side's counterpart is check_cma_step
+    (csrc/step_attach.hip).
+
+    Every control step but the first of an episode adapts a full 128 x 128 sampling covariance to the previous step's samples: the shape
+    is sigma_adapt's blend c ((1 - gamma) S(L L^T) + gamma S(C)) at log det = 2 n log sample_sigma (csrc/sigma_adapt.hip as it is), the
+    step size s follows cumulative step-size adaptation on the whitened mean displacement (csrc/cma_path.hip), and the step samples from
+    s^2 times the shape: info["cma_scale"] / ["cma_path_norm"] / ["cma_mu_eff"] / ["cma_flags"] / ["cma_rows"] [8].  step_size=False
+    keeps s = 1.  It implies compute_post_cov and compute_diag and goes with compute_plan, compute_fan, update=, ess_min, elite and iters.
+
+    The objections, in a fixed order, each naming the keyword: sigma_period > 1, sigma_adapt > 0, sigma_nodes, refine, then riccati,
+    riccati_feedback, plan_hold > 1 and riccati_box (ValueError: the controller decides its own Sigma every step and keeps no Hessian);
+    gamma anything but a real number in [0, 1), step_size anything but a bool, damping anything but a finite real number > 0, s_min /
+    s_max anything but finite real numbers with 0 < s_min <= 1 <= s_max (ValueError); then process_group (NotImplementedError: a
+    sample-sharded step has neither the posterior covariance nor the diagnostics) and the kernel-by-kernel path, materialize_eps /
+    noise_stream="jax" (NotImplementedError: it keeps no factor between steps)."""
+    import math
+    import numbers
+    if int(sigma_period) != 1:
+        raise ValueError(f"sigma_period={sigma_period} with {what}: it adapts its covariance every step and never refreshes one; give "
+                         "sigma_period=1")
+    if float(sigma_adapt) != 0.0:
+        raise ValueError(f"sigma_adapt={sigma_adapt} with {what}: the controller runs that blend itself, at gamma=; give sigma_adapt=0")
+    if sigma_nodes is not None:
+        raise ValueError(f"sigma_nodes={sigma_nodes} with {what}: the node-space Sigma is derived from a Hessian, which this controller "
+                         "never forms; give sigma_nodes=None")
+    if refine is not False:
+        raise ValueError(f"refine={refine!r} with {what}: the Newton refinement needs the Hessian-derived Sigma of covo-online; give "
+                         "refine=False")
+    for name, v, off in (("riccati", riccati, False), ("riccati_feedback", riccati_feedback, False), ("plan_hold", plan_hold, 1),
+                         ("riccati_box", riccati_box, False)):
+        if v != off or isinstance(v, bool) != isinstance(off, bool):
+            raise ValueError(f"{name}={v!r} with {what}: the Riccati switches belong to the sampling controllers with a Hessian path "
+                             f"(MPPI, covo-offline, covo-online, ilqr); give {name}={off!r}")
+
+    def real(v):
+        return not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v))
+    if not real(gamma) or not 0.0 <= float(gamma) < 1.0:
+        raise ValueError(f"gamma={gamma!r} outside [0, 1) (the weight of the previous step's posterior covariance in the shape, a real "
+                         "number; 0 = the shape only shifts)")
+    if not isinstance(step_size, bool):
+        raise ValueError(f"step_size={step_size!r} (True | False)")
+    if not real(damping) or not float(damping) > 0.0:
+        raise ValueError(f"damping={damping!r} (a finite real number > 0: the factor on the step-size damping d_sigma)")
+    if not real(s_min) or not real(s_max) or not 0.0 < float(s_min) <= 1.0 <= float(s_max):
+        raise ValueError(f"s_min={s_min!r}, s_max={s_max!r}: the step size's bounds relative to sample_sigma must be finite real numbers "
+                         "with 0 < s_min <= 1 <= s_max")
+    if process_group is not None:
+        raise NotImplementedError(f"process_group with {what}: a sample-sharded step has neither the posterior covariance nor the "
+                                  "diagnostics the next step adapts to (covo_set_step_post_cov and covo_set_step_diag refuse "
+                                  "sample-sharded steps)")
+    if materialize_eps or noise_stream != "philox":
+        raise NotImplementedError(f"{what} acts in the fused step (covo_mpc_step); the kernel-by-kernel path (materialize_eps / "
+                                  "noise_stream='jax') keeps no factor between steps")
+    return CMA(gamma=float(gamma), step_size=step_size, damping=float(damping), s_min=float(s_min), s_max=float(s_max))
+
+
+@dataclass(frozen=True)
 class SigmaNodes:
     """covo-online in node space, checked (check_sigma_nodes): what SamplingCore's sigma_nodes= keyword resolves to."""
     M: int              # nodes, 2 .. COVO_SIGMA_NODES_MAX; d = 4 M

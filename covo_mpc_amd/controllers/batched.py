@@ -337,6 +337,64 @@ class BatchedILQRController(BatchedCoVOController):
         return self(noisy_states, rng_acts)
 
 
+class BatchedCMAController(BatchedCoVOController):
+    """CMA-MPC (controllers/cma.py) for E instances: the same methods as BatchedCoVOController -- set_instances / bind_episode, __call__
+    (also as .step), run_episode, reset -- through covo_mpc_step_batched_mode / covo_run_episode_batched_mode in COVO_MODE_CMA: covo-online's
+    staged batch without its Hessian and Sigma chain, the shape and step-size launches with the instance as a grid dimension.  Every
+    instance keeps its own factor, path and step size; instance e's result is bit-identical to CMAController's on that instance alone
+    (tests/test_gpu_cma.py).  After a call: .cma_rows [E, 8], .cma_path [E, 128] float64, .a_cov [E, 128, 128] (the covariances the
+    step sampled from), .diag, .post_cov, .post_aux and the other step options' buffers (None for what is off)."""
+    MODE = _lib.MODE_CMA
+
+    def __init__(self, env, n_envs: int, N: int, H: int, lam: float, *, gamma: float = 0.2, step_size: bool = True, damping: float = 1.0,
+                 s_min: float = 0.1, s_max: float = 4.0, discount: float = 1.0, gamma_mean: float = 1.0, sample_sigma: float = 0.5,
+                 a_mean_init=None, device=None, compute_plan: bool = False, compute_fan=None, update: str = "softmax", ess_min=None,
+                 elite=None, iters: int = 1, sigma_period: int = 1, sigma_adapt: float = 0.0, sigma_nodes=None, refine: bool = False,
+                 riccati: bool = False, riccati_feedback: bool = False, plan_hold: int = 1, riccati_box: bool = False):
+        from ._options import check_cma
+        what = "the env-batched CMA controller"
+        self.cma = check_cma(gamma=gamma, step_size=step_size, damping=damping, s_min=s_min, s_max=s_max, sigma_period=sigma_period,
+                             sigma_adapt=sigma_adapt, sigma_nodes=sigma_nodes, refine=refine, riccati=riccati,
+                             riccati_feedback=riccati_feedback, plan_hold=plan_hold, riccati_box=riccati_box, what=what)
+        opts = dict(compute_diag=True, compute_plan=compute_plan, ess_min=ess_min, compute_fan=compute_fan, update=update, iters=iters,
+                    elite=elite, compute_post_cov=True)
+        check_step_options(N, what, **opts)
+        if not 0 < n_envs <= _lib.COVO_MAX_ENVS:
+            raise ValueError(f"n_envs={n_envs} outside (0, {_lib.COVO_MAX_ENVS}]")
+        self.mode, self.staged = self.MODE, False
+        self.env, self.E, self.N, self.H = env, int(n_envs), int(N), int(H)
+        self.gamma_mean, self.sample_sigma, self.gamma_sigma = float(gamma_mean), float(sample_sigma), 0.0
+        self.rollover_terminate = not getattr(env, "disable_rollover_terminate", True)
+        self.core = SamplingCore(N, H, lam, discount, device=device, compute_info=False, trust_clipped=True, use_graph=True,
+                                 diag_rows=int(n_envs), **opts)
+        self.core.attach_cma(self.cma)
+        for mine, cores in CORE_BUFFERS:
+            setattr(self, mine, getattr(self.core, cores))
+        self.cma_rows, self.cma_path = self.core.cma_rows, self.core.cma_p
+        torch = self.core.torch
+        f32 = dict(dtype=torch.float32, device=self.core.device)
+        E, n = self.E, self.N
+        self.a_mean = torch.zeros((E, COVO_NA), **f32)
+        if a_mean_init is not None:
+            self.a_mean.copy_(torch.as_tensor(a_mean_init, **f32).reshape(1, COVO_NA).expand(E, COVO_NA))
+        self.a_cov = torch.zeros((E, COVO_NA, COVO_NA), **f32)
+        self.a_cov_offline = self.a_chol_offline = None
+        self._a = torch.empty((E, COVO_H, n, 4), **f32)
+        self._cost = torch.empty((E, n), **f32)
+        self._groupmin = torch.empty((E, (n + 63) // 64), **f32)
+        self._states = torch.zeros((E, _lib.COVO_STATE_FLOATS), **f32)
+        self._traj = self._params = self._args = None
+
+    def reset(self, env_states=None, env_params=None, keys=None):
+        """Episode start: every instance's L = sample_sigma I, p = 0, log s = 0 -- the next step samples from sample_sigma^2 I."""
+        self.core.cma_reset()
+        return None
+
+    def step(self, noisy_states, rng_acts):
+        """One control step of every instance (= __call__) -> first actions [E, 4] (view of a_mean)."""
+        return self(noisy_states, rng_acts)
+
+
 class BatchedDialController(BatchedMPPIController):
     """Annealed MPPI (controllers/dial.py) for E instances: the same methods as BatchedMPPIController -- set_instances / bind_episode,
     __call__ (also as .step), run_episode, reset -- always on the staged env-batched MPPI step (the fused launch shifts and factors

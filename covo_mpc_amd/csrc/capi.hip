@@ -1,4 +1,5 @@
 // capi.hip -- the extern "C" surface declared in include/covo_hip.h.
+#include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
@@ -61,6 +62,7 @@ static int batched_step_at_age(covo_ctx *h, const covo_batch_args *args, const c
 {
     if (age != 0) return covo_hold_step_batched(h, args, age, row, s);  // (covo-online and iLQR only: the others refuse the Riccati refinement)
     if (norm->mode == COVO_MODE_ILQR) return covo_ilqr_step_batched_impl(h, args, params, keys, s);  // (its begin work)
+    if (norm->mode == COVO_MODE_CMA) return covo_step_batched_impl(h, args, params, keys, s, COVO_MODE_CMA);  // (covo-online's body)
     return norm->mode == COVO_MODE_COVO_ONLINE ? covo_step_batched_impl(h, args, params, keys, s)
            : covo_batched_staged(h)            ? covo_step_batched_staged_impl(h, norm, params, keys, s)
                                                : covo_step_batched_small_impl(h, norm, params, keys, s);
@@ -167,6 +169,7 @@ int covo_destroy(covo_handle_t h)
     DESTROY(hipFree(h->hold_b));
     DESTROY(hipFree(h->hold_t));
     DESTROY(hipFree(h->hold_keys));
+    DESTROY(hipFree(h->cma_ws));
     DESTROY(hipEventDestroy(h->ev_fork));
     DESTROY(hipEventDestroy(h->ev_join));
     DESTROY(hipStreamDestroy(h->side_stream));
@@ -952,6 +955,98 @@ int covo_sigma_adapt(covo_handle_t h, const float *L_in, const float *C, int32_t
     return launch_sigma_adapt(L_in, C, batch, gamma, sample_sigma, Sigma_out, L_out, rows_out, (hipStream_t)stream);
 }
 
+// ---- the CMA controller (cma_path.hip): the attachment a step in COVO_MODE_CMA reads.  The step's captured graphs
+// hold every value given here: a change bumps the epoch like a debug switch, and the state starts over.  What the step needs next to
+// it (a posterior covariance and a diagnostics target, no Sigma period ...) is checked at the step (check_cma_step)
+static bool cma_bounds_ok(float damping, float s_min, float s_max)
+{
+    return damping > 0.0f && damping < __builtin_inff() && s_min > 0.0f && s_min <= 1.0f && s_max >= 1.0f && s_max < __builtin_inff();
+}
+
+int covo_set_step_cma(covo_handle_t h, float gamma, int32_t step_size, float damping, float s_min, float s_max, float *rows_out,
+                      double *path_out, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_cma: null handle");
+    const bool on = rows_out != nullptr;
+    REQUIRE(!on || (gamma >= 0.0f && gamma < 1.0f), "covo_set_step_cma: gamma=%g outside [0, 1)", (double)gamma);
+    REQUIRE(!on || cma_bounds_ok(damping, s_min, s_max), "covo_set_step_cma: damping=%g, s_min=%g, s_max=%g: damping > 0 and 0 < s_min "
+            "<= 1 <= s_max < inf are required", (double)damping, (double)s_min, (double)s_max);
+    REQUIRE(!on || path_out != nullptr, "covo_set_step_cma: path_out is null (the evolution paths live there)");
+    REQUIRE(!on || (n_inst > 0 && n_inst <= COVO_MAX_ENVS), "covo_set_step_cma: n_inst=%d outside (0, %d]", n_inst, COVO_MAX_ENVS);
+    REQUIRE(!on || (((uintptr_t)rows_out | (uintptr_t)path_out) & 15) == 0, "covo_set_step_cma: rows_out and path_out must be 16-byte aligned");
+    if (on && n_inst > h->cma_ws_n) {  // (the second factor buffer only ever grows; the graphs that hold it are dropped below)
+        CHECK_DEVICE(h, "covo_set_step_cma");
+        COVO_CHECK_HIP(hipDeviceSynchronize());  // (a setter, off the per-step path) no step in flight reads the old buffer
+        COVO_CHECK_HIP(hipFree(h->cma_ws));
+        h->cma_ws = nullptr;
+        h->cma_ws_n = 0;
+        h->cma_rows = nullptr;  // (a failed allocation leaves the mode detached, not pointing into freed memory)
+        h->cma_p = nullptr;
+        h->cma_n = 0;
+        COVO_CHECK_HIP(hipMalloc(&h->cma_ws, covo_cma_ws_bytes(n_inst)));
+        h->cma_ws_n = n_inst;
+    }
+    h->cma_n = on ? n_inst : 0;  // the rows of THIS attachment: what a step's instance count is held to
+    h->cma_gamma = on ? gamma : 0.0f;
+    h->cma_step_size = on ? (step_size != 0) : 0;
+    h->cma_damping = damping;
+    h->cma_s_min = s_min;
+    h->cma_s_max = s_max;
+    h->cma_rows = on ? rows_out : nullptr;
+    h->cma_p = on ? path_out : nullptr;
+    h->cma_age = 0;
+    ++h->opt.epoch;
+    return 0;
+}
+
+int covo_cma_reset(covo_handle_t h)
+{
+    REQUIRE(h, "covo_cma_reset: null handle");
+    h->cma_age = 0;
+    return 0;
+}
+
+int covo_cma_path(covo_handle_t h, const float *L_prev, const float *aux, int32_t aux_stride, const float *ess, int32_t ess_stride,
+                  const float *L_hat, const float *Sigma_hat, const float *shape_rows, int32_t batch, int32_t n_samples, int32_t step_size,
+                  float damping, float s_min, float s_max, double *p, double *log_s, float *L_out, float *Sigma_out, float *rows_out,
+                  void *stream)
+{
+    REQUIRE(h, "covo_cma_path: null handle");
+    CHECK_DEVICE(h, "covo_cma_path");
+    REQUIRE(L_prev && aux && ess && L_hat && Sigma_hat && p && log_s && L_out && Sigma_out && rows_out && batch > 0 && batch <= 65535,
+            "covo_cma_path: bad argument");
+    REQUIRE(aux_stride > COVO_NA && ess_stride > 0 && n_samples > 0, "covo_cma_path: aux_stride=%d (> 128: d and W), ess_stride=%d, "
+            "n_samples=%d", aux_stride, ess_stride, n_samples);
+    REQUIRE(cma_bounds_ok(damping, s_min, s_max), "covo_cma_path: damping=%g, s_min=%g, s_max=%g: damping > 0 and 0 < s_min <= 1 <= s_max "
+            "< inf are required", (double)damping, (double)s_min, (double)s_max);
+    REQUIRE((((uintptr_t)L_prev | (uintptr_t)L_hat | (uintptr_t)Sigma_hat | (uintptr_t)shape_rows | (uintptr_t)L_out | (uintptr_t)Sigma_out |
+              (uintptr_t)rows_out) & 15) == 0 && (((uintptr_t)p | (uintptr_t)log_s) & 7) == 0,
+            "covo_cma_path: the matrices and rows must be 16-byte aligned, p and log_s 8-byte");
+    REQUIRE(L_out != L_hat && L_out != Sigma_hat && Sigma_out != L_hat && (const float *)Sigma_out != L_prev && Sigma_out != L_out,
+            "covo_cma_path: L_out may be L_prev and Sigma_out may be Sigma_hat; no other two matrices may coincide");
+    CmaPathDesc d;
+    d.L_prev = L_prev;
+    d.aux = aux;
+    d.aux_stride = aux_stride;
+    d.ess = ess;
+    d.ess_stride = ess_stride;
+    d.L_hat = L_hat;
+    d.Sigma_hat = Sigma_hat;
+    d.shape_rows = shape_rows;
+    d.batch = batch;
+    d.n_samples = n_samples;
+    d.step_size = step_size != 0;
+    d.damping = (double)damping;
+    d.log_s_min = std::log((double)s_min);
+    d.log_s_max = std::log((double)s_max);
+    d.p = p;
+    d.log_s = log_s;
+    d.L_out = L_out;
+    d.Sigma_out = Sigma_out;
+    d.rows_out = rows_out;
+    return launch_cma_path(d, (hipStream_t)stream);
+}
+
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
@@ -1582,6 +1677,8 @@ int covo_debug_time_step(covo_handle_t h, const covo_env_params *params, const c
     REQUIRE(h && params && args && us_out && reps > 0, "covo_debug_time_step: bad argument");
     REQUIRE(args->mode != COVO_MODE_ILQR, "covo_debug_time_step: the phase masks name the launches of a sampling step; an iLQR step "
             "(COVO_MODE_ILQR) has none of them");
+    REQUIRE(args->mode != COVO_MODE_CMA, "covo_debug_time_step: the phase timers replay a step without its state; a CMA step "
+            "(COVO_MODE_CMA) would adapt its covariance once per copy");
     REQUIRE(covo_step_iters(h) == 1, "covo_debug_time_step: the phase timers replay ONE pass; iterations per step are on "
             "(covo_set_step_iters, iters=%d): set iters = 1", covo_step_iters(h));
     return covo_debug_time_step_impl(h, params, args, step_mask, hess_mask, sigma_stages, reps, us_out, (hipStream_t)stream);  // (a refresh step's launches)

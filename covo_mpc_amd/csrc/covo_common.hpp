@@ -117,6 +117,19 @@ struct covo_ctx {
     float adapt_gamma;        // the weight of the previous step's posterior covariance in a reuse step's Sigma', in (0, 1)
     float *adapt_rows;        // caller's [adapt_n][COVO_SIGMA_ADAPT_FLOATS]: instance e's {fallback, c, log det M, 0} of every reuse step
     int adapt_n;
+    // the CMA controller (covo_set_step_cma; cma_path.hip); cma_rows null: not attached
+    float cma_gamma;          // the weight of the previous step's posterior covariance in the shape, in [0, 1)
+    int cma_step_size;        // 0: s = 1 for ever
+    float cma_damping, cma_s_min, cma_s_max;
+    float *cma_rows;          // caller's [cma_n][COVO_CMA_FLOATS]: instance e's row of every step
+    double *cma_p;            // caller's [cma_n][128]: the evolution paths, kept there between steps
+    int cma_n;                // the rows and paths of the current attachment (0: detached): a step of more instances is refused
+    void *cma_ws;             // the handle's own, one allocation: log s [COVO_MAX_ENVS] (fp64), the shape's rows [COVO_MAX_ENVS][4], L_hat [cma_ws_n][128][128]
+    int cma_ws_n;             // the instances cma_ws was allocated for (>= cma_n; only ever grows)
+    int cma_age;              // 0: the next CMA step is the first after a reset; else 1
+    const float *cma_L;       // the factor buffer (the single step's or the batch's) that holds the last CMA step's L ...
+    float cma_L_sigma;        // ... the sample_sigma it was built for ...
+    int cma_L_n;              // ... and for how many instances
     // the Newton refinement of the committed mean (covo_set_step_refine; cost_gradient.hip, newton_refine.hip); refine_out null: off
     float *refine_out;        // caller's [refine_n][COVO_REFINE_FLOATS]: instance e's refine row of every step
     int refine_n;
@@ -181,6 +194,29 @@ static inline float *covo_eplog_inst(const covo_ctx *h, int kind, int e, int row
 }
 static inline bool covo_post_cov_on(const covo_ctx *h) { return h->post_cov_out != nullptr; }
 static inline bool covo_sigma_adapt_on(const covo_ctx *h) { return h->adapt_rows != nullptr && h->adapt_gamma > 0.0f; }
+static inline bool covo_cma_on(const covo_ctx *h) { return h->cma_rows != nullptr; }
+// the three parts of cma_ws
+static inline double *covo_cma_log_s(const covo_ctx *h) { return reinterpret_cast<double *>(h->cma_ws); }
+static inline float *covo_cma_shape_rows(const covo_ctx *h) { return reinterpret_cast<float *>(covo_cma_log_s(h) + COVO_MAX_ENVS); }
+static inline float *covo_cma_L_hat(const covo_ctx *h) { return covo_cma_shape_rows(h) + (size_t)COVO_MAX_ENVS * COVO_SIGMA_ADAPT_FLOATS; }
+static inline size_t covo_cma_ws_bytes(int n_inst)
+{
+    return (size_t)COVO_MAX_ENVS * (sizeof(double) + COVO_SIGMA_ADAPT_FLOATS * sizeof(float)) + (size_t)n_inst * COVO_NA * COVO_NA * sizeof(float);
+}
+// the age this CMA step of n_inst instances runs at, given where its factor lives: 0 (the first step after a reset) unless L holds the
+// previous CMA step's factor for the same sample_sigma and instance count
+static inline int covo_cma_step_age(const covo_ctx *h, const float *L, float sample_sigma, int n_inst)
+{
+    if (h->cma_age == 0) return 0;
+    return (h->cma_L == L && L != nullptr && h->cma_L_sigma == sample_sigma && h->cma_L_n == n_inst) ? 1 : 0;
+}
+static inline void covo_cma_step_done(covo_ctx *h, const float *L, float sample_sigma, int n_inst)
+{
+    h->cma_age = 1;
+    h->cma_L = L;
+    h->cma_L_sigma = sample_sigma;
+    h->cma_L_n = n_inst;
+}
 // passes per control step of this handle (1: today's step) and where pass j of instance 0 logs its cost minimum (instance e: + e * iters)
 static inline int covo_sigma_period(const covo_ctx *h) { return h->sigma_period > 1 ? h->sigma_period : 1; }
 // the age this covo-online step of n_inst instances runs at, given where its factor lives: 0 (refresh) unless the period is on, the
@@ -326,6 +362,7 @@ int check_model(const covo_env_params *p, const char *what);
 int check_step_attachments(const covo_ctx *h, int n_samples, int n_inst, bool sharded, int derive_keys, int mode, const float *a_cov,
                            const covo_env_params *params, const char *what, float gamma_sigma = 0.0f, bool fused_batch = false);
 int check_ilqr_step(const covo_ctx *h, int n_inst, bool sharded, int derive_keys, const char *what);
+int check_cma_step(const covo_ctx *h, int n_inst, bool sharded, const float *a_cov, const char *what);
 int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, const char *what);
 int check_single_step(const covo_ctx *h, const covo_env_params *params, const covo_step_args *args, const char *what);
 int check_batch_models(const covo_env_params *params, int E, bool env_step, const char *what);
@@ -749,7 +786,7 @@ int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us
 int covo_debug_batched_hessians_impl(covo_ctx *h, double *out, int64_t offset_doubles, int64_t count, hipStream_t s);
 int covo_debug_sigma_factor_impl(covo_ctx *h, int batched, float *out, int64_t count, hipStream_t s);
 int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
-                           hipStream_t s);
+                           hipStream_t s, int mode = COVO_MODE_COVO_ONLINE);  // (or COVO_MODE_CMA)
 int covo_step_batched_small_impl(covo_ctx *h, const covo_batch_mode_args *m, const covo_env_params *params, const uint32_t *keys,
                                  hipStream_t s);
 // the same step as its staged launch sequence (covo_set_step_batched_staged): begin | tables | sampling | rollout | update per pass
@@ -771,6 +808,31 @@ int launch_sigma_shift(const float *L_in, int batch, float sample_sigma, float *
 int launch_sigma_adapt(const float *L_in, const float *C, int batch, float gamma, float sample_sigma, float *Sigma_out, float *L_out,
                        float *rows_out, hipStream_t s);
 int launch_sigma_adapt_idle(float *rows_out, int n_inst, hipStream_t s);  // a refresh step's rows {0, 1, 0, 0}
+// cma_path.hip: the CMA controller's step size behind sigma_adapt.hip's shape (the header of that file has the formulas).  One
+// workgroup per instance; writes p, log_s (on a fall-back: their mended entry values), L_out, Sigma_out and rows_out, nothing else
+struct CmaPathDesc {
+    const float *L_prev = nullptr;      // [batch][128][128] the factor the previous step sampled from (lower; all of it is read)
+    const float *aux = nullptr;         // instance e's {d[128], W, ...} of the previous step at aux + e * aux_stride (post_cov.hip's side row)
+    int aux_stride = COVO_POST_AUX_FLOATS;
+    const float *ess = nullptr;         // instance e's effective sample size of the previous step at ess + e * ess_stride
+    int ess_stride = COVO_DIAG_FLOATS;
+    const float *L_hat = nullptr;       // [batch][128][128] the shape's factor ...
+    const float *Sigma_hat = nullptr;   // ... and covariance (sigma_adapt.hip's outputs); Sigma_out may be Sigma_hat
+    const float *shape_rows = nullptr;  // [batch][COVO_SIGMA_ADAPT_FLOATS] the shape kernel's rows (flag 4), or null
+    int batch = 1;
+    int n_samples = 1;                  // N: mu_eff = clamp(ess, 1, N)
+    int step_size = 1;                  // 0: s = 1, copy only, p and log_s are not touched
+    double damping = 1.0;
+    double log_s_min = 0.0, log_s_max = 0.0;  // log of the fp32 bounds, taken in fp64 on the host
+    double *p = nullptr;                // [batch][128] in/out
+    double *log_s = nullptr;            // [batch] in/out
+    float *L_out = nullptr;             // [batch][128][128] fp32(s L_hat); may be L_prev
+    float *Sigma_out = nullptr;         // [batch][128][128] fp32(s^2 Sigma_hat)
+    float *rows_out = nullptr;          // [batch][COVO_CMA_FLOATS] {s, log s, |p|, |z|, mu_eff, c_sigma, d_sigma, flags}
+};
+int launch_cma_path(const CmaPathDesc &d, hipStream_t s);
+// L = sigma I, Sigma = sigma^2 I, p = 0, log s = 0 and the neutral row {1, 0, 0, 0, 0, 0, 0, 0} for `batch` instances; null: skipped
+int launch_cma_reset(float sample_sigma, int batch, float *L, float *Sigma, double *p, double *log_s, float *rows, hipStream_t s);
 size_t env_step_inst_bytes(int n);
 void env_step_fill_inst(const covo_env_params *params, int n, void *out);  // host: EnvInst[n] (to be copied to the device)
 int launch_env_step_batched(float *states, float *noisy, const float *pos_traj, const float *vel_traj, const float *acc_traj, int T,

@@ -7,6 +7,7 @@
 // The second call with the same buffers captures the sequence into a hipGraph, later calls replay it.
 // Quantities that change every step (Philox key, MPPI's shared disturbance draw) live in a 32-byte
 // device block refreshed by one async copy before each replay, so the captured kernel arguments stay valid.
+#include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
@@ -189,7 +190,40 @@ struct OnlineChainView {
     // one matrix only
     unsigned *sync = nullptr;     // the streamed finalize launch's flags: the GEMM may run inside the chain's last launch
     bool defer_cov = false;       // a_cov may be left to the GEMM's first workgroups (CovDeferred)
+    // COVO_MODE_CMA: no Hessian and no Sigma chain ever -- Sigma and L come from the samples (enqueue_cma_sigma); `reuse` then says
+    // "not the first step after a reset"
+    bool cma = false;
 };
+
+// the Sigma of a CMA step (covo_set_step_cma), E instances: the first step after a reset writes the reset state --
+// L = sigma0 I, a_cov = sigma0^2 I, p = 0, log s = 0, the neutral row; every later one runs the shape (sigma_adapt.hip as it is: the
+// handle's L and the posterior covariance the previous step left, into the handle's second buffer and a_cov) and behind it the step
+// size (cma_path.hip: path and log s from the previous step's displacement and ess; L' = s L_hat' back into L, a_cov scaled in place)
+static int enqueue_cma_sigma(covo_ctx *h, const OnlineChainView &v, hipStream_t s, bool first)
+{
+    if (first) return launch_cma_reset(v.sample_sigma, v.E, v.L, v.Sigma, h->cma_p, covo_cma_log_s(h), h->cma_rows, s);
+    int rc = launch_sigma_adapt(v.L, h->post_cov_out, v.E, h->cma_gamma, v.sample_sigma, v.Sigma, covo_cma_L_hat(h), covo_cma_shape_rows(h), s);
+    if (rc) return rc;
+    CmaPathDesc d;
+    d.L_prev = v.L;
+    d.aux = h->post_aux_out;
+    d.ess = covo_diag_target(h);
+    d.L_hat = covo_cma_L_hat(h);
+    d.Sigma_hat = v.Sigma;
+    d.shape_rows = covo_cma_shape_rows(h);
+    d.batch = v.E;
+    d.n_samples = v.N;
+    d.step_size = h->cma_step_size;
+    d.damping = (double)h->cma_damping;
+    d.log_s_min = std::log((double)h->cma_s_min);
+    d.log_s_max = std::log((double)h->cma_s_max);
+    d.p = h->cma_p;
+    d.log_s = covo_cma_log_s(h);
+    d.L_out = v.L;
+    d.Sigma_out = v.Sigma;
+    d.rows_out = h->cma_rows;
+    return launch_cma_path(d, s);
+}
 
 static int enqueue_online_chain(covo_ctx *h, const OnlineChainView &v, hipStream_t s, const DebugMasks &dbg, int pass, bool reuse)
 {
@@ -204,6 +238,10 @@ static int enqueue_online_chain(covo_ctx *h, const OnlineChainView &v, hipStream
     nd.a = v.a;
     nd.batch = v.E;
     nd.propagate_nan = covo_propagate_nan(h);
+    if (v.cma) {  // the samples are drawn as a reuse step draws them (in-kernel Philox); the later passes sample from the same L'
+        if (pass == 0 && (rc = enqueue_cma_sigma(h, v, s, !reuse))) return rc;
+        return launch_noise_gemm(nd, s);
+    }
     if (reuse) {
         // a reuse step of a Sigma period: no Hessian, no Sigma chain -- every instance's factor of the previous step is shifted in
         // place (sigma_shift.hip), a_cov is its Sigma', and the samples are drawn from it as covo-offline draws from a table row
@@ -400,8 +438,9 @@ static int enqueue_step(covo_ctx *h, StepState *st, const covo_env_params &p, co
     const bool tables = covo_needs_tables(p);
     if (tables && (rc = launch_disturb_tables_step(p, state, st->dyn, a.rollout_deterministic, st->f_tab_rollout,
                                                    (a.mode == COVO_MODE_COVO_ONLINE && !reuse) ? st->f_tab_hess : nullptr, s))) return rc;
-    if (a.mode == COVO_MODE_COVO_ONLINE) {
+    if (a.mode == COVO_MODE_COVO_ONLINE || a.mode == COVO_MODE_CMA) {
         OnlineChainView v;
+        v.cma = a.mode == COVO_MODE_CMA;
         v.dyn = st->dyn;
         v.sample_offset = a.sample_offset;
         v.N = N;
@@ -578,10 +617,12 @@ int covo_step_impl(covo_ctx *h, const covo_env_params *params, const covo_step_a
     step_sync_epoch(h);
     StepState *st = reinterpret_cast<StepState *>(h->step);
     // covo_set_step_sigma_period: the age this step runs at -- 0: today's step, which leaves its factor in st->L; else a reuse step
-    const bool online = args->mode == COVO_MODE_COVO_ONLINE;
-    const int age = online ? covo_sigma_step_age(h, st->L, args->sample_sigma, 1) : 0;
+    const bool online = args->mode == COVO_MODE_COVO_ONLINE, cma = args->mode == COVO_MODE_CMA;
+    // (a CMA step keeps its factor in st->L too: a covo-online step between two of them makes the next one a first step)
+    const int age = online ? covo_sigma_step_age(h, st->L, args->sample_sigma, 1) : cma ? covo_cma_step_age(h, st->L, args->sample_sigma, 1) : 0;
     int rc = step_enqueue_all(h, st, params, args, key0, key1, f_shared, s, age != 0);
-    if (rc == 0 && online) covo_sigma_step_done(h, age, st->L, args->sample_sigma, 1);
+    if (rc == 0 && online) covo_sigma_step_done(h, age, st->L, args->sample_sigma, 1), h->cma_age = 0;
+    if (rc == 0 && cma) covo_cma_step_done(h, st->L, args->sample_sigma, 1);
     if (rc == 0 && online && age == 0 && covo_sigma_adapt_on(h)) rc = launch_sigma_adapt_idle(h->adapt_rows, 1, s);  // (eager, behind the step)
     return rc;
 }
@@ -1015,6 +1056,7 @@ static int batch_enqueue(covo_ctx *h, BatchState *b, const covo_batch_args &a, h
     v.hess.f_tab = c.tables ? b->tab_hess : nullptr;
     v.hess.models_dev = c.models;
     v.ahead_groups = 4 | 8;
+    v.cma = c.key.mode == COVO_MODE_CMA;  // (the cold block keys the scratch by the mode)
     if ((rc = enqueue_online_chain(h, v, s, dbg, pass, reuse))) return rc;
     if ((M & 16) && (rc = launch_rollout_batched(c.ro_args_host.data(), c.ro_args, E, s))) return rc;
     if (!(M & 32)) return 0;
@@ -1030,6 +1072,11 @@ int covo_debug_time_batched_impl(covo_ctx *h, int step_mask, int reps, float *us
     BatchState *b = reinterpret_cast<BatchState *>(h->batch);
     if (!b || !b->online.have_key) {
         covo_set_error("covo_debug_time_batched: call covo_mpc_step_batched first");
+        return COVO_E_BADARG;
+    }
+    if (b->online.key.mode == COVO_MODE_CMA) {  // (the scratch's last step: every replayed copy would rewrite the factors, paths and rows)
+        covo_set_error("covo_debug_time_batched: the phase timers replay a step without its state; a CMA step (COVO_MODE_CMA) would "
+                       "adapt its covariance once per copy");
         return COVO_E_BADARG;
     }
     COVO_CHECK_HIP(hipStreamSynchronize(run));
@@ -1057,8 +1104,9 @@ static int batch_online_cold(covo_ctx *h, BatchState *b, const covo_batch_args *
         // (not eps_tiled and env_inst: the instance count may change between batch_env_inst and the env step launch that reads
         // env_inst; eps_tiled only ever grows)
         if (new_E || b->tab_hess == nullptr) {  // (null: an earlier attempt failed half way)
+            if (h->cma_L == b->L) h->cma_L = nullptr;  // (the factor buffer goes: the next batched CMA step is a first step ...
             free_and_null(b->R, b->Sigma, b->L, b->consts, b->tab_hess);
-            h->sigma_L = nullptr;  // (the factor buffer goes: the next step of a Sigma period refreshes)
+            h->sigma_L = nullptr;  // ... and the next step of a Sigma period refreshes)
             const size_t M = (size_t)COVO_NA * COVO_NA;
             COVO_CHECK_HIP(hipMalloc(&b->R, (size_t)E * M * sizeof(double)));
             COVO_CHECK_HIP(hipMalloc(&b->Sigma, (size_t)E * M * sizeof(float)));
@@ -1079,26 +1127,33 @@ static int batch_online_cold(covo_ctx *h, BatchState *b, const covo_batch_args *
     return 0;
 }
 
+// mode: COVO_MODE_COVO_ONLINE, or COVO_MODE_CMA on the same scratch and the same enqueue body (its "reuse" graph: every step but the
+// first after a reset)
 int covo_step_batched_impl(covo_ctx *h, const covo_batch_args *args, const covo_env_params *params, const uint32_t *keys,
-                           hipStream_t s)
+                           hipStream_t s, int mode)
 {
     const int E = args->n_envs;
+    const bool cma = mode == COVO_MODE_CMA;
     step_sync_epoch(h);
     BatchState *b = batch_state(h);
     BatchCommon *c = &b->online;
     bool same;
     int rc;
-    if ((rc = batch_online_cold(h, b, args, COVO_MODE_COVO_ONLINE, params, s, &same))) return rc;
+    if ((rc = batch_online_cold(h, b, args, mode, params, s, &same))) return rc;
     batch_upload_keys(c->dyn, keys, E, s);
     // covo_set_step_sigma_period: the batch shares one age -- 0: today's step, which leaves the factors in b->L; else a reuse step
-    const int age = covo_sigma_step_age(h, b->L, args->sample_sigma, E);
+    const int age = cma ? covo_cma_step_age(h, b->L, args->sample_sigma, E) : covo_sigma_step_age(h, b->L, args->sample_sigma, E);
     const bool reuse = age != 0;
     // both graphs are keyed by the step's key; each one's first call with these buffers runs eagerly, the second captures
     rc = step_run_passes(
         h, c->cache, reuse, graph_cache_seen(c->cache[reuse ? 1 : 0], same), s, "covo_mpc_step_batched",
         [&](hipStream_t on, int j) { return batch_enqueue(h, b, *args, on, DebugMasks(), j, reuse); },
-        [&](hipStream_t on, int) { return covo_plan_after_batched(h, AFTER_BETWEEN, args, COVO_MODE_COVO_ONLINE, params, nullptr, nullptr, -1, on); });
-    if (rc == 0) covo_sigma_step_done(h, age, b->L, args->sample_sigma, E);
+        [&](hipStream_t on, int) { return covo_plan_after_batched(h, AFTER_BETWEEN, args, mode, params, nullptr, nullptr, -1, on); });
+    if (rc == 0 && cma) {
+        covo_cma_step_done(h, b->L, args->sample_sigma, E);
+        return 0;
+    }
+    if (rc == 0) covo_sigma_step_done(h, age, b->L, args->sample_sigma, E), h->cma_age = 0;
     if (rc == 0 && !reuse && covo_sigma_adapt_on(h)) return launch_sigma_adapt_idle(h->adapt_rows, E, s);  // (eager, behind the step)
     return rc;
 }
@@ -1595,7 +1650,7 @@ int covo_plan_after_batched(covo_ctx *h, AfterForm form, const covo_batch_args *
     const int E = args->n_envs;
     // the batch with a begin launch: covo-online's (a hold step's too: the others refuse the Riccati refinement), the staged MPPI /
     // covo-offline step's (covo_set_step_batched_staged), or none behind the fused launch
-    const bool online = mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_ILQR || form == AFTER_HOLD;
+    const bool online = mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_ILQR || mode == COVO_MODE_CMA || form == AFTER_HOLD;
     const BatchCommon *c = online ? &b->online : (covo_batched_staged(h) ? &b->staged : nullptr);
     const float *nominal = nullptr;  // the update arbiter's: a begin launch leaves it, the fused launch's was formed ahead of it
     if (form != AFTER_HOLD && covo_arb_on(h)) {

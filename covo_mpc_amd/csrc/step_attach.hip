@@ -295,6 +295,33 @@ int check_ilqr_step(const covo_ctx *h, int n_inst, bool sharded, int derive_keys
     return 0;
 }
 
+// ---- what a step in COVO_MODE_CMA checks ahead of check_step_attachments, for every entry point alike: its attachment, the two
+// targets the next step reads, and nothing that decides a Sigma another way
+int check_cma_step(const covo_ctx *h, int n_inst, bool sharded, const float *a_cov, const char *what)
+{
+    REQUIRE(!sharded,
+            "%s: a CMA step (COVO_MODE_CMA) is not available for sample-sharded steps (partial_out != NULL): it needs the posterior "
+            "covariance and the diagnostics, which sample-sharded steps cannot have; run it on one rank", what);
+    REQUIRE(covo_cma_on(h), "%s: a CMA step (COVO_MODE_CMA) without covo_set_step_cma on the handle: its rows and its path live there; "
+            "attach them", what);
+    REQUIRE(n_inst <= h->cma_n, "%s: %d instances, the CMA rows (covo_set_step_cma) have n_inst=%d", what, n_inst, h->cma_n);
+    REQUIRE(covo_post_cov_on(h), "%s: a CMA step (COVO_MODE_CMA) without a posterior covariance target: the next step adapts to the "
+            "covariance and the displacement this one leaves there; attach one (covo_set_step_post_cov)", what);
+    REQUIRE(h->post_aux_out != nullptr, "%s: a CMA step (COVO_MODE_CMA) needs the posterior covariance's side rows (covo_set_step_post_cov, "
+            "aux): the step size reads the displacement and the weight sum there", what);
+    REQUIRE(covo_diag_target(h) != nullptr, "%s: a CMA step (COVO_MODE_CMA) without a diagnostics target: the next step reads this one's "
+            "effective sample size there; attach one (covo_set_step_diag)", what);
+    REQUIRE(covo_sigma_period(h) == 1, "%s: a CMA step (COVO_MODE_CMA) together with a Sigma period (covo_set_step_sigma_period, "
+            "period=%d): it adapts its covariance every step and never refreshes one; set period = 1", what, covo_sigma_period(h));
+    REQUIRE(!covo_sigma_adapt_on(h), "%s: a CMA step (COVO_MODE_CMA) together with Sigma adapt (covo_set_step_sigma_adapt, gamma=%g): "
+            "the step runs that blend itself at covo_set_step_cma's gamma; turn it off (gamma = 0)", what, (double)h->adapt_gamma);
+    REQUIRE(!covo_sigma_nodes_on(h), "%s: a CMA step (COVO_MODE_CMA) together with Sigma in node space (covo_set_step_sigma_nodes, "
+            "M=%d): it forms no Hessian; turn it off (a null W)", what, h->sn_M);
+    REQUIRE(a_cov != nullptr && ((uintptr_t)a_cov & 15) == 0, "%s: a CMA step (COVO_MODE_CMA) needs a_cov (float[128][128] per "
+            "instance, 16-byte aligned): the shape is formed and scaled there", what);
+    return 0;
+}
+
 // an episode driver that writes rows [first_row, first_row + n_steps) of every attached log (the single driver: first_row = 0)
 int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, const char *what)
 {
@@ -312,7 +339,7 @@ int check_episode_logs(const covo_ctx *h, int first_row, int n_steps, const char
 // have passed
 int check_single_step(const covo_ctx *h, const covo_env_params *params, const covo_step_args *args, const char *what)
 {
-    REQUIRE(args->mode >= 0 && args->mode <= COVO_MODE_ILQR, "%s: mode=%d", what, args->mode);
+    REQUIRE((args->mode >= 0 && args->mode <= COVO_MODE_ILQR) || args->mode == COVO_MODE_CMA, "%s: mode=%d", what, args->mode);
     REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "%s: n_samples=%d outside (0, %d]", what, args->n_samples,
             h->cfg.n_local);
     REQUIRE(args->state && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost && args->groupmin && args->T > 0,
@@ -328,6 +355,8 @@ int check_single_step(const covo_ctx *h, const covo_env_params *params, const co
             "%s: a_mean, a_mean_in and a_cov must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
     if (args->mode == COVO_MODE_ILQR)
         if (int rc = check_ilqr_step(h, 1, args->partial_out != nullptr, args->derive_keys, what)) return rc;
+    if (args->mode == COVO_MODE_CMA)
+        if (int rc = check_cma_step(h, 1, args->partial_out != nullptr, args->a_cov, what)) return rc;
     return check_step_attachments(h, args->n_samples, 1, args->partial_out != nullptr, args->derive_keys, args->mode, args->a_cov, params, what,
                                   args->gamma_sigma);
 }
@@ -357,7 +386,8 @@ int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo_batch_
     REQUIRE(args->n_samples > 0 && args->n_samples <= h->cfg.n_local, "%s: n_samples=%d outside (0, %d]", what, args->n_samples,
             h->cfg.n_local);
     const int mode = m ? m->mode : COVO_MODE_COVO_ONLINE;
-    REQUIRE(mode == COVO_MODE_MPPI || mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_COVO_OFFLINE || mode == COVO_MODE_ILQR,
+    REQUIRE(mode == COVO_MODE_MPPI || mode == COVO_MODE_COVO_ONLINE || mode == COVO_MODE_COVO_OFFLINE || mode == COVO_MODE_ILQR ||
+                mode == COVO_MODE_CMA,
             "%s: mode=%d is not a COVO_MODE_*", what, mode);
     REQUIRE(args->states && args->pos_traj && args->vel_traj && args->a_mean && args->a && args->cost &&
                 (args->groupmin || mode != COVO_MODE_COVO_ONLINE) && args->T > 0,
@@ -381,6 +411,14 @@ int check_batch_step(covo_ctx *h, const covo_batch_args *args, const covo_batch_
         if ((rc = check_ilqr_step(h, args->n_envs, false, 1, what))) return rc;
         REQUIRE(h->plan_hold <= 1 || ((uintptr_t)args->a_mean & 15) == 0,
                 "%s: a_mean must be 16-byte aligned under the plan hold (covo_set_step_plan_hold)", what);
+        return check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, params, what);
+    }
+    if (mode == COVO_MODE_CMA) {  // covo-online's staged batch: its own list, then the attachments'
+        if ((rc = check_cma_step(h, args->n_envs, false, args->a_cov, what))) return rc;
+        REQUIRE(args->groupmin != nullptr, "%s: a CMA step (COVO_MODE_CMA) needs base.groupmin (float[n_envs][ceil(n_samples / 64)])", what);
+        REQUIRE(!covo_riccati_on(h), "%s: the Riccati refinement (covo_set_step_riccati) is not available for the env-batched CMA step: "
+                "that batch carries no per-instance Hessian constants for it; detach it", what);
+        REQUIRE(h->plan_hold <= 1, "%s: the plan hold (covo_set_step_plan_hold) is not available for a CMA step; set period = 1", what);
         return check_step_attachments(h, args->n_samples, args->n_envs, false, 1, mode, args->a_cov, params, what);
     }
     // covo_set_step_batched_staged: the MPPI / covo-offline batch runs its staged launch sequence, which takes what the fused launch

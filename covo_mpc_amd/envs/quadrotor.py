@@ -619,11 +619,15 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
     by "ilqr"): every sweep solves the control-limited stage problem (check_riccati_box).  controller="dial": BatchedDialController
     (annealed MPPI, always staged) under iters / beta_pass / beta_stage / temp (check_dial; the other controllers ignore the last three);
     rows=True then also holds "lam": ep.read_lam(), the last pass's solver rows, when temp is given.  nodes=M / node_interp (keyword-only,
-    "dial" only): the spline-node perturbations of check_dial."""
-    if controller not in ("covo-online", "mppi", "covo-offline", "ilqr", "dial"):
-        raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline', 'ilqr' or 'dial'")
+    "dial" only): the spline-node perturbations of check_dial.  controller="cma": BatchedCMAController at its defaults (this signature
+    carries none of its keywords; _eval_cma_batched); rows=True then also holds "cma", the instances' last rows."""
+    if controller not in ("covo-online", "mppi", "covo-offline", "ilqr", "dial", "cma"):
+        raise ValueError(f"controller={controller!r}: eval_env_batched runs 'covo-online', 'mppi', 'covo-offline', 'ilqr', 'dial' or 'cma'")
     opts = take({**STEP_OPTION_DEFAULTS, **locals(), "compute_diag": diag, "compute_plan": trace, "compute_fan": fan})
     switches = take_switches(locals())
+    if controller == "cma":
+        return _eval_cma_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, fan, arbiter, rows, staged, switches,
+                                 opts)
     if controller == "ilqr":
         return _eval_ilqr_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, rows, staged, arbiter, switches,
                                   opts)
@@ -683,6 +687,51 @@ def eval_env_batched(env: Quad3D, n_envs: int, controller_params: str = "N4096_H
         if dial:
             reads["lam"] = ("lamlog", ep.read_lam)
         out += ({name: read() for name, (attr, read) in reads.items() if getattr(ep, attr) is not None},)
+    return out if len(out) > 1 else out[0]
+
+
+def _eval_cma_batched(env, n_envs, controller_params, n_steps, seed, device, verbose, trace, fan, arbiter, rows, staged, switches, opts):
+    """eval_env_batched(controller="cma"): BatchedCMAController (controllers/cma.py) at its defaults -- gamma=0.2, step_size=True,
+    damping=1, s_min=0.1, s_max=4: eval_env_batched's signature is pinned and carries none of them -- on the same instances and keys.
+    diag and compute_post_cov are implied; trace / fan / update (with arbiter) / iters / elite pass through; sigma_period, sigma_adapt, a
+    switch or staged=True is a ValueError (check_cma).  rows=True then also holds "cma": the instances' last rows [n_envs, 8]."""
+    from .. import controllers
+    from ..controllers._options import check_cma
+    check_cma(sigma_period=opts["sigma_period"], sigma_adapt=opts["sigma_adapt"], **switches, what="the env-batched CMA controller")
+    if staged:
+        raise ValueError("staged=True with controller='cma': its batch is a staged launch sequence already")
+    if arbiter and opts["update"] == "softmax":
+        raise ValueError("arbiter=True needs update='best' or 'guarded': under 'softmax' no arbiter is attached")
+    kw = dict(compute_plan=opts["compute_plan"], compute_fan=opts["compute_fan"], update=opts["update"], iters=opts["iters"],
+              elite=opts["elite"])
+    check_step_options(None, "the env-batched CMA controller", **kw)
+    rng = crandom.PRNGKey(seed)
+    ks = crandom.split(rng, 3 * n_envs + 1)
+    params = [env.sample_params(ks[e]) for e in range(n_envs)]
+    N, H, lam = (lambda p: (int(p[0][1:]), int(p[1][1:]), float(p[2][3:])))(controller_params.split("_"))
+    device = device if device is not None else (env.device if env.device is not None else "cuda")
+    dp = env.default_params
+    import torch
+    a_mean = torch.tensor([(dp.m * dp.g / dp.max_thrust) * 2.0 - 1.0, 0.0, 0.0, 0.0], dtype=torch.float32, device=device).repeat(H, 1)
+    b = controllers.BatchedCMAController(env, n_envs, N, H, lam, a_mean_init=a_mean, device=device, **kw)
+    ep = BatchedDeviceEpisode(env, ks[n_envs:2 * n_envs], params, (b.core.lib, b.core.h), b.core.device)
+    b.reset()
+    T = params[0].max_steps_in_episode if n_steps is None else int(n_steps)
+    t0 = time_module.time()
+    b.run_episode(ep, ks[2 * n_envs:3 * n_envs], T)
+    log = ep.read_log()
+    if verbose:
+        el = time_module.time() - t0
+        s = b.cma_rows[:, 0].cpu().numpy()
+        print(f"{n_envs} instances x {T} steps in {el:.2f}s = {n_envs * T / el:.0f} env-steps/s; err_pos mean over instances: "
+              f"{log[:, :, 1].mean():.3f}; last step sizes in [{s.min():.3f}, {s.max():.3f}]")
+    out = ((log[:, :, 1].mean(axis=1),) + ((ep.read_trace(),) if trace else ()) + ((ep.read_fan(),) if fan else ()) +
+           ((ep.read_arbiter(),) if arbiter else ()))
+    if rows:
+        reads = {"elite": ("elitelog", ep.read_elite), "iters": ("iterlog", ep.read_iters), "post": ("postlog", ep.read_post)}
+        found = {name: read() for name, (attr, read) in reads.items() if getattr(ep, attr) is not None}
+        found["cma"] = b.cma_rows.cpu().numpy()
+        out += (found,)
     return out if len(out) > 1 else out[0]
 
 
@@ -870,6 +919,24 @@ def get_controller(env, controller_name, controller_params=None, debug=False, de
     if controller_name == "dial":
         dial_opts = _check_dial_keywords(opts, switches, process_group, beta_pass, beta_stage, temp, nodes, node_interp)
     import torch
+    if controller_name == "cma":
+        # the CMA controller at its defaults (gamma=0.2, step_size=True, damping=1, s_min=0.1, s_max=4: this signature is pinned and
+        # carries none of them; build controllers.CMAController for others).  check_cma refuses sigma_period, sigma_adapt, the switches
+        # and a process_group; compute_diag and compute_post_cov are implied
+        from ..controllers._options import check_cma
+        check_cma(sigma_period=sigma_period, sigma_adapt=sigma_adapt, process_group=process_group, **switches)
+        N, H, lam = ((lambda p: (int(p[0][1:]), int(p[1][1:]), float(p[2][3:])))(controller_params.split("_")) if controller_params
+                     else (8192, 32, 0.01))
+        device = device if device is not None else (env.device if env.device is not None else "cuda")
+        dp = env.default_params
+        th = (dp.m * dp.g / dp.max_thrust) * 2.0 - 1.0
+        control_params = controllers.CMAParams(
+            gamma_mean=1.0, discount=1.0, sample_sigma=0.5,
+            a_mean=torch.tensor([th, 0.0, 0.0, 0.0], dtype=torch.float32, device=device).repeat(H, 1),
+            a_cov=torch.eye(H * env.action_dim, dtype=torch.float32, device=device) * 0.25)
+        return controllers.CMAController(env=env, control_params=control_params, N=N, H=H, lam=lam, device=device,
+                                         compute_info=compute_info, compute_plan=compute_plan, compute_fan=compute_fan, update=update,
+                                         ess_min=ess_min, elite=elite, iters=iters), control_params
     if controller_name == "ilqr":
         H = int(controller_params.split("_")[1][1:]) if controller_params else 32
         device = device if device is not None else (env.device if env.device is not None else "cuda")

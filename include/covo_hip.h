@@ -1069,6 +1069,58 @@ int covo_riccati_refine_box(covo_handle_t h, const float *state, const float *po
                             float *fb_rows_out, int32_t feedback, int32_t *masks_out, void *stream);
 int covo_set_step_riccati_box(covo_handle_t h, int32_t *masks /* DEVICE [n_inst][H]; NULL = off */, int32_t n_inst);
 int covo_set_step_ilqr_box(covo_handle_t h, int32_t *counts /* DEVICE [n_inst][COVO_MAX_STEP_ITERS]; NULL = off */, int32_t n_inst);
+
+/* The CMA controller: a full 128 x 128 covariance learned from the samples, with cumulative step-size adaptation (additive to ABI 10:
+ * COVO_HAS_CMA; a fifth step mode -- a handle never stepped in it launches, allocates and captures what it always did).  n = 128,
+ * sigma0 = sample_sigma, S the Sigma period's shift.  Per instance the handle keeps the factor L the previous step sampled from (fp32,
+ * step size included), the evolution path p (fp64 [128], in the caller's path_out) and log s (fp64), s the step size relative to sigma0.
+ * A reset leaves L = sigma0 I, p = 0, log s = 0.  The first step after a reset samples from sigma0^2 I, adapts nothing and writes the
+ * neutral row {1, 0, 0, 0, 0, 0, 0, 0}.  Every later step, before it samples:
+ *   shape   Sigma_hat' = c ((1 - gamma) S(L L^T) + gamma S(C)), log det Sigma_hat' = 2 n log sigma0, L_hat' its factor: covo_sigma_adapt
+ *           as it is, on the handle's L and the posterior covariance C the previous step left in the covo_set_step_post_cov target,
+ *           into a second buffer; its fall-back (the gamma = 0 result) is kept and reported as flag 4
+ *   step size (csrc/cma_path.hip, fp64): z = L^-1 d by forward substitution on the previous factor, d the previous step's mean
+ *           displacement (the posterior side row); mu_eff = clamp(ess, 1, N), ess the previous step's diagnostics' ess (K under the
+ *           elite set); c_s = (mu_eff + 2) / (n + mu_eff + 5); d_s = damping (1 + 2 max(0, sqrt((mu_eff - 1) / (n + 1)) - 1) + c_s);
+ *           p <- (1 - c_s) p + sqrt(c_s (2 - c_s) mu_eff) z;   log s <- clamp(log s + (c_s / d_s) (|p| / chi_n - 1), log s_min, log s_max),
+ *           chi_n = sqrt(n) (1 - 1/(4n) + 1/(21 n^2)).  p is not shifted: in whitened coordinates it is treated as isotropic.
+ *   scale   L' = fp32(s L_hat') becomes the handle's factor, Sigma' = fp32(s^2 Sigma_hat') the step's a_cov, each rounded once; the
+ *           strict upper triangle of L' stays exact zeros, Sigma' symmetric bit for bit
+ *   and it samples clip(shift(mu) + L' eps) with the step's own in-kernel Philox draw; rollout, update, after-step and posterior
+ *   launches are the existing ones.  Under covo_set_step_iters every pass samples from the step's one L'; the next step reads the last
+ *   pass's C, d and ess.
+ * Device-side fall-backs of the step size, reported in the row's flag word and never an error: 1 -- p and log s are left as they are
+ *   (W is not a positive finite number, ess or an entry of d or z is not finite, or a diagonal entry of L is not positive and finite);
+ *   2 -- the clamp was hit; 4 -- the shape kernel fell back.  The state is mended on entry: a log s that is not finite counts as 0 and
+ *   is then held inside [log s_min, log s_max], a path with an entry that is not finite counts as 0; so s always lies in
+ *   [s_min, s_max], on a fall-back too, and L' is finite whenever L_hat' is.
+ * covo_set_step_cma: 0 <= gamma < 1; step_size = 0 keeps s = 1 (the kernel only copies; row and path stay neutral); damping > 0;
+ *   0 < s_min <= 1 <= s_max; rows_out = DEVICE float[n_inst][COVO_CMA_FLOATS] = {s, log s, |p|, |z|, mu_eff, c_s, d_s, flags} (16-byte
+ *   aligned; after a fall-back of kind 1 the entries |z| .. d_s are 0), path_out = DEVICE double[n_inst][128]: the handle's path lives
+ *   there between steps -- read it, do not write it.  rows_out = NULL detaches.  Resets the state and drops the captured step graphs.
+ * covo_cma_reset: the next step in COVO_MODE_CMA is a first step.
+ * covo_cma_path: the step-size kernel alone on the caller's buffers.  L_prev, L_hat, Sigma_hat, L_out, Sigma_out = DEVICE
+ *   float[batch][128][128]; aux = instance e's {d[128], W, ...} at aux + e * aux_stride floats; ess = instance e's at ess + e *
+ *   ess_stride floats; shape_rows = covo_sigma_adapt's rows or NULL; p = DEVICE double[batch][128] and log_s = DEVICE double[batch],
+ *   in place; rows_out as above.  Matrices and rows 16-byte aligned.  L_out may be L_prev and Sigma_out may be Sigma_hat.  It writes
+ *   p and log_s (on a fall-back: their mended entry values), L_out, Sigma_out and rows_out, nothing else, and launches on hip_stream, the
+ *   caller's stream (a hipStream_t as void *, like every other entry's `stream`).
+ * COVO_MODE_CMA goes through covo_mpc_step and covo_run_episode.  Refused at the step with COVO_E_BADARG, before any launch: no
+ *   covo_set_step_cma on the handle; no covo_set_step_post_cov or covo_set_step_diag target; a sample-sharded step; a Sigma period
+ *   above 1; Sigma adapt or Sigma in node space attached; a_cov NULL or not 16-byte aligned; more instances than rows.
+ * covo_debug_time_step refuses the mode, covo_debug_time_batched refuses while the batch's last step was one: a replayed copy would adapt.
+ * The mode's number is 5: 4 stays an invalid mode. */
+#define COVO_HAS_CMA 1
+#define COVO_MODE_CMA 5
+#define COVO_CMA_FLOATS 8
+int covo_set_step_cma(covo_handle_t h, float gamma, int32_t step_size, float damping, float s_min, float s_max,
+                      float *rows_out /* DEVICE [n_inst][COVO_CMA_FLOATS]; NULL = off */, double *path_out /* DEVICE [n_inst][128] */,
+                      int32_t n_inst);
+int covo_cma_reset(covo_handle_t h);
+int covo_cma_path(covo_handle_t h, const float *L_prev, const float *aux, int32_t aux_stride, const float *ess, int32_t ess_stride,
+                  const float *L_hat, const float *Sigma_hat, const float *shape_rows, int32_t batch, int32_t n_samples, int32_t step_size,
+                  float damping, float s_min, float s_max, double *p, double *log_s, float *L_out, float *Sigma_out, float *rows_out,
+                  void *hip_stream);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

@@ -32,6 +32,9 @@ name = sys.argv[1]
 # (controllers/dial.py; defaults: get_controller's iters=1, 0.5 / 0.9 / 0.1); compare with `mppi iters=k`.  With temp every seed's line
 # also carries the share of steps whose last pass fell back to the configured temperature (the temperature log's bit 31 of entry 3)
 # python scripts/eval_seeds.py dial iters=k nodes=M [node_interp=cubic]: the same controller with spline-node perturbations
+# python scripts/eval_seeds.py cma [gamma=g] [damping=d] [s_min=a] [s_max=b] [step_size=0] [iters=k] [elite=K] [ess_min=e]: the CMA
+# controller (controllers/cma.py; defaults gamma=0.2, damping=1, s_min=0.1, s_max=4); every seed's line also carries the step size and
+# the flag word the last episode ended with
 rest = sys.argv[2:]
 # the boolean step switches as flags: --refine, --riccati, --riccati-feedback, --riccati-box
 flags = {f"--{s.replace('_', '-')}": s for s, default in STEP_SWITCH_DEFAULTS.items() if isinstance(default, bool)}
@@ -41,14 +44,22 @@ for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_a
     while flag in rest:
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
-FLOATS = ("sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp")
+FLOATS = ("sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp", "gamma", "damping", "s_min", "s_max")
+CMA_KEYS = ("gamma", "damping", "s_min", "s_max", "step_size")
 opts = {k: (None if v.lower() == "none" else v if k == "node_interp" else float(v) if k in FLOATS else int(v))
         for k, v in (arg.split("=") for arg in rest)}
 switches["plan_hold"] = opts.pop("plan_hold", 1)
-assert set(opts) <= {"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"} | ({"beta_pass", "beta_stage", "temp", "nodes", "node_interp"} if name == "dial" else set()), opts
+assert set(opts) <= ({"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"} |
+                     ({"beta_pass", "beta_stage", "temp", "nodes", "node_interp"} if name == "dial" else set()) |
+                     (set(CMA_KEYS) if name == "cma" else set())), opts
+cma_kw = {k: (bool(opts.pop(k)) if k == "step_size" else opts.pop(k)) for k in CMA_KEYS if k in opts}
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
                disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
 ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **switches, **opts)
+if cma_kw:  # (get_controller's signature carries none of them: the controller is built again with them)
+    from covo_mpc_amd import controllers
+    ctrl.core.close()
+    ctrl = controllers.CMAController(env, cp, ctrl.N, ctrl.H, ctrl.lam, **cma_kw, **{k: v for k, v in opts.items() if k in ("elite", "ess_min", "iters")})
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
@@ -99,6 +110,9 @@ def rows_of(ep):
         rows["held"] = rows.get("held", 0) + int(held.sum())
         rows["stale"] = rows.get("stale", 0) + int(((hold["flags"] & 4) != 0)[held].sum())
         rows["clipped"] = rows.get("clipped", 0) + int((hold["clipped"] > 0)[held].sum())
+    if name == "cma":
+        row = core.cma_rows[0].cpu().numpy()
+        rows["cma_s"], rows["cma_flags"] = float(row[0]), float(row[7])
     rows["steps"] = rows.get("steps", 0) + ep.n_steps
 
 
@@ -122,7 +136,8 @@ for seed in range(1, 13):
                                                            ("closed", "  plan steps with a closed-loop commit: %.3f", npl),
                                                            ("boxed", "  plan steps with a live box: %.3f", npl),
                                                            ("stale", "  hold steps on another trajectory's plan: %.3f", nh),
-                                                           ("clipped", "  hold steps with a clipped component: %.3f", nh)) if k in rows)
+                                                           ("clipped", "  hold steps with a clipped component: %.3f", nh),
+                                                           ("cma_s", "  last step size: %.3f", 1), ("cma_flags", "  last flags: %d", 1)) if k in rows)
     print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()) + extra,
           flush=True)
 allerr = np.concatenate(allerr)
