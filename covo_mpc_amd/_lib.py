@@ -96,6 +96,14 @@ COVO_HAS_ILQR = 1  # the "ilqr" controller (COVO_MODE_ILQR, covo_set_step_ilqr):
 COVO_ILQR_FLOATS = 8
 COVO_HAS_CMA = 1  # the "cma" controller (COVO_MODE_CMA, covo_set_step_cma): a learned full covariance with step-size control
 COVO_CMA_FLOATS = 8  # its row of one instance: {s, log s, |p|, |z|, mu_eff, c_sigma, d_sigma, flags}
+# controllers.StateEstimator (covo_set_step_estimator, covo_estimate, covo_set_episode_estimator_log): an EKF between env step and control
+# step.  Its side row: {bits(int32 flags), nis, |nu_pos|, |x - z|_pos, tr P_pos, tr P_vel, smallest pivot of S, bits(int32 time word)};
+# flags 1: initialised, 2: re-initialised (time word), 4: a measured coordinate not finite, 8: the update failed
+COVO_HAS_STATE_ESTIMATOR = 1
+COVO_EST_FLOATS = 8
+COVO_EST_STATE_DOUBLES = 16  # per instance: the estimate [13], then the force of the row last seen [3]
+COVO_EST_META_INTS = 2       # {valid, the time word of the row last seen}
+COVO_EST_LOG_FLOATS = 34     # a row of the episode log: measured [13], written [13], the side row [8]
 ILQR_FIELDS = ("cost_first", "cost", "moved", "fixed_at", "closed", "flags", "grad_norm")
 # riccati_box= on top of riccati= (covo_set_step_riccati_box, covo_riccati_box, covo_riccati_refine_box): the sweep's stages solve the
 # box QP on -1 <= clip(b) + du <= 1.  A mask word per stage: bits 0-3 coordinate i clamped at the lower bound, bits 4-7 at the upper
@@ -306,6 +314,12 @@ _SIGS = {
     "covo_cma_path": (C.c_int, [_P, _P, _P, C.c_int32, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_float,
                                 C.c_float, _P, _P, _P, _P, _P, _P]),
     "covo_debug_ilqr_costs": (C.c_int, [_P, _P, C.c_int32]),
+    # the state estimator (covo_hip.h: COVO_HAS_STATE_ESTIMATOR)
+    "covo_set_step_estimator": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, _P, _P, _P, _P, C.c_int32]),
+    "covo_estimator_reset": (C.c_int, [_P]),
+    "covo_estimate": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, _P,
+                                _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "covo_set_episode_estimator_log": (C.c_int, [_P, _P, C.c_int32]),
     # the Riccati box (covo_hip.h: COVO_HAS_RICCATI_BOX)
     "covo_riccati_box": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P,
                                    _P]),

@@ -8,3 +8,4 @@ from .batched import BatchedCMAController, BatchedCoVOController, BatchedDialCon
 from .ilqr import ILQRBoxController, ILQRController, ILQRParams  # noqa: F401
 from .dial import DialController  # noqa: F401
 from .cma import CMAController, CMAParams  # noqa: F401
+from .estimator import StateEstimator  # noqa: F401

@@ -425,7 +425,8 @@ class SamplingCore:
             (self.riccati_box_masks is not None, self.riccati_box_info),
             (getattr(self, "sigma_nodes_rows", None) is not None, self.sigma_nodes_info),
             (getattr(self, "anneal_rows", None) is not None, self.anneal_info),
-            (getattr(self, "cma_rows", None) is not None, self.cma_info)) if on]
+            (getattr(self, "cma_rows", None) is not None, self.cma_info),
+            (getattr(self, "estimator", None) is not None, self.estimator_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -460,6 +461,7 @@ class SamplingCore:
         for name in EPISODE_LOGS:
             self.attach_log(name, episode, rows_left)
         self.attach_hold_log(episode, rows_left)
+        self.attach_estimator_log(episode, rows_left)
 
     def attach_hold_log(self, episode, rows_left: int):
         """Bind `episode`'s hold log (episode.holdlog, [.., T + 1, 8]; allocated on first use) under plan_hold > 1: the hold launch,
@@ -727,6 +729,99 @@ class SamplingCore:
                                          float(damping), float(s_min), float(s_max), ptr(p), ptr(log_s), ptr(L_out), ptr(Sigma_out),
                                          ptr(rows), self.stream()), "covo_cma_path")
         return L_out, Sigma_out, rows
+
+    # ---- the state estimator (controllers.StateEstimator; csrc/state_estimator.hip)
+    estimator = None  # the _options.Estimator record while one is attached
+
+    def attach_estimator(self, est):
+        """covo_set_step_estimator (est: the record _options.check_estimator returns): self.est_rows [rows, 8] -- instance e's side row
+        of every launch --, self.est_xhat [rows, 16] float64 (the estimate [13], then the force of the row last seen), self.est_P
+        [rows, 13, 13] float64 and self.est_meta [rows, 2] int32 {valid, time word}: the filter's state lives there between steps.
+        The episode drivers then run the launch behind every env step; the host path goes through estimated()."""
+        torch = self.torch
+        if self.world > 1:
+            raise NotImplementedError("the state estimator on sample-sharded ranks: covo_set_step_estimator refuses sample-sharded steps")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        self.est_rows = torch.zeros((self._rows, _lib.COVO_EST_FLOATS), dtype=torch.float32, device=self.device)
+        self.est_xhat = torch.zeros((self._rows, _lib.COVO_EST_STATE_DOUBLES), **f64)
+        self.est_P = torch.zeros((self._rows, 13, 13), **f64)
+        self.est_meta = torch.zeros((self._rows, _lib.COVO_EST_META_INTS), dtype=torch.int32, device=self.device)
+        obs, proc = (C.c_double * 4)(*est.obs_std), (C.c_double * 4)(*est.proc_std)
+        check(self.lib.covo_set_step_estimator(self.h, obs, proc, float(est.force_std), ptr(self.est_xhat), ptr(self.est_P),
+                                               ptr(self.est_meta), ptr(self.est_rows), self._rows), "covo_set_step_estimator")
+        self.estimator = est
+        self._list_infos()
+
+    def detach_estimator(self):
+        """covo_set_step_estimator(NULL): the drivers and estimated() are what they were; the buffers stay readable."""
+        check(self.lib.covo_set_step_estimator(self.h, None, None, 0.0, None, None, None, None, 0), "covo_set_step_estimator")
+        self.estimator = None
+        self._list_infos()
+
+    def estimator_reset(self):
+        """covo_estimator_reset: the next launch -- a driver's, or estimated()'s -- treats every instance as one without a valid state."""
+        check(self.lib.covo_estimator_reset(self.h), "covo_estimator_reset")
+
+    def estimator_info(self) -> dict:
+        """{"est_rows" [8], "est_flags" (int32: 1 initialised, 2 re-initialised, 4 measurement not finite, 8 update failed), "est_nis"}
+        of the last launch as views of self.est_rows (no sync, no copy); {} with nothing attached."""
+        if self.estimator is None:
+            return {}
+        row = self.est_rows[0]
+        return {"est_rows": row, "est_flags": row[0:1].view(self.torch.int32)[0], "est_nis": row[1]}
+
+    def estimate(self, state_rows, u, params_c, xhat, P, meta, *, rows=None, obs_std, proc_std, force_std=0.0, reset=False, u_stride=None):
+        """covo_estimate (the stand-alone launch), IN PLACE on state_rows: float32 device tensor [32] or [E, 32], contiguous; u float32
+        with instance e's action at u.reshape(-1)[e * u_stride:][:4] (u_stride None: u is [E, 4]); params_c: one EnvParamsC or an
+        array of E; xhat float64 [E, 16], P float64 [E, 13, 13], meta int32 [E, 2]: the filter's state, updated in place; obs_std,
+        proc_std: four standard deviations each (a negative proc_std[1]: dt force_std / m).  reset: every instance counts as one
+        without a valid state (-1: when covo_estimator_reset was called on the handle since its last launch).  -> rows [E, 8]."""
+        torch = self.torch
+        E = int(state_rows.numel()) // _lib.COVO_STATE_FLOATS
+        assert state_rows.dtype == torch.float32 and state_rows.is_contiguous() and u.dtype == torch.float32 and u.is_contiguous()
+        assert xhat.dtype == torch.float64 and P.dtype == torch.float64 and meta.dtype == torch.int32
+        assert xhat.numel() == E * _lib.COVO_EST_STATE_DOUBLES and P.numel() == E * 169 and meta.numel() == E * _lib.COVO_EST_META_INTS
+        assert xhat.is_contiguous() and P.is_contiguous() and meta.is_contiguous()
+        stride = 4 if u_stride is None else int(u_stride)
+        assert u.numel() >= (E - 1) * stride + 4
+        if isinstance(params_c, _lib.EnvParamsC):
+            params_c = (_lib.EnvParamsC * E)(*([params_c] * E))
+        rows = torch.zeros((E, _lib.COVO_EST_FLOATS), dtype=torch.float32, device=self.device) if rows is None else rows
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_estimate(self.h, ptr(state_rows), ptr(u), stride, params_c, (C.c_double * 4)(*obs_std),
+                                         (C.c_double * 4)(*proc_std), float(force_std), ptr(xhat), ptr(P), ptr(meta), ptr(rows), E,
+                                         int(reset), self.stream()), "covo_estimate")
+        return rows
+
+    def estimated(self, dstate, a_mean, params_c):
+        """The one hook of the controllers' host path: the state the step plans from.  With nothing attached: dstate itself.  Otherwise a
+        DeviceState whose packed row is a copy of dstate's with its 13 kinematic floats replaced by the estimate -- the attached filter's
+        launch with u = the first four entries of a_mean, the mean that came into the call.  params_c: the step's EnvParamsC, or a
+        callable that returns it (called only when attached).  A [E, 32] tensor (the batched controllers' state buffer) is estimated in
+        place, with instance e's u at a_mean[e, :4]."""
+        est = self.estimator
+        if est is None:
+            return dstate
+        if callable(params_c):
+            params_c = params_c()
+        kw = dict(rows=self.est_rows, obs_std=est.obs_std, proc_std=est.proc_std, force_std=est.force_std, reset=-1)
+        if self.torch.is_tensor(dstate):
+            self.estimate(dstate, a_mean.reshape(-1), params_c, self.est_xhat, self.est_P, self.est_meta, u_stride=COVO_NA, **kw)
+            return dstate
+        import dataclasses
+        row = dstate.packed.clone()
+        self.estimate(row, a_mean.reshape(-1)[:4].contiguous(), params_c, self.est_xhat, self.est_P, self.est_meta, **kw)
+        return dataclasses.replace(dstate, packed=row)
+
+    def attach_estimator_log(self, episode, rows_left: int):
+        """Bind `episode`'s estimator log (episode.estlog, [.., T + 1, 34]; allocated on first use) while an estimator is attached: its
+        launch writes the rows itself (covo_set_episode_estimator_log), like the hold log's."""
+        if self.estimator is None:
+            return
+        if getattr(episode, "estlog", None) is None:
+            episode.alloc_estimator_log()
+        check(self.lib.covo_set_episode_estimator_log(self.h, ptr(episode.log_segment("estlog")), int(rows_left)),
+              "covo_set_episode_estimator_log")
 
     @property
     def lam_logged(self) -> bool:

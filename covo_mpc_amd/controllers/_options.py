@@ -702,3 +702,60 @@ def check_sigma_nodes(sigma_nodes, node_interp="linear", *, what="online", sigma
     if sharded:
         raise NotImplementedError(f"sigma_nodes={M} on sample-sharded ranks: covo_set_step_sigma_nodes refuses sample-sharded steps")
     return SigmaNodes(M=M, node_interp=node_interp, weights=node_basis(M, node_interp))
+
+
+@dataclass(frozen=True)
+class Estimator:
+    """What check_estimator returns: the four measurement and the four process standard deviations (pos, vel, quat, omega; a negative
+    velocity entry of proc_std: derive it from force_std and the instance's own dt and m) and force_std."""
+    obs_std: tuple
+    proc_std: tuple
+    force_std: float
+
+
+OBS_GROUP_SCALE = (0.25, 0.5, 0.02, 0.5)  # the env step's noise on pos, vel, quat, omega per unit obs_noise_scale (quadrotor.py:356-361)
+
+
+def check_estimator(*, n_inst=1, obs_std=None, proc_std=None, force_std=None, obs_noise_scale=0.05, dyn_noise_scale=0.05,
+                    process_group=None, materialize_eps=False, noise_stream="philox", what="the state estimator") -> Estimator:
+    """The keywords of controllers.StateEstimator -> the Estimator record SamplingCore.attach_estimator attaches.  The C side's
+    counterpart is estimator_fill_model (csrc/state_estimator.hip).
+
+    obs_std=None: obs_noise_scale (0.25, 0.5, 0.02, 0.5), the env step's own noise; proc_std=None: (0, derive, 0, 0), the velocity
+    allowance dt force_std / m of a force the model does not know; force_std=None: dyn_noise_scale.
+
+    The objections, each naming the keyword: n_inst anything but an integer in [1, COVO_MAX_ENVS]; obs_std anything but four positive
+    finite real numbers; proc_std anything but four finite real numbers >= 0 (the velocity entry may be negative: derive); force_std
+    anything but a finite real number >= 0 (ValueError); then process_group (NotImplementedError: sample-sharded ranks) and the
+    kernel-by-kernel path, materialize_eps / noise_stream="jax" (NotImplementedError)."""
+    import math
+    import numbers
+
+    def real(v):
+        return not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v))
+
+    def four(v):
+        try:
+            v = tuple(v)
+        except TypeError:
+            return None
+        return v if len(v) == 4 and all(real(x) for x in v) else None
+    if isinstance(n_inst, bool) or not isinstance(n_inst, numbers.Integral) or not 1 <= int(n_inst) <= _lib.COVO_MAX_ENVS:
+        raise ValueError(f"n_inst={n_inst!r} with {what}: an integer in [1, {_lib.COVO_MAX_ENVS}]")
+    obs = tuple(float(obs_noise_scale) * g for g in OBS_GROUP_SCALE) if obs_std is None else four(obs_std)
+    if obs is None or not all(float(x) > 0.0 for x in obs):
+        raise ValueError(f"obs_std={obs_std!r} with {what}: four positive finite standard deviations (pos, vel, quat, omega), or None for "
+                         "the env step's own")
+    proc = (0.0, -1.0, 0.0, 0.0) if proc_std is None else four(proc_std)
+    if proc is None or any(float(x) < 0.0 for i, x in enumerate(proc) if i != 1):
+        raise ValueError(f"proc_std={proc_std!r} with {what}: four finite standard deviations >= 0 (pos, vel, quat, omega; a negative "
+                         "velocity entry derives dt force_std / m), or None")
+    fs = float(dyn_noise_scale) if force_std is None else force_std
+    if not real(fs) or float(fs) < 0.0:
+        raise ValueError(f"force_std={force_std!r} with {what}: a finite standard deviation >= 0 in newtons, or None for dyn_noise_scale")
+    if process_group is not None:
+        raise NotImplementedError(f"process_group with {what}: covo_set_step_estimator refuses sample-sharded steps")
+    if materialize_eps or noise_stream != "philox":
+        raise NotImplementedError(f"{what} on the kernel-by-kernel path (materialize_eps / noise_stream={noise_stream!r}): it is "
+                                  "attached to the fused step's controllers")
+    return Estimator(obs_std=tuple(float(x) for x in obs), proc_std=tuple(float(x) for x in proc), force_std=float(fs))

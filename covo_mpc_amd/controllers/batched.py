@@ -140,6 +140,7 @@ class BatchedCoVOController:
         through CoVOController.reset_a_cov_offline (covo.py:58-104; once per episode, a host loop over the instances).
         -> (a_cov_offline, a_chol_offline) [E, T, 128, 128].  The other modes have nothing to build."""
         self.core.restart_plan_hold()  # (plan_hold: the episode's first step plans)
+        self.core.estimator_reset()
         if self.mode != _lib.MODE_COVO_OFFLINE:
             if self.core.sigma_period > 1:  # the schedule restarts: the episode's first step refreshes Sigma
                 self.core.set_sigma_period(self.core.sigma_period)
@@ -190,6 +191,7 @@ class BatchedCoVOController:
         else:
             packed = [as_device_state(s, self.core.device).packed for s in noisy_states]
             torch.stack(packed, out=buf)
+        self.core.estimated(buf, self.a_mean, self._params)  # (an attached StateEstimator: in place on the rows the step reads)
         keys = np.ascontiguousarray(np.asarray(rng_acts, dtype=np.uint32).reshape(self.E, 2))
         if self.mode == _lib.MODE_COVO_ONLINE:
             check(self.core.lib.covo_mpc_step_batched(self.core.h, C.byref(self._args.base), self._params,
@@ -388,6 +390,7 @@ class BatchedCMAController(BatchedCoVOController):
     def reset(self, env_states=None, env_params=None, keys=None):
         """Episode start: every instance's L = sample_sigma I, p = 0, log s = 0 -- the next step samples from sample_sigma^2 I."""
         self.core.cma_reset()
+        self.core.estimator_reset()
         return None
 
     def step(self, noisy_states, rng_acts):

@@ -67,6 +67,7 @@ class CMAController(BaseController):
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start: L = sample_sigma I, p = 0, log s = 0 -- the first step samples from sample_sigma^2 I and adapts nothing."""
         self.core.cma_reset()
+        self.core.estimator_reset()
         return super().reset(env_state, env_params, control_params, key)
 
     def _check_call(self):
@@ -91,6 +92,7 @@ class CMAController(BaseController):
         core = self.core
         self._check_call()
         dstate = as_device_state(info["noisy_state"], core.device)
+        dstate = core.estimated(dstate, control_params.a_mean, lambda: self._params_c(env_params))  # (an attached StateEstimator)
         # the sampling key and everything drawn from it are derived from the raw rng_act on the device, as for covo-online (step.hip);
         # the sampling rollouts are deterministic, as CoVO's are
         am, cov = core.step(_lib.MODE_CMA, dstate, self._params_c(env_params), control_params.a_mean, rng_act,

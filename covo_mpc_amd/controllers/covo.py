@@ -93,6 +93,7 @@ class CoVOController(BaseController):
         if self.core.sigma_period > 1:
             self.core.set_sigma_period(self.core.sigma_period)
         self.core.restart_plan_hold()  # (plan_hold: the episode's first step plans)
+        self.core.estimator_reset()
         return super().reset(env_state, env_params, control_params, key)
 
     def _needs_table(self, params_c) -> bool:
@@ -177,6 +178,7 @@ class CoVOController(BaseController):
         from .. import _lib
         core = self.core
         core.restart_plan_hold()  # (plan_hold: the episode's first step plans)
+        core.estimator_reset()
         T = self.env.default_params.max_steps_in_episode
         dstate = as_device_state(env_state, core.device)
         packed_d, a_means_d, keys_d = self._nominal_device(env_state, env_params, key)
@@ -212,6 +214,7 @@ class CoVOController(BaseController):
         core = self.core
         dstate = as_device_state(info["noisy_state"], core.device)  # covo.py:198
         params_c = self._params_c(env_params)
+        dstate = core.estimated(dstate, control_params.a_mean, params_c)  # (an attached StateEstimator)
         if self.mode == "offline" and control_params.a_chol_offline is None:
             raise RuntimeError("covo-offline: call controller.reset(...) first (a_cov_offline table missing)")
         if self.noise_stream not in ("philox", "jax"):

@@ -65,6 +65,7 @@ class ILQRController(BaseController):
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start: with a plan hold the schedule restarts -- the first step of the episode plans."""
         self.core.restart_plan_hold()
+        self.core.estimator_reset()
         return super().reset(env_state, env_params, control_params, key)
 
     def run_episode(self, episode, env_params, control_params, rng, n_steps):
@@ -80,6 +81,7 @@ class ILQRController(BaseController):
     def __call__(self, obs, env_state, env_params, rng_act, control_params: ILQRParams, info):
         core = self.core
         dstate = as_device_state(info["noisy_state"], core.device)
+        dstate = core.estimated(dstate, control_params.a_mean, lambda: self._params_c(env_params))  # (an attached StateEstimator)
         am, _ = core.step(_lib.MODE_ILQR, dstate, self._params_c(env_params), control_params.a_mean, rng_act, derive_keys=True,
                           rollout_deterministic=True)
         a_mean_new = am.view(self.H, 4)

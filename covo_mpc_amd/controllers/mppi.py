@@ -57,6 +57,7 @@ class MPPIController(BaseController):
     def reset(self, env_state=None, env_params=None, control_params=None, key=None):
         """Episode start: with a plan hold the schedule restarts -- the first step of the episode plans."""
         self.core.restart_plan_hold()
+        self.core.estimator_reset()
         return super().reset(env_state, env_params, control_params, key)
 
     def _check_gamma_sigma(self, control_params):
@@ -88,6 +89,7 @@ class MPPIController(BaseController):
         torch = core.torch
         self._check_gamma_sigma(control_params)
         dstate = as_device_state(info["noisy_state"], core.device)  # mppi.py:40
+        dstate = core.estimated(dstate, control_params.a_mean, lambda: self._params_c(env_params))  # (an attached StateEstimator)
         if self.noise_stream not in ("philox", "jax"):
             raise ValueError(f"noise_stream={self.noise_stream!r}")
         if not self.materialize_eps and self.noise_stream == "philox":

@@ -1047,6 +1047,104 @@ int covo_cma_path(covo_handle_t h, const float *L_prev, const float *aux, int32_
     return launch_cma_path(d, (hipStream_t)stream);
 }
 
+// ---- the state estimator (state_estimator.hip).  Its launch is eager and follows the env step of an episode driver:
+// no captured step graph knows about it, nothing here bumps the epoch
+static int check_estimator_buffers(const char *what, const double *xhat, const double *P, const int32_t *meta, const float *rows, int n_inst)
+{
+    REQUIRE(xhat && P && meta && rows, "%s: xhat, P, meta and rows must all be given", what);
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "%s: n_inst=%d outside (0, %d]", what, n_inst, COVO_MAX_ENVS);
+    REQUIRE((((uintptr_t)xhat | (uintptr_t)P) & 7) == 0 && (((uintptr_t)meta | (uintptr_t)rows) & 3) == 0,
+            "%s: xhat and P must be 8-byte aligned, meta and rows 4-byte", what);
+    return 0;
+}
+
+int covo_set_step_estimator(covo_handle_t h, const double *obs_std, const double *proc_std, double force_std, double *xhat, double *P,
+                            int32_t *meta, float *rows, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_estimator: null handle");
+    if (rows == nullptr) {  // off, the log with it
+        h->est_rows = nullptr;
+        h->est_xhat = h->est_P = nullptr;
+        h->est_meta = nullptr;
+        h->est_n = 0;
+        h->est_log = nullptr;
+        h->est_log_stride = 0;
+        return 0;
+    }
+    REQUIRE(obs_std && proc_std, "covo_set_step_estimator: obs_std and proc_std must be given");
+    if (int rc = check_estimator_buffers("covo_set_step_estimator", xhat, P, meta, rows, n_inst)) return rc;
+    EstDesc probe;  // (the values are checked on a default model: the derive marker needs the instance's own at the launch)
+    covo_env_params unit{};
+    unit.dt = unit.m = 1.0f;
+    if (int rc = estimator_fill_model(probe, unit, obs_std, proc_std, force_std, "covo_set_step_estimator")) return rc;
+    for (int g = 0; g < 4; ++g) {
+        h->est_obs_std[g] = obs_std[g];
+        h->est_proc_std[g] = proc_std[g];
+    }
+    h->est_force_std = force_std;
+    h->est_xhat = xhat;
+    h->est_P = P;
+    h->est_meta = meta;
+    h->est_rows = rows;
+    h->est_n = n_inst;
+    h->est_fresh = 1;
+    return 0;
+}
+
+int covo_estimator_reset(covo_handle_t h)
+{
+    REQUIRE(h, "covo_estimator_reset: null handle");
+    h->est_fresh = 1;
+    return 0;
+}
+
+int covo_set_episode_estimator_log(covo_handle_t h, float *log, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_estimator_log: null handle");
+    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_estimator_log: stride=%d", stride);
+    REQUIRE(log == nullptr || covo_estimator_on(h), "covo_set_episode_estimator_log: no estimator attached: call covo_set_step_estimator first");
+    h->est_log = log;
+    h->est_log_stride = log ? stride : 0;
+    return 0;
+}
+
+int covo_estimate(covo_handle_t h, float *state_rows, const float *u, int32_t u_stride, const covo_env_params *params,
+                  const double *obs_std, const double *proc_std, double force_std, double *xhat, double *P, int32_t *meta, float *rows,
+                  int32_t n_inst, int32_t reset, void *hip_stream)
+{
+    REQUIRE(h, "covo_estimate: null handle");
+    CHECK_DEVICE(h, "covo_estimate");
+    REQUIRE(state_rows && u && params && obs_std && proc_std && u_stride >= COVO_DU, "covo_estimate: bad argument");
+    if (int rc = check_estimator_buffers("covo_estimate", xhat, P, meta, rows, n_inst)) return rc;
+    static thread_local EstDesc d[COVO_MAX_ENVS];
+    std::memset(d, 0, (size_t)n_inst * sizeof(EstDesc));
+    for (int e = 0; e < n_inst; ++e) {
+        CHECK_MODEL(&params[e], "covo_estimate");
+        if (int rc = estimator_fill_model(d[e], params[e], obs_std, proc_std, force_std, "covo_estimate")) return rc;
+        d[e].state = state_rows + (size_t)e * COVO_STATE_FLOATS;
+        d[e].u = u + (size_t)e * u_stride;
+        d[e].xhat = xhat + (size_t)e * COVO_EST_STATE_DOUBLES;
+        d[e].P = P + (size_t)e * 13 * 13;
+        d[e].meta = meta + (size_t)e * COVO_EST_META_INTS;
+        d[e].row_out = rows + (size_t)e * COVO_EST_FLOATS;
+    }
+    const int fresh = reset < 0 ? h->est_fresh : (reset != 0);  // (reset < 0: what covo_estimator_reset left, taken once)
+    if (reset < 0) h->est_fresh = 0;
+    return launch_state_estimator(h, d, n_inst, n_inst > 1, true, fresh, -1, (hipStream_t)hip_stream);
+}
+
+// what an episode driver asks of the estimator before its first launch
+static int check_episode_estimator(const covo_ctx *h, int n_inst, bool sharded, int first_row, int n_steps, const char *what)
+{
+    if (!covo_estimator_on(h)) return 0;
+    REQUIRE(!sharded, "%s: the state estimator (covo_set_step_estimator) does not run on sample-sharded steps", what);
+    REQUIRE(n_inst <= h->est_n, "%s: %d instances, the estimator's rows (covo_set_step_estimator) have n_inst=%d", what, n_inst, h->est_n);
+    REQUIRE(h->est_log == nullptr || (first_row >= 0 && first_row + n_steps <= h->est_log_stride),
+            "%s: episode estimator log rows [%d, %d) outside [0, %d) (covo_set_episode_estimator_log)", what, first_row, first_row + n_steps,
+            h->est_log_stride);
+    return 0;
+}
+
 int covo_arbitrate(covo_handle_t h, const float *state, const float *pos_traj, const float *vel_traj, int32_t T,
                    const covo_env_params *params, const float *f_disturb_shared, const float *f_disturb_steps, const float *a,
                    const float *cost, int32_t N, const float *a_nominal, float *a_mean_inout, int32_t mask, float *row_out,
@@ -1517,6 +1615,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
             "covo_exchange_connect) and a_mean_shift");
     int rc = check_single_step(h, params, args, "covo_run_episode");
     if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode"))) return rc;
+    if ((rc = check_episode_estimator(h, 1, args->partial_out != nullptr, 0, n_steps, "covo_run_episode"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -1555,6 +1654,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
         rc = launch_env_step(state_true, const_cast<float *>(args->state), args->pos_traj, args->vel_traj, acc_traj, args->T,
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
+        if ((rc = covo_estimator_step(h, const_cast<float *>(args->state), args->a_mean, params, 1, false, t, s))) return rc;
         host_philox_split(nrng, 0u, key);
     }
     rng[0] = key[0];
@@ -1596,6 +1696,7 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
     REQUIRE(log == nullptr || (log_index >= 0 && log_index + n_steps <= log_stride),
             "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
     if ((rc = check_episode_logs(h, log_index, n_steps, what))) return rc;
+    if ((rc = check_episode_estimator(h, E, false, log_index, n_steps, what))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -1617,6 +1718,7 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
                                           args->T, params[0], inst, E, args->a_mean, step_keys, noisy_on, obs_noise_scale, log,
                                           log_stride, log_index + t, s)))
             return rc;
+        if ((rc = covo_estimator_step(h, const_cast<float *>(args->states), args->a_mean, params, E, true, log_index + t, s))) return rc;
         std::memcpy(rngs, next, (size_t)2 * E * sizeof(uint32_t));
     }
     return 0;

@@ -173,6 +173,15 @@ struct covo_ctx {
     int box_n;
     int *ilqr_box;            // caller's [ilqr_box_n][COVO_MAX_STEP_ITERS] (covo_set_step_ilqr_box): slot j = iteration j's clamped coordinates, or null
     int ilqr_box_n;
+    // the state estimator (covo_set_step_estimator; state_estimator.hip); est_rows null: not attached
+    float *est_rows;          // caller's [est_n][COVO_EST_FLOATS]: instance e's side row of every launch
+    double *est_xhat, *est_P; // caller's [est_n][COVO_EST_STATE_DOUBLES], [est_n][13][13]: the filter's state lives there between steps
+    int *est_meta;            // caller's [est_n][COVO_EST_META_INTS]
+    int est_n;
+    double est_obs_std[4], est_proc_std[4], est_force_std;
+    int est_fresh;            // 1: the next launch of a driver treats every instance as one without a valid state
+    float *est_log;           // caller's [n_inst][est_log_stride][COVO_EST_LOG_FLOATS] (covo_set_episode_estimator_log): the launch writes
+    int est_log_stride;       // its rows itself; not one of eplog's kinds -- an episode driver checks its extent next to theirs
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -984,6 +993,28 @@ struct LatchDesc {
 };
 int launch_plan_hold(covo_ctx *h, const HoldDesc *d, int n_inst, bool batched, bool primitive, int stage, int log_index, hipStream_t s);
 int launch_plan_latch(covo_ctx *h, const LatchDesc *d, int n_inst, bool batched, int log_index, hipStream_t s);
+// state_estimator.hip: one instance of the estimator's launch, the kernel's argument block as it stands (zeroed before it is filled:
+// compared bytewise); row_out and log are null or not for every instance of a launch alike
+struct EstDesc {
+    float *state;             // [32] the measured row: its 13 kinematic floats become the estimate, in place
+    const float *u;           // [4] the action applied during the step that led to this row
+    double *xhat;             // [COVO_EST_STATE_DOUBLES]: the estimate [13], then the force of the row last seen [3]
+    double *P;                // [13][13]
+    int *meta;                // [COVO_EST_META_INTS] = {valid, the time word of the row last seen}
+    float *row_out;           // [COVO_EST_FLOATS] or null
+    float *log;               // this instance's rows of the episode estimator log [stride][COVO_EST_LOG_FLOATS], or null
+    qm::Consts<double> c;     // the instance's model
+    double R[4], Q[4];        // the variances of the four coordinate groups: measurement, process
+};
+// fresh: every instance counts as one without a valid state (covo_estimator_reset)
+int launch_state_estimator(covo_ctx *h, const EstDesc *d, int n_inst, bool batched, bool primitive, int fresh, int log_index, hipStream_t s);
+// d's model and variances from the instance's parameters; 0, or COVO_E_BADARG with the error set (what: the entry's name)
+int estimator_fill_model(EstDesc &d, const covo_env_params &p, const double *obs_std, const double *proc_std, double force_std, const char *what);
+static inline bool covo_estimator_on(const covo_ctx *h) { return h->est_rows != nullptr; }
+// the estimator's launch of an episode driver's step, right behind the env step: on the rows the controller is about to read, with
+// u = the first action of each instance's mean (no-op with nothing attached)
+int covo_estimator_step(covo_ctx *h, float *states, const float *a_mean, const covo_env_params *params, int n_inst, bool batched,
+                        int log_index, hipStream_t s);
 // ilqr.hip: what frames the iterations of an iLQR step (COVO_MODE_ILQR).  IlqrTallyDesc: one instance of the tally launch behind an
 // iteration's line search, the kernel's argument block as it stands (all pointers; what is null is null for every instance)
 struct IlqrTallyDesc {

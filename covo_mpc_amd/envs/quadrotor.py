@@ -378,6 +378,28 @@ class _EpisodeLogs:
         return {"age": as_int(0), "alpha": rows[..., 1], "gain": rows[..., 2], "clipped": as_int(3), "flags": as_int(4),
                 "dpos": rows[..., 5], "time": as_int(6)}
 
+    # the estimator log of an attached controllers.StateEstimator -- [.., T + 1, 34], None until a controller with one attached runs the
+    # episode -- is not one of LOGS either: the estimator's launch writes its rows itself (SamplingCore.attach_estimator_log)
+    estlog = None
+
+    def alloc_estimator_log(self):
+        import torch
+        self.estlog = torch.zeros(tuple(self.log.shape[:-1]) + (self._lib.COVO_EST_LOG_FLOATS,), dtype=torch.float32, device=self.device)
+
+    def read_estimate(self):
+        """-> {measured [n, 13], estimate [n, 13], flags [n] (int32: 1 initialised, 2 re-initialised on the time word, 4 a measured
+        coordinate not finite, 8 the update failed), nis [n], innov_pos [n], moved_pos [n], trace_pos [n], trace_vel [n], pivot_min [n],
+        time [n] (int32)}: per enqueued step what the env step measured, what the estimator wrote over it and its side row
+        (include/covo_hip.h: covo_set_step_estimator), under a controller with a controllers.StateEstimator attached."""
+        if self.estlog is None:
+            raise RuntimeError("no estimator log: run_episode under a controller with a StateEstimator attached (StateEstimator.attach)")
+        self.read_log()  # synchronises and checks the device status
+        rows = self.estlog.narrow(self.STEP_AXIS, 0, self.n_steps).cpu().numpy()
+        as_int = lambda i: np.ascontiguousarray(rows[..., i]).view(np.int32)
+        return {"measured": rows[..., 0:13], "estimate": rows[..., 13:26], "flags": as_int(26), "nis": rows[..., 27],
+                "innov_pos": rows[..., 28], "moved_pos": rows[..., 29], "trace_pos": rows[..., 30], "trace_vel": rows[..., 31],
+                "pivot_min": rows[..., 32], "time": as_int(33)}
+
     def log_segment(self, name):
         """What the episode driver binds of log `name` for the next segment: one instance -- the rows from n_steps on (covo_run_episode
         counts its rows from 0); E instances -- the whole buffer (the batched drivers take the first row of a segment as log_index)."""

@@ -1121,6 +1121,51 @@ int covo_cma_path(covo_handle_t h, const float *L_prev, const float *aux, int32_
                   const float *L_hat, const float *Sigma_hat, const float *shape_rows, int32_t batch, int32_t n_samples, int32_t step_size,
                   float damping, float s_min, float s_max, double *p, double *log_s, float *L_out, float *Sigma_out, float *rows_out,
                   void *hip_stream);
+/* The state estimator: an extended Kalman filter between the env step and the control step (additive to ABI 10:
+ * COVO_HAS_STATE_ESTIMATOR; csrc/state_estimator.hip).  One launch overwrites, IN PLACE, the 13 kinematic floats of the
+ * packed state row the controller is about to read; no step path and no captured step graph changes; off unless attached.  fp64
+ * throughout.  Per instance the filter keeps x [13] (pos, vel, quat, omega), P [13][13] (symmetric bit for bit), the force f_prev and
+ * the time word t_prev of the row it last saw, and a valid bit, in the caller's buffers:
+ *   xhat = DEVICE double[n_inst][COVO_EST_STATE_DOUBLES] (x, then f_prev), P = DEVICE double[n_inst][13][13],
+ *   meta = DEVICE int32[n_inst][COVO_EST_META_INTS] = {valid, t_prev}, rows = DEVICE float[n_inst][COVO_EST_FLOATS].
+ * R = diag(obs_std[group]^2), Q = diag(proc_std[group]^2), groups pos, vel, quat, omega; a NEGATIVE proc_std[1] means
+ * dt force_std / m with the instance's own dt and m.  A call with the measured row z and the applied action u [4]:
+ *   no valid state, or time(z) != t_prev + 1: x = (double)z[0:13], P = R, the row is left as measured; otherwise
+ *   x- = f(x, clip(u), f_prev) (the model step of the rollouts in fp64, quaternion normalised on entry and exit), A = df/dx at x,
+ *   P- = A P A^T + Q;  S = P- + R factored without pivoting, nu = z - x-, K = P- S^-1, x = x- + K nu,
+ *   P = (I - K) P- (I - K)^T + K R K^T with the lower triangle mirrored;  row[0:13] = fp32(x), nothing else of the row changes;
+ *   f_prev = z.f_disturb, t_prev = time(z).  The quaternion is neither renormalised nor sign-aligned.
+ * Fall-backs, decided on the device, reported in the row's flag word, never an error: 1 -- initialised (no valid state); 2 --
+ *   re-initialised (the time word); 4 -- one of the 13 measured coordinates is not finite: the row is untouched and the filter is
+ *   invalidated; 8 -- a pivot of S is not positive and finite, or x / P has an entry that is not finite: re-initialised from z, the row
+ *   untouched.
+ * rows: {bits(flags), nu^T S^-1 nu, |nu_pos|, |x - z|_pos, P00 + P11 + P22, P33 + P44 + P55, smallest pivot of S, bits(time(z))}.
+ * covo_set_step_estimator: covo_run_episode, covo_run_episode_batched and covo_run_episode_batched_mode enqueue the launch right behind
+ *   their env step, whatever kind of step came before (a hold step included), on args->state[s] with u = the first four floats of
+ *   each instance's a_mean.  rows = NULL detaches (the episode log with it).  obs_std, proc_std: [host] double[4].
+ * covo_estimator_reset: the next launch of a driver treats every instance as one without a valid state.
+ * covo_estimate: the launch alone on the caller's buffers: state_rows = DEVICE float[n_inst][32], in place; instance e's u at
+ *   u + e * u_stride floats; params = [host] covo_env_params[n_inst]; reset > 0: every instance counts as one without a valid state;
+ *   reset < 0: they do when covo_estimator_reset was called on the handle since its last launch (the flag is taken).
+ *   It writes floats 0 .. 12 of each row, xhat, P, meta and rows, nothing else, and launches on hip_stream, the caller's stream (a
+ *   hipStream_t as void *, like every other entry's `stream`).
+ * covo_set_episode_estimator_log: log = DEVICE float[n_inst][stride][COVO_EST_LOG_FLOATS]; the launch of a driver's step t writes row
+ *   first_row + t of every instance itself: the 13 measured floats, the 13 written floats, the row.  NULL: off.
+ * Refused with COVO_E_BADARG before any launch: an obs_std entry that is not positive and finite; a proc_std entry that is negative
+ *   (other than the marker) or not finite; force_std negative or not finite while the marker is set; more instances than rows;
+ *   a sample-sharded episode step; a log with fewer rows than the episode segment needs. */
+#define COVO_HAS_STATE_ESTIMATOR 1
+#define COVO_EST_FLOATS 8
+#define COVO_EST_STATE_DOUBLES 16
+#define COVO_EST_META_INTS 2
+#define COVO_EST_LOG_FLOATS 34
+int covo_set_step_estimator(covo_handle_t h, const double *obs_std, const double *proc_std, double force_std, double *xhat, double *P,
+                            int32_t *meta, float *rows /* DEVICE [n_inst][COVO_EST_FLOATS]; NULL = off */, int32_t n_inst);
+int covo_estimator_reset(covo_handle_t h);
+int covo_estimate(covo_handle_t h, float *state_rows, const float *u, int32_t u_stride, const covo_env_params *params,
+                  const double *obs_std, const double *proc_std, double force_std, double *xhat, double *P, int32_t *meta, float *rows,
+                  int32_t n_inst, int32_t reset, void *hip_stream);
+int covo_set_episode_estimator_log(covo_handle_t h, float *log, int32_t stride);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

@@ -35,7 +35,13 @@ name = sys.argv[1]
 # python scripts/eval_seeds.py cma [gamma=g] [damping=d] [s_min=a] [s_max=b] [step_size=0] [iters=k] [elite=K] [ess_min=e]: the CMA
 # controller (controllers/cma.py; defaults gamma=0.2, damping=1, s_min=0.1, s_max=4); every seed's line also carries the step size and
 # the flag word the last episode ended with
+# python scripts/eval_seeds.py <controller> [...] --estimator [force_std=f]: a controllers.StateEstimator attached to the controller that
+# was built (csrc/state_estimator.hip): every control step plans from the filter's estimate of the noisy state; every seed's line also
+# carries the mean distance the estimate moved the measured position and the share of steps that (re-)initialised; compare the errors with
+# the same call without the flag
 rest = sys.argv[2:]
+with_estimator = "--estimator" in rest
+rest = [r for r in rest if r != "--estimator"]
 # the boolean step switches as flags: --refine, --riccati, --riccati-feedback, --riccati-box
 flags = {f"--{s.replace('_', '-')}": s for s, default in STEP_SWITCH_DEFAULTS.items() if isinstance(default, bool)}
 switches = {s: flag in rest for flag, s in flags.items()}
@@ -44,11 +50,13 @@ for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_a
     while flag in rest:
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
-FLOATS = ("sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp", "gamma", "damping", "s_min", "s_max")
+FLOATS = ("force_std", "sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp", "gamma", "damping", "s_min", "s_max")
 CMA_KEYS = ("gamma", "damping", "s_min", "s_max", "step_size")
 opts = {k: (None if v.lower() == "none" else v if k == "node_interp" else float(v) if k in FLOATS else int(v))
         for k, v in (arg.split("=") for arg in rest)}
 switches["plan_hold"] = opts.pop("plan_hold", 1)
+force_std = opts.pop("force_std", None)
+assert force_std is None or with_estimator, "force_std= belongs to --estimator"
 assert set(opts) <= ({"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"} |
                      ({"beta_pass", "beta_stage", "temp", "nodes", "node_interp"} if name == "dial" else set()) |
                      (set(CMA_KEYS) if name == "cma" else set())), opts
@@ -60,6 +68,9 @@ if cma_kw:  # (get_controller's signature carries none of them: the controller i
     from covo_mpc_amd import controllers
     ctrl.core.close()
     ctrl = controllers.CMAController(env, cp, ctrl.N, ctrl.H, ctrl.lam, **cma_kw, **{k: v for k, v in opts.items() if k in ("elite", "ess_min", "iters")})
+if with_estimator:
+    from covo_mpc_amd.controllers import StateEstimator
+    StateEstimator(env, force_std=force_std).attach(ctrl)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
@@ -110,6 +121,10 @@ def rows_of(ep):
         rows["held"] = rows.get("held", 0) + int(held.sum())
         rows["stale"] = rows.get("stale", 0) + int(((hold["flags"] & 4) != 0)[held].sum())
         rows["clipped"] = rows.get("clipped", 0) + int((hold["clipped"] > 0)[held].sum())
+    if ep.estlog is not None:
+        e = ep.read_estimate()
+        rows["est_init"] = rows.get("est_init", 0) + int((e["flags"] != 0).sum())
+        rows["est_moved"] = rows.get("est_moved", 0.0) + float(e["moved_pos"].sum())
     if name == "cma":
         row = core.cma_rows[0].cpu().numpy()
         rows["cma_s"], rows["cma_flags"] = float(row[0]), float(row[7])
@@ -137,6 +152,8 @@ for seed in range(1, 13):
                                                            ("boxed", "  plan steps with a live box: %.3f", npl),
                                                            ("stale", "  hold steps on another trajectory's plan: %.3f", nh),
                                                            ("clipped", "  hold steps with a clipped component: %.3f", nh),
+                                                           ("est_moved", "  estimate moved the position by: %.4f", n),
+                                                           ("est_init", "  steps that (re-)initialised the filter: %.4f", n),
                                                            ("cma_s", "  last step size: %.3f", 1), ("cma_flags", "  last flags: %d", 1)) if k in rows)
     print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()) + extra,
           flush=True)
