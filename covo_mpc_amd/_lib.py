@@ -104,6 +104,14 @@ COVO_EST_FLOATS = 8
 COVO_EST_STATE_DOUBLES = 16  # per instance: the estimate [13], then the force of the row last seen [3]
 COVO_EST_META_INTS = 2       # {valid, the time word of the row last seen}
 COVO_EST_LOG_FLOATS = 34     # a row of the episode log: measured [13], written [13], the side row [8]
+# controllers.ForceObserver (covo_set_step_force_observer, covo_observe_force, covo_set_episode_force_observer_log): a 16-state EKF that
+# estimates the disturbance force from the kinematic measurements and writes floats 0 .. 15 of the row.  Its side row: {bits(int32
+# flags), nis, |nu_pos|, |f^|, tr P_pos, tr P_force, smallest pivot of S, bits(int32 time word)}; the flags are the state estimator's
+COVO_HAS_FORCE_OBSERVER = 1
+COVO_OBS_FLOATS = 8
+COVO_OBS_STATE_DOUBLES = 16  # per instance: x [13], then the force estimate [3]
+COVO_OBS_META_INTS = 2       # {valid, the time word of the row last seen}
+COVO_OBS_LOG_FLOATS = 40     # a row of the episode log: measured [16] (slots 13 .. 15: the true force), written [16], the side row [8]
 ILQR_FIELDS = ("cost_first", "cost", "moved", "fixed_at", "closed", "flags", "grad_norm")
 # riccati_box= on top of riccati= (covo_set_step_riccati_box, covo_riccati_box, covo_riccati_refine_box): the sweep's stages solve the
 # box QP on -1 <= clip(b) + du <= 1.  A mask word per stage: bits 0-3 coordinate i clamped at the lower bound, bits 4-7 at the upper
@@ -320,6 +328,13 @@ _SIGS = {
     "covo_estimate": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, _P,
                                 _P, _P, _P, C.c_int32, C.c_int32, _P]),
     "covo_set_episode_estimator_log": (C.c_int, [_P, _P, C.c_int32]),
+    # the force observer (covo_hip.h: COVO_HAS_FORCE_OBSERVER)
+    "covo_set_step_force_observer": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double, C.c_double, _P, _P, _P, _P,
+                                               C.c_int32]),
+    "covo_force_observer_reset": (C.c_int, [_P]),
+    "covo_observe_force": (C.c_int, [_P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_double,
+                                     C.c_double, _P, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    "covo_set_episode_force_observer_log": (C.c_int, [_P, _P, C.c_int32]),
     # the Riccati box (covo_hip.h: COVO_HAS_RICCATI_BOX)
     "covo_riccati_box": (C.c_int, [_P, _P, _P, _P, C.c_int32, C.POINTER(EnvParamsC), _P, _P, C.c_int32, C.c_double, _P, _P, _P, _P, _P, _P,
                                    _P]),

@@ -9,3 +9,4 @@ from .ilqr import ILQRBoxController, ILQRController, ILQRParams  # noqa: F401
 from .dial import DialController  # noqa: F401
 from .cma import CMAController, CMAParams  # noqa: F401
 from .estimator import StateEstimator  # noqa: F401
+from .observer import ForceObserver  # noqa: F401

@@ -426,7 +426,8 @@ class SamplingCore:
             (getattr(self, "sigma_nodes_rows", None) is not None, self.sigma_nodes_info),
             (getattr(self, "anneal_rows", None) is not None, self.anneal_info),
             (getattr(self, "cma_rows", None) is not None, self.cma_info),
-            (getattr(self, "estimator", None) is not None, self.estimator_info)) if on]
+            (getattr(self, "estimator", None) is not None, self.estimator_info),
+            (getattr(self, "force_observer", None) is not None, self.force_observer_info)) if on]
 
     def step_info(self) -> dict:
         """Everything attached to the last step, merged: diag_info (compute_diag), plan_info (compute_plan), fan_info (compute_fan),
@@ -462,6 +463,7 @@ class SamplingCore:
             self.attach_log(name, episode, rows_left)
         self.attach_hold_log(episode, rows_left)
         self.attach_estimator_log(episode, rows_left)
+        self.attach_force_observer_log(episode, rows_left)
 
     def attach_hold_log(self, episode, rows_left: int):
         """Bind `episode`'s hold log (episode.holdlog, [.., T + 1, 8]; allocated on first use) under plan_hold > 1: the hold launch,
@@ -801,7 +803,7 @@ class SamplingCore:
         place, with instance e's u at a_mean[e, :4]."""
         est = self.estimator
         if est is None:
-            return dstate
+            return dstate if self.force_observer is None else self._observed(dstate, a_mean, params_c)
         if callable(params_c):
             params_c = params_c()
         kw = dict(rows=self.est_rows, obs_std=est.obs_std, proc_std=est.proc_std, force_std=est.force_std, reset=-1)
@@ -822,6 +824,104 @@ class SamplingCore:
             episode.alloc_estimator_log()
         check(self.lib.covo_set_episode_estimator_log(self.h, ptr(episode.log_segment("estlog")), int(rows_left)),
               "covo_set_episode_estimator_log")
+
+    # ---- the force observer (controllers.ForceObserver; csrc/force_observer.hip)
+    force_observer = None  # the _options.Observer record while one is attached
+
+    def attach_force_observer(self, obs):
+        """covo_set_step_force_observer (obs: the record _options.check_force_observer returns): self.obs_rows [rows, 8] -- instance e's
+        side row of every launch --, self.obs_xi [rows, 16] float64 (x [13], then the force estimate [3]), self.obs_P [rows, 16, 16]
+        float64 and self.obs_meta [rows, 2] int32 {valid, time word}: the filter's state lives there between steps.  The episode
+        drivers then run the launch behind every env step; the host path goes through estimated().  ValueError while a StateEstimator
+        is attached."""
+        torch = self.torch
+        if self.estimator is not None:
+            raise ValueError("the force observer on a controller that already has a StateEstimator attached: two filters must not "
+                             "write one row -- detach it first")
+        if self.world > 1:
+            raise NotImplementedError("the force observer on sample-sharded ranks: covo_set_step_force_observer refuses sample-sharded "
+                                      "steps")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        self.obs_rows = torch.zeros((self._rows, _lib.COVO_OBS_FLOATS), dtype=torch.float32, device=self.device)
+        self.obs_xi = torch.zeros((self._rows, _lib.COVO_OBS_STATE_DOUBLES), **f64)
+        self.obs_P = torch.zeros((self._rows, 16, 16), **f64)
+        self.obs_meta = torch.zeros((self._rows, _lib.COVO_OBS_META_INTS), dtype=torch.int32, device=self.device)
+        o, p = (C.c_double * 4)(*obs.obs_std), (C.c_double * 4)(*obs.proc_std)
+        check(self.lib.covo_set_step_force_observer(self.h, o, p, float(obs.force_walk_std), float(obs.force_init_std), ptr(self.obs_xi),
+                                                    ptr(self.obs_P), ptr(self.obs_meta), ptr(self.obs_rows), self._rows),
+              "covo_set_step_force_observer")
+        self.force_observer = obs
+        self._list_infos()
+
+    def detach_force_observer(self):
+        """covo_set_step_force_observer(NULL): the drivers and estimated() are what they were; the buffers stay readable."""
+        check(self.lib.covo_set_step_force_observer(self.h, None, None, 0.0, 0.0, None, None, None, None, 0), "covo_set_step_force_observer")
+        self.force_observer = None
+        self._list_infos()
+
+    def force_observer_reset(self):
+        """covo_force_observer_reset: the next launch -- a driver's, or estimated()'s -- treats every instance as one without a valid
+        state."""
+        check(self.lib.covo_force_observer_reset(self.h), "covo_force_observer_reset")
+
+    def force_observer_info(self) -> dict:
+        """{"obs_rows" [8], "obs_flags" (int32: 1 initialised, 2 re-initialised, 4 measurement not finite, 8 update failed), "obs_nis",
+        "obs_force" [3] (the estimate, float64)} of the last launch as views of self.obs_rows / self.obs_xi (no sync, no copy); {} with
+        nothing attached."""
+        if self.force_observer is None:
+            return {}
+        row = self.obs_rows[0]
+        return {"obs_rows": row, "obs_flags": row[0:1].view(self.torch.int32)[0], "obs_nis": row[1], "obs_force": self.obs_xi[0, 13:16]}
+
+    def observe_force(self, state_rows, u, params_c, xi, P, meta, *, rows=None, obs_std, proc_std=(0.0, 0.0, 0.0, 0.0), force_walk_std,
+                      force_init_std, reset=False, u_stride=None):
+        """covo_observe_force (the stand-alone launch), IN PLACE on floats 0 .. 15 of state_rows: float32 device tensor [32] or [E, 32],
+        contiguous; u float32 with instance e's action at u.reshape(-1)[e * u_stride:][:4] (u_stride None: u is [E, 4]); params_c: one
+        EnvParamsC or an array of E; xi float64 [E, 16], P float64 [E, 16, 16], meta int32 [E, 2]: the filter's state, updated in
+        place; obs_std, proc_std: four standard deviations each; force_walk_std, force_init_std in newtons.  reset: every instance
+        counts as one without a valid state (-1: when covo_force_observer_reset was called on the handle since its last launch).
+        -> rows [E, 8]."""
+        torch = self.torch
+        E = int(state_rows.numel()) // _lib.COVO_STATE_FLOATS
+        assert state_rows.dtype == torch.float32 and state_rows.is_contiguous() and u.dtype == torch.float32 and u.is_contiguous()
+        assert xi.dtype == torch.float64 and P.dtype == torch.float64 and meta.dtype == torch.int32
+        assert xi.numel() == E * _lib.COVO_OBS_STATE_DOUBLES and P.numel() == E * 256 and meta.numel() == E * _lib.COVO_OBS_META_INTS
+        assert xi.is_contiguous() and P.is_contiguous() and meta.is_contiguous()
+        stride = 4 if u_stride is None else int(u_stride)
+        assert u.numel() >= (E - 1) * stride + 4
+        if isinstance(params_c, _lib.EnvParamsC):
+            params_c = (_lib.EnvParamsC * E)(*([params_c] * E))
+        rows = torch.zeros((E, _lib.COVO_OBS_FLOATS), dtype=torch.float32, device=self.device) if rows is None else rows
+        with torch.cuda.device(self.device):
+            check(self.lib.covo_observe_force(self.h, ptr(state_rows), ptr(u), stride, params_c, (C.c_double * 4)(*obs_std),
+                                              (C.c_double * 4)(*proc_std), float(force_walk_std), float(force_init_std), ptr(xi), ptr(P),
+                                              ptr(meta), ptr(rows), E, int(reset), self.stream()), "covo_observe_force")
+        return rows
+
+    def _observed(self, dstate, a_mean, params_c):
+        """estimated() with a force observer attached: the same contract, on floats 0 .. 15 of the row."""
+        obs = self.force_observer
+        if callable(params_c):
+            params_c = params_c()
+        kw = dict(rows=self.obs_rows, obs_std=obs.obs_std, proc_std=obs.proc_std, force_walk_std=obs.force_walk_std,
+                  force_init_std=obs.force_init_std, reset=-1)
+        if self.torch.is_tensor(dstate):
+            self.observe_force(dstate, a_mean.reshape(-1), params_c, self.obs_xi, self.obs_P, self.obs_meta, u_stride=COVO_NA, **kw)
+            return dstate
+        import dataclasses
+        row = dstate.packed.clone()
+        self.observe_force(row, a_mean.reshape(-1)[:4].contiguous(), params_c, self.obs_xi, self.obs_P, self.obs_meta, **kw)
+        return dataclasses.replace(dstate, packed=row)
+
+    def attach_force_observer_log(self, episode, rows_left: int):
+        """Bind `episode`'s observer log (episode.obslog, [.., T + 1, 40]; allocated on first use) while a force observer is attached:
+        its launch writes the rows itself (covo_set_episode_force_observer_log), like the estimator log's."""
+        if self.force_observer is None:
+            return
+        if getattr(episode, "obslog", None) is None:
+            episode.alloc_force_observer_log()
+        check(self.lib.covo_set_episode_force_observer_log(self.h, ptr(episode.log_segment("obslog")), int(rows_left)),
+              "covo_set_episode_force_observer_log")
 
     @property
     def lam_logged(self) -> bool:

@@ -759,3 +759,69 @@ def check_estimator(*, n_inst=1, obs_std=None, proc_std=None, force_std=None, ob
         raise NotImplementedError(f"{what} on the kernel-by-kernel path (materialize_eps / noise_stream={noise_stream!r}): it is "
                                   "attached to the fused step's controllers")
     return Estimator(obs_std=tuple(float(x) for x in obs), proc_std=tuple(float(x) for x in proc), force_std=float(fs))
+
+
+@dataclass(frozen=True)
+class Observer:
+    """What check_force_observer returns: the four measurement and the four process standard deviations (pos, vel, quat, omega), the
+    force's random-walk step and its initial standard deviation, in newtons."""
+    obs_std: tuple
+    proc_std: tuple
+    force_walk_std: float
+    force_init_std: float
+
+
+def check_force_observer(*, n_inst=1, obs_std=None, proc_std=None, force_walk_std=None, force_init_std=None, obs_noise_scale=0.05,
+                         dyn_noise_scale=0.05, disturb_scale=0.2, state_estimator=False, process_group=None, materialize_eps=False,
+                         noise_stream="philox", what="the force observer") -> Observer:
+    """The keywords of controllers.ForceObserver -> the Observer record SamplingCore.attach_force_observer attaches.  The C side's
+    counterpart is observer_fill_model (csrc/force_observer.hip).
+
+    obs_std=None: obs_noise_scale (0.25, 0.5, 0.02, 0.5), the env step's own noise, as check_estimator resolves it; proc_std=None:
+    (0, 0, 0, 0); force_walk_std=None: dyn_noise_scale newtons per step (a starting point, not a tuned value); force_init_std=None:
+    disturb_scale / sqrt(3), the standard deviation of the U(-s, s) force a reset draws.
+
+    The objections, each naming the keyword: n_inst anything but an integer in [1, COVO_MAX_ENVS]; obs_std anything but four positive
+    finite real numbers; proc_std anything but four finite real numbers >= 0; force_walk_std / force_init_std anything but a finite
+    real number >= 0; state_estimator: the controller already has a StateEstimator (ValueError); then process_group
+    (NotImplementedError: sample-sharded ranks) and the kernel-by-kernel path, materialize_eps / noise_stream="jax"
+    (NotImplementedError)."""
+    import math
+    import numbers
+
+    def real(v):
+        return not isinstance(v, bool) and isinstance(v, numbers.Real) and math.isfinite(float(v))
+
+    def four(v):
+        try:
+            v = tuple(v)
+        except TypeError:
+            return None
+        return v if len(v) == 4 and all(real(x) for x in v) else None
+    if isinstance(n_inst, bool) or not isinstance(n_inst, numbers.Integral) or not 1 <= int(n_inst) <= _lib.COVO_MAX_ENVS:
+        raise ValueError(f"n_inst={n_inst!r} with {what}: an integer in [1, {_lib.COVO_MAX_ENVS}]")
+    obs = tuple(float(obs_noise_scale) * g for g in OBS_GROUP_SCALE) if obs_std is None else four(obs_std)
+    if obs is None or not all(float(x) > 0.0 for x in obs):
+        raise ValueError(f"obs_std={obs_std!r} with {what}: four positive finite standard deviations (pos, vel, quat, omega), or None for "
+                         "the env step's own")
+    proc = (0.0, 0.0, 0.0, 0.0) if proc_std is None else four(proc_std)
+    if proc is None or any(float(x) < 0.0 for x in proc):
+        raise ValueError(f"proc_std={proc_std!r} with {what}: four finite standard deviations >= 0 (pos, vel, quat, omega), or None")
+    fw = float(dyn_noise_scale) if force_walk_std is None else force_walk_std
+    if not real(fw) or float(fw) < 0.0:
+        raise ValueError(f"force_walk_std={force_walk_std!r} with {what}: a finite standard deviation >= 0 in newtons per step, or None "
+                         "for dyn_noise_scale")
+    fi = abs(float(disturb_scale)) / math.sqrt(3.0) if force_init_std is None else force_init_std
+    if not real(fi) or float(fi) < 0.0:
+        raise ValueError(f"force_init_std={force_init_std!r} with {what}: a finite standard deviation >= 0 in newtons, or None for "
+                         "disturb_scale / sqrt(3)")
+    if state_estimator:
+        raise ValueError(f"{what} on a controller that already has a StateEstimator attached (state_estimator): two filters must not "
+                         "write one row -- detach it first")
+    if process_group is not None:
+        raise NotImplementedError(f"process_group with {what}: covo_set_step_force_observer refuses sample-sharded steps")
+    if materialize_eps or noise_stream != "philox":
+        raise NotImplementedError(f"{what} on the kernel-by-kernel path (materialize_eps / noise_stream={noise_stream!r}): it is "
+                                  "attached to the fused step's controllers")
+    return Observer(obs_std=tuple(float(x) for x in obs), proc_std=tuple(float(x) for x in proc), force_walk_std=float(fw),
+                    force_init_std=float(fi))

@@ -141,6 +141,7 @@ class BatchedCoVOController:
         -> (a_cov_offline, a_chol_offline) [E, T, 128, 128].  The other modes have nothing to build."""
         self.core.restart_plan_hold()  # (plan_hold: the episode's first step plans)
         self.core.estimator_reset()
+        self.core.force_observer_reset()
         if self.mode != _lib.MODE_COVO_OFFLINE:
             if self.core.sigma_period > 1:  # the schedule restarts: the episode's first step refreshes Sigma
                 self.core.set_sigma_period(self.core.sigma_period)
@@ -391,6 +392,7 @@ class BatchedCMAController(BatchedCoVOController):
         """Episode start: every instance's L = sample_sigma I, p = 0, log s = 0 -- the next step samples from sample_sigma^2 I."""
         self.core.cma_reset()
         self.core.estimator_reset()
+        self.core.force_observer_reset()
         return None
 
     def step(self, noisy_states, rng_acts):

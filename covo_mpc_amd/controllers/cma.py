@@ -68,6 +68,7 @@ class CMAController(BaseController):
         """Episode start: L = sample_sigma I, p = 0, log s = 0 -- the first step samples from sample_sigma^2 I and adapts nothing."""
         self.core.cma_reset()
         self.core.estimator_reset()
+        self.core.force_observer_reset()
         return super().reset(env_state, env_params, control_params, key)
 
     def _check_call(self):

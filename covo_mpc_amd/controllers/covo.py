@@ -94,6 +94,7 @@ class CoVOController(BaseController):
             self.core.set_sigma_period(self.core.sigma_period)
         self.core.restart_plan_hold()  # (plan_hold: the episode's first step plans)
         self.core.estimator_reset()
+        self.core.force_observer_reset()
         return super().reset(env_state, env_params, control_params, key)
 
     def _needs_table(self, params_c) -> bool:
@@ -179,6 +180,7 @@ class CoVOController(BaseController):
         core = self.core
         core.restart_plan_hold()  # (plan_hold: the episode's first step plans)
         core.estimator_reset()
+        core.force_observer_reset()
         T = self.env.default_params.max_steps_in_episode
         dstate = as_device_state(env_state, core.device)
         packed_d, a_means_d, keys_d = self._nominal_device(env_state, env_params, key)

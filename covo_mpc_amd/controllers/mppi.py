@@ -58,6 +58,7 @@ class MPPIController(BaseController):
         """Episode start: with a plan hold the schedule restarts -- the first step of the episode plans."""
         self.core.restart_plan_hold()
         self.core.estimator_reset()
+        self.core.force_observer_reset()
         return super().reset(env_state, env_params, control_params, key)
 
     def _check_gamma_sigma(self, control_params):

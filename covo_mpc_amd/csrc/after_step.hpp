@@ -186,6 +186,7 @@ struct AfterState {
     ArgBlockCache hold, hold_primitive, latch;  // plan_hold.hip: a batched hold step's blocks, covo_plan_hold's, a batched plan step's latch
     ArgBlockCache ilqr;                         // ilqr.hip: a batched iLQR step's tally blocks
     ArgBlockCache est, est_primitive;           // state_estimator.hip: an episode driver's batched launch, covo_estimate's
+    ArgBlockCache obs, obs_primitive;           // force_observer.hip: an episode driver's batched launch, covo_observe_force's
     float *nominal = nullptr;  // [COVO_MAX_ENVS][128] the update arbiter's nominals of the env-batched fused step
 };
 static inline AfterState *after_state(covo_ctx *h)

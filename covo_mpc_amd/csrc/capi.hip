@@ -1071,6 +1071,8 @@ int covo_set_step_estimator(covo_handle_t h, const double *obs_std, const double
         h->est_log_stride = 0;
         return 0;
     }
+    REQUIRE(!covo_force_observer_on(h), "covo_set_step_estimator: a force observer is attached to this handle "
+            "(covo_set_step_force_observer): two filters must not write one row");
     REQUIRE(obs_std && proc_std, "covo_set_step_estimator: obs_std and proc_std must be given");
     if (int rc = check_estimator_buffers("covo_set_step_estimator", xhat, P, meta, rows, n_inst)) return rc;
     EstDesc probe;  // (the values are checked on a default model: the derive marker needs the instance's own at the launch)
@@ -1142,6 +1144,110 @@ static int check_episode_estimator(const covo_ctx *h, int n_inst, bool sharded, 
     REQUIRE(h->est_log == nullptr || (first_row >= 0 && first_row + n_steps <= h->est_log_stride),
             "%s: episode estimator log rows [%d, %d) outside [0, %d) (covo_set_episode_estimator_log)", what, first_row, first_row + n_steps,
             h->est_log_stride);
+    return 0;
+}
+
+// ---- the force observer (force_observer.hip).  Like the state estimator's, its launch is eager and follows the env step
+// of an episode driver: no captured step graph knows about it, nothing here bumps the epoch
+static int check_observer_buffers(const char *what, const double *xi, const double *P, const int32_t *meta, const float *rows, int n_inst)
+{
+    REQUIRE(xi && P && meta && rows, "%s: xi, P, meta and rows must all be given", what);
+    REQUIRE(n_inst > 0 && n_inst <= COVO_MAX_ENVS, "%s: n_inst=%d outside (0, %d]", what, n_inst, COVO_MAX_ENVS);
+    REQUIRE((((uintptr_t)xi | (uintptr_t)P) & 7) == 0 && (((uintptr_t)meta | (uintptr_t)rows) & 3) == 0,
+            "%s: xi and P must be 8-byte aligned, meta and rows 4-byte", what);
+    return 0;
+}
+
+int covo_set_step_force_observer(covo_handle_t h, const double *obs_std, const double *proc_std, double force_walk_std,
+                                 double force_init_std, double *xi, double *P, int32_t *meta, float *rows, int32_t n_inst)
+{
+    REQUIRE(h, "covo_set_step_force_observer: null handle");
+    if (rows == nullptr) {  // off, the log with it
+        h->obs_rows = nullptr;
+        h->obs_xi = h->obs_P = nullptr;
+        h->obs_meta = nullptr;
+        h->obs_n = 0;
+        h->obs_log = nullptr;
+        h->obs_log_stride = 0;
+        return 0;
+    }
+    REQUIRE(!covo_estimator_on(h), "covo_set_step_force_observer: a state estimator is attached to this handle (covo_set_step_estimator): "
+            "two filters must not write one row");
+    REQUIRE(obs_std && proc_std, "covo_set_step_force_observer: obs_std and proc_std must be given");
+    if (int rc = check_observer_buffers("covo_set_step_force_observer", xi, P, meta, rows, n_inst)) return rc;
+    ObsDesc probe;
+    covo_env_params unit{};
+    unit.dt = unit.m = 1.0f;
+    if (int rc = observer_fill_model(probe, unit, obs_std, proc_std, force_walk_std, force_init_std, "covo_set_step_force_observer")) return rc;
+    for (int g = 0; g < 4; ++g) {
+        h->obs_obs_std[g] = obs_std[g];
+        h->obs_proc_std[g] = proc_std[g];
+    }
+    h->obs_walk_std = force_walk_std;
+    h->obs_init_std = force_init_std;
+    h->obs_xi = xi;
+    h->obs_P = P;
+    h->obs_meta = meta;
+    h->obs_rows = rows;
+    h->obs_n = n_inst;
+    h->obs_fresh = 1;
+    return 0;
+}
+
+int covo_force_observer_reset(covo_handle_t h)
+{
+    REQUIRE(h, "covo_force_observer_reset: null handle");
+    h->obs_fresh = 1;
+    return 0;
+}
+
+int covo_set_episode_force_observer_log(covo_handle_t h, float *log, int32_t stride)
+{
+    REQUIRE(h, "covo_set_episode_force_observer_log: null handle");
+    REQUIRE(log == nullptr || stride > 0, "covo_set_episode_force_observer_log: stride=%d", stride);
+    REQUIRE(log == nullptr || covo_force_observer_on(h),
+            "covo_set_episode_force_observer_log: no force observer attached: call covo_set_step_force_observer first");
+    h->obs_log = log;
+    h->obs_log_stride = log ? stride : 0;
+    return 0;
+}
+
+int covo_observe_force(covo_handle_t h, float *state_rows, const float *u, int32_t u_stride, const covo_env_params *params,
+                       const double *obs_std, const double *proc_std, double force_walk_std, double force_init_std, double *xi, double *P,
+                       int32_t *meta, float *rows, int32_t n_inst, int32_t reset, void *hip_stream)
+{
+    REQUIRE(h, "covo_observe_force: null handle");
+    CHECK_DEVICE(h, "covo_observe_force");
+    REQUIRE(state_rows && u && params && obs_std && proc_std && u_stride >= COVO_DU, "covo_observe_force: bad argument");
+    if (int rc = check_observer_buffers("covo_observe_force", xi, P, meta, rows, n_inst)) return rc;
+    static thread_local ObsDesc d[COVO_MAX_ENVS];
+    std::memset(d, 0, (size_t)n_inst * sizeof(ObsDesc));
+    for (int e = 0; e < n_inst; ++e) {
+        CHECK_MODEL(&params[e], "covo_observe_force");
+        if (int rc = observer_fill_model(d[e], params[e], obs_std, proc_std, force_walk_std, force_init_std, "covo_observe_force")) return rc;
+        d[e].state = state_rows + (size_t)e * COVO_STATE_FLOATS;
+        d[e].u = u + (size_t)e * u_stride;
+        d[e].xi = xi + (size_t)e * COVO_OBS_STATE_DOUBLES;
+        d[e].P = P + (size_t)e * 16 * 16;
+        d[e].meta = meta + (size_t)e * COVO_OBS_META_INTS;
+        d[e].row_out = rows + (size_t)e * COVO_OBS_FLOATS;
+    }
+    const int fresh = reset < 0 ? h->obs_fresh : (reset != 0);  // (reset < 0: what covo_force_observer_reset left, taken once)
+    if (reset < 0) h->obs_fresh = 0;
+    return launch_force_observer(h, d, n_inst, n_inst > 1, true, fresh, -1, (hipStream_t)hip_stream);
+}
+
+// what an episode driver asks of the force observer before its first launch (next to check_episode_estimator)
+static int check_episode_force_observer(const covo_ctx *h, int n_inst, bool sharded, int first_row, int n_steps, const char *what)
+{
+    if (!covo_force_observer_on(h)) return 0;
+    REQUIRE(!covo_estimator_on(h), "%s: a state estimator and a force observer are both attached: two filters must not write one row", what);
+    REQUIRE(!sharded, "%s: the force observer (covo_set_step_force_observer) does not run on sample-sharded steps", what);
+    REQUIRE(n_inst <= h->obs_n, "%s: %d instances, the force observer's rows (covo_set_step_force_observer) have n_inst=%d", what, n_inst,
+            h->obs_n);
+    REQUIRE(h->obs_log == nullptr || (first_row >= 0 && first_row + n_steps <= h->obs_log_stride),
+            "%s: episode force observer log rows [%d, %d) outside [0, %d) (covo_set_episode_force_observer_log)", what, first_row,
+            first_row + n_steps, h->obs_log_stride);
     return 0;
 }
 
@@ -1616,6 +1722,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
     int rc = check_single_step(h, params, args, "covo_run_episode");
     if (rc || (rc = check_episode_logs(h, 0, n_steps, "covo_run_episode"))) return rc;
     if ((rc = check_episode_estimator(h, 1, args->partial_out != nullptr, 0, n_steps, "covo_run_episode"))) return rc;
+    if ((rc = check_episode_force_observer(h, 1, args->partial_out != nullptr, 0, n_steps, "covo_run_episode"))) return rc;
     hipStream_t s = (hipStream_t)stream;
     uint32_t key[2] = {rng[0], rng[1]};
     for (int t = 0; t < n_steps; ++t) {
@@ -1655,6 +1762,7 @@ int covo_run_episode(covo_handle_t h, const covo_env_params *params, const covo_
                              *params, args->a_mean, rng_step, noisy_on, obs_noise_scale, log, t, s);
         if (rc) return rc;
         if ((rc = covo_estimator_step(h, const_cast<float *>(args->state), args->a_mean, params, 1, false, t, s))) return rc;
+        if ((rc = covo_force_observer_step(h, const_cast<float *>(args->state), args->a_mean, params, 1, false, t, s))) return rc;
         host_philox_split(nrng, 0u, key);
     }
     rng[0] = key[0];
@@ -1697,6 +1805,7 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
             "%s: log rows [%d, %d) outside [0, %d)", what, log_index, log_index + n_steps, log_stride);
     if ((rc = check_episode_logs(h, log_index, n_steps, what))) return rc;
     if ((rc = check_episode_estimator(h, E, false, log_index, n_steps, what))) return rc;
+    if ((rc = check_episode_force_observer(h, E, false, log_index, n_steps, what))) return rc;
     hipStream_t s = (hipStream_t)stream;
     const void *inst = nullptr;
     if ((rc = batch_env_inst(h, params, E, s, &inst))) return rc;
@@ -1719,6 +1828,7 @@ static int run_episode_batched(covo_handle_t h, const covo_batch_args *args, con
                                           log_stride, log_index + t, s)))
             return rc;
         if ((rc = covo_estimator_step(h, const_cast<float *>(args->states), args->a_mean, params, E, true, log_index + t, s))) return rc;
+        if ((rc = covo_force_observer_step(h, const_cast<float *>(args->states), args->a_mean, params, E, true, log_index + t, s))) return rc;
         std::memcpy(rngs, next, (size_t)2 * E * sizeof(uint32_t));
     }
     return 0;

@@ -182,6 +182,16 @@ struct covo_ctx {
     int est_fresh;            // 1: the next launch of a driver treats every instance as one without a valid state
     float *est_log;           // caller's [n_inst][est_log_stride][COVO_EST_LOG_FLOATS] (covo_set_episode_estimator_log): the launch writes
     int est_log_stride;       // its rows itself; not one of eplog's kinds -- an episode driver checks its extent next to theirs
+    // the force observer (covo_set_step_force_observer; force_observer.hip); obs_rows null: not attached.  Never attached together
+    // with the state estimator: two filters must not write one row
+    float *obs_rows;          // caller's [obs_n][COVO_OBS_FLOATS]: instance e's side row of every launch
+    double *obs_xi, *obs_P;   // caller's [obs_n][COVO_OBS_STATE_DOUBLES], [obs_n][16][16]: the filter's state lives there between steps
+    int *obs_meta;            // caller's [obs_n][COVO_OBS_META_INTS]
+    int obs_n;
+    double obs_obs_std[4], obs_proc_std[4], obs_walk_std, obs_init_std;
+    int obs_fresh;            // 1: the next launch of a driver treats every instance as one without a valid state
+    float *obs_log;           // caller's [n_inst][obs_log_stride][COVO_OBS_LOG_FLOATS] (covo_set_episode_force_observer_log): like est_log,
+    int obs_log_stride;       // written by the launch itself and checked next to it
     // the episode logs, by kind (covo_eplog_kinds below says what each holds and who fills it); log null: off
     struct {
         float *log;  // caller's [n_inst][stride][one row of the kind]: every step of an episode driver leaves row `index` of every instance
@@ -1015,6 +1025,29 @@ static inline bool covo_estimator_on(const covo_ctx *h) { return h->est_rows != 
 // u = the first action of each instance's mean (no-op with nothing attached)
 int covo_estimator_step(covo_ctx *h, float *states, const float *a_mean, const covo_env_params *params, int n_inst, bool batched,
                         int log_index, hipStream_t s);
+// force_observer.hip: one instance of the force observer's launch, the kernel's argument block as it stands (zeroed before it is
+// filled: compared bytewise); row_out and log are null or not for every instance of a launch alike
+struct ObsDesc {
+    float *state;             // [32] the measured row: its floats 0 .. 15 become the estimate (x, then the force), in place
+    const float *u;           // [4] the action applied during the step that led to this row
+    double *xi;               // [COVO_OBS_STATE_DOUBLES]: x [13], then the force estimate [3]
+    double *P;                // [16][16]
+    int *meta;                // [COVO_OBS_META_INTS] = {valid, the time word of the row last seen}
+    float *row_out;           // [COVO_OBS_FLOATS] or null
+    float *log;               // this instance's rows of the episode observer log [stride][COVO_OBS_LOG_FLOATS], or null
+    qm::Consts<double> c;     // the instance's model
+    double R[4], Q[4];        // the variances of the four kinematic coordinate groups: measurement, process
+    double qf, pf;            // force_walk_std^2, force_init_std^2
+};
+int launch_force_observer(covo_ctx *h, const ObsDesc *d, int n_inst, bool batched, bool primitive, int fresh, int log_index, hipStream_t s);
+// d's model and variances from the instance's parameters; 0, or COVO_E_BADARG with the error set (what: the entry's name)
+int observer_fill_model(ObsDesc &d, const covo_env_params &p, const double *obs_std, const double *proc_std, double force_walk_std,
+                        double force_init_std, const char *what);
+static inline bool covo_force_observer_on(const covo_ctx *h) { return h->obs_rows != nullptr; }
+// the observer's launch of an episode driver's step, right behind the env step, where covo_estimator_step stands (no-op with
+// nothing attached)
+int covo_force_observer_step(covo_ctx *h, float *states, const float *a_mean, const covo_env_params *params, int n_inst, bool batched,
+                             int log_index, hipStream_t s);
 // ilqr.hip: what frames the iterations of an iLQR step (COVO_MODE_ILQR).  IlqrTallyDesc: one instance of the tally launch behind an
 // iteration's line search, the kernel's argument block as it stands (all pointers; what is null is null for every instance)
 struct IlqrTallyDesc {

@@ -202,7 +202,7 @@ void after_state_destroy(covo_ctx *h)
 {
     AfterState *as = reinterpret_cast<AfterState *>(h->after);
     if (!as) return;
-    for (ArgBlockCache *c : {&as->arbiter, &as->plan, &as->fan, &as->refine, &as->feedback, &as->hold, &as->hold_primitive, &as->latch, &as->ilqr, &as->est, &as->est_primitive}) (void)hipFree(c->dev);
+    for (ArgBlockCache *c : {&as->arbiter, &as->plan, &as->fan, &as->refine, &as->feedback, &as->hold, &as->hold_primitive, &as->latch, &as->ilqr, &as->est, &as->est_primitive, &as->obs, &as->obs_primitive}) (void)hipFree(c->dev);
     (void)hipFree(as->nominal);
     delete as;
     h->after = nullptr;

@@ -400,6 +400,26 @@ class _EpisodeLogs:
                 "innov_pos": rows[..., 28], "moved_pos": rows[..., 29], "trace_pos": rows[..., 30], "trace_vel": rows[..., 31],
                 "pivot_min": rows[..., 32], "time": as_int(33)}
 
+    # the observer log of an attached controllers.ForceObserver -- [.., T + 1, 40], None until a controller with one attached runs the
+    # episode --: like estlog, written by the filter's launch itself (SamplingCore.attach_force_observer_log)
+    obslog = None
+
+    def alloc_force_observer_log(self):
+        import torch
+        self.obslog = torch.zeros(tuple(self.log.shape[:-1]) + (self._lib.COVO_OBS_LOG_FLOATS,), dtype=torch.float32, device=self.device)
+
+    def read_force(self):
+        """-> {measured [n, 13], written [n, 16], force_true [n, 3], force_est [n, 3], rows [n, 8]}: per enqueued step what the env step
+        measured, the 16 floats the row held behind the observer's launch, the force the env step left in the row (the one the NEXT
+        plant step integrates), the observer's estimate of it (written[:, 13:16]) and its side row (include/covo_hip.h:
+        covo_set_step_force_observer; words 0 and 7 are int32 bits), under a controller with a controllers.ForceObserver attached."""
+        if self.obslog is None:
+            raise RuntimeError("no observer log: run_episode under a controller with a ForceObserver attached (ForceObserver.attach)")
+        self.read_log()  # synchronises and checks the device status
+        rows = self.obslog.narrow(self.STEP_AXIS, 0, self.n_steps).cpu().numpy()
+        return {"measured": rows[..., 0:13], "written": rows[..., 16:32], "force_true": rows[..., 13:16], "force_est": rows[..., 29:32],
+                "rows": rows[..., 32:40]}
+
     def log_segment(self, name):
         """What the episode driver binds of log `name` for the next segment: one instance -- the rows from n_steps on (covo_run_episode
         counts its rows from 0); E instances -- the whole buffer (the batched drivers take the first row of a segment as log_index)."""

@@ -1153,7 +1153,8 @@ int covo_cma_path(covo_handle_t h, const float *L_prev, const float *aux, int32_
  *   first_row + t of every instance itself: the 13 measured floats, the 13 written floats, the row.  NULL: off.
  * Refused with COVO_E_BADARG before any launch: an obs_std entry that is not positive and finite; a proc_std entry that is negative
  *   (other than the marker) or not finite; force_std negative or not finite while the marker is set; more instances than rows;
- *   a sample-sharded episode step; a log with fewer rows than the episode segment needs. */
+ *   a sample-sharded episode step; a log with fewer rows than the episode segment needs; covo_set_step_estimator while a force
+ *   observer (COVO_HAS_FORCE_OBSERVER, below) is attached to the handle: two filters must not write one row. */
 #define COVO_HAS_STATE_ESTIMATOR 1
 #define COVO_EST_FLOATS 8
 #define COVO_EST_STATE_DOUBLES 16
@@ -1166,6 +1167,57 @@ int covo_estimate(covo_handle_t h, float *state_rows, const float *u, int32_t u_
                   const double *obs_std, const double *proc_std, double force_std, double *xhat, double *P, int32_t *meta, float *rows,
                   int32_t n_inst, int32_t reset, void *hip_stream);
 int covo_set_episode_estimator_log(covo_handle_t h, float *log, int32_t stride);
+/* The force observer: a 16-state extended Kalman filter that estimates the disturbance force (additive to ABI 10:
+ * COVO_HAS_FORCE_OBSERVER; csrc/force_observer.hip).  A second, independent filter launch next to the state
+ * estimator's: it treats f_disturb as unknown, estimates it from the kinematic measurements alone and overwrites, IN PLACE, floats
+ * 0 .. 15 of the packed state row the controller is about to read (the 13 kinematic floats and the three force slots).  The row's
+ * force slots are never an input.  No step path and no captured step graph changes; off unless attached.  fp64 throughout.  Per
+ * instance the filter keeps xi = (x [13], f [3]), P [16][16] (symmetric bit for bit), the time word t_prev of the row it last saw and
+ * a valid bit, in the caller's buffers:
+ *   xi = DEVICE double[n_inst][COVO_OBS_STATE_DOUBLES], P = DEVICE double[n_inst][16][16],
+ *   meta = DEVICE int32[n_inst][COVO_OBS_META_INTS] = {valid, t_prev}, rows = DEVICE float[n_inst][COVO_OBS_FLOATS].
+ * R = diag(obs_std[group]^2) over pos, vel, quat, omega; Q = diag(proc_std[group]^2 (13), force_walk_std^2 (3)).  A call with the
+ * measured row z and the applied action u [4]:
+ *   no valid state, or time(z) != t_prev + 1: x = (double)z[0:13], f = 0, P = diag(R, force_init_std^2 I3); row[13:16] = 0, row[0:13]
+ *   is left as measured; otherwise
+ *   x- = model(x, clip(u), f) (the model step of the rollouts in fp64, quaternion normalised on entry and exit), f- = f,
+ *   A16 = d(x-, f-)/d(x, f) at xi, P- = A16 P A16^T + Q;  H = [I13 0], S = P-[0:13, 0:13] + R factored without pivoting, nu = z - x-,
+ *   K = P-[:, 0:13] S^-1 (16 x 13), xi = xi- + K nu, P = (I - K H) P- (I - K H)^T + K R K^T with the lower triangle mirrored;
+ *   row[0:16] = fp32(xi), nothing else of the row changes;  t_prev = time(z).  The quaternion is neither renormalised nor sign-aligned.
+ * Fall-backs, decided on the device, reported in the row's flag word, never an error: 1 -- initialised (no valid state); 2 --
+ *   re-initialised (the time word); 4 -- one of the 13 measured coordinates is not finite: the row is untouched and the filter is
+ *   invalidated; 8 -- a pivot of S is not positive and finite, or xi / P has an entry that is not finite: re-initialised from z,
+ *   row[0:13] untouched, the force slots 0.
+ * rows: {bits(flags), nu^T S^-1 nu, |nu_pos|, |f^|, P00 + P11 + P22, P13,13 + P14,14 + P15,15, smallest pivot of S, bits(time(z))}.
+ * covo_set_step_force_observer: covo_run_episode, covo_run_episode_batched and covo_run_episode_batched_mode enqueue the launch right
+ *   behind their env step, whatever kind of step came before (a hold step included), on args->state[s] with u = the first four floats
+ *   of each instance's a_mean.  rows = NULL detaches (the episode log with it).  obs_std, proc_std: [host] double[4].
+ * covo_force_observer_reset: the next launch of a driver treats every instance as one without a valid state.
+ * covo_observe_force: the launch alone on the caller's buffers: state_rows = DEVICE float[n_inst][32], in place; instance e's u at
+ *   u + e * u_stride floats; params = [host] covo_env_params[n_inst]; reset > 0: every instance counts as one without a valid state;
+ *   reset < 0: they do when covo_force_observer_reset was called on the handle since its last launch (the flag is taken).
+ *   It writes floats 0 .. 15 of each row, xi, P, meta and rows, nothing else, and launches on hip_stream, the caller's stream (a
+ *   hipStream_t as void *, like every other entry's `stream`).
+ * covo_set_episode_force_observer_log: log = DEVICE float[n_inst][stride][COVO_OBS_LOG_FLOATS]; the launch of a driver's step t writes
+ *   row first_row + t of every instance itself: the 16 measured floats (slots 13 .. 15: the TRUE force, as the env step left it), the
+ *   16 floats the row holds behind the launch, the side row.  NULL: off.
+ * Refused with COVO_E_BADARG before any launch: an obs_std entry that is not positive and finite; a proc_std entry, force_walk_std or
+ *   force_init_std that is negative or not finite; more instances than rows; a sample-sharded episode step; a log with fewer rows than
+ *   the episode segment needs; a state estimator attached to the same handle (and covo_set_step_estimator while an observer is
+ *   attached): two filters must not write one row. */
+#define COVO_HAS_FORCE_OBSERVER 1
+#define COVO_OBS_FLOATS 8
+#define COVO_OBS_STATE_DOUBLES 16
+#define COVO_OBS_META_INTS 2
+#define COVO_OBS_LOG_FLOATS 40
+int covo_set_step_force_observer(covo_handle_t h, const double *obs_std, const double *proc_std, double force_walk_std,
+                                 double force_init_std, double *xi, double *P, int32_t *meta,
+                                 float *rows /* DEVICE [n_inst][COVO_OBS_FLOATS]; NULL = off */, int32_t n_inst);
+int covo_force_observer_reset(covo_handle_t h);
+int covo_observe_force(covo_handle_t h, float *state_rows, const float *u, int32_t u_stride, const covo_env_params *params,
+                       const double *obs_std, const double *proc_std, double force_walk_std, double force_init_std, double *xi, double *P,
+                       int32_t *meta, float *rows, int32_t n_inst, int32_t reset, void *hip_stream);
+int covo_set_episode_force_observer_log(covo_handle_t h, float *log, int32_t stride);
 /* Test hook: `count` doubles at `offset_doubles` of the Hessians of the LAST covo_mpc_step_batched on this handle
  * ([n_envs][128][128], the Sigma chain's input), copied to the HOST buffer `out` (asynchronously on `stream`). */
 int covo_debug_batched_hessians(covo_handle_t h, double *out, int64_t offset_doubles, int64_t count, void *stream);

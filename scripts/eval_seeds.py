@@ -39,9 +39,16 @@ name = sys.argv[1]
 # was built (csrc/state_estimator.hip): every control step plans from the filter's estimate of the noisy state; every seed's line also
 # carries the mean distance the estimate moved the measured position and the share of steps that (re-)initialised; compare the errors with
 # the same call without the flag
+# python scripts/eval_seeds.py <controller> [...] --observer [force_walk_std=w] [disturb=periodic] [seeds=k]: a controllers.ForceObserver
+# attached instead (csrc/force_observer.hip): every control step plans from a row whose disturbance force is the observer's estimate, not
+# the plant's own; every seed's line also carries the RMS error of that estimate over the RMS of the true force and the share of steps
+# that (re-)initialised; compare the errors with the same call without the flag.  disturb= picks the plant's disturbance model (default
+# gaussian), seeds= the number of seeds (default 12), with or without a filter
 rest = sys.argv[2:]
 with_estimator = "--estimator" in rest
-rest = [r for r in rest if r != "--estimator"]
+with_observer = "--observer" in rest
+assert not (with_estimator and with_observer), "--estimator and --observer: two filters must not write one row"
+rest = [r for r in rest if r not in ("--estimator", "--observer")]
 # the boolean step switches as flags: --refine, --riccati, --riccati-feedback, --riccati-box
 flags = {f"--{s.replace('_', '-')}": s for s, default in STEP_SWITCH_DEFAULTS.items() if isinstance(default, bool)}
 switches = {s: flag in rest for flag, s in flags.items()}
@@ -50,19 +57,22 @@ for flag, key in (("--sigma-period", "sigma_period"), ("--sigma-adapt", "sigma_a
     while flag in rest:
         i = rest.index(flag)
         rest[i:i + 2] = [f"{key}={rest[i + 1]}"]
-FLOATS = ("force_std", "sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp", "gamma", "damping", "s_min", "s_max")
+FLOATS = ("force_std", "force_walk_std", "sigma_adapt", "ess_min", "beta_pass", "beta_stage", "temp", "gamma", "damping", "s_min", "s_max")
 CMA_KEYS = ("gamma", "damping", "s_min", "s_max", "step_size")
-opts = {k: (None if v.lower() == "none" else v if k == "node_interp" else float(v) if k in FLOATS else int(v))
+opts = {k: (None if v.lower() == "none" else v if k in ("node_interp", "disturb") else float(v) if k in FLOATS else int(v))
         for k, v in (arg.split("=") for arg in rest)}
 switches["plan_hold"] = opts.pop("plan_hold", 1)
 force_std = opts.pop("force_std", None)
 assert force_std is None or with_estimator, "force_std= belongs to --estimator"
+force_walk_std = opts.pop("force_walk_std", None)
+assert force_walk_std is None or with_observer, "force_walk_std= belongs to --observer"
+disturb, n_seeds = opts.pop("disturb", "gaussian"), opts.pop("seeds", 12)
 assert set(opts) <= ({"elite", "sigma_period", "sigma_adapt", "ess_min", "iters"} |
                      ({"beta_pass", "beta_stage", "temp", "nodes", "node_interp"} if name == "dial" else set()) |
                      (set(CMA_KEYS) if name == "cma" else set())), opts
 cma_kw = {k: (bool(opts.pop(k)) if k == "step_size" else opts.pop(k)) for k in CMA_KEYS if k in opts}
 env = Q.Quad3D(task="tracking_zigzag", obs_type="quad", lower_controller="base", enable_randomizer=False,
-               disturb_type="gaussian", disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
+               disturb_type=disturb, disable_rollover_terminate=True, generate_noisy_state=True, device="cuda")
 ctrl, cp = Q.get_controller(env, name, "N8192_H32_lam0.01", **switches, **opts)
 if cma_kw:  # (get_controller's signature carries none of them: the controller is built again with them)
     from covo_mpc_amd import controllers
@@ -71,6 +81,9 @@ if cma_kw:  # (get_controller's signature carries none of them: the controller i
 if with_estimator:
     from covo_mpc_amd.controllers import StateEstimator
     StateEstimator(env, force_std=force_std).attach(ctrl)
+if with_observer:
+    from covo_mpc_amd.controllers import ForceObserver
+    ForceObserver(env, force_walk_std=force_walk_std).attach(ctrl)
 np.set_printoptions(precision=3, linewidth=200)
 allerr = []
 core = getattr(ctrl, "core", None)
@@ -125,13 +138,18 @@ def rows_of(ep):
         e = ep.read_estimate()
         rows["est_init"] = rows.get("est_init", 0) + int((e["flags"] != 0).sum())
         rows["est_moved"] = rows.get("est_moved", 0.0) + float(e["moved_pos"].sum())
+    if ep.obslog is not None:
+        e = ep.read_force()
+        rows["obs_init"] = rows.get("obs_init", 0) + int((np.ascontiguousarray(e["rows"][:, 0]).view(np.int32) != 0).sum())
+        rows["obs_err2"] = rows.get("obs_err2", 0.0) + float(((e["force_est"] - e["force_true"]).astype(np.float64) ** 2).sum())
+        rows["obs_true2"] = rows.get("obs_true2", 0.0) + float((e["force_true"].astype(np.float64) ** 2).sum())
     if name == "cma":
         row = core.cma_rows[0].cpu().numpy()
         rows["cma_s"], rows["cma_flags"] = float(row[0]), float(row[7])
     rows["steps"] = rows.get("steps", 0) + ep.n_steps
 
 
-for seed in range(1, 13):
+for seed in range(1, 1 + n_seeds):
     rows = {}
     errs = Q.eval_env_device(env, controller=ctrl, total_steps=300*4*10, seed=seed, verbose=False, on_episode=rows_of if core else None)
     allerr.append(errs)
@@ -142,6 +160,8 @@ for seed in range(1, 13):
         if switches["riccati_box"]:
             rows["boxed"] = int(acc[3])
     n = max(rows.get("steps", 0), 1)
+    if "obs_err2" in rows:
+        rows["obs_ratio"] = (rows["obs_err2"] / max(rows["obs_true2"], 1e-300)) ** 0.5
     npl = max(rows.get("plans", 0), 1)
     nh = max(rows.get("held", 0), 1)
     extra = "".join(text % (rows[k] / d) for k, text, d in (("floor", "  lam_eff>lam: %.3f", n), ("fallback", "  adapt fallbacks: %d", 1),
@@ -154,6 +174,8 @@ for seed in range(1, 13):
                                                            ("clipped", "  hold steps with a clipped component: %.3f", nh),
                                                            ("est_moved", "  estimate moved the position by: %.4f", n),
                                                            ("est_init", "  steps that (re-)initialised the filter: %.4f", n),
+                                                           ("obs_ratio", "  rms force error / rms force: %.3f", 1),
+                                                           ("obs_init", "  steps that (re-)initialised the observer: %.4f", n),
                                                            ("cma_s", "  last step size: %.3f", 1), ("cma_flags", "  last flags: %d", 1)) if k in rows)
     print(name, "seed", seed, "mean %.3f med %.3f max %.3f  n>0.1: %d" % (errs.mean(), np.median(errs), errs.max(), (errs > 0.1).sum()) + extra,
           flush=True)
